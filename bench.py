@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- JPEG -> RGB throughput of the MI355X decode path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3|cfg2|cfg2rst|cfg5] [--images M]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3|cfg2|cfg2rst|cfg5] [--images M] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times K steps and prints the result line (`value`, `ms_per_step` = milliseconds of one timed
+step); `--dump-outputs DIR` first writes what the last timed step decoded (see dump_outputs).  Everything else below --
+`one_batch_in_flight`, `roofline`, `kernels_ms`, `variants`, `cxx_split_decode`, `pcie_inclusive`, `cli_end_to_end`,
+`cpu_baseline`, `--verify` -- is measured only with `--full`.
 
 One process per GPU (the driver launches N ranks with torch.distributed.run); every rank decodes its
 OWN batch (weak scaling, no data-path collective: images are independent).  A step = one pass of the
@@ -45,6 +50,28 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8 TB/s (spec)
+DUMP_SAMPLE = 8 << 20          # --dump-outputs: output bytes kept as float32 (32 MB) when the pictures hold more
+DUMP_WHOLE_FIRST = 4 << 20     # --dump-outputs: picture 0 is written whole up to this many bytes (16 MB as float32)
+
+
+def dump_outputs(d, outs, status):
+    """Write what the last timed step computed -- the per-picture outputs (BMP file images or RGB8) and status words a caller
+    of the batch receives -- as .npy files under `d`, 48 MB at most: status word, output size and byte sum of every picture,
+    picture 0 whole (when small enough) and the bytes at a fixed seeded sample of positions over all pictures laid end to end
+    (all of them when they fit).  The inputs are seeded, so two builds can be compared file by file."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    flat = np.concatenate([np.asarray(o).reshape(-1) for o in outs]) if outs else np.zeros(0, np.uint8)
+    if flat.size > DUMP_SAMPLE:
+        flat = flat[np.sort(np.random.default_rng(0).integers(0, flat.size, DUMP_SAMPLE))]
+    files = {"status": np.asarray(status, np.float64),
+             "output_bytes": np.array([np.asarray(o).size for o in outs], np.float64),
+             "output_byte_sum": np.array([np.asarray(o).sum(dtype=np.uint64) for o in outs], np.float64),
+             "output_sample": flat.astype(np.float32)}
+    if outs and np.asarray(outs[0]).size <= DUMP_WHOLE_FIRST:
+        files["picture0"] = np.asarray(outs[0]).astype(np.float32)
+    for name, a in files.items():
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def bundled_rgb(device):
@@ -62,6 +89,10 @@ def bundled_rgb(device):
 
 def make_workload(name, n_images, seed, tile, device=0):
     import synth
+    if not os.access(os.path.dirname(synth.SO), os.W_OK) and (
+            not os.path.exists(synth.SO) or os.path.getmtime(synth.SO) < os.path.getmtime(synth.SRC)):
+        # a tree this process may not write to, whose build did not leave the generator's library: compile it elsewhere
+        synth.SO = os.path.join(tempfile.mkdtemp(prefix="pjd_synth_"), "libjpegsynth.so")
     if name == "cfg3":
         jp = synth.cfg3_imagenet_like(n_images, seed=seed, detail=synth.DENSE_DETAIL, optimize=True, quality_shift=True,
                                       extra=[bundled_rgb(device)])
@@ -252,12 +283,19 @@ def main():
     ap.add_argument("--no-variants", action="store_true", help="skip the extra measurement on the lighter cfg3lite set")
     ap.add_argument("--out-format", default="bmp", choices=["bmp", "rgb8"],
                     help="what the device writes per picture: the BMP file image the reference's writer would emit (default), or tight RGB8")
-    ap.add_argument("--verify", action="store_true", help="check a few pictures against the oracle after the run")
+    ap.add_argument("--verify", action="store_true", help="with --full: check a few pictures against the oracle after the run")
     ap.add_argument("--no-cli", action="store_true", help="skip cli_end_to_end (bin/decoder --pipeline over the workload as files on tmpfs)")
     ap.add_argument("--e2e-batches", type=int, default=32,
                     help="also run the pipelined batcher (JPEG bytes in host memory -> BMP bytes in pinned host memory, "
                          "PCIe both ways) over this many batches of the workload; 0 = skip.  Reported as pcie_inclusive, never as value")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the serialised run (one_batch_in_flight), per-kernel "
+                         "times and roofline, the variants, the C++ split decode, pcie_inclusive, cli_end_to_end and cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one decoded as .npy files under DIR (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -310,9 +348,9 @@ def main():
         for b in group[:min(n, g)]:
             b.sync()
 
-    def measure(workload, steps, warmup, full):
-        """Generate `workload`, make `nfl` resident batches, time `steps` steps.  full: also the serialised run and the
-        per-kernel HIP-event timings."""
+    def measure(workload, steps, warmup, primary):
+        """Generate `workload`, make `nfl` resident batches, time `steps` steps.  With --full also the serialised run, and for
+        the primary measurement the per-kernel HIP-event timings and --verify.  primary: --dump-outputs applies to it too."""
         split = workload == "cfg5split" and world > 1
         t_gen = time.perf_counter()
         if split and rank != 0:
@@ -380,10 +418,13 @@ def main():
         if split:
             r["host_ms"]["distribute"] = round(t_dist * 1e3, 1)
             r["split_info"] = split_info
+        if primary and args.dump_outputs and rank == 0:
+            # the last timed step decoded batch (steps - 1) % nfl; its pictures and status words, as the caller downloads them
+            r["outputs"] = batches[(steps - 1) % len(batches)].download()
         # the same K steps strictly one after the other (reported beside `value`, never instead of it)
         r["info"] = batch.info()
         alone = batch                 # the batch that is decoded ALONE: planned for latency
-        if nfl > 1:
+        if args.full and nfl > 1:
             alone_mode = mode_of.get(args.plan_mode, pjd_amd.PLAN_LATENCY)
             if alone_mode != main_mode:
                 ctxs.append(pjd_amd.Context(local_rank, plan_mode=alone_mode))
@@ -406,7 +447,7 @@ def main():
             dist.all_reduce(tt, op=dist.ReduceOp.SUM)
             tot = [float(x) for x in tt.tolist()]
         r["tot"] = tot
-        if full:
+        if primary and args.full:
             # per-kernel durations, HIP events on the library's own stream (ungraphed launches of the same work)
             ktimes, ktotal, reps = {}, 0.0, 5
             for _ in range(reps):
@@ -455,8 +496,10 @@ def main():
         return o
 
     R = measure(args.workload, args.steps, args.warmup, True)
+    if "outputs" in R:
+        dump_outputs(args.dump_outputs, *R.pop("outputs"))
     variants = {}
-    if args.workload == "cfg3" and not args.no_variants:
+    if args.full and args.workload == "cfg3" and not args.no_variants:
         # the lighter round-1 set, same run (Annex-K tables shared by every picture, 0.32 B/px)
         V = measure("cfg3lite", max(5, args.steps // 2), args.warmup, False)
         variants["cfg3lite"] = dict(rates(V), workload=V["label"])
@@ -467,29 +510,13 @@ def main():
             variants["cfg5split"] = dict(rates(S), workload=S["label"], scaling="strong", split=S.get("split_info"), host_ms=S["host_ms"])
 
     if rank == 0:
-        info, ktimes = R["info"], R["ktimes"]
+        info = R["info"]
         main_rates = rates(R)
         pixels = info["pixels"]
-        dom = max(ktimes, key=ktimes.get)
-        alg_bytes = info["ecs_bytes"] + info["out_bytes"]            # ECS read once + picture written once
-        achieved = alg_bytes / (ktimes[dom] * 1e-3) / 1e9
-        # HBM traffic of the dominant kernel per launch and the VALU issue fraction, from the committed rocprofv3 PMC passes
-        # (profiles/<tag>_counters.json, written by tools/make_profile.py); only valid for the workload they were collected on
-        traffic, valu_issue_frac, prof_src = None, None, None
-        try:
-            tj = json.load(open(os.path.join(ROOT, "profiles", "r04_cfg3_counters.json")))
-            if args.workload == tj.get("workload_key") and args.images == 1024:
-                prof_src = tj.get("source")
-                for k, v in tj["per_kernel"].items():
-                    if dom in k:
-                        traffic = v.get("traffic_bytes")
-                        valu_issue_frac = v.get("valu_issue_frac")
-        except Exception:
-            pass
         line = {
             "metric": "MPixels/sec JPEG->RGB (bit-exact BMP)", "value": main_rates["value"], "unit": "MPix/s",
             "value_mode": (f"{nfl} batches in flight (each resident batch on its own HIP stream; every step drained and checked before its batch is "
-                           "decoded again; planned with PJD_PLAN_THROUGHPUT); one_batch_in_flight = the same steps strictly serialised on ONE "
+                           "decoded again; planned with PJD_PLAN_THROUGHPUT); one_batch_in_flight (--full) = the same steps strictly serialised on ONE "
                            "batch planned with PJD_PLAN_LATENCY (the library's default); --plan-mode forces one plan for both") if nfl > 1 else "one batch at a time",
             "n_gpus": world, "rccl_ranks": comm["ranks"], "collective_backend": comm["backend"], "steps": args.steps, "warmup": max(args.warmup, nfl),
             "ms_per_step": main_rates["ms_per_step"], "higher_is_better": True, "scaling": "strong" if R.get("split") else "weak",
@@ -511,15 +538,33 @@ def main():
                                          "re-sync round lasts as long as its slowest lane; walks = rounds a wave finished cooperatively "
                                          "(few lanes left), walk_lanes = lanes re-decoded that way (counted in sync_lane_passes too)")},
             "ecs_GBps": main_rates["ecs_GBps"], "huffman_symbols_per_s": main_rates["huffman_symbols_per_s"],
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "valu_issue_frac": valu_issue_frac,
-                         "counters_from": prof_src,
-                         "algorithmic_bytes_per_launch": alg_bytes, "kernel_ms": round(ktimes[dom], 4),
-                         "plan_mode": "throughput" if R.get("info_alone", info)["plan_mode"] else "latency"},
-            "kernels_ms": {k: round(v, 4) for k, v in ktimes.items()},
-            "kernel_pipeline_ms": round(R["ktotal"], 4),
             "host_ms": R["host_ms"],
         }
+        if args.full:
+            ktimes = R["ktimes"]
+            dom = max(ktimes, key=ktimes.get)
+            alg_bytes = info["ecs_bytes"] + info["out_bytes"]            # ECS read once + picture written once
+            achieved = alg_bytes / (ktimes[dom] * 1e-3) / 1e9
+            # HBM traffic of the dominant kernel per launch and the VALU issue fraction, from the committed rocprofv3 PMC passes
+            # (profiles/<tag>_counters.json, written by tools/make_profile.py); only valid for the workload they were collected on
+            traffic, valu_issue_frac, prof_src = None, None, None
+            try:
+                tj = json.load(open(os.path.join(ROOT, "profiles", "r04_cfg3_counters.json")))
+                if args.workload == tj.get("workload_key") and args.images == 1024:
+                    prof_src = tj.get("source")
+                    for k, v in tj["per_kernel"].items():
+                        if dom in k:
+                            traffic = v.get("traffic_bytes")
+                            valu_issue_frac = v.get("valu_issue_frac")
+            except Exception:
+                pass
+            line["roofline"] = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "valu_issue_frac": valu_issue_frac,
+                                "counters_from": prof_src,
+                                "algorithmic_bytes_per_launch": alg_bytes, "kernel_ms": round(ktimes[dom], 4),
+                                "plan_mode": "throughput" if R.get("info_alone", info)["plan_mode"] else "latency"}
+            line["kernels_ms"] = {k: round(v, 4) for k, v in ktimes.items()}
+            line["kernel_pipeline_ms"] = round(R["ktotal"], 4)
         if "one_batch_in_flight" in main_rates:
             serial_ms = main_rates["one_batch_in_flight"]["ms_per_step"]
             line["one_batch_in_flight"] = dict(main_rates["one_batch_in_flight"],
@@ -533,7 +578,7 @@ def main():
             line["variants"] = variants
         if R.get("split_info"):
             line["split"] = R["split_info"]
-        if world > 1 and (args.workload == "cfg5split" or (args.workload == "cfg3" and not args.no_variants)):
+        if args.full and world > 1 and (args.workload == "cfg5split" or (args.workload == "cfg3" and not args.no_variants)):
             # the C++ route to the same thing (pjd_split_decode: host threads + ONE ncclBroadcast), over the node's devices, in a child
             rehearsal = "PJD_BENCH_DEVICE" in os.environ          # one-GPU rehearsal: every "rank" is that device (RCCL refuses duplicates: host copies)
             if rehearsal:
@@ -542,7 +587,7 @@ def main():
         if R.get("verify") is not None:
             line["verified_against_oracle"] = bool(R["verify"])
         jpegs = R["jpegs"]
-        if world == 1 and args.e2e_batches > 0:
+        if args.full and world == 1 and args.e2e_batches > 0:
             # PCIe-inclusive rate: host scan + H2D + kernels + D2H, all overlapped by libpjdpipe (3 GPU slots)
             pipe_jpegs = jpegs * args.e2e_batches
             # warm-up: every slot allocates its HBM pool and page-locks its output buffer once
@@ -555,9 +600,9 @@ def main():
                 "d2h_GBps": round(ps["out_bytes"] / ps["wall_s"] / 1e9, 2), "exact_kernel_images": ps["n_exact_images"],
                 "worker_ms": {k[:-2]: round(ps[k] * 1e3, 1) for k in ("scan_s", "create_s", "upload_s", "exec_s", "download_s")},
                 "note": "JPEG bytes in host memory -> BMP bytes in page-locked host memory; pictures are not consumed further"}
-        if world == 1 and not args.no_cli and args.workload in ("cfg3", "cfg3lite"):
+        if args.full and world == 1 and not args.no_cli and args.workload in ("cfg3", "cfg3lite"):
             line["cli_end_to_end"] = cli_end_to_end(jpegs, local_rank)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(jpegs)
         print(json.dumps(line))
     if world > 1:

@@ -28,6 +28,21 @@ def ref():
 
 
 @pytest.fixture(scope="session")
+def live_ref():
+    """oracle/_ref where it is built, else None (tests then check the port against ref_record alone)."""
+    import oracle_lib
+    return oracle_lib.Ref() if oracle_lib.Ref.available() else None
+
+
+@pytest.fixture(scope="session")
+def ref_record():
+    """What oracle/_ref answered on the fixtures (tests/golden/ref_record.json, written by golden/make_ref_record.py)."""
+    import json
+    with open(os.path.join(HERE, "golden", "ref_record.json")) as f:
+        return json.load(f)
+
+
+@pytest.fixture(scope="session")
 def manifest():
     import json
     with open(os.path.join(HERE, "golden", "manifest.json")) as f:

@@ -8,6 +8,8 @@
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg import this.
 """
 import ctypes as C
+import hashlib
+import json
 import os
 import subprocess
 
@@ -46,6 +48,14 @@ class Info(C.Structure):
 def build_oracle():
     """(Re)build oracle/liboracle.so, and oracle/_ref when the reference tree is present."""
     subprocess.run(["make", "-s", "-C", ORACLE_DIR, "port", "_ref"], check=True)
+
+
+def ref_digest(parsed):
+    """One sha256 over a scanner result (Port.parse / Ref.parse_and_huffman): Info fields, ECS bytes, DPU metadata."""
+    h = hashlib.sha256(json.dumps(parsed["info"], sort_keys=True).encode())
+    h.update(parsed["ecs"].tobytes())
+    h.update(parsed["metadata"].astype(np.uint32).tobytes())
+    return h.hexdigest()
 
 
 def _u8(buf):

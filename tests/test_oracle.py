@@ -3,7 +3,8 @@
 * oracle/_ref (the reference's own scanner / Huffman / BMP code + dpu_stages.c)
   against the SURVEY section 0.4 known-answer hash;
 * oracle/liboracle.so (plain-C port) against oracle/_ref, field by field;
-* both against the committed manifest (generated from oracle/_ref).
+* both against the committed manifest and golden/ref_record.json (generated from oracle/_ref); where
+  oracle/_ref is not built (reference tree absent), the port is checked against them alone.
 """
 import hashlib
 import json
@@ -12,6 +13,7 @@ import os
 import numpy as np
 import pytest
 
+import oracle_lib
 from conftest import golden_bytes
 
 SURVEY_SHA256 = "11ab0c81cfc918410245c5ff0923f787219521073c094cbfd7e763f4b3444c1f"
@@ -31,10 +33,13 @@ def test_known_answer_port(port):
     assert hashlib.sha256(bmp).hexdigest() == SURVEY_SHA256
 
 
-def test_known_answer_ref(ref, tmp_path):
+def test_known_answer_ref(manifest, live_ref, tmp_path):
+    assert manifest["ilsvrc_val_00000001"]["bmp_sha256"] == SURVEY_SHA256      # the reference's answer, recorded by make_fixtures.py
+    if live_ref is None:
+        return
     jp = tmp_path / "a.jpg"
     jp.write_bytes(golden_bytes("ilsvrc_val_00000001"))
-    rc, _ = ref.run_cli(str(jp), str(tmp_path / "a.bmp"))
+    rc, _ = live_ref.run_cli(str(jp), str(tmp_path / "a.bmp"))
     assert rc == 0
     assert hashlib.sha256((tmp_path / "a.bmp").read_bytes()).hexdigest() == SURVEY_SHA256
 
@@ -58,20 +63,20 @@ def test_port_matches_manifest(port, manifest, name):
 
 
 @pytest.mark.parametrize("name", NAMES)
-def test_port_matches_ref_fields(port, ref, tmp_path, name):
+def test_port_matches_ref_fields(port, ref_record, live_ref, tmp_path, name):
+    """Scanner fields, ECS and DPU metadata: one digest (oracle_lib.ref_digest), None where the reference rejects the file."""
     data = golden_bytes(name)
-    jp = tmp_path / (name + ".jpg")
-    jp.write_bytes(data)
-    r = ref.parse_and_huffman(str(jp))
+    want = ref_record["fixtures"][name]
+    if live_ref is not None:
+        jp = tmp_path / (name + ".jpg")
+        jp.write_bytes(data)
+        r = live_ref.parse_and_huffman(str(jp))
+        assert r is not None
+        assert (oracle_lib.ref_digest(r) if r["info"]["valid"] else None) == want
     p = port.parse(data)
-    assert r is not None
-    assert r["info"]["valid"] == p["info"]["valid"]
-    if not r["info"]["valid"]:
-        return
-    for k, v in r["info"].items():
-        assert p["info"][k] == v, k
-    assert np.array_equal(r["ecs"], p["ecs"])
-    assert np.array_equal(r["metadata"], p["metadata"])
+    assert bool(p["info"]["valid"]) == (want is not None)
+    if want is not None:
+        assert oracle_lib.ref_digest(p) == want
 
 
 def test_stage_entry_points_compose(port):

@@ -1,5 +1,6 @@
 """The synthetic workload generator: its files are valid baseline JPEGs (Pillow decodes them close
-to the source), and the oracle port agrees with the reference's own code on them."""
+to the source), and the oracle port agrees with the reference's own code on them (as recorded in tests/golden/ref_record.json,
+and live where oracle/_ref is built)."""
 import hashlib
 import io
 import os
@@ -39,24 +40,27 @@ def test_synth_uses_annex_k_tables(port):
         assert a[k][:2] == b[k][:2], k
 
 
-def test_port_matches_ref_on_synth(port, ref, tmp_path):
+def synth_cases():
+    """(key, JPEG) of the synthetic pictures the port is checked on against the reference's CLI (tests/golden/ref_record.json)."""
     for i, (sub, ri, w, h) in enumerate([(synth.SUB_420, 0, 333, 200), (synth.SUB_444, 9, 120, 90), (synth.SUB_440, 0, 70, 130),
                                           (synth.SUB_422, 0, 200, 64), (synth.SUB_GREY, 3, 99, 99)]):
-        data = synth.make(w, h, 100 + i, 85, sub, ri)
-        jp = tmp_path / f"s{i}.jpg"
-        jp.write_bytes(data)
-        rc, out = ref.run_cli(str(jp), str(tmp_path / f"s{i}.bmp"))
-        assert rc == 0 and out == ""
-        o = port.decode(data)
-        assert o["bmp"] == (tmp_path / f"s{i}.bmp").read_bytes()
+        yield f"s{i}", synth.make(w, h, 100 + i, 85, sub, ri)
     # the dense set's pictures: more detail, per-picture optimised Huffman tables
     for i, (w, h, q) in enumerate([(333, 200, 97), (96, 160, 88)]):
-        data = synth.make(w, h, 200 + i, q, synth.SUB_420, 0, synth.DENSE_DETAIL, True)
-        jp = tmp_path / f"d{i}.jpg"
-        jp.write_bytes(data)
-        rc, out = ref.run_cli(str(jp), str(tmp_path / f"d{i}.bmp"))
-        assert rc == 0 and out == ""
-        assert port.decode(data)["bmp"] == (tmp_path / f"d{i}.bmp").read_bytes()
+        yield f"d{i}", synth.make(w, h, 200 + i, q, synth.SUB_420, 0, synth.DENSE_DETAIL, True)
+
+
+def test_port_matches_ref_on_synth(port, ref_record, live_ref, tmp_path):
+    for key, data in synth_cases():
+        jpeg_sha, bmp_sha = ref_record["synth"][key]
+        assert hashlib.sha256(data).hexdigest() == jpeg_sha, key      # the picture the record was made from
+        if live_ref is not None:
+            jp = tmp_path / f"{key}.jpg"
+            jp.write_bytes(data)
+            rc, out = live_ref.run_cli(str(jp), str(tmp_path / f"{key}.bmp"))
+            assert rc == 0 and out == ""
+            assert hashlib.sha256((tmp_path / f"{key}.bmp").read_bytes()).hexdigest() == bmp_sha
+        assert hashlib.sha256(port.decode(data)["bmp"]).hexdigest() == bmp_sha, key
 
 
 def test_imagenet_like_specs_are_deterministic():

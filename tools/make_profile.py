@@ -59,7 +59,7 @@ def main():
         for k, v in c.items():
             C.setdefault(k, {}).update(v)
             N[k] = max(N.get(k, 0), n[k])
-    cmd = "python3 bench.py --in-flight 1 --e2e-batches 0 --no-cpu-baseline --steps 10"
+    cmd = "python3 bench.py --in-flight 1 --e2e-batches 0 --no-cpu-baseline --steps 10 --full"
     md = [f"# profiles/{a.tag}.md -- rocprofv3 evidence, {a.workload_key}", "", a.note, "",
           "Commands (`tools/r2_pmc.sh`, MI355X box, ROCm 7.2, `cd /tmp && export TMPDIR=/tmp` first; one pass per line):", "",
           f"    rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -- {cmd}",
