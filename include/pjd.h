@@ -16,6 +16,8 @@
  *   4 x dpus()[0]->copy(ctr)  decoder_host.cpp:309-312  pjd_batch_decode_timed
  *   one picture over all DPUs decoder_host.cpp:125-149   pjd_split_decode (restart segments over GPUs)
  *   the per-DPU payload T0    decoder_dpu.c:57-58       pjd_exec_dpu_payload (literal)
+ *   (none: an addition)                                 PJD_F_SCALE_* + pjd_image_output_size: pictures out at
+ *                                                       1/2, 1/4 or 1/8 scale (libjpeg scale_num/scale_denom)
  *
  * Plain pointers and sizes only; no C++ or torch types.  Thread model: one
  * submitting thread per pjd_ctx (the reference has one consumer thread,
@@ -35,9 +37,10 @@ extern "C" {
 
 /* ABI version: bumped whenever a struct in this header changes size or layout (pjd_image_desc gained qt_slot48 and
  * pjd_batch_info grew in version 2; version 3 added the coefficient download and pjd_split_*; version 4 the progressive scans of
- * pjd_image_desc and the exact-path figures of pjd_batch_info; version 5 pjd_batch_info::n_steps).
+ * pjd_image_desc and the exact-path figures of pjd_batch_info; version 5 pjd_batch_info::n_steps; version 6 the output scale
+ * PJD_F_SCALE_* and pjd_pipe_opts::image_flags of pjd_pipeline.h).
  * A caller built against another version must not pass its structs: check pjd_version() == PJD_VERSION after loading.     */
-#define PJD_VERSION 5
+#define PJD_VERSION 6
 
 /* ---- error codes (library level) ---------------------------------------- */
 #define PJD_OK              0
@@ -61,7 +64,8 @@ extern "C" {
 #define PJD_ST_AC_BITS   7   /* "Error - Invalid AC value"  (value bits)                */
 
 /* ---- output formats ------------------------------------------------------- */
-#define PJD_OUT_RGB8   0   /* top-down, tightly packed R,G,B bytes: 3*W*H bytes              */
+#define PJD_OUT_RGB8   0   /* top-down, tightly packed R,G,B bytes: 3*W*H bytes (W, H: of the picture
+                              at its output scale, PJD_F_SCALE_*)                              */
 #define PJD_OUT_BMP    1   /* the complete file image bmp_writer.cpp:19-67 would emit:
                               26-byte BITMAPCOREHEADER file header, bottom-up B,G,R rows,
                               (W % 4) zero bytes after each row                               */
@@ -82,6 +86,22 @@ extern "C" {
                                        (jpeg_scanner.cpp:425-430) and its progressive branches (:521-704) handle one scan only --
                                        so this mode is NOT reference-comparable, parity for it is unpinned; it exists for
                                        SURVEY 8(f) N4 and is opt-in (pjd_scan_*_ex with PJD_SCAN_PROGRESSIVE).                */
+
+/* Reduced-size output, chosen per picture: s = 1 << ((flags >> 4) & 3), s = 1 (flag clear) is the full-size picture.  For s > 1,
+ * with P the W x H picture the library produces at s = 1 (as RGB8: the reference's picture, or the partial picture with grey after an
+ * entropy-coding error):
+ *   - the output is ceil(W/s) x ceil(H/s) (libjpeg's jdiv_round_up);
+ *   - output pixel (i, j) covers the source pixels x in [s*i, min(s*i + s, W)), y in [s*j, min(s*j + s, H)), n of them, and each
+ *     channel is (sum + (n >> 1)) / n in integer arithmetic over their clamped 8-bit R, G, B values (boxes are partial only at the
+ *     right and bottom picture edge);
+ *   - PJD_OUT_RGB8 gives tight rows of 3*ceil(W/s) bytes; PJD_OUT_BMP the file the reference's BMP writer would produce for a picture
+ *     of the scaled size (header with the scaled width and height, bottom-up B,G,R rows, sw % 4 zero bytes after each, sw = ceil(W/s));
+ *   - the status is the one of s = 1.
+ * Only the pixels change: coefficients (pjd_batch_download_coefficients) and pjd_exec_dpu_payload do not depend on the scale.  */
+#define PJD_F_SCALE_1_2        16u
+#define PJD_F_SCALE_1_4        32u
+#define PJD_F_SCALE_1_8        48u
+#define PJD_F_SCALE_MASK       48u
 
 /* Huffman table as the reference's scanner holds it (jpeg.h:129-134):
  * offsets[k] = number of codes of length <= k (offsets[0] = 0).               */
@@ -127,7 +147,7 @@ typedef struct pjd_image_desc {
     uint32_t flags;                    /* PJD_F_*                                             */
     /* Sharding of ONE image over several devices (restart segments are
      * independent): decode only segments [shard_first_seg, +shard_n_segs);
-     * shard_n_segs == 0 means "all".  The output buffer is always full-size;
+     * shard_n_segs == 0 means "all".  The output buffer is always the whole picture (at its output scale);
      * only the MCUs of the selected segments are written.                      */
     uint32_t shard_first_seg, shard_n_segs;
     uint32_t qt_slot48[4];             /* DQT entry 48 of each table: the reference's map sends it
@@ -152,13 +172,13 @@ typedef struct pjd_timings {
 
 typedef struct pjd_batch_info {
     int32_t  n_images;
-    uint64_t pixels;                   /* sum of width*height                                 */
+    uint64_t pixels;                   /* sum of width*height of the SOURCE pictures (the decode work, whatever the scale) */
     uint64_t ecs_bytes;                /* sum of ecs_len                                      */
-    uint64_t out_bytes;                /* sum of output sizes                                 */
+    uint64_t out_bytes;                /* sum of output sizes, each at the picture's output scale (PJD_F_SCALE_*) */
     uint64_t coef_bytes;               /* lane streams + transposed bitstream words + dense scratch in HBM */
     uint64_t n_data_units;
     uint64_t n_subsequences;           /* Huffman decode lanes                                */
-    uint64_t device_bytes;             /* everything this batch holds in HBM                  */
+    uint64_t device_bytes;             /* everything this batch holds in HBM (the output buffer at the scaled sizes) */
     int32_t  n_sequential;             /* images routed to the exact one-lane kernel up front */
     int32_t  n_fallback;               /* images re-decoded by it after the last decode       */
     uint64_t n_huff_workgroups;        /* Huffman workgroups (up to 2 waves of 64 lanes, one table set) */
@@ -256,7 +276,7 @@ int  pjd_decode_batch(pjd_ctx *ctx, const pjd_image_desc *images, int n_images,
  * intervals: device k of `devices` decodes a contiguous range of restart segments (pjd_split_plan), the
  * descriptor (tables + segment offsets, ~20 KB) is broadcast from the first device's HBM with one
  * ncclBroadcast (RCCL over xGMI; loaded on first use; plain copies if RCCL is missing), every device
- * uploads only its slice of `desc->ecs`, and the rows come back into `out` (pjd_output_size bytes).
+ * uploads only its slice of `desc->ecs`, and the rows come back into `out` (pjd_image_output_size bytes: at the output scale).
  * One host thread per device inside the call.  A picture that cannot be split (no DRI; subsampled luma
  * under the reference's restart rule) is decoded by devices[0] alone; so is, a second time, a picture whose
  * entropy decode reports an error, so that status and partial picture are the reference's.               */
@@ -308,6 +328,11 @@ void pjd_host_free(void *p);
 
 /* Size in bytes of one picture in a given output format.                      */
 uint64_t pjd_output_size(uint32_t width, uint32_t height, int out_format);
+/* Output dimensions of a width x height picture under descriptor flags `flags` (PJD_F_SCALE_*): ceil(W/s) x ceil(H/s).  Returns PJD_OK. */
+int  pjd_scaled_dims(uint32_t width, uint32_t height, uint32_t flags, uint32_t *out_w, uint32_t *out_h);
+/* Size in bytes of the picture of one descriptor in a given output format, at its output scale: what pjd_batch_output_size,
+ * pjd_decode_batch and pjd_split_decode use.  0 for a null descriptor.                                                       */
+uint64_t pjd_image_output_size(const pjd_image_desc *d, int out_format);
 
 #ifdef __cplusplus
 }

@@ -59,13 +59,15 @@ typedef struct pjd_pipe_opts {
     const int32_t *devices;  /* HIP ordinals to spread the batches over; NULL -> { device }    */
     int32_t n_devices;       /* entries in `devices` (at most PJD_PIPE_MAX_DEVICES)            */
     uint32_t scan_options;   /* PJD_SCAN_* of pjd_host.h handed to the scanner (0 = the reference's accept / reject set) */
+    uint32_t image_flags;    /* PJD_F_* ORed into every descriptor the scanner produces: PJD_F_SCALE_* (reduced-size pictures
+                                for the sink), PJD_F_STANDARD_*; 0 = as scanned.  Added in PJD_VERSION 6.               */
 } pjd_pipe_opts;
 
 typedef struct pjd_pipe_stats {
     double wall_s;           /* whole run                                                      */
     double scan_s, create_s, upload_s, exec_s, download_s, sink_s;   /* summed over workers   */
     uint64_t n_inputs, n_decoded, n_rejected, n_batches, n_batch_failures;
-    uint64_t pixels, in_bytes, ecs_bytes, out_bytes;
+    uint64_t pixels, in_bytes, ecs_bytes, out_bytes;  /* pixels of the source pictures; out_bytes of the pictures the sink got (scaled) */
     uint64_t n_devices;                              /* devices that opened                    */
     uint64_t n_stolen;                               /* batches run by another device than the one they were dealt to */
     uint64_t device_batches[PJD_PIPE_MAX_DEVICES];   /* batches run per entry of `devices` (an entry whose device did not open stays 0) */

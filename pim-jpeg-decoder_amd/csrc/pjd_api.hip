@@ -490,11 +490,12 @@ int enqueue_decode(pjd_batch *b, pjd_timings *timings, bool use_groups)
     //            entropy decoder's chains and stretch them -- 3.4-3.5 ms per batch against 2.6-2.7 for "groups" and 2.9 for "chain"
     //            (profiles/r04_experiments.md #16); kept as an experiment switch
     //   "chain"  as with several batches in flight: one chain of launches
+    // A batch that holds pictures with an output scale (PJD_F_SCALE_*) takes "groups" instead of "pull": the pull launch has no scaled form.
     static const int idle_form = [] { const char *e = std::getenv("PJD_IDLE_FORM"); return !e ? 1 : (!std::strcmp(e, "pull") ? 2 : (!std::strcmp(e, "chain") ? 0 : 1)); }();
     const bool idle = !timings && use_groups && parallel && !P.groups.empty() && idle_form != 0;       // per-kernel timing: one chain, kernel after kernel
-    const size_t ng = (idle && idle_form == 1) ? P.groups.size() : 0;
+    const size_t ng = (idle && (idle_form == 1 || P.scaled)) ? P.groups.size() : 0;
     const bool grouped = ng > 1 && ctx_group_streams(ctx, ng);
-    if (idle && idle_form == 2 && ctx_group_streams(ctx, 2)) {
+    if (idle && idle_form == 2 && !P.scaled && ctx_group_streams(ctx, 2)) {
         // The pull back end (pjd_internal.h): entropy decode on the context's stream, the back end's pull launch on a second stream
         // beside it (inside a capture: two parallel one-node branches), then the sweep over whatever the pull launch left.
         PjdDevBatch dv = b->dev;
@@ -524,7 +525,7 @@ int enqueue_decode(pjd_batch *b, pjd_timings *timings, bool use_groups)
             pjd_launch_lane_words_group(gs, b->dev, P.groups[g]);
             pjd_launch_huff_lanes_group(gs, b->dev, P.groups[g], (uint32_t)g);
             pjd_launch_group_dc(gs, b->dev, P.groups[g]);
-            pjd_launch_group_idct(gs, b->dev, P.groups[g]);
+            pjd_launch_group_idct(gs, b->dev, P.groups[g], P.scaled);
             if (g) { HIP_TRY(ctx, hipEventRecord(ctx->join_ev[g - 1], gs)); }
         }
         for (size_t g = 1; g < ng; g++) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->join_ev[g - 1], 0));
@@ -534,7 +535,7 @@ int enqueue_decode(pjd_batch *b, pjd_timings *timings, bool use_groups)
             pjd_launch_lane_words(s, b->dev);    kt.mark("lane_words");
             pjd_launch_huff_lanes(s, b->dev);    kt.mark("huff_lanes");
             pjd_launch_lane_dc_scan(s, b->dev);  kt.mark("dc_scan");
-            pjd_launch_idct_colour_lanes(s, b->dev);
+            pjd_launch_idct_colour_lanes(s, b->dev, P.scaled);
             kt.mark("idct_colour");
         }
     }
@@ -543,7 +544,7 @@ int enqueue_decode(pjd_batch *b, pjd_timings *timings, bool use_groups)
         pjd_launch_zero(s, b->dev.coef, P.dense_du * 64 * sizeof(int16_t));      // a kernel, not a memset node: see the reset above
         pjd_launch_huff_sequential(s, b->dev, b->d_seq_list, b->d_seq_base, (uint32_t)b->seq_list.size());
         if (!P.pscans.empty()) pjd_launch_progressive(s, b->dev, b->d_seq_list, b->d_seq_base, (uint32_t)b->seq_list.size());
-        pjd_launch_idct_colour(s, b->dev, b->d_iwgs_dense, b->d_seq_base, (uint32_t)P.iwgs_dense.size());
+        pjd_launch_idct_colour(s, b->dev, b->d_iwgs_dense, b->d_seq_base, (uint32_t)P.iwgs_dense.size(), P.scaled);
         kt.mark("exact_path");
     }
     HIP_TRY(ctx, hipGetLastError());
@@ -623,7 +624,7 @@ int settle(pjd_batch *b)
         if (e == hipSuccess) {
             if (ev0) (void)hipEventRecord(ev0, s);
             pjd_launch_huff_sequential(s, dv, d_list, d_base, (uint32_t)fb.size());
-            pjd_launch_idct_colour(s, dv, d_wgs, d_base, (uint32_t)fb_wgs.size());
+            pjd_launch_idct_colour(s, dv, d_wgs, d_base, (uint32_t)fb_wgs.size(), P.scaled);
             if (ev1) (void)hipEventRecord(ev1, s);
             e = hipGetLastError();
         }

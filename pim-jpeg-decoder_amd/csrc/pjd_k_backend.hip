@@ -286,8 +286,10 @@ __device__ __forceinline__ void pjd_tile_col(int16_t (*tile)[TILE_STRIDE], uint3
 // Row pass, column pass, chroma upsample + colour + raster store for the data units staged in `tile`
 // (natural order, dequantised).  Shared by the sparse and the dense front ends.
 // DO_IDCT = false: the caller has already run both passes on every unit (and this function's first barrier is
-// the one that separates them from the colour stage).
-template <bool DO_IDCT>
+// the one that separates them from the colour stage).  SCALED: pictures with an output scale take the scaled store (below).
+__device__ __forceinline__ void pjd_colour_dispatch_scaled(const int16_t (*tile)[TILE_STRIDE], const uint32_t *mcu_xy, const PjdDevBatch &B,
+                                                           const PjdDevImage &im, const PjdDevIdctWg &wg, uint32_t tid);
+template <bool DO_IDCT, bool SCALED>
 __device__ __forceinline__ void pjd_tile_to_pixels(int16_t (*tile)[TILE_STRIDE], uint32_t *mcu_xy, const PjdDevBatch &B,
                                                    const PjdDevImage &im, const PjdDevIdctWg &wg, uint32_t tid)
 {
@@ -304,6 +306,7 @@ __device__ __forceinline__ void pjd_tile_to_pixels(int16_t (*tile)[TILE_STRIDE],
         for (uint32_t i = tid; i < n_du * 8; i += PJD_IDCT_THREADS) pjd_tile_col(tile, i >> 3, i & 7);
         __syncthreads();
     }
+    if (SCALED && (im.flags & PJD_IF_SCALE_MASK)) { pjd_colour_dispatch_scaled(tile, mcu_xy, B, im, wg, tid); return; }
 
     // ---- chroma upsample (nearest neighbour, decoder_dpu.c:370), colour, raster store --------
     const uint32_t mw = 8 * hs, mh = 8 * vs;
@@ -495,9 +498,139 @@ __device__ __forceinline__ void pjd_bmp_header(uint8_t *out, uint32_t width, uin
     out[tid] = hb;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Reduced-size output (PJD_F_SCALE_*, include/pjd.h): output pixel (i, j) is the rounded mean of the clamped 8-bit colours of the
+// source box [S*i, S*i + S) x [S*j, S*j + S), cut at the right and bottom picture edge.  S divides 8 and an MCU is 8 or 16 pixels
+// on a side, so every box lies inside one MCU of the workgroup.  The colour arithmetic is pjd_colour_store's; a thread takes one
+// 4-pixel column group of an MCU over the S picture rows of one box row (the task index runs over all threads of the workgroup)
+// and keeps the sums in registers: 4 / S output pixels for S <= 4; at S = 8 the two column groups of a box are neighbouring lanes
+// and add their sums with one cross-lane move.  A full box divides by a shift, only edge boxes by n < S * S.
+// ---------------------------------------------------------------------------------------------
+template <int HS, int VS, bool BMP, int S>
+__device__ __forceinline__ void pjd_colour_store_scaled(const int16_t (*tile)[TILE_STRIDE], const uint32_t *mcu_xy, uint8_t *out,
+                                                        uint32_t width, uint32_t height, uint32_t stride, uint32_t ncomp,
+                                                        uint32_t n_mcu, uint32_t tid)
+{
+    constexpr uint32_t MW = 8 * HS, MH = 8 * VS, NL = HS * VS;
+    constexpr uint32_t CG_LOG = HS == 2 ? 2 : 1;               // log2 of the 4-pixel column groups per MCU row
+    constexpr uint32_t S_LOG = S == 2 ? 1 : (S == 4 ? 2 : 3);
+    constexpr uint32_t BR_LOG = (VS == 2 ? 4 : 3) - S_LOG;     // log2 of the box rows per MCU (MH / S)
+    constexpr int NCH = 4 / HS;                                 // chroma samples under 4 pixels
+    constexpr int NO = S < 4 ? 4 / S : 1;                       // output pixels a thread sums for
+    constexpr int PX_LOG = S < 4 ? S_LOG : 2;                   // log2 of the pixels of a row that go into one of them
+    static_assert(MH % S == 0 && S % VS == 0, "a box lies inside one MCU and covers whole chroma rows");
+    const uint32_t dus = NL + ncomp - 1;
+    const uint32_t tasks = n_mcu << (CG_LOG + BR_LOG);          // even: the two halves of an 8-wide box run in the same iterations
+    const uint32_t sh = (height + S - 1) >> S_LOG;
+    for (uint32_t t = tid; t < tasks; t += PJD_IDCT_THREADS) {
+        const uint32_t ml = t >> (CG_LOG + BR_LOG), j = (t >> CG_LOG) & ((1u << BR_LOG) - 1), px0 = (t & ((1u << CG_LOG) - 1)) * 4;
+        const uint32_t xy = mcu_xy[ml];
+        const uint32_t X = __umul24(xy & 0xffffu, MW) + px0, Yb = __umul24(xy >> 16, MH) + j * S;   // first pixel, first row of the box
+        const uint32_t d0 = __umul24(ml, dus);
+        uint32_t sf[NO], sg[NO], sl[NO];                        // sums of the first / middle / last output byte
+#pragma unroll
+        for (int k = 0; k < NO; k++) sf[k] = sg[k] = sl[k] = 0;
+        if (X < width && Yb < height) {
+#pragma unroll
+            for (uint32_t k = 0; k < S / VS; k++) {             // the chroma rows (row groups) of the box row
+                const uint32_t rg = j * (S / VS) + k, Y0 = Yb + k * VS;
+                if (Y0 >= height) break;
+                int cf[NCH], cg[NCH], cl[NCH];
+                {
+                    const uint32_t q = rg * 8 + px0 / HS;
+                    uint32_t cbw[2] = {0, 0}, crw[2] = {0, 0};
+                    if (ncomp > 1) {
+                        if (HS == 2) cbw[0] = *reinterpret_cast<const uint32_t *>(&tile[d0 + NL][q]);
+                        else { const uint2 t2 = *reinterpret_cast<const uint2 *>(&tile[d0 + NL][q]); cbw[0] = t2.x; cbw[1] = t2.y; }
+                    }
+                    if (ncomp > 2) {
+                        if (HS == 2) crw[0] = *reinterpret_cast<const uint32_t *>(&tile[d0 + NL + 1][q]);
+                        else { const uint2 t2 = *reinterpret_cast<const uint2 *>(&tile[d0 + NL + 1][q]); crw[0] = t2.x; crw[1] = t2.y; }
+                    }
+#pragma unroll
+                    for (int c = 0; c < NCH; c++) {
+                        const uint32_t bw = cbw[c >> 1], rw = crw[c >> 1];
+                        const int cbv = (c & 1) ? (int)bw >> 16 : (int)(int16_t)(bw & 0xffff);
+                        const int crv = (c & 1) ? (int)rw >> 16 : (int)(int16_t)(rw & 0xffff);
+                        const int rC = (__mul24(5880414, crv) >> 22) + 128, bC = (__mul24(7432306, cbv) >> 22) + 128;
+                        cg[c] = 128 - (__mul24(1442840, cbv) >> 22) - (__mul24(2994733, crv) >> 22);
+                        cf[c] = BMP ? bC : rC;
+                        cl[c] = BMP ? rC : bC;
+                    }
+                }
+#pragma unroll
+                for (int v = 0; v < VS; v++) {
+                    if (Y0 + v >= height) break;
+                    const uint32_t py = rg * VS + v;
+                    const int16_t *yp = &tile[d0 + (py >> 3) * HS + (px0 >> 3)][(py & 7) * 8 + (px0 & 7)];
+                    const uint2 yraw = *reinterpret_cast<const uint2 *>(yp);               // 4 luma samples
+                    const int yv[4] = {(int16_t)(yraw.x & 0xffff), (int)yraw.x >> 16, (int16_t)(yraw.y & 0xffff), (int)yraw.y >> 16};
+#pragma unroll
+                    for (int p = 0; p < 4; p++) {
+                        const int c = HS == 2 ? p >> 1 : p;                                  // chroma sample of pixel p
+                        // reference src/decoder_dpu.c:376-382: y + term + 128, clamped; pixels past the right edge do not count
+                        const bool in = p == 0 || X + p < width;
+                        sf[p >> PX_LOG] += in ? (uint32_t)pjd_clamp255(yv[p] + cf[c]) : 0u;
+                        sg[p >> PX_LOG] += in ? (uint32_t)pjd_clamp255(yv[p] + cg[c]) : 0u;
+                        sl[p >> PX_LOG] += in ? (uint32_t)pjd_clamp255(yv[p] + cl[c]) : 0u;
+                    }
+                }
+            }
+        }
+        if (S == 8) {                                           // the other half of the box: lane t ^ 1 (t and the lane index share bit 0)
+            sf[0] += (uint32_t)__shfl_xor((int)sf[0], 1);
+            sg[0] += (uint32_t)__shfl_xor((int)sg[0], 1);
+            sl[0] += (uint32_t)__shfl_xor((int)sl[0], 1);
+        }
+        if (X < width && Yb < height && (S < 8 || (px0 & 4) == 0)) {
+            const uint32_t bh = height - Yb < S ? height - Yb : S;
+            const uint32_t oy = Yb >> S_LOG, ox = X >> S_LOG;
+            uint8_t *o = BMP ? out + 26 + (size_t)(sh - 1 - oy) * stride + ox * 3 : out + (size_t)oy * stride + ox * 3;
+#pragma unroll
+            for (int k = 0; k < NO; k++) {
+                const uint32_t bx = X + k * S;                  // first column of the box
+                if (k > 0 && bx >= width) break;
+                const uint32_t n = (width - bx < S ? width - bx : S) * bh;
+                uint32_t a, b, c;
+                if (n == S * S) { a = (sf[k] + S * S / 2) >> (2 * S_LOG); b = (sg[k] + S * S / 2) >> (2 * S_LOG); c = (sl[k] + S * S / 2) >> (2 * S_LOG); }
+                else { a = (sf[k] + (n >> 1)) / n; b = (sg[k] + (n >> 1)) / n; c = (sl[k] + (n >> 1)) / n; }
+                o[3 * k] = (uint8_t)a; o[3 * k + 1] = (uint8_t)b; o[3 * k + 2] = (uint8_t)c;
+            }
+        }
+    }
+}
+
+__device__ __forceinline__ void pjd_colour_dispatch_scaled(const int16_t (*tile)[TILE_STRIDE], const uint32_t *mcu_xy, const PjdDevBatch &B,
+                                                           const PjdDevImage &im, const PjdDevIdctWg &wg, uint32_t tid)
+{
+    uint8_t *out = B.out + im.out_off;
+    const uint32_t width = im.width, height = im.height, stride = im.out_stride, nc = im.ncomp, n = wg.n_mcu;
+    const bool bmp = (im.flags & PJD_IF_BMP) != 0;
+    const uint32_t s_log = (im.flags & PJD_IF_SCALE_MASK) >> PJD_IF_SCALE_SHIFT;          // 1..3
+    if (bmp && wg.first_mcu == 0) pjd_bmp_header(out, (width + (1u << s_log) - 1) >> s_log, (height + (1u << s_log) - 1) >> s_log, stride, tid);
+    const uint32_t mode = (im.hs - 1) | ((im.vs - 1) << 1) | (bmp ? 4u : 0u) | ((s_log - 1) << 3);
+#define PJD_SCALED_CASE(M, HS_, VS_, BMP_, S_) \
+    case M: pjd_colour_store_scaled<HS_, VS_, BMP_, S_>(tile, mcu_xy, out, width, height, stride, nc, n, tid); break;
+#define PJD_SCALED_CASES(M0, S_)                                                                                          \
+    PJD_SCALED_CASE(M0 + 0, 1, 1, false, S_) PJD_SCALED_CASE(M0 + 1, 2, 1, false, S_) PJD_SCALED_CASE(M0 + 2, 1, 2, false, S_) \
+    PJD_SCALED_CASE(M0 + 3, 2, 2, false, S_) PJD_SCALED_CASE(M0 + 4, 1, 1, true, S_)  PJD_SCALED_CASE(M0 + 5, 2, 1, true, S_)  \
+    PJD_SCALED_CASE(M0 + 6, 1, 2, true, S_)  PJD_SCALED_CASE(M0 + 7, 2, 2, true, S_)
+    switch (mode) {
+        PJD_SCALED_CASES(0, 2)
+        PJD_SCALED_CASES(8, 4)
+        PJD_SCALED_CASES(16, 8)
+        default: break;
+    }
+#undef PJD_SCALED_CASES
+#undef PJD_SCALED_CASE
+}
+
+// SCALED: the kernel also serves pictures with an output scale (a kernel of its own, so that the full-size kernels stay as they are)
+template <bool SCALED>
 __device__ __forceinline__ void pjd_colour_dispatch(const int16_t (*tile)[TILE_STRIDE], const uint32_t *mcu_xy, const PjdDevBatch &B,
                                                     const PjdDevImage &im, const PjdDevIdctWg &wg, uint32_t tid)
 {
+    if (SCALED && (im.flags & PJD_IF_SCALE_MASK)) { pjd_colour_dispatch_scaled(tile, mcu_xy, B, im, wg, tid); return; }
     uint8_t *out = B.out + im.out_off;
     const uint32_t width = im.width, height = im.height, stride = im.out_stride, nc = im.ncomp, n = wg.n_mcu;
     const bool bmp = (im.flags & PJD_IF_BMP) != 0;
@@ -518,6 +651,9 @@ __device__ __forceinline__ void pjd_colour_dispatch(const int16_t (*tile)[TILE_S
 // ---------------------------------------------------------------------------------------------
 // Fused back end.  One workgroup = up to 96 data units = a run of consecutive MCUs of one image.
 // ---------------------------------------------------------------------------------------------
+// SCALED: the form for a batch that holds pictures with an output scale (PJD_F_SCALE_*); a kernel of its own, so that the full-size one
+// keeps its code and registers
+template <bool SCALED>
 __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_colour(PjdDevBatch B, const PjdDevIdctWg *__restrict__ wgs, const uint64_t *__restrict__ dense_base)
 {
     __shared__ __attribute__((aligned(16))) int16_t tile[PJD_IDCT_MAX_DU][TILE_STRIDE];
@@ -572,7 +708,7 @@ __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_colour(PjdDevBatc
         }
     }
     __syncthreads();
-    pjd_tile_to_pixels<true>(tile, mcu_xy, B, im, wg, tid);
+    pjd_tile_to_pixels<true, SCALED>(tile, mcu_xy, B, im, wg, tid);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -619,6 +755,8 @@ __device__ __forceinline__ void pjd_tile_put(uint32_t tile_lds, uint32_t u, uint
 }
 
 // One back-end range (PjdDevIdctWg `iwg`) by the whole workgroup; the LDS arrays are the kernel's.  Returns are workgroup-uniform.
+// SCALED: pictures with an output scale take the scaled store.
+template <bool SCALED>
 __device__ __forceinline__ void pjd_idct_range(const PjdDevBatch &B, uint32_t iwg, int16_t (*tile)[TILE_STRIDE], uint32_t (*qz)[64], uint32_t *mcu_xy,
                                                uint8_t *comp_of, uint32_t *wagg, uint32_t *ltab)
 {
@@ -840,7 +978,7 @@ __device__ __forceinline__ void pjd_idct_range(const PjdDevBatch &B, uint32_t iw
     if (tile[0][0] == 12345) B.out[0] = 1;
     return;
 #endif
-    pjd_colour_dispatch(tile, mcu_xy, B, im, wg, tid);
+    pjd_colour_dispatch<SCALED>(tile, mcu_xy, B, im, wg, tid);
 }
 
 // order: the launch's workgroup -> index into PjdDevBatch::iwgs / marks (null: the identity, one launch for the whole batch)
@@ -859,7 +997,24 @@ __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_colour_lanes(PjdD
 #endif
     const uint32_t iwg = order ? order[blockIdx.x] : blockIdx.x;
     if (sweep && __hip_atomic_load(B.range_done + iwg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
-    pjd_idct_range(B, iwg, tile, qz, mcu_xy, comp_of, wagg, ltab);
+    pjd_idct_range<false>(B, iwg, tile, qz, mcu_xy, comp_of, wagg, ltab);
+}
+
+// The same for a batch that holds pictures with an output scale (PJD_F_SCALE_*): a kernel of its own, so that the full-size one keeps
+// its code and registers.  Never a sweep: the pull form is not used for such batches.
+__global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_colour_lanes_scaled(PjdDevBatch B, const uint32_t *__restrict__ order)
+{
+    __shared__ __attribute__((aligned(16))) int16_t tile[PJD_IDCT_MAX_DU][TILE_STRIDE];
+    __shared__ uint32_t qz[3][64];
+    __shared__ uint32_t mcu_xy[PJD_IDCT_MAX_DU];
+    __shared__ uint8_t comp_of[PJD_IDCT_MAX_DU];
+    __shared__ uint32_t wagg[2];
+    __shared__ uint32_t ltab[96];
+
+#if PJD_IDCT_PRIO
+    __builtin_amdgcn_s_setprio(PJD_IDCT_PRIO);
+#endif
+    pjd_idct_range<true>(B, order ? order[blockIdx.x] : blockIdx.x, tile, qz, mcu_xy, comp_of, wagg, ltab);
 }
 
 // The pull launch (pjd_internal.h; experiment switch PJD_IDLE_FORM=pull): a few workgroups per CU stay and take the ranges of ready_list
@@ -904,16 +1059,17 @@ __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_pull(PjdDevBatch 
         continue;
 #endif
         __atomic_thread_fence(__ATOMIC_ACQUIRE);                           // what the picture's waves wrote (agent scope: other CUs)
-        pjd_idct_range(B, v - 1, tile, qz, mcu_xy, comp_of, wagg, ltab);
+        pjd_idct_range<false>(B, v - 1, tile, qz, mcu_xy, comp_of, wagg, ltab);
         __syncthreads();
         if (threadIdx.x == 0) __hip_atomic_store(B.range_done + (v - 1), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // read by the sweep: a later launch
     }
 }
 
-void pjd_launch_idct_colour_lanes(hipStream_t s, const PjdDevBatch &b)
+void pjd_launch_idct_colour_lanes(hipStream_t s, const PjdDevBatch &b, bool scaled)
 {
     if (b.n_iwg == 0) return;
-    hipLaunchKernelGGL(pjd_k_idct_colour_lanes, dim3(b.n_iwg), dim3(PJD_IDCT_THREADS), 0, s, b, (const uint32_t *)nullptr, 0);
+    if (scaled) hipLaunchKernelGGL(pjd_k_idct_colour_lanes_scaled, dim3(b.n_iwg), dim3(PJD_IDCT_THREADS), 0, s, b, (const uint32_t *)nullptr);
+    else hipLaunchKernelGGL(pjd_k_idct_colour_lanes, dim3(b.n_iwg), dim3(PJD_IDCT_THREADS), 0, s, b, (const uint32_t *)nullptr, 0);
 }
 
 void pjd_launch_idct_pull(hipStream_t s, const PjdDevBatch &b)
@@ -929,9 +1085,11 @@ void pjd_launch_idct_sweep(hipStream_t s, const PjdDevBatch &b)
     if (b.n_iwg) hipLaunchKernelGGL(pjd_k_idct_colour_lanes, dim3(b.n_iwg), dim3(PJD_IDCT_THREADS), 0, s, b, (const uint32_t *)nullptr, 1);
 }
 
-void pjd_launch_group_idct(hipStream_t s, const PjdDevBatch &b, const PjdDevGroup &g)
+void pjd_launch_group_idct(hipStream_t s, const PjdDevBatch &b, const PjdDevGroup &g, bool scaled)
 {
-    if (g.iwg_count) hipLaunchKernelGGL(pjd_k_idct_colour_lanes, dim3(g.iwg_count), dim3(PJD_IDCT_THREADS), 0, s, b, b.iwg_order + g.iwg_first, 0);
+    if (!g.iwg_count) return;
+    if (scaled) hipLaunchKernelGGL(pjd_k_idct_colour_lanes_scaled, dim3(g.iwg_count), dim3(PJD_IDCT_THREADS), 0, s, b, (const uint32_t *)(b.iwg_order + g.iwg_first));
+    else hipLaunchKernelGGL(pjd_k_idct_colour_lanes, dim3(g.iwg_count), dim3(PJD_IDCT_THREADS), 0, s, b, b.iwg_order + g.iwg_first, 0);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1013,9 +1171,10 @@ void pjd_launch_lane_dc_scan(hipStream_t s, const PjdDevBatch &b)
     hipLaunchKernelGGL(pjd_k_lane_dc_carry, dim3(1), dim3(256), 0, s, b);
 }
 
-void pjd_launch_idct_colour(hipStream_t s, const PjdDevBatch &b, const PjdDevIdctWg *wgs, const uint64_t *dense_base, uint32_t n_wg)
+void pjd_launch_idct_colour(hipStream_t s, const PjdDevBatch &b, const PjdDevIdctWg *wgs, const uint64_t *dense_base, uint32_t n_wg, bool scaled)
 {
     if (n_wg == 0) return;
-    hipLaunchKernelGGL(pjd_k_idct_colour, dim3(n_wg), dim3(PJD_IDCT_THREADS), 0, s, b, wgs, dense_base);
+    if (scaled) hipLaunchKernelGGL(pjd_k_idct_colour<true>, dim3(n_wg), dim3(PJD_IDCT_THREADS), 0, s, b, wgs, dense_base);
+    else hipLaunchKernelGGL(pjd_k_idct_colour<false>, dim3(n_wg), dim3(PJD_IDCT_THREADS), 0, s, b, wgs, dense_base);
 }
 

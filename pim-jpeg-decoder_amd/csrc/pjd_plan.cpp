@@ -37,6 +37,23 @@ extern "C" uint64_t pjd_output_size(uint32_t width, uint32_t height, int out_for
     return (uint64_t)width * height * 3;
 }
 
+// Reduced-size output (PJD_F_SCALE_*): ceil(W / s) x ceil(H / s), libjpeg's jdiv_round_up
+extern "C" int pjd_scaled_dims(uint32_t width, uint32_t height, uint32_t flags, uint32_t *out_w, uint32_t *out_h)
+{
+    const uint32_t sl = (flags & PJD_F_SCALE_MASK) >> 4;
+    if (out_w) *out_w = (uint32_t)(((uint64_t)width + (1u << sl) - 1) >> sl);
+    if (out_h) *out_h = (uint32_t)(((uint64_t)height + (1u << sl) - 1) >> sl);
+    return PJD_OK;
+}
+
+extern "C" uint64_t pjd_image_output_size(const pjd_image_desc *d, int out_format)
+{
+    if (!d) return 0;
+    uint32_t w = 0, h = 0;
+    pjd_scaled_dims(d->width, d->height, d->flags, &w, &h);
+    return pjd_output_size(w, h, out_format);
+}
+
 // ---------------------------------------------------------------------------------------------
 // Fewest bits of stream per STEP of the write pass that a table set can be made to sustain (x 256) -- what sizes the lane regions.
 // A step is one symbol or the pair the decode tables hold (pjd_internal.h): first symbol whole inside 9 bits (code + value bits, at
@@ -258,8 +275,11 @@ int pjd_make_plan(const pjd_image_desc *images, int n, int out_format, PjdPlan &
         g.n_mcu = g.mcux * g.mcuy;
         g.restart_interval = d.restart_interval;
         g.n_du = g.n_mcu * g.dus_per_mcu;
-        if (out_format == PJD_OUT_BMP) { g.flags |= PJD_IF_BMP; g.out_stride = d.width * 3 + d.width % 4; }
-        else g.out_stride = d.width * 3;
+        uint32_t sw = 0;                           // output width: the picture's, or its scaled width (PJD_F_SCALE_*)
+        pjd_scaled_dims(d.width, d.height, d.flags, &sw, nullptr);
+        if (out_format == PJD_OUT_BMP) { g.flags |= PJD_IF_BMP; g.out_stride = sw * 3 + sw % 4; }
+        else g.out_stride = sw * 3;
+        if (d.flags & PJD_F_SCALE_MASK) { g.flags |= ((d.flags & PJD_F_SCALE_MASK) >> 4) << PJD_IF_SCALE_SHIFT; P.scaled = true; }
         if (d.flags & PJD_F_STANDARD_RESTART) g.flags |= PJD_IF_STANDARD_RESTART;
         if (d.flags & PJD_F_STANDARD_ZIGZAG) g.flags |= PJD_IF_STANDARD_ZIGZAG;
 
@@ -537,7 +557,7 @@ int pjd_make_plan(const pjd_image_desc *images, int n, int out_format, PjdPlan &
             (sequential ? P.iwgs_dense : P.iwgs).push_back(w);
         }
         g.n_iwg = (uint32_t)(sequential ? P.iwgs_dense.size() : P.iwgs.size()) - g.iwg_base;
-        h.out_bytes = pjd_output_size(d.width, d.height, out_format);
+        h.out_bytes = pjd_image_output_size(&d, out_format);
         g.out_off = out_off;
         out_off = align_up(out_off + h.out_bytes, 256);
 

@@ -9,7 +9,7 @@
 struct PjdHostImage {
     const uint8_t *ecs_src;     // caller memory: first byte to upload
     uint64_t ecs_copy_len;      // bytes to upload
-    uint64_t out_bytes;         // size of this picture in the chosen output format
+    uint64_t out_bytes;         // size of this picture in the chosen output format, at its output scale
     bool sequential;            // routed to the exact one-lane kernel up front (or a progressive frame: pjd_k_progressive)
 };
 
@@ -50,7 +50,8 @@ struct PjdPlan {
     uint64_t n_dcblk = 0;
     uint64_t lut_buf_bytes = 0;            // decode-table blobs of all table sets the parallel path uses
     uint32_t max_lut_bytes = 0;            // largest blob (dynamic LDS of the Huffman kernel)
-    uint64_t pixels = 0, ecs_bytes = 0, out_bytes = 0;
+    uint64_t pixels = 0, ecs_bytes = 0, out_bytes = 0;   // pixels: of the source pictures; out_bytes: of the (scaled) output
+    bool scaled = false;                   // some picture has an output scale (PJD_F_SCALE_*): the back end's scaled kernels
     int plan_mode = 0;                     // PJD_PLAN_*
     std::vector<uint32_t> tset_step_bits;  // per table set: fewest bits of stream per step of the write pass, x 256 (sizes the lane regions)
 };

@@ -85,6 +85,8 @@ void drop_comms_locked()
     g_comm_devs.clear();
 }
 
+// In OUTPUT pixels: at an output scale s (PJD_F_SCALE_*) an MCU is mcu_w = 8 * h_samp / s columns and mcu_h = 8 * v_samp / s rows of
+// the ceil(W / s) x ceil(H / s) picture (s divides 8: a box never straddles two MCUs).
 struct Geometry {
     uint32_t mcu_w, mcu_h, mcux, mcuy, n_mcu, stride;
     bool bmp;
@@ -101,14 +103,15 @@ struct Geometry {
 Geometry geometry_of(const pjd_image_desc &d, int out_format)
 {
     Geometry g;
-    g.W = d.width; g.H = d.height;
-    g.mcu_w = 8u * d.h_samp; g.mcu_h = 8u * d.v_samp;
+    const uint32_t sl = (d.flags & PJD_F_SCALE_MASK) >> 4;
+    pjd_scaled_dims(d.width, d.height, d.flags, &g.W, &g.H);
+    g.mcu_w = (8u * d.h_samp) >> sl; g.mcu_h = (8u * d.v_samp) >> sl;
     const uint32_t w8 = (d.width + 7) / 8, h8 = (d.height + 7) / 8;
     g.mcux = (w8 + d.h_samp - 1) / d.h_samp;
     g.mcuy = (h8 + d.v_samp - 1) / d.v_samp;
     g.n_mcu = g.mcux * g.mcuy;
     g.bmp = out_format == PJD_OUT_BMP;
-    g.stride = g.bmp ? d.width * 3 + d.width % 4 : d.width * 3;
+    g.stride = g.bmp ? g.W * 3 + g.W % 4 : g.W * 3;
     return g;
 }
 
@@ -212,7 +215,7 @@ int pjd_split_decode(const pjd_image_desc *desc, const int32_t *devices, int n_d
     if (stats_out) *stats_out = st;
     if (!desc || !devices || n_devices <= 0 || n_devices > PJD_SPLIT_MAX_DEVICES || !out) return PJD_E_ARG;
     if (out_format != PJD_OUT_RGB8 && out_format != PJD_OUT_BMP) return PJD_E_ARG;
-    const uint64_t out_bytes = pjd_output_size(desc->width, desc->height, out_format);
+    const uint64_t out_bytes = pjd_image_output_size(desc, out_format);
     if (capacity < out_bytes) return PJD_E_ARG;
     const bool dup_ok = std::getenv("PJD_PIPE_ALLOW_DUP_DEVICES") != nullptr;     // tests on a one-GPU box: one ordinal, several ranks
     bool distinct = true;

@@ -20,6 +20,8 @@
 // device, the descriptor broadcast with RCCL, rows assembled on the host -- for single pictures larger than one device's share.
 // --progressive: progressive (SOF2) files are decoded scan by scan instead of being rejected as the reference rejects them
 // (not reference behaviour, parity unpinned).
+// --scale 1/2|1/4|1/8 (and 1/1): pictures are written at that scale, as `djpeg -scale` does -- each output pixel the rounded mean of
+// its box of source pixels (PJD_F_SCALE_* of include/pjd.h); in every mode.  Any other value is a usage error.
 #include <sys/stat.h>
 #include <time.h>
 
@@ -67,7 +69,7 @@ static void pipe_sink(void *user, int index, const char *name, const char *log, 
 }
 
 static int run_pipeline(const std::vector<std::string> &files, const std::vector<int32_t> &devices, int batch_images, int slots, int scan_threads,
-                        int write_threads, uint32_t scan_options)
+                        int write_threads, uint32_t scan_options, uint32_t image_flags)
 {
     std::vector<const char *> paths;
     for (const std::string &f : files) paths.push_back(f.c_str());
@@ -80,6 +82,7 @@ static int run_pipeline(const std::vector<std::string> &files, const std::vector
     o.slots = slots; o.scan_threads = scan_threads; o.sink_threads = write_threads;
     o.sink = pipe_sink; o.sink_user = &po;
     o.scan_options = scan_options;
+    o.image_flags = image_flags;
     pjd_pipe_stats st;
     const int rc = pjd_pipe_run_files(paths.data(), (int)paths.size(), &o, &st);
     if (rc == PJD_E_NODEVICE) {
@@ -112,7 +115,7 @@ static int run_pipeline(const std::vector<std::string> &files, const std::vector
 // For pictures larger than one device's share: the reference spreads every picture over all its DPUs (decoder_host.cpp:125-149,
 // 225); here a picture with restart intervals is cut into restart-segment ranges, one per device, the descriptor is broadcast
 // with RCCL and the rows are assembled on the host.  Pictures that cannot be cut are decoded by the first device.
-static int run_split(const std::vector<std::string> &files, const std::vector<int32_t> &devices, uint32_t scan_options)
+static int run_split(const std::vector<std::string> &files, const std::vector<int32_t> &devices, uint32_t scan_options, uint32_t image_flags)
 {
     double t_total = now_s(), t_scan = 0, t_bc = 0, t_up = 0, t_exec = 0, t_down = 0, t_bmp = 0;
     int calls = 0, rccl_calls = 0;
@@ -125,8 +128,10 @@ static int run_split(const std::vector<std::string> &files, const std::vector<in
         if (sr == 2) { std::cout << f << ": Error - Error opening input file\n" << f << ": Error - Invalid JPEG\n"; continue; }
         std::cout << pjd_scanned_log(s);
         if (sr != 0) { pjd_scanned_free(s); continue; }
-        const pjd_image_desc *d = pjd_scanned_desc(s);
-        std::vector<uint8_t> out(pjd_output_size(d->width, d->height, PJD_OUT_BMP));
+        pjd_image_desc dd = *pjd_scanned_desc(s);
+        dd.flags |= image_flags;
+        const pjd_image_desc *d = &dd;
+        std::vector<uint8_t> out(pjd_image_output_size(d, PJD_OUT_BMP));
         int32_t status = 0;
         pjd_split_stats st;
         const int rc = pjd_split_decode(d, devices.data(), (int)devices.size(), PJD_OUT_BMP, out.data(), out.size(), &status, &st);
@@ -165,7 +170,8 @@ int main(int argc, char **argv)
     int device = 0;
     size_t batch_images = 1024;
     bool pipeline = false, split = false;
-    uint32_t scan_options = 0;
+    uint32_t scan_options = 0, image_flags = 0;
+    bool bad_args = false;
     int slots = 0, scan_threads = 0, write_threads = 0;
     std::vector<std::string> files;
     std::vector<int32_t> devices;
@@ -185,12 +191,20 @@ int main(int argc, char **argv)
         else if (!std::strcmp(argv[i], "--pipeline")) pipeline = true;
         else if (!std::strcmp(argv[i], "--split")) split = true;
         else if (!std::strcmp(argv[i], "--progressive")) scan_options |= PJD_SCAN_PROGRESSIVE;
+        else if (!std::strcmp(argv[i], "--scale")) {
+            const char *v = i + 1 < argc ? argv[++i] : "";
+            if (!std::strcmp(v, "1/1")) image_flags = 0;
+            else if (!std::strcmp(v, "1/2")) image_flags = PJD_F_SCALE_1_2;
+            else if (!std::strcmp(v, "1/4")) image_flags = PJD_F_SCALE_1_4;
+            else if (!std::strcmp(v, "1/8")) image_flags = PJD_F_SCALE_1_8;
+            else bad_args = true;
+        }
         else if (!std::strcmp(argv[i], "--slots") && i + 1 < argc) slots = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--scan-threads") && i + 1 < argc) scan_threads = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--write-threads") && i + 1 < argc) write_threads = std::atoi(argv[++i]);
         else files.push_back(argv[i]);
     }
-    if (files.empty()) {
+    if (files.empty() || bad_args) {
         std::cout << "Error - Invalid arguments\n";
         return 1;
     }
@@ -206,13 +220,13 @@ int main(int argc, char **argv)
         for (const auto &p : sized) ordered.push_back(p.second);
         if (devices.empty()) devices.push_back(device);
         for (int32_t d : devices) if (d < 0) { std::cout << "Error - Invalid arguments\n"; return 1; }
-        return run_split(ordered, devices, scan_options);
+        return run_split(ordered, devices, scan_options, image_flags);
     }
     if (pipeline) {
         std::vector<std::string> ordered;
         for (const auto &p : sized) ordered.push_back(p.second);
         if (devices.empty()) devices.push_back(device);
-        return run_pipeline(ordered, devices, (int)batch_images, slots, scan_threads, write_threads, scan_options);
+        return run_pipeline(ordered, devices, (int)batch_images, slots, scan_threads, write_threads, scan_options, image_flags);
     }
 
     pjd_ctx *ctx = nullptr;
@@ -251,7 +265,10 @@ int main(int argc, char **argv)
         if (scanned.empty()) continue;
 
         std::vector<pjd_image_desc> descs;
-        for (pjd_scanned *s : scanned) descs.push_back(*pjd_scanned_desc(s));
+        for (pjd_scanned *s : scanned) {
+            descs.push_back(*pjd_scanned_desc(s));
+            descs.back().flags |= image_flags;
+        }
         pjd_batch *b = nullptr;
         t0 = now_s();
         rc = pjd_batch_create(ctx, descs.data(), (int)descs.size(), PJD_OUT_BMP, &b);

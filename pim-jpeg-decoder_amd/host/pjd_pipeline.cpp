@@ -214,7 +214,11 @@ struct Pipe {
             uint64_t rejected = 0;
             for (int i = job.first; i < job.first + job.count; i++) {
                 Input &x = in[i];
-                if (x.scan_rc == 0 && x.sc) { idx.push_back(i); descs.push_back(*pjd_scanned_desc(x.sc)); }
+                if (x.scan_rc == 0 && x.sc) {
+                    idx.push_back(i);
+                    descs.push_back(*pjd_scanned_desc(x.sc));
+                    descs.back().flags |= o.image_flags;       // e.g. PJD_F_SCALE_*: the sink receives the pictures at that scale
+                }
                 else { rejected++; emit(i, -1, nullptr, 0, &latch); }
             }
             double t_create = 0, t_up = 0, t_exec = 0, t_down = 0;

@@ -18,9 +18,10 @@ LIBPIPE = os.path.join(LIB_DIR, "libpjdpipe.so")
 OUT_RGB8, OUT_BMP = 0, 1
 PLAN_LATENCY, PLAN_THROUGHPUT = 0, 1      # pjd_set_plan_mode
 F_STANDARD_RESTART, F_FORCE_SEQUENTIAL, F_STANDARD_ZIGZAG, F_PROGRESSIVE = 1, 2, 4, 8
+F_SCALE_1_2, F_SCALE_1_4, F_SCALE_1_8, F_SCALE_MASK = 16, 32, 48, 48      # output scale s = 1 << ((flags >> 4) & 3) (pjd.h)
 SCAN_PROGRESSIVE = 1
 MAX_KERNELS = 16
-ABI_VERSION = 5          # PJD_VERSION of include/pjd.h these ctypes structs mirror
+ABI_VERSION = 6          # PJD_VERSION of include/pjd.h these ctypes structs mirror
 
 
 class HuffTable(C.Structure):
@@ -177,6 +178,10 @@ def dev_lib():
         L.pjd_exec_dpu_payload.argtypes = [vp, vp, vp, i32]
         L.pjd_output_size.restype = C.c_uint64
         L.pjd_output_size.argtypes = [C.c_uint32, C.c_uint32, i32]
+        L.pjd_scaled_dims.restype = i32
+        L.pjd_scaled_dims.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.pjd_image_output_size.restype = C.c_uint64
+        L.pjd_image_output_size.argtypes = [C.POINTER(ImageDesc), i32]
         L.pjd_coefficients_size.restype = C.c_uint64
         L.pjd_coefficients_size.argtypes = [C.c_uint32, C.c_uint32, C.c_uint8, C.c_uint8]
         L.pjd_batch_download_coefficients.restype = i32
@@ -356,7 +361,8 @@ class Batch:
         st = (C.c_int32 * max(self.n, 1))()
         self.ctx._check(self.L.pjd_batch_download(self._h, ptrs, st), "pjd_batch_download")
         if self.out_format == OUT_RGB8:
-            outs = [o.reshape(int(self._descs[i].height), int(self._descs[i].width), 3) for i, o in enumerate(outs)]
+            outs = [o.reshape(*reversed(scaled_dims(self._descs[i].width, self._descs[i].height, self._descs[i].flags)), 3)
+                    for i, o in enumerate(outs)]
         return outs, [int(st[i]) for i in range(self.n)]
 
 
@@ -396,7 +402,8 @@ class PipeOpts(C.Structure):
     _fields_ = [("device", C.c_int32), ("out_format", C.c_int32), ("batch_images", C.c_int32),
                 ("scan_threads", C.c_int32), ("slots", C.c_int32), ("sink_threads", C.c_int32),
                 ("sink", SINK_FN), ("sink_user", C.c_void_p),
-                ("devices", C.POINTER(C.c_int32)), ("n_devices", C.c_int32), ("scan_options", C.c_uint32)]
+                ("devices", C.POINTER(C.c_int32)), ("n_devices", C.c_int32), ("scan_options", C.c_uint32),
+                ("image_flags", C.c_uint32)]
 
 
 PIPE_MAX_DEVICES = 16
@@ -456,9 +463,10 @@ def pipe_assign(costs, n_devices):
 
 
 def pipe_run(jpegs=None, names=None, paths=None, out_format=OUT_BMP, batch_images=1024, scan_threads=0, slots=0,
-             sink_threads=0, sink=None, device=0, devices=None, scan_options=0):
+             sink_threads=0, sink=None, device=0, devices=None, scan_options=0, image_flags=0):
     """Run the pipelined batcher over in-memory JPEGs (`jpegs`: list of bytes) or files (`paths`).
     `devices`: HIP ordinals to spread the batches over (default: `device` alone).
+    `image_flags`: PJD_F_* ORed into every descriptor (F_SCALE_*: the sink receives reduced-size pictures).
 
     `sink(index, name, log, status, data)` is called from worker threads with `data` a numpy copy of the
     picture (or None).  Returns the statistics as a dict."""
@@ -467,6 +475,7 @@ def pipe_run(jpegs=None, names=None, paths=None, out_format=OUT_BMP, batch_image
     o.device, o.out_format, o.batch_images = device, out_format, batch_images
     o.scan_threads, o.slots, o.sink_threads = scan_threads, slots, sink_threads
     o.scan_options = scan_options
+    o.image_flags = image_flags
     if devices is not None:
         dv = (C.c_int32 * max(len(devices), 1))(*[int(d) for d in devices])
         o.devices, o.n_devices = C.cast(dv, C.POINTER(C.c_int32)), len(devices)
@@ -497,7 +506,7 @@ def split_decode(desc, devices, out_format=OUT_RGB8):
     """pjd_split_decode: ONE picture over several devices (restart-segment ranges, RCCL broadcast of the descriptor).
     -> (picture as np.uint8 array, status, stats dict)."""
     L = dev_lib()
-    n = int(L.pjd_output_size(desc.width, desc.height, out_format))
+    n = int(L.pjd_image_output_size(C.byref(desc), out_format))
     out = np.zeros(n, np.uint8)
     dv = (C.c_int32 * len(devices))(*[int(d) for d in devices])
     st, status = SplitStats(), C.c_int32(0)
@@ -505,7 +514,7 @@ def split_decode(desc, devices, out_format=OUT_RGB8):
     if rc != 0:
         raise PjdError(f"pjd_split_decode failed ({rc})")
     if out_format == OUT_RGB8:
-        out = out.reshape(int(desc.height), int(desc.width), 3)
+        out = out.reshape(*reversed(scaled_dims(desc.width, desc.height, desc.flags)), 3)
     return out, int(status.value), st.as_dict()
 
 
@@ -549,3 +558,16 @@ def plan_info(descs, out_format=OUT_RGB8):
     if rc != 0:
         raise PjdError(f"pjd_plan_info failed ({rc})")
     return {k: (list(getattr(bi, k)) if k == "flag_waves" else (float(getattr(bi, k)) if k == "exact_fallback_ms" else int(getattr(bi, k)))) for k, _ in bi._fields_}
+
+
+def scaled_dims(width, height, flags=0):
+    """pjd_scaled_dims: (width, height) of the output picture at the scale the descriptor flags ask for (F_SCALE_*)."""
+    L = dev_lib()
+    w, h = C.c_uint32(), C.c_uint32()
+    L.pjd_scaled_dims(int(width), int(height), int(flags), C.byref(w), C.byref(h))
+    return w.value, h.value
+
+
+def image_output_size(desc, out_format=OUT_RGB8):
+    """pjd_image_output_size: bytes of the picture of one descriptor in `out_format`, at its output scale."""
+    return int(dev_lib().pjd_image_output_size(C.byref(desc), out_format))
