@@ -798,8 +798,10 @@ __device__ __forceinline__ void write_span(const PhaseCtx &P, pjd_gptr wave_word
 // (reference src/jpeg_scanner.cpp:469-518): nothing of that symbol is stored, everything before it is; an error inside a unit's
 // AC part leaves the unit with what it has (closed here by an end-of-block entry), an error in the DC symbol leaves the unit
 // untouched.  Rare by construction: step words go straight to HBM, two symbols to a word wherever the first leaves its unit open.
-//   eof_rel: bits from the lane's first byte to the end of the stream, or ~0 if the stream does not end in this lane's segment:
-//            running out of bits is get_next_symbol's 0xFF / read_bits' -1 (reference src/headers/jpeg.h:91-113)
+//   eof_rel: bits from the lane's first byte to the end of the stream, or ~0 if no symbol of this lane can reach it: running out of
+//            bits is get_next_symbol's 0xFF / read_bits' -1 (reference src/headers/jpeg.h:91-113)
+//   to_eof:  the stream ends in this lane: decode on past end_bit until the units or the bits run out (a lane before it only
+//            finishes the symbol it started, which may run past the end of a stream whose last lane is a few bits long)
 struct Careful {
     // in: where the lane's marks start (the fast pass wrote them against ITS layout -- pairs share a step word there -- so they are written again)
     PjdDevMark *marks;
@@ -813,7 +815,8 @@ struct Careful {
 };
 
 __device__ __forceinline__ void careful_span(const PhaseCtx &P, pjd_gptr wave_words, uint32_t col, uint32_t p, uint32_t c, uint32_t z,
-                                          uint32_t end_bit, uint32_t eof_rel, uint32_t D, uint32_t D_end, uint16_t *region, uint32_t cap, Careful &R)
+                                          uint32_t end_bit, uint32_t eof_rel, bool to_eof, uint32_t D, uint32_t D_end, uint16_t *region, uint32_t cap,
+                                          Careful &R)
 {
     const uint32_t D_in = D;
     uint32_t *region32 = reinterpret_cast<uint32_t *>(region);
@@ -828,7 +831,7 @@ __device__ __forceinline__ void careful_span(const PhaseCtx &P, pjd_gptr wave_wo
     // lane's region is sized for.
     bool open = false;                                                           // the last step word written has its B half free
     uint32_t open_at = 0, open_ent = 0;
-    while (D < D_end && (p < end_bit || at_end)) {
+    while (D < D_end && (p < end_bit || to_eof)) {
         const bool is_dc = zb == 63;
         if (!open) {
             if ((R.n & (PJD_GROUP - 1)) == 0 && R.n + 2 <= cap) {                // a group begins: its head (pjd_internal.h)
@@ -1403,14 +1406,19 @@ __global__ __launch_bounds__(PJD_HUFF_THREADS) PJD_HUFF_OCC_ATTR void pjd_k_huff
             li.dc_sum[0] = (uint16_t)O.dcA; li.dc_sum[1] = (uint16_t)(O.dcA >> 16); li.dc_sum[2] = (uint16_t)O.dcB;
             const bool has_next = g.seg + 1 < im.seg_base + im.n_seg;
             // the lane in which the bitstream ends: too few bits for the picture is the reference's end-of-data error, not ours
-            const bool eof_lane = g.seg_last && !has_next && (im.flags & PJD_IF_ENDS_STREAM) != 0;
+            const bool last_seg = !has_next && (im.flags & PJD_IF_ENDS_STREAM) != 0;
+            const bool eof_lane = g.seg_last && last_seg;
+            // a lane before it whose last symbol ran past the end of the data (the last lane holds fewer bits than that symbol's
+            // code and value bits): that symbol is the reference's end-of-data error (the bits read past the end are not data)
+            const bool eof_crossed = last_seg && !g.seg_last && p > g.seg_end_bit;
             bool settled = false;
-            if (err || (eof_lane && (D < D_end || p > g.seg_end_bit))) {
+            if (err || (eof_lane && (D < D_end || p > g.seg_end_bit)) || eof_crossed) {
                 // an entropy-coding error of the TRUE decode (this lane started from the true state): find it exactly, keep what
                 // precedes it, report it by position -- the picture's verdict takes the first one (pjd_k_image_verdict)
                 Careful R;
                 R.marks = O.marks; R.mark_next = mark_next0; R.mark_D = mark_D0; R.ru = O.ru; R.lane_q = g.q;
-                careful_span(P, g.words, g.col, p0, c0, z0, g.end_bit, eof_lane ? g.seg_end_bit : 0xffffffffu, D_in, D_end, O.region, O.cap, R);
+                careful_span(P, g.words, g.col, p0, c0, z0, g.end_bit, (eof_lane || eof_crossed) ? g.seg_end_bit : 0xffffffffu, eof_lane,
+                             D_in, D_end, O.region, O.cap, R);
                 // the region and the lane's marks now have the careful pass's layout (one symbol per step word), error or not
                 li.n_ent = R.n;
                 npair = 0;

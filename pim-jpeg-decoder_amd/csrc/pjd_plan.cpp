@@ -85,7 +85,10 @@ static uint32_t min_step_bits_x256(const std::vector<std::pair<const pjd_huff_ta
     for (int u = 0; u < V; u++) for (int v = 0; v < V; v++) w[u][v] = INF;
     auto lower = [](uint32_t &dst, uint32_t bits) { if (bits < dst) dst = bits; };
     // the code after a symbol that stayed single is at least this long (a pair broken for another reason -- the lane ends -- happens once
-    // per lane: PJD_LANE_CAP's slack)
+    // per lane: PJD_LANE_CAP's slack).  A short code after it that stays out of the pair because its symbol is invalid (0xFF, an AC size
+    // > 10) is not modelled: that symbol is the reference's error, the decode stops there, and entries past the first error are never
+    // used (an overflow flagged behind it sends nothing to the exact kernel) -- at most one such step per lane before the error counts.
+    // tests/test_symbol_streams.py writes streams at this bound and brute-forces tiny tables with invalid symbols against it.
     auto need = [](uint32_t first_bits) { return first_bits >= 9 ? 1 : (int)(10 - first_bits); };
     for (size_t c = 0; c < combos.size(); c++) {
         bool seen = false;                               // Cb and Cr mostly share their tables: once is enough

@@ -252,6 +252,11 @@ def build_set():
     # over-subscribed table: three codes of one bit (reference generate_codes just keeps counting)
     counts = [3, 1, 2, 4] + [0] * 12
     S["huff_oversub_96x64_444"] = replace_dht(base, {(1, 0): (counts, ac_syms[:10])})
+    # --- hand-built entropy streams (tests/symbol_corpus.py): every symbol form, table shape and error class the reference's data-unit
+    #     decoder accepts, written symbol by symbol -- no encoder writes most of them
+    import symbol_corpus
+    for name, (data, _, _) in symbol_corpus.fixtures().items():
+        S[name] = data
     return S
 
 
