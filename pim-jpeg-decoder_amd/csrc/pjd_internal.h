@@ -66,7 +66,8 @@
 #ifndef PJD_IDCT_MAX_DU
 #define PJD_IDCT_MAX_DU    96       // data units staged in LDS per IDCT workgroup (<= PJD_IDCT_THREADS); with the group parser (round 3): 72 / 90 / 96 -> 0.59 / 0.53 / 0.525 ms on cfg3
 #endif
-#define PJD_COEF_SENTINEL  (-32768) // "slot 52 was visited with an explicit 0" (zigzag quirk)
+#define PJD_COEF_SENTINEL  (-32768) // at slot 52 of a baseline picture's dense scratch only: "slot 52 was visited with an explicit 0"
+                                    // (zigzag quirk); slot 0 (an absolute DC) and progressive pictures hold -32768 as a value
 
 // Bitstream words of one wave, transposed: row k holds big-endian word k of each of its 64 lanes, counted from
 // the lane's own first byte.  A lane reads at most 31 bits past its subsequence, holds three words and keeps two more in flight.

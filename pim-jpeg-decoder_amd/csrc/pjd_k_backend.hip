@@ -685,12 +685,15 @@ __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_colour(PjdDevBatc
         for (int j = 0; j < 8; j++) v[j] = rv[j];
         int16_t *t = tile[du];
         const uint16_t *q = qs[comp];
+        // the sentinel means "explicit zero" at slot 52 of a baseline picture only; everywhere else -32768 is a value (an
+        // absolute DC the int16 predictor reached, a progressive coefficient shifted by Al)
+        const bool zero52 = r == 6 && !(im.flags & PJD_IF_PROGRESSIVE) && v[4] == PJD_COEF_SENTINEL;
         if (r == 6 && !(im.flags & PJD_IF_STANDARD_ZIGZAG)) {
             // slots 48..55.  Natural position 38 is the target of slot 48 AND slot 52 (the
             // reference's zigzag_map[48] = 38): the later write wins, and an explicit zero
             // written at slot 52 (run/size symbol with size 0) is marked by the sentinel.
             const int v52 = v[4];
-            const int n38 = v52 != 0 ? (v52 == PJD_COEF_SENTINEL ? 0 : v52) : v[0];
+            const int n38 = v52 != 0 ? (zero52 ? 0 : v52) : v[0];
             t[38] = (int16_t)pjd_dequant(n38, q[38]);
             t[59] = (int16_t)pjd_dequant(v[1], q[59]);
             t[52] = (int16_t)pjd_dequant(v[2], q[52]);
@@ -703,7 +706,7 @@ __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_colour(PjdDevBatc
 #pragma unroll
             for (int j = 0; j < 8; j++) {
                 const uint32_t nat = (r == 6 && j == 0) ? 58u : c_zz[r * 8 + j];          // r == 6 here: PJD_IF_STANDARD_ZIGZAG
-                t[nat] = (int16_t)pjd_dequant(v[j] == PJD_COEF_SENTINEL ? 0 : v[j], q[nat]);
+                t[nat] = (int16_t)pjd_dequant(j == 4 && zero52 ? 0 : v[j], q[nat]);
             }
         }
     }

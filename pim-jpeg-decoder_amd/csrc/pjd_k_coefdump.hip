@@ -102,8 +102,9 @@ __global__ __launch_bounds__(64) void pjd_k_coefdump_lanes(PjdDevBatch B, uint32
     }
 }
 
-// Dense scratch of the exact kernel (zigzag-slot order, absolute DC, PJD_COEF_SENTINEL = explicit zero at slot 52) ->
-// reference layout.  One thread per data unit; `first_du` = image-relative index of the unit at scratch position 0.
+// Dense scratch of the exact kernel (zigzag-slot order, absolute DC, PJD_COEF_SENTINEL = explicit zero at slot 52 of a baseline
+// picture; -32768 in any other slot, or anywhere in a progressive picture, is a value) -> reference layout.  One thread per data
+// unit; `first_du` = image-relative index of the unit at scratch position 0.
 __global__ __launch_bounds__(256) void pjd_k_coefdump_dense(PjdDevBatch B, uint32_t image, const int16_t *__restrict__ scratch,
                                                             uint32_t first_du, uint32_t n_du, int16_t *__restrict__ out)
 {
@@ -113,10 +114,12 @@ __global__ __launch_bounds__(256) void pjd_k_coefdump_dense(PjdDevBatch B, uint3
     uint32_t comp;
     const size_t base = ref_unit_base(im, first_du + u, comp);
     const int16_t *src = scratch + (size_t)u * 64;
+    const bool sentinel = !(im.flags & PJD_IF_PROGRESSIVE);
     for (uint32_t z = 0; z < 64; z++) {      // ascending slots: a later slot overwrites an earlier one on the same position
         const int v = src[z];
         if (v == 0) continue;                // unvisited (or a zero that changes nothing: the buffer starts zeroed) ...
-        out[base + ref_natural(im, z)] = (int16_t)(v == PJD_COEF_SENTINEL ? 0 : v);      // ... except the explicit zero at slot 52
+        const bool zero52 = sentinel && z == 52 && v == PJD_COEF_SENTINEL;                  // ... except the explicit zero at slot 52
+        out[base + ref_natural(im, z)] = (int16_t)(zero52 ? 0 : v);
     }
 }
 

@@ -13,7 +13,8 @@
 // It is slow by construction (one dependent chain per image) and is never the fast path.
 //
 // Output: coefficients in zigzag-SLOT order (slot k of the D-th data unit decoded at coef[(dense_base+D)*64+k]),
-// absolute DC values in slot 0, and the PJD_COEF_SENTINEL mark for an explicit zero at slot 52.
+// absolute DC values in slot 0, and the PJD_COEF_SENTINEL mark for an explicit zero at slot 52.  The readers take the
+// mark at slot 52 only: an absolute DC of -32768 (the int16 predictor can reach it) stays a value.
 #include "pjd_device_common.h"
 #include "pjd_kernels.h"
 #include "../../include/pjd.h"

@@ -69,19 +69,29 @@ def wrap16(x):
 
 
 class Table:
-    """A DHT table as written: 16 counts and the symbols in code order (duplicates, 0xFF, anything -- up to 162)."""
+    """A DHT table as written: 16 counts and the symbols in code order (duplicates, 0xFF, anything -- up to 162).
 
-    def __init__(self, counts, symbols):
+    `oversubscribed=True` admits counts whose codes run out of their length, as the reference's generate_codes does (it keeps
+    counting): a code that no longer fits its length never matches (get_next_symbol compares whole codes), so its symbol cannot be
+    written, and the table is no prefix code the planner accepts."""
+
+    def __init__(self, counts, symbols, oversubscribed=False):
         counts, symbols = list(counts), list(symbols)
         assert len(counts) == 16 and sum(counts) == len(symbols) <= 162
         self.counts, self.symbols = counts, symbols
+        self.oversubscribed = False
         self.code_of = {}                  # symbol -> (length, code) of its FIRST occurrence
         self.codes = {}                    # (length, code) -> symbol
         code, q = 0, 0
         for ln in range(1, 17):
             for _ in range(counts[ln - 1]):
-                assert code < (1 << ln), "over-subscribed table"
-                self.codes[(ln, code)] = symbols[q]
+                if code >= (1 << ln):
+                    assert oversubscribed, "over-subscribed table"
+                    self.oversubscribed = True
+                    code += 1
+                    q += 1
+                    continue                   # a code that does not fit its length: the symbol cannot be written
+                self.codes.setdefault((ln, code), symbols[q])
                 self.code_of.setdefault(symbols[q], (ln, code))
                 code += 1
                 q += 1
@@ -118,12 +128,13 @@ class Component:
 class Frame:
     """width x height, components (luma first; only luma may be sampled 2x, as the reference requires), tables by id."""
 
-    def __init__(self, width, height, comps, dc, ac, qt=None, qt16=(), ri=0, standard_restart=False):
+    def __init__(self, width, height, comps, dc, ac, qt=None, qt16=(), ri=0, standard_restart=False, standard_zigzag=False):
         self.width, self.height, self.comps = width, height, comps
         self.dc, self.ac = dc, ac                                # {id: Table}
         self.qt = qt if qt is not None else {c.tq: list(range(1, 65)) for c in comps}     # {id: 64 values in zigzag order}
         self.qt16 = set(qt16)
         self.ri, self.standard_restart = ri, standard_restart
+        self.standard_zigzag = standard_zigzag                   # decoded with ITU T.81's map (PJD_F_STANDARD_ZIGZAG): not in the file
         self.hs, self.vs = comps[0].h, comps[0].v
         self.bw, self.bh = (width + 7) // 8, (height + 7) // 8                             # 8x8 blocks (the reference's mcu_w / mcu_h)
         self.bw_real = self.bw + (self.hs == 2 and self.bw % 2 == 1)
@@ -139,6 +150,21 @@ class Frame:
 
     def n_units(self):
         return len(self.mcus()) * len(self.unit_comps())
+
+    def sampling(self):
+        return {(1, 1, 1): "grey", (1, 1, 3): "444", (2, 1, 3): "422", (2, 2, 3): "420", (1, 2, 3): "440"}[(self.hs, self.vs, len(self.comps))]
+
+    def zigzag(self):
+        """Zigzag slot -> natural index of the map the frame is decoded with."""
+        return K_ZZ_T81 if self.standard_zigzag else K_ZZ
+
+    def quantiser(self, tq):
+        """Quantiser of each natural position, as the reference fills it from the DQT entries through the zigzag map (the later
+        entry wins at natural 38; natural 58 keeps 0 under the reference's map)."""
+        q = [0] * 64
+        for k, v in enumerate(self.qt[tq]):
+            q[self.zigzag()[k]] = v
+        return q
 
     def restarts_before(self):
         """MCU indices (in decode order) before which a restart happens: the reference's (y * Wr + x) % RI == 0 rule
@@ -304,6 +330,7 @@ def write(frame, units, eoi=True):
                 if size == 11:
                     it.forms.add("dc11_bits_zero" if b == 0 else "dc11_bits_ones" if b == (1 << 11) - 1 else "dc11")
                 raw = extend(size, b) + pred[c]
+                dc_wrapped = raw > 32767 or raw < -32768
                 if raw > 32767:
                     it.forms.add("dc_wrap_up")
                 if raw < -32768:
@@ -357,6 +384,7 @@ def write(frame, units, eoi=True):
             if toks[-1] != EOB:
                 it.forms.add("no_eob")
             it.n_decoded += 1
+            it.forms |= _edge_forms(f, it, u, c, m, dc_wrapped, rst)
     if not ended:
         assert len(units) == n_units, "fewer units than the frame has: end the stream with END or CUT"
     bits.pad()
@@ -379,6 +407,39 @@ def write(frame, units, eoi=True):
     return bytes(out), it
 
 
+INT16_EDGES = {-32768: "min", 32767: "max", -32767: "minp1"}
+COMP_NAMES = ["y", "cb", "cr"]
+
+
+def _edge_forms(f, it, u, c, m, dc_wrapped, rst):
+    """Forms of a decoded unit at the int16 edges: its absolute DC at -32768 / 32767 / -32767 (for -32768 also where and how it got
+    there), and natural positions whose dequantised value (int16)(coef * q) is one of those three."""
+    out = set()
+    dc = int(it.slots[u, 0])
+    if dc in INT16_EDGES:
+        out.add({"min": "dc_abs_min", "max": "dc_abs_max", "minp1": "dc_abs_min_plus1"}[INT16_EDGES[dc]])
+    if dc == -32768:
+        q = f.qt[f.comps[c].tq][0]
+        out |= {f"dc_abs_min_{COMP_NAMES[c]}", f"dc_abs_min_{f.sampling()}", "dc_abs_min_by_wrap" if dc_wrapped else "dc_abs_min_by_descent",
+                f"dc_abs_min_q{q}_{16 if f.comps[c].tq in f.qt16 else 8}bit", f"dc_abs_min_q_{'odd' if q % 2 else 'even'}"}
+        if u == f.n_units() - 1:
+            out.add("dc_abs_min_last_unit")
+        if any(r <= m for r in rst):
+            out.add("dc_abs_min_after_restart")
+        if it.visited[u, 52]:
+            out.add("dc_abs_min_value52" if it.slots[u, 52] else "dc_abs_min_zero52")
+    zz, q = f.zigzag(), f.quantiser(f.comps[c].tq)
+    src = {}
+    for k in np.flatnonzero(it.visited[u]):          # slot order: the later slot wins a shared natural position
+        src[zz[k]] = k
+    for n, k in src.items():
+        v = int(it.slots[u, k])
+        p = wrap16(v * q[n])
+        if v and p in INT16_EDGES:
+            out.add(f"deq_{INT16_EDGES[p]}_nat{n}" + (f"_slot{k}" if n == 38 else ""))
+    return out
+
+
 def _token_bits(t, table):
     """-> (bit string, code length) of a DC / AC / EOB token (no value bits for an out-of-range size or symbol 0xFF)."""
     if t[0] == "EOB":
@@ -399,6 +460,7 @@ def _token_bits(t, table):
 # zigzag slot -> natural index, with the reference's entry 48 = 38 (src/headers/common.h:9-18)
 K_ZZ = [0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
         35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 38, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63]
+K_ZZ_T81 = K_ZZ[:48] + [58] + K_ZZ[49:]          # ITU T.81 (PJD_F_STANDARD_ZIGZAG): slot 48 -> natural 58
 
 
 def unit_offsets(frame):
@@ -424,9 +486,10 @@ def n_dpus(frame):
 
 def intent_buffer(frame, intent):
     """The intent in the reference's MCU_buffer layout: each unit's visited slots written in slot order (so an explicit 0 at slot 52
-    overwrites natural 38 after slot 48 did)."""
+    overwrites natural 38 after slot 48 did), through the frame's zigzag map."""
     buf = np.zeros(n_dpus(frame) * 19200, np.int16)
+    zz = frame.zigzag()
     for u, off in enumerate(unit_offsets(frame)):
         for k in np.flatnonzero(intent.visited[u]):
-            buf[off + K_ZZ[k]] = intent.slots[u, k]
+            buf[off + zz[k]] = intent.slots[u, k]
     return buf.reshape(-1, 19200)

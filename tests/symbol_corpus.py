@@ -202,7 +202,206 @@ def plant(fr, units, u, cls, rng, keep_n=None, pick=None):
     return units
 
 
+def ac_oversub():
+    """ac_general with two more 16-bit codes than fit (the reference's generate_codes keeps counting; those two never match): a table
+    the planner refuses, so the picture goes to the literal kernel.  The 16-bit codes that fit decode to 0x01."""
+    t = ac_general()
+    code = 0
+    for ln in range(1, 17):
+        code = (code + t.counts[ln - 1]) << (1 if ln < 16 else 0)
+    extra = (1 << 16) - code + 2
+    return Table(t.counts[:15] + [t.counts[15] + extra], t.symbols + [0x01] * extra, oversubscribed=True)
+
+
 GENERAL = ({0: dc_general(), 1: dc_general()}, {0: ac_general(), 1: ac_162()})
+
+
+# ---- int16 edges -----------------------------------------------------------------------------------------------------------------
+# The exact kernels keep an absolute DC in slot 0 of the dense scratch and mark an explicit zero at slot 52 with -32768: a DC of
+# exactly -32768 (the int16 predictor reaches it) must stay a value.  These streams put absolute DCs at -32768, 32767 and -32767 in
+# every component and sampling, at the last unit, after a restart and beside either kind of slot 52, and AC values whose dequantised
+# product (int16)(c * q) is one of those three at natural positions 0, 1, 38 (from slot 48 and from slot 52), 58 (T.81 map) and 63.
+ZERO52 = [acv(15, 3), acv(15, -3), acv(15, 9), AC(3, 0), EOB]           # slot 48 = 9, then an explicit 0 at slot 52
+VALUE52 = [acv(15, 3), acv(15, -3), acv(15, -9), acv(3, 77), EOB]       # slot 48 = -9, then 77 at slot 52
+
+
+def _split(d, n):
+    """n DC differences (each within +-2047, zeros first) that add up to d."""
+    full, rem = divmod(abs(d), 2047)
+    s = 1 if d >= 0 else -1
+    steps = [s * 2047] * full + ([s * rem] if rem else [])
+    assert len(steps) <= n, (d, n)
+    return [0] * (n - len(steps)) + steps
+
+
+def dc_script(fr, anchors):
+    """DC difference of every data unit (decode order) that takes component c's absolute DC to each anchor: anchors[c] lists
+    (k, value, route) for the k-th unit of component c; route "wrap" goes there across the int16 wrap, anything else directly.
+    The predictor restarts at 0 after every restart marker; units after an anchor keep its value until the next one."""
+    per, rst = fr.unit_comps(), fr.restarts_before()
+    seq, seg = {c: [] for c in range(len(fr.comps))}, 0
+    for u in range(fr.n_units()):
+        m, j = divmod(u, len(per))
+        seg += j == 0 and m in rst
+        seq[per[j]].append((u, seg))
+    diffs = [0] * fr.n_units()
+    for c, anc in anchors.items():
+        units, pred, nxt, pseg = seq[c], 0, 0, 0
+        for k, t, route in sorted(anc):
+            if units[k][1] != pseg:                   # a restart since the last anchor: the predictor starts again at 0
+                pred, pseg = 0, units[k][1]
+                nxt = min(i for i in range(k + 1) if units[i][1] == pseg)
+            d = t - pred
+            if route == "wrap":
+                d += 65536 if d < 0 else -65536
+            for i, s in zip(range(nxt, k + 1), _split(d, k - nxt + 1)):
+                diffs[units[i][0]] = s
+            pred, nxt = t, k + 1
+    return diffs
+
+
+def _chain(k0, wrap_first):
+    """Anchors over >= 21 units of a component from its k0-th: -32768 straight down (16 x -2047, then -16), -32767, -32768, 32767
+    (down across the wrap), -32768 (up across the wrap); or first up to 32767 and across the wrap to -32768, -32767, -32768."""
+    if wrap_first:
+        return [(k0 + 16, 32767, "direct"), (k0 + 17, -32768, "wrap"), (k0 + 18, -32767, "direct"), (k0 + 19, -32768, "direct")]
+    return [(k0 + 16, -32768, "direct"), (k0 + 17, -32767, "direct"), (k0 + 18, -32768, "direct"), (k0 + 19, 32767, "wrap"),
+            (k0 + 20, -32768, "wrap")]
+
+
+def edge_anchors(fr):
+    """A _chain at the start of every restart segment that holds >= 21 units of a component (the two kinds in turn); every chain
+    ends at -32768 and the value stays, so the last unit of each such segment -- the picture's last unit among them -- is -32768."""
+    per, rst = fr.unit_comps(), fr.restarts_before()
+    segs = {c: [] for c in range(len(fr.comps))}
+    seg = 0
+    for u in range(fr.n_units()):
+        m, j = divmod(u, len(per))
+        seg += j == 0 and m in rst
+        segs[per[j]].append(seg)
+    anchors = {}
+    for c, ss in segs.items():
+        starts = [k for k in range(len(ss)) if k == 0 or ss[k] != ss[k - 1]]
+        anchors[c] = [a for n, k0 in enumerate(starts) if ss.count(ss[k0]) >= 21 for a in _chain(k0, (n + c) % 2 == 1)]
+        assert anchors[c], "no restart segment holds 21 units of a component"
+    return anchors
+
+
+def edge_frame(w, h, sub, q_dc, qt16, ri=0, std=False, ac=None):
+    """A frame of the general tables whose DC quantiser (zigzag entry 0 of every table) is q_dc."""
+    dc, _ = GENERAL
+    fr = frame(w, h, sub, dc, ac or {0: ac_general(), 1: ac_general()}, ri=ri, std=std, qt16=qt16)
+    for t in fr.qt:
+        fr.qt[t][0] = q_dc
+    return fr
+
+
+def dc_edge_units(fr, rng):
+    """Units of `fr` that follow dc_script(edge_anchors(fr)); the anchored units alternate an explicit zero and a value at slot 52."""
+    anchors = edge_anchors(fr)
+    diffs = dc_script(fr, anchors)
+    per = fr.unit_comps()
+    comp_k = {c: [u for u in range(fr.n_units()) if per[u % len(per)] == c] for c in range(len(fr.comps))}
+    marked = sorted(comp_k[c][k] for c, anc in anchors.items() for k, _, _ in anc)
+    units = []
+    for u in range(fr.n_units()):
+        dct, act = tables_of(fr, u)
+        body = random_unit(rng, dct, act)[1:]
+        if u in marked:
+            body = list(ZERO52 if marked.index(u) % 2 == 0 else VALUE52)
+        units.append([dcv(diffs[u])] + body)
+    return units
+
+
+# name -> (width, height, sampling, DC quantiser, 16-bit DQT, restart interval, T.81 restart rule, AC table).  Every colour frame
+# has >= 21 MCUs per restart segment, so that each chroma chain fits.
+DC_EDGE_FRAMES = {
+    "sym_edge_dc_grey_q1_ri24": (64, 48, "grey", 1, False, 24, False, None),
+    "sym_edge_dc_444_q3_ri21": (56, 48, "444", 3, False, 21, False, None),
+    "sym_edge_dc_420_q65535": (112, 48, "420", 65535, True, 0, False, None),
+    "sym_edge_dc_422_q32768": (112, 24, "422", 32768, True, 0, False, None),
+    "sym_edge_dc_440_q2": (56, 48, "440", 2, False, 0, False, None),
+    # not committed (the planner routes them, or they differ only in a quantiser): the edge family of the GPU tests and the corpus
+    "sym_edge_dc_444_q32767": (56, 24, "444", 32767, True, 0, False, None),
+    "sym_edge_dc_grey_q2_ri21": (8, 8 * 42, "grey", 2, False, 21, False, None),
+    "sym_edge_dc_420_q1_ri21_refrule": (112, 96, "420", 1, False, 21, False, None),      # subsampled luma + DRI: routed up front
+    "sym_edge_dc_420_q3_ri21_std": (112, 96, "420", 3, False, 21, True, None),
+    "sym_edge_dc_422_q1_ri21_refrule": (112, 48, "422", 1, False, 21, False, None),
+    "sym_edge_dc_440_q65535_ri21_std": (56, 96, "440", 65535, True, 21, True, None),
+    "sym_edge_dc_444_q3_oversub": (56, 24, "444", 3, False, 0, False, "oversub"),         # a table the planner refuses: literal kernel
+}
+COMMITTED_EDGE = ["sym_edge_dc_grey_q1_ri24", "sym_edge_dc_444_q3_ri21", "sym_edge_dc_420_q65535", "sym_edge_dc_422_q32768",
+                  "sym_edge_dc_440_q2", "sym_edge_deq_444"]
+
+
+def deq_edge_frame(standard_zigzag=False):
+    """4:4:4, a 16-bit quantisation table per component: Y 32768 everywhere (an odd coefficient -> -32768) but 64 at natural 38 (zigzag
+    entry 52 under either map: +-512 -> -32768); Cb 32767 (1 -> 32767, -1 -> -32767, a DC of -32768 -> -32768); Cr 32769 (1 -> -32767,
+    -1 -> 32767).  Under T.81's map (standard_zigzag) slot 48 lands on natural 58 with Y's 32768."""
+    dc, _ = GENERAL
+    y = [32768] * 64
+    y[52] = 64
+    return Frame(40, 32, [Component(1, 1, t, 0, 0) for t in range(3)], {0: dc[0]}, {0: ac_162()},
+                 qt={0: y, 1: [32767] * 64, 2: [32769] * 64}, qt16={0, 1, 2}, standard_zigzag=standard_zigzag)
+
+
+def deq_edge_units(fr):
+    """Per unit: DC, slot 1, slot 48, a slot 52 in every other MCU, slot 63 (no EOB).  The coefficients cycle through values whose
+    products land on the edges under the unit's table; Cb's DC goes down to -32768 at its 19th unit."""
+    per = fr.unit_comps()
+    n_mcu = len(fr.mcus())
+    anchors = {0: [(k, [1, -1, 3, -3][k % 4], "direct") for k in range(n_mcu)],
+               1: [(0, 1, "direct"), (1, -1, "direct"), (18, -32768, "direct")],
+               2: [(k, [1, -1][k % 2], "direct") for k in range(n_mcu)]}
+    diffs = dc_script(fr, anchors)
+    vals = {0: [1, -1, 3, 512, -512, 7], 1: [1, -1, 1, -1, 1, -1], 2: [1, -1, -1, 1, 1, -1]}
+    units = []
+    for u in range(fr.n_units()):
+        c, m = per[u % len(per)], u // len(per)
+        vv = vals[c]
+        body = [acv(0, vv[m % 6]), AC(15, 0), AC(15, 0), acv(14, vv[(m + 3) % 6])]       # slots 1 and 48
+        if m % 2:
+            body += [acv(3, vv[(m + 4) % 6]), acv(10, vv[(m + 1) % 6])]                  # slots 52 and 63
+        else:
+            body += [acv(14, vv[(m + 1) % 6])]                                              # slot 63
+        units.append([dcv(diffs[u])] + body)
+    return units
+
+
+def edge_family():
+    """{name: (jpeg, frame, intent)}: every int16-edge stream (COMMITTED_EDGE among them)."""
+    rng = np.random.default_rng(32768)
+    F = {}
+    for name, (w, h, sub, q, q16, ri, std, act) in DC_EDGE_FRAMES.items():
+        ac = {0: ac_oversub(), 1: ac_general()} if act == "oversub" else None
+        fr = edge_frame(w, h, sub, q, q16, ri=ri, std=std, ac=ac)
+        F[name] = (*write(fr, dc_edge_units(fr, rng)), fr)
+    for name, std in [("sym_edge_deq_444", False), ("sym_edge_deq_444_t81", True)]:
+        fr = deq_edge_frame(std)
+        F[name] = (*write(fr, deq_edge_units(fr)), fr)
+    return {n: (d, fr, it) for n, (d, it, fr) in F.items()}
+
+
+def edge_variants(rng, n):
+    """Seeded variants of the DC family for the corpus: sampling, size, quantiser, table precision and restart layout drawn at random."""
+    out = []
+    for k in range(n):
+        sub = str(rng.choice(list(SAMPLINGS)))
+        mw, mh = 8 * SAMPLINGS[sub][0][0], 8 * SAMPLINGS[sub][0][1]
+        q = int(rng.choice([1, 3, 255, 32767, 65535, 2, 32768]))
+        ri = int(rng.choice([0, 21, 25]))
+        per_row = int(rng.integers(1, 9))
+        rows = -(-max(ri, 21) * int(rng.integers(1, 3)) // per_row) + int(rng.integers(0, 2))
+        w, h = per_row * mw - int(rng.integers(0, mw // 2)), rows * mh - int(rng.integers(0, mh // 2))
+        std = bool(ri and rng.random() < 0.5)
+        fr = edge_frame(w, h, sub, q, q > 255 or bool(rng.random() < 0.3), ri=ri, std=std)
+        try:
+            units = dc_edge_units(fr, rng)
+        except AssertionError:
+            continue                              # a restart layout without a segment of 21 units of some component
+        data, it = write(fr, units)
+        out.append((f"edge{k}:{sub}:{w}x{h}:q{q}:ri{ri}{':std' if std else ''}", data, fr, it))
+    return out
 
 
 # ---- the fixtures ------------------------------------------------------------------------------------------------------------------
@@ -296,6 +495,12 @@ def fixtures():
     fr = frame(40, 16, "444", dc, ac)
     units = fill(fr, rng)[:17] + [[END]]
     add("sym_err_end_on_unit_boundary_444", fr, units)
+
+    # int16 edges: absolute DCs of -32768 / 32767 / -32767 and dequantised products at those values (the rest of the family: corpus())
+    edge = edge_family()
+    for name in COMMITTED_EDGE:
+        assert len(edge[name][0]) < 2048, name
+        F[name] = edge[name]
     return F
 
 
@@ -337,6 +542,8 @@ def corpus(n=300, seed=31337):
             continue                           # the planted form does not exist with these tables / at this bit position
         n_planted += ":err" in label
         out.append((label, data, fr, it))
+    out += [(name, *x) for name, x in edge_family().items() if name not in COMMITTED_EDGE]
+    out += edge_variants(np.random.default_rng(seed + 1), 12)
     return out
 
 
@@ -360,6 +567,8 @@ def _second_level_bytes(t):
 def tables_fit(fr):
     """Does the parallel decoder take the frame's tables?  One slot per distinct AC table, one per distinct (DC table, AC slot)."""
     key = lambda t: (tuple(t.counts), tuple(t.symbols))
+    if any(t.oversubscribed for c in fr.comps for t in (fr.dc[c.td], fr.ac[c.ta])):
+        return False                           # not a prefix code: the planner gives it no decode table
     ac_slots, dc_slots = [], []
     for c in fr.comps:
         a = key(fr.ac[c.ta])

@@ -60,13 +60,25 @@ def test_dpu_payload_random_blocks(ctx, port):
             meta[7:7 + ncomp] = rng.integers(0, 4, ncomp)
             meta[20:] = rng.integers(1, 70000, 256)
             amp = int(rng.choice([40, 1200, 32767]))
-            coef = rng.integers(-amp, amp + 1, (n, 19200)).astype(np.int16)
+            coef = rng.integers(-amp - (amp == 32767), amp + 1, (n, 19200)).astype(np.int16)     # the full int16 range at 32767
             want = coef.copy()
             for d in range(n):
                 port.dpu_exec(meta, want[d])
             got = coef.copy()
             ctx.exec_dpu_payload(np.tile(meta, (n, 1)), got)
             assert np.array_equal(got, want), (V, H, ncomp)
+    # -32768 in every position, with odd and even quantisers ((int16)(-32768 * q) is -32768 for odd q, 0 for even q)
+    for q in (1, 3, 32767, 65535, 2, 32768):
+        meta = np.zeros(276, np.uint32)
+        meta[4], meta[5], meta[6], meta[19] = 3, 2, 2, 100
+        meta[20:] = q
+        coef = np.full((2, 19200), -32768, np.int16)
+        want = coef.copy()
+        for d in range(2):
+            port.dpu_exec(meta, want[d])
+        got = coef.copy()
+        ctx.exec_dpu_payload(np.tile(meta, (2, 1)), got)
+        assert np.array_equal(got, want), q
 
 
 # ---- the whole path: JPEG bytes -> pictures -------------------------------------------------

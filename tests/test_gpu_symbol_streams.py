@@ -36,7 +36,8 @@ def _scan(items, force_sequential=False):
     for label, data, fr, it in items:
         s = pjd_amd.Scanned(data)
         assert s.valid, label
-        s.desc.flags = (pjd_amd.F_STANDARD_RESTART if fr.standard_restart else 0) | (pjd_amd.F_FORCE_SEQUENTIAL if force_sequential else 0)
+        s.desc.flags = ((pjd_amd.F_STANDARD_RESTART if fr.standard_restart else 0) | (pjd_amd.F_FORCE_SEQUENTIAL if force_sequential else 0)
+                        | (pjd_amd.F_STANDARD_ZIGZAG if fr.standard_zigzag else 0))
         scanned.append(s)
     return scanned
 
@@ -52,9 +53,13 @@ def _decode_and_check(ctx, port, items, scanned, check_routing=True):
             want = J.intent_buffer(fr, it)
             bad = np.argwhere(coef != want)
             assert bad.size == 0, (label, "coefficients differ from the intent at", bad[:4].tolist())
-            assert np.array_equal(outs[k], intent_rgb(port, data, fr, it)), label
-            if not (fr.standard_restart and fr.ri and (fr.hs, fr.vs) != (1, 1)):
-                assert np.array_equal(outs[k], port.decode(data)["rgb"]), label
+            port.standard_zigzag(fr.standard_zigzag)            # a frame decoded with T.81's map (PJD_F_STANDARD_ZIGZAG)
+            try:
+                assert np.array_equal(outs[k], intent_rgb(port, data, fr, it)), label
+                if not (fr.standard_restart and fr.ri and (fr.hs, fr.vs) != (1, 1)):
+                    assert np.array_equal(outs[k], port.decode(data)["rgb"]), label
+            finally:
+                port.standard_zigzag(False)
     if check_routing:
         assert info["n_sequential"] == sum(SC.expect_sequential(fr, it) for _, _, fr, it in items), info["n_sequential"]
         assert info["n_fallback"] == 0, info["flag_waves"]

@@ -29,7 +29,11 @@ FIXTURE_NAMES = sorted(SC.fixtures())
 
 
 def check_port(port, data, fr, it, label):
-    o = port.decode(data)
+    port.standard_zigzag(fr.standard_zigzag)          # the frame is decoded with T.81's map (PJD_F_STANDARD_ZIGZAG)
+    try:
+        o = port.decode(data)
+    finally:
+        port.standard_zigzag(False)
     assert o["valid"], label
     assert o["huff_rc"] == it.status, (label, o["huff_rc"], it.status)
     want = J.intent_buffer(fr, it)
@@ -61,6 +65,7 @@ def test_live_reference_equals_port(port, live_ref, tmp_path):
     if live_ref is None:
         pytest.skip("oracle/_ref not built (the fixtures' manifest entries pin the port to it)")
     items = [(n, d) for n, (d, _, _) in fixtures().items()] + [(lab, d) for lab, d, _, _ in corpus()[::3]]
+    items += [(n, d) for n, (d, _, _) in SC.edge_family().items() if n not in SC.COMMITTED_EDGE]     # every int16-edge stream
     for k, (label, data) in enumerate(items):
         jp, bp = tmp_path / f"s{k}.jpg", tmp_path / f"s{k}.bmp"
         jp.write_bytes(data)
@@ -80,7 +85,14 @@ REQUIRED_FORMS = (
        "dc11_bits_zero", "dc11_bits_ones", "dc_wrap_up", "dc_wrap_down", "ac10_1023", "ac10_-1023", "ac10_512", "ac10_-512",
        "mostly_ones", "restart", "raw_dc", "raw_ac", "dc_sym_ff", "ac_sym_ff", "cut_in_code", "cut_in_dc_bits", "cut_in_ac_bits",
        "end_at_unit_boundary"]
-    + [f"dc_size_{s}" for s in range(12, 16)] + [f"ac_size_{s}" for s in range(11, 16)])
+    + [f"dc_size_{s}" for s in range(12, 16)] + [f"ac_size_{s}" for s in range(11, 16)]
+    # int16 edges: absolute DCs at -32768 (in every component and sampling, both ways, at the last unit, after a restart, beside
+    # either kind of slot 52, odd and even DC quantisers in 8- and 16-bit tables), 32767 and -32767; dequantised products at the edges
+    + ["dc_abs_min", "dc_abs_max", "dc_abs_min_plus1", "dc_abs_min_by_descent", "dc_abs_min_by_wrap", "dc_abs_min_last_unit",
+       "dc_abs_min_after_restart", "dc_abs_min_zero52", "dc_abs_min_value52", "dc_abs_min_q_odd", "dc_abs_min_q_even"]
+    + [f"dc_abs_min_{c}" for c in ("y", "cb", "cr")] + [f"dc_abs_min_{s}" for s in ("grey", "444", "422", "420", "440")]
+    + [f"dc_abs_min_q{q}_{b}bit" for q, b in [(1, 8), (3, 8), (2, 8), (32767, 16), (65535, 16), (32768, 16)]]
+    + [f"deq_{e}_nat{n}" for e in ("min", "max", "minp1") for n in ("0", "1", "38_slot48", "38_slot52", "58", "63")])
 
 
 def test_coverage_of_forms_statuses_tables_and_frames():
