@@ -18,6 +18,8 @@
  *   the per-DPU payload T0    decoder_dpu.c:57-58       pjd_exec_dpu_payload (literal)
  *   (none: an addition)                                 PJD_F_SCALE_* + pjd_image_output_size: pictures out at
  *                                                       1/2, 1/4 or 1/8 scale (libjpeg scale_num/scale_denom)
+ *   (none: an addition)                                 PJD_OUT_RGB8_PLANAR + pjd_batch_bind_output: pictures as planar
+ *                                                       R, G, B channels in device memory the caller owns (tensors)
  *
  * Plain pointers and sizes only; no C++ or torch types.  Thread model: one
  * submitting thread per pjd_ctx (the reference has one consumer thread,
@@ -69,6 +71,12 @@ extern "C" {
 #define PJD_OUT_BMP    1   /* the complete file image bmp_writer.cpp:19-67 would emit:
                               26-byte BITMAPCOREHEADER file header, bottom-up B,G,R rows,
                               (W % 4) zero bytes after each row                               */
+#define PJD_OUT_RGB8_PLANAR 2  /* planar channels, uint8[3][H][W] ("CHW"): the R plane, then the G plane, then
+                              the B plane, each H top-down rows of W bytes, no padding: 3*W*H bytes (W, H
+                              at the output scale).  Byte (c, y, x) is byte (y, x, c) of the PJD_OUT_RGB8
+                              picture of the same descriptor; everything else (status words, partial
+                              pictures, shards, coefficients) is as for PJD_OUT_RGB8.  A one-component
+                              JPEG gives three equal planes.                                      */
 
 /* ---- descriptor flags ----------------------------------------------------- */
 #define PJD_F_STANDARD_RESTART  1u  /* restart at every `restart_interval`-th MCU (ITU T.81).
@@ -249,6 +257,28 @@ int  pjd_batch_download(pjd_batch *b, uint8_t *const *out, int32_t *status);
 int  pjd_batch_download_packed(pjd_batch *b, uint8_t *host, uint64_t capacity, int32_t *status);
 uint64_t pjd_batch_packed_size(pjd_batch *b);
 uint64_t pjd_batch_output_offset(pjd_batch *b, int image);
+/* After pjd_batch_create and before the first pjd_batch_upload / _capture / _decode of this batch (else PJD_E_STATE):
+ * pictures are written into caller-owned device memory instead of a buffer of the batch.  Picture i occupies
+ * [base + offsets[i], + pjd_batch_output_size(b, i)); offsets == NULL means the packed layout (pjd_batch_output_offset as
+ * reported before the call).  No alignment is required of base or of any offset.
+ * PJD_E_ARG for a PJD_OUT_BMP batch (its row padding relies on the library zeroing its own buffer), a pointer that is not
+ * device memory of the context's device, a `capacity` that reaches past the end of the allocation the pointer lies in (where the
+ * runtime can tell), a picture range that ends beyond `capacity`, two picture ranges that overlap.
+ * The batch's own output buffer goes back to the context's pool (pjd_batch_info::device_bytes shrinks by its size).  The
+ * library never frees, zeroes or reads the caller's memory: it writes pictures into it -- no byte outside the picture ranges,
+ * and every decode writes every byte of every unsharded picture's range, so the memory may be recycled between decodes -- and
+ * copies from it in pjd_batch_download.  pjd_batch_device_output / pjd_batch_output_offset report the bound addresses /
+ * offsets; pjd_batch_download_packed works with the packed layout only (explicit offsets: PJD_E_STATE); a captured graph
+ * records the bound addresses.  Work is issued on pjd_stream(ctx) as always, a stream without implicit order to any other: the
+ * caller orders its own streams against it, both ways.  Before upload / decode: whatever still reads or writes the memory on the
+ * caller's streams must have finished (or pjd_stream(ctx) made to wait for it).  After a decode: pjd_batch_sync (or a download)
+ * before the pictures are read or the memory reused -- only there are the status words read back and the pictures the parallel
+ * decoder gave up on decoded again by the exact kernel (pjd_batch_info::n_fallback), into the same memory.  An event recorded on
+ * pjd_stream(ctx) after pjd_batch_decode orders the kernels of that decode alone: it is enough only for a batch whose decodes
+ * need no such fallback (n_fallback == 0, e.g. known from an earlier pjd_batch_sync of the same batch).
+ * Where the memory comes from a sub-allocator (torch's caching allocator), "the allocation" above is the allocator's whole
+ * segment: that check catches a wild capacity, it does not prove that the range is the caller's own tensor.                    */
+int  pjd_batch_bind_output(pjd_batch *b, void *device_base, uint64_t capacity, const uint64_t *offsets);
 int  pjd_batch_get_info(pjd_batch *b, pjd_batch_info *info);
 uint64_t pjd_batch_output_size(pjd_batch *b, int image);
 void *pjd_batch_device_output(pjd_batch *b, int image);      /* device pointer (HBM)          */

@@ -49,7 +49,7 @@ typedef void (*pjd_pipe_sink)(void *user, int index, const char *name, const cha
 
 typedef struct pjd_pipe_opts {
     int32_t device;          /* HIP device ordinal                                             */
-    int32_t out_format;      /* PJD_OUT_BMP / PJD_OUT_RGB8                                     */
+    int32_t out_format;      /* PJD_OUT_BMP / PJD_OUT_RGB8 / PJD_OUT_RGB8_PLANAR (pjd.h)         */
     int32_t batch_images;    /* inputs per GPU batch               (0 -> 1024)                 */
     int32_t scan_threads;    /* JPEG scanner workers               (0 -> 4)                    */
     int32_t slots;           /* GPU batches in flight              (0 -> 3)                    */

@@ -121,6 +121,13 @@ int pool_dev_alloc(pjd_ctx *ctx, void **out, size_t bytes, std::vector<PoolBlock
     return PJD_OK;
 }
 
+std::string fmt_image(const char *f, int i)
+{
+    char buf[160];
+    std::snprintf(buf, sizeof buf, f, i);
+    return buf;
+}
+
 int pool_pin_alloc(pjd_ctx *ctx, void **out, size_t bytes, std::vector<PoolBlock> &owned)
 {
     if (bytes == 0) bytes = 16;
@@ -174,6 +181,10 @@ struct pjd_batch {
     hipGraph_t graph_groups = nullptr;           // the same decode with the picture groups' chains as parallel branches (pjd_internal.h)
     hipGraphExec_t graph_exec_groups = nullptr;
     bool counted = false;                        // this batch's decode is counted in g_active[device]
+    // pjd_batch_bind_output: dev.out is the caller's memory (never freed, zeroed or pooled here)
+    bool bound = false, bound_offsets = false;   // bound_offsets: the caller chose the picture offsets (no packed download)
+    uint64_t bound_capacity = 0;
+    std::vector<uint64_t> packed_off;            // the planner's picture offsets (the packed layout), kept for a second bind
 };
 
 extern "C" {
@@ -405,7 +416,9 @@ int pjd_batch_upload(pjd_batch *b)
     hipStream_t s = ctx->stream;
     // asynchronous: the blob is page-locked and owned by the batch
     HIP_TRY(ctx, hipMemcpyAsync(b->d_in, b->h_in, b->in_bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(ctx, hipMemsetAsync(b->dev.out, 0, P.out_buf_bytes, s));   // BMP row padding stays zero
+    // BMP row padding stays zero.  RGB8 and planar pictures are written whole by every decode, which is what a bound buffer
+    // (pjd_batch_bind_output: the caller's memory, never BMP) relies on: it is not touched here.
+    if (!b->bound) HIP_TRY(ctx, hipMemsetAsync(b->dev.out, 0, P.out_buf_bytes, s));
     b->uploaded = true;
     return PJD_OK;
 }
@@ -490,12 +503,14 @@ int enqueue_decode(pjd_batch *b, pjd_timings *timings, bool use_groups)
     //            entropy decoder's chains and stretch them -- 3.4-3.5 ms per batch against 2.6-2.7 for "groups" and 2.9 for "chain"
     //            (profiles/r04_experiments.md #16); kept as an experiment switch
     //   "chain"  as with several batches in flight: one chain of launches
-    // A batch that holds pictures with an output scale (PJD_F_SCALE_*) takes "groups" instead of "pull": the pull launch has no scaled form.
+    // A batch that holds pictures with an output scale (PJD_F_SCALE_*), and a planar batch (PJD_OUT_RGB8_PLANAR), take "groups" instead of
+    // "pull": the pull launch has no scaled and no planar form.
     static const int idle_form = [] { const char *e = std::getenv("PJD_IDLE_FORM"); return !e ? 1 : (!std::strcmp(e, "pull") ? 2 : (!std::strcmp(e, "chain") ? 0 : 1)); }();
     const bool idle = !timings && use_groups && parallel && !P.groups.empty() && idle_form != 0;       // per-kernel timing: one chain, kernel after kernel
-    const size_t ng = (idle && (idle_form == 1 || P.scaled)) ? P.groups.size() : 0;
+    const bool no_pull = P.scaled || P.planar;
+    const size_t ng = (idle && (idle_form == 1 || no_pull)) ? P.groups.size() : 0;
     const bool grouped = ng > 1 && ctx_group_streams(ctx, ng);
-    if (idle && idle_form == 2 && !P.scaled && ctx_group_streams(ctx, 2)) {
+    if (idle && idle_form == 2 && !no_pull && ctx_group_streams(ctx, 2)) {
         // The pull back end (pjd_internal.h): entropy decode on the context's stream, the back end's pull launch on a second stream
         // beside it (inside a capture: two parallel one-node branches), then the sweep over whatever the pull launch left.
         PjdDevBatch dv = b->dev;
@@ -525,7 +540,7 @@ int enqueue_decode(pjd_batch *b, pjd_timings *timings, bool use_groups)
             pjd_launch_lane_words_group(gs, b->dev, P.groups[g]);
             pjd_launch_huff_lanes_group(gs, b->dev, P.groups[g], (uint32_t)g);
             pjd_launch_group_dc(gs, b->dev, P.groups[g]);
-            pjd_launch_group_idct(gs, b->dev, P.groups[g], P.scaled);
+            pjd_launch_group_idct(gs, b->dev, P.groups[g], P.scaled, P.planar);
             if (g) { HIP_TRY(ctx, hipEventRecord(ctx->join_ev[g - 1], gs)); }
         }
         for (size_t g = 1; g < ng; g++) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->join_ev[g - 1], 0));
@@ -535,7 +550,7 @@ int enqueue_decode(pjd_batch *b, pjd_timings *timings, bool use_groups)
             pjd_launch_lane_words(s, b->dev);    kt.mark("lane_words");
             pjd_launch_huff_lanes(s, b->dev);    kt.mark("huff_lanes");
             pjd_launch_lane_dc_scan(s, b->dev);  kt.mark("dc_scan");
-            pjd_launch_idct_colour_lanes(s, b->dev, P.scaled);
+            pjd_launch_idct_colour_lanes(s, b->dev, P.scaled, P.planar);
             kt.mark("idct_colour");
         }
     }
@@ -544,7 +559,7 @@ int enqueue_decode(pjd_batch *b, pjd_timings *timings, bool use_groups)
         pjd_launch_zero(s, b->dev.coef, P.dense_du * 64 * sizeof(int16_t));      // a kernel, not a memset node: see the reset above
         pjd_launch_huff_sequential(s, b->dev, b->d_seq_list, b->d_seq_base, (uint32_t)b->seq_list.size());
         if (!P.pscans.empty()) pjd_launch_progressive(s, b->dev, b->d_seq_list, b->d_seq_base, (uint32_t)b->seq_list.size());
-        pjd_launch_idct_colour(s, b->dev, b->d_iwgs_dense, b->d_seq_base, (uint32_t)P.iwgs_dense.size(), P.scaled);
+        pjd_launch_idct_colour(s, b->dev, b->d_iwgs_dense, b->d_seq_base, (uint32_t)P.iwgs_dense.size(), P.scaled, P.planar);
         kt.mark("exact_path");
     }
     HIP_TRY(ctx, hipGetLastError());
@@ -624,7 +639,7 @@ int settle(pjd_batch *b)
         if (e == hipSuccess) {
             if (ev0) (void)hipEventRecord(ev0, s);
             pjd_launch_huff_sequential(s, dv, d_list, d_base, (uint32_t)fb.size());
-            pjd_launch_idct_colour(s, dv, d_wgs, d_base, (uint32_t)fb_wgs.size(), P.scaled);
+            pjd_launch_idct_colour(s, dv, d_wgs, d_base, (uint32_t)fb_wgs.size(), P.scaled, P.planar);
             if (ev1) (void)hipEventRecord(ev1, s);
             e = hipGetLastError();
         }
@@ -735,7 +750,10 @@ int pjd_batch_download_packed(pjd_batch *b, uint8_t *host, uint64_t capacity, in
     pjd_ctx *ctx = b->ctx;
     PjdPlan &P = b->plan;
     hipSetDevice(ctx->device);
+    if (b->bound_offsets) { ctx->err = "download_packed: the batch is bound with explicit picture offsets (no packed layout)"; return PJD_E_STATE; }
     if (capacity < P.out_buf_bytes) { ctx->err = "download_packed: buffer smaller than pjd_batch_packed_size"; return PJD_E_ARG; }
+    // a bound buffer need not reach past its last picture (the packed size is rounded up to 256 bytes)
+    const uint64_t copy_bytes = b->bound && b->bound_capacity < P.out_buf_bytes ? b->bound_capacity : P.out_buf_bytes;
     int rc = settle(b);
     if (rc != PJD_OK) return rc;
     // The runtime's copy (SDMA engine) by default.  PJD_DOWNLOAD=kernel: a small copy kernel on the device's download
@@ -745,7 +763,7 @@ int pjd_batch_download_packed(pjd_batch *b, uint8_t *host, uint64_t capacity, in
     void *mapped = nullptr;
     static const bool by_kernel = [] { const char *e = std::getenv("PJD_DOWNLOAD"); return e && !std::strcmp(e, "kernel"); }();
     hipPointerAttribute_t attr;
-    const bool pinned = by_kernel && (P.out_buf_bytes % 16) == 0 && ((uintptr_t)host % 16) == 0 &&
+    const bool pinned = by_kernel && !b->bound && (P.out_buf_bytes % 16) == 0 && ((uintptr_t)host % 16) == 0 &&
                         hipPointerGetAttributes(&attr, host) == hipSuccess && attr.type == hipMemoryTypeHost &&
                         hipHostGetDevicePointer(&mapped, host, 0) == hipSuccess && mapped;
     if (by_kernel && !pinned) (void)hipGetLastError();
@@ -760,7 +778,7 @@ int pjd_batch_download_packed(pjd_batch *b, uint8_t *host, uint64_t capacity, in
         (void)hipEventDestroy(done);
         HIP_TRY(ctx, e);
     } else {
-        HIP_TRY(ctx, hipMemcpyAsync(host, b->dev.out, P.out_buf_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(host, b->dev.out, copy_bytes, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
     if (status)
@@ -774,6 +792,63 @@ uint64_t pjd_batch_output_offset(pjd_batch *b, int image)
 {
     if (!b || image < 0 || (size_t)image >= b->plan.images.size()) return 0;
     return b->plan.images[image].out_off;
+}
+
+int pjd_batch_bind_output(pjd_batch *b, void *device_base, uint64_t capacity, const uint64_t *offsets)
+{
+    if (!b) return PJD_E_ARG;
+    pjd_ctx *ctx = b->ctx;
+    PjdPlan &P = b->plan;
+    if (b->uploaded) { ctx->err = "bind_output after upload"; return PJD_E_STATE; }
+    if (!device_base) { ctx->err = "bind_output: null pointer"; return PJD_E_ARG; }
+    if (P.out_format == PJD_OUT_BMP) { ctx->err = "bind_output: a BMP batch cannot be bound (its row padding relies on the batch's own zeroed buffer)"; return PJD_E_ARG; }
+    hipSetDevice(ctx->device);
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, device_base) != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != ctx->device) {
+        (void)hipGetLastError();
+        ctx->err = "bind_output: not device memory of the context's device";
+        return PJD_E_ARG;
+    }
+    {   // [base, base + capacity) lies inside the allocation the pointer belongs to (skipped where the runtime cannot tell; under a
+        // sub-allocator such as torch's the allocation is its whole segment: this catches a wild capacity, no more)
+        hipDeviceptr_t a_base = nullptr;
+        size_t a_size = 0;
+        if (hipMemGetAddressRange(&a_base, &a_size, (hipDeviceptr_t)device_base) != hipSuccess) (void)hipGetLastError();
+        else if ((uintptr_t)device_base - (uintptr_t)a_base > a_size || capacity > a_size - ((uintptr_t)device_base - (uintptr_t)a_base)) {
+            ctx->err = "bind_output: capacity reaches past the end of the allocation";
+            return PJD_E_ARG;
+        }
+    }
+    const size_t n = P.images.size();
+    if (b->packed_off.empty()) for (const PjdDevImage &g : P.images) b->packed_off.push_back(g.out_off);
+    std::vector<std::pair<uint64_t, uint64_t>> ranges(n);            // (offset, size) of every picture
+    for (size_t i = 0; i < n; i++) {
+        ranges[i] = {offsets ? offsets[i] : b->packed_off[i], P.host[i].out_bytes};
+        if (ranges[i].first > capacity || ranges[i].second > capacity - ranges[i].first) { ctx->err = fmt_image("bind_output: picture %d ends beyond the capacity", (int)i); return PJD_E_ARG; }
+    }
+    {
+        std::vector<std::pair<uint64_t, uint64_t>> sorted = ranges;
+        std::sort(sorted.begin(), sorted.end());
+        for (size_t i = 1; i < n; i++)
+            if (sorted[i - 1].first + sorted[i - 1].second > sorted[i].first) { ctx->err = "bind_output: picture ranges overlap"; return PJD_E_ARG; }
+    }
+    // from here on nothing fails.  The batch's own buffer goes back to the pool; the planner's image records (and their copy in
+    // the input blob, which pjd_batch_upload sends) take the bound offsets.
+    if (!b->bound)
+        for (size_t k = 0; k < b->dev_blocks.size(); k++)
+            if (b->dev_blocks[k].p == (void *)b->dev.out) {
+                if (!ctx->dev_pool.give(b->dev_blocks[k].p, b->dev_blocks[k].bytes, ctx->pool_cap)) hipFree(b->dev_blocks[k].p);
+                b->dev_blocks.erase(b->dev_blocks.begin() + (long)k);
+                b->device_bytes -= P.out_buf_bytes;
+                break;
+            }
+    PjdDevImage *h_images = reinterpret_cast<PjdDevImage *>(b->h_in + ((uint8_t *)b->d_images - b->d_in));
+    for (size_t i = 0; i < n; i++) P.images[i].out_off = h_images[i].out_off = ranges[i].first;
+    b->dev.out = (uint8_t *)device_base;
+    b->bound = true;
+    b->bound_offsets = offsets != nullptr;
+    b->bound_capacity = capacity;
+    return PJD_OK;
 }
 
 void *pjd_host_alloc(uint64_t bytes)

@@ -121,6 +121,8 @@
                                     // bits there is the reference's end-of-data error, handled by the parallel decoder itself
 #define PJD_IF_SCALE_SHIFT      6   // bits 7..6: log2 of the output scale denominator (PJD_F_SCALE_*): 0 full size, 1..3 = 1/2, 1/4, 1/8
 #define PJD_IF_SCALE_MASK       (3u << PJD_IF_SCALE_SHIFT)
+#define PJD_IF_PLANAR           256u // output is planar R, G, B (PJD_OUT_RGB8_PLANAR): three planes of out_stride x output rows bytes; a property of
+                                     // the whole batch (the planar back-end kernels are launched for it), never together with PJD_IF_BMP
 
 // status word per image: low 8 bits = PJD_ST_* class, bit 8 = "fast path gave up, needs exact kernel"
 #define PJD_STW_NEEDS_EXACT 0x100
@@ -180,8 +182,8 @@ struct PjdDevImage {
     uint64_t dense_base;               // first data unit of this image in the DENSE scratch (exact-kernel path only)
     uint32_t n_du;
     uint32_t image_index;
-    uint32_t out_stride;               // bytes per output row of the (scaled) picture, width w = ceil(W / s): BMP 3w + w%4, RGB8 3w
-    uint64_t out_off;                  // into the batch output buffer (256-byte aligned)
+    uint32_t out_stride;               // bytes per output row of the (scaled) picture, width w = ceil(W / s): BMP 3w + w%4, RGB8 3w, planar w (a plane row)
+    uint64_t out_off;                  // into the batch output buffer (256-byte aligned), or the caller's (pjd_batch_bind_output: any offset)
     uint32_t seg_base, n_seg;          // into PjdDevSegment[]
     uint32_t lane_base, n_lane;        // into PjdDevSub[] (global lane index)
     uint32_t hwave_base, n_hwave;      // Huffman waves of this image (global wave index)

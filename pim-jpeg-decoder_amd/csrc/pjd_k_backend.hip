@@ -11,6 +11,9 @@
 //                       (reference src/decoder_dpu.c:158-390 and src/bmp_writer.cpp:43-65 for the BMP row order).
 //                       _lanes parses the parallel decoder's lane streams (one 16-bit entry per symbol, one or two per
 //                       step word); the other reads the dense int16 scratch the exact kernel fills.
+//   pjd_k_idct_colour_lanes_planar / pjd_k_idct_colour_planar
+//                       the same two for a PJD_OUT_RGB8_PLANAR batch: R, G and B go to three planes (uint8[3][H][W]); kernels of
+//                       their own, so that the interleaved ones keep their code
 //
 // Integer work bound by VALU instruction issue (profiles/r03_cfg3.md: valu_issue_frac 1.0 -- the entry parser is its largest
 // phase), not by HBM: coefficients are read once with 16-byte loads, tiles live in LDS (row stride 144 B so that the column
@@ -287,9 +290,13 @@ __device__ __forceinline__ void pjd_tile_col(int16_t (*tile)[TILE_STRIDE], uint3
 // (natural order, dequantised).  Shared by the sparse and the dense front ends.
 // DO_IDCT = false: the caller has already run both passes on every unit (and this function's first barrier is
 // the one that separates them from the colour stage).  SCALED: pictures with an output scale take the scaled store (below).
+// PLANAR: the batch's output format is PJD_OUT_RGB8_PLANAR (never BMP): the three channels of a pixel go to three planes.
+template <bool PLANAR = false>
 __device__ __forceinline__ void pjd_colour_dispatch_scaled(const int16_t (*tile)[TILE_STRIDE], const uint32_t *mcu_xy, const PjdDevBatch &B,
                                                            const PjdDevImage &im, const PjdDevIdctWg &wg, uint32_t tid);
-template <bool DO_IDCT, bool SCALED>
+// One dword whatever its address: gfx950 global stores need no alignment (planar pictures start at any byte the caller binds)
+struct __attribute__((packed)) PjdPx4 { uint32_t a; };
+template <bool DO_IDCT, bool SCALED, bool PLANAR = false>
 __device__ __forceinline__ void pjd_tile_to_pixels(int16_t (*tile)[TILE_STRIDE], uint32_t *mcu_xy, const PjdDevBatch &B,
                                                    const PjdDevImage &im, const PjdDevIdctWg &wg, uint32_t tid)
 {
@@ -306,11 +313,11 @@ __device__ __forceinline__ void pjd_tile_to_pixels(int16_t (*tile)[TILE_STRIDE],
         for (uint32_t i = tid; i < n_du * 8; i += PJD_IDCT_THREADS) pjd_tile_col(tile, i >> 3, i & 7);
         __syncthreads();
     }
-    if (SCALED && (im.flags & PJD_IF_SCALE_MASK)) { pjd_colour_dispatch_scaled(tile, mcu_xy, B, im, wg, tid); return; }
+    if (SCALED && (im.flags & PJD_IF_SCALE_MASK)) { pjd_colour_dispatch_scaled<PLANAR>(tile, mcu_xy, B, im, wg, tid); return; }
 
     // ---- chroma upsample (nearest neighbour, decoder_dpu.c:370), colour, raster store --------
     const uint32_t mw = 8 * hs, mh = 8 * vs;
-    const bool bmp = (im.flags & PJD_IF_BMP) != 0;
+    const bool bmp = !PLANAR && (im.flags & PJD_IF_BMP) != 0;
     uint8_t *out = B.out + im.out_off;
     // image constants in registers: read through `im` they are re-fetched from HBM after every store
     const uint32_t width = im.width, height = im.height, stride = im.out_stride;
@@ -381,6 +388,21 @@ __device__ __forceinline__ void pjd_tile_to_pixels(int16_t (*tile)[TILE_STRIDE],
             const uint32_t f1 = pjd_clamp255(y1 + cf1), g1 = pjd_clamp255(y1 + cg1), l1 = pjd_clamp255(y1 + cl1);
             const uint32_t f2 = pjd_clamp255(y2 + cf2), g2 = pjd_clamp255(y2 + cg2), l2 = pjd_clamp255(y2 + cl2);
             const uint32_t f3 = pjd_clamp255(y3 + cf3), g3 = pjd_clamp255(y3 + cg3), l3 = pjd_clamp255(y3 + cl3);
+            if (PLANAR) {
+                // three plane rows (stride = width, plane = width x height); first / middle / last are R, G, B here
+                const size_t plane = (size_t)stride * height;
+                uint8_t *o = out + (size_t)Y * stride + X;
+                if (X + 4 <= width) {
+                    reinterpret_cast<PjdPx4 *>(o)->a = f0 | (f1 << 8) | (f2 << 16) | (f3 << 24);
+                    reinterpret_cast<PjdPx4 *>(o + plane)->a = g0 | (g1 << 8) | (g2 << 16) | (g3 << 24);
+                    reinterpret_cast<PjdPx4 *>(o + 2 * plane)->a = l0 | (l1 << 8) | (l2 << 16) | (l3 << 24);
+                } else {                                                         // right picture edge
+                    o[0] = (uint8_t)f0; o[plane] = (uint8_t)g0; o[2 * plane] = (uint8_t)l0;
+                    if (X + 1 < width) { o[1] = (uint8_t)f1; o[plane + 1] = (uint8_t)g1; o[2 * plane + 1] = (uint8_t)l1; }
+                    if (X + 2 < width) { o[2] = (uint8_t)f2; o[plane + 2] = (uint8_t)g2; o[2 * plane + 2] = (uint8_t)l2; }
+                }
+                continue;
+            }
             uint8_t *o = bmp ? out + 26 + (size_t)(height - 1 - Y) * stride + X * 3
                              : out + (size_t)Y * stride + X * 3;
             if (X + 4 <= width) {
@@ -407,11 +429,14 @@ __device__ __forceinline__ void pjd_tile_to_pixels(int16_t (*tile)[TILE_STRIDE],
 // ---------------------------------------------------------------------------------------------
 struct __attribute__((packed)) PjdPx12 { uint32_t a, b, c; };
 
-template <int HS, int VS, bool BMP>
+// PLANAR (never with BMP): three 4-byte stores, one per plane, instead of the 12-byte store; `stride` is the plane row (= width) and
+// `plane` the bytes of a plane.  A wave's store instruction then covers runs of one plane row, a dword per lane.
+template <int HS, int VS, bool BMP, bool PLANAR = false>
 __device__ __forceinline__ void pjd_colour_store(const int16_t (*tile)[TILE_STRIDE], const uint32_t *mcu_xy, uint8_t *out,
                                                  uint32_t width, uint32_t height, uint32_t stride, uint32_t ncomp,
-                                                 uint32_t n_mcu, uint32_t tid)
+                                                 uint32_t n_mcu, uint32_t tid, size_t plane = 0)
 {
+    static_assert(!(BMP && PLANAR), "a BMP file image is interleaved");
     constexpr uint32_t MW = 8 * HS, MH = 8 * VS, NL = HS * VS;
     constexpr uint32_t CG_LOG = HS == 2 ? 2 : 1;               // log2 of the 4-pixel column groups per MCU row
     constexpr int NCH = 4 / HS;                                 // chroma samples under 4 pixels
@@ -462,6 +487,19 @@ __device__ __forceinline__ void pjd_colour_store(const int16_t (*tile)[TILE_STRI
                 const uint32_t f1 = pjd_clamp255(y1 + cf[s1]), g1 = pjd_clamp255(y1 + cg[s1]), l1 = pjd_clamp255(y1 + cl[s1]);
                 const uint32_t f2 = pjd_clamp255(y2 + cf[s2]), g2 = pjd_clamp255(y2 + cg[s2]), l2 = pjd_clamp255(y2 + cl[s2]);
                 const uint32_t f3 = pjd_clamp255(y3 + cf[s3]), g3 = pjd_clamp255(y3 + cg[s3]), l3 = pjd_clamp255(y3 + cl[s3]);
+                if (PLANAR) {
+                    uint8_t *o = out + (size_t)Y * stride + X;
+                    if (X + 4 <= width) {
+                        reinterpret_cast<PjdPx4 *>(o)->a = f0 | (f1 << 8) | (f2 << 16) | (f3 << 24);
+                        reinterpret_cast<PjdPx4 *>(o + plane)->a = g0 | (g1 << 8) | (g2 << 16) | (g3 << 24);
+                        reinterpret_cast<PjdPx4 *>(o + 2 * plane)->a = l0 | (l1 << 8) | (l2 << 16) | (l3 << 24);
+                    } else {                                                         // right picture edge
+                        o[0] = (uint8_t)f0; o[plane] = (uint8_t)g0; o[2 * plane] = (uint8_t)l0;
+                        if (X + 1 < width) { o[1] = (uint8_t)f1; o[plane + 1] = (uint8_t)g1; o[2 * plane + 1] = (uint8_t)l1; }
+                        if (X + 2 < width) { o[2] = (uint8_t)f2; o[plane + 2] = (uint8_t)g2; o[2 * plane + 2] = (uint8_t)l2; }
+                    }
+                    continue;
+                }
                 uint8_t *o = BMP ? out + 26 + (size_t)(height - 1 - Y) * stride + X * 3 : out + (size_t)Y * stride + X * 3;
                 if (X + 4 <= width) {
                     PjdPx12 px;
@@ -506,11 +544,12 @@ __device__ __forceinline__ void pjd_bmp_header(uint8_t *out, uint32_t width, uin
 // and keeps the sums in registers: 4 / S output pixels for S <= 4; at S = 8 the two column groups of a box are neighbouring lanes
 // and add their sums with one cross-lane move.  A full box divides by a shift, only edge boxes by n < S * S.
 // ---------------------------------------------------------------------------------------------
-template <int HS, int VS, bool BMP, int S>
+template <int HS, int VS, bool BMP, int S, bool PLANAR = false>
 __device__ __forceinline__ void pjd_colour_store_scaled(const int16_t (*tile)[TILE_STRIDE], const uint32_t *mcu_xy, uint8_t *out,
                                                         uint32_t width, uint32_t height, uint32_t stride, uint32_t ncomp,
                                                         uint32_t n_mcu, uint32_t tid)
 {
+    static_assert(!(BMP && PLANAR), "a BMP file image is interleaved");
     constexpr uint32_t MW = 8 * HS, MH = 8 * VS, NL = HS * VS;
     constexpr uint32_t CG_LOG = HS == 2 ? 2 : 1;               // log2 of the 4-pixel column groups per MCU row
     constexpr uint32_t S_LOG = S == 2 ? 1 : (S == 4 ? 2 : 3);
@@ -585,7 +624,9 @@ __device__ __forceinline__ void pjd_colour_store_scaled(const int16_t (*tile)[TI
         if (X < width && Yb < height && (S < 8 || (px0 & 4) == 0)) {
             const uint32_t bh = height - Yb < S ? height - Yb : S;
             const uint32_t oy = Yb >> S_LOG, ox = X >> S_LOG;
-            uint8_t *o = BMP ? out + 26 + (size_t)(sh - 1 - oy) * stride + ox * 3 : out + (size_t)oy * stride + ox * 3;
+            const size_t plane = PLANAR ? (size_t)stride * sh : 0;                 // PLANAR: stride is the plane row, ceil(width / S)
+            uint8_t *o = PLANAR ? out + (size_t)oy * stride + ox
+                                : (BMP ? out + 26 + (size_t)(sh - 1 - oy) * stride + ox * 3 : out + (size_t)oy * stride + ox * 3);
 #pragma unroll
             for (int k = 0; k < NO; k++) {
                 const uint32_t bx = X + k * S;                  // first column of the box
@@ -594,17 +635,35 @@ __device__ __forceinline__ void pjd_colour_store_scaled(const int16_t (*tile)[TI
                 uint32_t a, b, c;
                 if (n == S * S) { a = (sf[k] + S * S / 2) >> (2 * S_LOG); b = (sg[k] + S * S / 2) >> (2 * S_LOG); c = (sl[k] + S * S / 2) >> (2 * S_LOG); }
                 else { a = (sf[k] + (n >> 1)) / n; b = (sg[k] + (n >> 1)) / n; c = (sl[k] + (n >> 1)) / n; }
-                o[3 * k] = (uint8_t)a; o[3 * k + 1] = (uint8_t)b; o[3 * k + 2] = (uint8_t)c;
+                if (PLANAR) { o[k] = (uint8_t)a; o[plane + k] = (uint8_t)b; o[2 * plane + k] = (uint8_t)c; }
+                else { o[3 * k] = (uint8_t)a; o[3 * k + 1] = (uint8_t)b; o[3 * k + 2] = (uint8_t)c; }
             }
         }
     }
 }
 
+template <bool PLANAR>
 __device__ __forceinline__ void pjd_colour_dispatch_scaled(const int16_t (*tile)[TILE_STRIDE], const uint32_t *mcu_xy, const PjdDevBatch &B,
                                                            const PjdDevImage &im, const PjdDevIdctWg &wg, uint32_t tid)
 {
     uint8_t *out = B.out + im.out_off;
     const uint32_t width = im.width, height = im.height, stride = im.out_stride, nc = im.ncomp, n = wg.n_mcu;
+    if (PLANAR) {
+        const uint32_t mode = (im.hs - 1) | ((im.vs - 1) << 1) | ((((im.flags & PJD_IF_SCALE_MASK) >> PJD_IF_SCALE_SHIFT) - 1) << 2);
+#define PJD_PLANAR_CASES(M0, S_)                                                                                                  \
+    case M0 + 0: pjd_colour_store_scaled<1, 1, false, S_, true>(tile, mcu_xy, out, width, height, stride, nc, n, tid); break;     \
+    case M0 + 1: pjd_colour_store_scaled<2, 1, false, S_, true>(tile, mcu_xy, out, width, height, stride, nc, n, tid); break;     \
+    case M0 + 2: pjd_colour_store_scaled<1, 2, false, S_, true>(tile, mcu_xy, out, width, height, stride, nc, n, tid); break;     \
+    case M0 + 3: pjd_colour_store_scaled<2, 2, false, S_, true>(tile, mcu_xy, out, width, height, stride, nc, n, tid); break;
+        switch (mode) {
+            PJD_PLANAR_CASES(0, 2)
+            PJD_PLANAR_CASES(4, 4)
+            PJD_PLANAR_CASES(8, 8)
+            default: break;
+        }
+#undef PJD_PLANAR_CASES
+        return;
+    }
     const bool bmp = (im.flags & PJD_IF_BMP) != 0;
     const uint32_t s_log = (im.flags & PJD_IF_SCALE_MASK) >> PJD_IF_SCALE_SHIFT;          // 1..3
     if (bmp && wg.first_mcu == 0) pjd_bmp_header(out, (width + (1u << s_log) - 1) >> s_log, (height + (1u << s_log) - 1) >> s_log, stride, tid);
@@ -626,13 +685,23 @@ __device__ __forceinline__ void pjd_colour_dispatch_scaled(const int16_t (*tile)
 }
 
 // SCALED: the kernel also serves pictures with an output scale (a kernel of its own, so that the full-size kernels stay as they are)
-template <bool SCALED>
+template <bool SCALED, bool PLANAR = false>
 __device__ __forceinline__ void pjd_colour_dispatch(const int16_t (*tile)[TILE_STRIDE], const uint32_t *mcu_xy, const PjdDevBatch &B,
                                                     const PjdDevImage &im, const PjdDevIdctWg &wg, uint32_t tid)
 {
-    if (SCALED && (im.flags & PJD_IF_SCALE_MASK)) { pjd_colour_dispatch_scaled(tile, mcu_xy, B, im, wg, tid); return; }
+    if (SCALED && (im.flags & PJD_IF_SCALE_MASK)) { pjd_colour_dispatch_scaled<PLANAR>(tile, mcu_xy, B, im, wg, tid); return; }
     uint8_t *out = B.out + im.out_off;
     const uint32_t width = im.width, height = im.height, stride = im.out_stride, nc = im.ncomp, n = wg.n_mcu;
+    if (PLANAR) {
+        const size_t plane = (size_t)stride * height;          // computed once per workgroup: no division anywhere near a store
+        switch ((im.hs - 1) | ((im.vs - 1) << 1)) {
+            case 0: pjd_colour_store<1, 1, false, true>(tile, mcu_xy, out, width, height, stride, nc, n, tid, plane); break;
+            case 1: pjd_colour_store<2, 1, false, true>(tile, mcu_xy, out, width, height, stride, nc, n, tid, plane); break;
+            case 2: pjd_colour_store<1, 2, false, true>(tile, mcu_xy, out, width, height, stride, nc, n, tid, plane); break;
+            default: pjd_colour_store<2, 2, false, true>(tile, mcu_xy, out, width, height, stride, nc, n, tid, plane); break;
+        }
+        return;
+    }
     const bool bmp = (im.flags & PJD_IF_BMP) != 0;
     if (bmp && wg.first_mcu == 0) pjd_bmp_header(out, width, height, stride, tid);
     const uint32_t mode = (im.hs - 1) | ((im.vs - 1) << 1) | (bmp ? 4u : 0u);
@@ -656,62 +725,18 @@ __device__ __forceinline__ void pjd_colour_dispatch(const int16_t (*tile)[TILE_S
 template <bool SCALED>
 __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_colour(PjdDevBatch B, const PjdDevIdctWg *__restrict__ wgs, const uint64_t *__restrict__ dense_base)
 {
-    __shared__ __attribute__((aligned(16))) int16_t tile[PJD_IDCT_MAX_DU][TILE_STRIDE];
-    __shared__ uint16_t qs[3][64];
-    __shared__ uint32_t mcu_xy[PJD_IDCT_MAX_DU];
+#define PJD_DENSE_PLANAR false
+#include "pjd_k_idct_dense_body.h"
+#undef PJD_DENSE_PLANAR
+}
 
-    const PjdDevIdctWg wg = wgs[blockIdx.x];
-    const PjdDevImage &im = B.images[wg.image];
-    const uint32_t tid = threadIdx.x;
-    const uint32_t dus = im.dus_per_mcu, nl = im.n_luma;
-    const uint32_t n_du = wg.n_mcu * dus;
-    const uint32_t RI = im.restart_interval;
-
-    if (tid < 192) qs[tid >> 6][tid & 63] = B.qtab[(size_t)wg.image * 192 + tid];
-    __syncthreads();
-
-    // ---- load (16 B per lane, coalesced), DC fix-up, de-zigzag, dequantise, row pass ----------
-    // lane (du, r) owns zigzag slots 8r..8r+7 on load; after the scatter to natural order a
-    // second sweep does the row pass.
-    const int16_t *cbase = B.coef + (dense_base[wg.pad_] + (uint64_t)(wg.first_mcu - im.first_mcu) * dus) * 64;
-    for (uint32_t i = tid; i < n_du * 8; i += PJD_IDCT_THREADS) {
-        const uint32_t du = i >> 3, r = i & 7;
-        const uint32_t ml = du / dus, k = du - ml * dus;
-        const uint32_t comp = k < nl ? 0 : k - nl + 1;
-        const int4 raw = *reinterpret_cast<const int4 *>(cbase + (size_t)du * 64 + r * 8);
-        const int16_t *rv = reinterpret_cast<const int16_t *>(&raw);
-        int v[8];
-#pragma unroll
-        for (int j = 0; j < 8; j++) v[j] = rv[j];
-        int16_t *t = tile[du];
-        const uint16_t *q = qs[comp];
-        // the sentinel means "explicit zero" at slot 52 of a baseline picture only; everywhere else -32768 is a value (an
-        // absolute DC the int16 predictor reached, a progressive coefficient shifted by Al)
-        const bool zero52 = r == 6 && !(im.flags & PJD_IF_PROGRESSIVE) && v[4] == PJD_COEF_SENTINEL;
-        if (r == 6 && !(im.flags & PJD_IF_STANDARD_ZIGZAG)) {
-            // slots 48..55.  Natural position 38 is the target of slot 48 AND slot 52 (the
-            // reference's zigzag_map[48] = 38): the later write wins, and an explicit zero
-            // written at slot 52 (run/size symbol with size 0) is marked by the sentinel.
-            const int v52 = v[4];
-            const int n38 = v52 != 0 ? (zero52 ? 0 : v52) : v[0];
-            t[38] = (int16_t)pjd_dequant(n38, q[38]);
-            t[59] = (int16_t)pjd_dequant(v[1], q[59]);
-            t[52] = (int16_t)pjd_dequant(v[2], q[52]);
-            t[45] = (int16_t)pjd_dequant(v[3], q[45]);
-            t[31] = (int16_t)pjd_dequant(v[5], q[31]);
-            t[39] = (int16_t)pjd_dequant(v[6], q[39]);
-            t[46] = (int16_t)pjd_dequant(v[7], q[46]);
-            t[58] = 0;                    // natural 58 is never written by the reference
-        } else {
-#pragma unroll
-            for (int j = 0; j < 8; j++) {
-                const uint32_t nat = (r == 6 && j == 0) ? 58u : c_zz[r * 8 + j];          // r == 6 here: PJD_IF_STANDARD_ZIGZAG
-                t[nat] = (int16_t)pjd_dequant(j == 4 && zero52 ? 0 : v[j], q[nat]);
-            }
-        }
-    }
-    __syncthreads();
-    pjd_tile_to_pixels<true, SCALED>(tile, mcu_xy, B, im, wg, tid);
+// The same for a PJD_OUT_RGB8_PLANAR batch: kernels of their own, so that the interleaved ones keep their code and registers
+template <bool SCALED>
+__global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_colour_planar(PjdDevBatch B, const PjdDevIdctWg *__restrict__ wgs, const uint64_t *__restrict__ dense_base)
+{
+#define PJD_DENSE_PLANAR true
+#include "pjd_k_idct_dense_body.h"
+#undef PJD_DENSE_PLANAR
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -758,8 +783,8 @@ __device__ __forceinline__ void pjd_tile_put(uint32_t tile_lds, uint32_t u, uint
 }
 
 // One back-end range (PjdDevIdctWg `iwg`) by the whole workgroup; the LDS arrays are the kernel's.  Returns are workgroup-uniform.
-// SCALED: pictures with an output scale take the scaled store.
-template <bool SCALED>
+// SCALED: pictures with an output scale take the scaled store.  PLANAR: the batch's output format is PJD_OUT_RGB8_PLANAR.
+template <bool SCALED, bool PLANAR = false>
 __device__ __forceinline__ void pjd_idct_range(const PjdDevBatch &B, uint32_t iwg, int16_t (*tile)[TILE_STRIDE], uint32_t (*qz)[64], uint32_t *mcu_xy,
                                                uint8_t *comp_of, uint32_t *wagg, uint32_t *ltab)
 {
@@ -981,7 +1006,7 @@ __device__ __forceinline__ void pjd_idct_range(const PjdDevBatch &B, uint32_t iw
     if (tile[0][0] == 12345) B.out[0] = 1;
     return;
 #endif
-    pjd_colour_dispatch<SCALED>(tile, mcu_xy, B, im, wg, tid);
+    pjd_colour_dispatch<SCALED, PLANAR>(tile, mcu_xy, B, im, wg, tid);
 }
 
 // order: the launch's workgroup -> index into PjdDevBatch::iwgs / marks (null: the identity, one launch for the whole batch)
@@ -1018,6 +1043,24 @@ __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_colour_lanes_scal
     __builtin_amdgcn_s_setprio(PJD_IDCT_PRIO);
 #endif
     pjd_idct_range<true>(B, order ? order[blockIdx.x] : blockIdx.x, tile, qz, mcu_xy, comp_of, wagg, ltab);
+}
+
+// The lane-stream back end of a PJD_OUT_RGB8_PLANAR batch, without and with pictures that have an output scale: kernels of their own
+// again.  Never a sweep: the pull form is not used for such batches.
+template <bool SCALED>
+__global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_colour_lanes_planar(PjdDevBatch B, const uint32_t *__restrict__ order)
+{
+    __shared__ __attribute__((aligned(16))) int16_t tile[PJD_IDCT_MAX_DU][TILE_STRIDE];
+    __shared__ uint32_t qz[3][64];
+    __shared__ uint32_t mcu_xy[PJD_IDCT_MAX_DU];
+    __shared__ uint8_t comp_of[PJD_IDCT_MAX_DU];
+    __shared__ uint32_t wagg[2];
+    __shared__ uint32_t ltab[96];
+
+#if PJD_IDCT_PRIO
+    __builtin_amdgcn_s_setprio(PJD_IDCT_PRIO);
+#endif
+    pjd_idct_range<SCALED, true>(B, order ? order[blockIdx.x] : blockIdx.x, tile, qz, mcu_xy, comp_of, wagg, ltab);
 }
 
 // The pull launch (pjd_internal.h; experiment switch PJD_IDLE_FORM=pull): a few workgroups per CU stay and take the ranges of ready_list
@@ -1068,10 +1111,12 @@ __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_pull(PjdDevBatch 
     }
 }
 
-void pjd_launch_idct_colour_lanes(hipStream_t s, const PjdDevBatch &b, bool scaled)
+void pjd_launch_idct_colour_lanes(hipStream_t s, const PjdDevBatch &b, bool scaled, bool planar)
 {
     if (b.n_iwg == 0) return;
-    if (scaled) hipLaunchKernelGGL(pjd_k_idct_colour_lanes_scaled, dim3(b.n_iwg), dim3(PJD_IDCT_THREADS), 0, s, b, (const uint32_t *)nullptr);
+    if (planar && scaled) hipLaunchKernelGGL(pjd_k_idct_colour_lanes_planar<true>, dim3(b.n_iwg), dim3(PJD_IDCT_THREADS), 0, s, b, (const uint32_t *)nullptr);
+    else if (planar) hipLaunchKernelGGL(pjd_k_idct_colour_lanes_planar<false>, dim3(b.n_iwg), dim3(PJD_IDCT_THREADS), 0, s, b, (const uint32_t *)nullptr);
+    else if (scaled) hipLaunchKernelGGL(pjd_k_idct_colour_lanes_scaled, dim3(b.n_iwg), dim3(PJD_IDCT_THREADS), 0, s, b, (const uint32_t *)nullptr);
     else hipLaunchKernelGGL(pjd_k_idct_colour_lanes, dim3(b.n_iwg), dim3(PJD_IDCT_THREADS), 0, s, b, (const uint32_t *)nullptr, 0);
 }
 
@@ -1088,10 +1133,12 @@ void pjd_launch_idct_sweep(hipStream_t s, const PjdDevBatch &b)
     if (b.n_iwg) hipLaunchKernelGGL(pjd_k_idct_colour_lanes, dim3(b.n_iwg), dim3(PJD_IDCT_THREADS), 0, s, b, (const uint32_t *)nullptr, 1);
 }
 
-void pjd_launch_group_idct(hipStream_t s, const PjdDevBatch &b, const PjdDevGroup &g, bool scaled)
+void pjd_launch_group_idct(hipStream_t s, const PjdDevBatch &b, const PjdDevGroup &g, bool scaled, bool planar)
 {
     if (!g.iwg_count) return;
-    if (scaled) hipLaunchKernelGGL(pjd_k_idct_colour_lanes_scaled, dim3(g.iwg_count), dim3(PJD_IDCT_THREADS), 0, s, b, (const uint32_t *)(b.iwg_order + g.iwg_first));
+    if (planar && scaled) hipLaunchKernelGGL(pjd_k_idct_colour_lanes_planar<true>, dim3(g.iwg_count), dim3(PJD_IDCT_THREADS), 0, s, b, (const uint32_t *)(b.iwg_order + g.iwg_first));
+    else if (planar) hipLaunchKernelGGL(pjd_k_idct_colour_lanes_planar<false>, dim3(g.iwg_count), dim3(PJD_IDCT_THREADS), 0, s, b, (const uint32_t *)(b.iwg_order + g.iwg_first));
+    else if (scaled) hipLaunchKernelGGL(pjd_k_idct_colour_lanes_scaled, dim3(g.iwg_count), dim3(PJD_IDCT_THREADS), 0, s, b, (const uint32_t *)(b.iwg_order + g.iwg_first));
     else hipLaunchKernelGGL(pjd_k_idct_colour_lanes, dim3(g.iwg_count), dim3(PJD_IDCT_THREADS), 0, s, b, b.iwg_order + g.iwg_first, 0);
 }
 
@@ -1174,10 +1221,12 @@ void pjd_launch_lane_dc_scan(hipStream_t s, const PjdDevBatch &b)
     hipLaunchKernelGGL(pjd_k_lane_dc_carry, dim3(1), dim3(256), 0, s, b);
 }
 
-void pjd_launch_idct_colour(hipStream_t s, const PjdDevBatch &b, const PjdDevIdctWg *wgs, const uint64_t *dense_base, uint32_t n_wg, bool scaled)
+void pjd_launch_idct_colour(hipStream_t s, const PjdDevBatch &b, const PjdDevIdctWg *wgs, const uint64_t *dense_base, uint32_t n_wg, bool scaled, bool planar)
 {
     if (n_wg == 0) return;
-    if (scaled) hipLaunchKernelGGL(pjd_k_idct_colour<true>, dim3(n_wg), dim3(PJD_IDCT_THREADS), 0, s, b, wgs, dense_base);
+    if (planar && scaled) hipLaunchKernelGGL(pjd_k_idct_colour_planar<true>, dim3(n_wg), dim3(PJD_IDCT_THREADS), 0, s, b, wgs, dense_base);
+    else if (planar) hipLaunchKernelGGL(pjd_k_idct_colour_planar<false>, dim3(n_wg), dim3(PJD_IDCT_THREADS), 0, s, b, wgs, dense_base);
+    else if (scaled) hipLaunchKernelGGL(pjd_k_idct_colour<true>, dim3(n_wg), dim3(PJD_IDCT_THREADS), 0, s, b, wgs, dense_base);
     else hipLaunchKernelGGL(pjd_k_idct_colour<false>, dim3(n_wg), dim3(PJD_IDCT_THREADS), 0, s, b, wgs, dense_base);
 }
 

@@ -56,12 +56,13 @@ void pjd_launch_reset(hipStream_t s, const PjdDevBatch &b, const int32_t *status
 void pjd_launch_copy_out(hipStream_t s, const void *src, void *dst_mapped, uint64_t bytes);   // HBM -> mapped page-locked host memory
 // dense input (exact path): wgs[k].pad_ = index into dense_base[] (data unit 0 of that image's scratch)
 // scaled: the batch holds pictures with an output scale (PJD_IF_SCALE_MASK): the back-end kernels that also serve them
-void pjd_launch_idct_colour(hipStream_t s, const PjdDevBatch &b, const PjdDevIdctWg *wgs, const uint64_t *dense_base, uint32_t n_wg, bool scaled);
-void pjd_launch_idct_colour_lanes(hipStream_t s, const PjdDevBatch &b, bool scaled);                                     // lane-stream input
+// planar: the batch's output format is PJD_OUT_RGB8_PLANAR (PJD_IF_PLANAR on every picture): the planar back-end kernels
+void pjd_launch_idct_colour(hipStream_t s, const PjdDevBatch &b, const PjdDevIdctWg *wgs, const uint64_t *dense_base, uint32_t n_wg, bool scaled, bool planar);
+void pjd_launch_idct_colour_lanes(hipStream_t s, const PjdDevBatch &b, bool scaled, bool planar);                                  // lane-stream input
 void pjd_launch_lane_dc_scan(hipStream_t s, const PjdDevBatch &b);      // three kernels: per-image verdict (status words), local scan, carry
 // one picture group (pjd_internal.h): verdict + DC predictors of its pictures in one launch, then its back-end workgroups
 void pjd_launch_group_dc(hipStream_t s, const PjdDevBatch &b, const PjdDevGroup &g);
-void pjd_launch_group_idct(hipStream_t s, const PjdDevBatch &b, const PjdDevGroup &g, bool scaled);
+void pjd_launch_group_idct(hipStream_t s, const PjdDevBatch &b, const PjdDevGroup &g, bool scaled, bool planar);
 // pull back end (pjd_internal.h): the launch that runs beside the entropy decoder, and the sweep over what it left
 void pjd_launch_idct_pull(hipStream_t s, const PjdDevBatch &b);
 void pjd_launch_idct_sweep(hipStream_t s, const PjdDevBatch &b);

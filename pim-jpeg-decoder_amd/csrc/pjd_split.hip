@@ -87,10 +87,13 @@ void drop_comms_locked()
 
 // In OUTPUT pixels: at an output scale s (PJD_F_SCALE_*) an MCU is mcu_w = 8 * h_samp / s columns and mcu_h = 8 * v_samp / s rows of
 // the ceil(W / s) x ceil(H / s) picture (s divides 8: a box never straddles two MCUs).
+// PJD_OUT_RGB8_PLANAR: three planes of `plane` = W x H bytes, px = 1 byte per pixel and row; else one "plane" of px = 3.
 struct Geometry {
     uint32_t mcu_w, mcu_h, mcux, mcuy, n_mcu, stride;
     bool bmp;
     uint32_t W, H;
+    uint32_t n_planes, px;
+    uint64_t plane;
     // bytes [lo, hi) of picture rows [y0, y1) in the output image
     void row_bytes(uint32_t y0, uint32_t y1, uint64_t &lo, uint64_t &hi) const
     {
@@ -111,7 +114,10 @@ Geometry geometry_of(const pjd_image_desc &d, int out_format)
     g.mcuy = (h8 + d.v_samp - 1) / d.v_samp;
     g.n_mcu = g.mcux * g.mcuy;
     g.bmp = out_format == PJD_OUT_BMP;
-    g.stride = g.bmp ? g.W * 3 + g.W % 4 : g.W * 3;
+    const bool planar = out_format == PJD_OUT_RGB8_PLANAR;
+    g.n_planes = planar ? 3 : 1; g.px = planar ? 1 : 3;
+    g.stride = g.bmp ? g.W * 3 + g.W % 4 : g.W * g.px;
+    g.plane = (uint64_t)g.W * g.H;
     return g;
 }
 
@@ -214,7 +220,7 @@ int pjd_split_decode(const pjd_image_desc *desc, const int32_t *devices, int n_d
     std::memset(&st, 0, sizeof st);
     if (stats_out) *stats_out = st;
     if (!desc || !devices || n_devices <= 0 || n_devices > PJD_SPLIT_MAX_DEVICES || !out) return PJD_E_ARG;
-    if (out_format != PJD_OUT_RGB8 && out_format != PJD_OUT_BMP) return PJD_E_ARG;
+    if (out_format != PJD_OUT_RGB8 && out_format != PJD_OUT_BMP && out_format != PJD_OUT_RGB8_PLANAR) return PJD_E_ARG;
     const uint64_t out_bytes = pjd_image_output_size(desc, out_format);
     if (capacity < out_bytes) return PJD_E_ARG;
     const bool dup_ok = std::getenv("PJD_PIPE_ALLOW_DUP_DEVICES") != nullptr;     // tests on a one-GPU box: one ordinal, several ranks
@@ -374,7 +380,8 @@ int pjd_split_decode(const pjd_image_desc *desc, const int32_t *devices, int n_d
                     if (!in_run) return;
                     uint64_t a, z;
                     g.row_bytes(run_lo * g.mcu_h, std::min(g.H, run_hi * g.mcu_h), a, z);
-                    if (e == hipSuccess) e = hipMemcpyAsync(out + a, dev_out + a, z - a, hipMemcpyDeviceToHost, s);
+                    for (uint32_t p = 0; p < g.n_planes; p++)       // the same rows of every plane
+                        if (e == hipSuccess) e = hipMemcpyAsync(out + p * g.plane + a, dev_out + p * g.plane + a, z - a, hipMemcpyDeviceToHost, s);
                     in_run = false;
                 };
                 for (uint32_t bnd = b_first; bnd <= b_last && e == hipSuccess; bnd++) {
@@ -389,14 +396,17 @@ int pjd_split_decode(const pjd_image_desc *desc, const int32_t *devices, int n_d
                     const uint32_t y0 = bnd * g.mcu_h, y1 = std::min(g.H, (bnd + 1) * g.mcu_h);
                     uint64_t a, z;
                     g.row_bytes(y0, y1, a, z);
-                    band.resize(z - a);
-                    e = hipMemcpyAsync(band.data(), dev_out + a, z - a, hipMemcpyDeviceToHost, s);
+                    band.resize((z - a) * g.n_planes);
+                    for (uint32_t p = 0; p < g.n_planes && e == hipSuccess; p++)
+                        e = hipMemcpyAsync(band.data() + p * (z - a), dev_out + p * g.plane + a, z - a, hipMemcpyDeviceToHost, s);
                     if (e == hipSuccess) e = hipStreamSynchronize(s);
                     if (e != hipSuccess) break;
-                    const uint64_t x0 = (uint64_t)c0 * g.mcu_w * 3;
-                    const uint64_t x1 = c1 == g.mcux ? g.stride : std::min<uint64_t>((uint64_t)c1 * g.mcu_w, g.W) * 3;   // the row's last MCU also owns its padding
+                    const uint64_t x0 = (uint64_t)c0 * g.mcu_w * g.px;
+                    const uint64_t x1 = c1 == g.mcux ? g.stride : std::min<uint64_t>((uint64_t)c1 * g.mcu_w, g.W) * g.px;   // the row's last MCU also owns its padding
                     if (x1 > x0)
-                        for (uint32_t y = y0; y < y1; y++) std::memcpy(out + g.row_off(y) + x0, band.data() + (g.row_off(y) - a) + x0, x1 - x0);
+                        for (uint32_t p = 0; p < g.n_planes; p++)
+                            for (uint32_t y = y0; y < y1; y++)
+                                std::memcpy(out + p * g.plane + g.row_off(y) + x0, band.data() + p * (z - a) + (g.row_off(y) - a) + x0, x1 - x0);
                 }
                 flush_run();
                 if (e == hipSuccess && g.bmp && m0 == 0) e = hipMemcpyAsync(out, dev_out, 26, hipMemcpyDeviceToHost, s);    // the file header comes with MCU 0

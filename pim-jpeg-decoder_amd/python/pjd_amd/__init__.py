@@ -16,6 +16,7 @@ LIBHOST = os.path.join(LIB_DIR, "libpjdhost.so")
 LIBPIPE = os.path.join(LIB_DIR, "libpjdpipe.so")
 
 OUT_RGB8, OUT_BMP = 0, 1
+OUT_RGB8_PLANAR = 2      # uint8[3][H][W]: the R, G and B planes one after the other (pjd.h)
 PLAN_LATENCY, PLAN_THROUGHPUT = 0, 1      # pjd_set_plan_mode
 F_STANDARD_RESTART, F_FORCE_SEQUENTIAL, F_STANDARD_ZIGZAG, F_PROGRESSIVE = 1, 2, 4, 8
 F_SCALE_1_2, F_SCALE_1_4, F_SCALE_1_8, F_SCALE_MASK = 16, 32, 48, 48      # output scale s = 1 << ((flags >> 4) & 3) (pjd.h)
@@ -162,6 +163,8 @@ def dev_lib():
         L.pjd_batch_packed_size.argtypes = [vp]
         L.pjd_batch_output_offset.restype = C.c_uint64
         L.pjd_batch_output_offset.argtypes = [vp, i32]
+        L.pjd_batch_bind_output.restype = i32
+        L.pjd_batch_bind_output.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
         L.pjd_host_alloc.restype = vp
         L.pjd_host_alloc.argtypes = [C.c_uint64]
         L.pjd_host_free.argtypes = [vp]
@@ -261,6 +264,7 @@ class Context:
             raise PjdError(f"pjd_open({device}) failed with {rc}: no usable gfx950 device")
         self._h = h
         self.L = L
+        self.device = int(device)
         if plan_mode is not None:
             self.set_plan_mode(plan_mode)
 
@@ -355,14 +359,46 @@ class Batch:
     def device_output(self, i):
         return self.L.pjd_batch_device_output(self._h, i)
 
+    def output_offset(self, i):
+        return int(self.L.pjd_batch_output_offset(self._h, i))
+
+    def packed_size(self):
+        return int(self.L.pjd_batch_packed_size(self._h))
+
+    def output_shape(self, i):
+        """Shape of picture i as download() returns it: (h, w, 3) for OUT_RGB8, (3, h, w) for OUT_RGB8_PLANAR, flat for OUT_BMP."""
+        d = self._descs[i]
+        w, h = scaled_dims(d.width, d.height, d.flags)
+        if self.out_format == OUT_RGB8:
+            return (h, w, 3)
+        if self.out_format == OUT_RGB8_PLANAR:
+            return (3, h, w)
+        return (self.output_size(i),)
+
+    def bind_output(self, device_ptr, capacity, offsets=None):
+        """pjd_batch_bind_output: pictures go into caller-owned device memory (`device_ptr`: a plain integer address, e.g. a
+        torch tensor's data_ptr(); `capacity` bytes) instead of a buffer of the batch.  `offsets`: byte offset of every picture,
+        or None for the packed layout (output_offset(i)).  Before upload(); not for OUT_BMP.  The caller keeps the memory alive
+        for as long as the batch decodes, and orders its own streams against the context's (sync())."""
+        arr = None
+        if offsets is not None:
+            if len(offsets) != self.n:
+                raise ValueError("bind_output: one offset per picture")
+            arr = (C.c_uint64 * max(self.n, 1))(*[int(o) for o in offsets])
+        self.ctx._check(self.L.pjd_batch_bind_output(self._h, C.c_void_p(int(device_ptr)), int(capacity), arr), "pjd_batch_bind_output")
+
+    def statuses(self):
+        """The status words of the last decode, without the pictures (synchronises)."""
+        st = (C.c_int32 * max(self.n, 1))()
+        self.ctx._check(self.L.pjd_batch_download(self._h, None, st), "pjd_batch_download")
+        return [int(st[i]) for i in range(self.n)]
+
     def download(self):
         outs = [np.zeros(self.output_size(i), np.uint8) for i in range(self.n)]
         ptrs = (C.c_void_p * max(self.n, 1))(*[o.ctypes.data for o in outs])
         st = (C.c_int32 * max(self.n, 1))()
         self.ctx._check(self.L.pjd_batch_download(self._h, ptrs, st), "pjd_batch_download")
-        if self.out_format == OUT_RGB8:
-            outs = [o.reshape(*reversed(scaled_dims(self._descs[i].width, self._descs[i].height, self._descs[i].flags)), 3)
-                    for i, o in enumerate(outs)]
+        outs = [o.reshape(self.output_shape(i)) for i, o in enumerate(outs)]
         return outs, [int(st[i]) for i in range(self.n)]
 
 
@@ -515,6 +551,8 @@ def split_decode(desc, devices, out_format=OUT_RGB8):
         raise PjdError(f"pjd_split_decode failed ({rc})")
     if out_format == OUT_RGB8:
         out = out.reshape(*reversed(scaled_dims(desc.width, desc.height, desc.flags)), 3)
+    elif out_format == OUT_RGB8_PLANAR:
+        out = out.reshape(3, *reversed(scaled_dims(desc.width, desc.height, desc.flags)))
     return out, int(status.value), st.as_dict()
 
 
