@@ -64,6 +64,18 @@ extern "C" {
 #define PJD_ST_AC_RUN    5   /* "Error - Zero run-length exceeded block component"      */
 #define PJD_ST_AC_LEN    6   /* "Error - AC coefficient length greater than 10"         */
 #define PJD_ST_AC_BITS   7   /* "Error - Invalid AC value"  (value bits)                */
+/* In the branches a progressive scan takes (jpeg_scanner.cpp:521-704) the reference words some of these otherwise; the classes, and
+ * the strings pjd_status_string returns, stay as above.  Message there -> class here:
+ *   "Invalid DC value" (no "(255)")                 -> PJD_ST_DC_SYM (no code for the DC symbol) or PJD_ST_DC_BITS (the data ends in
+ *                                                      the value bits, or before a DC refinement bit)
+ *   "DC coefficient length greater than 11"         -> PJD_ST_DC_LEN
+ *   "Invalid AC value"                              -> PJD_ST_AC_SYM (no code; a refinement symbol whose size is not 0 or 1) or
+ *                                                      PJD_ST_AC_BITS (the data ends in value bits, in the extra bits of an end-of-band
+ *                                                      run, before a sign bit or before a correction bit)
+ *   "Zero run-length exceeded spectral selection"   -> PJD_ST_AC_RUN (a run or a ZRL that passes Se in an AC first scan; in a refinement
+ *                                                      scan such a run is no error: the coefficient is dropped)
+ *   "AC coefficient length greater than 10"         -> PJD_ST_AC_LEN
+ * tests/test_progressive_streams.py checks every broken stream's reference message against this table.                              */
 
 /* ---- output formats ------------------------------------------------------- */
 #define PJD_OUT_RGB8   0   /* top-down, tightly packed R,G,B bytes: 3*W*H bytes (W, H: of the picture
@@ -89,11 +101,20 @@ extern "C" {
                                        the quantiser (qt_slot48).  NOT reference-comparable: the
                                        reference has no such mode, parity for it is unpinned.   */
 
-#define PJD_F_PROGRESSIVE       8u  /* a progressive (SOF2) frame: `scans` / `n_scans` describe its scans, `ecs` is unused.  The
-                                       reference cannot decode such files -- its scanner stops at the first marker between scans
-                                       (jpeg_scanner.cpp:425-430) and its progressive branches (:521-704) handle one scan only --
-                                       so this mode is NOT reference-comparable, parity for it is unpinned; it exists for
-                                       SURVEY 8(f) N4 and is opt-in (pjd_scan_*_ex with PJD_SCAN_PROGRESSIVE).                */
+#define PJD_F_PROGRESSIVE       8u  /* a progressive (SOF2) frame: `scans` / `n_scans` describe its scans (at most PJD_MAX_SCANS),
+                                       `ecs` is unused.  The reference cannot decode such a FILE -- its scanner stops at the first
+                                       marker between scans (jpeg_scanner.cpp:425-430) -- but it carries the four procedures
+                                       (decode_MCU_component, :521-704), and those are pinned: DC first, DC refinement, AC first and AC
+                                       refinement with end-of-band runs, the end-of-data rule and the error class of a broken scan
+                                       equal the reference's procedures run block by block on hand-built scans
+                                       (tests/test_progressive_streams.py, tests/test_gpu_progressive_streams.py).  Like the
+                                       reference, an AC first scan stores zeros over the slots of a run and of a ZRL (visible only
+                                       where bands overlap).  NOT the reference's: the order of the blocks of a non-interleaved
+                                       scan (ITU T.81 A.2.3, cross-checked against libjpeg's files), and the refinement history
+                                       per zigzag slot under PJD_F_STANDARD_ZIGZAG.  Opt-in (pjd_scan_*_ex with
+                                       PJD_SCAN_PROGRESSIVE), SURVEY 8(f) N4.                                                  */
+#define PJD_MAX_SCANS        1024u  /* scans of one progressive frame: the scanner rejects a file with more ("Too many scans"), the
+                                       planner a descriptor with more                                                          */
 
 /* Reduced-size output, chosen per picture: s = 1 << ((flags >> 4) & 3), s = 1 (flag clear) is the full-size picture.  For s > 1,
  * with P the W x H picture the library produces at s = 1 (as RGB8: the reference's picture, or the partial picture with grey after an

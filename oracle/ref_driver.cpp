@@ -19,6 +19,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <iostream>
+#include <sstream>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -27,6 +28,10 @@
 #include "headers/bmp.h"
 
 extern "C" void orc_dpu_exec(const uint32_t *metadata, int16_t *mcus);
+
+/* jpeg.h declares an older five-argument form; this is the one src/jpeg_scanner.cpp:467 defines */
+bool decode_MCU_component(Header *const header, BitReader &b, short *component, int &previous_DC, uint &skips, const HuffmanTable &DT,
+                          const HuffmanTable &AT);
 
 namespace {
 
@@ -169,6 +174,49 @@ int ref_decode_file(const char *in_path, const char *out_path)
     std::cout.flush();
     delete h;
     return 0;
+}
+
+/* ONE scan of a progressive frame through the reference's decode_MCU_component (reference src/jpeg_scanner.cpp:521-704), which
+ * read_JPEG can never reach from a file.  The caller owns the order of the blocks (block_off[k]: offset in int16 of block k's 64
+ * coefficients in `coef`; block_comp[k]: its component; restart_before[k] != 0: a restart interval starts with block k) -- the
+ * reference only knows the interleaved order, so the order is NOT the reference's.  Predictors and the end-of-band counter are
+ * kept as decode_Huffman_data keeps them (:714-729).  tab_offsets / tab_symbols: per component, the table of the scan's class (DC
+ * for Ss = 0, AC otherwise), handed over as both of the function's tables (each progressive branch reads one of them).
+ * Returns the number of blocks decoded without an error; `msg` receives what the reference printed (empty without an error). */
+int ref_progressive_scan(int ss, int se, int ah, int al, const uint8_t *tab_offsets /* [3][17] */, const uint8_t *tab_symbols /* [3][162] */,
+                         const uint8_t *ecs, int64_t ecs_len, int64_t n_blocks, const int64_t *block_off, const uint8_t *block_comp,
+                         const uint8_t *restart_before, int16_t *coef, char *msg, int msg_cap)
+{
+    Header h;
+    h.frame_type = SOF2;
+    h.start_of_selection = (byte)ss; h.end_of_selection = (byte)se;
+    h.successive_approximation_high = (byte)ah; h.successive_approximation_low = (byte)al;
+    h.huffman_data.assign(ecs, ecs + ecs_len);
+    HuffmanTable tabs[3];
+    for (int c = 0; c < 3; c++) {
+        std::memcpy(tabs[c].offsets, tab_offsets + 17 * c, 17);
+        std::memcpy(tabs[c].symbols, tab_symbols + 162 * c, 162);
+        tabs[c].set = true;
+        generate_codes(tabs[c]);
+    }
+    BitReader b(h.huffman_data);
+    int previous_DCs[3] = {0, 0, 0};
+    uint skips = 0;
+    std::ostringstream said;
+    std::streambuf *out = std::cout.rdbuf(said.rdbuf());
+    int64_t good = 0;
+    for (; good < n_blocks; good++) {
+        if (restart_before[good]) {
+            previous_DCs[0] = previous_DCs[1] = previous_DCs[2] = 0;
+            skips = 0;
+            b.align();
+        }
+        const int c = block_comp[good];
+        if (!decode_MCU_component(&h, b, coef + block_off[good], previous_DCs[c], skips, tabs[c], tabs[c])) break;
+    }
+    std::cout.rdbuf(out);
+    if (msg && msg_cap > 0) { std::strncpy(msg, said.str().c_str(), (size_t)msg_cap - 1); msg[msg_cap - 1] = 0; }
+    return (int)good;
 }
 
 }  /* extern "C" */

@@ -6,9 +6,17 @@
 // interleaved MCU order (:721-752).  This kernel is what that code would have to become: every scan of the frame in file order
 // (ITU T.81 G.1), non-interleaved scans over the component's own block grid, coefficients ACCUMULATED across scans in the dense
 // scratch (zigzag-slot order, absolute DC -- what the exact kernel leaves for a baseline picture), restart intervals per scan;
-// the dense back end (pjd_k_idct_colour) then does what it does for any picture.  NOT reference-comparable: parity is unpinned
-// (the check is that a progressive encoding of a picture decodes to the same pixels as the baseline encoding of the same
-// coefficients, tests/test_gpu_parity.py::test_progressive_*).
+// the dense back end (pjd_k_idct_colour) then does what it does for any picture.
+//
+// What is pinned (tests/test_progressive_streams.py, tests/test_gpu_progressive_streams.py): each of the four procedures, the bit
+// reader's end-of-data rule and the error class of every broken stream are the reference's, bit for bit -- a bit-level model written
+// from T.81 G.1.2 is run against decode_MCU_component itself (oracle/ref_driver.cpp, ref_progressive_scan) and against this kernel,
+// on hand-built scans.  Like the reference, an AC first scan stores zeros over the slots of a run and of a ZRL; that shows only where
+// bands overlap, which T.81 forbids and the scanner lets through.  What is NOT the reference's: the order of the blocks of a
+// non-interleaved scan (the reference only knows the interleaved order) -- that is T.81 A.2.3, cross-checked against libjpeg where
+// Pillow is installed -- the per-slot history with PJD_F_STANDARD_ZIGZAG (the reference's map sends slots 48 and 52 to one position),
+// and the messages: the reference prints "Invalid DC value" without "(255)" and "Zero run-length exceeded spectral selection" in
+// these branches; the PJD_ST_* classes are kept (the mapping is beside them in pjd.h).
 //
 // One lane per picture: scans are sequential by definition (each refines what the previous left), a picture's scans are ten
 // dependent chains.  A functional path, not a fast one (about 5 MPix/s per picture).
@@ -144,14 +152,14 @@ __global__ __launch_bounds__(64) void pjd_k_progressive(PjdDevBatch B, const uin
                                 const uint32_t run = (uint32_t)sym >> 4, len = (uint32_t)sym & 15;
                                 if (len != 0) {
                                     if (z + run > se) { status = PJD_ST_AC_RUN; break; }
-                                    z += run;
+                                    for (uint32_t j = 0; j < run; j++) unit[z++] = 0;       // the run's slots are stored, as the reference stores them (:570-572)
                                     if (len > 10) { status = PJD_ST_AC_LEN; break; }
                                     const int v2 = r.bits(len);
                                     if (v2 == -1) { status = PJD_ST_AC_BITS; break; }
                                     unit[z] = (int16_t)(extend(v2, len) << al);
                                 } else if (run == 15) {
                                     if (z + 15 > se) { status = PJD_ST_AC_RUN; break; }
-                                    z += 15;
+                                    for (uint32_t j = 0; j < 15; j++) unit[z++] = 0;        // (:591-593; the 16th slot is passed, not stored)
                                 } else {                                    // end of band for 2^run + extra blocks, this one included
                                     eobrun = (1u << run) - 1;
                                     const int x = r.bits(run);

@@ -239,7 +239,8 @@ int pjd_make_plan(const pjd_image_desc *images, int n, int out_format, PjdPlan &
         if (progressive) {
             // the scans carry their own tables (pjd_scan_desc); what a scan may be is ITU T.81 G.1.1.1 (the reference checks the same
             // in its SOS reader, src/jpeg_scanner.cpp:88-112)
-            if (!d.scans || d.n_scans == 0 || d.n_scans > 4096) { err = fmt("image %d: progressive frame without scans", i); return PJD_E_ARG; }
+            if (!d.scans || d.n_scans == 0) { err = fmt("image %d: progressive frame without scans", i); return PJD_E_ARG; }
+            if (d.n_scans > PJD_MAX_SCANS) { err = fmt("image %d: too many scans (%ld, at most %ld)", i, (long)d.n_scans, (long)PJD_MAX_SCANS); return PJD_E_ARG; }
             if (d.shard_n_segs != 0) { err = fmt("image %d: a progressive frame cannot be sharded", i); return PJD_E_ARG; }
             for (uint32_t k = 0; k < d.n_scans; k++) {
                 const pjd_scan_desc &sc = d.scans[k];

@@ -19,7 +19,7 @@
 // --split [--devices 0,1,...]: every picture is decoded by all listed devices TOGETHER (pjd_split_decode): restart-segment ranges per
 // device, the descriptor broadcast with RCCL, rows assembled on the host -- for single pictures larger than one device's share.
 // --progressive: progressive (SOF2) files are decoded scan by scan instead of being rejected as the reference rejects them
-// (not reference behaviour, parity unpinned).
+// (not reference behaviour: the reference rejects the file; its four progressive procedures are what the kernel is pinned to).
 // --scale 1/2|1/4|1/8 (and 1/1): pictures are written at that scale, as `djpeg -scale` does -- each output pixel the rounded mean of
 // its box of source pixels (PJD_F_SCALE_* of include/pjd.h); in every mode.  Any other value is a usage error.
 #include <sys/stat.h>

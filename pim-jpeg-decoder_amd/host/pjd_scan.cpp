@@ -331,6 +331,7 @@ void progressive_scans(Bytes &in, pjd_scanned &s)
         sc.ss = s.last_ss; sc.se = s.last_se; sc.ah = s.last_ah; sc.al = s.last_al;
         sc.restart_interval = d.restart_interval;
         if (sc.al > 13) return s.reject(": Error - Invalid successive approximation\n");
+        if (s.scans.size() >= PJD_MAX_SCANS) return s.reject(": Error - Too many scans\n");       // this scan would be one too many
         s.scan_ecs.emplace_back();
         if (!scan_bytes(in, s, s.scan_ecs.back())) return;
         s.scans.push_back(sc);
@@ -350,7 +351,6 @@ void progressive_scans(Bytes &in, pjd_scanned &s)
             if (!s.valid || in.bad) { if (s.valid) s.reject(": Error - File ended prematurely\n"); return; }
         }
         if (!s.valid) return;
-        if (s.scans.size() > 1024) return s.reject(": Error - Too many scans\n");
     }
 done:
     for (size_t k = 0; k < s.scans.size(); k++) { s.scans[k].ecs = s.scan_ecs[k].data(); s.scans[k].ecs_len = s.scan_ecs[k].size(); }

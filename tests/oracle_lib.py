@@ -200,6 +200,33 @@ class Ref:
         finally:
             self.L.ref_close(h)
 
+    def has_progressive_scan(self):
+        """False for an oracle/_ref built from an older oracle/ref_driver.cpp (a prebuilt copy where the reference tree is absent)."""
+        return hasattr(self.L, "ref_progressive_scan")
+
+    def progressive_scan(self, ss, se, ah, al, tables, ecs: bytes, block_off, block_comp, restart_before, coef: np.ndarray):
+        """ONE scan of a progressive frame through the reference's decode_MCU_component, block by block in the caller's order, into
+        `coef` (int16, in place).  tables: {component: (17 offsets, symbols)} of the scan's class.  -> (good blocks, message)."""
+        if not self.has_progressive_scan():
+            raise RuntimeError("oracle/_ref is older than oracle/ref_driver.cpp: rebuild it (make -C oracle _ref)")
+        fn = self.L.ref_progressive_scan
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_int] * 4 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_char_p, C.c_int]
+        offs, syms = np.zeros((3, 17), np.uint8), np.zeros((3, 162), np.uint8)
+        for c, (o, s) in tables.items():
+            offs[c] = o
+            syms[c, :len(s)] = s
+        assert coef.dtype == np.int16 and coef.flags.c_contiguous
+        e = np.frombuffer(ecs, np.uint8) if len(ecs) else np.zeros(1, np.uint8)
+        bo, bc = np.ascontiguousarray(block_off, np.int64), np.ascontiguousarray(block_comp, np.uint8)
+        rb = np.ascontiguousarray(restart_before, np.uint8)
+        assert len(bo) == len(bc) == len(rb) and (len(bo) == 0 or 0 <= bo.min() and bo.max() + 64 <= coef.size)
+        msg = C.create_string_buffer(512)
+        good = fn(ss, se, ah, al, offs.ctypes.data, syms.ctypes.data, e.ctypes.data, len(ecs), len(bo), bo.ctypes.data, bc.ctypes.data,
+                  rb.ctypes.data, coef.ctypes.data, msg, len(msg))
+        return int(good), msg.value.decode()
+
     @staticmethod
     def run_cli(in_path: str, out_path: str):
         """Run oracle/_ref/ref_decode as a child; -> (returncode, stdout text)."""

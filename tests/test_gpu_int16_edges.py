@@ -220,7 +220,8 @@ def test_progressive_stores_that_truncate_to_int16_min():
     refinement scan over it, AC first scans at Al = 13 with v = +-4 at slot 52 and elsewhere.  pjd_k_progressive never writes the
     slot-52 mark, so every -32768 is a value.  Decoded with PJD_F_STANDARD_ZIGZAG as test_gpu_parity's baseline-twin test does: the
     coefficient download equals the T.81 G.1.2 model, and the picture equals the oracle port's back end run on the model's
-    coefficients.  Parity with the reference stays unpinned: the reference cannot decode progressive files at all."""
+    coefficients.  The four procedures themselves are pinned to the reference's decode_MCU_component by tests/test_progressive_streams.py
+    (this writer's full form, a bit-level model, oracle/ref_driver.cpp); the reference cannot decode a progressive FILE."""
     import oracle_lib
     import pjd_amd
     import jpeg_progressive as P

@@ -1404,10 +1404,13 @@ def test_pull_form_of_the_back_end_is_bit_exact():
     assert r.returncode == 0 and "RESULT ok" in r.stdout, (r.stdout[-400:] + r.stderr[-400:])
 
 
-# ---- progressive frames: not reference-comparable, PARITY UNPINNED ----------------------------------------------
+# ---- progressive frames: libjpeg's files against their baseline twins (the procedures are pinned to the reference's
+# decode_MCU_component by tests/test_progressive_streams.py and tests/test_gpu_progressive_streams.py) ------------------------------
 def test_progressive_decodes_to_the_baseline_twin(ctx, port):
-    """The reference cannot decode progressive files (its scanner rejects them, src/jpeg_scanner.cpp:425-430), so nothing of
-    the reference pins this mode.  What is checked instead: libjpeg quantises a picture the same way whether it then writes a
+    """The reference cannot decode a progressive FILE (its scanner rejects them, src/jpeg_scanner.cpp:425-430).  Its four progressive
+    procedures are pinned elsewhere, on hand-built scans (tests/test_progressive_streams.py: a bit-level model against
+    decode_MCU_component; tests/test_gpu_progressive_streams.py: the kernel against the model); what is NOT the reference's is the
+    order of the blocks of a non-interleaved scan (T.81 A.2.3), and this test ties it to libjpeg's files: libjpeg quantises a picture the same way whether it then writes a
     baseline or a progressive file, so the coefficients in both files are the same -- and the progressive decode (opt-in scanner,
     pjd_k_progressive, dense back end) must give, bit for bit, the pixels the ORACLE gives for the baseline twin, with the
     standard zigzag map on both sides (PJD_F_STANDARD_ZIGZAG: the reference's map treats an explicit zero at slot 52 specially,
@@ -1457,7 +1460,8 @@ def test_progressive_decodes_to_the_baseline_twin(ctx, port):
 
 def test_progressive_in_a_mixed_batch_and_through_the_cli(ctx, port, tmp_path):
     """Progressive and baseline pictures in ONE batch (each keeps its own result); the pipelined batcher with scan option;
-    `bin/decoder --progressive` writes a BMP where the plain CLI prints the reference's rejection."""
+    `bin/decoder --progressive` writes a BMP where the plain CLI prints the reference's rejection.  Pillow's files only: the forms an
+    encoder does not pick, the error paths and what is pinned to the reference are in tests/test_gpu_progressive_streams.py."""
     import io
     import subprocess
     import pjd_amd

@@ -28,5 +28,7 @@ def test_scanner_and_planner_under_asan_ubsan(tmp_path):
     assert b.returncode == 0, b.stderr[-3000:]
     env = dict(os.environ, PJD_FUZZ_REPS="6", ASAN_OPTIONS="detect_leaks=1:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
     env.pop("LD_PRELOAD", None)
-    r = subprocess.run([str(exe)] + sorted(glob.glob(os.path.join(HERE, "golden", "*.jpg"))), capture_output=True, text=True, timeout=600, env=env)
+    files = sorted(glob.glob(os.path.join(HERE, "golden", "*.jpg"))) + sorted(glob.glob(os.path.join(HERE, "golden", "progressive", "*.jpg")))
+    assert any(os.path.basename(f).startswith("prog_") for f in files)
+    r = subprocess.run([str(exe)] + files, capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0 and "no sanitizer report" in r.stdout, (r.stdout[-500:], r.stderr[-3000:])
