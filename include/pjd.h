@@ -20,6 +20,8 @@
  *                                                       1/2, 1/4 or 1/8 scale (libjpeg scale_num/scale_denom)
  *   (none: an addition)                                 PJD_OUT_RGB8_PLANAR + pjd_batch_bind_output: pictures as planar
  *                                                       R, G, B channels in device memory the caller owns (tensors)
+ *   (none: an addition)                                 pjd_batch_set_resize + pjd_resize_tap: every picture of a ragged batch
+ *                                                       resampled to a size of its own inside the decode (one [N,3,H,W] tensor)
  *
  * Plain pointers and sizes only; no C++ or torch types.  Thread model: one
  * submitting thread per pjd_ctx (the reference has one consumer thread,
@@ -203,7 +205,7 @@ typedef struct pjd_batch_info {
     int32_t  n_images;
     uint64_t pixels;                   /* sum of width*height of the SOURCE pictures (the decode work, whatever the scale) */
     uint64_t ecs_bytes;                /* sum of ecs_len                                      */
-    uint64_t out_bytes;                /* sum of output sizes, each at the picture's output scale (PJD_F_SCALE_*) */
+    uint64_t out_bytes;                /* sum of output sizes, each at the picture's output scale (PJD_F_SCALE_*), or resized (pjd_batch_set_resize) */
     uint64_t coef_bytes;               /* lane streams + transposed bitstream words + dense scratch in HBM */
     uint64_t n_data_units;
     uint64_t n_subsequences;           /* Huffman decode lanes                                */
@@ -300,6 +302,47 @@ uint64_t pjd_batch_output_offset(pjd_batch *b, int image);
  * Where the memory comes from a sub-allocator (torch's caching allocator), "the allocation" above is the allocator's whole
  * segment: that check catches a wild capacity, it does not prove that the range is the caller's own tensor.                    */
 int  pjd_batch_bind_output(pjd_batch *b, void *device_base, uint64_t capacity, const uint64_t *offsets);
+/* ---- resize on decode ------------------------------------------------------------------------------------------------------ *
+ * pjd_batch_set_resize: picture i of the batch leaves the decode as out_w[i] x out_h[i] pixels (n_images entries each), whatever its
+ * own size: a ragged batch becomes pictures of one size, i.e. one uint8[N][3][H][W] tensor when bound at offsets i * 3 * H * W.
+ *
+ * THE ARITHMETIC (normative).  Let P be the sw x sh picture the library produces for the descriptor without this call -- the
+ * reference's picture, or the partial picture with grey after an entropy-coding error, box-filtered if PJD_F_SCALE_* is set -- and
+ * its 8-bit R, G, B the source.  For a target of tw x th each axis is handled on its own: with sn source samples, dn target samples
+ * and the target index i (integer arithmetic, divisions round down):
+ *     X  = (2*i + 1)*sn - dn                     (64-bit; this is 2*dn*((i + 0.5)*sn/dn - 0.5))
+ *     X  = clamp(X, 0, 2*dn*(sn - 1))
+ *     i0 = X / (2*dn)
+ *     w  = ((X - i0*2*dn)*256 + dn) / (2*dn)     (0..256)
+ *     i1 = min(i0 + 1, sn - 1)
+ * and per channel, with (x0, x1, wx) for the column and (y0, y1, wy) for the row of the target pixel:
+ *     out = ((256-wy)*((256-wx)*P[y0][x0] + wx*P[y0][x1]) + wy*((256-wx)*P[y1][x0] + wx*P[y1][x1]) + 32768) >> 16
+ * This is the bilinear filter with half-pixel centres -- torch.nn.functional.interpolate(mode="bilinear", align_corners=False,
+ * antialias=False) -- with the weights quantised to 1/256 and ONE rounding: it differs from that filter computed in float64 and
+ * rounded to nearest by at most 1 level (each quantised weight is off by at most 1/512: under 0.4981 levels per axis, under 0.9962
+ * before the one rounding).  Every intermediate fits 24 bits (at most 16 744 448).  A target equal to the source size reproduces P
+ * byte for byte (every w is 0).  pjd_resize_tap is the tap computation on its own, host only (no device needed), and the very
+ * code the kernel runs: PJD_E_ARG if src_n or dst_n is 0 or above 65535 or i >= dst_n; i0, i1, w may each be NULL.
+ * ADVICE: plain bilinear aliases when it shrinks by more than about 2x per axis.  Pre-scale with PJD_F_SCALE_*: choose the largest
+ * s of 1, 2, 4, 8 with ceil(W/s) >= tw and ceil(H/s) >= th (the box filter takes the bulk of the reduction, and less is decoded);
+ * the bilinear step then shrinks by less than 2x on the axis that limits s (on both where picture and target have one aspect ratio;
+ * beyond s = 8 nothing is left to take, and the other axis of a picture squeezed out of shape keeps its larger factor).
+ *
+ * CALL ORDER.  After pjd_batch_create and before any pjd_batch_bind_output / _upload / _capture / _decode of the batch, once:
+ * PJD_E_STATE otherwise.  PJD_E_ARG (pjd_last_error names the picture) for a null array, a target dimension of 0 or above 65535,
+ * a PJD_OUT_BMP batch, a batch that holds a shard (shard_n_segs != 0: a shard's picture is only partly written).
+ * FROM THEN ON pjd_batch_output_size(b, i) is 3 * out_w[i] * out_h[i]; pjd_batch_output_offset, _packed_size, _device_output,
+ * _download, _download_packed and _bind_output speak about the resized pictures (offsets in the library's own buffer stay 256-byte
+ * aligned; bind_output checks its ranges against the resized sizes and promises no alignment, as before).  PJD_OUT_RGB8_PLANAR gives
+ * uint8[3][th][tw], PJD_OUT_RGB8 tight rows of 3 * tw bytes.  Every decode writes every byte of every picture's range and no byte
+ * outside it.  The picture at its decode size lives in an intermediate buffer of the batch (in the batch's output format; counted in
+ * pjd_batch_info::device_bytes, and not given up by pjd_batch_bind_output, which redirects the resized pictures alone);
+ * pjd_batch_info::out_bytes is the sum of the resized sizes, `pixels` stays the source pixels.  The resample is one more launch on
+ * pjd_stream(ctx) behind the back end of every decode (part of a captured graph; pjd_batch_decode_timed names it "resize"), and
+ * runs again after the exact-kernel fallback of pjd_batch_sync.  Status words, coefficients (pjd_batch_download_coefficients) and
+ * pjd_plan_info are unaffected.                                                                                                  */
+int  pjd_batch_set_resize(pjd_batch *b, const uint32_t *out_w, const uint32_t *out_h);
+int  pjd_resize_tap(uint32_t src_n, uint32_t dst_n, uint32_t i, uint32_t *i0, uint32_t *i1, uint32_t *w);
 int  pjd_batch_get_info(pjd_batch *b, pjd_batch_info *info);
 uint64_t pjd_batch_output_size(pjd_batch *b, int image);
 void *pjd_batch_device_output(pjd_batch *b, int image);      /* device pointer (HBM)          */

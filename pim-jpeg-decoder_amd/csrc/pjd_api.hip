@@ -184,7 +184,21 @@ struct pjd_batch {
     // pjd_batch_bind_output: dev.out is the caller's memory (never freed, zeroed or pooled here)
     bool bound = false, bound_offsets = false;   // bound_offsets: the caller chose the picture offsets (no packed download)
     uint64_t bound_capacity = 0;
-    std::vector<uint64_t> packed_off;            // the planner's picture offsets (the packed layout), kept for a second bind
+    std::vector<uint64_t> packed_off;            // the packed layout of the results (256-byte aligned offsets), kept for a second bind
+    // Where the RESULT of a decode lies -- what download, output_offset / _size, device_output and bind_output speak about -- as
+    // opposed to where the back end writes (dev.out + PjdDevImage::out_off).  The two are one and the same (res_out == dev.out, the
+    // planner's offsets and sizes) until pjd_batch_set_resize separates them: the back end then keeps writing dev.out, the batch's
+    // own buffer at the planner's offsets (the intermediate), and the resample launch writes the pictures at their target sizes
+    // into res_out -- a second buffer of the batch, or the caller's memory once bound.
+    uint8_t *res_out = nullptr;
+    std::vector<uint64_t> res_off, res_bytes;
+    uint64_t res_buf_bytes = 0, res_out_bytes = 0;   // packed size (what pjd_batch_packed_size reports), sum of res_bytes
+    bool resized = false;                        // pjd_batch_set_resize
+    std::vector<uint32_t> rs_w, rs_h;
+    PjdDevResize *h_rs = nullptr, *d_rs = nullptr;   // the resample work list: page-locked / HBM, [n_images] records ...
+    uint32_t *d_rs_prefix = nullptr;             // ... followed by the prefix sum of tiles, [n_images + 1]
+    size_t rs_bytes = 0;
+    uint32_t rs_tiles = 0;
 };
 
 extern "C" {
@@ -403,6 +417,9 @@ int pjd_batch_create(pjd_ctx *ctx, const pjd_image_desc *images, int n_images, i
     b->dev.word_rows = PJD_WORD_ROWS(P.sub_bytes);
     b->dev.lane_cap = P.lane_cap;
     b->dev.max_lut_bytes = P.max_lut_bytes;
+    b->res_out = b->dev.out;
+    for (int i = 0; i < n_images; i++) { b->res_off.push_back(P.images[i].out_off); b->res_bytes.push_back(P.host[i].out_bytes); }
+    b->res_buf_bytes = P.out_buf_bytes; b->res_out_bytes = P.out_bytes;
     *out = b;
     return PJD_OK;
 }
@@ -418,7 +435,9 @@ int pjd_batch_upload(pjd_batch *b)
     HIP_TRY(ctx, hipMemcpyAsync(b->d_in, b->h_in, b->in_bytes, hipMemcpyHostToDevice, s));
     // BMP row padding stays zero.  RGB8 and planar pictures are written whole by every decode, which is what a bound buffer
     // (pjd_batch_bind_output: the caller's memory, never BMP) relies on: it is not touched here.
-    if (!b->bound) HIP_TRY(ctx, hipMemsetAsync(b->dev.out, 0, P.out_buf_bytes, s));
+    // With a resize set dev.out is the batch's intermediate, bound or not; the resized pictures are RGB8 or planar, written whole.
+    if (!b->bound || b->resized) HIP_TRY(ctx, hipMemsetAsync(b->dev.out, 0, P.out_buf_bytes, s));
+    if (b->resized) HIP_TRY(ctx, hipMemcpyAsync(b->d_rs, b->h_rs, b->rs_bytes, hipMemcpyHostToDevice, s));      // the resample work list (page-locked)
     b->uploaded = true;
     return PJD_OK;
 }
@@ -562,6 +581,12 @@ int enqueue_decode(pjd_batch *b, pjd_timings *timings, bool use_groups)
         pjd_launch_idct_colour(s, b->dev, b->d_iwgs_dense, b->d_seq_base, (uint32_t)P.iwgs_dense.size(), P.scaled, P.planar);
         kt.mark("exact_path");
     }
+    if (b->resized) {
+        // resize on decode: every picture from the intermediate (dev.out) to its target size in the result buffer, one launch behind
+        // whatever form the back end took (the groups' streams have joined `s` above)
+        pjd_launch_resize(s, b->dev.out, b->res_out, b->d_rs, b->d_rs_prefix, b->dev.n_images, b->rs_tiles, P.planar);
+        kt.mark("resize");
+    }
     HIP_TRY(ctx, hipGetLastError());
     kt.finish();
     b->decoded = true;
@@ -641,6 +666,8 @@ int settle(pjd_batch *b)
             pjd_launch_huff_sequential(s, dv, d_list, d_base, (uint32_t)fb.size());
             pjd_launch_idct_colour(s, dv, d_wgs, d_base, (uint32_t)fb_wgs.size(), P.scaled, P.planar);
             if (ev1) (void)hipEventRecord(ev1, s);
+            // the pictures just decoded again changed in the intermediate: resample (the whole batch: a rare path)
+            if (b->resized) pjd_launch_resize(s, b->dev.out, b->res_out, b->d_rs, b->d_rs_prefix, b->dev.n_images, b->rs_tiles, P.planar);
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipMemcpyAsync(b->h_status, b->dev.status, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s);
@@ -736,7 +763,7 @@ int pjd_batch_download(pjd_batch *b, uint8_t *const *out, int32_t *status)
     PjdPlan &P = b->plan;
     if (out)
         for (size_t i = 0; i < P.images.size(); i++)
-            if (out[i]) HIP_TRY(ctx, hipMemcpyAsync(out[i], b->dev.out + P.images[i].out_off, P.host[i].out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+            if (out[i]) HIP_TRY(ctx, hipMemcpyAsync(out[i], b->res_out + b->res_off[i], b->res_bytes[i], hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (status)
         for (size_t i = 0; i < P.images.size(); i++) status[i] = b->h_status[i] & 0xFF;
@@ -751,9 +778,9 @@ int pjd_batch_download_packed(pjd_batch *b, uint8_t *host, uint64_t capacity, in
     PjdPlan &P = b->plan;
     hipSetDevice(ctx->device);
     if (b->bound_offsets) { ctx->err = "download_packed: the batch is bound with explicit picture offsets (no packed layout)"; return PJD_E_STATE; }
-    if (capacity < P.out_buf_bytes) { ctx->err = "download_packed: buffer smaller than pjd_batch_packed_size"; return PJD_E_ARG; }
+    if (capacity < b->res_buf_bytes) { ctx->err = "download_packed: buffer smaller than pjd_batch_packed_size"; return PJD_E_ARG; }
     // a bound buffer need not reach past its last picture (the packed size is rounded up to 256 bytes)
-    const uint64_t copy_bytes = b->bound && b->bound_capacity < P.out_buf_bytes ? b->bound_capacity : P.out_buf_bytes;
+    const uint64_t copy_bytes = b->bound && b->bound_capacity < b->res_buf_bytes ? b->bound_capacity : b->res_buf_bytes;
     int rc = settle(b);
     if (rc != PJD_OK) return rc;
     // The runtime's copy (SDMA engine) by default.  PJD_DOWNLOAD=kernel: a small copy kernel on the device's download
@@ -763,7 +790,7 @@ int pjd_batch_download_packed(pjd_batch *b, uint8_t *host, uint64_t capacity, in
     void *mapped = nullptr;
     static const bool by_kernel = [] { const char *e = std::getenv("PJD_DOWNLOAD"); return e && !std::strcmp(e, "kernel"); }();
     hipPointerAttribute_t attr;
-    const bool pinned = by_kernel && !b->bound && (P.out_buf_bytes % 16) == 0 && ((uintptr_t)host % 16) == 0 &&
+    const bool pinned = by_kernel && !b->bound && (b->res_buf_bytes % 16) == 0 && ((uintptr_t)host % 16) == 0 &&
                         hipPointerGetAttributes(&attr, host) == hipSuccess && attr.type == hipMemoryTypeHost &&
                         hipHostGetDevicePointer(&mapped, host, 0) == hipSuccess && mapped;
     if (by_kernel && !pinned) (void)hipGetLastError();
@@ -772,13 +799,13 @@ int pjd_batch_download_packed(pjd_batch *b, uint8_t *host, uint64_t capacity, in
         // settle() has synchronised ctx->stream: the pictures are final
         hipEvent_t done;
         HIP_TRY(ctx, hipEventCreateWithFlags(&done, hipEventDisableTiming));
-        pjd_launch_copy_out(ds, b->dev.out, mapped, P.out_buf_bytes);
+        pjd_launch_copy_out(ds, b->res_out, mapped, b->res_buf_bytes);
         hipError_t e = hipEventRecord(done, ds);
         if (e == hipSuccess) e = hipEventSynchronize(done);
         (void)hipEventDestroy(done);
         HIP_TRY(ctx, e);
     } else {
-        HIP_TRY(ctx, hipMemcpyAsync(host, b->dev.out, copy_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(host, b->res_out, copy_bytes, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
     if (status)
@@ -786,12 +813,12 @@ int pjd_batch_download_packed(pjd_batch *b, uint8_t *host, uint64_t capacity, in
     return PJD_OK;
 }
 
-uint64_t pjd_batch_packed_size(pjd_batch *b) { return b ? b->plan.out_buf_bytes : 0; }
+uint64_t pjd_batch_packed_size(pjd_batch *b) { return b ? b->res_buf_bytes : 0; }
 
 uint64_t pjd_batch_output_offset(pjd_batch *b, int image)
 {
     if (!b || image < 0 || (size_t)image >= b->plan.images.size()) return 0;
-    return b->plan.images[image].out_off;
+    return b->res_off[image];
 }
 
 int pjd_batch_bind_output(pjd_batch *b, void *device_base, uint64_t capacity, const uint64_t *offsets)
@@ -820,10 +847,10 @@ int pjd_batch_bind_output(pjd_batch *b, void *device_base, uint64_t capacity, co
         }
     }
     const size_t n = P.images.size();
-    if (b->packed_off.empty()) for (const PjdDevImage &g : P.images) b->packed_off.push_back(g.out_off);
+    if (b->packed_off.empty()) b->packed_off = b->res_off;
     std::vector<std::pair<uint64_t, uint64_t>> ranges(n);            // (offset, size) of every picture
     for (size_t i = 0; i < n; i++) {
-        ranges[i] = {offsets ? offsets[i] : b->packed_off[i], P.host[i].out_bytes};
+        ranges[i] = {offsets ? offsets[i] : b->packed_off[i], b->res_bytes[i]};
         if (ranges[i].first > capacity || ranges[i].second > capacity - ranges[i].first) { ctx->err = fmt_image("bind_output: picture %d ends beyond the capacity", (int)i); return PJD_E_ARG; }
     }
     {
@@ -832,22 +859,104 @@ int pjd_batch_bind_output(pjd_batch *b, void *device_base, uint64_t capacity, co
         for (size_t i = 1; i < n; i++)
             if (sorted[i - 1].first + sorted[i - 1].second > sorted[i].first) { ctx->err = "bind_output: picture ranges overlap"; return PJD_E_ARG; }
     }
-    // from here on nothing fails.  The batch's own buffer goes back to the pool; the planner's image records (and their copy in
-    // the input blob, which pjd_batch_upload sends) take the bound offsets.
+    // from here on nothing fails.  The batch's own result buffer goes back to the pool.  Without a resize the result is what the back
+    // end writes: the planner's image records (and their copy in the input blob, which pjd_batch_upload sends) take the bound
+    // offsets.  With one, only the resample's work list does: the back end keeps writing the intermediate at the planner's offsets.
     if (!b->bound)
         for (size_t k = 0; k < b->dev_blocks.size(); k++)
-            if (b->dev_blocks[k].p == (void *)b->dev.out) {
+            if (b->dev_blocks[k].p == (void *)b->res_out) {
                 if (!ctx->dev_pool.give(b->dev_blocks[k].p, b->dev_blocks[k].bytes, ctx->pool_cap)) hipFree(b->dev_blocks[k].p);
                 b->dev_blocks.erase(b->dev_blocks.begin() + (long)k);
-                b->device_bytes -= P.out_buf_bytes;
+                b->device_bytes -= b->res_buf_bytes;
                 break;
             }
-    PjdDevImage *h_images = reinterpret_cast<PjdDevImage *>(b->h_in + ((uint8_t *)b->d_images - b->d_in));
-    for (size_t i = 0; i < n; i++) P.images[i].out_off = h_images[i].out_off = ranges[i].first;
-    b->dev.out = (uint8_t *)device_base;
+    for (size_t i = 0; i < n; i++) b->res_off[i] = ranges[i].first;
+    b->res_out = (uint8_t *)device_base;
+    if (b->resized) {
+        for (size_t i = 0; i < n; i++) b->h_rs[i].dst_off = ranges[i].first;
+    } else {
+        PjdDevImage *h_images = reinterpret_cast<PjdDevImage *>(b->h_in + ((uint8_t *)b->d_images - b->d_in));
+        for (size_t i = 0; i < n; i++) P.images[i].out_off = h_images[i].out_off = ranges[i].first;
+        b->dev.out = (uint8_t *)device_base;
+    }
     b->bound = true;
     b->bound_offsets = offsets != nullptr;
     b->bound_capacity = capacity;
+    return PJD_OK;
+}
+
+int pjd_resize_tap(uint32_t src_n, uint32_t dst_n, uint32_t i, uint32_t *i0, uint32_t *i1, uint32_t *w)
+{
+    if (src_n == 0 || src_n > 65535u || dst_n == 0 || dst_n > 65535u || i >= dst_n) return PJD_E_ARG;
+    uint32_t a, c, d;
+    pjd_resize_tap_calc(src_n, dst_n, i, a, c, d);
+    if (i0) *i0 = a;
+    if (i1) *i1 = c;
+    if (w) *w = d;
+    return PJD_OK;
+}
+
+int pjd_batch_set_resize(pjd_batch *b, const uint32_t *out_w, const uint32_t *out_h)
+{
+    if (!b) return PJD_E_ARG;
+    pjd_ctx *ctx = b->ctx;
+    PjdPlan &P = b->plan;
+    if (b->resized) { ctx->err = "set_resize: already set for this batch"; return PJD_E_STATE; }
+    if (b->bound) { ctx->err = "set_resize after bind_output"; return PJD_E_STATE; }
+    if (b->uploaded) { ctx->err = "set_resize after upload"; return PJD_E_STATE; }
+    if (!out_w || !out_h) { ctx->err = "set_resize: null size array"; return PJD_E_ARG; }
+    if (P.out_format == PJD_OUT_BMP) { ctx->err = "set_resize: a BMP batch cannot be resized (PJD_OUT_RGB8 or PJD_OUT_RGB8_PLANAR)"; return PJD_E_ARG; }
+    const size_t n = P.images.size();
+    uint64_t tiles = 0;
+    for (size_t i = 0; i < n; i++) {
+        if (out_w[i] == 0 || out_w[i] > 65535u || out_h[i] == 0 || out_h[i] > 65535u) {
+            ctx->err = fmt_image("set_resize: picture %d: target width and height must be 1..65535", (int)i);
+            return PJD_E_ARG;
+        }
+        if (P.host[i].shard) { ctx->err = fmt_image("set_resize: picture %d is a shard (its picture is only partly written)", (int)i); return PJD_E_ARG; }
+        tiles += (uint64_t)((out_w[i] + PJD_RS_COLS - 1) / PJD_RS_COLS) * ((out_h[i] + PJD_RS_ROWS - 1) / PJD_RS_ROWS);
+    }
+    if (tiles >= (1ull << 31)) { ctx->err = "set_resize: the targets of this batch are too large for one launch"; return PJD_E_ARG; }
+    hipSetDevice(ctx->device);
+    // the work list (page-locked; pjd_batch_upload sends it, pjd_batch_bind_output may still change its target offsets) and the
+    // result buffer: packed, 256-byte aligned offsets, as the planner lays out a batch's own buffer
+    const size_t rs_bytes = n * sizeof(PjdDevResize) + (n + 1) * sizeof(uint32_t);
+    void *h_rs = nullptr, *d_rs = nullptr, *d_res = nullptr;
+    std::vector<uint64_t> off(n), bytes(n);
+    uint64_t pos = 0, sum = 0;
+    for (size_t i = 0; i < n; i++) {
+        off[i] = pos; bytes[i] = 3ull * out_w[i] * out_h[i];
+        pos = (pos + bytes[i] + 255) & ~(uint64_t)255;
+        sum += bytes[i];
+    }
+    int rc = pool_pin_alloc(ctx, &h_rs, rs_bytes, b->pin_blocks);
+    if (rc == PJD_OK) rc = pool_dev_alloc(ctx, &d_rs, rs_bytes, b->dev_blocks);
+    if (rc == PJD_OK) rc = pool_dev_alloc(ctx, &d_res, (size_t)pos, b->dev_blocks);
+    if (rc != PJD_OK) return rc;                           // what was taken stays with the batch until it is destroyed
+    b->device_bytes += rs_bytes + pos;
+    b->h_rs = (PjdDevResize *)h_rs; b->d_rs = (PjdDevResize *)d_rs; b->rs_bytes = rs_bytes;
+    b->d_rs_prefix = (uint32_t *)(b->d_rs + n);
+    uint32_t *prefix = (uint32_t *)(b->h_rs + n);
+    uint32_t t = 0;
+    for (size_t i = 0; i < n; i++) {
+        const PjdDevImage &g = P.images[i];
+        PjdDevResize &r = b->h_rs[i];
+        uint32_t sw = 0, sh = 0;
+        pjd_scaled_dims(g.width, g.height, (g.flags & PJD_IF_SCALE_MASK) >> PJD_IF_SCALE_SHIFT << 4, &sw, &sh);
+        r.src_off = g.out_off; r.dst_off = off[i];
+        r.sw = sw; r.sh = sh; r.src_stride = g.out_stride;
+        r.tw = out_w[i]; r.th = out_h[i];
+        r.col_tiles = (out_w[i] + PJD_RS_COLS - 1) / PJD_RS_COLS;
+        prefix[i] = t;
+        t += r.col_tiles * ((out_h[i] + PJD_RS_ROWS - 1) / PJD_RS_ROWS);
+    }
+    prefix[n] = t;
+    b->rs_tiles = t;
+    b->rs_w.assign(out_w, out_w + n); b->rs_h.assign(out_h, out_h + n);
+    b->res_out = (uint8_t *)d_res;
+    b->res_off = off; b->res_bytes = bytes;
+    b->res_buf_bytes = pos; b->res_out_bytes = sum;
+    b->resized = true;
     return PJD_OK;
 }
 
@@ -867,7 +976,7 @@ int pjd_batch_get_info(pjd_batch *b, pjd_batch_info *info)
     hipSetDevice(b->ctx->device);
     std::memset(info, 0, sizeof *info);
     info->n_images = (int32_t)P.images.size();
-    info->pixels = P.pixels; info->ecs_bytes = P.ecs_bytes; info->out_bytes = P.out_bytes;
+    info->pixels = P.pixels; info->ecs_bytes = P.ecs_bytes; info->out_bytes = b->res_out_bytes;
     info->coef_bytes = P.n_ent * 2 + P.n_words * 4 + P.dense_du * 128;
     info->n_data_units = P.n_du;
     info->n_subsequences = P.subs.size();
@@ -981,13 +1090,13 @@ int pjd_plan_step_bits(const pjd_image_desc *image, uint32_t *step_bits_x256)
 uint64_t pjd_batch_output_size(pjd_batch *b, int image)
 {
     if (!b || image < 0 || (size_t)image >= b->plan.host.size()) return 0;
-    return b->plan.host[image].out_bytes;
+    return b->res_bytes[image];
 }
 
 void *pjd_batch_device_output(pjd_batch *b, int image)
 {
     if (!b || image < 0 || (size_t)image >= b->plan.host.size()) return nullptr;
-    return b->dev.out + b->plan.images[image].out_off;
+    return b->res_out + b->res_off[image];
 }
 
 void *pjd_batch_device_status(pjd_batch *b) { return b ? (void *)b->dev.status : nullptr; }

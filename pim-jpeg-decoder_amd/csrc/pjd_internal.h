@@ -346,3 +346,44 @@ static inline __host__ __device__ uint64_t pjd_pack_state(uint32_t p, uint32_t c
 {
     return (uint64_t)p | ((uint64_t)c << 32) | ((uint64_t)z << 40);
 }
+
+// ---- resize on decode (pjd_batch_set_resize; the arithmetic is normative: include/pjd.h) -------------------------------------
+// One axis of the bilinear filter: target sample i of dn, over sn source samples -> the two source samples i0, i1 and the weight w
+// of i1 in 1/256 (0..256).  THE implementation: pjd_resize_tap exports it to the host, pjd_k_resize runs it per column and per row.
+// sn, dn in 1..65535, i < dn.  Where sn * dn < 2^31 every value fits 32 bits (X < 2 * dn * sn, the remainder times 256 < 2^25) and the
+// two divisions are 32-bit ones -- every picture anyone decodes; the 64-bit form is the same arithmetic.
+static inline __host__ __device__ void pjd_resize_tap_calc(uint32_t sn, uint32_t dn, uint32_t i, uint32_t &i0, uint32_t &i1, uint32_t &w)
+{
+    const uint32_t d2 = 2u * dn;
+    if ((uint64_t)sn * dn < (1ull << 31)) {
+        const uint32_t a = (2u * i + 1u) * sn;                  // X = a - dn, clamped to [0, 2 * dn * (sn - 1)]
+        uint32_t X = a > dn ? a - dn : 0u;
+        const uint32_t hi = d2 * (sn - 1u);
+        X = X < hi ? X : hi;
+        i0 = X / d2;
+        w = ((X - i0 * d2) * 256u + dn) / d2;
+    } else {
+        const uint64_t a = (uint64_t)(2u * i + 1u) * sn;
+        uint64_t X = a > dn ? a - dn : 0u;
+        const uint64_t hi = (uint64_t)d2 * (sn - 1u);
+        X = X < hi ? X : hi;
+        i0 = (uint32_t)(X / d2);
+        w = (uint32_t)(((X - (uint64_t)i0 * d2) * 256u + dn) / d2);
+    }
+    i1 = i0 + 1u < sn ? i0 + 1u : sn - 1u;
+}
+
+// The work list of the resample launch (pjd_k_resize.hip), built by pjd_batch_set_resize: one record per picture and the prefix
+// sum of their TILES.  A tile is PJD_RS_ROWS target rows x PJD_RS_COLS target columns, the work of one wave: lane l makes
+// PJD_RS_PX adjacent pixels of every row of the tile.
+#define PJD_RS_PX    4
+#define PJD_RS_COLS  (64 * PJD_RS_PX)
+#define PJD_RS_ROWS  8
+#define PJD_RS_WAVES 4                 // waves (tiles) per workgroup
+struct PjdDevResize {
+    uint64_t src_off;                  // the picture at its decode size in the intermediate buffer (where the back end wrote it)
+    uint64_t dst_off;                  // the resized picture in the result buffer (the batch's, or the caller's: any offset)
+    uint32_t sw, sh, src_stride;       // source: pixels, and bytes per row (3 * sw interleaved, sw planar: a plane row)
+    uint32_t tw, th;                   // target
+    uint32_t col_tiles;                // tiles per tile row: ceil(tw / PJD_RS_COLS)
+};

@@ -420,6 +420,7 @@ int pjd_make_plan(const pjd_image_desc *images, int n, int out_format, PjdPlan &
             seg_lo = d.shard_first_seg; seg_hi = seg_lo + d.shard_n_segs;
         }
         h.sequential = sequential;
+        h.shard = d.shard_n_segs != 0;
         if (sequential) g.flags |= PJD_IF_SEQUENTIAL;
 
         uint64_t byte_lo = 0, byte_hi = d.ecs_len;

@@ -10,6 +10,7 @@ struct PjdHostImage {
     const uint8_t *ecs_src;     // caller memory: first byte to upload
     uint64_t ecs_copy_len;      // bytes to upload
     uint64_t out_bytes;         // size of this picture in the chosen output format, at its output scale
+    bool shard;                 // decodes only some restart segments (shard_n_segs != 0): the picture is partly written
     bool sequential;            // routed to the exact one-lane kernel up front (or a progressive frame: pjd_k_progressive)
 };
 

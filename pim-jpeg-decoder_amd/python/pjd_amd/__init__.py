@@ -165,6 +165,10 @@ def dev_lib():
         L.pjd_batch_output_offset.argtypes = [vp, i32]
         L.pjd_batch_bind_output.restype = i32
         L.pjd_batch_bind_output.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.pjd_batch_set_resize.restype = i32
+        L.pjd_batch_set_resize.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.pjd_resize_tap.restype = i32
+        L.pjd_resize_tap.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.pjd_host_alloc.restype = vp
         L.pjd_host_alloc.argtypes = [C.c_uint64]
         L.pjd_host_free.argtypes = [vp]
@@ -319,6 +323,7 @@ class Batch:
         h = C.c_void_p()
         ctx._check(self.L.pjd_batch_create(ctx._h, arr, self.n, out_format, C.byref(h)), "pjd_batch_create")
         self._h = h
+        self._resize = None                        # set_resize: the (h, w) of every picture
 
     def __enter__(self):
         return self
@@ -368,12 +373,30 @@ class Batch:
     def output_shape(self, i):
         """Shape of picture i as download() returns it: (h, w, 3) for OUT_RGB8, (3, h, w) for OUT_RGB8_PLANAR, flat for OUT_BMP."""
         d = self._descs[i]
-        w, h = scaled_dims(d.width, d.height, d.flags)
+        if self._resize is not None:
+            h, w = self._resize[i]
+        else:
+            w, h = scaled_dims(d.width, d.height, d.flags)
         if self.out_format == OUT_RGB8:
             return (h, w, 3)
         if self.out_format == OUT_RGB8_PLANAR:
             return (3, h, w)
         return (self.output_size(i),)
+
+    def set_resize(self, sizes):
+        """pjd_batch_set_resize: picture i leaves the decode resampled to sizes[i] = (h, w), with the bilinear filter include/pjd.h
+        specifies bit for bit.  Once, before bind_output() / upload(); not for OUT_BMP, not for shards.  output_size, output_shape,
+        output_offset, packed_size, download and bind_output speak about the resized pictures from then on."""
+        if len(sizes) != self.n:
+            raise ValueError("set_resize: one (h, w) per picture")
+        sizes = [(int(h), int(w)) for h, w in sizes]
+        for h, w in sizes:
+            if not (0 <= h < 2 ** 32 and 0 <= w < 2 ** 32):
+                raise ValueError("set_resize: sizes must fit 32 bits")
+        ws = (C.c_uint32 * max(self.n, 1))(*[w for _, w in sizes])
+        hs = (C.c_uint32 * max(self.n, 1))(*[h for h, _ in sizes])
+        self.ctx._check(self.L.pjd_batch_set_resize(self._h, ws, hs), "pjd_batch_set_resize")
+        self._resize = sizes
 
     def bind_output(self, device_ptr, capacity, offsets=None):
         """pjd_batch_bind_output: pictures go into caller-owned device memory (`device_ptr`: a plain integer address, e.g. a
@@ -596,6 +619,15 @@ def plan_info(descs, out_format=OUT_RGB8):
     if rc != 0:
         raise PjdError(f"pjd_plan_info failed ({rc})")
     return {k: (list(getattr(bi, k)) if k == "flag_waves" else (float(getattr(bi, k)) if k == "exact_fallback_ms" else int(getattr(bi, k)))) for k, _ in bi._fields_}
+
+
+def resize_tap(src_n, dst_n, i):
+    """pjd_resize_tap (host only): (i0, i1, w) -- the two source samples target sample i of dst_n reads over src_n source samples,
+    and the weight of i1 in 1/256; the code the resize kernel runs.  ValueError outside 1..65535 / i >= dst_n."""
+    a, b, w = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    if not all(0 <= int(v) < 2 ** 32 for v in (src_n, dst_n, i)) or dev_lib().pjd_resize_tap(int(src_n), int(dst_n), int(i), C.byref(a), C.byref(b), C.byref(w)) != 0:
+        raise ValueError(f"resize_tap({src_n}, {dst_n}, {i}): sizes must be 1..65535 and i < dst_n")
+    return a.value, b.value, w.value
 
 
 def scaled_dims(width, height, flags=0):

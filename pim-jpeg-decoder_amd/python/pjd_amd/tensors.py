@@ -3,7 +3,10 @@
 The batch is bound (Batch.bind_output, pjd_batch_bind_output of include/pjd.h) to ONE torch.uint8 buffer this module allocates
 on the context's device; the back end writes the pictures straight into it -- planar R, G, B (OUT_RGB8_PLANAR, "CHW") by
 default -- and the results are views of that buffer.  No native code of its own.  torch is imported inside the functions that
-need it: uniform_output_shape() is pure.
+need it: uniform_output_shape() and pick_scale_flags() are pure.
+
+Pictures of different sizes become ONE [N, 3, H, W] tensor with decode_resized_batch_tensor: the library resamples every picture to
+H x W inside the decode (Batch.set_resize, pjd_batch_set_resize), after the box pre-scale pick_scale_flags chooses.
 
 torch ships a HIP runtime of its own.  A tensor's address means something to libpjd.so only if both use ONE runtime, which is the
 case when torch is loaded first (libpjd.so then binds to the runtime torch brought): `import torch` before the first pjd_amd call
@@ -49,10 +52,12 @@ def _torch():
     return torch
 
 
-def _run(ctx, descs, out_format, capacity, offsets, device):
-    """Create, bind to a fresh torch buffer, upload, decode, sync -> (buffer, batch offsets, statuses)."""
+def _run(ctx, descs, out_format, capacity, offsets, device, resize=None):
+    """Create, (set the resize,) bind to a fresh torch buffer, upload, decode, sync -> (buffer, batch offsets, statuses)."""
     torch = _torch()
     with ctx.batch(descs, out_format) as b:
+        if resize is not None:
+            b.set_resize(resize)
         cap = b.packed_size() if capacity is None else capacity
         buf = torch.empty(max(cap, 1), dtype=torch.uint8, device=device)
         # the block may be a recycled one that work queued on torch's current stream still reads: order that work before ours
@@ -91,3 +96,45 @@ def decode_to_batch_tensor(ctx, descs, device=None):
     size = c * h * w
     buf, _, st = _run(ctx, descs, pjd_amd.OUT_RGB8_PLANAR, n * size, [i * size for i in range(n)], device)
     return buf.view(n, c, h, w), st
+
+
+def pick_scale_flags(w, h, tw, th):
+    """The F_SCALE_* value to decode a w x h picture with before it is resized to tw x th: that of the largest s of 1, 2, 4, 8 with
+    ceil(w / s) >= tw and ceil(h / s) >= th, so that the bilinear step shrinks by less than 2x on the axis that limits s (s < 8) whenever
+    the source is at least the target; 0 when the target is larger than the source on either axis.  Pure."""
+    w, h, tw, th = int(w), int(h), int(tw), int(th)
+    for log in (3, 2, 1):
+        if (w + (1 << log) - 1) >> log >= tw and (h + (1 << log) - 1) >> log >= th:
+            return log << 4
+    return 0
+
+
+def prescaled_descs(descs, size):
+    """Copies of `descs` whose scale flags are pick_scale_flags for the target size = (H, W); the caller's descriptors are not
+    touched (the copies share their bitstream and table memory, which the caller keeps alive as for any batch).  No device."""
+    import ctypes
+    th, tw = size
+    out = []
+    for d in descs:
+        c = pjd_amd.ImageDesc()
+        ctypes.memmove(ctypes.byref(c), ctypes.byref(d), ctypes.sizeof(pjd_amd.ImageDesc))
+        c.flags = (int(d.flags) & ~pjd_amd.F_SCALE_MASK) | pick_scale_flags(d.width, d.height, tw, th)
+        out.append(c)
+    return out
+
+
+def decode_resized_batch_tensor(ctx, descs, size, prescale=True, device=None):
+    """Pictures of ANY sizes -> (uint8 tensor [N, 3, H, W], statuses), size = (H, W): every picture is resampled to H x W inside
+    the decode (the bilinear filter of include/pjd.h, pjd_batch_set_resize) and lands at offset i * 3 * H * W of one buffer, so
+    the result is one contiguous NCHW tensor with no copy after the decode, complete on return and readable on any torch stream
+    (module docstring, "Stream order").  prescale: decode copies of the descriptors at the reduced size pick_scale_flags chooses
+    (the box filter takes the bulk of a large reduction: no aliasing, and less to decode); else the descriptors' own flags hold."""
+    if len(descs) == 0:
+        raise ValueError("decode_resized_batch_tensor: no pictures")
+    th, tw = int(size[0]), int(size[1])
+    torch = _torch()
+    device = torch.device("cuda", ctx.device) if device is None else device
+    run = prescaled_descs(descs, (th, tw)) if prescale else descs
+    n, plane = len(descs), 3 * th * tw
+    buf, _, st = _run(ctx, run, pjd_amd.OUT_RGB8_PLANAR, n * plane, [i * plane for i in range(n)], device, resize=[(th, tw)] * n)
+    return buf.view(n, 3, th, tw), st
