@@ -408,7 +408,9 @@ int  pjd_split_rccl_selftest(int device_ordinal, uint64_t bytes);
 int  pjd_exec_dpu_payload(pjd_ctx *ctx, const uint32_t *metadata, int16_t *mcus, int n_dpus);
 
 /* Host-only planning: what a batch of these images would occupy (no device needed).
- * Fills everything in `info` except device_bytes / n_fallback.                   */
+ * Fills everything in `info` except device_bytes / n_fallback.  Plans as a context
+ * opened now would: PJD_PLAN_MODE and PJD_SUB_BYTES (a subsequence size forced for the
+ * whole batch, a multiple of 64 in 128..1024) of the environment apply, as in pjd_open. */
 int  pjd_plan_info(const pjd_image_desc *images, int n_images, int out_format, pjd_batch_info *info);
 /* Debug, host-only: the bound behind the size of a picture's lane streams -- the fewest bits of bitstream per step of the entropy
  * decoder's write pass (one symbol, or the pair one table lookup yields) that ANY stream coded with this picture's Huffman tables can

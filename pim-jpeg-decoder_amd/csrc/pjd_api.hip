@@ -1055,9 +1055,10 @@ int pjd_plan_info(const pjd_image_desc *images, int n_images, int out_format, pj
     if (!info) return PJD_E_ARG;
     PjdPlan P;
     std::string err;
-    int mode = PJD_PLAN_LATENCY;           // as pjd_open: the environment's plan mode
+    int mode = PJD_PLAN_LATENCY;           // as pjd_open: the environment's plan mode and subsequence size
     if (const char *pm = std::getenv("PJD_PLAN_MODE")) mode = (pm[0] == 't' || pm[0] == '1') ? PJD_PLAN_THROUGHPUT : PJD_PLAN_LATENCY;
-    int rc = pjd_make_plan(images, n_images, out_format, P, err, 0, mode);
+    const char *sb = std::getenv("PJD_SUB_BYTES");
+    int rc = pjd_make_plan(images, n_images, out_format, P, err, sb ? (uint32_t)std::atoi(sb) : 0, mode);
     if (rc != PJD_OK) return rc;
     std::memset(info, 0, sizeof *info);
     info->n_images = (int32_t)P.images.size();

@@ -8,9 +8,9 @@
 
 // ---- tunables -----------------------------------------------------------------
 #ifndef PJD_SUB_BYTES_MIN
-#define PJD_SUB_BYTES_MIN  128      // Huffman subsequence (bytes of bitstream per decode lane): chosen per batch
-#endif
-#define PJD_SUB_BYTES_MAX  1024     //   by the planner (multiple of 64 in this range), see pjd_plan.cpp
+#define PJD_SUB_BYTES_MIN  128      // Huffman subsequence (bytes of bitstream per decode lane): chosen per batch (a multiple of 64)
+#endif                              //   and then per picture (a multiple of 16: PJD_WORD_ROWS a multiple of 4, checkpoints on word
+#define PJD_SUB_BYTES_MAX  1024     //   boundaries) by the planner, in this range, see pjd_plan.cpp
 #define PJD_HUFF_LANES     64       // subsequences per wave: lanes exchange states by shuffles, no barriers
 #ifndef PJD_HUFF_WAVES
 #define PJD_HUFF_WAVES     2        // waves per Huffman workgroup; they share one table set in LDS

@@ -210,6 +210,9 @@ int pjd_make_plan(const pjd_image_desc *images, int n, int out_format, PjdPlan &
     // experiments: one walker threshold for every picture of the plan (pjd_internal.h); read once per plan
     int walk_max_env = -1;
     if (const char *e = std::getenv("PJD_WALK_MAX")) { const int v = std::atoi(e); walk_max_env = v < 0 ? 0 : v; }
+    // experiments: what an odd number of waves per picture costs beside its wave-bytes, in percent of one wave (the per-image choice below)
+    uint64_t odd_wave_pct = 0;
+    if (const char *e = std::getenv("PJD_ODD_WAVE_PCT")) { const int v = std::atoi(e); odd_wave_pct = (uint64_t)(v < 0 ? 0 : (v > 100 ? 100 : v)); }
 
     uint64_t ecs_off = 0, out_off = 0, du_total = 0, dense_seq = 0, lut_off = 0;
     uint32_t sb_max = SB;                          // largest per-image subsequence: sizes the word rows and the lane regions
@@ -462,8 +465,14 @@ int pjd_make_plan(const pjd_image_desc *images, int n, int out_format, PjdPlan &
         g.seg_base = (uint32_t)P.segs.size();
         g.lane_base = (uint32_t)P.subs.size();
         g.hwave_base = (uint32_t)P.hwaves.size();
-        // Subsequence size of this image: the batch's, nudged so that the image's lanes fill whole waves (a wave holds lanes of
-        // one image; at 832 B an ImageNet-sized picture is ~2.1 waves' worth, i.e. three waves, the last nearly empty).
+        // Subsequence size of this image: the batch's, moved so that the image's lanes fill whole waves (a wave holds lanes of
+        // one image; at 832 B an ImageNet-sized picture is ~2.1 waves' worth, i.e. three waves, the last nearly empty).  Every
+        // pass of a wave costs what 64 lanes of S bytes cost whatever the number of lanes that hold work, so the choice is by
+        // WAVE-BYTES, waves x S: of the nearest number of whole waves, one more and one fewer, each with the smallest S (a
+        // multiple of 16 bytes: PJD_WORD_ROWS stays a multiple of 4, the checkpoint spacing a whole number of words) within
+        // -30 % / +45 % of the batch's size and the absolute limits whose lanes fit, the cheapest.  (Before, only the
+        // nearest count was tried, in steps of 64 bytes: where it needed more than PJD_SUB_BYTES_MAX the picture kept the
+        // batch's size and a nearly empty last wave -- one lane slot in ten of the default batch; profiles/lane_fill.md.)
         uint32_t SBi = SB;
         if (!sequential && !sub_bytes_override) {
             auto seg_len = [&](uint32_t k) {
@@ -476,15 +485,39 @@ int pjd_make_plan(const pjd_image_desc *images, int n, int out_format, PjdPlan &
                 return nl;
             };
             const uint64_t n0 = lanes_for(SB);
-            if (n0 > PJD_HUFF_LANES / 2 && n0 % PJD_HUFF_LANES != 0) {
-                const uint64_t kw = (n0 + PJD_HUFF_LANES / 2) / PJD_HUFF_LANES;           // nearest number of whole waves
-                uint32_t best = SB;
-                // smallest multiple of 64 bytes (within -30 % / +45 % of the batch's size) whose lanes fit kw waves
-                const uint32_t lo = SB * 7 / 10 / 64 * 64 > PJD_SUB_BYTES_MIN ? SB * 7 / 10 / 64 * 64 : PJD_SUB_BYTES_MIN;
-                const uint32_t hi = SB * 29 / 20 < PJD_SUB_BYTES_MAX ? SB * 29 / 20 : PJD_SUB_BYTES_MAX;
-                for (uint32_t S = lo; S <= hi; S += 64)
-                    if (lanes_for(S) <= kw * PJD_HUFF_LANES) { best = S; break; }
-                if (lanes_for(best) <= kw * PJD_HUFF_LANES) SBi = best;
+            if (n0 > PJD_HUFF_LANES / 2) {
+                const uint64_t kw0 = (n0 + PJD_HUFF_LANES / 2) / PJD_HUFF_LANES;          // nearest number of whole waves
+                const uint32_t lo = SB * 7 / 10 / 16 * 16 > PJD_SUB_BYTES_MIN ? SB * 7 / 10 / 16 * 16 : PJD_SUB_BYTES_MIN;
+                const uint32_t hi = (SB * 29 / 20 < PJD_SUB_BYTES_MAX ? SB * 29 / 20 : PJD_SUB_BYTES_MAX) / 16 * 16;
+                uint64_t cost[3], waves[3], cheapest = ~0ull;
+                uint32_t size[3];
+                int nc = 0;
+                for (uint64_t kw = kw0 > 1 ? kw0 - 1 : 1; kw <= kw0 + 1; kw++) {
+                    if (lanes_for(hi) > kw * PJD_HUFF_LANES) continue;                    // not within the range
+                    uint32_t a = lo / 16, b = hi / 16;                                    // lanes_for never grows with S: bisect
+                    while (a < b) { const uint32_t m = (a + b) / 2; if (lanes_for(m * 16) <= kw * PJD_HUFF_LANES) b = m; else a = m + 1; }
+                    size[nc] = b * 16;
+                    waves[nc] = (lanes_for(size[nc]) + PJD_HUFF_LANES - 1) / PJD_HUFF_LANES;
+                    // an odd count leaves one wave alone in its workgroup where pictures do not share a table set
+                    cost[nc] = (waves[nc] * 100 + (waves[nc] & 1) * odd_wave_pct) * size[nc];
+                    if (cost[nc] < cheapest) cheapest = cost[nc];
+                    nc++;
+                }
+                // within about 1 % of the cheapest: an even number of waves first, then the longer lanes (fewer re-sync passes)
+                int pick = -1;
+                for (int k = 0; k < nc; k++) {
+                    if (cost[k] > cheapest + cheapest / 100) continue;
+                    const bool even = !(waves[k] & 1), even_p = pick >= 0 && !(waves[pick] & 1);
+                    if (pick < 0 || (even && !even_p) || (even == even_p && size[k] > size[pick])) pick = k;
+                }
+                // wave-bytes do not count everything: longer lanes lengthen every pass of every chain, shorter ones add re-sync passes,
+                // and the batch's size is where the sweeps put that balance.  So another size has to save a sixteenth of the picture's
+                // wave-bytes -- a picture of 13 waves at 128 bytes does not go to 12 waves of 144 (3.6 % fewer wave-bytes, passes
+                // 12.5 % longer), one of 2.1 waves' worth still goes to two full ones.  Costs 0.5 % of the default batch's wave-bytes
+                // against taking every saving (profiles/lane_fill.md, where both variants are measured).
+                const uint64_t wb = (n0 + PJD_HUFF_LANES - 1) / PJD_HUFF_LANES;
+                const uint64_t stay = (wb * 100 + (wb & 1) * odd_wave_pct) * SB;
+                if (pick >= 0 && cost[pick] * 16 <= stay * 15) SBi = size[pick];
             }
         }
         g.sub_bytes = SBi;
