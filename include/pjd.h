@@ -322,7 +322,9 @@ int  pjd_batch_bind_output(pjd_batch *b, void *device_base, uint64_t capacity, c
  * rounded to nearest by at most 1 level (each quantised weight is off by at most 1/512: under 0.4981 levels per axis, under 0.9962
  * before the one rounding).  Every intermediate fits 24 bits (at most 16 744 448).  A target equal to the source size reproduces P
  * byte for byte (every w is 0).  pjd_resize_tap is the tap computation on its own, host only (no device needed), and the very
- * code the kernel runs: PJD_E_ARG if src_n or dst_n is 0 or above 65535 or i >= dst_n; i0, i1, w may each be NULL.
+ * code the kernel runs: PJD_E_ARG if src_n or dst_n is 0 or above 65535 or i >= dst_n; i0, i1, w may each be NULL.  Where
+ * src_n * dst_n reaches 2^31 the taps are computed in 64-bit arithmetic: tests/test_gpu_geometry.py pins that branch on the device
+ * (sources and targets 65535 samples long), tests/test_geometry_cpu.py on the host.
  * ADVICE: plain bilinear aliases when it shrinks by more than about 2x per axis.  Pre-scale with PJD_F_SCALE_*: choose the largest
  * s of 1, 2, 4, 8 with ceil(W/s) >= tw and ceil(H/s) >= th (the box filter takes the bulk of the reduction, and less is decoded);
  * the bilinear step then shrinks by less than 2x on the axis that limits s (on both where picture and target have one aspect ratio;

@@ -351,7 +351,9 @@ static inline __host__ __device__ uint64_t pjd_pack_state(uint32_t p, uint32_t c
 // One axis of the bilinear filter: target sample i of dn, over sn source samples -> the two source samples i0, i1 and the weight w
 // of i1 in 1/256 (0..256).  THE implementation: pjd_resize_tap exports it to the host, pjd_k_resize runs it per column and per row.
 // sn, dn in 1..65535, i < dn.  Where sn * dn < 2^31 every value fits 32 bits (X < 2 * dn * sn, the remainder times 256 < 2^25) and the
-// two divisions are 32-bit ones -- every picture anyone decodes; the 64-bit form is the same arithmetic.
+// two divisions are 32-bit ones -- every picture anyone decodes; the 64-bit form is the same arithmetic.  On the device the 64-bit
+// form and the top of the 32-bit one (sn = 32768, dn = 65535) are pinned by tests/test_gpu_geometry.py
+// (test_resize_at_the_dimension_limits), on the host by tests/test_geometry_cpu.py.
 static inline __host__ __device__ void pjd_resize_tap_calc(uint32_t sn, uint32_t dn, uint32_t i, uint32_t &i0, uint32_t &i1, uint32_t &w)
 {
     const uint32_t d2 = 2u * dn;
