@@ -69,6 +69,43 @@ __device__ __forceinline__ void pjd_ycc_to_rgb(int y, int cb, int cr, int &r, in
     b = pjd_clamp255(y + (__mul24(7432306, cb) >> 22) + 128);
 }
 
+// Packed 16-bit instructions of the colour stage's fast path (pjd_colour_store, pjd_k_backend.hip).  A dword holds two int16 (or
+// four uint8), element 0 in the low bits.  Why the pair "saturate to int16, then to uint8" equals pjd_clamp255 of the exact sum:
+// if both addends fit int16 the exact sum lies in [-65536, 65534]; saturation to int16 changes only sums outside
+// [-32768, 32767], and all of those lie outside [0, 255] on the same side.
+__device__ __forceinline__ uint32_t pjd_pk_add_i16_sat(uint32_t a, uint32_t b)      // per half: int16 sum, saturated to [-32768, 32767]
+{
+    uint32_t r;
+    asm("v_pk_add_i16 %0, %1, %2 clamp" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ uint32_t pjd_pk_add_u16(uint32_t a, uint32_t b)          // per half: sum modulo 2^16
+{
+    uint32_t r;
+    asm("v_pk_add_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ uint32_t pjd_sat_pk_u8_i16(uint32_t a)                   // bytes 0, 1 = the halves of a clamped to [0, 255]; bytes 2, 3 = 0
+{
+    uint32_t r;
+    asm("v_sat_pk_u8_i16 %0, %1" : "=v"(r) : "v"(a));
+    return r;
+}
+__device__ __forceinline__ void pjd_sat_pk_u8_i16_hi(uint32_t &d, uint32_t a)       // bytes 2, 3 of d = the same; bytes 0, 1 of d stay
+{
+    asm("v_sat_pk_u8_i16_sdwa %0, %1 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD" : "+v"(d) : "v"(a));
+}
+__device__ __forceinline__ uint32_t pjd_pack_i16(int lo, int hi)                    // (lo & 0xffff) | (hi << 16)
+{
+    return __builtin_amdgcn_perm((uint32_t)hi, (uint32_t)lo, 0x05040100u);
+}
+// v_perm_b32: byte i of the result is byte (sel >> 8i) & 7 of the eight bytes { lo: 0..3, hi: 4..7 }
+__device__ __forceinline__ uint32_t pjd_perm(uint32_t hi, uint32_t lo, uint32_t sel) { return __builtin_amdgcn_perm(hi, lo, sel); }
+// Both halves of a chroma dword inside [-16384, 16383]?  Then every chroma term of pjd_ycc_to_rgb, +128 included, fits int16:
+// |1.772 cb| + 129 <= 29162, |1.402 cr| + 129 <= 23100, 0.344 |cb| + 0.714 |cr| + 130 <= 17465.  Returns 0 if so: adding 0x4000
+// to a half (modulo 2^16) leaves bit 15 clear exactly for the values of that range.
+__device__ __forceinline__ uint32_t pjd_chroma_out_of_range(uint32_t w) { return pjd_pk_add_u16(w, 0x40004000u) & 0x80008000u; }
+
 // Full-rate 24-bit multiplies as single instructions.  Written as instructions, not as __mul24 / __umul24: where only the low
 // 16 bits of a product are kept the compiler proves that the operand masks do not matter, drops them, and then has to use the
 // quarter-rate 32-bit multiply (v_mul_lo_u32) on the unmasked registers (seen in the entry parser of pjd_k_idct_colour_lanes).
@@ -84,6 +121,12 @@ __device__ __forceinline__ uint32_t pjd_mad_u24(uint32_t a, uint32_t b, uint32_t
     asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
     return r;
 }
+
+// u / d for the unit tables of a back-end range: exact for u < 160 and 1 <= d <= 10, and for u < 7 * PJD_IDCT_MAX_DU with d = 7
+// (the error term u * (d * ceil(2^16 / d) - 2^16) stays below 2^16; tests/test_colour_packed_cpu.py checks every pair) -- one
+// full-rate multiply and a shift instead of the float-reciprocal sequence of a 32-bit division
+static __constant__ uint32_t c_recip16[11] = {0, 65536, 32768, 21846, 16384, 13108, 10923, 9363, 8192, 7282, 6554};   // ceil(2^16 / d)
+__device__ __forceinline__ uint32_t pjd_div_small(uint32_t u, uint32_t recip16) { return pjd_mul_u24(u, recip16) >> 16; }
 
 // Dequantise: short *= u32 with the product truncated to int16 on store
 // (reference src/decoder_dpu.c:169-172); only the low 16 bits of q matter.

@@ -452,6 +452,7 @@ __device__ __forceinline__ void pjd_colour_store(const int16_t (*tile)[TILE_STRI
             const uint32_t d0 = __umul24(ml, dus);
             // chroma terms, ordered first / middle / last output byte (R,G,B -- or B,G,R for the BMP image), +128 included
             int cf[NCH], cg[NCH], cl[NCH];
+            bool fast = X + 4 <= width;
             {
                 const uint32_t q = rg * 8 + px0 / HS;
                 uint32_t cbw[2] = {0, 0}, crw[2] = {0, 0};
@@ -463,6 +464,10 @@ __device__ __forceinline__ void pjd_colour_store(const int16_t (*tile)[TILE_STRI
                     if (HS == 2) crw[0] = *reinterpret_cast<const uint32_t *>(&tile[d0 + NL + 1][q]);
                     else { const uint2 t = *reinterpret_cast<const uint2 *>(&tile[d0 + NL + 1][q]); crw[0] = t.x; crw[1] = t.y; }
                 }
+                // the packed rows below need every chroma term in int16: all chroma samples under the task in [-16384, 16383]
+                uint32_t oor = pjd_chroma_out_of_range(cbw[0]) | pjd_chroma_out_of_range(crw[0]);
+                if (HS == 1) oor |= pjd_chroma_out_of_range(cbw[1]) | pjd_chroma_out_of_range(crw[1]);
+                fast = fast && oor == 0;
 #pragma unroll
                 for (int j = 0; j < NCH; j++) {
                     const uint32_t bw = cbw[j >> 1], rw = crw[j >> 1];
@@ -474,6 +479,46 @@ __device__ __forceinline__ void pjd_colour_store(const int16_t (*tile)[TILE_STRI
                     cl[j] = BMP ? rC : bC;
                 }
             }
+            if (fast) {
+                // Packed rows: the luma samples lie in LDS as two int16 pairs; pair + chroma-term pair with signed saturation, then
+                // saturation to bytes -- equal to pjd_clamp255(y + term) (pjd_device_common.h).  The term pairs serve all VS rows.
+                constexpr int s1 = HS == 2 ? 0 : 1, s2 = HS == 2 ? 1 : 2, s3 = HS == 2 ? 1 : 3;   // chroma sample of pixels 1..3
+                const uint32_t pf01 = pjd_pack_i16(cf[0], cf[s1]), pf23 = pjd_pack_i16(cf[s2], cf[s3]);
+                const uint32_t pg01 = pjd_pack_i16(cg[0], cg[s1]), pg23 = pjd_pack_i16(cg[s2], cg[s3]);
+                const uint32_t pl01 = pjd_pack_i16(cl[0], cl[s1]), pl23 = pjd_pack_i16(cl[s2], cl[s3]);
+#pragma unroll
+                for (int v = 0; v < VS; v++) {
+                    const uint32_t Y = Y0 + v;
+                    if (Y >= height) break;
+                    const uint32_t py = rg * VS + v;
+                    const int16_t *yp = &tile[d0 + (py >> 3) * HS + (px0 >> 3)][(py & 7) * 8 + (px0 & 7)];
+                    const uint2 yraw = *reinterpret_cast<const uint2 *>(yp);               // 4 luma samples: (y0, y1), (y2, y3)
+                    const uint32_t f01 = pjd_pk_add_i16_sat(yraw.x, pf01), f23 = pjd_pk_add_i16_sat(yraw.y, pf23);
+                    const uint32_t g01 = pjd_pk_add_i16_sat(yraw.x, pg01), g23 = pjd_pk_add_i16_sat(yraw.y, pg23);
+                    const uint32_t l01 = pjd_pk_add_i16_sat(yraw.x, pl01), l23 = pjd_pk_add_i16_sat(yraw.y, pl23);
+                    if (PLANAR) {
+                        uint32_t f = pjd_sat_pk_u8_i16(f01), g = pjd_sat_pk_u8_i16(g01), l = pjd_sat_pk_u8_i16(l01);
+                        pjd_sat_pk_u8_i16_hi(f, f23); pjd_sat_pk_u8_i16_hi(g, g23); pjd_sat_pk_u8_i16_hi(l, l23);
+                        uint8_t *o = out + (size_t)Y * stride + X;
+                        reinterpret_cast<PjdPx4 *>(o)->a = f;
+                        reinterpret_cast<PjdPx4 *>(o + plane)->a = g;
+                        reinterpret_cast<PjdPx4 *>(o + 2 * plane)->a = l;
+                    } else {
+                        // p = f0 f1 l0 l1, m = g0 g1 g2 g3, r = f2 f3 l2 l3: each of the three output dwords takes bytes of two of them,
+                        // but for the middle one (g1 l1 f2 g2), which takes two steps
+                        uint32_t p = pjd_sat_pk_u8_i16(f01), m = pjd_sat_pk_u8_i16(g01), r = pjd_sat_pk_u8_i16(f23);
+                        pjd_sat_pk_u8_i16_hi(p, l01); pjd_sat_pk_u8_i16_hi(m, g23); pjd_sat_pk_u8_i16_hi(r, l23);
+                        PjdPx12 px;
+                        px.a = pjd_perm(m, p, 0x01020400u);                                // f0 g0 l0 f1
+                        px.b = pjd_perm(m, pjd_perm(p, r, 0x00000700u), 0x06020105u);      // (f2 l1 f2 f2) -> g1 l1 f2 g2
+                        px.c = pjd_perm(m, r, 0x03070102u);                                // l2 f3 g3 l3
+                        uint8_t *o = BMP ? out + 26 + (size_t)(height - 1 - Y) * stride + X * 3 : out + (size_t)Y * stride + X * 3;
+                        *reinterpret_cast<PjdPx12 *>(o) = px;
+                    }
+                }
+                continue;
+            }
+            // the right picture edge inside the 4 pixels, or a chroma sample outside that range: 32-bit sums, a clamp per byte
 #pragma unroll
             for (int v = 0; v < VS; v++) {
                 const uint32_t Y = Y0 + v;
@@ -786,7 +831,7 @@ __device__ __forceinline__ void pjd_tile_put(uint32_t tile_lds, uint32_t u, uint
 // SCALED: pictures with an output scale take the scaled store.  PLANAR: the batch's output format is PJD_OUT_RGB8_PLANAR.
 template <bool SCALED, bool PLANAR = false>
 __device__ __forceinline__ void pjd_idct_range(const PjdDevBatch &B, uint32_t iwg, int16_t (*tile)[TILE_STRIDE], uint32_t (*qz)[64], uint32_t *mcu_xy,
-                                               uint8_t *comp_of, uint32_t *wagg, uint32_t *ltab)
+                                               uint8_t *comp_of, uint8_t *du_head, uint32_t *wagg, uint32_t *ltab)
 {
     const PjdDevIdctWg wg = B.iwgs[iwg];
     const PjdDevImage &im = B.images[wg.image];
@@ -809,11 +854,21 @@ __device__ __forceinline__ void pjd_idct_range(const PjdDevBatch &B, uint32_t iw
     }
     // unvisited positions are zero (the reference's buffers start zeroed); a row is 9 x 16 bytes, the last of them padding
     static_assert(TILE_STRIDE == 72, "the padding cell of a tile row is element 64");
-    for (uint32_t i = tid; i < n_du * (TILE_STRIDE * 2 / 16); i += PJD_IDCT_THREADS)
-        reinterpret_cast<uint4 *>(&tile[0][0])[i] = make_uint4(i % 9u == 8u ? (uint32_t)(uint16_t)PJD_COEF_SENTINEL : 0u, 0, 0, 0);
+    // (row, 16-byte column) by shift and mask: eight zero stores per row, then the row's padding
+    for (uint32_t i = tid; i < n_du * 8; i += PJD_IDCT_THREADS)
+        *reinterpret_cast<uint4 *>(&tile[i >> 3][(i & 7) * 8]) = make_uint4(0, 0, 0, 0);
+    if (tid < n_du) *reinterpret_cast<uint4 *>(&tile[tid][64]) = make_uint4((uint32_t)(uint16_t)PJD_COEF_SENTINEL, 0, 0, 0);
+    // Tables of the range, no division per unit: component of every unit; whether it is the first unit of an MCU that starts a
+    // restart segment (the DC stage resets the predictors there); the grid position of every MCU
     if (tid < PJD_IDCT_MAX_DU) {
-        const uint32_t kk = tid % dus;                          // the range starts on an MCU boundary
+        const uint32_t ml = pjd_div_small(tid, c_recip16[dus]), kk = tid - __umul24(ml, dus);   // the range starts on an MCU boundary
         comp_of[tid] = (uint8_t)(kk < nl ? 0 : kk - nl + 1);
+        if (kk != 0) du_head[tid] = 0;                          // the entries of first units come from the MCU's thread
+    }
+    if (tid < wg.n_mcu) {                                       // the only divisions: one per MCU, none per unit
+        const uint32_t m = wg.first_mcu + tid, my = m / im.mcux;
+        mcu_xy[tid] = (my << 16) | (m - my * im.mcux);
+        du_head[__umul24(tid, dus)] = (uint8_t)(m == im.first_mcu || (RI != 0 && m % RI == 0));
     }
 
     // units of this range that were decoded: all, unless the picture's first entropy-coding error lies in or before the range (the
@@ -953,21 +1008,20 @@ __device__ __forceinline__ void pjd_idct_range(const PjdDevBatch &B, uint32_t iw
     //      the row pass of rows 1..7 (only row 0 holds the DC coefficient) and the slot-52 rule (natural 38 lies in row 4)
     if (wv != 0) {
         for (uint32_t i = tid - 64; i < n_du * 7; i += PJD_IDCT_THREADS - 64) {
-            const uint32_t u = i / 7, r = 1 + (i - u * 7);
+            const uint32_t u = pjd_div_small(i, c_recip16[7]), r = 1 + (i - __umul24(u, 7u));   // i < 7 * PJD_IDCT_MAX_DU: exact
             if (r == 4 && tile[u][64] != (int16_t)PJD_COEF_SENTINEL) tile[u][38] = (int16_t)pjd_dequant((int)tile[u][64], qz[comp_of[u]][48] & 0xffffu);   // slot 52 over natural 38 (the quantiser of slot 48 is that position's)
             pjd_tile_row(tile, u, r);
         }
     } else {
-        const uint32_t d0 = wg.first_mcu * dus;
         // the parser left DEQUANTISED differences: the predictors that enter the range are scaled the same way (all modulo 2^16)
         const uint32_t q0y = qz[0][0] & 0xffffu, q0b = qz[1][0] & 0xffffu, q0r = qz[2][0] & 0xffffu;
         uint32_t cy = (pred0[0] * q0y) & 0xffffu, cc = ((pred0[1] * q0b) & 0xffffu) | ((pred0[2] * q0r) << 16);   // predictors entering the next group of 64 units
         for (uint32_t base = 0; base < n_du; base += 64) {
             const uint32_t u = base + lane;
             const bool on = u < n_valid;                        // an undecoded unit keeps DC 0: it is never predicted
-            const uint32_t d = d0 + u, m = d / dus, kk = d - m * dus, comp = kk < nl ? 0 : kk - nl + 1;
-            const uint32_t dv = on ? (uint32_t)(uint16_t)tile[on ? u : 0][0] : 0u;     // the unit's DC difference as the parser left it (zero if the unit has none)
-            const bool head = on && kk == 0 && (m == im.first_mcu || (RI != 0 && m % RI == 0));
+            const uint32_t us = on ? u : 0u, comp = comp_of[us];
+            const uint32_t dv = on ? (uint32_t)(uint16_t)tile[us][0] : 0u;             // the unit's DC difference as the parser left it (zero if the unit has none)
+            const bool head = on && du_head[us] != 0;
             // sums since the group start (inclusive), Y | Cb, Cr packed; then the same sums at the last head at or before the unit
             uint32_t vy = comp == 0 ? dv : 0u, vc = comp == 1 ? dv : (comp == 2 ? dv << 16 : 0u);
             PJD_WAVE_SCAN(pjd_op_add, vy);
@@ -989,10 +1043,6 @@ __device__ __forceinline__ void pjd_idct_range(const PjdDevBatch &B, uint32_t iw
         }
     }
     // ---- IDCT (reference src/decoder_dpu.c:210-321): rows, then columns; then colour
-    if (tid < wg.n_mcu) {                                   // grid position of each MCU: the only divisions
-        const uint32_t m = wg.first_mcu + tid, my = m / im.mcux;
-        mcu_xy[tid] = (my << 16) | (m - my * im.mcux);
-    }
     __syncthreads();
 #if defined(PJD_IDCT_STOP_AFTER) && PJD_IDCT_STOP_AFTER == 2
     if (tile[0][0] == 12345) B.out[0] = 1;
@@ -1017,6 +1067,7 @@ __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_colour_lanes(PjdD
     __shared__ uint32_t qz[3][64];            // per component, by zigzag SLOT: quantiser of its natural position | position << 16
     __shared__ uint32_t mcu_xy[PJD_IDCT_MAX_DU];
     __shared__ uint8_t comp_of[PJD_IDCT_MAX_DU];
+    __shared__ uint8_t du_head[PJD_IDCT_MAX_DU];
     __shared__ uint32_t wagg[2];              // group parser: groups in the lane window; whether the lane behind the window may belong to the range
     __shared__ uint32_t ltab[96];             // group parser: the window's lane table
 
@@ -1025,7 +1076,7 @@ __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_colour_lanes(PjdD
 #endif
     const uint32_t iwg = order ? order[blockIdx.x] : blockIdx.x;
     if (sweep && __hip_atomic_load(B.range_done + iwg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
-    pjd_idct_range<false>(B, iwg, tile, qz, mcu_xy, comp_of, wagg, ltab);
+    pjd_idct_range<false>(B, iwg, tile, qz, mcu_xy, comp_of, du_head, wagg, ltab);
 }
 
 // The same for a batch that holds pictures with an output scale (PJD_F_SCALE_*): a kernel of its own, so that the full-size one keeps
@@ -1036,13 +1087,14 @@ __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_colour_lanes_scal
     __shared__ uint32_t qz[3][64];
     __shared__ uint32_t mcu_xy[PJD_IDCT_MAX_DU];
     __shared__ uint8_t comp_of[PJD_IDCT_MAX_DU];
+    __shared__ uint8_t du_head[PJD_IDCT_MAX_DU];
     __shared__ uint32_t wagg[2];
     __shared__ uint32_t ltab[96];
 
 #if PJD_IDCT_PRIO
     __builtin_amdgcn_s_setprio(PJD_IDCT_PRIO);
 #endif
-    pjd_idct_range<true>(B, order ? order[blockIdx.x] : blockIdx.x, tile, qz, mcu_xy, comp_of, wagg, ltab);
+    pjd_idct_range<true>(B, order ? order[blockIdx.x] : blockIdx.x, tile, qz, mcu_xy, comp_of, du_head, wagg, ltab);
 }
 
 // The lane-stream back end of a PJD_OUT_RGB8_PLANAR batch, without and with pictures that have an output scale: kernels of their own
@@ -1054,13 +1106,14 @@ __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_colour_lanes_plan
     __shared__ uint32_t qz[3][64];
     __shared__ uint32_t mcu_xy[PJD_IDCT_MAX_DU];
     __shared__ uint8_t comp_of[PJD_IDCT_MAX_DU];
+    __shared__ uint8_t du_head[PJD_IDCT_MAX_DU];
     __shared__ uint32_t wagg[2];
     __shared__ uint32_t ltab[96];
 
 #if PJD_IDCT_PRIO
     __builtin_amdgcn_s_setprio(PJD_IDCT_PRIO);
 #endif
-    pjd_idct_range<SCALED, true>(B, order ? order[blockIdx.x] : blockIdx.x, tile, qz, mcu_xy, comp_of, wagg, ltab);
+    pjd_idct_range<SCALED, true>(B, order ? order[blockIdx.x] : blockIdx.x, tile, qz, mcu_xy, comp_of, du_head, wagg, ltab);
 }
 
 // The pull launch (pjd_internal.h; experiment switch PJD_IDLE_FORM=pull): a few workgroups per CU stay and take the ranges of ready_list
@@ -1072,6 +1125,7 @@ __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_pull(PjdDevBatch 
     __shared__ uint32_t qz[3][64];
     __shared__ uint32_t mcu_xy[PJD_IDCT_MAX_DU];
     __shared__ uint8_t comp_of[PJD_IDCT_MAX_DU];
+    __shared__ uint8_t du_head[PJD_IDCT_MAX_DU];
     __shared__ uint32_t wagg[2];
     __shared__ uint32_t ltab[96];
     // It waits only if every Huffman workgroup has started -- else the device is busy or the launches came in an unlucky order, and
@@ -1105,7 +1159,7 @@ __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_pull(PjdDevBatch 
         continue;
 #endif
         __atomic_thread_fence(__ATOMIC_ACQUIRE);                           // what the picture's waves wrote (agent scope: other CUs)
-        pjd_idct_range<false>(B, v - 1, tile, qz, mcu_xy, comp_of, wagg, ltab);
+        pjd_idct_range<false>(B, v - 1, tile, qz, mcu_xy, comp_of, du_head, wagg, ltab);
         __syncthreads();
         if (threadIdx.x == 0) __hip_atomic_store(B.range_done + (v - 1), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // read by the sweep: a later launch
     }
