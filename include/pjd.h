@@ -22,6 +22,8 @@
  *                                                       R, G, B channels in device memory the caller owns (tensors)
  *   (none: an addition)                                 pjd_batch_set_resize + pjd_resize_tap: every picture of a ragged batch
  *                                                       resampled to a size of its own inside the decode (one [N,3,H,W] tensor)
+ *   (none: an addition)                                 pjd_batch_set_normalize + pjd_normalize_value: the samples leave as fp16, bf16
+ *                                                       or fp32, v * scale[c] + bias[c], in that launch (the tensor a model takes)
  *
  * Plain pointers and sizes only; no C++ or torch types.  Thread model: one
  * submitting thread per pjd_ctx (the reference has one consumer thread,
@@ -205,7 +207,7 @@ typedef struct pjd_batch_info {
     int32_t  n_images;
     uint64_t pixels;                   /* sum of width*height of the SOURCE pictures (the decode work, whatever the scale) */
     uint64_t ecs_bytes;                /* sum of ecs_len                                      */
-    uint64_t out_bytes;                /* sum of output sizes, each at the picture's output scale (PJD_F_SCALE_*), or resized (pjd_batch_set_resize) */
+    uint64_t out_bytes;                /* sum of output sizes, each at the picture's output scale (PJD_F_SCALE_*), or resized (pjd_batch_set_resize), in the elements of pjd_batch_set_normalize */
     uint64_t coef_bytes;               /* lane streams + transposed bitstream words + dense scratch in HBM */
     uint64_t n_data_units;
     uint64_t n_subsequences;           /* Huffman decode lanes                                */
@@ -283,7 +285,7 @@ uint64_t pjd_batch_output_offset(pjd_batch *b, int image);
 /* After pjd_batch_create and before the first pjd_batch_upload / _capture / _decode of this batch (else PJD_E_STATE):
  * pictures are written into caller-owned device memory instead of a buffer of the batch.  Picture i occupies
  * [base + offsets[i], + pjd_batch_output_size(b, i)); offsets == NULL means the packed layout (pjd_batch_output_offset as
- * reported before the call).  No alignment is required of base or of any offset.
+ * reported before the call).  No alignment is required of base or of any offset (a normalised batch: element alignment, below).
  * PJD_E_ARG for a PJD_OUT_BMP batch (its row padding relies on the library zeroing its own buffer), a pointer that is not
  * device memory of the context's device, a `capacity` that reaches past the end of the allocation the pointer lies in (where the
  * runtime can tell), a picture range that ends beyond `capacity`, two picture ranges that overlap.
@@ -345,6 +347,45 @@ int  pjd_batch_bind_output(pjd_batch *b, void *device_base, uint64_t capacity, c
  * pjd_plan_info are unaffected.                                                                                                  */
 int  pjd_batch_set_resize(pjd_batch *b, const uint32_t *out_w, const uint32_t *out_h);
 int  pjd_resize_tap(uint32_t src_n, uint32_t dst_n, uint32_t i, uint32_t *i0, uint32_t *i1, uint32_t *w);
+/* ---- normalised float output ------------------------------------------------------------------------------------------------- *
+ * pjd_batch_set_normalize: the pictures of the batch leave the decode as floating-point elements, sample * scale[c] + bias[c] -- what
+ * x.float().div(255).sub(mean).div(std).to(dtype) makes of the uint8 tensor, without that tensor ever existing.  The caller passes
+ * scale[c] = 1 / (255 * std[c]) and bias[c] = -mean[c] / std[c]; any finite values are allowed.
+ *
+ * THE ARITHMETIC (normative).  Let P' be the uint8 picture the batch would deliver without this call -- the reference's picture, or
+ * the partial picture with grey after an entropy-coding error, after PJD_F_SCALE_* and after pjd_batch_set_resize if one is set.
+ * Every sample v = P'[c][y][x] of channel c (0 = R, 1 = G, 2 = B) leaves as
+ *     u   = fma((float)v, scale[c], bias[c])     one IEEE binary32 fused multiply-add: the exact value of v*scale + bias, rounded
+ *                                                once, to nearest even
+ *     out = u                                    PJD_DT_F32
+ *         = u rounded to binary16, nearest even  PJD_DT_F16  (subnormals kept, overflow gives infinity)
+ *         = u rounded to bfloat16, nearest even  PJD_DT_BF16 (bits = u's 32 bits; bits += 0x7fff + ((bits >> 16) & 1); out = bits >> 16)
+ * Elements are stored little-endian.  The fused form is deliberate: the compiler contracts a multiply and an add into the fma
+ * anyway, so it is written as one and does not depend on a build's contraction flags.  (An unfused float32 multiply-then-add gives
+ * other binary32 results on about half of the 256 levels with the ImageNet constants: tests/test_normalize_cpu.py.)
+ * pjd_normalize_value is that computation for one sample v <= 255, host only (no device needed); its fma stage is the very inline
+ * the kernel runs.  It writes 2 or 4 bytes to `out`; PJD_E_ARG for a dtype other than the three, v > 255, a non-finite scale or
+ * bias, a null `out`.
+ *
+ * CALL ORDER.  After pjd_batch_create, and after pjd_batch_set_resize if that is used; before any pjd_batch_bind_output / _upload /
+ * _capture / _decode of the batch; once: PJD_E_STATE otherwise.  PJD_E_ARG for a null array, a dtype other than the three, a
+ * non-finite scale or bias, a PJD_OUT_BMP batch, a batch that holds a shard (the exclusions of pjd_batch_set_resize).
+ * WITHOUT A RESIZE the call acts as if pjd_batch_set_resize had been called with every picture's own output size: every tap weight
+ * is then 0 and P' is the unresized picture byte for byte; the batch gains the intermediate buffer described there, and a later
+ * pjd_batch_set_resize returns PJD_E_STATE.
+ * FROM THEN ON an element has 2 (PJD_DT_F16, PJD_DT_BF16) or 4 (PJD_DT_F32) bytes: PJD_OUT_RGB8_PLANAR gives dtype[3][th][tw],
+ * PJD_OUT_RGB8 dtype[th][tw][3]; pjd_batch_output_size(b, i) is 3 * tw * th * sizeof(dtype); pjd_batch_output_offset, _packed_size,
+ * _device_output, _download and _download_packed move bytes as before; pjd_batch_bind_output, pjd_batch_info::out_bytes and
+ * device_bytes follow the larger elements.  The library's own offsets stay 256-byte aligned; pjd_batch_bind_output requires
+ * device_base + offsets[i] to be a multiple of the element size (PJD_E_ARG otherwise) and nothing beyond that.  Every decode writes
+ * every byte of every picture's range and no byte outside it.  The work is still the one launch behind the back end
+ * (pjd_batch_decode_timed still names it "resize"; part of a captured graph; it runs again after the exact-kernel fallback of
+ * pjd_batch_sync).  Status words, coefficients and pjd_plan_info are unaffected.                                                  */
+#define PJD_DT_F16   1   /* IEEE binary16 */
+#define PJD_DT_BF16  2   /* bfloat16 */
+#define PJD_DT_F32   3   /* IEEE binary32 */
+int  pjd_batch_set_normalize(pjd_batch *b, int dtype, const float scale[3], const float bias[3]);
+int  pjd_normalize_value(int dtype, uint32_t v, float scale, float bias, void *out);   /* host only, no device needed */
 int  pjd_batch_get_info(pjd_batch *b, pjd_batch_info *info);
 uint64_t pjd_batch_output_size(pjd_batch *b, int image);
 void *pjd_batch_device_output(pjd_batch *b, int image);      /* device pointer (HBM)          */

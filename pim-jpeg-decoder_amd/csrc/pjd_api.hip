@@ -199,6 +199,7 @@ struct pjd_batch {
     uint32_t *d_rs_prefix = nullptr;             // ... followed by the prefix sum of tiles, [n_images + 1]
     size_t rs_bytes = 0;
     uint32_t rs_tiles = 0;
+    PjdNormalize norm{};                         // pjd_batch_set_normalize: dtype != 0, the result holds elements of PJD_DT_SIZE(dtype) bytes
 };
 
 extern "C" {
@@ -584,7 +585,7 @@ int enqueue_decode(pjd_batch *b, pjd_timings *timings, bool use_groups)
     if (b->resized) {
         // resize on decode: every picture from the intermediate (dev.out) to its target size in the result buffer, one launch behind
         // whatever form the back end took (the groups' streams have joined `s` above)
-        pjd_launch_resize(s, b->dev.out, b->res_out, b->d_rs, b->d_rs_prefix, b->dev.n_images, b->rs_tiles, P.planar);
+        pjd_launch_resize(s, b->dev.out, b->res_out, b->d_rs, b->d_rs_prefix, b->dev.n_images, b->rs_tiles, P.planar, b->norm);
         kt.mark("resize");
     }
     HIP_TRY(ctx, hipGetLastError());
@@ -667,7 +668,7 @@ int settle(pjd_batch *b)
             pjd_launch_idct_colour(s, dv, d_wgs, d_base, (uint32_t)fb_wgs.size(), P.scaled, P.planar);
             if (ev1) (void)hipEventRecord(ev1, s);
             // the pictures just decoded again changed in the intermediate: resample (the whole batch: a rare path)
-            if (b->resized) pjd_launch_resize(s, b->dev.out, b->res_out, b->d_rs, b->d_rs_prefix, b->dev.n_images, b->rs_tiles, P.planar);
+            if (b->resized) pjd_launch_resize(s, b->dev.out, b->res_out, b->d_rs, b->d_rs_prefix, b->dev.n_images, b->rs_tiles, P.planar, b->norm);
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipMemcpyAsync(b->h_status, b->dev.status, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s);
@@ -852,6 +853,10 @@ int pjd_batch_bind_output(pjd_batch *b, void *device_base, uint64_t capacity, co
     for (size_t i = 0; i < n; i++) {
         ranges[i] = {offsets ? offsets[i] : b->packed_off[i], b->res_bytes[i]};
         if (ranges[i].first > capacity || ranges[i].second > capacity - ranges[i].first) { ctx->err = fmt_image("bind_output: picture %d ends beyond the capacity", (int)i); return PJD_E_ARG; }
+        if (b->norm.dtype != 0 && ((uintptr_t)device_base + ranges[i].first) % PJD_DT_SIZE(b->norm.dtype) != 0) {
+            ctx->err = fmt_image("bind_output: picture %d does not start at a multiple of the element size (pjd_batch_set_normalize)", (int)i);
+            return PJD_E_ARG;
+        }
     }
     {
         std::vector<std::pair<uint64_t, uint64_t>> sorted = ranges;
@@ -957,6 +962,121 @@ int pjd_batch_set_resize(pjd_batch *b, const uint32_t *out_w, const uint32_t *ou
     b->res_off = off; b->res_bytes = bytes;
     b->res_buf_bytes = pos; b->res_out_bytes = sum;
     b->resized = true;
+    return PJD_OK;
+}
+
+namespace {
+
+// binary32 -> binary16 bits, round to nearest even, subnormals kept, overflow to infinity (the host side of PJD_DT_F16; the device
+// converts in hardware, tests/test_gpu_normalize.py holds the two together)
+uint16_t f32_to_f16_bits(float f)
+{
+    uint32_t x;
+    std::memcpy(&x, &f, 4);
+    const uint32_t sign = (x >> 16) & 0x8000u, a = x & 0x7fffffffu;
+    if (a >= 0x7f800000u) return (uint16_t)(sign | (a > 0x7f800000u ? 0x7e00u : 0x7c00u));
+    if (a < 0x38800000u) {                                 // below 2^-14: a subnormal result, in units of 2^-24
+        const uint32_t e = a >> 23;
+        if (e < 102u) return (uint16_t)sign;               // below 2^-25: zero
+        const uint32_t m = (a & 0x7fffffu) | 0x800000u, shift = 126u - e;      // 14..24
+        uint32_t q = m >> shift;
+        const uint32_t rem = m & ((1u << shift) - 1u), half = 1u << (shift - 1u);
+        if (rem > half || (rem == half && (q & 1u))) q++;
+        return (uint16_t)(sign | q);
+    }
+    const uint32_t r = a - 0x38000000u;                    // exponent rebiased from 127 to 15
+    uint32_t q = r >> 13;
+    const uint32_t rem = r & 0x1fffu;
+    if (rem > 0x1000u || (rem == 0x1000u && (q & 1u))) q++;
+    if (q > 0x7c00u) q = 0x7c00u;
+    return (uint16_t)(sign | q);                           // a carry out of the mantissa runs into the exponent: 0x7c00 is infinity
+}
+
+bool finite_f32(float f)
+{
+    uint32_t x;
+    std::memcpy(&x, &f, 4);
+    return (x & 0x7f800000u) != 0x7f800000u;
+}
+
+}  // namespace
+
+int pjd_normalize_value(int dtype, uint32_t v, float scale, float bias, void *out)
+{
+    if (dtype != PJD_DT_F16 && dtype != PJD_DT_BF16 && dtype != PJD_DT_F32) return PJD_E_ARG;
+    if (v > 255u || !finite_f32(scale) || !finite_f32(bias) || !out) return PJD_E_ARG;
+    const float u = pjd_normalize_f32(v, scale, bias);
+    if (dtype == PJD_DT_F32) { std::memcpy(out, &u, 4); return PJD_OK; }
+    uint16_t h;
+    if (dtype == PJD_DT_F16) h = f32_to_f16_bits(u);
+    else {
+        uint32_t bits;
+        std::memcpy(&bits, &u, 4);
+        bits += 0x7fffu + ((bits >> 16) & 1u);
+        h = (uint16_t)(bits >> 16);
+    }
+    std::memcpy(out, &h, 2);
+    return PJD_OK;
+}
+
+int pjd_batch_set_normalize(pjd_batch *b, int dtype, const float scale[3], const float bias[3])
+{
+    if (!b) return PJD_E_ARG;
+    pjd_ctx *ctx = b->ctx;
+    PjdPlan &P = b->plan;
+    if (b->norm.dtype != 0) { ctx->err = "set_normalize: already set for this batch"; return PJD_E_STATE; }
+    if (b->bound) { ctx->err = "set_normalize after bind_output"; return PJD_E_STATE; }
+    if (b->uploaded) { ctx->err = "set_normalize after upload"; return PJD_E_STATE; }
+    if (!scale || !bias) { ctx->err = "set_normalize: null constant array"; return PJD_E_ARG; }
+    if (dtype != PJD_DT_F16 && dtype != PJD_DT_BF16 && dtype != PJD_DT_F32) { ctx->err = "set_normalize: unknown dtype (PJD_DT_F16, PJD_DT_BF16 or PJD_DT_F32)"; return PJD_E_ARG; }
+    for (int c = 0; c < 3; c++)
+        if (!finite_f32(scale[c]) || !finite_f32(bias[c])) { ctx->err = "set_normalize: scale and bias must be finite"; return PJD_E_ARG; }
+    if (P.out_format == PJD_OUT_BMP) { ctx->err = "set_normalize: a BMP batch cannot be normalised (PJD_OUT_RGB8 or PJD_OUT_RGB8_PLANAR)"; return PJD_E_ARG; }
+    const size_t n = P.images.size();
+    for (size_t i = 0; i < n; i++)
+        if (P.host[i].shard) { ctx->err = fmt_image("set_normalize: picture %d is a shard (its picture is only partly written)", (int)i); return PJD_E_ARG; }
+    hipSetDevice(ctx->device);
+    // the result buffer in elements of the new size: packed, 256-byte aligned offsets.  Taken before anything changes: a failure
+    // leaves the batch as it was (but for a block that stays with it until it is destroyed).
+    std::vector<uint32_t> w(n), h(n);
+    for (size_t i = 0; i < n; i++) {
+        if (b->resized) { w[i] = b->rs_w[i]; h[i] = b->rs_h[i]; }
+        else pjd_scaled_dims(P.images[i].width, P.images[i].height, (P.images[i].flags & PJD_IF_SCALE_MASK) >> PJD_IF_SCALE_SHIFT << 4, &w[i], &h[i]);
+    }
+    const uint64_t es = PJD_DT_SIZE(dtype);
+    std::vector<uint64_t> off(n), bytes(n);
+    uint64_t pos = 0, sum = 0;
+    for (size_t i = 0; i < n; i++) {
+        off[i] = pos; bytes[i] = 3ull * w[i] * h[i] * es;
+        pos = (pos + bytes[i] + 255) & ~(uint64_t)255;
+        sum += bytes[i];
+    }
+    // one of the batch's blocks back to the context's pool
+    auto give_back = [&](void *p, uint64_t counted) {
+        for (size_t k = 0; k < b->dev_blocks.size(); k++)
+            if (b->dev_blocks[k].p == p) {
+                if (!ctx->dev_pool.give(b->dev_blocks[k].p, b->dev_blocks[k].bytes, ctx->pool_cap)) hipFree(b->dev_blocks[k].p);
+                b->dev_blocks.erase(b->dev_blocks.begin() + (long)k);
+                b->device_bytes -= counted;
+                break;
+            }
+    };
+    void *d_res = nullptr;
+    int rc = pool_dev_alloc(ctx, &d_res, (size_t)pos, b->dev_blocks);
+    if (rc != PJD_OK) return rc;
+    b->device_bytes += pos;
+    if (!b->resized) {
+        // no resize set: the identity resample (every tap weight 0) of every picture at its own output size
+        rc = pjd_batch_set_resize(b, w.data(), h.data());
+        if (rc != PJD_OK) { give_back(d_res, pos); return rc; }
+    }
+    give_back(b->res_out, b->res_buf_bytes);               // the uint8 result buffer of the resize
+    for (size_t i = 0; i < n; i++) b->h_rs[i].dst_off = off[i];
+    b->res_out = (uint8_t *)d_res;
+    b->res_off = off; b->res_bytes = bytes;
+    b->res_buf_bytes = pos; b->res_out_bytes = sum;
+    b->norm.dtype = dtype;
+    for (int c = 0; c < 3; c++) { b->norm.scale[c] = scale[c]; b->norm.bias[c] = bias[c]; }
     return PJD_OK;
 }
 

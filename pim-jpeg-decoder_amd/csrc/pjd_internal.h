@@ -389,3 +389,17 @@ struct PjdDevResize {
     uint32_t tw, th;                   // target
     uint32_t col_tiles;                // tiles per tile row: ceil(tw / PJD_RS_COLS)
 };
+
+// ---- normalised float output (pjd_batch_set_normalize; the arithmetic is normative: include/pjd.h) ---------------------------
+// The fma stage of one sample: the exact value of v * scale + bias rounded ONCE to binary32, to nearest even.  THE implementation:
+// pjd_normalize_value exports it to the host (where it is libm's fmaf unless the target has the instruction), the epilogue of
+// pjd_k_resize_norm runs it per sample (v_fma_f32, or v_fma_mix*_f16 where the conversion to binary16 follows at once).  Written with
+// the builtin so that the result does not depend on the contraction flags of a build.
+static inline __host__ __device__ float pjd_normalize_f32(uint32_t v, float scale, float bias) { return __builtin_fmaf((float)v, scale, bias); }
+// bytes per element of a PJD_DT_* value (1 = PJD_DT_F16, 2 = PJD_DT_BF16, 3 = PJD_DT_F32 of include/pjd.h)
+#define PJD_DT_SIZE(dt) ((dt) == 3 ? 4u : 2u)
+// What a batch was given with pjd_batch_set_normalize, as the launcher of the resample takes it; dtype 0: none (uint8 pictures).
+struct PjdNormalize {
+    int32_t dtype;
+    float scale[3], bias[3];
+};

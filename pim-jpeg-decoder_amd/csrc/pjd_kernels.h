@@ -67,9 +67,10 @@ void pjd_launch_group_idct(hipStream_t s, const PjdDevBatch &b, const PjdDevGrou
 void pjd_launch_idct_pull(hipStream_t s, const PjdDevBatch &b);
 void pjd_launch_idct_sweep(hipStream_t s, const PjdDevBatch &b);
 // ---- resize on decode (pjd_k_resize.hip): every picture of the batch from `src` (interleaved RGB8, or planar) to its target size in `dst`
-// (the same layout), one launch; tile_prefix[i] = tiles of the pictures before i, tile_prefix[n_images] = n_tiles
+// (the same layout), one launch; tile_prefix[i] = tiles of the pictures before i, tile_prefix[n_images] = n_tiles.  norm.dtype != 0: the
+// samples leave as fp16 / bf16 / fp32 elements, v * scale[c] + bias[c] (pjd_batch_set_normalize); the records' dst_off stay byte offsets
 void pjd_launch_resize(hipStream_t s, const uint8_t *src, uint8_t *dst, const PjdDevResize *recs, const uint32_t *tile_prefix, uint32_t n_images,
-                       uint32_t n_tiles, bool planar);
+                       uint32_t n_tiles, bool planar, const PjdNormalize &norm);
 // ---- stage-level parity (pjd_k_coefdump.hip): coefficients in the reference's MCU_buffer layout; `out` is zeroed by the caller
 void pjd_launch_coefdump_lanes(hipStream_t s, const PjdDevBatch &b, uint32_t image, uint32_t n_iwg, int16_t *out);
 void pjd_launch_coefdump_dense(hipStream_t s, const PjdDevBatch &b, uint32_t image, const int16_t *scratch, uint32_t first_du, uint32_t n_du, int16_t *out);

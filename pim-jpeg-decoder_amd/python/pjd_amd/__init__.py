@@ -20,6 +20,7 @@ OUT_RGB8_PLANAR = 2      # uint8[3][H][W]: the R, G and B planes one after the o
 PLAN_LATENCY, PLAN_THROUGHPUT = 0, 1      # pjd_set_plan_mode
 F_STANDARD_RESTART, F_FORCE_SEQUENTIAL, F_STANDARD_ZIGZAG, F_PROGRESSIVE = 1, 2, 4, 8
 F_SCALE_1_2, F_SCALE_1_4, F_SCALE_1_8, F_SCALE_MASK = 16, 32, 48, 48      # output scale s = 1 << ((flags >> 4) & 3) (pjd.h)
+DT_F16, DT_BF16, DT_F32 = 1, 2, 3         # pjd_batch_set_normalize: IEEE binary16, bfloat16, IEEE binary32 (pjd.h)
 SCAN_PROGRESSIVE = 1
 MAX_KERNELS = 16
 ABI_VERSION = 6          # PJD_VERSION of include/pjd.h these ctypes structs mirror
@@ -169,6 +170,10 @@ def dev_lib():
         L.pjd_batch_set_resize.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.pjd_resize_tap.restype = i32
         L.pjd_resize_tap.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.pjd_batch_set_normalize.restype = i32
+        L.pjd_batch_set_normalize.argtypes = [vp, i32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        L.pjd_normalize_value.restype = i32
+        L.pjd_normalize_value.argtypes = [i32, C.c_uint32, C.c_float, C.c_float, vp]
         L.pjd_host_alloc.restype = vp
         L.pjd_host_alloc.argtypes = [C.c_uint64]
         L.pjd_host_free.argtypes = [vp]
@@ -324,6 +329,7 @@ class Batch:
         ctx._check(self.L.pjd_batch_create(ctx._h, arr, self.n, out_format, C.byref(h)), "pjd_batch_create")
         self._h = h
         self._resize = None                        # set_resize: the (h, w) of every picture
+        self._dtype = None                         # set_normalize: DT_*
 
     def __enter__(self):
         return self
@@ -398,6 +404,19 @@ class Batch:
         self.ctx._check(self.L.pjd_batch_set_resize(self._h, ws, hs), "pjd_batch_set_resize")
         self._resize = sizes
 
+    def set_normalize(self, dtype, scale, bias):
+        """pjd_batch_set_normalize: every sample v of channel c leaves the decode as fma(v, scale[c], bias[c]) in `dtype` (DT_F16,
+        DT_BF16, DT_F32), the arithmetic include/pjd.h specifies bit for bit; scale[c] = 1 / (255 * std[c]), bias[c] = -mean[c] / std[c]
+        (tensors.normalize_constants).  Once, after set_resize() if that is used, before bind_output() / upload(); not for OUT_BMP,
+        not for shards.  Sizes, offsets and bind_output speak about elements of 2 or 4 bytes from then on; download() returns
+        np.float16 / np.float32 arrays, and np.uint16 (the raw bits) for DT_BF16."""
+        if len(scale) != 3 or len(bias) != 3:
+            raise ValueError("set_normalize: three scales and three biases (R, G, B)")
+        sc = (C.c_float * 3)(*[float(v) for v in scale])
+        bi = (C.c_float * 3)(*[float(v) for v in bias])
+        self.ctx._check(self.L.pjd_batch_set_normalize(self._h, int(dtype), sc, bi), "pjd_batch_set_normalize")
+        self._dtype = int(dtype)
+
     def bind_output(self, device_ptr, capacity, offsets=None):
         """pjd_batch_bind_output: pictures go into caller-owned device memory (`device_ptr`: a plain integer address, e.g. a
         torch tensor's data_ptr(); `capacity` bytes) instead of a buffer of the batch.  `offsets`: byte offset of every picture,
@@ -421,6 +440,8 @@ class Batch:
         ptrs = (C.c_void_p * max(self.n, 1))(*[o.ctypes.data for o in outs])
         st = (C.c_int32 * max(self.n, 1))()
         self.ctx._check(self.L.pjd_batch_download(self._h, ptrs, st), "pjd_batch_download")
+        if self._dtype is not None:                # normalised: elements of 2 or 4 bytes (bf16 as its raw bits: numpy has no such type)
+            outs = [o.view({DT_F16: np.float16, DT_BF16: np.uint16, DT_F32: np.float32}[self._dtype]) for o in outs]
         outs = [o.reshape(self.output_shape(i)) for i, o in enumerate(outs)]
         return outs, [int(st[i]) for i in range(self.n)]
 
@@ -628,6 +649,15 @@ def resize_tap(src_n, dst_n, i):
     if not all(0 <= int(v) < 2 ** 32 for v in (src_n, dst_n, i)) or dev_lib().pjd_resize_tap(int(src_n), int(dst_n), int(i), C.byref(a), C.byref(b), C.byref(w)) != 0:
         raise ValueError(f"resize_tap({src_n}, {dst_n}, {i}): sizes must be 1..65535 and i < dst_n")
     return a.value, b.value, w.value
+
+
+def normalize_value(dtype, v, scale, bias):
+    """pjd_normalize_value (host only): the bits of one normalised sample, as an int of 16 (DT_F16, DT_BF16) or 32 (DT_F32) bits -- the
+    fma the kernel runs, then the conversion include/pjd.h specifies.  ValueError for what the library refuses."""
+    out = (C.c_uint8 * 4)()
+    if not 0 <= int(v) < 2 ** 32 or dev_lib().pjd_normalize_value(int(dtype), int(v), float(scale), float(bias), out) != 0:
+        raise ValueError(f"normalize_value({dtype}, {v}, {scale}, {bias}): dtype DT_F16 / DT_BF16 / DT_F32, v <= 255, finite constants")
+    return int.from_bytes(bytes(out[:4 if int(dtype) == DT_F32 else 2]), "little")
 
 
 def scaled_dims(width, height, flags=0):

@@ -3,10 +3,13 @@
 The batch is bound (Batch.bind_output, pjd_batch_bind_output of include/pjd.h) to ONE torch.uint8 buffer this module allocates
 on the context's device; the back end writes the pictures straight into it -- planar R, G, B (OUT_RGB8_PLANAR, "CHW") by
 default -- and the results are views of that buffer.  No native code of its own.  torch is imported inside the functions that
-need it: uniform_output_shape() and pick_scale_flags() are pure.
+need it: uniform_output_shape(), pick_scale_flags() and normalize_constants() are pure.
 
 Pictures of different sizes become ONE [N, 3, H, W] tensor with decode_resized_batch_tensor: the library resamples every picture to
 H x W inside the decode (Batch.set_resize, pjd_batch_set_resize), after the box pre-scale pick_scale_flags chooses.
+
+The tensor a model takes -- fp16, bf16 or fp32, (x / 255 - mean) / std -- comes out of the same launch with
+decode_normalized_batch_tensor (Batch.set_normalize, pjd_batch_set_normalize): no uint8 tensor, no elementwise kernels after it.
 
 torch ships a HIP runtime of its own.  A tensor's address means something to libpjd.so only if both use ONE runtime, which is the
 case when torch is loaded first (libpjd.so then binds to the runtime torch brought): `import torch` before the first pjd_amd call
@@ -52,12 +55,15 @@ def _torch():
     return torch
 
 
-def _run(ctx, descs, out_format, capacity, offsets, device, resize=None):
-    """Create, (set the resize,) bind to a fresh torch buffer, upload, decode, sync -> (buffer, batch offsets, statuses)."""
+def _run(ctx, descs, out_format, capacity, offsets, device, resize=None, normalize=None):
+    """Create, (set the resize, the normalisation,) bind to a fresh torch buffer, upload, decode, sync -> (buffer, batch offsets,
+    statuses).  The buffer is torch.uint8 whatever the elements are: torch aligns it far beyond an element."""
     torch = _torch()
     with ctx.batch(descs, out_format) as b:
         if resize is not None:
             b.set_resize(resize)
+        if normalize is not None:
+            b.set_normalize(*normalize)
         cap = b.packed_size() if capacity is None else capacity
         buf = torch.empty(max(cap, 1), dtype=torch.uint8, device=device)
         # the block may be a recycled one that work queued on torch's current stream still reads: order that work before ours
@@ -138,3 +144,42 @@ def decode_resized_batch_tensor(ctx, descs, size, prescale=True, device=None):
     n, plane = len(descs), 3 * th * tw
     buf, _, st = _run(ctx, run, pjd_amd.OUT_RGB8_PLANAR, n * plane, [i * plane for i in range(n)], device, resize=[(th, tw)] * n)
     return buf.view(n, 3, th, tw), st
+
+
+def normalize_constants(mean, std):
+    """(scale, bias), three np.float32 each, for Batch.set_normalize: scale[c] = 1 / (255 * std[c]), bias[c] = -mean[c] / std[c], so that
+    fma(v, scale, bias) is (v / 255 - mean) / std.  Computed in float64 and rounded once to float32.  Pure."""
+    import numpy as np
+    mean, std = np.asarray(mean, np.float64).reshape(-1), np.asarray(std, np.float64).reshape(-1)
+    if mean.shape != (3,) or std.shape != (3,):
+        raise ValueError("normalize_constants: three means and three standard deviations (R, G, B)")
+    if not (np.all(np.isfinite(mean)) and np.all(np.isfinite(std)) and np.all(std != 0)):
+        raise ValueError("normalize_constants: finite means, finite non-zero standard deviations")
+    return (1.0 / (255.0 * std)).astype(np.float32), (-mean / std).astype(np.float32)
+
+
+def decode_normalized_batch_tensor(ctx, descs, size, mean, std, dtype=None, channels_last=False, prescale=True, device=None):
+    """Pictures of ANY sizes -> (tensor of `dtype` [N, 3, H, W], statuses), size = (H, W); dtype torch.float16 (the default),
+    torch.bfloat16 or torch.float32.  As decode_resized_batch_tensor, and every sample v of channel c leaves the same launch as
+    fma(v, scale[c], bias[c]) with the constants of normalize_constants(mean, std), converted once to `dtype` (include/pjd.h,
+    pjd_batch_set_normalize): what x.float().div(255).sub(mean).div(std).to(dtype) makes of the uint8 tensor, which never exists.
+    channels_last=False: one contiguous NCHW tensor.  channels_last=True: the batch is decoded interleaved into an [N, H, W, 3] buffer
+    and the result is its permute(0, 3, 1, 2) view: shape [N, 3, H, W] in torch's channels_last memory format.  Complete on return and
+    readable on any torch stream (module docstring, "Stream order")."""
+    if len(descs) == 0:
+        raise ValueError("decode_normalized_batch_tensor: no pictures")
+    th, tw = int(size[0]), int(size[1])
+    scale, bias = normalize_constants(mean, std)
+    torch = _torch()
+    dtype = torch.float16 if dtype is None else dtype
+    dts = {torch.float16: (pjd_amd.DT_F16, 2), torch.bfloat16: (pjd_amd.DT_BF16, 2), torch.float32: (pjd_amd.DT_F32, 4)}
+    if dtype not in dts:
+        raise ValueError("decode_normalized_batch_tensor: dtype must be torch.float16, torch.bfloat16 or torch.float32")
+    dt, es = dts[dtype]
+    device = torch.device("cuda", ctx.device) if device is None else device
+    run = prescaled_descs(descs, (th, tw)) if prescale else descs
+    n, pic = len(descs), 3 * th * tw * es
+    buf, _, st = _run(ctx, run, pjd_amd.OUT_RGB8 if channels_last else pjd_amd.OUT_RGB8_PLANAR, n * pic, [i * pic for i in range(n)], device,
+                      resize=[(th, tw)] * n, normalize=(dt, scale, bias))
+    t = buf.view(dtype)
+    return (t.view(n, th, tw, 3).permute(0, 3, 1, 2) if channels_last else t.view(n, 3, th, tw)), st
