@@ -22,6 +22,8 @@
  *                                                       R, G, B channels in device memory the caller owns (tensors)
  *   (none: an addition)                                 pjd_batch_set_resize + pjd_resize_tap: every picture of a ragged batch
  *                                                       resampled to a size of its own inside the decode (one [N,3,H,W] tensor)
+ *   (none: an addition)                                 pjd_batch_set_resize_filter + pjd_resize_aa_taps: that resize with the
+ *                                                       antialiased triangle filter (torch antialias=True, Pillow BILINEAR)
  *   (none: an addition)                                 pjd_batch_set_normalize + pjd_normalize_value: the samples leave as fp16, bf16
  *                                                       or fp32, v * scale[c] + bias[c], in that launch (the tensor a model takes)
  *
@@ -330,7 +332,8 @@ int  pjd_batch_bind_output(pjd_batch *b, void *device_base, uint64_t capacity, c
  * ADVICE: plain bilinear aliases when it shrinks by more than about 2x per axis.  Pre-scale with PJD_F_SCALE_*: choose the largest
  * s of 1, 2, 4, 8 with ceil(W/s) >= tw and ceil(H/s) >= th (the box filter takes the bulk of the reduction, and less is decoded);
  * the bilinear step then shrinks by less than 2x on the axis that limits s (on both where picture and target have one aspect ratio;
- * beyond s = 8 nothing is left to take, and the other axis of a picture squeezed out of shape keeps its larger factor).
+ * beyond s = 8 nothing is left to take, and the other axis of a picture squeezed out of shape keeps its larger factor).  What the
+ * pre-scale leaves, pjd_batch_set_resize_filter(b, PJD_RESIZE_ANTIALIAS) removes: the antialiased filter below.
  *
  * CALL ORDER.  After pjd_batch_create and before any pjd_batch_bind_output / _upload / _capture / _decode of the batch, once:
  * PJD_E_STATE otherwise.  PJD_E_ARG (pjd_last_error names the picture) for a null array, a target dimension of 0 or above 65535,
@@ -347,6 +350,55 @@ int  pjd_batch_bind_output(pjd_batch *b, void *device_base, uint64_t capacity, c
  * pjd_plan_info are unaffected.                                                                                                  */
 int  pjd_batch_set_resize(pjd_batch *b, const uint32_t *out_w, const uint32_t *out_h);
 int  pjd_resize_tap(uint32_t src_n, uint32_t dst_n, uint32_t i, uint32_t *i0, uint32_t *i1, uint32_t *w);
+/* ---- antialiased resize ------------------------------------------------------------------------------------------------------ *
+ * pjd_batch_set_resize_filter(b, PJD_RESIZE_ANTIALIAS): the resize of the batch uses the triangle filter WIDENED where an axis
+ * shrinks -- torch.nn.functional.interpolate(mode="bilinear", antialias=True), Pillow's BILINEAR -- instead of the plain bilinear
+ * one above.  PJD_RESIZE_BILINEAR (and no call at all) leaves everything as described above.
+ *
+ * THE ARITHMETIC (normative).  The source P is the source of pjd_batch_set_resize: the picture at its decode size, after
+ * PJD_F_SCALE_*, with grey after an entropy-coding error.  Each axis is handled on its own.  Per axis, with sn source samples, dn
+ * target samples, the target index i and S = max(sn, dn) (integer arithmetic, 64-bit where needed, divisions round down):
+ *     r_j = max(0, 2*S - |(2*j + 1)*dn - (2*i + 1)*sn|)       raw weight of source sample j, 0 <= j < sn
+ * the triangle with half-pixel centres, of half-width 1 target sample where the axis grows or stays (bilinear) and of half-width
+ * sn/dn source samples where it shrinks; samples outside the picture are dropped and the rest renormalised, as Pillow and torch
+ * do.  The TAPS are the contiguous run of j with r_j > 0: `first`, `count`, and R = sum r_j.  Quantised to 1/65536:
+ *     q_j = (r_j*65536 + R/2) / R
+ * and then 65536 - sum q_j is added to the tap with the largest r_j (the lowest j on a tie), so that sum q_j == 65536 exactly.
+ * Every q_j lies in 0..65536; a single tap has q = 65536 (17 bits).  Per channel, with (first, count, qx) of the target column and
+ * (first, count, qy) of the target row:
+ *     h   = sum_x qx * P[y][x]                   (at most 65536 * 255, below 2^24)
+ *     h16 = (h + 128) >> 8                       (the row sample with 8 fraction bits, at most 65280)
+ *     v   = sum_y qy * h16                       (at most 65536 * 65280: v + 2^23 fits 32 bits)
+ *     out = (v + (1 << 23)) >> 24
+ * Every product has operands of at most 24 bits.  Where dn == sn the only tap is j == i with q = 65536: a target equal to the
+ * source size reproduces P byte for byte, and a constant picture stays constant (the weights sum to 65536 exactly).
+ * ERROR BOUND.  A rounded q_j is within 1/2 of r_j*65536/R, so the sum of the n rounded taps is within n/2 of 65536, and the
+ * correction moves one tap by at most n/2: the absolute errors of an axis' weights sum to at most n/65536 of a weight, i.e. at most
+ * 255*n/65536 levels per axis -- 0.1246 at the n = 32 of the limit below.  The horizontal error passes through the vertical pass
+ * with weights that sum to 1, h16 adds its rounding (1/512 level), the vertical weights their own 0.1246: under 0.252 levels from the
+ * exact filter before the ONE final rounding, which adds at most 1/2.  The result therefore differs from the filter computed in
+ * float64 and rounded to nearest by at most 1 level (measured: under 0.503 before rounding, tests/test_resize_aa_cpu.py).
+ * LIMIT.  sn <= 16*dn on each axis, at the decode size (with the 1/8 pre-scale of PJD_F_SCALE_* in front: 128x in all).
+ * PJD_AA_MAX_TAPS is the largest tap count the limit admits: the taps are the j with (2*j + 1)*dn inside an OPEN interval of length
+ * 4*S around (2*i + 1)*sn; the points are 2*dn apart, and an open interval of length L holds at most ceil(L / d) points d apart:
+ * ceil(2*S/dn) -- 2 where the axis grows, at most 32 where sn <= 16*dn, attained by 64 -> 4.  (33 would need the closed interval.)
+ *
+ * CALL ORDER.  After pjd_batch_set_resize; before any pjd_batch_set_normalize / _bind_output / _upload / _capture / _decode of the
+ * batch; once: PJD_E_STATE otherwise, also when no resize is set.  PJD_E_ARG for an unknown filter, or (PJD_RESIZE_ANTIALIAS) for
+ * a picture whose decode size exceeds 16x its target on an axis (pjd_last_error names the picture).
+ * FROM THEN ON everything pjd_batch_set_resize promises from its "FROM THEN ON" holds unchanged -- sizes, offsets, bind_output,
+ * downloads, every byte of every range written and none outside, the one launch named "resize", part of a captured graph, run again
+ * after the exact-kernel fallback -- and pjd_batch_set_normalize composes with it as with the bilinear filter: the fma and the
+ * conversion are applied to `out`.  The weights are computed once, by this call, into a table of the batch (shared between
+ * pictures with the same source and target length on an axis; counted in pjd_batch_info::device_bytes, sent by pjd_batch_upload).
+ * pjd_resize_aa_taps is the tap computation on its own, host only (no device needed), the very inline the table is built with:
+ * first, count and q[0 .. count-1] (q has room for PJD_AA_MAX_TAPS entries; each of the three may be NULL).  PJD_E_ARG if src_n or
+ * dst_n is 0 or above 65535, i >= dst_n, or src_n > 16*dst_n.                                                                      */
+#define PJD_RESIZE_BILINEAR  0
+#define PJD_RESIZE_ANTIALIAS 1
+#define PJD_AA_MAX_TAPS      32
+int  pjd_batch_set_resize_filter(pjd_batch *b, int filter);
+int  pjd_resize_aa_taps(uint32_t src_n, uint32_t dst_n, uint32_t i, uint32_t *first, uint32_t *count, uint32_t *q);   /* host only, no device needed */
 /* ---- normalised float output ------------------------------------------------------------------------------------------------- *
  * pjd_batch_set_normalize: the pictures of the batch leave the decode as floating-point elements, sample * scale[c] + bias[c] -- what
  * x.float().div(255).sub(mean).div(std).to(dtype) makes of the uint8 tensor, without that tensor ever existing.  The caller passes

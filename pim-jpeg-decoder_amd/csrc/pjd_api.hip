@@ -16,6 +16,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <atomic>
+#include <map>
 #include <mutex>
 #include <string>
 #include <type_traits>
@@ -200,6 +201,20 @@ struct pjd_batch {
     size_t rs_bytes = 0;
     uint32_t rs_tiles = 0;
     PjdNormalize norm{};                         // pjd_batch_set_normalize: dtype != 0, the result holds elements of PJD_DT_SIZE(dtype) bytes
+    bool filter_set = false, antialias = false;  // pjd_batch_set_resize_filter: called / with PJD_RESIZE_ANTIALIAS
+    uint8_t *h_aa = nullptr, *d_aa = nullptr;    // its per-picture records (PjdDevResizeAA[n_images]) and, behind them, the weight table: page-locked / HBM
+    size_t aa_bytes = 0;
+    uint32_t aa_lds = 0;                         // LDS of the launch: the largest row segment a tile of the batch stages
+
+    // the resample launch of this batch, bilinear or antialiased (both launch sites: the decode and the re-run after the fallback)
+    void launch_resize(hipStream_t s, bool planar) const
+    {
+        if (antialias)
+            pjd_launch_resize_aa(s, dev.out, res_out, d_rs, d_rs_prefix, dev.n_images, rs_tiles, planar, norm, (const PjdDevResizeAA *)d_aa,
+                                 (const uint32_t *)(d_aa + dev.n_images * sizeof(PjdDevResizeAA)), aa_lds);
+        else
+            pjd_launch_resize(s, dev.out, res_out, d_rs, d_rs_prefix, dev.n_images, rs_tiles, planar, norm);
+    }
 };
 
 extern "C" {
@@ -439,6 +454,7 @@ int pjd_batch_upload(pjd_batch *b)
     // With a resize set dev.out is the batch's intermediate, bound or not; the resized pictures are RGB8 or planar, written whole.
     if (!b->bound || b->resized) HIP_TRY(ctx, hipMemsetAsync(b->dev.out, 0, P.out_buf_bytes, s));
     if (b->resized) HIP_TRY(ctx, hipMemcpyAsync(b->d_rs, b->h_rs, b->rs_bytes, hipMemcpyHostToDevice, s));      // the resample work list (page-locked)
+    if (b->antialias) HIP_TRY(ctx, hipMemcpyAsync(b->d_aa, b->h_aa, b->aa_bytes, hipMemcpyHostToDevice, s));   // ... and its weight table
     b->uploaded = true;
     return PJD_OK;
 }
@@ -585,7 +601,7 @@ int enqueue_decode(pjd_batch *b, pjd_timings *timings, bool use_groups)
     if (b->resized) {
         // resize on decode: every picture from the intermediate (dev.out) to its target size in the result buffer, one launch behind
         // whatever form the back end took (the groups' streams have joined `s` above)
-        pjd_launch_resize(s, b->dev.out, b->res_out, b->d_rs, b->d_rs_prefix, b->dev.n_images, b->rs_tiles, P.planar, b->norm);
+        b->launch_resize(s, P.planar);
         kt.mark("resize");
     }
     HIP_TRY(ctx, hipGetLastError());
@@ -668,7 +684,7 @@ int settle(pjd_batch *b)
             pjd_launch_idct_colour(s, dv, d_wgs, d_base, (uint32_t)fb_wgs.size(), P.scaled, P.planar);
             if (ev1) (void)hipEventRecord(ev1, s);
             // the pictures just decoded again changed in the intermediate: resample (the whole batch: a rare path)
-            if (b->resized) pjd_launch_resize(s, b->dev.out, b->res_out, b->d_rs, b->d_rs_prefix, b->dev.n_images, b->rs_tiles, P.planar, b->norm);
+            if (b->resized) b->launch_resize(s, P.planar);
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipMemcpyAsync(b->h_status, b->dev.status, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s);
@@ -962,6 +978,89 @@ int pjd_batch_set_resize(pjd_batch *b, const uint32_t *out_w, const uint32_t *ou
     b->res_off = off; b->res_bytes = bytes;
     b->res_buf_bytes = pos; b->res_out_bytes = sum;
     b->resized = true;
+    return PJD_OK;
+}
+
+int pjd_resize_aa_taps(uint32_t src_n, uint32_t dst_n, uint32_t i, uint32_t *first, uint32_t *count, uint32_t *q)
+{
+    if (src_n == 0 || src_n > 65535u || dst_n == 0 || dst_n > 65535u || i >= dst_n || src_n > 16u * dst_n) return PJD_E_ARG;
+    uint32_t f, w[PJD_AA_MAX_TAPS];
+    const uint32_t n = pjd_resize_aa_taps_calc(src_n, dst_n, i, f, w);
+    if (first) *first = f;
+    if (count) *count = n;
+    if (q) std::memcpy(q, w, n * sizeof(uint32_t));
+    return PJD_OK;
+}
+
+int pjd_batch_set_resize_filter(pjd_batch *b, int filter)
+{
+    if (!b) return PJD_E_ARG;
+    pjd_ctx *ctx = b->ctx;
+    PjdPlan &P = b->plan;
+    if (!b->resized) { ctx->err = "set_resize_filter: no resize is set (pjd_batch_set_resize first)"; return PJD_E_STATE; }
+    if (b->filter_set) { ctx->err = "set_resize_filter: already set for this batch"; return PJD_E_STATE; }
+    if (b->norm.dtype != 0) { ctx->err = "set_resize_filter after set_normalize"; return PJD_E_STATE; }
+    if (b->bound) { ctx->err = "set_resize_filter after bind_output"; return PJD_E_STATE; }
+    if (b->uploaded) { ctx->err = "set_resize_filter after upload"; return PJD_E_STATE; }
+    if (filter != PJD_RESIZE_BILINEAR && filter != PJD_RESIZE_ANTIALIAS) { ctx->err = "set_resize_filter: unknown filter (PJD_RESIZE_BILINEAR or PJD_RESIZE_ANTIALIAS)"; return PJD_E_ARG; }
+    if (filter == PJD_RESIZE_BILINEAR) { b->filter_set = true; return PJD_OK; }
+    const size_t n = P.images.size();
+    for (size_t i = 0; i < n; i++) {
+        const PjdDevResize &r = b->h_rs[i];
+        if (r.sw > 16u * r.tw || r.sh > 16u * r.th) {
+            ctx->err = fmt_image("set_resize_filter: picture %d is more than 16x its target on an axis at its decode size (pre-scale with PJD_F_SCALE_*)", (int)i);
+            return PJD_E_ARG;
+        }
+    }
+    // The weight table: one axis table per distinct (source length, target length) of the batch -- the pictures of a data set share
+    // a few -- each dn heads `first | count << 16`, then taps x dn weights, tap-major, 0 behind a sample's own count (pjd_internal.h).
+    struct Axis { uint32_t off, taps; };
+    std::map<std::pair<uint32_t, uint32_t>, Axis> axes;
+    std::vector<uint32_t> tab;
+    auto axis = [&](uint32_t sn, uint32_t dn) -> Axis {
+        auto it = axes.find({sn, dn});
+        if (it != axes.end()) return it->second;
+        const size_t base = tab.size();
+        const uint32_t bound = (2u * std::max(sn, dn) + dn - 1u) / dn;          // no sample has more taps than ceil(2 * S / dn) (include/pjd.h)
+        const uint32_t cap = std::min<uint32_t>(std::max<uint32_t>(bound, 1u), PJD_AA_MAX_TAPS);
+        tab.resize(base + (size_t)dn * (1u + cap), 0u);
+        uint32_t taps = 0, w[PJD_AA_MAX_TAPS];
+        for (uint32_t i = 0; i < dn; i++) {
+            uint32_t first;
+            const uint32_t cnt = std::min(pjd_resize_aa_taps_calc(sn, dn, i, first, w), cap);
+            tab[base + i] = first | (cnt << 16);
+            for (uint32_t t = 0; t < cnt; t++) tab[base + (size_t)(t + 1u) * dn + i] = w[t];
+            taps = std::max(taps, cnt);
+        }
+        tab.resize(base + (size_t)dn * (1u + taps));       // the rows no sample reaches are dropped
+        const Axis a{(uint32_t)base, taps};
+        axes[{sn, dn}] = a;
+        return a;
+    };
+    std::vector<PjdDevResizeAA> recs(n);
+    uint32_t lds = 0;
+    for (size_t i = 0; i < n; i++) {
+        const PjdDevResize &r = b->h_rs[i];
+        if (tab.size() + ((size_t)r.tw + r.th) * (1u + PJD_AA_MAX_TAPS) >= (1ull << 31)) { ctx->err = "set_resize_filter: the weight table of this batch is too large"; return PJD_E_ARG; }
+        const Axis x = axis(r.sw, r.tw), y = axis(r.sh, r.th);
+        recs[i] = PjdDevResizeAA{x.off, x.taps, y.off, y.taps};
+        // the widest row segment one of its tiles stages: first tap of the tile's first column to the last tap of its last one
+        for (uint32_t c0 = 0; c0 < r.tw; c0 += PJD_RS_COLS) {
+            const uint32_t c1 = std::min(c0 + PJD_RS_COLS, r.tw) - 1u, h0 = tab[x.off + c0], h1 = tab[x.off + c1];
+            lds = std::max(lds, pjd_resize_aa_lds((h1 & 0xffffu) + (h1 >> 16) - (h0 & 0xffffu), P.planar));
+        }
+    }
+    hipSetDevice(ctx->device);
+    const size_t bytes = n * sizeof(PjdDevResizeAA) + tab.size() * sizeof(uint32_t);
+    void *h_aa = nullptr, *d_aa = nullptr;
+    int rc = pool_pin_alloc(ctx, &h_aa, bytes, b->pin_blocks);
+    if (rc == PJD_OK) rc = pool_dev_alloc(ctx, &d_aa, bytes, b->dev_blocks);
+    if (rc != PJD_OK) return rc;                           // what was taken stays with the batch until it is destroyed
+    std::memcpy(h_aa, recs.data(), n * sizeof(PjdDevResizeAA));
+    std::memcpy((uint8_t *)h_aa + n * sizeof(PjdDevResizeAA), tab.data(), tab.size() * sizeof(uint32_t));
+    b->device_bytes += bytes;
+    b->h_aa = (uint8_t *)h_aa; b->d_aa = (uint8_t *)d_aa; b->aa_bytes = bytes; b->aa_lds = lds;
+    b->filter_set = true; b->antialias = true;
     return PJD_OK;
 }
 

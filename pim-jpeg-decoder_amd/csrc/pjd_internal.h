@@ -390,6 +390,43 @@ struct PjdDevResize {
     uint32_t col_tiles;                // tiles per tile row: ceil(tw / PJD_RS_COLS)
 };
 
+// ---- antialiased resize (pjd_batch_set_resize_filter; the arithmetic is normative: include/pjd.h) ----------------------------
+// One axis of the widened triangle filter: target sample i of dn over sn source samples -> the first source sample with a weight,
+// the number of taps (returned; 1..PJD_AA_MAX_TAPS) and their weights q[0 .. count-1] in 1/65536, which sum to 65536 exactly.  THE
+// implementation: pjd_resize_aa_taps exports it, pjd_batch_set_resize_filter fills the batch's weight table with it (the kernel
+// divides nothing).  sn, dn in 1..65535, i < dn, sn <= 16 * dn.  All in 64 bits: (2 * i + 1) * sn reaches 2^33.
+static inline __host__ __device__ uint32_t pjd_resize_aa_taps_calc(uint32_t sn, uint32_t dn, uint32_t i, uint32_t &first, uint32_t *q)
+{
+    const int64_t S2 = 2 * (int64_t)(sn > dn ? sn : dn), c = (int64_t)(2u * i + 1u) * sn, d2 = 2 * (int64_t)dn;
+    const int64_t lo = c - S2;                                 // taps: lo < (2 * j + 1) * dn < c + S2
+    first = lo < (int64_t)dn ? 0u : (uint32_t)((lo - dn) / d2) + 1u;
+    uint32_t n = 0, best = 0;
+    uint64_t R = 0;
+    // n < 32 (PJD_AA_MAX_TAPS) never ends the loop where sn <= 16 * dn; it keeps a caller's array safe whatever comes in
+    for (int64_t p = (2 * (int64_t)first + 1) * dn; n < 32u && first + n < sn && p < c + S2; p += d2, n++) {
+        const int64_t dist = p > c ? p - c : c - p;
+        q[n] = (uint32_t)(S2 - dist);                          // r_j, 1..2S
+        R += q[n];
+        if (q[n] > q[best]) best = n;
+    }
+    int64_t rest = 65536;
+    for (uint32_t k = 0; k < n; k++) {
+        q[k] = (uint32_t)(((uint64_t)q[k] * 65536u + R / 2u) / R);
+        rest -= q[k];
+    }
+    q[best] = (uint32_t)((int64_t)q[best] + rest);
+    return n;
+}
+
+// What the antialiased launch (pjd_k_resize_aa.hip) reads beside the work list of the bilinear one: per picture, where the tables of
+// its two axes start in the batch's weight table (in words) and how many taps a row of each holds.  The table of one axis (sn -> dn,
+// shared by every picture and axis with that pair): dn head words `first | count << 16`, then taps x dn weights, TAP-MAJOR
+// (weight t of target sample i at dn + t * dn + i; 0 from `count` on), so that the lanes of a wave read adjacent words.
+struct PjdDevResizeAA {
+    uint32_t x_tab, x_taps;
+    uint32_t y_tab, y_taps;
+};
+
 // ---- normalised float output (pjd_batch_set_normalize; the arithmetic is normative: include/pjd.h) ---------------------------
 // The fma stage of one sample: the exact value of v * scale + bias rounded ONCE to binary32, to nearest even.  THE implementation:
 // pjd_normalize_value exports it to the host (where it is libm's fmaf unless the target has the instruction), the epilogue of

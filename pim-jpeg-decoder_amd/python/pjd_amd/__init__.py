@@ -20,6 +20,8 @@ OUT_RGB8_PLANAR = 2      # uint8[3][H][W]: the R, G and B planes one after the o
 PLAN_LATENCY, PLAN_THROUGHPUT = 0, 1      # pjd_set_plan_mode
 F_STANDARD_RESTART, F_FORCE_SEQUENTIAL, F_STANDARD_ZIGZAG, F_PROGRESSIVE = 1, 2, 4, 8
 F_SCALE_1_2, F_SCALE_1_4, F_SCALE_1_8, F_SCALE_MASK = 16, 32, 48, 48      # output scale s = 1 << ((flags >> 4) & 3) (pjd.h)
+RESIZE_BILINEAR, RESIZE_ANTIALIAS = 0, 1   # pjd_batch_set_resize_filter (pjd.h)
+AA_MAX_TAPS = 32                           # PJD_AA_MAX_TAPS: the most taps per axis pjd_resize_aa_taps returns
 DT_F16, DT_BF16, DT_F32 = 1, 2, 3         # pjd_batch_set_normalize: IEEE binary16, bfloat16, IEEE binary32 (pjd.h)
 SCAN_PROGRESSIVE = 1
 MAX_KERNELS = 16
@@ -170,6 +172,10 @@ def dev_lib():
         L.pjd_batch_set_resize.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.pjd_resize_tap.restype = i32
         L.pjd_resize_tap.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.pjd_batch_set_resize_filter.restype = i32
+        L.pjd_batch_set_resize_filter.argtypes = [vp, i32]
+        L.pjd_resize_aa_taps.restype = i32
+        L.pjd_resize_aa_taps.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.pjd_batch_set_normalize.restype = i32
         L.pjd_batch_set_normalize.argtypes = [vp, i32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         L.pjd_normalize_value.restype = i32
@@ -403,6 +409,13 @@ class Batch:
         hs = (C.c_uint32 * max(self.n, 1))(*[h for h, _ in sizes])
         self.ctx._check(self.L.pjd_batch_set_resize(self._h, ws, hs), "pjd_batch_set_resize")
         self._resize = sizes
+
+    def set_resize_filter(self, filter):
+        """pjd_batch_set_resize_filter: RESIZE_ANTIALIAS makes the resize the widened triangle filter include/pjd.h specifies bit for
+        bit (torch's antialias=True, Pillow's BILINEAR); RESIZE_BILINEAR is what a batch has without the call.  Once, after
+        set_resize() and before set_normalize() / bind_output() / upload(); a picture more than 16x its target on an axis at its
+        decode size is refused."""
+        self.ctx._check(self.L.pjd_batch_set_resize_filter(self._h, int(filter)), "pjd_batch_set_resize_filter")
 
     def set_normalize(self, dtype, scale, bias):
         """pjd_batch_set_normalize: every sample v of channel c leaves the decode as fma(v, scale[c], bias[c]) in `dtype` (DT_F16,
@@ -649,6 +662,16 @@ def resize_tap(src_n, dst_n, i):
     if not all(0 <= int(v) < 2 ** 32 for v in (src_n, dst_n, i)) or dev_lib().pjd_resize_tap(int(src_n), int(dst_n), int(i), C.byref(a), C.byref(b), C.byref(w)) != 0:
         raise ValueError(f"resize_tap({src_n}, {dst_n}, {i}): sizes must be 1..65535 and i < dst_n")
     return a.value, b.value, w.value
+
+
+def resize_aa_taps(src_n, dst_n, i):
+    """pjd_resize_aa_taps (host only): (first, [q ...]) -- the first source sample target sample i of dst_n reads over src_n source
+    samples with the antialiased filter, and the weights of that sample and the following ones in 1/65536 (they sum to 65536); the
+    code the batch's weight table is built with.  ValueError outside 1..65535, for i >= dst_n and for src_n > 16 * dst_n."""
+    first, count, q = C.c_uint32(), C.c_uint32(), (C.c_uint32 * AA_MAX_TAPS)()
+    if not all(0 <= int(v) < 2 ** 32 for v in (src_n, dst_n, i)) or dev_lib().pjd_resize_aa_taps(int(src_n), int(dst_n), int(i), C.byref(first), C.byref(count), q) != 0:
+        raise ValueError(f"resize_aa_taps({src_n}, {dst_n}, {i}): sizes must be 1..65535, i < dst_n and src_n <= 16 * dst_n")
+    return first.value, list(q[:count.value])
 
 
 def normalize_value(dtype, v, scale, bias):

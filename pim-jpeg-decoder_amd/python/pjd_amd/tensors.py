@@ -55,13 +55,15 @@ def _torch():
     return torch
 
 
-def _run(ctx, descs, out_format, capacity, offsets, device, resize=None, normalize=None):
-    """Create, (set the resize, the normalisation,) bind to a fresh torch buffer, upload, decode, sync -> (buffer, batch offsets,
+def _run(ctx, descs, out_format, capacity, offsets, device, resize=None, normalize=None, antialias=False):
+    """Create, (set the resize, its filter, the normalisation,) bind to a fresh torch buffer, upload, decode, sync -> (buffer, batch offsets,
     statuses).  The buffer is torch.uint8 whatever the elements are: torch aligns it far beyond an element."""
     torch = _torch()
     with ctx.batch(descs, out_format) as b:
         if resize is not None:
             b.set_resize(resize)
+            if antialias:
+                b.set_resize_filter(pjd_amd.RESIZE_ANTIALIAS)
         if normalize is not None:
             b.set_normalize(*normalize)
         cap = b.packed_size() if capacity is None else capacity
@@ -129,12 +131,17 @@ def prescaled_descs(descs, size):
     return out
 
 
-def decode_resized_batch_tensor(ctx, descs, size, prescale=True, device=None):
+def decode_resized_batch_tensor(ctx, descs, size, prescale=True, device=None, antialias=False):
     """Pictures of ANY sizes -> (uint8 tensor [N, 3, H, W], statuses), size = (H, W): every picture is resampled to H x W inside
     the decode (the bilinear filter of include/pjd.h, pjd_batch_set_resize) and lands at offset i * 3 * H * W of one buffer, so
     the result is one contiguous NCHW tensor with no copy after the decode, complete on return and readable on any torch stream
     (module docstring, "Stream order").  prescale: decode copies of the descriptors at the reduced size pick_scale_flags chooses
-    (the box filter takes the bulk of a large reduction: no aliasing, and less to decode); else the descriptors' own flags hold."""
+    (the box filter takes the bulk of a large reduction: no aliasing, and less to decode); else the descriptors' own flags hold.
+    antialias=True: the resize is the antialiased triangle filter of include/pjd.h (Batch.set_resize_filter) -- what
+    torch.nn.functional.interpolate(mode="bilinear", antialias=True), torchvision's Resize(antialias=True) and Pillow's BILINEAR
+    compute, to within 1 level.  With prescale=True the box pre-scale is still chosen (less to decode; the triangle filter removes
+    what the box leaves), so the result differs from an antialiased resize of the full-size picture; prescale=False gives exactly
+    that, for pictures up to 16x the target on each axis (beyond that the call raises)."""
     if len(descs) == 0:
         raise ValueError("decode_resized_batch_tensor: no pictures")
     th, tw = int(size[0]), int(size[1])
@@ -142,7 +149,8 @@ def decode_resized_batch_tensor(ctx, descs, size, prescale=True, device=None):
     device = torch.device("cuda", ctx.device) if device is None else device
     run = prescaled_descs(descs, (th, tw)) if prescale else descs
     n, plane = len(descs), 3 * th * tw
-    buf, _, st = _run(ctx, run, pjd_amd.OUT_RGB8_PLANAR, n * plane, [i * plane for i in range(n)], device, resize=[(th, tw)] * n)
+    buf, _, st = _run(ctx, run, pjd_amd.OUT_RGB8_PLANAR, n * plane, [i * plane for i in range(n)], device, resize=[(th, tw)] * n,
+                      antialias=antialias)
     return buf.view(n, 3, th, tw), st
 
 
@@ -158,14 +166,17 @@ def normalize_constants(mean, std):
     return (1.0 / (255.0 * std)).astype(np.float32), (-mean / std).astype(np.float32)
 
 
-def decode_normalized_batch_tensor(ctx, descs, size, mean, std, dtype=None, channels_last=False, prescale=True, device=None):
+def decode_normalized_batch_tensor(ctx, descs, size, mean, std, dtype=None, channels_last=False, prescale=True, device=None,
+                                   antialias=False):
     """Pictures of ANY sizes -> (tensor of `dtype` [N, 3, H, W], statuses), size = (H, W); dtype torch.float16 (the default),
     torch.bfloat16 or torch.float32.  As decode_resized_batch_tensor, and every sample v of channel c leaves the same launch as
     fma(v, scale[c], bias[c]) with the constants of normalize_constants(mean, std), converted once to `dtype` (include/pjd.h,
     pjd_batch_set_normalize): what x.float().div(255).sub(mean).div(std).to(dtype) makes of the uint8 tensor, which never exists.
     channels_last=False: one contiguous NCHW tensor.  channels_last=True: the batch is decoded interleaved into an [N, H, W, 3] buffer
     and the result is its permute(0, 3, 1, 2) view: shape [N, 3, H, W] in torch's channels_last memory format.  Complete on return and
-    readable on any torch stream (module docstring, "Stream order")."""
+    readable on any torch stream (module docstring, "Stream order").  antialias=True: the antialiased filter, as in
+    decode_resized_batch_tensor -- with prescale=True the result differs from an antialiased resize of the full-size picture (the box
+    pre-scale comes first), prescale=False gives exactly that up to the 16x limit."""
     if len(descs) == 0:
         raise ValueError("decode_normalized_batch_tensor: no pictures")
     th, tw = int(size[0]), int(size[1])
@@ -180,6 +191,6 @@ def decode_normalized_batch_tensor(ctx, descs, size, mean, std, dtype=None, chan
     run = prescaled_descs(descs, (th, tw)) if prescale else descs
     n, pic = len(descs), 3 * th * tw * es
     buf, _, st = _run(ctx, run, pjd_amd.OUT_RGB8 if channels_last else pjd_amd.OUT_RGB8_PLANAR, n * pic, [i * pic for i in range(n)], device,
-                      resize=[(th, tw)] * n, normalize=(dt, scale, bias))
+                      resize=[(th, tw)] * n, normalize=(dt, scale, bias), antialias=antialias)
     t = buf.view(dtype)
     return (t.view(n, th, tw, 3).permute(0, 3, 1, 2) if channels_last else t.view(n, 3, th, tw)), st

@@ -1,6 +1,6 @@
 """What resize on decode costs and what it saves: the default bench workload (1024 ragged pictures) to one uint8[N, 3, H, W] tensor.
 
-    python tools/resize_probe.py [--rounds 60] [--warmup 5] [--size 224] [--e2e-rounds 20]
+    python tools/resize_probe.py [--rounds 60] [--warmup 5] [--size 224] [--e2e-rounds 20] [--antialias]
 
 Prints one JSON line:
   kernel    per batch kind (prescale = pick_scale_flags, noprescale = full-size decode; planar and rgb8; planar bound to a torch
@@ -13,6 +13,9 @@ Prints one JSON line:
                         torch.nn.functional.interpolate per picture into a preallocated [N, 3, H, W] tensor
             each with and without the box pre-scale
   device_bytes of the resized default batch, unbound and bound
+--antialias: every batch kind a second time with the antialiased filter (Batch.set_resize_filter, key suffix `_aa`), resident beside
+its bilinear twin and decoded in the same alternation, and `aa_over_bilinear`: the ratio of the two `resize` medians per kind.
+--e2e-rounds 0 leaves the end-to-end part out.
 """
 import argparse
 import json
@@ -35,6 +38,7 @@ def main():
     ap.add_argument("--e2e-rounds", type=int, default=20)
     ap.add_argument("--images", type=int, default=1024)
     ap.add_argument("--size", type=int, default=224)
+    ap.add_argument("--antialias", action="store_true")
     args = ap.parse_args()
     # before anything loads libpjd.so: torch and the library then share one HIP runtime (pjd_amd/tensors.py)
     import torch
@@ -61,10 +65,13 @@ def main():
     kinds = [("prescale", "planar", False), ("noprescale", "planar", False), ("prescale", "rgb8", False), ("noprescale", "rgb8", False),
              ("prescale", "planar", True)]
     batches, keep = {}, []
-    for pre, fmt, bound in kinds:
-        key = f"{pre}_{fmt}" + ("_bound" if bound else "")
+    kinds = [k + (False,) for k in kinds] + ([k + (True,) for k in kinds] if args.antialias else [])
+    for pre, fmt, bound, antialias in kinds:
+        key = f"{pre}_{fmt}" + ("_bound" if bound else "") + ("_aa" if antialias else "")
         b = ctx.batch(descs[pre], pjd_amd.OUT_RGB8_PLANAR if fmt == "planar" else pjd_amd.OUT_RGB8)
         b.set_resize([(T, T)] * n)
+        if antialias:
+            b.set_resize_filter(pjd_amd.RESIZE_ANTIALIAS)
         out["device_bytes"][key] = b.info()["device_bytes"]
         if bound:
             buf = torch.empty(n * plane, dtype=torch.uint8, device="cuda:0")
@@ -95,10 +102,13 @@ def main():
         out["kernel"][k]["n_fallback"] = b.info()["n_fallback"]
         b.destroy()
     keep.clear()
+    if args.antialias:
+        out["aa_over_bilinear"] = {k: round(out["kernel"][k + "_aa"]["resize"]["median_ms"] / out["kernel"][k]["resize"]["median_ms"], 2)
+                                   for k in list(out["kernel"]) if not k.endswith("_aa")}
 
     # ---- end to end against today's route
     runs = {}
-    for pre in ("prescale", "noprescale"):
+    for pre in ("prescale", "noprescale") if args.e2e_rounds > 0 else ():
         result = torch.empty(n, 3, T, T, dtype=torch.uint8, device="cuda:0")
         b = ctx.batch(descs[pre], pjd_amd.OUT_RGB8_PLANAR)
         b.set_resize([(T, T)] * n)
@@ -138,7 +148,7 @@ def main():
                 times[k].append(dt)
     for k in runs:
         out["e2e"][k] = stat(times[k])
-    for pre in ("prescale", "noprescale"):
+    for pre in ("prescale", "noprescale") if args.e2e_rounds > 0 else ():
         a, bq = runs[f"resized_{pre}"][2], runs[f"torch_{pre}"][2][1]
         out["e2e"][f"max_abs_difference_{pre}"] = int((a.to(torch.int16) - bq.to(torch.int16)).abs().max().item())
         out["e2e"][f"torch_over_resized_{pre}"] = round(out["e2e"][f"torch_{pre}"]["median_ms"] / out["e2e"][f"resized_{pre}"]["median_ms"], 2)
