@@ -24,6 +24,8 @@
  *                                                       resampled to a size of its own inside the decode (one [N,3,H,W] tensor)
  *   (none: an addition)                                 pjd_batch_set_resize_filter + pjd_resize_aa_taps: that resize with the
  *                                                       antialiased triangle filter (torch antialias=True, Pillow BILINEAR)
+ *   (none: an addition)                                 pjd_batch_set_resize_window + pjd_resize_window_check: that resize from a
+ *                                                       window of the picture (RandomResizedCrop, Resize + CenterCrop, flip)
  *   (none: an addition)                                 pjd_batch_set_normalize + pjd_normalize_value: the samples leave as fp16, bf16
  *                                                       or fp32, v * scale[c] + bias[c], in that launch (the tensor a model takes)
  *
@@ -385,7 +387,9 @@ int  pjd_resize_tap(uint32_t src_n, uint32_t dst_n, uint32_t i, uint32_t *i0, ui
  *
  * CALL ORDER.  After pjd_batch_set_resize; before any pjd_batch_set_normalize / _bind_output / _upload / _capture / _decode of the
  * batch; once: PJD_E_STATE otherwise, also when no resize is set.  PJD_E_ARG for an unknown filter, or (PJD_RESIZE_ANTIALIAS) for
- * a picture whose decode size exceeds 16x its target on an axis (pjd_last_error names the picture).
+ * a picture whose decode size exceeds 16x its target on an axis (pjd_last_error names the picture); where the batch has source
+ * windows (pjd_batch_set_resize_window, below) the limit is each window's against its virtual target, and the weights are those of
+ * the windowed axes.
  * FROM THEN ON everything pjd_batch_set_resize promises from its "FROM THEN ON" holds unchanged -- sizes, offsets, bind_output,
  * downloads, every byte of every range written and none outside, the one launch named "resize", part of a captured graph, run again
  * after the exact-kernel fallback -- and pjd_batch_set_normalize composes with it as with the bilinear filter: the fma and the
@@ -399,6 +403,56 @@ int  pjd_resize_tap(uint32_t src_n, uint32_t dst_n, uint32_t i, uint32_t *i0, ui
 #define PJD_AA_MAX_TAPS      32
 int  pjd_batch_set_resize_filter(pjd_batch *b, int filter);
 int  pjd_resize_aa_taps(uint32_t src_n, uint32_t dst_n, uint32_t i, uint32_t *first, uint32_t *count, uint32_t *q);   /* host only, no device needed */
+/* ---- source windows: crop and flip inside the resize ------------------------------------------------------------------------------ *
+ * pjd_batch_set_resize_window: picture i of a resized batch is resampled from a WINDOW of the decoded picture, to a window of a
+ * VIRTUAL target, and mirrored left-right where asked (win: n_images records).  The pipelines of a vision loader in one launch:
+ * RandomResizedCrop (x, y, w, h = the crop; vw, vh = 0), Resize(s) + CenterCrop(t) (the whole picture; vw x vh = the resized
+ * size; ox, oy = where the centre crop starts), RandomHorizontalFlip (PJD_RW_HFLIP).  Every picture is still decoded whole: the
+ * window lives in the resample launch alone.
+ *
+ * THE ARITHMETIC (normative).  P is the source of pjd_batch_set_resize: the sw x sh picture at its decode size, after
+ * PJD_F_SCALE_*, with grey after an entropy-coding error; tw x th is the picture's target from pjd_batch_set_resize.  With the
+ * defaults resolved (w == h == 0: x = y = 0, w = sw, h = sh; vw == 0: vw = tw; vh == 0: vh = th), for target column i and row j:
+ *     i' = tw - 1 - i  with PJD_RW_HFLIP, else i
+ *   bilinear:    (i0, i1, wx)     = pjd_resize_tap(w, vw, ox + i');      the source columns are x + i0 and x + i1
+ *                (j0, j1, wy)     = pjd_resize_tap(h, vh, oy + j);       the source rows    are y + j0 and y + j1
+ *                the blend and its ONE rounding are those of pjd_batch_set_resize
+ *   antialiased: (first, count, q) = pjd_resize_aa_taps(w, vw, ox + i'); the source columns are x + first + t, t < count
+ *                (first, count, q) = pjd_resize_aa_taps(h, vh, oy + j);  the source rows    are y + first + t
+ *                h, h16, v and out are those of pjd_batch_set_resize_filter
+ * The delivered picture is therefore flip(resize(P[y:y+h, x:x+w], vw, vh)[oy:oy+th, ox:ox+tw]): no new arithmetic, the two tap
+ * functions above with a shifted index.  Samples outside the WINDOW are treated exactly as samples outside the picture are without
+ * one -- clamped (bilinear), dropped and the rest renormalised (antialiased) -- and never contribute, even where the picture has
+ * pixels there.  The error bounds of both filters carry over word for word.  An all-zero record is the identity; a batch whose
+ * records are all zero delivers byte for byte what it delivers without the call.
+ *
+ * VALIDATION.  pjd_resize_window_check (host only, no device needed) is the one implementation; pjd_batch_set_resize_window calls
+ * it for every picture with PJD_RESIZE_BILINEAR, pjd_batch_set_resize_filter again with the filter it is given.  PJD_OK, or
+ * PJD_E_ARG (pjd_last_error names the picture) for: sw, sh, tw or th outside 1..65535, a null record, an unknown filter;
+ * w == 0 xor h == 0; w == h == 0 with x or y non-zero; x + w > sw or y + h > sh; vw or vh above 65535; ox + tw > vw or
+ * oy + th > vh (defaults resolved); an unknown flag bit; reserved_ != 0; and with PJD_RESIZE_ANTIALIAS w > 16*vw or h > 16*vh.
+ * The 16x limit of the antialiased filter is the WINDOW's: a picture past 16x its target whose window is inside is accepted.
+ *
+ * CALL ORDER.  After pjd_batch_set_resize; before any pjd_batch_set_resize_filter / _set_normalize / _bind_output / _upload /
+ * _capture / _decode of the batch; once: PJD_E_STATE otherwise (so a batch that took pjd_batch_set_normalize without a resize
+ * takes no window).  PJD_E_ARG for a null array or a record the check refuses; the batch is then as it was, un-windowed.
+ * FROM THEN ON everything pjd_batch_set_resize promises from its "FROM THEN ON" holds unchanged -- sizes and offsets (those of
+ * tw x th), every byte of every range written and none outside, the one launch named "resize", part of a captured graph, run again
+ * after the exact-kernel fallback, bind_output and its alignment rules -- and pjd_batch_set_resize_filter and _set_normalize compose
+ * as before: the weight table of the antialiased filter is built from the windowed axes (w, vw) and (h, vh).  The records (40 bytes
+ * a picture) are counted in pjd_batch_info::device_bytes and sent by pjd_batch_upload; a batch whose records are all zero takes
+ * none and runs the launch it ran before.  Status words, partial pictures, coefficients and pjd_plan_info are unaffected.      */
+#define PJD_RW_HFLIP 1u
+typedef struct pjd_resize_window {
+    uint32_t x, y, w, h;   /* source window in P; w == h == 0 (then x == y == 0): the whole picture          */
+    uint32_t vw, vh;       /* virtual target the window is resampled to; 0: the picture's target (tw / th)  */
+    uint32_t ox, oy;       /* delivered: columns [ox, ox+tw), rows [oy, oy+th) of the virtual target        */
+    uint32_t flags;        /* PJD_RW_HFLIP: the delivered picture mirrored left-right                       */
+    uint32_t reserved_;    /* 0 */
+} pjd_resize_window;
+int  pjd_batch_set_resize_window(pjd_batch *b, const pjd_resize_window *win /* n_images */);
+int  pjd_resize_window_check(uint32_t sw, uint32_t sh, uint32_t tw, uint32_t th,
+                             const pjd_resize_window *win, int filter);   /* host only, no device needed */
 /* ---- normalised float output ------------------------------------------------------------------------------------------------- *
  * pjd_batch_set_normalize: the pictures of the batch leave the decode as floating-point elements, sample * scale[c] + bias[c] -- what
  * x.float().div(255).sub(mean).div(std).to(dtype) makes of the uint8 tensor, without that tensor ever existing.  The caller passes

@@ -205,11 +205,18 @@ struct pjd_batch {
     uint8_t *h_aa = nullptr, *d_aa = nullptr;    // its per-picture records (PjdDevResizeAA[n_images]) and, behind them, the weight table: page-locked / HBM
     size_t aa_bytes = 0;
     uint32_t aa_lds = 0;                         // LDS of the launch: the largest row segment a tile of the batch stages
+    bool win_set = false, windowed = false;      // pjd_batch_set_resize_window: called / with a record that is not all zero
+    PjdDevResizeWin *h_win = nullptr, *d_win = nullptr;   // then: the windows, defaults resolved, [n_images]: page-locked / HBM
+    size_t win_bytes = 0;
 
-    // the resample launch of this batch, bilinear or antialiased (both launch sites: the decode and the re-run after the fallback)
+    // the resample launch of this batch, bilinear or antialiased, windowed or not (both launch sites: the decode and the re-run
+    // after the fallback)
     void launch_resize(hipStream_t s, bool planar) const
     {
-        if (antialias)
+        if (windowed)
+            pjd_launch_resize_win(s, dev.out, res_out, d_rs, d_win, d_rs_prefix, dev.n_images, rs_tiles, planar, norm, antialias, (const PjdDevResizeAA *)d_aa,
+                                  antialias ? (const uint32_t *)(d_aa + dev.n_images * sizeof(PjdDevResizeAA)) : nullptr, aa_lds);
+        else if (antialias)
             pjd_launch_resize_aa(s, dev.out, res_out, d_rs, d_rs_prefix, dev.n_images, rs_tiles, planar, norm, (const PjdDevResizeAA *)d_aa,
                                  (const uint32_t *)(d_aa + dev.n_images * sizeof(PjdDevResizeAA)), aa_lds);
         else
@@ -455,6 +462,7 @@ int pjd_batch_upload(pjd_batch *b)
     if (!b->bound || b->resized) HIP_TRY(ctx, hipMemsetAsync(b->dev.out, 0, P.out_buf_bytes, s));
     if (b->resized) HIP_TRY(ctx, hipMemcpyAsync(b->d_rs, b->h_rs, b->rs_bytes, hipMemcpyHostToDevice, s));      // the resample work list (page-locked)
     if (b->antialias) HIP_TRY(ctx, hipMemcpyAsync(b->d_aa, b->h_aa, b->aa_bytes, hipMemcpyHostToDevice, s));   // ... and its weight table
+    if (b->windowed) HIP_TRY(ctx, hipMemcpyAsync(b->d_win, b->h_win, b->win_bytes, hipMemcpyHostToDevice, s));  // ... and its source windows
     b->uploaded = true;
     return PJD_OK;
 }
@@ -1007,7 +1015,14 @@ int pjd_batch_set_resize_filter(pjd_batch *b, int filter)
     const size_t n = P.images.size();
     for (size_t i = 0; i < n; i++) {
         const PjdDevResize &r = b->h_rs[i];
-        if (r.sw > 16u * r.tw || r.sh > 16u * r.th) {
+        if (b->windowed) {
+            // the limit is the window's (include/pjd.h): its size against the virtual target
+            const PjdDevResizeWin &w = b->h_win[i];
+            if (w.w > 16u * w.vw || w.h > 16u * w.vh) {
+                ctx->err = fmt_image("set_resize_filter: the window of picture %d is more than 16x its virtual target on an axis (pre-scale with PJD_F_SCALE_*)", (int)i);
+                return PJD_E_ARG;
+            }
+        } else if (r.sw > 16u * r.tw || r.sh > 16u * r.th) {
             ctx->err = fmt_image("set_resize_filter: picture %d is more than 16x its target on an axis at its decode size (pre-scale with PJD_F_SCALE_*)", (int)i);
             return PJD_E_ARG;
         }
@@ -1041,12 +1056,17 @@ int pjd_batch_set_resize_filter(pjd_batch *b, int filter)
     uint32_t lds = 0;
     for (size_t i = 0; i < n; i++) {
         const PjdDevResize &r = b->h_rs[i];
-        if (tab.size() + ((size_t)r.tw + r.th) * (1u + PJD_AA_MAX_TAPS) >= (1ull << 31)) { ctx->err = "set_resize_filter: the weight table of this batch is too large"; return PJD_E_ARG; }
-        const Axis x = axis(r.sw, r.tw), y = axis(r.sh, r.th);
+        // a windowed picture takes the tables of its windowed axes, over the whole virtual target (tap index ox + i', row length vw)
+        PjdDevResizeWin w{0, 0, r.sw, r.sh, r.tw, r.th, 0, 0, 0, 0};
+        if (b->windowed) w = b->h_win[i];
+        if (tab.size() + ((size_t)w.vw + w.vh) * (1u + PJD_AA_MAX_TAPS) >= (1ull << 31)) { ctx->err = "set_resize_filter: the weight table of this batch is too large"; return PJD_E_ARG; }
+        const Axis x = axis(w.w, w.vw), y = axis(w.h, w.vh);
         recs[i] = PjdDevResizeAA{x.off, x.taps, y.off, y.taps};
         // the widest row segment one of its tiles stages: first tap of the tile's first column to the last tap of its last one
         for (uint32_t c0 = 0; c0 < r.tw; c0 += PJD_RS_COLS) {
-            const uint32_t c1 = std::min(c0 + PJD_RS_COLS, r.tw) - 1u, h0 = tab[x.off + c0], h1 = tab[x.off + c1];
+            uint32_t e0, e1;                                // the tile's two ends in the table: mirrored where the window flips
+            pjd_resize_win_ends(w, r.tw, c0, std::min(c0 + PJD_RS_COLS, r.tw) - 1u, e0, e1);
+            const uint32_t h0 = tab[x.off + e0], h1 = tab[x.off + e1];
             lds = std::max(lds, pjd_resize_aa_lds((h1 & 0xffffu) + (h1 >> 16) - (h0 & 0xffffu), P.planar));
         }
     }
@@ -1065,6 +1085,25 @@ int pjd_batch_set_resize_filter(pjd_batch *b, int filter)
 }
 
 namespace {
+
+// THE validation of a source window (include/pjd.h): null, or what is wrong with it
+const char *resize_window_fault(uint32_t sw, uint32_t sh, uint32_t tw, uint32_t th, const pjd_resize_window *win, int filter)
+{
+    if (sw == 0 || sw > 65535u || sh == 0 || sh > 65535u || tw == 0 || tw > 65535u || th == 0 || th > 65535u) return "picture and target sizes must be 1..65535";
+    if (!win) return "null record";
+    if (filter != PJD_RESIZE_BILINEAR && filter != PJD_RESIZE_ANTIALIAS) return "unknown filter (PJD_RESIZE_BILINEAR or PJD_RESIZE_ANTIALIAS)";
+    if ((win->w == 0) != (win->h == 0)) return "an empty window (w and h are both 0 for the whole picture, or both at least 1)";
+    if (win->w == 0 && (win->x != 0 || win->y != 0)) return "x and y must be 0 where w == h == 0 (the whole picture)";
+    const uint64_t w = win->w ? win->w : sw, h = win->h ? win->h : sh;
+    if ((uint64_t)win->x + w > sw || (uint64_t)win->y + h > sh) return "the window is not inside the picture at its decode size";
+    if (win->vw > 65535u || win->vh > 65535u) return "the virtual target must be at most 65535 x 65535";
+    const uint64_t vw = win->vw ? win->vw : tw, vh = win->vh ? win->vh : th;
+    if ((uint64_t)win->ox + tw > vw || (uint64_t)win->oy + th > vh) return "the delivered columns and rows are not inside the virtual target";
+    if (win->flags & ~PJD_RW_HFLIP) return "unknown flag bits";
+    if (win->reserved_ != 0) return "reserved_ must be 0";
+    if (filter == PJD_RESIZE_ANTIALIAS && (w > 16u * vw || h > 16u * vh)) return "the window is more than 16x its virtual target on an axis (PJD_RESIZE_ANTIALIAS)";
+    return nullptr;
+}
 
 // binary32 -> binary16 bits, round to nearest even, subnormals kept, overflow to infinity (the host side of PJD_DT_F16; the device
 // converts in hardware, tests/test_gpu_normalize.py holds the two together)
@@ -1099,6 +1138,54 @@ bool finite_f32(float f)
 }
 
 }  // namespace
+
+int pjd_resize_window_check(uint32_t sw, uint32_t sh, uint32_t tw, uint32_t th, const pjd_resize_window *win, int filter)
+{
+    return resize_window_fault(sw, sh, tw, th, win, filter) ? PJD_E_ARG : PJD_OK;
+}
+
+int pjd_batch_set_resize_window(pjd_batch *b, const pjd_resize_window *win)
+{
+    if (!b) return PJD_E_ARG;
+    pjd_ctx *ctx = b->ctx;
+    if (!b->resized) { ctx->err = "set_resize_window: no resize is set (pjd_batch_set_resize first)"; return PJD_E_STATE; }
+    if (b->win_set) { ctx->err = "set_resize_window: already set for this batch"; return PJD_E_STATE; }
+    if (b->filter_set) { ctx->err = "set_resize_window after set_resize_filter"; return PJD_E_STATE; }
+    if (b->norm.dtype != 0) { ctx->err = "set_resize_window after set_normalize"; return PJD_E_STATE; }
+    if (b->bound) { ctx->err = "set_resize_window after bind_output"; return PJD_E_STATE; }
+    if (b->uploaded) { ctx->err = "set_resize_window after upload"; return PJD_E_STATE; }
+    if (!win) { ctx->err = "set_resize_window: null record array"; return PJD_E_ARG; }
+    const size_t n = b->plan.images.size();
+    bool any = false;
+    for (size_t i = 0; i < n; i++) {
+        const PjdDevResize &r = b->h_rs[i];
+        const pjd_resize_window &w = win[i];
+        if (const char *fault = resize_window_fault(r.sw, r.sh, r.tw, r.th, &w, PJD_RESIZE_BILINEAR)) {
+            ctx->err = fmt_image("set_resize_window: picture %d: ", (int)i) + fault;
+            return PJD_E_ARG;
+        }
+        any = any || w.x || w.y || w.w || w.h || w.vw || w.vh || w.ox || w.oy || w.flags;
+    }
+    if (any) {
+        // the records with every default resolved, as the kernels read them; all zero: the batch keeps the launch it had
+        hipSetDevice(ctx->device);
+        const size_t bytes = n * sizeof(PjdDevResizeWin);
+        void *h_win = nullptr, *d_win = nullptr;
+        int rc = pool_pin_alloc(ctx, &h_win, bytes, b->pin_blocks);
+        if (rc == PJD_OK) rc = pool_dev_alloc(ctx, &d_win, bytes, b->dev_blocks);
+        if (rc != PJD_OK) return rc;                       // what was taken stays with the batch until it is destroyed
+        b->device_bytes += bytes;
+        b->h_win = (PjdDevResizeWin *)h_win; b->d_win = (PjdDevResizeWin *)d_win; b->win_bytes = bytes;
+        for (size_t i = 0; i < n; i++) {
+            const PjdDevResize &r = b->h_rs[i];
+            const pjd_resize_window &w = win[i];
+            b->h_win[i] = PjdDevResizeWin{w.x, w.y, w.w ? w.w : r.sw, w.h ? w.h : r.sh, w.vw ? w.vw : r.tw, w.vh ? w.vh : r.th, w.ox, w.oy, w.flags, 0u};
+        }
+        b->windowed = true;
+    }
+    b->win_set = true;
+    return PJD_OK;
+}
 
 int pjd_normalize_value(int dtype, uint32_t v, float scale, float bias, void *out)
 {

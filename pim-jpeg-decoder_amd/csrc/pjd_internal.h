@@ -427,6 +427,32 @@ struct PjdDevResizeAA {
     uint32_t y_tab, y_taps;
 };
 
+// the LDS a tile needs for a row segment of `span` source pixels (the host sizes the launch with it, the kernel lays its segment out with it)
+static inline __host__ __device__ uint32_t pjd_resize_aa_lds(uint32_t span, bool planar) { return planar ? 3u * ((span + 6u) & ~3u) : (3u * span + 6u) & ~3u; }
+
+// ---- source windows (pjd_batch_set_resize_window; the arithmetic is normative: include/pjd.h) -----------------------------------
+// What the windowed launches (pjd_k_resize_win.hip) read beside the work list: per picture the window with every default resolved
+// (w, h >= 1; vw, vh >= 1; ox + tw <= vw, oy + th <= vh).  The taps of target column i are those of index ox + i' over (w, vw), i' = i
+// or tw - 1 - i with PJD_RW_HFLIP, and they address source columns from x on; rows likewise without the mirror.  PjdDevResize keeps
+// the whole picture (sh is the plane stride of a planar source) and the delivered target.  With the antialiased filter the tables
+// of PjdDevResizeAA are those of the axes (w, vw) and (h, vh): vw and vh are their row lengths.
+struct PjdDevResizeWin {
+    uint32_t x, y, w, h;
+    uint32_t vw, vh;
+    uint32_t ox, oy;
+    uint32_t flags;                    // PJD_RW_HFLIP
+    uint32_t pad_;
+};
+
+// the tap indices of the two ends of a tile's columns [c0, c1] of a windowed picture, lowest first: the staged segment runs from the
+// first tap of `lo` to the last tap of `hi` (the host sizes the LDS with it, the kernel stages with it)
+static inline __host__ __device__ void pjd_resize_win_ends(const PjdDevResizeWin &w, uint32_t tw, uint32_t c0, uint32_t c1, uint32_t &lo, uint32_t &hi)
+{
+    const bool flip = (w.flags & 1u) != 0;
+    lo = w.ox + (flip ? tw - 1u - c1 : c0);
+    hi = w.ox + (flip ? tw - 1u - c0 : c1);
+}
+
 // ---- normalised float output (pjd_batch_set_normalize; the arithmetic is normative: include/pjd.h) ---------------------------
 // The fma stage of one sample: the exact value of v * scale + bias rounded ONCE to binary32, to nearest even.  THE implementation:
 // pjd_normalize_value exports it to the host (where it is libm's fmaf unless the target has the instruction), the epilogue of

@@ -1,0 +1,68 @@
+// pjd_k_resize_win_body.h -- the body of the windowed bilinear kernel pjd_k_resize_win<PLANAR, DT> of pjd_k_resize_win.hip: the work
+// division of pjd_k_resize_body.h (one wave per tile, a lane PJD_RS_PX adjacent pixels of each of its rows, row taps made by the first
+// PJD_RS_ROWS lanes and read back as scalars), with the taps of a source WINDOW (pjd_batch_set_resize_window, include/pjd.h):
+//   - column taps are pjd_resize_tap_calc(w.w, w.vw, w.ox + i'), i' the lane's column or its mirror image (PJD_RW_HFLIP); the lane
+//     keeps its four target columns and their store order, only the tap index is mirrored;
+//   - row taps are pjd_resize_tap_calc(w.h, w.vh, w.oy + row), and y1 clamps to the window's last row, not the picture's;
+//   - both address the source from (w.x, w.y) on; the plane stride of a planar source stays the whole picture's (r.sh).
+// A textual include, so that tools/resize_window_host.cpp runs this very text on the host.
+// In scope: PLANAR, DT, src, dst, recs, win, tile_prefix, n_images, n_tiles, nz; lerp8 and store_row.
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t tile = __builtin_amdgcn_readfirstlane(blockIdx.x * PJD_RS_WAVES + (threadIdx.x >> 6));
+    if (tile >= n_tiles) return;
+    uint32_t lo = 0, hi = n_images;
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (tile_prefix[mid] <= tile) lo = mid; else hi = mid;
+    }
+    const PjdDevResize r = recs[lo];
+    const PjdDevResizeWin w = win[lo];
+    const uint32_t t = tile - tile_prefix[lo];
+    const uint32_t row0 = (t / r.col_tiles) * PJD_RS_ROWS;
+    const uint32_t col0 = (t % r.col_tiles) * PJD_RS_COLS + lane * PJD_RS_PX;
+
+    uint32_t rowtap[PJD_RS_ROWS];                          // y0 (in the window) | wy << 16
+    {
+        const uint32_t row = row0 + (lane & (PJD_RS_ROWS - 1));
+        uint32_t y0, y1, wy;
+        pjd_resize_tap_calc(w.h, w.vh, w.oy + (row < r.th ? row : r.th - 1), y0, y1, wy);
+        const uint32_t packed = y0 | (wy << 16);
+#pragma unroll
+        for (int k = 0; k < PJD_RS_ROWS; k++) rowtap[k] = __builtin_amdgcn_readlane(packed, k);
+    }
+    if (col0 >= r.tw) return;                              // only now: the lanes that computed row taps may have no column
+
+    const bool flip = (w.flags & PJD_RW_HFLIP) != 0;
+    uint32_t x0[PJD_RS_PX], x1[PJD_RS_PX], wx[PJD_RS_PX];
+#pragma unroll
+    for (int k = 0; k < PJD_RS_PX; k++) {
+        const uint32_t c = col0 + k < r.tw ? col0 + k : r.tw - 1;
+        pjd_resize_tap_calc(w.w, w.vw, w.ox + (flip ? r.tw - 1u - c : c), x0[k], x1[k], wx[k]);
+        x0[k] += w.x; x1[k] += w.x;                        // x1 was clamped to the window: nothing right of it is read
+        if (!PLANAR) { x0[k] *= 3u; x1[k] *= 3u; }
+    }
+    const uint32_t n_px = r.tw - col0 < PJD_RS_PX ? r.tw - col0 : PJD_RS_PX;
+    const uint8_t *sp = src + r.src_off + (uint64_t)w.y * r.src_stride;           // row 0 of the window
+    uint8_t *dp = dst + r.dst_off;
+    const uint64_t src_plane = PLANAR ? (uint64_t)r.src_stride * r.sh : 1u;        // the whole picture's plane
+    const uint64_t dst_plane = PLANAR ? (uint64_t)r.tw * r.th : 1u;
+    const uint32_t dst_stride = PLANAR ? r.tw : 3u * r.tw;
+
+#pragma unroll
+    for (int k = 0; k < PJD_RS_ROWS; k++) {
+        const uint32_t row = row0 + k;
+        if (row >= r.th) break;                            // uniform
+        const uint32_t y0 = rowtap[k] & 0xffffu, wy = rowtap[k] >> 16, y1 = y0 + 1u < w.h ? y0 + 1u : w.h - 1u;
+        const uint8_t *s0 = sp + (uint64_t)y0 * r.src_stride, *s1 = sp + (uint64_t)y1 * r.src_stride;
+        uint32_t px[3][PJD_RS_PX];
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            const uint8_t *c0 = s0 + c * src_plane, *c1 = s1 + c * src_plane;
+#pragma unroll
+            for (int q = 0; q < PJD_RS_PX; q++) {
+                const uint32_t top = lerp8(c0[x0[q]], c0[x1[q]], wx[q]), bot = lerp8(c1[x0[q]], c1[x1[q]], wx[q]);
+                px[c][q] = (__umul24(256u - wy, top) + __umul24(wy, bot) + 32768u) >> 16;
+            }
+        }
+        store_row<PLANAR, DT>(px, dp, row, col0, n_px, dst_plane, dst_stride, nz);
+    }

@@ -75,8 +75,12 @@ void pjd_launch_resize(hipStream_t s, const uint8_t *src, uint8_t *dst, const Pj
 // says where picture i's weights lie in `tab` (pjd_internal.h); lds_bytes is the largest row segment a tile of the batch stages.
 void pjd_launch_resize_aa(hipStream_t s, const uint8_t *src, uint8_t *dst, const PjdDevResize *recs, const uint32_t *tile_prefix, uint32_t n_images,
                           uint32_t n_tiles, bool planar, const PjdNormalize &norm, const PjdDevResizeAA *aa, const uint32_t *tab, uint32_t lds_bytes);
-// the LDS a tile needs for a row segment of `span` source pixels (the host sizes the launch with it, the kernel lays its segment out with it)
-static inline __host__ __device__ uint32_t pjd_resize_aa_lds(uint32_t span, bool planar) { return planar ? 3u * ((span + 6u) & ~3u) : (3u * span + 6u) & ~3u; }
+// ---- windowed resize (pjd_k_resize_win.hip): either filter of the two launches above where the batch has source windows
+// (pjd_batch_set_resize_window).  win[i] is picture i's window, defaults resolved; aa / tab / lds_bytes as above where `antialias`
+// (the tables are those of the windowed axes, lds_bytes covers the segments of mirrored tiles), unused otherwise.
+void pjd_launch_resize_win(hipStream_t s, const uint8_t *src, uint8_t *dst, const PjdDevResize *recs, const PjdDevResizeWin *win,
+                           const uint32_t *tile_prefix, uint32_t n_images, uint32_t n_tiles, bool planar, const PjdNormalize &norm, bool antialias,
+                           const PjdDevResizeAA *aa, const uint32_t *tab, uint32_t lds_bytes);
 // ---- stage-level parity (pjd_k_coefdump.hip): coefficients in the reference's MCU_buffer layout; `out` is zeroed by the caller
 void pjd_launch_coefdump_lanes(hipStream_t s, const PjdDevBatch &b, uint32_t image, uint32_t n_iwg, int16_t *out);
 void pjd_launch_coefdump_dense(hipStream_t s, const PjdDevBatch &b, uint32_t image, const int16_t *scratch, uint32_t first_du, uint32_t n_du, int16_t *out);

@@ -21,6 +21,7 @@ PLAN_LATENCY, PLAN_THROUGHPUT = 0, 1      # pjd_set_plan_mode
 F_STANDARD_RESTART, F_FORCE_SEQUENTIAL, F_STANDARD_ZIGZAG, F_PROGRESSIVE = 1, 2, 4, 8
 F_SCALE_1_2, F_SCALE_1_4, F_SCALE_1_8, F_SCALE_MASK = 16, 32, 48, 48      # output scale s = 1 << ((flags >> 4) & 3) (pjd.h)
 RESIZE_BILINEAR, RESIZE_ANTIALIAS = 0, 1   # pjd_batch_set_resize_filter (pjd.h)
+RW_HFLIP = 1                               # pjd_resize_window.flags: the delivered picture mirrored left-right
 AA_MAX_TAPS = 32                           # PJD_AA_MAX_TAPS: the most taps per axis pjd_resize_aa_taps returns
 DT_F16, DT_BF16, DT_F32 = 1, 2, 3         # pjd_batch_set_normalize: IEEE binary16, bfloat16, IEEE binary32 (pjd.h)
 SCAN_PROGRESSIVE = 1
@@ -62,6 +63,13 @@ class Timings(C.Structure):
 
     def as_dict(self):
         return {self.name[i].value.decode(): float(self.ms[i]) for i in range(self.n)}
+
+
+class ResizeWindow(C.Structure):
+    """pjd_resize_window (pjd.h): the source window (x, y, w, h; w == h == 0: the whole picture), the virtual target it is resampled to
+    (vw, vh; 0: the picture's target), the part of it that is delivered (from ox, oy) and RW_HFLIP in flags.  All zero: the identity."""
+    _fields_ = [("x", C.c_uint32), ("y", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32), ("vw", C.c_uint32), ("vh", C.c_uint32),
+                ("ox", C.c_uint32), ("oy", C.c_uint32), ("flags", C.c_uint32), ("reserved_", C.c_uint32)]
 
 
 class BatchInfo(C.Structure):
@@ -176,6 +184,10 @@ def dev_lib():
         L.pjd_batch_set_resize_filter.argtypes = [vp, i32]
         L.pjd_resize_aa_taps.restype = i32
         L.pjd_resize_aa_taps.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.pjd_batch_set_resize_window.restype = i32
+        L.pjd_batch_set_resize_window.argtypes = [vp, C.POINTER(ResizeWindow)]
+        L.pjd_resize_window_check.restype = i32
+        L.pjd_resize_window_check.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(ResizeWindow), i32]
         L.pjd_batch_set_normalize.restype = i32
         L.pjd_batch_set_normalize.argtypes = [vp, i32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         L.pjd_normalize_value.restype = i32
@@ -409,6 +421,19 @@ class Batch:
         hs = (C.c_uint32 * max(self.n, 1))(*[h for h, _ in sizes])
         self.ctx._check(self.L.pjd_batch_set_resize(self._h, ws, hs), "pjd_batch_set_resize")
         self._resize = sizes
+
+    def set_resize_window(self, windows):
+        """pjd_batch_set_resize_window: picture i is resampled from a window of the decoded picture to a window of a virtual target,
+        mirrored where asked -- flip(resize(P[y:y+h, x:x+w], vw, vh)[oy:oy+th, ox:ox+tw]), the arithmetic include/pjd.h specifies.
+        windows[i]: a ResizeWindow, None (the whole picture: the all-zero record), or a dict / tuple of its fields (x, y, w, h, vw, vh,
+        ox, oy, flags).  Once, after set_resize() and before set_resize_filter() / set_normalize() / bind_output() / upload()."""
+        if len(windows) != self.n:
+            raise ValueError("set_resize_window: one window (or None) per picture")
+        arr = (ResizeWindow * max(self.n, 1))()
+        for i, w in enumerate(windows):
+            if w is not None:
+                arr[i] = resize_window(w)
+        self.ctx._check(self.L.pjd_batch_set_resize_window(self._h, arr), "pjd_batch_set_resize_window")
 
     def set_resize_filter(self, filter):
         """pjd_batch_set_resize_filter: RESIZE_ANTIALIAS makes the resize the widened triangle filter include/pjd.h specifies bit for
@@ -672,6 +697,34 @@ def resize_aa_taps(src_n, dst_n, i):
     if not all(0 <= int(v) < 2 ** 32 for v in (src_n, dst_n, i)) or dev_lib().pjd_resize_aa_taps(int(src_n), int(dst_n), int(i), C.byref(first), C.byref(count), q) != 0:
         raise ValueError(f"resize_aa_taps({src_n}, {dst_n}, {i}): sizes must be 1..65535, i < dst_n and src_n <= 16 * dst_n")
     return first.value, list(q[:count.value])
+
+
+def resize_window(w):
+    """A ResizeWindow from a ResizeWindow (copied), a dict of its fields, or a tuple (x, y, w, h[, vw, vh, ox, oy, flags]).  ValueError
+    for a field outside 32 bits."""
+    if isinstance(w, ResizeWindow):
+        vals = [getattr(w, k) for k, _ in ResizeWindow._fields_]
+    elif isinstance(w, dict):
+        if set(w) - {k for k, _ in ResizeWindow._fields_}:
+            raise ValueError(f"resize_window: unknown fields {sorted(set(w) - {k for k, _ in ResizeWindow._fields_})}")
+        vals = [w.get(k, 0) for k, _ in ResizeWindow._fields_]
+    else:
+        vals = list(w) + [0] * (10 - len(w))
+        if not 4 <= len(w) <= 10 or vals[9] != 0:
+            raise ValueError("resize_window: (x, y, w, h[, vw, vh, ox, oy, flags])")
+    if not all(0 <= int(v) < 2 ** 32 for v in vals):
+        raise ValueError("resize_window: every field must fit 32 bits")
+    return ResizeWindow(*[int(v) for v in vals])
+
+
+def resize_window_check(sw, sh, tw, th, window, filter=RESIZE_BILINEAR):
+    """pjd_resize_window_check (host only): True where pjd_batch_set_resize_window (and, with RESIZE_ANTIALIAS, set_resize_filter) would
+    accept `window` (anything resize_window() takes; None: the all-zero record) for a picture of sw x sh at its decode size and a target
+    of tw x th; the one implementation of the rules of include/pjd.h."""
+    if not all(0 <= int(v) < 2 ** 32 for v in (sw, sh, tw, th)):
+        return False
+    rec = ResizeWindow() if window is None else resize_window(window)
+    return dev_lib().pjd_resize_window_check(int(sw), int(sh), int(tw), int(th), C.byref(rec), int(filter)) == 0
 
 
 def normalize_value(dtype, v, scale, bias):

@@ -3,10 +3,14 @@
 The batch is bound (Batch.bind_output, pjd_batch_bind_output of include/pjd.h) to ONE torch.uint8 buffer this module allocates
 on the context's device; the back end writes the pictures straight into it -- planar R, G, B (OUT_RGB8_PLANAR, "CHW") by
 default -- and the results are views of that buffer.  No native code of its own.  torch is imported inside the functions that
-need it: uniform_output_shape(), pick_scale_flags() and normalize_constants() are pure.
+need it: uniform_output_shape(), pick_scale_flags(), normalize_constants(), center_crop_window() and window_at_scale() are pure.
 
 Pictures of different sizes become ONE [N, 3, H, W] tensor with decode_resized_batch_tensor: the library resamples every picture to
 H x W inside the decode (Batch.set_resize, pjd_batch_set_resize), after the box pre-scale pick_scale_flags chooses.
+
+Crops and flips ride in that resample (Batch.set_resize_window, pjd_batch_set_resize_window): crops= takes what
+RandomResizedCrop.get_params returns, flips= mirrors, resize_short= is Resize(int) + CenterCrop(size).  Every picture is still decoded
+whole; the window costs no launch and no uint8 tensor.
 
 The tensor a model takes -- fp16, bf16 or fp32, (x / 255 - mean) / std -- comes out of the same launch with
 decode_normalized_batch_tensor (Batch.set_normalize, pjd_batch_set_normalize): no uint8 tensor, no elementwise kernels after it.
@@ -55,13 +59,15 @@ def _torch():
     return torch
 
 
-def _run(ctx, descs, out_format, capacity, offsets, device, resize=None, normalize=None, antialias=False):
-    """Create, (set the resize, its filter, the normalisation,) bind to a fresh torch buffer, upload, decode, sync -> (buffer, batch offsets,
+def _run(ctx, descs, out_format, capacity, offsets, device, resize=None, normalize=None, antialias=False, windows=None):
+    """Create, (set the resize, its windows, its filter, the normalisation,) bind to a fresh torch buffer, upload, decode, sync -> (buffer, batch offsets,
     statuses).  The buffer is torch.uint8 whatever the elements are: torch aligns it far beyond an element."""
     torch = _torch()
     with ctx.batch(descs, out_format) as b:
         if resize is not None:
             b.set_resize(resize)
+            if windows is not None:
+                b.set_resize_window(windows)
             if antialias:
                 b.set_resize_filter(pjd_amd.RESIZE_ANTIALIAS)
         if normalize is not None:
@@ -131,7 +137,81 @@ def prescaled_descs(descs, size):
     return out
 
 
-def decode_resized_batch_tensor(ctx, descs, size, prescale=True, device=None, antialias=False):
+def center_crop_window(src_hw, resize_short, size):
+    """torchvision's Resize(resize_short) followed by CenterCrop(size) of a picture of src_hw = (h, w), as the fields of a window over
+    the whole picture: {"vw", "vh", "ox", "oy"}.  The short side becomes resize_short, the long one int(resize_short * long / short);
+    ox, oy = int(round((v - t) / 2.0)) with Python's round-half-even, as torchvision.transforms.functional.center_crop has it.
+    ValueError where the resized picture is smaller than size = (H, W) on an axis: there is no padding here.  Pure."""
+    h, w = int(src_hw[0]), int(src_hw[1])
+    rs, th, tw = int(resize_short), int(size[0]), int(size[1])
+    if h < 1 or w < 1 or rs < 1 or th < 1 or tw < 1:
+        raise ValueError("center_crop_window: sizes must be at least 1")
+    if w <= h:
+        vw, vh = rs, int(rs * h / w)
+    else:
+        vw, vh = int(rs * w / h), rs
+    if vw < tw or vh < th:
+        raise ValueError(f"center_crop_window: a {w}x{h} picture resized to {vw}x{vh} is smaller than the crop {tw}x{th} (no padding)")
+    return {"vw": vw, "vh": vh, "ox": int(round((vw - tw) / 2.0)), "oy": int(round((vh - th) / 2.0))}
+
+
+def window_at_scale(crop, log2s, sw, sh):
+    """The crop (x, y, w, h), given in FULL-SIZE picture coordinates, at the decode scale s = 1 << log2s, where the picture is sw x sh:
+    the hull [x >> log2s, ceil((x + w) / s)) x [y >> log2s, ceil((y + h) / s)), clipped to the scaled picture -> (x, y, w, h).  An
+    approximation where s > 1: the box pre-scale comes first and its cells do not end at the crop's edges, so the result differs from a
+    resize of the crop of the full-size picture (as prescale=True differs for antialias); s = 1 is exact.  Pure."""
+    x, y, w, h = (int(v) for v in crop)
+    log, sw, sh = int(log2s), int(sw), int(sh)
+    if x < 0 or y < 0 or w < 1 or h < 1:
+        raise ValueError("window_at_scale: crop (x, y, w, h) with x, y >= 0 and w, h >= 1")
+    r = (1 << log) - 1
+    x0, y0 = min(x >> log, sw - 1), min(y >> log, sh - 1)
+    x1, y1 = min((x + w + r) >> log, sw), min((y + h + r) >> log, sh)
+    return x0, y0, max(x1 - x0, 1), max(y1 - y0, 1)
+
+
+def _windowed(descs, size, prescale, crops, flips, resize_short):
+    """The descriptors to decode and the windows to set for crops / flips / resize_short (None, None: nothing asked).  The pre-scale
+    is chosen per picture with the CROP's size against the virtual target."""
+    th, tw = size
+    n = len(descs)
+    if crops is None and flips is None and resize_short is None:
+        return (prescaled_descs(descs, size) if prescale else descs), None
+    if crops is not None and resize_short is not None:
+        raise ValueError("crops and resize_short exclude each other")
+    for name, v in (("crops", crops), ("flips", flips)):
+        if v is not None and len(v) != n:
+            raise ValueError(f"{name}: one entry per picture")
+    import ctypes
+    run, windows = [], []
+    for i, d in enumerate(descs):
+        W, H = int(d.width), int(d.height)
+        win = {}
+        crop = crops[i] if crops is not None else None
+        if crop is not None:
+            x, y, w, h = (int(v) for v in crop)
+            if x < 0 or y < 0 or w < 1 or h < 1 or x + w > W or y + h > H:
+                raise ValueError(f"crops[{i}] = {tuple(crop)} is not inside the {W}x{H} picture")
+        if resize_short is not None:
+            win.update(center_crop_window((H, W), resize_short, size))
+        vw, vh = win.get("vw", tw), win.get("vh", th)
+        if prescale:
+            c = pjd_amd.ImageDesc()
+            ctypes.memmove(ctypes.byref(c), ctypes.byref(d), ctypes.sizeof(pjd_amd.ImageDesc))
+            cw, ch = (crop[2], crop[3]) if crop is not None else (W, H)
+            c.flags = (int(d.flags) & ~pjd_amd.F_SCALE_MASK) | pick_scale_flags(cw, ch, vw, vh)
+            d = c
+        if crop is not None:
+            h_s, w_s = output_hw(d)
+            win["x"], win["y"], win["w"], win["h"] = window_at_scale(crop, _scale_log(d.flags), w_s, h_s)
+        if flips is not None and flips[i]:
+            win["flags"] = pjd_amd.RW_HFLIP
+        run.append(d)
+        windows.append(win or None)
+    return run, windows
+
+
+def decode_resized_batch_tensor(ctx, descs, size, prescale=True, device=None, antialias=False, crops=None, flips=None, resize_short=None):
     """Pictures of ANY sizes -> (uint8 tensor [N, 3, H, W], statuses), size = (H, W): every picture is resampled to H x W inside
     the decode (the bilinear filter of include/pjd.h, pjd_batch_set_resize) and lands at offset i * 3 * H * W of one buffer, so
     the result is one contiguous NCHW tensor with no copy after the decode, complete on return and readable on any torch stream
@@ -141,16 +221,22 @@ def decode_resized_batch_tensor(ctx, descs, size, prescale=True, device=None, an
     torch.nn.functional.interpolate(mode="bilinear", antialias=True), torchvision's Resize(antialias=True) and Pillow's BILINEAR
     compute, to within 1 level.  With prescale=True the box pre-scale is still chosen (less to decode; the triangle filter removes
     what the box leaves), so the result differs from an antialiased resize of the full-size picture; prescale=False gives exactly
-    that, for pictures up to 16x the target on each axis (beyond that the call raises)."""
+    that, for pictures up to 16x the target on each axis (beyond that the call raises).
+    crops=[(x, y, w, h) | None, ...]: picture i is that crop of the FULL-SIZE picture resized to H x W (what
+    RandomResizedCrop.get_params returns: x = left, y = top); flips=[bool, ...]: mirrored left-right; resize_short=int: torchvision's
+    Resize(int) + CenterCrop(size) (center_crop_window; ValueError where the resized picture is smaller than size).  All three ride in
+    the one resample launch (Batch.set_resize_window); the picture is decoded whole.  With prescale=False the result is exactly the
+    filter of include/pjd.h over the crop of the full-size picture; with prescale=True the pre-scale is chosen from the crop's size
+    and the crop becomes window_at_scale's hull of it, an approximation in the same sense as for antialias above."""
     if len(descs) == 0:
         raise ValueError("decode_resized_batch_tensor: no pictures")
     th, tw = int(size[0]), int(size[1])
+    run, windows = _windowed(descs, (th, tw), prescale, crops, flips, resize_short)
     torch = _torch()
     device = torch.device("cuda", ctx.device) if device is None else device
-    run = prescaled_descs(descs, (th, tw)) if prescale else descs
     n, plane = len(descs), 3 * th * tw
     buf, _, st = _run(ctx, run, pjd_amd.OUT_RGB8_PLANAR, n * plane, [i * plane for i in range(n)], device, resize=[(th, tw)] * n,
-                      antialias=antialias)
+                      antialias=antialias, windows=windows)
     return buf.view(n, 3, th, tw), st
 
 
@@ -167,7 +253,7 @@ def normalize_constants(mean, std):
 
 
 def decode_normalized_batch_tensor(ctx, descs, size, mean, std, dtype=None, channels_last=False, prescale=True, device=None,
-                                   antialias=False):
+                                   antialias=False, crops=None, flips=None, resize_short=None):
     """Pictures of ANY sizes -> (tensor of `dtype` [N, 3, H, W], statuses), size = (H, W); dtype torch.float16 (the default),
     torch.bfloat16 or torch.float32.  As decode_resized_batch_tensor, and every sample v of channel c leaves the same launch as
     fma(v, scale[c], bias[c]) with the constants of normalize_constants(mean, std), converted once to `dtype` (include/pjd.h,
@@ -176,7 +262,8 @@ def decode_normalized_batch_tensor(ctx, descs, size, mean, std, dtype=None, chan
     and the result is its permute(0, 3, 1, 2) view: shape [N, 3, H, W] in torch's channels_last memory format.  Complete on return and
     readable on any torch stream (module docstring, "Stream order").  antialias=True: the antialiased filter, as in
     decode_resized_batch_tensor -- with prescale=True the result differs from an antialiased resize of the full-size picture (the box
-    pre-scale comes first), prescale=False gives exactly that up to the 16x limit."""
+    pre-scale comes first), prescale=False gives exactly that up to the 16x limit.  crops, flips, resize_short: as in
+    decode_resized_batch_tensor."""
     if len(descs) == 0:
         raise ValueError("decode_normalized_batch_tensor: no pictures")
     th, tw = int(size[0]), int(size[1])
@@ -188,9 +275,9 @@ def decode_normalized_batch_tensor(ctx, descs, size, mean, std, dtype=None, chan
         raise ValueError("decode_normalized_batch_tensor: dtype must be torch.float16, torch.bfloat16 or torch.float32")
     dt, es = dts[dtype]
     device = torch.device("cuda", ctx.device) if device is None else device
-    run = prescaled_descs(descs, (th, tw)) if prescale else descs
+    run, windows = _windowed(descs, (th, tw), prescale, crops, flips, resize_short)
     n, pic = len(descs), 3 * th * tw * es
     buf, _, st = _run(ctx, run, pjd_amd.OUT_RGB8 if channels_last else pjd_amd.OUT_RGB8_PLANAR, n * pic, [i * pic for i in range(n)], device,
-                      resize=[(th, tw)] * n, normalize=(dt, scale, bias), antialias=antialias)
+                      resize=[(th, tw)] * n, normalize=(dt, scale, bias), antialias=antialias, windows=windows)
     t = buf.view(dtype)
     return (t.view(n, th, tw, 3).permute(0, 3, 1, 2) if channels_last else t.view(n, 3, th, tw)), st

@@ -1,6 +1,6 @@
 """What resize on decode costs and what it saves: the default bench workload (1024 ragged pictures) to one uint8[N, 3, H, W] tensor.
 
-    python tools/resize_probe.py [--rounds 60] [--warmup 5] [--size 224] [--e2e-rounds 20] [--antialias]
+    python tools/resize_probe.py [--rounds 60] [--warmup 5] [--size 224] [--e2e-rounds 20] [--antialias] [--window]
 
 Prints one JSON line:
   kernel    per batch kind (prescale = pick_scale_flags, noprescale = full-size decode; planar and rgb8; planar bound to a torch
@@ -15,10 +15,16 @@ Prints one JSON line:
   device_bytes of the resized default batch, unbound and bound
 --antialias: every batch kind a second time with the antialiased filter (Batch.set_resize_filter, key suffix `_aa`), resident beside
 its bilinear twin and decoded in the same alternation, and `aa_over_bilinear`: the ratio of the two `resize` medians per kind.
+--window: every batch kind (and its `_aa` twin) a second time with source windows (Batch.set_resize_window, key suffix `_win`): seeded
+RandomResizedCrop windows with torchvision's defaults (area 8-100 %, aspect 3/4-4/3), every second picture mirrored; with the pre-scale
+the scale is picked from the crop's size, as pjd_amd.tensors does.  Resident beside the un-windowed twin and decoded in the same
+alternation.  `window` holds, per kind, the `resize` launch windowed beside un-windowed: both medians, the un-windowed launch's own
+spread in this run (min, max, and the 10th and 90th percentile), and their ratio.
 --e2e-rounds 0 leaves the end-to-end part out.
 """
 import argparse
 import json
+import math
 import os
 import statistics
 import sys
@@ -31,6 +37,25 @@ def stat(v):
     return {"median_ms": round(statistics.median(v), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4)}
 
 
+def pct(v, p):
+    v = sorted(v)
+    return v[min(len(v) - 1, int(p * len(v)))]
+
+
+def random_resized_crop(rng, W, H):
+    """torchvision's RandomResizedCrop.get_params with its defaults (area 8-100 %, aspect 3/4-4/3, log-uniform; ten tries, then the
+    centre crop at the nearest allowed aspect) -> (x, y, w, h); rng: a numpy Generator."""
+    for _ in range(10):
+        area = W * H * rng.uniform(0.08, 1.0)
+        ratio = math.exp(rng.uniform(math.log(3 / 4), math.log(4 / 3)))
+        w, h = int(round(math.sqrt(area * ratio))), int(round(math.sqrt(area / ratio)))
+        if 0 < w <= W and 0 < h <= H:
+            return int(rng.integers(0, W - w + 1)), int(rng.integers(0, H - h + 1)), w, h
+    r = W / H
+    w, h = (W, int(round(W / (3 / 4)))) if r < 3 / 4 else ((int(round(H * (4 / 3))), H) if r > 4 / 3 else (W, H))
+    return (W - w) // 2, (H - h) // 2, w, h
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=60)
@@ -39,6 +64,7 @@ def main():
     ap.add_argument("--images", type=int, default=1024)
     ap.add_argument("--size", type=int, default=224)
     ap.add_argument("--antialias", action="store_true")
+    ap.add_argument("--window", action="store_true")
     args = ap.parse_args()
     # before anything loads libpjd.so: torch and the library then share one HIP runtime (pjd_amd/tensors.py)
     import torch
@@ -66,10 +92,23 @@ def main():
              ("prescale", "planar", True)]
     batches, keep = {}, []
     kinds = [k + (False,) for k in kinds] + ([k + (True,) for k in kinds] if args.antialias else [])
-    for pre, fmt, bound, antialias in kinds:
-        key = f"{pre}_{fmt}" + ("_bound" if bound else "") + ("_aa" if antialias else "")
+    kinds = [k + (False,) for k in kinds] + ([k + (True,) for k in kinds] if args.window else [])
+    windows = {}
+    if args.window:
+        import numpy as np
+        rng = np.random.default_rng(7)
+        crops = [random_resized_crop(rng, int(d.width), int(d.height)) for d in descs["noprescale"]]
+        flips = [i % 2 == 1 for i in range(n)]
+        for pre in ("prescale", "noprescale"):
+            descs[pre + "_win"], windows[pre] = tensors._windowed(descs["noprescale"], (T, T), pre == "prescale", crops, flips, None)
+    for pre, fmt, bound, antialias, windowed in kinds:
+        key = f"{pre}_{fmt}" + ("_bound" if bound else "") + ("_aa" if antialias else "") + ("_win" if windowed else "")
+        if windowed:
+            pre = pre + "_win"
         b = ctx.batch(descs[pre], pjd_amd.OUT_RGB8_PLANAR if fmt == "planar" else pjd_amd.OUT_RGB8)
         b.set_resize([(T, T)] * n)
+        if windowed:
+            b.set_resize_window(windows[pre[:-4]])
         if antialias:
             b.set_resize_filter(pjd_amd.RESIZE_ANTIALIAS)
         out["device_bytes"][key] = b.info()["device_bytes"]
@@ -104,7 +143,15 @@ def main():
     keep.clear()
     if args.antialias:
         out["aa_over_bilinear"] = {k: round(out["kernel"][k + "_aa"]["resize"]["median_ms"] / out["kernel"][k]["resize"]["median_ms"], 2)
-                                   for k in list(out["kernel"]) if not k.endswith("_aa")}
+                                   for k in list(out["kernel"]) if not k.endswith("_aa") and k + "_aa" in out["kernel"]}
+    if args.window:
+        out["window"] = {}
+        for k in [k for k in out["kernel"] if not k.endswith("_win")]:
+            plain, win = samples[k]["resize"], samples[k + "_win"]["resize"]
+            out["window"][k] = {"plain_ms": stat(plain)["median_ms"], "plain_min_ms": round(min(plain), 4), "plain_max_ms": round(max(plain), 4),
+                                "plain_p10_ms": round(pct(plain, 0.1), 4), "plain_p90_ms": round(pct(plain, 0.9), 4),
+                                "windowed_ms": stat(win)["median_ms"], "windowed_min_ms": round(min(win), 4), "windowed_max_ms": round(max(win), 4),
+                                "windowed_over_plain": round(statistics.median(win) / statistics.median(plain), 3)}
 
     # ---- end to end against today's route
     runs = {}

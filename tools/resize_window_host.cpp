@@ -1,0 +1,213 @@
+// resize_window_host.cpp -- the bodies of the windowed resample kernels (pim-jpeg-decoder_amd/csrc/pjd_k_resize_win_body.h and
+// pjd_k_resize_win_aa_body.h, with the stores of pjd_k_resize_store.h) run on the host, thread by thread, under the sanitizers:
+// window and offset indexing, the mirrored tap index, the staged segment of a mirrored tile, all four dword remainders of a segment's
+// first byte in both layouts, the plane stride of a planar source whose window is lower than the picture, guard bytes.
+//
+//     clang++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize=alignment -o resize_window_host tools/resize_window_host.cpp \
+//         && ./resize_window_host
+//
+// Device builtins are replaced by host stand-ins: a lane's row taps are computed directly instead of being read from lane k, a
+// barrier is nothing, and a thread stages the whole row segment for itself (PJD_WIN_STAGE_*) into an "LDS" of exactly the size the
+// host would give the launch, allocated per thread so that AddressSanitizer sees its end.  The 16-bit conversions are the host
+// compiler's, so this says nothing about the GPU's (tests/test_gpu_normalize.py does).  The source holds every picture back to back
+// with NO padding between them beyond what rounds the buffer to a dword (the kernels stage whole dwords): a read outside a window
+// that mattered would change the result, a read outside the buffer is a sanitizer report.  The expectation is a plain per-pixel
+// loop over the arithmetic of include/pjd.h -- the tap inlines with a shifted index.  Prints ALL EQUAL.
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+#define __host__
+#define __device__
+#define __forceinline__ inline
+#define __restrict__
+#include "../include/pjd.h"
+#include "../pim-jpeg-decoder_amd/csrc/pjd_internal.h"
+struct Dim { uint32_t x; };
+static thread_local Dim threadIdx, blockIdx;
+static inline uint32_t __umul24(uint32_t a, uint32_t b) { return (a & 0xffffff) * (b & 0xffffff); }
+static inline uint32_t lerp8(uint32_t a, uint32_t b, uint32_t w) { return __umul24(256u - w, a) + __umul24(w, b); }
+static inline void __syncthreads() {}
+#include "../pim-jpeg-decoder_amd/csrc/pjd_k_resize_store.h"
+#define __builtin_amdgcn_readfirstlane(x) (x)
+static inline uint32_t emu_tap(uint32_t sn, uint32_t dn, uint32_t i) { uint32_t y0, y1, wy; pjd_resize_tap_calc(sn, dn, i, y0, y1, wy); return y0 | (wy << 16); }
+#define __builtin_amdgcn_readlane(p, k) emu_tap(w.h, w.vh, w.oy + (row0 + (k) < r.th ? row0 + (k) : r.th - 1))
+#define PJD_WIN_STAGE_FIRST 0u
+#define PJD_WIN_STAGE_STEP  1u
+
+template <bool PLANAR, int DT>
+static void thread_bilinear(const uint8_t *src, uint8_t *dst, const PjdDevResize *recs, const PjdDevResizeWin *win, const uint32_t *tile_prefix,
+                            uint32_t n_images, uint32_t n_tiles, const NormArgs nz)
+{
+#include "../pim-jpeg-decoder_amd/csrc/pjd_k_resize_win_body.h"
+}
+
+template <bool PLANAR, int DT>
+static void thread_aa(uint32_t *seg, const uint8_t *src, uint8_t *dst, const PjdDevResize *recs, const PjdDevResizeWin *win, const uint32_t *tile_prefix,
+                      uint32_t n_images, uint32_t n_tiles, const PjdDevResizeAA *aa, const uint32_t *tab, uint32_t lds_bytes, const NormArgs nz)
+{
+#include "../pim-jpeg-decoder_amd/csrc/pjd_k_resize_win_aa_body.h"
+}
+
+struct Case { uint32_t sw, sh, tw, th; PjdDevResizeWin w; };
+
+// the tap-major table of one axis, as pjd_batch_set_resize_filter lays it out: dn heads `first | count << 16`, then taps x dn weights
+static uint32_t axis_table(std::vector<uint32_t> &tab, uint32_t sn, uint32_t dn, uint32_t &taps)
+{
+    const size_t base = tab.size();
+    tab.resize(base + (size_t)dn * (1u + PJD_AA_MAX_TAPS), 0u);
+    uint32_t w[PJD_AA_MAX_TAPS];
+    taps = 0;
+    for (uint32_t i = 0; i < dn; i++) {
+        uint32_t first;
+        const uint32_t cnt = pjd_resize_aa_taps_calc(sn, dn, i, first, w);
+        tab[base + i] = first | (cnt << 16);
+        for (uint32_t t = 0; t < cnt; t++) tab[base + (size_t)(t + 1u) * dn + i] = w[t];
+        taps = std::max(taps, cnt);
+    }
+    tab.resize(base + (size_t)dn * (1u + taps));
+    return (uint32_t)base;
+}
+
+template <bool PLANAR, int DT, bool AA>
+static int run(uint32_t misalign_elems, unsigned seed)
+{
+    const uint32_t ES = DT == 0 ? 1 : PJD_DT_SIZE(DT);
+    // x, y, w, h, vw, vh, ox, oy, flags: the geometry of tests/test_gpu_resize_window.py and the four remainders of x
+    std::vector<Case> cases = {
+        {600, 40, 259, 5, {1, 2, 597, 35, 259, 5, 0, 0, 0, 0}}, {600, 40, 259, 5, {2, 2, 597, 35, 259, 5, 0, 0, 1, 0}},
+        {600, 40, 259, 5, {3, 2, 597, 35, 259, 5, 0, 0, 0, 0}}, {600, 40, 259, 5, {4, 2, 596, 35, 259, 5, 0, 0, 1, 0}},
+        {200, 120, 4, 4, {100, 40, 64, 64, 4, 4, 0, 0, 0, 0}},
+        {300, 20, 270, 9, {0, 0, 300, 20, 600, 20, 250, 3, 0, 0}}, {300, 20, 270, 9, {0, 0, 300, 20, 600, 20, 250, 3, 1, 0}},
+        {61, 45, 50, 33, {0, 0, 21, 15, 50, 33, 0, 0, 0, 0}}, {61, 45, 50, 33, {40, 30, 21, 15, 50, 33, 0, 0, 0, 0}},
+        {40, 300, 5, 131, {3, 7, 30, 290, 5, 131, 0, 0, 1, 0}},
+        {33, 70, 9, 7, {5, 9, 1, 1, 9, 7, 0, 0, 1, 0}},
+        {61, 45, 61, 45, {0, 0, 61, 45, 61, 45, 0, 0, 0, 0}}};
+    srand(seed);
+    for (int k = 0; k < 10; k++) {
+        Case c;
+        c.sw = 1 + rand() % 150; c.sh = 1 + rand() % 90;
+        c.w.w = 1 + rand() % c.sw; c.w.h = 1 + rand() % c.sh; c.w.x = rand() % (c.sw - c.w.w + 1); c.w.y = rand() % (c.sh - c.w.h + 1);
+        c.w.vw = std::max<uint32_t>(1 + rand() % 300, (c.w.w + 15) / 16); c.w.vh = std::max<uint32_t>(1 + rand() % 40, (c.w.h + 15) / 16);
+        c.tw = 1 + rand() % c.w.vw; c.th = 1 + rand() % c.w.vh; c.w.ox = rand() % (c.w.vw - c.tw + 1); c.w.oy = rand() % (c.w.vh - c.th + 1);
+        c.w.flags = rand() & 1; c.w.pad_ = 0;
+        cases.push_back(c);
+    }
+    const size_t n = cases.size();
+    std::vector<PjdDevResize> recs(n); std::vector<PjdDevResizeWin> wins(n); std::vector<PjdDevResizeAA> aas(n); std::vector<uint32_t> prefix(n + 1), tab;
+    size_t spos = 0, dpos = misalign_elems * ES; uint32_t t = 0, lds = 0;
+    std::vector<size_t> doff(n);
+    for (size_t i = 0; i < n; i++) {
+        const Case &c = cases[i]; PjdDevResize &r = recs[i];
+        if (c.sw > 65535 || c.w.x + c.w.w > c.sw || c.w.y + c.w.h > c.sh || c.w.ox + c.tw > c.w.vw || c.w.oy + c.th > c.w.vh || c.w.w > 16 * c.w.vw || c.w.h > 16 * c.w.vh) {
+            printf("case %zu is not a valid window\n", i); return 1;
+        }
+        wins[i] = c.w;
+        r.src_off = spos; r.sw = c.sw; r.sh = c.sh; r.src_stride = PLANAR ? c.sw : 3 * c.sw; r.tw = c.tw; r.th = c.th;
+        r.col_tiles = (c.tw + PJD_RS_COLS - 1) / PJD_RS_COLS; r.dst_off = dpos;
+        doff[i] = dpos;
+        spos += 3ull * c.sw * c.sh;                        // back to back: a picture's neighbours are other pictures
+        dpos += 3ull * c.tw * c.th * ES + ES * (2 * (i % 3) + 1);                     // element-aligned odd gaps
+        prefix[i] = t; t += r.col_tiles * ((c.th + PJD_RS_ROWS - 1) / PJD_RS_ROWS);
+        if (AA) {
+            aas[i].x_tab = axis_table(tab, c.w.w, c.w.vw, aas[i].x_taps);
+            aas[i].y_tab = axis_table(tab, c.w.h, c.w.vh, aas[i].y_taps);
+            for (uint32_t c0 = 0; c0 < c.tw; c0 += PJD_RS_COLS) {                   // the sizing loop of pjd_batch_set_resize_filter
+                uint32_t e0, e1;
+                pjd_resize_win_ends(c.w, c.tw, c0, std::min<uint32_t>(c0 + PJD_RS_COLS, c.tw) - 1u, e0, e1);
+                const uint32_t h0 = tab[aas[i].x_tab + e0], h1 = tab[aas[i].x_tab + e1];
+                lds = std::max(lds, pjd_resize_aa_lds((h1 & 0xffffu) + (h1 >> 16) - (h0 & 0xffffu), PLANAR));
+            }
+        }
+    }
+    prefix[n] = t;
+    const size_t src_bytes = (spos + 3) & ~(size_t)3;        // whole dwords are staged: the buffer ends on one, as every allocation does
+    uint8_t *src = (uint8_t *)malloc(src_bytes);              // the sanitizer's view of the source is exactly src_bytes
+    for (size_t k = 0; k < src_bytes; k++) src[k] = (uint8_t)rand();
+    if (((uintptr_t)src & 3u) != 0) { printf("malloc gave an unaligned block\n"); return 1; }
+    uint8_t *dst = (uint8_t *)malloc(dpos + 256); memset(dst, 0xA5, dpos + 256);
+    NormArgs nz = {{0.01712475f, 0.017507f, -0.01742919f}, {-2.117904f, -2.0357144f, 1.8044444f}};
+    if (AA) {
+        for (uint32_t b = 0; b < t; b++) for (uint32_t th = 0; th < 64; th++) {
+            uint32_t *seg = (uint32_t *)malloc(lds ? lds : 4);                       // this thread's "LDS", of the launch's size
+            blockIdx.x = b; threadIdx.x = th;
+            thread_aa<PLANAR, DT>(seg, src, dst, recs.data(), wins.data(), prefix.data(), (uint32_t)n, t, aas.data(), tab.data(), lds, nz);
+            free(seg);
+        }
+    } else {
+        const uint32_t n_blocks = (t + PJD_RS_WAVES - 1) / PJD_RS_WAVES;
+        for (uint32_t b = 0; b < n_blocks; b++) for (uint32_t th = 0; th < 64 * PJD_RS_WAVES; th++) {
+            blockIdx.x = b; threadIdx.x = th;
+            thread_bilinear<PLANAR, DT>(src, dst, recs.data(), wins.data(), prefix.data(), (uint32_t)n, t, nz);
+        }
+    }
+    // the expectation: include/pjd.h, pixel by pixel
+    std::vector<uint8_t> want(dpos + 256, 0xA5);
+    for (size_t i = 0; i < n; i++) {
+        const Case &c = cases[i]; const PjdDevResizeWin &w = c.w; const uint8_t *sp = src + recs[i].src_off;
+        auto P = [&](int ch, uint32_t yy, uint32_t xx) -> uint32_t {
+            if (xx < w.x || xx >= w.x + w.w || yy < w.y || yy >= w.y + w.h) { printf("the expectation itself left the window\n"); exit(2); }
+            return PLANAR ? sp[(size_t)ch * c.sw * c.sh + (size_t)yy * c.sw + xx] : sp[((size_t)yy * c.sw + xx) * 3 + ch];
+        };
+        for (uint32_t y = 0; y < c.th; y++) for (uint32_t x = 0; x < c.tw; x++) for (int ch = 0; ch < 3; ch++) {
+            const uint32_t xi = w.ox + ((w.flags & PJD_RW_HFLIP) ? c.tw - 1 - x : x), yi = w.oy + y;
+            uint32_t v;
+            if (AA) {
+                uint32_t fx, fy, qx[PJD_AA_MAX_TAPS], qy[PJD_AA_MAX_TAPS];
+                const uint32_t nx = pjd_resize_aa_taps_calc(w.w, w.vw, xi, fx, qx), ny = pjd_resize_aa_taps_calc(w.h, w.vh, yi, fy, qy);
+                uint32_t acc = 0;
+                for (uint32_t b = 0; b < ny; b++) {
+                    uint32_t h = 0;
+                    for (uint32_t a = 0; a < nx; a++) h += qx[a] * P(ch, w.y + fy + b, w.x + fx + a);
+                    acc += qy[b] * ((h + 128u) >> 8);
+                }
+                v = (acc + (1u << 23)) >> 24;
+            } else {
+                uint32_t x0, x1, wx, y0, y1, wy;
+                pjd_resize_tap_calc(w.w, w.vw, xi, x0, x1, wx); pjd_resize_tap_calc(w.h, w.vh, yi, y0, y1, wy);
+                x0 += w.x; x1 += w.x; y0 += w.y; y1 += w.y;
+                v = ((256 - wy) * ((256 - wx) * P(ch, y0, x0) + wx * P(ch, y0, x1)) + wy * ((256 - wx) * P(ch, y1, x0) + wx * P(ch, y1, x1)) + 32768) >> 16;
+            }
+            const size_t e = PLANAR ? ((size_t)ch * c.th + y) * c.tw + x : ((size_t)y * c.tw + x) * 3 + ch;
+            uint8_t *o = want.data() + doff[i] + e * ES;
+            if (DT == 0) *o = (uint8_t)v;
+            else {
+                const float u = fmaf((float)v, nz.scale[ch], nz.bias[ch]);
+                if (DT == PJD_DT_F32) memcpy(o, &u, 4);
+                else if (DT == PJD_DT_F16) { const _Float16 h = (_Float16)u; memcpy(o, &h, 2); }
+                else { const __bf16 h = (__bf16)u; memcpy(o, &h, 2); }
+            }
+        }
+    }
+    int bad = 0;
+    for (size_t k = 0; k < dpos + 256; k++) if (dst[k] != want[k]) { if (bad < 4) printf("  mismatch at byte %zu got %02x want %02x\n", k, dst[k], want[k]); bad++; }
+    uint32_t rem = 0;
+    for (size_t i = 0; i < n; i++) rem |= 1u << ((recs[i].src_off + (PLANAR ? cases[i].w.x : 3 * cases[i].w.x) + (size_t)cases[i].w.y * recs[i].src_stride) & 3u);
+    printf("%s PLANAR=%d DT=%d misalign=%u: %zu pictures, %u tiles, lds %u, window remainders %x: %s\n", AA ? "antialias" : "bilinear ", (int)PLANAR, DT,
+           misalign_elems, n, t, lds, rem, bad ? "MISMATCH" : "equal, guards intact");
+    free(dst); free(src);
+    return bad != 0 || rem != 0xf;
+}
+
+template <bool AA>
+static int all()
+{
+    int rc = 0;
+    for (uint32_t mis : {0u, 1u, 2u, 3u}) {
+        rc |= run<true, 0, AA>(mis, 1); rc |= run<false, 0, AA>(mis, 2);
+        rc |= run<true, PJD_DT_F16, AA>(mis, 3); rc |= run<false, PJD_DT_F16, AA>(mis, 4);
+        rc |= run<true, PJD_DT_BF16, AA>(mis, 5); rc |= run<false, PJD_DT_BF16, AA>(mis, 6);
+        rc |= run<true, PJD_DT_F32, AA>(mis, 7); rc |= run<false, PJD_DT_F32, AA>(mis, 8);
+    }
+    return rc;
+}
+
+int main()
+{
+    const int rc = all<false>() | all<true>();
+    printf(rc ? "FAILED\n" : "ALL EQUAL\n");
+    return rc;
+}
