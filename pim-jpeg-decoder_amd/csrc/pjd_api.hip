@@ -213,14 +213,8 @@ struct pjd_batch {
     // after the fallback)
     void launch_resize(hipStream_t s, bool planar) const
     {
-        if (windowed)
-            pjd_launch_resize_win(s, dev.out, res_out, d_rs, d_win, d_rs_prefix, dev.n_images, rs_tiles, planar, norm, antialias, (const PjdDevResizeAA *)d_aa,
-                                  antialias ? (const uint32_t *)(d_aa + dev.n_images * sizeof(PjdDevResizeAA)) : nullptr, aa_lds);
-        else if (antialias)
-            pjd_launch_resize_aa(s, dev.out, res_out, d_rs, d_rs_prefix, dev.n_images, rs_tiles, planar, norm, (const PjdDevResizeAA *)d_aa,
-                                 (const uint32_t *)(d_aa + dev.n_images * sizeof(PjdDevResizeAA)), aa_lds);
-        else
-            pjd_launch_resize(s, dev.out, res_out, d_rs, d_rs_prefix, dev.n_images, rs_tiles, planar, norm);
+        pjd_launch_resize(s, PjdResizeLaunch{dev.out, res_out, d_rs, d_rs_prefix, dev.n_images, rs_tiles, planar, norm, windowed ? d_win : nullptr, antialias,
+                                             (const PjdDevResizeAA *)d_aa, antialias ? (const uint32_t *)(d_aa + dev.n_images * sizeof(PjdDevResizeAA)) : nullptr, aa_lds});
     }
 };
 
@@ -1057,8 +1051,7 @@ int pjd_batch_set_resize_filter(pjd_batch *b, int filter)
     for (size_t i = 0; i < n; i++) {
         const PjdDevResize &r = b->h_rs[i];
         // a windowed picture takes the tables of its windowed axes, over the whole virtual target (tap index ox + i', row length vw)
-        PjdDevResizeWin w{0, 0, r.sw, r.sh, r.tw, r.th, 0, 0, 0, 0};
-        if (b->windowed) w = b->h_win[i];
+        const PjdDevResizeWin w = b->windowed ? b->h_win[i] : pjd_resize_win_identity(r);
         if (tab.size() + ((size_t)w.vw + w.vh) * (1u + PJD_AA_MAX_TAPS) >= (1ull << 31)) { ctx->err = "set_resize_filter: the weight table of this batch is too large"; return PJD_E_ARG; }
         const Axis x = axis(w.w, w.vw), y = axis(w.h, w.vh);
         recs[i] = PjdDevResizeAA{x.off, x.taps, y.off, y.taps};

@@ -418,7 +418,7 @@ static inline __host__ __device__ uint32_t pjd_resize_aa_taps_calc(uint32_t sn, 
     return n;
 }
 
-// What the antialiased launch (pjd_k_resize_aa.hip) reads beside the work list of the bilinear one: per picture, where the tables of
+// What the antialiased launch (pjd_k_resize_aa_body.h) reads beside the work list of the bilinear one: per picture, where the tables of
 // its two axes start in the batch's weight table (in words) and how many taps a row of each holds.  The table of one axis (sn -> dn,
 // shared by every picture and axis with that pair): dn head words `first | count << 16`, then taps x dn weights, TAP-MAJOR
 // (weight t of target sample i at dn + t * dn + i; 0 from `count` on), so that the lanes of a wave read adjacent words.
@@ -431,7 +431,7 @@ struct PjdDevResizeAA {
 static inline __host__ __device__ uint32_t pjd_resize_aa_lds(uint32_t span, bool planar) { return planar ? 3u * ((span + 6u) & ~3u) : (3u * span + 6u) & ~3u; }
 
 // ---- source windows (pjd_batch_set_resize_window; the arithmetic is normative: include/pjd.h) -----------------------------------
-// What the windowed launches (pjd_k_resize_win.hip) read beside the work list: per picture the window with every default resolved
+// What the windowed launches (pjd_k_resize.hip, WIN) read beside the work list: per picture the window with every default resolved
 // (w, h >= 1; vw, vh >= 1; ox + tw <= vw, oy + th <= vh).  The taps of target column i are those of index ox + i' over (w, vw), i' = i
 // or tw - 1 - i with PJD_RW_HFLIP, and they address source columns from x on; rows likewise without the mirror.  PjdDevResize keeps
 // the whole picture (sh is the plane stride of a planar source) and the delivered target.  With the antialiased filter the tables
@@ -443,6 +443,13 @@ struct PjdDevResizeWin {
     uint32_t flags;                    // PJD_RW_HFLIP
     uint32_t pad_;
 };
+
+// the window of a picture that has none: all of it, to exactly its target.  A plain launch is the windowed one with this window (the
+// kernel bodies fold it away at compile time; the host sizes the LDS of a batch without windows with it)
+static inline __host__ __device__ PjdDevResizeWin pjd_resize_win_identity(const PjdDevResize &r)
+{
+    return PjdDevResizeWin{0, 0, r.sw, r.sh, r.tw, r.th, 0, 0, 0, 0};
+}
 
 // the tap indices of the two ends of a tile's columns [c0, c1] of a windowed picture, lowest first: the staged segment runs from the
 // first tap of `lo` to the last tap of `hi` (the host sizes the LDS with it, the kernel stages with it)

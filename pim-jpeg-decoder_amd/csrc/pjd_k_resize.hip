@@ -18,34 +18,34 @@
 // 8-byte (fp16 / bf16) or 16-byte (fp32) store planar, 24 or 48 bytes interleaved, where the address has that store's alignment and
 // the row has four pixels left; element stores otherwise (pjd_batch_bind_output promises element alignment, no more).  The six
 // constants are launch arguments: wave-uniform, they never pass through the per-picture record.
+//
+// The antialiased filter (pjd_batch_set_resize_filter, PJD_RESIZE_ANTIALIAS): the same launch -- the same tiles and prefix sum, a lane the
+// same four pixels of each row of its tile -- with the widened triangle filter include/pjd.h specifies bit for bit.  A workgroup is ONE
+// wave there: its barriers cost nothing.  An output sample has up to 32 x 32 taps, so nothing is gathered.  The filter is separable; a
+// wave STREAMS down the source rows its tile reads, and for each of them
+//   - stages the row's segment -- the source columns the tile's 256 target columns read -- in LDS with coalesced dword loads;
+//   - filters it horizontally, once per tile and not once per target row: per lane 4 pixels x 3 channels, the taps as byte reads from
+//     LDS (neighbouring lanes share most of them), the weights from the batch's table (tap-major: adjacent lanes, adjacent words;
+//     padded with weight 0 up to the axis' largest count, so the loop bound is uniform) -> twelve h16;
+//   - adds w * h16 to the accumulators of those of the tile's 8 target rows that have this source row among their taps -- a
+//     wave-uniform test, the weight a scalar load.  8 x 12 accumulators live in registers (no scratch).
+// Then the same epilogue.  The weights are made on the host (pjd_resize_aa_taps_calc, pjd_internal.h): no division here.
+//
+// Source windows (pjd_batch_set_resize_window): either filter from a WINDOW of the decoded picture to a window of a virtual target,
+// mirrored left-right where asked -- flip(resize(P[y:y+h, x:x+w], vw, vh)[oy:oy+th, ox:ox+tw]) of include/pjd.h.  No arithmetic of
+// its own: the taps are the same functions and tables with a shifted index, read from a per-picture record of its own
+// (PjdDevResizeWin) beside PjdDevResize.  Each filter is ONE body text (pjd_k_resize_body.h, pjd_k_resize_aa_body.h) with a
+// compile-time WIN: a batch without windows runs kernels built with the identity window, which are the kernels it ran before.
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "../../include/pjd.h"
 #include "pjd_kernels.h"
 
 namespace {
 
-// ((256 - w) * a + w * b): below 2^16; the products and sums of the second stage stay below 2^24 (include/pjd.h)
-__device__ __forceinline__ uint32_t lerp8(uint32_t a, uint32_t b, uint32_t w) { return __umul24(256u - w, a) + __umul24(w, b); }
-
-// the constants of a normalised launch, by value in the kernel arguments (scalar registers)
-struct NormArgs { float scale[3], bias[3]; };
-
-// native vectors: one store of the vector's size and alignment (HIP's float4 / uint2 are structs that copy member by member)
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-// two adjacent samples of one channel -> two 16-bit elements in a dword: fma in binary32, then ONE rounding to the 16-bit type
-template <int DT>
-__device__ __forceinline__ uint32_t norm_pair16(uint32_t v0, uint32_t v1, float scale, float bias)
-{
-    const f32x2 u = {pjd_normalize_f32(v0, scale, bias), pjd_normalize_f32(v1, scale, bias)};
-    if (DT == PJD_DT_F16) return __builtin_bit_cast(uint32_t, __builtin_convertvector(u, f16x2));
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(u, bf16x2));
-}
+#include "pjd_k_resize_store.h"
 
 template <bool PLANAR>
 __global__ void __launch_bounds__(64 * PJD_RS_WAVES)
@@ -53,6 +53,8 @@ pjd_k_resize(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, const P
              const uint32_t *__restrict__ tile_prefix, uint32_t n_images, uint32_t n_tiles)
 {
     constexpr int DT = 0;
+    constexpr bool WIN = false;
+    const PjdDevResizeWin *const win = nullptr;
     const NormArgs nz{};
 #include "pjd_k_resize_body.h"
 }
@@ -62,28 +64,80 @@ __global__ void __launch_bounds__(64 * PJD_RS_WAVES)
 pjd_k_resize_norm(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, const PjdDevResize *__restrict__ recs,
                   const uint32_t *__restrict__ tile_prefix, uint32_t n_images, uint32_t n_tiles, const NormArgs nz)
 {
+    constexpr bool WIN = false;
+    const PjdDevResizeWin *const win = nullptr;
 #include "pjd_k_resize_body.h"
+}
+
+template <bool PLANAR, int DT>
+__global__ void __launch_bounds__(64 * PJD_RS_WAVES)
+pjd_k_resize_win(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, const PjdDevResize *__restrict__ recs,
+                 const PjdDevResizeWin *__restrict__ win, const uint32_t *__restrict__ tile_prefix, uint32_t n_images, uint32_t n_tiles,
+                 const NormArgs nz)
+{
+    constexpr bool WIN = true;
+#include "pjd_k_resize_body.h"
+}
+
+template <bool PLANAR, int DT>
+__global__ void __launch_bounds__(64)
+pjd_k_resize_aa(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, const PjdDevResize *__restrict__ recs,
+                const uint32_t *__restrict__ tile_prefix, uint32_t n_images, uint32_t n_tiles, const PjdDevResizeAA *__restrict__ aa,
+                const uint32_t *__restrict__ tab, uint32_t lds_bytes, const NormArgs nz)
+{
+    extern __shared__ uint32_t seg[];                      // one source row's segment (three plane segments where PLANAR)
+    constexpr bool WIN = false;
+    const PjdDevResizeWin *const win = nullptr;
+#include "pjd_k_resize_aa_body.h"
+}
+
+template <bool PLANAR, int DT>
+__global__ void __launch_bounds__(64)
+pjd_k_resize_win_aa(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, const PjdDevResize *__restrict__ recs,
+                    const PjdDevResizeWin *__restrict__ win, const uint32_t *__restrict__ tile_prefix, uint32_t n_images, uint32_t n_tiles,
+                    const PjdDevResizeAA *__restrict__ aa, const uint32_t *__restrict__ tab, uint32_t lds_bytes, const NormArgs nz)
+{
+    extern __shared__ uint32_t seg[];
+    constexpr bool WIN = true;
+#include "pjd_k_resize_aa_body.h"
+}
+
+// f(planar, dtype) with both as compile-time constants: THE dtype x layout dispatch of the resample launch
+template <class F>
+void for_layout_and_dtype(bool planar, int dtype, F f)
+{
+    const auto with_layout = [&](auto P) {
+        switch (dtype) {
+        case 0:           f(P, std::integral_constant<int, 0>{});           break;
+        case PJD_DT_F16:  f(P, std::integral_constant<int, PJD_DT_F16>{});  break;
+        case PJD_DT_BF16: f(P, std::integral_constant<int, PJD_DT_BF16>{}); break;
+        default:          f(P, std::integral_constant<int, PJD_DT_F32>{});  break;
+        }
+    };
+    if (planar) with_layout(std::true_type{}); else with_layout(std::false_type{});
 }
 
 }  // namespace
 
-void pjd_launch_resize(hipStream_t s, const uint8_t *src, uint8_t *dst, const PjdDevResize *recs, const uint32_t *tile_prefix, uint32_t n_images,
-                       uint32_t n_tiles, bool planar, const PjdNormalize &norm)
+void pjd_launch_resize(hipStream_t s, const PjdResizeLaunch &a)
 {
-    if (n_tiles == 0) return;
-    const dim3 grid((n_tiles + PJD_RS_WAVES - 1) / PJD_RS_WAVES), block(64 * PJD_RS_WAVES);
-    if (norm.dtype == 0) {
-        if (planar) hipLaunchKernelGGL(pjd_k_resize<true>, grid, block, 0, s, src, dst, recs, tile_prefix, n_images, n_tiles);
-        else hipLaunchKernelGGL(pjd_k_resize<false>, grid, block, 0, s, src, dst, recs, tile_prefix, n_images, n_tiles);
-        return;
-    }
-    NormArgs nz;
-    for (int c = 0; c < 3; c++) { nz.scale[c] = norm.scale[c]; nz.bias[c] = norm.bias[c]; }
-#define PJD_RS_NORM(P, D) hipLaunchKernelGGL((pjd_k_resize_norm<P, D>), grid, block, 0, s, src, dst, recs, tile_prefix, n_images, n_tiles, nz)
-    switch (norm.dtype) {
-    case PJD_DT_F16:  if (planar) PJD_RS_NORM(true, PJD_DT_F16);  else PJD_RS_NORM(false, PJD_DT_F16);  break;
-    case PJD_DT_BF16: if (planar) PJD_RS_NORM(true, PJD_DT_BF16); else PJD_RS_NORM(false, PJD_DT_BF16); break;
-    default:          if (planar) PJD_RS_NORM(true, PJD_DT_F32);  else PJD_RS_NORM(false, PJD_DT_F32);  break;
-    }
-#undef PJD_RS_NORM
+    if (a.n_tiles == 0) return;
+    NormArgs nz{};
+    for (int c = 0; c < 3; c++) { nz.scale[c] = a.norm.scale[c]; nz.bias[c] = a.norm.bias[c]; }
+    // bilinear: PJD_RS_WAVES tiles per workgroup, no LDS; antialiased: a workgroup is one wave with its row segment in LDS
+    const dim3 grid(a.antialias ? a.n_tiles : (a.n_tiles + PJD_RS_WAVES - 1) / PJD_RS_WAVES), block(a.antialias ? 64 : 64 * PJD_RS_WAVES);
+    for_layout_and_dtype(a.planar, a.norm.dtype, [&](auto P, auto D) {
+        constexpr bool PL = decltype(P)::value;
+        constexpr int DT = decltype(D)::value;
+        if (a.antialias && a.win)
+            hipLaunchKernelGGL((pjd_k_resize_win_aa<PL, DT>), grid, block, a.lds_bytes, s, a.src, a.dst, a.recs, a.win, a.tile_prefix, a.n_images, a.n_tiles, a.aa, a.tab, a.lds_bytes, nz);
+        else if (a.antialias)
+            hipLaunchKernelGGL((pjd_k_resize_aa<PL, DT>), grid, block, a.lds_bytes, s, a.src, a.dst, a.recs, a.tile_prefix, a.n_images, a.n_tiles, a.aa, a.tab, a.lds_bytes, nz);
+        else if (a.win)
+            hipLaunchKernelGGL((pjd_k_resize_win<PL, DT>), grid, block, 0, s, a.src, a.dst, a.recs, a.win, a.tile_prefix, a.n_images, a.n_tiles, nz);
+        else if constexpr (DT == 0)
+            hipLaunchKernelGGL(pjd_k_resize<PL>, grid, block, 0, s, a.src, a.dst, a.recs, a.tile_prefix, a.n_images, a.n_tiles);
+        else
+            hipLaunchKernelGGL((pjd_k_resize_norm<PL, DT>), grid, block, 0, s, a.src, a.dst, a.recs, a.tile_prefix, a.n_images, a.n_tiles, nz);
+    });
 }

@@ -1,15 +1,19 @@
-// pjd_k_resize_win_aa_body.h -- the body of the windowed antialiased kernel pjd_k_resize_win_aa<PLANAR, DT> of pjd_k_resize_win.hip: the
-// streaming kernel of pjd_k_resize_aa.hip (a wave stages one source row segment in LDS, filters it horizontally once per tile and
-// adds it to the accumulators of the target rows that read it), with the taps of a source WINDOW (include/pjd.h):
+// pjd_k_resize_aa_body.h -- the body of the antialiased resample kernels of pjd_k_resize.hip, included once per kernel:
+// pjd_k_resize_aa<PLANAR, DT> and, with WIN, pjd_k_resize_win_aa<PLANAR, DT> (pjd_batch_set_resize_window).  A wave STREAMS down the
+// source rows its tile reads (pjd_k_resize.hip says how).  The taps are those of a source WINDOW (include/pjd.h), which without WIN
+// is the identity window (pjd_resize_win_identity) and folds away:
 //   - the tables are those of the axes (w.w, w.vw) and (w.h, w.vh); a column's entries are at index w.ox + i', i' the lane's column or
 //     its mirror image (PJD_RW_HFLIP), a row's at w.oy + row; the tap-major rows are w.vw and w.vh long;
 //   - `first` grows with the tap index, so a mirrored tile has its lowest taps at its LAST column: the staged segment runs from the
 //     first tap of the lower end to the last tap of the higher one (pjd_resize_win_ends, which also sizes the LDS on the host);
-//   - the segment starts at column w.x + xs of row w.y + y: any dword remainder occurs, whatever the picture's own alignment;
+//   - the segment starts at column w.x + xs of row w.y + y: any dword remainder occurs, whatever the picture's own alignment (the
+//     dword that holds its first byte is the first one loaded, and the taps read behind the remainder `sh`);
 //   - the guards are the window's: a table that would reach past w.w makes the tile return, rows end at w.h.
-// A textual include, so that tools/resize_window_host.cpp runs this very text on the host; PJD_WIN_STAGE_FIRST / _STEP say which
-// dwords of a segment this thread stages (its own of the wave's 64 here; all of them where a thread runs alone).
-// In scope: PLANAR, DT, seg (LDS), src, dst, recs, win, tile_prefix, n_images, n_tiles, aa, tab, lds_bytes, nz; store_row.
+// No lane leaves before the last barrier; lanes right of the picture compute its last column and store nothing.
+// A textual include, so that tools/resize_host.cpp runs this very text on the host; PJD_WIN_STAGE_FIRST / _STEP say which dwords of a
+// segment this thread stages (its own of the wave's 64 here; all of them where a thread runs alone).
+// In scope: PLANAR, DT, WIN (compile-time constants), seg (LDS), src, dst, recs, win (read only where WIN), tile_prefix, n_images,
+// n_tiles, aa, tab, lds_bytes, nz; store_row.
 #ifndef PJD_WIN_STAGE_FIRST
 #define PJD_WIN_STAGE_FIRST lane
 #define PJD_WIN_STAGE_STEP  64u
@@ -23,7 +27,7 @@
         if (tile_prefix[mid] <= tile) lo = mid; else hi = mid;
     }
     const PjdDevResize r = recs[lo];
-    const PjdDevResizeWin w = win[lo];
+    const PjdDevResizeWin w = WIN ? win[lo] : pjd_resize_win_identity(r);
     const PjdDevResizeAA a = aa[lo];
     const uint32_t t = tile - tile_prefix[lo];
     const uint32_t row0 = (t / r.col_tiles) * PJD_RS_ROWS;

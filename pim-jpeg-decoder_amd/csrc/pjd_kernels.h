@@ -67,20 +67,27 @@ void pjd_launch_group_idct(hipStream_t s, const PjdDevBatch &b, const PjdDevGrou
 void pjd_launch_idct_pull(hipStream_t s, const PjdDevBatch &b);
 void pjd_launch_idct_sweep(hipStream_t s, const PjdDevBatch &b);
 // ---- resize on decode (pjd_k_resize.hip): every picture of the batch from `src` (interleaved RGB8, or planar) to its target size in `dst`
-// (the same layout), one launch; tile_prefix[i] = tiles of the pictures before i, tile_prefix[n_images] = n_tiles.  norm.dtype != 0: the
-// samples leave as fp16 / bf16 / fp32 elements, v * scale[c] + bias[c] (pjd_batch_set_normalize); the records' dst_off stay byte offsets
-void pjd_launch_resize(hipStream_t s, const uint8_t *src, uint8_t *dst, const PjdDevResize *recs, const uint32_t *tile_prefix, uint32_t n_images,
-                       uint32_t n_tiles, bool planar, const PjdNormalize &norm);
-// ---- antialiased resize (pjd_k_resize_aa.hip): the same launch with the widened triangle filter (pjd_batch_set_resize_filter).  aa[i]
-// says where picture i's weights lie in `tab` (pjd_internal.h); lds_bytes is the largest row segment a tile of the batch stages.
-void pjd_launch_resize_aa(hipStream_t s, const uint8_t *src, uint8_t *dst, const PjdDevResize *recs, const uint32_t *tile_prefix, uint32_t n_images,
-                          uint32_t n_tiles, bool planar, const PjdNormalize &norm, const PjdDevResizeAA *aa, const uint32_t *tab, uint32_t lds_bytes);
-// ---- windowed resize (pjd_k_resize_win.hip): either filter of the two launches above where the batch has source windows
-// (pjd_batch_set_resize_window).  win[i] is picture i's window, defaults resolved; aa / tab / lds_bytes as above where `antialias`
-// (the tables are those of the windowed axes, lds_bytes covers the segments of mirrored tiles), unused otherwise.
-void pjd_launch_resize_win(hipStream_t s, const uint8_t *src, uint8_t *dst, const PjdDevResize *recs, const PjdDevResizeWin *win,
-                           const uint32_t *tile_prefix, uint32_t n_images, uint32_t n_tiles, bool planar, const PjdNormalize &norm, bool antialias,
-                           const PjdDevResizeAA *aa, const uint32_t *tab, uint32_t lds_bytes);
+// (the same layout), one launch whatever the batch asked for; tile_prefix[i] = tiles of the pictures before i, tile_prefix[n_images] =
+// n_tiles.  norm.dtype != 0: the samples leave as fp16 / bf16 / fp32 elements, v * scale[c] + bias[c] (pjd_batch_set_normalize); the
+// records' dst_off stay byte offsets.  win: null, or win[i] is picture i's source window, defaults resolved
+// (pjd_batch_set_resize_window).  antialias: the widened triangle filter (pjd_batch_set_resize_filter); aa[i] then says where picture
+// i's weights lie in `tab` (pjd_internal.h; the tables of the windowed axes where win), and lds_bytes is the largest row segment a tile
+// of the batch stages (mirrored tiles included); all three unused otherwise.
+struct PjdResizeLaunch {
+    const uint8_t *src;
+    uint8_t *dst;
+    const PjdDevResize *recs;
+    const uint32_t *tile_prefix;
+    uint32_t n_images, n_tiles;
+    bool planar;
+    PjdNormalize norm;
+    const PjdDevResizeWin *win;
+    bool antialias;
+    const PjdDevResizeAA *aa;
+    const uint32_t *tab;
+    uint32_t lds_bytes;
+};
+void pjd_launch_resize(hipStream_t s, const PjdResizeLaunch &a);
 // ---- stage-level parity (pjd_k_coefdump.hip): coefficients in the reference's MCU_buffer layout; `out` is zeroed by the caller
 void pjd_launch_coefdump_lanes(hipStream_t s, const PjdDevBatch &b, uint32_t image, uint32_t n_iwg, int16_t *out);
 void pjd_launch_coefdump_dense(hipStream_t s, const PjdDevBatch &b, uint32_t image, const int16_t *scratch, uint32_t first_du, uint32_t n_du, int16_t *out);

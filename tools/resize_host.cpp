@@ -1,24 +1,31 @@
-// resize_window_host.cpp -- the bodies of the windowed resample kernels (pim-jpeg-decoder_amd/csrc/pjd_k_resize_win_body.h and
-// pjd_k_resize_win_aa_body.h, with the stores of pjd_k_resize_store.h) run on the host, thread by thread, under the sanitizers:
-// window and offset indexing, the mirrored tap index, the staged segment of a mirrored tile, all four dword remainders of a segment's
-// first byte in both layouts, the plane stride of a planar source whose window is lower than the picture, guard bytes.
+// resize_host.cpp -- the bodies of the resample kernels (pim-jpeg-decoder_amd/csrc/pjd_k_resize_body.h and pjd_k_resize_aa_body.h, with
+// the stores of pjd_k_resize_store.h) run on the host, thread by thread, under the sanitizers, each with WIN false and true: indexing,
+// tile search, the vector and the element store paths at every alignment, window and offset indexing, the mirrored tap index, the
+// staged segment of a mirrored tile, all four dword remainders of a segment's first byte in both layouts, the plane stride of a planar
+// source whose window is lower than the picture, guard bytes.
 //
-//     clang++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize=alignment -o resize_window_host tools/resize_window_host.cpp \
-//         && ./resize_window_host
+//     clang++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize=alignment -o resize_host tools/resize_host.cpp && ./resize_host
 //
 // Device builtins are replaced by host stand-ins: a lane's row taps are computed directly instead of being read from lane k, a
 // barrier is nothing, and a thread stages the whole row segment for itself (PJD_WIN_STAGE_*) into an "LDS" of exactly the size the
-// host would give the launch, allocated per thread so that AddressSanitizer sees its end.  The 16-bit conversions are the host
-// compiler's, so this says nothing about the GPU's (tests/test_gpu_normalize.py does).  The source holds every picture back to back
-// with NO padding between them beyond what rounds the buffer to a dword (the kernels stage whole dwords): a read outside a window
-// that mattered would change the result, a read outside the buffer is a sanitizer report.  The expectation is a plain per-pixel
-// loop over the arithmetic of include/pjd.h -- the tap inlines with a shifted index.  Prints ALL EQUAL.
+// host would give the launch, allocated per thread so that AddressSanitizer sees its end.  The 16-bit conversions of the bodies are
+// the host compiler's, so this says nothing about the GPU's (tests/test_gpu_normalize.py does); the expectation makes them bit by bit.
+// Every variant (uint8 / fp16 / bf16 / fp32, planar / interleaved, bilinear / antialiased) writes two sets of pictures, each into one
+// buffer at element-aligned offsets with odd gaps, the buffer itself shifted by 0..3 elements:
+//   - plain: 31 pictures (tile edges, ragged right edges, random sizes; the antialiased body skips those that shrink more than 16x)
+//     through the WIN = false body, and again through the WIN = true body with the identity window: the same bytes;
+//   - windowed: 12 geometries (those of tests/test_gpu_resize_window.py and the four remainders of x) and 10 seeded windows.
+// The source holds every picture back to back with NO padding between them beyond what rounds the buffer to a dword (the kernels
+// stage whole dwords): a read outside a window that mattered would change the result, a read outside the buffer is a sanitizer
+// report.  The expectation is a plain per-pixel loop over the arithmetic of include/pjd.h -- the tap inlines with a shifted index;
+// the bytes between the pictures are compared too.  Prints ALL EQUAL.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 #define __host__
 #define __device__
@@ -29,7 +36,6 @@
 struct Dim { uint32_t x; };
 static thread_local Dim threadIdx, blockIdx;
 static inline uint32_t __umul24(uint32_t a, uint32_t b) { return (a & 0xffffff) * (b & 0xffffff); }
-static inline uint32_t lerp8(uint32_t a, uint32_t b, uint32_t w) { return __umul24(256u - w, a) + __umul24(w, b); }
 static inline void __syncthreads() {}
 #include "../pim-jpeg-decoder_amd/csrc/pjd_k_resize_store.h"
 #define __builtin_amdgcn_readfirstlane(x) (x)
@@ -38,19 +44,42 @@ static inline uint32_t emu_tap(uint32_t sn, uint32_t dn, uint32_t i) { uint32_t 
 #define PJD_WIN_STAGE_FIRST 0u
 #define PJD_WIN_STAGE_STEP  1u
 
-template <bool PLANAR, int DT>
+template <bool PLANAR, int DT, bool WIN>
 static void thread_bilinear(const uint8_t *src, uint8_t *dst, const PjdDevResize *recs, const PjdDevResizeWin *win, const uint32_t *tile_prefix,
                             uint32_t n_images, uint32_t n_tiles, const NormArgs nz)
 {
-#include "../pim-jpeg-decoder_amd/csrc/pjd_k_resize_win_body.h"
+#include "../pim-jpeg-decoder_amd/csrc/pjd_k_resize_body.h"
 }
 
-template <bool PLANAR, int DT>
+template <bool PLANAR, int DT, bool WIN>
 static void thread_aa(uint32_t *seg, const uint8_t *src, uint8_t *dst, const PjdDevResize *recs, const PjdDevResizeWin *win, const uint32_t *tile_prefix,
                       uint32_t n_images, uint32_t n_tiles, const PjdDevResizeAA *aa, const uint32_t *tab, uint32_t lds_bytes, const NormArgs nz)
 {
-#include "../pim-jpeg-decoder_amd/csrc/pjd_k_resize_win_aa_body.h"
+#include "../pim-jpeg-decoder_amd/csrc/pjd_k_resize_aa_body.h"
 }
+
+// the expectation's own conversions to binary16 and bfloat16, round to nearest even
+static uint16_t f16bits(float f)
+{
+    uint32_t x; memcpy(&x, &f, 4);
+    const uint32_t sign = (x >> 16) & 0x8000u, a = x & 0x7fffffffu;
+    if (a >= 0x7f800000u) return (uint16_t)(sign | (a > 0x7f800000u ? 0x7e00u : 0x7c00u));
+    if (a < 0x38800000u) {
+        const uint32_t e = a >> 23;
+        if (e < 102u) return (uint16_t)sign;
+        const uint32_t m = (a & 0x7fffffu) | 0x800000u, shift = 126u - e;
+        uint32_t q = m >> shift;
+        const uint32_t rem = m & ((1u << shift) - 1u), half = 1u << (shift - 1u);
+        if (rem > half || (rem == half && (q & 1u))) q++;
+        return (uint16_t)(sign | q);
+    }
+    const uint32_t r = a - 0x38000000u;
+    uint32_t q = r >> 13; const uint32_t rem = r & 0x1fffu;
+    if (rem > 0x1000u || (rem == 0x1000u && (q & 1u))) q++;
+    if (q > 0x7c00u) q = 0x7c00u;
+    return (uint16_t)(sign | q);
+}
+static uint16_t bf16bits(float f) { uint32_t b; memcpy(&b, &f, 4); b += 0x7fffu + ((b >> 16) & 1u); return (uint16_t)(b >> 16); }
 
 struct Case { uint32_t sw, sh, tw, th; PjdDevResizeWin w; };
 
@@ -72,10 +101,21 @@ static uint32_t axis_table(std::vector<uint32_t> &tab, uint32_t sn, uint32_t dn,
     return (uint32_t)base;
 }
 
-template <bool PLANAR, int DT, bool AA>
-static int run(uint32_t misalign_elems, unsigned seed)
+static std::vector<Case> plain_cases(unsigned seed, bool aa)
 {
-    const uint32_t ES = DT == 0 ? 1 : PJD_DT_SIZE(DT);
+    std::vector<Case> all = {{61,45,1,1},{61,45,5,9},{88,56,256,8},{88,56,257,9},{80,96,259,3},{33,70,7,17},{61,45,61,45},{88,56,88,56},{17,9,300,2},{1,1,9,9},{300,1,3,5}}, out;
+    srand(seed);
+    for (int k = 0; k < 20; k++) all.push_back({(uint32_t)(1 + rand() % 120), (uint32_t)(1 + rand() % 120), (uint32_t)(1 + rand() % 300), (uint32_t)(1 + rand() % 300)});
+    for (Case &c : all) {
+        PjdDevResize r{}; r.sw = c.sw; r.sh = c.sh; r.tw = c.tw; r.th = c.th;
+        c.w = pjd_resize_win_identity(r);
+        if (!aa || (c.sw <= 16 * c.tw && c.sh <= 16 * c.th)) out.push_back(c);
+    }
+    return out;
+}
+
+static std::vector<Case> window_cases(unsigned seed)
+{
     // x, y, w, h, vw, vh, ox, oy, flags: the geometry of tests/test_gpu_resize_window.py and the four remainders of x
     std::vector<Case> cases = {
         {600, 40, 259, 5, {1, 2, 597, 35, 259, 5, 0, 0, 0, 0}}, {600, 40, 259, 5, {2, 2, 597, 35, 259, 5, 0, 0, 1, 0}},
@@ -96,13 +136,21 @@ static int run(uint32_t misalign_elems, unsigned seed)
         c.w.flags = rand() & 1; c.w.pad_ = 0;
         cases.push_back(c);
     }
+    return cases;
+}
+
+template <bool PLANAR, int DT, bool AA>
+static int run(bool windowed, uint32_t misalign_elems, unsigned seed)
+{
+    const uint32_t ES = DT == 0 ? 1 : PJD_DT_SIZE(DT);
+    const std::vector<Case> cases = windowed ? window_cases(seed) : plain_cases(seed, AA);
     const size_t n = cases.size();
     std::vector<PjdDevResize> recs(n); std::vector<PjdDevResizeWin> wins(n); std::vector<PjdDevResizeAA> aas(n); std::vector<uint32_t> prefix(n + 1), tab;
     size_t spos = 0, dpos = misalign_elems * ES; uint32_t t = 0, lds = 0;
     std::vector<size_t> doff(n);
     for (size_t i = 0; i < n; i++) {
         const Case &c = cases[i]; PjdDevResize &r = recs[i];
-        if (c.sw > 65535 || c.w.x + c.w.w > c.sw || c.w.y + c.w.h > c.sh || c.w.ox + c.tw > c.w.vw || c.w.oy + c.th > c.w.vh || c.w.w > 16 * c.w.vw || c.w.h > 16 * c.w.vh) {
+        if (c.sw > 65535 || c.w.x + c.w.w > c.sw || c.w.y + c.w.h > c.sh || c.w.ox + c.tw > c.w.vw || c.w.oy + c.th > c.w.vh || (AA && (c.w.w > 16 * c.w.vw || c.w.h > 16 * c.w.vh))) {
             printf("case %zu is not a valid window\n", i); return 1;
         }
         wins[i] = c.w;
@@ -128,24 +176,34 @@ static int run(uint32_t misalign_elems, unsigned seed)
     uint8_t *src = (uint8_t *)malloc(src_bytes);              // the sanitizer's view of the source is exactly src_bytes
     for (size_t k = 0; k < src_bytes; k++) src[k] = (uint8_t)rand();
     if (((uintptr_t)src & 3u) != 0) { printf("malloc gave an unaligned block\n"); return 1; }
-    uint8_t *dst = (uint8_t *)malloc(dpos + 256); memset(dst, 0xA5, dpos + 256);
-    NormArgs nz = {{0.01712475f, 0.017507f, -0.01742919f}, {-2.117904f, -2.0357144f, 1.8044444f}};
-    if (AA) {
-        for (uint32_t b = 0; b < t; b++) for (uint32_t th = 0; th < 64; th++) {
-            uint32_t *seg = (uint32_t *)malloc(lds ? lds : 4);                       // this thread's "LDS", of the launch's size
+    const size_t dst_bytes = dpos + 256;
+    const NormArgs nz = {{0.01712475f, 0.017507f, -0.01742919f}, {-2.117904f, -2.0357144f, 1.8044444f}};
+    // every thread of the launch, with the WIN = true or the WIN = false body
+    auto launch = [&](auto WIN) {
+        constexpr bool W = decltype(WIN)::value;
+        uint8_t *dst = (uint8_t *)aligned_alloc(256, (dst_bytes + 255) & ~(size_t)255); memset(dst, 0xA5, dst_bytes);
+        const uint32_t n_threads = AA ? 64 : 64 * PJD_RS_WAVES, n_blocks = AA ? t : (t + PJD_RS_WAVES - 1) / PJD_RS_WAVES;
+        for (uint32_t b = 0; b < n_blocks; b++) for (uint32_t th = 0; th < n_threads; th++) {
             blockIdx.x = b; threadIdx.x = th;
-            thread_aa<PLANAR, DT>(seg, src, dst, recs.data(), wins.data(), prefix.data(), (uint32_t)n, t, aas.data(), tab.data(), lds, nz);
-            free(seg);
+            if constexpr (AA) {
+                uint32_t *seg = (uint32_t *)malloc(lds ? lds : 4);                   // this thread's "LDS", of the launch's size
+                thread_aa<PLANAR, DT, W>(seg, src, dst, recs.data(), W ? wins.data() : nullptr, prefix.data(), (uint32_t)n, t, aas.data(), tab.data(), lds, nz);
+                free(seg);
+            } else {
+                thread_bilinear<PLANAR, DT, W>(src, dst, recs.data(), W ? wins.data() : nullptr, prefix.data(), (uint32_t)n, t, nz);
+            }
         }
-    } else {
-        const uint32_t n_blocks = (t + PJD_RS_WAVES - 1) / PJD_RS_WAVES;
-        for (uint32_t b = 0; b < n_blocks; b++) for (uint32_t th = 0; th < 64 * PJD_RS_WAVES; th++) {
-            blockIdx.x = b; threadIdx.x = th;
-            thread_bilinear<PLANAR, DT>(src, dst, recs.data(), wins.data(), prefix.data(), (uint32_t)n, t, nz);
-        }
+        return dst;
+    };
+    uint8_t *dst = windowed ? launch(std::true_type{}) : launch(std::false_type{});
+    int bad = 0;
+    if (!windowed) {                                         // the identity window through the WIN = true body: the same bytes
+        uint8_t *again = launch(std::true_type{});
+        if (memcmp(dst, again, dst_bytes) != 0) { printf("  the identity window through the WIN body gives other bytes\n"); bad++; }
+        free(again);
     }
     // the expectation: include/pjd.h, pixel by pixel
-    std::vector<uint8_t> want(dpos + 256, 0xA5);
+    std::vector<uint8_t> want(dst_bytes, 0xA5);
     for (size_t i = 0; i < n; i++) {
         const Case &c = cases[i]; const PjdDevResizeWin &w = c.w; const uint8_t *sp = src + recs[i].src_off;
         auto P = [&](int ch, uint32_t yy, uint32_t xx) -> uint32_t {
@@ -177,37 +235,35 @@ static int run(uint32_t misalign_elems, unsigned seed)
             else {
                 const float u = fmaf((float)v, nz.scale[ch], nz.bias[ch]);
                 if (DT == PJD_DT_F32) memcpy(o, &u, 4);
-                else if (DT == PJD_DT_F16) { const _Float16 h = (_Float16)u; memcpy(o, &h, 2); }
-                else { const __bf16 h = (__bf16)u; memcpy(o, &h, 2); }
+                else { const uint16_t h = DT == PJD_DT_F16 ? f16bits(u) : bf16bits(u); memcpy(o, &h, 2); }
             }
         }
     }
-    int bad = 0;
-    for (size_t k = 0; k < dpos + 256; k++) if (dst[k] != want[k]) { if (bad < 4) printf("  mismatch at byte %zu got %02x want %02x\n", k, dst[k], want[k]); bad++; }
-    uint32_t rem = 0;
+    for (size_t k = 0; k < dst_bytes; k++) if (dst[k] != want[k]) { if (bad < 4) printf("  mismatch at byte %zu got %02x want %02x\n", k, dst[k], want[k]); bad++; }
+    uint32_t rem = windowed ? 0u : 0xfu;                     // the windowed set has a segment at every dword remainder
     for (size_t i = 0; i < n; i++) rem |= 1u << ((recs[i].src_off + (PLANAR ? cases[i].w.x : 3 * cases[i].w.x) + (size_t)cases[i].w.y * recs[i].src_stride) & 3u);
-    printf("%s PLANAR=%d DT=%d misalign=%u: %zu pictures, %u tiles, lds %u, window remainders %x: %s\n", AA ? "antialias" : "bilinear ", (int)PLANAR, DT,
-           misalign_elems, n, t, lds, rem, bad ? "MISMATCH" : "equal, guards intact");
+    printf("%s %s PLANAR=%d DT=%d misalign=%u: %zu pictures, %u tiles, lds %u, remainders %x: %s\n", AA ? "antialias" : "bilinear ", windowed ? "windowed" : "plain   ",
+           (int)PLANAR, DT, misalign_elems, n, t, lds, rem, bad ? "MISMATCH" : "equal, guards intact");
     free(dst); free(src);
     return bad != 0 || rem != 0xf;
 }
 
 template <bool AA>
-static int all()
+static int all(bool windowed)
 {
     int rc = 0;
     for (uint32_t mis : {0u, 1u, 2u, 3u}) {
-        rc |= run<true, 0, AA>(mis, 1); rc |= run<false, 0, AA>(mis, 2);
-        rc |= run<true, PJD_DT_F16, AA>(mis, 3); rc |= run<false, PJD_DT_F16, AA>(mis, 4);
-        rc |= run<true, PJD_DT_BF16, AA>(mis, 5); rc |= run<false, PJD_DT_BF16, AA>(mis, 6);
-        rc |= run<true, PJD_DT_F32, AA>(mis, 7); rc |= run<false, PJD_DT_F32, AA>(mis, 8);
+        rc |= run<true, 0, AA>(windowed, mis, 1); rc |= run<false, 0, AA>(windowed, mis, 2);
+        rc |= run<true, PJD_DT_F16, AA>(windowed, mis, 3); rc |= run<false, PJD_DT_F16, AA>(windowed, mis, 4);
+        rc |= run<true, PJD_DT_BF16, AA>(windowed, mis, 5); rc |= run<false, PJD_DT_BF16, AA>(windowed, mis, 6);
+        rc |= run<true, PJD_DT_F32, AA>(windowed, mis, 7); rc |= run<false, PJD_DT_F32, AA>(windowed, mis, 8);
     }
     return rc;
 }
 
 int main()
 {
-    const int rc = all<false>() | all<true>();
+    const int rc = all<false>(false) | all<false>(true) | all<true>(false) | all<true>(true);
     printf(rc ? "FAILED\n" : "ALL EQUAL\n");
     return rc;
 }

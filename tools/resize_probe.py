@@ -4,7 +4,7 @@
 
 Prints one JSON line:
   kernel    per batch kind (prescale = pick_scale_flags, noprescale = full-size decode; planar and rgb8; planar bound to a torch
-            buffer) the median, minimum and maximum of every kernel's time from pjd_batch_decode_timed, the batches resident on one
+            buffer) the median, minimum, maximum and 10th / 90th percentile of every kernel's time from pjd_batch_decode_timed, the batches resident on one
             context and decoded in alternation; beside the `resize` kernel the bytes it has to move, computed from the shapes (the
             source footprint read once + the output written once), and what that is in GB/s
   e2e       the same tensor two ways, host clock around a device synchronise, from "upload done" to "tensor complete", alternating:
@@ -33,13 +33,14 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def stat(v):
-    return {"median_ms": round(statistics.median(v), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4)}
-
-
 def pct(v, p):
     v = sorted(v)
     return v[min(len(v) - 1, int(p * len(v)))]
+
+
+def stat(v):
+    return {"median_ms": round(statistics.median(v), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4),
+            "p10_ms": round(pct(v, 0.1), 4), "p90_ms": round(pct(v, 0.9), 4)}
 
 
 def random_resized_crop(rng, W, H):
