@@ -72,6 +72,7 @@ struct pjd_ctx {
     bool force_sequential = false;
     uint32_t sub_bytes_override = 0;
     int plan_mode = PJD_PLAN_LATENCY;     // pjd_set_plan_mode
+    int poison = -1;                      // PJD_DEBUG_POISON: 0..255, the byte every allocation made for this context is filled with; -1: off
     // picture groups: the chains of groups 1.. run on these, forked from / joined to `stream` (created on first use)
     std::vector<hipStream_t> group_streams;
     std::vector<hipEvent_t> join_ev;
@@ -100,6 +101,17 @@ std::atomic<int> g_active[64];
 std::mutex g_ctx_m;
 std::vector<pjd_ctx *> g_ctxs;
 
+// PJD_DEBUG_POISON (a diagnostic switch, off unless set): device memory obtained for this context -- a fresh allocation or a block of
+// the pool -- is filled with the byte on the context's stream before anything else touches it, page-locked memory with memset.  A
+// kernel that reads a word its decode has not written then reads the poison instead of the zeros of fresh memory or the valid words of
+// a destroyed batch (tests/test_gpu_poisoned_memory.py).  Never reached inside a stream capture: every allocation is
+// made before the upload or after the stream has drained.
+hipError_t poison_dev(pjd_ctx *ctx, void *p, size_t bytes)
+{
+    if (ctx->poison < 0 || !p || bytes == 0) return hipSuccess;
+    return hipMemsetAsync(p, ctx->poison, bytes, ctx->stream);
+}
+
 int pool_dev_alloc(pjd_ctx *ctx, void **out, size_t bytes, std::vector<PoolBlock> &owned)
 {
     if (bytes == 0) bytes = 16;
@@ -119,6 +131,7 @@ int pool_dev_alloc(pjd_ctx *ctx, void **out, size_t bytes, std::vector<PoolBlock
     }
     owned.push_back({p, got});
     *out = p;
+    if (poison_dev(ctx, p, got) != hipSuccess) { (void)hipGetLastError(); ctx->err = "PJD_DEBUG_POISON: hipMemsetAsync failed"; return PJD_E_HIP; }
     return PJD_OK;
 }
 
@@ -140,6 +153,7 @@ int pool_pin_alloc(pjd_ctx *ctx, void **out, size_t bytes, std::vector<PoolBlock
     }
     owned.push_back({p, got});
     *out = p;
+    if (ctx->poison >= 0) std::memset(p, ctx->poison, got);
     return PJD_OK;
 }
 
@@ -243,6 +257,11 @@ int pjd_open(int device_ordinal, pjd_ctx **out)
     if (pg) c->pool_cap = (size_t)std::atoll(pg) << 30;
     const char *sb = std::getenv("PJD_SUB_BYTES");
     c->sub_bytes_override = sb ? (uint32_t)std::atoi(sb) : 0;
+    if (const char *po = std::getenv("PJD_DEBUG_POISON")) {                  // a byte, decimal or 0x..; anything else leaves the switch off
+        char *end = nullptr;
+        const long v = std::strtol(po, &end, 0);
+        if (end != po && *end == 0 && v >= 0 && v <= 255) c->poison = (int)v;
+    }
     if (const char *pm = std::getenv("PJD_PLAN_MODE")) c->plan_mode = (pm[0] == 't' || pm[0] == '1') ? PJD_PLAN_THROUGHPUT : PJD_PLAN_LATENCY;
     { std::lock_guard<std::mutex> l(g_ctx_m); g_ctxs.push_back(c); }
     *out = c;
@@ -319,6 +338,13 @@ int pjd_batch_create(pjd_ctx *ctx, const pjd_image_desc *images, int n_images, i
     *out = nullptr;
     pjd_batch *b = new pjd_batch;
     b->ctx = ctx;
+    std::vector<pjd_image_desc> forced;
+    if (ctx->force_sequential && images && n_images > 0) {
+        // PJD_FORCE_SEQUENTIAL=1: every picture as if its descriptor carried PJD_F_FORCE_SEQUENTIAL (a shard cannot: it keeps its path)
+        forced.assign(images, images + n_images);
+        for (pjd_image_desc &d : forced) if (d.shard_n_segs == 0) d.flags |= PJD_F_FORCE_SEQUENTIAL;
+        images = forced.data();
+    }
     int rc = pjd_make_plan(images, n_images, out_format, b->plan, ctx->err, ctx->sub_bytes_override, ctx->plan_mode);
     if (rc != PJD_OK) { delete b; return rc; }
     PjdPlan &P = b->plan;
@@ -675,8 +701,12 @@ int settle(pjd_batch *b)
         }
         PjdDevBatch dv = b->dev;
         dv.coef = coef;
+        hipError_t e = poison_dev(ctx, coef, du * 64 * sizeof(int16_t));
+        if (e == hipSuccess) e = poison_dev(ctx, d_list, fb.size() * sizeof(uint32_t));
+        if (e == hipSuccess) e = poison_dev(ctx, d_base, fb.size() * sizeof(uint64_t));
+        if (e == hipSuccess) e = poison_dev(ctx, d_wgs, fb_wgs.size() * sizeof(PjdDevIdctWg));
         pjd_launch_zero(s, coef, du * 64 * sizeof(int16_t));      // our own kernel, as everywhere on the decode path
-        hipError_t e = hipGetLastError();
+        if (e == hipSuccess) e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpyAsync(d_list, fb.data(), fb.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s);
         if (e == hipSuccess) e = hipMemcpyAsync(d_base, fb_base.data(), fb_base.size() * sizeof(uint64_t), hipMemcpyHostToDevice, s);
         if (e == hipSuccess) e = hipMemcpyAsync(d_wgs, fb_wgs.data(), fb_wgs.size() * sizeof(PjdDevIdctWg), hipMemcpyHostToDevice, s);
@@ -1428,11 +1458,11 @@ int pjd_batch_download_coefficients(pjd_batch *b, int image, int16_t *out, uint6
     uint32_t *d_list = nullptr; uint64_t *d_base = nullptr;
     auto cleanup = [&] { hipFree(d_out); hipFree(scratch); hipFree(d_list); hipFree(d_base); };
     if (hipMalloc((void **)&d_out, n16 * sizeof(int16_t)) != hipSuccess) { ctx->err = "hipMalloc failed (coefficients)"; return PJD_E_NOMEM; }
+    hipError_t e = poison_dev(ctx, d_out, n16 * sizeof(int16_t));
     pjd_launch_zero(s, d_out, n16 * sizeof(int16_t));                  // 19200 int16 per DPU: a multiple of 16 bytes
     const uint32_t n_du = (g.last_mcu - g.first_mcu) * g.dus_per_mcu, first_du = g.first_mcu * g.dus_per_mcu;
     const bool routed = P.host[image].sequential;
     const bool fell_back = !routed && (b->h_status[image] & PJD_STW_NEEDS_EXACT);
-    hipError_t e = hipSuccess;
     if (routed) {
         pjd_launch_coefdump_dense(s, b->dev, (uint32_t)image, b->dev.coef + g.dense_base * 64, first_du, n_du, d_out);
     } else if (fell_back) {
@@ -1440,8 +1470,11 @@ int pjd_batch_download_coefficients(pjd_batch *b, int image, int16_t *out, uint6
         const uint32_t one = (uint32_t)image; const uint64_t zero = 0;
         if (hipMalloc((void **)&scratch, (size_t)n_du * 64 * sizeof(int16_t)) != hipSuccess || hipMalloc((void **)&d_list, sizeof one) != hipSuccess ||
             hipMalloc((void **)&d_base, sizeof zero) != hipSuccess) { cleanup(); ctx->err = "hipMalloc failed (coefficients scratch)"; return PJD_E_NOMEM; }
+        if (e == hipSuccess) e = poison_dev(ctx, scratch, (size_t)n_du * 64 * sizeof(int16_t));
+        if (e == hipSuccess) e = poison_dev(ctx, d_list, sizeof one);
+        if (e == hipSuccess) e = poison_dev(ctx, d_base, sizeof zero);
         pjd_launch_zero(s, scratch, (size_t)n_du * 64 * sizeof(int16_t));
-        e = hipMemcpyAsync(d_list, &one, sizeof one, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_list, &one, sizeof one, hipMemcpyHostToDevice, s);
         if (e == hipSuccess) e = hipMemcpyAsync(d_base, &zero, sizeof zero, hipMemcpyHostToDevice, s);
         if (e == hipSuccess) {
             PjdDevBatch dv = b->dev;
@@ -1458,6 +1491,13 @@ int pjd_batch_download_coefficients(pjd_batch *b, int image, int16_t *out, uint6
     cleanup();
     if (e != hipSuccess) { ctx->err = std::string("download_coefficients: ") + hipGetErrorString(e); return PJD_E_HIP; }
     return PJD_OK;
+}
+
+// for pjd_split.hip, whose per-rank buffers are allocations on behalf of a context too: PJD_DEBUG_POISON's fill (no part of the ABI)
+int pjd_debug_poison_fill(pjd_ctx *ctx, void *p, uint64_t bytes)
+{
+    if (!ctx) return PJD_E_ARG;
+    return poison_dev(ctx, p, (size_t)bytes) == hipSuccess ? PJD_OK : PJD_E_HIP;
 }
 
 int pjd_decode_batch(pjd_ctx *ctx, const pjd_image_desc *images, int n_images, int out_format,
@@ -1490,6 +1530,8 @@ int pjd_exec_dpu_payload(pjd_ctx *ctx, const uint32_t *metadata, int16_t *mcus, 
     if (hipMalloc((void **)&dc, cb) != hipSuccess) { hipFree(dm); ctx->err = "hipMalloc(mcus)"; return PJD_E_NOMEM; }
     int rc = PJD_OK;
     auto chk = [&](hipError_t e, const char *what) { if (e != hipSuccess && rc == PJD_OK) { ctx->err = std::string(what) + ": " + hipGetErrorString(e); rc = PJD_E_HIP; } };
+    chk(poison_dev(ctx, dm, mb), "poison(metadata_buffer)");
+    chk(poison_dev(ctx, dc, cb), "poison(mcus)");
     chk(hipMemcpyAsync(dm, metadata, mb, hipMemcpyHostToDevice, ctx->stream), "copy(metadata_buffer)");
     chk(hipMemcpyAsync(dc, mcus, cb, hipMemcpyHostToDevice, ctx->stream), "copy(mcus)");
     if (rc == PJD_OK) { pjd_launch_dpu_payload(ctx->stream, dm, dc, n_dpus); chk(hipGetLastError(), "exec"); }

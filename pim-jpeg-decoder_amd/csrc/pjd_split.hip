@@ -29,6 +29,8 @@
 
 #include "../../include/pjd.h"
 
+extern "C" int pjd_debug_poison_fill(pjd_ctx *ctx, void *p, uint64_t bytes);   // pjd_api.hip: PJD_DEBUG_POISON's fill on the context's stream
+
 namespace {
 
 double now_s()
@@ -191,6 +193,7 @@ int pjd_split_rccl_selftest(int device_ordinal, uint64_t bytes)
     rccl_comm comm = nullptr;
     const int dev = device_ordinal;
     bool ok = hipSetDevice(dev) == hipSuccess && hipMalloc((void **)&src, bytes) == hipSuccess && hipMalloc((void **)&dst, bytes) == hipSuccess &&
+              pjd_debug_poison_fill(ctx, src, bytes) == PJD_OK && pjd_debug_poison_fill(ctx, dst, bytes) == PJD_OK &&
               hipMemcpyAsync(src, pat.data(), bytes, hipMemcpyHostToDevice, s) == hipSuccess && hipMemsetAsync(dst, 0, bytes, s) == hipSuccess;
     if (ok) ok = rccl().CommInitAll(&comm, 1, &dev) == 0;
     if (ok) {
@@ -281,6 +284,7 @@ int pjd_split_decode(const pjd_image_desc *desc, const int32_t *devices, int n_d
     for (int r = 0; r < world && he == hipSuccess; r++) {
         he = hipSetDevice(devices[r]);
         if (he == hipSuccess) he = hipMalloc((void **)&d_blob[(size_t)r], blob_bytes);
+        if (he == hipSuccess && pjd_debug_poison_fill(ctx[(size_t)r], d_blob[(size_t)r], blob_bytes) != PJD_OK) he = hipErrorUnknown;
     }
     if (he == hipSuccess) { hipSetDevice(devices[0]); he = hipMemcpyAsync(d_blob[0], blob.data(), blob_bytes, hipMemcpyHostToDevice, (hipStream_t)pjd_stream(ctx[0])); }
     bool by_rccl = false;

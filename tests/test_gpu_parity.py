@@ -609,17 +609,8 @@ def test_random_corrupted_streams_match_oracle(ctx, port):
     error class and the (partial) picture equal the oracle's (reference: the picture decoded so far is still written,
     src/decoder_host.cpp:181)."""
     import pjd_amd
-    synth = _synth()
-    rng = np.random.default_rng(4242)
-    jpegs = []
-    for k in range(200):
-        w, h = int(rng.integers(8, 301)), int(rng.integers(8, 301))
-        sub = int(rng.choice([synth.SUB_444, synth.SUB_422, synth.SUB_420, synth.SUB_440, synth.SUB_GREY]))
-        ri = int(rng.choice([0, 0, 3, 11]))
-        ba = bytearray(synth.make(w, h, 5000 + k, int(rng.choice([25, 75, 95])), sub, ri, float(rng.choice([1.0, synth.DENSE_DETAIL])), bool(k & 1)))
-        for _ in range(int(rng.integers(1, 4))):
-            ba[int(rng.integers(len(ba) // 2, len(ba) - 2))] = int(rng.integers(0, 256))
-        jpegs.append(bytes(ba))
+    import stream_cases
+    jpegs = list(stream_cases.corrupted_streams(200))
     scanned = [pjd_amd.Scanned(j) for j in jpegs]
     valid = [bool(port.parse(j)["info"]["valid"]) for j in jpegs]
     assert [bool(s.valid) for s in scanned] == valid
@@ -1228,22 +1219,9 @@ def test_error_in_a_unit_that_runs_on_into_the_next_lane(port, monkeypatch):
     2 and 5 bytes before every boundary of a dense picture cut into 128-byte subsequences; status, pixels and coefficients
     equal the oracle's for every one of them."""
     import pjd_amd
-    synth = _synth()
+    import stream_cases
     monkeypatch.setenv("PJD_SUB_BYTES", "128")
-    good = synth.make(200, 152, 77, 95, synth.SUB_420, 0, synth.DENSE_DETAIL, True)
-    body = good.rfind(b"\xff\xda") + 14
-    end = len(good) - 2
-    file_pos, i = [], body                    # file offset of every destuffed byte of the entropy-coded segment
-    while i < end:
-        file_pos.append(i)
-        i += 2 if good[i] == 0xFF else 1
-    jpegs = []
-    for k in range(1, len(file_pos) // 128):
-        for r in (2, 5):
-            f = file_pos[k * 128 - r - 2]
-            if 0xFF in good[f - 1:f + 5]:
-                continue
-            jpegs.append(good[:f] + b"\xff\x00\xff\x00" + good[f + 4:])
+    jpegs = list(stream_cases.runon_error_streams())
     assert len(jpegs) > 200
     scanned = [pjd_amd.Scanned(j) for j in jpegs]
     assert all(s.valid for s in scanned)
