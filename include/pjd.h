@@ -355,7 +355,8 @@ int  pjd_resize_tap(uint32_t src_n, uint32_t dst_n, uint32_t i, uint32_t *i0, ui
 /* ---- antialiased resize ------------------------------------------------------------------------------------------------------ *
  * pjd_batch_set_resize_filter(b, PJD_RESIZE_ANTIALIAS): the resize of the batch uses the triangle filter WIDENED where an axis
  * shrinks -- torch.nn.functional.interpolate(mode="bilinear", antialias=True), Pillow's BILINEAR -- instead of the plain bilinear
- * one above.  PJD_RESIZE_BILINEAR (and no call at all) leaves everything as described above.
+ * one above.  PJD_RESIZE_BILINEAR (and no call at all) leaves everything as described above;
+ * PJD_RESIZE_BICUBIC is specified further down.
  *
  * THE ARITHMETIC (normative).  The source P is the source of pjd_batch_set_resize: the picture at its decode size, after
  * PJD_F_SCALE_*, with grey after an entropy-coding error.  Each axis is handled on its own.  Per axis, with sn source samples, dn
@@ -403,6 +404,68 @@ int  pjd_resize_tap(uint32_t src_n, uint32_t dst_n, uint32_t i, uint32_t *i0, ui
 #define PJD_AA_MAX_TAPS      32
 int  pjd_batch_set_resize_filter(pjd_batch *b, int filter);
 int  pjd_resize_aa_taps(uint32_t src_n, uint32_t dst_n, uint32_t i, uint32_t *first, uint32_t *count, uint32_t *q);   /* host only, no device needed */
+/* ---- bicubic resize ---------------------------------------------------------------------------------------------------------- *
+ * pjd_batch_set_resize_filter(b, PJD_RESIZE_BICUBIC): the resize of the batch uses Keys' cubic convolution kernel with a = -0.5,
+ * WIDENED where an axis shrinks -- Pillow's BICUBIC (its bicubic_filter), torch.nn.functional.interpolate(mode="bicubic",
+ * antialias=True) (_upsample_bicubic2d_aa), torchvision's Resize(InterpolationMode.BICUBIC, antialias=True): the filter timm's and
+ * torchvision's ViT / DeiT / Swin / ConvNeXt / EfficientNet transforms use.  It is NOT the a = -0.75 kernel of torch's
+ * NON-antialiased bicubic mode (interpolate(mode="bicubic", antialias=False), OpenCV's INTER_CUBIC), which differs visibly.
+ *
+ * THE ARITHMETIC (normative).  The source P is the source of pjd_batch_set_resize: the picture at its decode size, after
+ * PJD_F_SCALE_*, with grey after an entropy-coding error.  Each axis is handled on its own.  Per axis, with sn source samples, dn
+ * target samples, the target index i, S = max(sn, dn), T = 2*S and, for source sample j, D = |(2*j + 1)*dn - (2*i + 1)*sn| (exact
+ * integers; D/T is the distance from the half-pixel centre in units of the support's scale):
+ *     r_j =  3*D^3 - 5*T*D^2 + 2*T^3                    for D < T
+ *     r_j =   -D^3 + 5*T*D^2 - 8*T^2*D + 4*T^3          for T <= D < 2*T          (zero or negative: the kernel's side lobe)
+ * which is 2*T^3 * k(D/T), k(x) = 1.5|x|^3 - 2.5|x|^2 + 1 for |x| < 1 and -0.5|x|^3 + 2.5|x|^2 - 4|x| + 2 for 1 <= |x| < 2: support 2
+ * target samples where the axis grows or stays, 2*sn/dn source samples where it shrinks.  Samples outside the picture are dropped
+ * and the rest renormalised, as Pillow and torch do.  The TAPS are the contiguous run of j in 0..sn-1 with D < 2*T: `first` and
+ * `count` are defined by the SUPPORT, not by r_j != 0 -- r_j is exactly 0 at D == T, which is inside the run: where sn == dn the taps
+ * of an inner sample are (0, 65536, 0), and a target equal to the source size reproduces P byte for byte.  R = sum r_j > 0 always
+ * (the centre lies inside the picture).  Quantised to 1/65536, SIGNED, divisions rounding DOWN (floor: round half up for either sign):
+ *     q_j = floor((2*65536*r_j + R) / (2*R))
+ * and then 65536 - sum q_j is added to the tap with the largest r_j (the lowest j on a tie), so that sum q_j == 65536 exactly.
+ * r_j * 2^17 needs 69 bits at 65535-sample axes: the tap function uses 128-bit integers and is host only; the kernel divides
+ * nothing.  Per channel, with (first, count, qx) of the target column and (first, count, qy) of the target row, all SIGNED 32-bit:
+ *     h   = sum_x qx * P[y][x]                   (may be negative)
+ *     h6  = (h + 512) >> 10                      (arithmetic shift: the row sample with 6 fraction bits)
+ *     v   = sum_y qy * h6
+ *     out = clamp((v + (1 << 21)) >> 22, 0, 255) (arithmetic shift)
+ * One rounding of the intermediate, one final rounding, ONE clamp -- none between the passes: an overshoot of the horizontal pass
+ * is carried into the vertical one, as the separable filter on float tensors carries it.  A constant picture stays constant.
+ * RANGE.  With A = the largest sum |q_j| over the target samples of both axes, |h| <= 255*A, |h6| <= 255*A/1024 + 1 and
+ * |v| <= A*|h6|: for A <= PJD_BICUBIC_MAX_GAIN = 92681 that is |h| <= 23 633 655, |h6| <= 23 080 and |v| + 2^21 <= 2 141 174 632
+ * < 2^31, so every accumulator fits a signed 32-bit word, and every product has operands within 24 signed bits (|q| <= A < 2^17,
+ * |h6| < 2^15, samples 8 bits).  The largest A found is 83 152 (gain 1.2688, the axis 14 -> 13 at i = 6: exhaustive over all admitted
+ * axes below 130 samples, 200 000 sampled axes up to 65535; tests/test_resize_bicubic_cpu.py repeats the search), but the kernel
+ * does not rest on that: pjd_batch_set_resize_filter sums |q_j| for every target sample of every table it builds and refuses an
+ * axis above 92681 with PJD_E_ARG (pjd_last_error names the picture).
+ * ERROR BOUND.  As for the triangle filter: a rounded q_j is within 1/2 of its exact value and the correction moves one tap by at
+ * most n/2, so the absolute errors of an axis' n weights sum to at most n/65536: 255*n/65536 levels per axis, 0.2491 at the n = 64
+ * of the limit below.  The horizontal error passes through the vertical pass with weights whose magnitudes sum to the gain
+ * g <= 1.4142 (= 92681/65536; 1.2688 found): 0.2491*g; h6 adds its rounding, 1/128 level, times g; the vertical weights add their
+ * own 0.2491 on samples that may overshoot to 255*g, i.e. 0.2491*g: at most (2*0.2491 + 1/128)*1.4142 = 0.716 levels (0.643 at the
+ * gain found) from the exact separable filter before the ONE final rounding -- below 1, so the result is within 1 level of that
+ * filter computed in float64, clamped once at the end and rounded to nearest, which is what torch computes on float tensors
+ * (measured: 0.012 levels before rounding on random and 0/255 pictures, tests/test_resize_bicubic_cpu.py).
+ * PILLOW'S uint8 PATH rounds and CLIPS the horizontal pass to 8 bits.  Where that pass overshoots 0..255 Pillow's result therefore
+ * differs from the float64 filter, and from this one: by at most 1 level on smooth content, by up to 29 levels on a random 0/255
+ * picture (measured, the same test).  That is a property of Pillow's 8-bit intermediate, not of the filter; it is not reproduced.
+ * LIMIT.  sn <= 16*dn on each axis, as for the triangle filter.  PJD_BICUBIC_MAX_TAPS is the largest tap count the limit admits:
+ * the points (2*j + 1)*dn inside an OPEN interval of length 4*T = 8*S, 2*dn apart: at most ceil(4*S/dn) -- 4 where the axis grows,
+ * 64 where sn <= 16*dn, attained where the axis shrinks by exactly 16x, e.g. by 96 -> 6 at i = 3 (tests/test_resize_bicubic_cpu.py).
+ *
+ * CALL ORDER, the errors and everything "FROM THEN ON" are those of PJD_RESIZE_ANTIALIAS above, word for word: the 16x refusal that
+ * names the picture, the window's limit and the tables of the windowed axes where the batch has source windows (their taps are
+ * pjd_resize_bicubic_taps(w, vw, ox + i') and (h, vh, oy + j), addressed from x and y on), the weight table shared per (sn, dn)
+ * pair and counted in device_bytes, the one launch named "resize", pjd_batch_set_normalize applied to `out`.
+ * pjd_resize_bicubic_taps is the tap computation on its own, host only (no device needed), the very inline the table is built
+ * with: first, count and q[0 .. count-1] (q has room for PJD_BICUBIC_MAX_TAPS entries; each of the three may be NULL).  PJD_E_ARG
+ * if src_n or dst_n is 0 or above 65535, i >= dst_n, or src_n > 16*dst_n.                                                        */
+#define PJD_RESIZE_BICUBIC      3   /* 2 is not a filter: it stays the unknown value callers were promised PJD_E_ARG for */
+#define PJD_BICUBIC_MAX_TAPS    64
+#define PJD_BICUBIC_MAX_GAIN    92681
+int  pjd_resize_bicubic_taps(uint32_t src_n, uint32_t dst_n, uint32_t i, uint32_t *first, uint32_t *count, int32_t *q);   /* host only, no device needed */
 /* ---- source windows: crop and flip inside the resize ------------------------------------------------------------------------------ *
  * pjd_batch_set_resize_window: picture i of a resized batch is resampled from a WINDOW of the decoded picture, to a window of a
  * VIRTUAL target, and mirrored left-right where asked (win: n_images records).  The pipelines of a vision loader in one launch:
@@ -430,7 +493,8 @@ int  pjd_resize_aa_taps(uint32_t src_n, uint32_t dst_n, uint32_t i, uint32_t *fi
  * it for every picture with PJD_RESIZE_BILINEAR, pjd_batch_set_resize_filter again with the filter it is given.  PJD_OK, or
  * PJD_E_ARG (pjd_last_error names the picture) for: sw, sh, tw or th outside 1..65535, a null record, an unknown filter;
  * w == 0 xor h == 0; w == h == 0 with x or y non-zero; x + w > sw or y + h > sh; vw or vh above 65535; ox + tw > vw or
- * oy + th > vh (defaults resolved); an unknown flag bit; reserved_ != 0; and with PJD_RESIZE_ANTIALIAS w > 16*vw or h > 16*vh.
+ * oy + th > vh (defaults resolved); an unknown flag bit; reserved_ != 0; and with PJD_RESIZE_ANTIALIAS or PJD_RESIZE_BICUBIC w > 16*vw
+ * or h > 16*vh.
  * The 16x limit of the antialiased filter is the WINDOW's: a picture past 16x its target whose window is inside is accepted.
  *
  * CALL ORDER.  After pjd_batch_set_resize; before any pjd_batch_set_resize_filter / _set_normalize / _bind_output / _upload /

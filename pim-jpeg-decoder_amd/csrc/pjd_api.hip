@@ -215,20 +215,21 @@ struct pjd_batch {
     size_t rs_bytes = 0;
     uint32_t rs_tiles = 0;
     PjdNormalize norm{};                         // pjd_batch_set_normalize: dtype != 0, the result holds elements of PJD_DT_SIZE(dtype) bytes
-    bool filter_set = false, antialias = false;  // pjd_batch_set_resize_filter: called / with PJD_RESIZE_ANTIALIAS
-    uint8_t *h_aa = nullptr, *d_aa = nullptr;    // its per-picture records (PjdDevResizeAA[n_images]) and, behind them, the weight table: page-locked / HBM
+    bool filter_set = false;                     // pjd_batch_set_resize_filter: called ...
+    int filter = PJD_RESIZE_BILINEAR;            // ... with this PJD_RESIZE_*; the two table-driven ones (antialiased, bicubic) have
+    uint8_t *h_aa = nullptr, *d_aa = nullptr;    // per-picture records (PjdDevResizeAA[n_images]) and, behind them, the weight table: page-locked / HBM
     size_t aa_bytes = 0;
     uint32_t aa_lds = 0;                         // LDS of the launch: the largest row segment a tile of the batch stages
     bool win_set = false, windowed = false;      // pjd_batch_set_resize_window: called / with a record that is not all zero
     PjdDevResizeWin *h_win = nullptr, *d_win = nullptr;   // then: the windows, defaults resolved, [n_images]: page-locked / HBM
     size_t win_bytes = 0;
 
-    // the resample launch of this batch, bilinear or antialiased, windowed or not (both launch sites: the decode and the re-run
+    // the resample launch of this batch, whatever its filter, windowed or not (both launch sites: the decode and the re-run
     // after the fallback)
     void launch_resize(hipStream_t s, bool planar) const
     {
-        pjd_launch_resize(s, PjdResizeLaunch{dev.out, res_out, d_rs, d_rs_prefix, dev.n_images, rs_tiles, planar, norm, windowed ? d_win : nullptr, antialias,
-                                             (const PjdDevResizeAA *)d_aa, antialias ? (const uint32_t *)(d_aa + dev.n_images * sizeof(PjdDevResizeAA)) : nullptr, aa_lds});
+        pjd_launch_resize(s, PjdResizeLaunch{dev.out, res_out, d_rs, d_rs_prefix, dev.n_images, rs_tiles, planar, norm, windowed ? d_win : nullptr, filter,
+                                             (const PjdDevResizeAA *)d_aa, d_aa ? (const uint32_t *)(d_aa + dev.n_images * sizeof(PjdDevResizeAA)) : nullptr, aa_lds});
     }
 };
 
@@ -481,7 +482,7 @@ int pjd_batch_upload(pjd_batch *b)
     // With a resize set dev.out is the batch's intermediate, bound or not; the resized pictures are RGB8 or planar, written whole.
     if (!b->bound || b->resized) HIP_TRY(ctx, hipMemsetAsync(b->dev.out, 0, P.out_buf_bytes, s));
     if (b->resized) HIP_TRY(ctx, hipMemcpyAsync(b->d_rs, b->h_rs, b->rs_bytes, hipMemcpyHostToDevice, s));      // the resample work list (page-locked)
-    if (b->antialias) HIP_TRY(ctx, hipMemcpyAsync(b->d_aa, b->h_aa, b->aa_bytes, hipMemcpyHostToDevice, s));   // ... and its weight table
+    if (b->d_aa) HIP_TRY(ctx, hipMemcpyAsync(b->d_aa, b->h_aa, b->aa_bytes, hipMemcpyHostToDevice, s));   // ... and its weight table
     if (b->windowed) HIP_TRY(ctx, hipMemcpyAsync(b->d_win, b->h_win, b->win_bytes, hipMemcpyHostToDevice, s));  // ... and its source windows
     b->uploaded = true;
     return PJD_OK;
@@ -1024,6 +1025,18 @@ int pjd_resize_aa_taps(uint32_t src_n, uint32_t dst_n, uint32_t i, uint32_t *fir
     return PJD_OK;
 }
 
+int pjd_resize_bicubic_taps(uint32_t src_n, uint32_t dst_n, uint32_t i, uint32_t *first, uint32_t *count, int32_t *q)
+{
+    if (src_n == 0 || src_n > 65535u || dst_n == 0 || dst_n > 65535u || i >= dst_n || src_n > 16u * dst_n) return PJD_E_ARG;
+    uint32_t f;
+    int32_t w[PJD_BICUBIC_MAX_TAPS];
+    const uint32_t n = pjd_resize_bicubic_taps_calc(src_n, dst_n, i, f, w);
+    if (first) *first = f;
+    if (count) *count = n;
+    if (q) std::memcpy(q, w, n * sizeof(int32_t));
+    return PJD_OK;
+}
+
 int pjd_batch_set_resize_filter(pjd_batch *b, int filter)
 {
     if (!b) return PJD_E_ARG;
@@ -1034,7 +1047,7 @@ int pjd_batch_set_resize_filter(pjd_batch *b, int filter)
     if (b->norm.dtype != 0) { ctx->err = "set_resize_filter after set_normalize"; return PJD_E_STATE; }
     if (b->bound) { ctx->err = "set_resize_filter after bind_output"; return PJD_E_STATE; }
     if (b->uploaded) { ctx->err = "set_resize_filter after upload"; return PJD_E_STATE; }
-    if (filter != PJD_RESIZE_BILINEAR && filter != PJD_RESIZE_ANTIALIAS) { ctx->err = "set_resize_filter: unknown filter (PJD_RESIZE_BILINEAR or PJD_RESIZE_ANTIALIAS)"; return PJD_E_ARG; }
+    if (filter != PJD_RESIZE_BILINEAR && filter != PJD_RESIZE_ANTIALIAS && filter != PJD_RESIZE_BICUBIC) { ctx->err = "set_resize_filter: unknown filter (PJD_RESIZE_BILINEAR, PJD_RESIZE_ANTIALIAS or PJD_RESIZE_BICUBIC)"; return PJD_E_ARG; }
     if (filter == PJD_RESIZE_BILINEAR) { b->filter_set = true; return PJD_OK; }
     const size_t n = P.images.size();
     for (size_t i = 0; i < n; i++) {
@@ -1053,26 +1066,35 @@ int pjd_batch_set_resize_filter(pjd_batch *b, int filter)
     }
     // The weight table: one axis table per distinct (source length, target length) of the batch -- the pictures of a data set share
     // a few -- each dn heads `first | count << 16`, then taps x dn weights, tap-major, 0 behind a sample's own count (pjd_internal.h).
-    struct Axis { uint32_t off, taps; };
+    // The bicubic filter has weights of either sign, kept as the bit patterns of int32, and its kernel's 32-bit accumulators hold only
+    // while sum |q_j| <= PJD_BICUBIC_MAX_GAIN (include/pjd.h): `gain` is the largest such sum of the axis, checked where it is used.
+    const bool cubic = filter == PJD_RESIZE_BICUBIC;
+    const uint32_t max_taps = cubic ? PJD_BICUBIC_MAX_TAPS : PJD_AA_MAX_TAPS;
+    struct Axis { uint32_t off, taps, gain; };
     std::map<std::pair<uint32_t, uint32_t>, Axis> axes;
     std::vector<uint32_t> tab;
     auto axis = [&](uint32_t sn, uint32_t dn) -> Axis {
         auto it = axes.find({sn, dn});
         if (it != axes.end()) return it->second;
         const size_t base = tab.size();
-        const uint32_t bound = (2u * std::max(sn, dn) + dn - 1u) / dn;          // no sample has more taps than ceil(2 * S / dn) (include/pjd.h)
-        const uint32_t cap = std::min<uint32_t>(std::max<uint32_t>(bound, 1u), PJD_AA_MAX_TAPS);
+        const uint32_t bound = ((cubic ? 4u : 2u) * std::max(sn, dn) + dn - 1u) / dn;   // no sample has more taps than ceil(2 * S / dn), bicubic ceil(4 * S / dn) (include/pjd.h)
+        const uint32_t cap = std::min<uint32_t>(std::max<uint32_t>(bound, 1u), max_taps);
         tab.resize(base + (size_t)dn * (1u + cap), 0u);
-        uint32_t taps = 0, w[PJD_AA_MAX_TAPS];
+        uint32_t taps = 0, gain = 0, w[PJD_BICUBIC_MAX_TAPS];
+        static_assert(PJD_BICUBIC_MAX_TAPS >= PJD_AA_MAX_TAPS, "one array for both filters");
         for (uint32_t i = 0; i < dn; i++) {
-            uint32_t first;
-            const uint32_t cnt = std::min(pjd_resize_aa_taps_calc(sn, dn, i, first, w), cap);
+            uint32_t first, sum = 0;
+            const uint32_t cnt = std::min(cubic ? pjd_resize_bicubic_taps_calc(sn, dn, i, first, (int32_t *)w) : pjd_resize_aa_taps_calc(sn, dn, i, first, w), cap);
             tab[base + i] = first | (cnt << 16);
-            for (uint32_t t = 0; t < cnt; t++) tab[base + (size_t)(t + 1u) * dn + i] = w[t];
+            for (uint32_t t = 0; t < cnt; t++) {
+                tab[base + (size_t)(t + 1u) * dn + i] = w[t];
+                sum += (int32_t)w[t] < 0 ? 0u - w[t] : w[t];
+            }
             taps = std::max(taps, cnt);
+            gain = std::max(gain, sum);
         }
         tab.resize(base + (size_t)dn * (1u + taps));       // the rows no sample reaches are dropped
-        const Axis a{(uint32_t)base, taps};
+        const Axis a{(uint32_t)base, taps, gain};
         axes[{sn, dn}] = a;
         return a;
     };
@@ -1082,8 +1104,12 @@ int pjd_batch_set_resize_filter(pjd_batch *b, int filter)
         const PjdDevResize &r = b->h_rs[i];
         // a windowed picture takes the tables of its windowed axes, over the whole virtual target (tap index ox + i', row length vw)
         const PjdDevResizeWin w = b->windowed ? b->h_win[i] : pjd_resize_win_identity(r);
-        if (tab.size() + ((size_t)w.vw + w.vh) * (1u + PJD_AA_MAX_TAPS) >= (1ull << 31)) { ctx->err = "set_resize_filter: the weight table of this batch is too large"; return PJD_E_ARG; }
+        if (tab.size() + ((size_t)w.vw + w.vh) * (1u + max_taps) >= (1ull << 31)) { ctx->err = "set_resize_filter: the weight table of this batch is too large"; return PJD_E_ARG; }
         const Axis x = axis(w.w, w.vw), y = axis(w.h, w.vh);
+        if (cubic && std::max(x.gain, y.gain) > PJD_BICUBIC_MAX_GAIN) {
+            ctx->err = fmt_image("set_resize_filter: the bicubic weights of picture %d sum to more than PJD_BICUBIC_MAX_GAIN in magnitude on an axis", (int)i);
+            return PJD_E_ARG;
+        }
         recs[i] = PjdDevResizeAA{x.off, x.taps, y.off, y.taps};
         // the widest row segment one of its tiles stages: first tap of the tile's first column to the last tap of its last one
         for (uint32_t c0 = 0; c0 < r.tw; c0 += PJD_RS_COLS) {
@@ -1103,7 +1129,7 @@ int pjd_batch_set_resize_filter(pjd_batch *b, int filter)
     std::memcpy((uint8_t *)h_aa + n * sizeof(PjdDevResizeAA), tab.data(), tab.size() * sizeof(uint32_t));
     b->device_bytes += bytes;
     b->h_aa = (uint8_t *)h_aa; b->d_aa = (uint8_t *)d_aa; b->aa_bytes = bytes; b->aa_lds = lds;
-    b->filter_set = true; b->antialias = true;
+    b->filter_set = true; b->filter = filter;
     return PJD_OK;
 }
 
@@ -1114,7 +1140,7 @@ const char *resize_window_fault(uint32_t sw, uint32_t sh, uint32_t tw, uint32_t 
 {
     if (sw == 0 || sw > 65535u || sh == 0 || sh > 65535u || tw == 0 || tw > 65535u || th == 0 || th > 65535u) return "picture and target sizes must be 1..65535";
     if (!win) return "null record";
-    if (filter != PJD_RESIZE_BILINEAR && filter != PJD_RESIZE_ANTIALIAS) return "unknown filter (PJD_RESIZE_BILINEAR or PJD_RESIZE_ANTIALIAS)";
+    if (filter != PJD_RESIZE_BILINEAR && filter != PJD_RESIZE_ANTIALIAS && filter != PJD_RESIZE_BICUBIC) return "unknown filter (PJD_RESIZE_BILINEAR, PJD_RESIZE_ANTIALIAS or PJD_RESIZE_BICUBIC)";
     if ((win->w == 0) != (win->h == 0)) return "an empty window (w and h are both 0 for the whole picture, or both at least 1)";
     if (win->w == 0 && (win->x != 0 || win->y != 0)) return "x and y must be 0 where w == h == 0 (the whole picture)";
     const uint64_t w = win->w ? win->w : sw, h = win->h ? win->h : sh;
@@ -1124,7 +1150,7 @@ const char *resize_window_fault(uint32_t sw, uint32_t sh, uint32_t tw, uint32_t 
     if ((uint64_t)win->ox + tw > vw || (uint64_t)win->oy + th > vh) return "the delivered columns and rows are not inside the virtual target";
     if (win->flags & ~PJD_RW_HFLIP) return "unknown flag bits";
     if (win->reserved_ != 0) return "reserved_ must be 0";
-    if (filter == PJD_RESIZE_ANTIALIAS && (w > 16u * vw || h > 16u * vh)) return "the window is more than 16x its virtual target on an axis (PJD_RESIZE_ANTIALIAS)";
+    if (filter != PJD_RESIZE_BILINEAR && (w > 16u * vw || h > 16u * vh)) return "the window is more than 16x its virtual target on an axis (PJD_RESIZE_ANTIALIAS, PJD_RESIZE_BICUBIC)";
     return nullptr;
 }
 

@@ -418,7 +418,40 @@ static inline __host__ __device__ uint32_t pjd_resize_aa_taps_calc(uint32_t sn, 
     return n;
 }
 
-// What the antialiased launch (pjd_k_resize_aa_body.h) reads beside the work list of the bilinear one: per picture, where the tables of
+// ---- bicubic resize (pjd_batch_set_resize_filter, PJD_RESIZE_BICUBIC; the arithmetic is normative: include/pjd.h) ----------------
+// One axis of Keys' cubic (a = -0.5), widened where the axis shrinks: target sample i of dn over sn source samples -> the first
+// source sample of the support, the number of taps (returned; 1..PJD_BICUBIC_MAX_TAPS) and their SIGNED weights q[0 .. count-1] in
+// 1/65536, which sum to 65536 exactly.  THE implementation: pjd_resize_bicubic_taps exports it, pjd_batch_set_resize_filter fills the
+// batch's weight table with it.  HOST ONLY: r_j * 2^17 needs 69 bits at 65535-sample axes, so the quantisation is in 128-bit
+// integers; the kernel divides nothing.  sn, dn in 1..65535, i < dn, sn <= 16 * dn.  The raw weights fit 64 bits: T < 2^17, D < 2 * T,
+// so every term of the two cubics stays below 2^56 and their sum over 64 taps below 2^62.
+static inline uint32_t pjd_resize_bicubic_taps_calc(uint32_t sn, uint32_t dn, uint32_t i, uint32_t &first, int32_t *q)
+{
+    const int64_t T = 2 * (int64_t)(sn > dn ? sn : dn), c = (int64_t)(2u * i + 1u) * sn, d2 = 2 * (int64_t)dn;
+    const int64_t lo = c - 2 * T;                              // taps: lo < (2 * j + 1) * dn < c + 2 * T, whatever their weight
+    first = lo < (int64_t)dn ? 0u : (uint32_t)((lo - dn) / d2) + 1u;
+    int64_t r[64], R = 0;
+    uint32_t n = 0, best = 0;
+    // n < 64 (PJD_BICUBIC_MAX_TAPS) never ends the loop where sn <= 16 * dn; it keeps the arrays safe whatever comes in
+    for (int64_t p = (2 * (int64_t)first + 1) * dn; n < 64u && first + n < sn && p < c + 2 * T; p += d2, n++) {
+        const int64_t D = p > c ? p - c : c - p;
+        r[n] = D < T ? 3 * D * D * D - 5 * T * D * D + 2 * T * T * T : -D * D * D + 5 * T * D * D - 8 * T * T * D + 4 * T * T * T;
+        R += r[n];
+        if (r[n] > r[best]) best = n;
+    }
+    int64_t rest = 65536;
+    for (uint32_t k = 0; k < n; k++) {
+        const __int128 num = (__int128)r[k] * 131072 + R, den = 2 * (__int128)R;       // R > 0: the centre lies inside the picture
+        __int128 v = num / den;
+        if (num % den < 0) v--;                                // floor: round half up for either sign
+        q[k] = (int32_t)v;
+        rest -= q[k];
+    }
+    q[best] = (int32_t)(q[best] + rest);
+    return n;
+}
+
+// What the antialiased launch (pjd_k_resize_aa_body.h; the bicubic one likewise) reads beside the work list of the bilinear one: per picture, where the tables of
 // its two axes start in the batch's weight table (in words) and how many taps a row of each holds.  The table of one axis (sn -> dn,
 // shared by every picture and axis with that pair): dn head words `first | count << 16`, then taps x dn weights, TAP-MAJOR
 // (weight t of target sample i at dn + t * dn + i; 0 from `count` on), so that the lanes of a wave read adjacent words.

@@ -31,10 +31,14 @@
 //     wave-uniform test, the weight a scalar load.  8 x 12 accumulators live in registers (no scratch).
 // Then the same epilogue.  The weights are made on the host (pjd_resize_aa_taps_calc, pjd_internal.h): no division here.
 //
-// Source windows (pjd_batch_set_resize_window): either filter from a WINDOW of the decoded picture to a window of a virtual target,
+// The bicubic filter (PJD_RESIZE_BICUBIC): that launch again -- the same streaming, staging, tables (tap-major, now up to 64 taps an
+// axis and weights of either sign) and epilogue -- with the signed arithmetic include/pjd.h specifies: signed 24-bit multiplies, the
+// row sample with 6 fraction bits, one clamp at the end.  The body is the antialiased one with a compile-time FILT.
+//
+// Source windows (pjd_batch_set_resize_window): any filter from a WINDOW of the decoded picture to a window of a virtual target,
 // mirrored left-right where asked -- flip(resize(P[y:y+h, x:x+w], vw, vh)[oy:oy+th, ox:ox+tw]) of include/pjd.h.  No arithmetic of
 // its own: the taps are the same functions and tables with a shifted index, read from a per-picture record of its own
-// (PjdDevResizeWin) beside PjdDevResize.  Each filter is ONE body text (pjd_k_resize_body.h, pjd_k_resize_aa_body.h) with a
+// (PjdDevResizeWin) beside PjdDevResize.  The gather and the table-driven filters are ONE body text each (pjd_k_resize_body.h, pjd_k_resize_aa_body.h) with a
 // compile-time WIN: a batch without windows runs kernels built with the identity window, which are the kernels it ran before.
 #include <hip/hip_runtime.h>
 
@@ -87,6 +91,7 @@ pjd_k_resize_aa(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, cons
 {
     extern __shared__ uint32_t seg[];                      // one source row's segment (three plane segments where PLANAR)
     constexpr bool WIN = false;
+    constexpr int FILT = PJD_RESIZE_ANTIALIAS;
     const PjdDevResizeWin *const win = nullptr;
 #include "pjd_k_resize_aa_body.h"
 }
@@ -99,6 +104,33 @@ pjd_k_resize_win_aa(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, 
 {
     extern __shared__ uint32_t seg[];
     constexpr bool WIN = true;
+    constexpr int FILT = PJD_RESIZE_ANTIALIAS;
+#include "pjd_k_resize_aa_body.h"
+}
+
+// the bicubic filter: the same two kernels with the body's other arithmetic
+template <bool PLANAR, int DT>
+__global__ void __launch_bounds__(64)
+pjd_k_resize_cubic(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, const PjdDevResize *__restrict__ recs,
+                   const uint32_t *__restrict__ tile_prefix, uint32_t n_images, uint32_t n_tiles, const PjdDevResizeAA *__restrict__ aa,
+                   const uint32_t *__restrict__ tab, uint32_t lds_bytes, const NormArgs nz)
+{
+    extern __shared__ uint32_t seg[];
+    constexpr bool WIN = false;
+    constexpr int FILT = PJD_RESIZE_BICUBIC;
+    const PjdDevResizeWin *const win = nullptr;
+#include "pjd_k_resize_aa_body.h"
+}
+
+template <bool PLANAR, int DT>
+__global__ void __launch_bounds__(64)
+pjd_k_resize_win_cubic(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, const PjdDevResize *__restrict__ recs,
+                       const PjdDevResizeWin *__restrict__ win, const uint32_t *__restrict__ tile_prefix, uint32_t n_images, uint32_t n_tiles,
+                       const PjdDevResizeAA *__restrict__ aa, const uint32_t *__restrict__ tab, uint32_t lds_bytes, const NormArgs nz)
+{
+    extern __shared__ uint32_t seg[];
+    constexpr bool WIN = true;
+    constexpr int FILT = PJD_RESIZE_BICUBIC;
 #include "pjd_k_resize_aa_body.h"
 }
 
@@ -124,14 +156,19 @@ void pjd_launch_resize(hipStream_t s, const PjdResizeLaunch &a)
     if (a.n_tiles == 0) return;
     NormArgs nz{};
     for (int c = 0; c < 3; c++) { nz.scale[c] = a.norm.scale[c]; nz.bias[c] = a.norm.bias[c]; }
-    // bilinear: PJD_RS_WAVES tiles per workgroup, no LDS; antialiased: a workgroup is one wave with its row segment in LDS
-    const dim3 grid(a.antialias ? a.n_tiles : (a.n_tiles + PJD_RS_WAVES - 1) / PJD_RS_WAVES), block(a.antialias ? 64 : 64 * PJD_RS_WAVES);
+    // bilinear: PJD_RS_WAVES tiles per workgroup, no LDS; the table-driven filters: a workgroup is one wave with its row segment in LDS
+    const bool tabled = a.filter != PJD_RESIZE_BILINEAR;
+    const dim3 grid(tabled ? a.n_tiles : (a.n_tiles + PJD_RS_WAVES - 1) / PJD_RS_WAVES), block(tabled ? 64 : 64 * PJD_RS_WAVES);
     for_layout_and_dtype(a.planar, a.norm.dtype, [&](auto P, auto D) {
         constexpr bool PL = decltype(P)::value;
         constexpr int DT = decltype(D)::value;
-        if (a.antialias && a.win)
+        if (a.filter == PJD_RESIZE_BICUBIC && a.win)
+            hipLaunchKernelGGL((pjd_k_resize_win_cubic<PL, DT>), grid, block, a.lds_bytes, s, a.src, a.dst, a.recs, a.win, a.tile_prefix, a.n_images, a.n_tiles, a.aa, a.tab, a.lds_bytes, nz);
+        else if (a.filter == PJD_RESIZE_BICUBIC)
+            hipLaunchKernelGGL((pjd_k_resize_cubic<PL, DT>), grid, block, a.lds_bytes, s, a.src, a.dst, a.recs, a.tile_prefix, a.n_images, a.n_tiles, a.aa, a.tab, a.lds_bytes, nz);
+        else if (tabled && a.win)
             hipLaunchKernelGGL((pjd_k_resize_win_aa<PL, DT>), grid, block, a.lds_bytes, s, a.src, a.dst, a.recs, a.win, a.tile_prefix, a.n_images, a.n_tiles, a.aa, a.tab, a.lds_bytes, nz);
-        else if (a.antialias)
+        else if (tabled)
             hipLaunchKernelGGL((pjd_k_resize_aa<PL, DT>), grid, block, a.lds_bytes, s, a.src, a.dst, a.recs, a.tile_prefix, a.n_images, a.n_tiles, a.aa, a.tab, a.lds_bytes, nz);
         else if (a.win)
             hipLaunchKernelGGL((pjd_k_resize_win<PL, DT>), grid, block, 0, s, a.src, a.dst, a.recs, a.win, a.tile_prefix, a.n_images, a.n_tiles, nz);

@@ -1,6 +1,9 @@
-// pjd_k_resize_aa_body.h -- the body of the antialiased resample kernels of pjd_k_resize.hip, included once per kernel:
-// pjd_k_resize_aa<PLANAR, DT> and, with WIN, pjd_k_resize_win_aa<PLANAR, DT> (pjd_batch_set_resize_window).  A wave STREAMS down the
-// source rows its tile reads (pjd_k_resize.hip says how).  The taps are those of a source WINDOW (include/pjd.h), which without WIN
+// pjd_k_resize_aa_body.h -- the body of the table-driven (separable) resample kernels of pjd_k_resize.hip, included once per kernel:
+// pjd_k_resize_aa<PLANAR, DT> and, with WIN, pjd_k_resize_win_aa<PLANAR, DT> (pjd_batch_set_resize_window) for the widened triangle
+// filter, pjd_k_resize_cubic / pjd_k_resize_win_cubic for the bicubic one.  A wave STREAMS down the source rows its tile reads
+// (pjd_k_resize.hip says how).  FILT (PJD_RESIZE_ANTIALIAS or PJD_RESIZE_BICUBIC, a compile-time constant) chooses the ARITHMETIC of a
+// tap, of the row sample between the passes and of the final rounding (tap_mac, tap_row, tap_out of pjd_k_resize_store.h: unsigned
+// with 8 fraction bits, or signed with 6 and one clamp); the streaming, the staging, the tables' layout and the guards are one text.  The taps are those of a source WINDOW (include/pjd.h), which without WIN
 // is the identity window (pjd_resize_win_identity) and folds away:
 //   - the tables are those of the axes (w.w, w.vw) and (w.h, w.vh); a column's entries are at index w.ox + i', i' the lane's column or
 //     its mirror image (PJD_RW_HFLIP), a row's at w.oy + row; the tap-major rows are w.vw and w.vh long;
@@ -12,7 +15,7 @@
 // No lane leaves before the last barrier; lanes right of the picture compute its last column and store nothing.
 // A textual include, so that tools/resize_host.cpp runs this very text on the host; PJD_WIN_STAGE_FIRST / _STEP say which dwords of a
 // segment this thread stages (its own of the wave's 64 here; all of them where a thread runs alone).
-// In scope: PLANAR, DT, WIN (compile-time constants), seg (LDS), src, dst, recs, win (read only where WIN), tile_prefix, n_images,
+// In scope: PLANAR, DT, WIN, FILT (compile-time constants), seg (LDS), src, dst, recs, win (read only where WIN), tile_prefix, n_images,
 // n_tiles, aa, tab, lds_bytes, nz; store_row.
 #ifndef PJD_WIN_STAGE_FIRST
 #define PJD_WIN_STAGE_FIRST lane
@@ -117,14 +120,14 @@
 #pragma unroll
                 for (int c = 0; c < 3; c++) {
                     const uint32_t v = PLANAR ? sb[c * pitch + sh[c] + j] : sb[sh[0] + 3u * j + c];
-                    h[c][q] += __umul24(wt, v);
+                    h[c][q] = tap_mac<FILT>(h[c][q], wt, v);
                 }
             }
         }
 #pragma unroll
         for (int c = 0; c < 3; c++)
 #pragma unroll
-            for (int q = 0; q < PJD_RS_PX; q++) h[c][q] = (h[c][q] + 128u) >> 8;
+            for (int q = 0; q < PJD_RS_PX; q++) h[c][q] = tap_row<FILT>(h[c][q]);
 
 #pragma unroll
         for (int k = 0; k < PJD_RS_ROWS; k++) {
@@ -134,7 +137,7 @@
 #pragma unroll
                 for (int c = 0; c < 3; c++)
 #pragma unroll
-                    for (int q = 0; q < PJD_RS_PX; q++) acc[k][c][q] += __umul24(wt, h[c][q]);
+                    for (int q = 0; q < PJD_RS_PX; q++) acc[k][c][q] = tap_mac<FILT>(acc[k][c][q], wt, h[c][q]);
             }
         }
     }
@@ -146,6 +149,6 @@
 #pragma unroll
         for (int c = 0; c < 3; c++)
 #pragma unroll
-            for (int q = 0; q < PJD_RS_PX; q++) px[c][q] = (acc[k][c][q] + (1u << 23)) >> 24;
+            for (int q = 0; q < PJD_RS_PX; q++) px[c][q] = tap_out<FILT>(acc[k][c][q]);
         store_row<PLANAR, DT>(px, dp, row0 + k, col0, n_px, dst_plane, dst_stride, nz);
     }

@@ -5,6 +5,32 @@
 // ((256 - w) * a + w * b): below 2^16; the products and sums of the second stage stay below 2^24 (include/pjd.h)
 __device__ __forceinline__ uint32_t lerp8(uint32_t a, uint32_t b, uint32_t w) { return __umul24(256u - w, a) + __umul24(w, b); }
 
+// The arithmetic of the two table-driven filters (pjd_k_resize_aa_body.h; normative in include/pjd.h), FILT a compile-time constant.
+// The triangle filter: weights 0..65536, everything unsigned, the row sample with 8 fraction bits.  The bicubic filter: weights of
+// either sign (|q| < 2^18) held as the bit patterns of int32, sums in two's complement, the row sample with 6 fraction bits
+// (|h6| < 2^15) and ONE clamp, at the end (v_med3_i32).  Every product has operands of at most 24 signed bits.
+template <int FILT>
+__device__ __forceinline__ uint32_t tap_mac(uint32_t acc, uint32_t w, uint32_t v)
+{
+    if (FILT == PJD_RESIZE_BICUBIC) return acc + (uint32_t)__mul24((int32_t)w, (int32_t)v);
+    return acc + __umul24(w, v);
+}
+template <int FILT>
+__device__ __forceinline__ uint32_t tap_row(uint32_t h)
+{
+    if (FILT == PJD_RESIZE_BICUBIC) return (uint32_t)(((int32_t)h + 512) >> 10);
+    return (h + 128u) >> 8;
+}
+template <int FILT>
+__device__ __forceinline__ uint32_t tap_out(uint32_t v)
+{
+    if (FILT == PJD_RESIZE_BICUBIC) {
+        const int32_t o = ((int32_t)v + (1 << 21)) >> 22;
+        return (uint32_t)(o < 0 ? 0 : o > 255 ? 255 : o);
+    }
+    return (v + (1u << 23)) >> 24;
+}
+
 // the constants of a normalised launch, by value in the kernel arguments (scalar registers)
 struct NormArgs { float scale[3], bias[3]; };
 

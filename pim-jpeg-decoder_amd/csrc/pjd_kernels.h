@@ -70,7 +70,7 @@ void pjd_launch_idct_sweep(hipStream_t s, const PjdDevBatch &b);
 // (the same layout), one launch whatever the batch asked for; tile_prefix[i] = tiles of the pictures before i, tile_prefix[n_images] =
 // n_tiles.  norm.dtype != 0: the samples leave as fp16 / bf16 / fp32 elements, v * scale[c] + bias[c] (pjd_batch_set_normalize); the
 // records' dst_off stay byte offsets.  win: null, or win[i] is picture i's source window, defaults resolved
-// (pjd_batch_set_resize_window).  antialias: the widened triangle filter (pjd_batch_set_resize_filter); aa[i] then says where picture
+// (pjd_batch_set_resize_window).  filter: PJD_RESIZE_* (pjd_batch_set_resize_filter); for the two table-driven ones aa[i] says where picture
 // i's weights lie in `tab` (pjd_internal.h; the tables of the windowed axes where win), and lds_bytes is the largest row segment a tile
 // of the batch stages (mirrored tiles included); all three unused otherwise.
 struct PjdResizeLaunch {
@@ -82,7 +82,7 @@ struct PjdResizeLaunch {
     bool planar;
     PjdNormalize norm;
     const PjdDevResizeWin *win;
-    bool antialias;
+    int filter;
     const PjdDevResizeAA *aa;
     const uint32_t *tab;
     uint32_t lds_bytes;

@@ -23,6 +23,9 @@ F_SCALE_1_2, F_SCALE_1_4, F_SCALE_1_8, F_SCALE_MASK = 16, 32, 48, 48      # outp
 RESIZE_BILINEAR, RESIZE_ANTIALIAS = 0, 1   # pjd_batch_set_resize_filter (pjd.h)
 RW_HFLIP = 1                               # pjd_resize_window.flags: the delivered picture mirrored left-right
 AA_MAX_TAPS = 32                           # PJD_AA_MAX_TAPS: the most taps per axis pjd_resize_aa_taps returns
+RESIZE_BICUBIC = 3                         # PJD_RESIZE_BICUBIC: Keys' cubic (a = -0.5), widened where an axis shrinks
+BICUBIC_MAX_TAPS = 64                      # PJD_BICUBIC_MAX_TAPS: the most taps per axis pjd_resize_bicubic_taps returns
+BICUBIC_MAX_GAIN = 92681                   # PJD_BICUBIC_MAX_GAIN: the largest sum |q_j| of an axis set_resize_filter accepts
 DT_F16, DT_BF16, DT_F32 = 1, 2, 3         # pjd_batch_set_normalize: IEEE binary16, bfloat16, IEEE binary32 (pjd.h)
 SCAN_PROGRESSIVE = 1
 MAX_KERNELS = 16
@@ -184,6 +187,8 @@ def dev_lib():
         L.pjd_batch_set_resize_filter.argtypes = [vp, i32]
         L.pjd_resize_aa_taps.restype = i32
         L.pjd_resize_aa_taps.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.pjd_resize_bicubic_taps.restype = i32
+        L.pjd_resize_bicubic_taps.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]
         L.pjd_batch_set_resize_window.restype = i32
         L.pjd_batch_set_resize_window.argtypes = [vp, C.POINTER(ResizeWindow)]
         L.pjd_resize_window_check.restype = i32
@@ -437,7 +442,8 @@ class Batch:
 
     def set_resize_filter(self, filter):
         """pjd_batch_set_resize_filter: RESIZE_ANTIALIAS makes the resize the widened triangle filter include/pjd.h specifies bit for
-        bit (torch's antialias=True, Pillow's BILINEAR); RESIZE_BILINEAR is what a batch has without the call.  Once, after
+        bit (torch's antialias=True, Pillow's BILINEAR), RESIZE_BICUBIC the bicubic one (Keys, a = -0.5, widened where an axis shrinks:
+        Pillow's BICUBIC, torch's mode="bicubic" with antialias=True); RESIZE_BILINEAR is what a batch has without the call.  Once, after
         set_resize() and before set_normalize() / bind_output() / upload(); a picture more than 16x its target on an axis at its
         decode size is refused."""
         self.ctx._check(self.L.pjd_batch_set_resize_filter(self._h, int(filter)), "pjd_batch_set_resize_filter")
@@ -699,6 +705,17 @@ def resize_aa_taps(src_n, dst_n, i):
     return first.value, list(q[:count.value])
 
 
+def resize_bicubic_taps(src_n, dst_n, i):
+    """pjd_resize_bicubic_taps (host only): (first, [q ...]) -- the first source sample in the support of target sample i of dst_n over
+    src_n source samples with the bicubic filter, and the SIGNED weights of that sample and the following ones in 1/65536 (they sum to
+    65536; a weight inside the support may be 0); the code the batch's weight table is built with.  ValueError outside 1..65535, for
+    i >= dst_n and for src_n > 16 * dst_n."""
+    first, count, q = C.c_uint32(), C.c_uint32(), (C.c_int32 * BICUBIC_MAX_TAPS)()
+    if not all(0 <= int(v) < 2 ** 32 for v in (src_n, dst_n, i)) or dev_lib().pjd_resize_bicubic_taps(int(src_n), int(dst_n), int(i), C.byref(first), C.byref(count), q) != 0:
+        raise ValueError(f"resize_bicubic_taps({src_n}, {dst_n}, {i}): sizes must be 1..65535, i < dst_n and src_n <= 16 * dst_n")
+    return first.value, list(q[:count.value])
+
+
 def resize_window(w):
     """A ResizeWindow from a ResizeWindow (copied), a dict of its fields, or a tuple (x, y, w, h[, vw, vh, ox, oy, flags]).  ValueError
     for a field outside 32 bits."""
@@ -718,7 +735,7 @@ def resize_window(w):
 
 
 def resize_window_check(sw, sh, tw, th, window, filter=RESIZE_BILINEAR):
-    """pjd_resize_window_check (host only): True where pjd_batch_set_resize_window (and, with RESIZE_ANTIALIAS, set_resize_filter) would
+    """pjd_resize_window_check (host only): True where pjd_batch_set_resize_window (and, with RESIZE_ANTIALIAS or RESIZE_BICUBIC, set_resize_filter) would
     accept `window` (anything resize_window() takes; None: the all-zero record) for a picture of sw x sh at its decode size and a target
     of tw x th; the one implementation of the rules of include/pjd.h."""
     if not all(0 <= int(v) < 2 ** 32 for v in (sw, sh, tw, th)):

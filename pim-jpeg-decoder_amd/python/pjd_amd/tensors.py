@@ -59,7 +59,7 @@ def _torch():
     return torch
 
 
-def _run(ctx, descs, out_format, capacity, offsets, device, resize=None, normalize=None, antialias=False, windows=None):
+def _run(ctx, descs, out_format, capacity, offsets, device, resize=None, normalize=None, antialias=False, windows=None, interpolation="bilinear"):
     """Create, (set the resize, its windows, its filter, the normalisation,) bind to a fresh torch buffer, upload, decode, sync -> (buffer, batch offsets,
     statuses).  The buffer is torch.uint8 whatever the elements are: torch aligns it far beyond an element."""
     torch = _torch()
@@ -68,7 +68,9 @@ def _run(ctx, descs, out_format, capacity, offsets, device, resize=None, normali
             b.set_resize(resize)
             if windows is not None:
                 b.set_resize_window(windows)
-            if antialias:
+            if interpolation == "bicubic":
+                b.set_resize_filter(pjd_amd.RESIZE_BICUBIC)
+            elif antialias:
                 b.set_resize_filter(pjd_amd.RESIZE_ANTIALIAS)
         if normalize is not None:
             b.set_normalize(*normalize)
@@ -211,7 +213,15 @@ def _windowed(descs, size, prescale, crops, flips, resize_short):
     return run, windows
 
 
-def decode_resized_batch_tensor(ctx, descs, size, prescale=True, device=None, antialias=False, crops=None, flips=None, resize_short=None):
+def _interpolation(name):
+    """The `interpolation` keyword of the resizing helpers, checked before anything is created."""
+    if name not in ("bilinear", "bicubic"):
+        raise ValueError(f"interpolation must be \"bilinear\" or \"bicubic\", not {name!r}")
+    return name
+
+
+def decode_resized_batch_tensor(ctx, descs, size, prescale=True, device=None, antialias=False, crops=None, flips=None, resize_short=None,
+                                interpolation="bilinear"):
     """Pictures of ANY sizes -> (uint8 tensor [N, 3, H, W], statuses), size = (H, W): every picture is resampled to H x W inside
     the decode (the bilinear filter of include/pjd.h, pjd_batch_set_resize) and lands at offset i * 3 * H * W of one buffer, so
     the result is one contiguous NCHW tensor with no copy after the decode, complete on return and readable on any torch stream
@@ -227,7 +237,14 @@ def decode_resized_batch_tensor(ctx, descs, size, prescale=True, device=None, an
     Resize(int) + CenterCrop(size) (center_crop_window; ValueError where the resized picture is smaller than size).  All three ride in
     the one resample launch (Batch.set_resize_window); the picture is decoded whole.  With prescale=False the result is exactly the
     filter of include/pjd.h over the crop of the full-size picture; with prescale=True the pre-scale is chosen from the crop's size
-    and the crop becomes window_at_scale's hull of it, an approximation in the same sense as for antialias above."""
+    and the crop becomes window_at_scale's hull of it, an approximation in the same sense as for antialias above.
+    interpolation="bicubic": the bicubic filter of include/pjd.h (RESIZE_BICUBIC: Keys' cubic with a = -0.5 -- Pillow's BICUBIC,
+    torch.nn.functional.interpolate(mode="bicubic", antialias=True), the default of timm's ViT-family transforms -- to within 1
+    level of the float64 filter).  It is always the widened form where an axis shrinks: `antialias` is not consulted.  With
+    prescale=True the box filter still comes first (less to decode), so the result is the bicubic filter over the box-filtered
+    picture; prescale=False is exactly the filter over the full-size picture, for pictures up to 16x the target on each axis.  Any
+    other string than "bilinear" (the default) or "bicubic" raises ValueError before anything is created."""
+    _interpolation(interpolation)
     if len(descs) == 0:
         raise ValueError("decode_resized_batch_tensor: no pictures")
     th, tw = int(size[0]), int(size[1])
@@ -236,7 +253,7 @@ def decode_resized_batch_tensor(ctx, descs, size, prescale=True, device=None, an
     device = torch.device("cuda", ctx.device) if device is None else device
     n, plane = len(descs), 3 * th * tw
     buf, _, st = _run(ctx, run, pjd_amd.OUT_RGB8_PLANAR, n * plane, [i * plane for i in range(n)], device, resize=[(th, tw)] * n,
-                      antialias=antialias, windows=windows)
+                      antialias=antialias, windows=windows, interpolation=interpolation)
     return buf.view(n, 3, th, tw), st
 
 
@@ -253,7 +270,7 @@ def normalize_constants(mean, std):
 
 
 def decode_normalized_batch_tensor(ctx, descs, size, mean, std, dtype=None, channels_last=False, prescale=True, device=None,
-                                   antialias=False, crops=None, flips=None, resize_short=None):
+                                   antialias=False, crops=None, flips=None, resize_short=None, interpolation="bilinear"):
     """Pictures of ANY sizes -> (tensor of `dtype` [N, 3, H, W], statuses), size = (H, W); dtype torch.float16 (the default),
     torch.bfloat16 or torch.float32.  As decode_resized_batch_tensor, and every sample v of channel c leaves the same launch as
     fma(v, scale[c], bias[c]) with the constants of normalize_constants(mean, std), converted once to `dtype` (include/pjd.h,
@@ -263,7 +280,10 @@ def decode_normalized_batch_tensor(ctx, descs, size, mean, std, dtype=None, chan
     readable on any torch stream (module docstring, "Stream order").  antialias=True: the antialiased filter, as in
     decode_resized_batch_tensor -- with prescale=True the result differs from an antialiased resize of the full-size picture (the box
     pre-scale comes first), prescale=False gives exactly that up to the 16x limit.  crops, flips, resize_short: as in
-    decode_resized_batch_tensor."""
+    decode_resized_batch_tensor.  interpolation="bicubic": the bicubic filter (RESIZE_BICUBIC), as there -- `antialias` is not consulted,
+    prescale=True still puts the box filter first, prescale=False is exactly the filter over the full-size picture up to the 16x
+    limit; any other string than "bilinear" or "bicubic" raises ValueError before anything is created."""
+    _interpolation(interpolation)
     if len(descs) == 0:
         raise ValueError("decode_normalized_batch_tensor: no pictures")
     th, tw = int(size[0]), int(size[1])
@@ -278,6 +298,6 @@ def decode_normalized_batch_tensor(ctx, descs, size, mean, std, dtype=None, chan
     run, windows = _windowed(descs, (th, tw), prescale, crops, flips, resize_short)
     n, pic = len(descs), 3 * th * tw * es
     buf, _, st = _run(ctx, run, pjd_amd.OUT_RGB8 if channels_last else pjd_amd.OUT_RGB8_PLANAR, n * pic, [i * pic for i in range(n)], device,
-                      resize=[(th, tw)] * n, normalize=(dt, scale, bias), antialias=antialias, windows=windows)
+                      resize=[(th, tw)] * n, normalize=(dt, scale, bias), antialias=antialias, windows=windows, interpolation=interpolation)
     t = buf.view(dtype)
     return (t.view(n, th, tw, 3).permute(0, 3, 1, 2) if channels_last else t.view(n, 3, th, tw)), st

@@ -1,4 +1,5 @@
-// resize_host.cpp -- the bodies of the resample kernels (pim-jpeg-decoder_amd/csrc/pjd_k_resize_body.h and pjd_k_resize_aa_body.h, with
+// resize_host.cpp -- the bodies of the resample kernels (pim-jpeg-decoder_amd/csrc/pjd_k_resize_body.h and pjd_k_resize_aa_body.h -- the latter
+// once per table-driven filter, FILT --, with
 // the stores of pjd_k_resize_store.h) run on the host, thread by thread, under the sanitizers, each with WIN false and true: indexing,
 // tile search, the vector and the element store paths at every alignment, window and offset indexing, the mirrored tap index, the
 // staged segment of a mirrored tile, all four dword remainders of a segment's first byte in both layouts, the plane stride of a planar
@@ -10,15 +11,16 @@
 // barrier is nothing, and a thread stages the whole row segment for itself (PJD_WIN_STAGE_*) into an "LDS" of exactly the size the
 // host would give the launch, allocated per thread so that AddressSanitizer sees its end.  The 16-bit conversions of the bodies are
 // the host compiler's, so this says nothing about the GPU's (tests/test_gpu_normalize.py does); the expectation makes them bit by bit.
-// Every variant (uint8 / fp16 / bf16 / fp32, planar / interleaved, bilinear / antialiased) writes two sets of pictures, each into one
+// Every variant (uint8 / fp16 / bf16 / fp32, planar / interleaved, bilinear / antialiased / bicubic) writes two sets of pictures, each into one
 // buffer at element-aligned offsets with odd gaps, the buffer itself shifted by 0..3 elements:
-//   - plain: 31 pictures (tile edges, ragged right edges, random sizes; the antialiased body skips those that shrink more than 16x)
+//   - plain: 31 pictures (tile edges, ragged right edges, random sizes; the table-driven body skips those that shrink more than 16x)
 //     through the WIN = false body, and again through the WIN = true body with the identity window: the same bytes;
 //   - windowed: 12 geometries (those of tests/test_gpu_resize_window.py and the four remainders of x) and 10 seeded windows.
 // The source holds every picture back to back with NO padding between them beyond what rounds the buffer to a dword (the kernels
 // stage whole dwords): a read outside a window that mattered would change the result, a read outside the buffer is a sanitizer
 // report.  The expectation is a plain per-pixel loop over the arithmetic of include/pjd.h -- the tap inlines with a shifted index;
-// the bytes between the pictures are compared too.  Prints ALL EQUAL.
+// the bytes between the pictures are compared too.  The bicubic variants run the same body text with FILT = PJD_RESIZE_BICUBIC: signed
+// weights, up to 64 taps an axis (a 16x shrink is among the pictures), results that clamp at both ends on this random source.  Prints ALL EQUAL.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -36,6 +38,8 @@
 struct Dim { uint32_t x; };
 static thread_local Dim threadIdx, blockIdx;
 static inline uint32_t __umul24(uint32_t a, uint32_t b) { return (a & 0xffffff) * (b & 0xffffff); }
+static inline int32_t sext24(int32_t a) { return (int32_t)((uint32_t)a << 8) >> 8; }
+static inline int32_t __mul24(int32_t a, int32_t b) { return (int32_t)(uint32_t)((int64_t)sext24(a) * sext24(b)); }   // the low 32 bits of the product of the low 24
 static inline void __syncthreads() {}
 #include "../pim-jpeg-decoder_amd/csrc/pjd_k_resize_store.h"
 #define __builtin_amdgcn_readfirstlane(x) (x)
@@ -51,7 +55,7 @@ static void thread_bilinear(const uint8_t *src, uint8_t *dst, const PjdDevResize
 #include "../pim-jpeg-decoder_amd/csrc/pjd_k_resize_body.h"
 }
 
-template <bool PLANAR, int DT, bool WIN>
+template <bool PLANAR, int DT, bool WIN, int FILT>
 static void thread_aa(uint32_t *seg, const uint8_t *src, uint8_t *dst, const PjdDevResize *recs, const PjdDevResizeWin *win, const uint32_t *tile_prefix,
                       uint32_t n_images, uint32_t n_tiles, const PjdDevResizeAA *aa, const uint32_t *tab, uint32_t lds_bytes, const NormArgs nz)
 {
@@ -84,15 +88,15 @@ static uint16_t bf16bits(float f) { uint32_t b; memcpy(&b, &f, 4); b += 0x7fffu 
 struct Case { uint32_t sw, sh, tw, th; PjdDevResizeWin w; };
 
 // the tap-major table of one axis, as pjd_batch_set_resize_filter lays it out: dn heads `first | count << 16`, then taps x dn weights
-static uint32_t axis_table(std::vector<uint32_t> &tab, uint32_t sn, uint32_t dn, uint32_t &taps)
+static uint32_t axis_table(std::vector<uint32_t> &tab, int filt, uint32_t sn, uint32_t dn, uint32_t &taps)
 {
     const size_t base = tab.size();
-    tab.resize(base + (size_t)dn * (1u + PJD_AA_MAX_TAPS), 0u);
-    uint32_t w[PJD_AA_MAX_TAPS];
+    tab.resize(base + (size_t)dn * (1u + PJD_BICUBIC_MAX_TAPS), 0u);
+    uint32_t w[PJD_BICUBIC_MAX_TAPS];
     taps = 0;
     for (uint32_t i = 0; i < dn; i++) {
         uint32_t first;
-        const uint32_t cnt = pjd_resize_aa_taps_calc(sn, dn, i, first, w);
+        const uint32_t cnt = filt == PJD_RESIZE_BICUBIC ? pjd_resize_bicubic_taps_calc(sn, dn, i, first, (int32_t *)w) : pjd_resize_aa_taps_calc(sn, dn, i, first, w);
         tab[base + i] = first | (cnt << 16);
         for (uint32_t t = 0; t < cnt; t++) tab[base + (size_t)(t + 1u) * dn + i] = w[t];
         taps = std::max(taps, cnt);
@@ -139,9 +143,10 @@ static std::vector<Case> window_cases(unsigned seed)
     return cases;
 }
 
-template <bool PLANAR, int DT, bool AA>
+template <bool PLANAR, int DT, int FILT>
 static int run(bool windowed, uint32_t misalign_elems, unsigned seed)
 {
+    constexpr bool AA = FILT != PJD_RESIZE_BILINEAR;          // a table-driven filter
     const uint32_t ES = DT == 0 ? 1 : PJD_DT_SIZE(DT);
     const std::vector<Case> cases = windowed ? window_cases(seed) : plain_cases(seed, AA);
     const size_t n = cases.size();
@@ -161,8 +166,8 @@ static int run(bool windowed, uint32_t misalign_elems, unsigned seed)
         dpos += 3ull * c.tw * c.th * ES + ES * (2 * (i % 3) + 1);                     // element-aligned odd gaps
         prefix[i] = t; t += r.col_tiles * ((c.th + PJD_RS_ROWS - 1) / PJD_RS_ROWS);
         if (AA) {
-            aas[i].x_tab = axis_table(tab, c.w.w, c.w.vw, aas[i].x_taps);
-            aas[i].y_tab = axis_table(tab, c.w.h, c.w.vh, aas[i].y_taps);
+            aas[i].x_tab = axis_table(tab, FILT, c.w.w, c.w.vw, aas[i].x_taps);
+            aas[i].y_tab = axis_table(tab, FILT, c.w.h, c.w.vh, aas[i].y_taps);
             for (uint32_t c0 = 0; c0 < c.tw; c0 += PJD_RS_COLS) {                   // the sizing loop of pjd_batch_set_resize_filter
                 uint32_t e0, e1;
                 pjd_resize_win_ends(c.w, c.tw, c0, std::min<uint32_t>(c0 + PJD_RS_COLS, c.tw) - 1u, e0, e1);
@@ -187,7 +192,7 @@ static int run(bool windowed, uint32_t misalign_elems, unsigned seed)
             blockIdx.x = b; threadIdx.x = th;
             if constexpr (AA) {
                 uint32_t *seg = (uint32_t *)malloc(lds ? lds : 4);                   // this thread's "LDS", of the launch's size
-                thread_aa<PLANAR, DT, W>(seg, src, dst, recs.data(), W ? wins.data() : nullptr, prefix.data(), (uint32_t)n, t, aas.data(), tab.data(), lds, nz);
+                thread_aa<PLANAR, DT, W, FILT>(seg, src, dst, recs.data(), W ? wins.data() : nullptr, prefix.data(), (uint32_t)n, t, aas.data(), tab.data(), lds, nz);
                 free(seg);
             } else {
                 thread_bilinear<PLANAR, DT, W>(src, dst, recs.data(), W ? wins.data() : nullptr, prefix.data(), (uint32_t)n, t, nz);
@@ -197,6 +202,7 @@ static int run(bool windowed, uint32_t misalign_elems, unsigned seed)
     };
     uint8_t *dst = windowed ? launch(std::true_type{}) : launch(std::false_type{});
     int bad = 0;
+    uint32_t clamped = FILT == PJD_RESIZE_BICUBIC ? 0u : 3u;   // bicubic: the final clamp is met at both ends
     if (!windowed) {                                         // the identity window through the WIN = true body: the same bytes
         uint8_t *again = launch(std::true_type{});
         if (memcmp(dst, again, dst_bytes) != 0) { printf("  the identity window through the WIN body gives other bytes\n"); bad++; }
@@ -213,7 +219,22 @@ static int run(bool windowed, uint32_t misalign_elems, unsigned seed)
         for (uint32_t y = 0; y < c.th; y++) for (uint32_t x = 0; x < c.tw; x++) for (int ch = 0; ch < 3; ch++) {
             const uint32_t xi = w.ox + ((w.flags & PJD_RW_HFLIP) ? c.tw - 1 - x : x), yi = w.oy + y;
             uint32_t v;
-            if (AA) {
+            if (FILT == PJD_RESIZE_BICUBIC) {
+                uint32_t fx, fy; int32_t qx[PJD_BICUBIC_MAX_TAPS], qy[PJD_BICUBIC_MAX_TAPS];
+                const uint32_t nx = pjd_resize_bicubic_taps_calc(w.w, w.vw, xi, fx, qx), ny = pjd_resize_bicubic_taps_calc(w.h, w.vh, yi, fy, qy);
+                int64_t acc = 0;                             // the expectation in 64 bits: it also says that 32 were enough
+                for (uint32_t b = 0; b < ny; b++) {
+                    int64_t h = 0;
+                    for (uint32_t a = 0; a < nx; a++) h += (int64_t)qx[a] * (int64_t)P(ch, w.y + fy + b, w.x + fx + a);
+                    const int64_t h6 = (h + 512) >> 10;
+                    if (h != (int32_t)h || h6 >= 32768 || h6 < -32768) { printf("the expectation left the bounds of include/pjd.h\n"); exit(2); }
+                    acc += qy[b] * h6;
+                }
+                if (acc + (1 << 21) != (int32_t)(acc + (1 << 21))) { printf("the expectation left 32 bits\n"); exit(2); }
+                const int64_t o = (acc + (1 << 21)) >> 22;
+                clamped |= o < 0 ? 1u : o > 255 ? 2u : 0u;
+                v = (uint32_t)(o < 0 ? 0 : o > 255 ? 255 : o);
+            } else if (AA) {
                 uint32_t fx, fy, qx[PJD_AA_MAX_TAPS], qy[PJD_AA_MAX_TAPS];
                 const uint32_t nx = pjd_resize_aa_taps_calc(w.w, w.vw, xi, fx, qx), ny = pjd_resize_aa_taps_calc(w.h, w.vh, yi, fy, qy);
                 uint32_t acc = 0;
@@ -242,28 +263,29 @@ static int run(bool windowed, uint32_t misalign_elems, unsigned seed)
     for (size_t k = 0; k < dst_bytes; k++) if (dst[k] != want[k]) { if (bad < 4) printf("  mismatch at byte %zu got %02x want %02x\n", k, dst[k], want[k]); bad++; }
     uint32_t rem = windowed ? 0u : 0xfu;                     // the windowed set has a segment at every dword remainder
     for (size_t i = 0; i < n; i++) rem |= 1u << ((recs[i].src_off + (PLANAR ? cases[i].w.x : 3 * cases[i].w.x) + (size_t)cases[i].w.y * recs[i].src_stride) & 3u);
-    printf("%s %s PLANAR=%d DT=%d misalign=%u: %zu pictures, %u tiles, lds %u, remainders %x: %s\n", AA ? "antialias" : "bilinear ", windowed ? "windowed" : "plain   ",
-           (int)PLANAR, DT, misalign_elems, n, t, lds, rem, bad ? "MISMATCH" : "equal, guards intact");
+    printf("%s %s PLANAR=%d DT=%d misalign=%u: %zu pictures, %u tiles, lds %u, remainders %x, clamps %x: %s\n", FILT == PJD_RESIZE_BICUBIC ? "bicubic  " : AA ? "antialias" : "bilinear ", windowed ? "windowed" : "plain   ",
+           (int)PLANAR, DT, misalign_elems, n, t, lds, rem, clamped, bad ? "MISMATCH" : "equal, guards intact");
     free(dst); free(src);
-    return bad != 0 || rem != 0xf;
+    return bad != 0 || rem != 0xf || clamped != 3u;
 }
 
-template <bool AA>
+template <int FILT>
 static int all(bool windowed)
 {
     int rc = 0;
     for (uint32_t mis : {0u, 1u, 2u, 3u}) {
-        rc |= run<true, 0, AA>(windowed, mis, 1); rc |= run<false, 0, AA>(windowed, mis, 2);
-        rc |= run<true, PJD_DT_F16, AA>(windowed, mis, 3); rc |= run<false, PJD_DT_F16, AA>(windowed, mis, 4);
-        rc |= run<true, PJD_DT_BF16, AA>(windowed, mis, 5); rc |= run<false, PJD_DT_BF16, AA>(windowed, mis, 6);
-        rc |= run<true, PJD_DT_F32, AA>(windowed, mis, 7); rc |= run<false, PJD_DT_F32, AA>(windowed, mis, 8);
+        rc |= run<true, 0, FILT>(windowed, mis, 1); rc |= run<false, 0, FILT>(windowed, mis, 2);
+        rc |= run<true, PJD_DT_F16, FILT>(windowed, mis, 3); rc |= run<false, PJD_DT_F16, FILT>(windowed, mis, 4);
+        rc |= run<true, PJD_DT_BF16, FILT>(windowed, mis, 5); rc |= run<false, PJD_DT_BF16, FILT>(windowed, mis, 6);
+        rc |= run<true, PJD_DT_F32, FILT>(windowed, mis, 7); rc |= run<false, PJD_DT_F32, FILT>(windowed, mis, 8);
     }
     return rc;
 }
 
 int main()
 {
-    const int rc = all<false>(false) | all<false>(true) | all<true>(false) | all<true>(true);
+    const int rc = all<PJD_RESIZE_BILINEAR>(false) | all<PJD_RESIZE_BILINEAR>(true) | all<PJD_RESIZE_ANTIALIAS>(false) | all<PJD_RESIZE_ANTIALIAS>(true) |
+                   all<PJD_RESIZE_BICUBIC>(false) | all<PJD_RESIZE_BICUBIC>(true);
     printf(rc ? "FAILED\n" : "ALL EQUAL\n");
     return rc;
 }
