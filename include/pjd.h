@@ -26,6 +26,8 @@
  *                                                       antialiased triangle filter (torch antialias=True, Pillow BILINEAR)
  *   (none: an addition)                                 pjd_batch_set_resize_window + pjd_resize_window_check: that resize from a
  *                                                       window of the picture (RandomResizedCrop, Resize + CenterCrop, flip)
+ *   (none: an addition)                                 pjd_batch_set_orientation: the eight EXIF orientations (mirrors, half turn,
+ *                                                       quarter turns) per picture inside that launch (pjd_scanned_orientation reads the tag)
  *   (none: an addition)                                 pjd_batch_set_normalize + pjd_normalize_value: the samples leave as fp16, bf16
  *                                                       or fp32, v * scale[c] + bias[c], in that launch (the tensor a model takes)
  *
@@ -497,8 +499,8 @@ int  pjd_resize_bicubic_taps(uint32_t src_n, uint32_t dst_n, uint32_t i, uint32_
  * or h > 16*vh.
  * The 16x limit of the antialiased filter is the WINDOW's: a picture past 16x its target whose window is inside is accepted.
  *
- * CALL ORDER.  After pjd_batch_set_resize; before any pjd_batch_set_resize_filter / _set_normalize / _bind_output / _upload /
- * _capture / _decode of the batch; once: PJD_E_STATE otherwise (so a batch that took pjd_batch_set_normalize without a resize
+ * CALL ORDER.  After pjd_batch_set_resize (and pjd_batch_set_orientation, below, where used); before any pjd_batch_set_resize_filter /
+ * _set_normalize / _bind_output / _upload / _capture / _decode of the batch; once: PJD_E_STATE otherwise (so a batch that took pjd_batch_set_normalize without a resize
  * takes no window).  PJD_E_ARG for a null array or a record the check refuses; the batch is then as it was, un-windowed.
  * FROM THEN ON everything pjd_batch_set_resize promises from its "FROM THEN ON" holds unchanged -- sizes and offsets (those of
  * tw x th), every byte of every range written and none outside, the one launch named "resize", part of a captured graph, run again
@@ -517,6 +519,40 @@ typedef struct pjd_resize_window {
 int  pjd_batch_set_resize_window(pjd_batch *b, const pjd_resize_window *win /* n_images */);
 int  pjd_resize_window_check(uint32_t sw, uint32_t sh, uint32_t tw, uint32_t th,
                              const pjd_resize_window *win, int filter);   /* host only, no device needed */
+/* ---- orientation: mirrors, half turn and quarter turns inside the resize ------------------------------------------------------------ *
+ * pjd_batch_set_orientation: picture i of a resized batch is delivered in EXIF orientation orientation[i], 1..8 (tag 0x0112; what
+ * pjd_scanned_orientation of pjd_host.h reads from the file, or any value the caller chooses: RandomVerticalFlip is 4, the quarter
+ * turns of an augmentation 6 and 8).  The permutation happens in the resample launch, on the way out: no oriented copy exists.
+ *
+ * THE ARITHMETIC (normative).  out_w[i] x out_h[i] is picture i's target from pjd_batch_set_resize; that is what is DELIVERED, and
+ * sizes and offsets never change.  The orientation o has the bits (t, v, h):
+ *     o                      1  2  3  4  5  6  7  8
+ *     t (transpose)          0  0  0  0  1  1  1  1
+ *     v (mirror top-bottom)  0  0  1  1  0  0  1  1
+ *     h (mirror left-right)  0  1  1  0  0  1  1  0
+ * Q is the picture the batch would deliver with everything else it has -- window, virtual target, PJD_RW_HFLIP, filter -- to the
+ * target out_w x out_h where t = 0 and to out_h x out_w, the axes swapped, where t = 1.  The delivered picture is
+ *     D = H^h(V^v(T^t(Q)))        transpose first, then the mirrors
+ * so o = 6 is Q turned a quarter clockwise (numpy.rot90(Q, -1)), o = 8 a quarter counter-clockwise (numpy.rot90(Q, 1)), o = 3 the half
+ * turn; the table is PIL.ImageOps.exif_transpose's for all eight values.  pjd_batch_set_normalize applies to D's samples as it does to
+ * Q's.  No new filter arithmetic: the resample happens in the STORED picture's coordinates and its result is permuted.  That differs
+ * from "orient the picture, then resize it" only where a filter's tie-breaking is not mirror-symmetric -- the round-half-up of the
+ * bilinear weight, the correction that goes to the lowest of equal taps -- and stays inside each filter's stated one-level bound,
+ * as PJD_RW_HFLIP does.  A caller who wants the upright picture at its own size passes pjd_batch_set_resize the picture's own
+ * dimensions, swapped for o >= 5: every tap weight is then 0 or 65536, and D is the exact permutation of the decoded picture.
+ *
+ * CALL ORDER.  After pjd_batch_set_resize; before any pjd_batch_set_resize_window / _set_resize_filter / _set_normalize /
+ * _bind_output / _upload / _capture / _decode of the batch; once: PJD_E_STATE otherwise, also when no resize is set.  PJD_E_ARG for a
+ * null array or a value outside 1..8 (pjd_last_error names the picture); the batch is then as it was.
+ * FROM THEN ON, for a picture with t = 1, everything later calls say about "the target" is about Q's target out_h x out_w: the
+ * defaults vw = 0 / vh = 0 of a window, ox + tw <= vw and oy + th <= vh, the 16x limit, the weight tables of (w, vw) and (h, vh).  A
+ * window is given in the stored picture's coordinates, as without an orientation, and its PJD_RW_HFLIP mirrors Q.  Everything
+ * pjd_batch_set_resize promises from its "FROM THEN ON" holds unchanged: pjd_batch_output_size, _offset, _packed_size, bind_output
+ * and its alignment rules, both downloads; every byte of every range written by every decode and none outside; the one launch
+ * named "resize", part of a captured graph, run again after the exact-kernel fallback.  What the call takes (the 40-byte record of
+ * a window per picture) is counted in pjd_batch_info::device_bytes and sent by pjd_batch_upload; an array of all 1 takes nothing
+ * and launches the very kernels the batch launched before.  A BMP batch takes no resize, so it takes no orientation.           */
+int  pjd_batch_set_orientation(pjd_batch *b, const uint8_t *orientation /* n_images, each 1..8 */);
 /* ---- normalised float output ------------------------------------------------------------------------------------------------- *
  * pjd_batch_set_normalize: the pictures of the batch leave the decode as floating-point elements, sample * scale[c] + bias[c] -- what
  * x.float().div(255).sub(mean).div(std).to(dtype) makes of the uint8 tensor, without that tensor ever existing.  The caller passes

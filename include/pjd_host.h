@@ -45,6 +45,18 @@ const char *pjd_scanned_log(const pjd_scanned *s);      /* what the reference wo
 int pjd_scanned_valid(const pjd_scanned *s);
 void pjd_scanned_free(pjd_scanned *s);
 
+/* The EXIF orientation of the file (tag 0x0112), 1..8 -- what pjd_batch_set_orientation of pjd.h takes -- and 1 whenever no valid tag
+ * is found.  THE RULE (normative):
+ *   - the first APP1 segment before SOS whose payload starts with "Exif\0\0" is the one read; other APP1 segments (XMP) are passed
+ *     over, and a later Exif segment is not looked at;
+ *   - its TIFF header: "II" (little-endian) or "MM" (big-endian), the magic 42, the offset of IFD0 (offsets count from the header);
+ *   - in IFD0 only, the entry with tag 0x0112, type SHORT (3), count 1, value 1..8;
+ *   - anything else gives 1: a segment that the file cuts off, an offset or an entry outside the segment, another type or count, a
+ *     value of 0 or above 8, a tag that only IFD1 or the Exif sub-IFD holds.  Every read is bounds-checked against the segment.
+ * Reading the tag changes nothing else: the scanner's accept / reject set, its log and every field of the descriptor are those of
+ * the same file without the segment.  Valid for rejected files too (the tag is read before whatever rejected the file, or is 1). */
+int pjd_scanned_orientation(const pjd_scanned *s);
+
 /* Reference metadata vector u32[276] for this image (decoder_host.cpp:156-178), for callers
  * that drive pjd_exec_dpu_payload.                                                        */
 void pjd_scanned_metadata(const pjd_scanned *s, uint32_t *m276);

@@ -223,12 +223,15 @@ struct pjd_batch {
     bool win_set = false, windowed = false;      // pjd_batch_set_resize_window: called / with a record that is not all zero
     PjdDevResizeWin *h_win = nullptr, *d_win = nullptr;   // then: the windows, defaults resolved, [n_images]: page-locked / HBM
     size_t win_bytes = 0;
+    bool ori_set = false, oriented = false;      // pjd_batch_set_orientation: called / with a value other than 1.  Then the batch is windowed
+                                                 // too (identity windows until pjd_batch_set_resize_window): h_win[i].flags hold PJD_RWI_*,
+                                                 // and h_rs[i].tw / th are those of Q, swapped against rs_w / rs_h where transposed
 
     // the resample launch of this batch, whatever its filter, windowed or not (both launch sites: the decode and the re-run
     // after the fallback)
     void launch_resize(hipStream_t s, bool planar) const
     {
-        pjd_launch_resize(s, PjdResizeLaunch{dev.out, res_out, d_rs, d_rs_prefix, dev.n_images, rs_tiles, planar, norm, windowed ? d_win : nullptr, filter,
+        pjd_launch_resize(s, PjdResizeLaunch{dev.out, res_out, d_rs, d_rs_prefix, dev.n_images, rs_tiles, planar, norm, windowed ? d_win : nullptr, oriented, filter,
                                              (const PjdDevResizeAA *)d_aa, d_aa ? (const uint32_t *)(d_aa + dev.n_images * sizeof(PjdDevResizeAA)) : nullptr, aa_lds});
     }
 };
@@ -1193,6 +1196,62 @@ int pjd_resize_window_check(uint32_t sw, uint32_t sh, uint32_t tw, uint32_t th, 
     return resize_window_fault(sw, sh, tw, th, win, filter) ? PJD_E_ARG : PJD_OK;
 }
 
+int pjd_batch_set_orientation(pjd_batch *b, const uint8_t *orientation)
+{
+    if (!b) return PJD_E_ARG;
+    pjd_ctx *ctx = b->ctx;
+    if (!b->resized) { ctx->err = "set_orientation: no resize is set (pjd_batch_set_resize first)"; return PJD_E_STATE; }
+    if (b->ori_set) { ctx->err = "set_orientation: already set for this batch"; return PJD_E_STATE; }
+    if (b->win_set) { ctx->err = "set_orientation after set_resize_window"; return PJD_E_STATE; }
+    if (b->filter_set) { ctx->err = "set_orientation after set_resize_filter"; return PJD_E_STATE; }
+    if (b->norm.dtype != 0) { ctx->err = "set_orientation after set_normalize"; return PJD_E_STATE; }
+    if (b->bound) { ctx->err = "set_orientation after bind_output"; return PJD_E_STATE; }
+    if (b->uploaded) { ctx->err = "set_orientation after upload"; return PJD_E_STATE; }
+    if (!orientation) { ctx->err = "set_orientation: null orientation array"; return PJD_E_ARG; }
+    const size_t n = b->plan.images.size();
+    bool any = false;
+    uint64_t tiles = 0;
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t o = orientation[i];
+        if (o < 1u || o > 8u) { ctx->err = fmt_image("set_orientation: picture %d: the orientation must be 1..8", (int)i); return PJD_E_ARG; }
+        any = any || o != 1u;
+        // the tiles of Q: its target is the delivered one with the axes swapped where the orientation transposes
+        const bool t = (pjd_orient_flags(o) & PJD_RWI_TRANSPOSE) != 0;
+        const uint32_t tw = t ? b->rs_h[i] : b->rs_w[i], th = t ? b->rs_w[i] : b->rs_h[i];
+        tiles += (uint64_t)((tw + PJD_RS_COLS - 1) / PJD_RS_COLS) * ((th + PJD_RS_ROWS - 1) / PJD_RS_ROWS);
+    }
+    if (tiles >= (1ull << 31)) { ctx->err = "set_orientation: the targets of this batch are too large for one launch"; return PJD_E_ARG; }
+    if (any) {
+        // Identity windows that carry the orientation (pjd_batch_set_resize_window fills in what it is given): the batch runs the
+        // windowed launch's ORI form.  All 1: nothing is taken and the batch keeps the launch it had.
+        hipSetDevice(ctx->device);
+        const size_t bytes = n * sizeof(PjdDevResizeWin);
+        void *h_win = nullptr, *d_win = nullptr;
+        int rc = pool_pin_alloc(ctx, &h_win, bytes, b->pin_blocks);
+        if (rc == PJD_OK) rc = pool_dev_alloc(ctx, &d_win, bytes, b->dev_blocks);
+        if (rc != PJD_OK) return rc;                       // what was taken stays with the batch until it is destroyed
+        b->device_bytes += bytes;
+        b->h_win = (PjdDevResizeWin *)h_win; b->d_win = (PjdDevResizeWin *)d_win; b->win_bytes = bytes;
+        uint32_t *prefix = (uint32_t *)(b->h_rs + n);
+        uint32_t t = 0;
+        for (size_t i = 0; i < n; i++) {
+            PjdDevResize &r = b->h_rs[i];
+            const uint32_t f = pjd_orient_flags(orientation[i]);
+            if (f & PJD_RWI_TRANSPOSE) { r.tw = b->rs_h[i]; r.th = b->rs_w[i]; }
+            r.col_tiles = (r.tw + PJD_RS_COLS - 1) / PJD_RS_COLS;
+            prefix[i] = t;
+            t += r.col_tiles * ((r.th + PJD_RS_ROWS - 1) / PJD_RS_ROWS);
+            b->h_win[i] = pjd_resize_win_identity(r);
+            b->h_win[i].flags = f;
+        }
+        prefix[n] = t;
+        b->rs_tiles = t;
+        b->windowed = b->oriented = true;
+    }
+    b->ori_set = true;
+    return PJD_OK;
+}
+
 int pjd_batch_set_resize_window(pjd_batch *b, const pjd_resize_window *win)
 {
     if (!b) return PJD_E_ARG;
@@ -1216,19 +1275,24 @@ int pjd_batch_set_resize_window(pjd_batch *b, const pjd_resize_window *win)
         any = any || w.x || w.y || w.w || w.h || w.vw || w.vh || w.ox || w.oy || w.flags;
     }
     if (any) {
-        // the records with every default resolved, as the kernels read them; all zero: the batch keeps the launch it had
-        hipSetDevice(ctx->device);
-        const size_t bytes = n * sizeof(PjdDevResizeWin);
-        void *h_win = nullptr, *d_win = nullptr;
-        int rc = pool_pin_alloc(ctx, &h_win, bytes, b->pin_blocks);
-        if (rc == PJD_OK) rc = pool_dev_alloc(ctx, &d_win, bytes, b->dev_blocks);
-        if (rc != PJD_OK) return rc;                       // what was taken stays with the batch until it is destroyed
-        b->device_bytes += bytes;
-        b->h_win = (PjdDevResizeWin *)h_win; b->d_win = (PjdDevResizeWin *)d_win; b->win_bytes = bytes;
+        // the records with every default resolved, as the kernels read them; all zero: the batch keeps the launch it had.  An oriented
+        // batch (pjd_batch_set_orientation) has the records already: r.tw and r.th are Q's there, and the window's mirror composes
+        // with the orientation's tap mirror by exclusive-or
+        if (!b->oriented) {
+            hipSetDevice(ctx->device);
+            const size_t bytes = n * sizeof(PjdDevResizeWin);
+            void *h_win = nullptr, *d_win = nullptr;
+            int rc = pool_pin_alloc(ctx, &h_win, bytes, b->pin_blocks);
+            if (rc == PJD_OK) rc = pool_dev_alloc(ctx, &d_win, bytes, b->dev_blocks);
+            if (rc != PJD_OK) return rc;                   // what was taken stays with the batch until it is destroyed
+            b->device_bytes += bytes;
+            b->h_win = (PjdDevResizeWin *)h_win; b->d_win = (PjdDevResizeWin *)d_win; b->win_bytes = bytes;
+        }
         for (size_t i = 0; i < n; i++) {
             const PjdDevResize &r = b->h_rs[i];
             const pjd_resize_window &w = win[i];
-            b->h_win[i] = PjdDevResizeWin{w.x, w.y, w.w ? w.w : r.sw, w.h ? w.h : r.sh, w.vw ? w.vw : r.tw, w.vh ? w.vh : r.th, w.ox, w.oy, w.flags, 0u};
+            const uint32_t ori = b->oriented ? b->h_win[i].flags : 0u;
+            b->h_win[i] = PjdDevResizeWin{w.x, w.y, w.w ? w.w : r.sw, w.h ? w.h : r.sh, w.vw ? w.vw : r.tw, w.vh ? w.vh : r.th, w.ox, w.oy, w.flags ^ ori, 0u};
         }
         b->windowed = true;
     }

@@ -473,9 +473,32 @@ struct PjdDevResizeWin {
     uint32_t x, y, w, h;
     uint32_t vw, vh;
     uint32_t ox, oy;
-    uint32_t flags;                    // PJD_RW_HFLIP
+    uint32_t flags;                    // PJD_RW_HFLIP; with an orientation (below) PJD_RWI_*
     uint32_t pad_;
 };
+
+// ---- orientation (pjd_batch_set_orientation; the arithmetic is normative: include/pjd.h) ----------------------------------------
+// D = H^h(V^v(T^t(Q))), Q the picture the resample computes (tw x th of PjdDevResize, which for t = 1 is the delivered picture's
+// height x width).  The kernels built with ORI read it from the flags of the picture's window record, already resolved into what
+// they do (pjd_orient_flags): bit 0 mirrors the column TAP index (the bit PJD_RW_HFLIP has: the two compose by exclusive-or),
+// PJD_RWI_YMIRROR mirrors the position at which a row of Q is stored, PJD_RWI_TRANSPOSE stores Q's columns as D's rows.
+//   t = 0:  D[i][j] = Q[v ? th-1-i : i][h ? tw-1-j : j]      -> tap mirror h, store mirror v
+//   t = 1:  D[i][j] = Q[h ? th-1-j : j][v ? tw-1-i : i]      -> tap mirror v, store mirror h (D has tw rows of th samples)
+#define PJD_RWI_XMIRROR   1u
+#define PJD_RWI_YMIRROR   2u
+#define PJD_RWI_TRANSPOSE 4u
+// the bits (t, v, h) of an EXIF orientation 1..8 (the table of include/pjd.h): t << 2 | v << 1 | h
+static inline uint32_t pjd_orient_tvh(uint32_t o)
+{
+    static const uint8_t tvh[8] = {0, 1, 3, 2, 4, 5, 7, 6};
+    return tvh[(o - 1u) & 7u];
+}
+// ... and the flags the kernels read for it (to be combined with the window's PJD_RW_HFLIP by exclusive-or)
+static inline uint32_t pjd_orient_flags(uint32_t o)
+{
+    const uint32_t b = pjd_orient_tvh(o), t = b >> 2, v = (b >> 1) & 1u, h = b & 1u;
+    return t ? PJD_RWI_TRANSPOSE | (v ? PJD_RWI_XMIRROR : 0u) | (h ? PJD_RWI_YMIRROR : 0u) : (h ? PJD_RWI_XMIRROR : 0u) | (v ? PJD_RWI_YMIRROR : 0u);
+}
 
 // the window of a picture that has none: all of it, to exactly its target.  A plain launch is the windowed one with this window (the
 // kernel bodies fold it away at compile time; the host sizes the LDS of a batch without windows with it)

@@ -40,6 +40,12 @@
 // its own: the taps are the same functions and tables with a shifted index, read from a per-picture record of its own
 // (PjdDevResizeWin) beside PjdDevResize.  The gather and the table-driven filters are ONE body text each (pjd_k_resize_body.h, pjd_k_resize_aa_body.h) with a
 // compile-time WIN: a batch without windows runs kernels built with the identity window, which are the kernels it ran before.
+//
+// Orientation (pjd_batch_set_orientation): the eight EXIF orientations, per picture, in that launch.  No arithmetic of its own either: the
+// resample happens in the stored picture's coordinates and its result is permuted on the way out -- the left-right mirror is the
+// tap mirror of the windows, the top-bottom one a mirrored store row, the transpose a second form of the epilogue (store_cols of
+// pjd_k_resize_store.h) that stores a lane's eight rows of one column as eight adjacent samples.  The same bodies with a compile-time
+// ORI, in kernels of their own (pjd_k_resize_ori, pjd_k_resize_ori_tab).
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -57,7 +63,7 @@ pjd_k_resize(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, const P
              const uint32_t *__restrict__ tile_prefix, uint32_t n_images, uint32_t n_tiles)
 {
     constexpr int DT = 0;
-    constexpr bool WIN = false;
+    constexpr bool WIN = false, ORI = false;
     const PjdDevResizeWin *const win = nullptr;
     const NormArgs nz{};
 #include "pjd_k_resize_body.h"
@@ -68,7 +74,7 @@ __global__ void __launch_bounds__(64 * PJD_RS_WAVES)
 pjd_k_resize_norm(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, const PjdDevResize *__restrict__ recs,
                   const uint32_t *__restrict__ tile_prefix, uint32_t n_images, uint32_t n_tiles, const NormArgs nz)
 {
-    constexpr bool WIN = false;
+    constexpr bool WIN = false, ORI = false;
     const PjdDevResizeWin *const win = nullptr;
 #include "pjd_k_resize_body.h"
 }
@@ -79,7 +85,7 @@ pjd_k_resize_win(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, con
                  const PjdDevResizeWin *__restrict__ win, const uint32_t *__restrict__ tile_prefix, uint32_t n_images, uint32_t n_tiles,
                  const NormArgs nz)
 {
-    constexpr bool WIN = true;
+    constexpr bool WIN = true, ORI = false;
 #include "pjd_k_resize_body.h"
 }
 
@@ -90,7 +96,7 @@ pjd_k_resize_aa(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, cons
                 const uint32_t *__restrict__ tab, uint32_t lds_bytes, const NormArgs nz)
 {
     extern __shared__ uint32_t seg[];                      // one source row's segment (three plane segments where PLANAR)
-    constexpr bool WIN = false;
+    constexpr bool WIN = false, ORI = false;
     constexpr int FILT = PJD_RESIZE_ANTIALIAS;
     const PjdDevResizeWin *const win = nullptr;
 #include "pjd_k_resize_aa_body.h"
@@ -103,7 +109,7 @@ pjd_k_resize_win_aa(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, 
                     const PjdDevResizeAA *__restrict__ aa, const uint32_t *__restrict__ tab, uint32_t lds_bytes, const NormArgs nz)
 {
     extern __shared__ uint32_t seg[];
-    constexpr bool WIN = true;
+    constexpr bool WIN = true, ORI = false;
     constexpr int FILT = PJD_RESIZE_ANTIALIAS;
 #include "pjd_k_resize_aa_body.h"
 }
@@ -116,7 +122,7 @@ pjd_k_resize_cubic(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, c
                    const uint32_t *__restrict__ tab, uint32_t lds_bytes, const NormArgs nz)
 {
     extern __shared__ uint32_t seg[];
-    constexpr bool WIN = false;
+    constexpr bool WIN = false, ORI = false;
     constexpr int FILT = PJD_RESIZE_BICUBIC;
     const PjdDevResizeWin *const win = nullptr;
 #include "pjd_k_resize_aa_body.h"
@@ -129,8 +135,32 @@ pjd_k_resize_win_cubic(const uint8_t *__restrict__ src, uint8_t *__restrict__ ds
                        const PjdDevResizeAA *__restrict__ aa, const uint32_t *__restrict__ tab, uint32_t lds_bytes, const NormArgs nz)
 {
     extern __shared__ uint32_t seg[];
-    constexpr bool WIN = true;
+    constexpr bool WIN = true, ORI = false;
     constexpr int FILT = PJD_RESIZE_BICUBIC;
+#include "pjd_k_resize_aa_body.h"
+}
+
+// orientation (pjd_batch_set_orientation): the windowed kernels again, with the store side that reads the picture's orientation
+// (PJD_RWI_* in the flags of its window record).  Kernels of their own and not a run-time branch of the windowed ones: a batch
+// without an orientation launches exactly what it launched before (profiles/orientation.md).
+template <bool PLANAR, int DT>
+__global__ void __launch_bounds__(64 * PJD_RS_WAVES)
+pjd_k_resize_ori(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, const PjdDevResize *__restrict__ recs,
+                 const PjdDevResizeWin *__restrict__ win, const uint32_t *__restrict__ tile_prefix, uint32_t n_images, uint32_t n_tiles,
+                 const NormArgs nz)
+{
+    constexpr bool WIN = true, ORI = true;
+#include "pjd_k_resize_body.h"
+}
+
+template <bool PLANAR, int DT, int FILT>
+__global__ void __launch_bounds__(64)
+pjd_k_resize_ori_tab(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, const PjdDevResize *__restrict__ recs,
+                     const PjdDevResizeWin *__restrict__ win, const uint32_t *__restrict__ tile_prefix, uint32_t n_images, uint32_t n_tiles,
+                     const PjdDevResizeAA *__restrict__ aa, const uint32_t *__restrict__ tab, uint32_t lds_bytes, const NormArgs nz)
+{
+    extern __shared__ uint32_t seg[];
+    constexpr bool WIN = true, ORI = true;
 #include "pjd_k_resize_aa_body.h"
 }
 
@@ -162,7 +192,13 @@ void pjd_launch_resize(hipStream_t s, const PjdResizeLaunch &a)
     for_layout_and_dtype(a.planar, a.norm.dtype, [&](auto P, auto D) {
         constexpr bool PL = decltype(P)::value;
         constexpr int DT = decltype(D)::value;
-        if (a.filter == PJD_RESIZE_BICUBIC && a.win)
+        if (a.oriented && a.filter == PJD_RESIZE_BICUBIC)
+            hipLaunchKernelGGL((pjd_k_resize_ori_tab<PL, DT, PJD_RESIZE_BICUBIC>), grid, block, a.lds_bytes, s, a.src, a.dst, a.recs, a.win, a.tile_prefix, a.n_images, a.n_tiles, a.aa, a.tab, a.lds_bytes, nz);
+        else if (a.oriented && tabled)
+            hipLaunchKernelGGL((pjd_k_resize_ori_tab<PL, DT, PJD_RESIZE_ANTIALIAS>), grid, block, a.lds_bytes, s, a.src, a.dst, a.recs, a.win, a.tile_prefix, a.n_images, a.n_tiles, a.aa, a.tab, a.lds_bytes, nz);
+        else if (a.oriented)
+            hipLaunchKernelGGL((pjd_k_resize_ori<PL, DT>), grid, block, 0, s, a.src, a.dst, a.recs, a.win, a.tile_prefix, a.n_images, a.n_tiles, nz);
+        else if (a.filter == PJD_RESIZE_BICUBIC && a.win)
             hipLaunchKernelGGL((pjd_k_resize_win_cubic<PL, DT>), grid, block, a.lds_bytes, s, a.src, a.dst, a.recs, a.win, a.tile_prefix, a.n_images, a.n_tiles, a.aa, a.tab, a.lds_bytes, nz);
         else if (a.filter == PJD_RESIZE_BICUBIC)
             hipLaunchKernelGGL((pjd_k_resize_cubic<PL, DT>), grid, block, a.lds_bytes, s, a.src, a.dst, a.recs, a.tile_prefix, a.n_images, a.n_tiles, a.aa, a.tab, a.lds_bytes, nz);

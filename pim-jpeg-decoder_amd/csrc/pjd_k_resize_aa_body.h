@@ -15,8 +15,8 @@
 // No lane leaves before the last barrier; lanes right of the picture compute its last column and store nothing.
 // A textual include, so that tools/resize_host.cpp runs this very text on the host; PJD_WIN_STAGE_FIRST / _STEP say which dwords of a
 // segment this thread stages (its own of the wave's 64 here; all of them where a thread runs alone).
-// In scope: PLANAR, DT, WIN, FILT (compile-time constants), seg (LDS), src, dst, recs, win (read only where WIN), tile_prefix, n_images,
-// n_tiles, aa, tab, lds_bytes, nz; store_row.
+// In scope: PLANAR, DT, WIN, ORI (implies WIN), FILT (compile-time constants), seg (LDS), src, dst, recs, win (read only where WIN), tile_prefix, n_images,
+// n_tiles, aa, tab, lds_bytes, nz; store_row and store_cols.
 #ifndef PJD_WIN_STAGE_FIRST
 #define PJD_WIN_STAGE_FIRST lane
 #define PJD_WIN_STAGE_STEP  64u
@@ -142,6 +142,21 @@
         }
     }
 
+    // With ORI (pjd_batch_set_orientation) the picture's flags say where the rows go: a transposed picture's leave as columns
+    // (store_cols), another one's at their own place or its mirror image.  The mirror is in the STORE row: the span ys..ye above
+    // assumes that the tile's taps ascend with its rows.
+    if constexpr (ORI) {
+        if (w.flags & PJD_RWI_TRANSPOSE) {                 // uniform
+#pragma unroll
+            for (int k = 0; k < PJD_RS_ROWS; k++)
+#pragma unroll
+                for (int c = 0; c < 3; c++)
+#pragma unroll
+                    for (int q = 0; q < PJD_RS_PX; q++) acc[k][c][q] = tap_out<FILT>(acc[k][c][q]);
+            store_cols<PLANAR, DT>(acc, dp, row0, r.th - row0 < PJD_RS_ROWS ? r.th - row0 : PJD_RS_ROWS, col0, n_px, (w.flags & PJD_RWI_YMIRROR) != 0, r.th, dst_plane, nz);
+            return;
+        }
+    }
 #pragma unroll
     for (int k = 0; k < PJD_RS_ROWS; k++) {
         if (row0 + k >= r.th) break;                       // uniform
@@ -150,5 +165,5 @@
         for (int c = 0; c < 3; c++)
 #pragma unroll
             for (int q = 0; q < PJD_RS_PX; q++) px[c][q] = tap_out<FILT>(acc[k][c][q]);
-        store_row<PLANAR, DT>(px, dp, row0 + k, col0, n_px, dst_plane, dst_stride, nz);
+        store_row<PLANAR, DT>(px, dp, ORI && (w.flags & PJD_RWI_YMIRROR) ? r.th - 1u - (row0 + k) : row0 + k, col0, n_px, dst_plane, dst_stride, nz);
     }

@@ -10,8 +10,10 @@
 // A textual include and not a function the kernels call: the uint8 kernels then compile to the instructions they had before the float
 // variants existed (profiles/normalized_output.md), which an inlined function did not give; and tools/resize_host.cpp runs this very
 // text on the host.
-// In scope: PLANAR, DT, WIN (compile-time constants), src, dst, recs, win (read only where WIN), tile_prefix, n_images, n_tiles, nz
-// (NormArgs; read only where DT != 0; r.dst_off stays a byte offset); lerp8 and store_row.
+// With ORI (which implies WIN) the store side reads the orientation of pjd_batch_set_orientation from the window's flags (PJD_RWI_* of
+// pjd_internal.h); the read side does not know of it: the tap mirror is the bit PJD_RW_HFLIP has.
+// In scope: PLANAR, DT, WIN, ORI (compile-time constants), src, dst, recs, win (read only where WIN), tile_prefix, n_images, n_tiles, nz
+// (NormArgs; read only where DT != 0; r.dst_off stays a byte offset); lerp8, store_row and store_cols.
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t tile = __builtin_amdgcn_readfirstlane(blockIdx.x * PJD_RS_WAVES + (threadIdx.x >> 6));
     if (tile >= n_tiles) return;
@@ -56,6 +58,7 @@
     const uint64_t dst_plane = PLANAR ? (uint64_t)r.tw * r.th : 1u;
     const uint32_t dst_stride = PLANAR ? r.tw : 3u * r.tw;
 
+    uint32_t kept[PJD_RS_ROWS][3][PJD_RS_PX] = {};         // ORI, a transposed picture: the rows of the tile (rows below the picture: 0, never stored); unused otherwise
 #pragma unroll
     for (int k = 0; k < PJD_RS_ROWS; k++) {
         const uint32_t row = row0 + k;
@@ -76,9 +79,24 @@
         // include it here, the windowed ones (and the antialiased body) call it as store_row.  The split is for the compiler's sake
         // alone: at -O3 either swap changes the instructions of all eight kernels of the side swapped (profiles/resize_unified.md), and
         // the two forms have not been timed against each other on a device.  Whoever has those timings can drop it.
-        if constexpr (WIN) {
+        // With ORI (pjd_batch_set_orientation) the picture's flags say where the row goes: to its own place or its mirror image, or --
+        // transposed -- nowhere yet: the tile keeps its rows, and they leave as columns behind the loop (store_cols).
+        if constexpr (ORI) {
+            if (w.flags & PJD_RWI_TRANSPOSE) {             // uniform
+#pragma unroll
+                for (int c = 0; c < 3; c++)
+#pragma unroll
+                    for (int q = 0; q < PJD_RS_PX; q++) kept[k][c][q] = px[c][q];
+            } else {
+                store_row<PLANAR, DT>(px, dp, (w.flags & PJD_RWI_YMIRROR) ? r.th - 1u - row : row, col0, n_px, dst_plane, dst_stride, nz);
+            }
+        } else if constexpr (WIN) {
             store_row<PLANAR, DT>(px, dp, row, col0, n_px, dst_plane, dst_stride, nz);
         } else {
 #include "pjd_k_resize_store_body.h"
         }
+    }
+    if constexpr (ORI) {
+        if (w.flags & PJD_RWI_TRANSPOSE)
+            store_cols<PLANAR, DT>(kept, dp, row0, r.th - row0 < PJD_RS_ROWS ? r.th - row0 : PJD_RS_ROWS, col0, n_px, (w.flags & PJD_RWI_YMIRROR) != 0, r.th, dst_plane, nz);
     }

@@ -82,6 +82,7 @@ struct PjdResizeLaunch {
     bool planar;
     PjdNormalize norm;
     const PjdDevResizeWin *win;
+    bool oriented;                       // pjd_batch_set_orientation: win is set, and its flags hold PJD_RWI_* (the ORI kernels)
     int filter;
     const PjdDevResizeAA *aa;
     const uint32_t *tab;

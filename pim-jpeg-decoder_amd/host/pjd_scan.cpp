@@ -59,6 +59,9 @@ struct pjd_scanned {
     uint8_t last_ss = 0, last_se = 63, last_ah = 0, last_al = 0, last_ncs = 0, last_comp[3] = {0, 0, 0};
     std::vector<pjd_scan_desc> scans;
     std::vector<std::vector<uint8_t>> scan_ecs;
+    // EXIF orientation (pjd_scanned_orientation): 1..8, from the first Exif APP1 segment before SOS; nothing else of the scan knows of it
+    uint8_t orientation = 1;
+    bool exif_seen = false;
 
     void say(const char *fmt, ...)
     {
@@ -226,6 +229,45 @@ void skip_segment(Bytes &in)
     in.pos += cnt;
 }
 
+// The orientation tag of an Exif APP1 segment (the rule of include/pjd_host.h): `seg` is the segment's payload, the n bytes behind its
+// length field, all of them inside the file.  1..8, or 1 for anything but a well-formed tag.  Every read is checked against n.
+uint8_t exif_orientation(const uint8_t *seg, uint64_t n)
+{
+    const uint8_t *t = seg + 6;                               // the TIFF header: offsets count from here
+    const uint64_t tn = n - 6;                                // the caller has seen "Exif\0\0"
+    if (tn < 8) return 1;
+    const bool le = t[0] == 'I' && t[1] == 'I';
+    if (!le && !(t[0] == 'M' && t[1] == 'M')) return 1;
+    auto u16 = [&](uint64_t o) -> uint32_t { return le ? (uint32_t)t[o] | (uint32_t)t[o + 1] << 8 : (uint32_t)t[o] << 8 | (uint32_t)t[o + 1]; };
+    auto u32 = [&](uint64_t o) -> uint32_t { return le ? u16(o) | u16(o + 2) << 16 : u16(o) << 16 | u16(o + 2); };
+    if (u16(2) != 42) return 1;
+    const uint64_t ifd = u32(4);
+    if (ifd > tn || tn - ifd < 2) return 1;                   // the entry count
+    const uint64_t count = u16(ifd);
+    for (uint64_t k = 0; k < count; k++) {
+        const uint64_t e = ifd + 2 + 12 * k;
+        if (e > tn || tn - e < 12) return 1;                  // an entry that is cut off: no valid tag
+        if (u16(e) != 0x0112) continue;
+        if (u16(e + 2) != 3 || u32(e + 4) != 1) return 1;     // SHORT, count 1: the value is in the first two bytes of the value field
+        const uint32_t v = u16(e + 8);
+        return v >= 1 && v <= 8 ? (uint8_t)v : 1;
+    }
+    return 1;
+}
+
+// An APP1 segment at in.pos (its length field): where it is the first Exif one and lies inside the file, its orientation is kept.
+// Reads through a copy of nothing but pointers: `in` is not touched, the segment is skipped by the caller as every APPn is.
+void note_exif(const Bytes &in, pjd_scanned &s)
+{
+    if (s.exif_seen || in.bad || in.n - in.pos < 2) return;
+    const uint64_t len = (uint64_t)in.p[in.pos] << 8 | in.p[in.pos + 1];
+    if (len < 8 || len > in.n - in.pos) return;               // shorter than the identifier, or cut off by the end of the file
+    const uint8_t *seg = in.p + in.pos + 2;
+    if (std::memcmp(seg, "Exif\0\0", 6) != 0) return;         // another APP1 (XMP): passed over
+    s.exif_seen = true;
+    s.orientation = exif_orientation(seg, len - 2);
+}
+
 // Bitstream buffers of freed pjd_scanned objects, kept for the next scans (at most 512 MiB): a batcher scans and frees
 // ~100 KB per picture around the clock, and handing that to malloc/free makes every scan fault fresh pages in and ends
 // a run with the allocator returning gigabytes to the system (100 ms at the end of a 16-batch run, profiles/r02_pcie.md).
@@ -388,8 +430,10 @@ void scan_all(const uint8_t *data, uint64_t len, pjd_scanned &s)
             d.restart_interval = in.be16();
             if (l - 4 != 0) s.reject(": Error - DRI invalid\n");
         }
-        else if ((cur >= 0xE0 && cur <= 0xEF) || cur == 0xFE || (cur >= 0xF0 && cur <= 0xFD) || cur == 0xDC || cur == 0xDE || cur == 0xDF)
+        else if ((cur >= 0xE0 && cur <= 0xEF) || cur == 0xFE || (cur >= 0xF0 && cur <= 0xFD) || cur == 0xDC || cur == 0xDE || cur == 0xDF) {
+            if (cur == 0xE1) note_exif(in, s);
             skip_segment(in);
+        }
         else if (cur == 0x01) { /* TEM */ }
         else if (cur == 0xFF) { cur = (uint8_t)in.get(); continue; }
         else s.say(": Error - Unknown marker: 0x%x\n", (unsigned)cur);
@@ -452,6 +496,7 @@ int pjd_scan_file_ex(const char *path, uint32_t options, pjd_scanned **out)
 const pjd_image_desc *pjd_scanned_desc(const pjd_scanned *s) { return &s->d; }
 const char *pjd_scanned_log(const pjd_scanned *s) { return s->log.c_str(); }
 int pjd_scanned_valid(const pjd_scanned *s) { return s->valid ? 1 : 0; }
+int pjd_scanned_orientation(const pjd_scanned *s) { return s->orientation; }
 void pjd_scanned_free(pjd_scanned *s)
 {
     if (!s) return;

@@ -129,6 +129,8 @@ def host_lib():
         L.pjd_scanned_log.argtypes = [C.c_void_p]
         L.pjd_scanned_valid.restype = C.c_int
         L.pjd_scanned_valid.argtypes = [C.c_void_p]
+        L.pjd_scanned_orientation.restype = C.c_int
+        L.pjd_scanned_orientation.argtypes = [C.c_void_p]
         L.pjd_scanned_free.argtypes = [C.c_void_p]
         L.pjd_scanned_metadata.argtypes = [C.c_void_p, C.c_void_p]
         L.pjd_rgb_to_bmp.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
@@ -191,6 +193,8 @@ def dev_lib():
         L.pjd_resize_bicubic_taps.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_int32)]
         L.pjd_batch_set_resize_window.restype = i32
         L.pjd_batch_set_resize_window.argtypes = [vp, C.POINTER(ResizeWindow)]
+        L.pjd_batch_set_orientation.restype = i32
+        L.pjd_batch_set_orientation.argtypes = [vp, C.POINTER(C.c_uint8)]
         L.pjd_resize_window_check.restype = i32
         L.pjd_resize_window_check.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(ResizeWindow), i32]
         L.pjd_batch_set_normalize.restype = i32
@@ -252,6 +256,7 @@ class Scanned:
         self.valid = bool(L.pjd_scanned_valid(h))
         self.log = L.pjd_scanned_log(h).decode()
         self.desc = L.pjd_scanned_desc(h).contents
+        self.orientation = int(L.pjd_scanned_orientation(h))    # the EXIF orientation tag, 1..8; 1 without a valid one (include/pjd_host.h)
 
     def metadata(self):
         m = np.zeros(276, np.uint32)
@@ -426,6 +431,20 @@ class Batch:
         hs = (C.c_uint32 * max(self.n, 1))(*[h for h, _ in sizes])
         self.ctx._check(self.L.pjd_batch_set_resize(self._h, ws, hs), "pjd_batch_set_resize")
         self._resize = sizes
+
+    def set_orientation(self, orientations):
+        """pjd_batch_set_orientation: picture i is delivered in EXIF orientation orientations[i] (1..8; Scanned.orientation, or a value of
+        the caller's: 4 is a vertical flip, 6 and 8 the quarter turns) -- D = H^h(V^v(T^t(Q))) of include/pjd.h, inside the resample
+        launch.  The sizes of set_resize() are those of the DELIVERED pictures; for 5..8 the resample's own target is (w, h), and that
+        is what later windows speak about.  Once, after set_resize() and before set_resize_window() / set_resize_filter() /
+        set_normalize() / bind_output() / upload()."""
+        if len(orientations) != self.n:
+            raise ValueError("set_orientation: one orientation per picture")
+        vals = [int(o) for o in orientations]
+        if any(not 0 <= o <= 255 for o in vals):
+            raise ValueError("set_orientation: orientations are 1..8")
+        arr = (C.c_uint8 * max(self.n, 1))(*vals)
+        self.ctx._check(self.L.pjd_batch_set_orientation(self._h, arr), "pjd_batch_set_orientation")
 
     def set_resize_window(self, windows):
         """pjd_batch_set_resize_window: picture i is resampled from a window of the decoded picture to a window of a virtual target,

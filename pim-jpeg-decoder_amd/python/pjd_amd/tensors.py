@@ -3,7 +3,8 @@
 The batch is bound (Batch.bind_output, pjd_batch_bind_output of include/pjd.h) to ONE torch.uint8 buffer this module allocates
 on the context's device; the back end writes the pictures straight into it -- planar R, G, B (OUT_RGB8_PLANAR, "CHW") by
 default -- and the results are views of that buffer.  No native code of its own.  torch is imported inside the functions that
-need it: uniform_output_shape(), pick_scale_flags(), normalize_constants(), center_crop_window() and window_at_scale() are pure.
+need it: uniform_output_shape(), pick_scale_flags(), normalize_constants(), center_crop_window(), window_at_scale(), orient_hw(),
+orient_then_hflip() and crop_to_stored() are pure.
 
 Pictures of different sizes become ONE [N, 3, H, W] tensor with decode_resized_batch_tensor: the library resamples every picture to
 H x W inside the decode (Batch.set_resize, pjd_batch_set_resize), after the box pre-scale pick_scale_flags chooses.
@@ -11,6 +12,11 @@ H x W inside the decode (Batch.set_resize, pjd_batch_set_resize), after the box 
 Crops and flips ride in that resample (Batch.set_resize_window, pjd_batch_set_resize_window): crops= takes what
 RandomResizedCrop.get_params returns, flips= mirrors, resize_short= is Resize(int) + CenterCrop(size).  Every picture is still decoded
 whole; the window costs no launch and no uint8 tensor.
+
+Orientation rides there too (Batch.set_orientation, pjd_batch_set_orientation): orientations= takes the EXIF orientation of every
+picture (Scanned.orientation) and the pictures come out upright -- what torchvision.io.decode_jpeg(apply_exif_orientation=True) and
+PIL.ImageOps.exif_transpose give -- with crops=, flips= and resize_short= speaking about the UPRIGHT picture.  No transpose / flip +
+.contiguous() pass over the finished tensor.
 
 The tensor a model takes -- fp16, bf16 or fp32, (x / 255 - mean) / std -- comes out of the same launch with
 decode_normalized_batch_tensor (Batch.set_normalize, pjd_batch_set_normalize): no uint8 tensor, no elementwise kernels after it.
@@ -59,13 +65,16 @@ def _torch():
     return torch
 
 
-def _run(ctx, descs, out_format, capacity, offsets, device, resize=None, normalize=None, antialias=False, windows=None, interpolation="bilinear"):
-    """Create, (set the resize, its windows, its filter, the normalisation,) bind to a fresh torch buffer, upload, decode, sync -> (buffer, batch offsets,
+def _run(ctx, descs, out_format, capacity, offsets, device, resize=None, normalize=None, antialias=False, windows=None, interpolation="bilinear",
+         orientations=None):
+    """Create, (set the resize, its orientations, its windows, its filter, the normalisation,) bind to a fresh torch buffer, upload, decode, sync -> (buffer, batch offsets,
     statuses).  The buffer is torch.uint8 whatever the elements are: torch aligns it far beyond an element."""
     torch = _torch()
     with ctx.batch(descs, out_format) as b:
         if resize is not None:
             b.set_resize(resize)
+            if orientations is not None:
+                b.set_orientation(orientations)
             if windows is not None:
                 b.set_resize_window(windows)
             if interpolation == "bicubic":
@@ -87,16 +96,24 @@ def _run(ctx, descs, out_format, capacity, offsets, device, resize=None, normali
     return buf, offs, st
 
 
-def decode_to_tensors(ctx, descs, planar=True, device=None):
+def decode_to_tensors(ctx, descs, planar=True, device=None, orientations=None):
     """Decode `descs` on `ctx` into ONE torch.uint8 buffer on the context's device -> (list of tensors, statuses).  Tensor i is
     a view of that buffer shaped (3, sh, sw) -- or (sh, sw, 3) with planar=False -- at the picture's output scale.  The tensors
-    are complete on return and may be read on any torch stream (module docstring, "Stream order")."""
+    are complete on return and may be read on any torch stream (module docstring, "Stream order").
+    orientations=[1..8, ...] (Scanned.orientation): every picture comes out upright, at its own size -- (3, sw, sh) for 5..8 --, the
+    exact permutation of the decoded picture (the identity resample of Batch.set_resize with Batch.set_orientation).  None: as the file
+    stores them."""
     torch = _torch()
     device = torch.device("cuda", ctx.device) if device is None else device
-    buf, offs, st = _run(ctx, descs, pjd_amd.OUT_RGB8_PLANAR if planar else pjd_amd.OUT_RGB8, None, None, device)
+    sizes = None
+    if orientations is not None:
+        _orientations(orientations, len(descs))
+        sizes = [orient_hw(o, *output_hw(d)) for o, d in zip(orientations, descs)]
+    buf, offs, st = _run(ctx, descs, pjd_amd.OUT_RGB8_PLANAR if planar else pjd_amd.OUT_RGB8, None, None, device, resize=sizes,
+                         orientations=orientations)
     out = []
-    for d, off in zip(descs, offs):
-        h, w = output_hw(d)
+    for i, (d, off) in enumerate(zip(descs, offs)):
+        h, w = output_hw(d) if sizes is None else sizes[i]
         flat = buf[off:off + 3 * h * w]
         out.append(flat.view(3, h, w) if planar else flat.view(h, w, 3))
     return out, st
@@ -172,6 +189,49 @@ def window_at_scale(crop, log2s, sw, sh):
     return x0, y0, max(x1 - x0, 1), max(y1 - y0, 1)
 
 
+def _tvh(o):
+    """The bits (t, v, h) of an EXIF orientation 1..8: D = H^h(V^v(T^t(Q))) (include/pjd.h)."""
+    o = int(o)
+    if not 1 <= o <= 8:
+        raise ValueError(f"an orientation is 1..8, not {o}")
+    return ((0, 0, 0), (0, 0, 1), (0, 1, 1), (0, 1, 0), (1, 0, 0), (1, 0, 1), (1, 1, 1), (1, 1, 0))[o - 1]
+
+
+def _orientations(orientations, n):
+    if len(orientations) != n:
+        raise ValueError("orientations: one entry per picture")
+    for o in orientations:
+        _tvh(o)
+
+
+def orient_hw(o, h, w):
+    """(h, w) of a picture of (h, w) after orientation o: swapped for 5..8.  Its own inverse: stored -> upright and back.  Pure."""
+    return (int(w), int(h)) if _tvh(o)[0] else (int(h), int(w))
+
+
+def orient_then_hflip(o):
+    """The orientation that delivers the picture of orientation o mirrored left-right (RandomHorizontalFlip of the UPRIGHT picture): the
+    mirror is the last step of D = H^h(V^v(T^t(Q))), so h ^= 1, which pairs 1 and 2, 3 and 4, 5 and 6, 7 and 8.  Pure."""
+    _tvh(o)
+    return ((int(o) - 1) ^ 1) + 1
+
+
+def crop_to_stored(o, crop, W, H):
+    """The crop (x, y, w, h), given in the UPRIGHT picture's coordinates, in the coordinates of the STORED picture of W x H, whose
+    orientation is o: orient(S, o)[y:y+h, x:x+w] == orient(S[ys:ys+hs, xs:xs+ws], o).  The mirrors are undone in the upright frame, then
+    the axes are swapped where o transposes -> (xs, ys, ws, hs).  ValueError where the crop is not inside the upright picture.  Pure."""
+    t, v, hm = _tvh(o)
+    x, y, w, h = (int(a) for a in crop)
+    UH, UW = orient_hw(o, H, W)
+    if x < 0 or y < 0 or w < 1 or h < 1 or x + w > UW or y + h > UH:
+        raise ValueError(f"crop_to_stored: the crop {(x, y, w, h)} is not inside the upright {UW}x{UH} picture")
+    if hm:
+        x = UW - x - w
+    if v:
+        y = UH - y - h
+    return (y, x, h, w) if t else (x, y, w, h)
+
+
 def _windowed(descs, size, prescale, crops, flips, resize_short):
     """The descriptors to decode and the windows to set for crops / flips / resize_short (None, None: nothing asked).  The pre-scale
     is chosen per picture with the CROP's size against the virtual target."""
@@ -213,6 +273,61 @@ def _windowed(descs, size, prescale, crops, flips, resize_short):
     return run, windows
 
 
+def _plan(descs, size, prescale, crops, flips, resize_short, orientations):
+    """(descriptors to decode, windows or None, orientations or None) of the resizing helpers."""
+    if orientations is None:
+        return _windowed(descs, size, prescale, crops, flips, resize_short) + (None,)
+    _orientations(orientations, len(descs))
+    return _windowed_oriented(descs, size, prescale, crops, flips, resize_short, [int(o) for o in orientations])
+
+
+def _windowed_oriented(descs, size, prescale, crops, flips, resize_short, orientations):
+    """_windowed where the pictures have orientations and crops / flips / resize_short speak about the UPRIGHT picture: crops and the
+    centre crop are mapped into the stored picture's coordinates (crop_to_stored), the virtual target is Q's (axes swapped for 5..8),
+    and a flip is folded into the orientation (orient_then_hflip): the windows' RW_HFLIP stays clear.  -> (descriptors, windows or
+    None, orientations to set)."""
+    th, tw = size
+    n = len(descs)
+    if crops is not None and resize_short is not None:
+        raise ValueError("crops and resize_short exclude each other")
+    for name, v in (("crops", crops), ("flips", flips)):
+        if v is not None and len(v) != n:
+            raise ValueError(f"{name}: one entry per picture")
+    import ctypes
+    run, windows, oris = [], [], []
+    for i, (d, o) in enumerate(zip(descs, orientations)):
+        W, H = int(d.width), int(d.height)
+        t = _tvh(o)[0]
+        qtw, qth = (th, tw) if t else (tw, th)            # Q's target: the delivered one with the axes swapped where o transposes
+        win = {}
+        crop = crops[i] if crops is not None else None
+        if crop is not None:
+            try:
+                crop = crop_to_stored(o, crop, W, H)
+            except ValueError:
+                raise ValueError(f"crops[{i}] = {tuple(crop)} is not inside the upright picture of the {W}x{H} one (orientation {o})")
+        if resize_short is not None:
+            cc = center_crop_window(orient_hw(o, H, W), resize_short, size)          # of the upright picture
+            svw, svh = (cc["vh"], cc["vw"]) if t else (cc["vw"], cc["vh"])           # Q's virtual target
+            ox, oy, _, _ = crop_to_stored(o, (cc["ox"], cc["oy"], tw, th), svw, svh)
+            win.update(vw=svw, vh=svh, ox=ox, oy=oy)
+        vw, vh = win.get("vw", qtw), win.get("vh", qth)
+        if prescale:
+            c = pjd_amd.ImageDesc()
+            ctypes.memmove(ctypes.byref(c), ctypes.byref(d), ctypes.sizeof(pjd_amd.ImageDesc))
+            cw, ch = (crop[2], crop[3]) if crop is not None else (W, H)
+            c.flags = (int(d.flags) & ~pjd_amd.F_SCALE_MASK) | pick_scale_flags(cw, ch, vw, vh)
+            d = c
+        if crop is not None:
+            h_s, w_s = output_hw(d)
+            win["x"], win["y"], win["w"], win["h"] = window_at_scale(crop, _scale_log(d.flags), w_s, h_s)
+        win = {k: v for k, v in win.items() if k in ("x", "y", "w", "h") or v}
+        run.append(d)
+        windows.append(win or None)
+        oris.append(orient_then_hflip(o) if flips is not None and flips[i] else o)
+    return run, (windows if any(w is not None for w in windows) else None), oris
+
+
 def _interpolation(name):
     """The `interpolation` keyword of the resizing helpers, checked before anything is created."""
     if name not in ("bilinear", "bicubic"):
@@ -221,7 +336,7 @@ def _interpolation(name):
 
 
 def decode_resized_batch_tensor(ctx, descs, size, prescale=True, device=None, antialias=False, crops=None, flips=None, resize_short=None,
-                                interpolation="bilinear"):
+                                interpolation="bilinear", orientations=None):
     """Pictures of ANY sizes -> (uint8 tensor [N, 3, H, W], statuses), size = (H, W): every picture is resampled to H x W inside
     the decode (the bilinear filter of include/pjd.h, pjd_batch_set_resize) and lands at offset i * 3 * H * W of one buffer, so
     the result is one contiguous NCHW tensor with no copy after the decode, complete on return and readable on any torch stream
@@ -243,17 +358,22 @@ def decode_resized_batch_tensor(ctx, descs, size, prescale=True, device=None, an
     level of the float64 filter).  It is always the widened form where an axis shrinks: `antialias` is not consulted.  With
     prescale=True the box filter still comes first (less to decode), so the result is the bicubic filter over the box-filtered
     picture; prescale=False is exactly the filter over the full-size picture, for pictures up to 16x the target on each axis.  Any
-    other string than "bilinear" (the default) or "bicubic" raises ValueError before anything is created."""
+    other string than "bilinear" (the default) or "bicubic" raises ValueError before anything is created.
+    orientations=[1..8, ...] (Scanned.orientation): the pictures are delivered upright (Batch.set_orientation: D = H^h(V^v(T^t(Q))) of
+    include/pjd.h, in the same launch), and crops, resize_short and flips speak about the UPRIGHT picture: crops are mapped with
+    crop_to_stored, the centre crop is computed from the upright size, flips are folded into the orientation (orient_then_hflip).  The
+    picture is resampled in the stored picture's coordinates and permuted on the way out, which is within each filter's one-level
+    bound of "orient, then resize".  None: today's behaviour, byte for byte."""
     _interpolation(interpolation)
     if len(descs) == 0:
         raise ValueError("decode_resized_batch_tensor: no pictures")
     th, tw = int(size[0]), int(size[1])
-    run, windows = _windowed(descs, (th, tw), prescale, crops, flips, resize_short)
+    run, windows, oris = _plan(descs, (th, tw), prescale, crops, flips, resize_short, orientations)
     torch = _torch()
     device = torch.device("cuda", ctx.device) if device is None else device
     n, plane = len(descs), 3 * th * tw
     buf, _, st = _run(ctx, run, pjd_amd.OUT_RGB8_PLANAR, n * plane, [i * plane for i in range(n)], device, resize=[(th, tw)] * n,
-                      antialias=antialias, windows=windows, interpolation=interpolation)
+                      antialias=antialias, windows=windows, interpolation=interpolation, orientations=oris)
     return buf.view(n, 3, th, tw), st
 
 
@@ -270,7 +390,7 @@ def normalize_constants(mean, std):
 
 
 def decode_normalized_batch_tensor(ctx, descs, size, mean, std, dtype=None, channels_last=False, prescale=True, device=None,
-                                   antialias=False, crops=None, flips=None, resize_short=None, interpolation="bilinear"):
+                                   antialias=False, crops=None, flips=None, resize_short=None, interpolation="bilinear", orientations=None):
     """Pictures of ANY sizes -> (tensor of `dtype` [N, 3, H, W], statuses), size = (H, W); dtype torch.float16 (the default),
     torch.bfloat16 or torch.float32.  As decode_resized_batch_tensor, and every sample v of channel c leaves the same launch as
     fma(v, scale[c], bias[c]) with the constants of normalize_constants(mean, std), converted once to `dtype` (include/pjd.h,
@@ -282,7 +402,8 @@ def decode_normalized_batch_tensor(ctx, descs, size, mean, std, dtype=None, chan
     pre-scale comes first), prescale=False gives exactly that up to the 16x limit.  crops, flips, resize_short: as in
     decode_resized_batch_tensor.  interpolation="bicubic": the bicubic filter (RESIZE_BICUBIC), as there -- `antialias` is not consulted,
     prescale=True still puts the box filter first, prescale=False is exactly the filter over the full-size picture up to the 16x
-    limit; any other string than "bilinear" or "bicubic" raises ValueError before anything is created."""
+    limit; any other string than "bilinear" or "bicubic" raises ValueError before anything is created.  orientations: as in
+    decode_resized_batch_tensor."""
     _interpolation(interpolation)
     if len(descs) == 0:
         raise ValueError("decode_normalized_batch_tensor: no pictures")
@@ -295,9 +416,10 @@ def decode_normalized_batch_tensor(ctx, descs, size, mean, std, dtype=None, chan
         raise ValueError("decode_normalized_batch_tensor: dtype must be torch.float16, torch.bfloat16 or torch.float32")
     dt, es = dts[dtype]
     device = torch.device("cuda", ctx.device) if device is None else device
-    run, windows = _windowed(descs, (th, tw), prescale, crops, flips, resize_short)
+    run, windows, oris = _plan(descs, (th, tw), prescale, crops, flips, resize_short, orientations)
     n, pic = len(descs), 3 * th * tw * es
     buf, _, st = _run(ctx, run, pjd_amd.OUT_RGB8 if channels_last else pjd_amd.OUT_RGB8_PLANAR, n * pic, [i * pic for i in range(n)], device,
-                      resize=[(th, tw)] * n, normalize=(dt, scale, bias), antialias=antialias, windows=windows, interpolation=interpolation)
+                      resize=[(th, tw)] * n, normalize=(dt, scale, bias), antialias=antialias, windows=windows, interpolation=interpolation,
+                      orientations=oris)
     t = buf.view(dtype)
     return (t.view(n, th, tw, 3).permute(0, 3, 1, 2) if channels_last else t.view(n, 3, th, tw)), st

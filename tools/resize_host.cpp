@@ -15,7 +15,10 @@
 // buffer at element-aligned offsets with odd gaps, the buffer itself shifted by 0..3 elements:
 //   - plain: 31 pictures (tile edges, ragged right edges, random sizes; the table-driven body skips those that shrink more than 16x)
 //     through the WIN = false body, and again through the WIN = true body with the identity window: the same bytes;
-//   - windowed: 12 geometries (those of tests/test_gpu_resize_window.py and the four remainders of x) and 10 seeded windows.
+//   - windowed: 12 geometries (those of tests/test_gpu_resize_window.py and the four remainders of x) and 10 seeded windows;
+//   - oriented: those windows and 16 shapes for the transposed store (all eight rows and ragged row tiles, one column, one row, rows of
+//     13 samples) through the ORI bodies, every orientation 1..8 (pjd_batch_set_orientation) under windows, mirrors and offsets; the
+//     expectation places Q's samples by the table of include/pjd.h.  The plain set also runs through the ORI body: the same bytes.
 // The source holds every picture back to back with NO padding between them beyond what rounds the buffer to a dword (the kernels
 // stage whole dwords): a read outside a window that mattered would change the result, a read outside the buffer is a sanitizer
 // report.  The expectation is a plain per-pixel loop over the arithmetic of include/pjd.h -- the tap inlines with a shifted index;
@@ -48,14 +51,14 @@ static inline uint32_t emu_tap(uint32_t sn, uint32_t dn, uint32_t i) { uint32_t 
 #define PJD_WIN_STAGE_FIRST 0u
 #define PJD_WIN_STAGE_STEP  1u
 
-template <bool PLANAR, int DT, bool WIN>
+template <bool PLANAR, int DT, bool WIN, bool ORI>
 static void thread_bilinear(const uint8_t *src, uint8_t *dst, const PjdDevResize *recs, const PjdDevResizeWin *win, const uint32_t *tile_prefix,
                             uint32_t n_images, uint32_t n_tiles, const NormArgs nz)
 {
 #include "../pim-jpeg-decoder_amd/csrc/pjd_k_resize_body.h"
 }
 
-template <bool PLANAR, int DT, bool WIN, int FILT>
+template <bool PLANAR, int DT, bool WIN, bool ORI, int FILT>
 static void thread_aa(uint32_t *seg, const uint8_t *src, uint8_t *dst, const PjdDevResize *recs, const PjdDevResizeWin *win, const uint32_t *tile_prefix,
                       uint32_t n_images, uint32_t n_tiles, const PjdDevResizeAA *aa, const uint32_t *tab, uint32_t lds_bytes, const NormArgs nz)
 {
@@ -85,7 +88,10 @@ static uint16_t f16bits(float f)
 }
 static uint16_t bf16bits(float f) { uint32_t b; memcpy(&b, &f, 4); b += 0x7fffu + ((b >> 16) & 1u); return (uint16_t)(b >> 16); }
 
-struct Case { uint32_t sw, sh, tw, th; PjdDevResizeWin w; };
+struct Case { uint32_t sw, sh, tw, th; PjdDevResizeWin w; uint32_t o = 1; };   // o: the orientation (oriented set), tw x th then Q's target
+
+// the bits t << 2 | v << 1 | h of an orientation, written out from the table of include/pjd.h (not pjd_orient_tvh: that is under test)
+static uint32_t tvh_of(uint32_t o) { return o == 1 ? 0u : o == 2 ? 1u : o == 3 ? 3u : o == 4 ? 2u : o == 5 ? 4u : o == 6 ? 5u : o == 7 ? 7u : 6u; }
 
 // the tap-major table of one axis, as pjd_batch_set_resize_filter lays it out: dn heads `first | count << 16`, then taps x dn weights
 static uint32_t axis_table(std::vector<uint32_t> &tab, int filt, uint32_t sn, uint32_t dn, uint32_t &taps)
@@ -143,12 +149,30 @@ static std::vector<Case> window_cases(unsigned seed)
     return cases;
 }
 
-template <bool PLANAR, int DT, int FILT>
-static int run(bool windowed, uint32_t misalign_elems, unsigned seed)
+// the oriented set: the windowed one and shapes that take the transposed store's paths (all eight rows and ragged, one column, one
+// row, D rows of 13 samples: every alignment), each case with the orientation 1 + (index % 8) and so every orientation with windows,
+// mirrors and offsets under it
+static std::vector<Case> oriented_cases(unsigned seed)
 {
+    std::vector<Case> cases = window_cases(seed);
+    for (Case c : std::vector<Case>{{61, 45, 259, 13}, {45, 300, 5, 259}, {20, 20, 8, 8}, {9, 9, 1, 1}, {9, 20, 1, 9}, {20, 9, 9, 1}, {88, 56, 24, 16}, {61, 45, 259, 13},
+                                    {88, 56, 40, 32}, {61, 45, 13, 259}, {88, 56, 16, 24}, {61, 45, 259, 13}, {30, 30, 8, 16}, {61, 45, 259, 13}, {30, 30, 16, 8}, {61, 45, 259, 13}}) {
+        PjdDevResize r{}; r.sw = c.sw; r.sh = c.sh; r.tw = c.tw; r.th = c.th;
+        c.w = pjd_resize_win_identity(r);
+        cases.push_back(c);
+    }
+    for (size_t i = 0; i < cases.size(); i++) cases[i].o = 1 + (uint32_t)((i + i / 8) % 8);
+    return cases;
+}
+
+// mode 0: plain, 1: windowed, 2: oriented (the ORI bodies: windows with an orientation)
+template <bool PLANAR, int DT, int FILT>
+static int run(int mode, uint32_t misalign_elems, unsigned seed)
+{
+    const bool windowed = mode != 0, oriented = mode == 2;
     constexpr bool AA = FILT != PJD_RESIZE_BILINEAR;          // a table-driven filter
     const uint32_t ES = DT == 0 ? 1 : PJD_DT_SIZE(DT);
-    const std::vector<Case> cases = windowed ? window_cases(seed) : plain_cases(seed, AA);
+    const std::vector<Case> cases = oriented ? oriented_cases(seed) : windowed ? window_cases(seed) : plain_cases(seed, AA);
     const size_t n = cases.size();
     std::vector<PjdDevResize> recs(n); std::vector<PjdDevResizeWin> wins(n); std::vector<PjdDevResizeAA> aas(n); std::vector<uint32_t> prefix(n + 1), tab;
     size_t spos = 0, dpos = misalign_elems * ES; uint32_t t = 0, lds = 0;
@@ -159,6 +183,7 @@ static int run(bool windowed, uint32_t misalign_elems, unsigned seed)
             printf("case %zu is not a valid window\n", i); return 1;
         }
         wins[i] = c.w;
+        if (oriented) wins[i].flags ^= pjd_orient_flags(c.o);  // as pjd_batch_set_orientation and _set_resize_window compose them
         r.src_off = spos; r.sw = c.sw; r.sh = c.sh; r.src_stride = PLANAR ? c.sw : 3 * c.sw; r.tw = c.tw; r.th = c.th;
         r.col_tiles = (c.tw + PJD_RS_COLS - 1) / PJD_RS_COLS; r.dst_off = dpos;
         doff[i] = dpos;
@@ -170,7 +195,7 @@ static int run(bool windowed, uint32_t misalign_elems, unsigned seed)
             aas[i].y_tab = axis_table(tab, FILT, c.w.h, c.w.vh, aas[i].y_taps);
             for (uint32_t c0 = 0; c0 < c.tw; c0 += PJD_RS_COLS) {                   // the sizing loop of pjd_batch_set_resize_filter
                 uint32_t e0, e1;
-                pjd_resize_win_ends(c.w, c.tw, c0, std::min<uint32_t>(c0 + PJD_RS_COLS, c.tw) - 1u, e0, e1);
+                pjd_resize_win_ends(wins[i], c.tw, c0, std::min<uint32_t>(c0 + PJD_RS_COLS, c.tw) - 1u, e0, e1);
                 const uint32_t h0 = tab[aas[i].x_tab + e0], h1 = tab[aas[i].x_tab + e1];
                 lds = std::max(lds, pjd_resize_aa_lds((h1 & 0xffffu) + (h1 >> 16) - (h0 & 0xffffu), PLANAR));
             }
@@ -184,28 +209,31 @@ static int run(bool windowed, uint32_t misalign_elems, unsigned seed)
     const size_t dst_bytes = dpos + 256;
     const NormArgs nz = {{0.01712475f, 0.017507f, -0.01742919f}, {-2.117904f, -2.0357144f, 1.8044444f}};
     // every thread of the launch, with the WIN = true or the WIN = false body
-    auto launch = [&](auto WIN) {
-        constexpr bool W = decltype(WIN)::value;
+    auto launch = [&](auto WIN, auto ORI) {
+        constexpr bool W = decltype(WIN)::value, O = decltype(ORI)::value;
         uint8_t *dst = (uint8_t *)aligned_alloc(256, (dst_bytes + 255) & ~(size_t)255); memset(dst, 0xA5, dst_bytes);
         const uint32_t n_threads = AA ? 64 : 64 * PJD_RS_WAVES, n_blocks = AA ? t : (t + PJD_RS_WAVES - 1) / PJD_RS_WAVES;
         for (uint32_t b = 0; b < n_blocks; b++) for (uint32_t th = 0; th < n_threads; th++) {
             blockIdx.x = b; threadIdx.x = th;
             if constexpr (AA) {
                 uint32_t *seg = (uint32_t *)malloc(lds ? lds : 4);                   // this thread's "LDS", of the launch's size
-                thread_aa<PLANAR, DT, W, FILT>(seg, src, dst, recs.data(), W ? wins.data() : nullptr, prefix.data(), (uint32_t)n, t, aas.data(), tab.data(), lds, nz);
+                thread_aa<PLANAR, DT, W, O, FILT>(seg, src, dst, recs.data(), W ? wins.data() : nullptr, prefix.data(), (uint32_t)n, t, aas.data(), tab.data(), lds, nz);
                 free(seg);
             } else {
-                thread_bilinear<PLANAR, DT, W>(src, dst, recs.data(), W ? wins.data() : nullptr, prefix.data(), (uint32_t)n, t, nz);
+                thread_bilinear<PLANAR, DT, W, O>(src, dst, recs.data(), W ? wins.data() : nullptr, prefix.data(), (uint32_t)n, t, nz);
             }
         }
         return dst;
     };
-    uint8_t *dst = windowed ? launch(std::true_type{}) : launch(std::false_type{});
+    uint8_t *dst = oriented ? launch(std::true_type{}, std::true_type{}) : windowed ? launch(std::true_type{}, std::false_type{}) : launch(std::false_type{}, std::false_type{});
     int bad = 0;
     uint32_t clamped = FILT == PJD_RESIZE_BICUBIC ? 0u : 3u;   // bicubic: the final clamp is met at both ends
     if (!windowed) {                                         // the identity window through the WIN = true body: the same bytes
-        uint8_t *again = launch(std::true_type{});
+        uint8_t *again = launch(std::true_type{}, std::false_type{});
         if (memcmp(dst, again, dst_bytes) != 0) { printf("  the identity window through the WIN body gives other bytes\n"); bad++; }
+        free(again);
+        again = launch(std::true_type{}, std::true_type{});  // ... and through the ORI body (orientation 1: no PJD_RWI_* bit)
+        if (memcmp(dst, again, dst_bytes) != 0) { printf("  the identity window through the ORI body gives other bytes\n"); bad++; }
         free(again);
     }
     // the expectation: include/pjd.h, pixel by pixel
@@ -250,7 +278,11 @@ static int run(bool windowed, uint32_t misalign_elems, unsigned seed)
                 x0 += w.x; x1 += w.x; y0 += w.y; y1 += w.y;
                 v = ((256 - wy) * ((256 - wx) * P(ch, y0, x0) + wx * P(ch, y0, x1)) + wy * ((256 - wx) * P(ch, y1, x0) + wx * P(ch, y1, x1)) + 32768) >> 16;
             }
-            const size_t e = PLANAR ? ((size_t)ch * c.th + y) * c.tw + x : ((size_t)y * c.tw + x) * 3 + ch;
+            // where Q[y][x] is delivered: D = H^h(V^v(T^t(Q))) of include/pjd.h, D being dw x dh
+            const uint32_t b3 = tvh_of(c.o), ot = b3 >> 2, ov = (b3 >> 1) & 1u, oh = b3 & 1u;
+            const uint32_t dw = ot ? c.th : c.tw, dh = ot ? c.tw : c.th;
+            const uint32_t di = ot ? (ov ? c.tw - 1 - x : x) : (ov ? c.th - 1 - y : y), dj = ot ? (oh ? c.th - 1 - y : y) : (oh ? c.tw - 1 - x : x);
+            const size_t e = PLANAR ? ((size_t)ch * dh + di) * dw + dj : ((size_t)di * dw + dj) * 3 + ch;
             uint8_t *o = want.data() + doff[i] + e * ES;
             if (DT == 0) *o = (uint8_t)v;
             else {
@@ -263,14 +295,14 @@ static int run(bool windowed, uint32_t misalign_elems, unsigned seed)
     for (size_t k = 0; k < dst_bytes; k++) if (dst[k] != want[k]) { if (bad < 4) printf("  mismatch at byte %zu got %02x want %02x\n", k, dst[k], want[k]); bad++; }
     uint32_t rem = windowed ? 0u : 0xfu;                     // the windowed set has a segment at every dword remainder
     for (size_t i = 0; i < n; i++) rem |= 1u << ((recs[i].src_off + (PLANAR ? cases[i].w.x : 3 * cases[i].w.x) + (size_t)cases[i].w.y * recs[i].src_stride) & 3u);
-    printf("%s %s PLANAR=%d DT=%d misalign=%u: %zu pictures, %u tiles, lds %u, remainders %x, clamps %x: %s\n", FILT == PJD_RESIZE_BICUBIC ? "bicubic  " : AA ? "antialias" : "bilinear ", windowed ? "windowed" : "plain   ",
+    printf("%s %s PLANAR=%d DT=%d misalign=%u: %zu pictures, %u tiles, lds %u, remainders %x, clamps %x: %s\n", FILT == PJD_RESIZE_BICUBIC ? "bicubic  " : AA ? "antialias" : "bilinear ", oriented ? "oriented" : windowed ? "windowed" : "plain   ",
            (int)PLANAR, DT, misalign_elems, n, t, lds, rem, clamped, bad ? "MISMATCH" : "equal, guards intact");
     free(dst); free(src);
     return bad != 0 || rem != 0xf || clamped != 3u;
 }
 
 template <int FILT>
-static int all(bool windowed)
+static int all(int windowed)
 {
     int rc = 0;
     for (uint32_t mis : {0u, 1u, 2u, 3u}) {
@@ -284,8 +316,8 @@ static int all(bool windowed)
 
 int main()
 {
-    const int rc = all<PJD_RESIZE_BILINEAR>(false) | all<PJD_RESIZE_BILINEAR>(true) | all<PJD_RESIZE_ANTIALIAS>(false) | all<PJD_RESIZE_ANTIALIAS>(true) |
-                   all<PJD_RESIZE_BICUBIC>(false) | all<PJD_RESIZE_BICUBIC>(true);
+    const int rc = all<PJD_RESIZE_BILINEAR>(0) | all<PJD_RESIZE_BILINEAR>(1) | all<PJD_RESIZE_BILINEAR>(2) | all<PJD_RESIZE_ANTIALIAS>(0) | all<PJD_RESIZE_ANTIALIAS>(1) |
+                   all<PJD_RESIZE_ANTIALIAS>(2) | all<PJD_RESIZE_BICUBIC>(0) | all<PJD_RESIZE_BICUBIC>(1) | all<PJD_RESIZE_BICUBIC>(2);
     printf(rc ? "FAILED\n" : "ALL EQUAL\n");
     return rc;
 }
