@@ -30,6 +30,8 @@
  *                                                       quarter turns) per picture inside that launch (pjd_scanned_orientation reads the tag)
  *   (none: an addition)                                 pjd_batch_set_normalize + pjd_normalize_value: the samples leave as fp16, bf16
  *                                                       or fp32, v * scale[c] + bias[c], in that launch (the tensor a model takes)
+ *   (none: an addition)                                 PJD_F_LIBJPEG + pjd_libjpeg_idct / _ycc_to_rgb / _upsample_row: the picture libjpeg
+ *                                                       decodes, bit for bit (islow IDCT, fancy upsampling, JFIF colour), per picture
  *
  * Plain pointers and sizes only; no C++ or torch types.  Thread model: one
  * submitting thread per pjd_ctx (the reference has one consumer thread,
@@ -50,7 +52,9 @@ extern "C" {
 /* ABI version: bumped whenever a struct in this header changes size or layout (pjd_image_desc gained qt_slot48 and
  * pjd_batch_info grew in version 2; version 3 added the coefficient download and pjd_split_*; version 4 the progressive scans of
  * pjd_image_desc and the exact-path figures of pjd_batch_info; version 5 pjd_batch_info::n_steps; version 6 the output scale
- * PJD_F_SCALE_* and pjd_pipe_opts::image_flags of pjd_pipeline.h).
+ * PJD_F_SCALE_* and pjd_pipe_opts::image_flags of pjd_pipeline.h).  PJD_OUT_RGB8_PLANAR and PJD_F_LIBJPEG changed no struct and
+ * no version: a caller that needs one of them checks for it by its symbols (pjd_libjpeg_idct is exported from the first library that
+ * knows PJD_F_LIBJPEG; an older one ignores the bit).
  * A caller built against another version must not pass its structs: check pjd_version() == PJD_VERSION after loading.     */
 #define PJD_VERSION 6
 
@@ -141,6 +145,69 @@ extern "C" {
 #define PJD_F_SCALE_1_4        32u
 #define PJD_F_SCALE_1_8        48u
 #define PJD_F_SCALE_MASK       48u
+
+/* ---- libjpeg-exact decode ------------------------------------------------------------------------------------------------------ *
+ * PJD_F_LIBJPEG, chosen per picture: the picture P of the descriptor is the one libjpeg (libjpeg-turbo, Pillow, torchvision.io,
+ * OpenCV) decodes with its defaults -- jpeg_idct_islow, do_fancy_upsampling, the JFIF colour tables -- byte for byte, instead of the
+ * reference's.  The flag implies PJD_F_STANDARD_ZIGZAG and PJD_F_STANDARD_RESTART for that picture, set or not.  Everything in this
+ * header that says "the picture the library produces" then means this P: the three output formats (the BMP is the same file image built
+ * from this P), the library's own buffer and pjd_batch_bind_output, pjd_batch_set_resize, _set_resize_filter, _set_resize_window,
+ * _set_orientation and _set_normalize (their kernels are unchanged: they read P).  Status words are unchanged; a batch may mix flagged
+ * and unflagged pictures, and the unflagged ones are decoded by the very kernels of a batch without the flag.
+ *
+ * THE ARITHMETIC (normative; all integers, 32-bit two's complement that WRAPS, shifts arithmetic).  Coefficients are the entropy
+ * decoder's, placed through the T.81 zigzag; a unit or slot never decoded is 0 (absolute DC 0) -- every unit behind an entropy-coding
+ * error included, which is what makes the partial picture grey (128) there.
+ *   1. Dequantise: d[k] = coef[k] * Q[k], coef an int16, Q the 8- or 16-bit quantiser, the product in 32 bits.
+ *   2. IDCT: libjpeg's jpeg_idct_islow (jidctint.c), CONST_BITS = 13, PASS1_BITS = 2.  The 1-D kernel on inputs i0..i7:
+ *          z1=(i2+i6)*4433; t2=z1-i6*15137; t3=z1+i2*6270; t0=(i0+i4)<<13; t1=(i0-i4)<<13
+ *          t10=t0+t3; t13=t0-t3; t11=t1+t2; t12=t1-t2
+ *          a0=i7; a1=i5; a2=i3; a3=i1; z1=a0+a3; z2=a1+a2; z3=a0+a2; z4=a1+a3; z5=(z3+z4)*9633
+ *          a0*=2446; a1*=16819; a2*=25172; a3*=12299; z1*=-7373; z2*=-20995; z3=z3*-16069+z5; z4=z4*-3196+z5
+ *          a0+=z1+z3; a1+=z2+z4; a2+=z2+z3; a3+=z1+z4
+ *          o0,o7=t10+-a3; o1,o6=t11+-a2; o2,o5=t12+-a1; o3,o4=t13+-a0;   each (o + (1<<(s-1))) >> s
+ *      Pass 1 runs on the COLUMNS of d with s = 11 into a 32-bit workspace, pass 2 on the workspace's rows with s = 18; the sample is
+ *      clamp(o + 128, 0, 255).  libjpeg's shortcut for a column without AC terms gives the value of the full pass (dc << 2): there is
+ *      no data-dependent form.  For a stream whose dequantised values fit int16 and whose passes do not overflow -- every file an
+ *      encoder made -- this is libjpeg's picture.  Beyond that it is THIS LIBRARY'S OWN deterministic definition (libjpeg masks its
+ *      range-limit table where this clamps, and its behaviour on overflow is undefined C): such streams are pinned to
+ *      pjd_libjpeg_idct below, not to libjpeg.
+ *   3. Chroma upsampling: libjpeg's do_fancy_upsampling.  With n = ceil(W/hs) columns and m = ceil(H/vs) rows of the chroma plane
+ *      (downsampled_width / _height) -- samples beyond n or m NEVER contribute, although the padded MCU holds decoded data there:
+ *        hs = 2, vs = 1, n > 2:  out[2i] = (3*c[i] + c[i-1] + 1) >> 2,  out[2i+1] = (3*c[i] + c[i+1] + 2) >> 2,
+ *                                except out[0] = c[0] and out[2n-1] = c[n-1]
+ *        hs = vs = 2, n > 2:     for output row 2r+v the neighbour row is r-1 (v = 0) or r+1 (v = 1), clamped to 0..m-1;
+ *                                s[i] = 3*c[r][i] + c[nb][i];  out[2i] = (3*s[i] + s[i-1] + 8) >> 4,  out[2i+1] = (3*s[i] + s[i+1] + 7) >> 4,
+ *                                except out[0] = (4*s[0] + 8) >> 4 and out[2n-1] = (4*s[n-1] + 7) >> 4
+ *        n <= 2 (pictures at most 4 wide): plain replication on both axes (libjpeg switches its fancy routines off there)
+ *        hs = vs = 1, and one-component pictures: no upsampling.
+ *   4. Colour: libjpeg's ycc_rgb_convert tables, 16 fraction bits.  With cb = Cb - 128, cr = Cr - 128:
+ *          R = clamp(Y + ((91881*cr + 32768) >> 16))
+ *          G = clamp(Y + ((-22554*cb - 46802*cr + 32768) >> 16))
+ *          B = clamp(Y + ((116130*cb + 32768) >> 16))
+ *      A one-component picture gives R = G = B = Y.
+ * tests/test_libjpeg_cpu.py and tests/test_gpu_libjpeg.py hold this against Pillow's decode of files Pillow wrote: zero tolerance.
+ *
+ * ENVELOPE.  Baseline and progressive frames (with PJD_F_PROGRESSIVE Pillow's progressive files equal Pillow's decode); sampling
+ * 4:4:4, 4:2:2 (h2v1), 4:2:0, or one component; the parallel path, PJD_F_FORCE_SEQUENTIAL and the exact-kernel fallback of
+ * pjd_batch_sync; captured graphs.  pjd_batch_create returns PJD_E_ARG (pjd_last_error names the picture) for the flag together with
+ * PJD_F_SCALE_* (libjpeg's reduced IDCTs are other filters), with 4:4:0 (h1v2) sampling, with two components, or on a shard
+ * (so pjd_split_decode refuses a flagged descriptor too).  pjd_batch_download_coefficients returns the coefficients as under
+ * PJD_F_STANDARD_ZIGZAG.
+ * HOW.  Two more launches for the flagged pictures of a batch (pjd_batch_decode_timed names them "idct_std" and "colour_std"; part of
+ * a captured graph; run again after the exact-kernel fallback): the IDCT into uint8 component planes -- an intermediate buffer of the
+ * batch, whole MCUs per picture, counted in pjd_batch_info::device_bytes, every byte written by every decode -- then upsampling,
+ * colour and the store into exactly the ranges the default back end writes.  A batch that holds a flagged picture is decoded as one
+ * chain of launches.  A batch without one allocates and launches nothing new.
+ * The three functions below are the arithmetic on its own, host only (no device needed), the very inlines the kernels run:
+ * pjd_libjpeg_idct steps 1 and 2 for one unit (coef, q and out in natural order); pjd_libjpeg_ycc_to_rgb step 4 for one pixel;
+ * pjd_libjpeg_upsample_row step 3 for one output row: `cur` is the chroma row c[r] and `nb` its neighbour row c[nb] (NULL: h2v1; `v`
+ * says which neighbour it is, and changes nothing), n samples each, and out receives 2n samples.  PJD_E_ARG for a null pointer or
+ * n = 0.                                                                                                                          */
+#define PJD_F_LIBJPEG          64u
+int  pjd_libjpeg_idct(const int16_t coef[64], const uint16_t q[64], uint8_t out[64]);            /* host only, no device needed */
+int  pjd_libjpeg_ycc_to_rgb(uint8_t y, uint8_t cb, uint8_t cr, uint8_t rgb[3]);                /* host only, no device needed */
+int  pjd_libjpeg_upsample_row(const uint8_t *cur, const uint8_t *nb, int v, uint32_t n, uint8_t *out /* 2n */);   /* host only */
 
 /* Huffman table as the reference's scanner holds it (jpeg.h:129-134):
  * offsets[k] = number of codes of length <= k (offsets[0] = 0).               */

@@ -60,7 +60,9 @@ typedef struct pjd_pipe_opts {
     int32_t n_devices;       /* entries in `devices` (at most PJD_PIPE_MAX_DEVICES)            */
     uint32_t scan_options;   /* PJD_SCAN_* of pjd_host.h handed to the scanner (0 = the reference's accept / reject set) */
     uint32_t image_flags;    /* PJD_F_* ORed into every descriptor the scanner produces: PJD_F_SCALE_* (reduced-size pictures
-                                for the sink), PJD_F_STANDARD_*; 0 = as scanned.  Added in PJD_VERSION 6.               */
+                                for the sink), PJD_F_STANDARD_*, PJD_F_LIBJPEG (libjpeg's pictures; a batch then fails as a
+                                whole if it holds a file outside that mode's envelope, such as 4:4:0 sampling); 0 = as
+                                scanned.  Added in PJD_VERSION 6.                                                      */
 } pjd_pipe_opts;
 
 typedef struct pjd_pipe_stats {

@@ -24,6 +24,7 @@
 
 #include "../../include/pjd.h"
 #include "pjd_kernels.h"
+#include "pjd_libjpeg.h"
 #include "pjd_plan.h"
 
 // Buffers of destroyed batches are kept per context and handed to the next batch (a steady stream of
@@ -174,6 +175,8 @@ struct pjd_batch {
     PjdDevHuffWg *d_hwgs = nullptr;
     PjdDevIdctWg *d_iwgs = nullptr;
     PjdDevIdctWg *d_iwgs_dense = nullptr;
+    PjdDevIdctWg *d_iwgs_dense_std = nullptr, *d_cwgs_std = nullptr;   // PJD_F_LIBJPEG pictures: ranges of those on the dense path, work list of the colour launch
+    uint8_t *d_planes = nullptr;         // ... and their component planes (null: the batch holds no such picture)
     uint8_t *d_ecs = nullptr;
     uint32_t *d_seq_list = nullptr;      // images routed to the exact kernel up front ...
     uint64_t *d_seq_base = nullptr;      // ... and where each one's data units start in the dense scratch
@@ -377,6 +380,7 @@ int pjd_batch_create(pjd_ctx *ctx, const pjd_image_desc *images, int n_images, i
     const size_t o_segs = part(P.segs, 0), o_lanes = part(P.subs, 0), o_hwaves = part(P.hwaves, 0), o_hwgs = part(P.hwgs, 0);
     const size_t o_iwgs = part(P.iwgs, 0), o_iwgs_dense = part(P.iwgs_dense, 0), o_pscans = part(P.pscans, 0);
     const size_t o_gimg = part(P.group_images, 0), o_iorder = part(P.iwg_order, 0);
+    const size_t o_iwgs_dense_std = P.libjpeg ? part(P.iwgs_dense_std, 0) : 0, o_cwgs_std = P.libjpeg ? part(P.cwgs_std, 0) : 0;
     const size_t o_seq_list = part(b->seq_list, (size_t)n_images), o_seq_base = part(seq_base, (size_t)n_images), o_st0 = part(st0, (size_t)n_images);
     const size_t o_ecs = in_bytes;
     in_bytes += P.ecs_buf_bytes;
@@ -427,6 +431,10 @@ int pjd_batch_create(pjd_ctx *ctx, const pjd_image_desc *images, int n_images, i
     b->d_seq_list = (uint32_t *)(b->d_in + o_seq_list); b->d_seq_base = (uint64_t *)(b->d_in + o_seq_base);
     b->d_status_init = (int32_t *)(b->d_in + o_st0);
     b->d_ecs = b->d_in + o_ecs;
+    if (P.libjpeg) {
+        b->d_iwgs_dense_std = (PjdDevIdctWg *)(b->d_in + o_iwgs_dense_std); b->d_cwgs_std = (PjdDevIdctWg *)(b->d_in + o_cwgs_std);
+        TRY_RC(dev_alloc(ctx, b->d_planes, (size_t)P.plane_bytes, tot));
+    }
     TRY_RC(dev_alloc(ctx, b->dev.luts, (size_t)P.lut_buf_bytes, tot));
     TRY_RC(dev_alloc(ctx, b->dev.words, (size_t)P.n_words, tot));
     TRY_RC(dev_alloc(ctx, b->dev.coef, P.dense_du * 64, tot));
@@ -618,8 +626,15 @@ int enqueue_decode(pjd_batch *b, pjd_timings *timings, bool use_groups)
             pjd_launch_lane_words(s, b->dev);    kt.mark("lane_words");
             pjd_launch_huff_lanes(s, b->dev);    kt.mark("huff_lanes");
             pjd_launch_lane_dc_scan(s, b->dev);  kt.mark("dc_scan");
-            pjd_launch_idct_colour_lanes(s, b->dev, P.scaled, P.planar);
+            if (!P.libjpeg) pjd_launch_idct_colour_lanes(s, b->dev, P.scaled, P.planar);
+            else {
+                // the ranges of the unflagged pictures through the default kernels, those of the flagged ones into their planes
+                PjdDevGroup def{};
+                def.iwg_first = 0; def.iwg_count = P.n_iwg_def;
+                pjd_launch_group_idct(s, b->dev, def, P.scaled, P.planar);
+            }
             kt.mark("idct_colour");
+            if (P.n_iwg_std) { pjd_launch_idct_std_lanes(s, b->dev, b->dev.iwg_order + P.n_iwg_def, P.n_iwg_std, b->d_planes); kt.mark("idct_std"); }
         }
     }
     if (!b->seq_list.empty()) {
@@ -628,7 +643,13 @@ int enqueue_decode(pjd_batch *b, pjd_timings *timings, bool use_groups)
         pjd_launch_huff_sequential(s, b->dev, b->d_seq_list, b->d_seq_base, (uint32_t)b->seq_list.size());
         if (!P.pscans.empty()) pjd_launch_progressive(s, b->dev, b->d_seq_list, b->d_seq_base, (uint32_t)b->seq_list.size());
         pjd_launch_idct_colour(s, b->dev, b->d_iwgs_dense, b->d_seq_base, (uint32_t)P.iwgs_dense.size(), P.scaled, P.planar);
+        if (P.libjpeg) pjd_launch_idct_std_dense(s, b->dev, b->d_iwgs_dense_std, b->d_seq_base, (uint32_t)P.iwgs_dense_std.size(), b->d_planes);
         kt.mark("exact_path");
+    }
+    if (P.libjpeg) {
+        // the flagged pictures' planes are complete, whichever front end filled them: upsample, colour, store
+        pjd_launch_colour_std(s, b->dev, b->d_cwgs_std, (uint32_t)P.cwgs_std.size(), b->d_planes);
+        kt.mark("colour_std");
     }
     if (b->resized) {
         // resize on decode: every picture from the intermediate (dev.out) to its target size in the result buffer, one launch behind
@@ -671,7 +692,7 @@ int settle(pjd_batch *b)
     if (b->counted) { g_active[ctx->device].fetch_sub(1); b->counted = false; }       // this decode has left the device
     std::vector<uint32_t> fb;
     std::vector<uint64_t> fb_base;
-    std::vector<PjdDevIdctWg> fb_wgs;
+    std::vector<PjdDevIdctWg> fb_wgs, fb_wgs_std;          // ranges to redo: of the default back end, of the PJD_F_LIBJPEG one
     std::vector<char> was_seq(n, 0);
     for (uint32_t i : b->seq_list) was_seq[i] = 1;
     uint64_t du = 0;
@@ -681,7 +702,7 @@ int settle(pjd_batch *b)
             for (uint32_t k = 0; k < g.n_iwg; k++) {
                 PjdDevIdctWg w = P.iwgs[g.iwg_base + k];
                 w.pad_ = (uint32_t)fb.size();
-                fb_wgs.push_back(w);
+                ((g.flags & PJD_IF_LIBJPEG) ? fb_wgs_std : fb_wgs).push_back(w);
             }
             fb.push_back((uint32_t)i);
             fb_base.push_back(du);
@@ -696,6 +717,8 @@ int settle(pjd_batch *b)
         hipEvent_t ev0 = nullptr, ev1 = nullptr;
         (void)hipEventCreate(&ev0); (void)hipEventCreate(&ev1);
         int16_t *coef = nullptr; uint32_t *d_list = nullptr; uint64_t *d_base = nullptr; PjdDevIdctWg *d_wgs = nullptr;
+        const size_t n_def = fb_wgs.size(), n_std = fb_wgs_std.size();
+        fb_wgs.insert(fb_wgs.end(), fb_wgs_std.begin(), fb_wgs_std.end());       // one list on the device: the default ranges, then the others
         auto cleanup = [&] { hipFree(coef); hipFree(d_list); hipFree(d_base); hipFree(d_wgs); };
         if (hipMalloc((void **)&coef, du * 64 * sizeof(int16_t)) != hipSuccess || hipMalloc((void **)&d_list, fb.size() * sizeof(uint32_t)) != hipSuccess ||
             hipMalloc((void **)&d_base, fb.size() * sizeof(uint64_t)) != hipSuccess || hipMalloc((void **)&d_wgs, fb_wgs.size() * sizeof(PjdDevIdctWg)) != hipSuccess) {
@@ -717,7 +740,12 @@ int settle(pjd_batch *b)
         if (e == hipSuccess) {
             if (ev0) (void)hipEventRecord(ev0, s);
             pjd_launch_huff_sequential(s, dv, d_list, d_base, (uint32_t)fb.size());
-            pjd_launch_idct_colour(s, dv, d_wgs, d_base, (uint32_t)fb_wgs.size(), P.scaled, P.planar);
+            pjd_launch_idct_colour(s, dv, d_wgs, d_base, (uint32_t)n_def, P.scaled, P.planar);
+            if (n_std) {
+                // flagged pictures: their planes again, then the colour launch (all flagged pictures of the batch: a rare path)
+                pjd_launch_idct_std_dense(s, dv, d_wgs + n_def, d_base, (uint32_t)n_std, b->d_planes);
+                pjd_launch_colour_std(s, dv, b->d_cwgs_std, (uint32_t)P.cwgs_std.size(), b->d_planes);
+            }
             if (ev1) (void)hipEventRecord(ev1, s);
             // the pictures just decoded again changed in the intermediate: resample (the whole batch: a rare path)
             if (b->resized) b->launch_resize(s, P.planar);
@@ -950,6 +978,46 @@ int pjd_resize_tap(uint32_t src_n, uint32_t dst_n, uint32_t i, uint32_t *i0, uin
     if (i0) *i0 = a;
     if (i1) *i1 = c;
     if (w) *w = d;
+    return PJD_OK;
+}
+
+// ---- PJD_F_LIBJPEG: the arithmetic on its own, host only (the inlines the kernels of pjd_k_backend_std.hip run) -----------------------
+int pjd_libjpeg_idct(const int16_t coef[64], const uint16_t q[64], uint8_t out[64])
+{
+    if (!coef || !q || !out) return PJD_E_ARG;
+    uint32_t ws[64];
+    for (int c = 0; c < 8; c++) {
+        uint32_t x[8], o[8];
+        for (int j = 0; j < 8; j++) x[j] = pjd_lj_dequant(coef[j * 8 + c], q[j * 8 + c]);
+        pjd_lj_idct1d(x, o);
+        for (int j = 0; j < 8; j++) ws[j * 8 + c] = pjd_lj_descale<PJD_LJ_PASS1_SHIFT>(o[j]);
+    }
+    for (int r = 0; r < 8; r++) {
+        uint32_t o[8];
+        pjd_lj_idct1d(ws + r * 8, o);
+        for (int j = 0; j < 8; j++) out[r * 8 + j] = (uint8_t)pjd_lj_sample(o[j]);
+    }
+    return PJD_OK;
+}
+
+int pjd_libjpeg_ycc_to_rgb(uint8_t y, uint8_t cb, uint8_t cr, uint8_t rgb[3])
+{
+    if (!rgb) return PJD_E_ARG;
+    int r, g, b;
+    pjd_lj_ycc_to_rgb(y, cb, cr, r, g, b);
+    rgb[0] = (uint8_t)r; rgb[1] = (uint8_t)g; rgb[2] = (uint8_t)b;
+    return PJD_OK;
+}
+
+int pjd_libjpeg_upsample_row(const uint8_t *cur, const uint8_t *nb, int v, uint32_t n, uint8_t *out)
+{
+    (void)v;                             // which neighbour `nb` is (0: the row above, 1: the row below) changes nothing in the arithmetic
+    if (!cur || !out || n == 0 || n > (1u << 30)) return PJD_E_ARG;
+    for (uint32_t X = 0; X < 2 * n; X += 4) {
+        int c[4];
+        pjd_lj_upsample4(cur, nb, n, X, c);
+        for (uint32_t k = 0; k < 4 && X + k < 2 * n; k++) out[X + k] = (uint8_t)c[k];
+    }
     return PJD_OK;
 }
 

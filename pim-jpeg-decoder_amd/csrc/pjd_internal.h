@@ -124,6 +124,9 @@
 #define PJD_IF_PLANAR           256u // output is planar R, G, B (PJD_OUT_RGB8_PLANAR): three planes of out_stride x output rows bytes; a property of
                                      // the whole batch (the planar back-end kernels are launched for it), never together with PJD_IF_BMP
 
+#define PJD_IF_LIBJPEG          512u // PJD_F_LIBJPEG: the picture is libjpeg's (islow IDCT, fancy upsampling, JFIF colour): the back end of pjd_k_backend_std.hip;
+                                     // always together with PJD_IF_STANDARD_ZIGZAG and PJD_IF_STANDARD_RESTART
+
 // status word per image: low 8 bits = PJD_ST_* class, bit 8 = "fast path gave up, needs exact kernel"
 #define PJD_STW_NEEDS_EXACT 0x100
 
@@ -197,7 +200,7 @@ struct PjdDevImage {
     uint8_t  pad_;
     uint32_t pscan_base, n_pscan;      // progressive frames: their scans in PjdDevBatch::pscans
     uint32_t lane_cap;                 // slots of one lane region of THIS image: PJD_LANE_CAP(sub_bytes, min symbol bits of its table set)
-    uint32_t pad2_;
+    uint32_t plane_off256;             // PJD_IF_LIBJPEG: the picture's component planes in the batch's plane buffer, in units of 256 bytes (pjd_k_backend_std.hip)
     uint64_t ent_base;                 // first slot of lane `lane_base` in PjdDevBatch::ent; lane q of the image owns [ent_base + (q - lane_base) * lane_cap, + lane_cap)
 };
 

@@ -20,10 +20,8 @@
 // pass is bank-conflict free), pictures are written once.
 #include <cstdlib>
 
-#include "pjd_device_common.h"
-#include "pjd_kernels.h"
+#include "pjd_k_backend_common.h"
 
-#define TILE_STRIDE 72   // int16 per data unit in LDS: 64 + 8 pad (144 B = 36 banks)
 
 // ---------------------------------------------------------------------------------------------
 // Literal DPU payload: metadata u32[276] + mcus i16[19200] per DPU.
@@ -176,14 +174,6 @@ __global__ __launch_bounds__(256) void pjd_k_image_verdict(PjdDevBatch B)
     else if (has_err) B.status[i] = (int32_t)((s.err_key >> 1) & 7u);
 }
 
-// Data units of a range [first_du, first_du + n_du) the back end materialises: all of them, or those up to the picture's first
-// entropy-coding error (the unit that holds it included, unless the error is in its DC symbol: pjd_internal.h, PjdDevImState).
-__device__ __forceinline__ uint32_t pjd_units_decoded(unsigned long long err_key, uint32_t first_du, uint32_t n_du)
-{
-    if (err_key == ~0ull) return n_du;
-    const uint32_t stop = (uint32_t)((err_key >> 4) & 0x0fffffffu) + ((err_key & 1u) ? 0u : 1u);
-    return stop <= first_du ? 0u : (stop - first_du < n_du ? stop - first_du : n_du);
-}
 
 __global__ __launch_bounds__(PJD_DC_BLOCK) void pjd_k_lane_dc_local(PjdDevBatch B)
 {
@@ -294,8 +284,6 @@ __device__ __forceinline__ void pjd_tile_col(int16_t (*tile)[TILE_STRIDE], uint3
 template <bool PLANAR = false>
 __device__ __forceinline__ void pjd_colour_dispatch_scaled(const int16_t (*tile)[TILE_STRIDE], const uint32_t *mcu_xy, const PjdDevBatch &B,
                                                            const PjdDevImage &im, const PjdDevIdctWg &wg, uint32_t tid);
-// One dword whatever its address: gfx950 global stores need no alignment (planar pictures start at any byte the caller binds)
-struct __attribute__((packed)) PjdPx4 { uint32_t a; };
 template <bool DO_IDCT, bool SCALED, bool PLANAR = false>
 __device__ __forceinline__ void pjd_tile_to_pixels(int16_t (*tile)[TILE_STRIDE], uint32_t *mcu_xy, const PjdDevBatch &B,
                                                    const PjdDevImage &im, const PjdDevIdctWg &wg, uint32_t tid)
@@ -427,7 +415,6 @@ __device__ __forceinline__ void pjd_tile_to_pixels(int16_t (*tile)[TILE_STRIDE],
 // (reference src/decoder_dpu.c:376-382) are computed once per sample.  A wave sweeps one row group across all MCUs of
 // the workgroup: its stores cover whole runs of a picture row.
 // ---------------------------------------------------------------------------------------------
-struct __attribute__((packed)) PjdPx12 { uint32_t a, b, c; };
 
 // PLANAR (never with BMP): three 4-byte stores, one per plane, instead of the 12-byte store; `stride` is the plane row (= width) and
 // `plane` the bytes of a plane.  A wave's store instruction then covers runs of one plane row, a dword per lane.
@@ -562,24 +549,6 @@ __device__ __forceinline__ void pjd_colour_store(const int16_t (*tile)[TILE_STRI
     }
 }
 
-// BMP file header exactly as reference src/bmp_writer.cpp:32-41
-__device__ __forceinline__ void pjd_bmp_header(uint8_t *out, uint32_t width, uint32_t height, uint32_t stride, uint32_t tid)
-{
-    if (tid >= 26) return;
-    const uint32_t size = 26 + height * stride;
-    uint8_t hb = 0;
-    switch (tid) {
-        case 0: hb = 'B'; break;  case 1: hb = 'M'; break;
-        case 2: hb = size & 255; break; case 3: hb = (size >> 8) & 255; break;
-        case 4: hb = (size >> 16) & 255; break; case 5: hb = (size >> 24) & 255; break;
-        case 10: hb = 0x1A; break; case 14: hb = 12; break;
-        case 18: hb = width & 255; break; case 19: hb = (width >> 8) & 255; break;
-        case 20: hb = height & 255; break; case 21: hb = (height >> 8) & 255; break;
-        case 22: hb = 1; break; case 24: hb = 24; break;
-        default: hb = 0;
-    }
-    out[tid] = hb;
-}
 
 // ---------------------------------------------------------------------------------------------
 // Reduced-size output (PJD_F_SCALE_*, include/pjd.h): output pixel (i, j) is the rounded mean of the clamped 8-bit colours of the
@@ -792,40 +761,6 @@ __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_colour_planar(Pjd
 // entry follow from the head and the entries before it in the group; it de-zigzags and dequantises into the LDS tile.
 // ---------------------------------------------------------------------------------------------
 
-// Inclusive scans over the 64 lanes of a wave with DPP moves (VALU only, no LDS round trips): shifts inside each row of
-// 16 lanes, then the last lane of a row broadcast into the following rows.  Values are unsigned; 0 is the identity of both.
-#define PJD_DPP_STEP(OP, v, ctrl, rmask)                                                               \
-    do { const uint32_t t_ = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(v), ctrl, rmask, 0xf, false); v = OP(v, t_); } while (0)
-__device__ __forceinline__ uint32_t pjd_op_add(uint32_t a, uint32_t b) { return a + b; }
-__device__ __forceinline__ uint32_t pjd_op_max(uint32_t a, uint32_t b) { return a > b ? a : b; }
-__device__ __forceinline__ uint32_t pjd_op_pkadd(uint32_t a, uint32_t b)
-{
-    typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-    return __builtin_bit_cast(uint32_t, (u16x2)(__builtin_bit_cast(u16x2, a) + __builtin_bit_cast(u16x2, b)));
-}
-__device__ __forceinline__ uint32_t pjd_op_pksub(uint32_t a, uint32_t b)
-{
-    typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-    return __builtin_bit_cast(uint32_t, (u16x2)(__builtin_bit_cast(u16x2, a) - __builtin_bit_cast(u16x2, b)));
-}
-#define PJD_WAVE_SCAN(OP, v)                                                                           \
-    do {                                                                                                \
-        PJD_DPP_STEP(OP, v, 0x111, 0xf); PJD_DPP_STEP(OP, v, 0x112, 0xf); PJD_DPP_STEP(OP, v, 0x114, 0xf);  \
-        PJD_DPP_STEP(OP, v, 0x118, 0xf); PJD_DPP_STEP(OP, v, 0x142, 0xa); PJD_DPP_STEP(OP, v, 0x143, 0xc);  \
-    } while (0)
-// the inclusive value of the lane before (0 in lane 0)
-__device__ __forceinline__ uint32_t pjd_wave_prev(uint32_t v)
-{
-    const uint32_t r = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
-    return r;
-}
-
-// tile[u][pos] = v (low 16 bits), the row offset by one full-rate multiply-add
-__device__ __forceinline__ void pjd_tile_put(uint32_t tile_lds, uint32_t u, uint32_t pos, uint32_t v)
-{
-    const uint32_t a = pjd_mad_u24(u, TILE_STRIDE * 2u, tile_lds + 2u * pos);
-    *reinterpret_cast<__attribute__((address_space(3))) int16_t *>(a) = (int16_t)v;
-}
 
 // One back-end range (PjdDevIdctWg `iwg`) by the whole workgroup; the LDS arrays are the kernel's.  Returns are workgroup-uniform.
 // SCALED: pictures with an output scale take the scaled store.  PLANAR: the batch's output format is PJD_OUT_RGB8_PLANAR.
@@ -833,173 +768,7 @@ template <bool SCALED, bool PLANAR = false>
 __device__ __forceinline__ void pjd_idct_range(const PjdDevBatch &B, uint32_t iwg, int16_t (*tile)[TILE_STRIDE], uint32_t (*qz)[64], uint32_t *mcu_xy,
                                                uint8_t *comp_of, uint8_t *du_head, uint32_t *wagg, uint32_t *ltab)
 {
-    const PjdDevIdctWg wg = B.iwgs[iwg];
-    const PjdDevImage &im = B.images[wg.image];
-    if ((im.flags & PJD_IF_SEQUENTIAL) || (B.status[wg.image] & PJD_STW_NEEDS_EXACT)) return;   // the dense path redoes it
-    const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const uint32_t dus = im.dus_per_mcu, nl = im.n_luma;
-    const uint32_t n_du = wg.n_mcu * dus;
-    const uint32_t RI = im.restart_interval;
-
-    const bool quirk = !(im.flags & PJD_IF_STANDARD_ZIGZAG);    // the reference's zigzag_map[48] = 38 (default)
-    // The reference's zigzag quirk: slots 48 AND 52 land on natural position 38, and the later one -- slot 52, even an explicit zero --
-    // wins.  Entries of one unit may be parsed by two threads, so slot 52 is parked in the first padding cell of the unit's tile row
-    // (position 64, raw value: quantiser 1; the cell starts as PJD_COEF_SENTINEL = "no slot 52 in this unit") and moved over
-    // position 38 when the rows are done.
-    if (tid < 192) {
-        const uint32_t nat = (!quirk && (tid & 63) == 48) ? 58u : c_zz[tid & 63];
-        uint32_t v = (uint32_t)B.qtab[(size_t)wg.image * 192 + (tid & ~63u) + nat] | (nat << 16);
-        if (quirk && (tid & 63) == 52) v = 1u | (64u << 16);
-        qz[tid >> 6][tid & 63] = v;
-    }
-    // unvisited positions are zero (the reference's buffers start zeroed); a row is 9 x 16 bytes, the last of them padding
-    static_assert(TILE_STRIDE == 72, "the padding cell of a tile row is element 64");
-    // (row, 16-byte column) by shift and mask: eight zero stores per row, then the row's padding
-    for (uint32_t i = tid; i < n_du * 8; i += PJD_IDCT_THREADS)
-        *reinterpret_cast<uint4 *>(&tile[i >> 3][(i & 7) * 8]) = make_uint4(0, 0, 0, 0);
-    if (tid < n_du) *reinterpret_cast<uint4 *>(&tile[tid][64]) = make_uint4((uint32_t)(uint16_t)PJD_COEF_SENTINEL, 0, 0, 0);
-    // Tables of the range, no division per unit: component of every unit; whether it is the first unit of an MCU that starts a
-    // restart segment (the DC stage resets the predictors there); the grid position of every MCU
-    if (tid < PJD_IDCT_MAX_DU) {
-        const uint32_t ml = pjd_div_small(tid, c_recip16[dus]), kk = tid - __umul24(ml, dus);   // the range starts on an MCU boundary
-        comp_of[tid] = (uint8_t)(kk < nl ? 0 : kk - nl + 1);
-        if (kk != 0) du_head[tid] = 0;                          // the entries of first units come from the MCU's thread
-    }
-    if (tid < wg.n_mcu) {                                       // the only divisions: one per MCU, none per unit
-        const uint32_t m = wg.first_mcu + tid, my = m / im.mcux;
-        mcu_xy[tid] = (my << 16) | (m - my * im.mcux);
-        du_head[__umul24(tid, dus)] = (uint8_t)(m == im.first_mcu || (RI != 0 && m % RI == 0));
-    }
-
-    // units of this range that were decoded: all, unless the picture's first entropy-coding error lies in or before the range (the
-    // others keep zero coefficients, as in the reference, whose buffers start zeroed and which stops at the error)
-    const unsigned long long err_key = B.imstate[wg.image].err_key;
-    const uint32_t n_valid = pjd_units_decoded(err_key, wg.first_mcu * dus, n_du);
-    const uint32_t err_byte = (uint32_t)(err_key >> 35);       // byte of the stream the offending symbol starts in (bit positions fit 32 bits); no error: past every lane
-    const PjdDevMark mark = B.marks[iwg];
-    const uint32_t lane_end = im.lane_base + im.n_lane;
-    uint32_t q = mark.lane, n = mark.ent_off;
-    (void)n;
-    if (n_valid == 0) { q = im.lane_base; n = 0; }              // nothing to parse: the mark may never have been written
-    else if (q < im.lane_base || q >= lane_end) return;         // never on a verified image; keeps a stale mark harmless
-    // predictors at the first unit: lane start (block-relative or absolute) + block carry + sums inside the lane
-    uint32_t pred0[3];
-    {
-        const PjdDevLaneDc ld = B.lane_dc[q];
-        const uint16_t *carry = B.dc_blk + (size_t)(q / PJD_DC_BLOCK) * 8 + 4;
-#pragma unroll
-        for (int c = 0; c < 3; c++) pred0[c] = (uint32_t)ld.dc_in[c] + (ld.abs ? 0u : (uint32_t)carry[c]) + mark.acc[c];
-    }
-    __syncthreads();
-#if defined(PJD_IDCT_STOP_AFTER) && PJD_IDCT_STOP_AFTER == 0      // timing experiments only: set-up alone
-    if (tile[0][0] == 12345) B.out[0] = 1;
-    return;
-#endif
-    // ---- parse: entries -> tile, one thread per GROUP (32 bytes: a head and 14 entries, pjd_internal.h) of a lane.  The write pass
-    // left in every head where the group's first entry stands (units completed in the lane before it, slot it fills from) and with
-    // every lane the unit its first entry belongs to (PjdDevLaneInfo::first_du), so a thread walks its 14 entries on its own: a DC
-    // entry opens a unit, an AC entry lands on slot + run, the LAST bit closes the unit -- no scans over entries, no barriers
-    // between chunks (round 2: two wave scans and two barriers per 1024 entries, ~70 instructions per entry against ~25 here).
-    // Lanes are taken in windows of 32 (a range of 96 units spans 3-4 lanes of a dense picture, ~20 of 128 bytes); the window's
-    // table holds the groups before each lane, its first unit relative to the range and its entry count.
-    {
-        // ltab: [0..31] groups before lane i of the window, [32..63] first_du - U0, [64..95] entries
-        const uint32_t U0 = wg.first_mcu * dus;
-        const uint32_t tile_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) int16_t *)&tile[0][0];
-        const uint32_t g0 = mark.ent_off / PJD_GROUP;          // the range starts in this group of lane q
-        // where the NEXT range starts (its mark) bounds this one; usable when every unit of this range was decoded
-        uint32_t q_end = 0xffffffffu, g_end = 0;
-        if (n_valid == n_du && iwg + 1 < im.iwg_base + im.n_iwg) {
-            const PjdDevMark nm = B.marks[iwg + 1];
-            if (nm.lane >= q && nm.lane < lane_end) { q_end = nm.lane; g_end = nm.ent_off / PJD_GROUP; }
-        }
-        for (uint32_t qw = q; n_valid != 0; qw += 32) {
-            bool more = false;
-            if (tid < 32) {
-                const uint32_t ql = qw + tid;
-                uint32_t ng = 0, fd = 0, ne = 0;
-                if (ql < lane_end) {
-                    const PjdDevLaneInfo li = B.lane_info[ql];
-                    fd = (li.first_du & 0x0fffffffu) - U0;                  // "negative" for the lane the range starts in
-                    ne = li.n_ent;
-                    // a lane that starts BEHIND the picture's first entropy-coding error holds what the reference never decoded; when the
-                    // erring unit was still open at the error (an error in its AC part), that lane's leading entries would land in it
-                    const bool in = (ql == q || (int)fd < (int)n_valid) && (ql == q || B.lanes[ql].byte_start <= err_byte);
-                    if (in && ql <= q_end) {
-                        const uint32_t gs = ql == q ? g0 : 0u, all = (ne + PJD_GROUP - 1) / PJD_GROUP;
-                        uint32_t ge = ql == q_end ? (g_end + 1 < all ? g_end + 1 : all) : all;
-                        ng = ge > gs ? ge - gs : 0u;
-                    }
-                    more = in && ql < q_end;
-                }
-                uint32_t inc = ng;
-#pragma unroll
-                for (int off = 1; off < 32; off <<= 1) { const uint32_t t = __shfl_up(inc, off); if ((int)tid >= off) inc += t; }
-                ltab[tid] = inc - ng; ltab[32 + tid] = fd; ltab[64 + tid] = ne;
-                if (tid == 31) { wagg[0] = inc; wagg[1] = more ? 1u : 0u; }   // groups in the window; the lane behind it may belong to the range too
-            }
-            __syncthreads();
-            const uint32_t G = wagg[0];
-            const bool again = wagg[1] != 0 && qw + 32 < lane_end;
-            for (uint32_t w = tid; w < G; w += PJD_IDCT_THREADS) {
-                uint32_t li_ = 0;                                           // last lane of the window whose groups start at or before w
-#pragma unroll
-                for (uint32_t step = 16; step != 0; step >>= 1) if (ltab[li_ + step] <= w) li_ += step;
-                const uint32_t ql = qw + li_;
-                const uint32_t g = w - ltab[li_] + (ql == q ? g0 : 0u);
-                const uint32_t ne = ltab[64 + li_];
-                const uint32_t cnt = ne - g * PJD_GROUP < PJD_GROUP ? ne - g * PJD_GROUP : PJD_GROUP;      // slots of this group that are in use (even)
-                const uint4 *src = reinterpret_cast<const uint4 *>(B.ent + im.ent_base + (size_t)(ql - im.lane_base) * im.lane_cap + (size_t)g * PJD_GROUP);
-                const uint4 r0 = src[0], r1 = src[1];                       // the group: 32 bytes, 32-byte aligned
-                const uint32_t wds[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
-                const uint32_t head = wds[0];
-                uint32_t u = ltab[32 + li_] + (head >> 8);                  // unit of the group's first entry, relative to the range ("negative" before it)
-                uint32_t slot = head & 63u;                                 // 0: that entry is a DC difference; else the next free zigzag slot of the open unit
-#pragma unroll
-                for (int k = 1; k < PJD_GROUP / 2; k++) {                   // the group's step words: entry A, and entry B unless it is PJD_ENT_NONE
-                    const uint32_t sw = wds[k];
-                    const bool on = (uint32_t)(2 * k) < cnt;
-                    {   // A: ONE path for both kinds of entry (the lanes of a wave stand at DC and AC entries at once): a DC difference
-                        // (slot == 0) is an entry with "run + 1" = 1 that lands on position 0 and is DEQUANTISED like any other: the DC
-                        // stage then sums products instead of multiplying the sum -- the same number modulo 2^16, which is all the
-                        // reference keeps (src/jpeg_scanner.cpp:485-486 stores the predictor as a short, src/decoder_dpu.c:169-172 the product)
-                        const bool dc = slot == 0;
-                        const uint32_t f = dc ? 1u : sw & 31u;              // run + 1; 0: EOB
-                        const uint32_t ns = slot + f, pos = ns - 1u;        // an EOB gives slot - 1: stores nothing (below)
-                        if (on && f != 0 && pos < 64 && u < n_valid) {
-                            const int val = dc ? (int)(int16_t)(sw & 0xffffu) : (int)(sw << 16) >> 21;
-                            const uint32_t qe = qz[comp_of[u]][pos];        // (slot 52 under the quirk: position 64, quantiser 1)
-                            // the low 16 bits of value x quantiser (reference src/decoder_dpu.c:169-172) depend on the low 16 bits of both only
-                            pjd_tile_put(tile_lds, u, qe >> 16, pjd_mul_u24((uint32_t)val, qe));
-                        }
-                        if (on) {
-                            const bool last = f == 0 || ns > 63;            // EOB, or the entry landed on slot 63 (or past it: a broken stream)
-                            slot = last ? 0u : ns;
-                            u += last ? 1u : 0u;
-                        }
-                    }
-                    {   // B: the second symbol of a pair -- an AC entry of the unit A left open
-                        const uint32_t f = (sw >> 16) & 31u;
-                        const bool onb = on && f <= 16;                     // PJD_ENT_NONE: "run + 1" = 31
-                        const uint32_t pos = slot + f - 1u;
-                        if (onb && f != 0 && pos < 64 && u < n_valid) {
-                            const int val = (int)sw >> 21;
-                            const uint32_t qe = qz[comp_of[u]][pos];
-                            pjd_tile_put(tile_lds, u, qe >> 16, pjd_mul_u24((uint32_t)val, qe));
-                        }
-                        if (onb) {
-                            const uint32_t ns = slot + f;
-                            const bool last = f == 0 || ns > 63;
-                            slot = last ? 0u : ns;
-                            u += last ? 1u : 0u;
-                        }
-                    }
-                }
-            }
-            __syncthreads();
-            if (!again) break;
-        }
-    }
+#include "pjd_k_lanes_parse_body.h"
 #if defined(PJD_IDCT_STOP_AFTER) && PJD_IDCT_STOP_AFTER == 1      // timing experiments only (tools/r2_occ.sh): pictures are wrong
     if (tile[0][0] == 12345) B.out[0] = 1;
     return;
@@ -1013,34 +782,7 @@ __device__ __forceinline__ void pjd_idct_range(const PjdDevBatch &B, uint32_t iw
             pjd_tile_row(tile, u, r);
         }
     } else {
-        // the parser left DEQUANTISED differences: the predictors that enter the range are scaled the same way (all modulo 2^16)
-        const uint32_t q0y = qz[0][0] & 0xffffu, q0b = qz[1][0] & 0xffffu, q0r = qz[2][0] & 0xffffu;
-        uint32_t cy = (pred0[0] * q0y) & 0xffffu, cc = ((pred0[1] * q0b) & 0xffffu) | ((pred0[2] * q0r) << 16);   // predictors entering the next group of 64 units
-        for (uint32_t base = 0; base < n_du; base += 64) {
-            const uint32_t u = base + lane;
-            const bool on = u < n_valid;                        // an undecoded unit keeps DC 0: it is never predicted
-            const uint32_t us = on ? u : 0u, comp = comp_of[us];
-            const uint32_t dv = on ? (uint32_t)(uint16_t)tile[us][0] : 0u;             // the unit's DC difference as the parser left it (zero if the unit has none)
-            const bool head = on && du_head[us] != 0;
-            // sums since the group start (inclusive), Y | Cb, Cr packed; then the same sums at the last head at or before the unit
-            uint32_t vy = comp == 0 ? dv : 0u, vc = comp == 1 ? dv : (comp == 2 ? dv << 16 : 0u);
-            PJD_WAVE_SCAN(pjd_op_add, vy);
-            PJD_WAVE_SCAN(pjd_op_pkadd, vc);
-            uint32_t hpos = head ? lane + 1 : 0u;               // 1 + lane of the last head at or before this unit
-            PJD_WAVE_SCAN(pjd_op_max, hpos);
-            // a head resets the predictors BEFORE its own difference is added: subtract the sums just before it
-            const uint32_t hl = hpos ? hpos - 1 : 0u;           // lane of that head
-            const uint32_t by = __shfl(vy, (int)hl) - __shfl(comp == 0 ? dv : 0u, (int)hl);
-            const uint32_t bc = __shfl(vc, (int)hl), bc_own = __shfl(comp == 1 ? dv : (comp == 2 ? dv << 16 : 0u), (int)hl);
-            uint32_t ty = vy, tc = vc;
-            if (hpos) { ty -= by; tc = pjd_op_pksub(tc, pjd_op_pksub(bc, bc_own)); }
-            else { ty += cy; tc = pjd_op_pkadd(tc, cc); }
-            if (on) {
-                const uint32_t dcv = comp == 0 ? ty : (comp == 1 ? tc : tc >> 16);
-                tile[u][0] = (int16_t)dcv;
-            }
-            cy = __shfl(ty, 63); cc = __shfl(tc, 63);
-        }
+#include "pjd_k_lanes_dc_body.h"
     }
     // ---- IDCT (reference src/decoder_dpu.c:210-321): rows, then columns; then colour
     __syncthreads();

@@ -1,0 +1,74 @@
+// pjd_k_backend_common.h -- what the back-end units (pjd_k_backend.hip, pjd_k_backend_std.hip) share: the LDS tile row, the
+// range of decoded units, the wide stores, the BMP header, the wave scans of the DC stage and the tile store of the entry parser.
+#pragma once
+#include "pjd_device_common.h"
+#include "pjd_kernels.h"
+
+#define TILE_STRIDE 72   // int16 per data unit in LDS: 64 + 8 pad (144 B = 36 banks)
+
+// Data units of a range [first_du, first_du + n_du) the back end materialises: all of them, or those up to the picture's first
+// entropy-coding error (the unit that holds it included, unless the error is in its DC symbol: pjd_internal.h, PjdDevImState).
+__device__ __forceinline__ uint32_t pjd_units_decoded(unsigned long long err_key, uint32_t first_du, uint32_t n_du)
+{
+    if (err_key == ~0ull) return n_du;
+    const uint32_t stop = (uint32_t)((err_key >> 4) & 0x0fffffffu) + ((err_key & 1u) ? 0u : 1u);
+    return stop <= first_du ? 0u : (stop - first_du < n_du ? stop - first_du : n_du);
+}
+
+// One dword whatever its address: gfx950 global stores need no alignment (planar pictures start at any byte the caller binds)
+struct __attribute__((packed)) PjdPx4 { uint32_t a; };
+struct __attribute__((packed)) PjdPx12 { uint32_t a, b, c; };
+
+// BMP file header exactly as reference src/bmp_writer.cpp:32-41
+__device__ __forceinline__ void pjd_bmp_header(uint8_t *out, uint32_t width, uint32_t height, uint32_t stride, uint32_t tid)
+{
+    if (tid >= 26) return;
+    const uint32_t size = 26 + height * stride;
+    uint8_t hb = 0;
+    switch (tid) {
+        case 0: hb = 'B'; break;  case 1: hb = 'M'; break;
+        case 2: hb = size & 255; break; case 3: hb = (size >> 8) & 255; break;
+        case 4: hb = (size >> 16) & 255; break; case 5: hb = (size >> 24) & 255; break;
+        case 10: hb = 0x1A; break; case 14: hb = 12; break;
+        case 18: hb = width & 255; break; case 19: hb = (width >> 8) & 255; break;
+        case 20: hb = height & 255; break; case 21: hb = (height >> 8) & 255; break;
+        case 22: hb = 1; break; case 24: hb = 24; break;
+        default: hb = 0;
+    }
+    out[tid] = hb;
+}
+
+// Inclusive scans over the 64 lanes of a wave with DPP moves (VALU only, no LDS round trips): shifts inside each row of
+// 16 lanes, then the last lane of a row broadcast into the following rows.  Values are unsigned; 0 is the identity of both.
+#define PJD_DPP_STEP(OP, v, ctrl, rmask)                                                               \
+    do { const uint32_t t_ = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(v), ctrl, rmask, 0xf, false); v = OP(v, t_); } while (0)
+__device__ __forceinline__ uint32_t pjd_op_add(uint32_t a, uint32_t b) { return a + b; }
+__device__ __forceinline__ uint32_t pjd_op_max(uint32_t a, uint32_t b) { return a > b ? a : b; }
+__device__ __forceinline__ uint32_t pjd_op_pkadd(uint32_t a, uint32_t b)
+{
+    typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+    return __builtin_bit_cast(uint32_t, (u16x2)(__builtin_bit_cast(u16x2, a) + __builtin_bit_cast(u16x2, b)));
+}
+__device__ __forceinline__ uint32_t pjd_op_pksub(uint32_t a, uint32_t b)
+{
+    typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+    return __builtin_bit_cast(uint32_t, (u16x2)(__builtin_bit_cast(u16x2, a) - __builtin_bit_cast(u16x2, b)));
+}
+#define PJD_WAVE_SCAN(OP, v)                                                                           \
+    do {                                                                                                \
+        PJD_DPP_STEP(OP, v, 0x111, 0xf); PJD_DPP_STEP(OP, v, 0x112, 0xf); PJD_DPP_STEP(OP, v, 0x114, 0xf);  \
+        PJD_DPP_STEP(OP, v, 0x118, 0xf); PJD_DPP_STEP(OP, v, 0x142, 0xa); PJD_DPP_STEP(OP, v, 0x143, 0xc);  \
+    } while (0)
+// the inclusive value of the lane before (0 in lane 0)
+__device__ __forceinline__ uint32_t pjd_wave_prev(uint32_t v)
+{
+    const uint32_t r = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
+    return r;
+}
+
+// tile[u][pos] = v (low 16 bits), the row offset by one full-rate multiply-add
+__device__ __forceinline__ void pjd_tile_put(uint32_t tile_lds, uint32_t u, uint32_t pos, uint32_t v)
+{
+    const uint32_t a = pjd_mad_u24(u, TILE_STRIDE * 2u, tile_lds + 2u * pos);
+    *reinterpret_cast<__attribute__((address_space(3))) int16_t *>(a) = (int16_t)v;
+}

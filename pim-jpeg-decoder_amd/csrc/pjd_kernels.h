@@ -66,6 +66,12 @@ void pjd_launch_group_idct(hipStream_t s, const PjdDevBatch &b, const PjdDevGrou
 // pull back end (pjd_internal.h): the launch that runs beside the entropy decoder, and the sweep over what it left
 void pjd_launch_idct_pull(hipStream_t s, const PjdDevBatch &b);
 void pjd_launch_idct_sweep(hipStream_t s, const PjdDevBatch &b);
+// ---- back end of PJD_F_LIBJPEG pictures (pjd_k_backend_std.hip): component planes (islow IDCT) from the lane streams (order[k]: index into
+// iwgs / marks) or from the dense scratch (wgs, dense_base as for pjd_launch_idct_colour), then upsample + colour + store
+// (cwgs[k] = {image, first 4-pixel item, -, -}); `planes` is the batch's plane buffer (PjdDevImage::plane_off256)
+void pjd_launch_idct_std_lanes(hipStream_t s, const PjdDevBatch &b, const uint32_t *order, uint32_t n_wg, uint8_t *planes);
+void pjd_launch_idct_std_dense(hipStream_t s, const PjdDevBatch &b, const PjdDevIdctWg *wgs, const uint64_t *dense_base, uint32_t n_wg, uint8_t *planes);
+void pjd_launch_colour_std(hipStream_t s, const PjdDevBatch &b, const PjdDevIdctWg *cwgs, uint32_t n_wg, uint8_t *planes);
 // ---- resize on decode (pjd_k_resize.hip): every picture of the batch from `src` (interleaved RGB8, or planar) to its target size in `dst`
 // (the same layout), one launch whatever the batch asked for; tile_prefix[i] = tiles of the pictures before i, tile_prefix[n_images] =
 // n_tiles.  norm.dtype != 0: the samples leave as fp16 / bf16 / fp32 elements, v * scale[c] + bias[c] (pjd_batch_set_normalize); the

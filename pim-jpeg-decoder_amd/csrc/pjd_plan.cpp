@@ -222,10 +222,21 @@ int pjd_make_plan(const pjd_image_desc *images, int n, int out_format, PjdPlan &
     std::vector<uint32_t> &tset_step_bits = P.tset_step_bits;      // per set: fewest bits per step of the write pass, x 256 (min_step_bits_x256)
     uint64_t ent_off = 0;                          // slots of the lane regions handed out so far
     for (int i = 0; i < n; i++) {
-        const pjd_image_desc &d = images[i];
+        pjd_image_desc d = images[i];
+        const bool lj = (d.flags & PJD_F_LIBJPEG) != 0;
+        if (lj) d.flags |= PJD_F_STANDARD_ZIGZAG | PJD_F_STANDARD_RESTART;       // implied: libjpeg's picture has no other reading
         PjdDevImage &g = P.images[i];
         PjdHostImage &h = P.host[i];
         std::memset(&g, 0, sizeof g);
+        if (lj) {
+            // the envelope of the mode (include/pjd.h)
+            if (d.flags & PJD_F_SCALE_MASK) { err = fmt("image %d: PJD_F_LIBJPEG takes no output scale (PJD_F_SCALE_*)", i); return PJD_E_ARG; }
+            if (d.shard_n_segs != 0) { err = fmt("image %d: PJD_F_LIBJPEG takes no shard", i); return PJD_E_ARG; }
+            if (d.num_components == 2) { err = fmt("image %d: PJD_F_LIBJPEG takes one or three components", i); return PJD_E_ARG; }
+            if (d.num_components == 3 && d.h_samp == 1 && d.v_samp == 2) { err = fmt("image %d: PJD_F_LIBJPEG does not take 4:4:0 (h1v2) sampling", i); return PJD_E_ARG; }
+            g.flags |= PJD_IF_LIBJPEG;
+            P.libjpeg = true;
+        }
 
         // ---- envelope: exactly what the reference scanner lets through (jpeg_scanner.cpp:187-285)
         if (d.width == 0 || d.height == 0 || d.width > 65535 || d.height > 65535) { err = fmt("image %d: bad dimensions", i); return PJD_E_ARG; }
@@ -586,16 +597,25 @@ int pjd_make_plan(const pjd_image_desc *images, int n, int out_format, PjdPlan &
         du_total += g.n_du;
         if (sequential) { g.dense_base = dense_seq; dense_seq += g.n_du; }
         g.idct_mcus = PJD_IDCT_MAX_DU / g.dus_per_mcu;
-        g.iwg_base = (uint32_t)(sequential ? P.iwgs_dense.size() : P.iwgs.size());
+        std::vector<PjdDevIdctWg> &iwg_list = sequential ? (lj ? P.iwgs_dense_std : P.iwgs_dense) : P.iwgs;
+        g.iwg_base = (uint32_t)iwg_list.size();
         for (uint32_t m = g.first_mcu; m < g.last_mcu; m += g.idct_mcus) {
             PjdDevIdctWg w;
             w.image = (uint32_t)i;
             w.first_mcu = m;
             w.n_mcu = (g.last_mcu - m < g.idct_mcus) ? g.last_mcu - m : g.idct_mcus;
             w.pad_ = sequential ? (uint32_t)(P.seq_images.size() - 1) : 0;   // dense path: which entry of the scratch-base list
-            (sequential ? P.iwgs_dense : P.iwgs).push_back(w);
+            iwg_list.push_back(w);
         }
-        g.n_iwg = (uint32_t)(sequential ? P.iwgs_dense.size() : P.iwgs.size()) - g.iwg_base;
+        g.n_iwg = (uint32_t)iwg_list.size() - g.iwg_base;
+        if (lj) {
+            // component planes, whole MCUs: Y, then Cb and Cr of a three-component picture; the colour launch's items of four pixels
+            g.plane_off256 = (uint32_t)(P.plane_bytes / 256);
+            const uint64_t cpl = (uint64_t)g.mcux * 8 * g.mcuy * 8;
+            P.plane_bytes = align_up(P.plane_bytes + cpl * g.n_luma + (g.ncomp == 3 ? 2 * cpl : 0), 256);
+            const uint32_t items = ((g.width + 3) / 4) * g.height;
+            for (uint32_t it = 0; it < items; it += PJD_IDCT_THREADS) P.cwgs_std.push_back(PjdDevIdctWg{(uint32_t)i, it, 0, 0});
+        }
         h.out_bytes = pjd_image_output_size(&d, out_format);
         g.out_off = out_off;
         out_off = align_up(out_off + h.out_bytes, 256);
@@ -684,6 +704,15 @@ int pjd_make_plan(const pjd_image_desc *images, int n, int out_format, PjdPlan &
             close_group(P.hwgs.size());
             if (P.groups.size() < 2) { P.groups.clear(); P.group_images.clear(); P.iwg_order.clear(); }
         }
+    }
+    if (P.libjpeg) {
+        // one chain of launches, the lane-stream back ends over two lists of ranges: the default kernels never see a flagged picture
+        P.groups.clear(); P.group_images.clear(); P.iwg_order.clear();
+        for (int pass = 0; pass < 2; pass++)
+            for (uint32_t k = 0; k < P.iwgs.size(); k++)
+                if (((P.images[P.iwgs[k].image].flags & PJD_IF_LIBJPEG) != 0) == (pass == 1)) P.iwg_order.push_back(k);
+        for (const PjdDevIdctWg &w : P.iwgs) (P.images[w.image].flags & PJD_IF_LIBJPEG ? P.n_iwg_std : P.n_iwg_def)++;
+        if (P.plane_bytes >= (1ull << 40)) { err = "batch needs too large a plane buffer"; return PJD_E_ARG; }
     }
     // the lane-word kernel copies PJD_WORD_ROWS words from every lane's first byte, whatever the lane's length
     P.ecs_buf_bytes = align_up(ecs_off + PJD_SUB_BYTES_MAX + 64, 256);

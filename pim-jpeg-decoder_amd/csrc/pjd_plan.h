@@ -54,6 +54,13 @@ struct PjdPlan {
     uint64_t pixels = 0, ecs_bytes = 0, out_bytes = 0;   // pixels: of the source pictures; out_bytes: of the (scaled) output
     bool scaled = false;                   // some picture has an output scale (PJD_F_SCALE_*): the back end's scaled kernels
     bool planar = false;                   // PJD_OUT_RGB8_PLANAR: the back end's planar kernels
+    // PJD_F_LIBJPEG (pjd_k_backend_std.hip).  A batch that holds such a picture decodes as one chain of launches (no picture groups), and its
+    // lane-stream back ends are launched over iwg_order: first the n_iwg_def ranges of the other pictures, then the n_iwg_std of the flagged
+    bool libjpeg = false;
+    uint32_t n_iwg_def = 0, n_iwg_std = 0;
+    std::vector<PjdDevIdctWg> iwgs_dense_std;   // flagged pictures routed to the exact kernel up front: their ranges (not in iwgs_dense)
+    std::vector<PjdDevIdctWg> cwgs_std;         // work list of the colour launch: {image, first item, 0, 0}, PJD_IDCT_THREADS items each
+    uint64_t plane_bytes = 0;                   // the plane buffer: Y, Cb, Cr of every flagged picture, padded to whole MCUs
     int plan_mode = 0;                     // PJD_PLAN_*
     std::vector<uint32_t> tset_step_bits;  // per table set: fewest bits of stream per step of the write pass, x 256 (sizes the lane regions)
 };

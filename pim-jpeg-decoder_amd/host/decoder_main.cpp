@@ -22,6 +22,8 @@
 // (not reference behaviour: the reference rejects the file; its four progressive procedures are what the kernel is pinned to).
 // --scale 1/2|1/4|1/8 (and 1/1): pictures are written at that scale, as `djpeg -scale` does -- each output pixel the rounded mean of
 // its box of source pixels (PJD_F_SCALE_* of include/pjd.h); in every mode.  Any other value is a usage error.
+// --libjpeg: the pictures are the ones libjpeg decodes, bit for bit (PJD_F_LIBJPEG of include/pjd.h: islow IDCT, fancy upsampling, JFIF
+// colour) instead of the reference's; with --pipeline and --progressive, not with a --scale other than 1/1 and not with --split.
 #include <sys/stat.h>
 #include <time.h>
 
@@ -169,7 +171,7 @@ int main(int argc, char **argv)
 {
     int device = 0;
     size_t batch_images = 1024;
-    bool pipeline = false, split = false;
+    bool pipeline = false, split = false, libjpeg = false;
     uint32_t scan_options = 0, image_flags = 0;
     bool bad_args = false;
     int slots = 0, scan_threads = 0, write_threads = 0;
@@ -191,6 +193,7 @@ int main(int argc, char **argv)
         else if (!std::strcmp(argv[i], "--pipeline")) pipeline = true;
         else if (!std::strcmp(argv[i], "--split")) split = true;
         else if (!std::strcmp(argv[i], "--progressive")) scan_options |= PJD_SCAN_PROGRESSIVE;
+        else if (!std::strcmp(argv[i], "--libjpeg")) libjpeg = true;
         else if (!std::strcmp(argv[i], "--scale")) {
             const char *v = i + 1 < argc ? argv[++i] : "";
             if (!std::strcmp(v, "1/1")) image_flags = 0;
@@ -207,6 +210,11 @@ int main(int argc, char **argv)
     if (files.empty() || bad_args) {
         std::cout << "Error - Invalid arguments\n";
         return 1;
+    }
+    if (libjpeg) {
+        if (image_flags & PJD_F_SCALE_MASK) { std::cout << "Error - --libjpeg takes no --scale other than 1/1 (libjpeg's reduced decodes are other filters)\n"; return 1; }
+        if (split) { std::cout << "Error - --libjpeg cannot be combined with --split (its upsampling reads across the rows a device decodes)\n"; return 1; }
+        image_flags |= PJD_F_LIBJPEG;
     }
     // ascending file size, like sort_by_size (decoder_host.cpp:46-61)
     std::vector<std::pair<long long, std::string>> sized;

@@ -20,6 +20,7 @@ OUT_RGB8_PLANAR = 2      # uint8[3][H][W]: the R, G and B planes one after the o
 PLAN_LATENCY, PLAN_THROUGHPUT = 0, 1      # pjd_set_plan_mode
 F_STANDARD_RESTART, F_FORCE_SEQUENTIAL, F_STANDARD_ZIGZAG, F_PROGRESSIVE = 1, 2, 4, 8
 F_SCALE_1_2, F_SCALE_1_4, F_SCALE_1_8, F_SCALE_MASK = 16, 32, 48, 48      # output scale s = 1 << ((flags >> 4) & 3) (pjd.h)
+F_LIBJPEG = 64           # the picture libjpeg decodes, bit for bit (islow IDCT, fancy upsampling, JFIF colour); implies the two F_STANDARD_* (pjd.h)
 RESIZE_BILINEAR, RESIZE_ANTIALIAS = 0, 1   # pjd_batch_set_resize_filter (pjd.h)
 RW_HFLIP = 1                               # pjd_resize_window.flags: the delivered picture mirrored left-right
 AA_MAX_TAPS = 32                           # PJD_AA_MAX_TAPS: the most taps per axis pjd_resize_aa_taps returns
@@ -199,6 +200,12 @@ def dev_lib():
         L.pjd_resize_window_check.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(ResizeWindow), i32]
         L.pjd_batch_set_normalize.restype = i32
         L.pjd_batch_set_normalize.argtypes = [vp, i32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        L.pjd_libjpeg_idct.restype = i32
+        L.pjd_libjpeg_idct.argtypes = [C.POINTER(C.c_int16), C.POINTER(C.c_uint16), C.POINTER(C.c_uint8)]
+        L.pjd_libjpeg_ycc_to_rgb.restype = i32
+        L.pjd_libjpeg_ycc_to_rgb.argtypes = [C.c_uint8, C.c_uint8, C.c_uint8, C.POINTER(C.c_uint8)]
+        L.pjd_libjpeg_upsample_row.restype = i32
+        L.pjd_libjpeg_upsample_row.argtypes = [C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), i32, C.c_uint32, C.POINTER(C.c_uint8)]
         L.pjd_normalize_value.restype = i32
         L.pjd_normalize_value.argtypes = [i32, C.c_uint32, C.c_float, C.c_float, vp]
         L.pjd_host_alloc.restype = vp
@@ -770,6 +777,43 @@ def normalize_value(dtype, v, scale, bias):
     if not 0 <= int(v) < 2 ** 32 or dev_lib().pjd_normalize_value(int(dtype), int(v), float(scale), float(bias), out) != 0:
         raise ValueError(f"normalize_value({dtype}, {v}, {scale}, {bias}): dtype DT_F16 / DT_BF16 / DT_F32, v <= 255, finite constants")
     return int.from_bytes(bytes(out[:4 if int(dtype) == DT_F32 else 2]), "little")
+
+
+def libjpeg_idct(coef, q):
+    """pjd_libjpeg_idct (host only): the 64 samples (uint8, natural order) of one unit under F_LIBJPEG -- coef (int16) times q (uint16), both
+    64 values in natural order, through libjpeg's islow IDCT; the inlines the kernel runs."""
+    c = np.ascontiguousarray(np.asarray(coef).reshape(64), np.int16)
+    qq = np.ascontiguousarray(np.asarray(q).reshape(64), np.uint16)
+    out = np.empty(64, np.uint8)
+    if dev_lib().pjd_libjpeg_idct(c.ctypes.data_as(C.POINTER(C.c_int16)), qq.ctypes.data_as(C.POINTER(C.c_uint16)), out.ctypes.data_as(C.POINTER(C.c_uint8))) != 0:
+        raise ValueError("libjpeg_idct: 64 coefficients and 64 quantisers")
+    return out
+
+
+def libjpeg_ycc_to_rgb(y, cb, cr):
+    """pjd_libjpeg_ycc_to_rgb (host only): (R, G, B) of one pixel under F_LIBJPEG; y, cb, cr in 0..255."""
+    if not all(0 <= int(v) <= 255 for v in (y, cb, cr)):
+        raise ValueError("libjpeg_ycc_to_rgb: samples are 0..255")
+    out = (C.c_uint8 * 3)()
+    if dev_lib().pjd_libjpeg_ycc_to_rgb(int(y), int(cb), int(cr), out) != 0:
+        raise ValueError("libjpeg_ycc_to_rgb refused")
+    return out[0], out[1], out[2]
+
+
+def libjpeg_upsample_row(cur, nb=None, v=0):
+    """pjd_libjpeg_upsample_row (host only): the 2n samples of one output row of fancy upsampling under F_LIBJPEG from the chroma row `cur`
+    (n samples) and, for 4:2:0, its neighbour row `nb` (the row above for v = 0, below for v = 1; None: 4:2:2)."""
+    c = np.ascontiguousarray(np.asarray(cur).reshape(-1), np.uint8)
+    nbp = None
+    if nb is not None:
+        nba = np.ascontiguousarray(np.asarray(nb).reshape(-1), np.uint8)
+        if nba.size != c.size:
+            raise ValueError("libjpeg_upsample_row: the two rows have one length")
+        nbp = nba.ctypes.data_as(C.POINTER(C.c_uint8))
+    out = np.empty(2 * c.size, np.uint8)
+    if dev_lib().pjd_libjpeg_upsample_row(c.ctypes.data_as(C.POINTER(C.c_uint8)), nbp, int(v), c.size, out.ctypes.data_as(C.POINTER(C.c_uint8))) != 0:
+        raise ValueError("libjpeg_upsample_row: at least one sample")
+    return out
 
 
 def scaled_dims(width, height, flags=0):

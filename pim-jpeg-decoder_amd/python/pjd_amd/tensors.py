@@ -35,6 +35,31 @@ statuses (fallback re-decodes included), so the returned tensors are complete an
 import pjd_amd
 
 
+def libjpeg_descs(descs):
+    """Copies of `descs` with F_LIBJPEG set (the picture libjpeg decodes, include/pjd.h); the caller's descriptors are not touched (the
+    copies share their bitstream and table memory, as prescaled_descs' do).  No device."""
+    import ctypes
+    out = []
+    for d in descs:
+        c = pjd_amd.ImageDesc()
+        ctypes.memmove(ctypes.byref(c), ctypes.byref(d), ctypes.sizeof(pjd_amd.ImageDesc))
+        c.flags = int(d.flags) | pjd_amd.F_LIBJPEG
+        out.append(c)
+    return out
+
+
+def _libjpeg(descs, libjpeg, prescale=False):
+    """The descriptors a helper decodes for its `libjpeg` keyword, checked before anything is created: the mode takes no output scale."""
+    if not libjpeg:
+        return descs
+    if prescale:
+        raise ValueError("libjpeg=True takes prescale=False: the box pre-scale (F_SCALE_*) is not libjpeg's reduced decode")
+    for i, d in enumerate(descs):
+        if int(d.flags) & pjd_amd.F_SCALE_MASK:
+            raise ValueError(f"libjpeg=True: picture {i} carries an output scale (F_SCALE_*)")
+    return libjpeg_descs(descs)
+
+
 def _scale_log(flags):
     return (int(flags) & pjd_amd.F_SCALE_MASK) >> 4
 
@@ -96,13 +121,14 @@ def _run(ctx, descs, out_format, capacity, offsets, device, resize=None, normali
     return buf, offs, st
 
 
-def decode_to_tensors(ctx, descs, planar=True, device=None, orientations=None):
+def decode_to_tensors(ctx, descs, planar=True, device=None, orientations=None, libjpeg=False):
     """Decode `descs` on `ctx` into ONE torch.uint8 buffer on the context's device -> (list of tensors, statuses).  Tensor i is
     a view of that buffer shaped (3, sh, sw) -- or (sh, sw, 3) with planar=False -- at the picture's output scale.  The tensors
     are complete on return and may be read on any torch stream (module docstring, "Stream order").
     orientations=[1..8, ...] (Scanned.orientation): every picture comes out upright, at its own size -- (3, sw, sh) for 5..8 --, the
     exact permutation of the decoded picture (the identity resample of Batch.set_resize with Batch.set_orientation).  None: as the file
-    stores them."""
+    stores them.  libjpeg=True: the pictures are libjpeg's, byte for byte (F_LIBJPEG on copies of the descriptors)."""
+    descs = _libjpeg(descs, libjpeg)
     torch = _torch()
     device = torch.device("cuda", ctx.device) if device is None else device
     sizes = None
@@ -119,10 +145,11 @@ def decode_to_tensors(ctx, descs, planar=True, device=None, orientations=None):
     return out, st
 
 
-def decode_to_batch_tensor(ctx, descs, device=None):
+def decode_to_batch_tensor(ctx, descs, device=None, libjpeg=False):
     """Pictures of ONE output size -> (uint8 tensor [N, 3, H, W], statuses): picture i is bound at offset i * 3 * H * W, so the
     result is one contiguous NCHW tensor with no copy after the decode, complete on return and readable on any torch stream.
-    ValueError (before anything is created) otherwise."""
+    ValueError (before anything is created) otherwise.  libjpeg=True: as in decode_to_tensors."""
+    descs = _libjpeg(descs, libjpeg)
     n, c, h, w = uniform_output_shape(descs)
     torch = _torch()
     device = torch.device("cuda", ctx.device) if device is None else device
@@ -336,7 +363,7 @@ def _interpolation(name):
 
 
 def decode_resized_batch_tensor(ctx, descs, size, prescale=True, device=None, antialias=False, crops=None, flips=None, resize_short=None,
-                                interpolation="bilinear", orientations=None):
+                                interpolation="bilinear", orientations=None, libjpeg=False):
     """Pictures of ANY sizes -> (uint8 tensor [N, 3, H, W], statuses), size = (H, W): every picture is resampled to H x W inside
     the decode (the bilinear filter of include/pjd.h, pjd_batch_set_resize) and lands at offset i * 3 * H * W of one buffer, so
     the result is one contiguous NCHW tensor with no copy after the decode, complete on return and readable on any torch stream
@@ -363,10 +390,14 @@ def decode_resized_batch_tensor(ctx, descs, size, prescale=True, device=None, an
     include/pjd.h, in the same launch), and crops, resize_short and flips speak about the UPRIGHT picture: crops are mapped with
     crop_to_stored, the centre crop is computed from the upright size, flips are folded into the orientation (orient_then_hflip).  The
     picture is resampled in the stored picture's coordinates and permuted on the way out, which is within each filter's one-level
-    bound of "orient, then resize".  None: today's behaviour, byte for byte."""
+    bound of "orient, then resize".  None: today's behaviour, byte for byte.
+    libjpeg=True: the picture the filters read is libjpeg's, byte for byte (F_LIBJPEG on copies of the descriptors): what a PIL or
+    torchvision.io pipeline resizes.  It takes prescale=False (ValueError before anything is created otherwise): the box pre-scale is
+    not libjpeg's reduced decode."""
     _interpolation(interpolation)
     if len(descs) == 0:
         raise ValueError("decode_resized_batch_tensor: no pictures")
+    descs = _libjpeg(descs, libjpeg, prescale)
     th, tw = int(size[0]), int(size[1])
     run, windows, oris = _plan(descs, (th, tw), prescale, crops, flips, resize_short, orientations)
     torch = _torch()
@@ -390,7 +421,8 @@ def normalize_constants(mean, std):
 
 
 def decode_normalized_batch_tensor(ctx, descs, size, mean, std, dtype=None, channels_last=False, prescale=True, device=None,
-                                   antialias=False, crops=None, flips=None, resize_short=None, interpolation="bilinear", orientations=None):
+                                   antialias=False, crops=None, flips=None, resize_short=None, interpolation="bilinear", orientations=None,
+                                   libjpeg=False):
     """Pictures of ANY sizes -> (tensor of `dtype` [N, 3, H, W], statuses), size = (H, W); dtype torch.float16 (the default),
     torch.bfloat16 or torch.float32.  As decode_resized_batch_tensor, and every sample v of channel c leaves the same launch as
     fma(v, scale[c], bias[c]) with the constants of normalize_constants(mean, std), converted once to `dtype` (include/pjd.h,
@@ -402,11 +434,12 @@ def decode_normalized_batch_tensor(ctx, descs, size, mean, std, dtype=None, chan
     pre-scale comes first), prescale=False gives exactly that up to the 16x limit.  crops, flips, resize_short: as in
     decode_resized_batch_tensor.  interpolation="bicubic": the bicubic filter (RESIZE_BICUBIC), as there -- `antialias` is not consulted,
     prescale=True still puts the box filter first, prescale=False is exactly the filter over the full-size picture up to the 16x
-    limit; any other string than "bilinear" or "bicubic" raises ValueError before anything is created.  orientations: as in
+    limit; any other string than "bilinear" or "bicubic" raises ValueError before anything is created.  orientations, libjpeg: as in
     decode_resized_batch_tensor."""
     _interpolation(interpolation)
     if len(descs) == 0:
         raise ValueError("decode_normalized_batch_tensor: no pictures")
+    descs = _libjpeg(descs, libjpeg, prescale)
     th, tw = int(size[0]), int(size[1])
     scale, bias = normalize_constants(mean, std)
     torch = _torch()
