@@ -28,6 +28,9 @@
  *                                                       window of the picture (RandomResizedCrop, Resize + CenterCrop, flip)
  *   (none: an addition)                                 pjd_batch_set_orientation: the eight EXIF orientations (mirrors, half turn,
  *                                                       quarter turns) per picture inside that launch (pjd_scanned_orientation reads the tag)
+ *   (none: an addition)                                 pjd_batch_set_resize_pad + _set_pad_value + pjd_resize_pad_check: the picture keeps
+ *                                                       its aspect ratio inside a fixed canvas and the rest is filled in that launch
+ *                                                       (letterbox: YOLO, DETR, SAM, "expand to square")
  *   (none: an addition)                                 pjd_batch_set_normalize + pjd_normalize_value: the samples leave as fp16, bf16
  *                                                       or fp32, v * scale[c] + bias[c], in that launch (the tensor a model takes)
  *   (none: an addition)                                 PJD_F_LIBJPEG + pjd_libjpeg_idct / _ycc_to_rgb / _upsample_row: the picture libjpeg
@@ -54,7 +57,8 @@ extern "C" {
  * pjd_image_desc and the exact-path figures of pjd_batch_info; version 5 pjd_batch_info::n_steps; version 6 the output scale
  * PJD_F_SCALE_* and pjd_pipe_opts::image_flags of pjd_pipeline.h).  PJD_OUT_RGB8_PLANAR and PJD_F_LIBJPEG changed no struct and
  * no version: a caller that needs one of them checks for it by its symbols (pjd_libjpeg_idct is exported from the first library that
- * knows PJD_F_LIBJPEG; an older one ignores the bit).
+ * knows PJD_F_LIBJPEG; an older one ignores the bit).  Pad on decode (pjd_batch_set_resize_pad, pjd_batch_set_pad_value) changed no
+ * struct either, so PJD_VERSION stays 6: a caller checks for it by the symbol pjd_resize_pad_check.
  * A caller built against another version must not pass its structs: check pjd_version() == PJD_VERSION after loading.     */
 #define PJD_VERSION 6
 
@@ -620,6 +624,49 @@ int  pjd_resize_window_check(uint32_t sw, uint32_t sh, uint32_t tw, uint32_t th,
  * a window per picture) is counted in pjd_batch_info::device_bytes and sent by pjd_batch_upload; an array of all 1 takes nothing
  * and launches the very kernels the batch launched before.  A BMP batch takes no resize, so it takes no orientation.           */
 int  pjd_batch_set_orientation(pjd_batch *b, const uint8_t *orientation /* n_images, each 1..8 */);
+/* ---- pad on decode: the picture as a rectangle of a fixed canvas (letterbox) -------------------------------------------------------- *
+ * pjd_batch_set_resize_pad: picture i of a resized batch fills only a rectangle of its target, and the rest of the target is set to a
+ * fill colour -- keep the aspect ratio, pad what is left -- inside the resample launch and one small launch behind it: no padded copy
+ * and no unpadded picture ever exists.
+ *
+ * THE CANVAS (normative).  out_w[i] x out_h[i] from pjd_batch_set_resize stays what is DELIVERED: the canvas.  Sizes, offsets,
+ * pjd_batch_output_size, _packed_size, bind_output and both downloads never change.
+ * THE CONTENT RECTANGLE of a record {left, top, right, bottom} is columns [left, out_w - right) and rows [top, out_h - bottom) of the
+ * canvas: cw = out_w - left - right by ch = out_h - top - bottom samples, each at least 1.
+ * THE TARGET.  From this call on, everything later calls say about "the target tw x th" is about cw x ch: for
+ * pjd_batch_set_orientation and the orientations 5..8 Q's target is ch x cw; the defaults vw = 0 and vh = 0 of a window; the rules
+ * ox + tw <= vw and oy + th <= vh; the 16x limit; the weight tables.
+ * THE DELIVERED CANVAS.  Let D be the cw x ch picture the batch would deliver to a target of that size with everything else it has --
+ * orientation, window, PJD_RW_HFLIP, filter.  Then
+ *     C[c][y][x] = D[c][y - top][x - left]      for left <= x < out_w - right and top <= y < out_h - bottom
+ *     C[c][y][x] = fill[c]                      everywhere else
+ * No new filter arithmetic.  The pad is given in the DELIVERED canvas's coordinates: neither an orientation nor PJD_RW_HFLIP moves
+ * or mirrors the rectangle; they act on D.
+ * THE FILL.  pjd_batch_set_normalize applies to C's samples, the fill included: a border element of channel c is
+ * pjd_normalize_value(dtype, fill[c], scale[c], bias[c]).  pjd_batch_set_pad_value replaces that for a normalised batch: a border
+ * element of channel c is then value[c] converted ONCE to the dtype, to nearest even (the conversions of pjd_batch_set_normalize, no
+ * fma) -- "zeros after normalisation" is value = {0, 0, 0}.
+ *
+ * CALL ORDER of pjd_batch_set_resize_pad.  After pjd_batch_set_resize; before any pjd_batch_set_orientation / _set_resize_window /
+ * _set_resize_filter / _set_normalize / _bind_output / _upload / _capture / _decode of the batch; once: PJD_E_STATE otherwise, also when
+ * no resize is set (a batch that took pjd_batch_set_normalize without a resize therefore takes no pad).  PJD_E_ARG for a null array, a
+ * null fill, or a record with left + right >= out_w or top + bottom >= out_h (the sums in 64 bits; pjd_last_error names the picture);
+ * the batch is then as it was and the call still open.  pjd_resize_pad_check is THE implementation of that test.
+ * CALL ORDER of pjd_batch_set_pad_value.  After pjd_batch_set_normalize on a batch that took pjd_batch_set_resize_pad; before
+ * _bind_output / _upload / _capture / _decode; once: PJD_E_STATE otherwise.  PJD_E_ARG for a null array or a value that is not finite.
+ * FROM THEN ON every decode writes every byte of every picture's range, border included, and no byte outside it: the content by the
+ * launch named "resize", the border by one named "pad" behind it, which write disjoint bytes; both are part of a captured graph and
+ * run again after the exact-kernel fallback of pjd_batch_sync.  Status words, partial pictures (grey in the content, fill in the
+ * border), coefficients and pjd_plan_info are unaffected; out_bytes stays the sum of the canvases.  What the call takes (a 32-byte
+ * record and a 40-byte window per picture, one prefix sum) is counted in pjd_batch_info::device_bytes and sent by pjd_batch_upload.  An
+ * array of all-zero records takes nothing: the batch launches the very kernels it launched before and delivers, byte for byte, what
+ * it delivers without the call.  A BMP batch takes no resize, so it takes no pad.
+ * VERSIONING.  No struct of this header changed, so PJD_VERSION stays 6; a caller checks for the feature by the symbol
+ * pjd_resize_pad_check.                                                                                                          */
+typedef struct pjd_resize_pad { uint32_t left, top, right, bottom; } pjd_resize_pad;
+int  pjd_batch_set_resize_pad(pjd_batch *b, const pjd_resize_pad *pad /* n_images */, const uint8_t fill[3]);
+int  pjd_batch_set_pad_value(pjd_batch *b, const float value[3]);
+int  pjd_resize_pad_check(uint32_t out_w, uint32_t out_h, const pjd_resize_pad *pad);   /* host only, no device needed */
 /* ---- normalised float output ------------------------------------------------------------------------------------------------- *
  * pjd_batch_set_normalize: the pictures of the batch leave the decode as floating-point elements, sample * scale[c] + bias[c] -- what
  * x.float().div(255).sub(mean).div(std).to(dtype) makes of the uint8 tensor, without that tensor ever existing.  The caller passes

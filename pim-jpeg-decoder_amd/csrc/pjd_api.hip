@@ -230,14 +230,48 @@ struct pjd_batch {
                                                  // too (identity windows until pjd_batch_set_resize_window): h_win[i].flags hold PJD_RWI_*,
                                                  // and h_rs[i].tw / th are those of Q, swapped against rs_w / rs_h where transposed
 
+    std::vector<uint32_t> ct_w, ct_h;            // the CONTENT of each delivered picture: rs_w x rs_h (the canvas) less its pad.  What "the target"
+                                                 // means to pjd_batch_set_orientation and everything behind it (include/pjd.h)
+    bool pad_set = false, padded = false;        // pjd_batch_set_resize_pad: called / with a record that is not all zero.  Then the batch is
+                                                 // windowed and oriented too (identity windows, flags 0): it runs the PAD kernels, the most general form
+    PjdDevResizePad *h_pad = nullptr, *d_pad = nullptr;   // then: the canvases [n_images], followed by the prefix sum of their border lines [n_images + 1]
+    size_t pad_bytes = 0;
+    uint32_t pad_lines = 0;
+    uint8_t pad_fill[3] = {0, 0, 0};
+    bool pad_value_set = false;                  // pjd_batch_set_pad_value
+    float pad_value[3] = {0, 0, 0};
+
     // the resample launch of this batch, whatever its filter, windowed or not (both launch sites: the decode and the re-run
     // after the fallback)
     void launch_resize(hipStream_t s, bool planar) const
     {
         pjd_launch_resize(s, PjdResizeLaunch{dev.out, res_out, d_rs, d_rs_prefix, dev.n_images, rs_tiles, planar, norm, windowed ? d_win : nullptr, oriented, filter,
-                                             (const PjdDevResizeAA *)d_aa, d_aa ? (const uint32_t *)(d_aa + dev.n_images * sizeof(PjdDevResizeAA)) : nullptr, aa_lds});
+                                             (const PjdDevResizeAA *)d_aa, d_aa ? (const uint32_t *)(d_aa + dev.n_images * sizeof(PjdDevResizeAA)) : nullptr, aa_lds,
+                                             padded ? d_pad : nullptr});
     }
+    // ... and the border of its padded pictures, behind it (the same two sites): the two write disjoint bytes
+    void launch_pad(hipStream_t s, bool planar) const;
 };
+
+namespace { uint32_t f32_to_dtype_bits(int dtype, float u); }
+
+// The fill as the border kernel takes it (PjdPadFill): the three elements -- the fill byte, or its normalised value
+// (pjd_normalize_value), or the batch's pad value converted once -- laid out over twelve bytes of a row.
+void pjd_batch::launch_pad(hipStream_t s, bool planar) const
+{
+    const uint32_t es = norm.dtype ? PJD_DT_SIZE(norm.dtype) : 1u;
+    uint32_t e[3];
+    for (int c = 0; c < 3; c++)
+        e[c] = !norm.dtype ? pad_fill[c] : f32_to_dtype_bits(norm.dtype, pad_value_set ? pad_value[c] : pjd_normalize_f32(pad_fill[c], norm.scale[c], norm.bias[c]));
+    PjdPadFill f{};
+    uint8_t bytes[12];
+    for (uint32_t t = 0; t < 12u; t++) bytes[t] = (uint8_t)(e[(t / es) % 3u] >> (8u * (t % es)));
+    if (planar)
+        for (int c = 0; c < 3; c++) f.d[c] = es == 1u ? e[c] * 0x01010101u : es == 2u ? e[c] * 0x00010001u : e[c];
+    else
+        std::memcpy(f.d, bytes, 12);
+    pjd_launch_resize_border(s, PjdBorderLaunch{res_out, d_rs, d_pad, (const uint32_t *)(d_pad + dev.n_images), dev.n_images, pad_lines, planar, es, f});
+}
 
 extern "C" {
 
@@ -495,6 +529,7 @@ int pjd_batch_upload(pjd_batch *b)
     if (b->resized) HIP_TRY(ctx, hipMemcpyAsync(b->d_rs, b->h_rs, b->rs_bytes, hipMemcpyHostToDevice, s));      // the resample work list (page-locked)
     if (b->d_aa) HIP_TRY(ctx, hipMemcpyAsync(b->d_aa, b->h_aa, b->aa_bytes, hipMemcpyHostToDevice, s));   // ... and its weight table
     if (b->windowed) HIP_TRY(ctx, hipMemcpyAsync(b->d_win, b->h_win, b->win_bytes, hipMemcpyHostToDevice, s));  // ... and its source windows
+    if (b->padded) HIP_TRY(ctx, hipMemcpyAsync(b->d_pad, b->h_pad, b->pad_bytes, hipMemcpyHostToDevice, s));    // ... and its canvases
     b->uploaded = true;
     return PJD_OK;
 }
@@ -656,6 +691,7 @@ int enqueue_decode(pjd_batch *b, pjd_timings *timings, bool use_groups)
         // whatever form the back end took (the groups' streams have joined `s` above)
         b->launch_resize(s, P.planar);
         kt.mark("resize");
+        if (b->padded) { b->launch_pad(s, P.planar); kt.mark("pad"); }
     }
     HIP_TRY(ctx, hipGetLastError());
     kt.finish();
@@ -749,6 +785,7 @@ int settle(pjd_batch *b)
             if (ev1) (void)hipEventRecord(ev1, s);
             // the pictures just decoded again changed in the intermediate: resample (the whole batch: a rare path)
             if (b->resized) b->launch_resize(s, P.planar);
+            if (b->padded) b->launch_pad(s, P.planar);
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipMemcpyAsync(b->h_status, b->dev.status, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s);
@@ -1078,6 +1115,7 @@ int pjd_batch_set_resize(pjd_batch *b, const uint32_t *out_w, const uint32_t *ou
     prefix[n] = t;
     b->rs_tiles = t;
     b->rs_w.assign(out_w, out_w + n); b->rs_h.assign(out_h, out_h + n);
+    b->ct_w = b->rs_w; b->ct_h = b->rs_h;
     b->res_out = (uint8_t *)d_res;
     b->res_off = off; b->res_bytes = bytes;
     b->res_buf_bytes = pos; b->res_out_bytes = sum;
@@ -1257,6 +1295,28 @@ bool finite_f32(float f)
     return (x & 0x7f800000u) != 0x7f800000u;
 }
 
+// binary32 -> one element of a PJD_DT_* type in the low bytes of a word: ONE rounding to nearest even for the 16-bit types (the
+// conversions of pjd_normalize_value, which the device makes in hardware)
+uint32_t f32_to_dtype_bits(int dtype, float u)
+{
+    uint32_t bits;
+    std::memcpy(&bits, &u, 4);
+    if (dtype == PJD_DT_F32) return bits;
+    if (dtype == PJD_DT_F16) return f32_to_f16_bits(u);
+    bits += 0x7fffu + ((bits >> 16) & 1u);
+    return bits >> 16;
+}
+
+// THE validation of a pad record (include/pjd.h): null, or what is wrong with it.  The sums are 64-bit: no record wraps into range.
+const char *resize_pad_fault(uint32_t out_w, uint32_t out_h, const pjd_resize_pad *pad)
+{
+    if (out_w == 0 || out_w > 65535u || out_h == 0 || out_h > 65535u) return "the canvas must be 1..65535 x 1..65535";
+    if (!pad) return "null record";
+    if ((uint64_t)pad->left + pad->right >= out_w) return "left + right leaves no column of content (it must be less than out_w)";
+    if ((uint64_t)pad->top + pad->bottom >= out_h) return "top + bottom leaves no row of content (it must be less than out_h)";
+    return nullptr;
+}
+
 }  // namespace
 
 int pjd_resize_window_check(uint32_t sw, uint32_t sh, uint32_t tw, uint32_t th, const pjd_resize_window *win, int filter)
@@ -1285,27 +1345,30 @@ int pjd_batch_set_orientation(pjd_batch *b, const uint8_t *orientation)
         any = any || o != 1u;
         // the tiles of Q: its target is the delivered one with the axes swapped where the orientation transposes
         const bool t = (pjd_orient_flags(o) & PJD_RWI_TRANSPOSE) != 0;
-        const uint32_t tw = t ? b->rs_h[i] : b->rs_w[i], th = t ? b->rs_w[i] : b->rs_h[i];
+        const uint32_t tw = t ? b->ct_h[i] : b->ct_w[i], th = t ? b->ct_w[i] : b->ct_h[i];
         tiles += (uint64_t)((tw + PJD_RS_COLS - 1) / PJD_RS_COLS) * ((th + PJD_RS_ROWS - 1) / PJD_RS_ROWS);
     }
     if (tiles >= (1ull << 31)) { ctx->err = "set_orientation: the targets of this batch are too large for one launch"; return PJD_E_ARG; }
     if (any) {
         // Identity windows that carry the orientation (pjd_batch_set_resize_window fills in what it is given): the batch runs the
         // windowed launch's ORI form.  All 1: nothing is taken and the batch keeps the launch it had.
-        hipSetDevice(ctx->device);
-        const size_t bytes = n * sizeof(PjdDevResizeWin);
-        void *h_win = nullptr, *d_win = nullptr;
-        int rc = pool_pin_alloc(ctx, &h_win, bytes, b->pin_blocks);
-        if (rc == PJD_OK) rc = pool_dev_alloc(ctx, &d_win, bytes, b->dev_blocks);
-        if (rc != PJD_OK) return rc;                       // what was taken stays with the batch until it is destroyed
-        b->device_bytes += bytes;
-        b->h_win = (PjdDevResizeWin *)h_win; b->d_win = (PjdDevResizeWin *)d_win; b->win_bytes = bytes;
+        // A padded batch (pjd_batch_set_resize_pad) has the windows already, and its targets are the contents.
+        if (!b->padded) {
+            hipSetDevice(ctx->device);
+            const size_t bytes = n * sizeof(PjdDevResizeWin);
+            void *h_win = nullptr, *d_win = nullptr;
+            int rc = pool_pin_alloc(ctx, &h_win, bytes, b->pin_blocks);
+            if (rc == PJD_OK) rc = pool_dev_alloc(ctx, &d_win, bytes, b->dev_blocks);
+            if (rc != PJD_OK) return rc;                   // what was taken stays with the batch until it is destroyed
+            b->device_bytes += bytes;
+            b->h_win = (PjdDevResizeWin *)h_win; b->d_win = (PjdDevResizeWin *)d_win; b->win_bytes = bytes;
+        }
         uint32_t *prefix = (uint32_t *)(b->h_rs + n);
         uint32_t t = 0;
         for (size_t i = 0; i < n; i++) {
             PjdDevResize &r = b->h_rs[i];
             const uint32_t f = pjd_orient_flags(orientation[i]);
-            if (f & PJD_RWI_TRANSPOSE) { r.tw = b->rs_h[i]; r.th = b->rs_w[i]; }
+            if (f & PJD_RWI_TRANSPOSE) { r.tw = b->ct_h[i]; r.th = b->ct_w[i]; }
             r.col_tiles = (r.tw + PJD_RS_COLS - 1) / PJD_RS_COLS;
             prefix[i] = t;
             t += r.col_tiles * ((r.th + PJD_RS_ROWS - 1) / PJD_RS_ROWS);
@@ -1368,20 +1431,102 @@ int pjd_batch_set_resize_window(pjd_batch *b, const pjd_resize_window *win)
     return PJD_OK;
 }
 
+int pjd_resize_pad_check(uint32_t out_w, uint32_t out_h, const pjd_resize_pad *pad)
+{
+    return resize_pad_fault(out_w, out_h, pad) ? PJD_E_ARG : PJD_OK;
+}
+
+int pjd_batch_set_resize_pad(pjd_batch *b, const pjd_resize_pad *pad, const uint8_t fill[3])
+{
+    if (!b) return PJD_E_ARG;
+    pjd_ctx *ctx = b->ctx;
+    if (!b->resized) { ctx->err = "set_resize_pad: no resize is set (pjd_batch_set_resize first)"; return PJD_E_STATE; }
+    if (b->pad_set) { ctx->err = "set_resize_pad: already set for this batch"; return PJD_E_STATE; }
+    if (b->ori_set) { ctx->err = "set_resize_pad after set_orientation"; return PJD_E_STATE; }
+    if (b->win_set) { ctx->err = "set_resize_pad after set_resize_window"; return PJD_E_STATE; }
+    if (b->filter_set) { ctx->err = "set_resize_pad after set_resize_filter"; return PJD_E_STATE; }
+    if (b->norm.dtype != 0) { ctx->err = "set_resize_pad after set_normalize"; return PJD_E_STATE; }
+    if (b->bound) { ctx->err = "set_resize_pad after bind_output"; return PJD_E_STATE; }
+    if (b->uploaded) { ctx->err = "set_resize_pad after upload"; return PJD_E_STATE; }
+    if (!pad) { ctx->err = "set_resize_pad: null record array"; return PJD_E_ARG; }
+    if (!fill) { ctx->err = "set_resize_pad: null fill"; return PJD_E_ARG; }
+    const size_t n = b->plan.images.size();
+    bool any = false;
+    uint64_t lines = 0;
+    for (size_t i = 0; i < n; i++) {
+        if (const char *fault = resize_pad_fault(b->rs_w[i], b->rs_h[i], &pad[i])) {
+            ctx->err = fmt_image("set_resize_pad: picture %d: ", (int)i) + fault;
+            return PJD_E_ARG;
+        }
+        const bool here = pad[i].left || pad[i].top || pad[i].right || pad[i].bottom;
+        any = any || here;
+        if (here) lines += (uint64_t)(b->plan.planar ? 3u : 1u) * b->rs_h[i];
+    }
+    if (lines >= (1ull << 31)) { ctx->err = "set_resize_pad: the canvases of this batch are too large for one launch"; return PJD_E_ARG; }
+    if (any) {
+        // The canvases, and identity windows without an orientation (pjd_batch_set_orientation and _set_resize_window fill in what they
+        // are given): the batch runs the PAD form of the oriented launch, whose targets are the contents.  The contents are no larger
+        // than the canvases, so the tiles stay below the limit pjd_batch_set_resize checked.  All zero: nothing is taken and the batch
+        // keeps the launch it had.
+        hipSetDevice(ctx->device);
+        const size_t win_bytes = n * sizeof(PjdDevResizeWin), pad_bytes = n * sizeof(PjdDevResizePad) + (n + 1) * sizeof(uint32_t);
+        void *h_win = nullptr, *d_win = nullptr, *h_pad = nullptr, *d_pad = nullptr;
+        int rc = pool_pin_alloc(ctx, &h_win, win_bytes, b->pin_blocks);
+        if (rc == PJD_OK) rc = pool_dev_alloc(ctx, &d_win, win_bytes, b->dev_blocks);
+        if (rc == PJD_OK) rc = pool_pin_alloc(ctx, &h_pad, pad_bytes, b->pin_blocks);
+        if (rc == PJD_OK) rc = pool_dev_alloc(ctx, &d_pad, pad_bytes, b->dev_blocks);
+        if (rc != PJD_OK) return rc;                       // what was taken stays with the batch until it is destroyed
+        b->device_bytes += win_bytes + pad_bytes;
+        b->h_win = (PjdDevResizeWin *)h_win; b->d_win = (PjdDevResizeWin *)d_win; b->win_bytes = win_bytes;
+        b->h_pad = (PjdDevResizePad *)h_pad; b->d_pad = (PjdDevResizePad *)d_pad; b->pad_bytes = pad_bytes;
+        uint32_t *prefix = (uint32_t *)(b->h_rs + n), *lprefix = (uint32_t *)(b->h_pad + n);
+        uint32_t t = 0, l = 0;
+        for (size_t i = 0; i < n; i++) {
+            PjdDevResize &r = b->h_rs[i];
+            const pjd_resize_pad &p = pad[i];
+            b->ct_w[i] = b->rs_w[i] - p.left - p.right; b->ct_h[i] = b->rs_h[i] - p.top - p.bottom;
+            r.tw = b->ct_w[i]; r.th = b->ct_h[i];
+            r.col_tiles = (r.tw + PJD_RS_COLS - 1) / PJD_RS_COLS;
+            prefix[i] = t;
+            t += r.col_tiles * ((r.th + PJD_RS_ROWS - 1) / PJD_RS_ROWS);
+            b->h_win[i] = pjd_resize_win_identity(r);
+            b->h_pad[i] = PjdDevResizePad{b->rs_w[i], b->rs_h[i], p.left, p.top, b->ct_w[i], b->ct_h[i], {0u, 0u}};
+            lprefix[i] = l;
+            if (p.left || p.top || p.right || p.bottom) l += (b->plan.planar ? 3u : 1u) * b->rs_h[i];
+        }
+        prefix[n] = t; lprefix[n] = l;
+        b->rs_tiles = t; b->pad_lines = l;
+        for (int c = 0; c < 3; c++) b->pad_fill[c] = fill[c];
+        b->windowed = b->oriented = b->padded = true;
+    }
+    b->pad_set = true;
+    return PJD_OK;
+}
+
+int pjd_batch_set_pad_value(pjd_batch *b, const float value[3])
+{
+    if (!b) return PJD_E_ARG;
+    pjd_ctx *ctx = b->ctx;
+    if (!b->pad_set) { ctx->err = "set_pad_value: the batch has no pad (pjd_batch_set_resize_pad first)"; return PJD_E_STATE; }
+    if (b->norm.dtype == 0) { ctx->err = "set_pad_value: the batch is not normalised (pjd_batch_set_normalize first)"; return PJD_E_STATE; }
+    if (b->pad_value_set) { ctx->err = "set_pad_value: already set for this batch"; return PJD_E_STATE; }
+    if (b->bound) { ctx->err = "set_pad_value after bind_output"; return PJD_E_STATE; }
+    if (b->uploaded) { ctx->err = "set_pad_value after upload"; return PJD_E_STATE; }
+    if (!value) { ctx->err = "set_pad_value: null value array"; return PJD_E_ARG; }
+    for (int c = 0; c < 3; c++)
+        if (!finite_f32(value[c])) { ctx->err = "set_pad_value: the values must be finite"; return PJD_E_ARG; }
+    for (int c = 0; c < 3; c++) b->pad_value[c] = value[c];
+    b->pad_value_set = true;
+    return PJD_OK;
+}
+
 int pjd_normalize_value(int dtype, uint32_t v, float scale, float bias, void *out)
 {
     if (dtype != PJD_DT_F16 && dtype != PJD_DT_BF16 && dtype != PJD_DT_F32) return PJD_E_ARG;
     if (v > 255u || !finite_f32(scale) || !finite_f32(bias) || !out) return PJD_E_ARG;
-    const float u = pjd_normalize_f32(v, scale, bias);
-    if (dtype == PJD_DT_F32) { std::memcpy(out, &u, 4); return PJD_OK; }
-    uint16_t h;
-    if (dtype == PJD_DT_F16) h = f32_to_f16_bits(u);
-    else {
-        uint32_t bits;
-        std::memcpy(&bits, &u, 4);
-        bits += 0x7fffu + ((bits >> 16) & 1u);
-        h = (uint16_t)(bits >> 16);
-    }
+    const uint32_t e = f32_to_dtype_bits(dtype, pjd_normalize_f32(v, scale, bias));
+    if (dtype == PJD_DT_F32) { std::memcpy(out, &e, 4); return PJD_OK; }
+    const uint16_t h = (uint16_t)e;
     std::memcpy(out, &h, 2);
     return PJD_OK;
 }

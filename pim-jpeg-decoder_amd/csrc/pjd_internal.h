@@ -519,6 +519,30 @@ static inline __host__ __device__ void pjd_resize_win_ends(const PjdDevResizeWin
     hi = w.ox + (flip ? tw - 1u - c0 : c1);
 }
 
+// ---- pad on decode (pjd_batch_set_resize_pad; normative: include/pjd.h) --------------------------------------------------------------
+// What the kernels built with PAD (pjd_k_resize.hip) and the border kernel read beside the work list: per picture the delivered CANVAS
+// and where the content rectangle lies in it, all in the delivered picture's coordinates (no orientation permutes them).  PjdDevResize
+// keeps the CONTENT as its target (tw x th, Q's where transposed): tiles, taps and mirror extents are the content's, while the row
+// length, the plane and the origin of every store are the canvas's.  A picture with an all-zero pad has cw == W, ch == H, left == top == 0.
+struct PjdDevResizePad {
+    uint32_t W, H;                     // the canvas: out_w x out_h of pjd_batch_set_resize
+    uint32_t left, top;                // the content's first column and row
+    uint32_t cw, ch;                   // the content: W - left - right by H - top - bottom, each >= 1
+    uint32_t pad_[2];
+};
+// the constants of the border kernel: the fill as twelve bytes of a canvas row.  Planar: d[c] is channel c's element repeated over a
+// dword.  Interleaved: d[0..2] are the first twelve bytes of a row of fill (R G B R ... in elements of 1, 2 or 4 bytes; 12 is a
+// multiple of every pixel size).  Made once on the host (pjd_batch_set_resize_pad / _set_normalize / _set_pad_value).
+struct PjdPadFill { uint32_t d[3]; };
+// the dword of fill at byte j of a canvas line (any j: an aligned ADDRESS need not be an aligned offset): four bytes of the pattern of
+// period 12 from j % 12 on.  p0..p2: d[0..2] interleaved, channel c's d[c] three times planar.
+static inline __host__ __device__ uint32_t pjd_pad_fill_dword(uint32_t p0, uint32_t p1, uint32_t p2, uint32_t j)
+{
+    const uint32_t m = j % 12u, q = m >> 2, sh = 8u * (m & 3u);
+    const uint32_t lo = q == 0u ? p0 : q == 1u ? p1 : p2, hi = q == 0u ? p1 : q == 1u ? p2 : p0;
+    return (uint32_t)((((uint64_t)hi << 32) | lo) >> sh);
+}
+
 // ---- normalised float output (pjd_batch_set_normalize; the arithmetic is normative: include/pjd.h) ---------------------------
 // The fma stage of one sample: the exact value of v * scale + bias rounded ONCE to binary32, to nearest even.  THE implementation:
 // pjd_normalize_value exports it to the host (where it is libm's fmaf unless the target has the instruction), the epilogue of

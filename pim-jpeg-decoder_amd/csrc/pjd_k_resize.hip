@@ -46,6 +46,10 @@
 // tap mirror of the windows, the top-bottom one a mirrored store row, the transpose a second form of the epilogue (store_cols of
 // pjd_k_resize_store.h) that stores a lane's eight rows of one column as eight adjacent samples.  The same bodies with a compile-time
 // ORI, in kernels of their own (pjd_k_resize_ori, pjd_k_resize_ori_tab).
+//
+// Pad on decode (pjd_batch_set_resize_pad): the picture is a rectangle of a larger canvas.  The same bodies with a compile-time PAD, in
+// kernels of their own again (pjd_k_resize_pad, pjd_k_resize_pad_tab): tiles, taps and mirrors are the content's, the stores' row
+// length, plane and origin the canvas's.  The border is a second, small kernel's (pjd_k_resize_border): the two write disjoint bytes.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -63,7 +67,8 @@ pjd_k_resize(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, const P
              const uint32_t *__restrict__ tile_prefix, uint32_t n_images, uint32_t n_tiles)
 {
     constexpr int DT = 0;
-    constexpr bool WIN = false, ORI = false;
+    constexpr bool WIN = false, ORI = false, PAD = false;
+    const PjdDevResizePad *const pad = nullptr;
     const PjdDevResizeWin *const win = nullptr;
     const NormArgs nz{};
 #include "pjd_k_resize_body.h"
@@ -74,7 +79,8 @@ __global__ void __launch_bounds__(64 * PJD_RS_WAVES)
 pjd_k_resize_norm(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, const PjdDevResize *__restrict__ recs,
                   const uint32_t *__restrict__ tile_prefix, uint32_t n_images, uint32_t n_tiles, const NormArgs nz)
 {
-    constexpr bool WIN = false, ORI = false;
+    constexpr bool WIN = false, ORI = false, PAD = false;
+    const PjdDevResizePad *const pad = nullptr;
     const PjdDevResizeWin *const win = nullptr;
 #include "pjd_k_resize_body.h"
 }
@@ -85,7 +91,8 @@ pjd_k_resize_win(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, con
                  const PjdDevResizeWin *__restrict__ win, const uint32_t *__restrict__ tile_prefix, uint32_t n_images, uint32_t n_tiles,
                  const NormArgs nz)
 {
-    constexpr bool WIN = true, ORI = false;
+    constexpr bool WIN = true, ORI = false, PAD = false;
+    const PjdDevResizePad *const pad = nullptr;
 #include "pjd_k_resize_body.h"
 }
 
@@ -96,7 +103,8 @@ pjd_k_resize_aa(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, cons
                 const uint32_t *__restrict__ tab, uint32_t lds_bytes, const NormArgs nz)
 {
     extern __shared__ uint32_t seg[];                      // one source row's segment (three plane segments where PLANAR)
-    constexpr bool WIN = false, ORI = false;
+    constexpr bool WIN = false, ORI = false, PAD = false;
+    const PjdDevResizePad *const pad = nullptr;
     constexpr int FILT = PJD_RESIZE_ANTIALIAS;
     const PjdDevResizeWin *const win = nullptr;
 #include "pjd_k_resize_aa_body.h"
@@ -109,7 +117,8 @@ pjd_k_resize_win_aa(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, 
                     const PjdDevResizeAA *__restrict__ aa, const uint32_t *__restrict__ tab, uint32_t lds_bytes, const NormArgs nz)
 {
     extern __shared__ uint32_t seg[];
-    constexpr bool WIN = true, ORI = false;
+    constexpr bool WIN = true, ORI = false, PAD = false;
+    const PjdDevResizePad *const pad = nullptr;
     constexpr int FILT = PJD_RESIZE_ANTIALIAS;
 #include "pjd_k_resize_aa_body.h"
 }
@@ -122,7 +131,8 @@ pjd_k_resize_cubic(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, c
                    const uint32_t *__restrict__ tab, uint32_t lds_bytes, const NormArgs nz)
 {
     extern __shared__ uint32_t seg[];
-    constexpr bool WIN = false, ORI = false;
+    constexpr bool WIN = false, ORI = false, PAD = false;
+    const PjdDevResizePad *const pad = nullptr;
     constexpr int FILT = PJD_RESIZE_BICUBIC;
     const PjdDevResizeWin *const win = nullptr;
 #include "pjd_k_resize_aa_body.h"
@@ -135,7 +145,8 @@ pjd_k_resize_win_cubic(const uint8_t *__restrict__ src, uint8_t *__restrict__ ds
                        const PjdDevResizeAA *__restrict__ aa, const uint32_t *__restrict__ tab, uint32_t lds_bytes, const NormArgs nz)
 {
     extern __shared__ uint32_t seg[];
-    constexpr bool WIN = true, ORI = false;
+    constexpr bool WIN = true, ORI = false, PAD = false;
+    const PjdDevResizePad *const pad = nullptr;
     constexpr int FILT = PJD_RESIZE_BICUBIC;
 #include "pjd_k_resize_aa_body.h"
 }
@@ -149,7 +160,8 @@ pjd_k_resize_ori(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, con
                  const PjdDevResizeWin *__restrict__ win, const uint32_t *__restrict__ tile_prefix, uint32_t n_images, uint32_t n_tiles,
                  const NormArgs nz)
 {
-    constexpr bool WIN = true, ORI = true;
+    constexpr bool WIN = true, ORI = true, PAD = false;
+    const PjdDevResizePad *const pad = nullptr;
 #include "pjd_k_resize_body.h"
 }
 
@@ -160,8 +172,49 @@ pjd_k_resize_ori_tab(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst,
                      const PjdDevResizeAA *__restrict__ aa, const uint32_t *__restrict__ tab, uint32_t lds_bytes, const NormArgs nz)
 {
     extern __shared__ uint32_t seg[];
-    constexpr bool WIN = true, ORI = true;
+    constexpr bool WIN = true, ORI = true, PAD = false;
+    const PjdDevResizePad *const pad = nullptr;
 #include "pjd_k_resize_aa_body.h"
+}
+
+// pad on decode (pjd_batch_set_resize_pad): the oriented kernels -- the most general form -- again, storing into a rectangle of a canvas:
+// row length, plane and origin of the stores from the picture's PjdDevResizePad.  Kernels of their own for the reason the oriented
+// ones are: a batch without a pad launches exactly what it launched before (profiles/resize_pad.md).
+template <bool PLANAR, int DT>
+__global__ void __launch_bounds__(64 * PJD_RS_WAVES)
+pjd_k_resize_pad(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, const PjdDevResize *__restrict__ recs,
+                 const PjdDevResizeWin *__restrict__ win, const PjdDevResizePad *__restrict__ pad, const uint32_t *__restrict__ tile_prefix,
+                 uint32_t n_images, uint32_t n_tiles, const NormArgs nz)
+{
+    constexpr bool WIN = true, ORI = true, PAD = true;
+#include "pjd_k_resize_body.h"
+}
+
+template <bool PLANAR, int DT, int FILT>
+__global__ void __launch_bounds__(64)
+pjd_k_resize_pad_tab(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, const PjdDevResize *__restrict__ recs,
+                     const PjdDevResizeWin *__restrict__ win, const PjdDevResizePad *__restrict__ pad, const uint32_t *__restrict__ tile_prefix,
+                     uint32_t n_images, uint32_t n_tiles, const PjdDevResizeAA *__restrict__ aa, const uint32_t *__restrict__ tab, uint32_t lds_bytes,
+                     const NormArgs nz)
+{
+    extern __shared__ uint32_t seg[];
+    constexpr bool WIN = true, ORI = true, PAD = true;
+#include "pjd_k_resize_aa_body.h"
+}
+
+// The border of the padded pictures: everything of a canvas outside its content rectangle, which the resample leaves alone, set to the
+// fill.  One wave per canvas LINE (a row of the interleaved picture; a row of one plane), found by the prefix sum over the pictures'
+// lines (pictures without a pad have none).  A line of the top or bottom band is one run of fill, any other line two: left and right
+// of the content.  Plain coalesced stores of a pattern made once on the host (PjdPadFill): dwords from the first 4-byte aligned address
+// of a run on, bytes before it and behind the last whole dword (at most three each: pjd_batch_bind_output promises element alignment,
+// no more).  No byte of the content rectangle is written, and no byte outside the canvas.
+__global__ void __launch_bounds__(64 * PJD_RS_WAVES)
+pjd_k_resize_border(uint8_t *__restrict__ dst, const PjdDevResize *__restrict__ recs, const PjdDevResizePad *__restrict__ pad,
+                    const uint32_t *__restrict__ line_prefix, uint32_t n_images, uint32_t n_lines, uint32_t planar, uint32_t es, const PjdPadFill fill)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t line = __builtin_amdgcn_readfirstlane(blockIdx.x * PJD_RS_WAVES + (threadIdx.x >> 6));
+#include "pjd_k_resize_border_body.h"
 }
 
 // f(planar, dtype) with both as compile-time constants: THE dtype x layout dispatch of the resample launch
@@ -192,7 +245,13 @@ void pjd_launch_resize(hipStream_t s, const PjdResizeLaunch &a)
     for_layout_and_dtype(a.planar, a.norm.dtype, [&](auto P, auto D) {
         constexpr bool PL = decltype(P)::value;
         constexpr int DT = decltype(D)::value;
-        if (a.oriented && a.filter == PJD_RESIZE_BICUBIC)
+        if (a.pad && a.filter == PJD_RESIZE_BICUBIC)
+            hipLaunchKernelGGL((pjd_k_resize_pad_tab<PL, DT, PJD_RESIZE_BICUBIC>), grid, block, a.lds_bytes, s, a.src, a.dst, a.recs, a.win, a.pad, a.tile_prefix, a.n_images, a.n_tiles, a.aa, a.tab, a.lds_bytes, nz);
+        else if (a.pad && tabled)
+            hipLaunchKernelGGL((pjd_k_resize_pad_tab<PL, DT, PJD_RESIZE_ANTIALIAS>), grid, block, a.lds_bytes, s, a.src, a.dst, a.recs, a.win, a.pad, a.tile_prefix, a.n_images, a.n_tiles, a.aa, a.tab, a.lds_bytes, nz);
+        else if (a.pad)
+            hipLaunchKernelGGL((pjd_k_resize_pad<PL, DT>), grid, block, 0, s, a.src, a.dst, a.recs, a.win, a.pad, a.tile_prefix, a.n_images, a.n_tiles, nz);
+        else if (a.oriented && a.filter == PJD_RESIZE_BICUBIC)
             hipLaunchKernelGGL((pjd_k_resize_ori_tab<PL, DT, PJD_RESIZE_BICUBIC>), grid, block, a.lds_bytes, s, a.src, a.dst, a.recs, a.win, a.tile_prefix, a.n_images, a.n_tiles, a.aa, a.tab, a.lds_bytes, nz);
         else if (a.oriented && tabled)
             hipLaunchKernelGGL((pjd_k_resize_ori_tab<PL, DT, PJD_RESIZE_ANTIALIAS>), grid, block, a.lds_bytes, s, a.src, a.dst, a.recs, a.win, a.tile_prefix, a.n_images, a.n_tiles, a.aa, a.tab, a.lds_bytes, nz);
@@ -213,4 +272,11 @@ void pjd_launch_resize(hipStream_t s, const PjdResizeLaunch &a)
         else
             hipLaunchKernelGGL((pjd_k_resize_norm<PL, DT>), grid, block, 0, s, a.src, a.dst, a.recs, a.tile_prefix, a.n_images, a.n_tiles, nz);
     });
+}
+
+void pjd_launch_resize_border(hipStream_t s, const PjdBorderLaunch &a)
+{
+    if (a.n_lines == 0) return;
+    hipLaunchKernelGGL(pjd_k_resize_border, dim3((a.n_lines + PJD_RS_WAVES - 1) / PJD_RS_WAVES), dim3(64 * PJD_RS_WAVES), 0, s, a.dst, a.recs, a.pad, a.line_prefix,
+                       a.n_images, a.n_lines, a.planar ? 1u : 0u, a.elem_bytes, a.fill);
 }

@@ -15,7 +15,8 @@
 // No lane leaves before the last barrier; lanes right of the picture compute its last column and store nothing.
 // A textual include, so that tools/resize_host.cpp runs this very text on the host; PJD_WIN_STAGE_FIRST / _STEP say which dwords of a
 // segment this thread stages (its own of the wave's 64 here; all of them where a thread runs alone).
-// In scope: PLANAR, DT, WIN, ORI (implies WIN), FILT (compile-time constants), seg (LDS), src, dst, recs, win (read only where WIN), tile_prefix, n_images,
+// In scope: PLANAR, DT, WIN, ORI (implies WIN), PAD (implies ORI), FILT (compile-time constants), seg (LDS), src, dst, recs, win (read only where WIN),
+// pad (read only where PAD), tile_prefix, n_images,
 // n_tiles, aa, tab, lds_bytes, nz; store_row and store_cols.
 #ifndef PJD_WIN_STAGE_FIRST
 #define PJD_WIN_STAGE_FIRST lane
@@ -71,10 +72,12 @@
     }
     const uint32_t n_px = col0 >= r.tw ? 0u : (r.tw - col0 < PJD_RS_PX ? r.tw - col0 : PJD_RS_PX);
     const uint8_t *sp = src + r.src_off + (uint64_t)w.y * r.src_stride + (PLANAR ? w.x + xs : 3u * (w.x + xs));   // the segment in row 0 of the window
-    uint8_t *dp = dst + r.dst_off;
+    // With PAD (pjd_batch_set_resize_pad): the canvas's row length, plane and origin for the stores, as in pjd_k_resize_body.h
+    const PjdDevResizePad cv = PAD ? pad[lo] : PjdDevResizePad{};
+    uint8_t *dp = dst + r.dst_off + (PAD ? ((uint64_t)cv.top * cv.W + cv.left) * (PLANAR ? 1u : 3u) * (DT == 0 ? 1u : PJD_DT_SIZE(DT)) : 0u);
     const uint64_t src_plane = PLANAR ? (uint64_t)r.src_stride * r.sh : 1u;        // the whole picture's plane
-    const uint64_t dst_plane = PLANAR ? (uint64_t)r.tw * r.th : 1u;
-    const uint32_t dst_stride = PLANAR ? r.tw : 3u * r.tw;
+    const uint64_t dst_plane = PLANAR ? (PAD ? (uint64_t)cv.W * cv.H : (uint64_t)r.tw * r.th) : 1u;
+    const uint32_t dst_stride = PAD ? (PLANAR ? cv.W : 3u * cv.W) : (PLANAR ? r.tw : 3u * r.tw);
     const uint8_t *sb = reinterpret_cast<const uint8_t *>(seg);
 
     uint32_t acc[PJD_RS_ROWS][3][PJD_RS_PX];
@@ -153,7 +156,7 @@
                 for (int c = 0; c < 3; c++)
 #pragma unroll
                     for (int q = 0; q < PJD_RS_PX; q++) acc[k][c][q] = tap_out<FILT>(acc[k][c][q]);
-            store_cols<PLANAR, DT>(acc, dp, row0, r.th - row0 < PJD_RS_ROWS ? r.th - row0 : PJD_RS_ROWS, col0, n_px, (w.flags & PJD_RWI_YMIRROR) != 0, r.th, dst_plane, nz);
+            store_cols<PLANAR, DT>(acc, dp, row0, r.th - row0 < PJD_RS_ROWS ? r.th - row0 : PJD_RS_ROWS, col0, n_px, (w.flags & PJD_RWI_YMIRROR) != 0, r.th, PAD ? cv.W : r.th, dst_plane, nz);
             return;
         }
     }

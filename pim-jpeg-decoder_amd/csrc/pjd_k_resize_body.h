@@ -12,7 +12,7 @@
 // text on the host.
 // With ORI (which implies WIN) the store side reads the orientation of pjd_batch_set_orientation from the window's flags (PJD_RWI_* of
 // pjd_internal.h); the read side does not know of it: the tap mirror is the bit PJD_RW_HFLIP has.
-// In scope: PLANAR, DT, WIN, ORI (compile-time constants), src, dst, recs, win (read only where WIN), tile_prefix, n_images, n_tiles, nz
+// In scope: PLANAR, DT, WIN, ORI, PAD (compile-time constants; PAD implies ORI), src, dst, recs, win (read only where WIN), pad (read only where PAD), tile_prefix, n_images, n_tiles, nz
 // (NormArgs; read only where DT != 0; r.dst_off stays a byte offset); lerp8, store_row and store_cols.
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t tile = __builtin_amdgcn_readfirstlane(blockIdx.x * PJD_RS_WAVES + (threadIdx.x >> 6));
@@ -53,10 +53,13 @@
     }
     const uint32_t n_px = r.tw - col0 < PJD_RS_PX ? r.tw - col0 : PJD_RS_PX;
     const uint8_t *sp = src + r.src_off + (uint64_t)w.y * r.src_stride;           // row 0 of the window
-    uint8_t *dp = dst + r.dst_off;
+    // With PAD (pjd_batch_set_resize_pad) the picture is a rectangle of a canvas: the row length, the plane and the origin of the stores
+    // are the canvas's (PjdDevResizePad), everything else -- tiles, taps, mirror extents -- stays the content's
+    const PjdDevResizePad cv = PAD ? pad[lo] : PjdDevResizePad{};
+    uint8_t *dp = dst + r.dst_off + (PAD ? ((uint64_t)cv.top * cv.W + cv.left) * (PLANAR ? 1u : 3u) * (DT == 0 ? 1u : PJD_DT_SIZE(DT)) : 0u);
     const uint64_t src_plane = PLANAR ? (uint64_t)r.src_stride * r.sh : 1u;        // from one channel to the next: the whole picture's plane
-    const uint64_t dst_plane = PLANAR ? (uint64_t)r.tw * r.th : 1u;
-    const uint32_t dst_stride = PLANAR ? r.tw : 3u * r.tw;
+    const uint64_t dst_plane = PLANAR ? (PAD ? (uint64_t)cv.W * cv.H : (uint64_t)r.tw * r.th) : 1u;
+    const uint32_t dst_stride = PAD ? (PLANAR ? cv.W : 3u * cv.W) : (PLANAR ? r.tw : 3u * r.tw);
 
     uint32_t kept[PJD_RS_ROWS][3][PJD_RS_PX] = {};         // ORI, a transposed picture: the rows of the tile (rows below the picture: 0, never stored); unused otherwise
 #pragma unroll
@@ -98,5 +101,5 @@
     }
     if constexpr (ORI) {
         if (w.flags & PJD_RWI_TRANSPOSE)
-            store_cols<PLANAR, DT>(kept, dp, row0, r.th - row0 < PJD_RS_ROWS ? r.th - row0 : PJD_RS_ROWS, col0, n_px, (w.flags & PJD_RWI_YMIRROR) != 0, r.th, dst_plane, nz);
+            store_cols<PLANAR, DT>(kept, dp, row0, r.th - row0 < PJD_RS_ROWS ? r.th - row0 : PJD_RS_ROWS, col0, n_px, (w.flags & PJD_RWI_YMIRROR) != 0, r.th, PAD ? cv.W : r.th, dst_plane, nz);
     }

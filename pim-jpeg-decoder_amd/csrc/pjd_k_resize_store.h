@@ -59,7 +59,8 @@ __device__ __forceinline__ void store_row(const uint32_t (&px)[3][PJD_RS_PX], ui
 
 // The transposed form of the epilogue (pjd_batch_set_orientation, orientations 5..8; the kernels built with ORI): the tile's PJD_RS_ROWS
 // rows of Q, px[k][c][q] for row row0 + k (k < n_rows) and column col0 + q (q < n_px; 0: nothing), leave as D's rows col0 + q, which
-// are r_th samples long.  A lane's rows of one column are adjacent samples of one row of D -- columns row0 .. row0 + 7, or with
+// are r_th samples long.  They lie row_len samples apart: r_th again, or with a pad (pjd_batch_set_resize_pad) the canvas's width, while
+// the mirror keeps counting from r_th, the content's.  A lane's rows of one column are adjacent samples of one row of D -- columns row0 .. row0 + 7, or with
 // `mirror` r_th - 1 - row0 downwards, which in ascending order is the same eight samples reversed -- so they leave in ONE store per
 // column and channel: 8 bytes planar uint8, 16 (fp16 / bf16) or 2 x 16 (fp32) planar floats, 24 bytes (3 x 8) interleaved RGB8, 3 or
 // 6 x 16 interleaved floats; where the tile has all its rows and the address has that store's alignment.  Element stores otherwise (a
@@ -71,7 +72,7 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 template <bool PLANAR, int DT>
 __device__ __forceinline__ void store_cols(const uint32_t (&px)[PJD_RS_ROWS][3][PJD_RS_PX], uint8_t *dp, uint32_t row0, uint32_t n_rows, uint32_t col0,
-                                           uint32_t n_px, bool mirror, uint32_t r_th, uint64_t dst_plane, const NormArgs &nz)
+                                           uint32_t n_px, bool mirror, uint32_t r_th, uint32_t row_len, uint64_t dst_plane, const NormArgs &nz)
 {
     constexpr int R = PJD_RS_ROWS;
     static_assert(R == 8, "the packing below is written for eight rows");
@@ -81,7 +82,7 @@ __device__ __forceinline__ void store_cols(const uint32_t (&px)[PJD_RS_ROWS][3][
 #pragma unroll
     for (int q = 0; q < PJD_RS_PX; q++) {
         if ((uint32_t)q >= n_px) break;
-        const int64_t first = (int64_t)((uint64_t)(col0 + q) * r_th) + jv;          // in samples of one channel, from the picture's (plane's) start
+        const int64_t first = (int64_t)((uint64_t)(col0 + q) * row_len) + jv;          // in samples of one channel, from the picture's (plane's) start
         uint32_t v[3][R];                                  // D's order
 #pragma unroll
         for (int c = 0; c < 3; c++)

@@ -93,8 +93,22 @@ struct PjdResizeLaunch {
     const PjdDevResizeAA *aa;
     const uint32_t *tab;
     uint32_t lds_bytes;
+    const PjdDevResizePad *pad;          // pjd_batch_set_resize_pad: null, or win is set too and pad[i] is picture i's canvas (the PAD kernels)
 };
 void pjd_launch_resize(hipStream_t s, const PjdResizeLaunch &a);
+// ... and the border of its padded pictures (pjd_k_resize_border): line_prefix[i] = canvas lines (rows interleaved, plane rows planar) of
+// the padded pictures before i, line_prefix[n_images] = n_lines; elem_bytes 1 (uint8), 2 or 4; fill: the pattern of PjdPadFill
+struct PjdBorderLaunch {
+    uint8_t *dst;
+    const PjdDevResize *recs;
+    const PjdDevResizePad *pad;
+    const uint32_t *line_prefix;
+    uint32_t n_images, n_lines;
+    bool planar;
+    uint32_t elem_bytes;
+    PjdPadFill fill;
+};
+void pjd_launch_resize_border(hipStream_t s, const PjdBorderLaunch &a);
 // ---- stage-level parity (pjd_k_coefdump.hip): coefficients in the reference's MCU_buffer layout; `out` is zeroed by the caller
 void pjd_launch_coefdump_lanes(hipStream_t s, const PjdDevBatch &b, uint32_t image, uint32_t n_iwg, int16_t *out);
 void pjd_launch_coefdump_dense(hipStream_t s, const PjdDevBatch &b, uint32_t image, const int16_t *scratch, uint32_t first_du, uint32_t n_du, int16_t *out);

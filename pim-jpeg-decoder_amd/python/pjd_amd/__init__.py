@@ -76,6 +76,12 @@ class ResizeWindow(C.Structure):
                 ("ox", C.c_uint32), ("oy", C.c_uint32), ("flags", C.c_uint32), ("reserved_", C.c_uint32)]
 
 
+class ResizePad(C.Structure):
+    """pjd_resize_pad (pjd.h): how many columns and rows of the delivered canvas lie left of, above, right of and below the content
+    rectangle.  All zero: the picture fills its canvas."""
+    _fields_ = [("left", C.c_uint32), ("top", C.c_uint32), ("right", C.c_uint32), ("bottom", C.c_uint32)]
+
+
 class BatchInfo(C.Structure):
     _fields_ = [("n_images", C.c_int32), ("pixels", C.c_uint64), ("ecs_bytes", C.c_uint64),
                 ("out_bytes", C.c_uint64), ("coef_bytes", C.c_uint64), ("n_data_units", C.c_uint64),
@@ -196,6 +202,12 @@ def dev_lib():
         L.pjd_batch_set_resize_window.argtypes = [vp, C.POINTER(ResizeWindow)]
         L.pjd_batch_set_orientation.restype = i32
         L.pjd_batch_set_orientation.argtypes = [vp, C.POINTER(C.c_uint8)]
+        L.pjd_batch_set_resize_pad.restype = i32
+        L.pjd_batch_set_resize_pad.argtypes = [vp, C.POINTER(ResizePad), C.POINTER(C.c_uint8)]
+        L.pjd_batch_set_pad_value.restype = i32
+        L.pjd_batch_set_pad_value.argtypes = [vp, C.POINTER(C.c_float)]
+        L.pjd_resize_pad_check.restype = i32
+        L.pjd_resize_pad_check.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(ResizePad)]
         L.pjd_resize_window_check.restype = i32
         L.pjd_resize_window_check.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(ResizeWindow), i32]
         L.pjd_batch_set_normalize.restype = i32
@@ -438,6 +450,32 @@ class Batch:
         hs = (C.c_uint32 * max(self.n, 1))(*[h for h, _ in sizes])
         self.ctx._check(self.L.pjd_batch_set_resize(self._h, ws, hs), "pjd_batch_set_resize")
         self._resize = sizes
+
+    def set_resize_pad(self, pads, fill=(0, 0, 0)):
+        """pjd_batch_set_resize_pad: picture i fills only the rectangle of its canvas (the size of set_resize()) that pads[i] leaves, and
+        the rest is `fill` (three bytes, R G B) -- C = paste(D, left, top) of include/pjd.h, inside the resample launch and the border
+        launch behind it.  pads[i]: a ResizePad, None (the all-zero record), or a dict / tuple of its fields (left, top, right, bottom).
+        From then on "the target" of every later call is the content, canvas less pad.  Once, after set_resize() and before
+        set_orientation() / set_resize_window() / set_resize_filter() / set_normalize() / bind_output() / upload()."""
+        if len(pads) != self.n:
+            raise ValueError("set_resize_pad: one pad (or None) per picture")
+        if len(fill) != 3 or any(not 0 <= int(v) <= 255 or int(v) != v for v in fill):
+            raise ValueError("set_resize_pad: the fill is three bytes (R, G, B)")
+        arr = (ResizePad * max(self.n, 1))()
+        for i, p in enumerate(pads):
+            if p is not None:
+                arr[i] = resize_pad(p)
+        fl = (C.c_uint8 * 3)(*[int(v) for v in fill])
+        self.ctx._check(self.L.pjd_batch_set_resize_pad(self._h, arr, fl), "pjd_batch_set_resize_pad")
+
+    def set_pad_value(self, values):
+        """pjd_batch_set_pad_value: the border elements of a padded, normalised batch are values[c], converted once to the batch's
+        dtype, instead of the normalised fill ((0, 0, 0): zeros after normalisation).  Once, after set_normalize() on a batch that took
+        set_resize_pad(), before bind_output() / upload()."""
+        if len(values) != 3:
+            raise ValueError("set_pad_value: three values (R, G, B)")
+        va = (C.c_float * 3)(*[float(v) for v in values])
+        self.ctx._check(self.L.pjd_batch_set_pad_value(self._h, va), "pjd_batch_set_pad_value")
 
     def set_orientation(self, orientations):
         """pjd_batch_set_orientation: picture i is delivered in EXIF orientation orientations[i] (1..8; Scanned.orientation, or a value of
@@ -758,6 +796,33 @@ def resize_window(w):
     if not all(0 <= int(v) < 2 ** 32 for v in vals):
         raise ValueError("resize_window: every field must fit 32 bits")
     return ResizeWindow(*[int(v) for v in vals])
+
+
+def resize_pad(p):
+    """A ResizePad from a ResizePad (copied), a dict of its fields, or a tuple (left, top, right, bottom).  ValueError for anything else."""
+    names = [k for k, _ in ResizePad._fields_]
+    if isinstance(p, ResizePad):
+        vals = [getattr(p, k) for k in names]
+    elif isinstance(p, dict):
+        if set(p) - set(names):
+            raise ValueError(f"resize_pad: unknown fields {sorted(set(p) - set(names))}")
+        vals = [p.get(k, 0) for k in names]
+    else:
+        vals = list(p)
+        if len(vals) != 4:
+            raise ValueError("resize_pad: (left, top, right, bottom)")
+    if any(not 0 <= int(v) < 2 ** 32 for v in vals):
+        raise ValueError("resize_pad: every field must fit 32 bits")
+    return ResizePad(*[int(v) for v in vals])
+
+
+def resize_pad_check(out_w, out_h, pad):
+    """pjd_resize_pad_check (host only): True where pjd_batch_set_resize_pad would accept `pad` (anything resize_pad() takes; None: the
+    null record, which it refuses) for a canvas of out_w x out_h."""
+    if not (0 <= int(out_w) < 2 ** 32 and 0 <= int(out_h) < 2 ** 32):
+        return False
+    ref = None if pad is None else C.byref(resize_pad(pad))
+    return dev_lib().pjd_resize_pad_check(int(out_w), int(out_h), ref) == 0
 
 
 def resize_window_check(sw, sh, tw, th, window, filter=RESIZE_BILINEAR):

@@ -91,13 +91,15 @@ def _torch():
 
 
 def _run(ctx, descs, out_format, capacity, offsets, device, resize=None, normalize=None, antialias=False, windows=None, interpolation="bilinear",
-         orientations=None):
+         orientations=None, pads=None, fill=(0, 0, 0), pad_value=None):
     """Create, (set the resize, its orientations, its windows, its filter, the normalisation,) bind to a fresh torch buffer, upload, decode, sync -> (buffer, batch offsets,
     statuses).  The buffer is torch.uint8 whatever the elements are: torch aligns it far beyond an element."""
     torch = _torch()
     with ctx.batch(descs, out_format) as b:
         if resize is not None:
             b.set_resize(resize)
+            if pads is not None:
+                b.set_resize_pad(pads, fill)
             if orientations is not None:
                 b.set_orientation(orientations)
             if windows is not None:
@@ -108,6 +110,8 @@ def _run(ctx, descs, out_format, capacity, offsets, device, resize=None, normali
                 b.set_resize_filter(pjd_amd.RESIZE_ANTIALIAS)
         if normalize is not None:
             b.set_normalize(*normalize)
+            if pads is not None and pad_value is not None:
+                b.set_pad_value(pad_value)
         cap = b.packed_size() if capacity is None else capacity
         buf = torch.empty(max(cap, 1), dtype=torch.uint8, device=device)
         # the block may be a recycled one that work queued on torch's current stream still reads: order that work before ours
@@ -355,6 +359,78 @@ def _windowed_oriented(descs, size, prescale, crops, flips, resize_short, orient
     return run, (windows if any(w is not None for w in windows) else None), oris
 
 
+def letterbox_plan(src_hw, size, mode="center"):
+    """Where an upright picture of src_hw = (h, w) goes in a canvas of size = (H, W) with its aspect ratio kept: (content_h, content_w,
+    left, top, right, bottom).  The side that limits fills the canvas, the other one is rounded to nearest (half up), at least 1 and at
+    most the canvas: if w * H <= h * W the height limits, ch = H and cw = (2 * w * H + h) // (2 * h); else cw = W and
+    ch = (2 * h * W + w) // (2 * w).  mode="center": left = (W - cw) // 2 and top = (H - ch) // 2, the odd column and row go right and
+    below (YOLO's letterbox, "expand to square"); mode="topleft": left = top = 0 (DETR, SAM).  Integers only.  Pure."""
+    h, w, H, W = int(src_hw[0]), int(src_hw[1]), int(size[0]), int(size[1])
+    if h < 1 or w < 1 or H < 1 or W < 1:
+        raise ValueError("letterbox_plan: sizes must be at least 1")
+    if mode not in ("center", "topleft"):
+        raise ValueError(f"letterbox_plan: mode must be \"center\" or \"topleft\", not {mode!r}")
+    if w * H <= h * W:
+        ch, cw = H, max(1, min(W, (2 * w * H + h) // (2 * h)))
+    else:
+        cw, ch = W, max(1, min(H, (2 * h * W + w) // (2 * w)))
+    left, top = ((W - cw) // 2, (H - ch) // 2) if mode == "center" else (0, 0)
+    return ch, cw, left, top, W - cw - left, H - ch - top
+
+
+def _fill(fill):
+    """The `fill` keyword of the letterboxing helpers: three bytes."""
+    fill = tuple(fill)
+    if len(fill) != 3 or any(int(v) != v or not 0 <= int(v) <= 255 for v in fill):
+        raise ValueError("fill: three bytes (R, G, B), each 0..255")
+    return tuple(int(v) for v in fill)
+
+
+def _pad_value(pad_value):
+    """The `pad_value` keyword: None, one finite number for all three channels, or three."""
+    import math
+    if pad_value is None:
+        return None
+    vals = [float(pad_value)] * 3 if isinstance(pad_value, (int, float)) else [float(v) for v in pad_value]
+    if len(vals) != 3 or not all(math.isfinite(v) for v in vals):
+        raise ValueError("pad_value: one finite number, or three (R, G, B)")
+    return vals
+
+
+def _plan_letterbox(descs, size, mode, prescale, crops, flips, resize_short, orientations):
+    """_plan for a letterboxed batch: the content of picture i is letterbox_plan of its UPRIGHT picture (of its crop, where it has one),
+    and everything _plan does happens per picture against that content size -- the pre-scale included.  -> (descriptors, windows or
+    None, orientations or None, pads)."""
+    if mode not in ("center", "topleft"):
+        raise ValueError(f"letterbox must be None, \"center\" or \"topleft\", not {mode!r}")
+    if resize_short is not None:
+        raise ValueError("letterbox and resize_short exclude each other: one crops to the target, the other pads to it")
+    n = len(descs)
+    for name, v in (("crops", crops), ("flips", flips)):
+        if v is not None and len(v) != n:
+            raise ValueError(f"{name}: one entry per picture")
+    if orientations is not None:
+        _orientations(orientations, n)
+    run, windows, oris, pads = [], [], [], []
+    for i, d in enumerate(descs):
+        o = int(orientations[i]) if orientations is not None else 1
+        crop = crops[i] if crops is not None else None
+        if crop is not None:
+            if len(tuple(crop)) != 4 or int(crop[2]) < 1 or int(crop[3]) < 1:
+                raise ValueError(f"crops[{i}] = {tuple(crop)}: (x, y, w, h) with w, h >= 1")
+            uh, uw = int(crop[3]), int(crop[2])
+        else:
+            uh, uw = orient_hw(o, int(d.height), int(d.width))
+        ch, cw, left, top, right, bottom = letterbox_plan((uh, uw), size, mode)
+        r, w, oo = _plan([d], (ch, cw), prescale, None if crops is None else [crop], None if flips is None else [flips[i]], None,
+                         None if orientations is None else [o])
+        run.append(r[0])
+        windows.append(w[0] if w is not None else None)
+        oris.append(oo[0] if oo is not None else 1)
+        pads.append((left, top, right, bottom))
+    return (run, (windows if any(w is not None for w in windows) else None), (oris if orientations is not None else None), pads)
+
+
 def _interpolation(name):
     """The `interpolation` keyword of the resizing helpers, checked before anything is created."""
     if name not in ("bilinear", "bicubic"):
@@ -363,7 +439,7 @@ def _interpolation(name):
 
 
 def decode_resized_batch_tensor(ctx, descs, size, prescale=True, device=None, antialias=False, crops=None, flips=None, resize_short=None,
-                                interpolation="bilinear", orientations=None, libjpeg=False):
+                                interpolation="bilinear", orientations=None, libjpeg=False, letterbox=None, fill=(0, 0, 0)):
     """Pictures of ANY sizes -> (uint8 tensor [N, 3, H, W], statuses), size = (H, W): every picture is resampled to H x W inside
     the decode (the bilinear filter of include/pjd.h, pjd_batch_set_resize) and lands at offset i * 3 * H * W of one buffer, so
     the result is one contiguous NCHW tensor with no copy after the decode, complete on return and readable on any torch stream
@@ -393,18 +469,26 @@ def decode_resized_batch_tensor(ctx, descs, size, prescale=True, device=None, an
     bound of "orient, then resize".  None: today's behaviour, byte for byte.
     libjpeg=True: the picture the filters read is libjpeg's, byte for byte (F_LIBJPEG on copies of the descriptors): what a PIL or
     torchvision.io pipeline resizes.  It takes prescale=False (ValueError before anything is created otherwise): the box pre-scale is
-    not libjpeg's reduced decode."""
+    not libjpeg's reduced decode.
+    letterbox="center" | "topleft": every picture keeps its aspect ratio inside the H x W canvas (letterbox_plan of the UPRIGHT picture,
+    or of its crop) and the rest of the canvas is `fill` (three bytes; YOLO: 114) -- Batch.set_resize_pad, in the same launch and one
+    small one behind it.  crops and orientations work as above against the content size, flips mirror the content inside its
+    rectangle, the pre-scale is picked from the content size; resize_short is excluded (ValueError).  None: today's behaviour."""
     _interpolation(interpolation)
     if len(descs) == 0:
         raise ValueError("decode_resized_batch_tensor: no pictures")
     descs = _libjpeg(descs, libjpeg, prescale)
     th, tw = int(size[0]), int(size[1])
-    run, windows, oris = _plan(descs, (th, tw), prescale, crops, flips, resize_short, orientations)
+    fill, pads = _fill(fill), None
+    if letterbox is not None:
+        run, windows, oris, pads = _plan_letterbox(descs, (th, tw), letterbox, prescale, crops, flips, resize_short, orientations)
+    else:
+        run, windows, oris = _plan(descs, (th, tw), prescale, crops, flips, resize_short, orientations)
     torch = _torch()
     device = torch.device("cuda", ctx.device) if device is None else device
     n, plane = len(descs), 3 * th * tw
     buf, _, st = _run(ctx, run, pjd_amd.OUT_RGB8_PLANAR, n * plane, [i * plane for i in range(n)], device, resize=[(th, tw)] * n,
-                      antialias=antialias, windows=windows, interpolation=interpolation, orientations=oris)
+                      antialias=antialias, windows=windows, interpolation=interpolation, orientations=oris, pads=pads, fill=fill)
     return buf.view(n, 3, th, tw), st
 
 
@@ -422,7 +506,7 @@ def normalize_constants(mean, std):
 
 def decode_normalized_batch_tensor(ctx, descs, size, mean, std, dtype=None, channels_last=False, prescale=True, device=None,
                                    antialias=False, crops=None, flips=None, resize_short=None, interpolation="bilinear", orientations=None,
-                                   libjpeg=False):
+                                   libjpeg=False, letterbox=None, fill=(0, 0, 0), pad_value=None):
     """Pictures of ANY sizes -> (tensor of `dtype` [N, 3, H, W], statuses), size = (H, W); dtype torch.float16 (the default),
     torch.bfloat16 or torch.float32.  As decode_resized_batch_tensor, and every sample v of channel c leaves the same launch as
     fma(v, scale[c], bias[c]) with the constants of normalize_constants(mean, std), converted once to `dtype` (include/pjd.h,
@@ -435,13 +519,22 @@ def decode_normalized_batch_tensor(ctx, descs, size, mean, std, dtype=None, chan
     decode_resized_batch_tensor.  interpolation="bicubic": the bicubic filter (RESIZE_BICUBIC), as there -- `antialias` is not consulted,
     prescale=True still puts the box filter first, prescale=False is exactly the filter over the full-size picture up to the 16x
     limit; any other string than "bilinear" or "bicubic" raises ValueError before anything is created.  orientations, libjpeg: as in
-    decode_resized_batch_tensor."""
+    decode_resized_batch_tensor.  letterbox, fill: as there; the border is normalised like every other sample (fill=(124, 116, 104) is
+    about the ImageNet mean colour), unless pad_value -- one number or three -- is given: the border elements are then exactly that
+    (Batch.set_pad_value; pad_value=0 is "zeros after normalisation": DETR, SAM).  pad_value without letterbox raises ValueError."""
     _interpolation(interpolation)
     if len(descs) == 0:
         raise ValueError("decode_normalized_batch_tensor: no pictures")
     descs = _libjpeg(descs, libjpeg, prescale)
     th, tw = int(size[0]), int(size[1])
     scale, bias = normalize_constants(mean, std)
+    fill, pad_value, pads = _fill(fill), _pad_value(pad_value), None
+    if pad_value is not None and letterbox is None:
+        raise ValueError("pad_value needs letterbox: without it there is no border")
+    plan = None
+    if letterbox is not None:                              # the new keywords are checked before anything is touched; the others where they were
+        plan = _plan_letterbox(descs, (th, tw), letterbox, prescale, crops, flips, resize_short, orientations)
+        plan, pads = plan[:3], plan[3]
     torch = _torch()
     dtype = torch.float16 if dtype is None else dtype
     dts = {torch.float16: (pjd_amd.DT_F16, 2), torch.bfloat16: (pjd_amd.DT_BF16, 2), torch.float32: (pjd_amd.DT_F32, 4)}
@@ -449,10 +542,10 @@ def decode_normalized_batch_tensor(ctx, descs, size, mean, std, dtype=None, chan
         raise ValueError("decode_normalized_batch_tensor: dtype must be torch.float16, torch.bfloat16 or torch.float32")
     dt, es = dts[dtype]
     device = torch.device("cuda", ctx.device) if device is None else device
-    run, windows, oris = _plan(descs, (th, tw), prescale, crops, flips, resize_short, orientations)
+    run, windows, oris = plan if plan is not None else _plan(descs, (th, tw), prescale, crops, flips, resize_short, orientations)
     n, pic = len(descs), 3 * th * tw * es
     buf, _, st = _run(ctx, run, pjd_amd.OUT_RGB8 if channels_last else pjd_amd.OUT_RGB8_PLANAR, n * pic, [i * pic for i in range(n)], device,
                       resize=[(th, tw)] * n, normalize=(dt, scale, bias), antialias=antialias, windows=windows, interpolation=interpolation,
-                      orientations=oris)
+                      orientations=oris, pads=pads, fill=fill, pad_value=pad_value)
     t = buf.view(dtype)
     return (t.view(n, th, tw, 3).permute(0, 3, 1, 2) if channels_last else t.view(n, 3, th, tw)), st

@@ -18,7 +18,12 @@
 //   - windowed: 12 geometries (those of tests/test_gpu_resize_window.py and the four remainders of x) and 10 seeded windows;
 //   - oriented: those windows and 16 shapes for the transposed store (all eight rows and ragged row tiles, one column, one row, rows of
 //     13 samples) through the ORI bodies, every orientation 1..8 (pjd_batch_set_orientation) under windows, mirrors and offsets; the
-//     expectation places Q's samples by the table of include/pjd.h.  The plain set also runs through the ORI body: the same bytes.
+//     expectation places Q's samples by the table of include/pjd.h.  The plain set also runs through the ORI body: the same bytes;
+//   - padded: the oriented set again, every picture a rectangle of a canvas (pjd_batch_set_resize_pad), through the PAD bodies and then
+//     the border kernel's body (pjd_k_resize_border_body.h), every thread of its grid: pads that put the rectangle and the canvas
+//     width at every remainder modulo four, on one side only, and none at all (such a picture has no border line).  The expectation
+//     is the canvas full of fill with the content written over its rectangle: a border byte left out, a content byte filled over or a
+//     byte outside a canvas shows.  The plain set also runs through the PAD body: the same bytes.
 // The source holds every picture back to back with NO padding between them beyond what rounds the buffer to a dword (the kernels
 // stage whole dwords): a read outside a window that mattered would change the result, a read outside the buffer is a sanitizer
 // report.  The expectation is a plain per-pixel loop over the arithmetic of include/pjd.h -- the tap inlines with a shifted index;
@@ -51,18 +56,26 @@ static inline uint32_t emu_tap(uint32_t sn, uint32_t dn, uint32_t i) { uint32_t 
 #define PJD_WIN_STAGE_FIRST 0u
 #define PJD_WIN_STAGE_STEP  1u
 
-template <bool PLANAR, int DT, bool WIN, bool ORI>
-static void thread_bilinear(const uint8_t *src, uint8_t *dst, const PjdDevResize *recs, const PjdDevResizeWin *win, const uint32_t *tile_prefix,
-                            uint32_t n_images, uint32_t n_tiles, const NormArgs nz)
+template <bool PLANAR, int DT, bool WIN, bool ORI, bool PAD>
+static void thread_bilinear(const uint8_t *src, uint8_t *dst, const PjdDevResize *recs, const PjdDevResizeWin *win, const PjdDevResizePad *pad,
+                            const uint32_t *tile_prefix, uint32_t n_images, uint32_t n_tiles, const NormArgs nz)
 {
 #include "../pim-jpeg-decoder_amd/csrc/pjd_k_resize_body.h"
 }
 
-template <bool PLANAR, int DT, bool WIN, bool ORI, int FILT>
-static void thread_aa(uint32_t *seg, const uint8_t *src, uint8_t *dst, const PjdDevResize *recs, const PjdDevResizeWin *win, const uint32_t *tile_prefix,
-                      uint32_t n_images, uint32_t n_tiles, const PjdDevResizeAA *aa, const uint32_t *tab, uint32_t lds_bytes, const NormArgs nz)
+template <bool PLANAR, int DT, bool WIN, bool ORI, bool PAD, int FILT>
+static void thread_aa(uint32_t *seg, const uint8_t *src, uint8_t *dst, const PjdDevResize *recs, const PjdDevResizeWin *win, const PjdDevResizePad *pad,
+                      const uint32_t *tile_prefix, uint32_t n_images, uint32_t n_tiles, const PjdDevResizeAA *aa, const uint32_t *tab, uint32_t lds_bytes,
+                      const NormArgs nz)
 {
 #include "../pim-jpeg-decoder_amd/csrc/pjd_k_resize_aa_body.h"
+}
+
+// one thread of the border kernel (pjd_k_resize_border): lane `lane` of the wave that has canvas line `line`
+static void thread_border(uint32_t lane, uint32_t line, uint8_t *dst, const PjdDevResize *recs, const PjdDevResizePad *pad, const uint32_t *line_prefix,
+                          uint32_t n_images, uint32_t n_lines, uint32_t planar, uint32_t es, const PjdPadFill fill)
+{
+#include "../pim-jpeg-decoder_amd/csrc/pjd_k_resize_border_body.h"
 }
 
 // the expectation's own conversions to binary16 and bfloat16, round to nearest even
@@ -88,7 +101,7 @@ static uint16_t f16bits(float f)
 }
 static uint16_t bf16bits(float f) { uint32_t b; memcpy(&b, &f, 4); b += 0x7fffu + ((b >> 16) & 1u); return (uint16_t)(b >> 16); }
 
-struct Case { uint32_t sw, sh, tw, th; PjdDevResizeWin w; uint32_t o = 1; };   // o: the orientation (oriented set), tw x th then Q's target
+struct Case { uint32_t sw, sh, tw, th; PjdDevResizeWin w; uint32_t o = 1; uint32_t pad[4] = {0, 0, 0, 0}; };   // o: the orientation (oriented set), tw x th then Q's target; pad: left, top, right, bottom of the delivered canvas (padded set)
 
 // the bits t << 2 | v << 1 | h of an orientation, written out from the table of include/pjd.h (not pjd_orient_tvh: that is under test)
 static uint32_t tvh_of(uint32_t o) { return o == 1 ? 0u : o == 2 ? 1u : o == 3 ? 3u : o == 4 ? 2u : o == 5 ? 4u : o == 6 ? 5u : o == 7 ? 7u : 6u; }
@@ -165,17 +178,31 @@ static std::vector<Case> oriented_cases(unsigned seed)
     return cases;
 }
 
-// mode 0: plain, 1: windowed, 2: oriented (the ORI bodies: windows with an orientation)
+// the padded set: the oriented one, every picture a rectangle of a canvas.  The pads walk through every remainder of left and of the
+// canvas width modulo four; every fifth picture has none (no border line of its own in a mixed launch), the others before it a
+// pad on one side only, in turn
+static std::vector<Case> padded_cases(unsigned seed)
+{
+    std::vector<Case> cases = oriented_cases(seed);
+    for (size_t i = 0; i < cases.size(); i++) {
+        const uint32_t k = (uint32_t)i, full[4] = {1 + k % 7, k % 4, (3 * k + 2) % 6, (k / 2) % 5};
+        for (int s = 0; s < 4; s++) cases[i].pad[s] = k % 5 == 4 ? 0u : k % 5 == 3 ? (s == (int)(k / 5 % 4) ? 3u + k % 3 : 0u) : full[s];
+    }
+    return cases;
+}
+
+// mode 0: plain, 1: windowed, 2: oriented (the ORI bodies: windows with an orientation), 3: padded (the PAD bodies and the border kernel's)
 template <bool PLANAR, int DT, int FILT>
 static int run(int mode, uint32_t misalign_elems, unsigned seed)
 {
-    const bool windowed = mode != 0, oriented = mode == 2;
+    const bool windowed = mode != 0, padded = mode == 3, oriented = mode == 2 || padded;
     constexpr bool AA = FILT != PJD_RESIZE_BILINEAR;          // a table-driven filter
     const uint32_t ES = DT == 0 ? 1 : PJD_DT_SIZE(DT);
-    const std::vector<Case> cases = oriented ? oriented_cases(seed) : windowed ? window_cases(seed) : plain_cases(seed, AA);
+    const std::vector<Case> cases = padded ? padded_cases(seed) : oriented ? oriented_cases(seed) : windowed ? window_cases(seed) : plain_cases(seed, AA);
     const size_t n = cases.size();
     std::vector<PjdDevResize> recs(n); std::vector<PjdDevResizeWin> wins(n); std::vector<PjdDevResizeAA> aas(n); std::vector<uint32_t> prefix(n + 1), tab;
-    size_t spos = 0, dpos = misalign_elems * ES; uint32_t t = 0, lds = 0;
+    std::vector<PjdDevResizePad> pads(n); std::vector<uint32_t> lprefix(n + 1);
+    size_t spos = 0, dpos = misalign_elems * ES; uint32_t t = 0, lds = 0, n_lines = 0;
     std::vector<size_t> doff(n);
     for (size_t i = 0; i < n; i++) {
         const Case &c = cases[i]; PjdDevResize &r = recs[i];
@@ -188,7 +215,14 @@ static int run(int mode, uint32_t misalign_elems, unsigned seed)
         r.col_tiles = (c.tw + PJD_RS_COLS - 1) / PJD_RS_COLS; r.dst_off = dpos;
         doff[i] = dpos;
         spos += 3ull * c.sw * c.sh;                        // back to back: a picture's neighbours are other pictures
-        dpos += 3ull * c.tw * c.th * ES + ES * (2 * (i % 3) + 1);                     // element-aligned odd gaps
+        {   // the canvas of the delivered picture (the content itself without a pad), as pjd_batch_set_resize_pad lays the records out
+            const bool tr = oriented && (tvh_of(c.o) >> 2) != 0;
+            const uint32_t dw = tr ? c.th : c.tw, dh = tr ? c.tw : c.th;
+            pads[i] = PjdDevResizePad{dw + c.pad[0] + c.pad[2], dh + c.pad[1] + c.pad[3], c.pad[0], c.pad[1], dw, dh, {0u, 0u}};
+            lprefix[i] = n_lines;
+            if (c.pad[0] | c.pad[1] | c.pad[2] | c.pad[3]) n_lines += (PLANAR ? 3u : 1u) * pads[i].H;
+        }
+        dpos += 3ull * pads[i].W * pads[i].H * ES + ES * (2 * (i % 3) + 1);           // element-aligned odd gaps
         prefix[i] = t; t += r.col_tiles * ((c.th + PJD_RS_ROWS - 1) / PJD_RS_ROWS);
         if (AA) {
             aas[i].x_tab = axis_table(tab, FILT, c.w.w, c.w.vw, aas[i].x_taps);
@@ -201,45 +235,69 @@ static int run(int mode, uint32_t misalign_elems, unsigned seed)
             }
         }
     }
-    prefix[n] = t;
+    prefix[n] = t; lprefix[n] = n_lines;
     const size_t src_bytes = (spos + 3) & ~(size_t)3;        // whole dwords are staged: the buffer ends on one, as every allocation does
     uint8_t *src = (uint8_t *)malloc(src_bytes);              // the sanitizer's view of the source is exactly src_bytes
     for (size_t k = 0; k < src_bytes; k++) src[k] = (uint8_t)rand();
     if (((uintptr_t)src & 3u) != 0) { printf("malloc gave an unaligned block\n"); return 1; }
     const size_t dst_bytes = dpos + 256;
     const NormArgs nz = {{0.01712475f, 0.017507f, -0.01742919f}, {-2.117904f, -2.0357144f, 1.8044444f}};
+    // the fill of the padded set as pjd_batch::launch_pad makes it: three elements (the fill byte, or its normalised value) over twelve bytes
+    const uint8_t fill_u8[3] = {114, 7, 201};
+    uint32_t fill_e[3];
+    for (int ch = 0; ch < 3; ch++) {
+        const float u = fmaf((float)fill_u8[ch], nz.scale[ch], nz.bias[ch]);
+        uint32_t b32; memcpy(&b32, &u, 4);
+        fill_e[ch] = DT == 0 ? fill_u8[ch] : DT == PJD_DT_F32 ? b32 : DT == PJD_DT_F16 ? f16bits(u) : bf16bits(u);
+    }
+    PjdPadFill pf{};
+    if (PLANAR) for (int ch = 0; ch < 3; ch++) pf.d[ch] = ES == 1 ? fill_e[ch] * 0x01010101u : ES == 2 ? fill_e[ch] * 0x00010001u : fill_e[ch];
+    else { uint8_t b12[12]; for (uint32_t k = 0; k < 12; k++) b12[k] = (uint8_t)(fill_e[(k / ES) % 3] >> (8 * (k % ES))); memcpy(pf.d, b12, 12); }
     // every thread of the launch, with the WIN = true or the WIN = false body
-    auto launch = [&](auto WIN, auto ORI) {
-        constexpr bool W = decltype(WIN)::value, O = decltype(ORI)::value;
+    auto launch = [&](auto WIN, auto ORI, auto PADDED) {
+        constexpr bool W = decltype(WIN)::value, O = decltype(ORI)::value, PD = decltype(PADDED)::value;
         uint8_t *dst = (uint8_t *)aligned_alloc(256, (dst_bytes + 255) & ~(size_t)255); memset(dst, 0xA5, dst_bytes);
         const uint32_t n_threads = AA ? 64 : 64 * PJD_RS_WAVES, n_blocks = AA ? t : (t + PJD_RS_WAVES - 1) / PJD_RS_WAVES;
         for (uint32_t b = 0; b < n_blocks; b++) for (uint32_t th = 0; th < n_threads; th++) {
             blockIdx.x = b; threadIdx.x = th;
             if constexpr (AA) {
                 uint32_t *seg = (uint32_t *)malloc(lds ? lds : 4);                   // this thread's "LDS", of the launch's size
-                thread_aa<PLANAR, DT, W, O, FILT>(seg, src, dst, recs.data(), W ? wins.data() : nullptr, prefix.data(), (uint32_t)n, t, aas.data(), tab.data(), lds, nz);
+                thread_aa<PLANAR, DT, W, O, PD, FILT>(seg, src, dst, recs.data(), W ? wins.data() : nullptr, PD ? pads.data() : nullptr, prefix.data(), (uint32_t)n, t, aas.data(), tab.data(), lds, nz);
                 free(seg);
             } else {
-                thread_bilinear<PLANAR, DT, W, O>(src, dst, recs.data(), W ? wins.data() : nullptr, prefix.data(), (uint32_t)n, t, nz);
+                thread_bilinear<PLANAR, DT, W, O, PD>(src, dst, recs.data(), W ? wins.data() : nullptr, PD ? pads.data() : nullptr, prefix.data(), (uint32_t)n, t, nz);
             }
         }
+        if constexpr (PD)                                    // the border kernel behind it: the grid of pjd_launch_resize_border, whole workgroups
+            for (uint32_t b = 0; b < (n_lines + PJD_RS_WAVES - 1) / PJD_RS_WAVES; b++) for (uint32_t th = 0; th < 64 * PJD_RS_WAVES; th++)
+                thread_border(th & 63u, b * PJD_RS_WAVES + (th >> 6), dst, recs.data(), pads.data(), lprefix.data(), (uint32_t)n, n_lines, PLANAR ? 1u : 0u, ES, pf);
         return dst;
     };
-    uint8_t *dst = oriented ? launch(std::true_type{}, std::true_type{}) : windowed ? launch(std::true_type{}, std::false_type{}) : launch(std::false_type{}, std::false_type{});
+    const std::true_type yes{}; const std::false_type no{};
+    uint8_t *dst = padded ? launch(yes, yes, yes) : oriented ? launch(yes, yes, no) : windowed ? launch(yes, no, no) : launch(no, no, no);
     int bad = 0;
     uint32_t clamped = FILT == PJD_RESIZE_BICUBIC ? 0u : 3u;   // bicubic: the final clamp is met at both ends
     if (!windowed) {                                         // the identity window through the WIN = true body: the same bytes
-        uint8_t *again = launch(std::true_type{}, std::false_type{});
+        uint8_t *again = launch(yes, no, no);
         if (memcmp(dst, again, dst_bytes) != 0) { printf("  the identity window through the WIN body gives other bytes\n"); bad++; }
         free(again);
-        again = launch(std::true_type{}, std::true_type{});  // ... and through the ORI body (orientation 1: no PJD_RWI_* bit)
+        again = launch(yes, yes, no);                        // ... and through the ORI body (orientation 1: no PJD_RWI_* bit)
         if (memcmp(dst, again, dst_bytes) != 0) { printf("  the identity window through the ORI body gives other bytes\n"); bad++; }
+        free(again);
+        again = launch(yes, yes, yes);                       // ... and through the PAD body (no pad: the canvas is the content, no border line)
+        if (memcmp(dst, again, dst_bytes) != 0) { printf("  the identity window through the PAD body gives other bytes\n"); bad++; }
         free(again);
     }
     // the expectation: include/pjd.h, pixel by pixel
     std::vector<uint8_t> want(dst_bytes, 0xA5);
     for (size_t i = 0; i < n; i++) {
         const Case &c = cases[i]; const PjdDevResizeWin &w = c.w; const uint8_t *sp = src + recs[i].src_off;
+        const PjdDevResizePad &cv = pads[i];
+        if (padded)                                          // the whole canvas is fill; the content is written over its rectangle below
+            for (size_t e = 0; e < 3ull * cv.W * cv.H; e++) {
+                const uint32_t v = fill_e[PLANAR ? e / ((size_t)cv.W * cv.H) : e % 3];
+                memcpy(want.data() + doff[i] + e * ES, &v, ES);   // little-endian: the element's low bytes
+            }
         auto P = [&](int ch, uint32_t yy, uint32_t xx) -> uint32_t {
             if (xx < w.x || xx >= w.x + w.w || yy < w.y || yy >= w.y + w.h) { printf("the expectation itself left the window\n"); exit(2); }
             return PLANAR ? sp[(size_t)ch * c.sw * c.sh + (size_t)yy * c.sw + xx] : sp[((size_t)yy * c.sw + xx) * 3 + ch];
@@ -282,7 +340,8 @@ static int run(int mode, uint32_t misalign_elems, unsigned seed)
             const uint32_t b3 = tvh_of(c.o), ot = b3 >> 2, ov = (b3 >> 1) & 1u, oh = b3 & 1u;
             const uint32_t dw = ot ? c.th : c.tw, dh = ot ? c.tw : c.th;
             const uint32_t di = ot ? (ov ? c.tw - 1 - x : x) : (ov ? c.th - 1 - y : y), dj = ot ? (oh ? c.th - 1 - y : y) : (oh ? c.tw - 1 - x : x);
-            const size_t e = PLANAR ? ((size_t)ch * dh + di) * dw + dj : ((size_t)di * dw + dj) * 3 + ch;
+            if (dw != cv.cw || dh != cv.ch) { printf("the canvas record is not the delivered picture's\n"); exit(2); }
+            const size_t e = PLANAR ? ((size_t)ch * cv.H + cv.top + di) * cv.W + cv.left + dj : ((size_t)(cv.top + di) * cv.W + cv.left + dj) * 3 + ch;
             uint8_t *o = want.data() + doff[i] + e * ES;
             if (DT == 0) *o = (uint8_t)v;
             else {
@@ -295,7 +354,7 @@ static int run(int mode, uint32_t misalign_elems, unsigned seed)
     for (size_t k = 0; k < dst_bytes; k++) if (dst[k] != want[k]) { if (bad < 4) printf("  mismatch at byte %zu got %02x want %02x\n", k, dst[k], want[k]); bad++; }
     uint32_t rem = windowed ? 0u : 0xfu;                     // the windowed set has a segment at every dword remainder
     for (size_t i = 0; i < n; i++) rem |= 1u << ((recs[i].src_off + (PLANAR ? cases[i].w.x : 3 * cases[i].w.x) + (size_t)cases[i].w.y * recs[i].src_stride) & 3u);
-    printf("%s %s PLANAR=%d DT=%d misalign=%u: %zu pictures, %u tiles, lds %u, remainders %x, clamps %x: %s\n", FILT == PJD_RESIZE_BICUBIC ? "bicubic  " : AA ? "antialias" : "bilinear ", oriented ? "oriented" : windowed ? "windowed" : "plain   ",
+    printf("%s %s PLANAR=%d DT=%d misalign=%u: %zu pictures, %u tiles, lds %u, remainders %x, clamps %x: %s\n", FILT == PJD_RESIZE_BICUBIC ? "bicubic  " : AA ? "antialias" : "bilinear ", padded ? "padded  " : oriented ? "oriented" : windowed ? "windowed" : "plain   ",
            (int)PLANAR, DT, misalign_elems, n, t, lds, rem, clamped, bad ? "MISMATCH" : "equal, guards intact");
     free(dst); free(src);
     return bad != 0 || rem != 0xf || clamped != 3u;
@@ -316,8 +375,9 @@ static int all(int windowed)
 
 int main()
 {
-    const int rc = all<PJD_RESIZE_BILINEAR>(0) | all<PJD_RESIZE_BILINEAR>(1) | all<PJD_RESIZE_BILINEAR>(2) | all<PJD_RESIZE_ANTIALIAS>(0) | all<PJD_RESIZE_ANTIALIAS>(1) |
-                   all<PJD_RESIZE_ANTIALIAS>(2) | all<PJD_RESIZE_BICUBIC>(0) | all<PJD_RESIZE_BICUBIC>(1) | all<PJD_RESIZE_BICUBIC>(2);
+    const int rc = all<PJD_RESIZE_BILINEAR>(0) | all<PJD_RESIZE_BILINEAR>(1) | all<PJD_RESIZE_BILINEAR>(2) | all<PJD_RESIZE_BILINEAR>(3) | all<PJD_RESIZE_ANTIALIAS>(0) |
+                   all<PJD_RESIZE_ANTIALIAS>(1) | all<PJD_RESIZE_ANTIALIAS>(2) | all<PJD_RESIZE_ANTIALIAS>(3) | all<PJD_RESIZE_BICUBIC>(0) | all<PJD_RESIZE_BICUBIC>(1) |
+                   all<PJD_RESIZE_BICUBIC>(2) | all<PJD_RESIZE_BICUBIC>(3);
     printf(rc ? "FAILED\n" : "ALL EQUAL\n");
     return rc;
 }
