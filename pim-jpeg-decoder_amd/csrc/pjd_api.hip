@@ -16,7 +16,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <atomic>
-#include <map>
 #include <mutex>
 #include <string>
 #include <type_traits>
@@ -26,6 +25,7 @@
 #include "pjd_kernels.h"
 #include "pjd_libjpeg.h"
 #include "pjd_plan.h"
+#include "pjd_resize_plan.h"
 
 // Buffers of destroyed batches are kept per context and handed to the next batch (a steady stream of
 // batches then allocates nothing); bounded by pool_cap, freed at pjd_close.
@@ -212,66 +212,111 @@ struct pjd_batch {
     std::vector<uint64_t> res_off, res_bytes;
     uint64_t res_buf_bytes = 0, res_out_bytes = 0;   // packed size (what pjd_batch_packed_size reports), sum of res_bytes
     bool resized = false;                        // pjd_batch_set_resize
-    std::vector<uint32_t> rs_w, rs_h;
-    PjdDevResize *h_rs = nullptr, *d_rs = nullptr;   // the resample work list: page-locked / HBM, [n_images] records ...
-    uint32_t *d_rs_prefix = nullptr;             // ... followed by the prefix sum of tiles, [n_images + 1]
-    size_t rs_bytes = 0;
-    uint32_t rs_tiles = 0;
+    // The resample (pjd_resize_plan.h): what the caller asked for so far, and what it resolves to.  Every setter adds its argument to
+    // the request and resolves all of it again; the records lie in the page-locked halves of the pairs below, pjd_batch_upload sends them.
+    PjdResizeSpec spec;
+    PjdResizeForm form;
+    struct Pair { uint8_t *h = nullptr, *d = nullptr; size_t bytes = 0; };   // page-locked / HBM, taken once (take_pair)
+    Pair rs;                                     // PjdDevResize[n_images], then the prefix sum of tiles [n_images + 1]
+    Pair win;                                    // form.windowed: PjdDevResizeWin[n_images]
+    Pair pad;                                    // form.padded: PjdDevResizePad[n_images], then the prefix sum of their border lines [n_images + 1]
+    Pair aa;                                     // a table-driven filter: PjdDevResizeAA[n_images], then the weight table
     PjdNormalize norm{};                         // pjd_batch_set_normalize: dtype != 0, the result holds elements of PJD_DT_SIZE(dtype) bytes
-    bool filter_set = false;                     // pjd_batch_set_resize_filter: called ...
-    int filter = PJD_RESIZE_BILINEAR;            // ... with this PJD_RESIZE_*; the two table-driven ones (antialiased, bicubic) have
-    uint8_t *h_aa = nullptr, *d_aa = nullptr;    // per-picture records (PjdDevResizeAA[n_images]) and, behind them, the weight table: page-locked / HBM
-    size_t aa_bytes = 0;
-    uint32_t aa_lds = 0;                         // LDS of the launch: the largest row segment a tile of the batch stages
-    bool win_set = false, windowed = false;      // pjd_batch_set_resize_window: called / with a record that is not all zero
-    PjdDevResizeWin *h_win = nullptr, *d_win = nullptr;   // then: the windows, defaults resolved, [n_images]: page-locked / HBM
-    size_t win_bytes = 0;
-    bool ori_set = false, oriented = false;      // pjd_batch_set_orientation: called / with a value other than 1.  Then the batch is windowed
-                                                 // too (identity windows until pjd_batch_set_resize_window): h_win[i].flags hold PJD_RWI_*,
-                                                 // and h_rs[i].tw / th are those of Q, swapped against rs_w / rs_h where transposed
-
-    std::vector<uint32_t> ct_w, ct_h;            // the CONTENT of each delivered picture: rs_w x rs_h (the canvas) less its pad.  What "the target"
-                                                 // means to pjd_batch_set_orientation and everything behind it (include/pjd.h)
-    bool pad_set = false, padded = false;        // pjd_batch_set_resize_pad: called / with a record that is not all zero.  Then the batch is
-                                                 // windowed and oriented too (identity windows, flags 0): it runs the PAD kernels, the most general form
-    PjdDevResizePad *h_pad = nullptr, *d_pad = nullptr;   // then: the canvases [n_images], followed by the prefix sum of their border lines [n_images + 1]
-    size_t pad_bytes = 0;
-    uint32_t pad_lines = 0;
-    uint8_t pad_fill[3] = {0, 0, 0};
+    uint8_t pad_fill[3] = {0, 0, 0};             // pjd_batch_set_resize_pad
     bool pad_value_set = false;                  // pjd_batch_set_pad_value
     float pad_value[3] = {0, 0, 0};
 
-    // the resample launch of this batch, whatever its filter, windowed or not (both launch sites: the decode and the re-run
-    // after the fallback)
+    // the resample launch of this batch, whatever its filter and form (both launch sites: the decode and the re-run after the fallback)
     void launch_resize(hipStream_t s, bool planar) const
     {
-        pjd_launch_resize(s, PjdResizeLaunch{dev.out, res_out, d_rs, d_rs_prefix, dev.n_images, rs_tiles, planar, norm, windowed ? d_win : nullptr, oriented, filter,
-                                             (const PjdDevResizeAA *)d_aa, d_aa ? (const uint32_t *)(d_aa + dev.n_images * sizeof(PjdDevResizeAA)) : nullptr, aa_lds,
-                                             padded ? d_pad : nullptr});
+        const size_t n = dev.n_images;
+        pjd_launch_resize(s, PjdResizeLaunch{dev.out, res_out, (const PjdDevResize *)rs.d, (const uint32_t *)(rs.d + n * sizeof(PjdDevResize)), dev.n_images, form.tiles, planar, norm,
+                                             form.windowed ? (const PjdDevResizeWin *)win.d : nullptr, form.oriented, spec.filter,
+                                             (const PjdDevResizeAA *)aa.d, aa.d ? (const uint32_t *)(aa.d + n * sizeof(PjdDevResizeAA)) : nullptr, form.lds,
+                                             form.padded ? (const PjdDevResizePad *)pad.d : nullptr});
     }
     // ... and the border of its padded pictures, behind it (the same two sites): the two write disjoint bytes
-    void launch_pad(hipStream_t s, bool planar) const;
+    void launch_pad(hipStream_t s, bool planar) const
+    {
+        const size_t n = dev.n_images;
+        pjd_launch_resize_border(s, PjdBorderLaunch{res_out, (const PjdDevResize *)rs.d, (const PjdDevResizePad *)pad.d, (const uint32_t *)(pad.d + n * sizeof(PjdDevResizePad)), dev.n_images,
+                                                    form.lines, planar, norm.dtype ? PJD_DT_SIZE(norm.dtype) : 1u, pjd_pad_fill(norm, planar, pad_fill, pad_value_set ? pad_value : nullptr)});
+    }
 };
 
-namespace { uint32_t f32_to_dtype_bits(int dtype, float u); }
+namespace {
 
-// The fill as the border kernel takes it (PjdPadFill): the three elements -- the fill byte, or its normalised value
-// (pjd_normalize_value), or the batch's pad value converted once -- laid out over twelve bytes of a row.
-void pjd_batch::launch_pad(hipStream_t s, bool planar) const
+// A page-locked and a device block of `bytes` for the batch, from the context's pools, counted in device_bytes.  Taken once: a pair the
+// batch has already is kept.  What a failing call took stays with the batch until it is destroyed.
+int take_pair(pjd_batch *b, pjd_batch::Pair &p, size_t bytes)
 {
-    const uint32_t es = norm.dtype ? PJD_DT_SIZE(norm.dtype) : 1u;
-    uint32_t e[3];
-    for (int c = 0; c < 3; c++)
-        e[c] = !norm.dtype ? pad_fill[c] : f32_to_dtype_bits(norm.dtype, pad_value_set ? pad_value[c] : pjd_normalize_f32(pad_fill[c], norm.scale[c], norm.bias[c]));
-    PjdPadFill f{};
-    uint8_t bytes[12];
-    for (uint32_t t = 0; t < 12u; t++) bytes[t] = (uint8_t)(e[(t / es) % 3u] >> (8u * (t % es)));
-    if (planar)
-        for (int c = 0; c < 3; c++) f.d[c] = es == 1u ? e[c] * 0x01010101u : es == 2u ? e[c] * 0x00010001u : e[c];
-    else
-        std::memcpy(f.d, bytes, 12);
-    pjd_launch_resize_border(s, PjdBorderLaunch{res_out, d_rs, d_pad, (const uint32_t *)(d_pad + dev.n_images), dev.n_images, pad_lines, planar, es, f});
+    if (p.d) return PJD_OK;
+    int rc = p.h ? PJD_OK : pool_pin_alloc(b->ctx, (void **)&p.h, bytes, b->pin_blocks);
+    if (rc == PJD_OK) rc = pool_dev_alloc(b->ctx, (void **)&p.d, bytes, b->dev_blocks);
+    if (rc != PJD_OK) return rc;
+    p.bytes = bytes;
+    b->device_bytes += bytes;
+    return PJD_OK;
 }
+
+// one of the batch's device blocks back to the context's pool, and `counted` bytes off device_bytes
+void give_back(pjd_batch *b, void *p, uint64_t counted)
+{
+    pjd_ctx *ctx = b->ctx;
+    for (size_t k = 0; k < b->dev_blocks.size(); k++)
+        if (b->dev_blocks[k].p == p) {
+            if (!ctx->dev_pool.give(b->dev_blocks[k].p, b->dev_blocks[k].bytes, ctx->pool_cap)) hipFree(b->dev_blocks[k].p);
+            b->dev_blocks.erase(b->dev_blocks.begin() + (long)k);
+            b->device_bytes -= counted;
+            break;
+        }
+}
+
+// records, and what follows them, into the page-locked half of their pair
+template <class A, class B = uint32_t>
+void put(const pjd_batch::Pair &p, const std::vector<A> &a, const std::vector<B> &behind = {})
+{
+    if (!a.empty()) std::memcpy(p.h, a.data(), a.size() * sizeof(A));
+    if (!behind.empty()) std::memcpy(p.h + a.size() * sizeof(A), behind.data(), behind.size() * sizeof(B));
+}
+
+// `spec` resolved to `w`: takes the buffers the records need that the batch does not have yet, then commits request and records.
+// Nothing of the batch changes where it fails (but for a block that stays with it until it is destroyed).
+int commit_request(pjd_batch *b, PjdResizeSpec &spec, const PjdResizeWork &w)
+{
+    hipSetDevice(b->ctx->device);
+    const size_t n = spec.pic.size();
+    int rc = take_pair(b, b->rs, n * sizeof(PjdDevResize) + (n + 1) * sizeof(uint32_t));
+    if (rc == PJD_OK && w.form.windowed) rc = take_pair(b, b->win, n * sizeof(PjdDevResizeWin));
+    if (rc == PJD_OK && w.form.padded) rc = take_pair(b, b->pad, n * sizeof(PjdDevResizePad) + (n + 1) * sizeof(uint32_t));
+    if (rc == PJD_OK && spec.filter != PJD_RESIZE_BILINEAR) rc = take_pair(b, b->aa, n * sizeof(PjdDevResizeAA) + w.tab.size() * sizeof(uint32_t));
+    if (rc != PJD_OK) return rc;
+    put(b->rs, w.recs, w.tile_prefix);
+    if (w.form.windowed) put(b->win, w.win);
+    if (w.form.padded) put(b->pad, w.pad, w.line_prefix);
+    if (spec.filter != PJD_RESIZE_BILINEAR) put(b->aa, w.aa, w.tab);
+    b->spec = std::move(spec);
+    b->form = w.form;
+    return PJD_OK;
+}
+
+// what every setter behind pjd_batch_set_resize does with the batch's request once its own argument is in it
+int apply_request(pjd_batch *b, PjdResizeSpec &spec, const char *setter)
+{
+    PjdResizeWork w;
+    const PjdResizeFault f = pjd_resize_resolve(spec, w);
+    if (!f.text.empty()) { b->ctx->err = std::string(setter) + ": " + f.text; return PJD_E_ARG; }
+    return commit_request(b, spec, w);
+}
+
+// the delivered pictures at other offsets of the result buffer (pjd_batch_set_normalize, pjd_batch_bind_output): request and records
+void set_result_offsets(pjd_batch *b, const std::vector<uint64_t> &off)
+{
+    PjdDevResize *recs = (PjdDevResize *)b->rs.h;
+    for (size_t i = 0; i < off.size(); i++) b->spec.pic[i].dst_off = recs[i].dst_off = off[i];
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -526,10 +571,10 @@ int pjd_batch_upload(pjd_batch *b)
     // (pjd_batch_bind_output: the caller's memory, never BMP) relies on: it is not touched here.
     // With a resize set dev.out is the batch's intermediate, bound or not; the resized pictures are RGB8 or planar, written whole.
     if (!b->bound || b->resized) HIP_TRY(ctx, hipMemsetAsync(b->dev.out, 0, P.out_buf_bytes, s));
-    if (b->resized) HIP_TRY(ctx, hipMemcpyAsync(b->d_rs, b->h_rs, b->rs_bytes, hipMemcpyHostToDevice, s));      // the resample work list (page-locked)
-    if (b->d_aa) HIP_TRY(ctx, hipMemcpyAsync(b->d_aa, b->h_aa, b->aa_bytes, hipMemcpyHostToDevice, s));   // ... and its weight table
-    if (b->windowed) HIP_TRY(ctx, hipMemcpyAsync(b->d_win, b->h_win, b->win_bytes, hipMemcpyHostToDevice, s));  // ... and its source windows
-    if (b->padded) HIP_TRY(ctx, hipMemcpyAsync(b->d_pad, b->h_pad, b->pad_bytes, hipMemcpyHostToDevice, s));    // ... and its canvases
+    if (b->resized) HIP_TRY(ctx, hipMemcpyAsync(b->rs.d, b->rs.h, b->rs.bytes, hipMemcpyHostToDevice, s));          // the resample work list (page-locked)
+    if (b->aa.d) HIP_TRY(ctx, hipMemcpyAsync(b->aa.d, b->aa.h, b->aa.bytes, hipMemcpyHostToDevice, s));             // ... and its weight table
+    if (b->form.windowed) HIP_TRY(ctx, hipMemcpyAsync(b->win.d, b->win.h, b->win.bytes, hipMemcpyHostToDevice, s));  // ... and its source windows
+    if (b->form.padded) HIP_TRY(ctx, hipMemcpyAsync(b->pad.d, b->pad.h, b->pad.bytes, hipMemcpyHostToDevice, s));    // ... and its canvases
     b->uploaded = true;
     return PJD_OK;
 }
@@ -691,7 +736,7 @@ int enqueue_decode(pjd_batch *b, pjd_timings *timings, bool use_groups)
         // whatever form the back end took (the groups' streams have joined `s` above)
         b->launch_resize(s, P.planar);
         kt.mark("resize");
-        if (b->padded) { b->launch_pad(s, P.planar); kt.mark("pad"); }
+        if (b->form.padded) { b->launch_pad(s, P.planar); kt.mark("pad"); }
     }
     HIP_TRY(ctx, hipGetLastError());
     kt.finish();
@@ -785,7 +830,7 @@ int settle(pjd_batch *b)
             if (ev1) (void)hipEventRecord(ev1, s);
             // the pictures just decoded again changed in the intermediate: resample (the whole batch: a rare path)
             if (b->resized) b->launch_resize(s, P.planar);
-            if (b->padded) b->launch_pad(s, P.planar);
+            if (b->form.padded) b->launch_pad(s, P.planar);
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipMemcpyAsync(b->h_status, b->dev.status, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s);
@@ -984,18 +1029,11 @@ int pjd_batch_bind_output(pjd_batch *b, void *device_base, uint64_t capacity, co
     // from here on nothing fails.  The batch's own result buffer goes back to the pool.  Without a resize the result is what the back
     // end writes: the planner's image records (and their copy in the input blob, which pjd_batch_upload sends) take the bound
     // offsets.  With one, only the resample's work list does: the back end keeps writing the intermediate at the planner's offsets.
-    if (!b->bound)
-        for (size_t k = 0; k < b->dev_blocks.size(); k++)
-            if (b->dev_blocks[k].p == (void *)b->res_out) {
-                if (!ctx->dev_pool.give(b->dev_blocks[k].p, b->dev_blocks[k].bytes, ctx->pool_cap)) hipFree(b->dev_blocks[k].p);
-                b->dev_blocks.erase(b->dev_blocks.begin() + (long)k);
-                b->device_bytes -= b->res_buf_bytes;
-                break;
-            }
+    if (!b->bound) give_back(b, b->res_out, b->res_buf_bytes);
     for (size_t i = 0; i < n; i++) b->res_off[i] = ranges[i].first;
     b->res_out = (uint8_t *)device_base;
     if (b->resized) {
-        for (size_t i = 0; i < n; i++) b->h_rs[i].dst_off = ranges[i].first;
+        set_result_offsets(b, b->res_off);
     } else {
         PjdDevImage *h_images = reinterpret_cast<PjdDevImage *>(b->h_in + ((uint8_t *)b->d_images - b->d_in));
         for (size_t i = 0; i < n; i++) P.images[i].out_off = h_images[i].out_off = ranges[i].first;
@@ -1069,56 +1107,34 @@ int pjd_batch_set_resize(pjd_batch *b, const uint32_t *out_w, const uint32_t *ou
     if (!out_w || !out_h) { ctx->err = "set_resize: null size array"; return PJD_E_ARG; }
     if (P.out_format == PJD_OUT_BMP) { ctx->err = "set_resize: a BMP batch cannot be resized (PJD_OUT_RGB8 or PJD_OUT_RGB8_PLANAR)"; return PJD_E_ARG; }
     const size_t n = P.images.size();
-    uint64_t tiles = 0;
-    for (size_t i = 0; i < n; i++) {
-        if (out_w[i] == 0 || out_w[i] > 65535u || out_h[i] == 0 || out_h[i] > 65535u) {
-            ctx->err = fmt_image("set_resize: picture %d: target width and height must be 1..65535", (int)i);
-            return PJD_E_ARG;
-        }
-        if (P.host[i].shard) { ctx->err = fmt_image("set_resize: picture %d is a shard (its picture is only partly written)", (int)i); return PJD_E_ARG; }
-        tiles += (uint64_t)((out_w[i] + PJD_RS_COLS - 1) / PJD_RS_COLS) * ((out_h[i] + PJD_RS_ROWS - 1) / PJD_RS_ROWS);
-    }
-    if (tiles >= (1ull << 31)) { ctx->err = "set_resize: the targets of this batch are too large for one launch"; return PJD_E_ARG; }
-    hipSetDevice(ctx->device);
-    // the work list (page-locked; pjd_batch_upload sends it, pjd_batch_bind_output may still change its target offsets) and the
-    // result buffer: packed, 256-byte aligned offsets, as the planner lays out a batch's own buffer
-    const size_t rs_bytes = n * sizeof(PjdDevResize) + (n + 1) * sizeof(uint32_t);
-    void *h_rs = nullptr, *d_rs = nullptr, *d_res = nullptr;
-    std::vector<uint64_t> off(n), bytes(n);
-    uint64_t pos = 0, sum = 0;
-    for (size_t i = 0; i < n; i++) {
-        off[i] = pos; bytes[i] = 3ull * out_w[i] * out_h[i];
-        pos = (pos + bytes[i] + 255) & ~(uint64_t)255;
-        sum += bytes[i];
-    }
-    int rc = pool_pin_alloc(ctx, &h_rs, rs_bytes, b->pin_blocks);
-    if (rc == PJD_OK) rc = pool_dev_alloc(ctx, &d_rs, rs_bytes, b->dev_blocks);
-    if (rc == PJD_OK) rc = pool_dev_alloc(ctx, &d_res, (size_t)pos, b->dev_blocks);
-    if (rc != PJD_OK) return rc;                           // what was taken stays with the batch until it is destroyed
-    b->device_bytes += rs_bytes + pos;
-    b->h_rs = (PjdDevResize *)h_rs; b->d_rs = (PjdDevResize *)d_rs; b->rs_bytes = rs_bytes;
-    b->d_rs_prefix = (uint32_t *)(b->d_rs + n);
-    uint32_t *prefix = (uint32_t *)(b->h_rs + n);
-    uint32_t t = 0;
+    // the request: every picture from where the back end wrote it at its decode size to the packed layout of the result buffer
+    // (256-byte aligned offsets, as the planner lays out a batch's own buffer; pjd_batch_bind_output may still change them)
+    const PjdPackedLayout lay = pjd_packed_layout(out_w, out_h, n, 1);
+    PjdResizeSpec spec;
+    spec.planar = P.planar;
+    spec.out_w.assign(out_w, out_w + n); spec.out_h.assign(out_h, out_h + n);
+    size_t shard = n;                                      // the first shard of the batch
     for (size_t i = 0; i < n; i++) {
         const PjdDevImage &g = P.images[i];
-        PjdDevResize &r = b->h_rs[i];
         uint32_t sw = 0, sh = 0;
         pjd_scaled_dims(g.width, g.height, (g.flags & PJD_IF_SCALE_MASK) >> PJD_IF_SCALE_SHIFT << 4, &sw, &sh);
-        r.src_off = g.out_off; r.dst_off = off[i];
-        r.sw = sw; r.sh = sh; r.src_stride = g.out_stride;
-        r.tw = out_w[i]; r.th = out_h[i];
-        r.col_tiles = (out_w[i] + PJD_RS_COLS - 1) / PJD_RS_COLS;
-        prefix[i] = t;
-        t += r.col_tiles * ((out_h[i] + PJD_RS_ROWS - 1) / PJD_RS_ROWS);
+        spec.pic.push_back(PjdResizePicture{g.out_off, lay.off[i], sw, sh, g.out_stride});
+        if (P.host[i].shard && shard == n) shard = i;
     }
-    prefix[n] = t;
-    b->rs_tiles = t;
-    b->rs_w.assign(out_w, out_w + n); b->rs_h.assign(out_h, out_h + n);
-    b->ct_w = b->rs_w; b->ct_h = b->rs_h;
+    PjdResizeWork w;
+    const PjdResizeFault f = pjd_resize_resolve(spec, w);
+    // picture by picture: its size, then whether it is a shard; the batch as a whole behind them
+    if (shard < n && !(f.picture >= 0 && (size_t)f.picture <= shard)) { ctx->err = fmt_image("set_resize: picture %d is a shard (its picture is only partly written)", (int)shard); return PJD_E_ARG; }
+    if (!f.text.empty()) { ctx->err = "set_resize: " + f.text; return PJD_E_ARG; }
+    hipSetDevice(ctx->device);
+    void *d_res = nullptr;                                 // the result buffer first: the batch is as it was until everything is taken
+    int rc = pool_dev_alloc(ctx, &d_res, (size_t)lay.buf_bytes, b->dev_blocks);
+    if (rc == PJD_OK) rc = commit_request(b, spec, w);
+    if (rc != PJD_OK) return rc;                           // what was taken stays with the batch until it is destroyed
+    b->device_bytes += lay.buf_bytes;
     b->res_out = (uint8_t *)d_res;
-    b->res_off = off; b->res_bytes = bytes;
-    b->res_buf_bytes = pos; b->res_out_bytes = sum;
+    b->res_off = lay.off; b->res_bytes = lay.bytes;
+    b->res_buf_bytes = lay.buf_bytes; b->res_out_bytes = lay.sum;
     b->resized = true;
     return PJD_OK;
 }
@@ -1150,143 +1166,17 @@ int pjd_batch_set_resize_filter(pjd_batch *b, int filter)
 {
     if (!b) return PJD_E_ARG;
     pjd_ctx *ctx = b->ctx;
-    PjdPlan &P = b->plan;
     if (!b->resized) { ctx->err = "set_resize_filter: no resize is set (pjd_batch_set_resize first)"; return PJD_E_STATE; }
-    if (b->filter_set) { ctx->err = "set_resize_filter: already set for this batch"; return PJD_E_STATE; }
+    if (b->spec.filter_set) { ctx->err = "set_resize_filter: already set for this batch"; return PJD_E_STATE; }
     if (b->norm.dtype != 0) { ctx->err = "set_resize_filter after set_normalize"; return PJD_E_STATE; }
     if (b->bound) { ctx->err = "set_resize_filter after bind_output"; return PJD_E_STATE; }
     if (b->uploaded) { ctx->err = "set_resize_filter after upload"; return PJD_E_STATE; }
-    if (filter != PJD_RESIZE_BILINEAR && filter != PJD_RESIZE_ANTIALIAS && filter != PJD_RESIZE_BICUBIC) { ctx->err = "set_resize_filter: unknown filter (PJD_RESIZE_BILINEAR, PJD_RESIZE_ANTIALIAS or PJD_RESIZE_BICUBIC)"; return PJD_E_ARG; }
-    if (filter == PJD_RESIZE_BILINEAR) { b->filter_set = true; return PJD_OK; }
-    const size_t n = P.images.size();
-    for (size_t i = 0; i < n; i++) {
-        const PjdDevResize &r = b->h_rs[i];
-        if (b->windowed) {
-            // the limit is the window's (include/pjd.h): its size against the virtual target
-            const PjdDevResizeWin &w = b->h_win[i];
-            if (w.w > 16u * w.vw || w.h > 16u * w.vh) {
-                ctx->err = fmt_image("set_resize_filter: the window of picture %d is more than 16x its virtual target on an axis (pre-scale with PJD_F_SCALE_*)", (int)i);
-                return PJD_E_ARG;
-            }
-        } else if (r.sw > 16u * r.tw || r.sh > 16u * r.th) {
-            ctx->err = fmt_image("set_resize_filter: picture %d is more than 16x its target on an axis at its decode size (pre-scale with PJD_F_SCALE_*)", (int)i);
-            return PJD_E_ARG;
-        }
-    }
-    // The weight table: one axis table per distinct (source length, target length) of the batch -- the pictures of a data set share
-    // a few -- each dn heads `first | count << 16`, then taps x dn weights, tap-major, 0 behind a sample's own count (pjd_internal.h).
-    // The bicubic filter has weights of either sign, kept as the bit patterns of int32, and its kernel's 32-bit accumulators hold only
-    // while sum |q_j| <= PJD_BICUBIC_MAX_GAIN (include/pjd.h): `gain` is the largest such sum of the axis, checked where it is used.
-    const bool cubic = filter == PJD_RESIZE_BICUBIC;
-    const uint32_t max_taps = cubic ? PJD_BICUBIC_MAX_TAPS : PJD_AA_MAX_TAPS;
-    struct Axis { uint32_t off, taps, gain; };
-    std::map<std::pair<uint32_t, uint32_t>, Axis> axes;
-    std::vector<uint32_t> tab;
-    auto axis = [&](uint32_t sn, uint32_t dn) -> Axis {
-        auto it = axes.find({sn, dn});
-        if (it != axes.end()) return it->second;
-        const size_t base = tab.size();
-        const uint32_t bound = ((cubic ? 4u : 2u) * std::max(sn, dn) + dn - 1u) / dn;   // no sample has more taps than ceil(2 * S / dn), bicubic ceil(4 * S / dn) (include/pjd.h)
-        const uint32_t cap = std::min<uint32_t>(std::max<uint32_t>(bound, 1u), max_taps);
-        tab.resize(base + (size_t)dn * (1u + cap), 0u);
-        uint32_t taps = 0, gain = 0, w[PJD_BICUBIC_MAX_TAPS];
-        static_assert(PJD_BICUBIC_MAX_TAPS >= PJD_AA_MAX_TAPS, "one array for both filters");
-        for (uint32_t i = 0; i < dn; i++) {
-            uint32_t first, sum = 0;
-            const uint32_t cnt = std::min(cubic ? pjd_resize_bicubic_taps_calc(sn, dn, i, first, (int32_t *)w) : pjd_resize_aa_taps_calc(sn, dn, i, first, w), cap);
-            tab[base + i] = first | (cnt << 16);
-            for (uint32_t t = 0; t < cnt; t++) {
-                tab[base + (size_t)(t + 1u) * dn + i] = w[t];
-                sum += (int32_t)w[t] < 0 ? 0u - w[t] : w[t];
-            }
-            taps = std::max(taps, cnt);
-            gain = std::max(gain, sum);
-        }
-        tab.resize(base + (size_t)dn * (1u + taps));       // the rows no sample reaches are dropped
-        const Axis a{(uint32_t)base, taps, gain};
-        axes[{sn, dn}] = a;
-        return a;
-    };
-    std::vector<PjdDevResizeAA> recs(n);
-    uint32_t lds = 0;
-    for (size_t i = 0; i < n; i++) {
-        const PjdDevResize &r = b->h_rs[i];
-        // a windowed picture takes the tables of its windowed axes, over the whole virtual target (tap index ox + i', row length vw)
-        const PjdDevResizeWin w = b->windowed ? b->h_win[i] : pjd_resize_win_identity(r);
-        if (tab.size() + ((size_t)w.vw + w.vh) * (1u + max_taps) >= (1ull << 31)) { ctx->err = "set_resize_filter: the weight table of this batch is too large"; return PJD_E_ARG; }
-        const Axis x = axis(w.w, w.vw), y = axis(w.h, w.vh);
-        if (cubic && std::max(x.gain, y.gain) > PJD_BICUBIC_MAX_GAIN) {
-            ctx->err = fmt_image("set_resize_filter: the bicubic weights of picture %d sum to more than PJD_BICUBIC_MAX_GAIN in magnitude on an axis", (int)i);
-            return PJD_E_ARG;
-        }
-        recs[i] = PjdDevResizeAA{x.off, x.taps, y.off, y.taps};
-        // the widest row segment one of its tiles stages: first tap of the tile's first column to the last tap of its last one
-        for (uint32_t c0 = 0; c0 < r.tw; c0 += PJD_RS_COLS) {
-            uint32_t e0, e1;                                // the tile's two ends in the table: mirrored where the window flips
-            pjd_resize_win_ends(w, r.tw, c0, std::min(c0 + PJD_RS_COLS, r.tw) - 1u, e0, e1);
-            const uint32_t h0 = tab[x.off + e0], h1 = tab[x.off + e1];
-            lds = std::max(lds, pjd_resize_aa_lds((h1 & 0xffffu) + (h1 >> 16) - (h0 & 0xffffu), P.planar));
-        }
-    }
-    hipSetDevice(ctx->device);
-    const size_t bytes = n * sizeof(PjdDevResizeAA) + tab.size() * sizeof(uint32_t);
-    void *h_aa = nullptr, *d_aa = nullptr;
-    int rc = pool_pin_alloc(ctx, &h_aa, bytes, b->pin_blocks);
-    if (rc == PJD_OK) rc = pool_dev_alloc(ctx, &d_aa, bytes, b->dev_blocks);
-    if (rc != PJD_OK) return rc;                           // what was taken stays with the batch until it is destroyed
-    std::memcpy(h_aa, recs.data(), n * sizeof(PjdDevResizeAA));
-    std::memcpy((uint8_t *)h_aa + n * sizeof(PjdDevResizeAA), tab.data(), tab.size() * sizeof(uint32_t));
-    b->device_bytes += bytes;
-    b->h_aa = (uint8_t *)h_aa; b->d_aa = (uint8_t *)d_aa; b->aa_bytes = bytes; b->aa_lds = lds;
-    b->filter_set = true; b->filter = filter;
-    return PJD_OK;
+    PjdResizeSpec spec = b->spec;
+    spec.filter_set = true; spec.filter = filter;
+    return apply_request(b, spec, "set_resize_filter");
 }
 
 namespace {
-
-// THE validation of a source window (include/pjd.h): null, or what is wrong with it
-const char *resize_window_fault(uint32_t sw, uint32_t sh, uint32_t tw, uint32_t th, const pjd_resize_window *win, int filter)
-{
-    if (sw == 0 || sw > 65535u || sh == 0 || sh > 65535u || tw == 0 || tw > 65535u || th == 0 || th > 65535u) return "picture and target sizes must be 1..65535";
-    if (!win) return "null record";
-    if (filter != PJD_RESIZE_BILINEAR && filter != PJD_RESIZE_ANTIALIAS && filter != PJD_RESIZE_BICUBIC) return "unknown filter (PJD_RESIZE_BILINEAR, PJD_RESIZE_ANTIALIAS or PJD_RESIZE_BICUBIC)";
-    if ((win->w == 0) != (win->h == 0)) return "an empty window (w and h are both 0 for the whole picture, or both at least 1)";
-    if (win->w == 0 && (win->x != 0 || win->y != 0)) return "x and y must be 0 where w == h == 0 (the whole picture)";
-    const uint64_t w = win->w ? win->w : sw, h = win->h ? win->h : sh;
-    if ((uint64_t)win->x + w > sw || (uint64_t)win->y + h > sh) return "the window is not inside the picture at its decode size";
-    if (win->vw > 65535u || win->vh > 65535u) return "the virtual target must be at most 65535 x 65535";
-    const uint64_t vw = win->vw ? win->vw : tw, vh = win->vh ? win->vh : th;
-    if ((uint64_t)win->ox + tw > vw || (uint64_t)win->oy + th > vh) return "the delivered columns and rows are not inside the virtual target";
-    if (win->flags & ~PJD_RW_HFLIP) return "unknown flag bits";
-    if (win->reserved_ != 0) return "reserved_ must be 0";
-    if (filter != PJD_RESIZE_BILINEAR && (w > 16u * vw || h > 16u * vh)) return "the window is more than 16x its virtual target on an axis (PJD_RESIZE_ANTIALIAS, PJD_RESIZE_BICUBIC)";
-    return nullptr;
-}
-
-// binary32 -> binary16 bits, round to nearest even, subnormals kept, overflow to infinity (the host side of PJD_DT_F16; the device
-// converts in hardware, tests/test_gpu_normalize.py holds the two together)
-uint16_t f32_to_f16_bits(float f)
-{
-    uint32_t x;
-    std::memcpy(&x, &f, 4);
-    const uint32_t sign = (x >> 16) & 0x8000u, a = x & 0x7fffffffu;
-    if (a >= 0x7f800000u) return (uint16_t)(sign | (a > 0x7f800000u ? 0x7e00u : 0x7c00u));
-    if (a < 0x38800000u) {                                 // below 2^-14: a subnormal result, in units of 2^-24
-        const uint32_t e = a >> 23;
-        if (e < 102u) return (uint16_t)sign;               // below 2^-25: zero
-        const uint32_t m = (a & 0x7fffffu) | 0x800000u, shift = 126u - e;      // 14..24
-        uint32_t q = m >> shift;
-        const uint32_t rem = m & ((1u << shift) - 1u), half = 1u << (shift - 1u);
-        if (rem > half || (rem == half && (q & 1u))) q++;
-        return (uint16_t)(sign | q);
-    }
-    const uint32_t r = a - 0x38000000u;                    // exponent rebiased from 127 to 15
-    uint32_t q = r >> 13;
-    const uint32_t rem = r & 0x1fffu;
-    if (rem > 0x1000u || (rem == 0x1000u && (q & 1u))) q++;
-    if (q > 0x7c00u) q = 0x7c00u;
-    return (uint16_t)(sign | q);                           // a carry out of the mantissa runs into the exponent: 0x7c00 is infinity
-}
 
 bool finite_f32(float f)
 {
@@ -1295,33 +1185,11 @@ bool finite_f32(float f)
     return (x & 0x7f800000u) != 0x7f800000u;
 }
 
-// binary32 -> one element of a PJD_DT_* type in the low bytes of a word: ONE rounding to nearest even for the 16-bit types (the
-// conversions of pjd_normalize_value, which the device makes in hardware)
-uint32_t f32_to_dtype_bits(int dtype, float u)
-{
-    uint32_t bits;
-    std::memcpy(&bits, &u, 4);
-    if (dtype == PJD_DT_F32) return bits;
-    if (dtype == PJD_DT_F16) return f32_to_f16_bits(u);
-    bits += 0x7fffu + ((bits >> 16) & 1u);
-    return bits >> 16;
-}
-
-// THE validation of a pad record (include/pjd.h): null, or what is wrong with it.  The sums are 64-bit: no record wraps into range.
-const char *resize_pad_fault(uint32_t out_w, uint32_t out_h, const pjd_resize_pad *pad)
-{
-    if (out_w == 0 || out_w > 65535u || out_h == 0 || out_h > 65535u) return "the canvas must be 1..65535 x 1..65535";
-    if (!pad) return "null record";
-    if ((uint64_t)pad->left + pad->right >= out_w) return "left + right leaves no column of content (it must be less than out_w)";
-    if ((uint64_t)pad->top + pad->bottom >= out_h) return "top + bottom leaves no row of content (it must be less than out_h)";
-    return nullptr;
-}
-
 }  // namespace
 
 int pjd_resize_window_check(uint32_t sw, uint32_t sh, uint32_t tw, uint32_t th, const pjd_resize_window *win, int filter)
 {
-    return resize_window_fault(sw, sh, tw, th, win, filter) ? PJD_E_ARG : PJD_OK;
+    return pjd_resize_window_fault(sw, sh, tw, th, win, filter) ? PJD_E_ARG : PJD_OK;
 }
 
 int pjd_batch_set_orientation(pjd_batch *b, const uint8_t *orientation)
@@ -1329,58 +1197,16 @@ int pjd_batch_set_orientation(pjd_batch *b, const uint8_t *orientation)
     if (!b) return PJD_E_ARG;
     pjd_ctx *ctx = b->ctx;
     if (!b->resized) { ctx->err = "set_orientation: no resize is set (pjd_batch_set_resize first)"; return PJD_E_STATE; }
-    if (b->ori_set) { ctx->err = "set_orientation: already set for this batch"; return PJD_E_STATE; }
-    if (b->win_set) { ctx->err = "set_orientation after set_resize_window"; return PJD_E_STATE; }
-    if (b->filter_set) { ctx->err = "set_orientation after set_resize_filter"; return PJD_E_STATE; }
+    if (b->spec.ori_set) { ctx->err = "set_orientation: already set for this batch"; return PJD_E_STATE; }
+    if (b->spec.win_set) { ctx->err = "set_orientation after set_resize_window"; return PJD_E_STATE; }
+    if (b->spec.filter_set) { ctx->err = "set_orientation after set_resize_filter"; return PJD_E_STATE; }
     if (b->norm.dtype != 0) { ctx->err = "set_orientation after set_normalize"; return PJD_E_STATE; }
     if (b->bound) { ctx->err = "set_orientation after bind_output"; return PJD_E_STATE; }
     if (b->uploaded) { ctx->err = "set_orientation after upload"; return PJD_E_STATE; }
     if (!orientation) { ctx->err = "set_orientation: null orientation array"; return PJD_E_ARG; }
-    const size_t n = b->plan.images.size();
-    bool any = false;
-    uint64_t tiles = 0;
-    for (size_t i = 0; i < n; i++) {
-        const uint32_t o = orientation[i];
-        if (o < 1u || o > 8u) { ctx->err = fmt_image("set_orientation: picture %d: the orientation must be 1..8", (int)i); return PJD_E_ARG; }
-        any = any || o != 1u;
-        // the tiles of Q: its target is the delivered one with the axes swapped where the orientation transposes
-        const bool t = (pjd_orient_flags(o) & PJD_RWI_TRANSPOSE) != 0;
-        const uint32_t tw = t ? b->ct_h[i] : b->ct_w[i], th = t ? b->ct_w[i] : b->ct_h[i];
-        tiles += (uint64_t)((tw + PJD_RS_COLS - 1) / PJD_RS_COLS) * ((th + PJD_RS_ROWS - 1) / PJD_RS_ROWS);
-    }
-    if (tiles >= (1ull << 31)) { ctx->err = "set_orientation: the targets of this batch are too large for one launch"; return PJD_E_ARG; }
-    if (any) {
-        // Identity windows that carry the orientation (pjd_batch_set_resize_window fills in what it is given): the batch runs the
-        // windowed launch's ORI form.  All 1: nothing is taken and the batch keeps the launch it had.
-        // A padded batch (pjd_batch_set_resize_pad) has the windows already, and its targets are the contents.
-        if (!b->padded) {
-            hipSetDevice(ctx->device);
-            const size_t bytes = n * sizeof(PjdDevResizeWin);
-            void *h_win = nullptr, *d_win = nullptr;
-            int rc = pool_pin_alloc(ctx, &h_win, bytes, b->pin_blocks);
-            if (rc == PJD_OK) rc = pool_dev_alloc(ctx, &d_win, bytes, b->dev_blocks);
-            if (rc != PJD_OK) return rc;                   // what was taken stays with the batch until it is destroyed
-            b->device_bytes += bytes;
-            b->h_win = (PjdDevResizeWin *)h_win; b->d_win = (PjdDevResizeWin *)d_win; b->win_bytes = bytes;
-        }
-        uint32_t *prefix = (uint32_t *)(b->h_rs + n);
-        uint32_t t = 0;
-        for (size_t i = 0; i < n; i++) {
-            PjdDevResize &r = b->h_rs[i];
-            const uint32_t f = pjd_orient_flags(orientation[i]);
-            if (f & PJD_RWI_TRANSPOSE) { r.tw = b->ct_h[i]; r.th = b->ct_w[i]; }
-            r.col_tiles = (r.tw + PJD_RS_COLS - 1) / PJD_RS_COLS;
-            prefix[i] = t;
-            t += r.col_tiles * ((r.th + PJD_RS_ROWS - 1) / PJD_RS_ROWS);
-            b->h_win[i] = pjd_resize_win_identity(r);
-            b->h_win[i].flags = f;
-        }
-        prefix[n] = t;
-        b->rs_tiles = t;
-        b->windowed = b->oriented = true;
-    }
-    b->ori_set = true;
-    return PJD_OK;
+    PjdResizeSpec spec = b->spec;
+    spec.ori_set = true; spec.orientation.assign(orientation, orientation + spec.pic.size());
+    return apply_request(b, spec, "set_orientation");
 }
 
 int pjd_batch_set_resize_window(pjd_batch *b, const pjd_resize_window *win)
@@ -1388,52 +1214,20 @@ int pjd_batch_set_resize_window(pjd_batch *b, const pjd_resize_window *win)
     if (!b) return PJD_E_ARG;
     pjd_ctx *ctx = b->ctx;
     if (!b->resized) { ctx->err = "set_resize_window: no resize is set (pjd_batch_set_resize first)"; return PJD_E_STATE; }
-    if (b->win_set) { ctx->err = "set_resize_window: already set for this batch"; return PJD_E_STATE; }
-    if (b->filter_set) { ctx->err = "set_resize_window after set_resize_filter"; return PJD_E_STATE; }
+    if (b->spec.win_set) { ctx->err = "set_resize_window: already set for this batch"; return PJD_E_STATE; }
+    if (b->spec.filter_set) { ctx->err = "set_resize_window after set_resize_filter"; return PJD_E_STATE; }
     if (b->norm.dtype != 0) { ctx->err = "set_resize_window after set_normalize"; return PJD_E_STATE; }
     if (b->bound) { ctx->err = "set_resize_window after bind_output"; return PJD_E_STATE; }
     if (b->uploaded) { ctx->err = "set_resize_window after upload"; return PJD_E_STATE; }
     if (!win) { ctx->err = "set_resize_window: null record array"; return PJD_E_ARG; }
-    const size_t n = b->plan.images.size();
-    bool any = false;
-    for (size_t i = 0; i < n; i++) {
-        const PjdDevResize &r = b->h_rs[i];
-        const pjd_resize_window &w = win[i];
-        if (const char *fault = resize_window_fault(r.sw, r.sh, r.tw, r.th, &w, PJD_RESIZE_BILINEAR)) {
-            ctx->err = fmt_image("set_resize_window: picture %d: ", (int)i) + fault;
-            return PJD_E_ARG;
-        }
-        any = any || w.x || w.y || w.w || w.h || w.vw || w.vh || w.ox || w.oy || w.flags;
-    }
-    if (any) {
-        // the records with every default resolved, as the kernels read them; all zero: the batch keeps the launch it had.  An oriented
-        // batch (pjd_batch_set_orientation) has the records already: r.tw and r.th are Q's there, and the window's mirror composes
-        // with the orientation's tap mirror by exclusive-or
-        if (!b->oriented) {
-            hipSetDevice(ctx->device);
-            const size_t bytes = n * sizeof(PjdDevResizeWin);
-            void *h_win = nullptr, *d_win = nullptr;
-            int rc = pool_pin_alloc(ctx, &h_win, bytes, b->pin_blocks);
-            if (rc == PJD_OK) rc = pool_dev_alloc(ctx, &d_win, bytes, b->dev_blocks);
-            if (rc != PJD_OK) return rc;                   // what was taken stays with the batch until it is destroyed
-            b->device_bytes += bytes;
-            b->h_win = (PjdDevResizeWin *)h_win; b->d_win = (PjdDevResizeWin *)d_win; b->win_bytes = bytes;
-        }
-        for (size_t i = 0; i < n; i++) {
-            const PjdDevResize &r = b->h_rs[i];
-            const pjd_resize_window &w = win[i];
-            const uint32_t ori = b->oriented ? b->h_win[i].flags : 0u;
-            b->h_win[i] = PjdDevResizeWin{w.x, w.y, w.w ? w.w : r.sw, w.h ? w.h : r.sh, w.vw ? w.vw : r.tw, w.vh ? w.vh : r.th, w.ox, w.oy, w.flags ^ ori, 0u};
-        }
-        b->windowed = true;
-    }
-    b->win_set = true;
-    return PJD_OK;
+    PjdResizeSpec spec = b->spec;
+    spec.win_set = true; spec.win.assign(win, win + spec.pic.size());
+    return apply_request(b, spec, "set_resize_window");
 }
 
 int pjd_resize_pad_check(uint32_t out_w, uint32_t out_h, const pjd_resize_pad *pad)
 {
-    return resize_pad_fault(out_w, out_h, pad) ? PJD_E_ARG : PJD_OK;
+    return pjd_resize_pad_fault(out_w, out_h, pad) ? PJD_E_ARG : PJD_OK;
 }
 
 int pjd_batch_set_resize_pad(pjd_batch *b, const pjd_resize_pad *pad, const uint8_t fill[3])
@@ -1441,73 +1235,27 @@ int pjd_batch_set_resize_pad(pjd_batch *b, const pjd_resize_pad *pad, const uint
     if (!b) return PJD_E_ARG;
     pjd_ctx *ctx = b->ctx;
     if (!b->resized) { ctx->err = "set_resize_pad: no resize is set (pjd_batch_set_resize first)"; return PJD_E_STATE; }
-    if (b->pad_set) { ctx->err = "set_resize_pad: already set for this batch"; return PJD_E_STATE; }
-    if (b->ori_set) { ctx->err = "set_resize_pad after set_orientation"; return PJD_E_STATE; }
-    if (b->win_set) { ctx->err = "set_resize_pad after set_resize_window"; return PJD_E_STATE; }
-    if (b->filter_set) { ctx->err = "set_resize_pad after set_resize_filter"; return PJD_E_STATE; }
+    if (b->spec.pad_set) { ctx->err = "set_resize_pad: already set for this batch"; return PJD_E_STATE; }
+    if (b->spec.ori_set) { ctx->err = "set_resize_pad after set_orientation"; return PJD_E_STATE; }
+    if (b->spec.win_set) { ctx->err = "set_resize_pad after set_resize_window"; return PJD_E_STATE; }
+    if (b->spec.filter_set) { ctx->err = "set_resize_pad after set_resize_filter"; return PJD_E_STATE; }
     if (b->norm.dtype != 0) { ctx->err = "set_resize_pad after set_normalize"; return PJD_E_STATE; }
     if (b->bound) { ctx->err = "set_resize_pad after bind_output"; return PJD_E_STATE; }
     if (b->uploaded) { ctx->err = "set_resize_pad after upload"; return PJD_E_STATE; }
     if (!pad) { ctx->err = "set_resize_pad: null record array"; return PJD_E_ARG; }
     if (!fill) { ctx->err = "set_resize_pad: null fill"; return PJD_E_ARG; }
-    const size_t n = b->plan.images.size();
-    bool any = false;
-    uint64_t lines = 0;
-    for (size_t i = 0; i < n; i++) {
-        if (const char *fault = resize_pad_fault(b->rs_w[i], b->rs_h[i], &pad[i])) {
-            ctx->err = fmt_image("set_resize_pad: picture %d: ", (int)i) + fault;
-            return PJD_E_ARG;
-        }
-        const bool here = pad[i].left || pad[i].top || pad[i].right || pad[i].bottom;
-        any = any || here;
-        if (here) lines += (uint64_t)(b->plan.planar ? 3u : 1u) * b->rs_h[i];
-    }
-    if (lines >= (1ull << 31)) { ctx->err = "set_resize_pad: the canvases of this batch are too large for one launch"; return PJD_E_ARG; }
-    if (any) {
-        // The canvases, and identity windows without an orientation (pjd_batch_set_orientation and _set_resize_window fill in what they
-        // are given): the batch runs the PAD form of the oriented launch, whose targets are the contents.  The contents are no larger
-        // than the canvases, so the tiles stay below the limit pjd_batch_set_resize checked.  All zero: nothing is taken and the batch
-        // keeps the launch it had.
-        hipSetDevice(ctx->device);
-        const size_t win_bytes = n * sizeof(PjdDevResizeWin), pad_bytes = n * sizeof(PjdDevResizePad) + (n + 1) * sizeof(uint32_t);
-        void *h_win = nullptr, *d_win = nullptr, *h_pad = nullptr, *d_pad = nullptr;
-        int rc = pool_pin_alloc(ctx, &h_win, win_bytes, b->pin_blocks);
-        if (rc == PJD_OK) rc = pool_dev_alloc(ctx, &d_win, win_bytes, b->dev_blocks);
-        if (rc == PJD_OK) rc = pool_pin_alloc(ctx, &h_pad, pad_bytes, b->pin_blocks);
-        if (rc == PJD_OK) rc = pool_dev_alloc(ctx, &d_pad, pad_bytes, b->dev_blocks);
-        if (rc != PJD_OK) return rc;                       // what was taken stays with the batch until it is destroyed
-        b->device_bytes += win_bytes + pad_bytes;
-        b->h_win = (PjdDevResizeWin *)h_win; b->d_win = (PjdDevResizeWin *)d_win; b->win_bytes = win_bytes;
-        b->h_pad = (PjdDevResizePad *)h_pad; b->d_pad = (PjdDevResizePad *)d_pad; b->pad_bytes = pad_bytes;
-        uint32_t *prefix = (uint32_t *)(b->h_rs + n), *lprefix = (uint32_t *)(b->h_pad + n);
-        uint32_t t = 0, l = 0;
-        for (size_t i = 0; i < n; i++) {
-            PjdDevResize &r = b->h_rs[i];
-            const pjd_resize_pad &p = pad[i];
-            b->ct_w[i] = b->rs_w[i] - p.left - p.right; b->ct_h[i] = b->rs_h[i] - p.top - p.bottom;
-            r.tw = b->ct_w[i]; r.th = b->ct_h[i];
-            r.col_tiles = (r.tw + PJD_RS_COLS - 1) / PJD_RS_COLS;
-            prefix[i] = t;
-            t += r.col_tiles * ((r.th + PJD_RS_ROWS - 1) / PJD_RS_ROWS);
-            b->h_win[i] = pjd_resize_win_identity(r);
-            b->h_pad[i] = PjdDevResizePad{b->rs_w[i], b->rs_h[i], p.left, p.top, b->ct_w[i], b->ct_h[i], {0u, 0u}};
-            lprefix[i] = l;
-            if (p.left || p.top || p.right || p.bottom) l += (b->plan.planar ? 3u : 1u) * b->rs_h[i];
-        }
-        prefix[n] = t; lprefix[n] = l;
-        b->rs_tiles = t; b->pad_lines = l;
-        for (int c = 0; c < 3; c++) b->pad_fill[c] = fill[c];
-        b->windowed = b->oriented = b->padded = true;
-    }
-    b->pad_set = true;
-    return PJD_OK;
+    PjdResizeSpec spec = b->spec;
+    spec.pad_set = true; spec.pad.assign(pad, pad + spec.pic.size());
+    const int rc = apply_request(b, spec, "set_resize_pad");
+    if (rc == PJD_OK) std::memcpy(b->pad_fill, fill, 3);
+    return rc;
 }
 
 int pjd_batch_set_pad_value(pjd_batch *b, const float value[3])
 {
     if (!b) return PJD_E_ARG;
     pjd_ctx *ctx = b->ctx;
-    if (!b->pad_set) { ctx->err = "set_pad_value: the batch has no pad (pjd_batch_set_resize_pad first)"; return PJD_E_STATE; }
+    if (!b->spec.pad_set) { ctx->err = "set_pad_value: the batch has no pad (pjd_batch_set_resize_pad first)"; return PJD_E_STATE; }
     if (b->norm.dtype == 0) { ctx->err = "set_pad_value: the batch is not normalised (pjd_batch_set_normalize first)"; return PJD_E_STATE; }
     if (b->pad_value_set) { ctx->err = "set_pad_value: already set for this batch"; return PJD_E_STATE; }
     if (b->bound) { ctx->err = "set_pad_value after bind_output"; return PJD_E_STATE; }
@@ -1524,7 +1272,7 @@ int pjd_normalize_value(int dtype, uint32_t v, float scale, float bias, void *ou
 {
     if (dtype != PJD_DT_F16 && dtype != PJD_DT_BF16 && dtype != PJD_DT_F32) return PJD_E_ARG;
     if (v > 255u || !finite_f32(scale) || !finite_f32(bias) || !out) return PJD_E_ARG;
-    const uint32_t e = f32_to_dtype_bits(dtype, pjd_normalize_f32(v, scale, bias));
+    const uint32_t e = pjd_f32_to_dtype_bits(dtype, pjd_normalize_f32(v, scale, bias));
     if (dtype == PJD_DT_F32) { std::memcpy(out, &e, 4); return PJD_OK; }
     const uint16_t h = (uint16_t)e;
     std::memcpy(out, &h, 2);
@@ -1550,43 +1298,26 @@ int pjd_batch_set_normalize(pjd_batch *b, int dtype, const float scale[3], const
     hipSetDevice(ctx->device);
     // the result buffer in elements of the new size: packed, 256-byte aligned offsets.  Taken before anything changes: a failure
     // leaves the batch as it was (but for a block that stays with it until it is destroyed).
-    std::vector<uint32_t> w(n), h(n);
-    for (size_t i = 0; i < n; i++) {
-        if (b->resized) { w[i] = b->rs_w[i]; h[i] = b->rs_h[i]; }
-        else pjd_scaled_dims(P.images[i].width, P.images[i].height, (P.images[i].flags & PJD_IF_SCALE_MASK) >> PJD_IF_SCALE_SHIFT << 4, &w[i], &h[i]);
+    std::vector<uint32_t> w = b->spec.out_w, h = b->spec.out_h;
+    if (!b->resized) {
+        w.resize(n); h.resize(n);
+        for (size_t i = 0; i < n; i++) pjd_scaled_dims(P.images[i].width, P.images[i].height, (P.images[i].flags & PJD_IF_SCALE_MASK) >> PJD_IF_SCALE_SHIFT << 4, &w[i], &h[i]);
     }
-    const uint64_t es = PJD_DT_SIZE(dtype);
-    std::vector<uint64_t> off(n), bytes(n);
-    uint64_t pos = 0, sum = 0;
-    for (size_t i = 0; i < n; i++) {
-        off[i] = pos; bytes[i] = 3ull * w[i] * h[i] * es;
-        pos = (pos + bytes[i] + 255) & ~(uint64_t)255;
-        sum += bytes[i];
-    }
-    // one of the batch's blocks back to the context's pool
-    auto give_back = [&](void *p, uint64_t counted) {
-        for (size_t k = 0; k < b->dev_blocks.size(); k++)
-            if (b->dev_blocks[k].p == p) {
-                if (!ctx->dev_pool.give(b->dev_blocks[k].p, b->dev_blocks[k].bytes, ctx->pool_cap)) hipFree(b->dev_blocks[k].p);
-                b->dev_blocks.erase(b->dev_blocks.begin() + (long)k);
-                b->device_bytes -= counted;
-                break;
-            }
-    };
+    const PjdPackedLayout lay = pjd_packed_layout(w.data(), h.data(), n, PJD_DT_SIZE(dtype));
     void *d_res = nullptr;
-    int rc = pool_dev_alloc(ctx, &d_res, (size_t)pos, b->dev_blocks);
+    int rc = pool_dev_alloc(ctx, &d_res, (size_t)lay.buf_bytes, b->dev_blocks);
     if (rc != PJD_OK) return rc;
-    b->device_bytes += pos;
+    b->device_bytes += lay.buf_bytes;
     if (!b->resized) {
         // no resize set: the identity resample (every tap weight 0) of every picture at its own output size
         rc = pjd_batch_set_resize(b, w.data(), h.data());
-        if (rc != PJD_OK) { give_back(d_res, pos); return rc; }
+        if (rc != PJD_OK) { give_back(b, d_res, lay.buf_bytes); return rc; }
     }
-    give_back(b->res_out, b->res_buf_bytes);               // the uint8 result buffer of the resize
-    for (size_t i = 0; i < n; i++) b->h_rs[i].dst_off = off[i];
+    give_back(b, b->res_out, b->res_buf_bytes);            // the uint8 result buffer of the resize
+    set_result_offsets(b, lay.off);
     b->res_out = (uint8_t *)d_res;
-    b->res_off = off; b->res_bytes = bytes;
-    b->res_buf_bytes = pos; b->res_out_bytes = sum;
+    b->res_off = lay.off; b->res_bytes = lay.bytes;
+    b->res_buf_bytes = lay.buf_bytes; b->res_out_bytes = lay.sum;
     b->norm.dtype = dtype;
     for (int c = 0; c < 3; c++) { b->norm.scale[c] = scale[c]; b->norm.bias[c] = bias[c]; }
     return PJD_OK;

@@ -378,7 +378,7 @@ static inline __host__ __device__ void pjd_resize_tap_calc(uint32_t sn, uint32_t
     i1 = i0 + 1u < sn ? i0 + 1u : sn - 1u;
 }
 
-// The work list of the resample launch (pjd_k_resize.hip), built by pjd_batch_set_resize: one record per picture and the prefix
+// The work list of the resample launch (pjd_k_resize.hip), built by pjd_resize_resolve (pjd_resize_plan.cpp): one record per picture and the prefix
 // sum of their TILES.  A tile is PJD_RS_ROWS target rows x PJD_RS_COLS target columns, the work of one wave: lane l makes
 // PJD_RS_PX adjacent pixels of every row of the tile.
 #define PJD_RS_PX    4
@@ -396,7 +396,7 @@ struct PjdDevResize {
 // ---- antialiased resize (pjd_batch_set_resize_filter; the arithmetic is normative: include/pjd.h) ----------------------------
 // One axis of the widened triangle filter: target sample i of dn over sn source samples -> the first source sample with a weight,
 // the number of taps (returned; 1..PJD_AA_MAX_TAPS) and their weights q[0 .. count-1] in 1/65536, which sum to 65536 exactly.  THE
-// implementation: pjd_resize_aa_taps exports it, pjd_batch_set_resize_filter fills the batch's weight table with it (the kernel
+// implementation: pjd_resize_aa_taps exports it, pjd_resize_resolve (pjd_resize_plan.cpp) fills the batch's weight table with it (the kernel
 // divides nothing).  sn, dn in 1..65535, i < dn, sn <= 16 * dn.  All in 64 bits: (2 * i + 1) * sn reaches 2^33.
 static inline __host__ __device__ uint32_t pjd_resize_aa_taps_calc(uint32_t sn, uint32_t dn, uint32_t i, uint32_t &first, uint32_t *q)
 {
@@ -424,7 +424,7 @@ static inline __host__ __device__ uint32_t pjd_resize_aa_taps_calc(uint32_t sn, 
 // ---- bicubic resize (pjd_batch_set_resize_filter, PJD_RESIZE_BICUBIC; the arithmetic is normative: include/pjd.h) ----------------
 // One axis of Keys' cubic (a = -0.5), widened where the axis shrinks: target sample i of dn over sn source samples -> the first
 // source sample of the support, the number of taps (returned; 1..PJD_BICUBIC_MAX_TAPS) and their SIGNED weights q[0 .. count-1] in
-// 1/65536, which sum to 65536 exactly.  THE implementation: pjd_resize_bicubic_taps exports it, pjd_batch_set_resize_filter fills the
+// 1/65536, which sum to 65536 exactly.  THE implementation: pjd_resize_bicubic_taps exports it, pjd_resize_resolve fills the
 // batch's weight table with it.  HOST ONLY: r_j * 2^17 needs 69 bits at 65535-sample axes, so the quantisation is in 128-bit
 // integers; the kernel divides nothing.  sn, dn in 1..65535, i < dn, sn <= 16 * dn.  The raw weights fit 64 bits: T < 2^17, D < 2 * T,
 // so every term of the two cubics stays below 2^56 and their sum over 64 taps below 2^62.
@@ -532,7 +532,7 @@ struct PjdDevResizePad {
 };
 // the constants of the border kernel: the fill as twelve bytes of a canvas row.  Planar: d[c] is channel c's element repeated over a
 // dword.  Interleaved: d[0..2] are the first twelve bytes of a row of fill (R G B R ... in elements of 1, 2 or 4 bytes; 12 is a
-// multiple of every pixel size).  Made once on the host (pjd_batch_set_resize_pad / _set_normalize / _set_pad_value).
+// multiple of every pixel size).  Made on the host by pjd_pad_fill (pjd_resize_plan.cpp).
 struct PjdPadFill { uint32_t d[3]; };
 // the dword of fill at byte j of a canvas line (any j: an aligned ADDRESS need not be an aligned offset): four bytes of the pattern of
 // period 12 from j % 12 on.  p0..p2: d[0..2] interleaved, channel c's d[c] three times planar.

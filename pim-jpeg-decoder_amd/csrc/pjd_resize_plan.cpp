@@ -1,0 +1,259 @@
+// pjd_resize_plan.cpp -- the resample work list as a function of the request (pjd_resize_plan.h).  Host only, no HIP call.
+#include "pjd_resize_plan.h"
+
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+#include <map>
+
+namespace {
+
+PjdResizeFault fault_at(int picture, const char *text, const char *more = "")
+{
+    char buf[64];
+    std::snprintf(buf, sizeof buf, "picture %d: ", picture);
+    return PjdResizeFault{std::string(buf) + text + more, picture};
+}
+
+PjdResizeFault fault_of(const char *fmt, int picture)        // a text that names its picture itself
+{
+    char buf[200];
+    std::snprintf(buf, sizeof buf, fmt, picture);
+    return PjdResizeFault{buf, picture};
+}
+
+// The weight table of a table-driven filter: one axis table per distinct (source length, target length) of the batch -- the pictures
+// of a data set share a few -- each dn heads `first | count << 16`, then taps x dn weights, tap-major, 0 behind a sample's own count
+// (pjd_internal.h).  The bicubic filter has weights of either sign, kept as the bit patterns of int32, and its kernel's 32-bit
+// accumulators hold only while sum |q_j| <= PJD_BICUBIC_MAX_GAIN (include/pjd.h): `gain` is the largest such sum of the axis.
+struct Axis { uint32_t off, taps, gain; };
+struct AxisTables {
+    const bool cubic;
+    const uint32_t max_taps;
+    std::vector<uint32_t> &tab;
+    std::map<std::pair<uint32_t, uint32_t>, Axis> axes;
+    AxisTables(int filter, std::vector<uint32_t> &t) : cubic(filter == PJD_RESIZE_BICUBIC), max_taps(cubic ? PJD_BICUBIC_MAX_TAPS : PJD_AA_MAX_TAPS), tab(t) {}
+    Axis axis(uint32_t sn, uint32_t dn)
+    {
+        auto it = axes.find({sn, dn});
+        if (it != axes.end()) return it->second;
+        const size_t base = tab.size();
+        const uint32_t bound = ((cubic ? 4u : 2u) * std::max(sn, dn) + dn - 1u) / dn;   // no sample has more taps than ceil(2 * S / dn), bicubic ceil(4 * S / dn) (include/pjd.h)
+        const uint32_t cap = std::min<uint32_t>(std::max<uint32_t>(bound, 1u), max_taps);
+        tab.resize(base + (size_t)dn * (1u + cap), 0u);
+        uint32_t taps = 0, gain = 0, w[PJD_BICUBIC_MAX_TAPS];
+        static_assert(PJD_BICUBIC_MAX_TAPS >= PJD_AA_MAX_TAPS, "one array for both filters");
+        for (uint32_t i = 0; i < dn; i++) {
+            uint32_t first, sum = 0;
+            const uint32_t cnt = std::min(cubic ? pjd_resize_bicubic_taps_calc(sn, dn, i, first, (int32_t *)w) : pjd_resize_aa_taps_calc(sn, dn, i, first, w), cap);
+            tab[base + i] = first | (cnt << 16);
+            for (uint32_t t = 0; t < cnt; t++) {
+                tab[base + (size_t)(t + 1u) * dn + i] = w[t];
+                sum += (int32_t)w[t] < 0 ? 0u - w[t] : w[t];
+            }
+            taps = std::max(taps, cnt);
+            gain = std::max(gain, sum);
+        }
+        tab.resize(base + (size_t)dn * (1u + taps));       // the rows no sample reaches are dropped
+        return axes[{sn, dn}] = Axis{(uint32_t)base, taps, gain};
+    }
+};
+
+uint64_t tiles_of(uint32_t tw, uint32_t th) { return (uint64_t)((tw + PJD_RS_COLS - 1) / PJD_RS_COLS) * ((th + PJD_RS_ROWS - 1) / PJD_RS_ROWS); }
+
+// binary32 -> binary16 bits, round to nearest even, subnormals kept, overflow to infinity (the host side of PJD_DT_F16; the device
+// converts in hardware, tests/test_gpu_normalize.py holds the two together)
+uint16_t f32_to_f16_bits(float f)
+{
+    uint32_t x;
+    std::memcpy(&x, &f, 4);
+    const uint32_t sign = (x >> 16) & 0x8000u, a = x & 0x7fffffffu;
+    if (a >= 0x7f800000u) return (uint16_t)(sign | (a > 0x7f800000u ? 0x7e00u : 0x7c00u));
+    if (a < 0x38800000u) {                                 // below 2^-14: a subnormal result, in units of 2^-24
+        const uint32_t e = a >> 23;
+        if (e < 102u) return (uint16_t)sign;               // below 2^-25: zero
+        const uint32_t m = (a & 0x7fffffu) | 0x800000u, shift = 126u - e;      // 14..24
+        uint32_t q = m >> shift;
+        const uint32_t rem = m & ((1u << shift) - 1u), half = 1u << (shift - 1u);
+        if (rem > half || (rem == half && (q & 1u))) q++;
+        return (uint16_t)(sign | q);
+    }
+    const uint32_t r = a - 0x38000000u;                    // exponent rebiased from 127 to 15
+    uint32_t q = r >> 13;
+    const uint32_t rem = r & 0x1fffu;
+    if (rem > 0x1000u || (rem == 0x1000u && (q & 1u))) q++;
+    if (q > 0x7c00u) q = 0x7c00u;
+    return (uint16_t)(sign | q);                           // a carry out of the mantissa runs into the exponent: 0x7c00 is infinity
+}
+
+}  // namespace
+
+const char *pjd_resize_window_fault(uint32_t sw, uint32_t sh, uint32_t tw, uint32_t th, const pjd_resize_window *win, int filter)
+{
+    if (sw == 0 || sw > 65535u || sh == 0 || sh > 65535u || tw == 0 || tw > 65535u || th == 0 || th > 65535u) return "picture and target sizes must be 1..65535";
+    if (!win) return "null record";
+    if (filter != PJD_RESIZE_BILINEAR && filter != PJD_RESIZE_ANTIALIAS && filter != PJD_RESIZE_BICUBIC) return "unknown filter (PJD_RESIZE_BILINEAR, PJD_RESIZE_ANTIALIAS or PJD_RESIZE_BICUBIC)";
+    if ((win->w == 0) != (win->h == 0)) return "an empty window (w and h are both 0 for the whole picture, or both at least 1)";
+    if (win->w == 0 && (win->x != 0 || win->y != 0)) return "x and y must be 0 where w == h == 0 (the whole picture)";
+    const uint64_t w = win->w ? win->w : sw, h = win->h ? win->h : sh;
+    if ((uint64_t)win->x + w > sw || (uint64_t)win->y + h > sh) return "the window is not inside the picture at its decode size";
+    if (win->vw > 65535u || win->vh > 65535u) return "the virtual target must be at most 65535 x 65535";
+    const uint64_t vw = win->vw ? win->vw : tw, vh = win->vh ? win->vh : th;
+    if ((uint64_t)win->ox + tw > vw || (uint64_t)win->oy + th > vh) return "the delivered columns and rows are not inside the virtual target";
+    if (win->flags & ~PJD_RW_HFLIP) return "unknown flag bits";
+    if (win->reserved_ != 0) return "reserved_ must be 0";
+    if (filter != PJD_RESIZE_BILINEAR && (w > 16u * vw || h > 16u * vh)) return "the window is more than 16x its virtual target on an axis (PJD_RESIZE_ANTIALIAS, PJD_RESIZE_BICUBIC)";
+    return nullptr;
+}
+
+// The sums are 64-bit: no record wraps into range.
+const char *pjd_resize_pad_fault(uint32_t out_w, uint32_t out_h, const pjd_resize_pad *pad)
+{
+    if (out_w == 0 || out_w > 65535u || out_h == 0 || out_h > 65535u) return "the canvas must be 1..65535 x 1..65535";
+    if (!pad) return "null record";
+    if ((uint64_t)pad->left + pad->right >= out_w) return "left + right leaves no column of content (it must be less than out_w)";
+    if ((uint64_t)pad->top + pad->bottom >= out_h) return "top + bottom leaves no row of content (it must be less than out_h)";
+    return nullptr;
+}
+
+PjdResizeFault pjd_resize_resolve(const PjdResizeSpec &spec, PjdResizeWork &out)
+{
+    out = PjdResizeWork{};
+    PjdResizeForm &form = out.form;
+    const size_t n = spec.pic.size();
+    const bool table = spec.filter == PJD_RESIZE_ANTIALIAS || spec.filter == PJD_RESIZE_BICUBIC;
+    if (!table && spec.filter != PJD_RESIZE_BILINEAR) return PjdResizeFault{"unknown filter (PJD_RESIZE_BILINEAR, PJD_RESIZE_ANTIALIAS or PJD_RESIZE_BICUBIC)", -1};
+    for (size_t i = 0; i < n; i++)
+        if (spec.out_w[i] == 0 || spec.out_w[i] > 65535u || spec.out_h[i] == 0 || spec.out_h[i] > 65535u) return fault_at((int)i, "target width and height must be 1..65535");
+
+    // the content of every delivered picture: its canvas less its pad; a padded picture has a border line per canvas line
+    out.ct_w = spec.out_w; out.ct_h = spec.out_h;
+    std::vector<uint8_t> bordered(n, 0);
+    uint64_t lines = 0;
+    if (spec.pad_set)
+        for (size_t i = 0; i < n; i++) {
+            const pjd_resize_pad &p = spec.pad[i];
+            if (const char *f = pjd_resize_pad_fault(spec.out_w[i], spec.out_h[i], &p)) return fault_at((int)i, f);
+            out.ct_w[i] -= p.left + p.right; out.ct_h[i] -= p.top + p.bottom;
+            bordered[i] = p.left || p.top || p.right || p.bottom;
+            if (bordered[i]) lines += (uint64_t)(spec.planar ? 3u : 1u) * spec.out_h[i];
+            form.padded = form.padded || bordered[i];
+        }
+    if (lines >= (1ull << 31)) return PjdResizeFault{"the canvases of this batch are too large for one launch", -1};
+
+    // Q, the picture the resample computes: its target is the content with the axes swapped where the orientation transposes
+    std::vector<uint32_t> ori(n, 0u), tw(out.ct_w), th(out.ct_h);
+    uint64_t tiles = 0;
+    for (size_t i = 0; i < n; i++) {
+        const uint32_t o = spec.ori_set ? spec.orientation[i] : 1u;
+        if (o < 1u || o > 8u) return fault_at((int)i, "the orientation must be 1..8");
+        ori[i] = pjd_orient_flags(o);
+        if (ori[i] & PJD_RWI_TRANSPOSE) std::swap(tw[i], th[i]);
+        form.oriented = form.oriented || o != 1u;
+        tiles += tiles_of(tw[i], th[i]);
+    }
+    if (tiles >= (1ull << 31)) return PjdResizeFault{"the targets of this batch are too large for one launch", -1};
+
+    bool any_win = false;
+    if (spec.win_set)
+        for (size_t i = 0; i < n; i++) {
+            const pjd_resize_window &w = spec.win[i];
+            if (const char *f = pjd_resize_window_fault(spec.pic[i].sw, spec.pic[i].sh, tw[i], th[i], &w, PJD_RESIZE_BILINEAR)) return fault_at((int)i, f);
+            any_win = any_win || w.x || w.y || w.w || w.h || w.vw || w.vh || w.ox || w.oy || w.flags;
+        }
+    // the most general form a batch needs is the one it runs: a pad brings the oriented launch, an orientation the windowed one
+    form.oriented = form.oriented || form.padded;
+    form.windowed = form.oriented || any_win;
+
+    // the records, as the kernels read them (pjd_internal.h)
+    out.recs.resize(n); out.tile_prefix.resize(n + 1);
+    if (form.windowed) out.win.resize(n);
+    if (form.padded) { out.pad.resize(n); out.line_prefix.resize(n + 1); }
+    for (size_t i = 0; i < n; i++) {
+        const PjdResizePicture &p = spec.pic[i];
+        PjdDevResize &r = out.recs[i];
+        r = PjdDevResize{p.src_off, p.dst_off, p.sw, p.sh, p.src_stride, tw[i], th[i], (tw[i] + PJD_RS_COLS - 1) / PJD_RS_COLS};
+        out.tile_prefix[i] = form.tiles;
+        form.tiles += (uint32_t)tiles_of(tw[i], th[i]);
+        if (form.windowed) {
+            // every default resolved; the window's mirror composes with the orientation's tap mirror by exclusive-or
+            const pjd_resize_window w = spec.win_set ? spec.win[i] : pjd_resize_window{};
+            out.win[i] = PjdDevResizeWin{w.x, w.y, w.w ? w.w : r.sw, w.h ? w.h : r.sh, w.vw ? w.vw : r.tw, w.vh ? w.vh : r.th, w.ox, w.oy, w.flags ^ ori[i], 0u};
+        }
+        if (form.padded) {
+            out.pad[i] = PjdDevResizePad{spec.out_w[i], spec.out_h[i], spec.pad[i].left, spec.pad[i].top, out.ct_w[i], out.ct_h[i], {0u, 0u}};
+            out.line_prefix[i] = form.lines;
+            if (bordered[i]) form.lines += (spec.planar ? 3u : 1u) * spec.out_h[i];
+        }
+    }
+    out.tile_prefix[n] = form.tiles;
+    if (form.padded) out.line_prefix[n] = form.lines;
+    if (!table) return PjdResizeFault{};
+
+    // a table-driven filter.  A windowed picture takes the tables of its windowed axes, over the whole virtual target (tap index
+    // ox + i', row length vw); one without is the windowed one with the identity window.  The limit is the window's (include/pjd.h)
+    auto window = [&](size_t i) { return form.windowed ? out.win[i] : pjd_resize_win_identity(out.recs[i]); };
+    for (size_t i = 0; i < n; i++) {
+        const PjdDevResizeWin w = window(i);
+        if (w.w > 16u * w.vw || w.h > 16u * w.vh)
+            return fault_of(form.windowed ? "the window of picture %d is more than 16x its virtual target on an axis (pre-scale with PJD_F_SCALE_*)"
+                                          : "picture %d is more than 16x its target on an axis at its decode size (pre-scale with PJD_F_SCALE_*)", (int)i);
+    }
+    AxisTables tables(spec.filter, out.tab);
+    out.aa.resize(n);
+    for (size_t i = 0; i < n; i++) {
+        const PjdDevResize &r = out.recs[i];
+        const PjdDevResizeWin w = window(i);
+        if (out.tab.size() + ((size_t)w.vw + w.vh) * (1u + tables.max_taps) >= (1ull << 31)) return PjdResizeFault{"the weight table of this batch is too large", -1};
+        const Axis x = tables.axis(w.w, w.vw), y = tables.axis(w.h, w.vh);
+        if (tables.cubic && std::max(x.gain, y.gain) > PJD_BICUBIC_MAX_GAIN)
+            return fault_of("the bicubic weights of picture %d sum to more than PJD_BICUBIC_MAX_GAIN in magnitude on an axis", (int)i);
+        out.aa[i] = PjdDevResizeAA{x.off, x.taps, y.off, y.taps};
+        // the widest row segment one of its tiles stages: first tap of the tile's first column to the last tap of its last one
+        for (uint32_t c0 = 0; c0 < r.tw; c0 += PJD_RS_COLS) {
+            uint32_t e0, e1;                                // the tile's two ends in the table: mirrored where the window flips
+            pjd_resize_win_ends(w, r.tw, c0, std::min(c0 + PJD_RS_COLS, r.tw) - 1u, e0, e1);
+            const uint32_t h0 = out.tab[x.off + e0], h1 = out.tab[x.off + e1];
+            form.lds = std::max(form.lds, pjd_resize_aa_lds((h1 & 0xffffu) + (h1 >> 16) - (h0 & 0xffffu), spec.planar));
+        }
+    }
+    return PjdResizeFault{};
+}
+
+PjdPackedLayout pjd_packed_layout(const uint32_t *w, const uint32_t *h, size_t n, uint64_t elem_bytes)
+{
+    PjdPackedLayout l;
+    l.off.resize(n); l.bytes.resize(n);
+    for (size_t i = 0; i < n; i++) {
+        l.off[i] = l.buf_bytes; l.bytes[i] = 3ull * w[i] * h[i] * elem_bytes;
+        l.buf_bytes = (l.buf_bytes + l.bytes[i] + 255) & ~(uint64_t)255;
+        l.sum += l.bytes[i];
+    }
+    return l;
+}
+
+uint32_t pjd_f32_to_dtype_bits(int dtype, float u)
+{
+    uint32_t bits;
+    std::memcpy(&bits, &u, 4);
+    if (dtype == PJD_DT_F32) return bits;
+    if (dtype == PJD_DT_F16) return f32_to_f16_bits(u);
+    bits += 0x7fffu + ((bits >> 16) & 1u);
+    return bits >> 16;
+}
+
+PjdPadFill pjd_pad_fill(const PjdNormalize &norm, bool planar, const uint8_t fill[3], const float *pad_value)
+{
+    const uint32_t es = norm.dtype ? PJD_DT_SIZE(norm.dtype) : 1u;
+    uint32_t e[3];
+    for (int c = 0; c < 3; c++)
+        e[c] = !norm.dtype ? fill[c] : pjd_f32_to_dtype_bits(norm.dtype, pad_value ? pad_value[c] : pjd_normalize_f32(fill[c], norm.scale[c], norm.bias[c]));
+    PjdPadFill f{};
+    uint8_t bytes[12];
+    for (uint32_t t = 0; t < 12u; t++) bytes[t] = (uint8_t)(e[(t / es) % 3u] >> (8u * (t % es)));
+    if (planar)
+        for (int c = 0; c < 3; c++) f.d[c] = es == 1u ? e[c] * 0x01010101u : es == 2u ? e[c] * 0x00010001u : e[c];
+    else
+        std::memcpy(f.d, bytes, 12);
+    return f;
+}

@@ -1,0 +1,75 @@
+// pjd_resize_plan.h -- resize on decode, host side: what a batch was asked for -> the work list of the resample launch.
+//
+// The records the kernels of pjd_k_resize.hip read are a PURE FUNCTION of the request: pjd_resize_resolve makes all of them from a
+// PjdResizeSpec in one go, and every setter of pjd_api.hip (pjd_batch_set_resize, _set_resize_pad, _set_orientation,
+// _set_resize_window, _set_resize_filter) adds its argument to the batch's request and resolves again.  Each rule of include/pjd.h --
+// content = canvas - pad, the transpose swap, window defaults, the mirror's exclusive-or, the prefix sums, the axis tables, the LDS of
+// the launch, every limit -- is stated once, here.  Plain C++, no HIP: tools/resize_plan_host.cpp checks it on the CPU under the
+// sanitizers, tools/resize_host.cpp runs the kernel bodies over its records.
+#pragma once
+#include <string>
+#include <vector>
+
+#include "../../include/pjd.h"
+#include "pjd_internal.h"
+
+// What the caller said, nothing derived.  An optional array that was given (`*_set`) but is all neutral -- all-zero pads, orientations
+// all 1, all-zero windows -- resolves to what its absence resolves to; the flags are what the call-order rules of the setters read.
+struct PjdResizePicture {
+    uint64_t src_off, dst_off;             // the picture at its decode size in the intermediate buffer; the delivered one in the result buffer
+    uint32_t sw, sh, src_stride;           // decode size, and bytes per source row
+};
+struct PjdResizeSpec {
+    std::vector<PjdResizePicture> pic;
+    bool planar = false;
+    std::vector<uint32_t> out_w, out_h;    // pjd_batch_set_resize: the delivered canvases
+    bool pad_set = false, ori_set = false, win_set = false, filter_set = false;
+    std::vector<pjd_resize_pad> pad;       // pjd_batch_set_resize_pad, as given
+    std::vector<uint8_t> orientation;      // pjd_batch_set_orientation, as given
+    std::vector<pjd_resize_window> win;    // pjd_batch_set_resize_window, as given: zeros for defaults
+    int filter = PJD_RESIZE_BILINEAR;      // pjd_batch_set_resize_filter
+};
+
+// What chooses the kernel and sizes its grid ...
+struct PjdResizeForm {
+    uint32_t tiles = 0, lines = 0, lds = 0;                     // tiles of the resample launch, canvas lines of the border launch, LDS bytes of a table-driven launch
+    bool windowed = false, oriented = false, padded = false;    // the WIN / ORI / PAD kernels; padded implies oriented implies windowed
+};
+// ... and everything it reads (pjd_internal.h).  win, pad + line_prefix, aa + tab are empty where the form does not read them.
+struct PjdResizeWork {
+    PjdResizeForm form;
+    std::vector<PjdDevResize> recs;        // target: Q's content (the canvas less its pad, axes swapped where the orientation transposes)
+    std::vector<uint32_t> tile_prefix;     // [n + 1]
+    std::vector<PjdDevResizeWin> win;      // defaults resolved, flags: PJD_RW_HFLIP ^ pjd_orient_flags
+    std::vector<PjdDevResizePad> pad;
+    std::vector<uint32_t> line_prefix;     // [n + 1]
+    std::vector<PjdDevResizeAA> aa;
+    std::vector<uint32_t> tab;             // one axis table per distinct (source length, target length)
+    std::vector<uint32_t> ct_w, ct_h;      // the content of each delivered picture: the canvas less its pad
+};
+
+// no fault: text is empty.  The text is what pjd_last_error reports behind the setter's own "set_...: "; picture -1: the batch as a whole
+struct PjdResizeFault {
+    std::string text;
+    int picture = -1;
+};
+PjdResizeFault pjd_resize_resolve(const PjdResizeSpec &spec, PjdResizeWork &out);
+
+// THE validation of a source window and of a pad record (include/pjd.h): null, or what is wrong with it
+const char *pjd_resize_window_fault(uint32_t sw, uint32_t sh, uint32_t tw, uint32_t th, const pjd_resize_window *win, int filter);
+const char *pjd_resize_pad_fault(uint32_t out_w, uint32_t out_h, const pjd_resize_pad *pad);
+
+// The packed layout of a batch's results, as the planner lays out a batch's own buffer: n pictures of 3 * w * h elements of
+// elem_bytes at 256-byte aligned offsets
+struct PjdPackedLayout {
+    std::vector<uint64_t> off, bytes;
+    uint64_t buf_bytes = 0, sum = 0;       // the buffer (what pjd_batch_packed_size reports); the pictures alone
+};
+PjdPackedLayout pjd_packed_layout(const uint32_t *w, const uint32_t *h, size_t n, uint64_t elem_bytes);
+
+// binary32 -> one element of a PJD_DT_* type in the low bytes of a word: ONE rounding to nearest even for the 16-bit types (the
+// conversions of pjd_normalize_value, which the device makes in hardware)
+uint32_t pjd_f32_to_dtype_bits(int dtype, float u);
+// The fill as the border kernel takes it: the three elements -- the fill byte (norm.dtype 0), or its normalised value, or pad_value
+// (null: none) converted once -- laid out over twelve bytes of a row
+PjdPadFill pjd_pad_fill(const PjdNormalize &norm, bool planar, const uint8_t fill[3], const float *pad_value);

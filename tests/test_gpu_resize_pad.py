@@ -275,6 +275,65 @@ def test_bound_unaligned_output_over_two_prefills(ctx, shape_cases, fmt, filt, d
     assert not np.array_equal(results[0], results[1]), "the two pre-fills differ"
 
 
+# ---- 2b: everything at once ---------------------------------------------------------------------------------------------------------------------
+# (Q's target, orientation, pad, window): a content 259 columns wide (a second, ragged column tile) that takes no window, a transposed
+# one under a mirrored window, a picture without a pad under a half turn and a window with offsets, a content of 9 rows (a second,
+# ragged row tile) mirrored
+STACKED = [((259, 5), 1, (5, 3, 6, 4), None), ((20, 9), 6, (1, 0, 3, 1), dict(x=3, y=5, w=40, h=30, flags=1)),
+           ((19, 11), 3, (0, 0, 0, 0), dict(x=1, y=2, w=50, h=40, vw=25, vh=14, ox=4, oy=2)), ((7, 9), 2, (0, 2, 0, 0), None)]
+
+
+@pytest.mark.parametrize("fmt,filt", [("rgb8", "antialias"), ("planar", "bicubic")])
+def test_every_setter_stacked_in_one_bound_batch(ctx, sources, fmt, filt):
+    """One batch that every setter has touched: a pad with one picture that has none, orientations 1, 2, 3 and the transposing 6,
+    windows of which two are all zero and one is mirrored, a table-driven filter, binary16 output with a pad value, bound into
+    caller-owned memory at offsets of the caller's choosing.  Bit for bit the models', and not a byte outside the canvases."""
+    import pjd_amd
+    planar, dtype, value = fmt == "planar", nm.DT_F16, (0.5, -1.0, 3e-6)
+    scale, bias = _constants()
+    data, rgb = sources[(61, 45, 53)]
+    met = set()
+    cases = [(data, _canvas(tw, th, o, pad), o, {filt: _case(rgb, win, tw, th, o, pad, filt, met, (tw, th, o, pad))}, pad) for (tw, th), o, pad, win in STACKED]
+    assert cases[0][1] == (12, 270) and cases[1][1] == (21, 13) and {c[2] for c in cases} == {1, 2, 3, 6}
+    donor_sc = _scanned(golden_bytes("big_640x480_420_q85"), 0)
+    with ctx.batch([donor_sc.desc], pjd_amd.OUT_RGB8) as donor:
+        donor.upload(); donor.decode()
+        (pattern,), _ = donor.download()
+        pattern = pattern.reshape(-1).copy()
+        mem, cap = donor.device_output(0), donor.output_size(0)
+        sc = [_scanned(c[0], 0) for c in cases]
+        with ctx.batch([x.desc for x in sc], _fmt(planar)) as b:
+            b.set_resize([c[1] for c in cases])
+            b.set_resize_pad([c[4] for c in cases], FILL)
+            b.set_orientation([c[2] for c in cases])
+            b.set_resize_window([s[3] for s in STACKED])
+            _filter(b, filt)
+            b.set_normalize(dtype, scale, bias)
+            b.set_pad_value(value)
+            offs, pos = [], 6
+            for i in range(b.n):                                 # every canvas one element past a dword, the gaps are guard bands
+                while pos % 4 != 2:
+                    pos += 2
+                offs.append(pos)
+                pos += b.output_size(i) + 6
+            assert pos <= cap
+            b.bind_output(mem, cap, offs)
+            b.upload(); b.decode()
+            outs, st = b.download()
+            sizes = [b.output_size(i) for i in range(b.n)]
+        (after,), _ = donor.download()
+        after = after.reshape(-1)
+    assert st == [0] * len(cases)
+    _check(cases, outs, planar, filt, dtype, value)
+    covered = np.zeros(cap, bool)
+    for c, off, size in zip(cases, offs, sizes):
+        want = _want(c, planar, filt, dtype, value)
+        assert size == want.nbytes and after[off:off + size].tobytes() == want.tobytes(), (c[1], c[2])
+        covered[off:off + size] = True
+    stray = np.flatnonzero(~covered & (after != pattern))
+    assert stray.size == 0, f"bytes outside every canvas were written, first at {stray[:8]}"
+
+
 # ---- 3: the other paths into the launch -------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def fixture_pictures(port):

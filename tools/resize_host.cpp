@@ -5,8 +5,12 @@
 // staged segment of a mirrored tile, all four dword remainders of a segment's first byte in both layouts, the plane stride of a planar
 // source whose window is lower than the picture, guard bytes.
 //
-//     clang++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize=alignment -o resize_host tools/resize_host.cpp && ./resize_host
+//     clang++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize=alignment -D__host__= -D__device__= -o resize_host
+//         tools/resize_host.cpp pim-jpeg-decoder_amd/csrc/pjd_resize_plan.cpp && ./resize_host
 //
+// Every record the bodies read -- work list, windows, canvases, prefix sums, weight table, the LDS of the launch, the fill pattern -- is
+// made by the product's own resolver (pjd_resize_plan.cpp, compiled in) from a request, as the setters of pjd_api.hip make them: the
+// bodies run over the host logic itself.  The expectation takes nothing from those records: it is computed from the case alone.
 // Device builtins are replaced by host stand-ins: a lane's row taps are computed directly instead of being read from lane k, a
 // barrier is nothing, and a thread stages the whole row segment for itself (PJD_WIN_STAGE_*) into an "LDS" of exactly the size the
 // host would give the launch, allocated per thread so that AddressSanitizer sees its end.  The 16-bit conversions of the bodies are
@@ -43,6 +47,7 @@
 #define __restrict__
 #include "../include/pjd.h"
 #include "../pim-jpeg-decoder_amd/csrc/pjd_internal.h"
+#include "../pim-jpeg-decoder_amd/csrc/pjd_resize_plan.h"
 struct Dim { uint32_t x; };
 static thread_local Dim threadIdx, blockIdx;
 static inline uint32_t __umul24(uint32_t a, uint32_t b) { return (a & 0xffffff) * (b & 0xffffff); }
@@ -105,24 +110,6 @@ struct Case { uint32_t sw, sh, tw, th; PjdDevResizeWin w; uint32_t o = 1; uint32
 
 // the bits t << 2 | v << 1 | h of an orientation, written out from the table of include/pjd.h (not pjd_orient_tvh: that is under test)
 static uint32_t tvh_of(uint32_t o) { return o == 1 ? 0u : o == 2 ? 1u : o == 3 ? 3u : o == 4 ? 2u : o == 5 ? 4u : o == 6 ? 5u : o == 7 ? 7u : 6u; }
-
-// the tap-major table of one axis, as pjd_batch_set_resize_filter lays it out: dn heads `first | count << 16`, then taps x dn weights
-static uint32_t axis_table(std::vector<uint32_t> &tab, int filt, uint32_t sn, uint32_t dn, uint32_t &taps)
-{
-    const size_t base = tab.size();
-    tab.resize(base + (size_t)dn * (1u + PJD_BICUBIC_MAX_TAPS), 0u);
-    uint32_t w[PJD_BICUBIC_MAX_TAPS];
-    taps = 0;
-    for (uint32_t i = 0; i < dn; i++) {
-        uint32_t first;
-        const uint32_t cnt = filt == PJD_RESIZE_BICUBIC ? pjd_resize_bicubic_taps_calc(sn, dn, i, first, (int32_t *)w) : pjd_resize_aa_taps_calc(sn, dn, i, first, w);
-        tab[base + i] = first | (cnt << 16);
-        for (uint32_t t = 0; t < cnt; t++) tab[base + (size_t)(t + 1u) * dn + i] = w[t];
-        taps = std::max(taps, cnt);
-    }
-    tab.resize(base + (size_t)dn * (1u + taps));
-    return (uint32_t)base;
-}
 
 static std::vector<Case> plain_cases(unsigned seed, bool aa)
 {
@@ -200,49 +187,50 @@ static int run(int mode, uint32_t misalign_elems, unsigned seed)
     const uint32_t ES = DT == 0 ? 1 : PJD_DT_SIZE(DT);
     const std::vector<Case> cases = padded ? padded_cases(seed) : oriented ? oriented_cases(seed) : windowed ? window_cases(seed) : plain_cases(seed, AA);
     const size_t n = cases.size();
-    std::vector<PjdDevResize> recs(n); std::vector<PjdDevResizeWin> wins(n); std::vector<PjdDevResizeAA> aas(n); std::vector<uint32_t> prefix(n + 1), tab;
-    std::vector<PjdDevResizePad> pads(n); std::vector<uint32_t> lprefix(n + 1);
-    size_t spos = 0, dpos = misalign_elems * ES; uint32_t t = 0, lds = 0, n_lines = 0;
+    // the request, as a caller of the setters would state it: canvases, pads, orientations, windows, the filter; sources back to back,
+    // results at element-aligned offsets with odd gaps
+    PjdResizeSpec spec;
+    spec.planar = PLANAR;
+    spec.pad_set = padded; spec.ori_set = oriented; spec.win_set = windowed; spec.filter_set = true; spec.filter = FILT;
+    size_t spos = 0, dpos = misalign_elems * ES;
     std::vector<size_t> doff(n);
+    std::vector<uint32_t> cvw(n), cvh(n);                    // the delivered canvases, from the case: Q's target as it is delivered, plus the pad
     for (size_t i = 0; i < n; i++) {
-        const Case &c = cases[i]; PjdDevResize &r = recs[i];
-        if (c.sw > 65535 || c.w.x + c.w.w > c.sw || c.w.y + c.w.h > c.sh || c.w.ox + c.tw > c.w.vw || c.w.oy + c.th > c.w.vh || (AA && (c.w.w > 16 * c.w.vw || c.w.h > 16 * c.w.vh))) {
-            printf("case %zu is not a valid window\n", i); return 1;
-        }
-        wins[i] = c.w;
-        if (oriented) wins[i].flags ^= pjd_orient_flags(c.o);  // as pjd_batch_set_orientation and _set_resize_window compose them
-        r.src_off = spos; r.sw = c.sw; r.sh = c.sh; r.src_stride = PLANAR ? c.sw : 3 * c.sw; r.tw = c.tw; r.th = c.th;
-        r.col_tiles = (c.tw + PJD_RS_COLS - 1) / PJD_RS_COLS; r.dst_off = dpos;
+        const Case &c = cases[i];
+        const bool tr = oriented && (tvh_of(c.o) >> 2) != 0;
+        cvw[i] = (tr ? c.th : c.tw) + c.pad[0] + c.pad[2]; cvh[i] = (tr ? c.tw : c.th) + c.pad[1] + c.pad[3];
+        spec.pic.push_back(PjdResizePicture{spos, dpos, c.sw, c.sh, PLANAR ? c.sw : 3 * c.sw});
+        spec.out_w.push_back(cvw[i]); spec.out_h.push_back(cvh[i]);
+        if (padded) spec.pad.push_back(pjd_resize_pad{c.pad[0], c.pad[1], c.pad[2], c.pad[3]});
+        if (oriented) spec.orientation.push_back((uint8_t)c.o);
+        if (windowed) spec.win.push_back(pjd_resize_window{c.w.x, c.w.y, c.w.w, c.w.h, c.w.vw, c.w.vh, c.w.ox, c.w.oy, c.w.flags, 0u});
         doff[i] = dpos;
         spos += 3ull * c.sw * c.sh;                        // back to back: a picture's neighbours are other pictures
-        {   // the canvas of the delivered picture (the content itself without a pad), as pjd_batch_set_resize_pad lays the records out
-            const bool tr = oriented && (tvh_of(c.o) >> 2) != 0;
-            const uint32_t dw = tr ? c.th : c.tw, dh = tr ? c.tw : c.th;
-            pads[i] = PjdDevResizePad{dw + c.pad[0] + c.pad[2], dh + c.pad[1] + c.pad[3], c.pad[0], c.pad[1], dw, dh, {0u, 0u}};
-            lprefix[i] = n_lines;
-            if (c.pad[0] | c.pad[1] | c.pad[2] | c.pad[3]) n_lines += (PLANAR ? 3u : 1u) * pads[i].H;
-        }
-        dpos += 3ull * pads[i].W * pads[i].H * ES + ES * (2 * (i % 3) + 1);           // element-aligned odd gaps
-        prefix[i] = t; t += r.col_tiles * ((c.th + PJD_RS_ROWS - 1) / PJD_RS_ROWS);
-        if (AA) {
-            aas[i].x_tab = axis_table(tab, FILT, c.w.w, c.w.vw, aas[i].x_taps);
-            aas[i].y_tab = axis_table(tab, FILT, c.w.h, c.w.vh, aas[i].y_taps);
-            for (uint32_t c0 = 0; c0 < c.tw; c0 += PJD_RS_COLS) {                   // the sizing loop of pjd_batch_set_resize_filter
-                uint32_t e0, e1;
-                pjd_resize_win_ends(wins[i], c.tw, c0, std::min<uint32_t>(c0 + PJD_RS_COLS, c.tw) - 1u, e0, e1);
-                const uint32_t h0 = tab[aas[i].x_tab + e0], h1 = tab[aas[i].x_tab + e1];
-                lds = std::max(lds, pjd_resize_aa_lds((h1 & 0xffffu) + (h1 >> 16) - (h0 & 0xffffu), PLANAR));
-            }
-        }
+        dpos += 3ull * cvw[i] * cvh[i] * ES + ES * (2 * (i % 3) + 1);                 // element-aligned odd gaps
     }
-    prefix[n] = t; lprefix[n] = n_lines;
+    PjdResizeWork work;
+    const PjdResizeFault fault = pjd_resize_resolve(spec, work);
+    if (!fault.text.empty()) { printf("the resolver refuses the cases: %s\n", fault.text.c_str()); return 1; }
+    if (work.form.windowed != windowed || work.form.oriented != oriented || work.form.padded != padded) { printf("the resolver chose another form than the cases ask for\n"); return 1; }
+    const std::vector<PjdDevResize> &recs = work.recs;
+    const std::vector<uint32_t> &prefix = work.tile_prefix, &tab = work.tab;
+    const std::vector<PjdDevResizeAA> &aas = work.aa;
+    const uint32_t t = work.form.tiles, lds = work.form.lds, n_lines = work.form.lines;
+    // the plain set runs through the WIN, ORI and PAD bodies too: with the identity window and a canvas that is the content
+    std::vector<PjdDevResizeWin> wins = work.win;
+    std::vector<PjdDevResizePad> pads = work.pad;
+    std::vector<uint32_t> lprefix = work.line_prefix;
+    if (!windowed) {
+        lprefix.assign(n + 1, 0u);
+        for (size_t i = 0; i < n; i++) { wins.push_back(pjd_resize_win_identity(recs[i])); pads.push_back(PjdDevResizePad{cvw[i], cvh[i], 0, 0, cvw[i], cvh[i], {0u, 0u}}); }
+    }
     const size_t src_bytes = (spos + 3) & ~(size_t)3;        // whole dwords are staged: the buffer ends on one, as every allocation does
     uint8_t *src = (uint8_t *)malloc(src_bytes);              // the sanitizer's view of the source is exactly src_bytes
     for (size_t k = 0; k < src_bytes; k++) src[k] = (uint8_t)rand();
     if (((uintptr_t)src & 3u) != 0) { printf("malloc gave an unaligned block\n"); return 1; }
     const size_t dst_bytes = dpos + 256;
     const NormArgs nz = {{0.01712475f, 0.017507f, -0.01742919f}, {-2.117904f, -2.0357144f, 1.8044444f}};
-    // the fill of the padded set as pjd_batch::launch_pad makes it: three elements (the fill byte, or its normalised value) over twelve bytes
+    // the fill of the padded set: the expectation's three elements (the fill byte, or its normalised value), and the pattern of the launch
     const uint8_t fill_u8[3] = {114, 7, 201};
     uint32_t fill_e[3];
     for (int ch = 0; ch < 3; ch++) {
@@ -250,9 +238,8 @@ static int run(int mode, uint32_t misalign_elems, unsigned seed)
         uint32_t b32; memcpy(&b32, &u, 4);
         fill_e[ch] = DT == 0 ? fill_u8[ch] : DT == PJD_DT_F32 ? b32 : DT == PJD_DT_F16 ? f16bits(u) : bf16bits(u);
     }
-    PjdPadFill pf{};
-    if (PLANAR) for (int ch = 0; ch < 3; ch++) pf.d[ch] = ES == 1 ? fill_e[ch] * 0x01010101u : ES == 2 ? fill_e[ch] * 0x00010001u : fill_e[ch];
-    else { uint8_t b12[12]; for (uint32_t k = 0; k < 12; k++) b12[k] = (uint8_t)(fill_e[(k / ES) % 3] >> (8 * (k % ES))); memcpy(pf.d, b12, 12); }
+    PjdNormalize norm{DT, {nz.scale[0], nz.scale[1], nz.scale[2]}, {nz.bias[0], nz.bias[1], nz.bias[2]}};
+    const PjdPadFill pf = pjd_pad_fill(norm, PLANAR, fill_u8, nullptr);
     // every thread of the launch, with the WIN = true or the WIN = false body
     auto launch = [&](auto WIN, auto ORI, auto PADDED) {
         constexpr bool W = decltype(WIN)::value, O = decltype(ORI)::value, PD = decltype(PADDED)::value;
@@ -292,10 +279,10 @@ static int run(int mode, uint32_t misalign_elems, unsigned seed)
     std::vector<uint8_t> want(dst_bytes, 0xA5);
     for (size_t i = 0; i < n; i++) {
         const Case &c = cases[i]; const PjdDevResizeWin &w = c.w; const uint8_t *sp = src + recs[i].src_off;
-        const PjdDevResizePad &cv = pads[i];
+        const size_t cW = cvw[i], cH = cvh[i], cleft = c.pad[0], ctop = c.pad[1];   // the canvas and the content's origin in it: the case's, not the records'
         if (padded)                                          // the whole canvas is fill; the content is written over its rectangle below
-            for (size_t e = 0; e < 3ull * cv.W * cv.H; e++) {
-                const uint32_t v = fill_e[PLANAR ? e / ((size_t)cv.W * cv.H) : e % 3];
+            for (size_t e = 0; e < 3ull * cW * cH; e++) {
+                const uint32_t v = fill_e[PLANAR ? e / (cW * cH) : e % 3];
                 memcpy(want.data() + doff[i] + e * ES, &v, ES);   // little-endian: the element's low bytes
             }
         auto P = [&](int ch, uint32_t yy, uint32_t xx) -> uint32_t {
@@ -338,10 +325,8 @@ static int run(int mode, uint32_t misalign_elems, unsigned seed)
             }
             // where Q[y][x] is delivered: D = H^h(V^v(T^t(Q))) of include/pjd.h, D being dw x dh
             const uint32_t b3 = tvh_of(c.o), ot = b3 >> 2, ov = (b3 >> 1) & 1u, oh = b3 & 1u;
-            const uint32_t dw = ot ? c.th : c.tw, dh = ot ? c.tw : c.th;
             const uint32_t di = ot ? (ov ? c.tw - 1 - x : x) : (ov ? c.th - 1 - y : y), dj = ot ? (oh ? c.th - 1 - y : y) : (oh ? c.tw - 1 - x : x);
-            if (dw != cv.cw || dh != cv.ch) { printf("the canvas record is not the delivered picture's\n"); exit(2); }
-            const size_t e = PLANAR ? ((size_t)ch * cv.H + cv.top + di) * cv.W + cv.left + dj : ((size_t)(cv.top + di) * cv.W + cv.left + dj) * 3 + ch;
+            const size_t e = PLANAR ? ((size_t)ch * cH + ctop + di) * cW + cleft + dj : ((ctop + di) * cW + cleft + dj) * 3 + ch;
             uint8_t *o = want.data() + doff[i] + e * ES;
             if (DT == 0) *o = (uint8_t)v;
             else {
