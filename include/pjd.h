@@ -191,6 +191,7 @@ extern "C" {
  *          B = clamp(Y + ((116130*cb + 32768) >> 16))
  *      A one-component picture gives R = G = B = Y.
  * tests/test_libjpeg_cpu.py and tests/test_gpu_libjpeg.py hold this against Pillow's decode of files Pillow wrote: zero tolerance.
+ * tests/test_libjpeg_corpus_cpu.py and tests/test_gpu_libjpeg_corpus.py do so on a seeded family up to libjpeg's 65500-sample limit.
  *
  * ENVELOPE.  Baseline and progressive frames (with PJD_F_PROGRESSIVE Pillow's progressive files equal Pillow's decode); sampling
  * 4:4:4, 4:2:2 (h2v1), 4:2:0, or one component; the parallel path, PJD_F_FORCE_SEQUENTIAL and the exact-kernel fallback of
@@ -775,6 +776,11 @@ int  pjd_exec_dpu_payload(pjd_ctx *ctx, const uint32_t *metadata, int16_t *mcus,
  * opened now would: PJD_PLAN_MODE and PJD_SUB_BYTES (a subsequence size forced for the
  * whole batch, a multiple of 64 in 128..1024) of the environment apply, as in pjd_open. */
 int  pjd_plan_info(const pjd_image_desc *images, int n_images, int out_format, pjd_batch_info *info);
+/* Host-only: would pjd_batch_create take these images?  Runs the planner's tests and returns its code; `text` (cap bytes, always
+ * terminated; may be NULL) receives "" or the reason pjd_last_error would report after pjd_batch_create ("image <i>: ..." where one
+ * picture is at fault).  What a caller that ORs one set of flags into many descriptors uses to sort out, picture by picture, the ones
+ * a flag does not take (PJD_F_LIBJPEG on 4:4:0 sampling, for one) before it builds its batch.                                       */
+int  pjd_plan_check(const pjd_image_desc *images, int n_images, int out_format, char *text, uint64_t cap);
 /* Debug, host-only: the bound behind the size of a picture's lane streams -- the fewest bits of bitstream per step of the entropy
  * decoder's write pass (one symbol, or the pair one table lookup yields) that ANY stream coded with this picture's Huffman tables can
  * sustain, x 256 (the minimum mean weight of a cycle of the step graph, pim-jpeg-decoder_amd/csrc/pjd_plan.cpp).  PJD_E_ARG for a

@@ -38,7 +38,8 @@ extern "C" {
  *   index   position of the input in the caller's list
  *   name    the path / name given for it
  *   log     what the reference would have printed while parsing this file ("" if nothing)
- *   status  -1: rejected by the scanner (no picture), -2: the GPU batch failed (no picture),
+ *   status  -1: rejected by the scanner (no picture), -2: the GPU batch failed, or opts.image_flags asks for what this
+ *           picture does not take (see image_flags; no picture),
  *           else PJD_ST_* of the entropy decode (0 = clean; > 0: partial picture, message =
  *           pjd_status_string(status))
  *   data/len  the picture in the requested output format; valid only during the call          */
@@ -60,9 +61,13 @@ typedef struct pjd_pipe_opts {
     int32_t n_devices;       /* entries in `devices` (at most PJD_PIPE_MAX_DEVICES)            */
     uint32_t scan_options;   /* PJD_SCAN_* of pjd_host.h handed to the scanner (0 = the reference's accept / reject set) */
     uint32_t image_flags;    /* PJD_F_* ORed into every descriptor the scanner produces: PJD_F_SCALE_* (reduced-size pictures
-                                for the sink), PJD_F_STANDARD_*, PJD_F_LIBJPEG (libjpeg's pictures; a batch then fails as a
-                                whole if it holds a file outside that mode's envelope, such as 4:4:0 sampling); 0 = as
-                                scanned.  Added in PJD_VERSION 6.                                                      */
+                                for the sink), PJD_F_STANDARD_*, PJD_F_LIBJPEG (libjpeg's pictures); 0 = as scanned.
+                                With PJD_F_LIBJPEG every scanned picture is tested on its own before its batch is built
+                                (pjd_plan_check, host only): one outside that mode's envelope, such as 4:4:0 sampling or
+                                two components, is left out of the batch and handed to the sink with status -2 and no
+                                data, its log ending in one more line "<name>: Error - <the planner's reason>"; it counts
+                                in n_rejected, not as a batch failure, and the other pictures of its batch decode as
+                                libjpeg's.  Added in PJD_VERSION 6.                                                    */
 } pjd_pipe_opts;
 
 typedef struct pjd_pipe_stats {

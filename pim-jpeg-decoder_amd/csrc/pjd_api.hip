@@ -1439,6 +1439,15 @@ int pjd_plan_info(const pjd_image_desc *images, int n_images, int out_format, pj
     return PJD_OK;
 }
 
+int pjd_plan_check(const pjd_image_desc *images, int n_images, int out_format, char *text, uint64_t cap)
+{
+    PjdPlan P;
+    std::string err;
+    const int rc = pjd_make_plan(images, n_images, out_format, P, err);
+    if (text && cap) std::snprintf(text, (size_t)cap, "%s", rc == PJD_OK ? "" : err.c_str());
+    return rc;
+}
+
 int pjd_plan_step_bits(const pjd_image_desc *image, uint32_t *step_bits_x256)
 {
     if (!image || !step_bits_x256) return PJD_E_ARG;

@@ -24,6 +24,8 @@
 // its box of source pixels (PJD_F_SCALE_* of include/pjd.h); in every mode.  Any other value is a usage error.
 // --libjpeg: the pictures are the ones libjpeg decodes, bit for bit (PJD_F_LIBJPEG of include/pjd.h: islow IDCT, fancy upsampling, JFIF
 // colour) instead of the reference's; with --pipeline and --progressive, not with a --scale other than 1/1 and not with --split.
+// A file outside that mode's envelope (4:4:0 sampling, two components) gets "<file>: Error - <the planner's reason>" and no BMP; the
+// other files decode.
 #include <sys/stat.h>
 #include <time.h>
 
@@ -62,7 +64,8 @@ static void pipe_sink(void *user, int index, const char *name, const char *log, 
     PipeOut *po = (PipeOut *)user;
     std::string &m = po->messages[(size_t)index];    // one call per index: no lock needed
     m = log;
-    if (status == -2) m += std::string(name) + ": Error - GPU batch failed\n";
+    // a picture --libjpeg does not take comes with status -2 as well, the reason already the last line of its log
+    if (status == -2 && m.find(std::string(name) + ": Error - ") == std::string::npos) m += std::string(name) + ": Error - GPU batch failed\n";
     if (status > 0) m += std::string(name) + ": " + pjd_status_string(status) + "\n";
     if (data) {
         const std::string out = bmp_name(name);
@@ -266,6 +269,18 @@ int main(int argc, char **argv)
             }
             std::cout << pjd_scanned_log(s);
             if (sr != 0) { pjd_scanned_free(s); continue; }
+            if (libjpeg) {
+                // the mode has an envelope (pjd.h): a picture outside it would make pjd_batch_create refuse the whole batch, so it
+                // is tested on its own (host only, the planner's very test), reported and left out
+                pjd_image_desc dd = *pjd_scanned_desc(s);
+                dd.flags |= image_flags;
+                char why[256];
+                if (pjd_plan_check(&dd, 1, PJD_OUT_BMP, why, sizeof why) == PJD_E_ARG) {
+                    std::cout << f << ": Error - " << (std::strncmp(why, "image 0: ", 9) == 0 ? why + 9 : why) << "\n";
+                    pjd_scanned_free(s);
+                    continue;
+                }
+            }
             scanned.push_back(s);
             names.push_back(f);
         }

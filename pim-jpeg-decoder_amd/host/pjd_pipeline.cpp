@@ -50,6 +50,7 @@ struct Input {
     const char *name = "";
     pjd_scanned *sc = nullptr;
     int scan_rc = 2;
+    std::string refusal;                 // "<name>: Error - <reason>\n" where opts.image_flags put the picture outside what the planner takes
 };
 
 struct Job {                             // one batch: inputs [first, first + count)
@@ -215,9 +216,20 @@ struct Pipe {
             for (int i = job.first; i < job.first + job.count; i++) {
                 Input &x = in[i];
                 if (x.scan_rc == 0 && x.sc) {
+                    pjd_image_desc dd = *pjd_scanned_desc(x.sc);
+                    dd.flags |= o.image_flags;                 // e.g. PJD_F_SCALE_*: the sink receives the pictures at that scale
+                    // PJD_F_LIBJPEG has an envelope (pjd.h): a picture outside it would make pjd_batch_create refuse the whole batch,
+                    // so it is tested on its own (host only, the planner's very test) and left out
+                    char why[256];
+                    if ((o.image_flags & PJD_F_LIBJPEG) && pjd_plan_check(&dd, 1, o.out_format, why, sizeof why) == PJD_E_ARG) {
+                        const char *r = std::strncmp(why, "image 0: ", 9) == 0 ? why + 9 : why;
+                        x.refusal = std::string(x.name) + ": Error - " + r + "\n";
+                        rejected++;
+                        emit(i, -2, nullptr, 0, &latch);
+                        continue;
+                    }
                     idx.push_back(i);
-                    descs.push_back(*pjd_scanned_desc(x.sc));
-                    descs.back().flags |= o.image_flags;       // e.g. PJD_F_SCALE_*: the sink receives the pictures at that scale
+                    descs.push_back(dd);
                 }
                 else { rejected++; emit(i, -1, nullptr, 0, &latch); }
             }
@@ -297,6 +309,10 @@ struct Pipe {
             std::string opened;
             if (x.scan_rc == 2) {                          // the reference's message for an unreadable file (jpeg_scanner.cpp:351)
                 opened = std::string(x.name) + ": Error - Error opening input file\n" + x.name + ": Error - Invalid JPEG\n";
+                log = opened.c_str();
+            }
+            if (!x.refusal.empty()) {
+                opened = std::string(log) + x.refusal;
                 log = opened.c_str();
             }
             o.sink(o.sink_user, t.index, x.name, log, t.status, t.data, t.len);

@@ -252,6 +252,8 @@ def dev_lib():
         L.pjd_split_release.restype = None
         L.pjd_plan_info.restype = i32
         L.pjd_plan_info.argtypes = [C.POINTER(ImageDesc), i32, i32, C.POINTER(BatchInfo)]
+        L.pjd_plan_check.restype = i32
+        L.pjd_plan_check.argtypes = [C.POINTER(ImageDesc), i32, i32, C.c_char_p, C.c_uint64]
         _dev = L
     return _dev
 
@@ -654,7 +656,9 @@ def pipe_run(jpegs=None, names=None, paths=None, out_format=OUT_BMP, batch_image
              sink_threads=0, sink=None, device=0, devices=None, scan_options=0, image_flags=0):
     """Run the pipelined batcher over in-memory JPEGs (`jpegs`: list of bytes) or files (`paths`).
     `devices`: HIP ordinals to spread the batches over (default: `device` alone).
-    `image_flags`: PJD_F_* ORed into every descriptor (F_SCALE_*: the sink receives reduced-size pictures).
+    `image_flags`: PJD_F_* ORed into every descriptor (F_SCALE_*: the sink receives reduced-size pictures; F_LIBJPEG: libjpeg's
+    pictures -- a picture outside that mode's envelope reaches the sink with status -2, no data and the planner's reason as the last
+    line of its log, and the rest of its batch decodes).
 
     `sink(index, name, log, status, data)` is called from worker threads with `data` a numpy copy of the
     picture (or None).  Returns the statistics as a dict."""
@@ -748,6 +752,18 @@ def plan_info(descs, out_format=OUT_RGB8):
     if rc != 0:
         raise PjdError(f"pjd_plan_info failed ({rc})")
     return {k: (list(getattr(bi, k)) if k == "flag_waves" else (float(getattr(bi, k)) if k == "exact_fallback_ms" else int(getattr(bi, k)))) for k, _ in bi._fields_}
+
+
+def plan_check(descs, out_format=OUT_RGB8):
+    """Host-only (pjd_plan_check): would a batch take these images?  -> (code, reason): (0, "") or the planner's refusal, which names
+    the picture -- what the batcher and the CLI ask, picture by picture, before they OR image_flags into a whole batch."""
+    L = dev_lib()
+    arr = (ImageDesc * max(len(descs), 1))()
+    for i, d in enumerate(descs):
+        C.memmove(C.byref(arr[i]), C.byref(d), C.sizeof(ImageDesc))
+    text = C.create_string_buffer(256)
+    rc = L.pjd_plan_check(arr, len(descs), out_format, text, len(text))
+    return int(rc), text.value.decode()
 
 
 def resize_tap(src_n, dst_n, i):
