@@ -340,7 +340,9 @@ void *pjd_stream(pjd_ctx *ctx);             /* the hipStream_t all work is issue
 /* ---- batch life cycle ------------------------------------------------------- *
  * create : plan + allocate (host pinned staging and HBM); copies the descriptors,
  *          the caller's ecs buffers may be released after pjd_batch_upload returns.
- * upload : H2D of bitstreams, tables and work lists (asynchronous on the stream).
+ * upload : H2D of bitstreams, tables and work lists, then -- once per upload, not per
+ *          decode -- the kernels that build the decode tables and the entropy
+ *          decoder's word rows from them (all asynchronous on the stream).
  * decode : enqueue the kernels; inputs and outputs stay resident in HBM.
  * download: D2H of pictures and statuses into caller memory, synchronises.
  * A batch can be decoded any number of times after one upload.                 */

@@ -575,6 +575,13 @@ int pjd_batch_upload(pjd_batch *b)
     if (b->aa.d) HIP_TRY(ctx, hipMemcpyAsync(b->aa.d, b->aa.h, b->aa.bytes, hipMemcpyHostToDevice, s));             // ... and its weight table
     if (b->form.windowed) HIP_TRY(ctx, hipMemcpyAsync(b->win.d, b->win.h, b->win.bytes, hipMemcpyHostToDevice, s));  // ... and its source windows
     if (b->form.padded) HIP_TRY(ctx, hipMemcpyAsync(b->pad.d, b->pad.h, b->pad.bytes, hipMemcpyHostToDevice, s));    // ... and its canvases
+    // What depends on the blob alone is made here, once per upload, behind its copy: the decode tables of every table set (the exact
+    // path uses them too) and the lanes' word rows.  No kernel of a decode writes either, so every decode of
+    // the resident batch -- launched or replayed from its graphs -- reads what this upload left.
+    const bool parallel = !P.hwgs.empty();
+    if (parallel || !b->seq_list.empty()) pjd_launch_build_tables(s, b->dev);
+    if (parallel) pjd_launch_lane_words(s, b->dev);
+    HIP_TRY(ctx, hipGetLastError());
     b->uploaded = true;
     return PJD_OK;
 }
@@ -671,8 +678,6 @@ int enqueue_decode(pjd_batch *b, pjd_timings *timings, bool use_groups)
         // beside it (inside a capture: two parallel one-node branches), then the sweep over whatever the pull launch left.
         PjdDevBatch dv = b->dev;
         dv.pull = 1;
-        pjd_launch_build_tables(s, dv);
-        pjd_launch_lane_words(s, dv);
         HIP_TRY(ctx, hipEventRecord(ctx->fork_ev, s));
         pjd_launch_huff_lanes(s, dv);
         hipStream_t s1 = ctx->group_streams[0];
@@ -682,18 +687,15 @@ int enqueue_decode(pjd_batch *b, pjd_timings *timings, bool use_groups)
         HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->join_ev[0], 0));
         pjd_launch_idct_sweep(s, dv);
     } else if (grouped) {
-        // Picture groups (pjd_internal.h): every group's chain bitstream words -> entropy decode -> DC predictors -> back end on a stream
-        // of its own, forked from and joined to the context's stream with events (inside a stream capture these become parallel
-        // branches of the graph).  Group 0 holds the densest pictures -- the longest chains of re-sync rounds -- and stays on the main
-        // stream.  The chains have the same shape on purpose: with the decode tables built on the second stream beside group 0's
-        // bitstream words (a branch one node longer than the other) the graph ran the two entropy decodes one after the other
-        // (4.65 ms instead of 2.60 for a batch alone; profiles/r04_experiments.md).
-        pjd_launch_build_tables(s, b->dev);
+        // Picture groups (pjd_internal.h): every group's chain entropy decode -> DC predictors -> back end on a stream of its own,
+        // forked from and joined to the context's stream with events (inside a stream capture these become parallel branches of the
+        // graph).  Group 0 holds the densest pictures -- the longest chains of re-sync rounds -- and stays on the main stream.  The
+        // chains have the same shape on purpose: with one branch a node longer than the other the graph ran the two entropy decodes
+        // one after the other (4.65 ms instead of 2.60 for a batch alone; profiles/r04_experiments.md).
         HIP_TRY(ctx, hipEventRecord(ctx->fork_ev, s));
         for (size_t g = 0; g < ng; g++) {
             hipStream_t gs = g == 0 ? s : ctx->group_streams[g - 1];
             if (g) HIP_TRY(ctx, hipStreamWaitEvent(gs, ctx->fork_ev, 0));
-            pjd_launch_lane_words_group(gs, b->dev, P.groups[g]);
             pjd_launch_huff_lanes_group(gs, b->dev, P.groups[g], (uint32_t)g);
             pjd_launch_group_dc(gs, b->dev, P.groups[g]);
             pjd_launch_group_idct(gs, b->dev, P.groups[g], P.scaled, P.planar);
@@ -701,11 +703,9 @@ int enqueue_decode(pjd_batch *b, pjd_timings *timings, bool use_groups)
         }
         for (size_t g = 1; g < ng; g++) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->join_ev[g - 1], 0));
     } else {
-        if (parallel || !b->seq_list.empty()) { pjd_launch_build_tables(s, b->dev);  kt.mark("build_tables"); }      // the exact path uses the decode tables too
         if (parallel) {
-            pjd_launch_lane_words(s, b->dev);    kt.mark("lane_words");
             pjd_launch_huff_lanes(s, b->dev);    kt.mark("huff_lanes");
-            pjd_launch_lane_dc_scan(s, b->dev);  kt.mark("dc_scan");
+            pjd_launch_lane_dc_scan(s, b->dev, P.dc_per_picture);  kt.mark("dc_scan");
             if (!P.libjpeg) pjd_launch_idct_colour_lanes(s, b->dev, P.scaled, P.planar);
             else {
                 // the ranges of the unflagged pictures through the default kernels, those of the flagged ones into their planes

@@ -60,6 +60,7 @@
                                     // A chain of non-merging lanes that crosses k wave boundaries needs k + 2 generations; never a chain over the whole image.
 #define PJD_SYNC_MAX_ITERS 72       // re-sync rounds per wave before giving up (a non-merging chain moves one lane per round)
 #define PJD_DC_BLOCK       256      // lanes per DC-prediction scan block
+#define PJD_DC_PICTURE_MAX_LANES (8 * PJD_DC_BLOCK)   // single chain: pictures up to this many lanes are settled by one workgroup each (pjd_plan.cpp)
 #ifndef PJD_IDCT_THREADS
 #define PJD_IDCT_THREADS   256
 #endif

@@ -942,11 +942,13 @@ void pjd_launch_group_idct(hipStream_t s, const PjdDevBatch &b, const PjdDevGrou
 // One picture group: verdict and DC predictors per PICTURE, one workgroup each (pictures of a group are small: the planner makes
 // groups only if no picture has more than 8192 lanes).  The same results as pjd_k_image_verdict + pjd_k_lane_dc_local / _carry leave,
 // with every lane's predictors absolute (PjdDevLaneDc::abs = 1: no block carry to add).
+// images == null: workgroup k takes picture k -- the whole batch in the single chain (PjdPlan::dc_per_picture); a picture routed to
+// the exact kernel up front has no lanes and keeps its status word.
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(PJD_DC_BLOCK) void pjd_k_group_dc(PjdDevBatch B, const uint32_t *__restrict__ images)
 {
     __shared__ uint32_t sy[PJD_DC_BLOCK], scb[PJD_DC_BLOCK], scr[PJD_DC_BLOCK], sf[PJD_DC_BLOCK];
-    const uint32_t i = images[blockIdx.x], tid = threadIdx.x;
+    const uint32_t i = images ? images[blockIdx.x] : blockIdx.x, tid = threadIdx.x;
     const PjdDevImage &im = B.images[i];
     if (tid == 0) {                                            // pjd_k_image_verdict
         const int32_t st = B.status[i];
@@ -1009,9 +1011,10 @@ void pjd_launch_group_dc(hipStream_t s, const PjdDevBatch &b, const PjdDevGroup 
     if (g.img_count) hipLaunchKernelGGL(pjd_k_group_dc, dim3(g.img_count), dim3(PJD_DC_BLOCK), 0, s, b, b.group_images + g.img_first);
 }
 
-void pjd_launch_lane_dc_scan(hipStream_t s, const PjdDevBatch &b)
+void pjd_launch_lane_dc_scan(hipStream_t s, const PjdDevBatch &b, bool per_picture)
 {
     if (b.n_dcblk == 0) return;
+    if (per_picture) { hipLaunchKernelGGL(pjd_k_group_dc, dim3(b.n_images), dim3(PJD_DC_BLOCK), 0, s, b, (const uint32_t *)nullptr); return; }
     hipLaunchKernelGGL(pjd_k_image_verdict, dim3((b.n_images + 255) / 256), dim3(256), 0, s, b);
     hipLaunchKernelGGL(pjd_k_lane_dc_local, dim3(b.n_dcblk), dim3(PJD_DC_BLOCK), 0, s, b);
     hipLaunchKernelGGL(pjd_k_lane_dc_carry, dim3(1), dim3(256), 0, s, b);

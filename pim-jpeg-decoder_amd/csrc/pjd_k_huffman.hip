@@ -9,6 +9,7 @@
 // 512 B -- bit position, zigzag slot AND the 6-unit MCU phase must all agree -- which shapes
 // everything below.
 //
+// Once per upload (pjd_batch_upload: both depend on the batch's blob alone, and no kernel of a decode writes what they make):
 //   pjd_k_build_tables   raw (offsets, symbols) tables -> two-level decode table per TABLE SET (images with the
 //                        same Huffman tables share one): 9-bit first level (32-bit entries: the symbol, and the PAIR of
 //                        symbols where both fit), one 128-entry second-level table
@@ -19,6 +20,7 @@
 //                        byte, transposed per wave ([word][lane]): a lane's refill is one dword of a row its
 //                        neighbours read too, so the 64 per-lane streams of a wave cost a few cache lines per
 //                        load instead of 64
+// Per decode:
 //   pjd_k_huff_lanes     one wave = 64 subsequences of one image; a workgroup = up to PJD_HUFF_WAVES (2) consecutive waves
 //                        that share one table set in LDS (nothing else: waves never meet at a barrier after the tables
 //                        are loaded).
@@ -148,17 +150,10 @@ struct __attribute__((packed)) UnalignedU32 { uint32_t v; };
 
 struct __attribute__((packed)) UnalignedU32x4 { uint32_t v[4]; };
 
-// hwg_count == 0: one block per wave of the batch; else the waves of the Huffman workgroups hwg_first .. (a picture group,
-// pjd_internal.h): two blocks per workgroup.
-__global__ __launch_bounds__(256) void pjd_k_lane_words(PjdDevBatch B, uint32_t hwg_first, uint32_t hwg_count)
+// Launched once per upload over all waves of the batch.
+__global__ __launch_bounds__(256) void pjd_k_lane_words(PjdDevBatch B)
 {
-    uint32_t wv = blockIdx.x;
-    if (hwg_count) {
-        const PjdDevHuffWg wg = B.hwgs[hwg_first + blockIdx.x / PJD_HUFF_WAVES];
-        const uint32_t k = blockIdx.x % PJD_HUFF_WAVES;
-        if (k >= wg.n_waves) return;
-        wv = wg.first_wave + k;
-    }
+    const uint32_t wv = blockIdx.x;
     const PjdDevHuffWave hw = B.hwaves[wv];
     const PjdDevImage &im = B.images[hw.image];
     const uint32_t l = threadIdx.x & 63, k0 = threadIdx.x >> 6;
@@ -1626,14 +1621,7 @@ void pjd_launch_lane_words(hipStream_t s, const PjdDevBatch &b)
 #if PJD_DIRECT_ECS
     return;
 #endif
-    if (b.n_hwave) hipLaunchKernelGGL(pjd_k_lane_words, dim3(b.n_hwave), dim3(256), 0, s, b, 0u, 0u);
-}
-void pjd_launch_lane_words_group(hipStream_t s, const PjdDevBatch &b, const PjdDevGroup &g)
-{
-#if PJD_DIRECT_ECS
-    return;
-#endif
-    if (g.hwg_count) hipLaunchKernelGGL(pjd_k_lane_words, dim3(g.hwg_count * PJD_HUFF_WAVES), dim3(256), 0, s, b, g.hwg_first, g.hwg_count);
+    if (b.n_hwave) hipLaunchKernelGGL(pjd_k_lane_words, dim3(b.n_hwave), dim3(256), 0, s, b);
 }
 void pjd_launch_huff_lanes(hipStream_t s, const PjdDevBatch &b)
 {

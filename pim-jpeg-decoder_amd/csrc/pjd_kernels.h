@@ -59,7 +59,9 @@ void pjd_launch_copy_out(hipStream_t s, const void *src, void *dst_mapped, uint6
 // planar: the batch's output format is PJD_OUT_RGB8_PLANAR (PJD_IF_PLANAR on every picture): the planar back-end kernels
 void pjd_launch_idct_colour(hipStream_t s, const PjdDevBatch &b, const PjdDevIdctWg *wgs, const uint64_t *dense_base, uint32_t n_wg, bool scaled, bool planar);
 void pjd_launch_idct_colour_lanes(hipStream_t s, const PjdDevBatch &b, bool scaled, bool planar);                                  // lane-stream input
-void pjd_launch_lane_dc_scan(hipStream_t s, const PjdDevBatch &b);      // three kernels: per-image verdict (status words), local scan, carry
+// verdict (status words) and DC predictors of the whole batch: one launch, a workgroup per picture (pjd_k_group_dc), or -- a batch with
+// a picture of very many lanes, PjdPlan::dc_per_picture -- three: per-image verdict, local scan, carry
+void pjd_launch_lane_dc_scan(hipStream_t s, const PjdDevBatch &b, bool per_picture);
 // one picture group (pjd_internal.h): verdict + DC predictors of its pictures in one launch, then its back-end workgroups
 void pjd_launch_group_dc(hipStream_t s, const PjdDevBatch &b, const PjdDevGroup &g);
 void pjd_launch_group_idct(hipStream_t s, const PjdDevBatch &b, const PjdDevGroup &g, bool scaled, bool planar);
@@ -118,8 +120,8 @@ void pjd_launch_huff_sequential(hipStream_t s, const PjdDevBatch &b, const uint3
 void pjd_launch_huff_exact_lut(hipStream_t s, const PjdDevBatch &b, const uint32_t *image_list, const uint64_t *dense_base, uint32_t n);   // the exact decoder, table-driven
 // progressive frames among image_list (the others are skipped): scan by scan into the dense scratch (pjd_k_progressive.hip)
 void pjd_launch_progressive(hipStream_t s, const PjdDevBatch &b, const uint32_t *image_list, const uint64_t *dense_base, uint32_t n);
+// once per upload (pjd_batch_upload), not per decode: no kernel of a decode writes luts or words
 void pjd_launch_build_tables(hipStream_t s, const PjdDevBatch &b);
 void pjd_launch_lane_words(hipStream_t s, const PjdDevBatch &b);     // bitstream -> per-lane big-endian words, transposed per wave
-void pjd_launch_lane_words_group(hipStream_t s, const PjdDevBatch &b, const PjdDevGroup &g);   // the same for the waves of one picture group
 void pjd_launch_huff_lanes(hipStream_t s, const PjdDevBatch &b);     // synchronise + stitch + scan + write
 void pjd_launch_huff_lanes_group(hipStream_t s, const PjdDevBatch &b, const PjdDevGroup &g, uint32_t group_index);   // the same for one picture group

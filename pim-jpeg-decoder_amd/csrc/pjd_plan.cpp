@@ -724,6 +724,21 @@ int pjd_make_plan(const pjd_image_desc *images, int n, int out_format, PjdPlan &
     P.dense_du = dense_seq;
     P.out_buf_bytes = align_up(out_off, 256);
     P.n_dcblk = (P.subs.size() + PJD_DC_BLOCK - 1) / PJD_DC_BLOCK;
+    // How the single chain settles a decode (verdict, DC predictors at the lane starts): one launch with a workgroup per picture
+    // (pjd_k_group_dc), or the batch-wide scan of three launches.  The per-picture workgroup walks its picture's lanes PJD_DC_BLOCK at
+    // a time, one after the other -- each chunk eight scan steps of two barriers, a microsecond or two -- while the scan spreads the
+    // lanes over n_dcblk workgroups at the price of two more dependent launches, some 0.02 ms in a chain.  So the one launch is the
+    // shorter up to about ten chunks per picture, and a batch of one large picture (tens of thousands of lanes) keeps the scan.
+    // PJD_DC_FORM=scan / picture for experiments (profiles/resident_tables.md).
+    {
+        uint32_t max_lanes = 0;
+        for (uint32_t i : P.fast_images) max_lanes = std::max(max_lanes, P.images[i].n_lane);
+        P.dc_per_picture = max_lanes <= PJD_DC_PICTURE_MAX_LANES;
+        if (const char *e = std::getenv("PJD_DC_FORM")) {
+            if (!std::strcmp(e, "picture")) P.dc_per_picture = true;
+            else if (!std::strcmp(e, "scan")) P.dc_per_picture = false;
+        }
+    }
     P.lut_buf_bytes = align_up(lut_off + 16, 256);
     if (P.ecs_buf_bytes >= (1ull << 40)) { err = "batch bitstream too large"; return PJD_E_ARG; }
     // every byte a lane can make the kernels read lies inside the bitstream buffer: pjd_k_lane_words copies PJD_WORD_ROWS words

@@ -61,6 +61,7 @@ struct PjdPlan {
     std::vector<PjdDevIdctWg> iwgs_dense_std;   // flagged pictures routed to the exact kernel up front: their ranges (not in iwgs_dense)
     std::vector<PjdDevIdctWg> cwgs_std;         // work list of the colour launch: {image, first item, 0, 0}, PJD_IDCT_THREADS items each
     uint64_t plane_bytes = 0;                   // the plane buffer: Y, Cb, Cr of every flagged picture, padded to whole MCUs
+    bool dc_per_picture = false;           // the single chain settles verdict and DC predictors with pjd_k_group_dc, one workgroup per picture (pjd_plan.cpp)
     int plan_mode = 0;                     // PJD_PLAN_*
     std::vector<uint32_t> tset_step_bits;  // per table set: fewest bits of stream per step of the write pass, x 256 (sizes the lane regions)
 };
