@@ -35,6 +35,8 @@
  *                                                       or fp32, v * scale[c] + bias[c], in that launch (the tensor a model takes)
  *   (none: an addition)                                 PJD_F_LIBJPEG + pjd_libjpeg_idct / _ycc_to_rgb / _upsample_row: the picture libjpeg
  *                                                       decodes, bit for bit (islow IDCT, fancy upsampling, JFIF colour), per picture
+ *   (none: an addition)                                 PJD_OUT_GRAY8 + pjd_output_channels: pictures as ONE 8-bit plane, the luma as libjpeg's
+ *                                                       JCS_GRAYSCALE delivers it (a third of the bytes, no chroma work in the back end)
  *
  * Plain pointers and sizes only; no C++ or torch types.  Thread model: one
  * submitting thread per pjd_ctx (the reference has one consumer thread,
@@ -107,6 +109,10 @@ extern "C" {
                               picture of the same descriptor; everything else (status words, partial
                               pictures, shards, coefficients) is as for PJD_OUT_RGB8.  A one-component
                               JPEG gives three equal planes.                                      */
+#define PJD_OUT_GRAY8  4   /* one plane, uint8[H][W]: H top-down rows of W bytes, no padding: W*H bytes (W, H at
+                              the output scale).  The luma of the picture, as libjpeg's JCS_GRAYSCALE delivers it:
+                              the section "grey output" below is normative.  3 is not a format: it stays the
+                              unknown value callers were promised PJD_E_ARG for (as 2 is no resize filter).     */
 
 /* ---- descriptor flags ----------------------------------------------------- */
 #define PJD_F_STANDARD_RESTART  1u  /* restart at every `restart_interval`-th MCU (ITU T.81).
@@ -213,6 +219,47 @@ extern "C" {
 int  pjd_libjpeg_idct(const int16_t coef[64], const uint16_t q[64], uint8_t out[64]);            /* host only, no device needed */
 int  pjd_libjpeg_ycc_to_rgb(uint8_t y, uint8_t cb, uint8_t cr, uint8_t rgb[3]);                /* host only, no device needed */
 int  pjd_libjpeg_upsample_row(const uint8_t *cur, const uint8_t *nb, int v, uint32_t n, uint8_t *out /* 2n */);   /* host only */
+
+/* ---- grey output ----------------------------------------------------------------------------------------------------------------- *
+ * PJD_OUT_GRAY8, chosen per batch: every picture leaves as ONE plane, uint8[H][W], top-down, tight rows, W*H bytes, W and H at the
+ * picture's output scale -- what torchvision.io.decode_jpeg(mode=GRAY), OpenCV's IMREAD_GRAYSCALE and Pillow's draft("L") deliver.
+ *
+ * DEFINITION (normative).  Let P0 be the picture the library would produce for the descriptor if every chroma sample were neutral:
+ * Cb = Cr = 0 after the IDCT under the reference's arithmetic, Cb = Cr = 128 under PJD_F_LIBJPEG.  Then R = G = B in P0, and byte
+ * (y, x) of the PJD_OUT_GRAY8 picture is that common value:
+ *   - under the reference's arithmetic clamp255(Y + 128), Y the int16 luma sample after the reference's IDCT (dequantisation, the
+ *     zigzag quirk and its slot-52 rule included): src/decoder_dpu.c:376-382 with both chroma terms zero;
+ *   - under PJD_F_LIBJPEG libjpeg's own luma sample, steps 1 and 2 of that section -- what libjpeg delivers with out_color_space =
+ *     JCS_GRAYSCALE.  It is NOT a weighted sum of the clamped R, G and B of the colour picture (Pillow's convert("L") of its RGB
+ *     decode is up to 24 levels away on the fixtures of tests/golden/libjpeg/); tests/golden/libjpeg_gray/ holds Pillow's draft("L").
+ * A one-component JPEG gives the plane its three equal RGB planes are.  After an entropy-coding error the undecoded part is 128.
+ * Status words, coefficients (pjd_batch_download_coefficients), every figure of pjd_plan_info but the byte counts, lane planning and
+ * the entropy decoder are those of any other format: only the back end differs.
+ * WITH PJD_F_SCALE_*: the box filter of that section on the one plane -- channel 0 of what it makes of P0.
+ * SIZES.  pjd_output_size, pjd_image_output_size and pjd_batch_output_size give W*H; pictures in the library's own buffer stay
+ * 256-byte aligned (pjd_batch_output_offset, pjd_batch_download_packed: a third of the bytes of an RGB batch over the host link);
+ * pjd_batch_bind_output takes the batch as it takes a planar one and promises no alignment; every decode writes every byte of every
+ * unsharded picture's range and no byte outside it; a shard (shard_n_segs != 0) is accepted as in a PJD_OUT_RGB8 batch and only its
+ * MCUs are written.  pjd_batch_capture, the exact-kernel fallback of pjd_batch_sync, pjd_decode_batch, pjd_plan_check and
+ * pjd_pipe_opts::out_format (the sink receives W*H bytes) take the format.
+ * EVERYTHING DOWNSTREAM is channel 0 of what the three-channel pipeline would do to P0; no filter has arithmetic of its own.  A grey
+ * batch is a planar batch with ONE plane: pjd_batch_set_resize, _set_resize_filter (all three filters), _set_resize_window,
+ * _set_orientation and _set_resize_pad keep their rules, call order and errors, and pjd_batch_output_size is tw*th (times the element
+ * size when normalised).  pjd_batch_set_normalize: fma(v, scale[0], bias[0]); all six constants are still validated as finite, entries
+ * [1] and [2] are ignored.  pjd_batch_set_resize_pad / _set_pad_value: fill[0] and value[0].  pjd_batch_bind_output of a normalised
+ * batch wants element alignment, as for the other formats.
+ * REFUSED with PJD_E_ARG: pjd_split_decode with this format; everything a planar batch refuses (a resize or a normalisation of a
+ * shard, targets outside 1..65535, a picture more than 16x its target under a table-driven filter, ...); PJD_F_LIBJPEG together with
+ * PJD_F_SCALE_*, 4:4:0 sampling, two components or a shard, exactly as in the other formats.
+ * HOW.  Kernels of their own (pjd_k_backend_gray.hip; pjd_batch_decode_timed names them "idct_gray" and, for the flagged pictures of a
+ * batch, "idct_gray_std"): the entropy decoder's streams interleave the components, so chroma entries are still walked, but chroma
+ * units are not dequantised, not DC-settled and not transformed; there is no upsampling and no colour arithmetic, and a lane stores
+ * eight adjacent pixels at once.  A flagged picture's luma rows go straight from the islow IDCT into the picture: a grey batch has no
+ * component planes (pjd_batch_info::device_bytes) and no "colour_std" launch.  The resample of a grey batch always runs the padded
+ * (most general) kernel form, with the identity window, orientation 1 and an all-zero pad where none was asked for: one channel is
+ * built for that form alone.  pjd_batch_decode_timed therefore lists "pad" behind "resize" for every resized grey batch; the border
+ * launch is skipped where no picture has a border.
+ * DETECTION.  No struct changed and PJD_VERSION stays 6: a caller checks for pjd_output_channels (below).                          */
 
 /* Huffman table as the reference's scanner holds it (jpeg.h:129-134):
  * offsets[k] = number of codes of length <= k (offsets[0] = 0).               */
@@ -795,6 +842,10 @@ void pjd_host_free(void *p);
 
 /* Size in bytes of one picture in a given output format.                      */
 uint64_t pjd_output_size(uint32_t width, uint32_t height, int out_format);
+/* Channels of an output format: 3 for PJD_OUT_RGB8, PJD_OUT_BMP and PJD_OUT_RGB8_PLANAR, 1 for PJD_OUT_GRAY8, 0 for a value that is
+ * no format.  Host only (no device needed).  PJD_OUT_GRAY8 changed no struct and no version: a caller that needs it checks for it by
+ * this symbol, which is exported from the first library that knows the format.                                                    */
+int  pjd_output_channels(int out_format);
 /* Output dimensions of a width x height picture under descriptor flags `flags` (PJD_F_SCALE_*): ceil(W/s) x ceil(H/s).  Returns PJD_OK. */
 int  pjd_scaled_dims(uint32_t width, uint32_t height, uint32_t flags, uint32_t *out_w, uint32_t *out_h);
 /* Size in bytes of the picture of one descriptor in a given output format, at its output scale: what pjd_batch_output_size,

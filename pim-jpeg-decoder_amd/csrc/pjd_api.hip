@@ -233,14 +233,14 @@ struct pjd_batch {
         pjd_launch_resize(s, PjdResizeLaunch{dev.out, res_out, (const PjdDevResize *)rs.d, (const uint32_t *)(rs.d + n * sizeof(PjdDevResize)), dev.n_images, form.tiles, planar, norm,
                                              form.windowed ? (const PjdDevResizeWin *)win.d : nullptr, form.oriented, spec.filter,
                                              (const PjdDevResizeAA *)aa.d, aa.d ? (const uint32_t *)(aa.d + n * sizeof(PjdDevResizeAA)) : nullptr, form.lds,
-                                             form.padded ? (const PjdDevResizePad *)pad.d : nullptr});
+                                             form.padded ? (const PjdDevResizePad *)pad.d : nullptr, spec.channels});
     }
     // ... and the border of its padded pictures, behind it (the same two sites): the two write disjoint bytes
     void launch_pad(hipStream_t s, bool planar) const
     {
         const size_t n = dev.n_images;
         pjd_launch_resize_border(s, PjdBorderLaunch{res_out, (const PjdDevResize *)rs.d, (const PjdDevResizePad *)pad.d, (const uint32_t *)(pad.d + n * sizeof(PjdDevResizePad)), dev.n_images,
-                                                    form.lines, planar, norm.dtype ? PJD_DT_SIZE(norm.dtype) : 1u, pjd_pad_fill(norm, planar, pad_fill, pad_value_set ? pad_value : nullptr)});
+                                                    form.lines, planar, norm.dtype ? PJD_DT_SIZE(norm.dtype) : 1u, pjd_pad_fill(norm, planar, pad_fill, pad_value_set ? pad_value : nullptr), spec.channels});
     }
 };
 
@@ -512,7 +512,7 @@ int pjd_batch_create(pjd_ctx *ctx, const pjd_image_desc *images, int n_images, i
     b->d_ecs = b->d_in + o_ecs;
     if (P.libjpeg) {
         b->d_iwgs_dense_std = (PjdDevIdctWg *)(b->d_in + o_iwgs_dense_std); b->d_cwgs_std = (PjdDevIdctWg *)(b->d_in + o_cwgs_std);
-        TRY_RC(dev_alloc(ctx, b->d_planes, (size_t)P.plane_bytes, tot));
+        if (!P.gray) TRY_RC(dev_alloc(ctx, b->d_planes, (size_t)P.plane_bytes, tot));     // a grey batch has no component planes
     }
     TRY_RC(dev_alloc(ctx, b->dev.luts, (size_t)P.lut_buf_bytes, tot));
     TRY_RC(dev_alloc(ctx, b->dev.words, (size_t)P.n_words, tot));
@@ -670,7 +670,7 @@ int enqueue_decode(pjd_batch *b, pjd_timings *timings, bool use_groups)
     // "pull": the pull launch has no scaled and no planar form.
     static const int idle_form = [] { const char *e = std::getenv("PJD_IDLE_FORM"); return !e ? 1 : (!std::strcmp(e, "pull") ? 2 : (!std::strcmp(e, "chain") ? 0 : 1)); }();
     const bool idle = !timings && use_groups && parallel && !P.groups.empty() && idle_form != 0;       // per-kernel timing: one chain, kernel after kernel
-    const bool no_pull = P.scaled || P.planar;
+    const bool no_pull = P.scaled || P.planar || P.gray;
     const size_t ng = (idle && (idle_form == 1 || no_pull)) ? P.groups.size() : 0;
     const bool grouped = ng > 1 && ctx_group_streams(ctx, ng);
     if (idle && idle_form == 2 && !no_pull && ctx_group_streams(ctx, 2)) {
@@ -698,7 +698,8 @@ int enqueue_decode(pjd_batch *b, pjd_timings *timings, bool use_groups)
             if (g) HIP_TRY(ctx, hipStreamWaitEvent(gs, ctx->fork_ev, 0));
             pjd_launch_huff_lanes_group(gs, b->dev, P.groups[g], (uint32_t)g);
             pjd_launch_group_dc(gs, b->dev, P.groups[g]);
-            pjd_launch_group_idct(gs, b->dev, P.groups[g], P.scaled, P.planar);
+            if (P.gray) pjd_launch_idct_gray_lanes(gs, b->dev, b->dev.iwg_order + P.groups[g].iwg_first, P.groups[g].iwg_count, P.scaled);
+            else pjd_launch_group_idct(gs, b->dev, P.groups[g], P.scaled, P.planar);
             if (g) { HIP_TRY(ctx, hipEventRecord(ctx->join_ev[g - 1], gs)); }
         }
         for (size_t g = 1; g < ng; g++) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->join_ev[g - 1], 0));
@@ -706,6 +707,12 @@ int enqueue_decode(pjd_batch *b, pjd_timings *timings, bool use_groups)
         if (parallel) {
             pjd_launch_huff_lanes(s, b->dev);    kt.mark("huff_lanes");
             pjd_launch_lane_dc_scan(s, b->dev, P.dc_per_picture);  kt.mark("dc_scan");
+            if (P.gray) {
+                // a grey batch: the luma units alone (pjd_k_backend_gray.hip); its flagged pictures store their rows themselves
+                pjd_launch_idct_gray_lanes(s, b->dev, P.libjpeg ? b->dev.iwg_order : nullptr, P.libjpeg ? P.n_iwg_def : b->dev.n_iwg, P.scaled);
+                kt.mark("idct_gray");
+                if (P.n_iwg_std) { pjd_launch_idct_gray_std_lanes(s, b->dev, b->dev.iwg_order + P.n_iwg_def, P.n_iwg_std); kt.mark("idct_gray_std"); }
+            } else {
             if (!P.libjpeg) pjd_launch_idct_colour_lanes(s, b->dev, P.scaled, P.planar);
             else {
                 // the ranges of the unflagged pictures through the default kernels, those of the flagged ones into their planes
@@ -715,6 +722,7 @@ int enqueue_decode(pjd_batch *b, pjd_timings *timings, bool use_groups)
             }
             kt.mark("idct_colour");
             if (P.n_iwg_std) { pjd_launch_idct_std_lanes(s, b->dev, b->dev.iwg_order + P.n_iwg_def, P.n_iwg_std, b->d_planes); kt.mark("idct_std"); }
+            }
         }
     }
     if (!b->seq_list.empty()) {
@@ -722,11 +730,16 @@ int enqueue_decode(pjd_batch *b, pjd_timings *timings, bool use_groups)
         pjd_launch_zero(s, b->dev.coef, P.dense_du * 64 * sizeof(int16_t));      // a kernel, not a memset node: see the reset above
         pjd_launch_huff_sequential(s, b->dev, b->d_seq_list, b->d_seq_base, (uint32_t)b->seq_list.size());
         if (!P.pscans.empty()) pjd_launch_progressive(s, b->dev, b->d_seq_list, b->d_seq_base, (uint32_t)b->seq_list.size());
+        if (P.gray) {
+            pjd_launch_idct_gray(s, b->dev, b->d_iwgs_dense, b->d_seq_base, (uint32_t)P.iwgs_dense.size(), P.scaled);
+            if (P.libjpeg) pjd_launch_idct_gray_std_dense(s, b->dev, b->d_iwgs_dense_std, b->d_seq_base, (uint32_t)P.iwgs_dense_std.size());
+        } else {
         pjd_launch_idct_colour(s, b->dev, b->d_iwgs_dense, b->d_seq_base, (uint32_t)P.iwgs_dense.size(), P.scaled, P.planar);
         if (P.libjpeg) pjd_launch_idct_std_dense(s, b->dev, b->d_iwgs_dense_std, b->d_seq_base, (uint32_t)P.iwgs_dense_std.size(), b->d_planes);
+        }
         kt.mark("exact_path");
     }
-    if (P.libjpeg) {
+    if (P.libjpeg && !P.gray) {
         // the flagged pictures' planes are complete, whichever front end filled them: upsample, colour, store
         pjd_launch_colour_std(s, b->dev, b->d_cwgs_std, (uint32_t)P.cwgs_std.size(), b->d_planes);
         kt.mark("colour_std");
@@ -734,9 +747,9 @@ int enqueue_decode(pjd_batch *b, pjd_timings *timings, bool use_groups)
     if (b->resized) {
         // resize on decode: every picture from the intermediate (dev.out) to its target size in the result buffer, one launch behind
         // whatever form the back end took (the groups' streams have joined `s` above)
-        b->launch_resize(s, P.planar);
+        b->launch_resize(s, P.planar || P.gray);
         kt.mark("resize");
-        if (b->form.padded) { b->launch_pad(s, P.planar); kt.mark("pad"); }
+        if (b->form.padded) { b->launch_pad(s, P.planar || P.gray); kt.mark("pad"); }
     }
     HIP_TRY(ctx, hipGetLastError());
     kt.finish();
@@ -821,16 +834,20 @@ int settle(pjd_batch *b)
         if (e == hipSuccess) {
             if (ev0) (void)hipEventRecord(ev0, s);
             pjd_launch_huff_sequential(s, dv, d_list, d_base, (uint32_t)fb.size());
+            if (P.gray) {
+                pjd_launch_idct_gray(s, dv, d_wgs, d_base, (uint32_t)n_def, P.scaled);
+                pjd_launch_idct_gray_std_dense(s, dv, d_wgs + n_def, d_base, (uint32_t)n_std);
+            } else
             pjd_launch_idct_colour(s, dv, d_wgs, d_base, (uint32_t)n_def, P.scaled, P.planar);
-            if (n_std) {
+            if (n_std && !P.gray) {
                 // flagged pictures: their planes again, then the colour launch (all flagged pictures of the batch: a rare path)
                 pjd_launch_idct_std_dense(s, dv, d_wgs + n_def, d_base, (uint32_t)n_std, b->d_planes);
                 pjd_launch_colour_std(s, dv, b->d_cwgs_std, (uint32_t)P.cwgs_std.size(), b->d_planes);
             }
             if (ev1) (void)hipEventRecord(ev1, s);
             // the pictures just decoded again changed in the intermediate: resample (the whole batch: a rare path)
-            if (b->resized) b->launch_resize(s, P.planar);
-            if (b->form.padded) b->launch_pad(s, P.planar);
+            if (b->resized) b->launch_resize(s, P.planar || P.gray);
+            if (b->form.padded) b->launch_pad(s, P.planar || P.gray);
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipMemcpyAsync(b->h_status, b->dev.status, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s);
@@ -1109,9 +1126,11 @@ int pjd_batch_set_resize(pjd_batch *b, const uint32_t *out_w, const uint32_t *ou
     const size_t n = P.images.size();
     // the request: every picture from where the back end wrote it at its decode size to the packed layout of the result buffer
     // (256-byte aligned offsets, as the planner lays out a batch's own buffer; pjd_batch_bind_output may still change them)
-    const PjdPackedLayout lay = pjd_packed_layout(out_w, out_h, n, 1);
+    const uint32_t channels = P.gray ? 1u : 3u;            // a grey batch is a planar batch with one plane
+    const PjdPackedLayout lay = pjd_packed_layout(out_w, out_h, n, 1, channels);
     PjdResizeSpec spec;
-    spec.planar = P.planar;
+    spec.planar = P.planar || P.gray;
+    spec.channels = channels;
     spec.out_w.assign(out_w, out_w + n); spec.out_h.assign(out_h, out_h + n);
     size_t shard = n;                                      // the first shard of the batch
     for (size_t i = 0; i < n; i++) {
@@ -1303,7 +1322,7 @@ int pjd_batch_set_normalize(pjd_batch *b, int dtype, const float scale[3], const
         w.resize(n); h.resize(n);
         for (size_t i = 0; i < n; i++) pjd_scaled_dims(P.images[i].width, P.images[i].height, (P.images[i].flags & PJD_IF_SCALE_MASK) >> PJD_IF_SCALE_SHIFT << 4, &w[i], &h[i]);
     }
-    const PjdPackedLayout lay = pjd_packed_layout(w.data(), h.data(), n, PJD_DT_SIZE(dtype));
+    const PjdPackedLayout lay = pjd_packed_layout(w.data(), h.data(), n, PJD_DT_SIZE(dtype), P.gray ? 1u : 3u);
     void *d_res = nullptr;
     int rc = pool_dev_alloc(ctx, &d_res, (size_t)lay.buf_bytes, b->dev_blocks);
     if (rc != PJD_OK) return rc;

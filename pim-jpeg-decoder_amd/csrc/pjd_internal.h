@@ -127,6 +127,8 @@
 
 #define PJD_IF_LIBJPEG          512u // PJD_F_LIBJPEG: the picture is libjpeg's (islow IDCT, fancy upsampling, JFIF colour): the back end of pjd_k_backend_std.hip;
                                      // always together with PJD_IF_STANDARD_ZIGZAG and PJD_IF_STANDARD_RESTART
+#define PJD_IF_GRAY             1024u // output is one plane (PJD_OUT_GRAY8): out_stride x output rows bytes; a property of the whole batch (the grey
+                                     // back-end kernels of pjd_k_backend_gray.hip are launched for it), never together with PJD_IF_BMP or PJD_IF_PLANAR
 
 // status word per image: low 8 bits = PJD_ST_* class, bit 8 = "fast path gave up, needs exact kernel"
 #define PJD_STW_NEEDS_EXACT 0x100
@@ -186,7 +188,7 @@ struct PjdDevImage {
     uint64_t dense_base;               // first data unit of this image in the DENSE scratch (exact-kernel path only)
     uint32_t n_du;
     uint32_t image_index;
-    uint32_t out_stride;               // bytes per output row of the (scaled) picture, width w = ceil(W / s): BMP 3w + w%4, RGB8 3w, planar w (a plane row)
+    uint32_t out_stride;               // bytes per output row of the (scaled) picture, width w = ceil(W / s): BMP 3w + w%4, RGB8 3w, planar and grey w (a plane row)
     uint64_t out_off;                  // into the batch output buffer (256-byte aligned), or the caller's (pjd_batch_bind_output: any offset)
     uint32_t seg_base, n_seg;          // into PjdDevSegment[]
     uint32_t lane_base, n_lane;        // into PjdDevSub[] (global lane index)
@@ -465,7 +467,8 @@ struct PjdDevResizeAA {
 };
 
 // the LDS a tile needs for a row segment of `span` source pixels (the host sizes the launch with it, the kernel lays its segment out with it)
-static inline __host__ __device__ uint32_t pjd_resize_aa_lds(uint32_t span, bool planar) { return planar ? 3u * ((span + 6u) & ~3u) : (3u * span + 6u) & ~3u; }
+// nc: the channels of a planar picture (3, or 1 for a grey batch: one plane segment)
+static inline __host__ __device__ uint32_t pjd_resize_aa_lds(uint32_t span, bool planar, uint32_t nc = 3u) { return planar ? nc * ((span + 6u) & ~3u) : (3u * span + 6u) & ~3u; }
 
 // ---- source windows (pjd_batch_set_resize_window; the arithmetic is normative: include/pjd.h) -----------------------------------
 // What the windowed launches (pjd_k_resize.hip, WIN) read beside the work list: per picture the window with every default resolved

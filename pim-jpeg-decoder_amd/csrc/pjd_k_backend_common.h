@@ -1,4 +1,4 @@
-// pjd_k_backend_common.h -- what the back-end units (pjd_k_backend.hip, pjd_k_backend_std.hip) share: the LDS tile row, the
+// pjd_k_backend_common.h -- what the back-end units (pjd_k_backend.hip, pjd_k_backend_std.hip, pjd_k_backend_gray.hip) share: the LDS tile row, the
 // range of decoded units, the wide stores, the BMP header, the wave scans of the DC stage and the tile store of the entry parser.
 #pragma once
 #include "pjd_device_common.h"

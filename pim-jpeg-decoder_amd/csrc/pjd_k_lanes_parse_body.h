@@ -2,7 +2,13 @@
 // pjd_idct_range (pjd_k_backend.hip) and by the plane kernel of the libjpeg-exact mode (pjd_k_backend_std.hip); textual inclusion
 // for the reason pjd_k_idct_dense_body.h gives.  Uses B, iwg, tile, qz, mcu_xy, comp_of, du_head, wagg, ltab of the including
 // function and leaves wg, im, tid, lane, wv, dus, nl, n_du, n_valid and pred0 behind.  With PJD_LANES_RAW defined the tile receives the
-// coefficients as decoded (quantiser 1, DC differences likewise) instead of their 16-bit products.
+// coefficients as decoded (quantiser 1, DC differences likewise) instead of their 16-bit products.  With PJD_LANES_LUMA_ONLY defined
+// (the grey back end, pjd_k_backend_gray.hip) the entries of chroma units are walked -- the stream interleaves them -- and dropped.
+#ifdef PJD_LANES_LUMA_ONLY
+#define PJD_LANES_KEEP(u) (comp_of[u] == 0)
+#else
+#define PJD_LANES_KEEP(u) true
+#endif
     const PjdDevIdctWg wg = B.iwgs[iwg];
     const PjdDevImage &im = B.images[wg.image];
     if ((im.flags & PJD_IF_SEQUENTIAL) || (B.status[wg.image] & PJD_STW_NEEDS_EXACT)) return;   // the dense path redoes it
@@ -140,7 +146,7 @@
                         const bool dc = slot == 0;
                         const uint32_t f = dc ? 1u : sw & 31u;              // run + 1; 0: EOB
                         const uint32_t ns = slot + f, pos = ns - 1u;        // an EOB gives slot - 1: stores nothing (below)
-                        if (on && f != 0 && pos < 64 && u < n_valid) {
+                        if (on && f != 0 && pos < 64 && u < n_valid && PJD_LANES_KEEP(u)) {
                             const int val = dc ? (int)(int16_t)(sw & 0xffffu) : (int)(sw << 16) >> 21;
                             const uint32_t qe = qz[comp_of[u]][pos];        // (slot 52 under the quirk: position 64, quantiser 1)
                             // the low 16 bits of value x quantiser (reference src/decoder_dpu.c:169-172) depend on the low 16 bits of both only
@@ -156,7 +162,7 @@
                         const uint32_t f = (sw >> 16) & 31u;
                         const bool onb = on && f <= 16;                     // PJD_ENT_NONE: "run + 1" = 31
                         const uint32_t pos = slot + f - 1u;
-                        if (onb && f != 0 && pos < 64 && u < n_valid) {
+                        if (onb && f != 0 && pos < 64 && u < n_valid && PJD_LANES_KEEP(u)) {
                             const int val = (int)sw >> 21;
                             const uint32_t qe = qz[comp_of[u]][pos];
                             pjd_tile_put(tile_lds, u, qe >> 16, pjd_mul_u24((uint32_t)val, qe));
@@ -174,3 +180,4 @@
             if (!again) break;
         }
     }
+#undef PJD_LANES_KEEP

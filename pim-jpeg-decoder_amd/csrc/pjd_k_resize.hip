@@ -68,6 +68,7 @@ pjd_k_resize(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, const P
 {
     constexpr int DT = 0;
     constexpr bool WIN = false, ORI = false, PAD = false;
+    constexpr int NC = 3;
     const PjdDevResizePad *const pad = nullptr;
     const PjdDevResizeWin *const win = nullptr;
     const NormArgs nz{};
@@ -80,6 +81,7 @@ pjd_k_resize_norm(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, co
                   const uint32_t *__restrict__ tile_prefix, uint32_t n_images, uint32_t n_tiles, const NormArgs nz)
 {
     constexpr bool WIN = false, ORI = false, PAD = false;
+    constexpr int NC = 3;
     const PjdDevResizePad *const pad = nullptr;
     const PjdDevResizeWin *const win = nullptr;
 #include "pjd_k_resize_body.h"
@@ -92,6 +94,7 @@ pjd_k_resize_win(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, con
                  const NormArgs nz)
 {
     constexpr bool WIN = true, ORI = false, PAD = false;
+    constexpr int NC = 3;
     const PjdDevResizePad *const pad = nullptr;
 #include "pjd_k_resize_body.h"
 }
@@ -104,6 +107,7 @@ pjd_k_resize_aa(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, cons
 {
     extern __shared__ uint32_t seg[];                      // one source row's segment (three plane segments where PLANAR)
     constexpr bool WIN = false, ORI = false, PAD = false;
+    constexpr int NC = 3;
     const PjdDevResizePad *const pad = nullptr;
     constexpr int FILT = PJD_RESIZE_ANTIALIAS;
     const PjdDevResizeWin *const win = nullptr;
@@ -118,6 +122,7 @@ pjd_k_resize_win_aa(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, 
 {
     extern __shared__ uint32_t seg[];
     constexpr bool WIN = true, ORI = false, PAD = false;
+    constexpr int NC = 3;
     const PjdDevResizePad *const pad = nullptr;
     constexpr int FILT = PJD_RESIZE_ANTIALIAS;
 #include "pjd_k_resize_aa_body.h"
@@ -132,6 +137,7 @@ pjd_k_resize_cubic(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, c
 {
     extern __shared__ uint32_t seg[];
     constexpr bool WIN = false, ORI = false, PAD = false;
+    constexpr int NC = 3;
     const PjdDevResizePad *const pad = nullptr;
     constexpr int FILT = PJD_RESIZE_BICUBIC;
     const PjdDevResizeWin *const win = nullptr;
@@ -146,6 +152,7 @@ pjd_k_resize_win_cubic(const uint8_t *__restrict__ src, uint8_t *__restrict__ ds
 {
     extern __shared__ uint32_t seg[];
     constexpr bool WIN = true, ORI = false, PAD = false;
+    constexpr int NC = 3;
     const PjdDevResizePad *const pad = nullptr;
     constexpr int FILT = PJD_RESIZE_BICUBIC;
 #include "pjd_k_resize_aa_body.h"
@@ -161,6 +168,7 @@ pjd_k_resize_ori(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, con
                  const NormArgs nz)
 {
     constexpr bool WIN = true, ORI = true, PAD = false;
+    constexpr int NC = 3;
     const PjdDevResizePad *const pad = nullptr;
 #include "pjd_k_resize_body.h"
 }
@@ -173,6 +181,7 @@ pjd_k_resize_ori_tab(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst,
 {
     extern __shared__ uint32_t seg[];
     constexpr bool WIN = true, ORI = true, PAD = false;
+    constexpr int NC = 3;
     const PjdDevResizePad *const pad = nullptr;
 #include "pjd_k_resize_aa_body.h"
 }
@@ -187,6 +196,7 @@ pjd_k_resize_pad(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, con
                  uint32_t n_images, uint32_t n_tiles, const NormArgs nz)
 {
     constexpr bool WIN = true, ORI = true, PAD = true;
+    constexpr int NC = 3;
 #include "pjd_k_resize_body.h"
 }
 
@@ -199,6 +209,35 @@ pjd_k_resize_pad_tab(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst,
 {
     extern __shared__ uint32_t seg[];
     constexpr bool WIN = true, ORI = true, PAD = true;
+    constexpr int NC = 3;
+#include "pjd_k_resize_aa_body.h"
+}
+
+// A grey batch (PJD_OUT_GRAY8): one plane.  Routed through the most general form alone -- the padded kernels, with the identity window,
+// orientation 1 and an all-zero pad where the batch asked for none -- so that one channel costs twelve instantiations and not sixty
+// (profiles/gray_output.md).  The same bodies with NC = 1: the channel loops run once, the LDS row segment is one plane segment.
+// Kernels of their own: the three-channel ones keep their symbols, code and registers.
+template <int DT>
+__global__ void __launch_bounds__(64 * PJD_RS_WAVES)
+pjd_k_resize_gray(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, const PjdDevResize *__restrict__ recs,
+                  const PjdDevResizeWin *__restrict__ win, const PjdDevResizePad *__restrict__ pad, const uint32_t *__restrict__ tile_prefix,
+                  uint32_t n_images, uint32_t n_tiles, const NormArgs nz)
+{
+    constexpr bool PLANAR = true, WIN = true, ORI = true, PAD = true;
+    constexpr int NC = 1;
+#include "pjd_k_resize_body.h"
+}
+
+template <int DT, int FILT>
+__global__ void __launch_bounds__(64)
+pjd_k_resize_gray_tab(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, const PjdDevResize *__restrict__ recs,
+                      const PjdDevResizeWin *__restrict__ win, const PjdDevResizePad *__restrict__ pad, const uint32_t *__restrict__ tile_prefix,
+                      uint32_t n_images, uint32_t n_tiles, const PjdDevResizeAA *__restrict__ aa, const uint32_t *__restrict__ tab, uint32_t lds_bytes,
+                      const NormArgs nz)
+{
+    extern __shared__ uint32_t seg[];
+    constexpr bool PLANAR = true, WIN = true, ORI = true, PAD = true;
+    constexpr int NC = 1;
 #include "pjd_k_resize_aa_body.h"
 }
 
@@ -245,6 +284,15 @@ void pjd_launch_resize(hipStream_t s, const PjdResizeLaunch &a)
     for_layout_and_dtype(a.planar, a.norm.dtype, [&](auto P, auto D) {
         constexpr bool PL = decltype(P)::value;
         constexpr int DT = decltype(D)::value;
+        if (a.channels == 1) {                             // a grey batch: planar, one plane, always with win and pad records
+            if (a.filter == PJD_RESIZE_BICUBIC)
+                hipLaunchKernelGGL((pjd_k_resize_gray_tab<DT, PJD_RESIZE_BICUBIC>), grid, block, a.lds_bytes, s, a.src, a.dst, a.recs, a.win, a.pad, a.tile_prefix, a.n_images, a.n_tiles, a.aa, a.tab, a.lds_bytes, nz);
+            else if (tabled)
+                hipLaunchKernelGGL((pjd_k_resize_gray_tab<DT, PJD_RESIZE_ANTIALIAS>), grid, block, a.lds_bytes, s, a.src, a.dst, a.recs, a.win, a.pad, a.tile_prefix, a.n_images, a.n_tiles, a.aa, a.tab, a.lds_bytes, nz);
+            else
+                hipLaunchKernelGGL((pjd_k_resize_gray<DT>), grid, block, 0, s, a.src, a.dst, a.recs, a.win, a.pad, a.tile_prefix, a.n_images, a.n_tiles, nz);
+            return;
+        }
         if (a.pad && a.filter == PJD_RESIZE_BICUBIC)
             hipLaunchKernelGGL((pjd_k_resize_pad_tab<PL, DT, PJD_RESIZE_BICUBIC>), grid, block, a.lds_bytes, s, a.src, a.dst, a.recs, a.win, a.pad, a.tile_prefix, a.n_images, a.n_tiles, a.aa, a.tab, a.lds_bytes, nz);
         else if (a.pad && tabled)

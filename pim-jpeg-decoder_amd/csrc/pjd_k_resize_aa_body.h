@@ -15,7 +15,7 @@
 // No lane leaves before the last barrier; lanes right of the picture compute its last column and store nothing.
 // A textual include, so that tools/resize_host.cpp runs this very text on the host; PJD_WIN_STAGE_FIRST / _STEP say which dwords of a
 // segment this thread stages (its own of the wave's 64 here; all of them where a thread runs alone).
-// In scope: PLANAR, DT, WIN, ORI (implies WIN), PAD (implies ORI), FILT (compile-time constants), seg (LDS), src, dst, recs, win (read only where WIN),
+// In scope: PLANAR, DT, WIN, ORI (implies WIN), PAD (implies ORI), FILT, NC (compile-time constants; NC: the channels, 3, or 1 only where PLANAR: ONE plane segment in LDS), seg (LDS), src, dst, recs, win (read only where WIN),
 // pad (read only where PAD), tile_prefix, n_images,
 // n_tiles, aa, tab, lds_bytes, nz; store_row and store_cols.
 #ifndef PJD_WIN_STAGE_FIRST
@@ -47,7 +47,7 @@
     const uint32_t head0 = xt[end_lo], head1 = xt[end_hi];
     const uint32_t xs = head0 & 0xffffu, xe = (head1 & 0xffffu) + (head1 >> 16), span = xe - xs;
     const uint32_t pitch = (span + 6u) & ~3u;              // bytes per plane segment (PLANAR)
-    if (xe > w.w || xe <= xs || pjd_resize_aa_lds(span, PLANAR) > lds_bytes) return;   // never with the host's table: nothing is read or written out of bounds
+    if (xe > w.w || xe <= xs || pjd_resize_aa_lds(span, PLANAR, NC) > lds_bytes) return;   // never with the host's table: nothing is read or written out of bounds
 
     // the source rows of the tile (relative to the window), and per target row its first tap and tap count
     uint32_t yf[PJD_RS_ROWS], yc[PJD_RS_ROWS];
@@ -84,7 +84,7 @@
 #pragma unroll
     for (int k = 0; k < PJD_RS_ROWS; k++)
 #pragma unroll
-        for (int c = 0; c < 3; c++)
+        for (int c = 0; c < NC; c++)
 #pragma unroll
             for (int q = 0; q < PJD_RS_PX; q++) acc[k][c][q] = 0u;
 
@@ -93,7 +93,7 @@
         uint32_t sh[3];                                    // bytes between the first dword staged and the segment's first byte
         if (PLANAR) {
 #pragma unroll
-            for (int c = 0; c < 3; c++) {
+            for (int c = 0; c < NC; c++) {
                 const uint8_t *g = sp + c * src_plane + (uint64_t)y * r.src_stride;
                 sh[c] = (uint32_t)((uintptr_t)g & 3u);
                 const uint32_t *g4 = reinterpret_cast<const uint32_t *>(g - sh[c]);
@@ -111,7 +111,7 @@
 
         uint32_t h[3][PJD_RS_PX];
 #pragma unroll
-        for (int c = 0; c < 3; c++)
+        for (int c = 0; c < NC; c++)
 #pragma unroll
             for (int q = 0; q < PJD_RS_PX; q++) h[c][q] = 0u;
         for (uint32_t tp = 0; tp < a.x_taps; tp++) {
@@ -121,14 +121,14 @@
                 const uint32_t wt = wrow[xi[q]];
                 const uint32_t j = xf[q] + tp < span ? xf[q] + tp : span - 1u;    // past the column's count the weight is 0: any staged byte
 #pragma unroll
-                for (int c = 0; c < 3; c++) {
+                for (int c = 0; c < NC; c++) {
                     const uint32_t v = PLANAR ? sb[c * pitch + sh[c] + j] : sb[sh[0] + 3u * j + c];
                     h[c][q] = tap_mac<FILT>(h[c][q], wt, v);
                 }
             }
         }
 #pragma unroll
-        for (int c = 0; c < 3; c++)
+        for (int c = 0; c < NC; c++)
 #pragma unroll
             for (int q = 0; q < PJD_RS_PX; q++) h[c][q] = tap_row<FILT>(h[c][q]);
 
@@ -138,7 +138,7 @@
             if (d < yc[k]) {                               // uniform
                 const uint32_t wt = yt[(size_t)(d + 1u) * w.vh + w.oy + row0 + k];
 #pragma unroll
-                for (int c = 0; c < 3; c++)
+                for (int c = 0; c < NC; c++)
 #pragma unroll
                     for (int q = 0; q < PJD_RS_PX; q++) acc[k][c][q] = tap_mac<FILT>(acc[k][c][q], wt, h[c][q]);
             }
@@ -153,10 +153,10 @@
 #pragma unroll
             for (int k = 0; k < PJD_RS_ROWS; k++)
 #pragma unroll
-                for (int c = 0; c < 3; c++)
+                for (int c = 0; c < NC; c++)
 #pragma unroll
                     for (int q = 0; q < PJD_RS_PX; q++) acc[k][c][q] = tap_out<FILT>(acc[k][c][q]);
-            store_cols<PLANAR, DT>(acc, dp, row0, r.th - row0 < PJD_RS_ROWS ? r.th - row0 : PJD_RS_ROWS, col0, n_px, (w.flags & PJD_RWI_YMIRROR) != 0, r.th, PAD ? cv.W : r.th, dst_plane, nz);
+            store_cols<PLANAR, DT, NC>(acc, dp, row0, r.th - row0 < PJD_RS_ROWS ? r.th - row0 : PJD_RS_ROWS, col0, n_px, (w.flags & PJD_RWI_YMIRROR) != 0, r.th, PAD ? cv.W : r.th, dst_plane, nz);
             return;
         }
     }
@@ -165,8 +165,8 @@
         if (row0 + k >= r.th) break;                       // uniform
         uint32_t px[3][PJD_RS_PX];
 #pragma unroll
-        for (int c = 0; c < 3; c++)
+        for (int c = 0; c < NC; c++)
 #pragma unroll
             for (int q = 0; q < PJD_RS_PX; q++) px[c][q] = tap_out<FILT>(acc[k][c][q]);
-        store_row<PLANAR, DT>(px, dp, ORI && (w.flags & PJD_RWI_YMIRROR) ? r.th - 1u - (row0 + k) : row0 + k, col0, n_px, dst_plane, dst_stride, nz);
+        store_row<PLANAR, DT, NC>(px, dp, ORI && (w.flags & PJD_RWI_YMIRROR) ? r.th - 1u - (row0 + k) : row0 + k, col0, n_px, dst_plane, dst_stride, nz);
     }

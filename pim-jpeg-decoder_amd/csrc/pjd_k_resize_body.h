@@ -12,7 +12,7 @@
 // text on the host.
 // With ORI (which implies WIN) the store side reads the orientation of pjd_batch_set_orientation from the window's flags (PJD_RWI_* of
 // pjd_internal.h); the read side does not know of it: the tap mirror is the bit PJD_RW_HFLIP has.
-// In scope: PLANAR, DT, WIN, ORI, PAD (compile-time constants; PAD implies ORI), src, dst, recs, win (read only where WIN), pad (read only where PAD), tile_prefix, n_images, n_tiles, nz
+// In scope: PLANAR, DT, WIN, ORI, PAD, NC (compile-time constants; PAD implies ORI; NC: the channels, 3, or 1 only where PLANAR -- a grey batch), src, dst, recs, win (read only where WIN), pad (read only where PAD), tile_prefix, n_images, n_tiles, nz
 // (NormArgs; read only where DT != 0; r.dst_off stays a byte offset); lerp8, store_row and store_cols.
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t tile = __builtin_amdgcn_readfirstlane(blockIdx.x * PJD_RS_WAVES + (threadIdx.x >> 6));
@@ -70,7 +70,7 @@
         const uint8_t *s0 = sp + (uint64_t)y0 * r.src_stride, *s1 = sp + (uint64_t)y1 * r.src_stride;
         uint32_t px[3][PJD_RS_PX];
 #pragma unroll
-        for (int c = 0; c < 3; c++) {
+        for (int c = 0; c < NC; c++) {
             const uint8_t *c0 = s0 + c * src_plane, *c1 = s1 + c * src_plane;
 #pragma unroll
             for (int q = 0; q < PJD_RS_PX; q++) {
@@ -87,19 +87,19 @@
         if constexpr (ORI) {
             if (w.flags & PJD_RWI_TRANSPOSE) {             // uniform
 #pragma unroll
-                for (int c = 0; c < 3; c++)
+                for (int c = 0; c < NC; c++)
 #pragma unroll
                     for (int q = 0; q < PJD_RS_PX; q++) kept[k][c][q] = px[c][q];
             } else {
-                store_row<PLANAR, DT>(px, dp, (w.flags & PJD_RWI_YMIRROR) ? r.th - 1u - row : row, col0, n_px, dst_plane, dst_stride, nz);
+                store_row<PLANAR, DT, NC>(px, dp, (w.flags & PJD_RWI_YMIRROR) ? r.th - 1u - row : row, col0, n_px, dst_plane, dst_stride, nz);
             }
         } else if constexpr (WIN) {
-            store_row<PLANAR, DT>(px, dp, row, col0, n_px, dst_plane, dst_stride, nz);
+            store_row<PLANAR, DT, NC>(px, dp, row, col0, n_px, dst_plane, dst_stride, nz);
         } else {
 #include "pjd_k_resize_store_body.h"
         }
     }
     if constexpr (ORI) {
         if (w.flags & PJD_RWI_TRANSPOSE)
-            store_cols<PLANAR, DT>(kept, dp, row0, r.th - row0 < PJD_RS_ROWS ? r.th - row0 : PJD_RS_ROWS, col0, n_px, (w.flags & PJD_RWI_YMIRROR) != 0, r.th, PAD ? cv.W : r.th, dst_plane, nz);
+            store_cols<PLANAR, DT, NC>(kept, dp, row0, r.th - row0 < PJD_RS_ROWS ? r.th - row0 : PJD_RS_ROWS, col0, n_px, (w.flags & PJD_RWI_YMIRROR) != 0, r.th, PAD ? cv.W : r.th, dst_plane, nz);
     }

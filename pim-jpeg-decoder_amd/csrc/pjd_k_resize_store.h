@@ -50,7 +50,8 @@ __device__ __forceinline__ uint32_t norm_pair16(uint32_t v0, uint32_t v1, float 
     return __builtin_bit_cast(uint32_t, __builtin_convertvector(u, bf16x2));
 }
 
-template <bool PLANAR, int DT>
+// NC: the channels stored, 3, or 1 only where PLANAR (a grey batch: one plane)
+template <bool PLANAR, int DT, int NC = 3>
 __device__ __forceinline__ void store_row(const uint32_t (&px)[3][PJD_RS_PX], uint8_t *dp, uint32_t row, uint32_t col0, uint32_t n_px,
                                           uint64_t dst_plane, uint32_t dst_stride, const NormArgs &nz)
 {
@@ -70,12 +71,13 @@ __device__ __forceinline__ void store_row(const uint32_t (&px)[3][PJD_RS_PX], ui
 // mirrored ragged tile: then only elements are stored, and only those of rows that exist).
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-template <bool PLANAR, int DT>
+template <bool PLANAR, int DT, int NC = 3>
 __device__ __forceinline__ void store_cols(const uint32_t (&px)[PJD_RS_ROWS][3][PJD_RS_PX], uint8_t *dp, uint32_t row0, uint32_t n_rows, uint32_t col0,
                                            uint32_t n_px, bool mirror, uint32_t r_th, uint32_t row_len, uint64_t dst_plane, const NormArgs &nz)
 {
     constexpr int R = PJD_RS_ROWS;
     static_assert(R == 8, "the packing below is written for eight rows");
+    static_assert(NC == 3 || (NC == 1 && PLANAR), "one channel is one plane");
     constexpr uint32_t ES = DT == 0 ? 1u : PJD_DT_SIZE(DT);
     const bool full = n_rows == (uint32_t)R;
     const int64_t jv = mirror ? (int64_t)r_th - (int64_t)row0 - R : (int64_t)row0;
@@ -85,14 +87,14 @@ __device__ __forceinline__ void store_cols(const uint32_t (&px)[PJD_RS_ROWS][3][
         const int64_t first = (int64_t)((uint64_t)(col0 + q) * row_len) + jv;          // in samples of one channel, from the picture's (plane's) start
         uint32_t v[3][R];                                  // D's order
 #pragma unroll
-        for (int c = 0; c < 3; c++)
+        for (int c = 0; c < NC; c++)
 #pragma unroll
             for (int m = 0; m < R; m++) v[c][m] = mirror ? px[R - 1 - m][c][q] : px[m][c][q];
         // element m is row (mirror ? 7 - m : m) of the tile
 #define PJD_COL_EXISTS(m) ((mirror ? (uint32_t)(R - 1 - (m)) : (uint32_t)(m)) < n_rows)
         if (PLANAR) {
 #pragma unroll
-            for (int c = 0; c < 3; c++) {
+            for (int c = 0; c < NC; c++) {
                 uint8_t *o = dp + ((int64_t)((uint64_t)c * dst_plane) + first) * (int64_t)ES;
                 if (DT == 0) {
                     if (full && ((uintptr_t)o & 7u) == 0) {

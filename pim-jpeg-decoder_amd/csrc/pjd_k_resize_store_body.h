@@ -2,12 +2,12 @@
 // rounded to 8 bits, leaves as uint8 or as normalised fp16 / bf16 / fp32 elements for row `row`, columns col0.. of the picture at dp.  The
 // widest store where the address has its alignment and all four pixels exist, element stores otherwise (pjd_batch_bind_output promises
 // element alignment, no more).  The body of store_row (pjd_k_resize_store.h); pjd_k_resize_body.h says who includes it directly.
-// In scope: PLANAR, DT (compile-time constants), px, dp, row, col0, n_px, dst_plane, dst_stride, nz (NormArgs; read only where DT != 0).
+// In scope: PLANAR, DT, NC (compile-time constants; NC: the planes a PLANAR picture has, 3 or 1), px, dp, row, col0, n_px, dst_plane, dst_stride, nz (NormArgs; read only where DT != 0).
         if constexpr (DT != 0) {
             constexpr uint32_t ES = PJD_DT_SIZE(DT);       // bytes per element
             if (PLANAR) {
 #pragma unroll
-                for (int c = 0; c < 3; c++) {
+                for (int c = 0; c < NC; c++) {
                     uint8_t *o = dp + ((uint64_t)c * dst_plane + (uint64_t)row * dst_stride + col0) * ES;
                     if (DT == PJD_DT_F32) {
                         if (n_px == PJD_RS_PX && ((uintptr_t)o & 15u) == 0) {
@@ -73,7 +73,7 @@
             }
         } else if (PLANAR) {
 #pragma unroll
-            for (int c = 0; c < 3; c++) {
+            for (int c = 0; c < NC; c++) {
                 uint8_t *o = dp + c * dst_plane + (uint64_t)row * dst_stride + col0;
                 if (n_px == PJD_RS_PX && ((uintptr_t)o & 3u) == 0)
                     *reinterpret_cast<uint32_t *>(o) = px[c][0] | (px[c][1] << 8) | (px[c][2] << 16) | (px[c][3] << 24);

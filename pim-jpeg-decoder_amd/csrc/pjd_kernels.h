@@ -74,6 +74,13 @@ void pjd_launch_idct_sweep(hipStream_t s, const PjdDevBatch &b);
 void pjd_launch_idct_std_lanes(hipStream_t s, const PjdDevBatch &b, const uint32_t *order, uint32_t n_wg, uint8_t *planes);
 void pjd_launch_idct_std_dense(hipStream_t s, const PjdDevBatch &b, const PjdDevIdctWg *wgs, const uint64_t *dense_base, uint32_t n_wg, uint8_t *planes);
 void pjd_launch_colour_std(hipStream_t s, const PjdDevBatch &b, const PjdDevIdctWg *cwgs, uint32_t n_wg, uint8_t *planes);
+// ---- back end of a PJD_OUT_GRAY8 batch (pjd_k_backend_gray.hip): the luma units alone, one plane.  Lane-stream input over order[k] (index
+// into iwgs / marks; null: the identity) or dense input (as for pjd_launch_idct_colour); the _std pair serves the PJD_F_LIBJPEG pictures
+// of such a batch and stores straight into the picture (no planes, no colour launch)
+void pjd_launch_idct_gray_lanes(hipStream_t s, const PjdDevBatch &b, const uint32_t *order, uint32_t n_wg, bool scaled);
+void pjd_launch_idct_gray(hipStream_t s, const PjdDevBatch &b, const PjdDevIdctWg *wgs, const uint64_t *dense_base, uint32_t n_wg, bool scaled);
+void pjd_launch_idct_gray_std_lanes(hipStream_t s, const PjdDevBatch &b, const uint32_t *order, uint32_t n_wg);
+void pjd_launch_idct_gray_std_dense(hipStream_t s, const PjdDevBatch &b, const PjdDevIdctWg *wgs, const uint64_t *dense_base, uint32_t n_wg);
 // ---- resize on decode (pjd_k_resize.hip): every picture of the batch from `src` (interleaved RGB8, or planar) to its target size in `dst`
 // (the same layout), one launch whatever the batch asked for; tile_prefix[i] = tiles of the pictures before i, tile_prefix[n_images] =
 // n_tiles.  norm.dtype != 0: the samples leave as fp16 / bf16 / fp32 elements, v * scale[c] + bias[c] (pjd_batch_set_normalize); the
@@ -96,6 +103,7 @@ struct PjdResizeLaunch {
     const uint32_t *tab;
     uint32_t lds_bytes;
     const PjdDevResizePad *pad;          // pjd_batch_set_resize_pad: null, or win is set too and pad[i] is picture i's canvas (the PAD kernels)
+    uint32_t channels = 3;               // 3, or 1 for a grey batch (PJD_OUT_GRAY8): planar, one plane, win and pad always set (the pjd_k_resize_gray kernels)
 };
 void pjd_launch_resize(hipStream_t s, const PjdResizeLaunch &a);
 // ... and the border of its padded pictures (pjd_k_resize_border): line_prefix[i] = canvas lines (rows interleaved, plane rows planar) of
@@ -109,6 +117,7 @@ struct PjdBorderLaunch {
     bool planar;
     uint32_t elem_bytes;
     PjdPadFill fill;
+    uint32_t channels = 3;               // 3, or 1 for a grey batch: planar with ONE plane, n_lines counts H lines a canvas and fill.d[0] alone is read
 };
 void pjd_launch_resize_border(hipStream_t s, const PjdBorderLaunch &a);
 // ---- stage-level parity (pjd_k_coefdump.hip): coefficients in the reference's MCU_buffer layout; `out` is zeroed by the caller

@@ -34,7 +34,14 @@ extern "C" uint64_t pjd_output_size(uint32_t width, uint32_t height, int out_for
 {
     if (out_format == PJD_OUT_BMP)   // reference src/bmp_writer.cpp:28-29 (its own padding rule: W % 4)
         return 26ull + (uint64_t)height * ((uint64_t)width * 3 + width % 4);
+    if (out_format == PJD_OUT_GRAY8) return (uint64_t)width * height;     // one plane
     return (uint64_t)width * height * 3;          // PJD_OUT_RGB8 and PJD_OUT_RGB8_PLANAR: the same bytes in another order
+}
+
+extern "C" int pjd_output_channels(int out_format)
+{
+    if (out_format == PJD_OUT_RGB8 || out_format == PJD_OUT_BMP || out_format == PJD_OUT_RGB8_PLANAR) return 3;
+    return out_format == PJD_OUT_GRAY8 ? 1 : 0;
 }
 
 // Reduced-size output (PJD_F_SCALE_*): ceil(W / s) x ceil(H / s), libjpeg's jdiv_round_up
@@ -162,7 +169,7 @@ int pjd_make_plan(const pjd_image_desc *images, int n, int out_format, PjdPlan &
                   uint32_t sub_bytes_override, int plan_mode)
 {
     if (n < 0 || (n > 0 && !images)) { err = "null image array"; return PJD_E_ARG; }
-    if (out_format != PJD_OUT_RGB8 && out_format != PJD_OUT_BMP && out_format != PJD_OUT_RGB8_PLANAR) { err = "unknown output format"; return PJD_E_ARG; }
+    if (pjd_output_channels(out_format) == 0) { err = "unknown output format"; return PJD_E_ARG; }
     P = PjdPlan();
     P.out_format = out_format;
     P.plan_mode = plan_mode == PJD_PLAN_THROUGHPUT ? PJD_PLAN_THROUGHPUT : PJD_PLAN_LATENCY;
@@ -297,6 +304,7 @@ int pjd_make_plan(const pjd_image_desc *images, int n, int out_format, PjdPlan &
         pjd_scaled_dims(d.width, d.height, d.flags, &sw, nullptr);
         if (out_format == PJD_OUT_BMP) { g.flags |= PJD_IF_BMP; g.out_stride = sw * 3 + sw % 4; }
         else if (out_format == PJD_OUT_RGB8_PLANAR) { g.flags |= PJD_IF_PLANAR; g.out_stride = sw; P.planar = true; }   // a plane row; plane = out_stride x output rows
+        else if (out_format == PJD_OUT_GRAY8) { g.flags |= PJD_IF_GRAY; g.out_stride = sw; P.gray = true; }                 // the one plane's row
         else g.out_stride = sw * 3;
         if (d.flags & PJD_F_SCALE_MASK) { g.flags |= ((d.flags & PJD_F_SCALE_MASK) >> 4) << PJD_IF_SCALE_SHIFT; P.scaled = true; }
         if (d.flags & PJD_F_STANDARD_RESTART) g.flags |= PJD_IF_STANDARD_RESTART;
@@ -608,7 +616,7 @@ int pjd_make_plan(const pjd_image_desc *images, int n, int out_format, PjdPlan &
             iwg_list.push_back(w);
         }
         g.n_iwg = (uint32_t)iwg_list.size() - g.iwg_base;
-        if (lj) {
+        if (lj && out_format != PJD_OUT_GRAY8) {         // a grey picture's luma rows go straight into the picture (pjd_k_backend_gray.hip)
             // component planes, whole MCUs: Y, then Cb and Cr of a three-component picture; the colour launch's items of four pixels
             g.plane_off256 = (uint32_t)(P.plane_bytes / 256);
             const uint64_t cpl = (uint64_t)g.mcux * 8 * g.mcuy * 8;

@@ -54,6 +54,7 @@ struct PjdPlan {
     uint64_t pixels = 0, ecs_bytes = 0, out_bytes = 0;   // pixels: of the source pictures; out_bytes: of the (scaled) output
     bool scaled = false;                   // some picture has an output scale (PJD_F_SCALE_*): the back end's scaled kernels
     bool planar = false;                   // PJD_OUT_RGB8_PLANAR: the back end's planar kernels
+    bool gray = false;                     // PJD_OUT_GRAY8: the grey back end (pjd_k_backend_gray.hip); its PJD_F_LIBJPEG pictures take no planes and no colour launch
     // PJD_F_LIBJPEG (pjd_k_backend_std.hip).  A batch that holds such a picture decodes as one chain of launches (no picture groups), and its
     // lane-stream back ends are launched over iwg_order: first the n_iwg_def ranges of the other pictures, then the n_iwg_std of the flagged
     bool libjpeg = false;

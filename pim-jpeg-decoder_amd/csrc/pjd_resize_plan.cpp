@@ -136,7 +136,7 @@ PjdResizeFault pjd_resize_resolve(const PjdResizeSpec &spec, PjdResizeWork &out)
             if (const char *f = pjd_resize_pad_fault(spec.out_w[i], spec.out_h[i], &p)) return fault_at((int)i, f);
             out.ct_w[i] -= p.left + p.right; out.ct_h[i] -= p.top + p.bottom;
             bordered[i] = p.left || p.top || p.right || p.bottom;
-            if (bordered[i]) lines += (uint64_t)(spec.planar ? 3u : 1u) * spec.out_h[i];
+            if (bordered[i]) lines += (uint64_t)(spec.planar ? spec.channels : 1u) * spec.out_h[i];
             form.padded = form.padded || bordered[i];
         }
     if (lines >= (1ull << 31)) return PjdResizeFault{"the canvases of this batch are too large for one launch", -1};
@@ -162,6 +162,8 @@ PjdResizeFault pjd_resize_resolve(const PjdResizeSpec &spec, PjdResizeWork &out)
             any_win = any_win || w.x || w.y || w.w || w.h || w.vw || w.vh || w.ox || w.oy || w.flags;
         }
     // the most general form a batch needs is the one it runs: a pad brings the oriented launch, an orientation the windowed one
+    // a grey batch has the padded kernels alone (pjd_k_resize.hip): a picture without a pad is its whole canvas, and has no border line
+    if (spec.channels == 1u) form.padded = true;
     form.oriented = form.oriented || form.padded;
     form.windowed = form.oriented || any_win;
 
@@ -181,9 +183,9 @@ PjdResizeFault pjd_resize_resolve(const PjdResizeSpec &spec, PjdResizeWork &out)
             out.win[i] = PjdDevResizeWin{w.x, w.y, w.w ? w.w : r.sw, w.h ? w.h : r.sh, w.vw ? w.vw : r.tw, w.vh ? w.vh : r.th, w.ox, w.oy, w.flags ^ ori[i], 0u};
         }
         if (form.padded) {
-            out.pad[i] = PjdDevResizePad{spec.out_w[i], spec.out_h[i], spec.pad[i].left, spec.pad[i].top, out.ct_w[i], out.ct_h[i], {0u, 0u}};
+            out.pad[i] = PjdDevResizePad{spec.out_w[i], spec.out_h[i], spec.pad_set ? spec.pad[i].left : 0u, spec.pad_set ? spec.pad[i].top : 0u, out.ct_w[i], out.ct_h[i], {0u, 0u}};
             out.line_prefix[i] = form.lines;
-            if (bordered[i]) form.lines += (spec.planar ? 3u : 1u) * spec.out_h[i];
+            if (bordered[i]) form.lines += (spec.planar ? spec.channels : 1u) * spec.out_h[i];
         }
     }
     out.tile_prefix[n] = form.tiles;
@@ -214,18 +216,18 @@ PjdResizeFault pjd_resize_resolve(const PjdResizeSpec &spec, PjdResizeWork &out)
             uint32_t e0, e1;                                // the tile's two ends in the table: mirrored where the window flips
             pjd_resize_win_ends(w, r.tw, c0, std::min(c0 + PJD_RS_COLS, r.tw) - 1u, e0, e1);
             const uint32_t h0 = out.tab[x.off + e0], h1 = out.tab[x.off + e1];
-            form.lds = std::max(form.lds, pjd_resize_aa_lds((h1 & 0xffffu) + (h1 >> 16) - (h0 & 0xffffu), spec.planar));
+            form.lds = std::max(form.lds, pjd_resize_aa_lds((h1 & 0xffffu) + (h1 >> 16) - (h0 & 0xffffu), spec.planar, spec.channels));
         }
     }
     return PjdResizeFault{};
 }
 
-PjdPackedLayout pjd_packed_layout(const uint32_t *w, const uint32_t *h, size_t n, uint64_t elem_bytes)
+PjdPackedLayout pjd_packed_layout(const uint32_t *w, const uint32_t *h, size_t n, uint64_t elem_bytes, uint32_t channels)
 {
     PjdPackedLayout l;
     l.off.resize(n); l.bytes.resize(n);
     for (size_t i = 0; i < n; i++) {
-        l.off[i] = l.buf_bytes; l.bytes[i] = 3ull * w[i] * h[i] * elem_bytes;
+        l.off[i] = l.buf_bytes; l.bytes[i] = (uint64_t)channels * w[i] * h[i] * elem_bytes;
         l.buf_bytes = (l.buf_bytes + l.bytes[i] + 255) & ~(uint64_t)255;
         l.sum += l.bytes[i];
     }

@@ -22,6 +22,7 @@ struct PjdResizePicture {
 struct PjdResizeSpec {
     std::vector<PjdResizePicture> pic;
     bool planar = false;
+    uint32_t channels = 3;                 // 3, or 1 for a grey batch (PJD_OUT_GRAY8): planar with one plane; it always resolves to the padded form
     std::vector<uint32_t> out_w, out_h;    // pjd_batch_set_resize: the delivered canvases
     bool pad_set = false, ori_set = false, win_set = false, filter_set = false;
     std::vector<pjd_resize_pad> pad;       // pjd_batch_set_resize_pad, as given
@@ -59,13 +60,13 @@ PjdResizeFault pjd_resize_resolve(const PjdResizeSpec &spec, PjdResizeWork &out)
 const char *pjd_resize_window_fault(uint32_t sw, uint32_t sh, uint32_t tw, uint32_t th, const pjd_resize_window *win, int filter);
 const char *pjd_resize_pad_fault(uint32_t out_w, uint32_t out_h, const pjd_resize_pad *pad);
 
-// The packed layout of a batch's results, as the planner lays out a batch's own buffer: n pictures of 3 * w * h elements of
+// The packed layout of a batch's results, as the planner lays out a batch's own buffer: n pictures of channels * w * h elements of
 // elem_bytes at 256-byte aligned offsets
 struct PjdPackedLayout {
     std::vector<uint64_t> off, bytes;
     uint64_t buf_bytes = 0, sum = 0;       // the buffer (what pjd_batch_packed_size reports); the pictures alone
 };
-PjdPackedLayout pjd_packed_layout(const uint32_t *w, const uint32_t *h, size_t n, uint64_t elem_bytes);
+PjdPackedLayout pjd_packed_layout(const uint32_t *w, const uint32_t *h, size_t n, uint64_t elem_bytes, uint32_t channels = 3);
 
 // binary32 -> one element of a PJD_DT_* type in the low bytes of a word: ONE rounding to nearest even for the 16-bit types (the
 // conversions of pjd_normalize_value, which the device makes in hardware)

@@ -223,7 +223,7 @@ int pjd_split_decode(const pjd_image_desc *desc, const int32_t *devices, int n_d
     std::memset(&st, 0, sizeof st);
     if (stats_out) *stats_out = st;
     if (!desc || !devices || n_devices <= 0 || n_devices > PJD_SPLIT_MAX_DEVICES || !out) return PJD_E_ARG;
-    if (out_format != PJD_OUT_RGB8 && out_format != PJD_OUT_BMP && out_format != PJD_OUT_RGB8_PLANAR) return PJD_E_ARG;
+    if (out_format != PJD_OUT_RGB8 && out_format != PJD_OUT_BMP && out_format != PJD_OUT_RGB8_PLANAR) return PJD_E_ARG;      // PJD_OUT_GRAY8 too: the row gather below has no one-plane form
     if (desc->flags & PJD_F_LIBJPEG) return PJD_E_ARG;         // its upsampling reads across the rows a rank decodes (include/pjd.h)
     const uint64_t out_bytes = pjd_image_output_size(desc, out_format);
     if (capacity < out_bytes) return PJD_E_ARG;

@@ -412,7 +412,7 @@ int run_pipe(Pipe &p, const pjd_pipe_opts *opts, pjd_pipe_stats *stats)
     if (p.o.scan_threads <= 0) p.o.scan_threads = 4;
     if (p.o.slots <= 0) p.o.slots = 3;
     if (p.o.sink_threads <= 0) p.o.sink_threads = 4;
-    if (p.o.out_format != PJD_OUT_BMP && p.o.out_format != PJD_OUT_RGB8 && p.o.out_format != PJD_OUT_RGB8_PLANAR) return PJD_E_ARG;
+    if (p.o.out_format != PJD_OUT_BMP && p.o.out_format != PJD_OUT_RGB8 && p.o.out_format != PJD_OUT_RGB8_PLANAR && p.o.out_format != PJD_OUT_GRAY8) return PJD_E_ARG;
     if (p.o.devices && p.o.n_devices > 0) {
         if (p.o.n_devices > PJD_PIPE_MAX_DEVICES) return PJD_E_ARG;
         // PJD_PIPE_ALLOW_DUP_DEVICES=1 (tests on a one-GPU box): the same ordinal may be listed several times and then counts as

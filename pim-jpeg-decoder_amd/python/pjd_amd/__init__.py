@@ -17,6 +17,7 @@ LIBPIPE = os.path.join(LIB_DIR, "libpjdpipe.so")
 
 OUT_RGB8, OUT_BMP = 0, 1
 OUT_RGB8_PLANAR = 2      # uint8[3][H][W]: the R, G and B planes one after the other (pjd.h)
+OUT_GRAY8 = 4            # uint8[H][W]: one plane, the luma as libjpeg's JCS_GRAYSCALE delivers it (pjd.h, "grey output"); 3 stays no format
 PLAN_LATENCY, PLAN_THROUGHPUT = 0, 1      # pjd_set_plan_mode
 F_STANDARD_RESTART, F_FORCE_SEQUENTIAL, F_STANDARD_ZIGZAG, F_PROGRESSIVE = 1, 2, 4, 8
 F_SCALE_1_2, F_SCALE_1_4, F_SCALE_1_8, F_SCALE_MASK = 16, 32, 48, 48      # output scale s = 1 << ((flags >> 4) & 3) (pjd.h)
@@ -236,6 +237,8 @@ def dev_lib():
         L.pjd_exec_dpu_payload.argtypes = [vp, vp, vp, i32]
         L.pjd_output_size.restype = C.c_uint64
         L.pjd_output_size.argtypes = [C.c_uint32, C.c_uint32, i32]
+        L.pjd_output_channels.restype = i32
+        L.pjd_output_channels.argtypes = [i32]
         L.pjd_scaled_dims.restype = i32
         L.pjd_scaled_dims.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.pjd_image_output_size.restype = C.c_uint64
@@ -426,7 +429,8 @@ class Batch:
         return int(self.L.pjd_batch_packed_size(self._h))
 
     def output_shape(self, i):
-        """Shape of picture i as download() returns it: (h, w, 3) for OUT_RGB8, (3, h, w) for OUT_RGB8_PLANAR, flat for OUT_BMP."""
+        """Shape of picture i as download() returns it: (h, w, 3) for OUT_RGB8, (3, h, w) for OUT_RGB8_PLANAR, (h, w) for OUT_GRAY8,
+        flat for OUT_BMP."""
         d = self._descs[i]
         if self._resize is not None:
             h, w = self._resize[i]
@@ -436,6 +440,8 @@ class Batch:
             return (h, w, 3)
         if self.out_format == OUT_RGB8_PLANAR:
             return (3, h, w)
+        if self.out_format == OUT_GRAY8:
+            return (h, w)
         return (self.output_size(i),)
 
     def set_resize(self, sizes):
@@ -903,6 +909,11 @@ def scaled_dims(width, height, flags=0):
     w, h = C.c_uint32(), C.c_uint32()
     L.pjd_scaled_dims(int(width), int(height), int(flags), C.byref(w), C.byref(h))
     return w.value, h.value
+
+
+def output_channels(out_format):
+    """pjd_output_channels (host only): 3 for OUT_RGB8, OUT_BMP and OUT_RGB8_PLANAR, 1 for OUT_GRAY8, 0 for a value that is no format."""
+    return int(dev_lib().pjd_output_channels(int(out_format)))
 
 
 def image_output_size(desc, out_format=OUT_RGB8):

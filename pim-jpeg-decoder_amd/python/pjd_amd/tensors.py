@@ -125,13 +125,36 @@ def _run(ctx, descs, out_format, capacity, offsets, device, resize=None, normali
     return buf, offs, st
 
 
-def decode_to_tensors(ctx, descs, planar=True, device=None, orientations=None, libjpeg=False):
+def _gray_layout(gray, planar=True):
+    """The `gray` keyword, checked before anything is created: one plane has no interleaved form."""
+    if gray and not planar:
+        raise ValueError("gray=True takes planar=True (and no channels_last): one plane has no interleaved form")
+
+
+def _gray3(v, what):
+    """A per-channel argument of a gray=True call -- one number, or a sequence of length 1 (or 3: entries [1] and [2] are ignored, as the
+    library ignores them) -- as the three entries the C ABI takes."""
+    if isinstance(v, (int, float)):
+        return [v, v, v]
+    v = list(v)
+    if len(v) == 1:
+        return [v[0]] * 3
+    if len(v) != 3:
+        raise ValueError(f"{what}: with gray=True one number, or a sequence of length 1 (or 3)")
+    return v
+
+
+def decode_to_tensors(ctx, descs, planar=True, device=None, orientations=None, libjpeg=False, gray=False):
     """Decode `descs` on `ctx` into ONE torch.uint8 buffer on the context's device -> (list of tensors, statuses).  Tensor i is
     a view of that buffer shaped (3, sh, sw) -- or (sh, sw, 3) with planar=False -- at the picture's output scale.  The tensors
     are complete on return and may be read on any torch stream (module docstring, "Stream order").
     orientations=[1..8, ...] (Scanned.orientation): every picture comes out upright, at its own size -- (3, sw, sh) for 5..8 --, the
     exact permutation of the decoded picture (the identity resample of Batch.set_resize with Batch.set_orientation).  None: as the file
-    stores them.  libjpeg=True: the pictures are libjpeg's, byte for byte (F_LIBJPEG on copies of the descriptors)."""
+    stores them.  libjpeg=True: the pictures are libjpeg's, byte for byte (F_LIBJPEG on copies of the descriptors).
+    gray=True: one plane per picture (OUT_GRAY8: the luma, what libjpeg's JCS_GRAYSCALE delivers with libjpeg=True), views shaped
+    (1, sh, sw) -- (1, sw, sh) for orientations 5..8 --; a third of the bytes.  It takes planar=True (ValueError before anything is created
+    otherwise)."""
+    _gray_layout(gray, planar)
     descs = _libjpeg(descs, libjpeg)
     torch = _torch()
     device = torch.device("cuda", ctx.device) if device is None else device
@@ -139,26 +162,30 @@ def decode_to_tensors(ctx, descs, planar=True, device=None, orientations=None, l
     if orientations is not None:
         _orientations(orientations, len(descs))
         sizes = [orient_hw(o, *output_hw(d)) for o, d in zip(orientations, descs)]
-    buf, offs, st = _run(ctx, descs, pjd_amd.OUT_RGB8_PLANAR if planar else pjd_amd.OUT_RGB8, None, None, device, resize=sizes,
-                         orientations=orientations)
+    fmt = pjd_amd.OUT_GRAY8 if gray else (pjd_amd.OUT_RGB8_PLANAR if planar else pjd_amd.OUT_RGB8)
+    buf, offs, st = _run(ctx, descs, fmt, None, None, device, resize=sizes, orientations=orientations)
     out = []
+    nc = 1 if gray else 3
     for i, (d, off) in enumerate(zip(descs, offs)):
         h, w = output_hw(d) if sizes is None else sizes[i]
-        flat = buf[off:off + 3 * h * w]
-        out.append(flat.view(3, h, w) if planar else flat.view(h, w, 3))
+        flat = buf[off:off + nc * h * w]
+        out.append(flat.view(nc, h, w) if planar else flat.view(h, w, 3))
     return out, st
 
 
-def decode_to_batch_tensor(ctx, descs, device=None, libjpeg=False):
+def decode_to_batch_tensor(ctx, descs, device=None, libjpeg=False, gray=False):
     """Pictures of ONE output size -> (uint8 tensor [N, 3, H, W], statuses): picture i is bound at offset i * 3 * H * W, so the
     result is one contiguous NCHW tensor with no copy after the decode, complete on return and readable on any torch stream.
-    ValueError (before anything is created) otherwise.  libjpeg=True: as in decode_to_tensors."""
+    ValueError (before anything is created) otherwise.  libjpeg=True: as in decode_to_tensors.  gray=True: [N, 1, H, W] (OUT_GRAY8),
+    picture i at offset i * H * W."""
     descs = _libjpeg(descs, libjpeg)
     n, c, h, w = uniform_output_shape(descs)
+    if gray:
+        c = 1
     torch = _torch()
     device = torch.device("cuda", ctx.device) if device is None else device
     size = c * h * w
-    buf, _, st = _run(ctx, descs, pjd_amd.OUT_RGB8_PLANAR, n * size, [i * size for i in range(n)], device)
+    buf, _, st = _run(ctx, descs, pjd_amd.OUT_GRAY8 if gray else pjd_amd.OUT_RGB8_PLANAR, n * size, [i * size for i in range(n)], device)
     return buf.view(n, c, h, w), st
 
 
@@ -378,9 +405,9 @@ def letterbox_plan(src_hw, size, mode="center"):
     return ch, cw, left, top, W - cw - left, H - ch - top
 
 
-def _fill(fill):
-    """The `fill` keyword of the letterboxing helpers: three bytes."""
-    fill = tuple(fill)
+def _fill(fill, gray=False):
+    """The `fill` keyword of the letterboxing helpers: three bytes; with gray=True one byte (a number or a sequence of length 1) will do."""
+    fill = tuple(_gray3(fill, "fill") if gray else fill)
     if len(fill) != 3 or any(int(v) != v or not 0 <= int(v) <= 255 for v in fill):
         raise ValueError("fill: three bytes (R, G, B), each 0..255")
     return tuple(int(v) for v in fill)
@@ -439,7 +466,7 @@ def _interpolation(name):
 
 
 def decode_resized_batch_tensor(ctx, descs, size, prescale=True, device=None, antialias=False, crops=None, flips=None, resize_short=None,
-                                interpolation="bilinear", orientations=None, libjpeg=False, letterbox=None, fill=(0, 0, 0)):
+                                interpolation="bilinear", orientations=None, libjpeg=False, letterbox=None, fill=(0, 0, 0), gray=False):
     """Pictures of ANY sizes -> (uint8 tensor [N, 3, H, W], statuses), size = (H, W): every picture is resampled to H x W inside
     the decode (the bilinear filter of include/pjd.h, pjd_batch_set_resize) and lands at offset i * 3 * H * W of one buffer, so
     the result is one contiguous NCHW tensor with no copy after the decode, complete on return and readable on any torch stream
@@ -473,23 +500,27 @@ def decode_resized_batch_tensor(ctx, descs, size, prescale=True, device=None, an
     letterbox="center" | "topleft": every picture keeps its aspect ratio inside the H x W canvas (letterbox_plan of the UPRIGHT picture,
     or of its crop) and the rest of the canvas is `fill` (three bytes; YOLO: 114) -- Batch.set_resize_pad, in the same launch and one
     small one behind it.  crops and orientations work as above against the content size, flips mirror the content inside its
-    rectangle, the pre-scale is picked from the content size; resize_short is excluded (ValueError).  None: today's behaviour."""
+    rectangle, the pre-scale is picked from the content size; resize_short is excluded (ValueError).  None: today's behaviour.
+    gray=True: uint8 [N, 1, H, W] (OUT_GRAY8: the luma plane -- with libjpeg=True what libjpeg's JCS_GRAYSCALE delivers -- through the same
+    filters: channel 0 of what they make of the picture with neutral chroma); every other keyword composes as without it, and `fill` may
+    be one byte."""
     _interpolation(interpolation)
     if len(descs) == 0:
         raise ValueError("decode_resized_batch_tensor: no pictures")
     descs = _libjpeg(descs, libjpeg, prescale)
     th, tw = int(size[0]), int(size[1])
-    fill, pads = _fill(fill), None
+    fill, pads = _fill(fill, gray), None
     if letterbox is not None:
         run, windows, oris, pads = _plan_letterbox(descs, (th, tw), letterbox, prescale, crops, flips, resize_short, orientations)
     else:
         run, windows, oris = _plan(descs, (th, tw), prescale, crops, flips, resize_short, orientations)
     torch = _torch()
     device = torch.device("cuda", ctx.device) if device is None else device
-    n, plane = len(descs), 3 * th * tw
-    buf, _, st = _run(ctx, run, pjd_amd.OUT_RGB8_PLANAR, n * plane, [i * plane for i in range(n)], device, resize=[(th, tw)] * n,
+    nc = 1 if gray else 3
+    n, plane = len(descs), nc * th * tw
+    buf, _, st = _run(ctx, run, pjd_amd.OUT_GRAY8 if gray else pjd_amd.OUT_RGB8_PLANAR, n * plane, [i * plane for i in range(n)], device, resize=[(th, tw)] * n,
                       antialias=antialias, windows=windows, interpolation=interpolation, orientations=oris, pads=pads, fill=fill)
-    return buf.view(n, 3, th, tw), st
+    return buf.view(n, nc, th, tw), st
 
 
 def normalize_constants(mean, std):
@@ -506,7 +537,7 @@ def normalize_constants(mean, std):
 
 def decode_normalized_batch_tensor(ctx, descs, size, mean, std, dtype=None, channels_last=False, prescale=True, device=None,
                                    antialias=False, crops=None, flips=None, resize_short=None, interpolation="bilinear", orientations=None,
-                                   libjpeg=False, letterbox=None, fill=(0, 0, 0), pad_value=None):
+                                   libjpeg=False, letterbox=None, fill=(0, 0, 0), pad_value=None, gray=False):
     """Pictures of ANY sizes -> (tensor of `dtype` [N, 3, H, W], statuses), size = (H, W); dtype torch.float16 (the default),
     torch.bfloat16 or torch.float32.  As decode_resized_batch_tensor, and every sample v of channel c leaves the same launch as
     fma(v, scale[c], bias[c]) with the constants of normalize_constants(mean, std), converted once to `dtype` (include/pjd.h,
@@ -521,14 +552,20 @@ def decode_normalized_batch_tensor(ctx, descs, size, mean, std, dtype=None, chan
     limit; any other string than "bilinear" or "bicubic" raises ValueError before anything is created.  orientations, libjpeg: as in
     decode_resized_batch_tensor.  letterbox, fill: as there; the border is normalised like every other sample (fill=(124, 116, 104) is
     about the ImageNet mean colour), unless pad_value -- one number or three -- is given: the border elements are then exactly that
-    (Batch.set_pad_value; pad_value=0 is "zeros after normalisation": DETR, SAM).  pad_value without letterbox raises ValueError."""
+    (Batch.set_pad_value; pad_value=0 is "zeros after normalisation": DETR, SAM).  pad_value without letterbox raises ValueError.
+    gray=True: [N, 1, H, W] of `dtype` (OUT_GRAY8): fma(v, scale[0], bias[0]) of the luma plane; mean and std may be one number or a
+    sequence of length 1, fill and pad_value one number; it takes channels_last=False (one plane has no interleaved form)."""
     _interpolation(interpolation)
+    _gray_layout(gray, not channels_last)
     if len(descs) == 0:
         raise ValueError("decode_normalized_batch_tensor: no pictures")
     descs = _libjpeg(descs, libjpeg, prescale)
     th, tw = int(size[0]), int(size[1])
+    if gray:
+        mean, std = _gray3(mean, "mean"), _gray3(std, "std")
+        pad_value = None if pad_value is None else _gray3(pad_value, "pad_value")
     scale, bias = normalize_constants(mean, std)
-    fill, pad_value, pads = _fill(fill), _pad_value(pad_value), None
+    fill, pad_value, pads = _fill(fill, gray), _pad_value(pad_value), None
     if pad_value is not None and letterbox is None:
         raise ValueError("pad_value needs letterbox: without it there is no border")
     plan = None
@@ -543,9 +580,10 @@ def decode_normalized_batch_tensor(ctx, descs, size, mean, std, dtype=None, chan
     dt, es = dts[dtype]
     device = torch.device("cuda", ctx.device) if device is None else device
     run, windows, oris = plan if plan is not None else _plan(descs, (th, tw), prescale, crops, flips, resize_short, orientations)
-    n, pic = len(descs), 3 * th * tw * es
-    buf, _, st = _run(ctx, run, pjd_amd.OUT_RGB8 if channels_last else pjd_amd.OUT_RGB8_PLANAR, n * pic, [i * pic for i in range(n)], device,
+    nc = 1 if gray else 3
+    n, pic = len(descs), nc * th * tw * es
+    buf, _, st = _run(ctx, run, pjd_amd.OUT_GRAY8 if gray else pjd_amd.OUT_RGB8 if channels_last else pjd_amd.OUT_RGB8_PLANAR, n * pic, [i * pic for i in range(n)], device,
                       resize=[(th, tw)] * n, normalize=(dt, scale, bias), antialias=antialias, windows=windows, interpolation=interpolation,
                       orientations=oris, pads=pads, fill=fill, pad_value=pad_value)
     t = buf.view(dtype)
-    return (t.view(n, th, tw, 3).permute(0, 3, 1, 2) if channels_last else t.view(n, 3, th, tw)), st
+    return (t.view(n, th, tw, 3).permute(0, 3, 1, 2) if channels_last else t.view(n, nc, th, tw)), st

@@ -65,6 +65,7 @@ template <bool PLANAR, int DT, bool WIN, bool ORI, bool PAD>
 static void thread_bilinear(const uint8_t *src, uint8_t *dst, const PjdDevResize *recs, const PjdDevResizeWin *win, const PjdDevResizePad *pad,
                             const uint32_t *tile_prefix, uint32_t n_images, uint32_t n_tiles, const NormArgs nz)
 {
+    constexpr int NC = 3;                                  // the kernels' channel count: three-channel pictures here
 #include "../pim-jpeg-decoder_amd/csrc/pjd_k_resize_body.h"
 }
 
@@ -73,6 +74,7 @@ static void thread_aa(uint32_t *seg, const uint8_t *src, uint8_t *dst, const Pjd
                       const uint32_t *tile_prefix, uint32_t n_images, uint32_t n_tiles, const PjdDevResizeAA *aa, const uint32_t *tab, uint32_t lds_bytes,
                       const NormArgs nz)
 {
+    constexpr int NC = 3;                                  // the kernels' channel count: three-channel pictures here
 #include "../pim-jpeg-decoder_amd/csrc/pjd_k_resize_aa_body.h"
 }
 
