@@ -163,6 +163,7 @@ int pool_pin_alloc(pjd_ctx *ctx, void **out, size_t bytes, std::vector<PoolBlock
 struct pjd_batch {
     pjd_ctx *ctx = nullptr;
     PjdPlan plan;
+    PjdBackForm back{};                  // the form of the plan's back end (pjd_kernels.h), set once by pjd_batch_create
     PjdDevBatch dev{};
     // owned device allocations (non-const views of what `dev` points to)
     PjdDevImage *d_images = nullptr;
@@ -226,19 +227,21 @@ struct pjd_batch {
     bool pad_value_set = false;                  // pjd_batch_set_pad_value
     float pad_value[3] = {0, 0, 0};
 
-    // the resample launch of this batch, whatever its filter and form (both launch sites: the decode and the re-run after the fallback)
-    void launch_resize(hipStream_t s, bool planar) const
+    // the resample launch of this batch, whatever its filter and form
+    void launch_resize(hipStream_t s) const
     {
         const size_t n = dev.n_images;
+        const bool planar = back.planes();
         pjd_launch_resize(s, PjdResizeLaunch{dev.out, res_out, (const PjdDevResize *)rs.d, (const uint32_t *)(rs.d + n * sizeof(PjdDevResize)), dev.n_images, form.tiles, planar, norm,
                                              form.windowed ? (const PjdDevResizeWin *)win.d : nullptr, form.oriented, spec.filter,
                                              (const PjdDevResizeAA *)aa.d, aa.d ? (const uint32_t *)(aa.d + n * sizeof(PjdDevResizeAA)) : nullptr, form.lds,
                                              form.padded ? (const PjdDevResizePad *)pad.d : nullptr, spec.channels});
     }
-    // ... and the border of its padded pictures, behind it (the same two sites): the two write disjoint bytes
-    void launch_pad(hipStream_t s, bool planar) const
+    // ... and the border of its padded pictures, behind it: the two write disjoint bytes
+    void launch_pad(hipStream_t s) const
     {
         const size_t n = dev.n_images;
+        const bool planar = back.planes();
         pjd_launch_resize_border(s, PjdBorderLaunch{res_out, (const PjdDevResize *)rs.d, (const PjdDevResizePad *)pad.d, (const uint32_t *)(pad.d + n * sizeof(PjdDevResizePad)), dev.n_images,
                                                     form.lines, planar, norm.dtype ? PJD_DT_SIZE(norm.dtype) : 1u, pjd_pad_fill(norm, planar, pad_fill, pad_value_set ? pad_value : nullptr), spec.channels});
     }
@@ -442,6 +445,7 @@ int pjd_batch_create(pjd_ctx *ctx, const pjd_image_desc *images, int n_images, i
     rc = PJD_OK;
     auto fail = [&](int code) { pjd_batch_destroy(b); return code; };
     b->seq_list = P.seq_images;
+    b->back = PjdBackForm{P.gray ? PJD_BACK_GRAY : (P.planar ? PJD_BACK_PLANAR : PJD_BACK_INTERLEAVED), P.scaled};
     std::vector<uint64_t> seq_base;
     std::vector<int32_t> st0(P.images.size(), 0);
     for (uint32_t i : b->seq_list) { st0[i] = PJD_STW_NEEDS_EXACT; seq_base.push_back(P.images[i].dense_base); }
@@ -644,6 +648,27 @@ bool ctx_group_streams(pjd_ctx *ctx, size_t ng)
     return true;
 }
 
+// Dense input: the ranges of the form's default kernel, then those of the PJD_F_LIBJPEG pictures (none: no launch) -- the exact path of
+// a decode and the fallback of settle(), which brings a scratch (dv.coef) and lists of its own
+void launch_dense(hipStream_t s, const pjd_batch *b, const PjdDevBatch &dv, const PjdDevIdctWg *wgs, size_t n, const PjdDevIdctWg *wgs_std, size_t n_std,
+                  const uint64_t *dense_base)
+{
+    pjd_launch_idct_dense(s, dv, b->back, wgs, dense_base, (uint32_t)n);
+    pjd_launch_idct_std_dense(s, dv, b->back, wgs_std, dense_base, (uint32_t)n_std, b->d_planes);
+}
+
+// Resize on decode: every picture from the intermediate (dev.out) to its target size in the result buffer, one launch, then the border
+// of the padded pictures (a pad is set on a resize only).  kt: null, or the timed decode's marks.
+void launch_resample(hipStream_t s, const pjd_batch *b, KernelTimer *kt)
+{
+    if (!b->resized) return;
+    b->launch_resize(s);
+    if (kt) kt->mark("resize");
+    if (!b->form.padded) return;
+    b->launch_pad(s);
+    if (kt) kt->mark("pad");
+}
+
 int enqueue_decode(pjd_batch *b, pjd_timings *timings, bool use_groups)
 {
     pjd_ctx *ctx = b->ctx;
@@ -670,7 +695,8 @@ int enqueue_decode(pjd_batch *b, pjd_timings *timings, bool use_groups)
     // "pull": the pull launch has no scaled and no planar form.
     static const int idle_form = [] { const char *e = std::getenv("PJD_IDLE_FORM"); return !e ? 1 : (!std::strcmp(e, "pull") ? 2 : (!std::strcmp(e, "chain") ? 0 : 1)); }();
     const bool idle = !timings && use_groups && parallel && !P.groups.empty() && idle_form != 0;       // per-kernel timing: one chain, kernel after kernel
-    const bool no_pull = P.scaled || P.planar || P.gray;
+    const PjdBackForm F = b->back;
+    const bool no_pull = !F.has_pull();
     const size_t ng = (idle && (idle_form == 1 || no_pull)) ? P.groups.size() : 0;
     const bool grouped = ng > 1 && ctx_group_streams(ctx, ng);
     if (idle && idle_form == 2 && !no_pull && ctx_group_streams(ctx, 2)) {
@@ -698,8 +724,7 @@ int enqueue_decode(pjd_batch *b, pjd_timings *timings, bool use_groups)
             if (g) HIP_TRY(ctx, hipStreamWaitEvent(gs, ctx->fork_ev, 0));
             pjd_launch_huff_lanes_group(gs, b->dev, P.groups[g], (uint32_t)g);
             pjd_launch_group_dc(gs, b->dev, P.groups[g]);
-            if (P.gray) pjd_launch_idct_gray_lanes(gs, b->dev, b->dev.iwg_order + P.groups[g].iwg_first, P.groups[g].iwg_count, P.scaled);
-            else pjd_launch_group_idct(gs, b->dev, P.groups[g], P.scaled, P.planar);
+            pjd_launch_idct_lanes(gs, b->dev, F, b->dev.iwg_order + P.groups[g].iwg_first, P.groups[g].iwg_count);
             if (g) { HIP_TRY(ctx, hipEventRecord(ctx->join_ev[g - 1], gs)); }
         }
         for (size_t g = 1; g < ng; g++) HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->join_ev[g - 1], 0));
@@ -707,22 +732,11 @@ int enqueue_decode(pjd_batch *b, pjd_timings *timings, bool use_groups)
         if (parallel) {
             pjd_launch_huff_lanes(s, b->dev);    kt.mark("huff_lanes");
             pjd_launch_lane_dc_scan(s, b->dev, P.dc_per_picture);  kt.mark("dc_scan");
-            if (P.gray) {
-                // a grey batch: the luma units alone (pjd_k_backend_gray.hip); its flagged pictures store their rows themselves
-                pjd_launch_idct_gray_lanes(s, b->dev, P.libjpeg ? b->dev.iwg_order : nullptr, P.libjpeg ? P.n_iwg_def : b->dev.n_iwg, P.scaled);
-                kt.mark("idct_gray");
-                if (P.n_iwg_std) { pjd_launch_idct_gray_std_lanes(s, b->dev, b->dev.iwg_order + P.n_iwg_def, P.n_iwg_std); kt.mark("idct_gray_std"); }
-            } else {
-            if (!P.libjpeg) pjd_launch_idct_colour_lanes(s, b->dev, P.scaled, P.planar);
-            else {
-                // the ranges of the unflagged pictures through the default kernels, those of the flagged ones into their planes
-                PjdDevGroup def{};
-                def.iwg_first = 0; def.iwg_count = P.n_iwg_def;
-                pjd_launch_group_idct(s, b->dev, def, P.scaled, P.planar);
-            }
-            kt.mark("idct_colour");
-            if (P.n_iwg_std) { pjd_launch_idct_std_lanes(s, b->dev, b->dev.iwg_order + P.n_iwg_def, P.n_iwg_std, b->d_planes); kt.mark("idct_std"); }
-            }
+            // a batch with PJD_F_LIBJPEG pictures: the ranges of the others come first in iwg_order and go through the form's default
+            // kernel, those of the flagged ones into their planes (a grey batch: straight into the picture)
+            pjd_launch_idct_lanes(s, b->dev, F, P.libjpeg ? b->dev.iwg_order : nullptr, P.libjpeg ? P.n_iwg_def : b->dev.n_iwg);
+            kt.mark(F.gray() ? "idct_gray" : "idct_colour");
+            if (P.n_iwg_std) { pjd_launch_idct_std_lanes(s, b->dev, F, b->dev.iwg_order + P.n_iwg_def, P.n_iwg_std, b->d_planes); kt.mark(F.gray() ? "idct_gray_std" : "idct_std"); }
         }
     }
     if (!b->seq_list.empty()) {
@@ -730,27 +744,15 @@ int enqueue_decode(pjd_batch *b, pjd_timings *timings, bool use_groups)
         pjd_launch_zero(s, b->dev.coef, P.dense_du * 64 * sizeof(int16_t));      // a kernel, not a memset node: see the reset above
         pjd_launch_huff_sequential(s, b->dev, b->d_seq_list, b->d_seq_base, (uint32_t)b->seq_list.size());
         if (!P.pscans.empty()) pjd_launch_progressive(s, b->dev, b->d_seq_list, b->d_seq_base, (uint32_t)b->seq_list.size());
-        if (P.gray) {
-            pjd_launch_idct_gray(s, b->dev, b->d_iwgs_dense, b->d_seq_base, (uint32_t)P.iwgs_dense.size(), P.scaled);
-            if (P.libjpeg) pjd_launch_idct_gray_std_dense(s, b->dev, b->d_iwgs_dense_std, b->d_seq_base, (uint32_t)P.iwgs_dense_std.size());
-        } else {
-        pjd_launch_idct_colour(s, b->dev, b->d_iwgs_dense, b->d_seq_base, (uint32_t)P.iwgs_dense.size(), P.scaled, P.planar);
-        if (P.libjpeg) pjd_launch_idct_std_dense(s, b->dev, b->d_iwgs_dense_std, b->d_seq_base, (uint32_t)P.iwgs_dense_std.size(), b->d_planes);
-        }
+        launch_dense(s, b, b->dev, b->d_iwgs_dense, P.iwgs_dense.size(), b->d_iwgs_dense_std, P.iwgs_dense_std.size(), b->d_seq_base);
         kt.mark("exact_path");
     }
-    if (P.libjpeg && !P.gray) {
+    if (P.libjpeg && !F.gray()) {
         // the flagged pictures' planes are complete, whichever front end filled them: upsample, colour, store
         pjd_launch_colour_std(s, b->dev, b->d_cwgs_std, (uint32_t)P.cwgs_std.size(), b->d_planes);
         kt.mark("colour_std");
     }
-    if (b->resized) {
-        // resize on decode: every picture from the intermediate (dev.out) to its target size in the result buffer, one launch behind
-        // whatever form the back end took (the groups' streams have joined `s` above)
-        b->launch_resize(s, P.planar || P.gray);
-        kt.mark("resize");
-        if (b->form.padded) { b->launch_pad(s, P.planar || P.gray); kt.mark("pad"); }
-    }
+    launch_resample(s, b, &kt);          // behind whatever form the back end took (the groups' streams have joined `s` above)
     HIP_TRY(ctx, hipGetLastError());
     kt.finish();
     b->decoded = true;
@@ -834,20 +836,12 @@ int settle(pjd_batch *b)
         if (e == hipSuccess) {
             if (ev0) (void)hipEventRecord(ev0, s);
             pjd_launch_huff_sequential(s, dv, d_list, d_base, (uint32_t)fb.size());
-            if (P.gray) {
-                pjd_launch_idct_gray(s, dv, d_wgs, d_base, (uint32_t)n_def, P.scaled);
-                pjd_launch_idct_gray_std_dense(s, dv, d_wgs + n_def, d_base, (uint32_t)n_std);
-            } else
-            pjd_launch_idct_colour(s, dv, d_wgs, d_base, (uint32_t)n_def, P.scaled, P.planar);
-            if (n_std && !P.gray) {
-                // flagged pictures: their planes again, then the colour launch (all flagged pictures of the batch: a rare path)
-                pjd_launch_idct_std_dense(s, dv, d_wgs + n_def, d_base, (uint32_t)n_std, b->d_planes);
-                pjd_launch_colour_std(s, dv, b->d_cwgs_std, (uint32_t)P.cwgs_std.size(), b->d_planes);
-            }
+            launch_dense(s, b, dv, d_wgs, n_def, d_wgs + n_def, n_std, d_base);
+            // flagged pictures had their planes filled again: the colour launch (all flagged pictures of the batch: a rare path)
+            if (n_std && !b->back.gray()) pjd_launch_colour_std(s, dv, b->d_cwgs_std, (uint32_t)P.cwgs_std.size(), b->d_planes);
             if (ev1) (void)hipEventRecord(ev1, s);
             // the pictures just decoded again changed in the intermediate: resample (the whole batch: a rare path)
-            if (b->resized) b->launch_resize(s, P.planar || P.gray);
-            if (b->form.padded) b->launch_pad(s, P.planar || P.gray);
+            launch_resample(s, b, nullptr);
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipMemcpyAsync(b->h_status, b->dev.status, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s);
@@ -1126,10 +1120,10 @@ int pjd_batch_set_resize(pjd_batch *b, const uint32_t *out_w, const uint32_t *ou
     const size_t n = P.images.size();
     // the request: every picture from where the back end wrote it at its decode size to the packed layout of the result buffer
     // (256-byte aligned offsets, as the planner lays out a batch's own buffer; pjd_batch_bind_output may still change them)
-    const uint32_t channels = P.gray ? 1u : 3u;            // a grey batch is a planar batch with one plane
+    const uint32_t channels = b->back.gray() ? 1u : 3u;    // a grey batch is a planar batch with one plane
     const PjdPackedLayout lay = pjd_packed_layout(out_w, out_h, n, 1, channels);
     PjdResizeSpec spec;
-    spec.planar = P.planar || P.gray;
+    spec.planar = b->back.planes();
     spec.channels = channels;
     spec.out_w.assign(out_w, out_w + n); spec.out_h.assign(out_h, out_h + n);
     size_t shard = n;                                      // the first shard of the batch

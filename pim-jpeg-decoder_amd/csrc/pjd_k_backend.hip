@@ -14,6 +14,10 @@
 //   pjd_k_idct_colour_lanes_planar / pjd_k_idct_colour_planar
 //                       the same two for a PJD_OUT_RGB8_PLANAR batch: R, G and B go to three planes (uint8[3][H][W]); kernels of
 //                       their own, so that the interleaved ones keep their code
+// What these kernels share with the other two back-end units stands once, in pjd_k_backend_common.h (LDS block, MCU positions, the two
+// IDCT passes) and in the bodies they include (pjd_k_lanes_parse_body.h, pjd_k_lanes_dc_body.h, pjd_k_idct_dense_body.h with
+// pjd_k_dense_stage_body.h).  pjd_launch_idct_lanes and pjd_launch_idct_dense pick the kernel of a batch's form (PjdBackForm), the grey
+// unit's included.
 //
 // Integer work bound by VALU instruction issue (profiles/r03_cfg3.md: valu_issue_frac 1.0 -- the entry parser is its largest
 // phase), not by HBM: coefficients are read once with 16-byte loads, tiles live in LDS (row stride 144 B so that the column
@@ -255,27 +259,6 @@ __global__ __launch_bounds__(256) void pjd_k_lane_dc_carry(PjdDevBatch B)
     }
 }
 
-__device__ __forceinline__ void pjd_tile_row(int16_t (*tile)[TILE_STRIDE], uint32_t du, uint32_t r)
-{
-    int4 raw = *reinterpret_cast<const int4 *>(&tile[du][r * 8]);
-    int16_t *rv = reinterpret_cast<int16_t *>(&raw);
-    int o[8];
-    pjd_idct8(rv[0], rv[1], rv[2], rv[3], rv[4], rv[5], rv[6], rv[7], o);
-#pragma unroll
-    for (int j = 0; j < 8; j++) rv[j] = (int16_t)o[j];
-    *reinterpret_cast<int4 *>(&tile[du][r * 8]) = raw;
-}
-
-__device__ __forceinline__ void pjd_tile_col(int16_t (*tile)[TILE_STRIDE], uint32_t du, uint32_t c)
-{
-    int x[8], o[8];
-#pragma unroll
-    for (int j = 0; j < 8; j++) x[j] = tile[du][j * 8 + c];
-    pjd_idct8(x[0], x[1], x[2], x[3], x[4], x[5], x[6], x[7], o);
-#pragma unroll
-    for (int j = 0; j < 8; j++) tile[du][j * 8 + c] = (int16_t)o[j];
-}
-
 // Row pass, column pass, chroma upsample + colour + raster store for the data units staged in `tile`
 // (natural order, dequantised).  Shared by the sparse and the dense front ends.
 // DO_IDCT = false: the caller has already run both passes on every unit (and this function's first barrier is
@@ -288,10 +271,7 @@ template <bool DO_IDCT, bool SCALED, bool PLANAR = false>
 __device__ __forceinline__ void pjd_tile_to_pixels(int16_t (*tile)[TILE_STRIDE], uint32_t *mcu_xy, const PjdDevBatch &B,
                                                    const PjdDevImage &im, const PjdDevIdctWg &wg, uint32_t tid)
 {
-    if (tid < wg.n_mcu) {                                   // grid position of each MCU: the only divisions
-        const uint32_t m = wg.first_mcu + tid, my = m / im.mcux;
-        mcu_xy[tid] = (my << 16) | (m - my * im.mcux);
-    }
+    pjd_fill_mcu_xy(mcu_xy, wg, im, tid);
     const uint32_t dus = im.dus_per_mcu, nl = im.n_luma, nc = im.ncomp, hs = im.hs, vs = im.vs;
     const uint32_t n_du = wg.n_mcu * dus;
     __syncthreads();
@@ -805,13 +785,7 @@ __device__ __forceinline__ void pjd_idct_range(const PjdDevBatch &B, uint32_t iw
 // sweep: only ranges not marked done by the pull launch (pjd_internal.h)
 __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_colour_lanes(PjdDevBatch B, const uint32_t *__restrict__ order, int sweep)
 {
-    __shared__ __attribute__((aligned(16))) int16_t tile[PJD_IDCT_MAX_DU][TILE_STRIDE];
-    __shared__ uint32_t qz[3][64];            // per component, by zigzag SLOT: quantiser of its natural position | position << 16
-    __shared__ uint32_t mcu_xy[PJD_IDCT_MAX_DU];
-    __shared__ uint8_t comp_of[PJD_IDCT_MAX_DU];
-    __shared__ uint8_t du_head[PJD_IDCT_MAX_DU];
-    __shared__ uint32_t wagg[2];              // group parser: groups in the lane window; whether the lane behind the window may belong to the range
-    __shared__ uint32_t ltab[96];             // group parser: the window's lane table
+    PJD_LANES_LDS
 
 #if PJD_IDCT_PRIO
     __builtin_amdgcn_s_setprio(PJD_IDCT_PRIO);
@@ -825,13 +799,7 @@ __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_colour_lanes(PjdD
 // its code and registers.  Never a sweep: the pull form is not used for such batches.
 __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_colour_lanes_scaled(PjdDevBatch B, const uint32_t *__restrict__ order)
 {
-    __shared__ __attribute__((aligned(16))) int16_t tile[PJD_IDCT_MAX_DU][TILE_STRIDE];
-    __shared__ uint32_t qz[3][64];
-    __shared__ uint32_t mcu_xy[PJD_IDCT_MAX_DU];
-    __shared__ uint8_t comp_of[PJD_IDCT_MAX_DU];
-    __shared__ uint8_t du_head[PJD_IDCT_MAX_DU];
-    __shared__ uint32_t wagg[2];
-    __shared__ uint32_t ltab[96];
+    PJD_LANES_LDS
 
 #if PJD_IDCT_PRIO
     __builtin_amdgcn_s_setprio(PJD_IDCT_PRIO);
@@ -844,13 +812,7 @@ __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_colour_lanes_scal
 template <bool SCALED>
 __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_colour_lanes_planar(PjdDevBatch B, const uint32_t *__restrict__ order)
 {
-    __shared__ __attribute__((aligned(16))) int16_t tile[PJD_IDCT_MAX_DU][TILE_STRIDE];
-    __shared__ uint32_t qz[3][64];
-    __shared__ uint32_t mcu_xy[PJD_IDCT_MAX_DU];
-    __shared__ uint8_t comp_of[PJD_IDCT_MAX_DU];
-    __shared__ uint8_t du_head[PJD_IDCT_MAX_DU];
-    __shared__ uint32_t wagg[2];
-    __shared__ uint32_t ltab[96];
+    PJD_LANES_LDS
 
 #if PJD_IDCT_PRIO
     __builtin_amdgcn_s_setprio(PJD_IDCT_PRIO);
@@ -863,13 +825,7 @@ __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_colour_lanes_plan
 // kernel above the loop cost it 35 registers (46 -> 81) and with them its occupancy (0.50 -> 0.66 ms, 118 -> 102 GPix/s in flight).
 __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_pull(PjdDevBatch B)
 {
-    __shared__ __attribute__((aligned(16))) int16_t tile[PJD_IDCT_MAX_DU][TILE_STRIDE];
-    __shared__ uint32_t qz[3][64];
-    __shared__ uint32_t mcu_xy[PJD_IDCT_MAX_DU];
-    __shared__ uint8_t comp_of[PJD_IDCT_MAX_DU];
-    __shared__ uint8_t du_head[PJD_IDCT_MAX_DU];
-    __shared__ uint32_t wagg[2];
-    __shared__ uint32_t ltab[96];
+    PJD_LANES_LDS
     // It waits only if every Huffman workgroup has started -- else the device is busy or the launches came in an unlucky order, and
     // the ranges are left to the sweep.
     if (threadIdx.x == 0) {
@@ -907,13 +863,18 @@ __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_pull(PjdDevBatch 
     }
 }
 
-void pjd_launch_idct_colour_lanes(hipStream_t s, const PjdDevBatch &b, bool scaled, bool planar)
+// The kernel of a form for lane-stream input.  The default form's kernel is also the sweep of the pull form and takes a third argument.
+void pjd_launch_idct_lanes(hipStream_t s, const PjdDevBatch &b, PjdBackForm f, const uint32_t *order, uint32_t n_wg)
 {
-    if (b.n_iwg == 0) return;
-    if (planar && scaled) hipLaunchKernelGGL(pjd_k_idct_colour_lanes_planar<true>, dim3(b.n_iwg), dim3(PJD_IDCT_THREADS), 0, s, b, (const uint32_t *)nullptr);
-    else if (planar) hipLaunchKernelGGL(pjd_k_idct_colour_lanes_planar<false>, dim3(b.n_iwg), dim3(PJD_IDCT_THREADS), 0, s, b, (const uint32_t *)nullptr);
-    else if (scaled) hipLaunchKernelGGL(pjd_k_idct_colour_lanes_scaled, dim3(b.n_iwg), dim3(PJD_IDCT_THREADS), 0, s, b, (const uint32_t *)nullptr);
-    else hipLaunchKernelGGL(pjd_k_idct_colour_lanes, dim3(b.n_iwg), dim3(PJD_IDCT_THREADS), 0, s, b, (const uint32_t *)nullptr, 0);
+    if (n_wg == 0) return;
+    if (f.layout == PJD_BACK_INTERLEAVED && !f.scaled) {
+        hipLaunchKernelGGL(pjd_k_idct_colour_lanes, dim3(n_wg), dim3(PJD_IDCT_THREADS), 0, s, b, order, 0);
+        return;
+    }
+    // scaled before full size in every table of the back end: the order the templates are instantiated in is part of a unit's text
+    static const PjdLanesKernel colour[3] = {pjd_k_idct_colour_lanes_planar<true>, pjd_k_idct_colour_lanes_planar<false>, pjd_k_idct_colour_lanes_scaled};
+    const PjdLanesKernel k = f.gray() ? pjd_gray_lanes_kernel(f.scaled ? PJD_GRAY_SCALED : PJD_GRAY_FULL) : colour[f.layout == PJD_BACK_PLANAR ? !f.scaled : 2];
+    hipLaunchKernelGGL(k, dim3(n_wg), dim3(PJD_IDCT_THREADS), 0, s, b, order);
 }
 
 void pjd_launch_idct_pull(hipStream_t s, const PjdDevBatch &b)
@@ -927,15 +888,6 @@ void pjd_launch_idct_pull(hipStream_t s, const PjdDevBatch &b)
 void pjd_launch_idct_sweep(hipStream_t s, const PjdDevBatch &b)
 {
     if (b.n_iwg) hipLaunchKernelGGL(pjd_k_idct_colour_lanes, dim3(b.n_iwg), dim3(PJD_IDCT_THREADS), 0, s, b, (const uint32_t *)nullptr, 1);
-}
-
-void pjd_launch_group_idct(hipStream_t s, const PjdDevBatch &b, const PjdDevGroup &g, bool scaled, bool planar)
-{
-    if (!g.iwg_count) return;
-    if (planar && scaled) hipLaunchKernelGGL(pjd_k_idct_colour_lanes_planar<true>, dim3(g.iwg_count), dim3(PJD_IDCT_THREADS), 0, s, b, (const uint32_t *)(b.iwg_order + g.iwg_first));
-    else if (planar) hipLaunchKernelGGL(pjd_k_idct_colour_lanes_planar<false>, dim3(g.iwg_count), dim3(PJD_IDCT_THREADS), 0, s, b, (const uint32_t *)(b.iwg_order + g.iwg_first));
-    else if (scaled) hipLaunchKernelGGL(pjd_k_idct_colour_lanes_scaled, dim3(g.iwg_count), dim3(PJD_IDCT_THREADS), 0, s, b, (const uint32_t *)(b.iwg_order + g.iwg_first));
-    else hipLaunchKernelGGL(pjd_k_idct_colour_lanes, dim3(g.iwg_count), dim3(PJD_IDCT_THREADS), 0, s, b, b.iwg_order + g.iwg_first, 0);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1020,12 +972,12 @@ void pjd_launch_lane_dc_scan(hipStream_t s, const PjdDevBatch &b, bool per_pictu
     hipLaunchKernelGGL(pjd_k_lane_dc_carry, dim3(1), dim3(256), 0, s, b);
 }
 
-void pjd_launch_idct_colour(hipStream_t s, const PjdDevBatch &b, const PjdDevIdctWg *wgs, const uint64_t *dense_base, uint32_t n_wg, bool scaled, bool planar)
+// ... and for dense input
+void pjd_launch_idct_dense(hipStream_t s, const PjdDevBatch &b, PjdBackForm f, const PjdDevIdctWg *wgs, const uint64_t *dense_base, uint32_t n_wg)
 {
     if (n_wg == 0) return;
-    if (planar && scaled) hipLaunchKernelGGL(pjd_k_idct_colour_planar<true>, dim3(n_wg), dim3(PJD_IDCT_THREADS), 0, s, b, wgs, dense_base);
-    else if (planar) hipLaunchKernelGGL(pjd_k_idct_colour_planar<false>, dim3(n_wg), dim3(PJD_IDCT_THREADS), 0, s, b, wgs, dense_base);
-    else if (scaled) hipLaunchKernelGGL(pjd_k_idct_colour<true>, dim3(n_wg), dim3(PJD_IDCT_THREADS), 0, s, b, wgs, dense_base);
-    else hipLaunchKernelGGL(pjd_k_idct_colour<false>, dim3(n_wg), dim3(PJD_IDCT_THREADS), 0, s, b, wgs, dense_base);
+    static const PjdDenseKernel colour[2][2] = {{pjd_k_idct_colour_planar<true>, pjd_k_idct_colour_planar<false>},
+                                                {pjd_k_idct_colour<true>, pjd_k_idct_colour<false>}};
+    const PjdDenseKernel k = f.gray() ? pjd_gray_dense_kernel(f.scaled ? PJD_GRAY_SCALED : PJD_GRAY_FULL) : colour[f.layout != PJD_BACK_PLANAR][!f.scaled];
+    hipLaunchKernelGGL(k, dim3(n_wg), dim3(PJD_IDCT_THREADS), 0, s, b, wgs, dense_base);
 }
-

@@ -1,10 +1,30 @@
 // pjd_k_backend_common.h -- what the back-end units (pjd_k_backend.hip, pjd_k_backend_std.hip, pjd_k_backend_gray.hip) share: the LDS tile row, the
-// range of decoded units, the wide stores, the BMP header, the wave scans of the DC stage and the tile store of the entry parser.
+// LDS block of a lane-stream kernel, the range of decoded units, the grid positions of a range's MCUs, the 1-D IDCT passes over the tile, the wide stores, the BMP header, the wave scans of the DC stage and the tile store of
+// the entry parser.  Each of these stands here once; the kernels differ in which units they walk and where they store.
 #pragma once
 #include "pjd_device_common.h"
 #include "pjd_kernels.h"
 
 #define TILE_STRIDE 72   // int16 per data unit in LDS: 64 + 8 pad (144 B = 36 banks)
+
+// The grey unit's kernels, for the launchers of the forms (pjd_kernels.h), which stand in the other two units
+typedef void (*PjdLanesKernel)(PjdDevBatch, const uint32_t *);
+typedef void (*PjdDenseKernel)(PjdDevBatch, const PjdDevIdctWg *, const uint64_t *);
+enum PjdGrayKernel { PJD_GRAY_SCALED = 0, PJD_GRAY_FULL = 1, PJD_GRAY_LIBJPEG = 2 };
+PjdLanesKernel pjd_gray_lanes_kernel(PjdGrayKernel which);
+PjdDenseKernel pjd_gray_dense_kernel(PjdGrayKernel which);
+
+// The LDS of a kernel that parses the lane streams (pjd_k_lanes_parse_body.h, pjd_k_lanes_dc_body.h), declared by all seven of them in
+// this order -- LDS offsets are part of a kernel's text.  The PJD_F_LIBJPEG kernels declare ws and qn between the tile and the rest.
+#define PJD_LANES_LDS_TILE __shared__ __attribute__((aligned(16))) int16_t tile[PJD_IDCT_MAX_DU][TILE_STRIDE];
+#define PJD_LANES_LDS_TABLES                                                                                                         \
+    __shared__ uint32_t qz[3][64];            /* per component, by zigzag SLOT: quantiser of its natural position | position << 16 */  \
+    __shared__ uint32_t mcu_xy[PJD_IDCT_MAX_DU];                                                                                     \
+    __shared__ uint8_t comp_of[PJD_IDCT_MAX_DU];                                                                                     \
+    __shared__ uint8_t du_head[PJD_IDCT_MAX_DU];                                                                                     \
+    __shared__ uint32_t wagg[2];              /* group parser: groups in the lane window; whether the lane behind it may belong */     \
+    __shared__ uint32_t ltab[96];             /* group parser: the window's lane table */
+#define PJD_LANES_LDS PJD_LANES_LDS_TILE PJD_LANES_LDS_TABLES
 
 // Data units of a range [first_du, first_du + n_du) the back end materialises: all of them, or those up to the picture's first
 // entropy-coding error (the unit that holds it included, unless the error is in its DC symbol: pjd_internal.h, PjdDevImState).
@@ -13,6 +33,37 @@ __device__ __forceinline__ uint32_t pjd_units_decoded(unsigned long long err_key
     if (err_key == ~0ull) return n_du;
     const uint32_t stop = (uint32_t)((err_key >> 4) & 0x0fffffffu) + ((err_key & 1u) ? 0u : 1u);
     return stop <= first_du ? 0u : (stop - first_du < n_du ? stop - first_du : n_du);
+}
+
+// Grid position (row << 16 | column) of each MCU of a range, by its first threads: the only divisions of a dense kernel
+__device__ __forceinline__ void pjd_fill_mcu_xy(uint32_t *mcu_xy, const PjdDevIdctWg &wg, const PjdDevImage &im, uint32_t tid)
+{
+    if (tid < wg.n_mcu) {
+        const uint32_t m = wg.first_mcu + tid, my = m / im.mcux;
+        mcu_xy[tid] = (my << 16) | (m - my * im.mcux);
+    }
+}
+
+// ---- the 1-D passes of the reference's IDCT on one row / one column of a unit of the tile (reference src/decoder_dpu.c:218-320)
+__device__ __forceinline__ void pjd_tile_row(int16_t (*tile)[TILE_STRIDE], uint32_t du, uint32_t r)
+{
+    int4 raw = *reinterpret_cast<const int4 *>(&tile[du][r * 8]);
+    int16_t *rv = reinterpret_cast<int16_t *>(&raw);
+    int o[8];
+    pjd_idct8(rv[0], rv[1], rv[2], rv[3], rv[4], rv[5], rv[6], rv[7], o);
+#pragma unroll
+    for (int j = 0; j < 8; j++) rv[j] = (int16_t)o[j];
+    *reinterpret_cast<int4 *>(&tile[du][r * 8]) = raw;
+}
+
+__device__ __forceinline__ void pjd_tile_col(int16_t (*tile)[TILE_STRIDE], uint32_t du, uint32_t c)
+{
+    int x[8], o[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) x[j] = tile[du][j * 8 + c];
+    pjd_idct8(x[0], x[1], x[2], x[3], x[4], x[5], x[6], x[7], o);
+#pragma unroll
+    for (int j = 0; j < 8; j++) tile[du][j * 8 + c] = (int16_t)o[j];
 }
 
 // One dword whatever its address: gfx950 global stores need no alignment (planar pictures start at any byte the caller binds)

@@ -12,11 +12,11 @@
 //   pjd_k_idct_gray_std_lanes / pjd_k_idct_gray_std_dense
 //                       PJD_F_LIBJPEG pictures: jpeg_idct_islow of the luma units (pjd_libjpeg.h) straight into the picture, clipped
 //                       to its width and height.  No component planes, no chroma, no colour launch.
-// Kernels of their own, as the planar and the scaled back ends are: the existing ones keep their code and registers.
-#include "pjd_k_backend_common.h"
-#include "pjd_libjpeg.h"
-
-#define WS_STRIDE 72     // int32 per data unit of the pass-1 workspace of the libjpeg kernels (pjd_k_backend_std.hip)
+// Kernels of their own, as the planar and the scaled back ends are: the existing ones keep their code and registers.  Of their own is
+// the walk over the luma units (pjd_gray_unit), the stores and pjd_gray_dc; the parser, the dense staging, the IDCT passes and the islow
+// passes are the texts the other units use (pjd_k_backend_common.h, pjd_k_dense_stage_body.h, pjd_libjpeg_passes.h).  No launcher
+// here: those of pjd_k_backend.hip and pjd_k_backend_std.hip take the kernels from the two accessors at the end.
+#include "pjd_libjpeg_passes.h"
 
 namespace {
 
@@ -150,31 +150,10 @@ __device__ __forceinline__ void pjd_gray_dispatch(const int16_t (*tile)[TILE_STR
     pjd_gray_store(tile, mcu_xy, out, im, n_mcu, tid);
 }
 
-// the 1-D passes of pjd_k_backend.hip on one row / one column of a unit of the tile (reference src/decoder_dpu.c:218-320)
-__device__ __forceinline__ void pjd_gray_tile_row(int16_t (*tile)[TILE_STRIDE], uint32_t du, uint32_t r)
-{
-    int4 raw = *reinterpret_cast<const int4 *>(&tile[du][r * 8]);
-    int16_t *rv = reinterpret_cast<int16_t *>(&raw);
-    int o[8];
-    pjd_idct8(rv[0], rv[1], rv[2], rv[3], rv[4], rv[5], rv[6], rv[7], o);
-#pragma unroll
-    for (int j = 0; j < 8; j++) rv[j] = (int16_t)o[j];
-    *reinterpret_cast<int4 *>(&tile[du][r * 8]) = raw;
-}
-
-__device__ __forceinline__ void pjd_gray_tile_col(int16_t (*tile)[TILE_STRIDE], uint32_t du, uint32_t c)
-{
-    int x[8], o[8];
-#pragma unroll
-    for (int j = 0; j < 8; j++) x[j] = tile[du][j * 8 + c];
-    pjd_idct8(x[0], x[1], x[2], x[3], x[4], x[5], x[6], x[7], o);
-#pragma unroll
-    for (int j = 0; j < 8; j++) tile[du][j * 8 + c] = (int16_t)o[j];
-}
-
-// DC prediction of the LUMA units of a range by wave 0 (pjd_k_lanes_dc_body.h with the chroma sums taken out): the differences the
-// parser left in tile[u][0] become absolute values, scaled by the quantiser in qz (all modulo 2^16).  A restart head is the first unit
-// of an MCU, which is a luma unit.
+// DC prediction of the LUMA units of a range by wave 0: the differences the parser left in tile[u][0] become absolute values, scaled
+// by the quantiser in qz (all modulo 2^16).  A restart head is the first unit of an MCU, which is a luma unit.  This is
+// pjd_k_lanes_dc_body.h with the chroma sums taken out, kept as a copy: that body with a luma-only switch did not compile to this
+// text in the three lane kernels below (profiles/backend_shared_stages.md).
 __device__ __forceinline__ void pjd_gray_dc(int16_t (*tile)[TILE_STRIDE], const uint32_t (*qz)[64], const uint8_t *comp_of, const uint8_t *du_head,
                                             uint32_t pred0y, uint32_t n_du, uint32_t n_valid, uint32_t lane)
 {
@@ -214,15 +193,15 @@ __device__ __forceinline__ void pjd_gray_range(const PjdDevBatch &B, uint32_t iw
             const uint32_t j = pjd_div_small(i, c_recip16[7]), r = 1 + (i - __umul24(j, 7u));   // i < 7 * PJD_IDCT_MAX_DU: exact
             const uint32_t u = pjd_gray_unit(j, nl_log, nl, dus);
             if (r == 4 && tile[u][64] != (int16_t)PJD_COEF_SENTINEL) tile[u][38] = (int16_t)pjd_dequant((int)tile[u][64], qz[0][48] & 0xffffu);
-            pjd_gray_tile_row(tile, u, r);
+            pjd_tile_row(tile, u, r);
         }
     } else {
         pjd_gray_dc(tile, qz, comp_of, du_head, pred0[0], n_du, n_valid, lane);
     }
     __syncthreads();
-    for (uint32_t j = tid; j < n_lu; j += PJD_IDCT_THREADS) pjd_gray_tile_row(tile, pjd_gray_unit(j, nl_log, nl, dus), 0);
+    for (uint32_t j = tid; j < n_lu; j += PJD_IDCT_THREADS) pjd_tile_row(tile, pjd_gray_unit(j, nl_log, nl, dus), 0);
     __syncthreads();
-    for (uint32_t i = tid; i < n_lu * 8; i += PJD_IDCT_THREADS) pjd_gray_tile_col(tile, pjd_gray_unit(i >> 3, nl_log, nl, dus), i & 7);
+    for (uint32_t i = tid; i < n_lu * 8; i += PJD_IDCT_THREADS) pjd_tile_col(tile, pjd_gray_unit(i >> 3, nl_log, nl, dus), i & 7);
     __syncthreads();
     pjd_gray_dispatch<SCALED>(tile, mcu_xy, B, im, wg.n_mcu, tid);
 }
@@ -237,12 +216,7 @@ __device__ __forceinline__ void pjd_gray_std_idct(const int16_t (*tile)[TILE_STR
     // pass 1: a thread takes one column of one unit
     for (uint32_t i = tid; i < n_lu * 8; i += PJD_IDCT_THREADS) {
         const uint32_t u = pjd_gray_unit(i >> 3, nl_log, nl, dus), c = i & 7;
-        uint32_t x[8], o[8];
-#pragma unroll
-        for (int j = 0; j < 8; j++) x[j] = pjd_lj_dequant((int)tile[u][j * 8 + c], q[j * 8 + c]);
-        pjd_lj_idct1d(x, o);
-#pragma unroll
-        for (int j = 0; j < 8; j++) ws[u][j * 8 + c] = pjd_lj_descale<PJD_LJ_PASS1_SHIFT>(o[j]);
+        PJD_LJ_PASS1_COL(tile, ws, u, q, c);
     }
     __syncthreads();
     // pass 2: a thread takes one row of one unit and stores its 8 samples
@@ -254,13 +228,7 @@ __device__ __forceinline__ void pjd_gray_std_idct(const int16_t (*tile)[TILE_STR
         const uint32_t xy = mcu_xy[ml];
         const uint32_t X = (__umul24(xy & 0xffffu, hs) + (k & (hs - 1u))) * 8u, Y = (__umul24(xy >> 16, vs) + (k >> (hs - 1u))) * 8u + r;
         if (X >= width || Y >= height) continue;
-        const uint4 lo = *reinterpret_cast<const uint4 *>(&ws[u][r * 8]), hi = *reinterpret_cast<const uint4 *>(&ws[u][r * 8 + 4]);
-        const uint32_t x[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-        uint32_t o[8];
-        pjd_lj_idct1d(x, o);
-        uint2 px;
-        px.x = pjd_lj_sample(o[0]) | (pjd_lj_sample(o[1]) << 8) | (pjd_lj_sample(o[2]) << 16) | (pjd_lj_sample(o[3]) << 24);
-        px.y = pjd_lj_sample(o[4]) | (pjd_lj_sample(o[5]) << 8) | (pjd_lj_sample(o[6]) << 16) | (pjd_lj_sample(o[7]) << 24);
+        const uint2 px = pjd_lj_pass2_row(ws, u, r);
         pjd_gray_store8(out + (size_t)Y * stride + X, px, X, width);
     }
 }
@@ -274,13 +242,7 @@ __device__ __forceinline__ void pjd_gray_std_idct(const int16_t (*tile)[TILE_STR
 template <bool SCALED>
 __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_gray_lanes(PjdDevBatch B, const uint32_t *__restrict__ order)
 {
-    __shared__ __attribute__((aligned(16))) int16_t tile[PJD_IDCT_MAX_DU][TILE_STRIDE];
-    __shared__ uint32_t qz[3][64];            // per component, by zigzag SLOT: quantiser of its natural position | position << 16
-    __shared__ uint32_t mcu_xy[PJD_IDCT_MAX_DU];
-    __shared__ uint8_t comp_of[PJD_IDCT_MAX_DU];
-    __shared__ uint8_t du_head[PJD_IDCT_MAX_DU];
-    __shared__ uint32_t wagg[2];
-    __shared__ uint32_t ltab[96];
+    PJD_LANES_LDS
 
 #if PJD_IDCT_PRIO
     __builtin_amdgcn_s_setprio(PJD_IDCT_PRIO);
@@ -306,10 +268,7 @@ __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_gray(PjdDevBatch 
     const uint32_t nl_log = nl == 4u ? 2u : nl - 1u, n_lu = wg.n_mcu * nl;
 
     if (tid < 64) qs[tid] = B.qtab[(size_t)wg.image * 192 + tid];
-    if (tid < wg.n_mcu) {                                   // grid position of each MCU: the only divisions
-        const uint32_t m = wg.first_mcu + tid, my = m / im.mcux;
-        mcu_xy[tid] = (my << 16) | (m - my * im.mcux);
-    }
+    pjd_fill_mcu_xy(mcu_xy, wg, im, tid);
     __syncthreads();
 
     // load (16 B per lane), de-zigzag, dequantise: lane (unit, r) owns zigzag slots 8r..8r+7
@@ -317,38 +276,14 @@ __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_gray(PjdDevBatch 
     for (uint32_t i = tid; i < n_lu * 8; i += PJD_IDCT_THREADS) {
         const uint32_t du = pjd_gray_unit(i >> 3, nl_log, nl, dus), r = i & 7;
         const int4 raw = *reinterpret_cast<const int4 *>(cbase + (size_t)du * 64 + r * 8);
-        const int16_t *rv = reinterpret_cast<const int16_t *>(&raw);
-        int v[8];
-#pragma unroll
-        for (int j = 0; j < 8; j++) v[j] = rv[j];
-        int16_t *t = tile[du];
-        const uint16_t *q = qs;
-        // the sentinel means "explicit zero" at slot 52 of a baseline picture only (pjd_k_idct_dense_body.h)
-        const bool zero52 = r == 6 && !(im.flags & PJD_IF_PROGRESSIVE) && v[4] == PJD_COEF_SENTINEL;
-        if (r == 6 && !(im.flags & PJD_IF_STANDARD_ZIGZAG)) {
-            // slots 48..55: natural position 38 is the target of slot 48 AND slot 52, the later write wins
-            const int v52 = v[4];
-            const int n38 = v52 != 0 ? (zero52 ? 0 : v52) : v[0];
-            t[38] = (int16_t)pjd_dequant(n38, q[38]);
-            t[59] = (int16_t)pjd_dequant(v[1], q[59]);
-            t[52] = (int16_t)pjd_dequant(v[2], q[52]);
-            t[45] = (int16_t)pjd_dequant(v[3], q[45]);
-            t[31] = (int16_t)pjd_dequant(v[5], q[31]);
-            t[39] = (int16_t)pjd_dequant(v[6], q[39]);
-            t[46] = (int16_t)pjd_dequant(v[7], q[46]);
-            t[58] = 0;                    // natural 58 is never written by the reference
-        } else {
-#pragma unroll
-            for (int j = 0; j < 8; j++) {
-                const uint32_t nat = (r == 6 && j == 0) ? 58u : c_zz[r * 8 + j];          // r == 6 here: PJD_IF_STANDARD_ZIGZAG
-                t[nat] = (int16_t)pjd_dequant(j == 4 && zero52 ? 0 : v[j], q[nat]);
-            }
-        }
+#define PJD_DENSE_Q qs
+#include "pjd_k_dense_stage_body.h"
+#undef PJD_DENSE_Q
     }
     __syncthreads();
-    for (uint32_t i = tid; i < n_lu * 8; i += PJD_IDCT_THREADS) pjd_gray_tile_row(tile, pjd_gray_unit(i >> 3, nl_log, nl, dus), i & 7);
+    for (uint32_t i = tid; i < n_lu * 8; i += PJD_IDCT_THREADS) pjd_tile_row(tile, pjd_gray_unit(i >> 3, nl_log, nl, dus), i & 7);
     __syncthreads();
-    for (uint32_t i = tid; i < n_lu * 8; i += PJD_IDCT_THREADS) pjd_gray_tile_col(tile, pjd_gray_unit(i >> 3, nl_log, nl, dus), i & 7);
+    for (uint32_t i = tid; i < n_lu * 8; i += PJD_IDCT_THREADS) pjd_tile_col(tile, pjd_gray_unit(i >> 3, nl_log, nl, dus), i & 7);
     __syncthreads();
     pjd_gray_dispatch<SCALED>(tile, mcu_xy, B, im, wg.n_mcu, tid);
 }
@@ -358,15 +293,10 @@ __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_gray(PjdDevBatch 
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_gray_std_lanes(PjdDevBatch B, const uint32_t *__restrict__ order)
 {
-    __shared__ __attribute__((aligned(16))) int16_t tile[PJD_IDCT_MAX_DU][TILE_STRIDE];
+    PJD_LANES_LDS_TILE
     __shared__ __attribute__((aligned(16))) uint32_t ws[PJD_IDCT_MAX_DU][WS_STRIDE];
     __shared__ uint16_t qn[64];               // the luma quantiser by natural position
-    __shared__ uint32_t qz[3][64];            // by zigzag SLOT: 1 | natural position << 16 (the parser stores what was decoded)
-    __shared__ uint32_t mcu_xy[PJD_IDCT_MAX_DU];
-    __shared__ uint8_t comp_of[PJD_IDCT_MAX_DU];
-    __shared__ uint8_t du_head[PJD_IDCT_MAX_DU];
-    __shared__ uint32_t wagg[2];
-    __shared__ uint32_t ltab[96];
+    PJD_LANES_LDS_TABLES                      // qz here: 1 | natural position << 16 (the parser stores what was decoded)
 
     const uint32_t iwg = order[blockIdx.x];
     if (threadIdx.x < 64) qn[threadIdx.x] = B.qtab[(size_t)B.iwgs[iwg].image * 192 + threadIdx.x];
@@ -393,47 +323,29 @@ __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_gray_std_dense(Pj
     const uint32_t dus = im.dus_per_mcu, nl = im.n_luma;
     const uint32_t nl_log = nl == 4u ? 2u : nl - 1u, n_lu = wg.n_mcu * nl;
     if (tid < 64) qn[tid] = B.qtab[(size_t)wg.image * 192 + tid];
-    if (tid < wg.n_mcu) {
-        const uint32_t m = wg.first_mcu + tid, my = m / im.mcux;
-        mcu_xy[tid] = (my << 16) | (m - my * im.mcux);
-    }
+    pjd_fill_mcu_xy(mcu_xy, wg, im, tid);
     const int16_t *cbase = B.coef + (dense_base[wg.pad_] + (uint64_t)(wg.first_mcu - im.first_mcu) * dus) * 64;
     const bool sentinel = !(im.flags & PJD_IF_PROGRESSIVE);
     for (uint32_t i = tid; i < n_lu * 8; i += PJD_IDCT_THREADS) {
         const uint32_t du = pjd_gray_unit(i >> 3, nl_log, nl, dus), r = i & 7;
         const int4 raw = *reinterpret_cast<const int4 *>(cbase + (size_t)du * 64 + r * 8);
-        const int16_t *rv = reinterpret_cast<const int16_t *>(&raw);
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const uint32_t nat = (r == 6 && j == 0) ? 58u : c_zz[r * 8 + j];              // the T.81 zigzag: slot 48 -> 58
-            const bool zero52 = sentinel && r == 6 && j == 4 && rv[j] == PJD_COEF_SENTINEL;
-            tile[du][nat] = zero52 ? (int16_t)0 : rv[j];
-        }
+#define PJD_DENSE_RAW
+#include "pjd_k_dense_stage_body.h"
+#undef PJD_DENSE_RAW
     }
     __syncthreads();
     pjd_gray_std_idct(tile, ws, qn, mcu_xy, B, im, wg.n_mcu, tid);
 }
 
-void pjd_launch_idct_gray_lanes(hipStream_t s, const PjdDevBatch &b, const uint32_t *order, uint32_t n_wg, bool scaled)
+// the grey kernels, scaled / full size / PJD_F_LIBJPEG: the launchers of the forms stand in pjd_k_backend.hip and pjd_k_backend_std.hip
+PjdLanesKernel pjd_gray_lanes_kernel(PjdGrayKernel which)
 {
-    if (n_wg == 0) return;
-    if (scaled) hipLaunchKernelGGL(pjd_k_idct_gray_lanes<true>, dim3(n_wg), dim3(PJD_IDCT_THREADS), 0, s, b, order);
-    else hipLaunchKernelGGL(pjd_k_idct_gray_lanes<false>, dim3(n_wg), dim3(PJD_IDCT_THREADS), 0, s, b, order);
+    static const PjdLanesKernel k[3] = {pjd_k_idct_gray_lanes<true>, pjd_k_idct_gray_lanes<false>, pjd_k_idct_gray_std_lanes};
+    return k[which];
 }
 
-void pjd_launch_idct_gray(hipStream_t s, const PjdDevBatch &b, const PjdDevIdctWg *wgs, const uint64_t *dense_base, uint32_t n_wg, bool scaled)
+PjdDenseKernel pjd_gray_dense_kernel(PjdGrayKernel which)
 {
-    if (n_wg == 0) return;
-    if (scaled) hipLaunchKernelGGL(pjd_k_idct_gray<true>, dim3(n_wg), dim3(PJD_IDCT_THREADS), 0, s, b, wgs, dense_base);
-    else hipLaunchKernelGGL(pjd_k_idct_gray<false>, dim3(n_wg), dim3(PJD_IDCT_THREADS), 0, s, b, wgs, dense_base);
-}
-
-void pjd_launch_idct_gray_std_lanes(hipStream_t s, const PjdDevBatch &b, const uint32_t *order, uint32_t n_wg)
-{
-    if (n_wg) hipLaunchKernelGGL(pjd_k_idct_gray_std_lanes, dim3(n_wg), dim3(PJD_IDCT_THREADS), 0, s, b, order);
-}
-
-void pjd_launch_idct_gray_std_dense(hipStream_t s, const PjdDevBatch &b, const PjdDevIdctWg *wgs, const uint64_t *dense_base, uint32_t n_wg)
-{
-    if (n_wg) hipLaunchKernelGGL(pjd_k_idct_gray_std_dense, dim3(n_wg), dim3(PJD_IDCT_THREADS), 0, s, b, wgs, dense_base);
+    static const PjdDenseKernel k[3] = {pjd_k_idct_gray<true>, pjd_k_idct_gray<false>, pjd_k_idct_gray_std_dense};
+    return k[which];
 }

@@ -9,12 +9,10 @@
 //                       on its rows and stores 8 samples of a component PLANE (uint8, padded to whole MCUs) as one 8-byte store
 //   pjd_k_colour_std    upsample + colour + store: a thread makes four adjacent pixels of one row and writes them where the
 //                       default back end writes them -- RGB8, planar or the BMP image
-// The arithmetic is pjd_libjpeg.h's, which the host entry points export.
-#include "pjd_k_backend_common.h"
-#include "pjd_libjpeg.h"
-
-#define WS_STRIDE 72     // int32 per data unit of the pass-1 workspace: 64 + 8 pad.  A ds_write_b32 banks by (a / 4) % 32 within each
-                         // half of the wave: its 4 units x 8 columns start 8 banks apart and cover the 32 banks once
+// The arithmetic is pjd_libjpeg.h's, which the host entry points export; the two passes over the LDS tile are pjd_libjpeg_passes.h's and
+// the dense staging pjd_k_dense_stage_body.h's, both shared with the grey unit.  pjd_launch_idct_std_lanes / _std_dense launch these
+// kernels or, for a grey batch, the grey unit's.
+#include "pjd_libjpeg_passes.h"
 
 namespace {
 
@@ -45,12 +43,7 @@ __device__ __forceinline__ void pjd_std_idct_to_planes(const int16_t (*tile)[TIL
         const uint32_t u = i >> 3, c = i & 7;
         const uint32_t ml = pjd_div_small(u, c_recip16[dus]), kk = u - __umul24(ml, dus);
         const uint16_t *q = qn[kk < nl ? 0 : kk - nl + 1];
-        uint32_t x[8], o[8];
-#pragma unroll
-        for (int j = 0; j < 8; j++) x[j] = pjd_lj_dequant((int)tile[u][j * 8 + c], q[j * 8 + c]);
-        pjd_lj_idct1d(x, o);
-#pragma unroll
-        for (int j = 0; j < 8; j++) ws[u][j * 8 + c] = pjd_lj_descale<PJD_LJ_PASS1_SHIFT>(o[j]);
+        PJD_LJ_PASS1_COL(tile, ws, u, q, c);
     }
     __syncthreads();
     // pass 2: a thread takes one row of one unit and stores its 8 samples
@@ -62,15 +55,8 @@ __device__ __forceinline__ void pjd_std_idct_to_planes(const int16_t (*tile)[TIL
         uint32_t comp, ux, uy;
         if (kk < nl) { comp = 0; ux = mx * hs + (kk & (hs - 1)); uy = my * im.vs + (kk >> (hs - 1)); }
         else { comp = kk - nl + 1; ux = mx; uy = my; }
-        const uint4 lo = *reinterpret_cast<const uint4 *>(&ws[u][r * 8]), hi = *reinterpret_cast<const uint4 *>(&ws[u][r * 8 + 4]);
-        const uint32_t x[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-        uint32_t o[8];
-        pjd_lj_idct1d(x, o);
-        uint2 px;
-        px.x = pjd_lj_sample(o[0]) | (pjd_lj_sample(o[1]) << 8) | (pjd_lj_sample(o[2]) << 16) | (pjd_lj_sample(o[3]) << 24);
-        px.y = pjd_lj_sample(o[4]) | (pjd_lj_sample(o[5]) << 8) | (pjd_lj_sample(o[6]) << 16) | (pjd_lj_sample(o[7]) << 24);
         // planes are whole MCUs wide and high: every unit of the picture lies inside, 8-byte aligned
-        *reinterpret_cast<uint2 *>(P.p[comp] + (size_t)(uy * 8 + r) * P.stride[comp] + ux * 8) = px;
+        *reinterpret_cast<uint2 *>(P.p[comp] + (size_t)(uy * 8 + r) * P.stride[comp] + ux * 8) = pjd_lj_pass2_row(ws, u, r);
     }
 }
 
@@ -82,15 +68,10 @@ __device__ __forceinline__ void pjd_std_idct_to_planes(const int16_t (*tile)[TIL
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_std_lanes(PjdDevBatch B, const uint32_t *__restrict__ order, uint8_t *__restrict__ planes)
 {
-    __shared__ __attribute__((aligned(16))) int16_t tile[PJD_IDCT_MAX_DU][TILE_STRIDE];
+    PJD_LANES_LDS_TILE
     __shared__ __attribute__((aligned(16))) uint32_t ws[PJD_IDCT_MAX_DU][WS_STRIDE];
     __shared__ uint16_t qn[3][64];            // per component: the quantiser by natural position
-    __shared__ uint32_t qz[3][64];            // per component, by zigzag SLOT: 1 | natural position << 16 (the parser stores what was decoded)
-    __shared__ uint32_t mcu_xy[PJD_IDCT_MAX_DU];
-    __shared__ uint8_t comp_of[PJD_IDCT_MAX_DU];
-    __shared__ uint8_t du_head[PJD_IDCT_MAX_DU];
-    __shared__ uint32_t wagg[2];
-    __shared__ uint32_t ltab[96];
+    PJD_LANES_LDS_TABLES                      // qz here: 1 | natural position << 16 (the parser stores what was decoded)
 
     const uint32_t iwg = order[blockIdx.x];
     if (threadIdx.x < 192) qn[threadIdx.x >> 6][threadIdx.x & 63] = B.qtab[(size_t)B.iwgs[iwg].image * 192 + threadIdx.x];
@@ -106,8 +87,7 @@ __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_std_lanes(PjdDevB
 
 // ---------------------------------------------------------------------------------------------
 // Dense front end (pictures of the exact kernel and progressive frames): wgs[k].pad_ = index into dense_base[], as in
-// pjd_k_idct_colour.  The scratch is in zigzag-slot order with absolute DC values; PJD_COEF_SENTINEL at slot 52 of a baseline
-// picture is an explicit zero.
+// pjd_k_idct_colour; staged as decoded (pjd_k_dense_stage_body.h with PJD_DENSE_RAW).
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_std_dense(PjdDevBatch B, const PjdDevIdctWg *__restrict__ wgs, const uint64_t *__restrict__ dense_base,
                                                                          uint8_t *__restrict__ planes)
@@ -123,22 +103,15 @@ __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_std_dense(PjdDevB
     const uint32_t dus = im.dus_per_mcu;
     const uint32_t n_du = wg.n_mcu * dus;
     if (tid < 192) qn[tid >> 6][tid & 63] = B.qtab[(size_t)wg.image * 192 + tid];
-    if (tid < wg.n_mcu) {
-        const uint32_t m = wg.first_mcu + tid, my = m / im.mcux;
-        mcu_xy[tid] = (my << 16) | (m - my * im.mcux);
-    }
+    pjd_fill_mcu_xy(mcu_xy, wg, im, tid);
     const int16_t *cbase = B.coef + (dense_base[wg.pad_] + (uint64_t)(wg.first_mcu - im.first_mcu) * dus) * 64;
     const bool sentinel = !(im.flags & PJD_IF_PROGRESSIVE);
     for (uint32_t i = tid; i < n_du * 8; i += PJD_IDCT_THREADS) {
         const uint32_t du = i >> 3, r = i & 7;
         const int4 raw = *reinterpret_cast<const int4 *>(cbase + (size_t)du * 64 + r * 8);
-        const int16_t *rv = reinterpret_cast<const int16_t *>(&raw);
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const uint32_t nat = (r == 6 && j == 0) ? 58u : c_zz[r * 8 + j];              // the T.81 zigzag: slot 48 -> 58
-            const bool zero52 = sentinel && r == 6 && j == 4 && rv[j] == PJD_COEF_SENTINEL;
-            tile[du][nat] = zero52 ? (int16_t)0 : rv[j];
-        }
+#define PJD_DENSE_RAW
+#include "pjd_k_dense_stage_body.h"
+#undef PJD_DENSE_RAW
     }
     __syncthreads();
     pjd_std_idct_to_planes(tile, ws, qn, mcu_xy, im, n_du, planes, tid);
@@ -217,14 +190,18 @@ __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_colour_std(PjdDevBatch
     }
 }
 
-void pjd_launch_idct_std_lanes(hipStream_t s, const PjdDevBatch &b, const uint32_t *order, uint32_t n_wg, uint8_t *planes)
+void pjd_launch_idct_std_lanes(hipStream_t s, const PjdDevBatch &b, PjdBackForm f, const uint32_t *order, uint32_t n_wg, uint8_t *planes)
 {
-    if (n_wg) hipLaunchKernelGGL(pjd_k_idct_std_lanes, dim3(n_wg), dim3(PJD_IDCT_THREADS), 0, s, b, order, planes);
+    if (n_wg == 0) return;
+    if (f.gray()) hipLaunchKernelGGL(pjd_gray_lanes_kernel(PJD_GRAY_LIBJPEG), dim3(n_wg), dim3(PJD_IDCT_THREADS), 0, s, b, order);
+    else hipLaunchKernelGGL(pjd_k_idct_std_lanes, dim3(n_wg), dim3(PJD_IDCT_THREADS), 0, s, b, order, planes);
 }
 
-void pjd_launch_idct_std_dense(hipStream_t s, const PjdDevBatch &b, const PjdDevIdctWg *wgs, const uint64_t *dense_base, uint32_t n_wg, uint8_t *planes)
+void pjd_launch_idct_std_dense(hipStream_t s, const PjdDevBatch &b, PjdBackForm f, const PjdDevIdctWg *wgs, const uint64_t *dense_base, uint32_t n_wg, uint8_t *planes)
 {
-    if (n_wg) hipLaunchKernelGGL(pjd_k_idct_std_dense, dim3(n_wg), dim3(PJD_IDCT_THREADS), 0, s, b, wgs, dense_base, planes);
+    if (n_wg == 0) return;
+    if (f.gray()) hipLaunchKernelGGL(pjd_gray_dense_kernel(PJD_GRAY_LIBJPEG), dim3(n_wg), dim3(PJD_IDCT_THREADS), 0, s, b, wgs, dense_base);
+    else hipLaunchKernelGGL(pjd_k_idct_std_dense, dim3(n_wg), dim3(PJD_IDCT_THREADS), 0, s, b, wgs, dense_base, planes);
 }
 
 void pjd_launch_colour_std(hipStream_t s, const PjdDevBatch &b, const PjdDevIdctWg *cwgs, uint32_t n_wg, uint8_t *planes)

@@ -1,5 +1,5 @@
 // pjd_k_lanes_parse_body.h -- set-up and entry parser of one back-end range of the lane streams, included textually by
-// pjd_idct_range (pjd_k_backend.hip) and by the plane kernel of the libjpeg-exact mode (pjd_k_backend_std.hip); textual inclusion
+// pjd_idct_range (pjd_k_backend.hip), the plane kernel of the libjpeg-exact mode (pjd_k_backend_std.hip) and the grey lane kernels; textual inclusion
 // for the reason pjd_k_idct_dense_body.h gives.  Uses B, iwg, tile, qz, mcu_xy, comp_of, du_head, wagg, ltab of the including
 // function and leaves wg, im, tid, lane, wv, dus, nl, n_du, n_valid and pred0 behind.  With PJD_LANES_RAW defined the tile receives the
 // coefficients as decoded (quantiser 1, DC differences likewise) instead of their 16-bit products.  With PJD_LANES_LUMA_ONLY defined

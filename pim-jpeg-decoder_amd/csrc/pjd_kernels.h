@@ -54,33 +54,37 @@ void pjd_launch_dpu_payload(hipStream_t s, const uint32_t *metadata, int16_t *mc
 void pjd_launch_zero(hipStream_t s, void *p, size_t bytes);          // bytes: a multiple of 16
 void pjd_launch_reset(hipStream_t s, const PjdDevBatch &b, const int32_t *status_init, uint64_t *opstate, size_t opstate_words, uint32_t dbg_words);   // per-decode state
 void pjd_launch_copy_out(hipStream_t s, const void *src, void *dst_mapped, uint64_t bytes);   // HBM -> mapped page-locked host memory
+// ---- the fused back end: coefficients -> pixels, one kernel family per form of the batch's output
+// The form: where the channels of a pixel go, and whether the batch holds pictures with an output scale (PJD_IF_SCALE_MASK: the
+// kernels that also serve them).  Built once from the plan (pjd_batch::back, pjd_api.hip); every launcher below picks its kernel by it.
+// Layouts: PJD_OUT_RGB8 and _BMP; PJD_OUT_RGB8_PLANAR (the _planar kernels); PJD_OUT_GRAY8 (pjd_k_backend_gray.hip: the luma units alone)
+enum PjdBackLayout : uint8_t { PJD_BACK_INTERLEAVED = 0, PJD_BACK_PLANAR = 1, PJD_BACK_GRAY = 2 };
+struct PjdBackForm {
+    PjdBackLayout layout;
+    bool scaled;
+    bool planes() const { return layout != PJD_BACK_INTERLEAVED; }     // what the resample reads and writes: planes (three, or one)
+    bool gray() const { return layout == PJD_BACK_GRAY; }
+    bool has_pull() const { return layout == PJD_BACK_INTERLEAVED && !scaled; }   // the pull form serves the default kernel alone
+};
+// lane-stream input: workgroup k takes range order[k] of iwgs / marks (null: the identity -- the whole batch when n_wg = n_iwg)
+void pjd_launch_idct_lanes(hipStream_t s, const PjdDevBatch &b, PjdBackForm f, const uint32_t *order, uint32_t n_wg);
 // dense input (exact path): wgs[k].pad_ = index into dense_base[] (data unit 0 of that image's scratch)
-// scaled: the batch holds pictures with an output scale (PJD_IF_SCALE_MASK): the back-end kernels that also serve them
-// planar: the batch's output format is PJD_OUT_RGB8_PLANAR (PJD_IF_PLANAR on every picture): the planar back-end kernels
-void pjd_launch_idct_colour(hipStream_t s, const PjdDevBatch &b, const PjdDevIdctWg *wgs, const uint64_t *dense_base, uint32_t n_wg, bool scaled, bool planar);
-void pjd_launch_idct_colour_lanes(hipStream_t s, const PjdDevBatch &b, bool scaled, bool planar);                                  // lane-stream input
+void pjd_launch_idct_dense(hipStream_t s, const PjdDevBatch &b, PjdBackForm f, const PjdDevIdctWg *wgs, const uint64_t *dense_base, uint32_t n_wg);
 // verdict (status words) and DC predictors of the whole batch: one launch, a workgroup per picture (pjd_k_group_dc), or -- a batch with
 // a picture of very many lanes, PjdPlan::dc_per_picture -- three: per-image verdict, local scan, carry
 void pjd_launch_lane_dc_scan(hipStream_t s, const PjdDevBatch &b, bool per_picture);
-// one picture group (pjd_internal.h): verdict + DC predictors of its pictures in one launch, then its back-end workgroups
+// one picture group (pjd_internal.h): verdict + DC predictors of its pictures in one launch (its back-end workgroups: pjd_launch_idct_lanes)
 void pjd_launch_group_dc(hipStream_t s, const PjdDevBatch &b, const PjdDevGroup &g);
-void pjd_launch_group_idct(hipStream_t s, const PjdDevBatch &b, const PjdDevGroup &g, bool scaled, bool planar);
 // pull back end (pjd_internal.h): the launch that runs beside the entropy decoder, and the sweep over what it left
 void pjd_launch_idct_pull(hipStream_t s, const PjdDevBatch &b);
 void pjd_launch_idct_sweep(hipStream_t s, const PjdDevBatch &b);
-// ---- back end of PJD_F_LIBJPEG pictures (pjd_k_backend_std.hip): component planes (islow IDCT) from the lane streams (order[k]: index into
-// iwgs / marks) or from the dense scratch (wgs, dense_base as for pjd_launch_idct_colour), then upsample + colour + store
-// (cwgs[k] = {image, first 4-pixel item, -, -}); `planes` is the batch's plane buffer (PjdDevImage::plane_off256)
-void pjd_launch_idct_std_lanes(hipStream_t s, const PjdDevBatch &b, const uint32_t *order, uint32_t n_wg, uint8_t *planes);
-void pjd_launch_idct_std_dense(hipStream_t s, const PjdDevBatch &b, const PjdDevIdctWg *wgs, const uint64_t *dense_base, uint32_t n_wg, uint8_t *planes);
+// ---- PJD_F_LIBJPEG pictures (islow IDCT), from the lane streams or the dense scratch as above.  Interleaved and planar batches
+// (pjd_k_backend_std.hip): into component planes -- `planes` is the batch's plane buffer (PjdDevImage::plane_off256) -- then upsample +
+// colour + store by pjd_launch_colour_std (cwgs[k] = {image, first 4-pixel item, -, -}).  A grey batch (pjd_k_backend_gray.hip): the
+// luma units straight into the picture; `planes` is unused and there is no colour launch.
+void pjd_launch_idct_std_lanes(hipStream_t s, const PjdDevBatch &b, PjdBackForm f, const uint32_t *order, uint32_t n_wg, uint8_t *planes);
+void pjd_launch_idct_std_dense(hipStream_t s, const PjdDevBatch &b, PjdBackForm f, const PjdDevIdctWg *wgs, const uint64_t *dense_base, uint32_t n_wg, uint8_t *planes);
 void pjd_launch_colour_std(hipStream_t s, const PjdDevBatch &b, const PjdDevIdctWg *cwgs, uint32_t n_wg, uint8_t *planes);
-// ---- back end of a PJD_OUT_GRAY8 batch (pjd_k_backend_gray.hip): the luma units alone, one plane.  Lane-stream input over order[k] (index
-// into iwgs / marks; null: the identity) or dense input (as for pjd_launch_idct_colour); the _std pair serves the PJD_F_LIBJPEG pictures
-// of such a batch and stores straight into the picture (no planes, no colour launch)
-void pjd_launch_idct_gray_lanes(hipStream_t s, const PjdDevBatch &b, const uint32_t *order, uint32_t n_wg, bool scaled);
-void pjd_launch_idct_gray(hipStream_t s, const PjdDevBatch &b, const PjdDevIdctWg *wgs, const uint64_t *dense_base, uint32_t n_wg, bool scaled);
-void pjd_launch_idct_gray_std_lanes(hipStream_t s, const PjdDevBatch &b, const uint32_t *order, uint32_t n_wg);
-void pjd_launch_idct_gray_std_dense(hipStream_t s, const PjdDevBatch &b, const PjdDevIdctWg *wgs, const uint64_t *dense_base, uint32_t n_wg);
 // ---- resize on decode (pjd_k_resize.hip): every picture of the batch from `src` (interleaved RGB8, or planar) to its target size in `dst`
 // (the same layout), one launch whatever the batch asked for; tile_prefix[i] = tiles of the pictures before i, tile_prefix[n_images] =
 // n_tiles.  norm.dtype != 0: the samples leave as fp16 / bf16 / fp32 elements, v * scale[c] + bias[c] (pjd_batch_set_normalize); the

@@ -5,8 +5,8 @@ decode (tests/golden/libjpeg_gray/), through the box model of the scaled tests f
 
 Kernel forms launched here (all of pjd_k_backend_gray.hip): pjd_k_idct_gray_lanes<false> and <true> (tests 1, 2: parallel),
 pjd_k_idct_gray<false> and <true> (tests 1, 2: sequential; test 5: the fallback), pjd_k_idct_gray_std_lanes and
-pjd_k_idct_gray_std_dense (test 3); and all of the one-plane resample, which has the padded (most general) form alone
-(pjd_k_resize.hip): pjd_k_resize_gray<DT> for DT = uint8, fp16, bf16, fp32 and pjd_k_resize_gray_tab<DT, FILT> for the same four and
+pjd_k_idct_gray_std_dense (test 3; test 5: the fallback of a flagged picture); and all of the one-plane resample, which has the
+padded (most general) form alone (pjd_k_resize.hip): pjd_k_resize_gray<DT> for DT = uint8, fp16, bf16, fp32 and pjd_k_resize_gray_tab<DT, FILT> for the same four and
 FILT = antialias, bicubic -- twelve forms, each launched by test 6, which crosses the three filters with the four element types (and
 lists what it launched)."""
 import json
@@ -234,6 +234,38 @@ def test_pictures_that_fall_to_the_exact_kernel(ctx, port):
                 _same(o, p, (k, rep))
 
 
+def test_fallback_redecodes_flagged_pictures_of_a_gray_batch(port, monkeypatch):
+    """The grey counterpart of tests/test_gpu_libjpeg_corpus.py::test_fallback_redecodes_flagged_pictures: the same broken streams once
+    flagged PJD_F_LIBJPEG and once plain, beside a good flagged picture, on a context of its own whose allocations start as 0xA5.
+    settle() decodes the flagged ones again through the dense libjpeg grey kernel, the plain ones through the dense grey kernel.  More
+    pictures are re-decoded than in the same batch without the flagged broken streams: a flagged one is among them."""
+    import pjd_amd
+    monkeypatch.setenv("PJD_DEBUG_POISON", "0xa5")
+    jpegs = G.misplaced_restart_markers(port)
+    assert len(jpegs) >= 6
+    good = "lj_8x8_444_q90"
+    plain = [(_scanned(j), G.ref_plane(port, j)) for j in jpegs]
+    rows = [(_scanned(j, pjd_amd.F_LIBJPEG), G.model_y_plane(port, j, broken=True)) for j in jpegs] + [(_lj(good), (0, G.l8(good)))] + plain
+    c = pjd_amd.Context(0)
+    try:
+        n_fallback = []
+        for batch in (rows, rows[len(jpegs):]):
+            with c.batch([s.desc for s, _ in batch], pjd_amd.OUT_GRAY8) as b:
+                b.upload()
+                for rep in range(2):
+                    b.decode(); b.sync()
+                    outs, st = b.download()
+                    for k, (_, (status, p)) in enumerate(batch):
+                        assert st[k] == status, (k, rep, len(batch))
+                        _same(outs[k], p, (k, rep, len(batch)))
+                info = b.info()
+            assert info["n_sequential"] == 0, info
+            n_fallback.append(info["n_fallback"])
+    finally:
+        c.close()
+    assert n_fallback[0] >= 2 and n_fallback[0] > n_fallback[1], n_fallback
+
+
 # ---- 6: shards -------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name,world", [("rst4_128x96_444", 4), ("rstrow_gray_100x60", 3)])
 def test_shard_writes_only_its_mcus(ctx, planes, name, world):
@@ -362,7 +394,8 @@ def test_refusals_leave_the_context_usable(ctx, planes):
         assert f"({code})" in str(e.value), str(e.value)
         return str(e.value)
 
-    raises(E_ARG, pjd_amd.split_decode, _scanned(golden_bytes("rst4_128x96_444")).desc, [0, 0], pjd_amd.OUT_GRAY8)
+    rst = _scanned(golden_bytes("rst4_128x96_444"))                  # kept: its descriptor lies in memory the Scanned owns
+    raises(E_ARG, pjd_amd.split_decode, rst.desc, [0, 0], pjd_amd.OUT_GRAY8)
     for flag in (pjd_amd.F_SCALE_1_2, pjd_amd.F_SCALE_1_4, pjd_amd.F_SCALE_1_8):
         bad = _lj("lj_136x72_420_q90", flag)
         assert "image 1" in raises(E_ARG, ctx.batch, [good.desc, bad.desc], pjd_amd.OUT_GRAY8)
