@@ -835,6 +835,20 @@ int  pjd_plan_check(const pjd_image_desc *images, int n_images, int out_format, 
  * sustain, x 256 (the minimum mean weight of a cycle of the step graph, pim-jpeg-decoder_amd/csrc/pjd_plan.cpp).  PJD_E_ARG for a
  * picture that does not take the parallel decoder.  tests/test_planner_bound.py recomputes it another way.                        */
 int  pjd_plan_step_bits(const pjd_image_desc *image, uint32_t *step_bits_x256);
+/* Debug, host-only: the decode tables of a picture's table set as the entropy decoder holds them in LDS, built in host memory by the
+ * text the device builds them with (pim-jpeg-decoder_amd/csrc/pjd_lut_build.h; the layout: pjd_internal.h, PjdDevTset).
+ * *real_bytes: the size of the blob (a multiple of 16; 0: the set takes the exact kernel and has no decode tables).  *nominal_bytes: its
+ * size at 256 bytes per 9-bit prefix that starts longer codes -- the figure that ROUTES a set (over 20,480: the exact kernel), which
+ * the blob itself no longer reaches.  `slots` (6 bytes, may be NULL): [component][0 = DC, 1 = AC] -> which 2,048-byte first-level
+ * table of the blob the component decodes with.  `blob` (may be NULL: the sizes alone) receives *real_bytes bytes; PJD_E_ARG where
+ * `cap` is smaller, and for a progressive frame (no table set: the scans bring their tables).  tests/test_lut_layout.py checks
+ * every 16-bit window of it against a canonical matcher.                                                                          */
+int  pjd_plan_luts(const pjd_image_desc *image, void *blob, uint64_t cap, uint32_t *real_bytes, uint32_t *nominal_bytes, uint8_t *slots);
+/* Debug: what the runtime answers for the entropy decoder's launch of this batch on its device
+ * (hipOccupancyMaxActiveBlocksPerMultiprocessor): workgroups of pjd_k_huff_lanes one CU holds at the batch's dynamic LDS, and that
+ * size (`lds_bytes`, may be NULL: pjd_batch_info.huff_lds_bytes plus PJD_EXTRA_LDS of the environment).  Also printed by
+ * pjd_batch_get_info under PJD_DEBUG_STATS.                                                                                       */
+int  pjd_batch_huff_occupancy(pjd_batch *batch, int32_t *workgroups_per_cu, uint32_t *lds_bytes);
 
 /* Page-locked host memory (hipHostMalloc) for pjd_batch_download_packed; NULL on failure.       */
 void *pjd_host_alloc(uint64_t bytes);

@@ -24,6 +24,7 @@
 #include "../../include/pjd.h"
 #include "pjd_kernels.h"
 #include "pjd_libjpeg.h"
+#include "pjd_lut_build.h"
 #include "pjd_plan.h"
 #include "pjd_resize_plan.h"
 
@@ -1379,6 +1380,12 @@ int pjd_batch_get_info(pjd_batch *b, pjd_batch_info *info)
         info->lane_fill_x1024 = (uint32_t)st[PJD_STAT_FILL];  // the fullest lane region
     }
     info->n_huff_workgroups = P.hwgs.size();
+    if (b->dev.dbg) {                        // PJD_DEBUG_STATS: what the runtime makes of the entropy decoder's LDS
+        int wg = 0;
+        size_t lds = 0;
+        if (pjd_huff_lanes_occupancy(b->dev, &wg, &lds) == hipSuccess)
+            std::fprintf(stderr, "[pjd waves] pjd_k_huff_lanes: %zu B of LDS per workgroup, %d workgroups per CU\n", lds, wg);
+    }
     if (b->dev.dbg && b->decoded) {          // PJD_DEBUG_STATS: wave timeline of the last decode (units of 10 ns)
         const size_t nw = P.hwaves.size();
         std::vector<uint32_t> d(nw * 32);
@@ -1470,6 +1477,54 @@ int pjd_plan_step_bits(const pjd_image_desc *image, uint32_t *step_bits_x256)
     if (rc != PJD_OK) return rc;
     if (P.images.empty() || P.tset_step_bits.empty() || (P.images[0].flags & PJD_IF_SEQUENTIAL)) return PJD_E_ARG;   // no lane streams for this picture
     *step_bits_x256 = P.tset_step_bits[P.images[0].tset];
+    return PJD_OK;
+}
+
+int pjd_plan_luts(const pjd_image_desc *image, void *blob, uint64_t cap, uint32_t *real_bytes, uint32_t *nominal_bytes, uint8_t *slots)
+{
+    if (!image || !real_bytes || !nominal_bytes) return PJD_E_ARG;
+    PjdPlan P;
+    std::string err;
+    int rc = pjd_make_plan(image, 1, PJD_OUT_RGB8, P, err);
+    if (rc != PJD_OK) return rc;
+    if (P.images.empty() || P.tsets.empty() || (P.images[0].flags & PJD_IF_PROGRESSIVE)) return PJD_E_ARG;   // no table set: the scans bring their tables
+    const PjdDevImage &im = P.images[0];
+    const PjdDevTset &T = P.tsets[im.tset];
+    *real_bytes = T.lut_bytes;
+    *nominal_bytes = P.tset_nominal_bytes[im.tset];
+    if (slots) std::memcpy(slots, im.tbl_slot, 6);
+    if (!blob || T.lut_bytes == 0) return PJD_OK;
+    if (cap < T.lut_bytes) return PJD_E_ARG;
+    std::memset(blob, 0, T.lut_bytes);
+    uint16_t *b16 = static_cast<uint16_t *>(blob);
+    for (uint32_t slot = 0; slot < T.n_tables; slot++) {              // as one block of pjd_k_build_tables
+        const PjdDevHuffRaw &r = P.tables[(size_t)im.tset * PJD_MAX_TABLES + slot];
+        const uint32_t partner = r.is_ac ? slot : (uint32_t)T.pair_ac[slot];
+        const bool has_partner = partner < T.n_tables;
+        const PjdDevHuffRaw &r2 = P.tables[(size_t)im.tset * PJD_MAX_TABLES + (has_partner ? partner : slot)];
+        uint32_t first[17], first2[17];
+        pjd_lut_first_codes(r, first);
+        pjd_lut_first_codes(r2, first2);
+        uint32_t *L1 = reinterpret_cast<uint32_t *>(b16 + slot * (PJD_L1_BYTES / 2));
+        const uint16_t *cp = T.l2_cp[slot], *ce = T.l2_ce[slot];
+        const uint32_t p1 = T.l2_p1[slot];
+        for (uint32_t idx = 0; idx < (1u << PJD_LUT_BITS); idx++)
+            L1[idx] = pjd_lut_l1_entry(r, first, has_partner ? &r2 : nullptr, first2, cp, ce, p1, idx);
+        const uint32_t n2 = pjd_lut_l2_entries(cp, p1);
+        for (uint32_t j = 0; j < n2; j++) b16[ce[0] + j] = (uint16_t)pjd_lut_l2_entry(r, first, cp, ce, j);
+    }
+    return PJD_OK;
+}
+
+int pjd_batch_huff_occupancy(pjd_batch *b, int32_t *workgroups_per_cu, uint32_t *lds_bytes)
+{
+    if (!b || !workgroups_per_cu) return PJD_E_ARG;
+    hipSetDevice(b->ctx->device);
+    int n = 0;
+    size_t lds = 0;
+    if (pjd_huff_lanes_occupancy(b->dev, &n, &lds) != hipSuccess) return PJD_E_HIP;
+    *workgroups_per_cu = n;
+    if (lds_bytes) *lds_bytes = (uint32_t)lds;
     return PJD_OK;
 }
 

@@ -227,7 +227,7 @@ struct PjdDevScan {
 // One table set = the deduplicated Huffman tables of an image; images with identical sets share one (a batch of
 // files written with the Annex-K tables has a single set), and so can the waves of one Huffman workgroup.
 // Decode-ready form, built on the device by pjd_k_build_tables, one blob per set:
-//   [table 0 L1][table 1 L1]...[table n-1 L1][second-level regions, 128 u16 per long prefix]
+//   [table 0 L1][table 1 L1]...[table n-1 L1][second-level regions: 2 .. 128 u16 per long prefix, table by table]
 // L1 is indexed by the next PJD_LUT_BITS (9) bits and holds 32-bit entries; the LOW half describes the symbol that starts there --
 // every field the per-symbol loops need comes out with one AND or one bit-field extract, and the zigzag bookkeeping is ONE
 // subtraction (see PJD_LUT_ADV):
@@ -242,9 +242,11 @@ struct PjdDevScan {
 //               14 = the reference's "symbol 0xFF": no code starts with these bits (then 16 bits are consumed, as its
 //                    get_next_symbol does), or the table really holds the symbol 0xFF (jpeg_scanner.cpp:470,490)
 //               15 = a DC size > 11 / an AC size > 10 (jpeg_scanner.cpp:474,506)
-//   pointer entry (bits 4..0 == 0): codes with this 9-bit prefix are longer than 9 bits; bits 15..5 = u16 index (relative to the
-//               blob) / 128 of the prefix's 128-entry second-level table (u16 entries of the form above with code lengths 10..16),
-//               indexed by the following 7 bits.
+//   pointer entry (bits 4..0 == 0): codes with this 9-bit prefix P are longer than 9 bits.  The prefix has a second-level table
+//               of 2^k u16 entries of the form above (code lengths 10 .. 9 + k), 9 + k the LONGEST code under P (k = 1..7),
+//               indexed by the top k of the seven bits that follow the prefix.  Bits 9..5 = 32 - k: the right shift that leaves
+//               that index of the window moved up by the prefix (PJD_LUT_PTR_SHIFT); bits 31..16 = BYTE offset of the table,
+//               relative to the blob (PJD_LUT_PTR_BYTES: a pointer entry has no pair, the lookup overwrites the high half).
 // The HIGH half of an L1 entry describes the PAIR "this symbol and the one after it" where the 9 bits hold the first symbol whole
 // (code and value bits), it is a valid run/size symbol (not an EOB) or a valid DC symbol, and the rest of the 9 bits determine the next
 // code (any valid AC symbol, an EOB too; its value bits may lie outside) -- for a DC table: a code of the AC table its components
@@ -253,15 +255,18 @@ struct PjdDevScan {
 //   bits 31..28 value bits (size) of the second symbol (its value is the last `size` of the bits both consume)
 // Every pass takes a pair in ONE step when the first symbol neither completes the unit nor reaches the next checkpoint /
 // subsequence end: dense streams average 5 bits per symbol, 60 % of the steps there are pairs (profiles/r03_experiments.md).
-// Canonical codes keep all long codes in one contiguous range of prefixes [p0, p1), so the second level
-// costs 256 bytes per long prefix.
+// Canonical codes keep all long codes in one contiguous range of prefixes [p0, p1), and codes grow with their value: k does not fall
+// as P rises, only the last prefix or two of a table hold 15- or 16-bit codes (128 entries), the ones before them need 2 to 8.  The
+// second-level region of a table is the tables of its prefixes p0 .. p1 - 1 one after the other, described by the first prefix and the
+// first entry of every class k (an empty class starts where the next one does).  The Annex-K set: a blob of 8,784 bytes (at 256 bytes
+// per long prefix, the layout before this one and still the accounting that ROUTES a set, pjd_plan.cpp: 11,008).
 struct PjdDevTset {
     uint32_t lut_off16;                // blob offset in PjdDevBatch::luts, 16-byte units
     uint32_t lut_bytes;                // multiple of 16
     uint32_t n_tables;
-    uint16_t l2_off[PJD_MAX_TABLES];   // second-level region of table k: first u16 index, relative to the blob
-    uint16_t l2_p0[PJD_MAX_TABLES];    // 9-bit prefixes [p0, p1) hold codes longer than PJD_LUT_BITS
-    uint16_t l2_p1[PJD_MAX_TABLES];
+    uint16_t l2_cp[PJD_MAX_TABLES][PJD_L2_BITS];   // table t, class k = 1..7 at [k - 1]: the first 9-bit prefix whose longest code has 9 + k bits (l2_cp[t][0] = p0) ...
+    uint16_t l2_ce[PJD_MAX_TABLES][PJD_L2_BITS];   // ... and the u16 index, relative to the blob, of that prefix's table; prefix P of the class: + ((P - first) << k)
+    uint16_t l2_p1[PJD_MAX_TABLES];    // 9-bit prefixes [p0, p1) hold codes longer than PJD_LUT_BITS
     uint8_t  pair_ac[PJD_MAX_TABLES];  // of a DC table: the AC table (slot) every component that uses it decodes with -- its entries hold the pair
                                        // "DC symbol + the unit's first AC symbol" -- or 0xff (none: components disagree)
     uint8_t  pad_[2];
@@ -272,6 +277,8 @@ struct PjdDevTset {
 #define PJD_LUT_PAIR_USED(e)  (((e) >> 16) & 31u)  // == PJD_LUT_USED(e): no pair (the pair field then repeats the symbol's used / advance)
 #define PJD_LUT_PAIR_ADV(e)   (((e) >> 21) & 127u)
 #define PJD_LUT_PAIR_SIZE2(e) ((e) >> 28)
+#define PJD_LUT_PTR_SHIFT(e)  (((e) >> 5) & 31u)   // of a pointer entry: 32 - k
+#define PJD_LUT_PTR_BYTES(e)  ((e) >> 16)          // ... and the byte offset of the prefix's second-level table
 #define PJD_LUT_EOB      0x0800u
 #define PJD_LUT_BADSYM   14u
 #define PJD_LUT_BADLEN   15u

@@ -12,8 +12,8 @@
 // Once per upload (pjd_batch_upload: both depend on the batch's blob alone, and no kernel of a decode writes what they make):
 //   pjd_k_build_tables   raw (offsets, symbols) tables -> two-level decode table per TABLE SET (images with the
 //                        same Huffman tables share one): 9-bit first level (32-bit entries: the symbol, and the PAIR of
-//                        symbols where both fit), one 128-entry second-level table
-//                        per 9-bit prefix that holds longer codes; an entry already carries bits consumed /
+//                        symbols where both fit), one second-level table per 9-bit prefix that holds longer
+//                        codes, sized by the longest of them (2 .. 128 entries); an entry already carries bits consumed /
 //                        run / size / EOB / error (semantics of reference generate_codes / get_next_symbol /
 //                        the size limits of decode_MCU_component, reference src/jpeg_scanner.cpp:438-520)
 //   pjd_k_lane_words     the bitstream of every lane as big-endian 32-bit words counted from the lane's first
@@ -50,6 +50,7 @@
 
 #include "pjd_device_common.h"
 #include "pjd_kernels.h"
+#include "pjd_lut_build.h"
 #include "../../include/pjd.h"
 
 static_assert(sizeof(PjdDevHuffRaw) == 180, "raw table layout");
@@ -57,26 +58,9 @@ static_assert(PJD_LUT_BITS + PJD_L2_BITS == 16 && PJD_L1_BYTES == (4 << PJD_LUT_
 static_assert(PJD_HUFF_LANES == 64, "one wave per 64 lanes");
 static_assert(PJD_STAGE_ENTRIES == PJD_GROUP && PJD_GROUP == 16, "a group (a head word + 7 step words) is what one flush of the staging buffer writes");
 
-#define LUT_BAD     PJD_LUT_ENTRY(16u, 1u, false, PJD_LUT_BADSYM)    // no code: consume 16 bits (as the reference's get_next_symbol)
-
 // ---------------------------------------------------------------------------------------------
-// One block per (table set, table slot): two-level decode table (layout: pjd_internal.h).
-__device__ __forceinline__ uint32_t lut_entry(uint32_t len, uint32_t sym, bool is_ac)
-{
-    uint32_t run = 0, size, bad = 0;
-    bool eob = false;
-    if (sym == 0xFF) bad = PJD_LUT_BADSYM;                              // the reference reads a returned 0xFF as "no symbol" (jpeg_scanner.cpp:470,490)
-    if (is_ac) {
-        run = sym >> 4; size = sym & 15u;
-        if (sym == 0) eob = true;
-        else if (size > 10 && !bad) bad = PJD_LUT_BADLEN;               // jpeg_scanner.cpp:506
-    } else {
-        size = sym;
-        if (sym > 11 && !bad) bad = PJD_LUT_BADLEN;                     // jpeg_scanner.cpp:474
-    }
-    return PJD_LUT_ENTRY(len + (bad ? 0u : size), eob ? 32u : run + 1, eob, bad ? bad : size);   // EOB: 32 + 64 = 96 slots (pjd_internal.h)
-}
-
+// One block per (table set, table slot): two-level decode table (layout: pjd_internal.h; the entries: pjd_lut_build.h, which
+// pjd_plan_luts runs on the host).
 __global__ __launch_bounds__(256) void pjd_k_build_tables(PjdDevBatch B)
 {
     const uint32_t ts = blockIdx.x / PJD_MAX_TABLES, slot = blockIdx.x % PJD_MAX_TABLES;
@@ -85,59 +69,22 @@ __global__ __launch_bounds__(256) void pjd_k_build_tables(PjdDevBatch B)
     const PjdDevHuffRaw &r = B.raw_tables[(size_t)ts * PJD_MAX_TABLES + slot];
     uint16_t *blob = reinterpret_cast<uint16_t *>(B.luts + (size_t)T.lut_off16 * 16);
     uint32_t *L1 = reinterpret_cast<uint32_t *>(blob + slot * (PJD_L1_BYTES / 2));
-    const uint32_t l2_off = T.l2_off[slot], p0 = T.l2_p0[slot], p1 = T.l2_p1[slot];
-    const bool is_ac = r.is_ac != 0;
     // the table the SECOND symbol of a pair is decoded with: this one (AC), or the AC table of the components that use this DC table
-    const uint32_t partner = is_ac ? slot : (uint32_t)T.pair_ac[slot];
+    const uint32_t partner = r.is_ac ? slot : (uint32_t)T.pair_ac[slot];
     const bool has_partner = partner < T.n_tables;
     const PjdDevHuffRaw &r2 = B.raw_tables[(size_t)ts * PJD_MAX_TABLES + (has_partner ? partner : slot)];
     __shared__ uint32_t first[17], first2[17];
-    __shared__ uint8_t offs[17], offs2[17];
+    __shared__ uint16_t cp[PJD_L2_BITS], ce[PJD_L2_BITS];
     const uint32_t tid = threadIdx.x;
-    if (tid < 2) {
-        const PjdDevHuffRaw &q = tid ? r2 : r;
-        uint32_t *f = tid ? first2 : first;
-        uint32_t code = 0;                       // reference generate_codes (jpeg_scanner.cpp:438-448)
-        f[0] = 0;
-        for (int len = 1; len <= 16; len++) {
-            f[len] = code;
-            code = (code + (uint32_t)(q.offsets[len] - q.offsets[len - 1])) << 1;
-        }
-    }
-    if (tid < 17) { offs[tid] = r.offsets[tid]; offs2[tid] = r2.offsets[tid]; }
+    if (tid < 2) pjd_lut_first_codes(tid ? r2 : r, tid ? first2 : first);
+    if (tid < PJD_L2_BITS) { cp[tid] = T.l2_cp[slot][tid]; ce[tid] = T.l2_ce[slot][tid]; }
     __syncthreads();
-    // the symbol whose code is the leading bits of `bits` (`nbits` of them are known); 0 if none is determined by them.  Shortest match wins, as the reference's scan
-    auto match_in = [&](const PjdDevHuffRaw &q, const uint32_t *f, const uint8_t *o, bool ac, uint32_t bits, uint32_t nbits, uint32_t lo, uint32_t hi) -> uint32_t {
-        for (uint32_t len = lo; len <= hi && len <= nbits; len++) {
-            const uint32_t c = bits >> (nbits - len);
-            const uint32_t d = c - f[len], cnt = (uint32_t)o[len] - o[len - 1];
-            if (c >= f[len] && d < cnt) return lut_entry(len, q.symbols[o[len - 1] + d], ac);
-        }
-        return 0u;
-    };
-    auto match = [&](uint32_t bits, uint32_t nbits, uint32_t lo, uint32_t hi) -> uint32_t { return match_in(r, first, offs, is_ac, bits, nbits, lo, hi); };
-    for (uint32_t idx = tid; idx < (1u << PJD_LUT_BITS); idx += 256) {
-        uint32_t e = (idx >= p0 && idx < p1) ? (((l2_off + ((idx - p0) << PJD_L2_BITS)) >> PJD_L2_BITS) << 5) : LUT_BAD;      // pointer entry: bits 4..0 == 0
-        const uint32_t m = match(idx, PJD_LUT_BITS, 1, PJD_LUT_BITS);
-        if (m) e = m;
-        // the pair: this symbol whole inside the 9 bits, a valid run/size (or DC) symbol, and the bits after it determine the next code
-        uint32_t pair = 0;
-        if (has_partner && m && !(m & PJD_LUT_EOB) && PJD_LUT_SIZE(m) < PJD_LUT_BADSYM && PJD_LUT_USED(m) < PJD_LUT_BITS) {
-            const uint32_t rest = PJD_LUT_BITS - PJD_LUT_USED(m);
-            const uint32_t m2 = match_in(r2, first2, offs2, true, idx & ((1u << rest) - 1u), rest, 1, rest);
-            if (m2 && PJD_LUT_SIZE(m2) < PJD_LUT_BADSYM && PJD_LUT_USED(m) + PJD_LUT_USED(m2) <= 31u)
-                pair = (PJD_LUT_USED(m) + PJD_LUT_USED(m2)) | ((PJD_LUT_ADV(m) + PJD_LUT_ADV(m2)) << 5) | (PJD_LUT_SIZE(m2) << 12);   // size 2: bits 31..28 of the entry
-        }
-        // no pair: the pair field repeats the symbol's own used / advance (a "pair" that is the symbol alone), so the state-only
-        // passes need not ask whether there is one; the write pass tells a real pair by used12 != used
-        if (!pair) pair = e & 0xfffu;
-        L1[idx] = (e & 0xffffu) | (pair << 16);
-    }
-    for (uint32_t j = tid; j < ((p1 - p0) << PJD_L2_BITS); j += 256) {
-        const uint32_t w16 = (p0 << PJD_L2_BITS) + j;
-        const uint32_t m = match(w16, 16, PJD_LUT_BITS + 1, 16);
-        blob[l2_off + j] = (uint16_t)(m ? m : LUT_BAD);
-    }
+    const uint32_t p1 = T.l2_p1[slot];
+    for (uint32_t idx = tid; idx < (1u << PJD_LUT_BITS); idx += 256)
+        L1[idx] = pjd_lut_l1_entry(r, first, has_partner ? &r2 : nullptr, first2, cp, ce, p1, idx);
+    const uint32_t n2 = pjd_lut_l2_entries(cp, p1);
+    for (uint32_t j = tid; j < n2; j += 256)
+        blob[ce[0] + j] = (uint16_t)pjd_lut_l2_entry(r, first, cp, ce, j);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -372,9 +319,10 @@ __device__ __forceinline__ void chk_finish(const ChkCtx &K, uint32_t j, uint32_t
 __device__ __forceinline__ uint32_t lut_lookup_pair(uint32_t lbase, uint32_t tab, uint32_t pk)
 {
     uint32_t e = lds_u32(tab + 4 * __builtin_amdgcn_ubfe(pk, 32 - PJD_LUT_BITS, PJD_LUT_BITS));
-    // code longer than 9 bits (a pointer entry consumes no bits): one more read, in the 128-entry table of this 9-bit prefix
+    // code longer than 9 bits (a pointer entry consumes no bits): one more read, in the 2^k-entry table of this 9-bit prefix, at the
+    // top k of the seven bits behind the prefix
     if (__builtin_expect(PJD_LUT_USED(e) == 0, 0)) {
-        e = lds_u16(lbase + 2 * ((((e >> 5) & 0x7ffu) << PJD_L2_BITS) + ((pk >> 16) & ((1u << PJD_L2_BITS) - 1u))));
+        e = lds_u16(lbase + PJD_LUT_PTR_BYTES(e) + 2u * ((pk << PJD_LUT_BITS) >> PJD_LUT_PTR_SHIFT(e)));
         e |= e << 16;                                  // no pair: as the first-level entries say it (the size lands in size2: unused)
     }
     return e;
@@ -570,7 +518,7 @@ __device__ __forceinline__ int walk_lane(const PhaseCtx &P, WalkBuf &wb, uint32_
         do {                                                                                                                \
             const uint32_t ep_ = (uint32_t)__builtin_amdgcn_readlane((int)(E_), (int)(st & 63u));                           \
             const uint32_t pl_ = (uint32_t)__builtin_amdgcn_readlane((int)pk, (int)(st & 63u));                             \
-            const uint32_t e2_ = rfl(lds_u16(lbase + 2u * ((((ep_ >> 5) & 0x7ffu) << PJD_L2_BITS) + ((pl_ >> 16) & ((1u << PJD_L2_BITS) - 1u)))));   \
+            const uint32_t e2_ = rfl(lds_u16(lbase + PJD_LUT_PTR_BYTES(ep_) + 2u * ((pl_ << PJD_LUT_BITS) >> PJD_LUT_PTR_SHIFT(ep_))));             \
             st = st - WALK_PTR + (PJD_LUT_USED(e2_) - (PJD_LUT_ADV(e2_) << 8));                                             \
         } while (0)
         const uint32_t bias = 128u - klim;
@@ -1626,6 +1574,11 @@ void pjd_launch_lane_words(hipStream_t s, const PjdDevBatch &b)
 void pjd_launch_huff_lanes(hipStream_t s, const PjdDevBatch &b)
 {
     if (b.n_hwg) hipLaunchKernelGGL(pjd_k_huff_lanes, dim3(b.n_hwg), dim3(PJD_HUFF_THREADS), huff_lds_bytes(b), s, b, 0u, b.ticket);
+}
+hipError_t pjd_huff_lanes_occupancy(const PjdDevBatch &b, int *workgroups_per_cu, size_t *lds_bytes)
+{
+    *lds_bytes = huff_lds_bytes(b);
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(workgroups_per_cu, pjd_k_huff_lanes, PJD_HUFF_THREADS, *lds_bytes);
 }
 void pjd_launch_huff_lanes_group(hipStream_t s, const PjdDevBatch &b, const PjdDevGroup &g, uint32_t group_index)
 {

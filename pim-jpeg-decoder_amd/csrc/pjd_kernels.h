@@ -137,4 +137,7 @@ void pjd_launch_progressive(hipStream_t s, const PjdDevBatch &b, const uint32_t 
 void pjd_launch_build_tables(hipStream_t s, const PjdDevBatch &b);
 void pjd_launch_lane_words(hipStream_t s, const PjdDevBatch &b);     // bitstream -> per-lane big-endian words, transposed per wave
 void pjd_launch_huff_lanes(hipStream_t s, const PjdDevBatch &b);     // synchronise + stitch + scan + write
+// what the runtime says of that launch on the current device: workgroups of pjd_k_huff_lanes one CU holds at the batch's dynamic LDS
+// (*lds_bytes: that size, PJD_EXTRA_LDS included)
+hipError_t pjd_huff_lanes_occupancy(const PjdDevBatch &b, int *workgroups_per_cu, size_t *lds_bytes);
 void pjd_launch_huff_lanes_group(hipStream_t s, const PjdDevBatch &b, const PjdDevGroup &g, uint32_t group_index);   // the same for one picture group

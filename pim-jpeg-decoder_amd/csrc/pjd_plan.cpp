@@ -5,6 +5,7 @@
 // walk: per-image geometry, restart segments, Huffman subsequences (one decode
 // lane each), Huffman workgroups, IDCT/colour workgroups, packed table sets.
 #include "pjd_plan.h"
+#include "pjd_lut_build.h"
 
 #include <cstdio>
 #include <cstring>
@@ -361,39 +362,33 @@ int pjd_make_plan(const pjd_image_desc *images, int n, int out_format, PjdPlan &
             std::memset(&T, 0, sizeof T);
             T.n_tables = (uint32_t)nt;
             P.tables.resize((size_t)(ts + 1) * PJD_MAX_TABLES, PjdDevHuffRaw());
-            // decode-table layout (pjd_internal.h): first-level tables, then one 128-entry second-level table per
-            // 9-bit prefix that holds codes longer than 9 bits.  Over-subscribed tables (not a prefix code) and
-            // tables whose long codes need more LDS than PJD_LUT_LDS_MAX go to the exact kernel.
+            // decode-table layout (pjd_internal.h): first-level tables, then one second-level table per 9-bit prefix
+            // that holds codes longer than 9 bits, sized by the longest of them.  Over-subscribed tables (not a prefix
+            // code) and tables whose long codes need more than PJD_LUT_LDS_MAX at 128 entries (256 bytes) per prefix -- the
+            // NOMINAL size: the rule is older than the sized tables and routing stays what it was -- go to the exact kernel.
             bool ok = true;
             uint32_t set_min_bits = 16;
-            uint32_t lut_bytes = (uint32_t)nt * PJD_L1_BYTES;
+            uint32_t lut_bytes = (uint32_t)nt * PJD_L1_BYTES, nominal_bytes = lut_bytes;
             for (int k = 0; k < nt; k++) {
                 PjdDevHuffRaw &r = P.tables[(size_t)ts * PJD_MAX_TABLES + k];
                 std::memcpy(r.offsets, seen[k]->offsets, 17);
                 std::memcpy(r.symbols, seen[k]->symbols, 162);
                 r.is_ac = seen_ac[k];
-                uint32_t code = 0, end10 = 0;
-                for (int len = 1; len <= 16; len++) {            // reference generate_codes (jpeg_scanner.cpp:438-448)
-                    const uint32_t cnt = (uint32_t)r.offsets[len] - r.offsets[len - 1];
+                for (int len = 1; len <= 16; len++) {
                     // bits the cheapest symbol of this length consumes: code + value bits (an out-of-range size stores no value)
                     for (uint32_t q = r.offsets[len - 1]; q < r.offsets[len] && q < 162; q++) {
                         const uint32_t sym = r.symbols[q], size = seen_ac[k] ? ((sym & 15u) > 10 ? 0u : (sym & 15u)) : (sym > 11 ? 0u : sym);
                         if ((uint32_t)len + size < P.min_sym_bits) P.min_sym_bits = (uint32_t)len + size;
                         if ((uint32_t)len + size < set_min_bits) set_min_bits = (uint32_t)len + size;
                     }
-                    if (code + cnt > (1u << len)) ok = false;
-                    if (len == PJD_LUT_BITS) end10 = code + cnt;
-                    code = (code + cnt) << 1;
                 }
-                const uint32_t end16 = code >> 1;
-                const uint32_t np = 1u << PJD_LUT_BITS;
-                uint32_t p0 = end10 < np ? end10 : np, p1 = (end16 + (1u << PJD_L2_BITS) - 1) >> PJD_L2_BITS;
-                if (p1 > np) p1 = np;
-                if (p1 < p0 || !ok) p1 = p0;
-                T.l2_p0[k] = (uint16_t)p0; T.l2_p1[k] = (uint16_t)p1;
-                T.l2_off[k] = (uint16_t)(lut_bytes / 2);
-                lut_bytes += (p1 - p0) * (2u << PJD_L2_BITS);
-                if (lut_bytes > PJD_LUT_LDS_MAX) ok = false;
+                if (!pjd_lut_geometry(r, T.l2_cp[k], T.l2_p1[k])) ok = false;
+                if (!ok) T.l2_p1[k] = T.l2_cp[k][0];             // no second level (as the geometry of a table that is no prefix code): no decode table for this set
+                for (int c = 1; c < PJD_L2_BITS; c++)
+                    if (T.l2_cp[k][c] > T.l2_p1[k]) T.l2_cp[k][c] = T.l2_p1[k];
+                lut_bytes += 2u * pjd_lut_l2_entries(T.l2_cp[k], T.l2_p1[k], lut_bytes / 2, T.l2_ce[k]);
+                nominal_bytes += ((uint32_t)T.l2_p1[k] - T.l2_cp[k][0]) * (2u << PJD_L2_BITS);
+                if (nominal_bytes > PJD_LUT_LDS_MAX) ok = false;
             }
             std::memcpy(T.pair_ac, pair_ac, sizeof pair_ac);
             {
@@ -411,6 +406,7 @@ int pjd_make_plan(const pjd_image_desc *images, int n, int out_format, PjdPlan &
             if (T.lut_bytes > P.max_lut_bytes) P.max_lut_bytes = T.lut_bytes;
             P.tsets.push_back(T);
             tset_parallel.push_back(ok ? 1 : 0);
+            P.tset_nominal_bytes.push_back((uint32_t)align_up(nominal_bytes, 16));
             tset_min_bits.push_back(set_min_bits < 1 ? 1u : set_min_bits);
         }
         g.tset = progressive ? 0u : found->second;

@@ -65,6 +65,7 @@ struct PjdPlan {
     bool dc_per_picture = false;           // the single chain settles verdict and DC predictors with pjd_k_group_dc, one workgroup per picture (pjd_plan.cpp)
     int plan_mode = 0;                     // PJD_PLAN_*
     std::vector<uint32_t> tset_step_bits;  // per table set: fewest bits of stream per step of the write pass, x 256 (sizes the lane regions)
+    std::vector<uint32_t> tset_nominal_bytes;   // per table set: its blob at 256 bytes per long prefix -- what routes the set (PJD_LUT_LDS_MAX), not what it occupies
 };
 
 // Returns PJD_OK or PJD_E_ARG (with a message in `err`).

@@ -416,6 +416,14 @@ class Batch:
         self.ctx._check(self.L.pjd_batch_get_info(self._h, C.byref(bi)), "pjd_batch_get_info")
         return {k: (list(getattr(bi, k)) if k == "flag_waves" else (float(getattr(bi, k)) if k == "exact_fallback_ms" else int(getattr(bi, k)))) for k, _ in bi._fields_}
 
+    def huff_occupancy(self):
+        """pjd_batch_huff_occupancy: (workgroups of the entropy decoder one CU holds, as the runtime computes it; the dynamic LDS it asked with)."""
+        self.L.pjd_batch_huff_occupancy.restype = C.c_int32
+        self.L.pjd_batch_huff_occupancy.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]
+        n, lds = C.c_int32(), C.c_uint32()
+        self.ctx._check(self.L.pjd_batch_huff_occupancy(self._h, C.byref(n), C.byref(lds)), "pjd_batch_huff_occupancy")
+        return int(n.value), int(lds.value)
+
     def output_size(self, i):
         return int(self.L.pjd_batch_output_size(self._h, i))
 
@@ -745,6 +753,22 @@ def plan_step_bits(desc):
     if rc != 0:
         raise PjdError(f"pjd_plan_step_bits failed ({rc})")
     return v.value / 256.0
+
+
+def plan_luts(desc):
+    """Host-only, debug (pjd_plan_luts): the decode tables of the picture's table set as the entropy decoder holds them in LDS ->
+    (blob as np.uint8 of the real size, nominal size -- the one that routes the set --, slots as a [3][2] list: [component][DC, AC] ->
+    first-level table).  An empty blob: the set takes the exact kernel."""
+    L = dev_lib()
+    L.pjd_plan_luts.restype = C.c_int32
+    L.pjd_plan_luts.argtypes = [C.POINTER(ImageDesc), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_void_p]
+    real, nominal = C.c_uint32(), C.c_uint32()
+    slots = np.zeros(6, np.uint8)
+    blob = np.zeros(6 * 2048 + 8192 + 16, np.uint8)          # PJD_LUT_LDS_MAX: no blob is larger
+    rc = L.pjd_plan_luts(C.byref(desc), blob.ctypes.data, blob.size, C.byref(real), C.byref(nominal), slots.ctypes.data)
+    if rc != 0:
+        raise PjdError(f"pjd_plan_luts failed ({rc})")
+    return blob[: real.value].copy(), int(nominal.value), slots.reshape(3, 2).tolist()
 
 
 def plan_info(descs, out_format=OUT_RGB8):
