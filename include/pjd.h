@@ -197,11 +197,21 @@ extern "C" {
  *          B = clamp(Y + ((116130*cb + 32768) >> 16))
  *      A one-component picture gives R = G = B = Y.
  * tests/test_libjpeg_cpu.py and tests/test_gpu_libjpeg.py hold this against Pillow's decode of files Pillow wrote: zero tolerance.
- * tests/test_libjpeg_corpus_cpu.py and tests/test_gpu_libjpeg_corpus.py do so on a seeded family up to libjpeg's 65500-sample limit.
+ * tests/test_libjpeg_corpus_cpu.py and tests/test_gpu_libjpeg_corpus.py do so on a seeded family up to libjpeg's 65500-sample limit;
+ * tests/test_libjpeg_progressive_cpu.py and tests/test_gpu_libjpeg_progressive.py on progressive frames under scan scripts no encoder
+ * writes (tests/golden/libjpeg_progressive/), and hold incomplete and broken progressive frames to the arithmetic above.
  *
  * ENVELOPE.  Baseline and progressive frames (with PJD_F_PROGRESSIVE Pillow's progressive files equal Pillow's decode); sampling
  * 4:4:4, 4:2:2 (h2v1), 4:2:0, or one component; the parallel path, PJD_F_FORCE_SEQUENTIAL and the exact-kernel fallback of
- * pjd_batch_sync; captured graphs.  pjd_batch_create returns PJD_E_ARG (pjd_last_error names the picture) for the flag together with
+ * pjd_batch_sync; captured graphs.  A PROGRESSIVE frame equals libjpeg's picture only where its scans leave every coefficient fully
+ * refined (each slot of each component reached by a first scan and by every refinement scan down to Al = 0), whatever the order,
+ * bands, restart intervals and table ids of the scans.  Otherwise -- a scan script that stops early -- and behind an entropy-coding
+ * error, P is THIS LIBRARY'S definition: the arithmetic above on the coefficients decoded so far (a slot no scan reached is 0, a slot
+ * refined down to Al keeps its low Al bits zero, scans behind an error are not run).  What is not reproduced is libjpeg's interblock
+ * smoothing (jdcoefct.c, do_block_smoothing), which it applies to a progressive frame whose coefficients are not fully refined: on
+ * five pictures of tests/golden/libjpeg_progressive/ rewritten without their last four scans Pillow's decode lies 19, 10, 3, 3 and 2
+ * levels from P (136 x 72 4:2:0 q50, 259 x 19 4:2:2 q75, 40 x 24 4:4:4 q95, 33 x 31 grey q85, 61 x 45 4:2:0 q90; the complete files:
+ * 0).  pjd_batch_create returns PJD_E_ARG (pjd_last_error names the picture) for the flag together with
  * PJD_F_SCALE_* (libjpeg's reduced IDCTs are other filters), with 4:4:0 (h1v2) sampling, with two components, or on a shard
  * (so pjd_split_decode refuses a flagged descriptor too).  pjd_batch_download_coefficients returns the coefficients as under
  * PJD_F_STANDARD_ZIGZAG.

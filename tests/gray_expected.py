@@ -62,6 +62,24 @@ def neutral_chroma_picture(port, data):
     return o["huff_rc"], rgb
 
 
+def ref_plane_of_coefficients(port, twin, coef):
+    """The expected H x W plane under the reference's arithmetic for coefficients given in the download's layout (n_dpus x 19200), as
+    neutral_chroma_picture makes it: a progressive frame, which the oracle cannot entropy-decode, brings the coefficients of the
+    model of tests/jpeg_progressive.py and `twin`, a baseline file of the same frame, for the metadata.  The caller sets the port's
+    zigzag map."""
+    o = port.parse(twin)
+    assert o["info"]["valid"]
+    meta = o["metadata"]
+    mcus = np.array(coef, np.int16).reshape(-1, 19200)
+    mcus.reshape(mcus.shape[0], 25, 3, 256)[:, :, 1:, :] = 0
+    for d in range(mcus.shape[0]):
+        port.L.orc_dpu_exec(meta.ctypes.data, mcus[d].ctypes.data)
+    rgb = np.zeros((o["info"]["height"], o["info"]["width"], 3), np.uint8)
+    port.L.orc_rgb_from_mcus(meta.ctypes.data, mcus.ctypes.data, rgb.ctypes.data)
+    assert np.array_equal(rgb[:, :, 0], rgb[:, :, 1]) and np.array_equal(rgb[:, :, 0], rgb[:, :, 2])
+    return np.ascontiguousarray(rgb[:, :, 0])
+
+
 def ref_plane(port, data):
     """(status, expected H x W plane) under the reference's arithmetic."""
     st, rgb = neutral_chroma_picture(port, data)
