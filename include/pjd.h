@@ -37,6 +37,8 @@
  *                                                       decodes, bit for bit (islow IDCT, fancy upsampling, JFIF colour), per picture
  *   (none: an addition)                                 PJD_OUT_GRAY8 + pjd_output_channels: pictures as ONE 8-bit plane, the luma as libjpeg's
  *                                                       JCS_GRAYSCALE delivers it (a third of the bytes, no chroma work in the back end)
+ *   (none: an addition)                                 PJD_F_LIBJPEG_SCALE_* + pjd_libjpeg_idct_scaled: libjpeg's reduced decode at 1/2, 1/4,
+ *                                                       1/8 (its scaled IDCTs: Pillow's draft(), OpenCV's IMREAD_REDUCED_*), bit for bit
  *
  * Plain pointers and sizes only; no C++ or torch types.  Thread model: one
  * submitting thread per pjd_ctx (the reference has one consumer thread,
@@ -229,6 +231,62 @@ extern "C" {
 int  pjd_libjpeg_idct(const int16_t coef[64], const uint16_t q[64], uint8_t out[64]);            /* host only, no device needed */
 int  pjd_libjpeg_ycc_to_rgb(uint8_t y, uint8_t cb, uint8_t cr, uint8_t rgb[3]);                /* host only, no device needed */
 int  pjd_libjpeg_upsample_row(const uint8_t *cur, const uint8_t *nb, int v, uint32_t n, uint8_t *out /* 2n */);   /* host only */
+
+/* ---- libjpeg-exact REDUCED-SIZE decode ------------------------------------------------------------------------------------------- *
+ * PJD_F_LIBJPEG_SCALE_*, per picture, only together with PJD_F_LIBJPEG: the picture P is the one libjpeg decodes with scale_num /
+ * scale_denom = 1/s, s = 2, 4 or 8 -- Pillow's Image.draft() and thumbnail(), OpenCV's IMREAD_REDUCED_*, draft-before-resize loaders
+ * -- through its reduced IDCTs (jidctred.c), byte for byte.  P is ceil(W/s) x ceil(H/s); pjd_scaled_dims, pjd_image_output_size,
+ * pjd_batch_output_size and the BMP header give that size, and everything downstream (resize filters, windows, orientation, pad,
+ * normalised output, bound output) reads this P.  These are bits of their own: PJD_F_SCALE_* stays the box filter, which is not what
+ * libjpeg does, and stays refused together with PJD_F_LIBJPEG.
+ *
+ * THE ARITHMETIC (normative; 32-bit two's complement that WRAPS, shifts arithmetic; coefficients, d[k] = coef[k] * Q[k], the zigzag and
+ * "never decoded is 0" as in the section above).  Let n = 8/s.
+ *   SIZES (libjpeg jdmaster.c).  A luma unit becomes n x n samples.  A chroma unit becomes cn x cn: cn starts at n and doubles while
+ *   cn < 8, 2*cn <= hs*n and 2*cn <= vs*n.  So 4:4:4 and one component: cn = n.  4:2:2 (h2v1): cn = n, the h2v1 upsampling remains.
+ *   4:2:0: cn = 2n and NO upsampling is left -- at 1/2 the chroma units go through the full jpeg_idct_islow, at 1/4 through the 4x4
+ *   transform, at 1/8 through the 2x2 one.
+ *   TRANSFORMS (libjpeg jidctred.c).  Each output o is (o + (1 << (sh-1))) >> sh; the sample is clamp(o + 128, 0, 255).  No
+ *   data-dependent form: libjpeg's DC-only shortcut gives the value of the full pass.
+ *     8x8  as in the section above.
+ *     4x4  the 1-D kernel reads i0, i1, i2, i3, i5, i6, i7 (input 4 is never read):
+ *              t0 = i0 << 14;  t2 = i2*15137 - i6*6270;  t10 = t0 + t2;  t12 = t0 - t2
+ *              a0 = -i7*1730 + i5*11893 - i3*17799 + i1*8697
+ *              a2 = -i7*4176 - i5*4926  + i3*7373  + i1*20995
+ *              o0 = t10 + a2;  o1 = t12 + a0;  o2 = t12 - a0;  o3 = t10 - a2
+ *          Pass 1 runs on columns 0, 1, 2, 3, 5, 6, 7 of d (rows as inputs) with sh = 12 into a workspace of 4 rows x 8 columns; pass 2
+ *          on each of the 4 workspace rows, reading columns 0, 1, 2, 3, 5, 6, 7, with sh = 19.
+ *     2x2  the 1-D kernel reads i0, i1, i3, i5, i7:
+ *              t10 = i0 << 15;  t0 = -i7*5906 + i5*6967 - i3*10426 + i1*29692;  o0 = t10 + t0;  o1 = t10 - t0
+ *          Pass 1 runs on columns 0, 1, 3, 5, 7 with sh = 13; pass 2 on the 2 workspace rows over the same columns with sh = 20.
+ *     1x1  clamp(((d[0] + 4) >> 3) + 128, 0, 255).
+ *   UPSAMPLING.  Only 4:2:2 has any left.  The chroma plane has dw = ceil(W*cn/16) columns and dh = ceil(H*cn/8) rows that belong to
+ *   the picture; samples beyond them never contribute.  Where n > 1 and dw > 2 it is the h2v1 fancy rule of step 3 above; at 1/8
+ *   (n = 1: libjpeg switches fancy upsampling off when min_DCT_scaled_size is 1) and where dw <= 2 it is plain replication.
+ *   COLOUR.  Step 4 above, unchanged.
+ *   GREY (PJD_OUT_GRAY8): the luma plane at n x n per unit -- what draft("L", ...) delivers.
+ *   Behind an entropy-coding error every sample is 128 at every scale.  For streams whose values overflow the caveat of the full-size
+ *   section holds: this text, not libjpeg, is the definition.
+ * VERIFIED on the CPU against Pillow 12.2.0 (libjpeg-turbo) with a numpy model of this text fed the oracle port's coefficients: 16
+ * sizes from 1x1 to 259x19, 4:4:4, 4:2:2, 4:2:0 and one component, q 50 / 90 / 100, scales 1/1 .. 1/8, RGB and draft("L") of colour
+ * files: 672 decodes each way, zero differing bytes.  tests/test_libjpeg_scaled_cpu.py and tests/test_gpu_libjpeg_scaled.py hold the
+ * model, the export below and the kernels against Pillow's recorded draft decodes (tests/golden/libjpeg_scaled/): zero tolerance.
+ *
+ * ENVELOPE.  That of PJD_F_LIBJPEG (no 4:4:0, no two components, no shard).  pjd_batch_create / pjd_plan_check return PJD_E_ARG, the
+ * picture named, for one of these bits without PJD_F_LIBJPEG and for one together with PJD_F_SCALE_*.  A batch may mix flagged
+ * pictures at any of the four scales with unflagged pictures, box-scaled or not; the unflagged ones and the full-size flagged ones
+ * keep the very kernels they have without this feature.  Coefficients and status words do not depend on the scale.
+ * HOW.  The reduced pictures' ranges go through kernels of their own in the same two launches' places (timed under the same names
+ * "idct_std", "colour_std", "idct_gray_std"): pass 1 only on the columns a transform reads, a unit row's n samples as one store, the
+ * component planes at the reduced geometry (luma mcux*hs*n x mcuy*vs*n, chroma mcux*cn x mcuy*cn: device_bytes shrinks with them).
+ * DETECTION.  No struct changed and PJD_VERSION stays 6: a caller checks for the symbol pjd_libjpeg_idct_scaled -- the inline the
+ * kernels run, host only: n x n samples of one unit for n = 8, 4, 2 or 1 (coef and q in natural order), PJD_E_ARG for any other n or a
+ * null pointer.  An older library ignores the bits and returns full-size pictures.                                                    */
+#define PJD_F_LIBJPEG_SCALE_1_2   128u
+#define PJD_F_LIBJPEG_SCALE_1_4   256u
+#define PJD_F_LIBJPEG_SCALE_1_8   384u
+#define PJD_F_LIBJPEG_SCALE_MASK  384u
+int  pjd_libjpeg_idct_scaled(const int16_t coef[64], const uint16_t q[64], uint32_t n, uint8_t *out /* n*n */);   /* host only */
 
 /* ---- grey output ----------------------------------------------------------------------------------------------------------------- *
  * PJD_OUT_GRAY8, chosen per batch: every picture leaves as ONE plane, uint8[H][W], top-down, tight rows, W*H bytes, W and H at the
@@ -870,7 +928,7 @@ uint64_t pjd_output_size(uint32_t width, uint32_t height, int out_format);
  * no format.  Host only (no device needed).  PJD_OUT_GRAY8 changed no struct and no version: a caller that needs it checks for it by
  * this symbol, which is exported from the first library that knows the format.                                                    */
 int  pjd_output_channels(int out_format);
-/* Output dimensions of a width x height picture under descriptor flags `flags` (PJD_F_SCALE_*): ceil(W/s) x ceil(H/s).  Returns PJD_OK. */
+/* Output dimensions of a width x height picture under descriptor flags `flags` (PJD_F_SCALE_*, or PJD_F_LIBJPEG_SCALE_*): ceil(W/s) x ceil(H/s).  Returns PJD_OK. */
 int  pjd_scaled_dims(uint32_t width, uint32_t height, uint32_t flags, uint32_t *out_w, uint32_t *out_h);
 /* Size in bytes of the picture of one descriptor in a given output format, at its output scale: what pjd_batch_output_size,
  * pjd_decode_batch and pjd_split_decode use.  0 for a null descriptor.                                                       */

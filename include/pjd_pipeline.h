@@ -61,7 +61,8 @@ typedef struct pjd_pipe_opts {
     int32_t n_devices;       /* entries in `devices` (at most PJD_PIPE_MAX_DEVICES)            */
     uint32_t scan_options;   /* PJD_SCAN_* of pjd_host.h handed to the scanner (0 = the reference's accept / reject set) */
     uint32_t image_flags;    /* PJD_F_* ORed into every descriptor the scanner produces: PJD_F_SCALE_* (reduced-size pictures
-                                for the sink), PJD_F_STANDARD_*, PJD_F_LIBJPEG (libjpeg's pictures); 0 = as scanned.
+                                for the sink), PJD_F_STANDARD_*, PJD_F_LIBJPEG (libjpeg's pictures; with PJD_F_LIBJPEG_SCALE_* its reduced decode: the
+                                sink receives the reduced picture); 0 = as scanned.
                                 With PJD_F_LIBJPEG every scanned picture is tested on its own before its batch is built
                                 (pjd_plan_check, host only): one outside that mode's envelope, such as 4:4:0 sampling or
                                 two components, is left out of the batch and handed to the sink with status -2 and no

@@ -651,11 +651,11 @@ bool ctx_group_streams(pjd_ctx *ctx, size_t ng)
 
 // Dense input: the ranges of the form's default kernel, then those of the PJD_F_LIBJPEG pictures (none: no launch) -- the exact path of
 // a decode and the fallback of settle(), which brings a scratch (dv.coef) and lists of its own
-void launch_dense(hipStream_t s, const pjd_batch *b, const PjdDevBatch &dv, const PjdDevIdctWg *wgs, size_t n, const PjdDevIdctWg *wgs_std, size_t n_std,
+void launch_dense(hipStream_t s, const pjd_batch *b, const PjdDevBatch &dv, const PjdDevIdctWg *wgs, size_t n, const PjdDevIdctWg *wgs_std, size_t n_std, size_t n_red,
                   const uint64_t *dense_base)
 {
     pjd_launch_idct_dense(s, dv, b->back, wgs, dense_base, (uint32_t)n);
-    pjd_launch_idct_std_dense(s, dv, b->back, wgs_std, dense_base, (uint32_t)n_std, b->d_planes);
+    pjd_launch_idct_std_dense(s, dv, b->back, wgs_std, dense_base, (uint32_t)n_std, (uint32_t)n_red, b->d_planes);     // n_std at full size, then n_red reduced
 }
 
 // Resize on decode: every picture from the intermediate (dev.out) to its target size in the result buffer, one launch, then the border
@@ -737,7 +737,10 @@ int enqueue_decode(pjd_batch *b, pjd_timings *timings, bool use_groups)
             // kernel, those of the flagged ones into their planes (a grey batch: straight into the picture)
             pjd_launch_idct_lanes(s, b->dev, F, P.libjpeg ? b->dev.iwg_order : nullptr, P.libjpeg ? P.n_iwg_def : b->dev.n_iwg);
             kt.mark(F.gray() ? "idct_gray" : "idct_colour");
-            if (P.n_iwg_std) { pjd_launch_idct_std_lanes(s, b->dev, F, b->dev.iwg_order + P.n_iwg_def, P.n_iwg_std, b->d_planes); kt.mark(F.gray() ? "idct_gray_std" : "idct_std"); }
+            if (P.n_iwg_std + P.n_iwg_red) {         // the reduced pictures' ranges (PJD_F_LIBJPEG_SCALE_*) stand behind: a launch of their own, one timed name
+                pjd_launch_idct_std_lanes(s, b->dev, F, b->dev.iwg_order + P.n_iwg_def, P.n_iwg_std, P.n_iwg_red, b->d_planes);
+                kt.mark(F.gray() ? "idct_gray_std" : "idct_std");
+            }
         }
     }
     if (!b->seq_list.empty()) {
@@ -745,12 +748,12 @@ int enqueue_decode(pjd_batch *b, pjd_timings *timings, bool use_groups)
         pjd_launch_zero(s, b->dev.coef, P.dense_du * 64 * sizeof(int16_t));      // a kernel, not a memset node: see the reset above
         pjd_launch_huff_sequential(s, b->dev, b->d_seq_list, b->d_seq_base, (uint32_t)b->seq_list.size());
         if (!P.pscans.empty()) pjd_launch_progressive(s, b->dev, b->d_seq_list, b->d_seq_base, (uint32_t)b->seq_list.size());
-        launch_dense(s, b, b->dev, b->d_iwgs_dense, P.iwgs_dense.size(), b->d_iwgs_dense_std, P.iwgs_dense_std.size(), b->d_seq_base);
+        launch_dense(s, b, b->dev, b->d_iwgs_dense, P.iwgs_dense.size(), b->d_iwgs_dense_std, P.libjpeg ? P.n_dense_std : 0, P.libjpeg ? P.n_dense_red : 0, b->d_seq_base);
         kt.mark("exact_path");
     }
     if (P.libjpeg && !F.gray()) {
         // the flagged pictures' planes are complete, whichever front end filled them: upsample, colour, store
-        pjd_launch_colour_std(s, b->dev, b->d_cwgs_std, (uint32_t)P.cwgs_std.size(), b->d_planes);
+        pjd_launch_colour_std(s, b->dev, b->d_cwgs_std, P.n_cwg_std, P.n_cwg_red, b->d_planes);
         kt.mark("colour_std");
     }
     launch_resample(s, b, &kt);          // behind whatever form the back end took (the groups' streams have joined `s` above)
@@ -789,7 +792,7 @@ int settle(pjd_batch *b)
     if (b->counted) { g_active[ctx->device].fetch_sub(1); b->counted = false; }       // this decode has left the device
     std::vector<uint32_t> fb;
     std::vector<uint64_t> fb_base;
-    std::vector<PjdDevIdctWg> fb_wgs, fb_wgs_std;          // ranges to redo: of the default back end, of the PJD_F_LIBJPEG one
+    std::vector<PjdDevIdctWg> fb_wgs, fb_wgs_std, fb_wgs_red;      // ranges to redo: of the default back end, of the PJD_F_LIBJPEG one at full size and reduced
     std::vector<char> was_seq(n, 0);
     for (uint32_t i : b->seq_list) was_seq[i] = 1;
     uint64_t du = 0;
@@ -799,7 +802,7 @@ int settle(pjd_batch *b)
             for (uint32_t k = 0; k < g.n_iwg; k++) {
                 PjdDevIdctWg w = P.iwgs[g.iwg_base + k];
                 w.pad_ = (uint32_t)fb.size();
-                ((g.flags & PJD_IF_LIBJPEG) ? fb_wgs_std : fb_wgs).push_back(w);
+                ((g.flags & PJD_IF_LIBJPEG) ? ((g.flags & PJD_IF_LJSCALE_MASK) ? fb_wgs_red : fb_wgs_std) : fb_wgs).push_back(w);
             }
             fb.push_back((uint32_t)i);
             fb_base.push_back(du);
@@ -814,8 +817,9 @@ int settle(pjd_batch *b)
         hipEvent_t ev0 = nullptr, ev1 = nullptr;
         (void)hipEventCreate(&ev0); (void)hipEventCreate(&ev1);
         int16_t *coef = nullptr; uint32_t *d_list = nullptr; uint64_t *d_base = nullptr; PjdDevIdctWg *d_wgs = nullptr;
-        const size_t n_def = fb_wgs.size(), n_std = fb_wgs_std.size();
+        const size_t n_def = fb_wgs.size(), n_std = fb_wgs_std.size(), n_red = fb_wgs_red.size();
         fb_wgs.insert(fb_wgs.end(), fb_wgs_std.begin(), fb_wgs_std.end());       // one list on the device: the default ranges, then the others
+        fb_wgs.insert(fb_wgs.end(), fb_wgs_red.begin(), fb_wgs_red.end());
         auto cleanup = [&] { hipFree(coef); hipFree(d_list); hipFree(d_base); hipFree(d_wgs); };
         if (hipMalloc((void **)&coef, du * 64 * sizeof(int16_t)) != hipSuccess || hipMalloc((void **)&d_list, fb.size() * sizeof(uint32_t)) != hipSuccess ||
             hipMalloc((void **)&d_base, fb.size() * sizeof(uint64_t)) != hipSuccess || hipMalloc((void **)&d_wgs, fb_wgs.size() * sizeof(PjdDevIdctWg)) != hipSuccess) {
@@ -837,9 +841,9 @@ int settle(pjd_batch *b)
         if (e == hipSuccess) {
             if (ev0) (void)hipEventRecord(ev0, s);
             pjd_launch_huff_sequential(s, dv, d_list, d_base, (uint32_t)fb.size());
-            launch_dense(s, b, dv, d_wgs, n_def, d_wgs + n_def, n_std, d_base);
+            launch_dense(s, b, dv, d_wgs, n_def, d_wgs + n_def, n_std, n_red, d_base);
             // flagged pictures had their planes filled again: the colour launch (all flagged pictures of the batch: a rare path)
-            if (n_std && !b->back.gray()) pjd_launch_colour_std(s, dv, b->d_cwgs_std, (uint32_t)P.cwgs_std.size(), b->d_planes);
+            if (n_std + n_red && !b->back.gray()) pjd_launch_colour_std(s, dv, b->d_cwgs_std, P.n_cwg_std, P.n_cwg_red, b->d_planes);
             if (ev1) (void)hipEventRecord(ev1, s);
             // the pictures just decoded again changed in the intermediate: resample (the whole batch: a rare path)
             launch_resample(s, b, nullptr);
@@ -1087,6 +1091,19 @@ int pjd_libjpeg_idct(const int16_t coef[64], const uint16_t q[64], uint8_t out[6
     return PJD_OK;
 }
 
+// ... and the reduced transforms of PJD_F_LIBJPEG_SCALE_*: n x n samples of one unit, n = 8 (the function above), 4, 2 or 1
+int pjd_libjpeg_idct_scaled(const int16_t coef[64], const uint16_t q[64], uint32_t n, uint8_t *out)
+{
+    if (!coef || !q || !out) return PJD_E_ARG;
+    switch (n) {
+        case 8: return pjd_libjpeg_idct(coef, q, out);
+        case 4: pjd_lj_idct_unit<4>(coef, q, out); return PJD_OK;
+        case 2: pjd_lj_idct_unit<2>(coef, q, out); return PJD_OK;
+        case 1: out[0] = (uint8_t)pjd_lj_sample_1x1(pjd_lj_dequant(coef[0], q[0])); return PJD_OK;
+        default: return PJD_E_ARG;
+    }
+}
+
 int pjd_libjpeg_ycc_to_rgb(uint8_t y, uint8_t cb, uint8_t cr, uint8_t rgb[3])
 {
     if (!rgb) return PJD_E_ARG;
@@ -1131,7 +1148,7 @@ int pjd_batch_set_resize(pjd_batch *b, const uint32_t *out_w, const uint32_t *ou
     for (size_t i = 0; i < n; i++) {
         const PjdDevImage &g = P.images[i];
         uint32_t sw = 0, sh = 0;
-        pjd_scaled_dims(g.width, g.height, (g.flags & PJD_IF_SCALE_MASK) >> PJD_IF_SCALE_SHIFT << 4, &sw, &sh);
+        pjd_scaled_dims(g.width, g.height, PJD_IF_OUT_SCALE_LOG(g.flags) << 4, &sw, &sh);
         spec.pic.push_back(PjdResizePicture{g.out_off, lay.off[i], sw, sh, g.out_stride});
         if (P.host[i].shard && shard == n) shard = i;
     }
@@ -1315,7 +1332,7 @@ int pjd_batch_set_normalize(pjd_batch *b, int dtype, const float scale[3], const
     std::vector<uint32_t> w = b->spec.out_w, h = b->spec.out_h;
     if (!b->resized) {
         w.resize(n); h.resize(n);
-        for (size_t i = 0; i < n; i++) pjd_scaled_dims(P.images[i].width, P.images[i].height, (P.images[i].flags & PJD_IF_SCALE_MASK) >> PJD_IF_SCALE_SHIFT << 4, &w[i], &h[i]);
+        for (size_t i = 0; i < n; i++) pjd_scaled_dims(P.images[i].width, P.images[i].height, PJD_IF_OUT_SCALE_LOG(P.images[i].flags) << 4, &w[i], &h[i]);
     }
     const PjdPackedLayout lay = pjd_packed_layout(w.data(), h.data(), n, PJD_DT_SIZE(dtype), P.gray ? 1u : 3u);
     void *d_res = nullptr;

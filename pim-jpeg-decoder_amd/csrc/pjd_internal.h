@@ -129,6 +129,19 @@
                                      // always together with PJD_IF_STANDARD_ZIGZAG and PJD_IF_STANDARD_RESTART
 #define PJD_IF_GRAY             1024u // output is one plane (PJD_OUT_GRAY8): out_stride x output rows bytes; a property of the whole batch (the grey
                                      // back-end kernels of pjd_k_backend_gray.hip are launched for it), never together with PJD_IF_BMP or PJD_IF_PLANAR
+#define PJD_IF_LJSCALE_SHIFT    11  // bits 12..11: PJD_F_LIBJPEG_SCALE_* of a PJD_IF_LIBJPEG picture, log2 of the denominator (0 full size, 1..3 = 1/2, 1/4,
+#define PJD_IF_LJSCALE_MASK     (3u << PJD_IF_LJSCALE_SHIFT)   // 1/8): libjpeg's reduced IDCTs -- the _red kernels of pjd_k_backend_std.hip / _gray.hip.
+                                                               // Never together with PJD_IF_SCALE_MASK (the box filter)
+// log2 of a picture's output scale denominator, whichever of the two scales it has
+#define PJD_IF_OUT_SCALE_LOG(flags) ((((flags) & PJD_IF_SCALE_MASK) >> PJD_IF_SCALE_SHIFT) + (((flags) & PJD_IF_LJSCALE_MASK) >> PJD_IF_LJSCALE_SHIFT))
+// Samples a side of a CHROMA unit's IDCT where a luma unit has n (8, 4, 2, 1): libjpeg's rule (jdmaster.c) -- the transform doubles while
+// that leaves no more samples than the luma has on either axis.  4:2:0 below full size: 2n, and no upsampling is left; everything else: n.
+static inline __host__ __device__ uint32_t pjd_lj_chroma_size(uint32_t n, uint32_t hs, uint32_t vs)
+{
+    uint32_t cn = n;
+    while (cn < 8u && 2u * cn <= hs * n && 2u * cn <= vs * n) cn *= 2u;
+    return cn;
+}
 
 // status word per image: low 8 bits = PJD_ST_* class, bit 8 = "fast path gave up, needs exact kernel"
 #define PJD_STW_NEEDS_EXACT 0x100

@@ -10,7 +10,7 @@
 // The grey unit's kernels, for the launchers of the forms (pjd_kernels.h), which stand in the other two units
 typedef void (*PjdLanesKernel)(PjdDevBatch, const uint32_t *);
 typedef void (*PjdDenseKernel)(PjdDevBatch, const PjdDevIdctWg *, const uint64_t *);
-enum PjdGrayKernel { PJD_GRAY_SCALED = 0, PJD_GRAY_FULL = 1, PJD_GRAY_LIBJPEG = 2 };
+enum PjdGrayKernel { PJD_GRAY_SCALED = 0, PJD_GRAY_FULL = 1, PJD_GRAY_LIBJPEG = 2, PJD_GRAY_LIBJPEG_RED = 3 };
 PjdLanesKernel pjd_gray_lanes_kernel(PjdGrayKernel which);
 PjdDenseKernel pjd_gray_dense_kernel(PjdGrayKernel which);
 

@@ -337,15 +337,121 @@ __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_gray_std_dense(Pj
     pjd_gray_std_idct(tile, ws, qn, mcu_xy, B, im, wg.n_mcu, tid);
 }
 
-// the grey kernels, scaled / full size / PJD_F_LIBJPEG: the launchers of the forms stand in pjd_k_backend.hip and pjd_k_backend_std.hip
+// ---------------------------------------------------------------------------------------------
+// PJD_F_LIBJPEG_SCALE_* pictures of a grey batch: the luma units through libjpeg's reduced IDCT of M = 4, 2 or 1 samples a side
+// (PjdLjRed<M>, pjd_libjpeg.h), straight into the picture, clipped at its reduced width and height.  Kernels of their own: the two above
+// keep their text.  M is the picture's, uniform over the workgroup.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+struct __attribute__((packed)) PjdPx2 { uint16_t a; };
+
+template <int M>
+__device__ __forceinline__ void pjd_gray_red_idct(const int16_t (*tile)[TILE_STRIDE], uint32_t (*ws)[WS_STRIDE], const uint16_t *q, const uint32_t *mcu_xy,
+                                                  const PjdDevBatch &B, const PjdDevImage &im, uint32_t n_mcu, uint32_t tid)
+{
+    constexpr uint32_t M_LOG = M == 4 ? 2 : (M == 2 ? 1 : 0), COLS = M == 4 ? 7 : 5;
+    const uint32_t dus = im.dus_per_mcu, nl = im.n_luma, hs = im.hs, vs = im.vs;
+    const uint32_t nl_log = nl == 4u ? 2u : nl - 1u, n_lu = n_mcu * nl;
+    if (M > 1) {
+        // pass 1: a thread takes one of the columns the transform reads of one unit
+        for (uint32_t i = tid; i < n_lu * COLS; i += PJD_IDCT_THREADS) {
+            const uint32_t j = pjd_div_small(i, c_recip16[COLS]), k = i - j * COLS;     // i < 7 * PJD_IDCT_MAX_DU: exact
+            pjd_lj_red_pass1_col<(M == 2 ? 2 : 4)>(tile, ws, pjd_gray_unit(j, nl_log, nl, dus), q, k);
+        }
+        __syncthreads();
+    }
+    // pass 2: a thread takes one row of one unit and stores its M samples
+    const uint32_t width = (im.width + 8u / M - 1u) >> (3u - M_LOG), height = (im.height + 8u / M - 1u) >> (3u - M_LOG), stride = im.out_stride;
+    uint8_t *out = B.out + im.out_off;
+    for (uint32_t i = tid; i < (n_lu << M_LOG); i += PJD_IDCT_THREADS) {
+        const uint32_t j = i >> M_LOG, r = i & (M - 1u);
+        const uint32_t ml = j >> nl_log, k = j & (nl - 1u), u = __umul24(ml, dus) + k;
+        const uint32_t xy = mcu_xy[ml];
+        const uint32_t X = (__umul24(xy & 0xffffu, hs) + (k & (hs - 1u))) * M, Y = (__umul24(xy >> 16, vs) + (k >> (hs - 1u))) * M + r;
+        if (X >= width || Y >= height) continue;
+        uint8_t *o = out + (size_t)Y * stride + X;
+        if (M == 1) { *o = (uint8_t)pjd_lj_sample_1x1(pjd_lj_dequant((int)tile[u][0], q[0])); continue; }
+        const uint32_t px = pjd_lj_red_pass2_row<(M == 2 ? 2 : 4)>(ws, u, r);
+        // one store of the row's samples to ANY address (pjd_gray_store8); bytes in front of the right edge
+        if (X + M <= width) {
+            if (M == 4) reinterpret_cast<PjdPx4 *>(o)->a = px;
+            else reinterpret_cast<PjdPx2 *>(o)->a = (uint16_t)px;
+        } else {
+            for (uint32_t p = 0; p < width - X; p++) o[p] = (uint8_t)(px >> (8 * p));
+        }
+    }
+}
+
+__device__ __forceinline__ void pjd_gray_red_dispatch(const int16_t (*tile)[TILE_STRIDE], uint32_t (*ws)[WS_STRIDE], const uint16_t *q, const uint32_t *mcu_xy,
+                                                      const PjdDevBatch &B, const PjdDevImage &im, uint32_t n_mcu, uint32_t tid)
+{
+    switch ((im.flags & PJD_IF_LJSCALE_MASK) >> PJD_IF_LJSCALE_SHIFT) {
+        case 1: pjd_gray_red_idct<4>(tile, ws, q, mcu_xy, B, im, n_mcu, tid); break;
+        case 2: pjd_gray_red_idct<2>(tile, ws, q, mcu_xy, B, im, n_mcu, tid); break;
+        case 3: pjd_gray_red_idct<1>(tile, ws, q, mcu_xy, B, im, n_mcu, tid); break;
+        default: break;                                         // never: the planner sends full-size pictures to the kernels above
+    }
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_gray_std_lanes_red(PjdDevBatch B, const uint32_t *__restrict__ order)
+{
+    PJD_LANES_LDS_TILE
+    __shared__ __attribute__((aligned(16))) uint32_t ws[PJD_IDCT_MAX_DU][WS_STRIDE];
+    __shared__ uint16_t qn[64];
+    PJD_LANES_LDS_TABLES
+
+    const uint32_t iwg = order[blockIdx.x];
+    if (threadIdx.x < 64) qn[threadIdx.x] = B.qtab[(size_t)B.iwgs[iwg].image * 192 + threadIdx.x];
+#define PJD_LANES_RAW
+#define PJD_LANES_LUMA_ONLY
+#include "pjd_k_lanes_parse_body.h"
+#undef PJD_LANES_LUMA_ONLY
+#undef PJD_LANES_RAW
+    if (wv == 0) pjd_gray_dc(tile, qz, comp_of, du_head, pred0[0], n_du, n_valid, lane);
+    __syncthreads();
+    pjd_gray_red_dispatch(tile, ws, qn, mcu_xy, B, im, wg.n_mcu, tid);
+}
+
+__global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_gray_std_dense_red(PjdDevBatch B, const PjdDevIdctWg *__restrict__ wgs, const uint64_t *__restrict__ dense_base)
+{
+    __shared__ __attribute__((aligned(16))) int16_t tile[PJD_IDCT_MAX_DU][TILE_STRIDE];
+    __shared__ __attribute__((aligned(16))) uint32_t ws[PJD_IDCT_MAX_DU][WS_STRIDE];
+    __shared__ uint16_t qn[64];
+    __shared__ uint32_t mcu_xy[PJD_IDCT_MAX_DU];
+
+    const PjdDevIdctWg wg = wgs[blockIdx.x];
+    const PjdDevImage &im = B.images[wg.image];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t dus = im.dus_per_mcu, nl = im.n_luma;
+    const uint32_t nl_log = nl == 4u ? 2u : nl - 1u, n_lu = wg.n_mcu * nl;
+    if (tid < 64) qn[tid] = B.qtab[(size_t)wg.image * 192 + tid];
+    pjd_fill_mcu_xy(mcu_xy, wg, im, tid);
+    const int16_t *cbase = B.coef + (dense_base[wg.pad_] + (uint64_t)(wg.first_mcu - im.first_mcu) * dus) * 64;
+    const bool sentinel = !(im.flags & PJD_IF_PROGRESSIVE);
+    for (uint32_t i = tid; i < n_lu * 8; i += PJD_IDCT_THREADS) {
+        const uint32_t du = pjd_gray_unit(i >> 3, nl_log, nl, dus), r = i & 7;
+        const int4 raw = *reinterpret_cast<const int4 *>(cbase + (size_t)du * 64 + r * 8);
+#define PJD_DENSE_RAW
+#include "pjd_k_dense_stage_body.h"
+#undef PJD_DENSE_RAW
+    }
+    __syncthreads();
+    pjd_gray_red_dispatch(tile, ws, qn, mcu_xy, B, im, wg.n_mcu, tid);
+}
+
+// the grey kernels, scaled / full size / PJD_F_LIBJPEG / PJD_F_LIBJPEG_SCALE_*: the launchers of the forms stand in pjd_k_backend.hip and
+// pjd_k_backend_std.hip
 PjdLanesKernel pjd_gray_lanes_kernel(PjdGrayKernel which)
 {
-    static const PjdLanesKernel k[3] = {pjd_k_idct_gray_lanes<true>, pjd_k_idct_gray_lanes<false>, pjd_k_idct_gray_std_lanes};
+    static const PjdLanesKernel k[4] = {pjd_k_idct_gray_lanes<true>, pjd_k_idct_gray_lanes<false>, pjd_k_idct_gray_std_lanes, pjd_k_idct_gray_std_lanes_red};
     return k[which];
 }
 
 PjdDenseKernel pjd_gray_dense_kernel(PjdGrayKernel which)
 {
-    static const PjdDenseKernel k[3] = {pjd_k_idct_gray<true>, pjd_k_idct_gray<false>, pjd_k_idct_gray_std_dense};
+    static const PjdDenseKernel k[4] = {pjd_k_idct_gray<true>, pjd_k_idct_gray<false>, pjd_k_idct_gray_std_dense, pjd_k_idct_gray_std_dense_red};
     return k[which];
 }

@@ -190,21 +190,261 @@ __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_colour_std(PjdDevBatch
     }
 }
 
-void pjd_launch_idct_std_lanes(hipStream_t s, const PjdDevBatch &b, PjdBackForm f, const uint32_t *order, uint32_t n_wg, uint8_t *planes)
+// =============================================================================================
+// PJD_F_LIBJPEG_SCALE_*: the flagged pictures libjpeg decodes through its reduced IDCTs (include/pjd.h).  Kernels of their own -- the three
+// above keep their text -- with the same front ends (the same included bodies) and other passes: a luma unit becomes N x N samples, N = 4, 2
+// or 1, a chroma unit CN x CN, CN = N or, for 4:2:0, 2N (pjd_lj_chroma_size), through PjdLjRed<M> of pjd_libjpeg.h.  The planes have that
+// geometry: luma mcux*hs*N x mcuy*vs*N, chroma mcux*CN x mcuy*CN.  (N, CN) is a property of the PICTURE, so of the workgroup: one uniform
+// switch picks the instantiation, and inside it the luma units and the chroma units of the range are walked in loops of their own, each
+// with its size at compile time -- no lane chooses a transform.
+// =============================================================================================
+namespace {
+
+__device__ __forceinline__ PjdStdPlanes pjd_std_planes_red(uint8_t *planes, const PjdDevImage &im, uint32_t n, uint32_t cn)
 {
-    if (n_wg == 0) return;
-    if (f.gray()) hipLaunchKernelGGL(pjd_gray_lanes_kernel(PJD_GRAY_LIBJPEG), dim3(n_wg), dim3(PJD_IDCT_THREADS), 0, s, b, order);
-    else hipLaunchKernelGGL(pjd_k_idct_std_lanes, dim3(n_wg), dim3(PJD_IDCT_THREADS), 0, s, b, order, planes);
+    PjdStdPlanes P;
+    const uint32_t yw = im.mcux * im.hs * n, yh = im.mcuy * im.vs * n, cw = im.mcux * cn, ch = im.mcuy * cn;
+    P.p[0] = planes + (size_t)im.plane_off256 * 256;
+    P.p[1] = P.p[0] + (size_t)yw * yh;
+    P.p[2] = P.p[1] + (size_t)cw * ch;
+    P.stride[0] = yw; P.stride[1] = cw; P.stride[2] = cw;
+    return P;
 }
 
-void pjd_launch_idct_std_dense(hipStream_t s, const PjdDevBatch &b, PjdBackForm f, const PjdDevIdctWg *wgs, const uint64_t *dense_base, uint32_t n_wg, uint8_t *planes)
+// unit j of one class of a range's units -- the luma units (j counts them alone, MCU after MCU), or the chroma units (two per MCU) -- ->
+// its MCU of the range, its index among all units of the range, its component and its position in that component's grid of units
+template <bool CHROMA>
+__device__ __forceinline__ void pjd_std_red_unit(uint32_t j, const PjdDevImage &im, const uint32_t *mcu_xy, uint32_t &u, uint32_t &comp, uint32_t &ux, uint32_t &uy)
 {
-    if (n_wg == 0) return;
-    if (f.gray()) hipLaunchKernelGGL(pjd_gray_dense_kernel(PJD_GRAY_LIBJPEG), dim3(n_wg), dim3(PJD_IDCT_THREADS), 0, s, b, wgs, dense_base);
-    else hipLaunchKernelGGL(pjd_k_idct_std_dense, dim3(n_wg), dim3(PJD_IDCT_THREADS), 0, s, b, wgs, dense_base, planes);
+    const uint32_t nl = im.n_luma, hs = im.hs, dus = im.dus_per_mcu;
+    if (CHROMA) {
+        const uint32_t ml = j >> 1, xy = mcu_xy[ml];
+        comp = 1u + (j & 1u); u = __umul24(ml, dus) + nl + (j & 1u); ux = xy & 0xffffu; uy = xy >> 16;
+    } else {
+        const uint32_t nl_log = nl == 4u ? 2u : nl - 1u, ml = j >> nl_log, k = j & (nl - 1u), xy = mcu_xy[ml];
+        comp = 0; u = __umul24(ml, dus) + k; ux = __umul24(xy & 0xffffu, hs) + (k & (hs - 1u)); uy = __umul24(xy >> 16, im.vs) + (k >> (hs - 1u));
+    }
 }
 
-void pjd_launch_colour_std(hipStream_t s, const PjdDevBatch &b, const PjdDevIdctWg *cwgs, uint32_t n_wg, uint8_t *planes)
+// pass 1 of the n_units units of one class at size M: a thread takes one of the COLS columns the transform reads of one unit.  M = 8 is the
+// full pass (the chroma of a 4:2:0 picture at 1/2); M = 1 has no pass 1.
+template <int M, bool CHROMA>
+__device__ __forceinline__ void pjd_std_red_pass1(const int16_t (*tile)[TILE_STRIDE], uint32_t (*ws)[WS_STRIDE], const uint16_t (*qn)[64], const uint32_t *mcu_xy,
+                                                  const PjdDevImage &im, uint32_t n_units, uint32_t tid)
+{
+    if (M == 1) return;
+    constexpr uint32_t COLS = M == 8 ? 8 : (M == 4 ? 7 : 5);
+    for (uint32_t i = tid; i < n_units * COLS; i += PJD_IDCT_THREADS) {
+        const uint32_t j = COLS == 8 ? i >> 3 : pjd_div_small(i, c_recip16[COLS]), k = i - j * COLS;      // i < 8 * PJD_IDCT_MAX_DU: exact
+        uint32_t u, comp, ux, uy;
+        pjd_std_red_unit<CHROMA>(j, im, mcu_xy, u, comp, ux, uy);
+        const uint16_t *q = qn[comp];
+        if (M == 8) PJD_LJ_PASS1_COL(tile, ws, u, q, k);
+        else pjd_lj_red_pass1_col<(M == 2 ? 2 : 4)>(tile, ws, u, q, k);
+    }
+}
+
+// pass 2 and the plane store: a thread takes one of the M rows of one unit and stores its M samples as one store (planes are whole MCUs:
+// a row of a unit starts at a multiple of M bytes of a plane whose size is a multiple of 4 wherever M > 1)
+template <int M, bool CHROMA>
+__device__ __forceinline__ void pjd_std_red_pass2(const int16_t (*tile)[TILE_STRIDE], const uint32_t (*ws)[WS_STRIDE], const uint16_t (*qn)[64], const uint32_t *mcu_xy,
+                                                  const PjdDevImage &im, uint32_t n_units, const PjdStdPlanes &P, uint32_t tid)
+{
+    constexpr uint32_t M_LOG = M == 8 ? 3 : (M == 4 ? 2 : (M == 2 ? 1 : 0));
+    for (uint32_t i = tid; i < (n_units << M_LOG); i += PJD_IDCT_THREADS) {
+        const uint32_t j = i >> M_LOG, r = i & (M - 1u);
+        uint32_t u, comp, ux, uy;
+        pjd_std_red_unit<CHROMA>(j, im, mcu_xy, u, comp, ux, uy);
+        // the plane by a select, not by an index: an indexed PjdStdPlanes lives in scratch memory
+        uint8_t *plane = CHROMA ? (comp == 1u ? P.p[1] : P.p[2]) : P.p[0];
+        uint8_t *dst = plane + (size_t)(uy * M + r) * (CHROMA ? P.stride[1] : P.stride[0]) + ux * M;
+        if (M == 8) *reinterpret_cast<uint2 *>(dst) = pjd_lj_pass2_row(ws, u, r);
+        else if (M == 4) *reinterpret_cast<uint32_t *>(dst) = pjd_lj_red_pass2_row<4>(ws, u, r);
+        else if (M == 2) *reinterpret_cast<uint16_t *>(dst) = (uint16_t)pjd_lj_red_pass2_row<2>(ws, u, r);
+        else *dst = (uint8_t)pjd_lj_sample_1x1(pjd_lj_dequant((int)tile[u][0], qn[comp][0]));
+    }
+}
+
+template <int N, int CN>
+__device__ __forceinline__ void pjd_std_red_body(const int16_t (*tile)[TILE_STRIDE], uint32_t (*ws)[WS_STRIDE], const uint16_t (*qn)[64], const uint32_t *mcu_xy,
+                                                 const PjdDevImage &im, uint32_t n_mcu, uint8_t *planes, uint32_t tid)
+{
+    const uint32_t n_lu = n_mcu * im.n_luma, n_cu = im.ncomp == 3 ? n_mcu * 2u : 0u;
+    pjd_std_red_pass1<N, false>(tile, ws, qn, mcu_xy, im, n_lu, tid);
+    pjd_std_red_pass1<CN, true>(tile, ws, qn, mcu_xy, im, n_cu, tid);
+    __syncthreads();
+    const PjdStdPlanes P = pjd_std_planes_red(planes, im, N, CN);
+    pjd_std_red_pass2<N, false>(tile, ws, qn, mcu_xy, im, n_lu, P, tid);
+    pjd_std_red_pass2<CN, true>(tile, ws, qn, mcu_xy, im, n_cu, P, tid);
+}
+
+// the picture's (N, CN): uniform over the workgroup
+__device__ __forceinline__ void pjd_std_red_to_planes(const int16_t (*tile)[TILE_STRIDE], uint32_t (*ws)[WS_STRIDE], const uint16_t (*qn)[64], const uint32_t *mcu_xy,
+                                                      const PjdDevImage &im, uint32_t n_mcu, uint8_t *planes, uint32_t tid)
+{
+    const uint32_t sl = (im.flags & PJD_IF_LJSCALE_MASK) >> PJD_IF_LJSCALE_SHIFT;
+    const bool dbl = im.hs == 2 && im.vs == 2;                  // pjd_lj_chroma_size: 4:2:0 alone doubles
+    switch (sl) {
+        case 1: if (dbl) pjd_std_red_body<4, 8>(tile, ws, qn, mcu_xy, im, n_mcu, planes, tid); else pjd_std_red_body<4, 4>(tile, ws, qn, mcu_xy, im, n_mcu, planes, tid); break;
+        case 2: if (dbl) pjd_std_red_body<2, 4>(tile, ws, qn, mcu_xy, im, n_mcu, planes, tid); else pjd_std_red_body<2, 2>(tile, ws, qn, mcu_xy, im, n_mcu, planes, tid); break;
+        case 3: if (dbl) pjd_std_red_body<1, 2>(tile, ws, qn, mcu_xy, im, n_mcu, planes, tid); else pjd_std_red_body<1, 1>(tile, ws, qn, mcu_xy, im, n_mcu, planes, tid); break;
+        default: break;                                         // never: the planner sends full-size pictures to the kernels above
+    }
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_std_lanes_red(PjdDevBatch B, const uint32_t *__restrict__ order, uint8_t *__restrict__ planes)
+{
+    PJD_LANES_LDS_TILE
+    __shared__ __attribute__((aligned(16))) uint32_t ws[PJD_IDCT_MAX_DU][WS_STRIDE];
+    __shared__ uint16_t qn[3][64];
+    PJD_LANES_LDS_TABLES
+
+    const uint32_t iwg = order[blockIdx.x];
+    if (threadIdx.x < 192) qn[threadIdx.x >> 6][threadIdx.x & 63] = B.qtab[(size_t)B.iwgs[iwg].image * 192 + threadIdx.x];
+#define PJD_LANES_RAW
+#include "pjd_k_lanes_parse_body.h"
+#undef PJD_LANES_RAW
+    if (wv == 0) {
+#include "pjd_k_lanes_dc_body.h"
+    }
+    __syncthreads();
+    pjd_std_red_to_planes(tile, ws, qn, mcu_xy, im, wg.n_mcu, planes, tid);
+}
+
+__global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_std_dense_red(PjdDevBatch B, const PjdDevIdctWg *__restrict__ wgs, const uint64_t *__restrict__ dense_base,
+                                                                             uint8_t *__restrict__ planes)
+{
+    __shared__ __attribute__((aligned(16))) int16_t tile[PJD_IDCT_MAX_DU][TILE_STRIDE];
+    __shared__ __attribute__((aligned(16))) uint32_t ws[PJD_IDCT_MAX_DU][WS_STRIDE];
+    __shared__ uint16_t qn[3][64];
+    __shared__ uint32_t mcu_xy[PJD_IDCT_MAX_DU];
+
+    const PjdDevIdctWg wg = wgs[blockIdx.x];
+    const PjdDevImage &im = B.images[wg.image];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t dus = im.dus_per_mcu;
+    const uint32_t n_du = wg.n_mcu * dus;
+    if (tid < 192) qn[tid >> 6][tid & 63] = B.qtab[(size_t)wg.image * 192 + tid];
+    pjd_fill_mcu_xy(mcu_xy, wg, im, tid);
+    const int16_t *cbase = B.coef + (dense_base[wg.pad_] + (uint64_t)(wg.first_mcu - im.first_mcu) * dus) * 64;
+    const bool sentinel = !(im.flags & PJD_IF_PROGRESSIVE);
+    for (uint32_t i = tid; i < n_du * 8; i += PJD_IDCT_THREADS) {
+        const uint32_t du = i >> 3, r = i & 7;
+        const int4 raw = *reinterpret_cast<const int4 *>(cbase + (size_t)du * 64 + r * 8);
+#define PJD_DENSE_RAW
+#include "pjd_k_dense_stage_body.h"
+#undef PJD_DENSE_RAW
+    }
+    __syncthreads();
+    pjd_std_red_to_planes(tile, ws, qn, mcu_xy, im, wg.n_mcu, planes, tid);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Upsample + colour + store of a reduced picture: pjd_k_colour_std's items and stores over ceil(W/s) x ceil(H/s) and the reduced planes.
+// 4:4:4 and 4:2:0 (chroma at 2N) read their chroma sample for sample; 4:2:2 keeps the h2v1 rule -- fancy where N > 1 and the chroma row
+// has more than two samples of the picture, replicated otherwise (libjpeg has no fancy upsampling at min_DCT_scaled_size 1).
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_colour_std_red(PjdDevBatch B, const PjdDevIdctWg *__restrict__ cwgs, uint8_t *__restrict__ planes)
+{
+    const PjdDevIdctWg wg = cwgs[blockIdx.x];
+    const PjdDevImage &im = B.images[wg.image];
+    const uint32_t flags = im.flags, sl = (flags & PJD_IF_LJSCALE_MASK) >> PJD_IF_LJSCALE_SHIFT, rnd = (1u << sl) - 1u;
+    const uint32_t width = (im.width + rnd) >> sl, height = (im.height + rnd) >> sl, stride = im.out_stride;
+    const uint32_t per_row = (width + 3) >> 2;
+    const uint32_t item = wg.first_mcu + threadIdx.x;
+    uint8_t *out = B.out + im.out_off;
+    const bool bmp = (flags & PJD_IF_BMP) != 0;
+    if (bmp && wg.first_mcu == 0) pjd_bmp_header(out, width, height, stride, threadIdx.x);
+    const uint32_t y = item / per_row, X = (item - y * per_row) * 4;
+    if (y >= height) return;
+    const uint32_t N = 8u >> sl;
+    const PjdStdPlanes P = pjd_std_planes_red(planes, im, N, pjd_lj_chroma_size(N, im.hs, im.vs));
+    // a plane row need not be a multiple of 4 bytes: any address (PjdPx4); what lies behind the row's samples is never used (`left`)
+    const uint32_t yv = reinterpret_cast<const PjdPx4 *>(P.p[0] + (size_t)y * P.stride[0] + X)->a;
+    int cb[4], cr[4];
+    if (im.ncomp < 3) { cb[0] = cb[1] = cb[2] = cb[3] = 128; cr[0] = cr[1] = cr[2] = cr[3] = 128; }
+    else if (im.hs == 1 || im.vs == 2) {
+        const size_t o = (size_t)y * P.stride[1] + X;
+        const uint32_t bw = reinterpret_cast<const PjdPx4 *>(P.p[1] + o)->a, rw = reinterpret_cast<const PjdPx4 *>(P.p[2] + o)->a;
+#pragma unroll
+        for (int k = 0; k < 4; k++) { cb[k] = (bw >> (8 * k)) & 255; cr[k] = (rw >> (8 * k)) & 255; }
+    } else {
+        // h2v1.  dw: the samples of a chroma row that belong to the picture, ceil(W * N / 16) = ceil(width / 2)
+        const uint32_t dw = (width + 1) >> 1;
+        const size_t row = (size_t)y * P.stride[1];
+        if (N > 1) {                                            // pjd_lj_upsample4 replicates where dw <= 2
+            pjd_lj_upsample4(P.p[1] + row, nullptr, dw, X, cb);
+            pjd_lj_upsample4(P.p[2] + row, nullptr, dw, X, cr);
+        } else {
+            const uint32_t i0 = X >> 1, i1 = i0 + 1 < dw ? i0 + 1 : dw - 1;
+            cb[0] = cb[1] = P.p[1][row + i0]; cb[2] = cb[3] = P.p[1][row + i1];
+            cr[0] = cr[1] = P.p[2][row + i0]; cr[2] = cr[3] = P.p[2][row + i1];
+        }
+    }
+    uint32_t f[4], g[4], l[4];            // first / middle / last byte of a pixel: R, G, B -- B, G, R in the BMP image
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        int r_, g_, b_;
+        const int yy = (int)((yv >> (8 * k)) & 255);
+        if (im.ncomp < 3) r_ = g_ = b_ = yy;
+        else pjd_lj_ycc_to_rgb(yy, cb[k], cr[k], r_, g_, b_);
+        f[k] = (uint32_t)(bmp ? b_ : r_); g[k] = (uint32_t)g_; l[k] = (uint32_t)(bmp ? r_ : b_);
+    }
+    const uint32_t left = width - X;      // pixels of the item that belong to the picture: 1..4 count
+    if (flags & PJD_IF_PLANAR) {
+        const size_t plane = (size_t)stride * height;
+        uint8_t *o = out + (size_t)y * stride + X;
+        if (left >= 4) {
+            reinterpret_cast<PjdPx4 *>(o)->a = f[0] | (f[1] << 8) | (f[2] << 16) | (f[3] << 24);
+            reinterpret_cast<PjdPx4 *>(o + plane)->a = g[0] | (g[1] << 8) | (g[2] << 16) | (g[3] << 24);
+            reinterpret_cast<PjdPx4 *>(o + 2 * plane)->a = l[0] | (l[1] << 8) | (l[2] << 16) | (l[3] << 24);
+        } else {
+            for (uint32_t k = 0; k < left; k++) { o[k] = (uint8_t)f[k]; o[plane + k] = (uint8_t)g[k]; o[2 * plane + k] = (uint8_t)l[k]; }
+        }
+        return;
+    }
+    uint8_t *o = bmp ? out + 26 + (size_t)(height - 1 - y) * stride + X * 3 : out + (size_t)y * stride + X * 3;
+    if (left >= 4) {
+        PjdPx12 v;
+        v.a = f[0] | (g[0] << 8) | (l[0] << 16) | (f[1] << 24);
+        v.b = g[1] | (l[1] << 8) | (f[2] << 16) | (g[2] << 24);
+        v.c = l[2] | (f[3] << 8) | (g[3] << 16) | (l[3] << 24);
+        *reinterpret_cast<PjdPx12 *>(o) = v;
+    } else {
+        for (uint32_t k = 0; k < left; k++) { o[3 * k] = (uint8_t)f[k]; o[3 * k + 1] = (uint8_t)g[k]; o[3 * k + 2] = (uint8_t)l[k]; }
+    }
+}
+
+// The launchers take a list in two parts: n_wg ranges (items) of full-size flagged pictures, then n_red of reduced ones.
+void pjd_launch_idct_std_lanes(hipStream_t s, const PjdDevBatch &b, PjdBackForm f, const uint32_t *order, uint32_t n_wg, uint32_t n_red, uint8_t *planes)
+{
+    if (n_wg) {
+        if (f.gray()) hipLaunchKernelGGL(pjd_gray_lanes_kernel(PJD_GRAY_LIBJPEG), dim3(n_wg), dim3(PJD_IDCT_THREADS), 0, s, b, order);
+        else hipLaunchKernelGGL(pjd_k_idct_std_lanes, dim3(n_wg), dim3(PJD_IDCT_THREADS), 0, s, b, order, planes);
+    }
+    if (n_red) {
+        if (f.gray()) hipLaunchKernelGGL(pjd_gray_lanes_kernel(PJD_GRAY_LIBJPEG_RED), dim3(n_red), dim3(PJD_IDCT_THREADS), 0, s, b, order + n_wg);
+        else hipLaunchKernelGGL(pjd_k_idct_std_lanes_red, dim3(n_red), dim3(PJD_IDCT_THREADS), 0, s, b, order + n_wg, planes);
+    }
+}
+
+void pjd_launch_idct_std_dense(hipStream_t s, const PjdDevBatch &b, PjdBackForm f, const PjdDevIdctWg *wgs, const uint64_t *dense_base, uint32_t n_wg, uint32_t n_red,
+                               uint8_t *planes)
+{
+    if (n_wg) {
+        if (f.gray()) hipLaunchKernelGGL(pjd_gray_dense_kernel(PJD_GRAY_LIBJPEG), dim3(n_wg), dim3(PJD_IDCT_THREADS), 0, s, b, wgs, dense_base);
+        else hipLaunchKernelGGL(pjd_k_idct_std_dense, dim3(n_wg), dim3(PJD_IDCT_THREADS), 0, s, b, wgs, dense_base, planes);
+    }
+    if (n_red) {
+        if (f.gray()) hipLaunchKernelGGL(pjd_gray_dense_kernel(PJD_GRAY_LIBJPEG_RED), dim3(n_red), dim3(PJD_IDCT_THREADS), 0, s, b, wgs + n_wg, dense_base);
+        else hipLaunchKernelGGL(pjd_k_idct_std_dense_red, dim3(n_red), dim3(PJD_IDCT_THREADS), 0, s, b, wgs + n_wg, dense_base, planes);
+    }
+}
+
+void pjd_launch_colour_std(hipStream_t s, const PjdDevBatch &b, const PjdDevIdctWg *cwgs, uint32_t n_wg, uint32_t n_red, uint8_t *planes)
 {
     if (n_wg) hipLaunchKernelGGL(pjd_k_colour_std, dim3(n_wg), dim3(PJD_IDCT_THREADS), 0, s, b, cwgs, planes);
+    if (n_red) hipLaunchKernelGGL(pjd_k_colour_std_red, dim3(n_red), dim3(PJD_IDCT_THREADS), 0, s, b, cwgs + n_wg, planes);
 }

@@ -82,9 +82,12 @@ void pjd_launch_idct_sweep(hipStream_t s, const PjdDevBatch &b);
 // (pjd_k_backend_std.hip): into component planes -- `planes` is the batch's plane buffer (PjdDevImage::plane_off256) -- then upsample +
 // colour + store by pjd_launch_colour_std (cwgs[k] = {image, first 4-pixel item, -, -}).  A grey batch (pjd_k_backend_gray.hip): the
 // luma units straight into the picture; `planes` is unused and there is no colour launch.
-void pjd_launch_idct_std_lanes(hipStream_t s, const PjdDevBatch &b, PjdBackForm f, const uint32_t *order, uint32_t n_wg, uint8_t *planes);
-void pjd_launch_idct_std_dense(hipStream_t s, const PjdDevBatch &b, PjdBackForm f, const PjdDevIdctWg *wgs, const uint64_t *dense_base, uint32_t n_wg, uint8_t *planes);
-void pjd_launch_colour_std(hipStream_t s, const PjdDevBatch &b, const PjdDevIdctWg *cwgs, uint32_t n_wg, uint8_t *planes);
+// Every list has two parts: n_wg ranges (colour: workgroups of items) of pictures at full size, then n_red of pictures with
+// PJD_F_LIBJPEG_SCALE_*, which take the _red kernels -- libjpeg's reduced IDCTs into planes of the reduced geometry, a reduced picture.
+void pjd_launch_idct_std_lanes(hipStream_t s, const PjdDevBatch &b, PjdBackForm f, const uint32_t *order, uint32_t n_wg, uint32_t n_red, uint8_t *planes);
+void pjd_launch_idct_std_dense(hipStream_t s, const PjdDevBatch &b, PjdBackForm f, const PjdDevIdctWg *wgs, const uint64_t *dense_base, uint32_t n_wg, uint32_t n_red,
+                               uint8_t *planes);
+void pjd_launch_colour_std(hipStream_t s, const PjdDevBatch &b, const PjdDevIdctWg *cwgs, uint32_t n_wg, uint32_t n_red, uint8_t *planes);
 // ---- resize on decode (pjd_k_resize.hip): every picture of the batch from `src` (interleaved RGB8, or planar) to its target size in `dst`
 // (the same layout), one launch whatever the batch asked for; tile_prefix[i] = tiles of the pictures before i, tile_prefix[n_images] =
 // n_tiles.  norm.dtype != 0: the samples leave as fp16 / bf16 / fp32 elements, v * scale[c] + bias[c] (pjd_batch_set_normalize); the

@@ -41,6 +41,69 @@ static inline __host__ __device__ uint32_t pjd_lj_sample(uint32_t o) { return (u
 // The 32-bit product of a coefficient and its quantiser (|coef| <= 32768, q <= 65535: no overflow)
 static inline __host__ __device__ uint32_t pjd_lj_dequant(int coef, uint32_t q) { return (uint32_t)coef * q; }
 
+// ---- the reduced transforms of PJD_F_LIBJPEG_SCALE_* (libjpeg jidctred.c, CONST_BITS = 13; normative text: include/pjd.h) ----
+// One 1-D pass of jpeg_idct_4x4 before its rounding shift.  i[4] is never read: pass 1 skips column 4, pass 2 column 4 of the workspace.
+static inline __host__ __device__ void pjd_lj_idct1d_4(const uint32_t i[8], uint32_t o[4])
+{
+    const uint32_t t0 = i[0] << 14, t2 = i[2] * 15137u + i[6] * (uint32_t)-6270;
+    const uint32_t t10 = t0 + t2, t12 = t0 - t2;
+    const uint32_t a0 = i[7] * (uint32_t)-1730 + i[5] * 11893u + i[3] * (uint32_t)-17799 + i[1] * 8697u;
+    const uint32_t a2 = i[7] * (uint32_t)-4176 + i[5] * (uint32_t)-4926 + i[3] * 7373u + i[1] * 20995u;
+    o[0] = t10 + a2; o[3] = t10 - a2;
+    o[1] = t12 + a0; o[2] = t12 - a0;
+}
+// One 1-D pass of jpeg_idct_2x2: reads i[0], i[1], i[3], i[5], i[7]
+static inline __host__ __device__ void pjd_lj_idct1d_2(const uint32_t i[8], uint32_t o[2])
+{
+    const uint32_t t10 = i[0] << 15;
+    const uint32_t t0 = i[7] * (uint32_t)-5906 + i[5] * 6967u + i[3] * (uint32_t)-10426 + i[1] * 29692u;
+    o[0] = t10 + t0; o[1] = t10 - t0;
+}
+// The transform of size M (8, 4, 2): its 1-D kernel, the rounding shifts of its two passes, the columns (pass 2: workspace columns)
+// it reads -- COLS of them, the k-th being col(k)
+template <int M> struct PjdLjRed;
+template <> struct PjdLjRed<8> {
+    enum { COLS = 8, SH1 = PJD_LJ_PASS1_SHIFT, SH2 = PJD_LJ_PASS2_SHIFT };
+    static inline __host__ __device__ uint32_t col(uint32_t k) { return k; }
+    static inline __host__ __device__ void run(const uint32_t i[8], uint32_t o[8]) { pjd_lj_idct1d(i, o); }
+};
+template <> struct PjdLjRed<4> {
+    enum { COLS = 7, SH1 = 12, SH2 = 19 };
+    static inline __host__ __device__ uint32_t col(uint32_t k) { return k < 4u ? k : k + 1u; }            // 0 1 2 3 5 6 7
+    static inline __host__ __device__ void run(const uint32_t i[8], uint32_t o[4]) { pjd_lj_idct1d_4(i, o); }
+};
+template <> struct PjdLjRed<2> {
+    enum { COLS = 5, SH1 = 13, SH2 = 20 };
+    static inline __host__ __device__ uint32_t col(uint32_t k) { return k < 2u ? k : 2u * k - 1u; }       // 0 1 3 5 7
+    static inline __host__ __device__ void run(const uint32_t i[8], uint32_t o[2]) { pjd_lj_idct1d_2(i, o); }
+};
+template <int S>
+static inline __host__ __device__ uint32_t pjd_lj_sample_sh(uint32_t o) { return (uint32_t)pjd_lj_clamp255((int32_t)pjd_lj_descale<S>(o) + 128); }
+// jpeg_idct_1x1: the sample of a unit's dequantised DC term
+static inline __host__ __device__ uint32_t pjd_lj_sample_1x1(uint32_t d0) { return pjd_lj_sample_sh<3>(d0); }
+
+// One unit through the transform of size M on the host's terms (coef, q natural order; out M x M): what pjd_libjpeg_idct_scaled exports
+template <int M>
+static inline __host__ __device__ void pjd_lj_idct_unit(const int16_t *coef, const uint16_t *q, uint8_t *out)
+{
+    typedef PjdLjRed<M> T;
+    uint32_t ws[M][8];
+    for (uint32_t k = 0; k < (uint32_t)T::COLS; k++) {
+        const uint32_t c = T::col(k);
+        uint32_t x[8], o[M];
+        for (int j = 0; j < 8; j++) x[j] = pjd_lj_dequant((int)coef[j * 8 + c], q[j * 8 + c]);
+        T::run(x, o);
+        for (int j = 0; j < M; j++) ws[j][c] = pjd_lj_descale<T::SH1>(o[j]);
+    }
+    for (int r = 0; r < M; r++) {
+        uint32_t x[8], o[M];
+        for (int j = 0; j < 8; j++) x[j] = 0;
+        for (uint32_t k = 0; k < (uint32_t)T::COLS; k++) x[T::col(k)] = ws[r][T::col(k)];
+        T::run(x, o);
+        for (int j = 0; j < M; j++) out[r * M + j] = (uint8_t)pjd_lj_sample_sh<T::SH2>(o[j]);
+    }
+}
+
 // ycc_rgb_convert's tables (libjpeg jdcolor.c), 16 fraction bits
 static inline __host__ __device__ void pjd_lj_ycc_to_rgb(int y, int cb, int cr, int &r, int &g, int &b)
 {

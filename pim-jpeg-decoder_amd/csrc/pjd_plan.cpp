@@ -45,10 +45,12 @@ extern "C" int pjd_output_channels(int out_format)
     return out_format == PJD_OUT_GRAY8 ? 1 : 0;
 }
 
-// Reduced-size output (PJD_F_SCALE_*): ceil(W / s) x ceil(H / s), libjpeg's jdiv_round_up
+// Reduced-size output (PJD_F_SCALE_*, or PJD_F_LIBJPEG_SCALE_* of a flagged picture: never both): ceil(W / s) x ceil(H / s), libjpeg's
+// jdiv_round_up
 extern "C" int pjd_scaled_dims(uint32_t width, uint32_t height, uint32_t flags, uint32_t *out_w, uint32_t *out_h)
 {
-    const uint32_t sl = (flags & PJD_F_SCALE_MASK) >> 4;
+    uint32_t sl = (flags & PJD_F_SCALE_MASK) >> 4;
+    if (!sl) sl = (flags & PJD_F_LIBJPEG_SCALE_MASK) >> 7;
     if (out_w) *out_w = (uint32_t)(((uint64_t)width + (1u << sl) - 1) >> sl);
     if (out_h) *out_h = (uint32_t)(((uint64_t)height + (1u << sl) - 1) >> sl);
     return PJD_OK;
@@ -238,12 +240,16 @@ int pjd_make_plan(const pjd_image_desc *images, int n, int out_format, PjdPlan &
         std::memset(&g, 0, sizeof g);
         if (lj) {
             // the envelope of the mode (include/pjd.h)
+            if ((d.flags & PJD_F_SCALE_MASK) && (d.flags & PJD_F_LIBJPEG_SCALE_MASK)) { err = fmt("image %d: PJD_F_LIBJPEG_SCALE_* together with PJD_F_SCALE_*", i); return PJD_E_ARG; }
             if (d.flags & PJD_F_SCALE_MASK) { err = fmt("image %d: PJD_F_LIBJPEG takes no output scale (PJD_F_SCALE_*)", i); return PJD_E_ARG; }
             if (d.shard_n_segs != 0) { err = fmt("image %d: PJD_F_LIBJPEG takes no shard", i); return PJD_E_ARG; }
             if (d.num_components == 2) { err = fmt("image %d: PJD_F_LIBJPEG takes one or three components", i); return PJD_E_ARG; }
             if (d.num_components == 3 && d.h_samp == 1 && d.v_samp == 2) { err = fmt("image %d: PJD_F_LIBJPEG does not take 4:4:0 (h1v2) sampling", i); return PJD_E_ARG; }
-            g.flags |= PJD_IF_LIBJPEG;
+            g.flags |= PJD_IF_LIBJPEG | (((d.flags & PJD_F_LIBJPEG_SCALE_MASK) >> 7) << PJD_IF_LJSCALE_SHIFT);
             P.libjpeg = true;
+        } else if (d.flags & PJD_F_LIBJPEG_SCALE_MASK) {
+            err = fmt("image %d: PJD_F_LIBJPEG_SCALE_* needs PJD_F_LIBJPEG (the box filter is PJD_F_SCALE_*)", i);
+            return PJD_E_ARG;
         }
 
         // ---- envelope: exactly what the reference scanner lets through (jpeg_scanner.cpp:187-285)
@@ -601,7 +607,8 @@ int pjd_make_plan(const pjd_image_desc *images, int n, int out_format, PjdPlan &
         du_total += g.n_du;
         if (sequential) { g.dense_base = dense_seq; dense_seq += g.n_du; }
         g.idct_mcus = PJD_IDCT_MAX_DU / g.dus_per_mcu;
-        std::vector<PjdDevIdctWg> &iwg_list = sequential ? (lj ? P.iwgs_dense_std : P.iwgs_dense) : P.iwgs;
+        const uint32_t lj_sl = (g.flags & PJD_IF_LJSCALE_MASK) >> PJD_IF_LJSCALE_SHIFT;     // a flagged picture's reduced decode: 1..3
+        std::vector<PjdDevIdctWg> &iwg_list = sequential ? (lj ? (lj_sl ? P.iwgs_dense_red : P.iwgs_dense_std) : P.iwgs_dense) : P.iwgs;
         g.iwg_base = (uint32_t)iwg_list.size();
         for (uint32_t m = g.first_mcu; m < g.last_mcu; m += g.idct_mcus) {
             PjdDevIdctWg w;
@@ -615,10 +622,17 @@ int pjd_make_plan(const pjd_image_desc *images, int n, int out_format, PjdPlan &
         if (lj && out_format != PJD_OUT_GRAY8) {         // a grey picture's luma rows go straight into the picture (pjd_k_backend_gray.hip)
             // component planes, whole MCUs: Y, then Cb and Cr of a three-component picture; the colour launch's items of four pixels
             g.plane_off256 = (uint32_t)(P.plane_bytes / 256);
-            const uint64_t cpl = (uint64_t)g.mcux * 8 * g.mcuy * 8;
-            P.plane_bytes = align_up(P.plane_bytes + cpl * g.n_luma + (g.ncomp == 3 ? 2 * cpl : 0), 256);
-            const uint32_t items = ((g.width + 3) / 4) * g.height;
-            for (uint32_t it = 0; it < items; it += PJD_IDCT_THREADS) P.cwgs_std.push_back(PjdDevIdctWg{(uint32_t)i, it, 0, 0});
+            // at PJD_F_LIBJPEG_SCALE_*: n = 8 / s samples a side per luma unit, cn per chroma unit (pjd_lj_chroma_size: libjpeg's rule), and
+            // the items of the reduced picture.  A row of a reduced plane need not be a multiple of four bytes: eight spare bytes keep the
+            // colour launch's four-byte reads of the last row inside the buffer
+            const uint32_t n = 8u >> lj_sl, cn = pjd_lj_chroma_size(n, g.hs, g.vs);
+            const uint64_t ypl = (uint64_t)g.mcux * g.hs * n * g.mcuy * g.vs * n, cpl = (uint64_t)g.mcux * cn * g.mcuy * cn;
+            P.plane_bytes = align_up(P.plane_bytes + ypl + (g.ncomp == 3 ? 2 * cpl : 0) + (lj_sl ? 8 : 0), 256);
+            uint32_t ow = 0, oh = 0;
+            pjd_scaled_dims(d.width, d.height, d.flags, &ow, &oh);
+            const uint32_t items = ((ow + 3) / 4) * oh;
+            std::vector<PjdDevIdctWg> &cl = lj_sl ? P.cwgs_red : P.cwgs_std;
+            for (uint32_t it = 0; it < items; it += PJD_IDCT_THREADS) cl.push_back(PjdDevIdctWg{(uint32_t)i, it, 0, 0});
         }
         h.out_bytes = pjd_image_output_size(&d, out_format);
         g.out_off = out_off;
@@ -712,10 +726,17 @@ int pjd_make_plan(const pjd_image_desc *images, int n, int out_format, PjdPlan &
     if (P.libjpeg) {
         // one chain of launches, the lane-stream back ends over two lists of ranges: the default kernels never see a flagged picture
         P.groups.clear(); P.group_images.clear(); P.iwg_order.clear();
-        for (int pass = 0; pass < 2; pass++)
+        // (0: unflagged, 1: flagged at full size, 2: flagged with PJD_F_LIBJPEG_SCALE_* -- the reduced kernels)
+        auto cls = [&](uint32_t image) { const uint32_t f = P.images[image].flags; return !(f & PJD_IF_LIBJPEG) ? 0 : ((f & PJD_IF_LJSCALE_MASK) ? 2 : 1); };
+        for (int pass = 0; pass < 3; pass++)
             for (uint32_t k = 0; k < P.iwgs.size(); k++)
-                if (((P.images[P.iwgs[k].image].flags & PJD_IF_LIBJPEG) != 0) == (pass == 1)) P.iwg_order.push_back(k);
-        for (const PjdDevIdctWg &w : P.iwgs) (P.images[w.image].flags & PJD_IF_LIBJPEG ? P.n_iwg_std : P.n_iwg_def)++;
+                if (cls(P.iwgs[k].image) == pass) P.iwg_order.push_back(k);
+        for (const PjdDevIdctWg &w : P.iwgs) { const int c = cls(w.image); (c == 0 ? P.n_iwg_def : (c == 1 ? P.n_iwg_std : P.n_iwg_red))++; }
+        // one list each on the device: the full-size ranges (items), then the reduced ones
+        P.n_dense_std = (uint32_t)P.iwgs_dense_std.size(); P.n_dense_red = (uint32_t)P.iwgs_dense_red.size();
+        P.iwgs_dense_std.insert(P.iwgs_dense_std.end(), P.iwgs_dense_red.begin(), P.iwgs_dense_red.end());
+        P.n_cwg_std = (uint32_t)P.cwgs_std.size(); P.n_cwg_red = (uint32_t)P.cwgs_red.size();
+        P.cwgs_std.insert(P.cwgs_std.end(), P.cwgs_red.begin(), P.cwgs_red.end());
         if (P.plane_bytes >= (1ull << 40)) { err = "batch needs too large a plane buffer"; return PJD_E_ARG; }
     }
     // the lane-word kernel copies PJD_WORD_ROWS words from every lane's first byte, whatever the lane's length

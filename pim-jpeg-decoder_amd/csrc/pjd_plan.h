@@ -61,7 +61,12 @@ struct PjdPlan {
     uint32_t n_iwg_def = 0, n_iwg_std = 0;
     std::vector<PjdDevIdctWg> iwgs_dense_std;   // flagged pictures routed to the exact kernel up front: their ranges (not in iwgs_dense)
     std::vector<PjdDevIdctWg> cwgs_std;         // work list of the colour launch: {image, first item, 0, 0}, PJD_IDCT_THREADS items each
-    uint64_t plane_bytes = 0;                   // the plane buffer: Y, Cb, Cr of every flagged picture, padded to whole MCUs
+    // PJD_F_LIBJPEG_SCALE_*: flagged pictures decoded through libjpeg's reduced IDCTs take the _red kernels.  Their ranges stand BEHIND those
+    // of the full-size flagged pictures in each list: iwg_order holds n_iwg_def, n_iwg_std, then n_iwg_red ranges; iwgs_dense_std n_dense_std
+    // ranges, then n_dense_red; cwgs_std n_cwg_std workgroups, then n_cwg_red (the two _red vectors are the planner's own, appended at its end)
+    uint32_t n_iwg_red = 0, n_dense_std = 0, n_dense_red = 0, n_cwg_std = 0, n_cwg_red = 0;
+    std::vector<PjdDevIdctWg> iwgs_dense_red, cwgs_red;
+    uint64_t plane_bytes = 0;                   // the plane buffer: Y, Cb, Cr of every flagged picture, padded to whole MCUs (at the picture's reduced size)
     bool dc_per_picture = false;           // the single chain settles verdict and DC predictors with pjd_k_group_dc, one workgroup per picture (pjd_plan.cpp)
     int plan_mode = 0;                     // PJD_PLAN_*
     std::vector<uint32_t> tset_step_bits;  // per table set: fewest bits of stream per step of the write pass, x 256 (sizes the lane regions)

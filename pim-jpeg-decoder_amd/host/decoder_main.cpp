@@ -24,6 +24,9 @@
 // its box of source pixels (PJD_F_SCALE_* of include/pjd.h); in every mode.  Any other value is a usage error.
 // --libjpeg: the pictures are the ones libjpeg decodes, bit for bit (PJD_F_LIBJPEG of include/pjd.h: islow IDCT, fancy upsampling, JFIF
 // colour) instead of the reference's; with --pipeline and --progressive, not with a --scale other than 1/1 and not with --split.
+// --libjpeg --draft 1/2|1/4|1/8 (and 1/1): libjpeg's own reduced decode (PJD_F_LIBJPEG_SCALE_* of include/pjd.h: its scaled IDCTs -- what
+// Pillow's draft() and OpenCV's IMREAD_REDUCED_* deliver), pictures of ceil(W/s) x ceil(H/s).  --draft without --libjpeg is refused before a
+// device is opened; --libjpeg --scale stays refused.
 // A file outside that mode's envelope (4:4:0 sampling, two components) gets "<file>: Error - <the planner's reason>" and no BMP; the
 // other files decode.
 #include <sys/stat.h>
@@ -175,8 +178,8 @@ int main(int argc, char **argv)
     int device = 0;
     size_t batch_images = 1024;
     bool pipeline = false, split = false, libjpeg = false;
-    uint32_t scan_options = 0, image_flags = 0;
-    bool bad_args = false;
+    uint32_t scan_options = 0, image_flags = 0, draft_flags = 0;
+    bool bad_args = false, draft = false;
     int slots = 0, scan_threads = 0, write_threads = 0;
     std::vector<std::string> files;
     std::vector<int32_t> devices;
@@ -205,6 +208,15 @@ int main(int argc, char **argv)
             else if (!std::strcmp(v, "1/8")) image_flags = PJD_F_SCALE_1_8;
             else bad_args = true;
         }
+        else if (!std::strcmp(argv[i], "--draft")) {
+            const char *v = i + 1 < argc ? argv[++i] : "";
+            draft = true;
+            if (!std::strcmp(v, "1/1")) draft_flags = 0;
+            else if (!std::strcmp(v, "1/2")) draft_flags = PJD_F_LIBJPEG_SCALE_1_2;
+            else if (!std::strcmp(v, "1/4")) draft_flags = PJD_F_LIBJPEG_SCALE_1_4;
+            else if (!std::strcmp(v, "1/8")) draft_flags = PJD_F_LIBJPEG_SCALE_1_8;
+            else bad_args = true;
+        }
         else if (!std::strcmp(argv[i], "--slots") && i + 1 < argc) slots = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--scan-threads") && i + 1 < argc) scan_threads = std::atoi(argv[++i]);
         else if (!std::strcmp(argv[i], "--write-threads") && i + 1 < argc) write_threads = std::atoi(argv[++i]);
@@ -214,10 +226,11 @@ int main(int argc, char **argv)
         std::cout << "Error - Invalid arguments\n";
         return 1;
     }
+    if (draft && !libjpeg) { std::cout << "Error - --draft needs --libjpeg (libjpeg's reduced decode; the box filter is --scale)\n"; return 1; }
     if (libjpeg) {
         if (image_flags & PJD_F_SCALE_MASK) { std::cout << "Error - --libjpeg takes no --scale other than 1/1 (libjpeg's reduced decodes are other filters)\n"; return 1; }
         if (split) { std::cout << "Error - --libjpeg cannot be combined with --split (its upsampling reads across the rows a device decodes)\n"; return 1; }
-        image_flags |= PJD_F_LIBJPEG;
+        image_flags |= PJD_F_LIBJPEG | draft_flags;
     }
     // ascending file size, like sort_by_size (decoder_host.cpp:46-61)
     std::vector<std::pair<long long, std::string>> sized;

@@ -21,6 +21,7 @@ OUT_GRAY8 = 4            # uint8[H][W]: one plane, the luma as libjpeg's JCS_GRA
 PLAN_LATENCY, PLAN_THROUGHPUT = 0, 1      # pjd_set_plan_mode
 F_STANDARD_RESTART, F_FORCE_SEQUENTIAL, F_STANDARD_ZIGZAG, F_PROGRESSIVE = 1, 2, 4, 8
 F_SCALE_1_2, F_SCALE_1_4, F_SCALE_1_8, F_SCALE_MASK = 16, 32, 48, 48      # output scale s = 1 << ((flags >> 4) & 3) (pjd.h)
+F_LIBJPEG_SCALE_1_2, F_LIBJPEG_SCALE_1_4, F_LIBJPEG_SCALE_1_8, F_LIBJPEG_SCALE_MASK = 128, 256, 384, 384   # with F_LIBJPEG: libjpeg's reduced decode (its scaled IDCTs), s = 1 << ((flags >> 7) & 3) (pjd.h)
 F_LIBJPEG = 64           # the picture libjpeg decodes, bit for bit (islow IDCT, fancy upsampling, JFIF colour); implies the two F_STANDARD_* (pjd.h)
 RESIZE_BILINEAR, RESIZE_ANTIALIAS = 0, 1   # pjd_batch_set_resize_filter (pjd.h)
 RW_HFLIP = 1                               # pjd_resize_window.flags: the delivered picture mirrored left-right
@@ -215,6 +216,8 @@ def dev_lib():
         L.pjd_batch_set_normalize.argtypes = [vp, i32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
         L.pjd_libjpeg_idct.restype = i32
         L.pjd_libjpeg_idct.argtypes = [C.POINTER(C.c_int16), C.POINTER(C.c_uint16), C.POINTER(C.c_uint8)]
+        L.pjd_libjpeg_idct_scaled.restype = i32
+        L.pjd_libjpeg_idct_scaled.argtypes = [C.POINTER(C.c_int16), C.POINTER(C.c_uint16), C.c_uint32, C.POINTER(C.c_uint8)]
         L.pjd_libjpeg_ycc_to_rgb.restype = i32
         L.pjd_libjpeg_ycc_to_rgb.argtypes = [C.c_uint8, C.c_uint8, C.c_uint8, C.POINTER(C.c_uint8)]
         L.pjd_libjpeg_upsample_row.restype = i32
@@ -901,6 +904,18 @@ def libjpeg_idct(coef, q):
     return out
 
 
+def libjpeg_idct_scaled(coef, q, n):
+    """pjd_libjpeg_idct_scaled (host only): the n x n samples (uint8, row by row) of one unit under F_LIBJPEG_SCALE_* -- n = 8 (full size), 4,
+    2 or 1: libjpeg's reduced IDCTs; the inlines the kernels run.  ValueError for any other n."""
+    c = np.ascontiguousarray(np.asarray(coef).reshape(64), np.int16)
+    qq = np.ascontiguousarray(np.asarray(q).reshape(64), np.uint16)
+    out = np.empty(64, np.uint8)
+    if dev_lib().pjd_libjpeg_idct_scaled(c.ctypes.data_as(C.POINTER(C.c_int16)), qq.ctypes.data_as(C.POINTER(C.c_uint16)), int(n) & 0xffffffff,
+                                         out.ctypes.data_as(C.POINTER(C.c_uint8))) != 0:
+        raise ValueError("libjpeg_idct_scaled: n is 8, 4, 2 or 1")
+    return out[:int(n) * int(n)].copy()
+
+
 def libjpeg_ycc_to_rgb(y, cb, cr):
     """pjd_libjpeg_ycc_to_rgb (host only): (R, G, B) of one pixel under F_LIBJPEG; y, cb, cr in 0..255."""
     if not all(0 <= int(v) <= 255 for v in (y, cb, cr)):
@@ -928,7 +943,7 @@ def libjpeg_upsample_row(cur, nb=None, v=0):
 
 
 def scaled_dims(width, height, flags=0):
-    """pjd_scaled_dims: (width, height) of the output picture at the scale the descriptor flags ask for (F_SCALE_*)."""
+    """pjd_scaled_dims: (width, height) of the output picture at the scale the descriptor flags ask for (F_SCALE_*, F_LIBJPEG_SCALE_*)."""
     L = dev_lib()
     w, h = C.c_uint32(), C.c_uint32()
     L.pjd_scaled_dims(int(width), int(height), int(flags), C.byref(w), C.byref(h))

@@ -3,7 +3,7 @@
 The batch is bound (Batch.bind_output, pjd_batch_bind_output of include/pjd.h) to ONE torch.uint8 buffer this module allocates
 on the context's device; the back end writes the pictures straight into it -- planar R, G, B (OUT_RGB8_PLANAR, "CHW") by
 default -- and the results are views of that buffer.  No native code of its own.  torch is imported inside the functions that
-need it: uniform_output_shape(), pick_scale_flags(), normalize_constants(), center_crop_window(), window_at_scale(), orient_hw(),
+need it: uniform_output_shape(), pick_scale_flags(), pick_libjpeg_scale_flags(), normalize_constants(), center_crop_window(), window_at_scale(), orient_hw(),
 orient_then_hflip() and crop_to_stored() are pure.
 
 Pictures of different sizes become ONE [N, 3, H, W] tensor with decode_resized_batch_tensor: the library resamples every picture to
@@ -48,8 +48,11 @@ def libjpeg_descs(descs):
     return out
 
 
-def _libjpeg(descs, libjpeg, prescale=False):
-    """The descriptors a helper decodes for its `libjpeg` keyword, checked before anything is created: the mode takes no output scale."""
+def _libjpeg(descs, libjpeg, prescale=False, draft=False):
+    """The descriptors a helper decodes for its `libjpeg` keyword, checked before anything is created: the mode takes no output scale
+    but libjpeg's own (`draft`), which in turn needs the mode."""
+    if draft and not libjpeg:
+        raise ValueError("draft needs libjpeg=True: libjpeg's reduced decode (F_LIBJPEG_SCALE_*) exists only for its picture; the box pre-scale is prescale=True")
     if not libjpeg:
         return descs
     if prescale:
@@ -61,11 +64,12 @@ def _libjpeg(descs, libjpeg, prescale=False):
 
 
 def _scale_log(flags):
-    return (int(flags) & pjd_amd.F_SCALE_MASK) >> 4
+    """log2 of the output scale denominator: the box filter's (F_SCALE_*) or, on a flagged picture, libjpeg's (F_LIBJPEG_SCALE_*)."""
+    return ((int(flags) & pjd_amd.F_SCALE_MASK) >> 4) or ((int(flags) & pjd_amd.F_LIBJPEG_SCALE_MASK) >> 7)
 
 
 def output_hw(desc):
-    """(h, w) of the picture a descriptor gives at its output scale (F_SCALE_*): ceil(H / s), ceil(W / s).  Pure."""
+    """(h, w) of the picture a descriptor gives at its output scale (F_SCALE_* or F_LIBJPEG_SCALE_*): ceil(H / s), ceil(W / s).  Pure."""
     s = _scale_log(desc.flags)
     return (int(desc.height) + (1 << s) - 1) >> s, (int(desc.width) + (1 << s) - 1) >> s
 
@@ -144,7 +148,43 @@ def _gray3(v, what):
     return v
 
 
-def decode_to_tensors(ctx, descs, planar=True, device=None, orientations=None, libjpeg=False, gray=False):
+def pick_libjpeg_scale_flags(w, h, tw, th):
+    """The F_LIBJPEG_SCALE_* value to decode a flagged w x h picture with before it is resized to tw x th: that of the largest s of 1, 2,
+    4, 8 with ceil(w / s) >= tw and ceil(h / s) >= th (what a loader that drafts before it resizes asks libjpeg for); 0 when the target
+    is larger than the source on either axis.  Pure."""
+    return (pick_scale_flags(w, h, tw, th) >> 4) << 7
+
+
+def drafted_descs(descs, size):
+    """Copies of `descs` (flagged F_LIBJPEG, or about to be) whose F_LIBJPEG_SCALE_* bits are pick_libjpeg_scale_flags for the target
+    size = (H, W); the caller's descriptors are not touched.  No device."""
+    th, tw = size
+    return [_scaled_copy(d, "draft", d.width, d.height, tw, th) for d in descs]
+
+
+def _scaled_copy(d, prescale, cw, ch, vw, vh):
+    """A copy of descriptor d with the scale picked for a cw x ch source against a vw x vh target: the box filter's (prescale true) or
+    libjpeg's own (prescale == "draft")."""
+    import ctypes
+    c = pjd_amd.ImageDesc()
+    ctypes.memmove(ctypes.byref(c), ctypes.byref(d), ctypes.sizeof(pjd_amd.ImageDesc))
+    if prescale == "draft":
+        c.flags = (int(d.flags) & ~pjd_amd.F_LIBJPEG_SCALE_MASK) | pick_libjpeg_scale_flags(cw, ch, vw, vh)
+    else:
+        c.flags = (int(d.flags) & ~pjd_amd.F_SCALE_MASK) | pick_scale_flags(cw, ch, vw, vh)
+    return c
+
+
+def _draft_flags(draft):
+    """The `draft` keyword of decode_to_tensors: False, or the denominator 1, 2, 4 or 8 -> F_LIBJPEG_SCALE_* bits."""
+    if draft is False or draft is None:
+        return 0
+    if draft is True or int(draft) != draft or int(draft) not in (1, 2, 4, 8):
+        raise ValueError("decode_to_tensors: draft is False or a scale denominator 1, 2, 4 or 8 (there is no target size to pick one from)")
+    return {1: 0, 2: pjd_amd.F_LIBJPEG_SCALE_1_2, 4: pjd_amd.F_LIBJPEG_SCALE_1_4, 8: pjd_amd.F_LIBJPEG_SCALE_1_8}[int(draft)]
+
+
+def decode_to_tensors(ctx, descs, planar=True, device=None, orientations=None, libjpeg=False, gray=False, draft=False):
     """Decode `descs` on `ctx` into ONE torch.uint8 buffer on the context's device -> (list of tensors, statuses).  Tensor i is
     a view of that buffer shaped (3, sh, sw) -- or (sh, sw, 3) with planar=False -- at the picture's output scale.  The tensors
     are complete on return and may be read on any torch stream (module docstring, "Stream order").
@@ -153,9 +193,14 @@ def decode_to_tensors(ctx, descs, planar=True, device=None, orientations=None, l
     stores them.  libjpeg=True: the pictures are libjpeg's, byte for byte (F_LIBJPEG on copies of the descriptors).
     gray=True: one plane per picture (OUT_GRAY8: the luma, what libjpeg's JCS_GRAYSCALE delivers with libjpeg=True), views shaped
     (1, sh, sw) -- (1, sw, sh) for orientations 5..8 --; a third of the bytes.  It takes planar=True (ValueError before anything is created
-    otherwise)."""
+    otherwise).  draft=2 | 4 | 8 (only with libjpeg=True, ValueError otherwise): libjpeg's reduced decode at 1/draft (F_LIBJPEG_SCALE_* on
+    the flagged copies) -- what PIL's Image.draft() or OpenCV's IMREAD_REDUCED_* deliver, byte for byte, ceil(H / s) x ceil(W / s)."""
     _gray_layout(gray, planar)
-    descs = _libjpeg(descs, libjpeg)
+    dflags = _draft_flags(draft)
+    descs = _libjpeg(descs, libjpeg, draft=draft not in (False, None))
+    if dflags:
+        for d in descs:
+            d.flags = (int(d.flags) & ~pjd_amd.F_LIBJPEG_SCALE_MASK) | dflags
     torch = _torch()
     device = torch.device("cuda", ctx.device) if device is None else device
     sizes = None
@@ -296,13 +341,12 @@ def _windowed(descs, size, prescale, crops, flips, resize_short):
     th, tw = size
     n = len(descs)
     if crops is None and flips is None and resize_short is None:
-        return (prescaled_descs(descs, size) if prescale else descs), None
+        return ((drafted_descs(descs, size) if prescale == "draft" else prescaled_descs(descs, size)) if prescale else descs), None
     if crops is not None and resize_short is not None:
         raise ValueError("crops and resize_short exclude each other")
     for name, v in (("crops", crops), ("flips", flips)):
         if v is not None and len(v) != n:
             raise ValueError(f"{name}: one entry per picture")
-    import ctypes
     run, windows = [], []
     for i, d in enumerate(descs):
         W, H = int(d.width), int(d.height)
@@ -316,11 +360,8 @@ def _windowed(descs, size, prescale, crops, flips, resize_short):
             win.update(center_crop_window((H, W), resize_short, size))
         vw, vh = win.get("vw", tw), win.get("vh", th)
         if prescale:
-            c = pjd_amd.ImageDesc()
-            ctypes.memmove(ctypes.byref(c), ctypes.byref(d), ctypes.sizeof(pjd_amd.ImageDesc))
             cw, ch = (crop[2], crop[3]) if crop is not None else (W, H)
-            c.flags = (int(d.flags) & ~pjd_amd.F_SCALE_MASK) | pick_scale_flags(cw, ch, vw, vh)
-            d = c
+            d = _scaled_copy(d, prescale, cw, ch, vw, vh)
         if crop is not None:
             h_s, w_s = output_hw(d)
             win["x"], win["y"], win["w"], win["h"] = window_at_scale(crop, _scale_log(d.flags), w_s, h_s)
@@ -351,7 +392,6 @@ def _windowed_oriented(descs, size, prescale, crops, flips, resize_short, orient
     for name, v in (("crops", crops), ("flips", flips)):
         if v is not None and len(v) != n:
             raise ValueError(f"{name}: one entry per picture")
-    import ctypes
     run, windows, oris = [], [], []
     for i, (d, o) in enumerate(zip(descs, orientations)):
         W, H = int(d.width), int(d.height)
@@ -371,11 +411,8 @@ def _windowed_oriented(descs, size, prescale, crops, flips, resize_short, orient
             win.update(vw=svw, vh=svh, ox=ox, oy=oy)
         vw, vh = win.get("vw", qtw), win.get("vh", qth)
         if prescale:
-            c = pjd_amd.ImageDesc()
-            ctypes.memmove(ctypes.byref(c), ctypes.byref(d), ctypes.sizeof(pjd_amd.ImageDesc))
             cw, ch = (crop[2], crop[3]) if crop is not None else (W, H)
-            c.flags = (int(d.flags) & ~pjd_amd.F_SCALE_MASK) | pick_scale_flags(cw, ch, vw, vh)
-            d = c
+            d = _scaled_copy(d, prescale, cw, ch, vw, vh)
         if crop is not None:
             h_s, w_s = output_hw(d)
             win["x"], win["y"], win["w"], win["h"] = window_at_scale(crop, _scale_log(d.flags), w_s, h_s)
@@ -466,7 +503,7 @@ def _interpolation(name):
 
 
 def decode_resized_batch_tensor(ctx, descs, size, prescale=True, device=None, antialias=False, crops=None, flips=None, resize_short=None,
-                                interpolation="bilinear", orientations=None, libjpeg=False, letterbox=None, fill=(0, 0, 0), gray=False):
+                                interpolation="bilinear", orientations=None, libjpeg=False, letterbox=None, fill=(0, 0, 0), gray=False, draft=False):
     """Pictures of ANY sizes -> (uint8 tensor [N, 3, H, W], statuses), size = (H, W): every picture is resampled to H x W inside
     the decode (the bilinear filter of include/pjd.h, pjd_batch_set_resize) and lands at offset i * 3 * H * W of one buffer, so
     the result is one contiguous NCHW tensor with no copy after the decode, complete on return and readable on any torch stream
@@ -496,7 +533,9 @@ def decode_resized_batch_tensor(ctx, descs, size, prescale=True, device=None, an
     bound of "orient, then resize".  None: today's behaviour, byte for byte.
     libjpeg=True: the picture the filters read is libjpeg's, byte for byte (F_LIBJPEG on copies of the descriptors): what a PIL or
     torchvision.io pipeline resizes.  It takes prescale=False (ValueError before anything is created otherwise): the box pre-scale is
-    not libjpeg's reduced decode.
+    not libjpeg's reduced decode.  draft=True (only with libjpeg=True, ValueError otherwise) IS that reduced decode: every flagged copy
+    is decoded at the scale pick_libjpeg_scale_flags chooses for it (F_LIBJPEG_SCALE_*: libjpeg's reduced IDCTs, what Image.draft() and
+    the loaders built on it do before they resize) and the filters read that reduced picture; crops become window_at_scale's hull.
     letterbox="center" | "topleft": every picture keeps its aspect ratio inside the H x W canvas (letterbox_plan of the UPRIGHT picture,
     or of its crop) and the rest of the canvas is `fill` (three bytes; YOLO: 114) -- Batch.set_resize_pad, in the same launch and one
     small one behind it.  crops and orientations work as above against the content size, flips mirror the content inside its
@@ -507,7 +546,8 @@ def decode_resized_batch_tensor(ctx, descs, size, prescale=True, device=None, an
     _interpolation(interpolation)
     if len(descs) == 0:
         raise ValueError("decode_resized_batch_tensor: no pictures")
-    descs = _libjpeg(descs, libjpeg, prescale)
+    descs = _libjpeg(descs, libjpeg, prescale, draft)
+    prescale = "draft" if draft else prescale
     th, tw = int(size[0]), int(size[1])
     fill, pads = _fill(fill, gray), None
     if letterbox is not None:
@@ -537,7 +577,7 @@ def normalize_constants(mean, std):
 
 def decode_normalized_batch_tensor(ctx, descs, size, mean, std, dtype=None, channels_last=False, prescale=True, device=None,
                                    antialias=False, crops=None, flips=None, resize_short=None, interpolation="bilinear", orientations=None,
-                                   libjpeg=False, letterbox=None, fill=(0, 0, 0), pad_value=None, gray=False):
+                                   libjpeg=False, letterbox=None, fill=(0, 0, 0), pad_value=None, gray=False, draft=False):
     """Pictures of ANY sizes -> (tensor of `dtype` [N, 3, H, W], statuses), size = (H, W); dtype torch.float16 (the default),
     torch.bfloat16 or torch.float32.  As decode_resized_batch_tensor, and every sample v of channel c leaves the same launch as
     fma(v, scale[c], bias[c]) with the constants of normalize_constants(mean, std), converted once to `dtype` (include/pjd.h,
@@ -549,7 +589,7 @@ def decode_normalized_batch_tensor(ctx, descs, size, mean, std, dtype=None, chan
     pre-scale comes first), prescale=False gives exactly that up to the 16x limit.  crops, flips, resize_short: as in
     decode_resized_batch_tensor.  interpolation="bicubic": the bicubic filter (RESIZE_BICUBIC), as there -- `antialias` is not consulted,
     prescale=True still puts the box filter first, prescale=False is exactly the filter over the full-size picture up to the 16x
-    limit; any other string than "bilinear" or "bicubic" raises ValueError before anything is created.  orientations, libjpeg: as in
+    limit; any other string than "bilinear" or "bicubic" raises ValueError before anything is created.  orientations, libjpeg, draft: as in
     decode_resized_batch_tensor.  letterbox, fill: as there; the border is normalised like every other sample (fill=(124, 116, 104) is
     about the ImageNet mean colour), unless pad_value -- one number or three -- is given: the border elements are then exactly that
     (Batch.set_pad_value; pad_value=0 is "zeros after normalisation": DETR, SAM).  pad_value without letterbox raises ValueError.
@@ -559,7 +599,8 @@ def decode_normalized_batch_tensor(ctx, descs, size, mean, std, dtype=None, chan
     _gray_layout(gray, not channels_last)
     if len(descs) == 0:
         raise ValueError("decode_normalized_batch_tensor: no pictures")
-    descs = _libjpeg(descs, libjpeg, prescale)
+    descs = _libjpeg(descs, libjpeg, prescale, draft)
+    prescale = "draft" if draft else prescale
     th, tw = int(size[0]), int(size[1])
     if gray:
         mean, std = _gray3(mean, "mean"), _gray3(std, "std")
