@@ -39,6 +39,9 @@
  *                                                       JCS_GRAYSCALE delivers it (a third of the bytes, no chroma work in the back end)
  *   (none: an addition)                                 PJD_F_LIBJPEG_SCALE_* + pjd_libjpeg_idct_scaled: libjpeg's reduced decode at 1/2, 1/4,
  *                                                       1/8 (its scaled IDCTs: Pillow's draft(), OpenCV's IMREAD_REDUCED_*), bit for bit
+ *   (none: an addition)                                 pjd_batch_set_views + pjd_batch_n_outputs: several resampled outputs of one decoded
+ *                                                       picture (two augmented views, multi-crop, FiveCrop, two resolutions, tiles): the
+ *                                                       entropy decoder and the back end run once per picture, the resample once per view
  *
  * Plain pointers and sizes only; no C++ or torch types.  Thread model: one
  * submitting thread per pjd_ctx (the reference has one consumer thread,
@@ -62,7 +65,8 @@ extern "C" {
  * PJD_F_SCALE_* and pjd_pipe_opts::image_flags of pjd_pipeline.h).  PJD_OUT_RGB8_PLANAR and PJD_F_LIBJPEG changed no struct and
  * no version: a caller that needs one of them checks for it by its symbols (pjd_libjpeg_idct is exported from the first library that
  * knows PJD_F_LIBJPEG; an older one ignores the bit).  Pad on decode (pjd_batch_set_resize_pad, pjd_batch_set_pad_value) changed no
- * struct either, so PJD_VERSION stays 6: a caller checks for it by the symbol pjd_resize_pad_check.
+ * struct either, so PJD_VERSION stays 6: a caller checks for it by the symbol pjd_resize_pad_check.  Views (pjd_batch_set_views)
+ * changed no struct: a caller checks for them by the symbol pjd_batch_n_outputs.
  * A caller built against another version must not pass its structs: check pjd_version() == PJD_VERSION after loading.     */
 #define PJD_VERSION 6
 
@@ -824,6 +828,50 @@ int  pjd_resize_pad_check(uint32_t out_w, uint32_t out_h, const pjd_resize_pad *
 #define PJD_DT_F32   3   /* IEEE binary32 */
 int  pjd_batch_set_normalize(pjd_batch *b, int dtype, const float scale[3], const float bias[3]);
 int  pjd_normalize_value(int dtype, uint32_t v, float scale, float bias, void *out);   /* host only, no device needed */
+/* ---- views: several resampled outputs of one decoded picture --------------------------------------------------------------------- *
+ * pjd_batch_set_views: the batch delivers n_views OUTPUTS instead of one per picture; view v is a resample of picture
+ * picture_of_view[v] -- two augmented views of every picture (SimCLR, MoCo, BYOL), 2 global + 6..10 local crops (DINO, SwAV),
+ * FiveCrop / TenCrop, one picture at two resolutions, one large picture cut into tiles.  Every picture is still decoded whole and
+ * ONCE: the entropy decoder and the back end do the work of n_images pictures, the resample launch that of n_views outputs.
+ *
+ * MEANING (normative).  View v is an output of its own.  Its source P is the picture that picture_of_view[v] produces at its decode
+ * size -- after PJD_F_SCALE_* / PJD_F_LIBJPEG_SCALE_*, with grey behind an entropy-coding error: exactly the P of pjd_batch_set_resize.
+ * Views may name pictures in any order; a picture may have any number of views, zero included (it is still decoded and still has its
+ * status word).  No new arithmetic: each view is what a one-view batch would deliver for that picture with the same setters.
+ *
+ * CALL ORDER.  After pjd_batch_create; before any pjd_batch_set_resize / _set_normalize / _bind_output / _upload / _capture / _decode
+ * of the batch; once: PJD_E_STATE otherwise.  PJD_E_ARG for a null array, n_views == 0 or above PJD_MAX_VIEWS, an entry >= n_images
+ * (pjd_last_error names the view), a PJD_OUT_BMP batch.  After a failure the batch is as it was and the call is still open.
+ * PJD_MAX_VIEWS bounds the page-locked record arrays of a batch (about 130 bytes a view with every record kind in use: 8.5 MB at
+ * the cap); it is a bound of this header, NOT a measured figure.
+ * FROM THEN ON the output index is the VIEW.  Every per-picture array of the resample setters has n_views entries, indexed by view:
+ * out_w / out_h of pjd_batch_set_resize, pad of pjd_batch_set_resize_pad, orientation of pjd_batch_set_orientation, win of
+ * pjd_batch_set_resize_window.  So have offsets of pjd_batch_bind_output and out of pjd_batch_download; the index of
+ * pjd_batch_output_size / _output_offset / _device_output is the view; pjd_batch_packed_size and pjd_batch_download_packed speak about
+ * the packed views; pjd_batch_info::out_bytes is the sum over the views.  What stays per PICTURE: status of both downloads and
+ * pjd_batch_device_status (n_images words), pjd_batch_download_coefficients, and n_images, pixels and every planning figure of
+ * pjd_batch_info (n_subsequences, n_huff_workgroups, n_data_units, ...: those of the batch without views).
+ * THE SETTERS.  Every rule, limit, call order and error of pjd_batch_set_resize, _set_resize_pad, _set_orientation,
+ * _set_resize_window, _set_resize_filter, _set_normalize and _set_pad_value holds word for word PER VIEW, each view against its own
+ * picture's decode size; where pjd_last_error names a picture it names the view: "view <v> (picture <p>): ...".  A view of a shard is
+ * refused by pjd_batch_set_resize (and by pjd_batch_set_normalize), as a shard is without views.  pjd_batch_set_normalize without a
+ * resize acts as if pjd_batch_set_resize had been called with each view's own picture's output size.
+ * VIEWS NEED THE RESAMPLE: pjd_batch_bind_output, _upload, _capture and _decode return PJD_E_STATE on a batch that has views but
+ * neither a resize nor a normalisation (until then pjd_batch_output_size / _offset answer with the view's picture's).
+ * GUARANTEES.  Every decode writes every byte of every view's range and no byte outside it.  The work is still the one launch named
+ * "resize", plus "pad" where there are borders; both are part of a captured graph and run again after the exact-kernel fallback of
+ * pjd_batch_sync.  No kernel is new or changed: the resample's records (source offset and size, target, window, pad, tables) were
+ * always self-contained, and two records may read one source.  IDENTITY: picture_of_view = {0, 1, .., n_images - 1} delivers byte for
+ * byte what the batch delivers without the call, and launches the same kernels.
+ * COST.  The records, one set per view, are counted in pjd_batch_info::device_bytes and sent by pjd_batch_upload; the intermediate
+ * buffer is per picture, as without views.  One launch covers fewer than 2^31 tiles and 2^31 border lines, summed over the views
+ * in 64 bits: a request beyond that is refused with PJD_E_ARG by the setter that reaches it, never wrapped.
+ * OUT OF SCOPE: pjd_pipeline.h (the batcher's sink stays per picture), bin/decoder, pjd_split_decode, pjd_decode_batch.
+ * DETECTION.  No struct changed and PJD_VERSION stays 6: a caller checks for the symbol pjd_batch_n_outputs -- n_views once views
+ * are set, else n_images; 0 for NULL.                                                                                                */
+#define PJD_MAX_VIEWS 65536u
+int  pjd_batch_set_views(pjd_batch *b, const uint32_t *picture_of_view, uint32_t n_views);
+uint32_t pjd_batch_n_outputs(pjd_batch *b);
 int  pjd_batch_get_info(pjd_batch *b, pjd_batch_info *info);
 uint64_t pjd_batch_output_size(pjd_batch *b, int image);
 void *pjd_batch_device_output(pjd_batch *b, int image);      /* device pointer (HBM)          */

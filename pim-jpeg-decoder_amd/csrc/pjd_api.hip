@@ -137,10 +137,10 @@ int pool_dev_alloc(pjd_ctx *ctx, void **out, size_t bytes, std::vector<PoolBlock
     return PJD_OK;
 }
 
-std::string fmt_image(const char *f, int i)
+std::string fmt_name(const char *f, const std::string &name)          // f has one %s: "picture <i>" or "view <v> (picture <p>)"
 {
-    char buf[160];
-    std::snprintf(buf, sizeof buf, f, i);
+    char buf[240];
+    std::snprintf(buf, sizeof buf, f, name.c_str());
     return buf;
 }
 
@@ -214,15 +214,30 @@ struct pjd_batch {
     std::vector<uint64_t> res_off, res_bytes;
     uint64_t res_buf_bytes = 0, res_out_bytes = 0;   // packed size (what pjd_batch_packed_size reports), sum of res_bytes
     bool resized = false;                        // pjd_batch_set_resize
+    // pjd_batch_set_views: the OUTPUTS of the batch are views, view v a resample of picture view_pic[v].  Everything above that speaks
+    // about results (res_off / res_bytes, packed_off, the records of the pairs below) has n_out() entries; status words, the planner's
+    // lists and the intermediate stay per picture.  Without the call output i is picture i.
+    bool viewed = false;
+    std::vector<uint32_t> view_pic;
+    size_t n_out() const { return viewed ? view_pic.size() : plan.images.size(); }
+    uint32_t pic_of(size_t v) const { return viewed ? view_pic[v] : (uint32_t)v; }
+    std::string out_name(size_t v) const
+    {
+        char buf[64];
+        if (viewed) std::snprintf(buf, sizeof buf, "view %zu (picture %u)", v, view_pic[v]);
+        else std::snprintf(buf, sizeof buf, "picture %zu", v);
+        return buf;
+    }
+    bool views_unresolved() const { return viewed && !resized; }     // views without a resample: nothing can deliver them
     // The resample (pjd_resize_plan.h): what the caller asked for so far, and what it resolves to.  Every setter adds its argument to
     // the request and resolves all of it again; the records lie in the page-locked halves of the pairs below, pjd_batch_upload sends them.
     PjdResizeSpec spec;
     PjdResizeForm form;
     struct Pair { uint8_t *h = nullptr, *d = nullptr; size_t bytes = 0; };   // page-locked / HBM, taken once (take_pair)
-    Pair rs;                                     // PjdDevResize[n_images], then the prefix sum of tiles [n_images + 1]
-    Pair win;                                    // form.windowed: PjdDevResizeWin[n_images]
-    Pair pad;                                    // form.padded: PjdDevResizePad[n_images], then the prefix sum of their border lines [n_images + 1]
-    Pair aa;                                     // a table-driven filter: PjdDevResizeAA[n_images], then the weight table
+    Pair rs;                                     // PjdDevResize[n_out], then the prefix sum of tiles [n_out + 1]
+    Pair win;                                    // form.windowed: PjdDevResizeWin[n_out]
+    Pair pad;                                    // form.padded: PjdDevResizePad[n_out], then the prefix sum of their border lines [n_out + 1]
+    Pair aa;                                     // a table-driven filter: PjdDevResizeAA[n_out], then the weight table
     PjdNormalize norm{};                         // pjd_batch_set_normalize: dtype != 0, the result holds elements of PJD_DT_SIZE(dtype) bytes
     uint8_t pad_fill[3] = {0, 0, 0};             // pjd_batch_set_resize_pad
     bool pad_value_set = false;                  // pjd_batch_set_pad_value
@@ -231,9 +246,9 @@ struct pjd_batch {
     // the resample launch of this batch, whatever its filter and form
     void launch_resize(hipStream_t s) const
     {
-        const size_t n = dev.n_images;
+        const size_t n = n_out();                // the records' count: the kernels find a tile's record by it, whatever picture the record reads
         const bool planar = back.planes();
-        pjd_launch_resize(s, PjdResizeLaunch{dev.out, res_out, (const PjdDevResize *)rs.d, (const uint32_t *)(rs.d + n * sizeof(PjdDevResize)), dev.n_images, form.tiles, planar, norm,
+        pjd_launch_resize(s, PjdResizeLaunch{dev.out, res_out, (const PjdDevResize *)rs.d, (const uint32_t *)(rs.d + n * sizeof(PjdDevResize)), (uint32_t)n, form.tiles, planar, norm,
                                              form.windowed ? (const PjdDevResizeWin *)win.d : nullptr, form.oriented, spec.filter,
                                              (const PjdDevResizeAA *)aa.d, aa.d ? (const uint32_t *)(aa.d + n * sizeof(PjdDevResizeAA)) : nullptr, form.lds,
                                              form.padded ? (const PjdDevResizePad *)pad.d : nullptr, spec.channels});
@@ -241,9 +256,9 @@ struct pjd_batch {
     // ... and the border of its padded pictures, behind it: the two write disjoint bytes
     void launch_pad(hipStream_t s) const
     {
-        const size_t n = dev.n_images;
+        const size_t n = n_out();
         const bool planar = back.planes();
-        pjd_launch_resize_border(s, PjdBorderLaunch{res_out, (const PjdDevResize *)rs.d, (const PjdDevResizePad *)pad.d, (const uint32_t *)(pad.d + n * sizeof(PjdDevResizePad)), dev.n_images,
+        pjd_launch_resize_border(s, PjdBorderLaunch{res_out, (const PjdDevResize *)rs.d, (const PjdDevResizePad *)pad.d, (const uint32_t *)(pad.d + n * sizeof(PjdDevResizePad)), (uint32_t)n,
                                                     form.lines, planar, norm.dtype ? PJD_DT_SIZE(norm.dtype) : 1u, pjd_pad_fill(norm, planar, pad_fill, pad_value_set ? pad_value : nullptr), spec.channels});
     }
 };
@@ -568,6 +583,7 @@ int pjd_batch_upload(pjd_batch *b)
     if (!b) return PJD_E_ARG;
     pjd_ctx *ctx = b->ctx;
     PjdPlan &P = b->plan;
+    if (b->views_unresolved()) { ctx->err = "upload: the batch has views but no resample (pjd_batch_set_resize or pjd_batch_set_normalize first)"; return PJD_E_STATE; }
     hipSetDevice(ctx->device);
     hipStream_t s = ctx->stream;
     // asynchronous: the blob is page-locked and owned by the batch
@@ -879,6 +895,7 @@ static bool device_idle_then_count(pjd_batch *b)
 int pjd_batch_decode(pjd_batch *b)
 {
     if (!b) return PJD_E_ARG;
+    if (b->views_unresolved()) { b->ctx->err = "decode: the batch has views but no resample (pjd_batch_set_resize or pjd_batch_set_normalize first)"; return PJD_E_STATE; }
     if (!b->uploaded) { b->ctx->err = "decode before upload"; return PJD_E_STATE; }
     hipSetDevice(b->ctx->device);
     const bool groups = !b->plan.groups.empty() && device_idle_then_count(b);
@@ -894,6 +911,7 @@ int pjd_batch_decode(pjd_batch *b)
 int pjd_batch_decode_timed(pjd_batch *b, pjd_timings *t)
 {
     if (!b || !t) return PJD_E_ARG;
+    if (b->views_unresolved()) { b->ctx->err = "decode: the batch has views but no resample (pjd_batch_set_resize or pjd_batch_set_normalize first)"; return PJD_E_STATE; }
     if (!b->uploaded) { b->ctx->err = "decode before upload"; return PJD_E_STATE; }
     hipSetDevice(b->ctx->device);
     std::memset(t, 0, sizeof *t);
@@ -903,6 +921,7 @@ int pjd_batch_decode_timed(pjd_batch *b, pjd_timings *t)
 int pjd_batch_capture(pjd_batch *b)
 {
     if (!b) return PJD_E_ARG;
+    if (b->views_unresolved()) { b->ctx->err = "capture: the batch has views but no resample (pjd_batch_set_resize or pjd_batch_set_normalize first)"; return PJD_E_STATE; }
     if (!b->uploaded) { b->ctx->err = "capture before upload"; return PJD_E_STATE; }
     pjd_ctx *ctx = b->ctx;
     hipSetDevice(ctx->device);
@@ -941,7 +960,7 @@ int pjd_batch_download(pjd_batch *b, uint8_t *const *out, int32_t *status)
     pjd_ctx *ctx = b->ctx;
     PjdPlan &P = b->plan;
     if (out)
-        for (size_t i = 0; i < P.images.size(); i++)
+        for (size_t i = 0; i < b->n_out(); i++)                  // the outputs: the views where the batch has them; the status words stay per picture
             if (out[i]) HIP_TRY(ctx, hipMemcpyAsync(out[i], b->res_out + b->res_off[i], b->res_bytes[i], hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (status)
@@ -996,7 +1015,7 @@ uint64_t pjd_batch_packed_size(pjd_batch *b) { return b ? b->res_buf_bytes : 0; 
 
 uint64_t pjd_batch_output_offset(pjd_batch *b, int image)
 {
-    if (!b || image < 0 || (size_t)image >= b->plan.images.size()) return 0;
+    if (!b || image < 0 || (size_t)image >= b->n_out()) return 0;
     return b->res_off[image];
 }
 
@@ -1006,6 +1025,7 @@ int pjd_batch_bind_output(pjd_batch *b, void *device_base, uint64_t capacity, co
     pjd_ctx *ctx = b->ctx;
     PjdPlan &P = b->plan;
     if (b->uploaded) { ctx->err = "bind_output after upload"; return PJD_E_STATE; }
+    if (b->views_unresolved()) { ctx->err = "bind_output: the batch has views but no resample (pjd_batch_set_resize or pjd_batch_set_normalize first)"; return PJD_E_STATE; }
     if (!device_base) { ctx->err = "bind_output: null pointer"; return PJD_E_ARG; }
     if (P.out_format == PJD_OUT_BMP) { ctx->err = "bind_output: a BMP batch cannot be bound (its row padding relies on the batch's own zeroed buffer)"; return PJD_E_ARG; }
     hipSetDevice(ctx->device);
@@ -1025,14 +1045,14 @@ int pjd_batch_bind_output(pjd_batch *b, void *device_base, uint64_t capacity, co
             return PJD_E_ARG;
         }
     }
-    const size_t n = P.images.size();
+    const size_t n = b->n_out();                                     // the outputs: pictures, or views
     if (b->packed_off.empty()) b->packed_off = b->res_off;
-    std::vector<std::pair<uint64_t, uint64_t>> ranges(n);            // (offset, size) of every picture
+    std::vector<std::pair<uint64_t, uint64_t>> ranges(n);            // (offset, size) of every output
     for (size_t i = 0; i < n; i++) {
         ranges[i] = {offsets ? offsets[i] : b->packed_off[i], b->res_bytes[i]};
-        if (ranges[i].first > capacity || ranges[i].second > capacity - ranges[i].first) { ctx->err = fmt_image("bind_output: picture %d ends beyond the capacity", (int)i); return PJD_E_ARG; }
+        if (ranges[i].first > capacity || ranges[i].second > capacity - ranges[i].first) { ctx->err = fmt_name("bind_output: %s ends beyond the capacity", b->out_name(i)); return PJD_E_ARG; }
         if (b->norm.dtype != 0 && ((uintptr_t)device_base + ranges[i].first) % PJD_DT_SIZE(b->norm.dtype) != 0) {
-            ctx->err = fmt_image("bind_output: picture %d does not start at a multiple of the element size (pjd_batch_set_normalize)", (int)i);
+            ctx->err = fmt_name("bind_output: %s does not start at a multiple of the element size (pjd_batch_set_normalize)", b->out_name(i));
             return PJD_E_ARG;
         }
     }
@@ -1040,7 +1060,7 @@ int pjd_batch_bind_output(pjd_batch *b, void *device_base, uint64_t capacity, co
         std::vector<std::pair<uint64_t, uint64_t>> sorted = ranges;
         std::sort(sorted.begin(), sorted.end());
         for (size_t i = 1; i < n; i++)
-            if (sorted[i - 1].first + sorted[i - 1].second > sorted[i].first) { ctx->err = "bind_output: picture ranges overlap"; return PJD_E_ARG; }
+            if (sorted[i - 1].first + sorted[i - 1].second > sorted[i].first) { ctx->err = b->viewed ? "bind_output: view ranges overlap" : "bind_output: picture ranges overlap"; return PJD_E_ARG; }
     }
     // from here on nothing fails.  The batch's own result buffer goes back to the pool.  Without a resize the result is what the back
     // end writes: the planner's image records (and their copy in the input blob, which pjd_batch_upload sends) take the bound
@@ -1125,6 +1145,40 @@ int pjd_libjpeg_upsample_row(const uint8_t *cur, const uint8_t *nb, int v, uint3
     return PJD_OK;
 }
 
+int pjd_batch_set_views(pjd_batch *b, const uint32_t *picture_of_view, uint32_t n_views)
+{
+    if (!b) return PJD_E_ARG;
+    pjd_ctx *ctx = b->ctx;
+    PjdPlan &P = b->plan;
+    if (b->viewed) { ctx->err = "set_views: already set for this batch"; return PJD_E_STATE; }
+    if (b->resized) { ctx->err = b->norm.dtype != 0 ? "set_views after set_normalize" : "set_views after set_resize"; return PJD_E_STATE; }
+    if (b->bound) { ctx->err = "set_views after bind_output"; return PJD_E_STATE; }
+    if (b->uploaded) { ctx->err = "set_views after upload"; return PJD_E_STATE; }
+    if (!picture_of_view) { ctx->err = "set_views: null view array"; return PJD_E_ARG; }
+    if (n_views == 0 || n_views > PJD_MAX_VIEWS) { ctx->err = "set_views: the number of views must be 1..PJD_MAX_VIEWS"; return PJD_E_ARG; }
+    if (P.out_format == PJD_OUT_BMP) { ctx->err = "set_views: a BMP batch takes no views (it takes no resample: PJD_OUT_RGB8, PJD_OUT_RGB8_PLANAR or PJD_OUT_GRAY8)"; return PJD_E_ARG; }
+    const size_t n_pic = P.images.size();
+    for (uint32_t v = 0; v < n_views; v++)
+        if (picture_of_view[v] >= n_pic) {
+            char buf[120];
+            std::snprintf(buf, sizeof buf, "set_views: view %u names picture %u, the batch has %zu", v, picture_of_view[v], n_pic);
+            ctx->err = buf;
+            return PJD_E_ARG;
+        }
+    // from here on nothing fails.  Until the resample is set -- nothing can be bound, uploaded or decoded before -- an output's offset
+    // and size are those of its picture in the batch's own buffer.
+    b->view_pic.assign(picture_of_view, picture_of_view + n_views);
+    b->viewed = true;
+    std::vector<uint64_t> off(n_views), bytes(n_views);
+    uint64_t sum = 0;
+    for (uint32_t v = 0; v < n_views; v++) { off[v] = b->res_off[b->view_pic[v]]; bytes[v] = b->res_bytes[b->view_pic[v]]; sum += bytes[v]; }
+    b->res_off = std::move(off); b->res_bytes = std::move(bytes);
+    b->res_out_bytes = sum;
+    return PJD_OK;
+}
+
+uint32_t pjd_batch_n_outputs(pjd_batch *b) { return b ? (uint32_t)b->n_out() : 0u; }
+
 int pjd_batch_set_resize(pjd_batch *b, const uint32_t *out_w, const uint32_t *out_h)
 {
     if (!b) return PJD_E_ARG;
@@ -1135,27 +1189,30 @@ int pjd_batch_set_resize(pjd_batch *b, const uint32_t *out_w, const uint32_t *ou
     if (b->uploaded) { ctx->err = "set_resize after upload"; return PJD_E_STATE; }
     if (!out_w || !out_h) { ctx->err = "set_resize: null size array"; return PJD_E_ARG; }
     if (P.out_format == PJD_OUT_BMP) { ctx->err = "set_resize: a BMP batch cannot be resized (PJD_OUT_RGB8 or PJD_OUT_RGB8_PLANAR)"; return PJD_E_ARG; }
-    const size_t n = P.images.size();
-    // the request: every picture from where the back end wrote it at its decode size to the packed layout of the result buffer
-    // (256-byte aligned offsets, as the planner lays out a batch's own buffer; pjd_batch_bind_output may still change them)
+    const size_t n = b->n_out();
+    // the request: every output -- picture i, or view i of its picture -- from where the back end wrote its source at its decode size to
+    // the packed layout of the result buffer (256-byte aligned offsets, as the planner lays out a batch's own buffer;
+    // pjd_batch_bind_output may still change them)
     const uint32_t channels = b->back.gray() ? 1u : 3u;    // a grey batch is a planar batch with one plane
     const PjdPackedLayout lay = pjd_packed_layout(out_w, out_h, n, 1, channels);
     PjdResizeSpec spec;
     spec.planar = b->back.planes();
     spec.channels = channels;
     spec.out_w.assign(out_w, out_w + n); spec.out_h.assign(out_h, out_h + n);
-    size_t shard = n;                                      // the first shard of the batch
+    if (b->viewed) spec.view_pic = b->view_pic;
+    size_t shard = n;                                      // the first output that reads a shard
     for (size_t i = 0; i < n; i++) {
-        const PjdDevImage &g = P.images[i];
+        const uint32_t p = b->pic_of(i);
+        const PjdDevImage &g = P.images[p];
         uint32_t sw = 0, sh = 0;
         pjd_scaled_dims(g.width, g.height, PJD_IF_OUT_SCALE_LOG(g.flags) << 4, &sw, &sh);
         spec.pic.push_back(PjdResizePicture{g.out_off, lay.off[i], sw, sh, g.out_stride});
-        if (P.host[i].shard && shard == n) shard = i;
+        if (P.host[p].shard && shard == n) shard = i;
     }
     PjdResizeWork w;
     const PjdResizeFault f = pjd_resize_resolve(spec, w);
     // picture by picture: its size, then whether it is a shard; the batch as a whole behind them
-    if (shard < n && !(f.picture >= 0 && (size_t)f.picture <= shard)) { ctx->err = fmt_image("set_resize: picture %d is a shard (its picture is only partly written)", (int)shard); return PJD_E_ARG; }
+    if (shard < n && !(f.picture >= 0 && (size_t)f.picture <= shard)) { ctx->err = fmt_name("set_resize: %s is a shard (its picture is only partly written)", b->out_name(shard)); return PJD_E_ARG; }
     if (!f.text.empty()) { ctx->err = "set_resize: " + f.text; return PJD_E_ARG; }
     hipSetDevice(ctx->device);
     void *d_res = nullptr;                                 // the result buffer first: the batch is as it was until everything is taken
@@ -1323,16 +1380,19 @@ int pjd_batch_set_normalize(pjd_batch *b, int dtype, const float scale[3], const
     for (int c = 0; c < 3; c++)
         if (!finite_f32(scale[c]) || !finite_f32(bias[c])) { ctx->err = "set_normalize: scale and bias must be finite"; return PJD_E_ARG; }
     if (P.out_format == PJD_OUT_BMP) { ctx->err = "set_normalize: a BMP batch cannot be normalised (PJD_OUT_RGB8 or PJD_OUT_RGB8_PLANAR)"; return PJD_E_ARG; }
-    const size_t n = P.images.size();
+    const size_t n = b->n_out();
     for (size_t i = 0; i < n; i++)
-        if (P.host[i].shard) { ctx->err = fmt_image("set_normalize: picture %d is a shard (its picture is only partly written)", (int)i); return PJD_E_ARG; }
+        if (P.host[b->pic_of(i)].shard) { ctx->err = fmt_name("set_normalize: %s is a shard (its picture is only partly written)", b->out_name(i)); return PJD_E_ARG; }
     hipSetDevice(ctx->device);
     // the result buffer in elements of the new size: packed, 256-byte aligned offsets.  Taken before anything changes: a failure
     // leaves the batch as it was (but for a block that stays with it until it is destroyed).
     std::vector<uint32_t> w = b->spec.out_w, h = b->spec.out_h;
     if (!b->resized) {
         w.resize(n); h.resize(n);
-        for (size_t i = 0; i < n; i++) pjd_scaled_dims(P.images[i].width, P.images[i].height, PJD_IF_OUT_SCALE_LOG(P.images[i].flags) << 4, &w[i], &h[i]);
+        for (size_t i = 0; i < n; i++) {                      // every output at its own picture's output size
+            const PjdDevImage &g = P.images[b->pic_of(i)];
+            pjd_scaled_dims(g.width, g.height, PJD_IF_OUT_SCALE_LOG(g.flags) << 4, &w[i], &h[i]);
+        }
     }
     const PjdPackedLayout lay = pjd_packed_layout(w.data(), h.data(), n, PJD_DT_SIZE(dtype), P.gray ? 1u : 3u);
     void *d_res = nullptr;
@@ -1340,7 +1400,7 @@ int pjd_batch_set_normalize(pjd_batch *b, int dtype, const float scale[3], const
     if (rc != PJD_OK) return rc;
     b->device_bytes += lay.buf_bytes;
     if (!b->resized) {
-        // no resize set: the identity resample (every tap weight 0) of every picture at its own output size
+        // no resize set: the identity resample (every tap weight 0) of every picture (every view: of its picture) at its own output size
         rc = pjd_batch_set_resize(b, w.data(), h.data());
         if (rc != PJD_OK) { give_back(b, d_res, lay.buf_bytes); return rc; }
     }
@@ -1547,13 +1607,13 @@ int pjd_batch_huff_occupancy(pjd_batch *b, int32_t *workgroups_per_cu, uint32_t 
 
 uint64_t pjd_batch_output_size(pjd_batch *b, int image)
 {
-    if (!b || image < 0 || (size_t)image >= b->plan.host.size()) return 0;
+    if (!b || image < 0 || (size_t)image >= b->n_out()) return 0;
     return b->res_bytes[image];
 }
 
 void *pjd_batch_device_output(pjd_batch *b, int image)
 {
-    if (!b || image < 0 || (size_t)image >= b->plan.host.size()) return nullptr;
+    if (!b || image < 0 || (size_t)image >= b->n_out()) return nullptr;
     return b->res_out + b->res_off[image];
 }
 

@@ -8,18 +8,16 @@
 
 namespace {
 
-PjdResizeFault fault_at(int picture, const char *text, const char *more = "")
+PjdResizeFault fault_at(const PjdResizeSpec &spec, size_t i, const char *text)
 {
-    char buf[64];
-    std::snprintf(buf, sizeof buf, "picture %d: ", picture);
-    return PjdResizeFault{std::string(buf) + text + more, picture};
+    return PjdResizeFault{pjd_resize_output_name(spec, i) + ": " + text, (int)i};
 }
 
-PjdResizeFault fault_of(const char *fmt, int picture)        // a text that names its picture itself
+PjdResizeFault fault_of(const PjdResizeSpec &spec, const char *fmt, size_t i)        // a text that names its picture itself (%s)
 {
-    char buf[200];
-    std::snprintf(buf, sizeof buf, fmt, picture);
-    return PjdResizeFault{buf, picture};
+    char buf[240];
+    std::snprintf(buf, sizeof buf, fmt, pjd_resize_output_name(spec, i).c_str());
+    return PjdResizeFault{buf, (int)i};
 }
 
 // The weight table of a table-driven filter: one axis table per distinct (source length, target length) of the batch -- the pictures
@@ -88,6 +86,14 @@ uint16_t f32_to_f16_bits(float f)
 
 }  // namespace
 
+std::string pjd_resize_output_name(const PjdResizeSpec &spec, size_t i)
+{
+    char buf[64];
+    if (i < spec.view_pic.size()) std::snprintf(buf, sizeof buf, "view %zu (picture %u)", i, spec.view_pic[i]);
+    else std::snprintf(buf, sizeof buf, "picture %zu", i);
+    return buf;
+}
+
 const char *pjd_resize_window_fault(uint32_t sw, uint32_t sh, uint32_t tw, uint32_t th, const pjd_resize_window *win, int filter)
 {
     if (sw == 0 || sw > 65535u || sh == 0 || sh > 65535u || tw == 0 || tw > 65535u || th == 0 || th > 65535u) return "picture and target sizes must be 1..65535";
@@ -124,7 +130,7 @@ PjdResizeFault pjd_resize_resolve(const PjdResizeSpec &spec, PjdResizeWork &out)
     const bool table = spec.filter == PJD_RESIZE_ANTIALIAS || spec.filter == PJD_RESIZE_BICUBIC;
     if (!table && spec.filter != PJD_RESIZE_BILINEAR) return PjdResizeFault{"unknown filter (PJD_RESIZE_BILINEAR, PJD_RESIZE_ANTIALIAS or PJD_RESIZE_BICUBIC)", -1};
     for (size_t i = 0; i < n; i++)
-        if (spec.out_w[i] == 0 || spec.out_w[i] > 65535u || spec.out_h[i] == 0 || spec.out_h[i] > 65535u) return fault_at((int)i, "target width and height must be 1..65535");
+        if (spec.out_w[i] == 0 || spec.out_w[i] > 65535u || spec.out_h[i] == 0 || spec.out_h[i] > 65535u) return fault_at(spec, i, "target width and height must be 1..65535");
 
     // the content of every delivered picture: its canvas less its pad; a padded picture has a border line per canvas line
     out.ct_w = spec.out_w; out.ct_h = spec.out_h;
@@ -133,12 +139,14 @@ PjdResizeFault pjd_resize_resolve(const PjdResizeSpec &spec, PjdResizeWork &out)
     if (spec.pad_set)
         for (size_t i = 0; i < n; i++) {
             const pjd_resize_pad &p = spec.pad[i];
-            if (const char *f = pjd_resize_pad_fault(spec.out_w[i], spec.out_h[i], &p)) return fault_at((int)i, f);
+            if (const char *f = pjd_resize_pad_fault(spec.out_w[i], spec.out_h[i], &p)) return fault_at(spec, i, f);
             out.ct_w[i] -= p.left + p.right; out.ct_h[i] -= p.top + p.bottom;
             bordered[i] = p.left || p.top || p.right || p.bottom;
             if (bordered[i]) lines += (uint64_t)(spec.planar ? spec.channels : 1u) * spec.out_h[i];
             form.padded = form.padded || bordered[i];
         }
+    // both prefix sums are made in 64 bits and refused from 2^31 on: with views (up to PJD_MAX_VIEWS outputs of up to 2^21 tiles each) a
+    // request can pass 2^32, and nothing of it is narrowed to the kernels' 32-bit words before it has been refused here
     if (lines >= (1ull << 31)) return PjdResizeFault{"the canvases of this batch are too large for one launch", -1};
 
     // Q, the picture the resample computes: its target is the content with the axes swapped where the orientation transposes
@@ -146,7 +154,7 @@ PjdResizeFault pjd_resize_resolve(const PjdResizeSpec &spec, PjdResizeWork &out)
     uint64_t tiles = 0;
     for (size_t i = 0; i < n; i++) {
         const uint32_t o = spec.ori_set ? spec.orientation[i] : 1u;
-        if (o < 1u || o > 8u) return fault_at((int)i, "the orientation must be 1..8");
+        if (o < 1u || o > 8u) return fault_at(spec, i, "the orientation must be 1..8");
         ori[i] = pjd_orient_flags(o);
         if (ori[i] & PJD_RWI_TRANSPOSE) std::swap(tw[i], th[i]);
         form.oriented = form.oriented || o != 1u;
@@ -158,7 +166,7 @@ PjdResizeFault pjd_resize_resolve(const PjdResizeSpec &spec, PjdResizeWork &out)
     if (spec.win_set)
         for (size_t i = 0; i < n; i++) {
             const pjd_resize_window &w = spec.win[i];
-            if (const char *f = pjd_resize_window_fault(spec.pic[i].sw, spec.pic[i].sh, tw[i], th[i], &w, PJD_RESIZE_BILINEAR)) return fault_at((int)i, f);
+            if (const char *f = pjd_resize_window_fault(spec.pic[i].sw, spec.pic[i].sh, tw[i], th[i], &w, PJD_RESIZE_BILINEAR)) return fault_at(spec, i, f);
             any_win = any_win || w.x || w.y || w.w || w.h || w.vw || w.vh || w.ox || w.oy || w.flags;
         }
     // the most general form a batch needs is the one it runs: a pad brings the oriented launch, an orientation the windowed one
@@ -198,8 +206,8 @@ PjdResizeFault pjd_resize_resolve(const PjdResizeSpec &spec, PjdResizeWork &out)
     for (size_t i = 0; i < n; i++) {
         const PjdDevResizeWin w = window(i);
         if (w.w > 16u * w.vw || w.h > 16u * w.vh)
-            return fault_of(form.windowed ? "the window of picture %d is more than 16x its virtual target on an axis (pre-scale with PJD_F_SCALE_*)"
-                                          : "picture %d is more than 16x its target on an axis at its decode size (pre-scale with PJD_F_SCALE_*)", (int)i);
+            return fault_of(spec, form.windowed ? "the window of %s is more than 16x its virtual target on an axis (pre-scale with PJD_F_SCALE_*)"
+                                                : "%s is more than 16x its target on an axis at its decode size (pre-scale with PJD_F_SCALE_*)", i);
     }
     AxisTables tables(spec.filter, out.tab);
     out.aa.resize(n);
@@ -209,7 +217,7 @@ PjdResizeFault pjd_resize_resolve(const PjdResizeSpec &spec, PjdResizeWork &out)
         if (out.tab.size() + ((size_t)w.vw + w.vh) * (1u + tables.max_taps) >= (1ull << 31)) return PjdResizeFault{"the weight table of this batch is too large", -1};
         const Axis x = tables.axis(w.w, w.vw), y = tables.axis(w.h, w.vh);
         if (tables.cubic && std::max(x.gain, y.gain) > PJD_BICUBIC_MAX_GAIN)
-            return fault_of("the bicubic weights of picture %d sum to more than PJD_BICUBIC_MAX_GAIN in magnitude on an axis", (int)i);
+            return fault_of(spec, "the bicubic weights of %s sum to more than PJD_BICUBIC_MAX_GAIN in magnitude on an axis", i);
         out.aa[i] = PjdDevResizeAA{x.off, x.taps, y.off, y.taps};
         // the widest row segment one of its tiles stages: first tap of the tile's first column to the last tap of its last one
         for (uint32_t c0 = 0; c0 < r.tw; c0 += PJD_RS_COLS) {

@@ -20,7 +20,9 @@ struct PjdResizePicture {
     uint32_t sw, sh, src_stride;           // decode size, and bytes per source row
 };
 struct PjdResizeSpec {
-    std::vector<PjdResizePicture> pic;
+    std::vector<PjdResizePicture> pic;     // one per OUTPUT: entries may repeat a source and name sources in any order (pjd_batch_set_views)
+    std::vector<uint32_t> view_pic;        // pjd_batch_set_views: the picture of every output (as many as `pic`); empty: output i is picture i.
+                                           // Read by the fault texts alone ("view <v> (picture <p>)"): no record depends on it
     bool planar = false;
     uint32_t channels = 3;                 // 3, or 1 for a grey batch (PJD_OUT_GRAY8): planar with one plane; it always resolves to the padded form
     std::vector<uint32_t> out_w, out_h;    // pjd_batch_set_resize: the delivered canvases
@@ -49,11 +51,14 @@ struct PjdResizeWork {
     std::vector<uint32_t> ct_w, ct_h;      // the content of each delivered picture: the canvas less its pad
 };
 
-// no fault: text is empty.  The text is what pjd_last_error reports behind the setter's own "set_...: "; picture -1: the batch as a whole
+// no fault: text is empty.  The text is what pjd_last_error reports behind the setter's own "set_...: "; picture -1: the batch as a whole,
+// else the index of the output at fault (the view, where the batch has views)
 struct PjdResizeFault {
     std::string text;
     int picture = -1;
 };
+// "picture <i>", or "view <i> (picture <p>)" where the request has views: how every fault text names an output
+std::string pjd_resize_output_name(const PjdResizeSpec &spec, size_t i);
 PjdResizeFault pjd_resize_resolve(const PjdResizeSpec &spec, PjdResizeWork &out);
 
 // THE validation of a source window and of a pad record (include/pjd.h): null, or what is wrong with it

@@ -190,6 +190,10 @@ def dev_lib():
         L.pjd_batch_output_offset.argtypes = [vp, i32]
         L.pjd_batch_bind_output.restype = i32
         L.pjd_batch_bind_output.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.pjd_batch_set_views.restype = i32
+        L.pjd_batch_set_views.argtypes = [vp, C.POINTER(C.c_uint32), C.c_uint32]
+        L.pjd_batch_n_outputs.restype = C.c_uint32
+        L.pjd_batch_n_outputs.argtypes = [vp]
         L.pjd_batch_set_resize.restype = i32
         L.pjd_batch_set_resize.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.pjd_resize_tap.restype = i32
@@ -383,7 +387,8 @@ class Batch:
         h = C.c_void_p()
         ctx._check(self.L.pjd_batch_create(ctx._h, arr, self.n, out_format, C.byref(h)), "pjd_batch_create")
         self._h = h
-        self._resize = None                        # set_resize: the (h, w) of every picture
+        self._resize = None                        # set_resize: the (h, w) of every output
+        self.views = None                          # set_views: the picture of every view
         self._dtype = None                         # set_normalize: DT_*
 
     def __enter__(self):
@@ -396,6 +401,27 @@ class Batch:
         if self._h:
             self.L.pjd_batch_destroy(self._h)
             self._h = None
+
+    @property
+    def n_out(self):
+        """The outputs of the batch (pjd_batch_n_outputs): its views once set_views() was called, else its pictures.  Status words stay
+        per picture (`n`)."""
+        return self.n if self.views is None else len(self.views)
+
+    def set_views(self, picture_of_view):
+        """pjd_batch_set_views: the batch delivers len(picture_of_view) outputs, view v a resample of picture picture_of_view[v] (any
+        order, any number of views per picture, none included); every picture is decoded once.  From then on every per-picture argument
+        of set_resize(), set_resize_pad(), set_orientation(), set_resize_window() and bind_output(), and the index of output_size(),
+        output_offset(), output_shape() and device_output(), is per VIEW (n_out entries); download() returns n_out arrays and n statuses.
+        Once, first: before set_resize() / set_normalize() / bind_output() / upload(), one of the first two must follow; not for OUT_BMP."""
+        views = [int(p) for p in picture_of_view]
+        if any(not 0 <= p < 2 ** 32 for p in views):
+            raise ValueError("set_views: picture indices must fit 32 bits")
+        if len(views) >= 2 ** 32:
+            raise ValueError("set_views: too many views")
+        arr = (C.c_uint32 * max(len(views), 1))(*views)
+        self.ctx._check(self.L.pjd_batch_set_views(self._h, arr, len(views)), "pjd_batch_set_views")
+        self.views = views
 
     def upload(self):
         self.ctx._check(self.L.pjd_batch_upload(self._h), "pjd_batch_upload")
@@ -442,7 +468,7 @@ class Batch:
     def output_shape(self, i):
         """Shape of picture i as download() returns it: (h, w, 3) for OUT_RGB8, (3, h, w) for OUT_RGB8_PLANAR, (h, w) for OUT_GRAY8,
         flat for OUT_BMP."""
-        d = self._descs[i]
+        d = self._descs[i if self.views is None else self.views[i]]
         if self._resize is not None:
             h, w = self._resize[i]
         else:
@@ -459,14 +485,14 @@ class Batch:
         """pjd_batch_set_resize: picture i leaves the decode resampled to sizes[i] = (h, w), with the bilinear filter include/pjd.h
         specifies bit for bit.  Once, before bind_output() / upload(); not for OUT_BMP, not for shards.  output_size, output_shape,
         output_offset, packed_size, download and bind_output speak about the resized pictures from then on."""
-        if len(sizes) != self.n:
-            raise ValueError("set_resize: one (h, w) per picture")
+        if len(sizes) != self.n_out:
+            raise ValueError("set_resize: one (h, w) per picture (per view after set_views)")
         sizes = [(int(h), int(w)) for h, w in sizes]
         for h, w in sizes:
             if not (0 <= h < 2 ** 32 and 0 <= w < 2 ** 32):
                 raise ValueError("set_resize: sizes must fit 32 bits")
-        ws = (C.c_uint32 * max(self.n, 1))(*[w for _, w in sizes])
-        hs = (C.c_uint32 * max(self.n, 1))(*[h for h, _ in sizes])
+        ws = (C.c_uint32 * max(self.n_out, 1))(*[w for _, w in sizes])
+        hs = (C.c_uint32 * max(self.n_out, 1))(*[h for h, _ in sizes])
         self.ctx._check(self.L.pjd_batch_set_resize(self._h, ws, hs), "pjd_batch_set_resize")
         self._resize = sizes
 
@@ -476,11 +502,11 @@ class Batch:
         launch behind it.  pads[i]: a ResizePad, None (the all-zero record), or a dict / tuple of its fields (left, top, right, bottom).
         From then on "the target" of every later call is the content, canvas less pad.  Once, after set_resize() and before
         set_orientation() / set_resize_window() / set_resize_filter() / set_normalize() / bind_output() / upload()."""
-        if len(pads) != self.n:
-            raise ValueError("set_resize_pad: one pad (or None) per picture")
+        if len(pads) != self.n_out:
+            raise ValueError("set_resize_pad: one pad (or None) per picture (per view after set_views)")
         if len(fill) != 3 or any(not 0 <= int(v) <= 255 or int(v) != v for v in fill):
             raise ValueError("set_resize_pad: the fill is three bytes (R, G, B)")
-        arr = (ResizePad * max(self.n, 1))()
+        arr = (ResizePad * max(self.n_out, 1))()
         for i, p in enumerate(pads):
             if p is not None:
                 arr[i] = resize_pad(p)
@@ -502,12 +528,12 @@ class Batch:
         launch.  The sizes of set_resize() are those of the DELIVERED pictures; for 5..8 the resample's own target is (w, h), and that
         is what later windows speak about.  Once, after set_resize() and before set_resize_window() / set_resize_filter() /
         set_normalize() / bind_output() / upload()."""
-        if len(orientations) != self.n:
-            raise ValueError("set_orientation: one orientation per picture")
+        if len(orientations) != self.n_out:
+            raise ValueError("set_orientation: one orientation per picture (per view after set_views)")
         vals = [int(o) for o in orientations]
         if any(not 0 <= o <= 255 for o in vals):
             raise ValueError("set_orientation: orientations are 1..8")
-        arr = (C.c_uint8 * max(self.n, 1))(*vals)
+        arr = (C.c_uint8 * max(self.n_out, 1))(*vals)
         self.ctx._check(self.L.pjd_batch_set_orientation(self._h, arr), "pjd_batch_set_orientation")
 
     def set_resize_window(self, windows):
@@ -515,9 +541,9 @@ class Batch:
         mirrored where asked -- flip(resize(P[y:y+h, x:x+w], vw, vh)[oy:oy+th, ox:ox+tw]), the arithmetic include/pjd.h specifies.
         windows[i]: a ResizeWindow, None (the whole picture: the all-zero record), or a dict / tuple of its fields (x, y, w, h, vw, vh,
         ox, oy, flags).  Once, after set_resize() and before set_resize_filter() / set_normalize() / bind_output() / upload()."""
-        if len(windows) != self.n:
-            raise ValueError("set_resize_window: one window (or None) per picture")
-        arr = (ResizeWindow * max(self.n, 1))()
+        if len(windows) != self.n_out:
+            raise ValueError("set_resize_window: one window (or None) per picture (per view after set_views)")
+        arr = (ResizeWindow * max(self.n_out, 1))()
         for i, w in enumerate(windows):
             if w is not None:
                 arr[i] = resize_window(w)
@@ -551,9 +577,9 @@ class Batch:
         for as long as the batch decodes, and orders its own streams against the context's (sync())."""
         arr = None
         if offsets is not None:
-            if len(offsets) != self.n:
-                raise ValueError("bind_output: one offset per picture")
-            arr = (C.c_uint64 * max(self.n, 1))(*[int(o) for o in offsets])
+            if len(offsets) != self.n_out:
+                raise ValueError("bind_output: one offset per picture (per view after set_views)")
+            arr = (C.c_uint64 * max(self.n_out, 1))(*[int(o) for o in offsets])
         self.ctx._check(self.L.pjd_batch_bind_output(self._h, C.c_void_p(int(device_ptr)), int(capacity), arr), "pjd_batch_bind_output")
 
     def statuses(self):
@@ -563,8 +589,8 @@ class Batch:
         return [int(st[i]) for i in range(self.n)]
 
     def download(self):
-        outs = [np.zeros(self.output_size(i), np.uint8) for i in range(self.n)]
-        ptrs = (C.c_void_p * max(self.n, 1))(*[o.ctypes.data for o in outs])
+        outs = [np.zeros(self.output_size(i), np.uint8) for i in range(self.n_out)]
+        ptrs = (C.c_void_p * max(self.n_out, 1))(*[o.ctypes.data for o in outs])
         st = (C.c_int32 * max(self.n, 1))()
         self.ctx._check(self.L.pjd_batch_download(self._h, ptrs, st), "pjd_batch_download")
         if self._dtype is not None:                # normalised: elements of 2 or 4 bytes (bf16 as its raw bits: numpy has no such type)
@@ -593,7 +619,7 @@ class Batch:
             self.ctx._check(self.L.pjd_batch_download_packed(self._h, host, size, st), "pjd_batch_download_packed")
             whole = np.ctypeslib.as_array(C.cast(host, C.POINTER(C.c_uint8)), shape=(size,))
             outs = []
-            for i in range(self.n):
+            for i in range(self.n_out):
                 off, n = int(self.L.pjd_batch_output_offset(self._h, i)), self.output_size(i)
                 outs.append(whole[off:off + n].copy())
         finally:

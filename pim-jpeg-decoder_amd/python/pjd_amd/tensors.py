@@ -4,7 +4,7 @@ The batch is bound (Batch.bind_output, pjd_batch_bind_output of include/pjd.h) t
 on the context's device; the back end writes the pictures straight into it -- planar R, G, B (OUT_RGB8_PLANAR, "CHW") by
 default -- and the results are views of that buffer.  No native code of its own.  torch is imported inside the functions that
 need it: uniform_output_shape(), pick_scale_flags(), pick_libjpeg_scale_flags(), normalize_constants(), center_crop_window(), window_at_scale(), orient_hw(),
-orient_then_hflip() and crop_to_stored() are pure.
+orient_then_hflip(), crop_to_stored(), tile_views(), least_reduced_scale_flags() and plan_views() are pure.
 
 Pictures of different sizes become ONE [N, 3, H, W] tensor with decode_resized_batch_tensor: the library resamples every picture to
 H x W inside the decode (Batch.set_resize, pjd_batch_set_resize), after the box pre-scale pick_scale_flags chooses.
@@ -17,6 +17,10 @@ Orientation rides there too (Batch.set_orientation, pjd_batch_set_orientation): 
 picture (Scanned.orientation) and the pictures come out upright -- what torchvision.io.decode_jpeg(apply_exif_orientation=True) and
 PIL.ImageOps.exif_transpose give -- with crops=, flips= and resize_short= speaking about the UPRIGHT picture.  No transpose / flip +
 .contiguous() pass over the finished tensor.
+
+Several outputs of one picture -- two augmented views, multi-crop, FiveCrop, two scales of a crop, tiles -- come from ONE decode of it
+with views= (Batch.set_views, pjd_batch_set_views): view v is a resample of picture views[v], every per-picture keyword then has one
+entry per view, the result is [V, C, H, W] and the statuses stay per picture.  tile_views() cuts one picture into a grid of tiles.
 
 The tensor a model takes -- fp16, bf16 or fp32, (x / 255 - mean) / std -- comes out of the same launch with
 decode_normalized_batch_tensor (Batch.set_normalize, pjd_batch_set_normalize): no uint8 tensor, no elementwise kernels after it.
@@ -95,11 +99,13 @@ def _torch():
 
 
 def _run(ctx, descs, out_format, capacity, offsets, device, resize=None, normalize=None, antialias=False, windows=None, interpolation="bilinear",
-         orientations=None, pads=None, fill=(0, 0, 0), pad_value=None):
+         orientations=None, pads=None, fill=(0, 0, 0), pad_value=None, views=None):
     """Create, (set the resize, its orientations, its windows, its filter, the normalisation,) bind to a fresh torch buffer, upload, decode, sync -> (buffer, batch offsets,
     statuses).  The buffer is torch.uint8 whatever the elements are: torch aligns it far beyond an element."""
     torch = _torch()
     with ctx.batch(descs, out_format) as b:
+        if views is not None:
+            b.set_views(views)                      # from here on every per-picture argument is per view; the statuses stay per picture
         if resize is not None:
             b.set_resize(resize)
             if pads is not None:
@@ -125,7 +131,7 @@ def _run(ctx, descs, out_format, capacity, offsets, device, resize=None, normali
         b.decode()
         b.sync()                                    # the library's stream has drained, fallbacks are settled: readable on any stream
         st = b.statuses()
-        offs = [b.output_offset(i) for i in range(b.n)]
+        offs = [b.output_offset(i) for i in range(b.n if views is None else len(views))]
     return buf, offs, st
 
 
@@ -495,6 +501,76 @@ def _plan_letterbox(descs, size, mode, prescale, crops, flips, resize_short, ori
     return (run, (windows if any(w is not None for w in windows) else None), (oris if orientations is not None else None), pads)
 
 
+def tile_views(h, w, th, tw):
+    """An h x w picture cut into a grid of tiles of at most th x tw, edge tiles smaller -> (windows, sizes), row-major (left to right,
+    then top to bottom): windows[k] = {"x", "y", "w", "h"} for Batch.set_resize_window and sizes[k] = (tile_h, tile_w) for
+    Batch.set_resize, ceil(h / th) * ceil(w / tw) of each.  Every target equals its window, so every tap weight of every filter is the
+    identity and the tiles put side by side are the decoded picture byte for byte.  With Batch.set_views([p] * len(sizes)) one picture
+    leaves its one decode as its tiles.  Pure."""
+    h, w, th, tw = int(h), int(w), int(th), int(tw)
+    if h < 1 or w < 1 or th < 1 or tw < 1:
+        raise ValueError("tile_views: sizes must be at least 1")
+    windows, sizes = [], []
+    for y in range(0, h, th):
+        for x in range(0, w, tw):
+            ww, hh = min(tw, w - x), min(th, h - y)
+            windows.append({"x": x, "y": y, "w": ww, "h": hh})
+            sizes.append((hh, ww))
+    return windows, sizes
+
+
+def least_reduced_scale_flags(flags_of_views, draft=False):
+    """The pre-scale of a picture that has several views: the LEAST reduced of the scales its views picked for themselves
+    (pick_scale_flags / pick_libjpeg_scale_flags of each view's window against its target) -- the view with the largest target against
+    its window decides, and no view is resampled up from a picture decoded too small for it.  flags_of_views: the F_SCALE_* values
+    (draft: F_LIBJPEG_SCALE_*) of the views, other bits ignored.  No view at all: 1/8, nothing reads the picture.  Pure."""
+    mask, low = (pjd_amd.F_LIBJPEG_SCALE_MASK, pjd_amd.F_LIBJPEG_SCALE_1_2) if draft else (pjd_amd.F_SCALE_MASK, pjd_amd.F_SCALE_1_2)
+    logs = [(int(f) & mask) // low for f in flags_of_views]
+    return (min(logs) if logs else 3) * low
+
+
+def _views(views, n_pictures):
+    """The `views` keyword, checked before anything is created -> list of ints."""
+    views = [int(p) for p in views]
+    if len(views) == 0:
+        raise ValueError("views: at least one view")
+    for v, p in enumerate(views):
+        if not 0 <= p < n_pictures:
+            raise ValueError(f"views[{v}] = {p}: the batch has {n_pictures} pictures")
+    return views
+
+
+def plan_views(descs, views, size, prescale=True, crops=None, flips=None, resize_short=None, orientations=None, letterbox=None):
+    """What the resizing helpers do with views=: -> (descriptors to decode, one per PICTURE; windows, orientations, pads, one per VIEW or
+    None).  crops, flips, orientations have one entry per view and speak about that view's picture, exactly as they speak about picture i
+    without views.  The pre-scale (prescale true, or "draft" for libjpeg's own) is chosen per PICTURE: each view picks as a picture of
+    its own would, the least reduced of a picture's views wins (least_reduced_scale_flags), and every view's window is then taken at
+    THAT scale (window_at_scale).  Pure: no device, no torch."""
+    views = _views(views, len(descs))
+    vdescs = [descs[p] for p in views]
+
+    def plan(ds, ps):
+        if letterbox is not None:
+            return _plan_letterbox(ds, size, letterbox, ps, crops, flips, resize_short, orientations)
+        return _plan(ds, size, ps, crops, flips, resize_short, orientations) + (None,)
+
+    pics = list(descs)
+    if prescale:
+        import ctypes
+        draft = prescale == "draft"
+        mask = pjd_amd.F_LIBJPEG_SCALE_MASK if draft else pjd_amd.F_SCALE_MASK
+        picked = plan(vdescs, prescale)[0]                 # every view as a picture of its own
+        pics = []
+        for p, d in enumerate(descs):
+            c = pjd_amd.ImageDesc()
+            ctypes.memmove(ctypes.byref(c), ctypes.byref(d), ctypes.sizeof(pjd_amd.ImageDesc))
+            c.flags = (int(d.flags) & ~mask) | least_reduced_scale_flags([picked[v].flags for v in range(len(views)) if views[v] == p], draft)
+            pics.append(c)
+        vdescs = [pics[p] for p in views]
+    _, windows, oris, pads = plan(vdescs, False)           # the windows at the scale the pictures are decoded at
+    return pics, windows, oris, pads
+
+
 def _interpolation(name):
     """The `interpolation` keyword of the resizing helpers, checked before anything is created."""
     if name not in ("bilinear", "bicubic"):
@@ -503,7 +579,8 @@ def _interpolation(name):
 
 
 def decode_resized_batch_tensor(ctx, descs, size, prescale=True, device=None, antialias=False, crops=None, flips=None, resize_short=None,
-                                interpolation="bilinear", orientations=None, libjpeg=False, letterbox=None, fill=(0, 0, 0), gray=False, draft=False):
+                                interpolation="bilinear", orientations=None, libjpeg=False, letterbox=None, fill=(0, 0, 0), gray=False, draft=False,
+                                views=None):
     """Pictures of ANY sizes -> (uint8 tensor [N, 3, H, W], statuses), size = (H, W): every picture is resampled to H x W inside
     the decode (the bilinear filter of include/pjd.h, pjd_batch_set_resize) and lands at offset i * 3 * H * W of one buffer, so
     the result is one contiguous NCHW tensor with no copy after the decode, complete on return and readable on any torch stream
@@ -542,7 +619,12 @@ def decode_resized_batch_tensor(ctx, descs, size, prescale=True, device=None, an
     rectangle, the pre-scale is picked from the content size; resize_short is excluded (ValueError).  None: today's behaviour.
     gray=True: uint8 [N, 1, H, W] (OUT_GRAY8: the luma plane -- with libjpeg=True what libjpeg's JCS_GRAYSCALE delivers -- through the same
     filters: channel 0 of what they make of the picture with neutral chroma); every other keyword composes as without it, and `fill` may
-    be one byte."""
+    be one byte.
+    views=[picture index, ...] of length V (Batch.set_views): the result is [V, C, H, W], view v a resample of picture views[v] -- any
+    order, any number of views of a picture, none included -- and every picture is decoded ONCE.  crops, flips and orientations then have V
+    entries (entry v speaks about picture views[v] as entry i speaks about picture i without views); resize_short and letterbox apply to
+    every view.  The statuses stay per picture.  The pre-scale of a picture is the least reduced of what its views would pick
+    (plan_views).  None: nothing changes."""
     _interpolation(interpolation)
     if len(descs) == 0:
         raise ValueError("decode_resized_batch_tensor: no pictures")
@@ -550,16 +632,19 @@ def decode_resized_batch_tensor(ctx, descs, size, prescale=True, device=None, an
     prescale = "draft" if draft else prescale
     th, tw = int(size[0]), int(size[1])
     fill, pads = _fill(fill, gray), None
-    if letterbox is not None:
+    if views is not None:
+        views = _views(views, len(descs))
+        run, windows, oris, pads = plan_views(descs, views, (th, tw), prescale, crops, flips, resize_short, orientations, letterbox)
+    elif letterbox is not None:
         run, windows, oris, pads = _plan_letterbox(descs, (th, tw), letterbox, prescale, crops, flips, resize_short, orientations)
     else:
         run, windows, oris = _plan(descs, (th, tw), prescale, crops, flips, resize_short, orientations)
     torch = _torch()
     device = torch.device("cuda", ctx.device) if device is None else device
     nc = 1 if gray else 3
-    n, plane = len(descs), nc * th * tw
+    n, plane = (len(descs) if views is None else len(views)), nc * th * tw
     buf, _, st = _run(ctx, run, pjd_amd.OUT_GRAY8 if gray else pjd_amd.OUT_RGB8_PLANAR, n * plane, [i * plane for i in range(n)], device, resize=[(th, tw)] * n,
-                      antialias=antialias, windows=windows, interpolation=interpolation, orientations=oris, pads=pads, fill=fill)
+                      antialias=antialias, windows=windows, interpolation=interpolation, orientations=oris, pads=pads, fill=fill, views=views)
     return buf.view(n, nc, th, tw), st
 
 
@@ -577,7 +662,7 @@ def normalize_constants(mean, std):
 
 def decode_normalized_batch_tensor(ctx, descs, size, mean, std, dtype=None, channels_last=False, prescale=True, device=None,
                                    antialias=False, crops=None, flips=None, resize_short=None, interpolation="bilinear", orientations=None,
-                                   libjpeg=False, letterbox=None, fill=(0, 0, 0), pad_value=None, gray=False, draft=False):
+                                   libjpeg=False, letterbox=None, fill=(0, 0, 0), pad_value=None, gray=False, draft=False, views=None):
     """Pictures of ANY sizes -> (tensor of `dtype` [N, 3, H, W], statuses), size = (H, W); dtype torch.float16 (the default),
     torch.bfloat16 or torch.float32.  As decode_resized_batch_tensor, and every sample v of channel c leaves the same launch as
     fma(v, scale[c], bias[c]) with the constants of normalize_constants(mean, std), converted once to `dtype` (include/pjd.h,
@@ -594,7 +679,9 @@ def decode_normalized_batch_tensor(ctx, descs, size, mean, std, dtype=None, chan
     about the ImageNet mean colour), unless pad_value -- one number or three -- is given: the border elements are then exactly that
     (Batch.set_pad_value; pad_value=0 is "zeros after normalisation": DETR, SAM).  pad_value without letterbox raises ValueError.
     gray=True: [N, 1, H, W] of `dtype` (OUT_GRAY8): fma(v, scale[0], bias[0]) of the luma plane; mean and std may be one number or a
-    sequence of length 1, fill and pad_value one number; it takes channels_last=False (one plane has no interleaved form)."""
+    sequence of length 1, fill and pad_value one number; it takes channels_last=False (one plane has no interleaved form).
+    views: as in decode_resized_batch_tensor -- [V, C, H, W] of `dtype` (channels_last: the permuted view of [V, H, W, 3]), per-view crops,
+    flips and orientations, per-picture statuses, every picture decoded once."""
     _interpolation(interpolation)
     _gray_layout(gray, not channels_last)
     if len(descs) == 0:
@@ -610,7 +697,11 @@ def decode_normalized_batch_tensor(ctx, descs, size, mean, std, dtype=None, chan
     if pad_value is not None and letterbox is None:
         raise ValueError("pad_value needs letterbox: without it there is no border")
     plan = None
-    if letterbox is not None:                              # the new keywords are checked before anything is touched; the others where they were
+    if views is not None:
+        views = _views(views, len(descs))
+        plan = plan_views(descs, views, (th, tw), prescale, crops, flips, resize_short, orientations, letterbox)
+        plan, pads = plan[:3], plan[3]
+    elif letterbox is not None:                            # the new keywords are checked before anything is touched; the others where they were
         plan = _plan_letterbox(descs, (th, tw), letterbox, prescale, crops, flips, resize_short, orientations)
         plan, pads = plan[:3], plan[3]
     torch = _torch()
@@ -622,9 +713,9 @@ def decode_normalized_batch_tensor(ctx, descs, size, mean, std, dtype=None, chan
     device = torch.device("cuda", ctx.device) if device is None else device
     run, windows, oris = plan if plan is not None else _plan(descs, (th, tw), prescale, crops, flips, resize_short, orientations)
     nc = 1 if gray else 3
-    n, pic = len(descs), nc * th * tw * es
+    n, pic = (len(descs) if views is None else len(views)), nc * th * tw * es
     buf, _, st = _run(ctx, run, pjd_amd.OUT_GRAY8 if gray else pjd_amd.OUT_RGB8 if channels_last else pjd_amd.OUT_RGB8_PLANAR, n * pic, [i * pic for i in range(n)], device,
                       resize=[(th, tw)] * n, normalize=(dt, scale, bias), antialias=antialias, windows=windows, interpolation=interpolation,
-                      orientations=oris, pads=pads, fill=fill, pad_value=pad_value)
+                      orientations=oris, pads=pads, fill=fill, pad_value=pad_value, views=views)
     t = buf.view(dtype)
     return (t.view(n, th, tw, 3).permute(0, 3, 1, 2) if channels_last else t.view(n, nc, th, tw)), st
