@@ -1,5 +1,5 @@
 // pjd_k_backend_common.h -- what the back-end units (pjd_k_backend.hip, pjd_k_backend_std.hip, pjd_k_backend_gray.hip) share: the LDS tile row, the
-// LDS block of a lane-stream kernel, the range of decoded units, the grid positions of a range's MCUs, the 1-D IDCT passes over the tile, the wide stores, the BMP header, the wave scans of the DC stage and the tile store of
+// LDS block of a lane-stream kernel, the range of decoded units, the grid positions of a range's MCUs, the walk over a range's luma units, the 1-D IDCT passes over the tile, the wide stores, the BMP header, the wave scans of the DC stage and the tile store of
 // the entry parser.  Each of these stands here once; the kernels differ in which units they walk and where they store.
 #pragma once
 #include "pjd_device_common.h"
@@ -42,6 +42,26 @@ __device__ __forceinline__ void pjd_fill_mcu_xy(uint32_t *mcu_xy, const PjdDevId
         const uint32_t m = wg.first_mcu + tid, my = m / im.mcux;
         mcu_xy[tid] = (my << 16) | (m - my * im.mcux);
     }
+}
+
+// The luma units of a range, counted alone, MCU after MCU: unit j is luma unit j & (nl-1) of the range's MCU j >> nl_log (an MCU holds
+// nl = hs * vs = 1, 2 or 4 of them, row by row, in front of its chroma units).  The figures of the walk, made once in front of the loops:
+struct PjdLumaUnits { uint32_t dus, nl, nl_log; };
+__device__ __forceinline__ PjdLumaUnits pjd_luma_units(uint32_t dus, uint32_t nl)
+{
+    PjdLumaUnits L;
+    L.dus = dus; L.nl = nl; L.nl_log = nl == 4u ? 2u : nl - 1u;
+    return L;
+}
+__device__ __forceinline__ PjdLumaUnits pjd_luma_units(const PjdDevImage &im) { return pjd_luma_units(im.dus_per_mcu, im.n_luma); }
+// luma unit j -> its index among all units of the range
+__device__ __forceinline__ uint32_t pjd_luma_unit(uint32_t j, const PjdLumaUnits L) { return __umul24(j >> L.nl_log, L.dus) + (j & (L.nl - 1u)); }
+// luma unit j -> the position (.x, .y) of its first sample in the luma plane, a unit being m samples a side (8, or 4, 2, 1 behind a
+// reduced IDCT; 1: its position in the grid of units); hs, vs: the picture's; mcu_xy: pjd_fill_mcu_xy's, or the parser's
+__device__ __forceinline__ uint2 pjd_luma_unit_xy(uint32_t j, const PjdLumaUnits L, uint32_t hs, uint32_t vs, const uint32_t *mcu_xy, uint32_t m)
+{
+    const uint32_t ml = j >> L.nl_log, k = j & (L.nl - 1u), xy = mcu_xy[ml];
+    return make_uint2((__umul24(xy & 0xffffu, hs) + (k & (hs - 1u))) * m, (__umul24(xy >> 16, vs) + (k >> (hs - 1u))) * m);
 }
 
 // ---- the 1-D passes of the reference's IDCT on one row / one column of a unit of the tile (reference src/decoder_dpu.c:218-320)

@@ -9,24 +9,20 @@
 //                       store: a lane takes the eight samples of one row of one unit and writes them as one 8-byte store (bytes at the
 //                       ragged right edge).  SCALED: pictures with PJD_F_SCALE_* take the box filter of include/pjd.h on the one plane;
 //                       a box of 2, 4 or 8 pixels a side lies inside one luma unit.
-//   pjd_k_idct_gray_std_lanes / pjd_k_idct_gray_std_dense
-//                       PJD_F_LIBJPEG pictures: jpeg_idct_islow of the luma units (pjd_libjpeg.h) straight into the picture, clipped
-//                       to its width and height.  No component planes, no chroma, no colour launch.
-// Kernels of their own, as the planar and the scaled back ends are: the existing ones keep their code and registers.  Of their own is
-// the walk over the luma units (pjd_gray_unit), the stores and pjd_gray_dc; the parser, the dense staging, the IDCT passes and the islow
-// passes are the texts the other units use (pjd_k_backend_common.h, pjd_k_dense_stage_body.h, pjd_libjpeg_passes.h).  No launcher
-// here: those of pjd_k_backend.hip and pjd_k_backend_std.hip take the kernels from the two accessors at the end.
+//   pjd_k_idct_gray_std_lanes[_red] / pjd_k_idct_gray_std_dense[_red]
+//                       PJD_F_LIBJPEG pictures: jpeg_idct_islow of the luma units (pjd_libjpeg.h) -- _red: libjpeg's reduced IDCT, for the
+//                       pictures with PJD_F_LIBJPEG_SCALE_* -- straight into the picture, clipped to its width and height.  No component
+//                       planes, no chroma, no colour launch.  A kernel and its _red twin share their front end: pjd_gray_std_lanes<RED>,
+//                       and pjd_k_libjpeg_dense_body.h with PJD_LJ_LUMA_ONLY (the text of pjd_k_backend_std.hip's dense kernels too).
+// Kernels of their own, as the planar and the scaled back ends are.  Of their own are the stores and pjd_gray_dc; the walk over the luma
+// units (PjdLumaUnits), the parser, the dense staging, the IDCT passes and the islow passes are the texts the other units use
+// (pjd_k_backend_common.h, pjd_k_dense_stage_body.h, pjd_libjpeg_passes.h).  No launcher here: those of pjd_k_backend.hip and
+// pjd_k_backend_std.hip take the kernels from the two accessors at the end.
 #include "pjd_libjpeg_passes.h"
 
 namespace {
 
 struct __attribute__((packed)) PjdPx8 { uint32_t a, b; };
-
-// luma unit j of a range (j counts the luma units alone, MCU after MCU) -> its index among all units of the range
-__device__ __forceinline__ uint32_t pjd_gray_unit(uint32_t j, uint32_t nl_log, uint32_t nl, uint32_t dus)
-{
-    return __umul24(j >> nl_log, dus) + (j & (nl - 1u));
-}
 
 // eight int16 luma samples (four dwords) -> eight bytes clamp255(y + 128): the int16 sum saturates only outside [0, 255]
 __device__ __forceinline__ uint2 pjd_gray_bytes(const uint4 w)
@@ -92,17 +88,15 @@ __device__ __forceinline__ void pjd_gray_store_scaled(const int16_t (*tile)[TILE
 {
     constexpr uint32_t S_LOG = S == 2 ? 1 : (S == 4 ? 2 : 3), BR_LOG = 3 - S_LOG;
     constexpr int NO = 8 / S;
-    const uint32_t width = im.width, height = im.height, stride = im.out_stride, hs = im.hs, vs = im.vs, dus = im.dus_per_mcu, nl = im.n_luma;
-    const uint32_t nl_log = nl == 4u ? 2u : nl - 1u;
-    const uint32_t tasks = (n_mcu * nl) << BR_LOG;
+    const uint32_t width = im.width, height = im.height, stride = im.out_stride, hs = im.hs, vs = im.vs;
+    const PjdLumaUnits L = pjd_luma_units(im);
+    const uint32_t tasks = (n_mcu * L.nl) << BR_LOG;
     for (uint32_t t = tid; t < tasks; t += PJD_IDCT_THREADS) {
         const uint32_t j = t >> BR_LOG, br = t & ((1u << BR_LOG) - 1u);
-        const uint32_t ml = j >> nl_log, k = j & (nl - 1u);
-        const uint32_t xy = mcu_xy[ml];
-        const uint32_t X = (__umul24(xy & 0xffffu, hs) + (k & (hs - 1u))) * 8u;
-        const uint32_t Yb = (__umul24(xy >> 16, vs) + (k >> (hs - 1u))) * 8u + br * S;
+        const uint2 at = pjd_luma_unit_xy(j, L, hs, vs, mcu_xy, 8u);
+        const uint32_t X = at.x, Yb = at.y + br * S;
         if (X >= width || Yb >= height) continue;
-        const uint32_t u = __umul24(ml, dus) + k;
+        const uint32_t u = pjd_luma_unit(j, L);
         const uint32_t bh = height - Yb < S ? height - Yb : S;
         uint32_t sum[NO];
 #pragma unroll
@@ -185,13 +179,14 @@ __device__ __forceinline__ void pjd_gray_range(const PjdDevBatch &B, uint32_t iw
 #define PJD_LANES_LUMA_ONLY
 #include "pjd_k_lanes_parse_body.h"
 #undef PJD_LANES_LUMA_ONLY
-    const uint32_t nl_log = nl == 4u ? 2u : nl - 1u, n_lu = wg.n_mcu * nl;
+    const PjdLumaUnits L = pjd_luma_units(dus, nl);
+    const uint32_t n_lu = wg.n_mcu * nl;
     // DC prediction by wave 0, while the other waves do the row pass of rows 1..7 (only row 0 holds the DC coefficient) and the slot-52
     // rule (natural 38 lies in row 4) -- of the luma units alone
     if (wv != 0) {
         for (uint32_t i = tid - 64; i < n_lu * 7; i += PJD_IDCT_THREADS - 64) {
             const uint32_t j = pjd_div_small(i, c_recip16[7]), r = 1 + (i - __umul24(j, 7u));   // i < 7 * PJD_IDCT_MAX_DU: exact
-            const uint32_t u = pjd_gray_unit(j, nl_log, nl, dus);
+            const uint32_t u = pjd_luma_unit(j, L);
             if (r == 4 && tile[u][64] != (int16_t)PJD_COEF_SENTINEL) tile[u][38] = (int16_t)pjd_dequant((int)tile[u][64], qz[0][48] & 0xffffu);
             pjd_tile_row(tile, u, r);
         }
@@ -199,9 +194,9 @@ __device__ __forceinline__ void pjd_gray_range(const PjdDevBatch &B, uint32_t iw
         pjd_gray_dc(tile, qz, comp_of, du_head, pred0[0], n_du, n_valid, lane);
     }
     __syncthreads();
-    for (uint32_t j = tid; j < n_lu; j += PJD_IDCT_THREADS) pjd_tile_row(tile, pjd_gray_unit(j, nl_log, nl, dus), 0);
+    for (uint32_t j = tid; j < n_lu; j += PJD_IDCT_THREADS) pjd_tile_row(tile, pjd_luma_unit(j, L), 0);
     __syncthreads();
-    for (uint32_t i = tid; i < n_lu * 8; i += PJD_IDCT_THREADS) pjd_tile_col(tile, pjd_gray_unit(i >> 3, nl_log, nl, dus), i & 7);
+    for (uint32_t i = tid; i < n_lu * 8; i += PJD_IDCT_THREADS) pjd_tile_col(tile, pjd_luma_unit(i >> 3, L), i & 7);
     __syncthreads();
     pjd_gray_dispatch<SCALED>(tile, mcu_xy, B, im, wg.n_mcu, tid);
 }
@@ -211,11 +206,11 @@ __device__ __forceinline__ void pjd_gray_range(const PjdDevBatch &B, uint32_t iw
 __device__ __forceinline__ void pjd_gray_std_idct(const int16_t (*tile)[TILE_STRIDE], uint32_t (*ws)[WS_STRIDE], const uint16_t *q, const uint32_t *mcu_xy,
                                                   const PjdDevBatch &B, const PjdDevImage &im, uint32_t n_mcu, uint32_t tid)
 {
-    const uint32_t dus = im.dus_per_mcu, nl = im.n_luma, hs = im.hs, vs = im.vs;
-    const uint32_t nl_log = nl == 4u ? 2u : nl - 1u, n_lu = n_mcu * nl;
+    const PjdLumaUnits L = pjd_luma_units(im);
+    const uint32_t hs = im.hs, vs = im.vs, n_lu = n_mcu * L.nl;
     // pass 1: a thread takes one column of one unit
     for (uint32_t i = tid; i < n_lu * 8; i += PJD_IDCT_THREADS) {
-        const uint32_t u = pjd_gray_unit(i >> 3, nl_log, nl, dus), c = i & 7;
+        const uint32_t u = pjd_luma_unit(i >> 3, L), c = i & 7;
         PJD_LJ_PASS1_COL(tile, ws, u, q, c);
     }
     __syncthreads();
@@ -223,10 +218,9 @@ __device__ __forceinline__ void pjd_gray_std_idct(const int16_t (*tile)[TILE_STR
     const uint32_t width = im.width, height = im.height, stride = im.out_stride;
     uint8_t *out = B.out + im.out_off;
     for (uint32_t i = tid; i < n_lu * 8; i += PJD_IDCT_THREADS) {
-        const uint32_t j = i >> 3, r = i & 7;
-        const uint32_t ml = j >> nl_log, k = j & (nl - 1u), u = __umul24(ml, dus) + k;
-        const uint32_t xy = mcu_xy[ml];
-        const uint32_t X = (__umul24(xy & 0xffffu, hs) + (k & (hs - 1u))) * 8u, Y = (__umul24(xy >> 16, vs) + (k >> (hs - 1u))) * 8u + r;
+        const uint32_t j = i >> 3, r = i & 7, u = pjd_luma_unit(j, L);
+        const uint2 at = pjd_luma_unit_xy(j, L, hs, vs, mcu_xy, 8u);
+        const uint32_t X = at.x, Y = at.y + r;
         if (X >= width || Y >= height) continue;
         const uint2 px = pjd_lj_pass2_row(ws, u, r);
         pjd_gray_store8(out + (size_t)Y * stride + X, px, X, width);
@@ -264,8 +258,8 @@ __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_gray(PjdDevBatch 
     const PjdDevIdctWg wg = wgs[blockIdx.x];
     const PjdDevImage &im = B.images[wg.image];
     const uint32_t tid = threadIdx.x;
-    const uint32_t dus = im.dus_per_mcu, nl = im.n_luma;
-    const uint32_t nl_log = nl == 4u ? 2u : nl - 1u, n_lu = wg.n_mcu * nl;
+    const PjdLumaUnits L = pjd_luma_units(im);
+    const uint32_t dus = L.dus, n_lu = wg.n_mcu * L.nl;
 
     if (tid < 64) qs[tid] = B.qtab[(size_t)wg.image * 192 + tid];
     pjd_fill_mcu_xy(mcu_xy, wg, im, tid);
@@ -274,73 +268,25 @@ __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_gray(PjdDevBatch 
     // load (16 B per lane), de-zigzag, dequantise: lane (unit, r) owns zigzag slots 8r..8r+7
     const int16_t *cbase = B.coef + (dense_base[wg.pad_] + (uint64_t)(wg.first_mcu - im.first_mcu) * dus) * 64;
     for (uint32_t i = tid; i < n_lu * 8; i += PJD_IDCT_THREADS) {
-        const uint32_t du = pjd_gray_unit(i >> 3, nl_log, nl, dus), r = i & 7;
+        const uint32_t du = pjd_luma_unit(i >> 3, L), r = i & 7;
         const int4 raw = *reinterpret_cast<const int4 *>(cbase + (size_t)du * 64 + r * 8);
 #define PJD_DENSE_Q qs
 #include "pjd_k_dense_stage_body.h"
 #undef PJD_DENSE_Q
     }
     __syncthreads();
-    for (uint32_t i = tid; i < n_lu * 8; i += PJD_IDCT_THREADS) pjd_tile_row(tile, pjd_gray_unit(i >> 3, nl_log, nl, dus), i & 7);
+    for (uint32_t i = tid; i < n_lu * 8; i += PJD_IDCT_THREADS) pjd_tile_row(tile, pjd_luma_unit(i >> 3, L), i & 7);
     __syncthreads();
-    for (uint32_t i = tid; i < n_lu * 8; i += PJD_IDCT_THREADS) pjd_tile_col(tile, pjd_gray_unit(i >> 3, nl_log, nl, dus), i & 7);
+    for (uint32_t i = tid; i < n_lu * 8; i += PJD_IDCT_THREADS) pjd_tile_col(tile, pjd_luma_unit(i >> 3, L), i & 7);
     __syncthreads();
     pjd_gray_dispatch<SCALED>(tile, mcu_xy, B, im, wg.n_mcu, tid);
 }
 
 // ---------------------------------------------------------------------------------------------
-// PJD_F_LIBJPEG pictures of a grey batch, from the lane streams and from the dense scratch.
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_gray_std_lanes(PjdDevBatch B, const uint32_t *__restrict__ order)
-{
-    PJD_LANES_LDS_TILE
-    __shared__ __attribute__((aligned(16))) uint32_t ws[PJD_IDCT_MAX_DU][WS_STRIDE];
-    __shared__ uint16_t qn[64];               // the luma quantiser by natural position
-    PJD_LANES_LDS_TABLES                      // qz here: 1 | natural position << 16 (the parser stores what was decoded)
-
-    const uint32_t iwg = order[blockIdx.x];
-    if (threadIdx.x < 64) qn[threadIdx.x] = B.qtab[(size_t)B.iwgs[iwg].image * 192 + threadIdx.x];
-#define PJD_LANES_RAW
-#define PJD_LANES_LUMA_ONLY
-#include "pjd_k_lanes_parse_body.h"
-#undef PJD_LANES_LUMA_ONLY
-#undef PJD_LANES_RAW
-    if (wv == 0) pjd_gray_dc(tile, qz, comp_of, du_head, pred0[0], n_du, n_valid, lane);
-    __syncthreads();
-    pjd_gray_std_idct(tile, ws, qn, mcu_xy, B, im, wg.n_mcu, tid);
-}
-
-__global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_gray_std_dense(PjdDevBatch B, const PjdDevIdctWg *__restrict__ wgs, const uint64_t *__restrict__ dense_base)
-{
-    __shared__ __attribute__((aligned(16))) int16_t tile[PJD_IDCT_MAX_DU][TILE_STRIDE];
-    __shared__ __attribute__((aligned(16))) uint32_t ws[PJD_IDCT_MAX_DU][WS_STRIDE];
-    __shared__ uint16_t qn[64];
-    __shared__ uint32_t mcu_xy[PJD_IDCT_MAX_DU];
-
-    const PjdDevIdctWg wg = wgs[blockIdx.x];
-    const PjdDevImage &im = B.images[wg.image];
-    const uint32_t tid = threadIdx.x;
-    const uint32_t dus = im.dus_per_mcu, nl = im.n_luma;
-    const uint32_t nl_log = nl == 4u ? 2u : nl - 1u, n_lu = wg.n_mcu * nl;
-    if (tid < 64) qn[tid] = B.qtab[(size_t)wg.image * 192 + tid];
-    pjd_fill_mcu_xy(mcu_xy, wg, im, tid);
-    const int16_t *cbase = B.coef + (dense_base[wg.pad_] + (uint64_t)(wg.first_mcu - im.first_mcu) * dus) * 64;
-    const bool sentinel = !(im.flags & PJD_IF_PROGRESSIVE);
-    for (uint32_t i = tid; i < n_lu * 8; i += PJD_IDCT_THREADS) {
-        const uint32_t du = pjd_gray_unit(i >> 3, nl_log, nl, dus), r = i & 7;
-        const int4 raw = *reinterpret_cast<const int4 *>(cbase + (size_t)du * 64 + r * 8);
-#define PJD_DENSE_RAW
-#include "pjd_k_dense_stage_body.h"
-#undef PJD_DENSE_RAW
-    }
-    __syncthreads();
-    pjd_gray_std_idct(tile, ws, qn, mcu_xy, B, im, wg.n_mcu, tid);
-}
-
-// ---------------------------------------------------------------------------------------------
-// PJD_F_LIBJPEG_SCALE_* pictures of a grey batch: the luma units through libjpeg's reduced IDCT of M = 4, 2 or 1 samples a side
-// (PjdLjRed<M>, pjd_libjpeg.h), straight into the picture, clipped at its reduced width and height.  Kernels of their own: the two above
-// keep their text.  M is the picture's, uniform over the workgroup.
+// PJD_F_LIBJPEG pictures of a grey batch, from the lane streams and from the dense scratch.  RED: the pictures with PJD_F_LIBJPEG_SCALE_*,
+// whose luma units go through libjpeg's reduced IDCT of M = 4, 2 or 1 samples a side (PjdLjRed<M>, pjd_libjpeg.h), straight into the
+// picture, clipped at its reduced width and height; M is the picture's, uniform over the workgroup.  Each front end is one text, the
+// body of its two kernels, which differ in the passes behind it.
 // ---------------------------------------------------------------------------------------------
 namespace {
 
@@ -351,13 +297,13 @@ __device__ __forceinline__ void pjd_gray_red_idct(const int16_t (*tile)[TILE_STR
                                                   const PjdDevBatch &B, const PjdDevImage &im, uint32_t n_mcu, uint32_t tid)
 {
     constexpr uint32_t M_LOG = M == 4 ? 2 : (M == 2 ? 1 : 0), COLS = M == 4 ? 7 : 5;
-    const uint32_t dus = im.dus_per_mcu, nl = im.n_luma, hs = im.hs, vs = im.vs;
-    const uint32_t nl_log = nl == 4u ? 2u : nl - 1u, n_lu = n_mcu * nl;
+    const PjdLumaUnits L = pjd_luma_units(im);
+    const uint32_t hs = im.hs, vs = im.vs, n_lu = n_mcu * L.nl;
     if (M > 1) {
         // pass 1: a thread takes one of the columns the transform reads of one unit
         for (uint32_t i = tid; i < n_lu * COLS; i += PJD_IDCT_THREADS) {
             const uint32_t j = pjd_div_small(i, c_recip16[COLS]), k = i - j * COLS;     // i < 7 * PJD_IDCT_MAX_DU: exact
-            pjd_lj_red_pass1_col<(M == 2 ? 2 : 4)>(tile, ws, pjd_gray_unit(j, nl_log, nl, dus), q, k);
+            pjd_lj_red_pass1_col<(M == 2 ? 2 : 4)>(tile, ws, pjd_luma_unit(j, L), q, k);
         }
         __syncthreads();
     }
@@ -365,10 +311,9 @@ __device__ __forceinline__ void pjd_gray_red_idct(const int16_t (*tile)[TILE_STR
     const uint32_t width = (im.width + 8u / M - 1u) >> (3u - M_LOG), height = (im.height + 8u / M - 1u) >> (3u - M_LOG), stride = im.out_stride;
     uint8_t *out = B.out + im.out_off;
     for (uint32_t i = tid; i < (n_lu << M_LOG); i += PJD_IDCT_THREADS) {
-        const uint32_t j = i >> M_LOG, r = i & (M - 1u);
-        const uint32_t ml = j >> nl_log, k = j & (nl - 1u), u = __umul24(ml, dus) + k;
-        const uint32_t xy = mcu_xy[ml];
-        const uint32_t X = (__umul24(xy & 0xffffu, hs) + (k & (hs - 1u))) * M, Y = (__umul24(xy >> 16, vs) + (k >> (hs - 1u))) * M + r;
+        const uint32_t j = i >> M_LOG, r = i & (M - 1u), u = pjd_luma_unit(j, L);
+        const uint2 at = pjd_luma_unit_xy(j, L, hs, vs, mcu_xy, M);
+        const uint32_t X = at.x, Y = at.y + r;
         if (X >= width || Y >= height) continue;
         uint8_t *o = out + (size_t)Y * stride + X;
         if (M == 1) { *o = (uint8_t)pjd_lj_sample_1x1(pjd_lj_dequant((int)tile[u][0], q[0])); continue; }
@@ -394,14 +339,13 @@ __device__ __forceinline__ void pjd_gray_red_dispatch(const int16_t (*tile)[TILE
     }
 }
 
-}  // namespace
-
-__global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_gray_std_lanes_red(PjdDevBatch B, const uint32_t *__restrict__ order)
+template <bool RED>
+__device__ __forceinline__ void pjd_gray_std_lanes(const PjdDevBatch &B, const uint32_t *order)
 {
     PJD_LANES_LDS_TILE
     __shared__ __attribute__((aligned(16))) uint32_t ws[PJD_IDCT_MAX_DU][WS_STRIDE];
-    __shared__ uint16_t qn[64];
-    PJD_LANES_LDS_TABLES
+    __shared__ uint16_t qn[64];               // the luma quantiser by natural position
+    PJD_LANES_LDS_TABLES                      // qz here: 1 | natural position << 16 (the parser stores what was decoded)
 
     const uint32_t iwg = order[blockIdx.x];
     if (threadIdx.x < 64) qn[threadIdx.x] = B.qtab[(size_t)B.iwgs[iwg].image * 192 + threadIdx.x];
@@ -412,33 +356,35 @@ __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_gray_std_lanes_re
 #undef PJD_LANES_RAW
     if (wv == 0) pjd_gray_dc(tile, qz, comp_of, du_head, pred0[0], n_du, n_valid, lane);
     __syncthreads();
-    pjd_gray_red_dispatch(tile, ws, qn, mcu_xy, B, im, wg.n_mcu, tid);
+    if (RED) pjd_gray_red_dispatch(tile, ws, qn, mcu_xy, B, im, wg.n_mcu, tid);
+    else pjd_gray_std_idct(tile, ws, qn, mcu_xy, B, im, wg.n_mcu, tid);
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_gray_std_lanes(PjdDevBatch B, const uint32_t *__restrict__ order)
+{
+    pjd_gray_std_lanes<false>(B, order);
+}
+
+__global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_gray_std_lanes_red(PjdDevBatch B, const uint32_t *__restrict__ order)
+{
+    pjd_gray_std_lanes<true>(B, order);
+}
+
+__global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_gray_std_dense(PjdDevBatch B, const PjdDevIdctWg *__restrict__ wgs, const uint64_t *__restrict__ dense_base)
+{
+#define PJD_LJ_LUMA_ONLY
+#include "pjd_k_libjpeg_dense_body.h"
+#undef PJD_LJ_LUMA_ONLY
+    pjd_gray_std_idct(tile, ws, qn, mcu_xy, B, im, wg.n_mcu, tid);
 }
 
 __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_gray_std_dense_red(PjdDevBatch B, const PjdDevIdctWg *__restrict__ wgs, const uint64_t *__restrict__ dense_base)
 {
-    __shared__ __attribute__((aligned(16))) int16_t tile[PJD_IDCT_MAX_DU][TILE_STRIDE];
-    __shared__ __attribute__((aligned(16))) uint32_t ws[PJD_IDCT_MAX_DU][WS_STRIDE];
-    __shared__ uint16_t qn[64];
-    __shared__ uint32_t mcu_xy[PJD_IDCT_MAX_DU];
-
-    const PjdDevIdctWg wg = wgs[blockIdx.x];
-    const PjdDevImage &im = B.images[wg.image];
-    const uint32_t tid = threadIdx.x;
-    const uint32_t dus = im.dus_per_mcu, nl = im.n_luma;
-    const uint32_t nl_log = nl == 4u ? 2u : nl - 1u, n_lu = wg.n_mcu * nl;
-    if (tid < 64) qn[tid] = B.qtab[(size_t)wg.image * 192 + tid];
-    pjd_fill_mcu_xy(mcu_xy, wg, im, tid);
-    const int16_t *cbase = B.coef + (dense_base[wg.pad_] + (uint64_t)(wg.first_mcu - im.first_mcu) * dus) * 64;
-    const bool sentinel = !(im.flags & PJD_IF_PROGRESSIVE);
-    for (uint32_t i = tid; i < n_lu * 8; i += PJD_IDCT_THREADS) {
-        const uint32_t du = pjd_gray_unit(i >> 3, nl_log, nl, dus), r = i & 7;
-        const int4 raw = *reinterpret_cast<const int4 *>(cbase + (size_t)du * 64 + r * 8);
-#define PJD_DENSE_RAW
-#include "pjd_k_dense_stage_body.h"
-#undef PJD_DENSE_RAW
-    }
-    __syncthreads();
+#define PJD_LJ_LUMA_ONLY
+#include "pjd_k_libjpeg_dense_body.h"
+#undef PJD_LJ_LUMA_ONLY
     pjd_gray_red_dispatch(tile, ws, qn, mcu_xy, B, im, wg.n_mcu, tid);
 }
 

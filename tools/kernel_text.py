@@ -8,10 +8,13 @@ Kernels are matched by SYMBOL, whichever unit holds them, so a kernel that moved
 text runs from its label to .Lfunc_end, descriptor (.amdhsa_kernel: registers, LDS, scratch) included; comments are stripped, and the
 function's index within its unit (.LBB<n>_, .Lfunc_end<n>) is dropped, since it changes with the kernel's position and nothing else.
 For a kernel that differs the figures a reviewer asks for are printed for both sides: VGPRs, SGPRs, occupancy, scratch, vector loads,
-vector stores, LDS instructions, all instructions.  Units that hold no kernel named by --moved (default: the resize kernels) must be
-equal as whole files but for their __hip_cuid lines.  Exit status 1 where such a unit differs, or a kernel that --may-differ does not name.
+vector stores, LDS instructions, all instructions, LDS bytes -- and whether registers, occupancy, scratch, LDS bytes and the multiset of
+instruction mnemonics are equal: a kernel that --may-differ names may differ in its text alone, not in any of these.  Units that hold
+no kernel named by --moved (default: the resize kernels) must be equal as whole files but for their __hip_cuid lines.  Exit status 1
+where such a unit differs, or a kernel that --may-differ does not name, or one that it names and that lost one of those equalities.
 """
 import argparse
+import collections
 import os
 import re
 import subprocess
@@ -20,6 +23,8 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "pim-jpeg-decoder_amd", "csrc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "--cuda-device-only", "-S"]
+# what a kernel that --may-differ names must keep: its registers, occupancy, scratch, LDS bytes and the multiset of its mnemonics
+SAME_FIGURES = ("NumVgprs", "TotalNumSgprs", "Occupancy", "ScratchSize", "lds_bytes", "mnemonics")
 
 
 def dump(out_dir):
@@ -54,7 +59,9 @@ def kernels(path):
         fig = {"insts": len(code),
                "vload": sum(c.startswith(("global_load", "buffer_load", "flat_load")) for c in code),
                "vstore": sum(c.startswith(("global_store", "buffer_store", "flat_store")) for c in code),
-               "lds": sum(c.startswith("ds_") for c in code)}
+               "lds": sum(c.startswith("ds_") for c in code),
+               "mnemonics": collections.Counter(code),
+               "lds_bytes": next(int(c.split()[1]) for c in text if c.lstrip().startswith(".amdhsa_group_segment_fixed_size"))}
         for l in lines[end:end + 60]:
             m = re.match(r"; (NumVgprs|TotalNumSgprs|ScratchSize|Occupancy): (\d+)", l)
             if m and m.group(1) not in fig:
@@ -89,8 +96,10 @@ def compare(old_dir, new_dir, moved, may_differ):
             for side, k in (("old", old[sym]), ("new", new[sym])):
                 f = k[1]
                 print(f"    {side}: vgpr {f['NumVgprs']} sgpr {f['TotalNumSgprs']} occupancy {f['Occupancy']} scratch {f['ScratchSize']} "
-                      f"vload {f['vload']} vstore {f['vstore']} lds {f['lds']} insts {f['insts']}")
-            bad += not (may_differ and re.search(may_differ, sym))
+                      f"vload {f['vload']} vstore {f['vstore']} lds {f['lds']} insts {f['insts']} lds bytes {f['lds_bytes']}")
+            same = {k: old[sym][1][k] == new[sym][1][k] for k in SAME_FIGURES}
+            print("    " + ", ".join(f"{k} {'equal' if v else 'NOT EQUAL'}" for k, v in same.items()))
+            bad += not (may_differ and re.search(may_differ, sym) and all(same.values()))
     for f in sorted(set(old_units) | set(new_units)):
         a, b = old_units.get(f), new_units.get(f)
         if any(re.search(moved, s) for u in (a, b) if u for s in u[0]):
@@ -111,6 +120,6 @@ if __name__ == "__main__":
     c.add_argument("old")
     c.add_argument("new")
     c.add_argument("--moved", default="pjd_k_resize", help="regex: kernels that changed units; the units that hold them are not compared whole")
-    c.add_argument("--may-differ", default="", help="regex: kernels whose difference is reported with its figures and does not fail the run")
+    c.add_argument("--may-differ", default="", help="regex: kernels whose text may differ where registers, occupancy, scratch, LDS bytes and mnemonics are equal")
     a = ap.parse_args()
     sys.exit(dump(a.dir) if a.cmd == "dump" else compare(a.old, a.new, a.moved, a.may_differ))
