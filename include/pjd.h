@@ -962,7 +962,7 @@ int  pjd_plan_step_bits(const pjd_image_desc *image, uint32_t *step_bits_x256);
 int  pjd_plan_luts(const pjd_image_desc *image, void *blob, uint64_t cap, uint32_t *real_bytes, uint32_t *nominal_bytes, uint8_t *slots);
 /* Debug: what the runtime answers for the entropy decoder's launch of this batch on its device
  * (hipOccupancyMaxActiveBlocksPerMultiprocessor): workgroups of pjd_k_huff_lanes one CU holds at the batch's dynamic LDS, and that
- * size (`lds_bytes`, may be NULL: pjd_batch_info.huff_lds_bytes plus PJD_EXTRA_LDS of the environment).  Also printed by
+ * size (`lds_bytes`, may be NULL: pjd_batch_info.huff_lds_bytes).  Also printed by
  * pjd_batch_get_info under PJD_DEBUG_STATS.                                                                                       */
 int  pjd_batch_huff_occupancy(pjd_batch *batch, int32_t *workgroups_per_cu, uint32_t *lds_bytes);
 

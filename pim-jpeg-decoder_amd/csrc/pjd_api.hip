@@ -335,6 +335,19 @@ void set_result_offsets(pjd_batch *b, const std::vector<uint64_t> &off)
     for (size_t i = 0; i < off.size(); i++) b->spec.pic[i].dst_off = recs[i].dst_off = off[i];
 }
 
+// the environment's plan mode and subsequence size, as pjd_open and pjd_plan_info both read them
+int env_plan_mode()
+{
+    const char *pm = std::getenv("PJD_PLAN_MODE");
+    return pm && (pm[0] == 't' || pm[0] == '1') ? PJD_PLAN_THROUGHPUT : PJD_PLAN_LATENCY;
+}
+
+uint32_t env_sub_bytes()
+{
+    const char *sb = std::getenv("PJD_SUB_BYTES");
+    return sb ? (uint32_t)std::atoi(sb) : 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -360,14 +373,13 @@ int pjd_open(int device_ordinal, pjd_ctx **out)
     c->force_sequential = fs && fs[0] == '1';
     const char *pg = std::getenv("PJD_POOL_GB");
     if (pg) c->pool_cap = (size_t)std::atoll(pg) << 30;
-    const char *sb = std::getenv("PJD_SUB_BYTES");
-    c->sub_bytes_override = sb ? (uint32_t)std::atoi(sb) : 0;
+    c->sub_bytes_override = env_sub_bytes();
     if (const char *po = std::getenv("PJD_DEBUG_POISON")) {                  // a byte, decimal or 0x..; anything else leaves the switch off
         char *end = nullptr;
         const long v = std::strtol(po, &end, 0);
         if (end != po && *end == 0 && v >= 0 && v <= 255) c->poison = (int)v;
     }
-    if (const char *pm = std::getenv("PJD_PLAN_MODE")) c->plan_mode = (pm[0] == 't' || pm[0] == '1') ? PJD_PLAN_THROUGHPUT : PJD_PLAN_LATENCY;
+    c->plan_mode = env_plan_mode();
     { std::lock_guard<std::mutex> l(g_ctx_m); g_ctxs.push_back(c); }
     *out = c;
     return PJD_OK;
@@ -546,14 +558,10 @@ int pjd_batch_create(pjd_ctx *ctx, const pjd_image_desc *images, int n_images, i
     TRY_RC(dev_alloc(ctx, b->dev.status, (size_t)n_images, tot));
     TRY_RC(dev_alloc(ctx, b->dev.imstate, (size_t)n_images, tot));
     // wave_gen [PJD_GENS][n_hwave], wave_desc [n_hwave] and the ticket live in one allocation, zeroed before every launch
-    // ... a ticket per picture group, and the pull back end's list, tail and done flags (pjd_internal.h)
-    const size_t op_words = n_hwave * (PJD_GENS + 1) + 2 + PJD_MAX_GROUPS, pull_words = P.iwgs.size() + 2;      // 64-bit words: 2 x n_iwg + 2 dwords
-    TRY_RC(dev_alloc(ctx, b->d_opstate, op_words + pull_words, tot));
-    b->opstate_bytes = (op_words + pull_words) * sizeof(uint64_t);
-    b->dev.ready_tail = reinterpret_cast<uint32_t *>(b->d_opstate + op_words);
-    b->dev.ready_list = b->dev.ready_tail + 2;
-    b->dev.range_done = b->dev.ready_list + P.iwgs.size();
-    b->dev.pull = 0;
+    // ... and a ticket per picture group
+    const size_t op_words = n_hwave * (PJD_GENS + 1) + 2 + PJD_MAX_GROUPS;      // 64-bit words
+    TRY_RC(dev_alloc(ctx, b->d_opstate, op_words, tot));
+    b->opstate_bytes = op_words * sizeof(uint64_t);
     b->dev.wave_gen = b->d_opstate;
     b->dev.wave_desc = b->d_opstate + n_hwave * PJD_GENS;
     b->dev.ticket = reinterpret_cast<uint32_t *>(b->d_opstate + n_hwave * (PJD_GENS + 1));
@@ -702,34 +710,14 @@ int enqueue_decode(pjd_batch *b, pjd_timings *timings, bool use_groups)
                      b->dev.dbg ? (uint32_t)(P.hwaves.size() * 32) : 0u);
     kt.mark("reset");
     // What a decode looks like on an otherwise idle device (use_groups), for a batch of many small pictures (the planner made groups):
-    //   "groups" (default) three chains of launches (pictures by density) on three streams
-    //   "pull"   the back end runs BESIDE the entropy decoder and takes pictures as their last wave completes them (pjd_internal.h).
-    //            Bit-exact and complete (the GPU suite passes in this form), but SLOWER: the back end's waves share SIMDs with the
-    //            entropy decoder's chains and stretch them -- 3.4-3.5 ms per batch against 2.6-2.7 for "groups" and 2.9 for "chain"
-    //            (profiles/r04_experiments.md #16); kept as an experiment switch
+    //   "groups" (default; any other word too) three chains of launches (pictures by density) on three streams
     //   "chain"  as with several batches in flight: one chain of launches
-    // A batch that holds pictures with an output scale (PJD_F_SCALE_*), and a planar batch (PJD_OUT_RGB8_PLANAR), take "groups" instead of
-    // "pull": the pull launch has no scaled and no planar form.
-    static const int idle_form = [] { const char *e = std::getenv("PJD_IDLE_FORM"); return !e ? 1 : (!std::strcmp(e, "pull") ? 2 : (!std::strcmp(e, "chain") ? 0 : 1)); }();
-    const bool idle = !timings && use_groups && parallel && !P.groups.empty() && idle_form != 0;       // per-kernel timing: one chain, kernel after kernel
+    static const bool idle_groups = [] { const char *e = std::getenv("PJD_IDLE_FORM"); return !e || std::strcmp(e, "chain") != 0; }();
+    const bool idle = !timings && use_groups && parallel && !P.groups.empty() && idle_groups;       // per-kernel timing: one chain, kernel after kernel
     const PjdBackForm F = b->back;
-    const bool no_pull = !F.has_pull();
-    const size_t ng = (idle && (idle_form == 1 || no_pull)) ? P.groups.size() : 0;
+    const size_t ng = idle ? P.groups.size() : 0;
     const bool grouped = ng > 1 && ctx_group_streams(ctx, ng);
-    if (idle && idle_form == 2 && !no_pull && ctx_group_streams(ctx, 2)) {
-        // The pull back end (pjd_internal.h): entropy decode on the context's stream, the back end's pull launch on a second stream
-        // beside it (inside a capture: two parallel one-node branches), then the sweep over whatever the pull launch left.
-        PjdDevBatch dv = b->dev;
-        dv.pull = 1;
-        HIP_TRY(ctx, hipEventRecord(ctx->fork_ev, s));
-        pjd_launch_huff_lanes(s, dv);
-        hipStream_t s1 = ctx->group_streams[0];
-        HIP_TRY(ctx, hipStreamWaitEvent(s1, ctx->fork_ev, 0));
-        pjd_launch_idct_pull(s1, dv);
-        HIP_TRY(ctx, hipEventRecord(ctx->join_ev[0], s1));
-        HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->join_ev[0], 0));
-        pjd_launch_idct_sweep(s, dv);
-    } else if (grouped) {
+    if (grouped) {
         // Picture groups (pjd_internal.h): every group's chain entropy decode -> DC predictors -> back end on a stream of its own,
         // forked from and joined to the context's stream with events (inside a stream capture these become parallel branches of the
         // graph).  Group 0 holds the densest pictures -- the longest chains of re-sync rounds -- and stays on the main stream.  The
@@ -785,17 +773,6 @@ int enqueue_decode(pjd_batch *b, pjd_timings *timings, bool use_groups)
 // or otherwise irregular streams).  Runs on the GPU.  A shard is re-decoded over its own segment range.
 // As in the reference (decoder_host.cpp:181 drops decode_Huffman_data's result) such an image keeps its status
 // and its partial picture; the rest of the batch is unaffected.
-// one stream per device for the packed downloads of all contexts (never destroyed: a process has few devices)
-hipStream_t download_stream(int device)
-{
-    static std::mutex m;
-    static hipStream_t streams[64] = {nullptr};
-    if (device < 0 || device >= 64) return nullptr;
-    std::lock_guard<std::mutex> l(m);
-    if (!streams[device] && hipStreamCreateWithFlags(&streams[device], hipStreamNonBlocking) != hipSuccess) streams[device] = nullptr;
-    return streams[device];
-}
-
 int settle(pjd_batch *b)
 {
     pjd_ctx *ctx = b->ctx;
@@ -981,31 +958,9 @@ int pjd_batch_download_packed(pjd_batch *b, uint8_t *host, uint64_t capacity, in
     const uint64_t copy_bytes = b->bound && b->bound_capacity < b->res_buf_bytes ? b->bound_capacity : b->res_buf_bytes;
     int rc = settle(b);
     if (rc != PJD_OK) return rc;
-    // The runtime's copy (SDMA engine) by default.  PJD_DOWNLOAD=kernel: a small copy kernel on the device's download
-    // stream storing into the mapped page-locked destination instead -- it keeps the link as busy (tools/pcie_probe.hip)
-    // and leaves the engine to the uploads, but stores waiting for the link slow concurrent decode kernels down, and
-    // the pipelined batcher measured 9.1 GPix/s with it against 11.8 with the engine (profiles/r02_pcie.md).
-    void *mapped = nullptr;
-    static const bool by_kernel = [] { const char *e = std::getenv("PJD_DOWNLOAD"); return e && !std::strcmp(e, "kernel"); }();
-    hipPointerAttribute_t attr;
-    const bool pinned = by_kernel && !b->bound && (b->res_buf_bytes % 16) == 0 && ((uintptr_t)host % 16) == 0 &&
-                        hipPointerGetAttributes(&attr, host) == hipSuccess && attr.type == hipMemoryTypeHost &&
-                        hipHostGetDevicePointer(&mapped, host, 0) == hipSuccess && mapped;
-    if (by_kernel && !pinned) (void)hipGetLastError();
-    hipStream_t ds = pinned ? download_stream(ctx->device) : nullptr;
-    if (ds) {
-        // settle() has synchronised ctx->stream: the pictures are final
-        hipEvent_t done;
-        HIP_TRY(ctx, hipEventCreateWithFlags(&done, hipEventDisableTiming));
-        pjd_launch_copy_out(ds, b->res_out, mapped, b->res_buf_bytes);
-        hipError_t e = hipEventRecord(done, ds);
-        if (e == hipSuccess) e = hipEventSynchronize(done);
-        (void)hipEventDestroy(done);
-        HIP_TRY(ctx, e);
-    } else {
-        HIP_TRY(ctx, hipMemcpyAsync(host, b->res_out, copy_bytes, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    }
+    // the runtime's copy (SDMA engine): a copy kernel into mapped host memory lost to it, 9.1 against 11.8 GPix/s (profiles/r02_pcie.md)
+    HIP_TRY(ctx, hipMemcpyAsync(host, b->res_out, copy_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (status)
         for (size_t i = 0; i < P.images.size(); i++) status[i] = b->h_status[i] & 0xFF;
     return PJD_OK;
@@ -1515,10 +1470,7 @@ int pjd_plan_info(const pjd_image_desc *images, int n_images, int out_format, pj
     if (!info) return PJD_E_ARG;
     PjdPlan P;
     std::string err;
-    int mode = PJD_PLAN_LATENCY;           // as pjd_open: the environment's plan mode and subsequence size
-    if (const char *pm = std::getenv("PJD_PLAN_MODE")) mode = (pm[0] == 't' || pm[0] == '1') ? PJD_PLAN_THROUGHPUT : PJD_PLAN_LATENCY;
-    const char *sb = std::getenv("PJD_SUB_BYTES");
-    int rc = pjd_make_plan(images, n_images, out_format, P, err, sb ? (uint32_t)std::atoi(sb) : 0, mode);
+    int rc = pjd_make_plan(images, n_images, out_format, P, err, env_sub_bytes(), env_plan_mode());      // as a context opened now would plan
     if (rc != PJD_OK) return rc;
     std::memset(info, 0, sizeof *info);
     info->n_images = (int32_t)P.images.size();

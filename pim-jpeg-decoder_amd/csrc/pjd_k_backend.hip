@@ -2,8 +2,7 @@
 //
 //   pjd_k_dpu_payload   the reference's per-DPU contract, one workgroup per 16x16 "block"
 //                       (reference src/decoder_dpu.c:82-390)
-//   pjd_k_reset / _zero / _copy_out
-//                       per-decode state reset (kernels of ours, not runtime memset nodes), packed download by a kernel
+//   pjd_k_reset / _zero per-decode state reset (kernels of ours, not runtime memset nodes)
 //   pjd_k_lane_dc_local /  DC prediction: the entropy decoder leaves DC DIFFERENCES and per-lane sums; the predictors at every
 //   pjd_k_lane_dc_carry    lane start are a two-level segmented scan over lanes (reference src/jpeg_scanner.cpp:485-486,723-727)
 //   pjd_k_idct_colour_lanes / pjd_k_idct_colour
@@ -22,8 +21,6 @@
 // Integer work bound by VALU instruction issue (profiles/r03_cfg3.md: valu_issue_frac 1.0 -- the entry parser is its largest
 // phase), not by HBM: coefficients are read once with 16-byte loads, tiles live in LDS (row stride 144 B so that the column
 // pass is bank-conflict free), pictures are written once.
-#include <cstdlib>
-
 #include "pjd_k_backend_common.h"
 
 
@@ -89,27 +86,6 @@ __global__ __launch_bounds__(128) void pjd_k_dpu_payload(const uint32_t *__restr
 }
 
 // ---------------------------------------------------------------------------------------------
-// Packed download by a kernel (opt-in, PJD_DOWNLOAD=kernel): pictures go from HBM straight into mapped
-// page-locked host memory.  Few workgroups on purpose: stores waiting for the link hold memory-system
-// queues that other kernels need (128 workgroups per copy made concurrent decode kernels 5x slower,
-// profiles/r02_pcie.md).
-// ---------------------------------------------------------------------------------------------
-typedef unsigned int pjd_u32x4 __attribute__((ext_vector_type(4)));
-
-__global__ __launch_bounds__(256) void pjd_k_copy_out(const pjd_u32x4 *__restrict__ src, pjd_u32x4 *__restrict__ dst, uint64_t n16)
-{
-    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (uint64_t)gridDim.x * 256)
-        __builtin_nontemporal_store(__builtin_nontemporal_load(src + i), dst + i);
-}
-
-void pjd_launch_copy_out(hipStream_t s, const void *src, void *dst_mapped, uint64_t bytes)
-{
-    const uint64_t n16 = bytes / 16;       // the packed output buffer is a multiple of 256 bytes
-    static const int wgs = [] { const char *e = std::getenv("PJD_COPY_WGS"); const int v = e ? std::atoi(e) : 0; return v > 0 && v <= 4096 ? v : 16; }();
-    if (n16) hipLaunchKernelGGL(pjd_k_copy_out, dim3(wgs), dim3(256), 0, s, (const pjd_u32x4 *)src, (pjd_u32x4 *)dst_mapped, n16);
-}
-
-// ---------------------------------------------------------------------------------------------
 // Per-decode reset: status words from their initial values (images routed to the exact kernel start flagged), the
 // statistics, the words the Huffman waves publish to each other, the debug timeline.
 // ---------------------------------------------------------------------------------------------
@@ -119,7 +95,7 @@ __global__ __launch_bounds__(256) void pjd_k_reset(PjdDevBatch B, const int32_t 
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i < B.n_images) {
         B.status[i] = status_init[i];
-        PjdDevImState st; st.err_key = ~0ull; st.flag_pos = 0xffffffffu; st.waves_done = 0;
+        PjdDevImState st; st.err_key = ~0ull; st.flag_pos = 0xffffffffu;
         B.imstate[i] = st;
     }
     if (i < 16) B.stats[i] = 0;
@@ -749,10 +725,6 @@ __device__ __forceinline__ void pjd_idct_range(const PjdDevBatch &B, uint32_t iw
                                                uint8_t *comp_of, uint8_t *du_head, uint32_t *wagg, uint32_t *ltab)
 {
 #include "pjd_k_lanes_parse_body.h"
-#if defined(PJD_IDCT_STOP_AFTER) && PJD_IDCT_STOP_AFTER == 1      // timing experiments only (tools/r2_occ.sh): pictures are wrong
-    if (tile[0][0] == 12345) B.out[0] = 1;
-    return;
-#endif
     // ---- DC prediction over the range (reference src/jpeg_scanner.cpp:485-486) by wave 0, while the other waves already do
     //      the row pass of rows 1..7 (only row 0 holds the DC coefficient) and the slot-52 rule (natural 38 lies in row 4)
     if (wv != 0) {
@@ -766,37 +738,26 @@ __device__ __forceinline__ void pjd_idct_range(const PjdDevBatch &B, uint32_t iw
     }
     // ---- IDCT (reference src/decoder_dpu.c:210-321): rows, then columns; then colour
     __syncthreads();
-#if defined(PJD_IDCT_STOP_AFTER) && PJD_IDCT_STOP_AFTER == 2
-    if (tile[0][0] == 12345) B.out[0] = 1;
-    return;
-#endif
     for (uint32_t u = tid; u < n_du; u += PJD_IDCT_THREADS) pjd_tile_row(tile, u, 0);
     __syncthreads();
     for (uint32_t i = tid; i < n_du * 8; i += PJD_IDCT_THREADS) pjd_tile_col(tile, i >> 3, i & 7);
     __syncthreads();
-#if defined(PJD_IDCT_STOP_AFTER) && PJD_IDCT_STOP_AFTER == 3
-    if (tile[0][0] == 12345) B.out[0] = 1;
-    return;
-#endif
     pjd_colour_dispatch<SCALED, PLANAR>(tile, mcu_xy, B, im, wg, tid);
 }
 
 // order: the launch's workgroup -> index into PjdDevBatch::iwgs / marks (null: the identity, one launch for the whole batch)
-// sweep: only ranges not marked done by the pull launch (pjd_internal.h)
-__global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_colour_lanes(PjdDevBatch B, const uint32_t *__restrict__ order, int sweep)
+__global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_colour_lanes(PjdDevBatch B, const uint32_t *__restrict__ order)
 {
     PJD_LANES_LDS
 
 #if PJD_IDCT_PRIO
     __builtin_amdgcn_s_setprio(PJD_IDCT_PRIO);
 #endif
-    const uint32_t iwg = order ? order[blockIdx.x] : blockIdx.x;
-    if (sweep && __hip_atomic_load(B.range_done + iwg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
-    pjd_idct_range<false>(B, iwg, tile, qz, mcu_xy, comp_of, du_head, wagg, ltab);
+    pjd_idct_range<false>(B, order ? order[blockIdx.x] : blockIdx.x, tile, qz, mcu_xy, comp_of, du_head, wagg, ltab);
 }
 
 // The same for a batch that holds pictures with an output scale (PJD_F_SCALE_*): a kernel of its own, so that the full-size one keeps
-// its code and registers.  Never a sweep: the pull form is not used for such batches.
+// its code and registers.
 __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_colour_lanes_scaled(PjdDevBatch B, const uint32_t *__restrict__ order)
 {
     PJD_LANES_LDS
@@ -808,7 +769,7 @@ __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_colour_lanes_scal
 }
 
 // The lane-stream back end of a PJD_OUT_RGB8_PLANAR batch, without and with pictures that have an output scale: kernels of their own
-// again.  Never a sweep: the pull form is not used for such batches.
+// again.
 template <bool SCALED>
 __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_colour_lanes_planar(PjdDevBatch B, const uint32_t *__restrict__ order)
 {
@@ -820,74 +781,18 @@ __global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_colour_lanes_plan
     pjd_idct_range<SCALED, true>(B, order ? order[blockIdx.x] : blockIdx.x, tile, qz, mcu_xy, comp_of, du_head, wagg, ltab);
 }
 
-// The pull launch (pjd_internal.h; experiment switch PJD_IDLE_FORM=pull): a few workgroups per CU stay and take the ranges of ready_list
-// in order -- workgroup w the entries w, w + gridDim.x, ... -- waiting for each to appear.  A kernel of its own: inlined into the
-// kernel above the loop cost it 35 registers (46 -> 81) and with them its occupancy (0.50 -> 0.66 ms, 118 -> 102 GPix/s in flight).
-__global__ __launch_bounds__(PJD_IDCT_THREADS) void pjd_k_idct_pull(PjdDevBatch B)
-{
-    PJD_LANES_LDS
-    // It waits only if every Huffman workgroup has started -- else the device is busy or the launches came in an unlucky order, and
-    // the ranges are left to the sweep.
-    if (threadIdx.x == 0) {
-        uint32_t started = 0;
-        for (uint32_t it = 0; it < 64 && !started; it++) {
-            started = __hip_atomic_load(B.ticket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= B.n_hwg ? 1u : 0u;
-            if (!started) __builtin_amdgcn_s_sleep(64);
-        }
-        wagg[1] = started;
-    }
-    __syncthreads();
-    if (wagg[1] == 0) return;
-    for (uint32_t slot = blockIdx.x; slot < B.n_iwg; slot += gridDim.x) {
-        __syncthreads();                                                   // the LDS arrays of the range before
-        if (threadIdx.x == 0) {
-            uint32_t v = 0;
-            for (uint32_t it = 0; it < PJD_PULL_SPIN_LIMIT; it++) {
-                v = __hip_atomic_load(B.ready_list + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (v) break;
-                __builtin_amdgcn_s_sleep(64);
-            }
-            wagg[0] = v;
-        }
-        __syncthreads();
-        const uint32_t v = wagg[0];
-        __syncthreads();
-        if (v == 0) return;                                                // gave up: this entry and the workgroup's later ones go to the sweep
-#if defined(PJD_PULL_EXPERIMENT) && PJD_PULL_EXPERIMENT == 1             // measurement only: take the entry, do nothing (the sweep does the work)
-        continue;
-#endif
-        __atomic_thread_fence(__ATOMIC_ACQUIRE);                           // what the picture's waves wrote (agent scope: other CUs)
-        pjd_idct_range<false>(B, v - 1, tile, qz, mcu_xy, comp_of, du_head, wagg, ltab);
-        __syncthreads();
-        if (threadIdx.x == 0) __hip_atomic_store(B.range_done + (v - 1), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // read by the sweep: a later launch
-    }
-}
-
-// The kernel of a form for lane-stream input.  The default form's kernel is also the sweep of the pull form and takes a third argument.
+// The kernel of a form for lane-stream input.
 void pjd_launch_idct_lanes(hipStream_t s, const PjdDevBatch &b, PjdBackForm f, const uint32_t *order, uint32_t n_wg)
 {
     if (n_wg == 0) return;
     if (f.layout == PJD_BACK_INTERLEAVED && !f.scaled) {
-        hipLaunchKernelGGL(pjd_k_idct_colour_lanes, dim3(n_wg), dim3(PJD_IDCT_THREADS), 0, s, b, order, 0);
+        hipLaunchKernelGGL(pjd_k_idct_colour_lanes, dim3(n_wg), dim3(PJD_IDCT_THREADS), 0, s, b, order);
         return;
     }
     // scaled before full size in every table of the back end: the order the templates are instantiated in is part of a unit's text
     static const PjdLanesKernel colour[3] = {pjd_k_idct_colour_lanes_planar<true>, pjd_k_idct_colour_lanes_planar<false>, pjd_k_idct_colour_lanes_scaled};
     const PjdLanesKernel k = f.gray() ? pjd_gray_lanes_kernel(f.scaled ? PJD_GRAY_SCALED : PJD_GRAY_FULL) : colour[f.layout == PJD_BACK_PLANAR ? !f.scaled : 2];
     hipLaunchKernelGGL(k, dim3(n_wg), dim3(PJD_IDCT_THREADS), 0, s, b, order);
-}
-
-void pjd_launch_idct_pull(hipStream_t s, const PjdDevBatch &b)
-{
-    // two workgroups per CU: enough to keep up with the pictures as they complete, few enough to leave the entropy decoder its issue slots
-    static const uint32_t workers = [] { const char *e = std::getenv("PJD_PULL_WORKERS"); const int v = e ? std::atoi(e) : 0; return (uint32_t)(v > 0 ? v : 512); }();
-    const uint32_t n = b.n_iwg < workers ? b.n_iwg : workers;
-    if (n) hipLaunchKernelGGL(pjd_k_idct_pull, dim3(n), dim3(PJD_IDCT_THREADS), 0, s, b);
-}
-
-void pjd_launch_idct_sweep(hipStream_t s, const PjdDevBatch &b)
-{
-    if (b.n_iwg) hipLaunchKernelGGL(pjd_k_idct_colour_lanes, dim3(b.n_iwg), dim3(PJD_IDCT_THREADS), 0, s, b, (const uint32_t *)nullptr, 1);
 }
 
 // ---------------------------------------------------------------------------------------------

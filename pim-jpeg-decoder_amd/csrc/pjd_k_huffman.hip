@@ -46,7 +46,6 @@
 // reproduce its synchronised exit -- is reported with its position (PjdDevImState::flag_pos); only if
 // that lies before the picture's first error does pjd_batch_sync re-decode the picture with the
 // one-lane exact kernel, on the GPU.
-#include <cstdlib>
 
 #include "pjd_device_common.h"
 #include "pjd_kernels.h"
@@ -91,10 +90,6 @@ __global__ __launch_bounds__(256) void pjd_k_build_tables(PjdDevBatch B)
 // One block per Huffman wave: the wave's 64 lane streams as big-endian words, transposed.
 // A lane's 128-byte source lines are re-read from L1 for 32 consecutive rows; the rows are written whole.
 struct __attribute__((packed)) UnalignedU32 { uint32_t v; };
-#ifndef PJD_WORDS_X4
-#define PJD_WORDS_X4 1
-#endif
-
 struct __attribute__((packed)) UnalignedU32x4 { uint32_t v[4]; };
 
 // Launched once per upload over all waves of the batch.
@@ -108,7 +103,6 @@ __global__ __launch_bounds__(256) void pjd_k_lane_words(PjdDevBatch B)
     uint32_t *dst = B.words + (size_t)wv * B.word_rows * 64;
     const bool valid = l < hw.n_lanes;
     const uint8_t *src = B.ecs + im.ecs_off + (valid ? B.lanes[hw.first_lane + l].byte_start : 0u);
-#if PJD_WORDS_X4
     // 16 bytes of the lane's stream per load (four rows), four groups of rows in flight per thread
     for (uint32_t k = 4 * k0; k < rows; k += 16) {
         uint32_t w[4] = {0, 0, 0, 0};
@@ -120,13 +114,6 @@ __global__ __launch_bounds__(256) void pjd_k_lane_words(PjdDevBatch B)
 #pragma unroll
         for (int j = 0; j < 4; j++) dst[(k + j) * 64 + l] = w[j];
     }
-#else
-    for (uint32_t k = k0; k < rows; k += 4) {
-        uint32_t w = 0;
-        if (valid) w = __builtin_bswap32(reinterpret_cast<const UnalignedU32 *>(src + 4 * k)->v);
-        dst[k * 64 + l] = w;
-    }
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -136,25 +123,17 @@ __global__ __launch_bounds__(256) void pjd_k_lane_words(PjdDevBatch B)
 // ---------------------------------------------------------------------------------------------
 typedef const __attribute__((address_space(1))) uint8_t *pjd_gptr;      // global memory, so that loads are global_load (a generic
                                                                          // pointer gives flat_load, which also counts as an LDS access)
-#if PJD_DIRECT_ECS
-#define PJD_WORD_STRIDE 4u          // the lanes read the batch's bitstream itself: a lane's words are consecutive (unaligned) dwords
-#else
 #define PJD_WORD_STRIDE 256u        // transposed rows (pjd_k_lane_words): word k of a lane is 256 bytes after word k-1
-#endif
 struct BitWin {
-    pjd_gptr wb;          // wave-uniform: row 0 of the wave's word rows / the first byte of the picture's bitstream
+    pjd_gptr wb;          // wave-uniform: row 0 of the wave's word rows
     uint32_t hi, lo, nxt;
     uint32_t off;         // byte offset (from wb) of this lane's next word to fetch
     int s;
     __device__ __forceinline__ uint32_t word(uint32_t byte_off) const
     {
-#if PJD_DIRECT_ECS
-        return __builtin_bswap32(reinterpret_cast<const __attribute__((address_space(1))) UnalignedU32 *>(wb + byte_off)->v);
-#else
         return *reinterpret_cast<const __attribute__((address_space(1))) uint32_t *>(wb + byte_off);
-#endif
     }
-    // col = byte offset of the lane's word 0 from wb: lane * 4 in the transposed rows, the lane's first byte in the bitstream
+    // col = byte offset of the lane's word 0 from wb: lane * 4 in the transposed rows
     __device__ __forceinline__ void init(pjd_gptr wave_words, uint32_t col, uint32_t p)
     {
         wb = wave_words;
@@ -1013,67 +992,6 @@ __device__ __forceinline__ uint64_t op_wait_flag(const uint64_t *p, bool &timeou
 }
 
 // ---------------------------------------------------------------------------------------------
-// The pull back end (pjd_internal.h): what the LAST wave of a picture to finish does for the picture, with its 64 lanes -- the
-// verdict (pjd_k_image_verdict), the DC predictors at every lane start (pjd_k_lane_dc_local / _carry: a segmented scan over the
-// picture's lanes, here in chunks of 64 with absolute results) -- and the hand-over of the picture's back-end ranges.
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void finish_picture(const PjdDevBatch &B, uint32_t image, uint32_t l)
-{
-    const PjdDevImage &im = B.images[image];
-    __atomic_thread_fence(__ATOMIC_ACQUIRE);                    // what the picture's other waves wrote
-    if (l == 0) {
-        const int32_t st = B.status[image];
-        if (!(st & PJD_STW_NEEDS_EXACT)) {
-            const PjdDevImState s = B.imstate[image];
-            const bool has_err = s.err_key != ~0ull;
-            const uint32_t err_pos = (uint32_t)(s.err_key >> 32);
-            if (s.flag_pos != 0xffffffffu && (!has_err || s.flag_pos <= err_pos)) B.status[image] = st | PJD_STW_NEEDS_EXACT;
-            else if (has_err) B.status[image] = (int32_t)((s.err_key >> 1) & 7u);
-        }
-    }
-    uint32_t cy = 0, ccb = 0, ccr = 0;                         // predictors entering the current chunk of lanes (wave-uniform)
-    const uint32_t n_lane = rfl(im.n_lane), lane_base = rfl(im.lane_base);
-    for (uint32_t base = 0; base < n_lane; base += 64) {
-        const bool on = base + l < n_lane;
-        uint32_t vy = 0, vcb = 0, vcr = 0, head = 0;
-        if (on) {
-            const PjdDevLaneInfo li = B.lane_info[lane_base + base + l];
-            vy = li.dc_sum[0]; vcb = li.dc_sum[1]; vcr = li.dc_sum[2]; head = li.first_du >> 31;
-        }
-        uint32_t f = head;
-        for (int off = 1; off < 64; off <<= 1) {                // inclusive segmented scan: a lane that starts a restart segment resets
-            const uint32_t ay = __shfl_up(vy, off), acb = __shfl_up(vcb, off), acr = __shfl_up(vcr, off), af = __shfl_up(f, off);
-            if ((int)l >= off) {
-                if (!f) { vy += ay; vcb += acb; vcr += acr; }
-                f |= af;
-            }
-        }
-        // predictors entering this lane: zero at a segment head; else the inclusive result of the lane before it, plus the chunk's
-        // carry-in unless a head lies between the chunk start and this lane
-        const uint32_t py = __shfl_up(vy, 1), pcb = __shfl_up(vcb, 1), pcr = __shfl_up(vcr, 1), pf = __shfl_up(f, 1);
-        if (on) {
-            PjdDevLaneDc d;
-            d.dc_in[0] = d.dc_in[1] = d.dc_in[2] = 0;
-            d.abs = 1;
-            if (!head) {
-                uint32_t qy = cy, qcb = ccb, qcr = ccr;
-                if (l > 0) { qy = (pf ? 0u : cy) + py; qcb = (pf ? 0u : ccb) + pcb; qcr = (pf ? 0u : ccr) + pcr; }
-                d.dc_in[0] = (uint16_t)qy; d.dc_in[1] = (uint16_t)qcb; d.dc_in[2] = (uint16_t)qcr;
-            }
-            B.lane_dc[lane_base + base + l] = d;
-        }
-        const uint32_t ly = __shfl(vy, 63), lcb = __shfl(vcb, 63), lcr = __shfl(vcr, 63), lf = __shfl(f, 63);
-        cy = (lf ? 0u : cy) + ly; ccb = (lf ? 0u : ccb) + lcb; ccr = (lf ? 0u : ccr) + lcr;
-    }
-    __atomic_thread_fence(__ATOMIC_RELEASE);                    // status and predictors before the ranges appear in the list
-    const uint32_t n_iwg = rfl(im.n_iwg), iwg_base = rfl(im.iwg_base);
-    uint32_t base = 0;
-    if (l == 0) base = atomicAdd(B.ready_tail, n_iwg);
-    base = rfl(base);
-    for (uint32_t k = l; k < n_iwg; k += 64) __hip_atomic_store(B.ready_list + base + k, iwg_base + k + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// ---------------------------------------------------------------------------------------------
 // The kernel.
 //
 // With one launch per stage every stage waits for the slowest wave of the whole batch, and that wave is
@@ -1150,9 +1068,6 @@ __global__ __launch_bounds__(PJD_HUFF_THREADS) PJD_HUFF_OCC_ATTR void pjd_k_huff
     P.build(l);                                                // this wave's phase table (read by this wave only)
     __syncthreads();                                           // the last barrier: from here on waves run on their own
     if (!wave_on) return;
-    // beside the pull back end (pjd_internal.h) every wave of the entropy decoder issues ahead of the back end's: its chains are the
-    // critical path, the back end fills what they leave
-    if (B.pull) __builtin_amdgcn_s_setprio(1);
 
     const uint64_t ts0 = B.dbg ? __builtin_amdgcn_s_memrealtime() : 0;
     const uint64_t tc0 = B.dbg ? __builtin_amdgcn_s_memtime() : 0;          // shader clock: with ts0..ts5 (100 MHz) it gives the clock the chip held
@@ -1163,13 +1078,8 @@ __global__ __launch_bounds__(PJD_HUFF_THREADS) PJD_HUFF_OCC_ATTR void pjd_k_huff
     g.q = hw.first_lane + l;
     g.seg_first = g.seg_last = false;
     g.seg = 0; g.end_bit = g.seg_end_bit = g.base_bit = 0;
-#if PJD_DIRECT_ECS
-    g.words = (pjd_gptr)readfirstlane_u64((uint64_t)(B.ecs + im.ecs_off));
-    g.col = 0;
-#else
     g.words = (pjd_gptr)readfirstlane_u64((uint64_t)(B.words + (size_t)w * B.word_rows * 64));
     g.col = l * 4;
-#endif
     uint32_t seg_first_du = 0, seg_n_du = 0;
     const uint32_t sub_bytes = rfl(im.sub_bytes);        // of this wave's image
     if (g.valid) {
@@ -1180,9 +1090,6 @@ __global__ __launch_bounds__(PJD_HUFF_THREADS) PJD_HUFF_OCC_ATTR void pjd_k_huff
         const uint32_t end_byte = sb.byte_start + sub_bytes < sg.byte_end ? sb.byte_start + sub_bytes : sg.byte_end;
         g.seg_last = end_byte == sg.byte_end;
         g.base_bit = sb.byte_start * 8;
-#if PJD_DIRECT_ECS
-        g.col = sb.byte_start;
-#endif
         g.end_bit = (end_byte - sb.byte_start) * 8;
         g.seg_end_bit = (sg.byte_end - sb.byte_start) * 8;
         seg_first_du = sg.first_du; seg_n_du = sg.n_du;
@@ -1419,13 +1326,6 @@ __global__ __launch_bounds__(PJD_HUFF_THREADS) PJD_HUFF_OCC_ATTR void pjd_k_huff
         for (int r = 0; r < PJD_FLAG_REASONS; r++)
             if (wflag & (1u << r)) atomicAdd(B.stats + PJD_STAT_FLAG0 + r, 1ull);
     }
-    if (B.pull) {
-        // the pull back end (pjd_internal.h): the picture's last wave to get here settles the picture and hands its ranges over
-        __atomic_thread_fence(__ATOMIC_RELEASE);                // this wave's entries, lane_info, marks, error state
-        uint32_t done = 0;
-        if (l == 0) done = atomicAdd(&B.imstate[hw.image].waves_done, 1u) + 1u;
-        if (rfl(done) == rfl(im.n_hwave)) finish_picture(B, hw.image, l);
-    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1555,8 +1455,7 @@ void pjd_launch_huff_exact_lut(hipStream_t s, const PjdDevBatch &b, const uint32
 // ---------------------------------------------------------------------------------------------
 static size_t huff_lds_bytes(const PjdDevBatch &b)
 {
-    static const size_t extra = [] { const char *e = std::getenv("PJD_EXTRA_LDS"); return e ? (size_t)std::atoi(e) : (size_t)0; }();   // occupancy experiments
-    return (size_t)b.max_lut_bytes + PJD_HUFF_WAVES * (PJD_WAVE_LDS + PJD_PHASE_LDS) + 16 + extra;
+    return (size_t)b.max_lut_bytes + PJD_HUFF_WAVES * (PJD_WAVE_LDS + PJD_PHASE_LDS) + 16;
 }
 
 void pjd_launch_build_tables(hipStream_t s, const PjdDevBatch &b)
@@ -1566,9 +1465,6 @@ void pjd_launch_build_tables(hipStream_t s, const PjdDevBatch &b)
 }
 void pjd_launch_lane_words(hipStream_t s, const PjdDevBatch &b)
 {
-#if PJD_DIRECT_ECS
-    return;
-#endif
     if (b.n_hwave) hipLaunchKernelGGL(pjd_k_lane_words, dim3(b.n_hwave), dim3(256), 0, s, b);
 }
 void pjd_launch_huff_lanes(hipStream_t s, const PjdDevBatch &b)

@@ -35,10 +35,6 @@ struct PjdDevBatch {
     uint64_t *wave_gen;                  // [PJD_GENS][n_hwave]: exit state of a wave's last lane | flag, one word per generation (pjd_internal.h)
     uint64_t *wave_desc;                 // per Huffman wave: look-back descriptor (status | poison | head | units)
     uint32_t *ticket;                    // workgroup index dispenser
-    uint32_t *ready_list;                // pull back end (pjd_internal.h): [n_iwg] range index + 1 in the order pictures complete; 0: not yet
-    uint32_t *ready_tail;                // entries appended so far
-    uint32_t *range_done;                // [n_iwg] 1: the range's pixels are written
-    uint32_t pull;                       // 1: this launch takes part in the pull protocol (Huffman waves publish, back-end workgroups take from the list)
     uint32_t *dbg;                       // PJD_DEBUG_STATS: per wave, 8 timestamps (10 ns units); else null
     unsigned long long *stats;           // [16] diagnostics: 0 re-sync rounds, 1 lane passes in them, 2 / 3 the same for the stitch
                                          //      stage, PJD_STAT_FLAG0.. waves that flagged their image, by reason, 12 / 13 cooperative walks and the lanes walked in them
@@ -53,7 +49,6 @@ struct PjdDevBatch {
 void pjd_launch_dpu_payload(hipStream_t s, const uint32_t *metadata, int16_t *mcus, int n_dpus);
 void pjd_launch_zero(hipStream_t s, void *p, size_t bytes);          // bytes: a multiple of 16
 void pjd_launch_reset(hipStream_t s, const PjdDevBatch &b, const int32_t *status_init, uint64_t *opstate, size_t opstate_words, uint32_t dbg_words);   // per-decode state
-void pjd_launch_copy_out(hipStream_t s, const void *src, void *dst_mapped, uint64_t bytes);   // HBM -> mapped page-locked host memory
 // ---- the fused back end: coefficients -> pixels, one kernel family per form of the batch's output
 // The form: where the channels of a pixel go, and whether the batch holds pictures with an output scale (PJD_IF_SCALE_MASK: the
 // kernels that also serve them).  Built once from the plan (pjd_batch::back, pjd_api.hip); every launcher below picks its kernel by it.
@@ -64,7 +59,6 @@ struct PjdBackForm {
     bool scaled;
     bool planes() const { return layout != PJD_BACK_INTERLEAVED; }     // what the resample reads and writes: planes (three, or one)
     bool gray() const { return layout == PJD_BACK_GRAY; }
-    bool has_pull() const { return layout == PJD_BACK_INTERLEAVED && !scaled; }   // the pull form serves the default kernel alone
 };
 // lane-stream input: workgroup k takes range order[k] of iwgs / marks (null: the identity -- the whole batch when n_wg = n_iwg)
 void pjd_launch_idct_lanes(hipStream_t s, const PjdDevBatch &b, PjdBackForm f, const uint32_t *order, uint32_t n_wg);
@@ -75,9 +69,6 @@ void pjd_launch_idct_dense(hipStream_t s, const PjdDevBatch &b, PjdBackForm f, c
 void pjd_launch_lane_dc_scan(hipStream_t s, const PjdDevBatch &b, bool per_picture);
 // one picture group (pjd_internal.h): verdict + DC predictors of its pictures in one launch (its back-end workgroups: pjd_launch_idct_lanes)
 void pjd_launch_group_dc(hipStream_t s, const PjdDevBatch &b, const PjdDevGroup &g);
-// pull back end (pjd_internal.h): the launch that runs beside the entropy decoder, and the sweep over what it left
-void pjd_launch_idct_pull(hipStream_t s, const PjdDevBatch &b);
-void pjd_launch_idct_sweep(hipStream_t s, const PjdDevBatch &b);
 // ---- PJD_F_LIBJPEG pictures (islow IDCT), from the lane streams or the dense scratch as above.  Interleaved and planar batches
 // (pjd_k_backend_std.hip): into component planes -- `planes` is the batch's plane buffer (PjdDevImage::plane_off256) -- then upsample +
 // colour + store by pjd_launch_colour_std (cwgs[k] = {image, first 4-pixel item, -, -}).  A grey batch (pjd_k_backend_gray.hip): the
@@ -141,6 +132,6 @@ void pjd_launch_build_tables(hipStream_t s, const PjdDevBatch &b);
 void pjd_launch_lane_words(hipStream_t s, const PjdDevBatch &b);     // bitstream -> per-lane big-endian words, transposed per wave
 void pjd_launch_huff_lanes(hipStream_t s, const PjdDevBatch &b);     // synchronise + stitch + scan + write
 // what the runtime says of that launch on the current device: workgroups of pjd_k_huff_lanes one CU holds at the batch's dynamic LDS
-// (*lds_bytes: that size, PJD_EXTRA_LDS included)
+// (*lds_bytes: that size)
 hipError_t pjd_huff_lanes_occupancy(const PjdDevBatch &b, int *workgroups_per_cu, size_t *lds_bytes);
 void pjd_launch_huff_lanes_group(hipStream_t s, const PjdDevBatch &b, const PjdDevGroup &g, uint32_t group_index);   // the same for one picture group

@@ -3,12 +3,11 @@ on one axis, one MCU column thousands of MCU rows tall, MCU grids 8192 wide and 
 DRI of 65535, widths on both sides of 32768 -- on every decode path: lane streams in both plan modes and all three output formats,
 each member alone, the exact kernel with the dense back end, picture groups, reduced size, resize on decode (the 64-bit taps, the
 top of the 32-bit branch, row taps up to 65534), bound outputs with guard bytes, entropy errors, shards and split decode, the
-literal DPU payload, the CLI and the pipelined batcher, the pull form, and progressive frames.
+literal DPU payload, the CLI and the pipelined batcher, and progressive frames.
 
 Every comparison is byte equality, and every expected byte comes from the oracle port (oracle/liboracle.so), tests/resize_model.py,
 the box filter of test_gpu_scaled.py or the progressive model of tests/jpeg_progressive.py; none from a decode by this library.  Every
 test asserts how many pictures it compared."""
-import hashlib
 import json
 import os
 import subprocess
@@ -524,53 +523,7 @@ def test_family_through_the_pipelined_batcher(port, oracle):
     assert st["out_bytes"] == sum(len(oracle[G.REF_RULE if n == G.STD_RULE else n]["bmp"]) for n in G.NAMES)
 
 
-# ---- 12: the pull form -----------------------------------------------------------------------------------------------------------------------
-PULL_CHILD = """
-import os, sys, json, hashlib
-os.environ["PJD_IDLE_FORM"] = "pull"
-sys.path[:0] = json.loads(sys.argv[2])
-import numpy as np, pjd_amd
-work = sys.argv[1]
-items = json.load(open(work + "/items.json"))       # [[file, flags]]
-scanned = []
-for f, flags in items:
-    s = pjd_amd.Scanned(open(work + "/" + f, "rb").read())
-    assert s.valid
-    s.desc.flags = int(s.desc.flags) | flags
-    scanned.append(s)
-ctx = pjd_amd.Context(0)
-b = ctx.batch([s.desc for s in scanned], pjd_amd.OUT_RGB8)
-b.upload(); b.capture()
-for rep in range(2):
-    b.decode(); b.sync()
-outs, st = b.download()
-info = b.info()
-sha = lambda a: hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
-print("RESULT", json.dumps({"status": st, "shape": [list(o.shape) for o in outs], "rgb": [sha(o) for o in outs],
-                            "coef": [sha(b.coefficients(k)) for k in range(len(items))],
-                            "n_fallback": info["n_fallback"], "n_sequential": info["n_sequential"]}))
-"""
-
-
-def test_pull_form(tmp_path, oracle):
-    """PJD_IDLE_FORM=pull (the back end beside the entropy decoder; the switch is read once: a child process) on the lane-path
-    members, captured and replayed twice: the digests of pictures and coefficients are those of the oracle's."""
-    for name in LANE:
-        (tmp_path / (name + ".jpg")).write_bytes(G.jpeg(name))
-    (tmp_path / "items.json").write_text(json.dumps([[name + ".jpg", G.flags(name)] for name in LANE]))
-    r = subprocess.run([sys.executable, "-c", PULL_CHILD, str(tmp_path), json.dumps(PYTHONPATH)], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "RESULT " in r.stdout, (r.stdout[-1500:] + r.stderr[-3000:])
-    got = json.loads(r.stdout.split("RESULT ", 1)[1])
-    sha = lambda a: hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
-    assert got["status"] == [0] * 14 and got["n_fallback"] == 0 and got["n_sequential"] == 0, got
-    for k, name in enumerate(LANE):
-        assert got["shape"][k] == list(oracle[name]["rgb"].shape), name
-        assert got["rgb"][k] == sha(oracle[name]["rgb"]), (name, "picture")
-        assert got["coef"][k] == sha(oracle[name]["coef"]), (name, "coefficients")
-    assert len(got["rgb"]) == len(got["coef"]) == len(LANE) == 14
-
-
-# ---- 13: progressive frames --------------------------------------------------------------------------------------------------------------------
+# ---- 12: progressive frames --------------------------------------------------------------------------------------------------------------------
 # (label, sampling, w, h, PC.full_script?)  The full dimension with a short script (DC first at Al = 0, then one AC band 1..63), a quarter
 # of it with every refinement level: the writer and the model take some ten seconds of CPU per frame at 65521 x 16 and 9 x 65535.
 # full_script's luma AC scans are not interleaved and cover ceil(w / 8) block columns: 2047 of the 2048 of the MCU grid at 16369.

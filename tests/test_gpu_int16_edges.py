@@ -2,15 +2,12 @@
 32767 and -32767 in every component and sampling, at the last unit and after restarts, beside an explicit zero and a value at slot 52,
 and AC values whose dequantised product is at those values at natural positions 0, 1, 38, 58 (T.81 map) and 63 -- on every decode
 path: lane streams (both plan modes, picture groups), the table-driven exact kernel, the literal kernel, up-front routing, reduced-size
-output on the lane and dense back ends, split decode and the pull form.
+output on the lane and dense back ends, and split decode.
 
 The exact kernels keep an absolute DC in slot 0 of the dense scratch and mark an explicit zero at slot 52 with -32768: a DC of -32768
 must stay a value there.  Status, pictures and coefficients must equal the streams' intent (tests/jpeg_symbols.py) and, where the
 reference's restart rule applies, the oracle port, which follows the reference: (int16)(-32768 * q) is -32768 for an odd quantiser."""
 import functools
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -21,8 +18,6 @@ from test_gpu_scaled import SCALES, box
 from test_gpu_symbol_streams import _decode_and_check, _scan, intent_rgb
 
 pytestmark = pytest.mark.gpu
-
-HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 @functools.lru_cache(maxsize=1)
@@ -172,39 +167,6 @@ def test_split_decode_of_restart_segmented_edge_pictures(port, monkeypatch):
     finally:
         ctx.close()
         pjd_amd.dev_lib().pjd_split_release()
-
-
-def test_pull_form_on_the_edge_family():
-    """PJD_IDLE_FORM=pull (the back end beside the entropy decoder) on the lane-path members, in a child process (the switch is read
-    once): pictures and coefficients equal the intent."""
-    code = f"""
-import os, sys
-os.environ["PJD_IDLE_FORM"] = "pull"
-sys.path.insert(0, {os.path.join(os.path.dirname(HERE), "pim-jpeg-decoder_amd", "python")!r}); sys.path.insert(0, {HERE!r})
-import numpy as np, pjd_amd, oracle_lib
-import jpeg_symbols as J
-from test_gpu_int16_edges import _lane_items
-from test_gpu_symbol_streams import _scan, intent_rgb
-port = oracle_lib.Port()
-items = _lane_items()
-sc = _scan(items)
-ctx = pjd_amd.Context(0)
-b = ctx.batch([s.desc for s in sc], pjd_amd.OUT_RGB8)
-b.upload(); b.capture()
-for rep in range(2):
-    b.decode(); b.sync()
-outs, st = b.download()
-info = b.info()
-bad = []
-for k, (label, data, fr, it) in enumerate(items):
-    port.standard_zigzag(fr.standard_zigzag)
-    if st[k] != it.status or not np.array_equal(outs[k], intent_rgb(port, data, fr, it)) or not np.array_equal(b.coefficients(k), J.intent_buffer(fr, it)):
-        bad.append(label)
-    port.standard_zigzag(False)
-print("RESULT", "ok" if not bad and info["n_fallback"] == 0 else ("bad %s fb %s" % (bad[:5], info["n_fallback"])))
-"""
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "RESULT ok" in r.stdout, (r.stdout[-400:] + r.stderr[-400:])
 
 
 def _progressive_frame(sub, w, h):

@@ -1348,14 +1348,12 @@ def test_plan_modes_give_the_same_pictures(port):
     assert lanes[pjd_amd.PLAN_LATENCY] > lanes[pjd_amd.PLAN_THROUGHPUT] * 5 // 4
 
 
-def test_pull_form_of_the_back_end_is_bit_exact():
-    """PJD_IDLE_FORM=pull (an experiment switch: the back end runs beside the entropy decoder and takes every picture as its last
-    wave completes it; slower than the picture groups on this hardware) stays correct: a batch with dense pictures,
-    restart intervals, every sampling mode and damaged streams against the oracle, in a child process (the switch is read once)."""
+def test_mixed_batch_replayed_on_an_idle_device_is_bit_exact():
+    """A batch alone on an idle device (a child process of its own), captured and replayed three times: dense pictures, restart
+    intervals, every sampling mode and a damaged stream against the oracle, pictures, statuses and one picture's coefficients."""
     import subprocess, sys, textwrap
     code = textwrap.dedent("""
         import os, sys
-        os.environ["PJD_IDLE_FORM"] = "pull"
         sys.path.insert(0, %r); sys.path.insert(0, %r); sys.path.insert(0, %r)
         import numpy as np, pjd_amd, oracle_lib, synth
         port = oracle_lib.Port()

@@ -237,13 +237,12 @@ def test_pipeline_planar_sink_payloads(ctx, oracle):
         assert np.array_equal(data, chw(oracle[n][1]).reshape(-1)), n
 
 
-# ---- 11: the pull form -------------------------------------------------------------------------------------------------------------
-def test_idle_device_form_pull_falls_back_for_planar_batches():
-    """PJD_IDLE_FORM=pull has no planar back end: a planar batch takes the picture groups instead and comes out right (child
-    process: the switch is read once)."""
+# ---- 11: a batch alone on an idle device -------------------------------------------------------------------------------------------
+def test_planar_batch_of_80_replayed_on_an_idle_device():
+    """A planar batch of 80 pictures, captured and replayed on an idle device (a child process of its own: nothing else of this suite
+    is on the device): it takes the picture groups and comes out right."""
     code = f"""
 import os, sys
-os.environ["PJD_IDLE_FORM"] = "pull"
 sys.path.insert(0, {os.path.join(ROOT, "pim-jpeg-decoder_amd", "python")!r}); sys.path.insert(0, {HERE!r}); sys.path.insert(0, {os.path.join(ROOT, "tools")!r})
 import numpy as np, pjd_amd, oracle_lib, synth
 port = oracle_lib.Port()

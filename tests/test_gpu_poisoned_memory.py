@@ -422,14 +422,6 @@ def _child(poison, env):
     return [int(v) for v in r.stdout.split("RESULT ok")[1].split()]
 
 
-def test_pull_form_in_a_child_process(poison):
-    """PJD_IDLE_FORM=pull is read once per process: a fresh child decodes the lane-path fixtures and damaged streams (more than 64
-    pictures, so that the form is taken), captured and replayed; the back end then reads status, error state, predictors and marks
-    across streams, in the order the entropy decoder's waves finish."""
-    n, n_err, _, _ = _child(poison, {"PJD_IDLE_FORM": "pull"})
-    assert n >= 100 and n_err >= 3 * (len(HUFF_ERR) - 2)
-
-
 @pytest.mark.parametrize("walk_max", ["64", "0"])
 def test_walker_forced_on_and_off(poison, walk_max):
     """PJD_WALK_MAX=64: every re-sync round of every picture is a cooperative walk; 0: never.  The same batch, the same checks."""

@@ -167,12 +167,11 @@ def test_cfg3_batch_round_robin_scales(port, plan_mode):
         c.close()
 
 
-def test_idle_device_form_pull_falls_back_for_scaled_batches():
-    """PJD_IDLE_FORM=pull has no scaled back end: a batch with scaled pictures takes the picture groups instead and comes out right
-    (child process: the switch is read once)."""
+def test_scaled_batch_of_80_replayed_on_an_idle_device():
+    """A batch of 80 pictures at all four scales, captured and replayed on an idle device (a child process of its own: nothing else
+    of this suite is on the device): it takes the picture groups and comes out right."""
     code = f"""
 import os, sys
-os.environ["PJD_IDLE_FORM"] = "pull"
 sys.path.insert(0, {os.path.join(ROOT, "pim-jpeg-decoder_amd", "python")!r}); sys.path.insert(0, {HERE!r}); sys.path.insert(0, {os.path.join(ROOT, "tools")!r})
 import numpy as np, pjd_amd, oracle_lib, synth
 from test_gpu_scaled import box
