@@ -370,7 +370,10 @@ typedef struct pjd_image_desc {
     uint32_t restart_interval;         /* DRI value, 0 = none                                 */
     const uint8_t *ecs;                /* entropy-coded bytes, destuffed (FF00 -> FF) and with
                                           RSTn removed == Header::huffman_data (jpeg.h:168)   */
-    uint64_t ecs_len;
+    uint64_t ecs_len;                  /* below 2^29 (512 MiB: the decoder's bit positions are
+                                          32-bit); 2^29 and more is refused with PJD_E_ARG.
+                                          tests/test_giant_cpu.py pins the refusal on both sides,
+                                          tests/test_gpu_giant.py decodes 2^29 - 1 bytes        */
     const uint64_t *seg_offsets;       /* byte offset in `ecs` of each restart segment,
                                           seg_offsets[0] == 0; NULL => one segment            */
     uint32_t n_segments;

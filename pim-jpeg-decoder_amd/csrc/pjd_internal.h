@@ -150,12 +150,18 @@ static inline __host__ __device__ uint32_t pjd_lj_chroma_size(uint32_t n, uint32
 //             the write pass finds it by itself -- bad symbol, bad size, run past slot 63, end of data -- so such pictures
 //             need no second decode
 //   flag_pos  bit position (start of the lane, or of the wave's first lane) of the earliest thing the decoder could NOT resolve
-//             (PJD_FLAG_*): only that, and only if it lies before the first error, sends the picture to the exact kernel
+//             (PJD_FLAG_*): only that, and only if it lies before the first error and not behind the picture's last unit, sends the
+//             picture to the exact kernel
+//   end_pos   bit position at which the last unit of the picture ended, published by the unflagged lane whose write pass completed
+//             the stream's last segment.  Bytes behind it (padding in front of the EOI) hold nothing the reference decodes: a lane
+//             that STARTS behind it has no unit, and what the decoder could not resolve there -- a long run of bytes that never
+//             self-synchronises ends as PJD_FLAG_STITCH -- does not count.  A lane that published from a stale entry state lies
+//             in a wave that is flagged itself, at or before that lane, so a wrong end_pos never hides a flag
 // layout of err_key's low word: bits 31..4 data unit, bits 3..1 PJD_ST_* class, bit 0 = the error is in the unit's DC symbol
 struct PjdDevImState {
     unsigned long long err_key;        // ~0: none
     uint32_t flag_pos;                 // ~0: none
-    uint32_t pad_;                     // keeps the record 16 bytes (err_key is 64-bit); never read
+    uint32_t end_pos;                  // ~0: none
 };
 
 // why the parallel decoder flagged an image (PjdDevBatch::stats[PJD_STAT_FLAG0 + reason], counted per wave)

@@ -95,7 +95,7 @@ __global__ __launch_bounds__(256) void pjd_k_reset(PjdDevBatch B, const int32_t 
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i < B.n_images) {
         B.status[i] = status_init[i];
-        PjdDevImState st; st.err_key = ~0ull; st.flag_pos = 0xffffffffu;
+        PjdDevImState st; st.err_key = ~0ull; st.flag_pos = 0xffffffffu; st.end_pos = 0xffffffffu;
         B.imstate[i] = st;
     }
     if (i < 16) B.stats[i] = 0;
@@ -150,7 +150,8 @@ __global__ __launch_bounds__(256) void pjd_k_image_verdict(PjdDevBatch B)
     const PjdDevImState s = B.imstate[i];
     const bool has_err = s.err_key != ~0ull;
     const uint32_t err_pos = (uint32_t)(s.err_key >> 32);
-    if (s.flag_pos != 0xffffffffu && (!has_err || s.flag_pos <= err_pos)) B.status[i] = st | PJD_STW_NEEDS_EXACT;
+    const bool flagged = s.flag_pos != 0xffffffffu && s.flag_pos <= s.end_pos;      // not behind the picture's last unit (pjd_internal.h)
+    if (flagged && (!has_err || s.flag_pos <= err_pos)) B.status[i] = st | PJD_STW_NEEDS_EXACT;
     else if (has_err) B.status[i] = (int32_t)((s.err_key >> 1) & 7u);
 }
 
@@ -813,7 +814,8 @@ __global__ __launch_bounds__(PJD_DC_BLOCK) void pjd_k_group_dc(PjdDevBatch B, co
             const PjdDevImState s = B.imstate[i];
             const bool has_err = s.err_key != ~0ull;
             const uint32_t err_pos = (uint32_t)(s.err_key >> 32);
-            if (s.flag_pos != 0xffffffffu && (!has_err || s.flag_pos <= err_pos)) B.status[i] = st | PJD_STW_NEEDS_EXACT;
+            const bool flagged = s.flag_pos != 0xffffffffu && s.flag_pos <= s.end_pos;
+            if (flagged && (!has_err || s.flag_pos <= err_pos)) B.status[i] = st | PJD_STW_NEEDS_EXACT;
             else if (has_err) B.status[i] = (int32_t)((s.err_key >> 1) & 7u);
         }
     }

@@ -1286,6 +1286,8 @@ __global__ __launch_bounds__(PJD_HUFF_THREADS) PJD_HUFF_OCC_ATTR void pjd_k_huff
                 if (D == D_end) {
                     if (p > g.seg_end_bit) flag |= 1u << PJD_FLAG_SEGMENT;
                     if (has_next && ((p + 7) & ~7u) != g.seg_end_bit) flag |= 1u << PJD_FLAG_SEGMENT;
+                    // the picture's last unit ends here: what lanes that start behind it cannot resolve does not count (PjdDevImState::end_pos)
+                    if (last_seg && !flag) atomicMin(&B.imstate[hw.image].end_pos, g.base_bit + p);
                 } else {
                     if (S.p_img - g.base_bit != p || (S.cz >> 8) != c || (S.cz & 255) != z) flag |= 1u << PJD_FLAG_VERIFY;
                     if (D - D_in != S.cnt) flag |= 1u << PJD_FLAG_VERIFY;
