@@ -166,27 +166,17 @@ struct pjd_batch {
     PjdPlan plan;
     PjdBackForm back{};                  // the form of the plan's back end (pjd_kernels.h), set once by pjd_batch_create
     PjdDevBatch dev{};
-    // owned device allocations (non-const views of what `dev` points to)
-    PjdDevImage *d_images = nullptr;
-    PjdDevTset *d_tsets = nullptr;
-    PjdDevHuffRaw *d_raw = nullptr;
-    uint16_t *d_qtab = nullptr;
-    PjdDevSegment *d_segs = nullptr;
-    PjdDevSub *d_lanes = nullptr;
-    PjdDevHuffWave *d_hwaves = nullptr;
-    PjdDevHuffWg *d_hwgs = nullptr;
-    PjdDevIdctWg *d_iwgs = nullptr;
+    // device memory of the batch that `dev` does not name
     PjdDevIdctWg *d_iwgs_dense = nullptr;
     PjdDevIdctWg *d_iwgs_dense_std = nullptr, *d_cwgs_std = nullptr;   // PJD_F_LIBJPEG pictures: ranges of those on the dense path, work list of the colour launch
     uint8_t *d_planes = nullptr;         // ... and their component planes (null: the batch holds no such picture)
-    uint8_t *d_ecs = nullptr;
     uint32_t *d_seq_list = nullptr;      // images routed to the exact kernel up front ...
     uint64_t *d_seq_base = nullptr;      // ... and where each one's data units start in the dense scratch
     int32_t *d_status_init = nullptr;
     uint64_t *d_opstate = nullptr;       // wave_gen + wave_desc + ticket
     size_t opstate_bytes = 0;
     uint8_t *d_in = nullptr, *h_in = nullptr;   // the input blob (work lists + bitstreams) in HBM / page-locked memory
-    size_t in_bytes = 0;
+    size_t in_bytes = 0, images_off = 0;        // ... its size, and where the image records (dev.images) lie in it
     int32_t *h_status = nullptr;         // pinned
     unsigned long long *h_stats = nullptr;   // pinned, 16 words
     std::vector<uint32_t> seq_list;      // what d_seq_list holds
@@ -228,7 +218,6 @@ struct pjd_batch {
         else std::snprintf(buf, sizeof buf, "picture %zu", v);
         return buf;
     }
-    bool views_unresolved() const { return viewed && !resized; }     // views without a resample: nothing can deliver them
     // The resample (pjd_resize_plan.h): what the caller asked for so far, and what it resolves to.  Every setter adds its argument to
     // the request and resolves all of it again; the records lie in the page-locked halves of the pairs below, pjd_batch_upload sends them.
     PjdResizeSpec spec;
@@ -333,6 +322,54 @@ void set_result_offsets(pjd_batch *b, const std::vector<uint64_t> &off)
 {
     PjdDevResize *recs = (PjdDevResize *)b->rs.h;
     for (size_t i = 0; i < off.size(); i++) b->spec.pic[i].dst_off = recs[i].dst_off = off[i];
+}
+
+// The order of the calls that shape a batch (include/pjd.h, CALL ORDER): the stages, each passed at most once but for the
+// last two.  A new setter is a row here, at its place.
+enum Stage { ST_NONE = -1, ST_VIEWS, ST_RESIZE, ST_PAD, ST_ORIENTATION, ST_WINDOW, ST_FILTER, ST_NORMALIZE, ST_PAD_VALUE, ST_BIND, ST_UPLOAD, N_STAGES };
+struct StageRule {
+    const char *name;                          // the call, as the messages spell it
+    bool (*passed)(const pjd_batch *);         // has the batch been through it?
+    bool repeatable;
+    Stage needs[2];                            // the stages the call comes too early without ...
+    const char *missing;                       // ... and what a call that needs THIS stage says where it is missing ("": none needs it)
+};
+const StageRule STAGES[N_STAGES] = {
+    {"set_views",         [](const pjd_batch *b) { return b->viewed; },          false, {ST_NONE, ST_NONE},     ""},
+    {"set_resize",        [](const pjd_batch *b) { return b->resized; },         false, {ST_NONE, ST_NONE},     "no resize is set (pjd_batch_set_resize first)"},
+    {"set_resize_pad",    [](const pjd_batch *b) { return b->spec.pad_set; },    false, {ST_RESIZE, ST_NONE},   "the batch has no pad (pjd_batch_set_resize_pad first)"},
+    {"set_orientation",   [](const pjd_batch *b) { return b->spec.ori_set; },    false, {ST_RESIZE, ST_NONE},   ""},
+    {"set_resize_window", [](const pjd_batch *b) { return b->spec.win_set; },    false, {ST_RESIZE, ST_NONE},   ""},
+    {"set_resize_filter", [](const pjd_batch *b) { return b->spec.filter_set; }, false, {ST_RESIZE, ST_NONE},   ""},
+    {"set_normalize",     [](const pjd_batch *b) { return b->norm.dtype != 0; }, false, {ST_NONE, ST_NONE},     "the batch is not normalised (pjd_batch_set_normalize first)"},
+    {"set_pad_value",     [](const pjd_batch *b) { return b->pad_value_set; },   false, {ST_PAD, ST_NORMALIZE}, ""},
+    {"bind_output",       [](const pjd_batch *b) { return b->bound; },           true,  {ST_NONE, ST_NONE},     ""},
+    {"upload",            [](const pjd_batch *b) { return b->uploaded; },        true,  {ST_NONE, ST_NONE},     ""},
+};
+
+int refuse(pjd_batch *b, const std::string &why) { b->ctx->err = why; return PJD_E_STATE; }
+
+// May the call of stage `s` be made on the batch now?  Of several reasons why not, the first of: a stage it needs is missing, it was
+// made before, the earliest stage behind it that the batch has passed.
+int check_order(pjd_batch *b, Stage s)
+{
+    const StageRule &r = STAGES[s];
+    const std::string call = r.name;
+    for (Stage need : r.needs)
+        if (need != ST_NONE && !STAGES[need].passed(b)) return refuse(b, call + ": " + STAGES[need].missing);
+    if (!r.repeatable && r.passed(b)) return refuse(b, call + ": already set for this batch");
+    // the one exception: set_normalize brings a resize (the identity) where the batch has none, and set_views names the call that was made
+    if (s == ST_VIEWS && STAGES[ST_NORMALIZE].passed(b)) return refuse(b, call + " after set_normalize");
+    for (int t = s + 1; t < N_STAGES; t++)
+        if (STAGES[t].passed(b)) return refuse(b, call + " after " + STAGES[t].name);
+    return PJD_OK;
+}
+
+// views without a resample: nothing can deliver them, so `call` (upload, decode, capture, bind_output) is refused
+int check_views_resolved(pjd_batch *b, const char *call)
+{
+    if (!b->viewed || b->resized) return PJD_OK;
+    return refuse(b, std::string(call) + ": the batch has views but no resample (pjd_batch_set_resize or pjd_batch_set_normalize first)");
 }
 
 // the environment's plan mode and subsequence size, as pjd_open and pjd_plan_info both read them
@@ -470,29 +507,29 @@ int pjd_batch_create(pjd_ctx *ctx, const pjd_image_desc *images, int n_images, i
     // One input blob per batch: the work lists and tables, then the packed bitstreams.  It is assembled in page-locked
     // memory now (the caller's buffers can go away) and goes up in ONE copy: every separate copy of a pageable vector is
     // staged by the runtime and waits its turn behind other streams' transfers on the copy engine (profiles/r02_pcie.md).
-    rc = PJD_OK;
     auto fail = [&](int code) { pjd_batch_destroy(b); return code; };
     b->seq_list = P.seq_images;
     b->back = PjdBackForm{P.gray ? PJD_BACK_GRAY : (P.planar ? PJD_BACK_PLANAR : PJD_BACK_INTERLEAVED), P.scaled};
     std::vector<uint64_t> seq_base;
     std::vector<int32_t> st0(P.images.size(), 0);
     for (uint32_t i : b->seq_list) { st0[i] = PJD_STW_NEEDS_EXACT; seq_base.push_back(P.images[i].dense_base); }
-    struct Part { const void *src; size_t bytes, off; };
+    struct Part { const void *src; size_t bytes, off; void *dev; };        // dev: the batch's pointer to the part in HBM, set once d_in is known
     std::vector<Part> parts;
     size_t in_bytes = 0;
-    auto part = [&](const auto &vec, size_t min_count) {
+    auto part = [&](const auto &vec, size_t min_count, auto *&dev) {
         using T = std::remove_cv_t<std::remove_reference_t<decltype(vec[0])>>;
+        static_assert(std::is_same<T, std::remove_cv_t<std::remove_reference_t<decltype(*dev)>>>::value, "the list and its device pointer differ in type");
         const size_t off = in_bytes;
-        parts.push_back({vec.data(), vec.size() * sizeof(T), off});
+        parts.push_back({vec.data(), vec.size() * sizeof(T), off, &dev});
         in_bytes = (off + std::max(vec.size(), std::max(min_count, (size_t)1)) * sizeof(T) + 255) & ~(size_t)255;
         return off;
     };
-    const size_t o_images = part(P.images, 0), o_tsets = part(P.tsets, 0), o_raw = part(P.tables, 0), o_qtab = part(P.qtab, 0);
-    const size_t o_segs = part(P.segs, 0), o_lanes = part(P.subs, 0), o_hwaves = part(P.hwaves, 0), o_hwgs = part(P.hwgs, 0);
-    const size_t o_iwgs = part(P.iwgs, 0), o_iwgs_dense = part(P.iwgs_dense, 0), o_pscans = part(P.pscans, 0);
-    const size_t o_gimg = part(P.group_images, 0), o_iorder = part(P.iwg_order, 0);
-    const size_t o_iwgs_dense_std = P.libjpeg ? part(P.iwgs_dense_std, 0) : 0, o_cwgs_std = P.libjpeg ? part(P.cwgs_std, 0) : 0;
-    const size_t o_seq_list = part(b->seq_list, (size_t)n_images), o_seq_base = part(seq_base, (size_t)n_images), o_st0 = part(st0, (size_t)n_images);
+    b->images_off = part(P.images, 0, b->dev.images);
+    part(P.tsets, 0, b->dev.tsets); part(P.tables, 0, b->dev.raw_tables); part(P.qtab, 0, b->dev.qtab); part(P.segs, 0, b->dev.segs); part(P.subs, 0, b->dev.lanes);
+    part(P.hwaves, 0, b->dev.hwaves); part(P.hwgs, 0, b->dev.hwgs); part(P.iwgs, 0, b->dev.iwgs); part(P.iwgs_dense, 0, b->d_iwgs_dense); part(P.pscans, 0, b->dev.pscans);
+    part(P.group_images, 0, b->dev.group_images); part(P.iwg_order, 0, b->dev.iwg_order);
+    if (P.libjpeg) { part(P.iwgs_dense_std, 0, b->d_iwgs_dense_std); part(P.cwgs_std, 0, b->d_cwgs_std); }
+    part(b->seq_list, (size_t)n_images, b->d_seq_list); part(seq_base, (size_t)n_images, b->d_seq_base); part(st0, (size_t)n_images, b->d_status_init);
     const size_t o_ecs = in_bytes;
     in_bytes += P.ecs_buf_bytes;
     b->in_bytes = in_bytes;
@@ -519,59 +556,43 @@ int pjd_batch_create(pjd_ctx *ctx, const pjd_image_desc *images, int n_images, i
     if (pool_pin_alloc(ctx, (void **)&b->h_status, sizeof(int32_t) * (n_images + 1), b->pin_blocks) != PJD_OK) return fail(PJD_E_NOMEM);
     if (pool_pin_alloc(ctx, (void **)&b->h_stats, 16 * sizeof(unsigned long long), b->pin_blocks) != PJD_OK) return fail(PJD_E_NOMEM);
 
-    uint64_t &tot = b->device_bytes;
 #define TRY_RC(x) do { int rc_ = (x); if (rc_ != PJD_OK) return fail(rc_); } while (0)
-    auto dev_alloc = [&](pjd_ctx *c, auto *&dptr, size_t n, uint64_t &total) {
+    auto dev_alloc = [&](auto *&dptr, size_t n) {                  // n elements from the context's pool, counted in device_bytes
         using T = std::remove_reference_t<decltype(*dptr)>;
         if (n == 0) n = 1;
         void *p = nullptr;
-        const int r = pool_dev_alloc(c, &p, n * sizeof(T), b->dev_blocks);
+        const int r = pool_dev_alloc(ctx, &p, n * sizeof(T), b->dev_blocks);
         dptr = (T *)p;
-        total += n * sizeof(T);
+        b->device_bytes += n * sizeof(T);
         return r;
     };
     const size_t n_hwave = P.hwaves.size();
-    TRY_RC(dev_alloc(ctx, b->d_in, in_bytes, tot));
-    b->d_images = (PjdDevImage *)(b->d_in + o_images); b->d_tsets = (PjdDevTset *)(b->d_in + o_tsets);
-    b->d_raw = (PjdDevHuffRaw *)(b->d_in + o_raw); b->d_qtab = (uint16_t *)(b->d_in + o_qtab);
-    b->d_segs = (PjdDevSegment *)(b->d_in + o_segs); b->d_lanes = (PjdDevSub *)(b->d_in + o_lanes);
-    b->d_hwaves = (PjdDevHuffWave *)(b->d_in + o_hwaves); b->d_hwgs = (PjdDevHuffWg *)(b->d_in + o_hwgs);
-    b->d_iwgs = (PjdDevIdctWg *)(b->d_in + o_iwgs); b->d_iwgs_dense = (PjdDevIdctWg *)(b->d_in + o_iwgs_dense);
-    b->dev.pscans = (const PjdDevScan *)(b->d_in + o_pscans);
-    b->dev.group_images = (const uint32_t *)(b->d_in + o_gimg); b->dev.iwg_order = (const uint32_t *)(b->d_in + o_iorder);
-    b->d_seq_list = (uint32_t *)(b->d_in + o_seq_list); b->d_seq_base = (uint64_t *)(b->d_in + o_seq_base);
-    b->d_status_init = (int32_t *)(b->d_in + o_st0);
-    b->d_ecs = b->d_in + o_ecs;
-    if (P.libjpeg) {
-        b->d_iwgs_dense_std = (PjdDevIdctWg *)(b->d_in + o_iwgs_dense_std); b->d_cwgs_std = (PjdDevIdctWg *)(b->d_in + o_cwgs_std);
-        if (!P.gray) TRY_RC(dev_alloc(ctx, b->d_planes, (size_t)P.plane_bytes, tot));     // a grey batch has no component planes
-    }
-    TRY_RC(dev_alloc(ctx, b->dev.luts, (size_t)P.lut_buf_bytes, tot));
-    TRY_RC(dev_alloc(ctx, b->dev.words, (size_t)P.n_words, tot));
-    TRY_RC(dev_alloc(ctx, b->dev.coef, P.dense_du * 64, tot));
-    TRY_RC(dev_alloc(ctx, b->dev.ent, (size_t)P.n_ent, tot));
-    TRY_RC(dev_alloc(ctx, b->dev.lane_info, P.subs.size(), tot));
-    TRY_RC(dev_alloc(ctx, b->dev.lane_dc, P.subs.size(), tot));
-    TRY_RC(dev_alloc(ctx, b->dev.dc_blk, (size_t)P.n_dcblk * 8, tot));
-    TRY_RC(dev_alloc(ctx, b->dev.marks, P.iwgs.size(), tot));
-    TRY_RC(dev_alloc(ctx, b->dev.out, P.out_buf_bytes, tot));
-    TRY_RC(dev_alloc(ctx, b->dev.status, (size_t)n_images, tot));
-    TRY_RC(dev_alloc(ctx, b->dev.imstate, (size_t)n_images, tot));
+    TRY_RC(dev_alloc(b->d_in, in_bytes));
+    for (const Part &q : parts) { const uint8_t *p = b->d_in + q.off; std::memcpy(q.dev, &p, sizeof p); }      // every object pointer has this representation
+    b->dev.ecs = b->d_in + o_ecs;
+    if (P.libjpeg && !P.gray) TRY_RC(dev_alloc(b->d_planes, (size_t)P.plane_bytes));     // a grey batch has no component planes
+    TRY_RC(dev_alloc(b->dev.luts, (size_t)P.lut_buf_bytes));
+    TRY_RC(dev_alloc(b->dev.words, (size_t)P.n_words));
+    TRY_RC(dev_alloc(b->dev.coef, P.dense_du * 64));
+    TRY_RC(dev_alloc(b->dev.ent, (size_t)P.n_ent));
+    TRY_RC(dev_alloc(b->dev.lane_info, P.subs.size()));
+    TRY_RC(dev_alloc(b->dev.lane_dc, P.subs.size()));
+    TRY_RC(dev_alloc(b->dev.dc_blk, (size_t)P.n_dcblk * 8));
+    TRY_RC(dev_alloc(b->dev.marks, P.iwgs.size()));
+    TRY_RC(dev_alloc(b->dev.out, P.out_buf_bytes));
+    TRY_RC(dev_alloc(b->dev.status, (size_t)n_images));
+    TRY_RC(dev_alloc(b->dev.imstate, (size_t)n_images));
     // wave_gen [PJD_GENS][n_hwave], wave_desc [n_hwave] and the ticket live in one allocation, zeroed before every launch
     // ... and a ticket per picture group
     const size_t op_words = n_hwave * (PJD_GENS + 1) + 2 + PJD_MAX_GROUPS;      // 64-bit words
-    TRY_RC(dev_alloc(ctx, b->d_opstate, op_words, tot));
+    TRY_RC(dev_alloc(b->d_opstate, op_words));
     b->opstate_bytes = op_words * sizeof(uint64_t);
     b->dev.wave_gen = b->d_opstate;
     b->dev.wave_desc = b->d_opstate + n_hwave * PJD_GENS;
     b->dev.ticket = reinterpret_cast<uint32_t *>(b->d_opstate + n_hwave * (PJD_GENS + 1));
-    b->dev.dbg = nullptr;
-    if (std::getenv("PJD_DEBUG_STATS")) TRY_RC(dev_alloc(ctx, b->dev.dbg, n_hwave * 32, tot));
-    TRY_RC(dev_alloc(ctx, b->dev.stats, 16, tot));
+    if (std::getenv("PJD_DEBUG_STATS")) TRY_RC(dev_alloc(b->dev.dbg, n_hwave * 32));
+    TRY_RC(dev_alloc(b->dev.stats, 16));
 #undef TRY_RC
-    b->dev.images = b->d_images; b->dev.tsets = b->d_tsets; b->dev.raw_tables = b->d_raw; b->dev.qtab = b->d_qtab;
-    b->dev.segs = b->d_segs; b->dev.lanes = b->d_lanes; b->dev.hwaves = b->d_hwaves; b->dev.hwgs = b->d_hwgs; b->dev.iwgs = b->d_iwgs;
-    b->dev.ecs = b->d_ecs;
     b->dev.n_images = (uint32_t)n_images; b->dev.n_tsets = (uint32_t)P.tsets.size(); b->dev.n_lanes = (uint32_t)P.subs.size();
     b->dev.n_hwave = (uint32_t)n_hwave; b->dev.n_hwg = (uint32_t)P.hwgs.size();
     b->dev.n_iwg = (uint32_t)P.iwgs.size(); b->dev.n_dcblk = (uint32_t)P.n_dcblk;
@@ -591,7 +612,7 @@ int pjd_batch_upload(pjd_batch *b)
     if (!b) return PJD_E_ARG;
     pjd_ctx *ctx = b->ctx;
     PjdPlan &P = b->plan;
-    if (b->views_unresolved()) { ctx->err = "upload: the batch has views but no resample (pjd_batch_set_resize or pjd_batch_set_normalize first)"; return PJD_E_STATE; }
+    if (int rc = check_views_resolved(b, "upload")) return rc;
     hipSetDevice(ctx->device);
     hipStream_t s = ctx->stream;
     // asynchronous: the blob is page-locked and owned by the batch
@@ -768,6 +789,54 @@ int enqueue_decode(pjd_batch *b, pjd_timings *timings, bool use_groups)
     return PJD_OK;
 }
 
+// The temporary device blocks and events of one call: plain hipMalloc (rare paths with sizes of their own: never the context's pool),
+// all of it released when the owner goes out of scope, whichever way the call ends.
+struct Scratch {
+    std::vector<void *> blocks;
+    std::vector<hipEvent_t> events;
+    bool out_of_memory = false;                  // an alloc() failed
+    Scratch() = default;
+    Scratch(const Scratch &) = delete;
+    ~Scratch() { for (hipEvent_t e : events) (void)hipEventDestroy(e); for (void *p : blocks) (void)hipFree(p); }
+    template <class T> hipError_t alloc(T *&p, size_t bytes)
+    {
+        const hipError_t e = hipMalloc((void **)&p, bytes);
+        if (e == hipSuccess) blocks.push_back(p); else { p = nullptr; out_of_memory = true; }
+        return e;
+    }
+    hipEvent_t event()                           // null where the runtime gives none: the caller then does without
+    {
+        hipEvent_t e = nullptr;
+        if (hipEventCreate(&e) == hipSuccess) events.push_back(e); else e = nullptr;
+        return e;
+    }
+};
+
+// "Decode these pictures again with the exact kernel into a scratch of their own" (settle(), pjd_batch_download_coefficients).  list /
+// base [n]: the pictures, and where each one's units start in a dense scratch of `du` units; extra: a further array that goes up with
+// them (null: none); before: an event recorded in front of the exact kernel (null: none).  Enqueues the poison fills, the zero kernel,
+// the copies and the exact kernel on `dv` (dev with coef = the scratch); d[]: scratch, list, base, extra on the device, owned by `tmp`.
+hipError_t redo_exact(const pjd_batch *b, Scratch &tmp, const uint32_t *list, const uint64_t *base, size_t n, uint64_t du, const void *extra, size_t extra_bytes,
+                      hipEvent_t before, PjdDevBatch &dv, uint8_t *d[4])
+{
+    hipStream_t s = b->ctx->stream;
+    const void *h[4] = {nullptr, list, base, extra};
+    const size_t bytes[4] = {(size_t)du * 64 * sizeof(int16_t), n * sizeof(uint32_t), n * sizeof(uint64_t), extra_bytes};
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < 4 && e == hipSuccess; k++) { d[k] = nullptr; if (k == 0 || h[k]) e = tmp.alloc(d[k], bytes[k]); }
+    for (int k = 0; k < 4 && e == hipSuccess; k++) e = poison_dev(b->ctx, d[k], bytes[k]);
+    if (e != hipSuccess) return e;
+    pjd_launch_zero(s, d[0], bytes[0]);          // our own kernel, as everywhere on the decode path
+    e = hipGetLastError();
+    for (int k = 1; k < 4 && e == hipSuccess; k++) if (h[k]) e = hipMemcpyAsync(d[k], h[k], bytes[k], hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) return e;
+    dv = b->dev;
+    dv.coef = (int16_t *)d[0];
+    if (before) (void)hipEventRecord(before, s);
+    pjd_launch_huff_sequential(s, dv, (const uint32_t *)d[1], (const uint64_t *)d[2], (uint32_t)n);
+    return hipSuccess;
+}
+
 // After the stream drained: re-decode, with the exact kernel, every image the parallel decoder
 // flagged -- all of them in ONE launch, into a dense scratch allocated for just them (a rare path: corrupt
 // or otherwise irregular streams).  Runs on the GPU.  A shard is re-decoded over its own segment range.
@@ -807,34 +876,18 @@ int settle(pjd_batch *b)
     for (size_t i = 0; i < n; i++)
         if (!(b->h_status[i] & PJD_STW_NEEDS_EXACT) && (b->h_status[i] & 0xFF) != 0) b->n_entropy_errors++;
     if (!fb.empty()) {
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;
-        (void)hipEventCreate(&ev0); (void)hipEventCreate(&ev1);
-        int16_t *coef = nullptr; uint32_t *d_list = nullptr; uint64_t *d_base = nullptr; PjdDevIdctWg *d_wgs = nullptr;
         const size_t n_def = fb_wgs.size(), n_std = fb_wgs_std.size(), n_red = fb_wgs_red.size();
         fb_wgs.insert(fb_wgs.end(), fb_wgs_std.begin(), fb_wgs_std.end());       // one list on the device: the default ranges, then the others
         fb_wgs.insert(fb_wgs.end(), fb_wgs_red.begin(), fb_wgs_red.end());
-        auto cleanup = [&] { hipFree(coef); hipFree(d_list); hipFree(d_base); hipFree(d_wgs); };
-        if (hipMalloc((void **)&coef, du * 64 * sizeof(int16_t)) != hipSuccess || hipMalloc((void **)&d_list, fb.size() * sizeof(uint32_t)) != hipSuccess ||
-            hipMalloc((void **)&d_base, fb.size() * sizeof(uint64_t)) != hipSuccess || hipMalloc((void **)&d_wgs, fb_wgs.size() * sizeof(PjdDevIdctWg)) != hipSuccess) {
-            cleanup();
-            ctx->err = "hipMalloc failed for the exact-kernel scratch";
-            return PJD_E_NOMEM;
-        }
-        PjdDevBatch dv = b->dev;
-        dv.coef = coef;
-        hipError_t e = poison_dev(ctx, coef, du * 64 * sizeof(int16_t));
-        if (e == hipSuccess) e = poison_dev(ctx, d_list, fb.size() * sizeof(uint32_t));
-        if (e == hipSuccess) e = poison_dev(ctx, d_base, fb.size() * sizeof(uint64_t));
-        if (e == hipSuccess) e = poison_dev(ctx, d_wgs, fb_wgs.size() * sizeof(PjdDevIdctWg));
-        pjd_launch_zero(s, coef, du * 64 * sizeof(int16_t));      // our own kernel, as everywhere on the decode path
-        if (e == hipSuccess) e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(d_list, fb.data(), fb.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_base, fb_base.data(), fb_base.size() * sizeof(uint64_t), hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_wgs, fb_wgs.data(), fb_wgs.size() * sizeof(PjdDevIdctWg), hipMemcpyHostToDevice, s);
+        Scratch tmp;
+        hipEvent_t ev0 = tmp.event(), ev1 = tmp.event();          // exact_fallback_ms: from the exact kernel to the colour launch
+        PjdDevBatch dv;
+        uint8_t *d[4];                                            // the scratch, the list, the bases and the ranges on the device
+        hipError_t e = redo_exact(b, tmp, fb.data(), fb_base.data(), fb.size(), du, fb_wgs.data(), fb_wgs.size() * sizeof(PjdDevIdctWg), ev0, dv, d);
+        if (tmp.out_of_memory) { ctx->err = "hipMalloc failed for the exact-kernel scratch"; return PJD_E_NOMEM; }
         if (e == hipSuccess) {
-            if (ev0) (void)hipEventRecord(ev0, s);
-            pjd_launch_huff_sequential(s, dv, d_list, d_base, (uint32_t)fb.size());
-            launch_dense(s, b, dv, d_wgs, n_def, d_wgs + n_def, n_std, n_red, d_base);
+            const PjdDevIdctWg *d_wgs = (const PjdDevIdctWg *)d[3];
+            launch_dense(s, b, dv, d_wgs, n_def, d_wgs + n_def, n_std, n_red, (const uint64_t *)d[2]);
             // flagged pictures had their planes filled again: the colour launch (all flagged pictures of the batch: a rare path)
             if (n_std + n_red && !b->back.gray()) pjd_launch_colour_std(s, dv, b->d_cwgs_std, P.n_cwg_std, P.n_cwg_red, b->d_planes);
             if (ev1) (void)hipEventRecord(ev1, s);
@@ -845,9 +898,6 @@ int settle(pjd_batch *b)
         if (e == hipSuccess) e = hipMemcpyAsync(b->h_status, b->dev.status, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);        // also: the host vectors above are pageable
         if (e == hipSuccess && ev0 && ev1) (void)hipEventElapsedTime(&b->exact_fallback_ms, ev0, ev1);
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-        cleanup();
         if (e != hipSuccess) { ctx->err = std::string("exact-kernel fallback: ") + hipGetErrorString(e); return PJD_E_HIP; }
     }
     b->settled = true;
@@ -872,7 +922,7 @@ static bool device_idle_then_count(pjd_batch *b)
 int pjd_batch_decode(pjd_batch *b)
 {
     if (!b) return PJD_E_ARG;
-    if (b->views_unresolved()) { b->ctx->err = "decode: the batch has views but no resample (pjd_batch_set_resize or pjd_batch_set_normalize first)"; return PJD_E_STATE; }
+    if (int rc = check_views_resolved(b, "decode")) return rc;
     if (!b->uploaded) { b->ctx->err = "decode before upload"; return PJD_E_STATE; }
     hipSetDevice(b->ctx->device);
     const bool groups = !b->plan.groups.empty() && device_idle_then_count(b);
@@ -888,7 +938,7 @@ int pjd_batch_decode(pjd_batch *b)
 int pjd_batch_decode_timed(pjd_batch *b, pjd_timings *t)
 {
     if (!b || !t) return PJD_E_ARG;
-    if (b->views_unresolved()) { b->ctx->err = "decode: the batch has views but no resample (pjd_batch_set_resize or pjd_batch_set_normalize first)"; return PJD_E_STATE; }
+    if (int rc = check_views_resolved(b, "decode")) return rc;          // the timed decode speaks as the decode
     if (!b->uploaded) { b->ctx->err = "decode before upload"; return PJD_E_STATE; }
     hipSetDevice(b->ctx->device);
     std::memset(t, 0, sizeof *t);
@@ -898,7 +948,7 @@ int pjd_batch_decode_timed(pjd_batch *b, pjd_timings *t)
 int pjd_batch_capture(pjd_batch *b)
 {
     if (!b) return PJD_E_ARG;
-    if (b->views_unresolved()) { b->ctx->err = "capture: the batch has views but no resample (pjd_batch_set_resize or pjd_batch_set_normalize first)"; return PJD_E_STATE; }
+    if (int rc = check_views_resolved(b, "capture")) return rc;
     if (!b->uploaded) { b->ctx->err = "capture before upload"; return PJD_E_STATE; }
     pjd_ctx *ctx = b->ctx;
     hipSetDevice(ctx->device);
@@ -979,8 +1029,8 @@ int pjd_batch_bind_output(pjd_batch *b, void *device_base, uint64_t capacity, co
     if (!b) return PJD_E_ARG;
     pjd_ctx *ctx = b->ctx;
     PjdPlan &P = b->plan;
-    if (b->uploaded) { ctx->err = "bind_output after upload"; return PJD_E_STATE; }
-    if (b->views_unresolved()) { ctx->err = "bind_output: the batch has views but no resample (pjd_batch_set_resize or pjd_batch_set_normalize first)"; return PJD_E_STATE; }
+    if (int rc = check_order(b, ST_BIND)) return rc;
+    if (int rc = check_views_resolved(b, "bind_output")) return rc;
     if (!device_base) { ctx->err = "bind_output: null pointer"; return PJD_E_ARG; }
     if (P.out_format == PJD_OUT_BMP) { ctx->err = "bind_output: a BMP batch cannot be bound (its row padding relies on the batch's own zeroed buffer)"; return PJD_E_ARG; }
     hipSetDevice(ctx->device);
@@ -1026,7 +1076,7 @@ int pjd_batch_bind_output(pjd_batch *b, void *device_base, uint64_t capacity, co
     if (b->resized) {
         set_result_offsets(b, b->res_off);
     } else {
-        PjdDevImage *h_images = reinterpret_cast<PjdDevImage *>(b->h_in + ((uint8_t *)b->d_images - b->d_in));
+        PjdDevImage *h_images = reinterpret_cast<PjdDevImage *>(b->h_in + b->images_off);
         for (size_t i = 0; i < n; i++) P.images[i].out_off = h_images[i].out_off = ranges[i].first;
         b->dev.out = (uint8_t *)device_base;
     }
@@ -1105,10 +1155,7 @@ int pjd_batch_set_views(pjd_batch *b, const uint32_t *picture_of_view, uint32_t 
     if (!b) return PJD_E_ARG;
     pjd_ctx *ctx = b->ctx;
     PjdPlan &P = b->plan;
-    if (b->viewed) { ctx->err = "set_views: already set for this batch"; return PJD_E_STATE; }
-    if (b->resized) { ctx->err = b->norm.dtype != 0 ? "set_views after set_normalize" : "set_views after set_resize"; return PJD_E_STATE; }
-    if (b->bound) { ctx->err = "set_views after bind_output"; return PJD_E_STATE; }
-    if (b->uploaded) { ctx->err = "set_views after upload"; return PJD_E_STATE; }
+    if (int rc = check_order(b, ST_VIEWS)) return rc;
     if (!picture_of_view) { ctx->err = "set_views: null view array"; return PJD_E_ARG; }
     if (n_views == 0 || n_views > PJD_MAX_VIEWS) { ctx->err = "set_views: the number of views must be 1..PJD_MAX_VIEWS"; return PJD_E_ARG; }
     if (P.out_format == PJD_OUT_BMP) { ctx->err = "set_views: a BMP batch takes no views (it takes no resample: PJD_OUT_RGB8, PJD_OUT_RGB8_PLANAR or PJD_OUT_GRAY8)"; return PJD_E_ARG; }
@@ -1139,9 +1186,7 @@ int pjd_batch_set_resize(pjd_batch *b, const uint32_t *out_w, const uint32_t *ou
     if (!b) return PJD_E_ARG;
     pjd_ctx *ctx = b->ctx;
     PjdPlan &P = b->plan;
-    if (b->resized) { ctx->err = "set_resize: already set for this batch"; return PJD_E_STATE; }
-    if (b->bound) { ctx->err = "set_resize after bind_output"; return PJD_E_STATE; }
-    if (b->uploaded) { ctx->err = "set_resize after upload"; return PJD_E_STATE; }
+    if (int rc = check_order(b, ST_RESIZE)) return rc;
     if (!out_w || !out_h) { ctx->err = "set_resize: null size array"; return PJD_E_ARG; }
     if (P.out_format == PJD_OUT_BMP) { ctx->err = "set_resize: a BMP batch cannot be resized (PJD_OUT_RGB8 or PJD_OUT_RGB8_PLANAR)"; return PJD_E_ARG; }
     const size_t n = b->n_out();
@@ -1208,12 +1253,7 @@ int pjd_resize_bicubic_taps(uint32_t src_n, uint32_t dst_n, uint32_t i, uint32_t
 int pjd_batch_set_resize_filter(pjd_batch *b, int filter)
 {
     if (!b) return PJD_E_ARG;
-    pjd_ctx *ctx = b->ctx;
-    if (!b->resized) { ctx->err = "set_resize_filter: no resize is set (pjd_batch_set_resize first)"; return PJD_E_STATE; }
-    if (b->spec.filter_set) { ctx->err = "set_resize_filter: already set for this batch"; return PJD_E_STATE; }
-    if (b->norm.dtype != 0) { ctx->err = "set_resize_filter after set_normalize"; return PJD_E_STATE; }
-    if (b->bound) { ctx->err = "set_resize_filter after bind_output"; return PJD_E_STATE; }
-    if (b->uploaded) { ctx->err = "set_resize_filter after upload"; return PJD_E_STATE; }
+    if (int rc = check_order(b, ST_FILTER)) return rc;
     PjdResizeSpec spec = b->spec;
     spec.filter_set = true; spec.filter = filter;
     return apply_request(b, spec, "set_resize_filter");
@@ -1238,15 +1278,8 @@ int pjd_resize_window_check(uint32_t sw, uint32_t sh, uint32_t tw, uint32_t th, 
 int pjd_batch_set_orientation(pjd_batch *b, const uint8_t *orientation)
 {
     if (!b) return PJD_E_ARG;
-    pjd_ctx *ctx = b->ctx;
-    if (!b->resized) { ctx->err = "set_orientation: no resize is set (pjd_batch_set_resize first)"; return PJD_E_STATE; }
-    if (b->spec.ori_set) { ctx->err = "set_orientation: already set for this batch"; return PJD_E_STATE; }
-    if (b->spec.win_set) { ctx->err = "set_orientation after set_resize_window"; return PJD_E_STATE; }
-    if (b->spec.filter_set) { ctx->err = "set_orientation after set_resize_filter"; return PJD_E_STATE; }
-    if (b->norm.dtype != 0) { ctx->err = "set_orientation after set_normalize"; return PJD_E_STATE; }
-    if (b->bound) { ctx->err = "set_orientation after bind_output"; return PJD_E_STATE; }
-    if (b->uploaded) { ctx->err = "set_orientation after upload"; return PJD_E_STATE; }
-    if (!orientation) { ctx->err = "set_orientation: null orientation array"; return PJD_E_ARG; }
+    if (int rc = check_order(b, ST_ORIENTATION)) return rc;
+    if (!orientation) { b->ctx->err ="set_orientation: null orientation array"; return PJD_E_ARG; }
     PjdResizeSpec spec = b->spec;
     spec.ori_set = true; spec.orientation.assign(orientation, orientation + spec.pic.size());
     return apply_request(b, spec, "set_orientation");
@@ -1255,14 +1288,8 @@ int pjd_batch_set_orientation(pjd_batch *b, const uint8_t *orientation)
 int pjd_batch_set_resize_window(pjd_batch *b, const pjd_resize_window *win)
 {
     if (!b) return PJD_E_ARG;
-    pjd_ctx *ctx = b->ctx;
-    if (!b->resized) { ctx->err = "set_resize_window: no resize is set (pjd_batch_set_resize first)"; return PJD_E_STATE; }
-    if (b->spec.win_set) { ctx->err = "set_resize_window: already set for this batch"; return PJD_E_STATE; }
-    if (b->spec.filter_set) { ctx->err = "set_resize_window after set_resize_filter"; return PJD_E_STATE; }
-    if (b->norm.dtype != 0) { ctx->err = "set_resize_window after set_normalize"; return PJD_E_STATE; }
-    if (b->bound) { ctx->err = "set_resize_window after bind_output"; return PJD_E_STATE; }
-    if (b->uploaded) { ctx->err = "set_resize_window after upload"; return PJD_E_STATE; }
-    if (!win) { ctx->err = "set_resize_window: null record array"; return PJD_E_ARG; }
+    if (int rc = check_order(b, ST_WINDOW)) return rc;
+    if (!win) { b->ctx->err ="set_resize_window: null record array"; return PJD_E_ARG; }
     PjdResizeSpec spec = b->spec;
     spec.win_set = true; spec.win.assign(win, win + spec.pic.size());
     return apply_request(b, spec, "set_resize_window");
@@ -1277,14 +1304,7 @@ int pjd_batch_set_resize_pad(pjd_batch *b, const pjd_resize_pad *pad, const uint
 {
     if (!b) return PJD_E_ARG;
     pjd_ctx *ctx = b->ctx;
-    if (!b->resized) { ctx->err = "set_resize_pad: no resize is set (pjd_batch_set_resize first)"; return PJD_E_STATE; }
-    if (b->spec.pad_set) { ctx->err = "set_resize_pad: already set for this batch"; return PJD_E_STATE; }
-    if (b->spec.ori_set) { ctx->err = "set_resize_pad after set_orientation"; return PJD_E_STATE; }
-    if (b->spec.win_set) { ctx->err = "set_resize_pad after set_resize_window"; return PJD_E_STATE; }
-    if (b->spec.filter_set) { ctx->err = "set_resize_pad after set_resize_filter"; return PJD_E_STATE; }
-    if (b->norm.dtype != 0) { ctx->err = "set_resize_pad after set_normalize"; return PJD_E_STATE; }
-    if (b->bound) { ctx->err = "set_resize_pad after bind_output"; return PJD_E_STATE; }
-    if (b->uploaded) { ctx->err = "set_resize_pad after upload"; return PJD_E_STATE; }
+    if (int rc = check_order(b, ST_PAD)) return rc;
     if (!pad) { ctx->err = "set_resize_pad: null record array"; return PJD_E_ARG; }
     if (!fill) { ctx->err = "set_resize_pad: null fill"; return PJD_E_ARG; }
     PjdResizeSpec spec = b->spec;
@@ -1298,11 +1318,7 @@ int pjd_batch_set_pad_value(pjd_batch *b, const float value[3])
 {
     if (!b) return PJD_E_ARG;
     pjd_ctx *ctx = b->ctx;
-    if (!b->spec.pad_set) { ctx->err = "set_pad_value: the batch has no pad (pjd_batch_set_resize_pad first)"; return PJD_E_STATE; }
-    if (b->norm.dtype == 0) { ctx->err = "set_pad_value: the batch is not normalised (pjd_batch_set_normalize first)"; return PJD_E_STATE; }
-    if (b->pad_value_set) { ctx->err = "set_pad_value: already set for this batch"; return PJD_E_STATE; }
-    if (b->bound) { ctx->err = "set_pad_value after bind_output"; return PJD_E_STATE; }
-    if (b->uploaded) { ctx->err = "set_pad_value after upload"; return PJD_E_STATE; }
+    if (int rc = check_order(b, ST_PAD_VALUE)) return rc;
     if (!value) { ctx->err = "set_pad_value: null value array"; return PJD_E_ARG; }
     for (int c = 0; c < 3; c++)
         if (!finite_f32(value[c])) { ctx->err = "set_pad_value: the values must be finite"; return PJD_E_ARG; }
@@ -1327,9 +1343,7 @@ int pjd_batch_set_normalize(pjd_batch *b, int dtype, const float scale[3], const
     if (!b) return PJD_E_ARG;
     pjd_ctx *ctx = b->ctx;
     PjdPlan &P = b->plan;
-    if (b->norm.dtype != 0) { ctx->err = "set_normalize: already set for this batch"; return PJD_E_STATE; }
-    if (b->bound) { ctx->err = "set_normalize after bind_output"; return PJD_E_STATE; }
-    if (b->uploaded) { ctx->err = "set_normalize after upload"; return PJD_E_STATE; }
+    if (int rc = check_order(b, ST_NORMALIZE)) return rc;
     if (!scale || !bias) { ctx->err = "set_normalize: null constant array"; return PJD_E_ARG; }
     if (dtype != PJD_DT_F16 && dtype != PJD_DT_BF16 && dtype != PJD_DT_F32) { ctx->err = "set_normalize: unknown dtype (PJD_DT_F16, PJD_DT_BF16 or PJD_DT_F32)"; return PJD_E_ARG; }
     for (int c = 0; c < 3; c++)
@@ -1378,48 +1392,33 @@ void *pjd_host_alloc(uint64_t bytes)
 
 void pjd_host_free(void *p) { if (p) hipHostFree(p); }
 
-int pjd_batch_get_info(pjd_batch *b, pjd_batch_info *info)
+// everything of a pjd_batch_info that the plan alone decides, the rest zero (pjd_plan_info, pjd_batch_get_info)
+static void plan_info(const PjdPlan &P, pjd_batch_info *info)
 {
-    if (!b || !info) return PJD_E_ARG;
-    PjdPlan &P = b->plan;
-    hipSetDevice(b->ctx->device);
     std::memset(info, 0, sizeof *info);
     info->n_images = (int32_t)P.images.size();
-    info->pixels = P.pixels; info->ecs_bytes = P.ecs_bytes; info->out_bytes = b->res_out_bytes;
-    info->coef_bytes = P.n_ent * 2 + P.n_words * 4 + P.dense_du * 128;
+    info->pixels = P.pixels; info->ecs_bytes = P.ecs_bytes; info->out_bytes = P.out_bytes;
+    info->coef_bytes = P.n_ent * 2 + P.n_words * 4 + P.dense_du * 128;      // lane streams + transposed words + dense scratch
     info->n_data_units = P.n_du;
     info->n_subsequences = P.subs.size();
-    info->device_bytes = b->device_bytes;
-    info->n_sequential = (int32_t)b->seq_list.size();
-    info->n_fallback = b->n_fallback;
-    info->exact_fallback_ms = b->exact_fallback_ms;
-    info->n_entropy_errors = b->n_entropy_errors;
+    info->n_sequential = (int32_t)P.seq_images.size();
     info->sub_bytes = P.sub_bytes;
     info->plan_mode = (uint32_t)P.plan_mode;
     info->n_table_sets = (uint32_t)P.tsets.size();
     info->huff_lds_bytes = (uint32_t)(P.max_lut_bytes + PJD_HUFF_WAVES * (PJD_WAVE_LDS + PJD_PHASE_LDS) + 16);
     info->n_huff_waves = P.hwaves.size();
-    // on the batch's own stream into page-locked memory: a plain hipMemcpy would wait for every other stream of the
-    // device (it made the slots of the pipelined batcher run in lockstep, profiles/r02_pcie.md)
-    unsigned long long *st = b->h_stats;
-    if (b->decoded && hipMemcpyAsync(st, b->dev.stats, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost, b->ctx->stream) == hipSuccess &&
-        hipStreamSynchronize(b->ctx->stream) == hipSuccess) {
-        info->sync_rounds = st[0]; info->sync_lane_passes = st[1]; info->fix_rounds = st[2]; info->fix_lane_passes = st[3];
-        info->walks = st[PJD_STAT_WALKS]; info->walk_lanes = st[PJD_STAT_WALKS + 1];
-        for (int r = 0; r < PJD_FLAG_REASONS && r < 8; r++) info->flag_waves[r] = st[PJD_STAT_FLAG0 + r];
-        info->n_entries = st[PJD_STAT_ENTRIES];               // entries the lanes emitted in the last decode
-        info->n_steps = st[PJD_STAT_STEPS];                   // ... in this many steps of the write pass
-        info->lane_fill_x1024 = (uint32_t)st[PJD_STAT_FILL];  // the fullest lane region
-    }
     info->n_huff_workgroups = P.hwgs.size();
-    if (b->dev.dbg) {                        // PJD_DEBUG_STATS: what the runtime makes of the entropy decoder's LDS
-        int wg = 0;
-        size_t lds = 0;
-        if (pjd_huff_lanes_occupancy(b->dev, &wg, &lds) == hipSuccess)
-            std::fprintf(stderr, "[pjd waves] pjd_k_huff_lanes: %zu B of LDS per workgroup, %d workgroups per CU\n", lds, wg);
-    }
-    if (b->dev.dbg && b->decoded) {          // PJD_DEBUG_STATS: wave timeline of the last decode (units of 10 ns)
-        const size_t nw = P.hwaves.size();
+}
+
+// PJD_DEBUG_STATS: what the runtime makes of the entropy decoder's LDS, and the wave timeline of the last decode, to stderr
+static void print_wave_timeline(const pjd_batch *b)
+{
+    int wg = 0;
+    size_t lds = 0;
+    if (pjd_huff_lanes_occupancy(b->dev, &wg, &lds) == hipSuccess)
+        std::fprintf(stderr, "[pjd waves] pjd_k_huff_lanes: %zu B of LDS per workgroup, %d workgroups per CU\n", lds, wg);
+    if (b->decoded) {                        // wave timeline of the last decode (units of 10 ns)
+        const size_t nw = b->plan.hwaves.size();
         std::vector<uint32_t> d(nw * 32);
         if (hipMemcpy(d.data(), b->dev.dbg, d.size() * 4, hipMemcpyDeviceToHost) == hipSuccess && nw) {
             if (const char *dump = std::getenv("PJD_DEBUG_DUMP")) {          // the raw timeline (32 words per wave) for offline analysis
@@ -1462,6 +1461,29 @@ int pjd_batch_get_info(pjd_batch *b, pjd_batch_info *info)
                 }
         }
     }
+}
+
+int pjd_batch_get_info(pjd_batch *b, pjd_batch_info *info)
+{
+    if (!b || !info) return PJD_E_ARG;
+    hipSetDevice(b->ctx->device);
+    plan_info(b->plan, info);
+    info->out_bytes = b->res_out_bytes;                       // the results: resized, normalised or views where the batch has them
+    info->device_bytes = b->device_bytes;
+    info->n_fallback = b->n_fallback; info->exact_fallback_ms = b->exact_fallback_ms; info->n_entropy_errors = b->n_entropy_errors;
+    // on the batch's own stream into page-locked memory: a plain hipMemcpy would wait for every other stream of the
+    // device (it made the slots of the pipelined batcher run in lockstep, profiles/r02_pcie.md)
+    unsigned long long *st = b->h_stats;
+    if (b->decoded && hipMemcpyAsync(st, b->dev.stats, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost, b->ctx->stream) == hipSuccess &&
+        hipStreamSynchronize(b->ctx->stream) == hipSuccess) {
+        info->sync_rounds = st[0]; info->sync_lane_passes = st[1]; info->fix_rounds = st[2]; info->fix_lane_passes = st[3];
+        info->walks = st[PJD_STAT_WALKS]; info->walk_lanes = st[PJD_STAT_WALKS + 1];
+        for (int r = 0; r < PJD_FLAG_REASONS && r < 8; r++) info->flag_waves[r] = st[PJD_STAT_FLAG0 + r];
+        info->n_entries = st[PJD_STAT_ENTRIES];               // entries the lanes emitted in the last decode
+        info->n_steps = st[PJD_STAT_STEPS];                   // ... in this many steps of the write pass
+        info->lane_fill_x1024 = (uint32_t)st[PJD_STAT_FILL];  // the fullest lane region
+    }
+    if (b->dev.dbg) print_wave_timeline(b);
     return PJD_OK;
 }
 
@@ -1472,19 +1494,7 @@ int pjd_plan_info(const pjd_image_desc *images, int n_images, int out_format, pj
     std::string err;
     int rc = pjd_make_plan(images, n_images, out_format, P, err, env_sub_bytes(), env_plan_mode());      // as a context opened now would plan
     if (rc != PJD_OK) return rc;
-    std::memset(info, 0, sizeof *info);
-    info->n_images = (int32_t)P.images.size();
-    info->pixels = P.pixels; info->ecs_bytes = P.ecs_bytes; info->out_bytes = P.out_bytes;
-    info->coef_bytes = P.n_ent * 2 + P.n_words * 4 + P.dense_du * 128;      // as pjd_batch_get_info: lane streams + transposed words + dense scratch
-    info->n_data_units = P.n_du;
-    info->n_subsequences = P.subs.size();
-    info->n_sequential = (int32_t)P.seq_images.size();
-    info->sub_bytes = P.sub_bytes;
-    info->plan_mode = (uint32_t)P.plan_mode;
-    info->n_table_sets = (uint32_t)P.tsets.size();
-    info->huff_lds_bytes = (uint32_t)(P.max_lut_bytes + PJD_HUFF_WAVES * (PJD_WAVE_LDS + PJD_PHASE_LDS) + 16);
-    info->n_huff_waves = P.hwaves.size();
-    info->n_huff_workgroups = P.hwgs.size();
+    plan_info(P, info);
     return PJD_OK;
 }
 
@@ -1594,41 +1604,30 @@ int pjd_batch_download_coefficients(pjd_batch *b, int image, int16_t *out, uint6
     const uint64_t n16 = pjd_coefficients_size(g.width, g.height, (uint8_t)g.hs, (uint8_t)g.vs);
     if (capacity_int16 < n16) { ctx->err = "download_coefficients: buffer smaller than pjd_coefficients_size"; return PJD_E_ARG; }
     hipStream_t s = ctx->stream;
-    int16_t *d_out = nullptr, *scratch = nullptr;
-    uint32_t *d_list = nullptr; uint64_t *d_base = nullptr;
-    auto cleanup = [&] { hipFree(d_out); hipFree(scratch); hipFree(d_list); hipFree(d_base); };
-    if (hipMalloc((void **)&d_out, n16 * sizeof(int16_t)) != hipSuccess) { ctx->err = "hipMalloc failed (coefficients)"; return PJD_E_NOMEM; }
+    Scratch tmp;
+    int16_t *d_out = nullptr;
+    if (tmp.alloc(d_out, n16 * sizeof(int16_t)) != hipSuccess) { ctx->err = "hipMalloc failed (coefficients)"; return PJD_E_NOMEM; }
     hipError_t e = poison_dev(ctx, d_out, n16 * sizeof(int16_t));
     pjd_launch_zero(s, d_out, n16 * sizeof(int16_t));                  // 19200 int16 per DPU: a multiple of 16 bytes
     const uint32_t n_du = (g.last_mcu - g.first_mcu) * g.dus_per_mcu, first_du = g.first_mcu * g.dus_per_mcu;
     const bool routed = P.host[image].sequential;
     const bool fell_back = !routed && (b->h_status[image] & PJD_STW_NEEDS_EXACT);
+    const uint32_t one = (uint32_t)image; const uint64_t zero = 0;     // the fallback's list and base: read until the stream is drained below
     if (routed) {
         pjd_launch_coefdump_dense(s, b->dev, (uint32_t)image, b->dev.coef + g.dense_base * 64, first_du, n_du, d_out);
     } else if (fell_back) {
         // the scratch settle() used is gone: run the exact kernel for this one image again (its status word does not change)
-        const uint32_t one = (uint32_t)image; const uint64_t zero = 0;
-        if (hipMalloc((void **)&scratch, (size_t)n_du * 64 * sizeof(int16_t)) != hipSuccess || hipMalloc((void **)&d_list, sizeof one) != hipSuccess ||
-            hipMalloc((void **)&d_base, sizeof zero) != hipSuccess) { cleanup(); ctx->err = "hipMalloc failed (coefficients scratch)"; return PJD_E_NOMEM; }
-        if (e == hipSuccess) e = poison_dev(ctx, scratch, (size_t)n_du * 64 * sizeof(int16_t));
-        if (e == hipSuccess) e = poison_dev(ctx, d_list, sizeof one);
-        if (e == hipSuccess) e = poison_dev(ctx, d_base, sizeof zero);
-        pjd_launch_zero(s, scratch, (size_t)n_du * 64 * sizeof(int16_t));
-        if (e == hipSuccess) e = hipMemcpyAsync(d_list, &one, sizeof one, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_base, &zero, sizeof zero, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) {
-            PjdDevBatch dv = b->dev;
-            dv.coef = scratch;
-            pjd_launch_huff_sequential(s, dv, d_list, d_base, 1);
-            pjd_launch_coefdump_dense(s, dv, (uint32_t)image, scratch, first_du, n_du, d_out);
-        }
+        PjdDevBatch dv;
+        uint8_t *d[4];
+        if (e == hipSuccess) e = redo_exact(b, tmp, &one, &zero, 1, n_du, nullptr, 0, nullptr, dv, d);
+        if (tmp.out_of_memory) { ctx->err = "hipMalloc failed (coefficients scratch)"; return PJD_E_NOMEM; }
+        if (e == hipSuccess) pjd_launch_coefdump_dense(s, dv, (uint32_t)image, dv.coef, first_du, n_du, d_out);
     } else {
         pjd_launch_coefdump_lanes(s, b->dev, (uint32_t)image, g.n_iwg, d_out);
     }
     if (e == hipSuccess) e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, n16 * sizeof(int16_t), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    cleanup();
     if (e != hipSuccess) { ctx->err = std::string("download_coefficients: ") + hipGetErrorString(e); return PJD_E_HIP; }
     return PJD_OK;
 }
@@ -1664,10 +1663,11 @@ int pjd_exec_dpu_payload(pjd_ctx *ctx, const uint32_t *metadata, int16_t *mcus, 
         for (uint32_t c = 0; c < m[4]; c++) if ((m[7 + c] & 255) > 3) { ctx->err = "DPU metadata: quantisation table id > 3"; return PJD_E_ARG; }
     }
     hipSetDevice(ctx->device);
+    Scratch tmp;
     uint32_t *dm = nullptr; int16_t *dc = nullptr;
     const size_t mb = (size_t)n_dpus * 276 * 4, cb = (size_t)n_dpus * 19200 * 2;
-    HIP_TRY(ctx, hipMalloc((void **)&dm, mb));
-    if (hipMalloc((void **)&dc, cb) != hipSuccess) { hipFree(dm); ctx->err = "hipMalloc(mcus)"; return PJD_E_NOMEM; }
+    if (const hipError_t e = tmp.alloc(dm, mb)) { ctx->err = std::string("hipMalloc((void **)&dm, mb): ") + hipGetErrorString(e); return PJD_E_HIP; }
+    if (tmp.alloc(dc, cb) != hipSuccess) { ctx->err = "hipMalloc(mcus)"; return PJD_E_NOMEM; }
     int rc = PJD_OK;
     auto chk = [&](hipError_t e, const char *what) { if (e != hipSuccess && rc == PJD_OK) { ctx->err = std::string(what) + ": " + hipGetErrorString(e); rc = PJD_E_HIP; } };
     chk(poison_dev(ctx, dm, mb), "poison(metadata_buffer)");
@@ -1677,7 +1677,6 @@ int pjd_exec_dpu_payload(pjd_ctx *ctx, const uint32_t *metadata, int16_t *mcus, 
     if (rc == PJD_OK) { pjd_launch_dpu_payload(ctx->stream, dm, dc, n_dpus); chk(hipGetLastError(), "exec"); }
     chk(hipMemcpyAsync(mcus, dc, cb, hipMemcpyDeviceToHost, ctx->stream), "copy back");
     chk(hipStreamSynchronize(ctx->stream), "sync");
-    hipFree(dm); hipFree(dc);
     return rc;
 }
 
