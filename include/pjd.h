@@ -440,7 +440,9 @@ typedef struct pjd_batch_info {
                                           pair that one table lookup yields): n_entries / n_steps = symbols per step               */
     uint32_t lane_fill_x1024;          /* last decode: the fullest lane region, slots written x 1024 / its capacity (capacities are a
                                           bound computed from the picture's Huffman tables: never above 1024)                    */
-    uint32_t reserved2_;
+    uint32_t dc_plan;                  /* how the plan settles DC prediction across lanes.  Bits 0..7: the single chain's form, 0 the
+                                          batch-wide scan of three launches, 1 one workgroup per picture.  Bits 8..15: the picture
+                                          groups planned for an idle device (each settles its own pictures, one workgroup each), 0 if none */
 } pjd_batch_info;
 
 /* ---- context --------------------------------------------------------------- */

@@ -1408,6 +1408,7 @@ static void plan_info(const PjdPlan &P, pjd_batch_info *info)
     info->huff_lds_bytes = (uint32_t)(P.max_lut_bytes + PJD_HUFF_WAVES * (PJD_WAVE_LDS + PJD_PHASE_LDS) + 16);
     info->n_huff_waves = P.hwaves.size();
     info->n_huff_workgroups = P.hwgs.size();
+    info->dc_plan = (P.dc_per_picture ? 1u : 0u) | ((uint32_t)P.groups.size() << 8);      // PJD_MAX_GROUPS fits the eight bits
 }
 
 // PJD_DEBUG_STATS: what the runtime makes of the entropy decoder's LDS, and the wave timeline of the last decode, to stderr
