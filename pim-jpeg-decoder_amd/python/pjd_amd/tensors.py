@@ -36,20 +36,25 @@ was consuming them) -- stream order protects such a block on torch's stream only
 the allocation and before the library writes.  After the decode: Batch.sync() has drained the library's stream and settled the
 statuses (fallback re-decodes included), so the returned tensors are complete and safe to read on any stream.
 """
+import collections
+
 import pjd_amd
+
+
+def _copy_desc(d, mask, bits):
+    """A copy of descriptor d whose flag bits under `mask` are `bits`: the one place a descriptor is copied.  d is not written; the
+    copy shares its bitstream and table memory, which the caller keeps alive as for any batch."""
+    import ctypes
+    c = pjd_amd.ImageDesc()
+    ctypes.memmove(ctypes.byref(c), ctypes.byref(d), ctypes.sizeof(pjd_amd.ImageDesc))
+    c.flags = (int(d.flags) & ~mask) | bits
+    return c
 
 
 def libjpeg_descs(descs):
     """Copies of `descs` with F_LIBJPEG set (the picture libjpeg decodes, include/pjd.h); the caller's descriptors are not touched (the
     copies share their bitstream and table memory, as prescaled_descs' do).  No device."""
-    import ctypes
-    out = []
-    for d in descs:
-        c = pjd_amd.ImageDesc()
-        ctypes.memmove(ctypes.byref(c), ctypes.byref(d), ctypes.sizeof(pjd_amd.ImageDesc))
-        c.flags = int(d.flags) | pjd_amd.F_LIBJPEG
-        out.append(c)
-    return out
+    return [_copy_desc(d, pjd_amd.F_LIBJPEG, pjd_amd.F_LIBJPEG) for d in descs]
 
 
 def _libjpeg(descs, libjpeg, prescale=False, draft=False):
@@ -98,40 +103,45 @@ def _torch():
     return torch
 
 
-def _run(ctx, descs, out_format, capacity, offsets, device, resize=None, normalize=None, antialias=False, windows=None, interpolation="bilinear",
-         orientations=None, pads=None, fill=(0, 0, 0), pad_value=None, views=None):
-    """Create, (set the resize, its orientations, its windows, its filter, the normalisation,) bind to a fresh torch buffer, upload, decode, sync -> (buffer, batch offsets,
-    statuses).  The buffer is torch.uint8 whatever the elements are: torch aligns it far beyond an element."""
+# What one call asks of a batch, settled before the batch exists: the descriptors to decode and the output format; the capacity and the
+# offsets to bind (None: packed); then what the setters take, each None where its setter is not called -- views, sizes (set_resize), pads
+# with fill (set_resize_pad), orientations, windows, filter (set_resize_filter), normalize = (dtype, scale, bias), pad_value.
+_Request = collections.namedtuple("_Request", "descs out_format capacity offsets views sizes pads fill orientations windows filter normalize pad_value",
+                                  defaults=(None,) * 11)
+
+
+def _run(ctx, req, device):
+    """Create the batch of request `req`, make the setter calls it holds, bind to a fresh torch buffer, upload, decode, sync -> (buffer,
+    batch offsets, statuses).  The buffer is torch.uint8 whatever the elements are: torch aligns it far beyond an element."""
     torch = _torch()
-    with ctx.batch(descs, out_format) as b:
-        if views is not None:
-            b.set_views(views)                      # from here on every per-picture argument is per view; the statuses stay per picture
-        if resize is not None:
-            b.set_resize(resize)
-            if pads is not None:
-                b.set_resize_pad(pads, fill)
-            if orientations is not None:
-                b.set_orientation(orientations)
-            if windows is not None:
-                b.set_resize_window(windows)
-            if interpolation == "bicubic":
-                b.set_resize_filter(pjd_amd.RESIZE_BICUBIC)
-            elif antialias:
-                b.set_resize_filter(pjd_amd.RESIZE_ANTIALIAS)
-        if normalize is not None:
-            b.set_normalize(*normalize)
-            if pads is not None and pad_value is not None:
-                b.set_pad_value(pad_value)
-        cap = b.packed_size() if capacity is None else capacity
+    device = torch.device("cuda", ctx.device) if device is None else device
+    with ctx.batch(req.descs, req.out_format) as b:
+        if req.views is not None:
+            b.set_views(req.views)                  # from here on every per-picture argument is per view; the statuses stay per picture
+        if req.sizes is not None:
+            b.set_resize(req.sizes)
+            if req.pads is not None:
+                b.set_resize_pad(req.pads, req.fill)
+            if req.orientations is not None:
+                b.set_orientation(req.orientations)
+            if req.windows is not None:
+                b.set_resize_window(req.windows)
+            if req.filter is not None:
+                b.set_resize_filter(req.filter)
+        if req.normalize is not None:
+            b.set_normalize(*req.normalize)
+            if req.pads is not None and req.pad_value is not None:
+                b.set_pad_value(req.pad_value)
+        cap = b.packed_size() if req.capacity is None else req.capacity
         buf = torch.empty(max(cap, 1), dtype=torch.uint8, device=device)
         # the block may be a recycled one that work queued on torch's current stream still reads: order that work before ours
         torch.cuda.current_stream(device).synchronize()
-        b.bind_output(buf.data_ptr(), cap, offsets)
+        b.bind_output(buf.data_ptr(), cap, req.offsets)
         b.upload()
         b.decode()
         b.sync()                                    # the library's stream has drained, fallbacks are settled: readable on any stream
         st = b.statuses()
-        offs = [b.output_offset(i) for i in range(b.n if views is None else len(views))]
+        offs = [b.output_offset(i) for i in range(b.n if req.views is None else len(req.views))]
     return buf, offs, st
 
 
@@ -171,14 +181,9 @@ def drafted_descs(descs, size):
 def _scaled_copy(d, prescale, cw, ch, vw, vh):
     """A copy of descriptor d with the scale picked for a cw x ch source against a vw x vh target: the box filter's (prescale true) or
     libjpeg's own (prescale == "draft")."""
-    import ctypes
-    c = pjd_amd.ImageDesc()
-    ctypes.memmove(ctypes.byref(c), ctypes.byref(d), ctypes.sizeof(pjd_amd.ImageDesc))
     if prescale == "draft":
-        c.flags = (int(d.flags) & ~pjd_amd.F_LIBJPEG_SCALE_MASK) | pick_libjpeg_scale_flags(cw, ch, vw, vh)
-    else:
-        c.flags = (int(d.flags) & ~pjd_amd.F_SCALE_MASK) | pick_scale_flags(cw, ch, vw, vh)
-    return c
+        return _copy_desc(d, pjd_amd.F_LIBJPEG_SCALE_MASK, pick_libjpeg_scale_flags(cw, ch, vw, vh))
+    return _copy_desc(d, pjd_amd.F_SCALE_MASK, pick_scale_flags(cw, ch, vw, vh))
 
 
 def _draft_flags(draft):
@@ -205,16 +210,14 @@ def decode_to_tensors(ctx, descs, planar=True, device=None, orientations=None, l
     dflags = _draft_flags(draft)
     descs = _libjpeg(descs, libjpeg, draft=draft not in (False, None))
     if dflags:
-        for d in descs:
-            d.flags = (int(d.flags) & ~pjd_amd.F_LIBJPEG_SCALE_MASK) | dflags
-    torch = _torch()
-    device = torch.device("cuda", ctx.device) if device is None else device
+        descs = [_copy_desc(d, pjd_amd.F_LIBJPEG_SCALE_MASK, dflags) for d in descs]
     sizes = None
     if orientations is not None:
-        _orientations(orientations, len(descs))
+        if len(orientations) != len(descs):
+            raise ValueError("orientations: one entry per picture")
         sizes = [orient_hw(o, *output_hw(d)) for o, d in zip(orientations, descs)]
     fmt = pjd_amd.OUT_GRAY8 if gray else (pjd_amd.OUT_RGB8_PLANAR if planar else pjd_amd.OUT_RGB8)
-    buf, offs, st = _run(ctx, descs, fmt, None, None, device, resize=sizes, orientations=orientations)
+    buf, offs, st = _run(ctx, _Request(descs, fmt, sizes=sizes, orientations=orientations), device)
     out = []
     nc = 1 if gray else 3
     for i, (d, off) in enumerate(zip(descs, offs)):
@@ -233,10 +236,8 @@ def decode_to_batch_tensor(ctx, descs, device=None, libjpeg=False, gray=False):
     n, c, h, w = uniform_output_shape(descs)
     if gray:
         c = 1
-    torch = _torch()
-    device = torch.device("cuda", ctx.device) if device is None else device
     size = c * h * w
-    buf, _, st = _run(ctx, descs, pjd_amd.OUT_GRAY8 if gray else pjd_amd.OUT_RGB8_PLANAR, n * size, [i * size for i in range(n)], device)
+    buf, _, st = _run(ctx, _Request(descs, pjd_amd.OUT_GRAY8 if gray else pjd_amd.OUT_RGB8_PLANAR, n * size, [i * size for i in range(n)]), device)
     return buf.view(n, c, h, w), st
 
 
@@ -254,15 +255,8 @@ def pick_scale_flags(w, h, tw, th):
 def prescaled_descs(descs, size):
     """Copies of `descs` whose scale flags are pick_scale_flags for the target size = (H, W); the caller's descriptors are not
     touched (the copies share their bitstream and table memory, which the caller keeps alive as for any batch).  No device."""
-    import ctypes
     th, tw = size
-    out = []
-    for d in descs:
-        c = pjd_amd.ImageDesc()
-        ctypes.memmove(ctypes.byref(c), ctypes.byref(d), ctypes.sizeof(pjd_amd.ImageDesc))
-        c.flags = (int(d.flags) & ~pjd_amd.F_SCALE_MASK) | pick_scale_flags(d.width, d.height, tw, th)
-        out.append(c)
-    return out
+    return [_scaled_copy(d, True, d.width, d.height, tw, th) for d in descs]
 
 
 def center_crop_window(src_hw, resize_short, size):
@@ -306,13 +300,6 @@ def _tvh(o):
     return ((0, 0, 0), (0, 0, 1), (0, 1, 1), (0, 1, 0), (1, 0, 0), (1, 0, 1), (1, 1, 1), (1, 1, 0))[o - 1]
 
 
-def _orientations(orientations, n):
-    if len(orientations) != n:
-        raise ValueError("orientations: one entry per picture")
-    for o in orientations:
-        _tvh(o)
-
-
 def orient_hw(o, h, w):
     """(h, w) of a picture of (h, w) after orientation o: swapped for 5..8.  Its own inverse: stored -> upright and back.  Pure."""
     return (int(w), int(h)) if _tvh(o)[0] else (int(h), int(w))
@@ -339,94 +326,6 @@ def crop_to_stored(o, crop, W, H):
     if v:
         y = UH - y - h
     return (y, x, h, w) if t else (x, y, w, h)
-
-
-def _windowed(descs, size, prescale, crops, flips, resize_short):
-    """The descriptors to decode and the windows to set for crops / flips / resize_short (None, None: nothing asked).  The pre-scale
-    is chosen per picture with the CROP's size against the virtual target."""
-    th, tw = size
-    n = len(descs)
-    if crops is None and flips is None and resize_short is None:
-        return ((drafted_descs(descs, size) if prescale == "draft" else prescaled_descs(descs, size)) if prescale else descs), None
-    if crops is not None and resize_short is not None:
-        raise ValueError("crops and resize_short exclude each other")
-    for name, v in (("crops", crops), ("flips", flips)):
-        if v is not None and len(v) != n:
-            raise ValueError(f"{name}: one entry per picture")
-    run, windows = [], []
-    for i, d in enumerate(descs):
-        W, H = int(d.width), int(d.height)
-        win = {}
-        crop = crops[i] if crops is not None else None
-        if crop is not None:
-            x, y, w, h = (int(v) for v in crop)
-            if x < 0 or y < 0 or w < 1 or h < 1 or x + w > W or y + h > H:
-                raise ValueError(f"crops[{i}] = {tuple(crop)} is not inside the {W}x{H} picture")
-        if resize_short is not None:
-            win.update(center_crop_window((H, W), resize_short, size))
-        vw, vh = win.get("vw", tw), win.get("vh", th)
-        if prescale:
-            cw, ch = (crop[2], crop[3]) if crop is not None else (W, H)
-            d = _scaled_copy(d, prescale, cw, ch, vw, vh)
-        if crop is not None:
-            h_s, w_s = output_hw(d)
-            win["x"], win["y"], win["w"], win["h"] = window_at_scale(crop, _scale_log(d.flags), w_s, h_s)
-        if flips is not None and flips[i]:
-            win["flags"] = pjd_amd.RW_HFLIP
-        run.append(d)
-        windows.append(win or None)
-    return run, windows
-
-
-def _plan(descs, size, prescale, crops, flips, resize_short, orientations):
-    """(descriptors to decode, windows or None, orientations or None) of the resizing helpers."""
-    if orientations is None:
-        return _windowed(descs, size, prescale, crops, flips, resize_short) + (None,)
-    _orientations(orientations, len(descs))
-    return _windowed_oriented(descs, size, prescale, crops, flips, resize_short, [int(o) for o in orientations])
-
-
-def _windowed_oriented(descs, size, prescale, crops, flips, resize_short, orientations):
-    """_windowed where the pictures have orientations and crops / flips / resize_short speak about the UPRIGHT picture: crops and the
-    centre crop are mapped into the stored picture's coordinates (crop_to_stored), the virtual target is Q's (axes swapped for 5..8),
-    and a flip is folded into the orientation (orient_then_hflip): the windows' RW_HFLIP stays clear.  -> (descriptors, windows or
-    None, orientations to set)."""
-    th, tw = size
-    n = len(descs)
-    if crops is not None and resize_short is not None:
-        raise ValueError("crops and resize_short exclude each other")
-    for name, v in (("crops", crops), ("flips", flips)):
-        if v is not None and len(v) != n:
-            raise ValueError(f"{name}: one entry per picture")
-    run, windows, oris = [], [], []
-    for i, (d, o) in enumerate(zip(descs, orientations)):
-        W, H = int(d.width), int(d.height)
-        t = _tvh(o)[0]
-        qtw, qth = (th, tw) if t else (tw, th)            # Q's target: the delivered one with the axes swapped where o transposes
-        win = {}
-        crop = crops[i] if crops is not None else None
-        if crop is not None:
-            try:
-                crop = crop_to_stored(o, crop, W, H)
-            except ValueError:
-                raise ValueError(f"crops[{i}] = {tuple(crop)} is not inside the upright picture of the {W}x{H} one (orientation {o})")
-        if resize_short is not None:
-            cc = center_crop_window(orient_hw(o, H, W), resize_short, size)          # of the upright picture
-            svw, svh = (cc["vh"], cc["vw"]) if t else (cc["vw"], cc["vh"])           # Q's virtual target
-            ox, oy, _, _ = crop_to_stored(o, (cc["ox"], cc["oy"], tw, th), svw, svh)
-            win.update(vw=svw, vh=svh, ox=ox, oy=oy)
-        vw, vh = win.get("vw", qtw), win.get("vh", qth)
-        if prescale:
-            cw, ch = (crop[2], crop[3]) if crop is not None else (W, H)
-            d = _scaled_copy(d, prescale, cw, ch, vw, vh)
-        if crop is not None:
-            h_s, w_s = output_hw(d)
-            win["x"], win["y"], win["w"], win["h"] = window_at_scale(crop, _scale_log(d.flags), w_s, h_s)
-        win = {k: v for k, v in win.items() if k in ("x", "y", "w", "h") or v}
-        run.append(d)
-        windows.append(win or None)
-        oris.append(orient_then_hflip(o) if flips is not None and flips[i] else o)
-    return run, (windows if any(w is not None for w in windows) else None), oris
 
 
 def letterbox_plan(src_hw, size, mode="center"):
@@ -467,38 +366,66 @@ def _pad_value(pad_value):
     return vals
 
 
-def _plan_letterbox(descs, size, mode, prescale, crops, flips, resize_short, orientations):
-    """_plan for a letterboxed batch: the content of picture i is letterbox_plan of its UPRIGHT picture (of its crop, where it has one),
-    and everything _plan does happens per picture against that content size -- the pre-scale included.  -> (descriptors, windows or
-    None, orientations or None, pads)."""
-    if mode not in ("center", "topleft"):
-        raise ValueError(f"letterbox must be None, \"center\" or \"topleft\", not {mode!r}")
-    if resize_short is not None:
+def _plan_outputs(descs, size, prescale, crops, flips, orientations, resize_short=None, letterbox=None):
+    """The one planner of the resizing helpers -> (descriptors to decode, windows or None, orientations or None, pads or None), one entry
+    per output.  crops, flips and orientations have one entry per output or are None; everything speaks about the UPRIGHT picture, and
+    an absent orientation is orientation 1.  Per output: the crop is mapped into the stored picture (crop_to_stored); the centre crop
+    of resize_short is worked out; with a letterbox the content size -- letterbox_plan of the upright picture, or of its crop --
+    becomes the target; the pre-scale (prescale true, or "draft" for libjpeg's own) is picked from the crop's size (else the
+    picture's) against Q's virtual target, the axes swapped for orientations 5..8; the window is taken at the scale the descriptor
+    ended with.  A flip is RW_HFLIP in the window where no orientations were given, and folded into the orientation
+    (orient_then_hflip) where they were.  A window holds x, y, w, h iff there is a crop and every other field iff it is not zero."""
+    if letterbox not in (None, "center", "topleft"):
+        raise ValueError(f"letterbox must be None, \"center\" or \"topleft\", not {letterbox!r}")
+    if resize_short is not None and crops is not None:
+        raise ValueError("crops and resize_short exclude each other")
+    if resize_short is not None and letterbox is not None:
         raise ValueError("letterbox and resize_short exclude each other: one crops to the target, the other pads to it")
-    n = len(descs)
-    for name, v in (("crops", crops), ("flips", flips)):
-        if v is not None and len(v) != n:
+    for name, v in (("crops", crops), ("flips", flips), ("orientations", orientations)):
+        if v is not None and len(v) != len(descs):
             raise ValueError(f"{name}: one entry per picture")
-    if orientations is not None:
-        _orientations(orientations, n)
+    th, tw = size
     run, windows, oris, pads = [], [], [], []
     for i, d in enumerate(descs):
-        o = int(orientations[i]) if orientations is not None else 1
+        W, H = int(d.width), int(d.height)
+        o = 1 if orientations is None else int(orientations[i])
+        t = _tvh(o)[0]
+        UW, UH = (H, W) if t else (W, H)                  # the upright picture; below, its crop where there is one
+        win = {}
         crop = crops[i] if crops is not None else None
         if crop is not None:
-            if len(tuple(crop)) != 4 or int(crop[2]) < 1 or int(crop[3]) < 1:
-                raise ValueError(f"crops[{i}] = {tuple(crop)}: (x, y, w, h) with w, h >= 1")
-            uh, uw = int(crop[3]), int(crop[2])
-        else:
-            uh, uw = orient_hw(o, int(d.height), int(d.width))
-        ch, cw, left, top, right, bottom = letterbox_plan((uh, uw), size, mode)
-        r, w, oo = _plan([d], (ch, cw), prescale, None if crops is None else [crop], None if flips is None else [flips[i]], None,
-                         None if orientations is None else [o])
-        run.append(r[0])
-        windows.append(w[0] if w is not None else None)
-        oris.append(oo[0] if oo is not None else 1)
-        pads.append((left, top, right, bottom))
-    return (run, (windows if any(w is not None for w in windows) else None), (oris if orientations is not None else None), pads)
+            try:
+                crop = crop_to_stored(o, crop, W, H)
+            except ValueError:
+                raise ValueError(f"crops[{i}] = {tuple(crop)}: (x, y, w, h) with w, h >= 1, inside the upright {UW}x{UH} picture "
+                                 f"(the {W}x{H} one, orientation {o})")
+            UW, UH = (crop[3], crop[2]) if t else (crop[2], crop[3])
+        vw, vh = (th, tw) if t else (tw, th)              # Q's target: the delivered one with the axes swapped where o transposes
+        if resize_short is not None:
+            cc = center_crop_window((UH, UW), resize_short, size)
+            vw, vh = (cc["vh"], cc["vw"]) if t else (cc["vw"], cc["vh"])
+            ox, oy, _, _ = crop_to_stored(o, (cc["ox"], cc["oy"], tw, th), vw, vh)
+            win.update(vw=vw, vh=vh, ox=ox, oy=oy)
+        if letterbox is not None:
+            ch, cw, left, top, right, bottom = letterbox_plan((UH, UW), size, letterbox)
+            vw, vh = (ch, cw) if t else (cw, ch)
+            pads.append((left, top, right, bottom))
+        if prescale:
+            sw, sh = crop[2:] if crop is not None else (W, H)
+            d = _scaled_copy(d, prescale, sw, sh, vw, vh)
+        if crop is not None:
+            sh, sw = output_hw(d)
+            win["x"], win["y"], win["w"], win["h"] = window_at_scale(crop, _scale_log(d.flags), sw, sh)
+        flip = flips is not None and flips[i]
+        if flip and orientations is None:
+            win["flags"] = pjd_amd.RW_HFLIP
+        run.append(d)
+        windows.append({k: v for k, v in win.items() if v or k in ("x", "y", "w", "h")} or None)
+        oris.append(orient_then_hflip(o) if flip else o)
+    # windows that are all None are still set where the plain path was asked for any: a window array can select another resample kernel
+    asked = orientations is None and letterbox is None and not (crops is None and flips is None and resize_short is None)
+    return ((run if prescale else descs), (windows if asked or any(w is not None for w in windows) else None),
+            (oris if orientations is not None else None), (pads if letterbox is not None else None))
 
 
 def tile_views(h, w, th, tw):
@@ -547,35 +474,41 @@ def plan_views(descs, views, size, prescale=True, crops=None, flips=None, resize
     its own would, the least reduced of a picture's views wins (least_reduced_scale_flags), and every view's window is then taken at
     THAT scale (window_at_scale).  Pure: no device, no torch."""
     views = _views(views, len(descs))
-    vdescs = [descs[p] for p in views]
 
-    def plan(ds, ps):
-        if letterbox is not None:
-            return _plan_letterbox(ds, size, letterbox, ps, crops, flips, resize_short, orientations)
-        return _plan(ds, size, ps, crops, flips, resize_short, orientations) + (None,)
+    def plan(pics, ps):
+        return _plan_outputs([pics[p] for p in views], size, ps, crops, flips, orientations, resize_short, letterbox)
 
     pics = list(descs)
     if prescale:
-        import ctypes
         draft = prescale == "draft"
         mask = pjd_amd.F_LIBJPEG_SCALE_MASK if draft else pjd_amd.F_SCALE_MASK
-        picked = plan(vdescs, prescale)[0]                 # every view as a picture of its own
-        pics = []
-        for p, d in enumerate(descs):
-            c = pjd_amd.ImageDesc()
-            ctypes.memmove(ctypes.byref(c), ctypes.byref(d), ctypes.sizeof(pjd_amd.ImageDesc))
-            c.flags = (int(d.flags) & ~mask) | least_reduced_scale_flags([picked[v].flags for v in range(len(views)) if views[v] == p], draft)
-            pics.append(c)
-        vdescs = [pics[p] for p in views]
-    _, windows, oris, pads = plan(vdescs, False)           # the windows at the scale the pictures are decoded at
-    return pics, windows, oris, pads
+        picked = plan(descs, prescale)[0]                  # every view as a picture of its own
+        pics = [_copy_desc(d, mask, least_reduced_scale_flags([picked[v].flags for v in range(len(views)) if views[v] == p], draft))
+                for p, d in enumerate(descs)]
+    return (pics,) + plan(pics, False)[1:]                 # the windows at the scale the pictures are decoded at
 
 
-def _interpolation(name):
-    """The `interpolation` keyword of the resizing helpers, checked before anything is created."""
-    if name not in ("bilinear", "bicubic"):
-        raise ValueError(f"interpolation must be \"bilinear\" or \"bicubic\", not {name!r}")
-    return name
+def _resize_request(who, descs, size, out_format, prescale, antialias, crops, flips, resize_short, interpolation, orientations, libjpeg,
+                    letterbox, fill, draft, views):
+    """What the two resizing helpers (`who`) share, all of it before anything is created: the keywords are checked, the outputs are
+    planned (_plan_outputs, plan_views) -> the _Request of a batch of uint8 outputs of `size`, one after the other in one buffer."""
+    if interpolation not in ("bilinear", "bicubic"):
+        raise ValueError(f"interpolation must be \"bilinear\" or \"bicubic\", not {interpolation!r}")
+    if len(descs) == 0:
+        raise ValueError(f"{who}: no pictures")
+    descs = _libjpeg(descs, libjpeg, prescale, draft)
+    prescale = "draft" if draft else prescale
+    th, tw = int(size[0]), int(size[1])
+    gray = out_format == pjd_amd.OUT_GRAY8
+    fill = _fill(fill, gray)
+    if views is not None:
+        views = _views(views, len(descs))
+        run, windows, oris, pads = plan_views(descs, views, (th, tw), prescale, crops, flips, resize_short, orientations, letterbox)
+    else:
+        run, windows, oris, pads = _plan_outputs(descs, (th, tw), prescale, crops, flips, orientations, resize_short, letterbox)
+    n, plane = (len(descs) if views is None else len(views)), (1 if gray else 3) * th * tw
+    filter = pjd_amd.RESIZE_BICUBIC if interpolation == "bicubic" else pjd_amd.RESIZE_ANTIALIAS if antialias else None
+    return _Request(run, out_format, n * plane, [i * plane for i in range(n)], views, [(th, tw)] * n, pads, fill, oris, windows, filter)
 
 
 def decode_resized_batch_tensor(ctx, descs, size, prescale=True, device=None, antialias=False, crops=None, flips=None, resize_short=None,
@@ -625,27 +558,10 @@ def decode_resized_batch_tensor(ctx, descs, size, prescale=True, device=None, an
     entries (entry v speaks about picture views[v] as entry i speaks about picture i without views); resize_short and letterbox apply to
     every view.  The statuses stay per picture.  The pre-scale of a picture is the least reduced of what its views would pick
     (plan_views).  None: nothing changes."""
-    _interpolation(interpolation)
-    if len(descs) == 0:
-        raise ValueError("decode_resized_batch_tensor: no pictures")
-    descs = _libjpeg(descs, libjpeg, prescale, draft)
-    prescale = "draft" if draft else prescale
-    th, tw = int(size[0]), int(size[1])
-    fill, pads = _fill(fill, gray), None
-    if views is not None:
-        views = _views(views, len(descs))
-        run, windows, oris, pads = plan_views(descs, views, (th, tw), prescale, crops, flips, resize_short, orientations, letterbox)
-    elif letterbox is not None:
-        run, windows, oris, pads = _plan_letterbox(descs, (th, tw), letterbox, prescale, crops, flips, resize_short, orientations)
-    else:
-        run, windows, oris = _plan(descs, (th, tw), prescale, crops, flips, resize_short, orientations)
-    torch = _torch()
-    device = torch.device("cuda", ctx.device) if device is None else device
-    nc = 1 if gray else 3
-    n, plane = (len(descs) if views is None else len(views)), nc * th * tw
-    buf, _, st = _run(ctx, run, pjd_amd.OUT_GRAY8 if gray else pjd_amd.OUT_RGB8_PLANAR, n * plane, [i * plane for i in range(n)], device, resize=[(th, tw)] * n,
-                      antialias=antialias, windows=windows, interpolation=interpolation, orientations=oris, pads=pads, fill=fill, views=views)
-    return buf.view(n, nc, th, tw), st
+    req = _resize_request("decode_resized_batch_tensor", descs, size, pjd_amd.OUT_GRAY8 if gray else pjd_amd.OUT_RGB8_PLANAR, prescale, antialias,
+                          crops, flips, resize_short, interpolation, orientations, libjpeg, letterbox, fill, draft, views)
+    buf, _, st = _run(ctx, req, device)
+    return buf.view(len(req.sizes), 1 if gray else 3, *req.sizes[0]), st
 
 
 def normalize_constants(mean, std):
@@ -682,40 +598,24 @@ def decode_normalized_batch_tensor(ctx, descs, size, mean, std, dtype=None, chan
     sequence of length 1, fill and pad_value one number; it takes channels_last=False (one plane has no interleaved form).
     views: as in decode_resized_batch_tensor -- [V, C, H, W] of `dtype` (channels_last: the permuted view of [V, H, W, 3]), per-view crops,
     flips and orientations, per-picture statuses, every picture decoded once."""
-    _interpolation(interpolation)
     _gray_layout(gray, not channels_last)
-    if len(descs) == 0:
-        raise ValueError("decode_normalized_batch_tensor: no pictures")
-    descs = _libjpeg(descs, libjpeg, prescale, draft)
-    prescale = "draft" if draft else prescale
-    th, tw = int(size[0]), int(size[1])
     if gray:
         mean, std = _gray3(mean, "mean"), _gray3(std, "std")
         pad_value = None if pad_value is None else _gray3(pad_value, "pad_value")
     scale, bias = normalize_constants(mean, std)
-    fill, pad_value, pads = _fill(fill, gray), _pad_value(pad_value), None
+    pad_value = _pad_value(pad_value)
     if pad_value is not None and letterbox is None:
         raise ValueError("pad_value needs letterbox: without it there is no border")
-    plan = None
-    if views is not None:
-        views = _views(views, len(descs))
-        plan = plan_views(descs, views, (th, tw), prescale, crops, flips, resize_short, orientations, letterbox)
-        plan, pads = plan[:3], plan[3]
-    elif letterbox is not None:                            # the new keywords are checked before anything is touched; the others where they were
-        plan = _plan_letterbox(descs, (th, tw), letterbox, prescale, crops, flips, resize_short, orientations)
-        plan, pads = plan[:3], plan[3]
+    req = _resize_request("decode_normalized_batch_tensor", descs, size, pjd_amd.OUT_GRAY8 if gray else pjd_amd.OUT_RGB8 if channels_last else pjd_amd.OUT_RGB8_PLANAR,
+                          prescale, antialias, crops, flips, resize_short, interpolation, orientations, libjpeg, letterbox, fill, draft, views)
     torch = _torch()
     dtype = torch.float16 if dtype is None else dtype
     dts = {torch.float16: (pjd_amd.DT_F16, 2), torch.bfloat16: (pjd_amd.DT_BF16, 2), torch.float32: (pjd_amd.DT_F32, 4)}
     if dtype not in dts:
         raise ValueError("decode_normalized_batch_tensor: dtype must be torch.float16, torch.bfloat16 or torch.float32")
     dt, es = dts[dtype]
-    device = torch.device("cuda", ctx.device) if device is None else device
-    run, windows, oris = plan if plan is not None else _plan(descs, (th, tw), prescale, crops, flips, resize_short, orientations)
-    nc = 1 if gray else 3
-    n, pic = (len(descs) if views is None else len(views)), nc * th * tw * es
-    buf, _, st = _run(ctx, run, pjd_amd.OUT_GRAY8 if gray else pjd_amd.OUT_RGB8 if channels_last else pjd_amd.OUT_RGB8_PLANAR, n * pic, [i * pic for i in range(n)], device,
-                      resize=[(th, tw)] * n, normalize=(dt, scale, bias), antialias=antialias, windows=windows, interpolation=interpolation,
-                      orientations=oris, pads=pads, fill=fill, pad_value=pad_value, views=views)
+    req = req._replace(capacity=req.capacity * es, offsets=[o * es for o in req.offsets], normalize=(dt, scale, bias), pad_value=pad_value)
+    buf, _, st = _run(ctx, req, device)
+    n, (th, tw) = len(req.sizes), req.sizes[0]
     t = buf.view(dtype)
-    return (t.view(n, th, tw, 3).permute(0, 3, 1, 2) if channels_last else t.view(n, nc, th, tw)), st
+    return (t.view(n, th, tw, 3).permute(0, 3, 1, 2) if channels_last else t.view(n, 1 if gray else 3, th, tw)), st

@@ -216,7 +216,7 @@ def test_the_plan_of_the_tensor_helpers_is_orient_then_crop_then_flip():
         UH, UW = U.shape[:2]
         for flip in (False, True):
             x, y, w, h = 2, 1, UW - 4, UH - 3
-            run, wins, oris = tensors._plan([_desc(13, 9)], (h, w), False, [(x, y, w, h)], [flip], None, [o])
+            run, wins, oris = tensors._plan_outputs([_desc(13, 9)], (h, w), False, [(x, y, w, h)], [flip], [o])[:3]
             assert len(run) == 1 and not (wins[0] or {}).get("flags"), "the flip is folded into the orientation"
             got = om.oriented(P, wins[0], w, h, oris[0])
             want = U[y:y + h, x:x + w]
@@ -224,20 +224,20 @@ def test_the_plan_of_the_tensor_helpers_is_orient_then_crop_then_flip():
         # Resize(short side) + CenterCrop: the resize is the identity, the crop is torchvision's
         short = min(UH, UW)
         th, tw = UH - 3, UW - 2
-        run, wins, oris = tensors._plan([_desc(13, 9)], (th, tw), False, None, None, short, [o])
+        run, wins, oris = tensors._plan_outputs([_desc(13, 9)], (th, tw), False, None, None, [o], short)[:3]
         cc = tensors.center_crop_window((UH, UW), short, (th, tw))
         assert (cc["vw"], cc["vh"]) == (UW, UH)
         got = om.oriented(P, wins[0], tw, th, oris[0])
         assert np.array_equal(got, U[cc["oy"]:cc["oy"] + th, cc["ox"]:cc["ox"] + tw]), o
     # no orientations: the plan is what it was
-    run, wins, oris = tensors._plan([_desc(13, 9)], (4, 4), False, [(1, 1, 5, 5)], [True], None, None)
+    run, wins, oris = tensors._plan_outputs([_desc(13, 9)], (4, 4), False, [(1, 1, 5, 5)], [True], None)[:3]
     assert oris is None and wins == [dict(x=1, y=1, w=5, h=5, flags=1)]
     with pytest.raises(ValueError):
-        tensors._plan([_desc(13, 9)], (4, 4), False, None, None, None, [9])
+        tensors._plan_outputs([_desc(13, 9)], (4, 4), False, None, None, [9])
     with pytest.raises(ValueError):
-        tensors._plan([_desc(13, 9)], (4, 4), False, None, None, None, [1, 1])
+        tensors._plan_outputs([_desc(13, 9)], (4, 4), False, None, None, [1, 1])
     with pytest.raises(ValueError):
-        tensors._plan([_desc(13, 9)], (4, 4), False, [(0, 0, 13, 9)], None, None, [6])      # 13 x 9 is not inside the upright 9 x 13
+        tensors._plan_outputs([_desc(13, 9)], (4, 4), False, [(0, 0, 13, 9)], None, [6])      # 13 x 9 is not inside the upright 9 x 13
 
 
 # ---- the ABI -----------------------------------------------------------------------------------------------------------------------------

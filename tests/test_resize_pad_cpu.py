@@ -162,7 +162,7 @@ def test_the_letterbox_plan_of_the_tensor_helpers():
         U = om.orient(P, o)
         UH, UW = U.shape[:2]
         for flip in (False, True):
-            run, wins, oris, pads = tensors._plan_letterbox([_desc(13, 9)], (H, W), "center", False, None, [flip], None, [o])
+            run, wins, oris, pads = tensors._plan_outputs([_desc(13, 9)], (H, W), False, None, [flip], [o], None, "center")
             ch, cw, l, t, r, b = tensors.letterbox_plan((UH, UW), (H, W))
             assert pads == [(l, t, r, b)] and (cw, ch) == pm.content(W, H, pads[0])
             got = pm.padded(P, (wins or [None])[0], W, H, pads[0], (1, 2, 3), oris[0])
@@ -170,15 +170,15 @@ def test_the_letterbox_plan_of_the_tensor_helpers():
             assert np.array_equal(got, pm.paste(D[:, ::-1] if flip else D, W, H, pads[0], (1, 2, 3))), (o, flip)
         # a crop of the upright picture: the plan is the crop's, and at the crop's own size the content is the crop itself
         x, y, w, h = 1, 2, UW - 3, UH - 4
-        run, wins, oris, pads = tensors._plan_letterbox([_desc(13, 9)], (h + 3, w), "topleft", False, [(x, y, w, h)], None, None, [o])
+        run, wins, oris, pads = tensors._plan_outputs([_desc(13, 9)], (h + 3, w), False, [(x, y, w, h)], None, [o], None, "topleft")
         assert pads == [(0, 0, 0, 3)]                                                   # the width limits, the scale is 1
         got = pm.padded(P, wins[0], w, h + 3, pads[0], (9, 9, 9), oris[0])
         assert np.array_equal(got, pm.paste(U[y:y + h, x:x + w], w, h + 3, pads[0], (9, 9, 9))), o
     # no orientations: none are set; a flip is the window's flag
-    run, wins, oris, pads = tensors._plan_letterbox([_desc(13, 9), _desc(9, 13)], (12, 12), "center", False, None, [True, False], None, None)
+    run, wins, oris, pads = tensors._plan_outputs([_desc(13, 9), _desc(9, 13)], (12, 12), False, None, [True, False], None, None, "center")
     assert oris is None and wins == [dict(flags=pjd_amd.RW_HFLIP), None] and pads == [(0, 2, 0, 2), (2, 0, 2, 0)]
     # the pre-scale comes from the content size: 640 x 480 into 64 x 64 has a content of 64 x 48, so 1/8 (80 x 60) still covers it
-    run, _, _, pads = tensors._plan_letterbox([_desc(640, 480)], (64, 64), "center", True, None, None, None, None)
+    run, _, _, pads = tensors._plan_outputs([_desc(640, 480)], (64, 64), True, None, None, None, None, "center")
     assert pads == [(0, 8, 0, 8)] and int(run[0].flags) & pjd_amd.F_SCALE_MASK == tensors.pick_scale_flags(640, 480, 64, 48) == 3 << 4
 
 

@@ -200,7 +200,7 @@ def test_windowed_plan_uses_the_crop_for_the_prescale(monkeypatch):
     calls = []
     real = tensors.pick_scale_flags
     monkeypatch.setattr(tensors, "pick_scale_flags", lambda w, h, tw, th: calls.append((w, h, tw, th)) or real(w, h, tw, th))
-    run, wins = tensors._windowed(descs, (224, 224), True, [(100, 200, 1000, 900), None, (0, 0, 300, 300)], [False, True, True], None)
+    run, wins = tensors._plan_outputs(descs, (224, 224), True, [(100, 200, 1000, 900), None, (0, 0, 300, 300)], [False, True, True], None)[:2]
     assert calls == [(1000, 900, 224, 224), (2000, 1500, 224, 224), (300, 300, 224, 224)]
     assert [int(d.flags) >> 4 for d in run] == [2, 2, 0] and all(int(d.flags) == 0 for d in descs)
     assert wins[0] == {"x": 25, "y": 50, "w": 250, "h": 225}
@@ -208,15 +208,15 @@ def test_windowed_plan_uses_the_crop_for_the_prescale(monkeypatch):
     assert wins[2] == {"x": 0, "y": 0, "w": 300, "h": 300, "flags": pjd_amd.RW_HFLIP}
     # resize_short: the virtual target comes from the full-size picture, the pre-scale is picked against it
     calls.clear()
-    run, wins = tensors._windowed(descs[:1], (224, 224), True, None, None, 256)
+    run, wins = tensors._plan_outputs(descs[:1], (224, 224), True, None, None, None, 256)[:2]
     assert calls == [(2000, 1500, 341, 256)] and int(run[0].flags) >> 4 == 2
     assert wins == [{"vw": 341, "vh": 256, "ox": 58, "oy": 16}]
     # nothing asked: no windows, the plain pre-scale
-    run, wins = tensors._windowed(descs, (224, 224), False, None, None, None)
+    run, wins = tensors._plan_outputs(descs, (224, 224), False, None, None, None)[:2]
     assert wins is None and run is descs
     with pytest.raises(ValueError):
-        tensors._windowed(descs, (224, 224), False, [(0, 0, 10, 10)] * 3, None, 256)
+        tensors._plan_outputs(descs, (224, 224), False, [(0, 0, 10, 10)] * 3, None, None, 256)
     with pytest.raises(ValueError):
-        tensors._windowed(descs, (224, 224), False, [(1995, 0, 10, 10)] * 3, None, None)
+        tensors._plan_outputs(descs, (224, 224), False, [(1995, 0, 10, 10)] * 3, None, None)
     with pytest.raises(ValueError):
-        tensors._windowed(descs, (224, 224), False, None, [True], None)
+        tensors._plan_outputs(descs, (224, 224), False, None, [True], None)

@@ -101,7 +101,7 @@ def main():
         crops = [random_resized_crop(rng, int(d.width), int(d.height)) for d in descs["noprescale"]]
         flips = [i % 2 == 1 for i in range(n)]
         for pre in ("prescale", "noprescale"):
-            descs[pre + "_win"], windows[pre] = tensors._windowed(descs["noprescale"], (T, T), pre == "prescale", crops, flips, None)
+            descs[pre + "_win"], windows[pre] = tensors._plan_outputs(descs["noprescale"], (T, T), pre == "prescale", crops, flips, None)[:2]
     for pre, fmt, bound, antialias, windowed in kinds:
         key = f"{pre}_{fmt}" + ("_bound" if bound else "") + ("_aa" if antialias else "") + ("_win" if windowed else "")
         if windowed:
