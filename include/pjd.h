@@ -42,6 +42,9 @@
  *   (none: an addition)                                 pjd_batch_set_views + pjd_batch_n_outputs: several resampled outputs of one decoded
  *                                                       picture (two augmented views, multi-crop, FiveCrop, two resolutions, tiles): the
  *                                                       entropy decoder and the back end run once per picture, the resample once per view
+ *   (none: an addition)                                 pjd_batch_set_resize_affine + pjd_warp_tap + pjd_resize_affine_check: every output under
+ *                                                       an inverse 2 x 3 map of its own -- rotation, scale, shear, translation, a fill outside --
+ *                                                       in one launch (RandomRotation, RandomAffine, DALI warp_affine, RandAugment)
  *
  * Plain pointers and sizes only; no C++ or torch types.  Thread model: one
  * submitting thread per pjd_ctx (the reference has one consumer thread,
@@ -66,7 +69,8 @@ extern "C" {
  * no version: a caller that needs one of them checks for it by its symbols (pjd_libjpeg_idct is exported from the first library that
  * knows PJD_F_LIBJPEG; an older one ignores the bit).  Pad on decode (pjd_batch_set_resize_pad, pjd_batch_set_pad_value) changed no
  * struct either, so PJD_VERSION stays 6: a caller checks for it by the symbol pjd_resize_pad_check.  Views (pjd_batch_set_views)
- * changed no struct: a caller checks for them by the symbol pjd_batch_n_outputs.
+ * changed no struct: a caller checks for them by the symbol pjd_batch_n_outputs.  The affine warp (pjd_batch_set_resize_affine) changed
+ * none: a caller checks for it by the symbol pjd_warp_tap.
  * A caller built against another version must not pass its structs: check pjd_version() == PJD_VERSION after loading.     */
 #define PJD_VERSION 6
 
@@ -794,6 +798,63 @@ typedef struct pjd_resize_pad { uint32_t left, top, right, bottom; } pjd_resize_
 int  pjd_batch_set_resize_pad(pjd_batch *b, const pjd_resize_pad *pad /* n_images */, const uint8_t fill[3]);
 int  pjd_batch_set_pad_value(pjd_batch *b, const float value[3]);
 int  pjd_resize_pad_check(uint32_t out_w, uint32_t out_h, const pjd_resize_pad *pad);   /* host only, no device needed */
+/* ---- affine warp on decode: rotate, scale, shear and translate per output ------------------------------------------------------------ *
+ * pjd_batch_set_resize_affine: output i of a resized batch -- picture i, or view i after pjd_batch_set_views -- with target tw x th from
+ * pjd_batch_set_resize is read from its picture under six doubles m[i] = {m00, m01, m02, m10, m11, m12}: the INVERSE map, from target
+ * pixel centres to source pixel centres.  The one transform of a loader that is not separable -- every other setter of the resample is
+ * a per-axis tap computation -- and so a launch of its own, which writes the fill where the target looks outside the picture too.
+ *
+ * THE ARITHMETIC (normative).  P is the sw x sh source of pjd_batch_set_resize: the picture at its decode size, after PJD_F_SCALE_* /
+ * PJD_F_LIBJPEG_SCALE_*, grey behind an entropy-coding error.
+ * SOURCE POSITION.  Target pixel (i, j) -- column i, row j -- looks at u = m00 * (i + 1/2) + m01 * (j + 1/2) + m02 and
+ * v = m10 * (i + 1/2) + m11 * (j + 1/2) + m12; the centre of source pixel (x, y) is (x + 1/2, y + 1/2).
+ * FIXED POINT, Q40.  Each coefficient is a = llrint(m * 2^40): an IEEE double product with a power of two (exact), rounded to nearest
+ * even.  All further arithmetic is 64-bit two's-complement integer:
+ *     X  = a00 * (2i + 1) + a01 * (2j + 1) + 2 * a02 - 2^40       2 * (u - 1/2) in Q40
+ *     fx = (X + 2^32) >> 33                                      an arithmetic shift: u - 1/2 in 1/256 pixel, rounded to nearest
+ *     x0 = fx >> 8  (the floor: may be negative)        wx = fx & 255
+ * and Y, fy, y0, wy likewise from row 1 of the matrix.
+ * TAPS.  The four taps are (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1).  A tap with 0 <= x < sw and 0 <= y < sh reads
+ * P[c][y][x], any other tap reads fill[c].  The blend and its one rounding are those of pjd_batch_set_resize:
+ *     out = ((256 - wy) * ((256 - wx) * s00 + wx * s01) + wy * ((256 - wx) * s10 + wx * s11) + 32768) >> 16
+ * every product with operands within 24 bits.  This is grid_sample(mode="bilinear", padding_mode="zeros", align_corners=False) with
+ * torchvision's mask blend towards `fill`.
+ * LIMITS, checked on the quantised values: |a00|, |a01|, |a10|, |a11| <= 16 * 2^40 and |a02|, |a12| <= 2^18 * 2^40.  16 source pixels per
+ * target pixel is the 16x of the table-driven filters.  Why nothing wraps: i, j <= 65534, so 2i + 1 < 2^17 and
+ *     |X| <= 2^44 * 2^17 + 2^44 * 2^17 + 2 * 2^58 + 2^40 = 2^62 + 2^59 + 2^40 < 2^62.17,    |X + 2^32| < 2^62.3 < 2^63
+ * and |fx| < 2^29.3: from fx on 32 bits hold everything.
+ * CONSEQUENCES.  The identity matrix {1,0,0, 0,1,0} with tw = sw, th = sh reproduces P byte for byte: X = 2^40 * 2i, fx = 256 * i,
+ * every weight is 0, and a tap outside with weight 0 contributes nothing.  Integer translations, mirrors and quarter turns are exact
+ * permutations with `fill` where nothing maps: {0,-1,sw, 1,0,0} onto sh x sw is the quarter turn D[j][i] = P[i][sw - 1 - j].  A constant
+ * picture under a map that stays inside stays constant (the weights of a blend sum to 65536).
+ * ERROR BOUND.  Rounding fx is off by at most 1/512 pixel per axis.  Quantising the coefficients moves u by at most
+ * 2^-41 * (i + 1/2) + 2^-41 * (j + 1/2) + 2^-41 < 2^-41 * 2^17 + 2^-41 < 2^-23 pixel.  A bilinear sample changes by at most 255 levels
+ * per pixel of position on each axis, so the exact blend of the rounded position is within 255 * 2 * (1/512 + 2^-23) < 0.9963 levels
+ * of the blend at the exact position, before the one rounding: the result is within 1 level of the same filter in float64 rounded
+ * to nearest.
+ * ALIASING.  Plain bilinear aliases where the map shrinks by more than about 2x: as with pjd_batch_set_resize, pre-scale with
+ * PJD_F_SCALE_* and multiply the scale into the matrix.
+ *
+ * CALL ORDER.  After pjd_batch_set_resize, and after pjd_batch_set_views where used; before any pjd_batch_set_normalize / _bind_output /
+ * _upload / _capture / _decode; once: PJD_E_STATE otherwise, also when no resize is set.  It is an ALTERNATIVE to the per-axis request,
+ * not a layer on it: PJD_E_STATE on a batch that took pjd_batch_set_resize_pad, _set_orientation, _set_resize_window or
+ * _set_resize_filter, and those four return PJD_E_STATE on a batch that took this call -- each of them is a matrix the caller
+ * multiplies in.  PJD_E_ARG for a null array, a null fill, or a matrix pjd_resize_affine_check refuses (pjd_last_error names the
+ * picture, or "view <v> (picture <p>)"); the batch is then as it was and the call still open.
+ * COMPOSES WITH pjd_batch_set_normalize (fill is a sample like any other and goes through the fma: there is no pad value),
+ * pjd_batch_bind_output, views (one matrix per view), PJD_OUT_RGB8, PJD_OUT_RGB8_PLANAR and PJD_OUT_GRAY8 (grey reads fill[0]),
+ * PJD_F_LIBJPEG pictures, captured graphs, and the exact-kernel fallback of pjd_batch_sync, behind which the launch runs again.
+ * FROM THEN ON everything pjd_batch_set_resize promises holds.  Every decode writes every byte of every output's range and none outside,
+ * in ONE launch -- there is no border launch -- which pjd_batch_decode_timed names "warp".  The 48-byte record per output is counted in
+ * pjd_batch_info::device_bytes and sent by pjd_batch_upload.  A batch that never makes the call allocates, uploads and launches what
+ * it did before.
+ * pjd_warp_tap and pjd_resize_affine_check are host only and THE implementations: the inline the kernel runs, and the test the setter
+ * makes.  Both return PJD_E_ARG for a null matrix, a value that is not finite, a coefficient beyond the limits or a dimension outside
+ * 1..65535; pjd_warp_tap also for i or j at or above 65535.  Its outputs may be NULL.
+ * DETECTION.  No struct changed and PJD_VERSION stays 6: a caller checks for the symbol pjd_warp_tap.                              */
+int  pjd_batch_set_resize_affine(pjd_batch *b, const double (*m)[6] /* n outputs */, const uint8_t fill[3]);
+int  pjd_warp_tap(const double m[6], uint32_t i, uint32_t j, int64_t *x0, int64_t *y0, uint32_t *wx, uint32_t *wy);   /* host only */
+int  pjd_resize_affine_check(uint32_t sw, uint32_t sh, uint32_t tw, uint32_t th, const double m[6]);                /* host only */
 /* ---- normalised float output ------------------------------------------------------------------------------------------------- *
  * pjd_batch_set_normalize: the pictures of the batch leave the decode as floating-point elements, sample * scale[c] + bias[c] -- what
  * x.float().div(255).sub(mean).div(std).to(dtype) makes of the uint8 tensor, without that tensor ever existing.  The caller passes

@@ -227,6 +227,7 @@ struct pjd_batch {
     Pair win;                                    // form.windowed: PjdDevResizeWin[n_out]
     Pair pad;                                    // form.padded: PjdDevResizePad[n_out], then the prefix sum of their border lines [n_out + 1]
     Pair aa;                                     // a table-driven filter: PjdDevResizeAA[n_out], then the weight table
+    Pair warp;                                   // form.warp (pjd_batch_set_resize_affine): PjdDevWarp[n_out]
     PjdNormalize norm{};                         // pjd_batch_set_normalize: dtype != 0, the result holds elements of PJD_DT_SIZE(dtype) bytes
     uint8_t pad_fill[3] = {0, 0, 0};             // pjd_batch_set_resize_pad
     bool pad_value_set = false;                  // pjd_batch_set_pad_value
@@ -241,6 +242,14 @@ struct pjd_batch {
                                              form.windowed ? (const PjdDevResizeWin *)win.d : nullptr, form.oriented, spec.filter,
                                              (const PjdDevResizeAA *)aa.d, aa.d ? (const uint32_t *)(aa.d + n * sizeof(PjdDevResizeAA)) : nullptr, form.lds,
                                              form.padded ? (const PjdDevResizePad *)pad.d : nullptr, spec.channels});
+    }
+    // the affine warp of this batch (form.warp), in place of the two launches around it: it writes the fill too
+    void launch_warp(hipStream_t s) const
+    {
+        const size_t n = n_out();
+        const uint8_t *f = spec.affine_fill;
+        pjd_launch_warp(s, PjdWarpLaunch{dev.out, res_out, (const PjdDevResize *)rs.d, (const PjdDevWarp *)warp.d, (const uint32_t *)(rs.d + n * sizeof(PjdDevResize)), (uint32_t)n, form.tiles,
+                                         back.planes(), norm, (uint32_t)f[0] | ((uint32_t)f[1] << 8) | ((uint32_t)f[2] << 16), spec.channels});
     }
     // ... and the border of its padded pictures, behind it: the two write disjoint bytes
     void launch_pad(hipStream_t s) const
@@ -298,11 +307,13 @@ int commit_request(pjd_batch *b, PjdResizeSpec &spec, const PjdResizeWork &w)
     if (rc == PJD_OK && w.form.windowed) rc = take_pair(b, b->win, n * sizeof(PjdDevResizeWin));
     if (rc == PJD_OK && w.form.padded) rc = take_pair(b, b->pad, n * sizeof(PjdDevResizePad) + (n + 1) * sizeof(uint32_t));
     if (rc == PJD_OK && spec.filter != PJD_RESIZE_BILINEAR) rc = take_pair(b, b->aa, n * sizeof(PjdDevResizeAA) + w.tab.size() * sizeof(uint32_t));
+    if (rc == PJD_OK && w.form.warp) rc = take_pair(b, b->warp, n * sizeof(PjdDevWarp));
     if (rc != PJD_OK) return rc;
     put(b->rs, w.recs, w.tile_prefix);
     if (w.form.windowed) put(b->win, w.win);
     if (w.form.padded) put(b->pad, w.pad, w.line_prefix);
     if (spec.filter != PJD_RESIZE_BILINEAR) put(b->aa, w.aa, w.tab);
+    if (w.form.warp) put(b->warp, w.warp);
     b->spec = std::move(spec);
     b->form = w.form;
     return PJD_OK;
@@ -313,7 +324,7 @@ int apply_request(pjd_batch *b, PjdResizeSpec &spec, const char *setter)
 {
     PjdResizeWork w;
     const PjdResizeFault f = pjd_resize_resolve(spec, w);
-    if (!f.text.empty()) { b->ctx->err = std::string(setter) + ": " + f.text; return PJD_E_ARG; }
+    if (!f.text.empty()) { b->ctx->err = std::string(setter) + ": " + f.text; return f.state ? PJD_E_STATE : PJD_E_ARG; }
     return commit_request(b, spec, w);
 }
 
@@ -326,7 +337,7 @@ void set_result_offsets(pjd_batch *b, const std::vector<uint64_t> &off)
 
 // The order of the calls that shape a batch (include/pjd.h, CALL ORDER): the stages, each passed at most once but for the
 // last two.  A new setter is a row here, at its place.
-enum Stage { ST_NONE = -1, ST_VIEWS, ST_RESIZE, ST_PAD, ST_ORIENTATION, ST_WINDOW, ST_FILTER, ST_NORMALIZE, ST_PAD_VALUE, ST_BIND, ST_UPLOAD, N_STAGES };
+enum Stage { ST_NONE = -1, ST_VIEWS, ST_RESIZE, ST_PAD, ST_ORIENTATION, ST_WINDOW, ST_FILTER, ST_AFFINE, ST_NORMALIZE, ST_PAD_VALUE, ST_BIND, ST_UPLOAD, N_STAGES };
 struct StageRule {
     const char *name;                          // the call, as the messages spell it
     bool (*passed)(const pjd_batch *);         // has the batch been through it?
@@ -341,6 +352,7 @@ const StageRule STAGES[N_STAGES] = {
     {"set_orientation",   [](const pjd_batch *b) { return b->spec.ori_set; },    false, {ST_RESIZE, ST_NONE},   ""},
     {"set_resize_window", [](const pjd_batch *b) { return b->spec.win_set; },    false, {ST_RESIZE, ST_NONE},   ""},
     {"set_resize_filter", [](const pjd_batch *b) { return b->spec.filter_set; }, false, {ST_RESIZE, ST_NONE},   ""},
+    {"set_resize_affine", [](const pjd_batch *b) { return b->spec.affine_set; }, false, {ST_RESIZE, ST_NONE},   ""},
     {"set_normalize",     [](const pjd_batch *b) { return b->norm.dtype != 0; }, false, {ST_NONE, ST_NONE},     "the batch is not normalised (pjd_batch_set_normalize first)"},
     {"set_pad_value",     [](const pjd_batch *b) { return b->pad_value_set; },   false, {ST_PAD, ST_NORMALIZE}, ""},
     {"bind_output",       [](const pjd_batch *b) { return b->bound; },           true,  {ST_NONE, ST_NONE},     ""},
@@ -625,6 +637,7 @@ int pjd_batch_upload(pjd_batch *b)
     if (b->aa.d) HIP_TRY(ctx, hipMemcpyAsync(b->aa.d, b->aa.h, b->aa.bytes, hipMemcpyHostToDevice, s));             // ... and its weight table
     if (b->form.windowed) HIP_TRY(ctx, hipMemcpyAsync(b->win.d, b->win.h, b->win.bytes, hipMemcpyHostToDevice, s));  // ... and its source windows
     if (b->form.padded) HIP_TRY(ctx, hipMemcpyAsync(b->pad.d, b->pad.h, b->pad.bytes, hipMemcpyHostToDevice, s));    // ... and its canvases
+    if (b->form.warp) HIP_TRY(ctx, hipMemcpyAsync(b->warp.d, b->warp.h, b->warp.bytes, hipMemcpyHostToDevice, s));   // ... or its affine maps
     // What depends on the blob alone is made here, once per upload, behind its copy: the decode tables of every table set (the exact
     // path uses them too) and the lanes' word rows.  No kernel of a decode writes either, so every decode of
     // the resident batch -- launched or replayed from its graphs -- reads what this upload left.
@@ -708,6 +721,11 @@ void launch_dense(hipStream_t s, const pjd_batch *b, const PjdDevBatch &dv, cons
 void launch_resample(hipStream_t s, const pjd_batch *b, KernelTimer *kt)
 {
     if (!b->resized) return;
+    if (b->form.warp) {                                    // pjd_batch_set_resize_affine: the one launch, which writes the fill too
+        b->launch_warp(s);
+        if (kt) kt->mark("warp");
+        return;
+    }
     b->launch_resize(s);
     if (kt) kt->mark("resize");
     if (!b->form.padded) return;
@@ -1293,6 +1311,42 @@ int pjd_batch_set_resize_window(pjd_batch *b, const pjd_resize_window *win)
     PjdResizeSpec spec = b->spec;
     spec.win_set = true; spec.win.assign(win, win + spec.pic.size());
     return apply_request(b, spec, "set_resize_window");
+}
+
+int pjd_warp_tap(const double m[6], uint32_t i, uint32_t j, int64_t *x0, int64_t *y0, uint32_t *wx, uint32_t *wy)
+{
+    PjdDevWarp rec;
+    if (!m || i >= 65535u || j >= 65535u || pjd_warp_quantise(m, rec)) return PJD_E_ARG;
+    int32_t a, c;
+    uint32_t u, v;
+    pjd_warp_tap_calc(rec, i, j, a, c, u, v);
+    if (x0) *x0 = a;
+    if (y0) *y0 = c;
+    if (wx) *wx = u;
+    if (wy) *wy = v;
+    return PJD_OK;
+}
+
+int pjd_resize_affine_check(uint32_t sw, uint32_t sh, uint32_t tw, uint32_t th, const double m[6])
+{
+    return pjd_resize_affine_fault(sw, sh, tw, th, m) ? PJD_E_ARG : PJD_OK;
+}
+
+int pjd_batch_set_resize_affine(pjd_batch *b, const double (*m)[6], const uint8_t fill[3])
+{
+    if (!b) return PJD_E_ARG;
+    pjd_ctx *ctx = b->ctx;
+    if (int rc = check_order(b, ST_AFFINE)) return rc;
+    // what the batch took before decides first: the rule, and its text, are the resolver's
+    if (const char *other = pjd_resize_affine_excludes(b->spec)) return refuse(b, std::string("set_resize_affine after ") + other + ": the two exclude each other on one batch (multiply it into the matrix)");
+    if (!m) { ctx->err = "set_resize_affine: null matrix array"; return PJD_E_ARG; }
+    if (!fill) { ctx->err = "set_resize_affine: null fill"; return PJD_E_ARG; }
+    PjdResizeSpec spec = b->spec;
+    spec.affine_set = true;
+    spec.affine.resize(spec.pic.size());
+    for (size_t i = 0; i < spec.pic.size(); i++) std::memcpy(spec.affine[i].m, m[i], sizeof spec.affine[i].m);
+    std::memcpy(spec.affine_fill, fill, 3);
+    return apply_request(b, spec, "set_resize_affine");
 }
 
 int pjd_resize_pad_check(uint32_t out_w, uint32_t out_h, const pjd_resize_pad *pad)

@@ -574,3 +574,50 @@ struct PjdNormalize {
     int32_t dtype;
     float scale[3], bias[3];
 };
+
+// ---- affine warp (pjd_batch_set_resize_affine; the arithmetic is normative: include/pjd.h) ------------------------------------
+// The inverse map of one output in Q40, as the kernels of pjd_k_warp.hip read it beside the output's PjdDevResize (whose col_tiles
+// then counts tiles of PJD_WARP_COLS columns): row 0 of the matrix makes X = a00 * (2i + 1) + a01 * (2j + 1) + b0 for target pixel
+// (i, j), which is 2 * (u - 1/2) in Q40 -- b0 = 2 * a02 - 2^40 has the half pixel of both grids folded in -- and row 1 makes Y
+// likewise.  48 bytes.  Made by pjd_warp_quantise (pjd_resize_plan.cpp), which also holds the limits: |a00|, |a01|, |a10|, |a11| <=
+// 2^44 and |a02|, |a12| <= 2^58, so that with 2i + 1 < 2^17 + 2^7 (a lane past the last column or row of a tile still steps) every sum
+// stays below 2^62.3 in magnitude and no step of the 64-bit arithmetic wraps.
+struct PjdDevWarp {
+    int64_t a00, a01, b0;
+    int64_t a10, a11, b1;
+};
+// A tile of the warp launch: one wave, PJD_WARP_LX lanes along a row with PJD_RS_PX adjacent pixels each and 64 / PJD_WARP_LX lanes down,
+// every lane PJD_WARP_RPL rows that lie PJD_WARP_LY apart.  32 columns x 32 rows, and one load instruction of the wave covers 32 x 8
+// target pixels: its footprint in the source is as compact under a quarter turn as under none, where the resize tile (PJD_WARP_LX 64,
+// PJD_WARP_RPL 8: 256 x 8) touches 256 source rows.  Five shapes were measured (profiles/affine_warp.md); both are build options for
+// tools/warp_probe.py.
+#ifndef PJD_WARP_LX
+#define PJD_WARP_LX   8
+#endif
+#define PJD_WARP_LY   (64 / PJD_WARP_LX)
+#ifndef PJD_WARP_RPL
+#define PJD_WARP_RPL  4
+#endif
+#define PJD_WARP_COLS (PJD_WARP_LX * PJD_RS_PX)
+#define PJD_WARP_ROWS (PJD_WARP_LY * PJD_WARP_RPL)
+#define PJD_WARP_WAVES 4               // waves (tiles) per workgroup
+// X (or Y) of target pixel (i, j) from one row of the record.  Unsigned sums: the same bits, and no signed overflow to reason about.
+static inline __host__ __device__ int64_t pjd_warp_pos(int64_t a0, int64_t a1, int64_t b, uint32_t i, uint32_t j)
+{
+    return (int64_t)((uint64_t)a0 * (uint64_t)(2u * i + 1u) + (uint64_t)a1 * (uint64_t)(2u * j + 1u) + (uint64_t)b);
+}
+// X -> the source position u - 1/2 in 1/256 pixel, rounded to nearest: its floor p0 (may be negative) and the weight w of p0 + 1 in
+// 1/256 (0..255).  |X| < 2^62.3, so the position fits 32 bits.
+static inline __host__ __device__ void pjd_warp_fix(int64_t X, int32_t &p0, uint32_t &w)
+{
+    const int32_t f = (int32_t)((X + ((int64_t)1 << 32)) >> 33);
+    p0 = f >> 8;
+    w = (uint32_t)f & 255u;
+}
+// THE implementation of a warp tap: pjd_warp_tap exports it to the host, the body of the warp kernels (pjd_k_warp_body.h) runs
+// pjd_warp_pos once per row of a lane, steps it by 2 * a00 and 2 * a10 per pixel -- the same sum, term by term -- and calls pjd_warp_fix.
+static inline __host__ __device__ void pjd_warp_tap_calc(const PjdDevWarp &m, uint32_t i, uint32_t j, int32_t &x0, int32_t &y0, uint32_t &wx, uint32_t &wy)
+{
+    pjd_warp_fix(pjd_warp_pos(m.a00, m.a01, m.b0, i, j), x0, wx);
+    pjd_warp_fix(pjd_warp_pos(m.a10, m.a11, m.b1, i, j), y0, wy);
+}

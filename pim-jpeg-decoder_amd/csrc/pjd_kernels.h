@@ -118,6 +118,22 @@ struct PjdBorderLaunch {
     uint32_t channels = 3;               // 3, or 1 for a grey batch: planar with ONE plane, n_lines counts H lines a canvas and fill.d[0] alone is read
 };
 void pjd_launch_resize_border(hipStream_t s, const PjdBorderLaunch &a);
+// ---- affine warp on decode (pjd_k_warp.hip; pjd_batch_set_resize_affine): every output from its picture in `src` under its own inverse
+// map warp[i] (pjd_internal.h) into `dst`, one launch that writes every byte; recs and tile_prefix as above, but in tiles of
+// PJD_WARP_COLS x PJD_WARP_ROWS; fill: R | G << 8 | B << 16 (a grey batch: the low byte), a sample like any other under norm
+struct PjdWarpLaunch {
+    const uint8_t *src;
+    uint8_t *dst;
+    const PjdDevResize *recs;
+    const PjdDevWarp *warp;
+    const uint32_t *tile_prefix;
+    uint32_t n_images, n_tiles;
+    bool planar;
+    PjdNormalize norm;
+    uint32_t fill;
+    uint32_t channels = 3;
+};
+void pjd_launch_warp(hipStream_t s, const PjdWarpLaunch &a);
 // ---- stage-level parity (pjd_k_coefdump.hip): coefficients in the reference's MCU_buffer layout; `out` is zeroed by the caller
 void pjd_launch_coefdump_lanes(hipStream_t s, const PjdDevBatch &b, uint32_t image, uint32_t n_iwg, int16_t *out);
 void pjd_launch_coefdump_dense(hipStream_t s, const PjdDevBatch &b, uint32_t image, const int16_t *scratch, uint32_t first_du, uint32_t n_du, int16_t *out);

@@ -2,6 +2,7 @@
 #include "pjd_resize_plan.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <map>
@@ -57,6 +58,7 @@ struct AxisTables {
     }
 };
 
+uint64_t warp_tiles_of(uint32_t tw, uint32_t th) { return (uint64_t)((tw + PJD_WARP_COLS - 1) / PJD_WARP_COLS) * ((th + PJD_WARP_ROWS - 1) / PJD_WARP_ROWS); }
 uint64_t tiles_of(uint32_t tw, uint32_t th) { return (uint64_t)((tw + PJD_RS_COLS - 1) / PJD_RS_COLS) * ((th + PJD_RS_ROWS - 1) / PJD_RS_ROWS); }
 
 // binary32 -> binary16 bits, round to nearest even, subnormals kept, overflow to infinity (the host side of PJD_DT_F16; the device
@@ -122,6 +124,37 @@ const char *pjd_resize_pad_fault(uint32_t out_w, uint32_t out_h, const pjd_resiz
     return nullptr;
 }
 
+// The limits are those of include/pjd.h, checked on the quantised values: |a| <= 16 * 2^40 for the four linear coefficients (16 source
+// pixels per target pixel, the 16x of the table-driven filters), |a| <= 2^18 * 2^40 for the two translations.  m * 2^40 is exact in
+// binary64 (a power of two), llrint rounds it to nearest even once; the magnitude is bounded before the conversion, so it is defined.
+const char *pjd_warp_quantise(const double m[6], PjdDevWarp &out)
+{
+    int64_t a[6];
+    for (int k = 0; k < 6; k++) {
+        if (!std::isfinite(m[k])) return "the matrix has a value that is not finite";
+        const bool shift = k == 2 || k == 5;
+        if (std::fabs(m[k]) > (shift ? 262145.0 : 17.0)) return shift ? "a translation is beyond 2^18 pixels in magnitude" : "a coefficient of the linear part is beyond 16 in magnitude";
+        a[k] = (int64_t)std::llrint(std::ldexp(m[k], 40));
+        const int64_t lim = shift ? (int64_t)1 << 58 : (int64_t)1 << 44;
+        if (a[k] > lim || a[k] < -lim) return shift ? "a translation is beyond 2^18 pixels in magnitude" : "a coefficient of the linear part is beyond 16 in magnitude";
+    }
+    out = PjdDevWarp{a[0], a[1], 2 * a[2] - ((int64_t)1 << 40), a[3], a[4], 2 * a[5] - ((int64_t)1 << 40)};
+    return nullptr;
+}
+
+const char *pjd_resize_affine_fault(uint32_t sw, uint32_t sh, uint32_t tw, uint32_t th, const double m[6])
+{
+    if (sw == 0 || sw > 65535u || sh == 0 || sh > 65535u || tw == 0 || tw > 65535u || th == 0 || th > 65535u) return "picture and target sizes must be 1..65535";
+    if (!m) return "null matrix";
+    PjdDevWarp rec;
+    return pjd_warp_quantise(m, rec);
+}
+
+const char *pjd_resize_affine_excludes(const PjdResizeSpec &spec)
+{
+    return spec.pad_set ? "set_resize_pad" : spec.ori_set ? "set_orientation" : spec.win_set ? "set_resize_window" : spec.filter_set ? "set_resize_filter" : nullptr;
+}
+
 PjdResizeFault pjd_resize_resolve(const PjdResizeSpec &spec, PjdResizeWork &out)
 {
     out = PjdResizeWork{};
@@ -131,6 +164,28 @@ PjdResizeFault pjd_resize_resolve(const PjdResizeSpec &spec, PjdResizeWork &out)
     if (!table && spec.filter != PJD_RESIZE_BILINEAR) return PjdResizeFault{"unknown filter (PJD_RESIZE_BILINEAR, PJD_RESIZE_ANTIALIAS or PJD_RESIZE_BICUBIC)", -1};
     for (size_t i = 0; i < n; i++)
         if (spec.out_w[i] == 0 || spec.out_w[i] > 65535u || spec.out_h[i] == 0 || spec.out_h[i] > 65535u) return fault_at(spec, i, "target width and height must be 1..65535");
+
+    // An affine map (pjd_batch_set_resize_affine) is the whole request: no pad, orientation, window or filter beside it -- each is a matrix
+    // the caller multiplies in -- and a form of its own, one record per output beside the work list, in tiles of the warp launch.
+    if (spec.affine_set) {
+        if (const char *other = pjd_resize_affine_excludes(spec))
+            return PjdResizeFault{std::string("an affine map and ") + other + " exclude each other on one batch (multiply it into the matrix)", -1, true};
+        out.ct_w = spec.out_w; out.ct_h = spec.out_h;
+        out.recs.resize(n); out.tile_prefix.resize(n + 1); out.warp.resize(n);
+        uint64_t tiles = 0;
+        for (size_t i = 0; i < n; i++) {
+            const PjdResizePicture &p = spec.pic[i];
+            if (const char *f = pjd_resize_affine_fault(p.sw, p.sh, spec.out_w[i], spec.out_h[i], spec.affine[i].m)) return fault_at(spec, i, f);
+            pjd_warp_quantise(spec.affine[i].m, out.warp[i]);
+            out.recs[i] = PjdDevResize{p.src_off, p.dst_off, p.sw, p.sh, p.src_stride, spec.out_w[i], spec.out_h[i], (spec.out_w[i] + PJD_WARP_COLS - 1) / PJD_WARP_COLS};
+            out.tile_prefix[i] = (uint32_t)tiles;
+            tiles += warp_tiles_of(spec.out_w[i], spec.out_h[i]);
+            if (tiles >= (1ull << 31)) return PjdResizeFault{"the targets of this batch are too large for one launch", -1};
+        }
+        out.tile_prefix[n] = form.tiles = (uint32_t)tiles;
+        form.warp = true;
+        return PjdResizeFault{};
+    }
 
     // the content of every delivered picture: its canvas less its pad; a padded picture has a border line per canvas line
     out.ct_w = spec.out_w; out.ct_h = spec.out_h;

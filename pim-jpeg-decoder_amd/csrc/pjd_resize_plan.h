@@ -2,7 +2,7 @@
 //
 // The records the kernels of pjd_k_resize.hip read are a PURE FUNCTION of the request: pjd_resize_resolve makes all of them from a
 // PjdResizeSpec in one go, and every setter of pjd_api.hip (pjd_batch_set_resize, _set_resize_pad, _set_orientation,
-// _set_resize_window, _set_resize_filter) adds its argument to the batch's request and resolves again.  Each rule of include/pjd.h --
+// _set_resize_window, _set_resize_filter, _set_resize_affine) adds its argument to the batch's request and resolves again.  Each rule of include/pjd.h --
 // content = canvas - pad, the transpose swap, window defaults, the mirror's exclusive-or, the prefix sums, the axis tables, the LDS of
 // the launch, every limit -- is stated once, here.  Plain C++, no HIP: tools/resize_plan_host.cpp checks it on the CPU under the
 // sanitizers, tools/resize_host.cpp runs the kernel bodies over its records.
@@ -12,6 +12,9 @@
 
 #include "../../include/pjd.h"
 #include "pjd_internal.h"
+
+// one inverse 2 x 3 map of pjd_batch_set_resize_affine, as given: {m00, m01, m02, m10, m11, m12}
+struct PjdAffine { double m[6]; };
 
 // What the caller said, nothing derived.  An optional array that was given (`*_set`) but is all neutral -- all-zero pads, orientations
 // all 1, all-zero windows -- resolves to what its absence resolves to; the flags are what the call-order rules of the setters read.
@@ -31,12 +34,18 @@ struct PjdResizeSpec {
     std::vector<uint8_t> orientation;      // pjd_batch_set_orientation, as given
     std::vector<pjd_resize_window> win;    // pjd_batch_set_resize_window, as given: zeros for defaults
     int filter = PJD_RESIZE_BILINEAR;      // pjd_batch_set_resize_filter
+    // pjd_batch_set_resize_affine: an alternative to the per-axis request above, not a layer on it -- with affine_set none of pad_set,
+    // ori_set, win_set and filter_set may be (pjd_resize_affine_excludes), in whichever order the two were asked for
+    bool affine_set = false;
+    std::vector<PjdAffine> affine;         // one inverse map per output, as given
+    uint8_t affine_fill[3] = {0, 0, 0};    // what a tap outside the picture reads
 };
 
 // What chooses the kernel and sizes its grid ...
 struct PjdResizeForm {
     uint32_t tiles = 0, lines = 0, lds = 0;                     // tiles of the resample launch, canvas lines of the border launch, LDS bytes of a table-driven launch
     bool windowed = false, oriented = false, padded = false;    // the WIN / ORI / PAD kernels; padded implies oriented implies windowed
+    bool warp = false;                                          // pjd_batch_set_resize_affine: the launch of pjd_k_warp.hip, whose tiles are PJD_WARP_COLS x PJD_WARP_ROWS; none of the three above
 };
 // ... and everything it reads (pjd_internal.h).  win, pad + line_prefix, aa + tab are empty where the form does not read them.
 struct PjdResizeWork {
@@ -49,6 +58,7 @@ struct PjdResizeWork {
     std::vector<PjdDevResizeAA> aa;
     std::vector<uint32_t> tab;             // one axis table per distinct (source length, target length)
     std::vector<uint32_t> ct_w, ct_h;      // the content of each delivered picture: the canvas less its pad
+    std::vector<PjdDevWarp> warp;          // form.warp: the quantised map of every output
 };
 
 // no fault: text is empty.  The text is what pjd_last_error reports behind the setter's own "set_...: "; picture -1: the batch as a whole,
@@ -56,6 +66,7 @@ struct PjdResizeWork {
 struct PjdResizeFault {
     std::string text;
     int picture = -1;
+    bool state = false;                    // the request is refused for what the batch took before (PJD_E_STATE), not for an argument (PJD_E_ARG)
 };
 // "picture <i>", or "view <i> (picture <p>)" where the request has views: how every fault text names an output
 std::string pjd_resize_output_name(const PjdResizeSpec &spec, size_t i);
@@ -64,6 +75,15 @@ PjdResizeFault pjd_resize_resolve(const PjdResizeSpec &spec, PjdResizeWork &out)
 // THE validation of a source window and of a pad record (include/pjd.h): null, or what is wrong with it
 const char *pjd_resize_window_fault(uint32_t sw, uint32_t sh, uint32_t tw, uint32_t th, const pjd_resize_window *win, int filter);
 const char *pjd_resize_pad_fault(uint32_t out_w, uint32_t out_h, const pjd_resize_pad *pad);
+
+// THE rules of an affine map (include/pjd.h).  pjd_warp_quantise: m -> the Q40 record the kernels read, every coefficient
+// llrint(m * 2^40) with the half pixels folded into b0 and b1; null, or what is wrong with m: a value that is not finite, a
+// coefficient beyond the limits, which are checked on the quantised values.  pjd_resize_affine_fault: that, behind the sizes.
+// pjd_resize_affine_excludes: null, or the setter among pad / orientation / window / filter that the request holds and an affine map
+// excludes ("set_resize_pad", ...).
+const char *pjd_warp_quantise(const double m[6], PjdDevWarp &out);
+const char *pjd_resize_affine_fault(uint32_t sw, uint32_t sh, uint32_t tw, uint32_t th, const double m[6]);
+const char *pjd_resize_affine_excludes(const PjdResizeSpec &spec);
 
 // The packed layout of a batch's results, as the planner lays out a batch's own buffer: n pictures of channels * w * h elements of
 // elem_bytes at 256-byte aligned offsets

@@ -212,6 +212,12 @@ def dev_lib():
         L.pjd_batch_set_resize_pad.argtypes = [vp, C.POINTER(ResizePad), C.POINTER(C.c_uint8)]
         L.pjd_batch_set_pad_value.restype = i32
         L.pjd_batch_set_pad_value.argtypes = [vp, C.POINTER(C.c_float)]
+        L.pjd_batch_set_resize_affine.restype = i32
+        L.pjd_batch_set_resize_affine.argtypes = [vp, C.POINTER(C.c_double * 6), C.POINTER(C.c_uint8)]
+        L.pjd_warp_tap.restype = i32
+        L.pjd_warp_tap.argtypes = [C.POINTER(C.c_double), C.c_uint32, C.c_uint32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.pjd_resize_affine_check.restype = i32
+        L.pjd_resize_affine_check.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]
         L.pjd_resize_pad_check.restype = i32
         L.pjd_resize_pad_check.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(ResizePad)]
         L.pjd_resize_window_check.restype = i32
@@ -549,6 +555,23 @@ class Batch:
                 arr[i] = resize_window(w)
         self.ctx._check(self.L.pjd_batch_set_resize_window(self._h, arr), "pjd_batch_set_resize_window")
 
+    def set_resize_affine(self, matrices, fill=(0, 0, 0)):
+        """pjd_batch_set_resize_affine: output i is read from its picture under matrices[i] = (m00, m01, m02, m10, m11, m12), the INVERSE
+        map from the centres of its target pixels (the size of set_resize()) to source pixel centres at the decode size, bilinear in the
+        fixed point include/pjd.h specifies bit for bit, with `fill` (three bytes, R G B; grey reads the first) where a tap lies outside
+        the picture: rotation, scale, shear and translation in one launch.  An alternative to set_resize_pad() / set_orientation() /
+        set_resize_window() / set_resize_filter(), which it excludes and which exclude it.  Once, after set_resize() (and set_views()),
+        before set_normalize() / bind_output() / upload()."""
+        if len(matrices) != self.n_out:
+            raise ValueError("set_resize_affine: one matrix of six values per picture (per view after set_views)")
+        if len(fill) != 3 or any(not 0 <= int(v) <= 255 or int(v) != v for v in fill):
+            raise ValueError("set_resize_affine: the fill is three bytes (R, G, B)")
+        arr = ((C.c_double * 6) * max(self.n_out, 1))()
+        for i, m in enumerate(matrices):
+            arr[i] = _affine6(m, "set_resize_affine")
+        fl = (C.c_uint8 * 3)(*[int(v) for v in fill])
+        self.ctx._check(self.L.pjd_batch_set_resize_affine(self._h, arr, fl), "pjd_batch_set_resize_affine")
+
     def set_resize_filter(self, filter):
         """pjd_batch_set_resize_filter: RESIZE_ANTIALIAS makes the resize the widened triangle filter include/pjd.h specifies bit for
         bit (torch's antialias=True, Pillow's BILINEAR), RESIZE_BICUBIC the bicubic one (Keys, a = -0.5, widened where an axis shrinks:
@@ -853,6 +876,32 @@ def resize_bicubic_taps(src_n, dst_n, i):
     if not all(0 <= int(v) < 2 ** 32 for v in (src_n, dst_n, i)) or dev_lib().pjd_resize_bicubic_taps(int(src_n), int(dst_n), int(i), C.byref(first), C.byref(count), q) != 0:
         raise ValueError(f"resize_bicubic_taps({src_n}, {dst_n}, {i}): sizes must be 1..65535, i < dst_n and src_n <= 16 * dst_n")
     return first.value, list(q[:count.value])
+
+
+def _affine6(m, who):
+    """six doubles from a flat sequence of six or from two rows of three"""
+    vals = [float(v) for row in m for v in (row if hasattr(row, "__len__") else (row,))]
+    if len(vals) != 6:
+        raise ValueError(f"{who}: a matrix is six values (m00, m01, m02, m10, m11, m12), or two rows of three")
+    return (C.c_double * 6)(*vals)
+
+
+def warp_tap(m, i, j):
+    """pjd_warp_tap (host only): (x0, y0, wx, wy) -- the top-left source sample (either may be negative) target pixel (i, j), column i and
+    row j, reads under the inverse map m of six values, and the weights of x0 + 1 and y0 + 1 in 1/256; the code the warp kernel runs.
+    ValueError for a matrix that is not finite or beyond the limits, and for i or j at or above 65535."""
+    x0, y0, wx, wy = C.c_int64(), C.c_int64(), C.c_uint32(), C.c_uint32()
+    if not all(0 <= int(v) < 2 ** 32 for v in (i, j)) or dev_lib().pjd_warp_tap(_affine6(m, "warp_tap"), int(i), int(j), C.byref(x0), C.byref(y0), C.byref(wx), C.byref(wy)) != 0:
+        raise ValueError(f"warp_tap({list(m)}, {i}, {j}): the matrix must be finite and within the limits, i and j below 65535")
+    return x0.value, y0.value, wx.value, wy.value
+
+
+def resize_affine_check(sw, sh, tw, th, m):
+    """pjd_resize_affine_check (host only): True where pjd_batch_set_resize_affine would accept the inverse map m (six values) for a
+    picture of sw x sh at its decode size and a target of tw x th."""
+    if not all(0 <= int(v) < 2 ** 32 for v in (sw, sh, tw, th)):
+        return False
+    return dev_lib().pjd_resize_affine_check(int(sw), int(sh), int(tw), int(th), _affine6(m, "resize_affine_check")) == 0
 
 
 def resize_window(w):

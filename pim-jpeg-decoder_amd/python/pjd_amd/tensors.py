@@ -4,7 +4,8 @@ The batch is bound (Batch.bind_output, pjd_batch_bind_output of include/pjd.h) t
 on the context's device; the back end writes the pictures straight into it -- planar R, G, B (OUT_RGB8_PLANAR, "CHW") by
 default -- and the results are views of that buffer.  No native code of its own.  torch is imported inside the functions that
 need it: uniform_output_shape(), pick_scale_flags(), pick_libjpeg_scale_flags(), normalize_constants(), center_crop_window(), window_at_scale(), orient_hw(),
-orient_then_hflip(), crop_to_stored(), tile_views(), least_reduced_scale_flags() and plan_views() are pure.
+orient_then_hflip(), crop_to_stored(), tile_views(), least_reduced_scale_flags(), plan_views(), affine_inverse_matrix(), orientation_matrix()
+and plan_affines() are pure.
 
 Pictures of different sizes become ONE [N, 3, H, W] tensor with decode_resized_batch_tensor: the library resamples every picture to
 H x W inside the decode (Batch.set_resize, pjd_batch_set_resize), after the box pre-scale pick_scale_flags chooses.
@@ -21,6 +22,11 @@ PIL.ImageOps.exif_transpose give -- with crops=, flips= and resize_short= speaki
 Several outputs of one picture -- two augmented views, multi-crop, FiveCrop, two scales of a crop, tiles -- come from ONE decode of it
 with views= (Batch.set_views, pjd_batch_set_views): view v is a resample of picture views[v], every per-picture keyword then has one
 entry per view, the result is [V, C, H, W] and the statuses stay per picture.  tile_views() cuts one picture into a grid of tiles.
+
+Rotation, shear, anisotropic scale and translation -- torchvision's RandomRotation / RandomAffine, DALI's warp_affine, the geometric
+ops of RandAugment -- come out of the decode with affines= (Batch.set_resize_affine, pjd_batch_set_resize_affine): one inverse 2 x 3
+matrix per output, which affine_inverse_matrix() makes from an angle, a translation, a scale and a shear; `fill` where the output looks
+outside the picture.  No grid_sample pass over a float tensor.
 
 The tensor a model takes -- fp16, bf16 or fp32, (x / 255 - mean) / std -- comes out of the same launch with
 decode_normalized_batch_tensor (Batch.set_normalize, pjd_batch_set_normalize): no uint8 tensor, no elementwise kernels after it.
@@ -106,8 +112,9 @@ def _torch():
 # What one call asks of a batch, settled before the batch exists: the descriptors to decode and the output format; the capacity and the
 # offsets to bind (None: packed); then what the setters take, each None where its setter is not called -- views, sizes (set_resize), pads
 # with fill (set_resize_pad), orientations, windows, filter (set_resize_filter), normalize = (dtype, scale, bias), pad_value.
-_Request = collections.namedtuple("_Request", "descs out_format capacity offsets views sizes pads fill orientations windows filter normalize pad_value",
-                                  defaults=(None,) * 11)
+# affines (set_resize_affine, with fill) stands in place of pads, orientations, windows and filter.
+_Request = collections.namedtuple("_Request", "descs out_format capacity offsets views sizes pads fill orientations windows filter normalize pad_value affines",
+                                  defaults=(None,) * 12)
 
 
 def _run(ctx, req, device):
@@ -120,6 +127,8 @@ def _run(ctx, req, device):
             b.set_views(req.views)                  # from here on every per-picture argument is per view; the statuses stay per picture
         if req.sizes is not None:
             b.set_resize(req.sizes)
+            if req.affines is not None:
+                b.set_resize_affine(req.affines, req.fill)
             if req.pads is not None:
                 b.set_resize_pad(req.pads, req.fill)
             if req.orientations is not None:
@@ -428,6 +437,98 @@ def _plan_outputs(descs, size, prescale, crops, flips, orientations, resize_shor
             (oris if orientations is not None else None), (pads if letterbox is not None else None))
 
 
+def affine_inverse_matrix(src_hw, out_hw, angle=0, translate=(0, 0), scale=1, shear=(0, 0), center=None):
+    """The inverse 2 x 3 matrix (m00, m01, m02, m10, m11, m12) that Batch.set_resize_affine and affines= take, for a picture of
+    src_hw = (h, w) delivered as out_hw = (H, W): torchvision's affine -- rotate by `angle` degrees about `center`, shear by `shear` = (x, y)
+    degrees, scale by `scale`, then translate by `translate` = (tx, ty) pixels -- with the centre of the output on the centre of the
+    source.  A positive angle turns the picture COUNTER-CLOCKWISE, as torchvision.transforms.functional.rotate and RandomRotation have
+    it; functional.affine and RandomAffine count clockwise, so their angle goes in negated (the matrix is functional's
+    _get_inverse_affine_matrix(center, -angle, translate, scale, shear)).  center = (x, y) in the source picture's coordinates, origin
+    at its top-left corner; None: its middle, (w / 2, h / 2).  The output frame is the source frame shifted so that the two middles
+    coincide: out_hw == src_hw is torchvision's same-size output, out_hw = (w, h) with angle=90 is numpy.rot90(P, 1) exactly.  Angles
+    that are multiples of 90 use exact sines.  Coordinates are at full size: the helpers divide by the decode scale.  Pure."""
+    import math
+    sh, sw = float(src_hw[0]), float(src_hw[1])
+    oh, ow = float(out_hw[0]), float(out_hw[1])
+    if min(sh, sw, oh, ow) < 1 or not float(scale) > 0:
+        raise ValueError("affine_inverse_matrix: sizes of at least 1 and a scale above 0")
+    shear = (shear, 0.0) if isinstance(shear, (int, float)) else tuple(shear)
+    tx, ty = (float(v) for v in translate)
+    cx, cy = (sw / 2, sh / 2) if center is None else (float(center[0]), float(center[1]))
+
+    def cs(deg):                                           # exact at the quarter turns
+        q, r = divmod(deg, 90.0)
+        if r == 0:
+            return ((1.0, 0.0), (0.0, 1.0), (-1.0, 0.0), (0.0, -1.0))[int(q) % 4]
+        return math.cos(math.radians(deg)), math.sin(math.radians(deg))
+
+    rot = -float(angle)
+    sx, sy = float(shear[0]), float(shear[1])
+    if math.cos(math.radians(sy)) == 0:
+        raise ValueError("affine_inverse_matrix: a shear of 90 degrees has no matrix")
+    c_rs, s_rs = cs(rot - sy)
+    c_r, s_r = cs(rot)
+    csy, tsx = math.cos(math.radians(sy)), math.tan(math.radians(sx))
+    a, b = c_rs / csy, -c_rs * tsx / csy - s_r
+    c, d = s_rs / csy, -s_rs * tsx / csy + c_r
+    m = [d / scale, -b / scale, 0.0, -c / scale, a / scale, 0.0]
+    # the output pixel at p (its own frame) lies at p - (ow / 2, oh / 2) + (sw / 2, sh / 2) of the source frame
+    ox, oy = sw / 2 - ow / 2, sh / 2 - oh / 2
+    m[2] = m[0] * (ox - cx - tx) + m[1] * (oy - cy - ty) + cx
+    m[5] = m[3] * (ox - cx - tx) + m[4] * (oy - cy - ty) + cy
+    return tuple(m)
+
+
+def orientation_matrix(o, W, H):
+    """The exact integer 2 x 3 matrix from the UPRIGHT picture's coordinates to those of the STORED picture of W x H whose EXIF
+    orientation is o (pixel centres at +1/2, as everywhere): the mirrors undone in the upright frame, then the axes swapped where o
+    transposes -- crop_to_stored for points.  With the identity as the map and the upright size as the target it is
+    Batch.set_orientation's permutation.  Pure."""
+    t, v, hm = _tvh(o)
+    UH, UW = orient_hw(o, H, W)
+    rx = (-1, 0, UW) if hm else (1, 0, 0)
+    ry = (0, -1, UH) if v else (0, 1, 0)
+    return (ry + rx) if t else (rx + ry)
+
+
+def _compose(a, b):
+    """the 2 x 3 map a after b"""
+    return (a[0] * b[0] + a[1] * b[3], a[0] * b[1] + a[1] * b[4], a[0] * b[2] + a[1] * b[5] + a[2],
+            a[3] * b[0] + a[4] * b[3], a[3] * b[1] + a[4] * b[4], a[3] * b[2] + a[4] * b[5] + a[5])
+
+
+def plan_affines(descs, affines, prescale=True, orientations=None, views=None):
+    """What the resizing helpers do with affines= -> (descriptors to decode, one per PICTURE; matrices for Batch.set_resize_affine, one
+    per OUTPUT).  affines[i]: six values, or two rows of three: the inverse map of output i from its pixel centres to the FULL-SIZE
+    picture's -- the UPRIGHT one where orientations are given: orientation_matrix is then multiplied in, exactly.  The pre-scale
+    (prescale true: F_SCALE_*, "draft": F_LIBJPEG_SCALE_*) of a picture is the largest s of 8, 4, 2 for which both column norms of the
+    matrix -- the source pixels one step along each target axis covers -- are at least s, the least reduced among a picture's views; else
+    the descriptors' own flags hold.  Every matrix is then divided by the scale its picture is decoded at.  Pure."""
+    import math
+    pic_of = list(range(len(descs))) if views is None else _views(views, len(descs))
+    for name, v in (("affines", affines), ("orientations", orientations)):
+        if v is not None and len(v) != len(pic_of):
+            raise ValueError(f"{name}: one entry per picture (per view with views=)")
+    full = []
+    for i, p in enumerate(pic_of):
+        m = tuple(float(v) for row in affines[i] for v in (row if hasattr(row, "__len__") else (row,)))
+        if len(m) != 6 or not all(math.isfinite(v) for v in m):
+            raise ValueError(f"affines[{i}]: six finite values (m00, m01, m02, m10, m11, m12), or two rows of three")
+        if orientations is not None:
+            m = _compose(orientation_matrix(orientations[i], int(descs[p].width), int(descs[p].height)), m)
+        full.append(m)
+    run = list(descs)
+    if prescale:
+        draft = prescale == "draft"
+        mask, low = (pjd_amd.F_LIBJPEG_SCALE_MASK, pjd_amd.F_LIBJPEG_SCALE_1_2) if draft else (pjd_amd.F_SCALE_MASK, pjd_amd.F_SCALE_1_2)
+        logs = [3] * len(descs)                            # no view at all: 1/8, nothing reads the picture
+        for m, p in zip(full, pic_of):
+            shrink = min(math.hypot(m[0], m[3]), math.hypot(m[1], m[4]))
+            logs[p] = min(logs[p], 3 if shrink >= 8 else 2 if shrink >= 4 else 1 if shrink >= 2 else 0)
+        run = [_copy_desc(d, mask, log * low) for d, log in zip(descs, logs)]
+    return run, [tuple(v / (1 << _scale_log(run[p].flags)) for v in m) for m, p in zip(full, pic_of)]
+
+
 def tile_views(h, w, th, tw):
     """An h x w picture cut into a grid of tiles of at most th x tw, edge tiles smaller -> (windows, sizes), row-major (left to right,
     then top to bottom): windows[k] = {"x", "y", "w", "h"} for Batch.set_resize_window and sizes[k] = (tile_h, tile_w) for
@@ -489,7 +590,7 @@ def plan_views(descs, views, size, prescale=True, crops=None, flips=None, resize
 
 
 def _resize_request(who, descs, size, out_format, prescale, antialias, crops, flips, resize_short, interpolation, orientations, libjpeg,
-                    letterbox, fill, draft, views):
+                    letterbox, fill, draft, views, affines=None):
     """What the two resizing helpers (`who`) share, all of it before anything is created: the keywords are checked, the outputs are
     planned (_plan_outputs, plan_views) -> the _Request of a batch of uint8 outputs of `size`, one after the other in one buffer."""
     if interpolation not in ("bilinear", "bicubic"):
@@ -501,6 +602,16 @@ def _resize_request(who, descs, size, out_format, prescale, antialias, crops, fl
     th, tw = int(size[0]), int(size[1])
     gray = out_format == pjd_amd.OUT_GRAY8
     fill = _fill(fill, gray)
+    if affines is not None:
+        # the map is the whole geometry: each of these is a matrix the caller multiplies in (affine_inverse_matrix, orientation_matrix)
+        for name, given in (("crops", crops is not None), ("flips", flips is not None), ("resize_short", resize_short is not None), ("letterbox", letterbox is not None),
+                            ("antialias", bool(antialias)), ("interpolation", interpolation != "bilinear")):
+            if given:
+                raise ValueError(f"{who}: affines= excludes {name}= (fold it into the matrix; the warp is bilinear)")
+        views = None if views is None else _views(views, len(descs))
+        run, mats = plan_affines(descs, affines, prescale, orientations, views)
+        n, plane = len(mats), (1 if gray else 3) * th * tw
+        return _Request(run, out_format, n * plane, [i * plane for i in range(n)], views, [(th, tw)] * n, fill=fill, affines=mats)
     if views is not None:
         views = _views(views, len(descs))
         run, windows, oris, pads = plan_views(descs, views, (th, tw), prescale, crops, flips, resize_short, orientations, letterbox)
@@ -513,7 +624,7 @@ def _resize_request(who, descs, size, out_format, prescale, antialias, crops, fl
 
 def decode_resized_batch_tensor(ctx, descs, size, prescale=True, device=None, antialias=False, crops=None, flips=None, resize_short=None,
                                 interpolation="bilinear", orientations=None, libjpeg=False, letterbox=None, fill=(0, 0, 0), gray=False, draft=False,
-                                views=None):
+                                views=None, affines=None):
     """Pictures of ANY sizes -> (uint8 tensor [N, 3, H, W], statuses), size = (H, W): every picture is resampled to H x W inside
     the decode (the bilinear filter of include/pjd.h, pjd_batch_set_resize) and lands at offset i * 3 * H * W of one buffer, so
     the result is one contiguous NCHW tensor with no copy after the decode, complete on return and readable on any torch stream
@@ -557,9 +668,16 @@ def decode_resized_batch_tensor(ctx, descs, size, prescale=True, device=None, an
     order, any number of views of a picture, none included -- and every picture is decoded ONCE.  crops, flips and orientations then have V
     entries (entry v speaks about picture views[v] as entry i speaks about picture i without views); resize_short and letterbox apply to
     every view.  The statuses stay per picture.  The pre-scale of a picture is the least reduced of what its views would pick
-    (plan_views).  None: nothing changes."""
+    (plan_views).  None: nothing changes.
+    affines=[(m00, m01, m02, m10, m11, m12), ...]: output i is the picture under that INVERSE map, from the centres of the H x W target's
+    pixels to those of the FULL-SIZE stored picture (affine_inverse_matrix makes it from an angle, a translation, a scale and a shear:
+    RandomRotation, RandomAffine), bilinear in the fixed point of include/pjd.h (Batch.set_resize_affine), with `fill` wherever a tap
+    lies outside the picture -- one launch, no grid_sample pass.  With orientations= the map speaks about the UPRIGHT picture and the
+    exact orientation matrix is multiplied in (plan_affines); with views= there is one matrix per view.  prescale=True decodes a picture
+    at the largest box scale that every one of its maps shrinks by; prescale=False is exactly the filter over the full-size picture.
+    crops, flips, resize_short, letterbox, antialias and interpolation raise ValueError beside it: each is a matrix to fold in."""
     req = _resize_request("decode_resized_batch_tensor", descs, size, pjd_amd.OUT_GRAY8 if gray else pjd_amd.OUT_RGB8_PLANAR, prescale, antialias,
-                          crops, flips, resize_short, interpolation, orientations, libjpeg, letterbox, fill, draft, views)
+                          crops, flips, resize_short, interpolation, orientations, libjpeg, letterbox, fill, draft, views, affines)
     buf, _, st = _run(ctx, req, device)
     return buf.view(len(req.sizes), 1 if gray else 3, *req.sizes[0]), st
 
@@ -578,7 +696,7 @@ def normalize_constants(mean, std):
 
 def decode_normalized_batch_tensor(ctx, descs, size, mean, std, dtype=None, channels_last=False, prescale=True, device=None,
                                    antialias=False, crops=None, flips=None, resize_short=None, interpolation="bilinear", orientations=None,
-                                   libjpeg=False, letterbox=None, fill=(0, 0, 0), pad_value=None, gray=False, draft=False, views=None):
+                                   libjpeg=False, letterbox=None, fill=(0, 0, 0), pad_value=None, gray=False, draft=False, views=None, affines=None):
     """Pictures of ANY sizes -> (tensor of `dtype` [N, 3, H, W], statuses), size = (H, W); dtype torch.float16 (the default),
     torch.bfloat16 or torch.float32.  As decode_resized_batch_tensor, and every sample v of channel c leaves the same launch as
     fma(v, scale[c], bias[c]) with the constants of normalize_constants(mean, std), converted once to `dtype` (include/pjd.h,
@@ -597,7 +715,9 @@ def decode_normalized_batch_tensor(ctx, descs, size, mean, std, dtype=None, chan
     gray=True: [N, 1, H, W] of `dtype` (OUT_GRAY8): fma(v, scale[0], bias[0]) of the luma plane; mean and std may be one number or a
     sequence of length 1, fill and pad_value one number; it takes channels_last=False (one plane has no interleaved form).
     views: as in decode_resized_batch_tensor -- [V, C, H, W] of `dtype` (channels_last: the permuted view of [V, H, W, 3]), per-view crops,
-    flips and orientations, per-picture statuses, every picture decoded once."""
+    flips and orientations, per-picture statuses, every picture decoded once.
+    affines, with fill: as in decode_resized_batch_tensor; the fill is a sample like any other and is normalised with the rest (there is
+    no pad_value beside it: that needs a letterbox)."""
     _gray_layout(gray, not channels_last)
     if gray:
         mean, std = _gray3(mean, "mean"), _gray3(std, "std")
@@ -607,7 +727,7 @@ def decode_normalized_batch_tensor(ctx, descs, size, mean, std, dtype=None, chan
     if pad_value is not None and letterbox is None:
         raise ValueError("pad_value needs letterbox: without it there is no border")
     req = _resize_request("decode_normalized_batch_tensor", descs, size, pjd_amd.OUT_GRAY8 if gray else pjd_amd.OUT_RGB8 if channels_last else pjd_amd.OUT_RGB8_PLANAR,
-                          prescale, antialias, crops, flips, resize_short, interpolation, orientations, libjpeg, letterbox, fill, draft, views)
+                          prescale, antialias, crops, flips, resize_short, interpolation, orientations, libjpeg, letterbox, fill, draft, views, affines)
     torch = _torch()
     dtype = torch.float16 if dtype is None else dtype
     dts = {torch.float16: (pjd_amd.DT_F16, 2), torch.bfloat16: (pjd_amd.DT_BF16, 2), torch.float32: (pjd_amd.DT_F32, 4)}

@@ -1,0 +1,281 @@
+// warp_host.cpp -- the body of the affine warp kernels (pim-jpeg-decoder_amd/csrc/pjd_k_warp_body.h, with the stores of pjd_k_resize_store.h)
+// run on the host, thread by thread, under the sanitizers, in the manner of tools/resize_host.cpp; and the rules of the resolver for an
+// affine request (pjd_resize_plan.cpp) checked beside it.
+//
+//     clang++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize=alignment -D__host__= -D__device__= -o warp_host
+//         tools/warp_host.cpp pim-jpeg-decoder_amd/csrc/pjd_resize_plan.cpp && ./warp_host
+//
+// (clang: the store header uses its vector extensions and 16-bit float types.  tests/test_warp_cpu.py builds and runs it.)
+// Every record the body reads -- work list, prefix sum, quantised maps -- is made by the product's own resolver from a request, as the
+// setter of pjd_api.hip makes it.  The expectation takes nothing from those records and nothing from pjd_internal.h: a plain loop over
+// the arithmetic of include/pjd.h, the position sum in 128 bits, the conversions to the 16-bit types bit by bit.
+// All twelve forms (interleaved, planar and the one-plane grey form x uint8 / fp16 / bf16 / fp32) write the same cases into one buffer
+// at element-aligned offsets with odd gaps, the buffer itself shifted by 0..3 elements; the sources lie back to back with NO padding, so
+// a read outside a picture that mattered changes the result and a read outside the buffer is a sanitizer report; the destination is
+// compared whole, guard bytes included.  Cases: the identity; both quarter turns and the half turn of a non-square picture; a mirror;
+// an integer translation with a fill band on two sides; a half-pixel shift; a map wholly outside (all fill); a 1 x 1 source; a 1 x 1
+// target; targets one pixel past a tile edge on each axis; a 65535-sample axis with |a| = 16 and the largest translation of either sign
+// (sums near 2^62); ten seeded general maps.  Prints ALL EQUAL and the number of failed checks.
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <type_traits>
+#include <vector>
+#define __host__
+#define __device__
+#define __forceinline__ inline
+#define __restrict__
+#include "../include/pjd.h"
+#include "../pim-jpeg-decoder_amd/csrc/pjd_internal.h"
+#include "../pim-jpeg-decoder_amd/csrc/pjd_resize_plan.h"
+struct Dim { uint32_t x; };
+static thread_local Dim threadIdx, blockIdx;
+static inline uint32_t __umul24(uint32_t a, uint32_t b) { return (a & 0xffffff) * (b & 0xffffff); }
+static inline int32_t sext24(int32_t a) { return (int32_t)((uint32_t)a << 8) >> 8; }
+static inline int32_t __mul24(int32_t a, int32_t b) { return (int32_t)(uint32_t)((int64_t)sext24(a) * sext24(b)); }
+#include "../pim-jpeg-decoder_amd/csrc/pjd_k_resize_store.h"
+#define __builtin_amdgcn_readfirstlane(x) (x)
+
+template <bool PLANAR, int DT, int NC>
+static void thread_warp(const uint8_t *src, uint8_t *dst, const PjdDevResize *recs, const PjdDevWarp *warp, const uint32_t *tile_prefix, uint32_t n_images,
+                        uint32_t n_tiles, uint32_t fill, const NormArgs nz)
+{
+#include "../pim-jpeg-decoder_amd/csrc/pjd_k_warp_body.h"
+}
+
+static int failed = 0;
+#define CHECK(cond, ...) do { if (!(cond)) { failed++; printf("FAILED %s:%d: ", __FILE__, __LINE__); printf(__VA_ARGS__); printf("\n"); } } while (0)
+
+// the expectation's own conversions to binary16 and bfloat16, round to nearest even
+static uint16_t f16bits(float f)
+{
+    uint32_t x; memcpy(&x, &f, 4);
+    const uint32_t sign = (x >> 16) & 0x8000u, a = x & 0x7fffffffu;
+    if (a >= 0x7f800000u) return (uint16_t)(sign | (a > 0x7f800000u ? 0x7e00u : 0x7c00u));
+    if (a < 0x38800000u) {
+        const uint32_t e = a >> 23;
+        if (e < 102u) return (uint16_t)sign;
+        const uint32_t m = (a & 0x7fffffu) | 0x800000u, shift = 126u - e;
+        uint32_t q = m >> shift;
+        const uint32_t rem = m & ((1u << shift) - 1u), half = 1u << (shift - 1u);
+        if (rem > half || (rem == half && (q & 1u))) q++;
+        return (uint16_t)(sign | q);
+    }
+    const uint32_t r = a - 0x38000000u;
+    uint32_t q = r >> 13; const uint32_t rem = r & 0x1fffu;
+    if (rem > 0x1000u || (rem == 0x1000u && (q & 1u))) q++;
+    if (q > 0x7c00u) q = 0x7c00u;
+    return (uint16_t)(sign | q);
+}
+static uint16_t bf16bits(float f) { uint32_t b; memcpy(&b, &f, 4); b += 0x7fffu + ((b >> 16) & 1u); return (uint16_t)(b >> 16); }
+
+struct Case { uint32_t sw, sh, tw, th; double m[6]; };
+
+static std::vector<Case> cases(unsigned seed)
+{
+    const double T = 262144.0;                              // 2^18: the largest translation
+    std::vector<Case> c = {
+        {61, 45, 61, 45, {1, 0, 0, 0, 1, 0}},               // the identity
+        {61, 45, 45, 61, {0, -1, 61, 1, 0, 0}},             // a quarter turn ...
+        {61, 45, 45, 61, {0, 1, 0, -1, 0, 45}},             // ... and the other
+        {61, 45, 61, 45, {-1, 0, 61, 0, -1, 45}},           // the half turn
+        {33, 70, 33, 70, {-1, 0, 33, 0, 1, 0}},             // a mirror
+        {61, 45, 61, 45, {1, 0, -7, 0, 1, 5}},              // an integer translation: a fill band left and at the bottom
+        {61, 45, 61, 45, {1, 0, 0.5, 0, 1, -0.5}},          // half a pixel
+        {61, 45, 40, 30, {1, 0, 1000, 0, 1, -1000}},        // wholly outside: all fill
+        {1, 1, 9, 7, {0.25, 0, -0.6, 0, 0.25, -0.3}},       // a 1 x 1 source
+        {80, 96, 1, 1, {3, 1, 20.25, -2, 1, 40.75}},        // a 1 x 1 target
+        {88, 56, PJD_WARP_COLS + 1, PJD_WARP_ROWS + 1, {1.3, 0.2, -3, -0.1, 0.8, 2}},     // one pixel past a tile edge on each axis
+        {88, 56, 257, 9, {0.33, 0.01, 1, 0.02, 5.5, 0.5}},  // ... and past the resize tile's
+        {65535, 1, 65535, 2, {16, 0, -T, 0, 1, -0.25}},     // the 64-bit range: the sums reach -2^59 .. 2^61 ...
+        {65535, 1, 65535, 2, {-16, 0, T, 0, -16, T}},       // ... and 2^59 .. -2^61; rows far outside
+        {2, 65535, 3, 65535, {1, 0, -0.5, -16, 16, T - 8}}, // the same down a column, both linear coefficients at the limit
+    };
+    srand(seed);
+    for (int k = 0; k < 10; k++) {
+        Case g;
+        g.sw = 1 + rand() % 120; g.sh = 1 + rand() % 90; g.tw = 1 + rand() % 150; g.th = 1 + rand() % 80;
+        const double ang = (rand() % 36000) * 3.14159265358979323846 / 18000.0, s = 0.3 + (rand() % 2700) / 1000.0, shx = (rand() % 200 - 100) / 250.0;
+        const double a = std::cos(ang) * s, b = -std::sin(ang) * s + shx, cc = std::sin(ang) * s, d = std::cos(ang) * s * (0.7 + (rand() % 60) / 100.0);
+        const double cx = g.sw / 2.0 + (rand() % 21 - 10), cy = g.sh / 2.0 + (rand() % 21 - 10);
+        g.m[0] = a; g.m[1] = b; g.m[2] = cx - a * g.tw / 2.0 - b * g.th / 2.0; g.m[3] = cc; g.m[4] = d; g.m[5] = cy - cc * g.tw / 2.0 - d * g.th / 2.0;
+        c.push_back(g);
+    }
+    return c;
+}
+
+// include/pjd.h, written out: one sample of one channel
+static uint32_t expect_sample(const uint8_t *pic, bool planar, uint32_t nc, uint32_t ch, const Case &c, uint32_t i, uint32_t j, uint32_t fill)
+{
+    int64_t p0[2]; uint32_t w[2];
+    for (int r = 0; r < 2; r++) {
+        const __int128 a0 = std::llrint(std::ldexp(c.m[3 * r], 40)), a1 = std::llrint(std::ldexp(c.m[3 * r + 1], 40)), a2 = std::llrint(std::ldexp(c.m[3 * r + 2], 40));
+        const __int128 X = a0 * (2 * (__int128)i + 1) + a1 * (2 * (__int128)j + 1) + 2 * a2 - ((__int128)1 << 40);
+        const __int128 f = (X + ((__int128)1 << 32)) >> 33;
+        p0[r] = (int64_t)(f >> 8); w[r] = (uint32_t)(f & 255);
+    }
+    uint32_t s[4];
+    for (int t = 0; t < 4; t++) {
+        const int64_t x = p0[0] + (t & 1), y = p0[1] + (t >> 1);
+        if (x < 0 || x >= c.sw || y < 0 || y >= c.sh) s[t] = fill;
+        else s[t] = planar ? pic[((size_t)ch * c.sh + (size_t)y) * c.sw + (size_t)x] : pic[((size_t)y * c.sw + (size_t)x) * nc + ch];
+    }
+    return ((256 - w[1]) * ((256 - w[0]) * s[0] + w[0] * s[1]) + w[1] * ((256 - w[0]) * s[2] + w[0] * s[3]) + 32768) >> 16;
+}
+
+template <bool PLANAR, int DT, int NC>
+static void run(uint32_t misalign_elems, unsigned seed)
+{
+    const uint32_t ES = DT == 0 ? 1 : PJD_DT_SIZE(DT);
+    const std::vector<Case> cs = cases(seed);
+    const size_t n = cs.size();
+    PjdResizeSpec spec;
+    spec.planar = PLANAR; spec.channels = NC;
+    spec.affine_set = true;
+    const uint8_t fill_u8[3] = {114, 7, 201};
+    memcpy(spec.affine_fill, fill_u8, 3);
+    size_t spos = 0, dpos = misalign_elems * ES;
+    std::vector<size_t> soff(n), doff(n);
+    for (size_t i = 0; i < n; i++) {
+        const Case &c = cs[i];
+        spec.pic.push_back(PjdResizePicture{spos, dpos, c.sw, c.sh, PLANAR ? c.sw : 3 * c.sw});
+        spec.out_w.push_back(c.tw); spec.out_h.push_back(c.th);
+        PjdAffine a; memcpy(a.m, c.m, sizeof a.m); spec.affine.push_back(a);
+        soff[i] = spos; doff[i] = dpos;
+        spos += (size_t)NC * c.sw * c.sh;                   // back to back
+        dpos += (size_t)NC * c.tw * c.th * ES + ES * (2 * (i % 3) + 1);     // element-aligned odd gaps
+    }
+    PjdResizeWork work;
+    const PjdResizeFault fault = pjd_resize_resolve(spec, work);
+    CHECK(fault.text.empty(), "the resolver refuses the cases: %s", fault.text.c_str());
+    if (!fault.text.empty()) return;
+    CHECK(work.form.warp && !work.form.windowed && !work.form.oriented && !work.form.padded && work.form.lines == 0 && work.form.lds == 0, "the form of an affine request");
+    CHECK(work.warp.size() == n && work.recs.size() == n && work.tile_prefix.size() == n + 1 && work.win.empty() && work.pad.empty() && work.aa.empty() && work.tab.empty(), "the records of an affine request");
+    uint8_t *src = (uint8_t *)malloc(spos);                  // the sanitizer's view of the source is exactly the pictures
+    for (size_t k = 0; k < spos; k++) src[k] = (uint8_t)rand();
+    const size_t dst_bytes = dpos + 64;
+    uint8_t *dst = (uint8_t *)aligned_alloc(256, (dst_bytes + 255) & ~(size_t)255), *want = (uint8_t *)malloc(dst_bytes);
+    memset(dst, 0xA5, dst_bytes); memset(want, 0xA5, dst_bytes);
+    const NormArgs nz = {{0.01712475f, 0.017507f, -0.01742919f}, {-2.117904f, -2.0357144f, 1.8044444f}};
+    const uint32_t fill = fill_u8[0] | (fill_u8[1] << 8) | (fill_u8[2] << 16);
+    const uint32_t t = work.form.tiles, n_blocks = (t + PJD_WARP_WAVES - 1) / PJD_WARP_WAVES;
+    for (uint32_t b = 0; b < n_blocks; b++)
+        for (uint32_t th = 0; th < 64 * PJD_WARP_WAVES; th++) {
+            blockIdx.x = b; threadIdx.x = th;
+            thread_warp<PLANAR, DT, NC>(src, dst, work.recs.data(), work.warp.data(), work.tile_prefix.data(), (uint32_t)n, t, fill, nz);
+        }
+    for (size_t k = 0; k < n; k++) {
+        const Case &c = cs[k];
+        for (uint32_t j = 0; j < c.th; j++)
+            for (uint32_t i = 0; i < c.tw; i++)
+                for (uint32_t ch = 0; ch < (uint32_t)NC; ch++) {
+                    const uint32_t v = expect_sample(src + soff[k], PLANAR, NC, ch, c, i, j, fill_u8[ch]);
+                    const size_t e = PLANAR ? ((size_t)ch * c.th + j) * c.tw + i : ((size_t)j * c.tw + i) * 3 + ch;
+                    uint8_t *o = want + doff[k] + e * ES;
+                    if (DT == 0) { o[0] = (uint8_t)v; continue; }
+                    const float u = fmaf((float)v, nz.scale[ch], nz.bias[ch]);
+                    if (DT == PJD_DT_F32) memcpy(o, &u, 4);
+                    else { const uint16_t h = DT == PJD_DT_F16 ? f16bits(u) : bf16bits(u); memcpy(o, &h, 2); }
+                }
+    }
+    size_t bad = 0, first = 0;
+    for (size_t k = 0; k < dst_bytes; k++)
+        if (dst[k] != want[k] && !bad++) first = k;
+    size_t pic = 0;
+    while (pic + 1 < n && doff[pic + 1] <= first) pic++;
+    CHECK(bad == 0, "planar %d dtype %d channels %d shift %u: %zu bytes differ, the first at %zu (case %zu from %zu)", (int)PLANAR, DT, NC, misalign_elems, bad, first, pic, doff[pic]);
+    free(src); free(dst); free(want);
+}
+
+// ---- the resolver's rules for an affine request ------------------------------------------------------------------------------------
+static PjdResizeSpec small_spec(size_t n, bool views)
+{
+    PjdResizeSpec s;
+    s.planar = true;
+    for (size_t i = 0; i < n; i++) {
+        s.pic.push_back(PjdResizePicture{i * 3000u, i * 4096u, 40, 25, 40});
+        s.out_w.push_back(40); s.out_h.push_back(25);
+        if (views) s.view_pic.push_back((uint32_t)(n - 1 - i));
+    }
+    return s;
+}
+static void with_affine(PjdResizeSpec &s, const double m[6])
+{
+    s.affine_set = true;
+    s.affine.assign(s.pic.size(), PjdAffine{{m[0], m[1], m[2], m[3], m[4], m[5]}});
+}
+
+static void resolver_rules()
+{
+    const double ident[6] = {1, 0, 0, 0, 1, 0};
+    PjdResizeWork w;
+    // all-identity matrices: still the warp form (an identity map onto another size is a crop, not a resize), and the records say 2^40
+    {
+        PjdResizeSpec s = small_spec(3, false);
+        with_affine(s, ident);
+        const PjdResizeFault f = pjd_resize_resolve(s, w);
+        CHECK(f.text.empty() && w.form.warp && w.warp.size() == 3, "identity maps resolve");
+        const int64_t one = (int64_t)1 << 40;
+        for (const PjdDevWarp &r : w.warp) CHECK(r.a00 == one && r.a01 == 0 && r.b0 == -one && r.a10 == 0 && r.a11 == one && r.b1 == -one, "the record of the identity");
+        CHECK(w.form.tiles == 3 * ((40 + PJD_WARP_COLS - 1) / PJD_WARP_COLS) * ((25 + PJD_WARP_ROWS - 1) / PJD_WARP_ROWS) && w.tile_prefix[3] == w.form.tiles, "tiles of the warp launch");
+        CHECK(w.recs[1].src_off == 3000 && w.recs[1].dst_off == 4096 && w.recs[1].tw == 40 && w.recs[1].col_tiles == (40 + PJD_WARP_COLS - 1) / PJD_WARP_COLS, "the work list of an affine request");
+        // a grey batch takes the warp form too, and no canvas records
+        s.channels = 1;
+        CHECK(pjd_resize_resolve(s, w).text.empty() && w.form.warp && !w.form.padded && w.pad.empty(), "a grey affine request");
+    }
+    // each exclusion, the request grown in both orders: the other setter first, then the map; the map first, then the other setter
+    for (int other = 0; other < 4; other++)
+        for (int order = 0; order < 2; order++) {
+            PjdResizeSpec s = small_spec(2, false);
+            auto add_other = [&] {
+                if (other == 0) { s.pad_set = true; s.pad.assign(2, pjd_resize_pad{0, 0, 0, 0}); }
+                if (other == 1) { s.ori_set = true; s.orientation.assign(2, 1); }
+                if (other == 2) { s.win_set = true; s.win.assign(2, pjd_resize_window{}); }
+                if (other == 3) { s.filter_set = true; s.filter = PJD_RESIZE_BILINEAR; }
+            };
+            if (order == 0) { add_other(); with_affine(s, ident); } else { with_affine(s, ident); add_other(); }
+            const char *names[4] = {"set_resize_pad", "set_orientation", "set_resize_window", "set_resize_filter"};
+            const PjdResizeFault f = pjd_resize_resolve(s, w);
+            CHECK(f.state && f.picture == -1 && f.text.find(names[other]) != std::string::npos && f.text.find("exclude") != std::string::npos, "exclusion %d order %d: %s", other, order, f.text.c_str());
+            CHECK(pjd_resize_affine_excludes(s) && std::string(pjd_resize_affine_excludes(s)) == names[other], "the excluded setter's name");
+        }
+    // the fault texts, with and without views
+    for (int views = 0; views < 2; views++) {
+        PjdResizeSpec s = small_spec(3, views != 0);
+        with_affine(s, ident);
+        s.affine[1].m[4] = std::nextafter(16.0, 17.0);     // quantises to 16 * 2^40: accepted
+        CHECK(pjd_resize_resolve(s, w).text.empty(), "16 + 1 ulp quantises to the limit");
+        s.affine[1].m[4] = 16.0 + std::ldexp(1.0, -40);    // the next quantised value
+        PjdResizeFault f = pjd_resize_resolve(s, w);
+        CHECK(!f.state && f.picture == 1 && f.text == std::string(views ? "view 1 (picture 1)" : "picture 1") + ": a coefficient of the linear part is beyond 16 in magnitude", "text: %s", f.text.c_str());
+        s.affine[1].m[4] = 1; s.affine[2].m[5] = -262144.0 - std::ldexp(1.0, -22);
+        f = pjd_resize_resolve(s, w);
+        CHECK(f.picture == 2 && f.text == std::string(views ? "view 2 (picture 0)" : "picture 2") + ": a translation is beyond 2^18 pixels in magnitude", "text: %s", f.text.c_str());
+        s.affine[2].m[5] = -262144.0; s.affine[0].m[0] = NAN;
+        f = pjd_resize_resolve(s, w);
+        CHECK(f.picture == 0 && f.text == std::string(views ? "view 0 (picture 2)" : "picture 0") + ": the matrix has a value that is not finite", "text: %s", f.text.c_str());
+        s.affine[0].m[0] = -16; s.affine[0].m[1] = 16; s.affine[0].m[2] = 262144.0;
+        CHECK(pjd_resize_resolve(s, w).text.empty(), "every limit met exactly");
+    }
+    CHECK(pjd_resize_affine_fault(0, 5, 5, 5, ident) && pjd_resize_affine_fault(5, 65536, 5, 5, ident) && pjd_resize_affine_fault(5, 5, 0, 5, ident) && pjd_resize_affine_fault(5, 5, 5, 65536, ident) &&
+          pjd_resize_affine_fault(5, 5, 5, 5, nullptr) && !pjd_resize_affine_fault(65535, 65535, 65535, 65535, ident), "sizes and null");
+    // a request without the call resolves to what it did: no warp record, no warp form
+    PjdResizeSpec plain = small_spec(2, false);
+    CHECK(pjd_resize_resolve(plain, w).text.empty() && !w.form.warp && w.warp.empty() && w.form.tiles == 2 * 4, "a request without a map is untouched");
+}
+
+int main()
+{
+    resolver_rules();
+    for (uint32_t mis = 0; mis < 4; mis++) {
+        run<false, 0, 3>(mis, 11 + mis); run<false, PJD_DT_F16, 3>(mis, 21 + mis); run<false, PJD_DT_BF16, 3>(mis, 31 + mis); run<false, PJD_DT_F32, 3>(mis, 41 + mis);
+        run<true, 0, 3>(mis, 51 + mis);  run<true, PJD_DT_F16, 3>(mis, 61 + mis);  run<true, PJD_DT_BF16, 3>(mis, 71 + mis);  run<true, PJD_DT_F32, 3>(mis, 81 + mis);
+        run<true, 0, 1>(mis, 91 + mis);  run<true, PJD_DT_F16, 1>(mis, 101 + mis); run<true, PJD_DT_BF16, 1>(mis, 111 + mis); run<true, PJD_DT_F32, 1>(mis, 121 + mis);
+    }
+    printf("%s, %d checks failed; no sanitizer report\n", failed ? "DIFFERENCES" : "ALL EQUAL", failed);
+    return failed ? 1 : 0;
+}
