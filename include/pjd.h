@@ -45,6 +45,9 @@
  *   (none: an addition)                                 pjd_batch_set_resize_affine + pjd_warp_tap + pjd_resize_affine_check: every output under
  *                                                       an inverse 2 x 3 map of its own -- rotation, scale, shear, translation, a fill outside --
  *                                                       in one launch (RandomRotation, RandomAffine, DALI warp_affine, RandAugment)
+ *   (none: an addition)                                 pjd_batch_set_colour + pjd_colour_value + pjd_colour_check: every output's 8-bit triple
+ *                                                       through a 3 x 4 colour map of its own inside that launch (ColorJitter,
+ *                                                       RandomGrayscale, BGR, DALI color_twist / hsv / brightness_contrast)
  *
  * Plain pointers and sizes only; no C++ or torch types.  Thread model: one
  * submitting thread per pjd_ctx (the reference has one consumer thread,
@@ -70,7 +73,8 @@ extern "C" {
  * knows PJD_F_LIBJPEG; an older one ignores the bit).  Pad on decode (pjd_batch_set_resize_pad, pjd_batch_set_pad_value) changed no
  * struct either, so PJD_VERSION stays 6: a caller checks for it by the symbol pjd_resize_pad_check.  Views (pjd_batch_set_views)
  * changed no struct: a caller checks for them by the symbol pjd_batch_n_outputs.  The affine warp (pjd_batch_set_resize_affine) changed
- * none: a caller checks for it by the symbol pjd_warp_tap.
+ * none: a caller checks for it by the symbol pjd_warp_tap.  The colour map (pjd_batch_set_colour) changed none: a caller checks for it
+ * by the symbol pjd_colour_value.
  * A caller built against another version must not pass its structs: check pjd_version() == PJD_VERSION after loading.     */
 #define PJD_VERSION 6
 
@@ -855,6 +859,47 @@ int  pjd_resize_pad_check(uint32_t out_w, uint32_t out_h, const pjd_resize_pad *
 int  pjd_batch_set_resize_affine(pjd_batch *b, const double (*m)[6] /* n outputs */, const uint8_t fill[3]);
 int  pjd_warp_tap(const double m[6], uint32_t i, uint32_t j, int64_t *x0, int64_t *y0, uint32_t *wx, uint32_t *wy);   /* host only */
 int  pjd_resize_affine_check(uint32_t sw, uint32_t sh, uint32_t tw, uint32_t th, const double m[6]);                /* host only */
+/* ---- colour map on decode: a 3 x 4 colour map per output ------------------------------------------------------------------------------ *
+ * pjd_batch_set_colour: output i of a resized batch -- picture i, or view i after pjd_batch_set_views -- has its resampled 8-bit triple
+ * (R, G, B) replaced by m[i] applied to it, twelve doubles, row-major: out[c] = m[4c] * R + m[4c+1] * G + m[4c+2] * B + m[4c+3], the last
+ * column in 8-bit levels.  Inside the one resample or warp launch, before the normalisation and the store: brightness, contrast about a
+ * constant, saturation, hue, grey, channel order and any product of them are one such matrix.
+ *
+ * THE ARITHMETIC (normative).  R, G, B are the samples the resample delivers: the 8-bit values that would be stored without this call,
+ * whatever filter, window, orientation or affine map made them.
+ * FIXED POINT, Q16.  q[c][k] = llrint(m[4c+k] * 65536) for k = 0..2 and o[c] = llrint(m[4c+3] * 65536): an IEEE double product with a power
+ * of two (exact), rounded to nearest even.  Then
+ *     out[c] = clamp((q[c][0] * R + q[c][1] * G + q[c][2] * B + o[c] + 32768) >> 16, 0, 255)
+ * Everything is 32-bit signed two's complement, the shift is arithmetic, and there is ONE clamp, at the end.
+ * LIMITS, checked on the quantised values: |q| <= 2^20 (|weight| <= 16) and |o| <= 2^28 (|offset| <= 4096 levels); every value finite.  No sum
+ * can wrap: 3 * 255 * 2^20 + 2^28 + 2^15 = 1 070 628 864 < 2^31.  Every product has operands of at most 24 signed bits (v_mad_i32_i24).
+ * CONSEQUENCES.  The identity, the six channel permutations, any 0/1 selection matrix and integer offsets are exact: q * v is a multiple
+ * of 65536, the rounding term shifts out.  Against the same map in float64, with x = m[4c] * R + m[4c+1] * G + m[4c+2] * B + m[4c+3]
+ * unrounded, |out - clamp(x, 0, 255)| <= 0.5 + 2^-7: the one rounding is half a level, and quantising the weights contributes at most
+ * (3 * 255 + 1) * 2^-17 = 0.00585 levels.
+ * ORDER.  The normalisation of pjd_batch_set_normalize reads out[c].  Under pjd_batch_set_resize_affine the fill takes part in the blend as
+ * any sample does, so it passes through the map (torchvision's order: RandomAffine before ColorJitter).  Under pjd_batch_set_resize_pad
+ * the border is not content: it stays the fill / the pad value as given, and the border launch is unchanged.
+ *
+ * CALL ORDER.  After pjd_batch_set_resize and whatever shapes the resample (pad, orientation, window, filter, affine map; after
+ * pjd_batch_set_views where used: one matrix per OUTPUT); before pjd_batch_set_normalize / _bind_output / _upload; once: PJD_E_STATE
+ * otherwise, also when no resize is set.  PJD_E_ARG for a PJD_OUT_GRAY8 batch (one plane has no colour map: gain and offset are the
+ * normalisation's), a null pointer, or a matrix pjd_colour_check refuses (pjd_last_error names the picture, or "view <v> (picture <p>)");
+ * the batch is then as it was and the call still open.
+ * COMPOSES WITH all three filters, windows, orientations, pad, views, the affine warp, pjd_batch_set_normalize (all element types),
+ * PJD_OUT_RGB8 and PJD_OUT_RGB8_PLANAR, pjd_batch_bind_output, PJD_F_LIBJPEG pictures, both scale families, captured graphs, and the
+ * exact-kernel fallback of pjd_batch_sync, behind which the launch runs again.
+ * FROM THEN ON everything pjd_batch_set_resize promises holds; pjd_batch_decode_timed keeps the names "resize", "pad" and "warp".  The
+ * 64-byte record per output is counted in pjd_batch_info::device_bytes and sent by pjd_batch_upload.  A map that is the identity after
+ * quantisation is skipped by the kernel (the same bytes: the identity is exact).  A batch that never makes the call allocates, uploads
+ * and launches what it did before.
+ * pjd_colour_value and pjd_colour_check are host only and THE implementations: the inline the kernels run, and the test the setter
+ * makes.  pjd_colour_value returns PJD_E_ARG for a null pointer or a matrix beyond the limits; pjd_colour_check returns 1 for a matrix the
+ * setter accepts and 0 for one it refuses (null included).
+ * DETECTION.  No struct changed and PJD_VERSION stays 6: a caller checks for the symbol pjd_colour_value.                         */
+int  pjd_batch_set_colour(pjd_batch *b, const double (*m)[12] /* pjd_batch_n_outputs(b) */);
+int  pjd_colour_value(const double m[12], const uint8_t rgb[3], uint8_t out[3]);   /* host only, no device needed */
+int  pjd_colour_check(const double m[12]);                                        /* host only: 1 ok, 0 refused */
 /* ---- normalised float output ------------------------------------------------------------------------------------------------- *
  * pjd_batch_set_normalize: the pictures of the batch leave the decode as floating-point elements, sample * scale[c] + bias[c] -- what
  * x.float().div(255).sub(mean).div(std).to(dtype) makes of the uint8 tensor, without that tensor ever existing.  The caller passes

@@ -228,6 +228,7 @@ struct pjd_batch {
     Pair pad;                                    // form.padded: PjdDevResizePad[n_out], then the prefix sum of their border lines [n_out + 1]
     Pair aa;                                     // a table-driven filter: PjdDevResizeAA[n_out], then the weight table
     Pair warp;                                   // form.warp (pjd_batch_set_resize_affine): PjdDevWarp[n_out]
+    Pair col;                                    // form.coloured (pjd_batch_set_colour): PjdDevColour[n_out]
     PjdNormalize norm{};                         // pjd_batch_set_normalize: dtype != 0, the result holds elements of PJD_DT_SIZE(dtype) bytes
     uint8_t pad_fill[3] = {0, 0, 0};             // pjd_batch_set_resize_pad
     bool pad_value_set = false;                  // pjd_batch_set_pad_value
@@ -241,7 +242,8 @@ struct pjd_batch {
         pjd_launch_resize(s, PjdResizeLaunch{dev.out, res_out, (const PjdDevResize *)rs.d, (const uint32_t *)(rs.d + n * sizeof(PjdDevResize)), (uint32_t)n, form.tiles, planar, norm,
                                              form.windowed ? (const PjdDevResizeWin *)win.d : nullptr, form.oriented, spec.filter,
                                              (const PjdDevResizeAA *)aa.d, aa.d ? (const uint32_t *)(aa.d + n * sizeof(PjdDevResizeAA)) : nullptr, form.lds,
-                                             form.padded ? (const PjdDevResizePad *)pad.d : nullptr, spec.channels});
+                                             form.padded ? (const PjdDevResizePad *)pad.d : nullptr, spec.channels,
+                                             form.coloured ? (const PjdDevColour *)col.d : nullptr});
     }
     // the affine warp of this batch (form.warp), in place of the two launches around it: it writes the fill too
     void launch_warp(hipStream_t s) const
@@ -249,7 +251,8 @@ struct pjd_batch {
         const size_t n = n_out();
         const uint8_t *f = spec.affine_fill;
         pjd_launch_warp(s, PjdWarpLaunch{dev.out, res_out, (const PjdDevResize *)rs.d, (const PjdDevWarp *)warp.d, (const uint32_t *)(rs.d + n * sizeof(PjdDevResize)), (uint32_t)n, form.tiles,
-                                         back.planes(), norm, (uint32_t)f[0] | ((uint32_t)f[1] << 8) | ((uint32_t)f[2] << 16), spec.channels});
+                                         back.planes(), norm, (uint32_t)f[0] | ((uint32_t)f[1] << 8) | ((uint32_t)f[2] << 16), spec.channels,
+                                         form.coloured ? (const PjdDevColour *)col.d : nullptr});
     }
     // ... and the border of its padded pictures, behind it: the two write disjoint bytes
     void launch_pad(hipStream_t s) const
@@ -308,12 +311,14 @@ int commit_request(pjd_batch *b, PjdResizeSpec &spec, const PjdResizeWork &w)
     if (rc == PJD_OK && w.form.padded) rc = take_pair(b, b->pad, n * sizeof(PjdDevResizePad) + (n + 1) * sizeof(uint32_t));
     if (rc == PJD_OK && spec.filter != PJD_RESIZE_BILINEAR) rc = take_pair(b, b->aa, n * sizeof(PjdDevResizeAA) + w.tab.size() * sizeof(uint32_t));
     if (rc == PJD_OK && w.form.warp) rc = take_pair(b, b->warp, n * sizeof(PjdDevWarp));
+    if (rc == PJD_OK && w.form.coloured) rc = take_pair(b, b->col, n * sizeof(PjdDevColour));
     if (rc != PJD_OK) return rc;
     put(b->rs, w.recs, w.tile_prefix);
     if (w.form.windowed) put(b->win, w.win);
     if (w.form.padded) put(b->pad, w.pad, w.line_prefix);
     if (spec.filter != PJD_RESIZE_BILINEAR) put(b->aa, w.aa, w.tab);
     if (w.form.warp) put(b->warp, w.warp);
+    if (w.form.coloured) put(b->col, w.colour);
     b->spec = std::move(spec);
     b->form = w.form;
     return PJD_OK;
@@ -337,7 +342,7 @@ void set_result_offsets(pjd_batch *b, const std::vector<uint64_t> &off)
 
 // The order of the calls that shape a batch (include/pjd.h, CALL ORDER): the stages, each passed at most once but for the
 // last two.  A new setter is a row here, at its place.
-enum Stage { ST_NONE = -1, ST_VIEWS, ST_RESIZE, ST_PAD, ST_ORIENTATION, ST_WINDOW, ST_FILTER, ST_AFFINE, ST_NORMALIZE, ST_PAD_VALUE, ST_BIND, ST_UPLOAD, N_STAGES };
+enum Stage { ST_NONE = -1, ST_VIEWS, ST_RESIZE, ST_PAD, ST_ORIENTATION, ST_WINDOW, ST_FILTER, ST_AFFINE, ST_COLOUR, ST_NORMALIZE, ST_PAD_VALUE, ST_BIND, ST_UPLOAD, N_STAGES };
 struct StageRule {
     const char *name;                          // the call, as the messages spell it
     bool (*passed)(const pjd_batch *);         // has the batch been through it?
@@ -353,6 +358,7 @@ const StageRule STAGES[N_STAGES] = {
     {"set_resize_window", [](const pjd_batch *b) { return b->spec.win_set; },    false, {ST_RESIZE, ST_NONE},   ""},
     {"set_resize_filter", [](const pjd_batch *b) { return b->spec.filter_set; }, false, {ST_RESIZE, ST_NONE},   ""},
     {"set_resize_affine", [](const pjd_batch *b) { return b->spec.affine_set; }, false, {ST_RESIZE, ST_NONE},   ""},
+    {"set_colour",        [](const pjd_batch *b) { return b->spec.colour_set; }, false, {ST_RESIZE, ST_NONE},   ""},
     {"set_normalize",     [](const pjd_batch *b) { return b->norm.dtype != 0; }, false, {ST_NONE, ST_NONE},     "the batch is not normalised (pjd_batch_set_normalize first)"},
     {"set_pad_value",     [](const pjd_batch *b) { return b->pad_value_set; },   false, {ST_PAD, ST_NORMALIZE}, ""},
     {"bind_output",       [](const pjd_batch *b) { return b->bound; },           true,  {ST_NONE, ST_NONE},     ""},
@@ -638,6 +644,7 @@ int pjd_batch_upload(pjd_batch *b)
     if (b->form.windowed) HIP_TRY(ctx, hipMemcpyAsync(b->win.d, b->win.h, b->win.bytes, hipMemcpyHostToDevice, s));  // ... and its source windows
     if (b->form.padded) HIP_TRY(ctx, hipMemcpyAsync(b->pad.d, b->pad.h, b->pad.bytes, hipMemcpyHostToDevice, s));    // ... and its canvases
     if (b->form.warp) HIP_TRY(ctx, hipMemcpyAsync(b->warp.d, b->warp.h, b->warp.bytes, hipMemcpyHostToDevice, s));   // ... or its affine maps
+    if (b->form.coloured) HIP_TRY(ctx, hipMemcpyAsync(b->col.d, b->col.h, b->col.bytes, hipMemcpyHostToDevice, s));  // ... and its colour maps
     // What depends on the blob alone is made here, once per upload, behind its copy: the decode tables of every table set (the exact
     // path uses them too) and the lanes' word rows.  No kernel of a decode writes either, so every decode of
     // the resident batch -- launched or replayed from its graphs -- reads what this upload left.
@@ -1347,6 +1354,34 @@ int pjd_batch_set_resize_affine(pjd_batch *b, const double (*m)[6], const uint8_
     for (size_t i = 0; i < spec.pic.size(); i++) std::memcpy(spec.affine[i].m, m[i], sizeof spec.affine[i].m);
     std::memcpy(spec.affine_fill, fill, 3);
     return apply_request(b, spec, "set_resize_affine");
+}
+
+int pjd_colour_check(const double m[12])
+{
+    PjdDevColour rec;
+    return m && !pjd_colour_quantise(m, rec) ? 1 : 0;
+}
+
+int pjd_colour_value(const double m[12], const uint8_t rgb[3], uint8_t out[3])
+{
+    PjdDevColour rec;
+    if (!m || !rgb || !out || pjd_colour_quantise(m, rec)) return PJD_E_ARG;
+    for (int c = 0; c < 3; c++) out[c] = (uint8_t)pjd_colour_calc(rec.q[c], rec.o[c] + 32768, rgb[0], rgb[1], rgb[2]);
+    return PJD_OK;
+}
+
+int pjd_batch_set_colour(pjd_batch *b, const double (*m)[12])
+{
+    if (!b) return PJD_E_ARG;
+    pjd_ctx *ctx = b->ctx;
+    if (int rc = check_order(b, ST_COLOUR)) return rc;
+    if (b->back.gray()) { ctx->err = "set_colour: a grey batch has no colour map (one plane: gain and offset are pjd_batch_set_normalize's)"; return PJD_E_ARG; }
+    if (!m) { ctx->err = "set_colour: null matrix array"; return PJD_E_ARG; }
+    PjdResizeSpec spec = b->spec;
+    spec.colour_set = true;
+    spec.colour.resize(spec.pic.size());
+    for (size_t i = 0; i < spec.pic.size(); i++) std::memcpy(spec.colour[i].m, m[i], sizeof spec.colour[i].m);
+    return apply_request(b, spec, "set_colour");
 }
 
 int pjd_resize_pad_check(uint32_t out_w, uint32_t out_h, const pjd_resize_pad *pad)

@@ -621,3 +621,38 @@ static inline __host__ __device__ void pjd_warp_tap_calc(const PjdDevWarp &m, ui
     pjd_warp_fix(pjd_warp_pos(m.a00, m.a01, m.b0, i, j), x0, wx);
     pjd_warp_fix(pjd_warp_pos(m.a10, m.a11, m.b1, i, j), y0, wy);
 }
+
+// ---- colour map (pjd_batch_set_colour; the arithmetic is normative: include/pjd.h) ----------------------------------------------
+// The 3 x 4 map of one output in Q16, as the coloured kernels (pjd_k_resize_col*, pjd_k_warp_col) read it beside the output's
+// PjdDevResize: q[c][k] = llrint(m[4c + k] * 65536), o[c] = llrint(m[4c + 3] * 65536).  64 bytes, so that a wave reads its record with
+// scalar loads of whole lines.  Made by pjd_colour_quantise (pjd_resize_plan.cpp), which also holds the limits: |q| <= 2^20 and
+// |o| <= 2^28, so that no sum of pjd_colour_calc wraps: 3 * 255 * 2^20 + 2^28 + 2^15 < 2^31.
+#define PJD_COL_IDENTITY 1u            // flags: q is 65536 * I and o is 0 -- the map changes no sample, and the kernels skip it
+struct PjdDevColour {
+    int32_t q[3][3], o[3];
+    uint32_t flags;
+    uint32_t pad_[3];
+};
+// THE implementation of one sample triple: pjd_colour_value exports it to the host, colour_px of pjd_k_resize_store.h runs it per pixel.
+// r, g, b are 8-bit samples and |q| <= 2^20: every product has operands within 24 signed bits, so the 32-bit product of the host text
+// is the value of the device's 24-bit multiply-add.  half = o[c] + 32768, the rounding add folded in: three multiply-adds, a shift, one
+// med3.  Written as instructions on the device, as pjd_mul_i24 of pjd_device_common.h is and for its reason: the compiler does not see
+// the range of a weight it loads, and where it is told (a sign extension) it pairs two multiplies with an add instead of chaining
+// three multiply-adds, at a register cost that takes a wave per SIMD from pjd_k_resize_col<planar, uint8> (169 VGPRs against 152:
+// figures of the compiler's output, not measured times; profiles/colour_matrix.md).  So the host and the device run two texts of
+// one arithmetic, and what holds them together is the byte equality of tests/test_gpu_colour.py against tests/colour_model.py, which
+// tests/test_colour_cpu.py holds the host text to.
+// The weights are wave-uniform (the record of the tile's output): the "s" operands.
+static inline __host__ __device__ uint32_t pjd_colour_calc(const int32_t (&q)[3], int32_t half, uint32_t r, uint32_t g, uint32_t b)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    int32_t s = half;
+    asm("v_mad_i32_i24 %0, %1, %2, %0" : "+v"(s) : "s"(q[0]), "v"(r));
+    asm("v_mad_i32_i24 %0, %1, %2, %0" : "+v"(s) : "s"(q[1]), "v"(g));
+    asm("v_mad_i32_i24 %0, %1, %2, %0" : "+v"(s) : "s"(q[2]), "v"(b));
+    s >>= 16;
+#else
+    const int32_t s = (q[0] * (int32_t)r + q[1] * (int32_t)g + q[2] * (int32_t)b + half) >> 16;
+#endif
+    return (uint32_t)(s < 0 ? 0 : s > 255 ? 255 : s);
+}

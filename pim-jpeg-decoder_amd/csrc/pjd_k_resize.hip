@@ -69,6 +69,8 @@ pjd_k_resize(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, const P
     constexpr int DT = 0;
     constexpr bool WIN = false, ORI = false, PAD = false;
     constexpr int NC = 3;
+    constexpr bool COL = false;
+    const PjdDevColour *const colour = nullptr;
     const PjdDevResizePad *const pad = nullptr;
     const PjdDevResizeWin *const win = nullptr;
     const NormArgs nz{};
@@ -82,6 +84,8 @@ pjd_k_resize_norm(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, co
 {
     constexpr bool WIN = false, ORI = false, PAD = false;
     constexpr int NC = 3;
+    constexpr bool COL = false;
+    const PjdDevColour *const colour = nullptr;
     const PjdDevResizePad *const pad = nullptr;
     const PjdDevResizeWin *const win = nullptr;
 #include "pjd_k_resize_body.h"
@@ -95,6 +99,8 @@ pjd_k_resize_win(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, con
 {
     constexpr bool WIN = true, ORI = false, PAD = false;
     constexpr int NC = 3;
+    constexpr bool COL = false;
+    const PjdDevColour *const colour = nullptr;
     const PjdDevResizePad *const pad = nullptr;
 #include "pjd_k_resize_body.h"
 }
@@ -108,6 +114,8 @@ pjd_k_resize_aa(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, cons
     extern __shared__ uint32_t seg[];                      // one source row's segment (three plane segments where PLANAR)
     constexpr bool WIN = false, ORI = false, PAD = false;
     constexpr int NC = 3;
+    constexpr bool COL = false;
+    const PjdDevColour *const colour = nullptr;
     const PjdDevResizePad *const pad = nullptr;
     constexpr int FILT = PJD_RESIZE_ANTIALIAS;
     const PjdDevResizeWin *const win = nullptr;
@@ -123,6 +131,8 @@ pjd_k_resize_win_aa(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, 
     extern __shared__ uint32_t seg[];
     constexpr bool WIN = true, ORI = false, PAD = false;
     constexpr int NC = 3;
+    constexpr bool COL = false;
+    const PjdDevColour *const colour = nullptr;
     const PjdDevResizePad *const pad = nullptr;
     constexpr int FILT = PJD_RESIZE_ANTIALIAS;
 #include "pjd_k_resize_aa_body.h"
@@ -138,6 +148,8 @@ pjd_k_resize_cubic(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, c
     extern __shared__ uint32_t seg[];
     constexpr bool WIN = false, ORI = false, PAD = false;
     constexpr int NC = 3;
+    constexpr bool COL = false;
+    const PjdDevColour *const colour = nullptr;
     const PjdDevResizePad *const pad = nullptr;
     constexpr int FILT = PJD_RESIZE_BICUBIC;
     const PjdDevResizeWin *const win = nullptr;
@@ -153,6 +165,8 @@ pjd_k_resize_win_cubic(const uint8_t *__restrict__ src, uint8_t *__restrict__ ds
     extern __shared__ uint32_t seg[];
     constexpr bool WIN = true, ORI = false, PAD = false;
     constexpr int NC = 3;
+    constexpr bool COL = false;
+    const PjdDevColour *const colour = nullptr;
     const PjdDevResizePad *const pad = nullptr;
     constexpr int FILT = PJD_RESIZE_BICUBIC;
 #include "pjd_k_resize_aa_body.h"
@@ -169,6 +183,8 @@ pjd_k_resize_ori(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, con
 {
     constexpr bool WIN = true, ORI = true, PAD = false;
     constexpr int NC = 3;
+    constexpr bool COL = false;
+    const PjdDevColour *const colour = nullptr;
     const PjdDevResizePad *const pad = nullptr;
 #include "pjd_k_resize_body.h"
 }
@@ -182,6 +198,8 @@ pjd_k_resize_ori_tab(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst,
     extern __shared__ uint32_t seg[];
     constexpr bool WIN = true, ORI = true, PAD = false;
     constexpr int NC = 3;
+    constexpr bool COL = false;
+    const PjdDevColour *const colour = nullptr;
     const PjdDevResizePad *const pad = nullptr;
 #include "pjd_k_resize_aa_body.h"
 }
@@ -197,6 +215,8 @@ pjd_k_resize_pad(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, con
 {
     constexpr bool WIN = true, ORI = true, PAD = true;
     constexpr int NC = 3;
+    constexpr bool COL = false;
+    const PjdDevColour *const colour = nullptr;
 #include "pjd_k_resize_body.h"
 }
 
@@ -210,6 +230,8 @@ pjd_k_resize_pad_tab(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst,
     extern __shared__ uint32_t seg[];
     constexpr bool WIN = true, ORI = true, PAD = true;
     constexpr int NC = 3;
+    constexpr bool COL = false;
+    const PjdDevColour *const colour = nullptr;
 #include "pjd_k_resize_aa_body.h"
 }
 
@@ -225,6 +247,8 @@ pjd_k_resize_gray(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, co
 {
     constexpr bool PLANAR = true, WIN = true, ORI = true, PAD = true;
     constexpr int NC = 1;
+    constexpr bool COL = false;
+    const PjdDevColour *const colour = nullptr;
 #include "pjd_k_resize_body.h"
 }
 
@@ -238,6 +262,37 @@ pjd_k_resize_gray_tab(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst
     extern __shared__ uint32_t seg[];
     constexpr bool PLANAR = true, WIN = true, ORI = true, PAD = true;
     constexpr int NC = 1;
+    constexpr bool COL = false;
+    const PjdDevColour *const colour = nullptr;
+#include "pjd_k_resize_aa_body.h"
+}
+
+// A colour map (pjd_batch_set_colour): every output's 8-bit triple through a 3 x 4 map of its own, between the blend and the store
+// (colour_px of pjd_k_resize_store.h; normative in include/pjd.h).  A lane holds all three channels of its pixels in registers at that
+// point, so the map needs no LDS, no pass of its own and no change to either epilogue.  Routed through the most general form alone, as
+// a grey batch is and for the same reason: 8 + 16 instantiations, not sixty more.  The same bodies with COL; kernels of their own, so
+// that a batch without a colour map launches exactly what it launched before (profiles/colour_matrix.md).
+template <bool PLANAR, int DT>
+__global__ void __launch_bounds__(64 * PJD_RS_WAVES)
+pjd_k_resize_col(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, const PjdDevResize *__restrict__ recs,
+                 const PjdDevResizeWin *__restrict__ win, const PjdDevResizePad *__restrict__ pad, const PjdDevColour *__restrict__ colour,
+                 const uint32_t *__restrict__ tile_prefix, uint32_t n_images, uint32_t n_tiles, const NormArgs nz)
+{
+    constexpr bool WIN = true, ORI = true, PAD = true, COL = true;
+    constexpr int NC = 3;
+#include "pjd_k_resize_body.h"
+}
+
+template <bool PLANAR, int DT, int FILT>
+__global__ void __launch_bounds__(64)
+pjd_k_resize_col_tab(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, const PjdDevResize *__restrict__ recs,
+                     const PjdDevResizeWin *__restrict__ win, const PjdDevResizePad *__restrict__ pad, const PjdDevColour *__restrict__ colour,
+                     const uint32_t *__restrict__ tile_prefix, uint32_t n_images, uint32_t n_tiles, const PjdDevResizeAA *__restrict__ aa,
+                     const uint32_t *__restrict__ tab, uint32_t lds_bytes, const NormArgs nz)
+{
+    extern __shared__ uint32_t seg[];
+    constexpr bool WIN = true, ORI = true, PAD = true, COL = true;
+    constexpr int NC = 3;
 #include "pjd_k_resize_aa_body.h"
 }
 
@@ -291,6 +346,15 @@ void pjd_launch_resize(hipStream_t s, const PjdResizeLaunch &a)
                 hipLaunchKernelGGL((pjd_k_resize_gray_tab<DT, PJD_RESIZE_ANTIALIAS>), grid, block, a.lds_bytes, s, a.src, a.dst, a.recs, a.win, a.pad, a.tile_prefix, a.n_images, a.n_tiles, a.aa, a.tab, a.lds_bytes, nz);
             else
                 hipLaunchKernelGGL((pjd_k_resize_gray<DT>), grid, block, 0, s, a.src, a.dst, a.recs, a.win, a.pad, a.tile_prefix, a.n_images, a.n_tiles, nz);
+            return;
+        }
+        if (a.colour) {                                    // a coloured batch: three channels, always with win and pad records
+            if (a.filter == PJD_RESIZE_BICUBIC)
+                hipLaunchKernelGGL((pjd_k_resize_col_tab<PL, DT, PJD_RESIZE_BICUBIC>), grid, block, a.lds_bytes, s, a.src, a.dst, a.recs, a.win, a.pad, a.colour, a.tile_prefix, a.n_images, a.n_tiles, a.aa, a.tab, a.lds_bytes, nz);
+            else if (tabled)
+                hipLaunchKernelGGL((pjd_k_resize_col_tab<PL, DT, PJD_RESIZE_ANTIALIAS>), grid, block, a.lds_bytes, s, a.src, a.dst, a.recs, a.win, a.pad, a.colour, a.tile_prefix, a.n_images, a.n_tiles, a.aa, a.tab, a.lds_bytes, nz);
+            else
+                hipLaunchKernelGGL((pjd_k_resize_col<PL, DT>), grid, block, 0, s, a.src, a.dst, a.recs, a.win, a.pad, a.colour, a.tile_prefix, a.n_images, a.n_tiles, nz);
             return;
         }
         if (a.pad && a.filter == PJD_RESIZE_BICUBIC)

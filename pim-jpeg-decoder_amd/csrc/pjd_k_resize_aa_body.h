@@ -15,9 +15,9 @@
 // No lane leaves before the last barrier; lanes right of the picture compute its last column and store nothing.
 // A textual include, so that tools/resize_host.cpp runs this very text on the host; PJD_WIN_STAGE_FIRST / _STEP say which dwords of a
 // segment this thread stages (its own of the wave's 64 here; all of them where a thread runs alone).
-// In scope: PLANAR, DT, WIN, ORI (implies WIN), PAD (implies ORI), FILT, NC (compile-time constants; NC: the channels, 3, or 1 only where PLANAR: ONE plane segment in LDS), seg (LDS), src, dst, recs, win (read only where WIN),
+// In scope: PLANAR, DT, WIN, ORI (implies WIN), PAD (implies ORI), COL (colour is read; NC is 3), FILT, NC (compile-time constants; NC: the channels, 3, or 1 only where PLANAR: ONE plane segment in LDS), seg (LDS), src, dst, recs, win (read only where WIN),
 // pad (read only where PAD), tile_prefix, n_images,
-// n_tiles, aa, tab, lds_bytes, nz; store_row and store_cols.
+// n_tiles, aa, tab, lds_bytes, nz, colour (read only where COL, which implies ORI); colour_tile, store_row and store_cols.
 #ifndef PJD_WIN_STAGE_FIRST
 #define PJD_WIN_STAGE_FIRST lane
 #define PJD_WIN_STAGE_STEP  64u
@@ -33,6 +33,8 @@
     const PjdDevResize r = recs[lo];
     const PjdDevResizeWin w = WIN ? win[lo] : pjd_resize_win_identity(r);
     const PjdDevResizeAA a = aa[lo];
+    PjdDevColour cm{};                                     // COL (pjd_batch_set_colour): the map of this OUTPUT, as in pjd_k_resize_body.h
+    if constexpr (COL) cm = colour[lo];
     const uint32_t t = tile - tile_prefix[lo];
     const uint32_t row0 = (t / r.col_tiles) * PJD_RS_ROWS;
     const uint32_t colt = (t % r.col_tiles) * PJD_RS_COLS;
@@ -145,6 +147,36 @@
         }
     }
 
+    // With COL (pjd_batch_set_colour) the whole tile is finished in place first and goes through the output's map under one branch
+    // (colour_tile); rows below the picture hold zeros, are mapped with the rest and never stored.  Then the two epilogues, as below:
+    // the store_cols call and the store_row loop here are COPIES of the ones behind this block, less their tap_out, and must stay in
+    // step with them -- an argument changed there is changed here.  The text behind this block was left word for word as it was, so
+    // that the uncoloured kernels keep their instructions (tools/kernel_text.py compares them with the commit before); sharing one
+    // store loop between the two has not been tried against that comparison.
+    if constexpr (COL) {
+#pragma unroll
+        for (int k = 0; k < PJD_RS_ROWS; k++)
+#pragma unroll
+            for (int c = 0; c < NC; c++)
+#pragma unroll
+                for (int q = 0; q < PJD_RS_PX; q++) acc[k][c][q] = tap_out<FILT>(acc[k][c][q]);
+        colour_tile(acc, cm);
+        if (w.flags & PJD_RWI_TRANSPOSE) {                 // uniform
+            store_cols<PLANAR, DT, NC>(acc, dp, row0, r.th - row0 < PJD_RS_ROWS ? r.th - row0 : PJD_RS_ROWS, col0, n_px, (w.flags & PJD_RWI_YMIRROR) != 0, r.th, PAD ? cv.W : r.th, dst_plane, nz);
+            return;
+        }
+#pragma unroll
+        for (int k = 0; k < PJD_RS_ROWS; k++) {
+            if (row0 + k >= r.th) break;                   // uniform
+            uint32_t px[3][PJD_RS_PX];
+#pragma unroll
+            for (int c = 0; c < NC; c++)
+#pragma unroll
+                for (int q = 0; q < PJD_RS_PX; q++) px[c][q] = acc[k][c][q];
+            store_row<PLANAR, DT, NC>(px, dp, (w.flags & PJD_RWI_YMIRROR) ? r.th - 1u - (row0 + k) : row0 + k, col0, n_px, dst_plane, dst_stride, nz);
+        }
+        return;
+    }
     // With ORI (pjd_batch_set_orientation) the picture's flags say where the rows go: a transposed picture's leave as columns
     // (store_cols), another one's at their own place or its mirror image.  The mirror is in the STORE row: the span ys..ye above
     // assumes that the tile's taps ascend with its rows.

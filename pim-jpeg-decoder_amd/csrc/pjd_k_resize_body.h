@@ -12,8 +12,8 @@
 // text on the host.
 // With ORI (which implies WIN) the store side reads the orientation of pjd_batch_set_orientation from the window's flags (PJD_RWI_* of
 // pjd_internal.h); the read side does not know of it: the tap mirror is the bit PJD_RW_HFLIP has.
-// In scope: PLANAR, DT, WIN, ORI, PAD, NC (compile-time constants; PAD implies ORI; NC: the channels, 3, or 1 only where PLANAR -- a grey batch), src, dst, recs, win (read only where WIN), pad (read only where PAD), tile_prefix, n_images, n_tiles, nz
-// (NormArgs; read only where DT != 0; r.dst_off stays a byte offset); lerp8, store_row and store_cols.
+// In scope: PLANAR, DT, WIN, ORI, PAD, COL, NC (compile-time constants; PAD implies ORI; COL: colour is read, NC is 3; NC: the channels, 3, or 1 only where PLANAR -- a grey batch), src, dst, recs, win (read only where WIN), pad (read only where PAD), colour (read only where COL), tile_prefix, n_images, n_tiles, nz
+// (NormArgs; read only where DT != 0; r.dst_off stays a byte offset); lerp8, colour_px, store_row and store_cols.
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t tile = __builtin_amdgcn_readfirstlane(blockIdx.x * PJD_RS_WAVES + (threadIdx.x >> 6));
     if (tile >= n_tiles) return;
@@ -25,6 +25,8 @@
     }
     const PjdDevResize r = recs[lo];
     const PjdDevResizeWin w = WIN ? win[lo] : pjd_resize_win_identity(r);
+    PjdDevColour cm{};                                     // COL (pjd_batch_set_colour): the map of this OUTPUT, wave-uniform as r and w are
+    if constexpr (COL) cm = colour[lo];
     const uint32_t t = tile - tile_prefix[lo];
     const uint32_t row0 = (t / r.col_tiles) * PJD_RS_ROWS;
     const uint32_t col0 = (t % r.col_tiles) * PJD_RS_COLS + lane * PJD_RS_PX;
@@ -78,6 +80,7 @@
                 px[c][q] = (__umul24(256u - wy, top) + __umul24(wy, bot) + 32768u) >> 16;
             }
         }
+        if constexpr (COL) colour_px(px, cm);              // the finished row, all three channels in registers: before either epilogue
         // The epilogue is one text in two forms, and the form is the only thing the two sides do not share: the kernels without a window
         // include it here, the windowed ones (and the antialiased body) call it as store_row.  The split is for the compiler's sake
         // alone: at -O3 either swap changes the instructions of all eight kernels of the side swapped (profiles/resize_unified.md), and

@@ -50,6 +50,39 @@ __device__ __forceinline__ uint32_t norm_pair16(uint32_t v0, uint32_t v1, float 
     return __builtin_bit_cast(uint32_t, __builtin_convertvector(u, bf16x2));
 }
 
+// The colour map of pjd_batch_set_colour (the kernels built with COL; normative in include/pjd.h) on a lane's finished row: every pixel's
+// 8-bit triple through the output's 3 x 4 map in Q16 -- per sample three 24-bit multiply-adds (the first takes o + 32768), a shift and
+// one med3 (pjd_colour_calc of pjd_internal.h, the code pjd_colour_value exports).  `m` is the record of the tile's OUTPUT: wave-uniform,
+// read through the index that picks recs[lo], so it lies in scalar registers and the multiplies take their weights from there.  A
+// record flagged PJD_COL_IDENTITY skips the arithmetic under a wave-uniform branch: the same bytes, since the identity is exact.
+__device__ __forceinline__ void colour_px(uint32_t (&px)[3][PJD_RS_PX], const PjdDevColour &m)
+{
+    if (m.flags & PJD_COL_IDENTITY) return;                // uniform
+    const int32_t half[3] = {m.o[0] + 32768, m.o[1] + 32768, m.o[2] + 32768};
+#pragma unroll
+    for (int q = 0; q < PJD_RS_PX; q++) {
+        const uint32_t r = px[0][q], g = px[1][q], b = px[2][q];
+#pragma unroll
+        for (int c = 0; c < 3; c++) px[c][q] = pjd_colour_calc(m.q[c], half[c], r, g, b);
+    }
+}
+
+// ... and on all finished rows of a tile at once, in place, under ONE such branch (the table-driven body, which holds the whole tile in
+// its accumulators: a branch per row there costs a third of the kernel's registers -- 205 VGPRs against 146, profiles/colour_matrix.md)
+__device__ __forceinline__ void colour_tile(uint32_t (&px)[PJD_RS_ROWS][3][PJD_RS_PX], const PjdDevColour &m)
+{
+    if (m.flags & PJD_COL_IDENTITY) return;                // uniform
+    const int32_t half[3] = {m.o[0] + 32768, m.o[1] + 32768, m.o[2] + 32768};
+#pragma unroll
+    for (int k = 0; k < PJD_RS_ROWS; k++)
+#pragma unroll
+        for (int q = 0; q < PJD_RS_PX; q++) {
+            const uint32_t r = px[k][0][q], g = px[k][1][q], b = px[k][2][q];
+#pragma unroll
+            for (int c = 0; c < 3; c++) px[k][c][q] = pjd_colour_calc(m.q[c], half[c], r, g, b);
+        }
+}
+
 // NC: the channels stored, 3, or 1 only where PLANAR (a grey batch: one plane)
 template <bool PLANAR, int DT, int NC = 3>
 __device__ __forceinline__ void store_row(const uint32_t (&px)[3][PJD_RS_PX], uint8_t *dp, uint32_t row, uint32_t col0, uint32_t n_px,

@@ -10,7 +10,8 @@
 // stores where the address has their alignment.  The source is read with byte loads; neighbouring lanes' taps fall into the same or
 // adjacent cache lines whatever the angle.  No LDS, no scratch.
 //
-// Twelve kernels: interleaved and planar x (uint8, fp16, bf16, fp32) with three channels, and the one-plane form of a grey batch.
+// Twelve kernels: interleaved and planar x (uint8, fp16, bf16, fp32) with three channels, and the one-plane form of a grey batch;
+// eight more with a colour map (pjd_k_warp_col).
 // Wave-uniform values -- the record of the output, the fill, the six constants of a normalised launch -- come through readfirstlane
 // and the kernel arguments.
 #include <hip/hip_runtime.h>
@@ -30,6 +31,21 @@ pjd_k_warp(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, const Pjd
            const uint32_t *__restrict__ tile_prefix, uint32_t n_images, uint32_t n_tiles, uint32_t fill, const NormArgs nz)
 {
     static_assert(NC == 3 || (NC == 1 && PLANAR), "one channel is one plane");
+    constexpr bool COL = false;
+    const PjdDevColour *const colour = nullptr;
+#include "pjd_k_warp_body.h"
+}
+
+// With a colour map (pjd_batch_set_colour): the same body with COL -- colour_px of pjd_k_resize_store.h on every finished row, the
+// fill included -- in kernels of their own, so that a batch without one launches exactly what it launched before.  Three channels.
+template <bool PLANAR, int DT>
+__global__ void __launch_bounds__(64 * PJD_WARP_WAVES)
+pjd_k_warp_col(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, const PjdDevResize *__restrict__ recs, const PjdDevWarp *__restrict__ warp,
+               const PjdDevColour *__restrict__ colour, const uint32_t *__restrict__ tile_prefix, uint32_t n_images, uint32_t n_tiles, uint32_t fill,
+               const NormArgs nz)
+{
+    constexpr bool COL = true;
+    constexpr int NC = 3;
 #include "pjd_k_warp_body.h"
 }
 
@@ -45,6 +61,18 @@ void launch(hipStream_t s, const PjdWarpLaunch &a, const NormArgs &nz)
     }
 }
 
+template <bool PLANAR>
+void launch_col(hipStream_t s, const PjdWarpLaunch &a, const NormArgs &nz)
+{
+    const dim3 grid((a.n_tiles + PJD_WARP_WAVES - 1) / PJD_WARP_WAVES), block(64 * PJD_WARP_WAVES);
+    switch (a.norm.dtype) {
+    case 0:           hipLaunchKernelGGL((pjd_k_warp_col<PLANAR, 0>), grid, block, 0, s, a.src, a.dst, a.recs, a.warp, a.colour, a.tile_prefix, a.n_images, a.n_tiles, a.fill, nz); break;
+    case PJD_DT_F16:  hipLaunchKernelGGL((pjd_k_warp_col<PLANAR, PJD_DT_F16>), grid, block, 0, s, a.src, a.dst, a.recs, a.warp, a.colour, a.tile_prefix, a.n_images, a.n_tiles, a.fill, nz); break;
+    case PJD_DT_BF16: hipLaunchKernelGGL((pjd_k_warp_col<PLANAR, PJD_DT_BF16>), grid, block, 0, s, a.src, a.dst, a.recs, a.warp, a.colour, a.tile_prefix, a.n_images, a.n_tiles, a.fill, nz); break;
+    default:          hipLaunchKernelGGL((pjd_k_warp_col<PLANAR, PJD_DT_F32>), grid, block, 0, s, a.src, a.dst, a.recs, a.warp, a.colour, a.tile_prefix, a.n_images, a.n_tiles, a.fill, nz); break;
+    }
+}
+
 }  // namespace
 
 void pjd_launch_warp(hipStream_t s, const PjdWarpLaunch &a)
@@ -52,7 +80,8 @@ void pjd_launch_warp(hipStream_t s, const PjdWarpLaunch &a)
     if (a.n_tiles == 0) return;
     NormArgs nz{};
     for (int c = 0; c < 3; c++) { nz.scale[c] = a.norm.scale[c]; nz.bias[c] = a.norm.bias[c]; }
-    if (a.channels == 1) launch<true, 1>(s, a, nz);        // a grey batch: planar, one plane
+    if (a.colour) { if (a.planar) launch_col<true>(s, a, nz); else launch_col<false>(s, a, nz); }   // a coloured batch: three channels
+    else if (a.channels == 1) launch<true, 1>(s, a, nz);   // a grey batch: planar, one plane
     else if (a.planar) launch<true, 3>(s, a, nz);
     else launch<false, 3>(s, a, nz);
 }

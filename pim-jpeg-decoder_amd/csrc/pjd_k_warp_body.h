@@ -15,8 +15,8 @@
 // Measured on the MI355X against 32 x 64, 64 x 32, 128 x 16 and the resize tile's 256 x 8 (the same text, -DPJD_WARP_LX / -DPJD_WARP_RPL):
 // pure scaling 0.44 / 0.50 / 0.40 / 0.41 / 0.41 ms, a quarter turn 0.54 / 0.56 / 1.13 / 1.51 / 2.03 ms for the 1024-picture batch
 // (profiles/affine_warp.md).  No LDS.
-// In scope: PLANAR, DT, NC (compile-time constants; NC 3, or 1 only where PLANAR -- a grey batch), src, dst, recs, warp, tile_prefix,
-// n_images, n_tiles, fill (R | G << 8 | B << 16; grey: the low byte), nz (NormArgs; read only where DT != 0); store_row.
+// In scope: PLANAR, DT, COL, NC (compile-time constants; NC 3, or 1 only where PLANAR -- a grey batch; COL: colour is read, NC is 3), src, dst, recs, warp, colour, tile_prefix,
+// n_images, n_tiles, fill (R | G << 8 | B << 16; grey: the low byte), nz (NormArgs; read only where DT != 0); colour_px, store_row.
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t tile = __builtin_amdgcn_readfirstlane(blockIdx.x * PJD_WARP_WAVES + (threadIdx.x >> 6));
     if (tile >= n_tiles) return;
@@ -28,6 +28,8 @@
     }
     const PjdDevResize r = recs[lo];
     const PjdDevWarp m = warp[lo];
+    PjdDevColour cm{};                                     // COL (pjd_batch_set_colour): the map of this OUTPUT, wave-uniform as r and m are
+    if constexpr (COL) cm = colour[lo];
     const uint32_t t = tile - tile_prefix[lo];
     const uint32_t row0 = (t / r.col_tiles) * PJD_WARP_ROWS + lane / PJD_WARP_LX;       // the lane's first row
     const uint32_t col0 = (t % r.col_tiles) * PJD_WARP_COLS + (lane % PJD_WARP_LX) * PJD_RS_PX;
@@ -70,6 +72,7 @@
                     px[c][q] = (__umul24(256u - wy, top) + __umul24(wy, bot) + 32768u) >> 16;
                 }
             }
+            if constexpr (COL) colour_px(px, cm);          // the fill took part in the blend as any sample: it passes through the map
             store_row<PLANAR, DT, NC>(px, dp, row, col0, n_px, dst_plane, dst_stride, nz);
         }
         Xr += 2 * PJD_WARP_LY * m.a01; Yr += 2 * PJD_WARP_LY * m.a11;

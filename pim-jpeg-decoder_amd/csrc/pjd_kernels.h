@@ -102,6 +102,7 @@ struct PjdResizeLaunch {
     uint32_t lds_bytes;
     const PjdDevResizePad *pad;          // pjd_batch_set_resize_pad: null, or win is set too and pad[i] is picture i's canvas (the PAD kernels)
     uint32_t channels = 3;               // 3, or 1 for a grey batch (PJD_OUT_GRAY8): planar, one plane, win and pad always set (the pjd_k_resize_gray kernels)
+    const PjdDevColour *colour = nullptr; // pjd_batch_set_colour: null, or colour[i] is output i's map; win and pad always set, three channels (the pjd_k_resize_col kernels)
 };
 void pjd_launch_resize(hipStream_t s, const PjdResizeLaunch &a);
 // ... and the border of its padded pictures (pjd_k_resize_border): line_prefix[i] = canvas lines (rows interleaved, plane rows planar) of
@@ -132,6 +133,7 @@ struct PjdWarpLaunch {
     PjdNormalize norm;
     uint32_t fill;
     uint32_t channels = 3;
+    const PjdDevColour *colour = nullptr; // pjd_batch_set_colour: null, or colour[i] is output i's map, applied to the blend (the fill included); three channels (pjd_k_warp_col)
 };
 void pjd_launch_warp(hipStream_t s, const PjdWarpLaunch &a);
 // ---- stage-level parity (pjd_k_coefdump.hip): coefficients in the reference's MCU_buffer layout; `out` is zeroed by the caller

@@ -155,6 +155,31 @@ const char *pjd_resize_affine_excludes(const PjdResizeSpec &spec)
     return spec.pad_set ? "set_resize_pad" : spec.ori_set ? "set_orientation" : spec.win_set ? "set_resize_window" : spec.filter_set ? "set_resize_filter" : nullptr;
 }
 
+// The limits are those of include/pjd.h, checked on the quantised values as the warp's are: |q| <= 16 * 2^16 for the nine weights,
+// |o| <= 4096 * 2^16 for the three offsets.  m * 65536 is exact in binary64, llrint rounds it to nearest even once; the magnitude is
+// bounded before the conversion, so it is defined.
+const char *pjd_colour_quantise(const double m[12], PjdDevColour &out)
+{
+    int32_t v[12];
+    for (int k = 0; k < 12; k++) {
+        if (!std::isfinite(m[k])) return "the matrix has a value that is not finite";
+        const bool offset = (k & 3) == 3;
+        const char *beyond = offset ? "an offset is beyond 4096 levels in magnitude" : "a weight is beyond 16 in magnitude";
+        if (std::fabs(m[k]) > (offset ? 4097.0 : 17.0)) return beyond;
+        const long long q = std::llrint(std::ldexp(m[k], 16)), lim = offset ? 1ll << 28 : 1ll << 20;
+        if (q > lim || q < -lim) return beyond;
+        v[k] = (int32_t)q;
+    }
+    out = PjdDevColour{};
+    bool identity = true;
+    for (int c = 0; c < 3; c++) {
+        for (int k = 0; k < 3; k++) { out.q[c][k] = v[4 * c + k]; identity = identity && v[4 * c + k] == (c == k ? 65536 : 0); }
+        out.o[c] = v[4 * c + 3]; identity = identity && v[4 * c + 3] == 0;
+    }
+    out.flags = identity ? PJD_COL_IDENTITY : 0u;
+    return nullptr;
+}
+
 PjdResizeFault pjd_resize_resolve(const PjdResizeSpec &spec, PjdResizeWork &out)
 {
     out = PjdResizeWork{};
@@ -164,6 +189,16 @@ PjdResizeFault pjd_resize_resolve(const PjdResizeSpec &spec, PjdResizeWork &out)
     if (!table && spec.filter != PJD_RESIZE_BILINEAR) return PjdResizeFault{"unknown filter (PJD_RESIZE_BILINEAR, PJD_RESIZE_ANTIALIAS or PJD_RESIZE_BICUBIC)", -1};
     for (size_t i = 0; i < n; i++)
         if (spec.out_w[i] == 0 || spec.out_w[i] > 65535u || spec.out_h[i] == 0 || spec.out_h[i] > 65535u) return fault_at(spec, i, "target width and height must be 1..65535");
+
+    // A colour map (pjd_batch_set_colour) is a layer on either request below: one record per output beside the work list, and the form
+    // with the fewest kernels -- the padded one (identity window, orientation 1 and an all-zero pad where none was asked for), or the warp
+    if (spec.colour_set) {
+        if (spec.channels != 3u) return PjdResizeFault{"a grey batch has no colour map (one plane: gain and offset are pjd_batch_set_normalize's)", -1};
+        out.colour.resize(n);
+        for (size_t i = 0; i < n; i++)
+            if (const char *f = pjd_colour_quantise(spec.colour[i].m, out.colour[i])) return fault_at(spec, i, f);
+        form.coloured = true;
+    }
 
     // An affine map (pjd_batch_set_resize_affine) is the whole request: no pad, orientation, window or filter beside it -- each is a matrix
     // the caller multiplies in -- and a form of its own, one record per output beside the work list, in tiles of the warp launch.
@@ -226,7 +261,8 @@ PjdResizeFault pjd_resize_resolve(const PjdResizeSpec &spec, PjdResizeWork &out)
         }
     // the most general form a batch needs is the one it runs: a pad brings the oriented launch, an orientation the windowed one
     // a grey batch has the padded kernels alone (pjd_k_resize.hip): a picture without a pad is its whole canvas, and has no border line
-    if (spec.channels == 1u) form.padded = true;
+    // a coloured batch likewise, for the same reason: the instantiation count
+    if (spec.channels == 1u || form.coloured) form.padded = true;
     form.oriented = form.oriented || form.padded;
     form.windowed = form.oriented || any_win;
 

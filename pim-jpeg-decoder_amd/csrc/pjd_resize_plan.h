@@ -2,7 +2,7 @@
 //
 // The records the kernels of pjd_k_resize.hip read are a PURE FUNCTION of the request: pjd_resize_resolve makes all of them from a
 // PjdResizeSpec in one go, and every setter of pjd_api.hip (pjd_batch_set_resize, _set_resize_pad, _set_orientation,
-// _set_resize_window, _set_resize_filter, _set_resize_affine) adds its argument to the batch's request and resolves again.  Each rule of include/pjd.h --
+// _set_resize_window, _set_resize_filter, _set_resize_affine, _set_colour) adds its argument to the batch's request and resolves again.  Each rule of include/pjd.h --
 // content = canvas - pad, the transpose swap, window defaults, the mirror's exclusive-or, the prefix sums, the axis tables, the LDS of
 // the launch, every limit -- is stated once, here.  Plain C++, no HIP: tools/resize_plan_host.cpp checks it on the CPU under the
 // sanitizers, tools/resize_host.cpp runs the kernel bodies over its records.
@@ -15,6 +15,9 @@
 
 // one inverse 2 x 3 map of pjd_batch_set_resize_affine, as given: {m00, m01, m02, m10, m11, m12}
 struct PjdAffine { double m[6]; };
+
+// one 3 x 4 colour map of pjd_batch_set_colour, as given: row-major, the last column in 8-bit levels
+struct PjdColour { double m[12]; };
 
 // What the caller said, nothing derived.  An optional array that was given (`*_set`) but is all neutral -- all-zero pads, orientations
 // all 1, all-zero windows -- resolves to what its absence resolves to; the flags are what the call-order rules of the setters read.
@@ -39,6 +42,9 @@ struct PjdResizeSpec {
     bool affine_set = false;
     std::vector<PjdAffine> affine;         // one inverse map per output, as given
     uint8_t affine_fill[3] = {0, 0, 0};    // what a tap outside the picture reads
+    // pjd_batch_set_colour: a layer on either request.  It brings the most general per-axis form (as a grey batch does), or the warp form
+    bool colour_set = false;
+    std::vector<PjdColour> colour;         // one map per output, as given
 };
 
 // What chooses the kernel and sizes its grid ...
@@ -46,6 +52,7 @@ struct PjdResizeForm {
     uint32_t tiles = 0, lines = 0, lds = 0;                     // tiles of the resample launch, canvas lines of the border launch, LDS bytes of a table-driven launch
     bool windowed = false, oriented = false, padded = false;    // the WIN / ORI / PAD kernels; padded implies oriented implies windowed
     bool warp = false;                                          // pjd_batch_set_resize_affine: the launch of pjd_k_warp.hip, whose tiles are PJD_WARP_COLS x PJD_WARP_ROWS; none of the three above
+    bool coloured = false;                                      // pjd_batch_set_colour: the COL kernels; padded (so oriented and windowed), or warp
 };
 // ... and everything it reads (pjd_internal.h).  win, pad + line_prefix, aa + tab are empty where the form does not read them.
 struct PjdResizeWork {
@@ -59,6 +66,7 @@ struct PjdResizeWork {
     std::vector<uint32_t> tab;             // one axis table per distinct (source length, target length)
     std::vector<uint32_t> ct_w, ct_h;      // the content of each delivered picture: the canvas less its pad
     std::vector<PjdDevWarp> warp;          // form.warp: the quantised map of every output
+    std::vector<PjdDevColour> colour;      // form.coloured: the quantised colour map of every output
 };
 
 // no fault: text is empty.  The text is what pjd_last_error reports behind the setter's own "set_...: "; picture -1: the batch as a whole,
@@ -84,6 +92,11 @@ const char *pjd_resize_pad_fault(uint32_t out_w, uint32_t out_h, const pjd_resiz
 const char *pjd_warp_quantise(const double m[6], PjdDevWarp &out);
 const char *pjd_resize_affine_fault(uint32_t sw, uint32_t sh, uint32_t tw, uint32_t th, const double m[6]);
 const char *pjd_resize_affine_excludes(const PjdResizeSpec &spec);
+
+// THE rules of a colour map (include/pjd.h), the one statement of its limits.  pjd_colour_quantise: m -> the Q16 record the kernels read,
+// every value llrint(m * 65536), bit 0 of the flags set where that is the identity; null, or what is wrong with m: a value that is not
+// finite, a weight beyond 16 or an offset beyond 4096 levels in magnitude, checked on the quantised values.
+const char *pjd_colour_quantise(const double m[12], PjdDevColour &out);
 
 // The packed layout of a batch's results, as the planner lays out a batch's own buffer: n pictures of channels * w * h elements of
 // elem_bytes at 256-byte aligned offsets

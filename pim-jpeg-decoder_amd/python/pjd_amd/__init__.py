@@ -218,6 +218,12 @@ def dev_lib():
         L.pjd_warp_tap.argtypes = [C.POINTER(C.c_double), C.c_uint32, C.c_uint32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.pjd_resize_affine_check.restype = i32
         L.pjd_resize_affine_check.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]
+        L.pjd_batch_set_colour.restype = i32
+        L.pjd_batch_set_colour.argtypes = [vp, C.POINTER(C.c_double * 12)]
+        L.pjd_colour_value.restype = i32
+        L.pjd_colour_value.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]
+        L.pjd_colour_check.restype = i32
+        L.pjd_colour_check.argtypes = [C.POINTER(C.c_double)]
         L.pjd_resize_pad_check.restype = i32
         L.pjd_resize_pad_check.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(ResizePad)]
         L.pjd_resize_window_check.restype = i32
@@ -572,6 +578,20 @@ class Batch:
         fl = (C.c_uint8 * 3)(*[int(v) for v in fill])
         self.ctx._check(self.L.pjd_batch_set_resize_affine(self._h, arr, fl), "pjd_batch_set_resize_affine")
 
+    def set_colour(self, matrices):
+        """pjd_batch_set_colour: output i's resampled 8-bit triple goes through the 3 x 4 map matrices[i] -- twelve values, row-major,
+        out[c] = m[4c] * R + m[4c + 1] * G + m[4c + 2] * B + m[4c + 3] with the last column in 8-bit levels (or three rows of four; None:
+        the identity) -- in the Q16 fixed point include/pjd.h specifies bit for bit, inside the resample or warp launch, before the
+        normalisation and the store: ColorJitter, RandomGrayscale, BGR, DALI's color_twist (tensors.colour_matrix builds the numbers).
+        The border of set_resize_pad() keeps its fill; the fill of set_resize_affine() passes through the map.  Once, after set_resize()
+        (and whatever shapes the resample), before set_normalize() / bind_output() / upload(); not on a grey batch."""
+        if len(matrices) != self.n_out:
+            raise ValueError("set_colour: one matrix of twelve values (or None) per picture (per view after set_views)")
+        arr = ((C.c_double * 12) * max(self.n_out, 1))()
+        for i, m in enumerate(matrices):
+            arr[i] = _colour12(COLOUR_IDENTITY if m is None else m, "set_colour")
+        self.ctx._check(self.L.pjd_batch_set_colour(self._h, arr), "pjd_batch_set_colour")
+
     def set_resize_filter(self, filter):
         """pjd_batch_set_resize_filter: RESIZE_ANTIALIAS makes the resize the widened triangle filter include/pjd.h specifies bit for
         bit (torch's antialias=True, Pillow's BILINEAR), RESIZE_BICUBIC the bicubic one (Keys, a = -0.5, widened where an axis shrinks:
@@ -902,6 +922,33 @@ def resize_affine_check(sw, sh, tw, th, m):
     if not all(0 <= int(v) < 2 ** 32 for v in (sw, sh, tw, th)):
         return False
     return dev_lib().pjd_resize_affine_check(int(sw), int(sh), int(tw), int(th), _affine6(m, "resize_affine_check")) == 0
+
+
+COLOUR_IDENTITY = (1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0)
+
+
+def _colour12(m, who):
+    """twelve doubles from a flat sequence of twelve or from three rows of four"""
+    vals = [float(v) for row in m for v in (row if hasattr(row, "__len__") else (row,))]
+    if len(vals) != 12:
+        raise ValueError(f"{who}: a colour map is twelve values (row-major 3 x 4), or three rows of four")
+    return (C.c_double * 12)(*vals)
+
+
+def colour_value(m, rgb):
+    """pjd_colour_value (host only): the triple (R', G', B') the 3 x 4 colour map m makes of the 8-bit triple rgb; the code the coloured
+    kernels run.  ValueError for a map that is not finite or beyond the limits (|weight| <= 16, |offset| <= 4096 levels)."""
+    if len(rgb) != 3 or any(not 0 <= int(v) <= 255 for v in rgb):
+        raise ValueError(f"colour_value: rgb is three bytes, not {list(rgb)}")
+    out = (C.c_uint8 * 3)()
+    if dev_lib().pjd_colour_value(_colour12(m, "colour_value"), (C.c_uint8 * 3)(*[int(v) for v in rgb]), out) != 0:
+        raise ValueError(f"colour_value({list(m)}): the map must be finite and within the limits")
+    return out[0], out[1], out[2]
+
+
+def colour_check(m):
+    """pjd_colour_check (host only): True where pjd_batch_set_colour would accept the 3 x 4 colour map m (twelve values)."""
+    return dev_lib().pjd_colour_check(_colour12(m, "colour_check")) == 1
 
 
 def resize_window(w):

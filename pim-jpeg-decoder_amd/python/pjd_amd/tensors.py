@@ -4,8 +4,8 @@ The batch is bound (Batch.bind_output, pjd_batch_bind_output of include/pjd.h) t
 on the context's device; the back end writes the pictures straight into it -- planar R, G, B (OUT_RGB8_PLANAR, "CHW") by
 default -- and the results are views of that buffer.  No native code of its own.  torch is imported inside the functions that
 need it: uniform_output_shape(), pick_scale_flags(), pick_libjpeg_scale_flags(), normalize_constants(), center_crop_window(), window_at_scale(), orient_hw(),
-orient_then_hflip(), crop_to_stored(), tile_views(), least_reduced_scale_flags(), plan_views(), affine_inverse_matrix(), orientation_matrix()
-and plan_affines() are pure.
+orient_then_hflip(), crop_to_stored(), tile_views(), least_reduced_scale_flags(), plan_views(), affine_inverse_matrix(), orientation_matrix(),
+plan_affines() and colour_matrix() are pure.
 
 Pictures of different sizes become ONE [N, 3, H, W] tensor with decode_resized_batch_tensor: the library resamples every picture to
 H x W inside the decode (Batch.set_resize, pjd_batch_set_resize), after the box pre-scale pick_scale_flags chooses.
@@ -43,6 +43,7 @@ the allocation and before the library writes.  After the decode: Batch.sync() ha
 statuses (fallback re-decodes included), so the returned tensors are complete and safe to read on any stream.
 """
 import collections
+import math
 
 import pjd_amd
 
@@ -112,9 +113,10 @@ def _torch():
 # What one call asks of a batch, settled before the batch exists: the descriptors to decode and the output format; the capacity and the
 # offsets to bind (None: packed); then what the setters take, each None where its setter is not called -- views, sizes (set_resize), pads
 # with fill (set_resize_pad), orientations, windows, filter (set_resize_filter), normalize = (dtype, scale, bias), pad_value.
-# affines (set_resize_affine, with fill) stands in place of pads, orientations, windows and filter.
-_Request = collections.namedtuple("_Request", "descs out_format capacity offsets views sizes pads fill orientations windows filter normalize pad_value affines",
-                                  defaults=(None,) * 12)
+# affines (set_resize_affine, with fill) stands in place of pads, orientations, windows and filter.  colours (set_colour) comes behind
+# all of them and before normalize.
+_Request = collections.namedtuple("_Request", "descs out_format capacity offsets views sizes pads fill orientations windows filter normalize pad_value affines colours",
+                                  defaults=(None,) * 13)
 
 
 def _run(ctx, req, device):
@@ -137,6 +139,8 @@ def _run(ctx, req, device):
                 b.set_resize_window(req.windows)
             if req.filter is not None:
                 b.set_resize_filter(req.filter)
+            if req.colours is not None:
+                b.set_colour(req.colours)
         if req.normalize is not None:
             b.set_normalize(*req.normalize)
             if req.pads is not None and req.pad_value is not None:
@@ -529,6 +533,62 @@ def plan_affines(descs, affines, prescale=True, orientations=None, views=None):
     return run, [tuple(v / (1 << _scale_log(run[p].flags)) for v in m) for m, p in zip(full, pic_of)]
 
 
+_LUMA = (0.299, 0.587, 0.114)
+_YIQ = ((0.299, 0.587, 0.114), (0.5959, -0.2746, -0.3213), (0.2115, -0.5227, 0.3112))
+
+
+def colour_matrix(brightness=1.0, contrast=1.0, saturation=1.0, hue=0.0, grayscale=False, channel_order="rgb", pivot=128.0,
+                  order=("brightness", "contrast", "saturation", "hue")):
+    """The twelve numbers of a 3 x 4 colour map (row-major, the last column in 8-bit levels) for Batch.set_colour and colours=: the
+    product of 4 x 4 homogeneous factors applied in `order` (a permutation of the four names; a factor at its neutral value is left out,
+    so the defaults give the identity exactly):
+      brightness b: b * x;
+      contrast c: c * x + (1 - c) * pivot, about the CONSTANT `pivot`;
+      saturation s: s * x + (1 - s) * L with L = 0.299 R + 0.587 G + 0.114 B;
+      hue h: a rotation by h turns (h = 0.5: half a turn) about the grey axis in YIQ.
+    Then grayscale=True puts L of the result in all three rows (RandomGrayscale: a grey picture of three equal channels), and
+    channel_order="bgr" swaps the first and the last row, last of all.  Pure; float64.
+    This is the model of DALI's color_twist / hsv / brightness_contrast.  It differs from torchvision's ColorJitter, which works on the
+    pixels step by step: there is no clamp to 0..255 BETWEEN the factors (one clamp at the end); contrast pivots on a constant and not
+    on the picture's mean grey (that needs a reduction over the picture); and torchvision truncates its grey to uint8 before it blends
+    for saturation and contrast.  For small jitters the results are within a few levels of each other."""
+    import numpy as np
+    if sorted(order) != ["brightness", "contrast", "hue", "saturation"]:
+        raise ValueError("colour_matrix: order is a permutation of (\"brightness\", \"contrast\", \"saturation\", \"hue\")")
+    if channel_order not in ("rgb", "bgr"):
+        raise ValueError("colour_matrix: channel_order is \"rgb\" or \"bgr\"")
+    vals = [float(v) for v in (brightness, contrast, saturation, hue, pivot)]
+    if not all(math.isfinite(v) for v in vals):
+        raise ValueError("colour_matrix: finite values")
+    b, c, s, h, pivot = vals
+    luma = np.tile(np.asarray(_LUMA, np.float64), (3, 1))
+    m = np.eye(4)
+    for name in order:
+        f = np.eye(4)
+        if name == "brightness" and b != 1.0:
+            f[:3, :3] *= b
+        elif name == "contrast" and c != 1.0:
+            f[:3, :3] *= c
+            f[:3, 3] = (1.0 - c) * pivot
+        elif name == "saturation" and s != 1.0:
+            f[:3, :3] = s * np.eye(3) + (1.0 - s) * luma
+        elif name == "hue" and h != 0.0:
+            t = np.asarray(_YIQ, np.float64)
+            a = 2.0 * math.pi * h
+            rot = np.array([[1.0, 0.0, 0.0], [0.0, math.cos(a), -math.sin(a)], [0.0, math.sin(a), math.cos(a)]])
+            f[:3, :3] = np.linalg.inv(t) @ rot @ t
+        else:
+            continue
+        m = f @ m
+    if grayscale:
+        g = np.eye(4)
+        g[:3, :3] = luma
+        m = g @ m
+    if channel_order == "bgr":
+        m = m[[2, 1, 0, 3]]
+    return tuple(float(v) for v in m[:3].reshape(-1))
+
+
 def tile_views(h, w, th, tw):
     """An h x w picture cut into a grid of tiles of at most th x tw, edge tiles smaller -> (windows, sizes), row-major (left to right,
     then top to bottom): windows[k] = {"x", "y", "w", "h"} for Batch.set_resize_window and sizes[k] = (tile_h, tile_w) for
@@ -590,7 +650,22 @@ def plan_views(descs, views, size, prescale=True, crops=None, flips=None, resize
 
 
 def _resize_request(who, descs, size, out_format, prescale, antialias, crops, flips, resize_short, interpolation, orientations, libjpeg,
-                    letterbox, fill, draft, views, affines=None):
+                    letterbox, fill, draft, views, affines=None, colours=None):
+    """The _Request of one of the two resizing helpers (`who`): its geometry (_resize_request_geometry), and colours= checked against it
+    -- one map or None per output, none on a grey batch -- before anything is created."""
+    req = _resize_request_geometry(who, descs, size, out_format, prescale, antialias, crops, flips, resize_short, interpolation, orientations, libjpeg,
+                                   letterbox, fill, draft, views, affines)
+    if colours is None:
+        return req
+    if out_format == pjd_amd.OUT_GRAY8:
+        raise ValueError(f"{who}: colours= takes gray=False (one plane has no colour map; grayscale=True of colour_matrix makes a grey RGB picture)")
+    if len(colours) != len(req.sizes):
+        raise ValueError(f"{who}: colours= has one matrix (or None) per output: {len(req.sizes)}, not {len(colours)}")
+    return req._replace(colours=[None if m is None else tuple(float(v) for row in m for v in (row if hasattr(row, "__len__") else (row,))) for m in colours])
+
+
+def _resize_request_geometry(who, descs, size, out_format, prescale, antialias, crops, flips, resize_short, interpolation, orientations, libjpeg,
+                             letterbox, fill, draft, views, affines=None):
     """What the two resizing helpers (`who`) share, all of it before anything is created: the keywords are checked, the outputs are
     planned (_plan_outputs, plan_views) -> the _Request of a batch of uint8 outputs of `size`, one after the other in one buffer."""
     if interpolation not in ("bilinear", "bicubic"):
@@ -624,7 +699,7 @@ def _resize_request(who, descs, size, out_format, prescale, antialias, crops, fl
 
 def decode_resized_batch_tensor(ctx, descs, size, prescale=True, device=None, antialias=False, crops=None, flips=None, resize_short=None,
                                 interpolation="bilinear", orientations=None, libjpeg=False, letterbox=None, fill=(0, 0, 0), gray=False, draft=False,
-                                views=None, affines=None):
+                                views=None, affines=None, colours=None):
     """Pictures of ANY sizes -> (uint8 tensor [N, 3, H, W], statuses), size = (H, W): every picture is resampled to H x W inside
     the decode (the bilinear filter of include/pjd.h, pjd_batch_set_resize) and lands at offset i * 3 * H * W of one buffer, so
     the result is one contiguous NCHW tensor with no copy after the decode, complete on return and readable on any torch stream
@@ -675,9 +750,13 @@ def decode_resized_batch_tensor(ctx, descs, size, prescale=True, device=None, an
     lies outside the picture -- one launch, no grid_sample pass.  With orientations= the map speaks about the UPRIGHT picture and the
     exact orientation matrix is multiplied in (plan_affines); with views= there is one matrix per view.  prescale=True decodes a picture
     at the largest box scale that every one of its maps shrinks by; prescale=False is exactly the filter over the full-size picture.
-    crops, flips, resize_short, letterbox, antialias and interpolation raise ValueError beside it: each is a matrix to fold in."""
+    crops, flips, resize_short, letterbox, antialias and interpolation raise ValueError beside it: each is a matrix to fold in.
+    colours=[m | None, ...]: output i's resampled 8-bit triple goes through the 3 x 4 colour map m (twelve values, row-major, the last
+    column in 8-bit levels: colour_matrix makes them; None: the identity) inside the same launch, in the fixed point of include/pjd.h
+    (Batch.set_colour): ColorJitter, RandomGrayscale, BGR.  One entry per OUTPUT (per view with views=).  It composes with every keyword
+    above; a letterbox border keeps its `fill`, the `fill` of affines= passes through the map.  With gray=True it raises ValueError."""
     req = _resize_request("decode_resized_batch_tensor", descs, size, pjd_amd.OUT_GRAY8 if gray else pjd_amd.OUT_RGB8_PLANAR, prescale, antialias,
-                          crops, flips, resize_short, interpolation, orientations, libjpeg, letterbox, fill, draft, views, affines)
+                          crops, flips, resize_short, interpolation, orientations, libjpeg, letterbox, fill, draft, views, affines, colours)
     buf, _, st = _run(ctx, req, device)
     return buf.view(len(req.sizes), 1 if gray else 3, *req.sizes[0]), st
 
@@ -696,7 +775,8 @@ def normalize_constants(mean, std):
 
 def decode_normalized_batch_tensor(ctx, descs, size, mean, std, dtype=None, channels_last=False, prescale=True, device=None,
                                    antialias=False, crops=None, flips=None, resize_short=None, interpolation="bilinear", orientations=None,
-                                   libjpeg=False, letterbox=None, fill=(0, 0, 0), pad_value=None, gray=False, draft=False, views=None, affines=None):
+                                   libjpeg=False, letterbox=None, fill=(0, 0, 0), pad_value=None, gray=False, draft=False, views=None, affines=None,
+                                   colours=None):
     """Pictures of ANY sizes -> (tensor of `dtype` [N, 3, H, W], statuses), size = (H, W); dtype torch.float16 (the default),
     torch.bfloat16 or torch.float32.  As decode_resized_batch_tensor, and every sample v of channel c leaves the same launch as
     fma(v, scale[c], bias[c]) with the constants of normalize_constants(mean, std), converted once to `dtype` (include/pjd.h,
@@ -717,7 +797,9 @@ def decode_normalized_batch_tensor(ctx, descs, size, mean, std, dtype=None, chan
     views: as in decode_resized_batch_tensor -- [V, C, H, W] of `dtype` (channels_last: the permuted view of [V, H, W, 3]), per-view crops,
     flips and orientations, per-picture statuses, every picture decoded once.
     affines, with fill: as in decode_resized_batch_tensor; the fill is a sample like any other and is normalised with the rest (there is
-    no pad_value beside it: that needs a letterbox)."""
+    no pad_value beside it: that needs a letterbox).
+    colours: as in decode_resized_batch_tensor; the map comes BEFORE the normalisation, which reads its 8-bit result -- the order of
+    ColorJitter, RandomGrayscale, ToTensor, Normalize."""
     _gray_layout(gray, not channels_last)
     if gray:
         mean, std = _gray3(mean, "mean"), _gray3(std, "std")
@@ -727,7 +809,7 @@ def decode_normalized_batch_tensor(ctx, descs, size, mean, std, dtype=None, chan
     if pad_value is not None and letterbox is None:
         raise ValueError("pad_value needs letterbox: without it there is no border")
     req = _resize_request("decode_normalized_batch_tensor", descs, size, pjd_amd.OUT_GRAY8 if gray else pjd_amd.OUT_RGB8 if channels_last else pjd_amd.OUT_RGB8_PLANAR,
-                          prescale, antialias, crops, flips, resize_short, interpolation, orientations, libjpeg, letterbox, fill, draft, views, affines)
+                          prescale, antialias, crops, flips, resize_short, interpolation, orientations, libjpeg, letterbox, fill, draft, views, affines, colours)
     torch = _torch()
     dtype = torch.float16 if dtype is None else dtype
     dts = {torch.float16: (pjd_amd.DT_F16, 2), torch.bfloat16: (pjd_amd.DT_BF16, 2), torch.float32: (pjd_amd.DT_F32, 4)}

@@ -27,7 +27,10 @@
 //     the border kernel's body (pjd_k_resize_border_body.h), every thread of its grid: pads that put the rectangle and the canvas
 //     width at every remainder modulo four, on one side only, and none at all (such a picture has no border line).  The expectation
 //     is the canvas full of fill with the content written over its rectangle: a border byte left out, a content byte filled over or a
-//     byte outside a canvas shows.  The plain set also runs through the PAD body: the same bytes.
+//     byte outside a canvas shows.  The plain set also runs through the PAD body: the same bytes;
+//   - coloured: the padded set again with a 3 x 4 colour map per picture (pjd_batch_set_colour), through the COL bodies -- the form a
+//     coloured request resolves to.  The expectation applies the arithmetic of include/pjd.h in 64 bits to each triple; the border
+//     stays the fill as given.  Identity maps (the skipped branch), a permutation, both saturating extremes, the limits.
 // The source holds every picture back to back with NO padding between them beyond what rounds the buffer to a dword (the kernels
 // stage whole dwords): a read outside a window that mattered would change the result, a read outside the buffer is a sanitizer
 // report.  The expectation is a plain per-pixel loop over the arithmetic of include/pjd.h -- the tap inlines with a shifted index;
@@ -61,17 +64,17 @@ static inline uint32_t emu_tap(uint32_t sn, uint32_t dn, uint32_t i) { uint32_t 
 #define PJD_WIN_STAGE_FIRST 0u
 #define PJD_WIN_STAGE_STEP  1u
 
-template <bool PLANAR, int DT, bool WIN, bool ORI, bool PAD>
+template <bool PLANAR, int DT, bool WIN, bool ORI, bool PAD, bool COL>
 static void thread_bilinear(const uint8_t *src, uint8_t *dst, const PjdDevResize *recs, const PjdDevResizeWin *win, const PjdDevResizePad *pad,
-                            const uint32_t *tile_prefix, uint32_t n_images, uint32_t n_tiles, const NormArgs nz)
+                            const PjdDevColour *colour, const uint32_t *tile_prefix, uint32_t n_images, uint32_t n_tiles, const NormArgs nz)
 {
     constexpr int NC = 3;                                  // the kernels' channel count: three-channel pictures here
 #include "../pim-jpeg-decoder_amd/csrc/pjd_k_resize_body.h"
 }
 
-template <bool PLANAR, int DT, bool WIN, bool ORI, bool PAD, int FILT>
+template <bool PLANAR, int DT, bool WIN, bool ORI, bool PAD, bool COL, int FILT>
 static void thread_aa(uint32_t *seg, const uint8_t *src, uint8_t *dst, const PjdDevResize *recs, const PjdDevResizeWin *win, const PjdDevResizePad *pad,
-                      const uint32_t *tile_prefix, uint32_t n_images, uint32_t n_tiles, const PjdDevResizeAA *aa, const uint32_t *tab, uint32_t lds_bytes,
+                      const PjdDevColour *colour, const uint32_t *tile_prefix, uint32_t n_images, uint32_t n_tiles, const PjdDevResizeAA *aa, const uint32_t *tab, uint32_t lds_bytes,
                       const NormArgs nz)
 {
     constexpr int NC = 3;                                  // the kernels' channel count: three-channel pictures here
@@ -180,11 +183,32 @@ static std::vector<Case> padded_cases(unsigned seed)
     return cases;
 }
 
-// mode 0: plain, 1: windowed, 2: oriented (the ORI bodies: windows with an orientation), 3: padded (the PAD bodies and the border kernel's)
+// The colour maps of the coloured set (pjd_batch_set_colour), one per picture: seeded jitters, every fourth the identity (the branch the
+// kernels skip the arithmetic under), a permutation, both saturating extremes, and weights and offsets at the limits with mixed signs
+static std::vector<PjdColour> colour_cases(size_t n, unsigned seed)
+{
+    std::vector<PjdColour> cols(n);
+    srand(seed + 77);
+    for (size_t i = 0; i < n; i++) {
+        double *m = cols[i].m;
+        for (int k = 0; k < 12; k++) m[k] = k % 5 == 0 ? 1.0 : 0.0;                  // the identity
+        if (i % 4 == 0) continue;
+        if (i % 11 == 1) { for (int k = 0; k < 12; k++) m[k] = k % 4 == 3 ? 4096.0 : 16.0; continue; }
+        if (i % 11 == 2) { for (int k = 0; k < 12; k++) m[k] = k % 4 == 3 ? -4096.0 : -16.0; continue; }
+        if (i % 11 == 3) { const double bgr[12] = {0, 0, 1, 0, 0, 1, 0, 0, 1, 0, 0, 0}; memcpy(m, bgr, sizeof bgr); continue; }
+        if (i % 11 == 5) { for (int k = 0; k < 12; k++) m[k] = k % 4 == 3 ? (k & 4 ? 4096.0 : -4096.0) : ((k + k / 4) & 1 ? -16.0 : 16.0); continue; }
+        for (int k = 0; k < 12; k++) m[k] = k % 4 == 3 ? (rand() % 18001 - 9000) / 100.0 : (k % 5 == 0 ? 0.4 + (rand() % 1400) / 1000.0 : 0.0) + (rand() % 1201 - 600) / 1000.0;
+    }
+    return cols;
+}
+
+// mode 0: plain, 1: windowed, 2: oriented (the ORI bodies: windows with an orientation), 3: padded (the PAD bodies and the border kernel's),
+// 4: coloured (the padded set with a colour map per picture, through the COL bodies: the form a coloured request resolves to)
 template <bool PLANAR, int DT, int FILT>
 static int run(int mode, uint32_t misalign_elems, unsigned seed)
 {
-    const bool windowed = mode != 0, padded = mode == 3, oriented = mode == 2 || padded;
+    const bool coloured = mode == 4;
+    const bool windowed = mode != 0, padded = mode == 3 || coloured, oriented = mode == 2 || padded;
     constexpr bool AA = FILT != PJD_RESIZE_BILINEAR;          // a table-driven filter
     const uint32_t ES = DT == 0 ? 1 : PJD_DT_SIZE(DT);
     const std::vector<Case> cases = padded ? padded_cases(seed) : oriented ? oriented_cases(seed) : windowed ? window_cases(seed) : plain_cases(seed, AA);
@@ -210,10 +234,12 @@ static int run(int mode, uint32_t misalign_elems, unsigned seed)
         spos += 3ull * c.sw * c.sh;                        // back to back: a picture's neighbours are other pictures
         dpos += 3ull * cvw[i] * cvh[i] * ES + ES * (2 * (i % 3) + 1);                 // element-aligned odd gaps
     }
+    const std::vector<PjdColour> cols = colour_cases(n, seed);
+    if (coloured) { spec.colour_set = true; spec.colour = cols; }
     PjdResizeWork work;
     const PjdResizeFault fault = pjd_resize_resolve(spec, work);
     if (!fault.text.empty()) { printf("the resolver refuses the cases: %s\n", fault.text.c_str()); return 1; }
-    if (work.form.windowed != windowed || work.form.oriented != oriented || work.form.padded != padded) { printf("the resolver chose another form than the cases ask for\n"); return 1; }
+    if (work.form.windowed != windowed || work.form.oriented != oriented || work.form.padded != padded || work.form.coloured != coloured || work.colour.size() != (coloured ? n : 0)) { printf("the resolver chose another form than the cases ask for\n"); return 1; }
     const std::vector<PjdDevResize> &recs = work.recs;
     const std::vector<uint32_t> &prefix = work.tile_prefix, &tab = work.tab;
     const std::vector<PjdDevResizeAA> &aas = work.aa;
@@ -243,18 +269,18 @@ static int run(int mode, uint32_t misalign_elems, unsigned seed)
     PjdNormalize norm{DT, {nz.scale[0], nz.scale[1], nz.scale[2]}, {nz.bias[0], nz.bias[1], nz.bias[2]}};
     const PjdPadFill pf = pjd_pad_fill(norm, PLANAR, fill_u8, nullptr);
     // every thread of the launch, with the WIN = true or the WIN = false body
-    auto launch = [&](auto WIN, auto ORI, auto PADDED) {
-        constexpr bool W = decltype(WIN)::value, O = decltype(ORI)::value, PD = decltype(PADDED)::value;
+    auto launch = [&](auto WIN, auto ORI, auto PADDED, auto COLOURED) {
+        constexpr bool W = decltype(WIN)::value, O = decltype(ORI)::value, PD = decltype(PADDED)::value, CL = decltype(COLOURED)::value;
         uint8_t *dst = (uint8_t *)aligned_alloc(256, (dst_bytes + 255) & ~(size_t)255); memset(dst, 0xA5, dst_bytes);
         const uint32_t n_threads = AA ? 64 : 64 * PJD_RS_WAVES, n_blocks = AA ? t : (t + PJD_RS_WAVES - 1) / PJD_RS_WAVES;
         for (uint32_t b = 0; b < n_blocks; b++) for (uint32_t th = 0; th < n_threads; th++) {
             blockIdx.x = b; threadIdx.x = th;
             if constexpr (AA) {
                 uint32_t *seg = (uint32_t *)malloc(lds ? lds : 4);                   // this thread's "LDS", of the launch's size
-                thread_aa<PLANAR, DT, W, O, PD, FILT>(seg, src, dst, recs.data(), W ? wins.data() : nullptr, PD ? pads.data() : nullptr, prefix.data(), (uint32_t)n, t, aas.data(), tab.data(), lds, nz);
+                thread_aa<PLANAR, DT, W, O, PD, CL, FILT>(seg, src, dst, recs.data(), W ? wins.data() : nullptr, PD ? pads.data() : nullptr, CL ? work.colour.data() : nullptr, prefix.data(), (uint32_t)n, t, aas.data(), tab.data(), lds, nz);
                 free(seg);
             } else {
-                thread_bilinear<PLANAR, DT, W, O, PD>(src, dst, recs.data(), W ? wins.data() : nullptr, PD ? pads.data() : nullptr, prefix.data(), (uint32_t)n, t, nz);
+                thread_bilinear<PLANAR, DT, W, O, PD, CL>(src, dst, recs.data(), W ? wins.data() : nullptr, PD ? pads.data() : nullptr, CL ? work.colour.data() : nullptr, prefix.data(), (uint32_t)n, t, nz);
             }
         }
         if constexpr (PD)                                    // the border kernel behind it: the grid of pjd_launch_resize_border, whole workgroups
@@ -263,20 +289,29 @@ static int run(int mode, uint32_t misalign_elems, unsigned seed)
         return dst;
     };
     const std::true_type yes{}; const std::false_type no{};
-    uint8_t *dst = padded ? launch(yes, yes, yes) : oriented ? launch(yes, yes, no) : windowed ? launch(yes, no, no) : launch(no, no, no);
+    // -DPJD_HOST_COLOURED_ONLY builds the coloured set alone (a fifth of the instantiations: tests/test_colour_cpu.py)
+#ifdef PJD_HOST_COLOURED_ONLY
+    if (!coloured) { printf("built with PJD_HOST_COLOURED_ONLY\n"); return 1; }
+    uint8_t *dst = launch(yes, yes, yes, yes);
+#else
+    uint8_t *dst = coloured ? launch(yes, yes, yes, yes) : padded ? launch(yes, yes, yes, no) : oriented ? launch(yes, yes, no, no) : windowed ? launch(yes, no, no, no) : launch(no, no, no, no);
+#endif
     int bad = 0;
     uint32_t clamped = FILT == PJD_RESIZE_BICUBIC ? 0u : 3u;   // bicubic: the final clamp is met at both ends
+    uint32_t colour_clamped = coloured ? 0u : 3u;            // coloured: the map's one clamp likewise
+#ifndef PJD_HOST_COLOURED_ONLY
     if (!windowed) {                                         // the identity window through the WIN = true body: the same bytes
-        uint8_t *again = launch(yes, no, no);
+        uint8_t *again = launch(yes, no, no, no);
         if (memcmp(dst, again, dst_bytes) != 0) { printf("  the identity window through the WIN body gives other bytes\n"); bad++; }
         free(again);
-        again = launch(yes, yes, no);                        // ... and through the ORI body (orientation 1: no PJD_RWI_* bit)
+        again = launch(yes, yes, no, no);                        // ... and through the ORI body (orientation 1: no PJD_RWI_* bit)
         if (memcmp(dst, again, dst_bytes) != 0) { printf("  the identity window through the ORI body gives other bytes\n"); bad++; }
         free(again);
-        again = launch(yes, yes, yes);                       // ... and through the PAD body (no pad: the canvas is the content, no border line)
+        again = launch(yes, yes, yes, no);                       // ... and through the PAD body (no pad: the canvas is the content, no border line)
         if (memcmp(dst, again, dst_bytes) != 0) { printf("  the identity window through the PAD body gives other bytes\n"); bad++; }
         free(again);
     }
+#endif
     // the expectation: include/pjd.h, pixel by pixel
     std::vector<uint8_t> want(dst_bytes, 0xA5);
     for (size_t i = 0; i < n; i++) {
@@ -291,7 +326,9 @@ static int run(int mode, uint32_t misalign_elems, unsigned seed)
             if (xx < w.x || xx >= w.x + w.w || yy < w.y || yy >= w.y + w.h) { printf("the expectation itself left the window\n"); exit(2); }
             return PLANAR ? sp[(size_t)ch * c.sw * c.sh + (size_t)yy * c.sw + xx] : sp[((size_t)yy * c.sw + xx) * 3 + ch];
         };
-        for (uint32_t y = 0; y < c.th; y++) for (uint32_t x = 0; x < c.tw; x++) for (int ch = 0; ch < 3; ch++) {
+        for (uint32_t y = 0; y < c.th; y++) for (uint32_t x = 0; x < c.tw; x++) {
+          uint32_t v3[3];
+          for (int ch = 0; ch < 3; ch++) {
             const uint32_t xi = w.ox + ((w.flags & PJD_RW_HFLIP) ? c.tw - 1 - x : x), yi = w.oy + y;
             uint32_t v;
             if (FILT == PJD_RESIZE_BICUBIC) {
@@ -325,6 +362,23 @@ static int run(int mode, uint32_t misalign_elems, unsigned seed)
                 x0 += w.x; x1 += w.x; y0 += w.y; y1 += w.y;
                 v = ((256 - wy) * ((256 - wx) * P(ch, y0, x0) + wx * P(ch, y0, x1)) + wy * ((256 - wx) * P(ch, y1, x0) + wx * P(ch, y1, x1)) + 32768) >> 16;
             }
+            v3[ch] = v;
+          }
+          if (coloured) {                                    // include/pjd.h, "colour map", written out in 64 bits: it also says that 32 were enough
+              const double *m = cols[i].m;
+              uint32_t out[3];
+              for (int ch = 0; ch < 3; ch++) {
+                  const int64_t sum = (int64_t)std::llrint(m[4 * ch] * 65536.0) * v3[0] + (int64_t)std::llrint(m[4 * ch + 1] * 65536.0) * v3[1] + (int64_t)std::llrint(m[4 * ch + 2] * 65536.0) * v3[2] +
+                                      (int64_t)std::llrint(m[4 * ch + 3] * 65536.0) + 32768;
+                  if (sum != (int32_t)sum) { printf("the colour expectation left 32 bits\n"); exit(2); }
+                  const int64_t o = sum >> 16;
+                  colour_clamped |= o < 0 ? 1u : o > 255 ? 2u : 0u;
+                  out[ch] = (uint32_t)(o < 0 ? 0 : o > 255 ? 255 : o);
+              }
+              memcpy(v3, out, sizeof out);
+          }
+          for (int ch = 0; ch < 3; ch++) {
+            const uint32_t v = v3[ch];
             // where Q[y][x] is delivered: D = H^h(V^v(T^t(Q))) of include/pjd.h, D being dw x dh
             const uint32_t b3 = tvh_of(c.o), ot = b3 >> 2, ov = (b3 >> 1) & 1u, oh = b3 & 1u;
             const uint32_t di = ot ? (ov ? c.tw - 1 - x : x) : (ov ? c.th - 1 - y : y), dj = ot ? (oh ? c.th - 1 - y : y) : (oh ? c.tw - 1 - x : x);
@@ -336,15 +390,16 @@ static int run(int mode, uint32_t misalign_elems, unsigned seed)
                 if (DT == PJD_DT_F32) memcpy(o, &u, 4);
                 else { const uint16_t h = DT == PJD_DT_F16 ? f16bits(u) : bf16bits(u); memcpy(o, &h, 2); }
             }
+          }
         }
     }
     for (size_t k = 0; k < dst_bytes; k++) if (dst[k] != want[k]) { if (bad < 4) printf("  mismatch at byte %zu got %02x want %02x\n", k, dst[k], want[k]); bad++; }
     uint32_t rem = windowed ? 0u : 0xfu;                     // the windowed set has a segment at every dword remainder
     for (size_t i = 0; i < n; i++) rem |= 1u << ((recs[i].src_off + (PLANAR ? cases[i].w.x : 3 * cases[i].w.x) + (size_t)cases[i].w.y * recs[i].src_stride) & 3u);
-    printf("%s %s PLANAR=%d DT=%d misalign=%u: %zu pictures, %u tiles, lds %u, remainders %x, clamps %x: %s\n", FILT == PJD_RESIZE_BICUBIC ? "bicubic  " : AA ? "antialias" : "bilinear ", padded ? "padded  " : oriented ? "oriented" : windowed ? "windowed" : "plain   ",
+    printf("%s %s PLANAR=%d DT=%d misalign=%u: %zu pictures, %u tiles, lds %u, remainders %x, clamps %x: %s\n", FILT == PJD_RESIZE_BICUBIC ? "bicubic  " : AA ? "antialias" : "bilinear ", coloured ? "coloured" : padded ? "padded  " : oriented ? "oriented" : windowed ? "windowed" : "plain   ",
            (int)PLANAR, DT, misalign_elems, n, t, lds, rem, clamped, bad ? "MISMATCH" : "equal, guards intact");
     free(dst); free(src);
-    return bad != 0 || rem != 0xf || clamped != 3u;
+    return bad != 0 || rem != 0xf || clamped != 3u || colour_clamped != 3u;
 }
 
 template <int FILT>
@@ -360,9 +415,15 @@ static int all(int windowed)
     return rc;
 }
 
+// every set; built with -DPJD_HOST_COLOURED_ONLY the coloured set alone (what tests/test_colour_cpu.py builds and runs)
 int main()
 {
-    const int rc = all<PJD_RESIZE_BILINEAR>(0) | all<PJD_RESIZE_BILINEAR>(1) | all<PJD_RESIZE_BILINEAR>(2) | all<PJD_RESIZE_BILINEAR>(3) | all<PJD_RESIZE_ANTIALIAS>(0) |
+#ifdef PJD_HOST_COLOURED_ONLY
+    const int only = all<PJD_RESIZE_BILINEAR>(4) | all<PJD_RESIZE_ANTIALIAS>(4) | all<PJD_RESIZE_BICUBIC>(4);
+    printf(only ? "FAILED\n" : "ALL EQUAL\n");
+    return only;
+#endif
+    const int rc = all<PJD_RESIZE_BILINEAR>(4) | all<PJD_RESIZE_ANTIALIAS>(4) | all<PJD_RESIZE_BICUBIC>(4) | all<PJD_RESIZE_BILINEAR>(0) | all<PJD_RESIZE_BILINEAR>(1) | all<PJD_RESIZE_BILINEAR>(2) | all<PJD_RESIZE_BILINEAR>(3) | all<PJD_RESIZE_ANTIALIAS>(0) |
                    all<PJD_RESIZE_ANTIALIAS>(1) | all<PJD_RESIZE_ANTIALIAS>(2) | all<PJD_RESIZE_ANTIALIAS>(3) | all<PJD_RESIZE_BICUBIC>(0) | all<PJD_RESIZE_BICUBIC>(1) |
                    all<PJD_RESIZE_BICUBIC>(2) | all<PJD_RESIZE_BICUBIC>(3);
     printf(rc ? "FAILED\n" : "ALL EQUAL\n");

@@ -1,13 +1,15 @@
 // resize_plan_host.cpp -- the resolver of the resample work list (pim-jpeg-decoder_amd/csrc/pjd_resize_plan.cpp) on the CPU, under the
 // sanitizers: every limit on both sides of its boundary with the picture it names, a seeded family over the full cross of pads,
 // orientations, windows, filters and layouts whose records are held against statements written out HERE from include/pjd.h (never
-// against the helpers under test), and the setters' order: the request built up call by call resolves to what it resolves to in one go.
+// against the helpers under test), and the setters' order: the request built up call by call resolves to what it resolves to in one go;
+// and the rules of a colour map (pjd_batch_set_colour): limits, records, the identity flag, the padded form it brings.
 //
 //     g++ -std=c++17 -O1 -g -fsanitize=address,undefined -D__host__= -D__device__= -o resize_plan_host
 //         tools/resize_plan_host.cpp pim-jpeg-decoder_amd/csrc/pjd_resize_plan.cpp && ./resize_plan_host
 //
 // tests/test_resize_plan_cpu.py builds and runs it.  Prints `no sanitizer report` at the end; exit status 1 where a check failed.
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -16,8 +18,8 @@
 
 #include "../pim-jpeg-decoder_amd/csrc/pjd_resize_plan.h"
 
-static int g_bad = 0;
-#define CHECK(cond, ...) do { if (!(cond)) { if (g_bad++ < 20) { printf("FAILED %s:%d: %s: ", __FILE__, __LINE__, #cond); printf(__VA_ARGS__); printf("\n"); } } } while (0)
+static int g_bad = 0, g_checks = 0;
+#define CHECK(cond, ...) do { g_checks++; if (!(cond)) { if (g_bad++ < 20) { printf("FAILED %s:%d: %s: ", __FILE__, __LINE__, #cond); printf(__VA_ARGS__); printf("\n"); } } } while (0)
 
 static uint32_t g_seed = 1;
 static uint32_t rnd(uint32_t n) { g_seed = g_seed * 1664525u + 1013904223u; return (g_seed >> 8) % n; }   // 0 .. n-1
@@ -329,9 +331,101 @@ static void layout_and_fill()
           "rounding to nearest even");
 }
 
+// A colour map (pjd_batch_set_colour): the limits on both sides of their boundary in every slot, the records against the statement of
+// include/pjd.h written out here, and the form -- the padded one with the identity window, orientation 1 and an all-zero pad where
+// none was asked for -- whose other records are those of the same request with a neutral pad, orientation and window
+static void coloured()
+{
+    const int checks0 = g_checks, bad0 = g_bad;
+    const double ident[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    auto with_colour = [&](PjdResizeSpec s, size_t i, int slot, double v) {
+        s.colour_set = true;
+        PjdColour c; memcpy(c.m, ident, sizeof ident);
+        s.colour.assign(s.pic.size(), c);
+        if (slot >= 0) s.colour[i].m[slot] = v;
+        return s;
+    };
+    const PjdResizeSpec base = plain_spec(3, 61, 45, 30, 20, true);
+    expect(with_colour(base, 0, -1, 0), -2, "identity maps");
+    for (int slot = 0; slot < 12; slot++) {
+        const bool off = slot % 4 == 3;
+        const double lim = off ? 4096.0 : 16.0;
+        for (double sign : {1.0, -1.0}) {
+            expect(with_colour(base, 1, slot, sign * lim), -2, "a value at the limit");
+            expect(with_colour(base, 1, slot, sign * std::nextafter(lim, 2 * lim)), -2, "the next double quantises to the limit");
+            expect(with_colour(base, 1, slot, sign * (lim + 1.0 / 65536.0)), 1, "the next quantised value");
+        }
+        for (double bad : {(double)NAN, (double)INFINITY, -(double)INFINITY, 1e300, -1e300}) expect(with_colour(base, 2, slot, bad), 2, "not finite, or far beyond");
+        PjdDevColour rec;
+        PjdColour c; memcpy(c.m, ident, sizeof ident); c.m[slot] = lim + 1.0 / 65536.0;
+        const char *text = pjd_colour_quantise(c.m, rec);
+        CHECK(text && std::string(text) == (off ? "an offset is beyond 4096 levels in magnitude" : "a weight is beyond 16 in magnitude"), "the text of slot %d: %s", slot, text ? text : "(accepted)");
+    }
+    {   // grey: refused for the batch as a whole
+        PjdResizeSpec g = with_colour(base, 0, -1, 0);
+        g.channels = 1;
+        expect(g, -1, "a grey batch");
+    }
+    // the records: llrint(m * 65536), ties to even; the flag where that is the identity, also for a matrix that only rounds to it
+    {
+        PjdResizeSpec s = with_colour(base, 0, -1, 0);
+        const double m1[12] = {0.299, 0.587, 0.114, 0, -0.5, 1.25, 1.0 / 131072, -12.75, 3.0 / 131072, -1.0 / 131072, 16, 4096};
+        memcpy(s.colour[1].m, m1, sizeof m1);
+        s.colour[2].m[0] = 1.0 + 1.0 / 262144; s.colour[2].m[7] = -1.0 / 262144;       // a quarter of a unit: rounds to the identity
+        PjdResizeWork w;
+        const PjdResizeFault f = pjd_resize_resolve(s, w);
+        CHECK(f.text.empty() && w.form.coloured && w.colour.size() == 3, "the request resolves: %s", f.text.c_str());
+        if (w.colour.size() == 3) {
+            const int32_t want[12] = {19595, 38470, 7471, 0, -32768, 81920, 0, -835584, 2, 0, 1048576, 268435456};
+            for (int c = 0; c < 3; c++) {
+                for (int k = 0; k < 3; k++) CHECK(w.colour[1].q[c][k] == want[4 * c + k], "q[%d][%d] = %d", c, k, w.colour[1].q[c][k]);
+                CHECK(w.colour[1].o[c] == want[4 * c + 3], "o[%d] = %d", c, w.colour[1].o[c]);
+            }
+            CHECK(w.colour[0].flags == PJD_COL_IDENTITY && w.colour[1].flags == 0 && w.colour[2].flags == PJD_COL_IDENTITY && w.colour[2].q[0][0] == 65536 && w.colour[2].o[1] == 0, "the identity flag");
+        }
+    }
+    // the form, over every filter and layout and with a real pad, orientation and window under it
+    int n = 0;
+    for (int filter : {PJD_RESIZE_BILINEAR, PJD_RESIZE_ANTIALIAS, PJD_RESIZE_BICUBIC})
+        for (int planar = 0; planar < 2; planar++)
+            for (int shaped = 0; shaped < 2; shaped++, n++) {
+                PjdResizeSpec s = with_filter(plain_spec(3, 61, 45, 30, 20, planar != 0), filter);
+                if (shaped) {
+                    s = with_pad(s, 1, pjd_resize_pad{2, 1, 3, 0});
+                    s.ori_set = true; s.orientation.assign(3, 1); s.orientation[2] = 6;
+                    s = with_window(s, 0, pjd_resize_window{3, 4, 40, 30, 0, 0, 0, 0, PJD_RW_HFLIP, 0});
+                }
+                PjdResizeSpec neutral = s;                   // the same request with every array given: what the coloured one must equal but for its own records
+                if (!shaped) { neutral.pad_set = true; neutral.pad.assign(3, pjd_resize_pad{}); neutral.ori_set = true; neutral.orientation.assign(3, 1); neutral.win_set = true; neutral.win.assign(3, pjd_resize_window{}); }
+                PjdResizeWork plain, col;
+                CHECK(pjd_resize_resolve(neutral, plain).text.empty(), "the uncoloured request resolves");
+                const PjdResizeFault f = pjd_resize_resolve(with_colour(s, 1, 5, 0.5), col);
+                CHECK(f.text.empty() && col.form.coloured && col.form.padded && col.form.oriented && col.form.windowed && !col.form.warp, "member %d: the form of a coloured request", n);
+                CHECK(col.win.size() == 3 && col.pad.size() == 3 && col.line_prefix.size() == 4 && col.colour.size() == 3, "member %d: the records of a coloured request", n);
+                CHECK(col.form.tiles == plain.form.tiles && col.form.lds == plain.form.lds && col.form.lines == (shaped ? plain.form.lines : 0u), "member %d: tiles, LDS and border lines", n);
+                CHECK(same(col.recs, plain.recs) && same(col.tile_prefix, plain.tile_prefix) && same(col.aa, plain.aa) && same(col.tab, plain.tab), "member %d: work list and tables", n);
+                if (shaped) CHECK(same(col.win, plain.win) && same(col.pad, plain.pad) && same(col.line_prefix, plain.line_prefix), "member %d: windows and canvases", n);
+                else for (size_t i = 0; i < 3; i++) {
+                    const PjdDevResizePad &c = col.pad[i];
+                    CHECK(c.W == 30 && c.H == 20 && c.left == 0 && c.top == 0 && c.cw == 30 && c.ch == 20 && col.line_prefix[i] == 0 && col.win[i].flags == 0 && col.win[i].w == 61 && col.win[i].vh == 20, "member %d: the neutral records of picture %zu", n, i);
+                }
+                CHECK(!plain.form.coloured && plain.colour.empty(), "a request without a map has no colour record");
+            }
+    // views: the fault names view and picture
+    {
+        PjdResizeSpec s = with_colour(base, 2, 3, -4097.0);
+        s.view_pic = {2, 0, 0};
+        PjdResizeWork w;
+        const PjdResizeFault f = pjd_resize_resolve(s, w);
+        CHECK(!f.state && f.picture == 2 && f.text == "view 2 (picture 0): an offset is beyond 4096 levels in magnitude", "text: %s", f.text.c_str());
+    }
+    printf("coloured: %d checks, %d failed\n", g_checks - checks0, g_bad - bad0);
+}
+
 int main()
 {
     limits();
+    coloured();
     int members = 0;
     for (int pads = 0; pads < 3; pads++) for (int oris = 0; oris < 3; oris++) for (int wins = 0; wins < 3; wins++)
         for (int filter : {PJD_RESIZE_BILINEAR, PJD_RESIZE_ANTIALIAS, PJD_RESIZE_BICUBIC})

@@ -15,7 +15,9 @@
 // compared whole, guard bytes included.  Cases: the identity; both quarter turns and the half turn of a non-square picture; a mirror;
 // an integer translation with a fill band on two sides; a half-pixel shift; a map wholly outside (all fill); a 1 x 1 source; a 1 x 1
 // target; targets one pixel past a tile edge on each axis; a 65535-sample axis with |a| = 16 and the largest translation of either sign
-// (sums near 2^62); ten seeded general maps.  Prints ALL EQUAL and the number of failed checks.
+// (sums near 2^62); ten seeded general maps.  The eight three-channel forms run once more with a colour map per output
+// (pjd_batch_set_colour; the COL body): the expectation applies the arithmetic of include/pjd.h in 64 bits to each blended triple, the
+// fill included.  Prints ALL EQUAL and the number of failed checks.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -40,9 +42,9 @@ static inline int32_t __mul24(int32_t a, int32_t b) { return (int32_t)(uint32_t)
 #include "../pim-jpeg-decoder_amd/csrc/pjd_k_resize_store.h"
 #define __builtin_amdgcn_readfirstlane(x) (x)
 
-template <bool PLANAR, int DT, int NC>
-static void thread_warp(const uint8_t *src, uint8_t *dst, const PjdDevResize *recs, const PjdDevWarp *warp, const uint32_t *tile_prefix, uint32_t n_images,
-                        uint32_t n_tiles, uint32_t fill, const NormArgs nz)
+template <bool PLANAR, int DT, int NC, bool COL>
+static void thread_warp(const uint8_t *src, uint8_t *dst, const PjdDevResize *recs, const PjdDevWarp *warp, const PjdDevColour *colour, const uint32_t *tile_prefix,
+                        uint32_t n_images, uint32_t n_tiles, uint32_t fill, const NormArgs nz)
 {
 #include "../pim-jpeg-decoder_amd/csrc/pjd_k_warp_body.h"
 }
@@ -127,7 +129,22 @@ static uint32_t expect_sample(const uint8_t *pic, bool planar, uint32_t nc, uint
     return ((256 - w[1]) * ((256 - w[0]) * s[0] + w[0] * s[1]) + w[1] * ((256 - w[0]) * s[2] + w[0] * s[3]) + 32768) >> 16;
 }
 
-template <bool PLANAR, int DT, int NC>
+// the colour map of case k of a coloured run (pjd_batch_set_colour): seeded jitters, every fourth the identity (the branch the kernels
+// skip the arithmetic under), a permutation, and both saturating extremes
+static PjdColour colour_of(size_t k, unsigned seed)
+{
+    PjdColour c;
+    for (int i = 0; i < 12; i++) c.m[i] = i % 5 == 0 ? 1.0 : 0.0;
+    if (k % 4 == 0) return c;
+    if (k % 7 == 1) { for (int i = 0; i < 12; i++) c.m[i] = i % 4 == 3 ? 4096.0 : 16.0; return c; }
+    if (k % 7 == 2) { for (int i = 0; i < 12; i++) c.m[i] = i % 4 == 3 ? -4096.0 : -16.0; return c; }
+    if (k % 7 == 3) { const double bgr[12] = {0, 0, 1, 0, 0, 1, 0, 0, 1, 0, 0, 0}; memcpy(c.m, bgr, sizeof bgr); return c; }
+    srand(seed * 131u + (unsigned)k);
+    for (int i = 0; i < 12; i++) c.m[i] = i % 4 == 3 ? (rand() % 18001 - 9000) / 100.0 : (i % 5 == 0 ? 0.4 + (rand() % 1400) / 1000.0 : 0.0) + (rand() % 1201 - 600) / 1000.0;
+    return c;
+}
+
+template <bool PLANAR, int DT, int NC, bool COL = false>
 static void run(uint32_t misalign_elems, unsigned seed)
 {
     const uint32_t ES = DT == 0 ? 1 : PJD_DT_SIZE(DT);
@@ -149,10 +166,12 @@ static void run(uint32_t misalign_elems, unsigned seed)
         spos += (size_t)NC * c.sw * c.sh;                   // back to back
         dpos += (size_t)NC * c.tw * c.th * ES + ES * (2 * (i % 3) + 1);     // element-aligned odd gaps
     }
+    if (COL) { spec.colour_set = true; for (size_t i = 0; i < n; i++) spec.colour.push_back(colour_of(i, seed)); }
     PjdResizeWork work;
     const PjdResizeFault fault = pjd_resize_resolve(spec, work);
     CHECK(fault.text.empty(), "the resolver refuses the cases: %s", fault.text.c_str());
     if (!fault.text.empty()) return;
+    CHECK(work.form.coloured == COL && work.colour.size() == (COL ? n : 0), "the colour records of the request");
     CHECK(work.form.warp && !work.form.windowed && !work.form.oriented && !work.form.padded && work.form.lines == 0 && work.form.lds == 0, "the form of an affine request");
     CHECK(work.warp.size() == n && work.recs.size() == n && work.tile_prefix.size() == n + 1 && work.win.empty() && work.pad.empty() && work.aa.empty() && work.tab.empty(), "the records of an affine request");
     uint8_t *src = (uint8_t *)malloc(spos);                  // the sanitizer's view of the source is exactly the pictures
@@ -166,14 +185,28 @@ static void run(uint32_t misalign_elems, unsigned seed)
     for (uint32_t b = 0; b < n_blocks; b++)
         for (uint32_t th = 0; th < 64 * PJD_WARP_WAVES; th++) {
             blockIdx.x = b; threadIdx.x = th;
-            thread_warp<PLANAR, DT, NC>(src, dst, work.recs.data(), work.warp.data(), work.tile_prefix.data(), (uint32_t)n, t, fill, nz);
+            thread_warp<PLANAR, DT, NC, COL>(src, dst, work.recs.data(), work.warp.data(), COL ? work.colour.data() : nullptr, work.tile_prefix.data(), (uint32_t)n, t, fill, nz);
         }
     for (size_t k = 0; k < n; k++) {
         const Case &c = cs[k];
         for (uint32_t j = 0; j < c.th; j++)
-            for (uint32_t i = 0; i < c.tw; i++)
+            for (uint32_t i = 0; i < c.tw; i++) {
+                uint32_t v3[3] = {0, 0, 0};
+                for (uint32_t ch = 0; ch < (uint32_t)NC; ch++) v3[ch] = expect_sample(src + soff[k], PLANAR, NC, ch, c, i, j, fill_u8[ch]);
+                if (COL) {                                  // include/pjd.h, "colour map", in 64 bits; the fill went through the blend, so through the map
+                    const double *m = spec.colour[k].m;
+                    uint32_t out[3];
+                    for (int ch = 0; ch < 3; ch++) {
+                        const int64_t sum = (int64_t)std::llrint(m[4 * ch] * 65536.0) * v3[0] + (int64_t)std::llrint(m[4 * ch + 1] * 65536.0) * v3[1] + (int64_t)std::llrint(m[4 * ch + 2] * 65536.0) * v3[2] +
+                                            (int64_t)std::llrint(m[4 * ch + 3] * 65536.0) + 32768;
+                        CHECK(sum == (int32_t)sum, "the colour expectation left 32 bits");
+                        const int64_t o = sum >> 16;
+                        out[ch] = (uint32_t)(o < 0 ? 0 : o > 255 ? 255 : o);
+                    }
+                    memcpy(v3, out, sizeof out);
+                }
                 for (uint32_t ch = 0; ch < (uint32_t)NC; ch++) {
-                    const uint32_t v = expect_sample(src + soff[k], PLANAR, NC, ch, c, i, j, fill_u8[ch]);
+                    const uint32_t v = v3[ch];
                     const size_t e = PLANAR ? ((size_t)ch * c.th + j) * c.tw + i : ((size_t)j * c.tw + i) * 3 + ch;
                     uint8_t *o = want + doff[k] + e * ES;
                     if (DT == 0) { o[0] = (uint8_t)v; continue; }
@@ -181,13 +214,15 @@ static void run(uint32_t misalign_elems, unsigned seed)
                     if (DT == PJD_DT_F32) memcpy(o, &u, 4);
                     else { const uint16_t h = DT == PJD_DT_F16 ? f16bits(u) : bf16bits(u); memcpy(o, &h, 2); }
                 }
+            }
     }
     size_t bad = 0, first = 0;
     for (size_t k = 0; k < dst_bytes; k++)
         if (dst[k] != want[k] && !bad++) first = k;
     size_t pic = 0;
     while (pic + 1 < n && doff[pic + 1] <= first) pic++;
-    CHECK(bad == 0, "planar %d dtype %d channels %d shift %u: %zu bytes differ, the first at %zu (case %zu from %zu)", (int)PLANAR, DT, NC, misalign_elems, bad, first, pic, doff[pic]);
+    if (COL) printf("coloured warp PLANAR=%d DT=%d shift=%u: %zu outputs, %s\n", (int)PLANAR, DT, misalign_elems, n, bad ? "MISMATCH" : "equal, guards intact");
+    CHECK(bad == 0, "%splanar %d dtype %d channels %d shift %u: %zu bytes differ, the first at %zu (case %zu from %zu)", COL ? "coloured " : "", (int)PLANAR, DT, NC, misalign_elems, bad, first, pic, doff[pic]);
     free(src); free(dst); free(want);
 }
 
@@ -226,6 +261,24 @@ static void resolver_rules()
         // a grey batch takes the warp form too, and no canvas records
         s.channels = 1;
         CHECK(pjd_resize_resolve(s, w).text.empty() && w.form.warp && !w.form.padded && w.pad.empty(), "a grey affine request");
+    }
+    // a colour map on an affine request: still the warp form and nothing of the padded one, one colour record per output
+    {
+        PjdResizeSpec s = small_spec(3, true);
+        with_affine(s, ident);
+        s.colour_set = true;
+        s.colour.assign(3, colour_of(1, 0));
+        s.colour[2] = colour_of(0, 0);
+        PjdResizeFault f = pjd_resize_resolve(s, w);
+        CHECK(f.text.empty() && w.form.warp && w.form.coloured && !w.form.padded && !w.form.windowed && w.pad.empty() && w.win.empty() && w.colour.size() == 3, "a coloured affine request");
+        CHECK(w.colour[0].q[0][0] == 16 << 16 && w.colour[0].o[2] == 4096 << 16 && w.colour[0].flags == 0 && w.colour[2].flags == PJD_COL_IDENTITY && w.colour[2].q[1][1] == 65536, "the colour records");
+        s.colour[1].m[7] = 4096.0 + 1.0 / 65536.0;
+        f = pjd_resize_resolve(s, w);
+        CHECK(!f.state && f.picture == 1 && f.text == "view 1 (picture 1): an offset is beyond 4096 levels in magnitude", "text: %s", f.text.c_str());
+        s.colour[1].m[7] = 0; s.channels = 1;
+        f = pjd_resize_resolve(s, w);
+        CHECK(!f.state && f.picture == -1 && f.text.find("grey") != std::string::npos, "a grey batch has no colour map: %s", f.text.c_str());
+        printf("coloured affine request: resolver rules checked\n");
     }
     // each exclusion, the request grown in both orders: the other setter first, then the map; the map first, then the other setter
     for (int other = 0; other < 4; other++)
@@ -275,6 +328,9 @@ int main()
         run<false, 0, 3>(mis, 11 + mis); run<false, PJD_DT_F16, 3>(mis, 21 + mis); run<false, PJD_DT_BF16, 3>(mis, 31 + mis); run<false, PJD_DT_F32, 3>(mis, 41 + mis);
         run<true, 0, 3>(mis, 51 + mis);  run<true, PJD_DT_F16, 3>(mis, 61 + mis);  run<true, PJD_DT_BF16, 3>(mis, 71 + mis);  run<true, PJD_DT_F32, 3>(mis, 81 + mis);
         run<true, 0, 1>(mis, 91 + mis);  run<true, PJD_DT_F16, 1>(mis, 101 + mis); run<true, PJD_DT_BF16, 1>(mis, 111 + mis); run<true, PJD_DT_F32, 1>(mis, 121 + mis);
+        // the eight coloured forms (pjd_k_warp_col): a colour map per output
+        run<false, 0, 3, true>(mis, 131 + mis); run<false, PJD_DT_F16, 3, true>(mis, 141 + mis); run<false, PJD_DT_BF16, 3, true>(mis, 151 + mis); run<false, PJD_DT_F32, 3, true>(mis, 161 + mis);
+        run<true, 0, 3, true>(mis, 171 + mis);  run<true, PJD_DT_F16, 3, true>(mis, 181 + mis);  run<true, PJD_DT_BF16, 3, true>(mis, 191 + mis);  run<true, PJD_DT_F32, 3, true>(mis, 201 + mis);
     }
     printf("%s, %d checks failed; no sanitizer report\n", failed ? "DIFFERENCES" : "ALL EQUAL", failed);
     return failed ? 1 : 0;
