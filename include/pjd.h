@@ -74,7 +74,7 @@ extern "C" {
  * struct either, so PJD_VERSION stays 6: a caller checks for it by the symbol pjd_resize_pad_check.  Views (pjd_batch_set_views)
  * changed no struct: a caller checks for them by the symbol pjd_batch_n_outputs.  The affine warp (pjd_batch_set_resize_affine) changed
  * none: a caller checks for it by the symbol pjd_warp_tap.  The colour map (pjd_batch_set_colour) changed none: a caller checks for it
- * by the symbol pjd_colour_value.
+ * by the symbol pjd_colour_value.  pjd_batch_decode_chains changed none either: a caller checks for it by its own symbol.
  * A caller built against another version must not pass its structs: check pjd_version() == PJD_VERSION after loading.     */
 #define PJD_VERSION 6
 
@@ -486,6 +486,12 @@ int  pjd_batch_decode_timed(pjd_batch *b, pjd_timings *t);   /* same work, event
 int  pjd_batch_capture(pjd_batch *b);       /* record the decode as a hipGraph; later
                                                pjd_batch_decode calls replay it               */
 int  pjd_batch_sync(pjd_batch *b);
+/* The form the LAST decode of the batch was issued in: 0 before the first one, 1 for one chain of launches, g >= 2 for the chains of
+ * g picture groups on streams of their own (what a batch of 64 or more small pictures takes when no other grouped decode is in flight
+ * on the device; PJD_IDLE_FORM=chain turns it off).  What was issued, not what the planner made (pjd_batch_info.dc_plan >> 8): 1 where
+ * the group streams could not be had, 1 for every pjd_batch_decode_timed, and for a replay the form of the graph that was launched.
+ * pjd_batch_capture and the exact-kernel fallback of pjd_batch_sync leave it alone.  PJD_E_ARG for NULL.  Host only.             */
+int  pjd_batch_decode_chains(pjd_batch *b);
 int  pjd_batch_download(pjd_batch *b, uint8_t *const *out, int32_t *status);
 /* All pictures in ONE device-to-host copy: `host` receives the batch's output buffer as it lies
  * in HBM (picture i at pjd_batch_output_offset(b, i), 256-byte aligned, pjd_batch_packed_size(b)

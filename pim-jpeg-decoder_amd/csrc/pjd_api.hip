@@ -191,6 +191,8 @@ struct pjd_batch {
     hipGraph_t graph_groups = nullptr;           // the same decode with the picture groups' chains as parallel branches (pjd_internal.h)
     hipGraphExec_t graph_exec_groups = nullptr;
     bool counted = false;                        // this batch's decode is counted in g_active[device]
+    int chains = 0;                              // pjd_batch_decode_chains: the form the last decode was issued in (0: none yet)
+    int graph_chains[2] = {0, 0};                // ... and the form each captured graph holds (graph_exec, graph_exec_groups)
     // pjd_batch_bind_output: dev.out is the caller's memory (never freed, zeroed or pooled here)
     bool bound = false, bound_offsets = false;   // bound_offsets: the caller chose the picture offsets (no packed download)
     uint64_t bound_capacity = 0;
@@ -811,6 +813,7 @@ int enqueue_decode(pjd_batch *b, pjd_timings *timings, bool use_groups)
     kt.finish();
     b->decoded = true;
     b->settled = false;
+    b->chains = grouped ? (int)ng : 1;           // what was issued, not what the planner made (pjd_batch_capture puts its own back)
     return PJD_OK;
 }
 
@@ -955,6 +958,7 @@ int pjd_batch_decode(pjd_batch *b)
         hipGraphExec_t ge = (groups && b->graph_exec_groups) ? b->graph_exec_groups : b->graph_exec;
         HIP_TRY(b->ctx, hipGraphLaunch(ge, b->ctx->stream));
         b->decoded = true; b->settled = false;
+        b->chains = b->graph_chains[ge == b->graph_exec ? 0 : 1];
         return PJD_OK;
     }
     return enqueue_decode(b, nullptr, groups);
@@ -982,7 +986,10 @@ int pjd_batch_capture(pjd_batch *b)
         // variant 0: the whole batch in one chain of launches; variant 1: the picture groups' chains as parallel branches
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         HIP_TRY(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
+        const int chains = b->chains;              // a capture is no decode: pjd_batch_decode_chains keeps speaking about the last one
         int rc = enqueue_decode(b, nullptr, variant == 1);
+        b->graph_chains[variant] = b->chains;
+        b->chains = chains;
         hipGraph_t &gr = variant ? b->graph_groups : b->graph;
         hipError_t e = hipStreamEndCapture(ctx->stream, &gr);
         b->decoded = false;
@@ -991,6 +998,11 @@ int pjd_batch_capture(pjd_batch *b)
         HIP_TRY(ctx, hipGraphInstantiate(variant ? &b->graph_exec_groups : &b->graph_exec, gr, nullptr, nullptr, 0));
     }
     return PJD_OK;
+}
+
+int pjd_batch_decode_chains(pjd_batch *b)
+{
+    return b ? b->chains : PJD_E_ARG;
 }
 
 int pjd_batch_sync(pjd_batch *b)

@@ -682,8 +682,21 @@ int pjd_make_plan(const pjd_image_desc *images, int n, int out_format, PjdPlan &
         std::vector<uint32_t> cuts_pct = {30, 65};
         if (const char *e = std::getenv("PJD_GROUPS")) { const int v = std::atoi(e); want = (uint32_t)(v < 1 ? 1 : (v > PJD_MAX_GROUPS ? PJD_MAX_GROUPS : v)); cuts_pct.clear(); }
         if (const char *e = std::getenv("PJD_GROUP_CUTS")) {
+            // a list of percents, strictly ascending within 1..99, separated by one comma and any spaces; anything else: the default cuts
             cuts_pct.clear();
-            for (const char *q = e; *q;) { cuts_pct.push_back((uint32_t)std::strtoul(q, const_cast<char **>(&q), 10)); while (*q == ',' || *q == ' ') q++; }
+            bool ok = true;
+            for (const char *q = e; ok;) {
+                char *end = nullptr;
+                const unsigned long v = std::strtoul(q, &end, 10);
+                ok = end != q && v >= 1 && v <= 99 && (cuts_pct.empty() || v > cuts_pct.back());        // end == q: nothing consumed
+                if (!ok) break;
+                cuts_pct.push_back((uint32_t)v);
+                for (q = end; *q == ' '; q++) {}
+                if (!*q) break;
+                ok = *q == ',';
+                q++;
+            }
+            if (!ok) cuts_pct = {30, 65};
             want = (uint32_t)cuts_pct.size() + 1;
             if (want > PJD_MAX_GROUPS) { want = PJD_MAX_GROUPS; cuts_pct.resize(PJD_MAX_GROUPS - 1); }
         }

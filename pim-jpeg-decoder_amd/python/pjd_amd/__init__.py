@@ -452,6 +452,16 @@ class Batch:
     def sync(self):
         self.ctx._check(self.L.pjd_batch_sync(self._h), "pjd_batch_sync")
 
+    def decode_chains(self):
+        """pjd_batch_decode_chains: the form the last decode was issued in -- 0 before the first, 1 for one chain of launches, g >= 2 for
+        the chains of g picture groups (a replay: the form of the graph that was launched; decode_timed: always 1)."""
+        self.L.pjd_batch_decode_chains.restype = C.c_int32
+        self.L.pjd_batch_decode_chains.argtypes = [C.c_void_p]
+        n = int(self.L.pjd_batch_decode_chains(self._h))
+        if n < 0:
+            self.ctx._check(n, "pjd_batch_decode_chains")
+        return n
+
     def info(self):
         bi = BatchInfo()
         self.ctx._check(self.L.pjd_batch_get_info(self._h, C.byref(bi)), "pjd_batch_get_info")

@@ -216,9 +216,10 @@ def _group_items():
     return [D.member("ladder64")] + [D.member(l) for l in D.group_batch()]
 
 
-def _groups_run(port, items, want_groups):
+def _groups_run(port, items, want_groups, want_chains=None):
     """Decode the group batch in this process' environment; everything against the intent; -> a digest of statuses, coefficients and
-    pictures."""
+    pictures.  want_chains: the form the decode must report (Batch.decode_chains); None: the planner's groups, one chain where it
+    made none."""
     import pjd_amd
     scanned = _scan(items)
     scanned[0].desc.flags = int(scanned[0].desc.flags) | pjd_amd.F_FORCE_SEQUENTIAL
@@ -227,6 +228,7 @@ def _groups_run(port, items, want_groups):
     try:
         with ctx.batch([s.desc for s in scanned]) as b:
             b.upload(); b.decode(); b.sync()
+            assert b.decode_chains() == ((want_groups or 1) if want_chains is None else want_chains), (b.decode_chains(), want_groups, want_chains)
             outs, st = b.download()
             info = b.info()
             assert info["dc_plan"] >> 8 == want_groups and info["sub_bytes"] == D.S, info["dc_plan"]
@@ -272,7 +274,7 @@ def _groups_child(path):
     with open(path, "rb") as f:
         items, exp = pickle.load(f)
     _EXPECTED.update(exp)
-    return _groups_run(oracle_lib.Port(), items, 3)
+    return _groups_run(oracle_lib.Port(), items, 3, want_chains=1)
 
 
 def test_picture_groups_planned_but_run_as_one_chain(port, lanes128, monkeypatch, tmp_path):

@@ -1279,12 +1279,14 @@ def test_idle_device_forms_equal_the_single_chain(ctx, port):
                     busy.capture()
                 # (1) alone: the library finds the device idle -> picture groups
                 b.decode(); b.sync()
+                assert b.decode_chains() == 3, (graph, b.decode_chains())
                 outs, st = b.download()
                 results.append(([o.tobytes() for o in outs], list(st), b.coefficients(7).tobytes(), b.coefficients(40).tobytes()))
                 # (2) issued while another batch's decode is in flight -> one chain
                 busy.decode()
                 b.decode()
                 busy.sync(); b.sync()
+                assert b.decode_chains() == 1 and busy.decode_chains() == 3, (graph, b.decode_chains(), busy.decode_chains())
                 outs, st = b.download()
                 results.append(([o.tobytes() for o in outs], list(st), b.coefficients(7).tobytes(), b.coefficients(40).tobytes()))
             info = b.info()

@@ -253,6 +253,7 @@ b = ctx.batch([s.desc for s in sc], pjd_amd.OUT_RGB8_PLANAR)
 b.upload(); b.capture()
 for rep in range(2):
     b.decode(); b.sync()
+    assert b.decode_chains() == 3, (rep, b.decode_chains())
 outs, st = b.download()
 bad = [k for k in range(len(jpegs)) if st[k] != 0 or not np.array_equal(outs[k], port.decode(jpegs[k])["rgb"].transpose(2, 0, 1))]
 print("RESULT", "ok" if not bad else bad[:5])

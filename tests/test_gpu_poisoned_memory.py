@@ -386,6 +386,7 @@ def test_picture_groups_with_damaged_pictures(pctx):
                 b.capture()
             b.decode()
             outs, st = b.download()
+            assert b.info()["dc_plan"] >> 8 == 3 and b.decode_chains() == 3, (step, b.info()["dc_plan"] >> 8, b.decode_chains())
             assert _check_streams(jpegs, outs, st, "bmp") >= 10, step
 
 

@@ -126,7 +126,7 @@ def _many_small():
     return tuple(out)
 
 
-def _groups_run():
+def _groups_run(want_chains=3):
     import pjd_amd
     items = _many_small()
     c = pjd_amd.Context(0)
@@ -139,6 +139,7 @@ def _groups_run():
                     b.capture()
                 b.decode()
                 _check(b, items)
+                assert b.decode_chains() == want_chains, (step, b.decode_chains())
             info = b.info()
         assert info["n_sequential"] == 0 and info["n_fallback"] == 0 and info["n_table_sets"] > 8, info
     finally:
@@ -159,7 +160,7 @@ def test_idle_device_forms():
     """The picture-group form a decode takes on an idle device (this process: nothing else is in flight), and PJD_IDLE_FORM=chain in a
     fresh child: no group's chain makes its word rows any more, both forms read the upload's."""
     assert _groups_run() >= 64
-    assert int(_child("_groups_run()", {"PJD_IDLE_FORM": "chain"})[0]) >= 64
+    assert int(_child("_groups_run(1)", {"PJD_IDLE_FORM": "chain"})[0]) >= 64
 
 
 # ---- 4 ---------------------------------------------------------------------------------------------------------------------------------
