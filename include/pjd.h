@@ -48,6 +48,9 @@
  *   (none: an addition)                                 pjd_batch_set_colour + pjd_colour_value + pjd_colour_check: every output's 8-bit triple
  *                                                       through a 3 x 4 colour map of its own inside that launch (ColorJitter,
  *                                                       RandomGrayscale, BGR, DALI color_twist / hsv / brightness_contrast)
+ *   (none: an addition)                                 pjd_batch_set_blur + pjd_blur_taps + pjd_blur_index + pjd_blur_check: every output
+ *                                                       through a separable Gaussian of its own in one launch behind the resample
+ *                                                       (torchvision's GaussianBlur of SimCLR, MoCo v2, BYOL, DINO, SwAV)
  *
  * Plain pointers and sizes only; no C++ or torch types.  Thread model: one
  * submitting thread per pjd_ctx (the reference has one consumer thread,
@@ -74,7 +77,7 @@ extern "C" {
  * struct either, so PJD_VERSION stays 6: a caller checks for it by the symbol pjd_resize_pad_check.  Views (pjd_batch_set_views)
  * changed no struct: a caller checks for them by the symbol pjd_batch_n_outputs.  The affine warp (pjd_batch_set_resize_affine) changed
  * none: a caller checks for it by the symbol pjd_warp_tap.  The colour map (pjd_batch_set_colour) changed none: a caller checks for it
- * by the symbol pjd_colour_value.  pjd_batch_decode_chains changed none either: a caller checks for it by its own symbol.
+ * by the symbol pjd_colour_value.  The Gaussian blur (pjd_batch_set_blur) changed none: the symbol pjd_blur_taps.  pjd_batch_decode_chains changed none either: a caller checks for it by its own symbol.
  * A caller built against another version must not pass its structs: check pjd_version() == PJD_VERSION after loading.     */
 #define PJD_VERSION 6
 
@@ -906,6 +909,65 @@ int  pjd_resize_affine_check(uint32_t sw, uint32_t sh, uint32_t tw, uint32_t th,
 int  pjd_batch_set_colour(pjd_batch *b, const double (*m)[12] /* pjd_batch_n_outputs(b) */);
 int  pjd_colour_value(const double m[12], const uint8_t rgb[3], uint8_t out[3]);   /* host only, no device needed */
 int  pjd_colour_check(const double m[12]);                                        /* host only: 1 ok, 0 refused */
+/* ---- Gaussian blur on decode: a separable blur per output ----------------------------------------------------------------------------- *
+ * pjd_batch_set_blur: output i of a resized batch -- picture i, or view i after pjd_batch_set_views -- leaves as the separable Gaussian of
+ * what the batch would deliver without the call, in one more launch behind the resample (or the warp): torchvision's GaussianBlur of the
+ * SimCLR, MoCo v2, BYOL, DINO and SwAV recipes, between the colour ops and the normalisation.
+ *
+ * MEANING (normative).  Let U be the uint8 output the same batch delivers without this call and without pjd_batch_set_normalize: after
+ * whatever filter, window, orientation, views, affine warp (fill included) and colour map are set, and whatever PJD_F_* made the picture.
+ * An output with ksize == 0 (sigma must then be 0) is U, byte for byte.  Otherwise the output is the separable Gaussian of U over the whole
+ * tw x th output, the same taps on both axes, each channel on its own.
+ * TAPS.  ksize is odd and within 1..PJD_BLUR_MAX_TAPS, r = ksize / 2; sigma is finite and greater than 0.  In IEEE double:
+ *     w[j] = exp(-0.5 * ((j - r) / sigma)^2),  t = w[0] + w[1] + ... in index order,  q[j] = llrint(w[j] / t * 65536),
+ * then q[r] += 65536 - sum(q).  The taps are symmetric, non-negative and sum to exactly 65536 (the centre is the largest tap, of at least
+ * 65536 / ksize, and the correction at most ksize / 2 in magnitude).  The HOST builds the table once per distinct (ksize, sigma) of a batch
+ * (pjd_blur_taps is that code); the kernel reads it and never evaluates exp.
+ * BORDER.  torchvision's "reflect", defined for every size: sample i of an axis of n samples is sample idx(i), where for n == 1
+ * idx(i) = 0 and otherwise, with p = 2 * (n - 1): m = i mod p (0 <= m < p), idx(i) = m < n ? m : p - m.  A halo wider than the output
+ * folds several times.  pjd_blur_index is this rule.
+ * ARITHMETIC.  Unsigned 32-bit, the triangle filter's own (pjd_batch_set_resize_filter, PJD_RESIZE_ANTIALIAS).  Horizontal first:
+ *     h   = sum_j q[j] * U[y][idx(x + j - r)]             at most 255 * 65536 < 2^24
+ *     h8  = (h + 128) >> 8                                 the row sample, at most 65280: 16 bits
+ *     v   = sum_j q[j] * h8[idx(y + j - r)][x]             v + 2^23 is at most 65536 * 65280 + 2^23 = 4 286 578 688 < 2^32
+ *     out = (v + 2^23) >> 24
+ * CONSEQUENCES.  A table whose only non-zero tap is the centre (ksize 1; sigma 0.1 at any ksize) is the identity, exactly: h8 = 256 * U
+ * and out = U; the kernel skips nothing but reads that one tap.  A constant picture stays constant, for the taps sum to 65536.  Against
+ * the same filter in float64 (the unquantised w[j] / t, no intermediate rounding) the result differs by less than one level: half a level
+ * for the final rounding, 2^-9 for the row sample (half a unit of h8, 1/256 level, through vertical taps that sum to 1), and per axis at
+ * most ksize * 2^-16 * 255 for the taps -- each within 2^-17 of its value before the centre takes up to ksize * 2^-17 more -- so
+ * 0.5 + 0.002 + 2 * 63 * 255 / 65536 = 0.993 at 63 taps (0.506 was the worst found by the model of tests/blur_model.py).  It is within one
+ * level of torchvision.transforms.v2.functional.gaussian_blur on the uint8 tensor wherever r < min(tw, th), torch's own limit for reflect
+ * padding.  Pillow's ImageFilter.GaussianBlur is a box approximation and is NOT reproduced.
+ * ORDER.  The normalisation of pjd_batch_set_normalize reads the blurred byte.
+ *
+ * CALL ORDER.  After pjd_batch_set_resize and everything that shapes the resample, pjd_batch_set_colour included (after pjd_batch_set_views
+ * where used: one entry per OUTPUT); before pjd_batch_set_normalize / _bind_output / _upload; once: PJD_E_STATE otherwise, also when no
+ * resize is set, and for a shaping setter called behind it.  PJD_E_ARG for a null pointer, an entry pjd_blur_check refuses (an even ksize,
+ * one above PJD_BLUR_MAX_TAPS, a sigma that is not finite or not positive with ksize > 0, a non-zero sigma with ksize == 0, a non-zero
+ * reserved_; pjd_last_error names the picture, or "view <v> (picture <p>)"), and for a batch with pjd_batch_set_resize_pad: the border
+ * there is not content, and a pad value has no 8-bit form.  The batch is then as it was and the call still open.
+ * COMPOSES WITH all three filters, windows, orientations, views, the affine warp, the colour map, PJD_OUT_RGB8, PJD_OUT_RGB8_PLANAR and
+ * PJD_OUT_GRAY8 (one channel), pjd_batch_set_normalize (all element types), pjd_batch_bind_output (any element-aligned offset),
+ * PJD_F_LIBJPEG pictures, both scale families, captured graphs, and the exact-kernel fallback of pjd_batch_sync, behind which the launch
+ * runs again.
+ * HOW.  The resample (or warp) launch of a blurred batch writes U, uint8 and not normalised, into one more intermediate buffer of the
+ * batch (the packed layout of the uint8 outputs); the blur launch reads it and writes the final ranges, normalised where asked for.
+ * Outputs with ksize == 0 pass through that launch as a copy.  Every decode writes every byte of every output's range and none outside
+ * it, and every byte of the intermediate buffer that the blur launch reads.  pjd_batch_decode_timed names the launch "blur", behind
+ * "resize" or "warp".  The buffer, one 40-byte record per output, the tile prefix and the tap table are counted in
+ * pjd_batch_info::device_bytes and sent by pjd_batch_upload.  A batch that never makes the call allocates, uploads and launches what it
+ * did before.
+ * pjd_blur_taps, pjd_blur_index and pjd_blur_check are host only and THE implementations.  pjd_blur_taps and pjd_blur_index return
+ * PJD_E_ARG for a null pointer or arguments beyond the limits (n is 1..65535); pjd_blur_check returns 1 for an entry the setter accepts
+ * and 0 for one it refuses (null included).
+ * DETECTION.  No struct changed and PJD_VERSION stays 6: a caller checks for the symbol pjd_blur_taps.                               */
+#define PJD_BLUR_MAX_TAPS 63
+typedef struct pjd_blur { double sigma; uint32_t ksize; uint32_t reserved_; } pjd_blur;
+int  pjd_batch_set_blur(pjd_batch *b, const pjd_blur *blur /* pjd_batch_n_outputs(b) */);
+int  pjd_blur_taps(uint32_t ksize, double sigma, uint32_t *q /* ksize */);         /* host only */
+int  pjd_blur_index(uint32_t n, int64_t i, uint32_t *src);                         /* host only: the border rule */
+int  pjd_blur_check(const pjd_blur *blur);                                         /* host only: 1 ok, 0 refused */
 /* ---- normalised float output ------------------------------------------------------------------------------------------------- *
  * pjd_batch_set_normalize: the pictures of the batch leave the decode as floating-point elements, sample * scale[c] + bias[c] -- what
  * x.float().div(255).sub(mean).div(std).to(dtype) makes of the uint8 tensor, without that tensor ever existing.  The caller passes

@@ -231,6 +231,13 @@ struct pjd_batch {
     Pair aa;                                     // a table-driven filter: PjdDevResizeAA[n_out], then the weight table
     Pair warp;                                   // form.warp (pjd_batch_set_resize_affine): PjdDevWarp[n_out]
     Pair col;                                    // form.coloured (pjd_batch_set_colour): PjdDevColour[n_out]
+    // form.blurred (pjd_batch_set_blur): PjdDevBlur[n_out], the prefix sum of the blur launch's tiles [n_out + 1], then the tap table; and
+    // the blur intermediate, U of every output as uint8 in the packed layout.  The resample (or warp) launch then writes THAT, not
+    // normalised, and the blur launch behind it writes res_out: the final offsets are the blur records' (set_result_offsets).
+    Pair blur;
+    uint8_t *d_blur_buf = nullptr;
+    uint8_t *resample_dst() const { return form.blurred ? d_blur_buf : res_out; }
+    PjdNormalize resample_norm() const { return form.blurred ? PjdNormalize{} : norm; }
     PjdNormalize norm{};                         // pjd_batch_set_normalize: dtype != 0, the result holds elements of PJD_DT_SIZE(dtype) bytes
     uint8_t pad_fill[3] = {0, 0, 0};             // pjd_batch_set_resize_pad
     bool pad_value_set = false;                  // pjd_batch_set_pad_value
@@ -241,7 +248,7 @@ struct pjd_batch {
     {
         const size_t n = n_out();                // the records' count: the kernels find a tile's record by it, whatever picture the record reads
         const bool planar = back.planes();
-        pjd_launch_resize(s, PjdResizeLaunch{dev.out, res_out, (const PjdDevResize *)rs.d, (const uint32_t *)(rs.d + n * sizeof(PjdDevResize)), (uint32_t)n, form.tiles, planar, norm,
+        pjd_launch_resize(s, PjdResizeLaunch{dev.out, resample_dst(), (const PjdDevResize *)rs.d, (const uint32_t *)(rs.d + n * sizeof(PjdDevResize)), (uint32_t)n, form.tiles, planar, resample_norm(),
                                              form.windowed ? (const PjdDevResizeWin *)win.d : nullptr, form.oriented, spec.filter,
                                              (const PjdDevResizeAA *)aa.d, aa.d ? (const uint32_t *)(aa.d + n * sizeof(PjdDevResizeAA)) : nullptr, form.lds,
                                              form.padded ? (const PjdDevResizePad *)pad.d : nullptr, spec.channels,
@@ -252,9 +259,17 @@ struct pjd_batch {
     {
         const size_t n = n_out();
         const uint8_t *f = spec.affine_fill;
-        pjd_launch_warp(s, PjdWarpLaunch{dev.out, res_out, (const PjdDevResize *)rs.d, (const PjdDevWarp *)warp.d, (const uint32_t *)(rs.d + n * sizeof(PjdDevResize)), (uint32_t)n, form.tiles,
-                                         back.planes(), norm, (uint32_t)f[0] | ((uint32_t)f[1] << 8) | ((uint32_t)f[2] << 16), spec.channels,
+        pjd_launch_warp(s, PjdWarpLaunch{dev.out, resample_dst(), (const PjdDevResize *)rs.d, (const PjdDevWarp *)warp.d, (const uint32_t *)(rs.d + n * sizeof(PjdDevResize)), (uint32_t)n, form.tiles,
+                                         back.planes(), resample_norm(), (uint32_t)f[0] | ((uint32_t)f[1] << 8) | ((uint32_t)f[2] << 16), spec.channels,
                                          form.coloured ? (const PjdDevColour *)col.d : nullptr});
+    }
+    // the blur of this batch (form.blurred), behind either: from the blur intermediate to the final ranges, normalised where asked for
+    void launch_blur(hipStream_t s) const
+    {
+        const size_t n = n_out();
+        const uint8_t *prefix = blur.d + n * sizeof(PjdDevBlur);
+        pjd_launch_blur(s, PjdBlurLaunch{d_blur_buf, res_out, (const PjdDevBlur *)blur.d, (const uint32_t *)prefix, (const uint32_t *)(prefix + (n + 1) * sizeof(uint32_t)), (uint32_t)n,
+                                         form.blur_tiles, back.planes(), norm, spec.channels, form.blur_lds});
     }
     // ... and the border of its padded pictures, behind it: the two write disjoint bytes
     void launch_pad(hipStream_t s) const
@@ -314,6 +329,11 @@ int commit_request(pjd_batch *b, PjdResizeSpec &spec, const PjdResizeWork &w)
     if (rc == PJD_OK && spec.filter != PJD_RESIZE_BILINEAR) rc = take_pair(b, b->aa, n * sizeof(PjdDevResizeAA) + w.tab.size() * sizeof(uint32_t));
     if (rc == PJD_OK && w.form.warp) rc = take_pair(b, b->warp, n * sizeof(PjdDevWarp));
     if (rc == PJD_OK && w.form.coloured) rc = take_pair(b, b->col, n * sizeof(PjdDevColour));
+    if (rc == PJD_OK && w.form.blurred) rc = take_pair(b, b->blur, n * sizeof(PjdDevBlur) + (n + 1) * sizeof(uint32_t) + w.blur_taps.size() * sizeof(uint32_t));
+    if (rc == PJD_OK && w.form.blurred && !b->d_blur_buf) {            // the blur intermediate, taken once as the pairs are
+        rc = pool_dev_alloc(b->ctx, (void **)&b->d_blur_buf, (size_t)w.form.blur_buf_bytes, b->dev_blocks);
+        if (rc == PJD_OK) b->device_bytes += w.form.blur_buf_bytes;
+    }
     if (rc != PJD_OK) return rc;
     put(b->rs, w.recs, w.tile_prefix);
     if (w.form.windowed) put(b->win, w.win);
@@ -321,6 +341,10 @@ int commit_request(pjd_batch *b, PjdResizeSpec &spec, const PjdResizeWork &w)
     if (spec.filter != PJD_RESIZE_BILINEAR) put(b->aa, w.aa, w.tab);
     if (w.form.warp) put(b->warp, w.warp);
     if (w.form.coloured) put(b->col, w.colour);
+    if (w.form.blurred) {
+        put(b->blur, w.blur, w.blur_prefix);
+        std::memcpy(b->blur.h + n * sizeof(PjdDevBlur) + (n + 1) * sizeof(uint32_t), w.blur_taps.data(), w.blur_taps.size() * sizeof(uint32_t));
+    }
     b->spec = std::move(spec);
     b->form = w.form;
     return PJD_OK;
@@ -338,13 +362,19 @@ int apply_request(pjd_batch *b, PjdResizeSpec &spec, const char *setter)
 // the delivered pictures at other offsets of the result buffer (pjd_batch_set_normalize, pjd_batch_bind_output): request and records
 void set_result_offsets(pjd_batch *b, const std::vector<uint64_t> &off)
 {
+    // a blurred batch (pjd_batch_set_blur): the blur launch writes the results, the resample keeps writing the blur intermediate
+    if (b->form.blurred) {
+        PjdDevBlur *recs = (PjdDevBlur *)b->blur.h;
+        for (size_t i = 0; i < off.size(); i++) b->spec.pic[i].dst_off = recs[i].dst_off = off[i];
+        return;
+    }
     PjdDevResize *recs = (PjdDevResize *)b->rs.h;
     for (size_t i = 0; i < off.size(); i++) b->spec.pic[i].dst_off = recs[i].dst_off = off[i];
 }
 
 // The order of the calls that shape a batch (include/pjd.h, CALL ORDER): the stages, each passed at most once but for the
 // last two.  A new setter is a row here, at its place.
-enum Stage { ST_NONE = -1, ST_VIEWS, ST_RESIZE, ST_PAD, ST_ORIENTATION, ST_WINDOW, ST_FILTER, ST_AFFINE, ST_COLOUR, ST_NORMALIZE, ST_PAD_VALUE, ST_BIND, ST_UPLOAD, N_STAGES };
+enum Stage { ST_NONE = -1, ST_VIEWS, ST_RESIZE, ST_PAD, ST_ORIENTATION, ST_WINDOW, ST_FILTER, ST_AFFINE, ST_COLOUR, ST_BLUR, ST_NORMALIZE, ST_PAD_VALUE, ST_BIND, ST_UPLOAD, N_STAGES };
 struct StageRule {
     const char *name;                          // the call, as the messages spell it
     bool (*passed)(const pjd_batch *);         // has the batch been through it?
@@ -361,6 +391,7 @@ const StageRule STAGES[N_STAGES] = {
     {"set_resize_filter", [](const pjd_batch *b) { return b->spec.filter_set; }, false, {ST_RESIZE, ST_NONE},   ""},
     {"set_resize_affine", [](const pjd_batch *b) { return b->spec.affine_set; }, false, {ST_RESIZE, ST_NONE},   ""},
     {"set_colour",        [](const pjd_batch *b) { return b->spec.colour_set; }, false, {ST_RESIZE, ST_NONE},   ""},
+    {"set_blur",          [](const pjd_batch *b) { return b->spec.blur_set; },   false, {ST_RESIZE, ST_NONE},   ""},
     {"set_normalize",     [](const pjd_batch *b) { return b->norm.dtype != 0; }, false, {ST_NONE, ST_NONE},     "the batch is not normalised (pjd_batch_set_normalize first)"},
     {"set_pad_value",     [](const pjd_batch *b) { return b->pad_value_set; },   false, {ST_PAD, ST_NORMALIZE}, ""},
     {"bind_output",       [](const pjd_batch *b) { return b->bound; },           true,  {ST_NONE, ST_NONE},     ""},
@@ -647,6 +678,7 @@ int pjd_batch_upload(pjd_batch *b)
     if (b->form.padded) HIP_TRY(ctx, hipMemcpyAsync(b->pad.d, b->pad.h, b->pad.bytes, hipMemcpyHostToDevice, s));    // ... and its canvases
     if (b->form.warp) HIP_TRY(ctx, hipMemcpyAsync(b->warp.d, b->warp.h, b->warp.bytes, hipMemcpyHostToDevice, s));   // ... or its affine maps
     if (b->form.coloured) HIP_TRY(ctx, hipMemcpyAsync(b->col.d, b->col.h, b->col.bytes, hipMemcpyHostToDevice, s));  // ... and its colour maps
+    if (b->form.blurred) HIP_TRY(ctx, hipMemcpyAsync(b->blur.d, b->blur.h, b->blur.bytes, hipMemcpyHostToDevice, s));  // ... and the work list and taps of its blur
     // What depends on the blob alone is made here, once per upload, behind its copy: the decode tables of every table set (the exact
     // path uses them too) and the lanes' word rows.  No kernel of a decode writes either, so every decode of
     // the resident batch -- launched or replayed from its graphs -- reads what this upload left.
@@ -733,13 +765,17 @@ void launch_resample(hipStream_t s, const pjd_batch *b, KernelTimer *kt)
     if (b->form.warp) {                                    // pjd_batch_set_resize_affine: the one launch, which writes the fill too
         b->launch_warp(s);
         if (kt) kt->mark("warp");
-        return;
+    } else {
+        b->launch_resize(s);
+        if (kt) kt->mark("resize");
+        if (b->form.padded) {
+            b->launch_pad(s);
+            if (kt) kt->mark("pad");
+        }
     }
-    b->launch_resize(s);
-    if (kt) kt->mark("resize");
-    if (!b->form.padded) return;
-    b->launch_pad(s);
-    if (kt) kt->mark("pad");
+    if (!b->form.blurred) return;
+    b->launch_blur(s);                                     // pjd_batch_set_blur: what was just written is U, in the blur intermediate
+    if (kt) kt->mark("blur");
 }
 
 int enqueue_decode(pjd_batch *b, pjd_timings *timings, bool use_groups)
@@ -1394,6 +1430,36 @@ int pjd_batch_set_colour(pjd_batch *b, const double (*m)[12])
     spec.colour.resize(spec.pic.size());
     for (size_t i = 0; i < spec.pic.size(); i++) std::memcpy(spec.colour[i].m, m[i], sizeof spec.colour[i].m);
     return apply_request(b, spec, "set_colour");
+}
+
+int pjd_blur_check(const pjd_blur *blur) { return pjd_blur_fault(blur) ? 0 : 1; }
+
+int pjd_blur_taps(uint32_t ksize, double sigma, uint32_t *q)
+{
+    const pjd_blur e{sigma, ksize, 0u};
+    if (!q || ksize == 0 || pjd_blur_fault(&e)) return PJD_E_ARG;
+    pjd_blur_taps_calc(ksize, sigma, q);
+    return PJD_OK;
+}
+
+int pjd_blur_index(uint32_t n, int64_t i, uint32_t *src)
+{
+    if (!src || n == 0 || n > 65535u) return PJD_E_ARG;
+    const int64_t p = n > 1u ? 2 * ((int64_t)n - 1) : 1;  // the period: the rule folds by it, so does the 64-bit index before it is narrowed
+    *src = pjd_blur_index_calc(n, (int32_t)(i % p));
+    return PJD_OK;
+}
+
+int pjd_batch_set_blur(pjd_batch *b, const pjd_blur *blur)
+{
+    if (!b) return PJD_E_ARG;
+    pjd_ctx *ctx = b->ctx;
+    if (int rc = check_order(b, ST_BLUR)) return rc;
+    if (!blur) { ctx->err = "set_blur: null record array"; return PJD_E_ARG; }
+    PjdResizeSpec spec = b->spec;
+    spec.blur_set = true;
+    spec.blur.assign(blur, blur + spec.pic.size());
+    return apply_request(b, spec, "set_blur");
 }
 
 int pjd_resize_pad_check(uint32_t out_w, uint32_t out_h, const pjd_resize_pad *pad)

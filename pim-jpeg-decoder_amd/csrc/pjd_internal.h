@@ -656,3 +656,41 @@ static inline __host__ __device__ uint32_t pjd_colour_calc(const int32_t (&q)[3]
 #endif
     return (uint32_t)(s < 0 ? 0 : s > 255 ? 255 : s);
 }
+
+// ---- Gaussian blur (pjd_batch_set_blur; the arithmetic is normative: include/pjd.h) ----------------------------------------------
+// One output of the blur launch (pjd_k_blur.hip), made by pjd_resize_resolve: U, the uint8 output the resample (or warp) launch of a
+// blurred batch wrote into the batch's blur intermediate at src_off, in the batch's layout; the final range at dst_off in the result
+// buffer; the taps at taps[tap_off .. tap_off + ksize).  Row 0 of the table is the one tap {65536}, which a record flagged
+// PJD_BLUR_IDENTITY reads whatever its ksize (no blur asked for, or a table whose only non-zero tap is the centre): the same arithmetic
+// with r = 0, which is the copy.  40 bytes.
+#define PJD_BLUR_IDENTITY 1u
+struct PjdDevBlur {
+    uint64_t src_off, dst_off;
+    uint32_t tw, th;
+    uint32_t ksize, tap_off;           // as asked for (0: none); the first tap in the table
+    uint32_t flags;
+    uint32_t col_tiles;                // tiles per tile row: ceil(tw / PJD_BLUR_COLS)
+};
+// A tile of the blur launch: one workgroup of PJD_BLUR_THREADS, PJD_BLUR_COLS x PJD_BLUR_ROWS samples of one output, a thread
+// PJD_RS_PX adjacent pixels of two adjacent rows (pjd_k_blur_body.h)
+#define PJD_BLUR_COLS    64
+#define PJD_BLUR_ROWS    32
+#define PJD_BLUR_THREADS 256
+// the LDS of a tile with radius r, ONE channel at a time: the staged bytes (tile + halo, the row pitch a multiple of 4), the row samples
+// as 16-bit words, and the finished bytes of all nc channels
+static inline __host__ __device__ uint32_t pjd_blur_pitch(uint32_t r) { return (PJD_BLUR_COLS + 2u * r + 3u) & ~3u; }
+static inline __host__ __device__ uint32_t pjd_blur_lds(uint32_t r, uint32_t nc)
+{
+    return (PJD_BLUR_ROWS + 2u * r) * (pjd_blur_pitch(r) + 2u * PJD_BLUR_COLS) + nc * PJD_BLUR_ROWS * PJD_BLUR_COLS;
+}
+// THE border rule (reflect, include/pjd.h): n in 1..65535, any 32-bit i -- the kernel asks for -31 .. n + 30, which is several periods
+// where n is small, so the general case folds by remainder.  pjd_blur_index exports it (its 64-bit i reduced by the period first).
+static inline __host__ __device__ uint32_t pjd_blur_index_calc(uint32_t n, int32_t i)
+{
+    if ((uint32_t)i < n) return (uint32_t)i;               // inside: every sample of an interior tile
+    if (n == 1u) return 0u;
+    const int32_t p = 2 * ((int32_t)n - 1);
+    int32_t m = i % p;
+    if (m < 0) m += p;
+    return (uint32_t)(m < (int32_t)n ? m : p - m);
+}

@@ -136,6 +136,22 @@ struct PjdWarpLaunch {
     const PjdDevColour *colour = nullptr; // pjd_batch_set_colour: null, or colour[i] is output i's map, applied to the blend (the fill included); three channels (pjd_k_warp_col)
 };
 void pjd_launch_warp(hipStream_t s, const PjdWarpLaunch &a);
+// ---- Gaussian blur on decode (pjd_k_blur.hip; pjd_batch_set_blur): every output from U in `src` (the blur intermediate: uint8, the
+// batch's layout) through its own taps into `dst`, one launch that writes every byte; tile_prefix in tiles of PJD_BLUR_COLS x
+// PJD_BLUR_ROWS; taps: the table recs[i].tap_off points into; lds_bytes: pjd_blur_lds of the batch's largest radius
+struct PjdBlurLaunch {
+    const uint8_t *src;
+    uint8_t *dst;
+    const PjdDevBlur *recs;
+    const uint32_t *tile_prefix;
+    const uint32_t *taps;
+    uint32_t n_images, n_tiles;
+    bool planar;
+    PjdNormalize norm;
+    uint32_t channels = 3;               // 3, or 1 for a grey batch: planar, one plane
+    uint32_t lds_bytes = 0;
+};
+void pjd_launch_blur(hipStream_t s, const PjdBlurLaunch &a);
 // ---- stage-level parity (pjd_k_coefdump.hip): coefficients in the reference's MCU_buffer layout; `out` is zeroed by the caller
 void pjd_launch_coefdump_lanes(hipStream_t s, const PjdDevBatch &b, uint32_t image, uint32_t n_iwg, int16_t *out);
 void pjd_launch_coefdump_dense(hipStream_t s, const PjdDevBatch &b, uint32_t image, const int16_t *scratch, uint32_t first_du, uint32_t n_du, int16_t *out);

@@ -86,7 +86,86 @@ uint16_t f32_to_f16_bits(float f)
     return (uint16_t)(sign | q);                           // a carry out of the mantissa runs into the exponent: 0x7c00 is infinity
 }
 
+uint64_t blur_tiles_of(uint32_t tw, uint32_t th) { return (uint64_t)((tw + PJD_BLUR_COLS - 1) / PJD_BLUR_COLS) * ((th + PJD_BLUR_ROWS - 1) / PJD_BLUR_ROWS); }
+
+// The blur launch behind a resolved request (pjd_batch_set_blur): U of every output moves into the blur intermediate -- the packed layout
+// of the uint8 outputs, which the resample's (or warp's) records then write -- and one blur record per output takes it from there to the
+// final range.  The tap table: row 0 is the one tap {65536}, which every output without a blur and every table whose only non-zero tap is
+// the centre reads; behind it one row per distinct (ksize, sigma), in the order the outputs name them.  The entries were checked before.
+PjdResizeFault blur_stage(const PjdResizeSpec &spec, PjdResizeWork &out)
+{
+    if (!spec.blur_set) return PjdResizeFault{};
+    const size_t n = spec.pic.size();
+    const PjdPackedLayout lay = pjd_packed_layout(spec.out_w.data(), spec.out_h.data(), n, 1, spec.channels);
+    out.blur.resize(n); out.blur_prefix.resize(n + 1);
+    out.blur_taps.assign(1, 65536u);
+    std::map<std::pair<uint32_t, uint64_t>, uint32_t> rows;           // (ksize, the bits of sigma) -> the row's offset; 0: the identity
+    uint64_t tiles = 0;
+    uint32_t r_max = 0;
+    for (size_t i = 0; i < n; i++) {
+        const pjd_blur &e = spec.blur[i];
+        uint32_t off = 0;
+        if (e.ksize > 1u) {
+            uint64_t bits;
+            std::memcpy(&bits, &e.sigma, 8);
+            auto it = rows.find({e.ksize, bits});
+            if (it != rows.end()) off = it->second;
+            else {
+                uint32_t q[PJD_BLUR_MAX_TAPS];
+                pjd_blur_taps_calc(e.ksize, e.sigma, q);
+                if (q[e.ksize / 2u] != 65536u) {           // the taps sum to 65536: the centre holds all of it, or the table blurs
+                    off = (uint32_t)out.blur_taps.size();
+                    out.blur_taps.insert(out.blur_taps.end(), q, q + e.ksize);
+                }
+                rows[{e.ksize, bits}] = off;
+            }
+        }
+        out.blur[i] = PjdDevBlur{lay.off[i], spec.pic[i].dst_off, spec.out_w[i], spec.out_h[i], e.ksize, off, off ? 0u : PJD_BLUR_IDENTITY,
+                                 (spec.out_w[i] + PJD_BLUR_COLS - 1) / PJD_BLUR_COLS};
+        out.recs[i].dst_off = lay.off[i];
+        if (off) r_max = std::max(r_max, e.ksize / 2u);
+        out.blur_prefix[i] = (uint32_t)tiles;
+        tiles += blur_tiles_of(spec.out_w[i], spec.out_h[i]);
+        if (tiles >= (1ull << 31)) return PjdResizeFault{"the targets of this batch are too large for one launch", -1};
+    }
+    out.blur_prefix[n] = out.form.blur_tiles = (uint32_t)tiles;
+    out.form.blurred = true;
+    out.form.blur_lds = pjd_blur_lds(r_max, spec.channels);
+    out.form.blur_buf_bytes = lay.buf_bytes;
+    return PjdResizeFault{};
+}
+
 }  // namespace
+
+const char *pjd_blur_fault(const pjd_blur *blur)
+{
+    if (!blur) return "null record";
+    if (blur->reserved_ != 0) return "reserved_ must be 0";
+    if (blur->ksize == 0) return blur->sigma == 0.0 ? nullptr : "sigma must be 0 where ksize == 0 (no blur)";
+    if (blur->ksize > PJD_BLUR_MAX_TAPS) return "ksize is beyond PJD_BLUR_MAX_TAPS";
+    if ((blur->ksize & 1u) == 0) return "ksize must be odd";
+    if (!std::isfinite(blur->sigma) || !(blur->sigma > 0.0)) return "sigma must be finite and greater than 0";
+    return nullptr;
+}
+
+// include/pjd.h, TAPS, term by term.  w[r] = exp(-0) = 1 and every other w is at most 1, so q[r] is the largest tap, at least
+// 65536 / ksize, and the correction -- at most half a unit per tap -- cannot take it below zero.
+void pjd_blur_taps_calc(uint32_t ksize, double sigma, uint32_t *q)
+{
+    const uint32_t r = ksize / 2u;
+    double w[PJD_BLUR_MAX_TAPS], t = 0.0;
+    for (uint32_t j = 0; j < ksize; j++) {
+        const double d = ((double)j - (double)r) / sigma;
+        w[j] = std::exp(-0.5 * (d * d));
+        t += w[j];
+    }
+    int64_t sum = 0;
+    for (uint32_t j = 0; j < ksize; j++) {
+        q[j] = (uint32_t)std::llrint(w[j] / t * 65536.0);
+        sum += q[j];
+    }
+    q[r] = (uint32_t)((int64_t)q[r] + 65536 - sum);
+}
 
 std::string pjd_resize_output_name(const PjdResizeSpec &spec, size_t i)
 {
@@ -190,6 +269,14 @@ PjdResizeFault pjd_resize_resolve(const PjdResizeSpec &spec, PjdResizeWork &out)
     for (size_t i = 0; i < n; i++)
         if (spec.out_w[i] == 0 || spec.out_w[i] > 65535u || spec.out_h[i] == 0 || spec.out_h[i] > 65535u) return fault_at(spec, i, "target width and height must be 1..65535");
 
+    // A blur (pjd_batch_set_blur) is a launch behind either request below (blur_stage), never behind a pad: the border there is not
+    // content, and a pad value has no 8-bit form
+    if (spec.blur_set) {
+        if (spec.pad_set) return PjdResizeFault{"a blur and set_resize_pad exclude each other on one batch (the border is not content)", -1};
+        for (size_t i = 0; i < n; i++)
+            if (const char *f = pjd_blur_fault(&spec.blur[i])) return fault_at(spec, i, f);
+    }
+
     // A colour map (pjd_batch_set_colour) is a layer on either request below: one record per output beside the work list, and the form
     // with the fewest kernels -- the padded one (identity window, orientation 1 and an all-zero pad where none was asked for), or the warp
     if (spec.colour_set) {
@@ -219,7 +306,7 @@ PjdResizeFault pjd_resize_resolve(const PjdResizeSpec &spec, PjdResizeWork &out)
         }
         out.tile_prefix[n] = form.tiles = (uint32_t)tiles;
         form.warp = true;
-        return PjdResizeFault{};
+        return blur_stage(spec, out);
     }
 
     // the content of every delivered picture: its canvas less its pad; a padded picture has a border line per canvas line
@@ -289,7 +376,7 @@ PjdResizeFault pjd_resize_resolve(const PjdResizeSpec &spec, PjdResizeWork &out)
     }
     out.tile_prefix[n] = form.tiles;
     if (form.padded) out.line_prefix[n] = form.lines;
-    if (!table) return PjdResizeFault{};
+    if (!table) return blur_stage(spec, out);
 
     // a table-driven filter.  A windowed picture takes the tables of its windowed axes, over the whole virtual target (tap index
     // ox + i', row length vw); one without is the windowed one with the identity window.  The limit is the window's (include/pjd.h)
@@ -318,7 +405,7 @@ PjdResizeFault pjd_resize_resolve(const PjdResizeSpec &spec, PjdResizeWork &out)
             form.lds = std::max(form.lds, pjd_resize_aa_lds((h1 & 0xffffu) + (h1 >> 16) - (h0 & 0xffffu), spec.planar, spec.channels));
         }
     }
-    return PjdResizeFault{};
+    return blur_stage(spec, out);
 }
 
 PjdPackedLayout pjd_packed_layout(const uint32_t *w, const uint32_t *h, size_t n, uint64_t elem_bytes, uint32_t channels)

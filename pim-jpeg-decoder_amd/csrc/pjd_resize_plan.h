@@ -2,7 +2,7 @@
 //
 // The records the kernels of pjd_k_resize.hip read are a PURE FUNCTION of the request: pjd_resize_resolve makes all of them from a
 // PjdResizeSpec in one go, and every setter of pjd_api.hip (pjd_batch_set_resize, _set_resize_pad, _set_orientation,
-// _set_resize_window, _set_resize_filter, _set_resize_affine, _set_colour) adds its argument to the batch's request and resolves again.  Each rule of include/pjd.h --
+// _set_resize_window, _set_resize_filter, _set_resize_affine, _set_colour, _set_blur) adds its argument to the batch's request and resolves again.  Each rule of include/pjd.h --
 // content = canvas - pad, the transpose swap, window defaults, the mirror's exclusive-or, the prefix sums, the axis tables, the LDS of
 // the launch, every limit -- is stated once, here.  Plain C++, no HIP: tools/resize_plan_host.cpp checks it on the CPU under the
 // sanitizers, tools/resize_host.cpp runs the kernel bodies over its records.
@@ -45,6 +45,10 @@ struct PjdResizeSpec {
     // pjd_batch_set_colour: a layer on either request.  It brings the most general per-axis form (as a grey batch does), or the warp form
     bool colour_set = false;
     std::vector<PjdColour> colour;         // one map per output, as given
+    // pjd_batch_set_blur: a launch of its own behind either request (never with a pad).  The resample then writes U, uint8, into the blur
+    // intermediate, and `pic[i].dst_off` -- the final range -- is where the blur record of output i writes
+    bool blur_set = false;
+    std::vector<pjd_blur> blur;            // one entry per output, as given
 };
 
 // What chooses the kernel and sizes its grid ...
@@ -53,6 +57,9 @@ struct PjdResizeForm {
     bool windowed = false, oriented = false, padded = false;    // the WIN / ORI / PAD kernels; padded implies oriented implies windowed
     bool warp = false;                                          // pjd_batch_set_resize_affine: the launch of pjd_k_warp.hip, whose tiles are PJD_WARP_COLS x PJD_WARP_ROWS; none of the three above
     bool coloured = false;                                      // pjd_batch_set_colour: the COL kernels; padded (so oriented and windowed), or warp
+    bool blurred = false;                                       // pjd_batch_set_blur: the launch of pjd_k_blur.hip behind the resample or warp, which then writes the blur intermediate
+    uint32_t blur_tiles = 0, blur_lds = 0;                      // ... its tiles (PJD_BLUR_COLS x PJD_BLUR_ROWS) and its LDS bytes: those of the batch's largest radius
+    uint64_t blur_buf_bytes = 0;                                // ... and the intermediate: the packed layout of the uint8 outputs
 };
 // ... and everything it reads (pjd_internal.h).  win, pad + line_prefix, aa + tab are empty where the form does not read them.
 struct PjdResizeWork {
@@ -67,6 +74,9 @@ struct PjdResizeWork {
     std::vector<uint32_t> ct_w, ct_h;      // the content of each delivered picture: the canvas less its pad
     std::vector<PjdDevWarp> warp;          // form.warp: the quantised map of every output
     std::vector<PjdDevColour> colour;      // form.coloured: the quantised colour map of every output
+    std::vector<PjdDevBlur> blur;          // form.blurred: one record per output (recs[i].dst_off is then its src_off, in the intermediate)
+    std::vector<uint32_t> blur_prefix;     // [n + 1]: the tiles of the blur launch
+    std::vector<uint32_t> blur_taps;       // row 0: {65536}; then one row per distinct (ksize, sigma) that is not the identity
 };
 
 // no fault: text is empty.  The text is what pjd_last_error reports behind the setter's own "set_...: "; picture -1: the batch as a whole,
@@ -97,6 +107,11 @@ const char *pjd_resize_affine_excludes(const PjdResizeSpec &spec);
 // every value llrint(m * 65536), bit 0 of the flags set where that is the identity; null, or what is wrong with m: a value that is not
 // finite, a weight beyond 16 or an offset beyond 4096 levels in magnitude, checked on the quantised values.
 const char *pjd_colour_quantise(const double m[12], PjdDevColour &out);
+
+// THE rules of a blur entry (include/pjd.h).  pjd_blur_fault: null, or what is wrong with it.  pjd_blur_taps_calc: the ksize taps of a
+// checked entry with ksize > 0, the code pjd_blur_taps exports and the table of a batch is made with.
+const char *pjd_blur_fault(const pjd_blur *blur);
+void pjd_blur_taps_calc(uint32_t ksize, double sigma, uint32_t *q);
 
 // The packed layout of a batch's results, as the planner lays out a batch's own buffer: n pictures of channels * w * h elements of
 // elem_bytes at 256-byte aligned offsets

@@ -84,6 +84,14 @@ class ResizePad(C.Structure):
     _fields_ = [("left", C.c_uint32), ("top", C.c_uint32), ("right", C.c_uint32), ("bottom", C.c_uint32)]
 
 
+BLUR_MAX_TAPS = 63                         # PJD_BLUR_MAX_TAPS
+
+
+class Blur(C.Structure):
+    """pjd_blur (pjd.h): one output's Gaussian -- sigma and the odd tap count ksize; ksize == 0 with sigma == 0: no blur."""
+    _fields_ = [("sigma", C.c_double), ("ksize", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
 class BatchInfo(C.Structure):
     _fields_ = [("n_images", C.c_int32), ("pixels", C.c_uint64), ("ecs_bytes", C.c_uint64),
                 ("out_bytes", C.c_uint64), ("coef_bytes", C.c_uint64), ("n_data_units", C.c_uint64),
@@ -224,6 +232,14 @@ def dev_lib():
         L.pjd_colour_value.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]
         L.pjd_colour_check.restype = i32
         L.pjd_colour_check.argtypes = [C.POINTER(C.c_double)]
+        L.pjd_batch_set_blur.restype = i32
+        L.pjd_batch_set_blur.argtypes = [vp, C.POINTER(Blur)]
+        L.pjd_blur_taps.restype = i32
+        L.pjd_blur_taps.argtypes = [C.c_uint32, C.c_double, C.POINTER(C.c_uint32)]
+        L.pjd_blur_index.restype = i32
+        L.pjd_blur_index.argtypes = [C.c_uint32, C.c_int64, C.POINTER(C.c_uint32)]
+        L.pjd_blur_check.restype = i32
+        L.pjd_blur_check.argtypes = [C.POINTER(Blur)]
         L.pjd_resize_pad_check.restype = i32
         L.pjd_resize_pad_check.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(ResizePad)]
         L.pjd_resize_window_check.restype = i32
@@ -602,6 +618,19 @@ class Batch:
             arr[i] = _colour12(COLOUR_IDENTITY if m is None else m, "set_colour")
         self.ctx._check(self.L.pjd_batch_set_colour(self._h, arr), "pjd_batch_set_colour")
 
+    def set_blur(self, blurs):
+        """pjd_batch_set_blur: output i leaves as the separable Gaussian of what the batch would deliver without the call -- blurs[i] =
+        (ksize, sigma), ksize odd and at most BLUR_MAX_TAPS, or None for no blur -- with the taps, the reflect border and the unsigned
+        fixed point include/pjd.h specifies bit for bit (blur_taps, blur_index), in one launch behind the resample or warp and before the
+        normalisation: torchvision's GaussianBlur to within 1 level, not Pillow's.  Once, after set_resize() (and whatever shapes the
+        resample, set_colour() included), before set_normalize() / bind_output() / upload(); not on a batch with set_resize_pad()."""
+        if len(blurs) != self.n_out:
+            raise ValueError("set_blur: one (ksize, sigma) (or None) per picture (per view after set_views)")
+        arr = (Blur * max(self.n_out, 1))()
+        for i, e in enumerate(blurs):
+            arr[i] = Blur(0.0, 0, 0) if e is None else Blur(float(e[1]), int(e[0]), 0)
+        self.ctx._check(self.L.pjd_batch_set_blur(self._h, arr), "pjd_batch_set_blur")
+
     def set_resize_filter(self, filter):
         """pjd_batch_set_resize_filter: RESIZE_ANTIALIAS makes the resize the widened triangle filter include/pjd.h specifies bit for
         bit (torch's antialias=True, Pillow's BILINEAR), RESIZE_BICUBIC the bicubic one (Keys, a = -0.5, widened where an axis shrinks:
@@ -954,6 +983,30 @@ def colour_value(m, rgb):
     if dev_lib().pjd_colour_value(_colour12(m, "colour_value"), (C.c_uint8 * 3)(*[int(v) for v in rgb]), out) != 0:
         raise ValueError(f"colour_value({list(m)}): the map must be finite and within the limits")
     return out[0], out[1], out[2]
+
+
+def blur_taps(ksize, sigma):
+    """pjd_blur_taps (host only): the ksize taps, in 1/65536, of the Gaussian of Batch.set_blur -- symmetric, non-negative, summing to
+    65536 exactly; the table the blur kernel reads."""
+    ksize = int(ksize)
+    q = (C.c_uint32 * max(ksize, 1))()
+    if not 0 < ksize < 2 ** 32 or dev_lib().pjd_blur_taps(ksize, float(sigma), q) != 0:
+        raise ValueError(f"blur_taps({ksize}, {sigma}): ksize is odd and at most {BLUR_MAX_TAPS}, sigma finite and greater than 0")
+    return list(q)
+
+
+def blur_index(n, i):
+    """pjd_blur_index (host only): the sample that index i of an axis of n samples reads under the border rule of Batch.set_blur
+    (torchvision's reflect, folded as often as it takes)."""
+    src = C.c_uint32()
+    if not 0 < int(n) < 2 ** 32 or not -2 ** 63 <= int(i) < 2 ** 63 or dev_lib().pjd_blur_index(int(n), int(i), C.byref(src)) != 0:
+        raise ValueError(f"blur_index({n}, {i}): n is 1..65535")
+    return src.value
+
+
+def blur_check(ksize, sigma, reserved=0):
+    """pjd_blur_check (host only): True where pjd_batch_set_blur would accept the entry (ksize, sigma); (0, 0.0) is no blur."""
+    return dev_lib().pjd_blur_check(C.byref(Blur(float(sigma), int(ksize) & 0xffffffff, int(reserved)))) == 1
 
 
 def colour_check(m):

@@ -114,9 +114,9 @@ def _torch():
 # offsets to bind (None: packed); then what the setters take, each None where its setter is not called -- views, sizes (set_resize), pads
 # with fill (set_resize_pad), orientations, windows, filter (set_resize_filter), normalize = (dtype, scale, bias), pad_value.
 # affines (set_resize_affine, with fill) stands in place of pads, orientations, windows and filter.  colours (set_colour) comes behind
-# all of them and before normalize.
-_Request = collections.namedtuple("_Request", "descs out_format capacity offsets views sizes pads fill orientations windows filter normalize pad_value affines colours",
-                                  defaults=(None,) * 13)
+# all of them and before normalize, blurs (set_blur) behind colours.
+_Request = collections.namedtuple("_Request", "descs out_format capacity offsets views sizes pads fill orientations windows filter normalize pad_value affines colours blurs",
+                                  defaults=(None,) * 14)
 
 
 def _run(ctx, req, device):
@@ -141,6 +141,8 @@ def _run(ctx, req, device):
                 b.set_resize_filter(req.filter)
             if req.colours is not None:
                 b.set_colour(req.colours)
+            if req.blurs is not None:
+                b.set_blur(req.blurs)
         if req.normalize is not None:
             b.set_normalize(*req.normalize)
             if req.pads is not None and req.pad_value is not None:
@@ -650,11 +652,18 @@ def plan_views(descs, views, size, prescale=True, crops=None, flips=None, resize
 
 
 def _resize_request(who, descs, size, out_format, prescale, antialias, crops, flips, resize_short, interpolation, orientations, libjpeg,
-                    letterbox, fill, draft, views, affines=None, colours=None):
+                    letterbox, fill, draft, views, affines=None, colours=None, blurs=None):
     """The _Request of one of the two resizing helpers (`who`): its geometry (_resize_request_geometry), and colours= checked against it
-    -- one map or None per output, none on a grey batch -- before anything is created."""
+    -- one map or None per output, none on a grey batch -- before anything is created; blurs= likewise -- one (ksize, sigma) or None per
+    output, none beside letterbox=."""
     req = _resize_request_geometry(who, descs, size, out_format, prescale, antialias, crops, flips, resize_short, interpolation, orientations, libjpeg,
                                    letterbox, fill, draft, views, affines)
+    if blurs is not None:
+        if letterbox is not None:
+            raise ValueError(f"{who}: blurs= excludes letterbox= (the border is not content; Batch.set_blur)")
+        if len(blurs) != len(req.sizes):
+            raise ValueError(f"{who}: blurs= has one (ksize, sigma) (or None) per output: {len(req.sizes)}, not {len(blurs)}")
+        req = req._replace(blurs=[None if e is None else (int(e[0]), float(e[1])) for e in blurs])
     if colours is None:
         return req
     if out_format == pjd_amd.OUT_GRAY8:
@@ -699,7 +708,7 @@ def _resize_request_geometry(who, descs, size, out_format, prescale, antialias, 
 
 def decode_resized_batch_tensor(ctx, descs, size, prescale=True, device=None, antialias=False, crops=None, flips=None, resize_short=None,
                                 interpolation="bilinear", orientations=None, libjpeg=False, letterbox=None, fill=(0, 0, 0), gray=False, draft=False,
-                                views=None, affines=None, colours=None):
+                                views=None, affines=None, colours=None, blurs=None):
     """Pictures of ANY sizes -> (uint8 tensor [N, 3, H, W], statuses), size = (H, W): every picture is resampled to H x W inside
     the decode (the bilinear filter of include/pjd.h, pjd_batch_set_resize) and lands at offset i * 3 * H * W of one buffer, so
     the result is one contiguous NCHW tensor with no copy after the decode, complete on return and readable on any torch stream
@@ -754,9 +763,14 @@ def decode_resized_batch_tensor(ctx, descs, size, prescale=True, device=None, an
     colours=[m | None, ...]: output i's resampled 8-bit triple goes through the 3 x 4 colour map m (twelve values, row-major, the last
     column in 8-bit levels: colour_matrix makes them; None: the identity) inside the same launch, in the fixed point of include/pjd.h
     (Batch.set_colour): ColorJitter, RandomGrayscale, BGR.  One entry per OUTPUT (per view with views=).  It composes with every keyword
-    above; a letterbox border keeps its `fill`, the `fill` of affines= passes through the map.  With gray=True it raises ValueError."""
+    above; a letterbox border keeps its `fill`, the `fill` of affines= passes through the map.  With gray=True it raises ValueError.
+    blurs=[(ksize, sigma) | None, ...]: output i leaves as the separable Gaussian of what it would be without the keyword -- ksize odd, up
+    to 63, the taps, the reflect border and the fixed point of include/pjd.h (Batch.set_blur; one more launch behind the resample):
+    torchvision's GaussianBlur on the uint8 tensor to within 1 level, NOT Pillow's ImageFilter.GaussianBlur, which is a box approximation.
+    One entry per OUTPUT (per view with views=); None: that output is not blurred.  It comes behind colours= and composes with every
+    keyword above but letterbox=, beside which it raises ValueError, as it does for a wrong count."""
     req = _resize_request("decode_resized_batch_tensor", descs, size, pjd_amd.OUT_GRAY8 if gray else pjd_amd.OUT_RGB8_PLANAR, prescale, antialias,
-                          crops, flips, resize_short, interpolation, orientations, libjpeg, letterbox, fill, draft, views, affines, colours)
+                          crops, flips, resize_short, interpolation, orientations, libjpeg, letterbox, fill, draft, views, affines, colours, blurs)
     buf, _, st = _run(ctx, req, device)
     return buf.view(len(req.sizes), 1 if gray else 3, *req.sizes[0]), st
 
@@ -776,7 +790,7 @@ def normalize_constants(mean, std):
 def decode_normalized_batch_tensor(ctx, descs, size, mean, std, dtype=None, channels_last=False, prescale=True, device=None,
                                    antialias=False, crops=None, flips=None, resize_short=None, interpolation="bilinear", orientations=None,
                                    libjpeg=False, letterbox=None, fill=(0, 0, 0), pad_value=None, gray=False, draft=False, views=None, affines=None,
-                                   colours=None):
+                                   colours=None, blurs=None):
     """Pictures of ANY sizes -> (tensor of `dtype` [N, 3, H, W], statuses), size = (H, W); dtype torch.float16 (the default),
     torch.bfloat16 or torch.float32.  As decode_resized_batch_tensor, and every sample v of channel c leaves the same launch as
     fma(v, scale[c], bias[c]) with the constants of normalize_constants(mean, std), converted once to `dtype` (include/pjd.h,
@@ -799,7 +813,9 @@ def decode_normalized_batch_tensor(ctx, descs, size, mean, std, dtype=None, chan
     affines, with fill: as in decode_resized_batch_tensor; the fill is a sample like any other and is normalised with the rest (there is
     no pad_value beside it: that needs a letterbox).
     colours: as in decode_resized_batch_tensor; the map comes BEFORE the normalisation, which reads its 8-bit result -- the order of
-    ColorJitter, RandomGrayscale, ToTensor, Normalize."""
+    ColorJitter, RandomGrayscale, ToTensor, Normalize.
+    blurs: as in decode_resized_batch_tensor; the normalisation reads the blurred byte -- ColorJitter, RandomGrayscale, GaussianBlur,
+    ToTensor, Normalize, the order of the SimCLR family."""
     _gray_layout(gray, not channels_last)
     if gray:
         mean, std = _gray3(mean, "mean"), _gray3(std, "std")
@@ -809,7 +825,7 @@ def decode_normalized_batch_tensor(ctx, descs, size, mean, std, dtype=None, chan
     if pad_value is not None and letterbox is None:
         raise ValueError("pad_value needs letterbox: without it there is no border")
     req = _resize_request("decode_normalized_batch_tensor", descs, size, pjd_amd.OUT_GRAY8 if gray else pjd_amd.OUT_RGB8 if channels_last else pjd_amd.OUT_RGB8_PLANAR,
-                          prescale, antialias, crops, flips, resize_short, interpolation, orientations, libjpeg, letterbox, fill, draft, views, affines, colours)
+                          prescale, antialias, crops, flips, resize_short, interpolation, orientations, libjpeg, letterbox, fill, draft, views, affines, colours, blurs)
     torch = _torch()
     dtype = torch.float16 if dtype is None else dtype
     dts = {torch.float16: (pjd_amd.DT_F16, 2), torch.bfloat16: (pjd_amd.DT_BF16, 2), torch.float32: (pjd_amd.DT_F32, 4)}
